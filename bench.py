@@ -13,12 +13,16 @@ resident in HBM, followed by the gather of the landmark records to rank 0.  Para
 forest) are loaded on rank 0 and broadcast over RCCL before the timed region.  No data-path
 collective: meshes are independent (weak scaling).
 
-The JSON line also carries
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line (`value`,
+`ms_per_step`, ...).  --dump-outputs DIR then writes the landmark records of the last timed step as
+DIR/<field>.npy (float64).  --full adds everything else, as one line:
   roofline      for the kernel with the largest share of device time (HIP events on the engine's
                 stream around every launch of the timed steps), algorithmic flops/bytes per launch
                 (DESIGN.md "Kernels") / average launch duration vs the gfx950 peak;
   cpu_baseline  the oracle (NumPy/SciPy restatement of the reference, oracle/) on the same synthetic
-                meshes, one thread, rank 0, N=1 only, a bounded sample.
+                meshes, one thread, rank 0, N=1 only, a bounded sample;
+  extra legs    (N=1) f32 / f32x / f16 UNet, the other hull mode, one humerus, steady state, one lane,
+                streamed batches from host memory and from STL bytes.
 """
 import argparse
 import json
@@ -322,7 +326,13 @@ def main():
     ap.add_argument("--hull", choices=["auto", "host", "device"], default="auto", help="where the convex hull of the OBB stage runs (sh_set_hull_mode); "
                     "auto = host quickhull where the rank has enough usable hardware threads (16 alone on its host, 48 per rank otherwise), else the device hull")
     ap.add_argument("--check-gather", action="store_true", help="after the timed region rank 0 compares the records the last gather delivered for its own shard with a run of its own engine")
+    ap.add_argument("--full", action="store_true", help="besides the headline: CPU baseline, the extra legs (N=1), per-kernel HIP-event times, roofline and "
+                    "geometry tables (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps (rank 0) write the landmark records of the last timed step "
+                    "as DIR/<field>.npy, float64, humeri along axis 0 (every rank's at N > 1); at most 64 MB in all (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torch.distributed.run: this process becomes the launcher of its own N ranks and never initialises the GPU
@@ -351,7 +361,7 @@ def main():
 
     weights = unet_spec.make_teacher_weights()
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # before anything touches the GPU: the pooled leg starts worker processes
         cpu = cpu_baseline(verts, faces, synth.similarity_transforms(B, verts, seed=1234), weights, args.cpu_meshes, args.cpu_pool)
     # Lanes: independent engine contexts (own stream, own scratch) on this GPU.  Step s runs on lane s % lanes, so the launch-
@@ -438,11 +448,13 @@ def main():
         elif host_batch is not None:
             e.upload_packed(host_batch)
 
-    leg_info = {"error_status": 0, "records": 0}
+    leg_info = {"error_status": 0, "records": 0, "last": None}
 
-    def run_leg(leg_engs, unet, steps, warmup, pipelined, stream=None):
+    def run_leg(leg_engs, unet, steps, warmup, pipelined, stream=None, timing=2):
         """`warmup` untimed steps, then exactly `steps` timed steps of SH_STAGE_ALL on `leg_engs` (step s on lane s % len),
         bracketed by barrier + synchronize on both sides.  -> (seconds: max over ranks, per-layer HIP-event times of the region).
+        timing = 0: no HIP events in the region (the per-layer times are empty).  leg_info["last"]: the records of the last
+        timed step as the lane handed them over (a view of its page-locked buffer; None when they went to a send buffer).
         `stream` (make_stream): step s works on batch s % n of the stream, handed over through the lane's staging side -- staged
         right behind the lane's previous submit (copies, device-side checks / STL merge and hulls run beside that step), committed
         when that step has been collected; every stage, commit, submit and collect of the K steps lies inside the timed region."""
@@ -468,7 +480,7 @@ def main():
         # events around all ~150 launches of a step stretch the step by ~0.7 ms.  The other kernels are timed in one extra
         # pass after the region (level 1).
         for e in leg_engs:
-            e.enable_timing(2)
+            e.enable_timing(timing)
             e.reset_timers()
         # Streaming schedule: inside the timed region the hulls of step k+1 are computed by host threads while the device
         # works on step k.  Nothing is carried in from the warmup (discard) and nothing is prepared for a step K+1 (overlap
@@ -476,7 +488,7 @@ def main():
         for e in leg_engs:
             e.discard_prepared()
             e.set_overlap(overlap and not stream)      # (a streamed batch runs once: its hulls are prepared by the staging side)
-        leg_info.update(error_status=0, records=0)
+        leg_info.update(error_status=0, records=0, last=None)
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -492,6 +504,7 @@ def main():
 
             def finish(k, e):
                 rec = e.collect()
+                leg_info["last"] = rec
                 if rec is not None:
                     leg_info["error_status"] += int((rec["status"] != 0).sum())
                     leg_info["records"] += len(rec)
@@ -540,7 +553,7 @@ def main():
                     e.collect()
                     dist.gather(lm_t, gather_list, dst=0)      # landmark records of every rank to rank 0 (device to device)
                 else:
-                    e.run(_lib.STAGE_ALL, fetch="view")        # records land in the engine's page-locked buffer
+                    leg_info["last"] = e.run(_lib.STAGE_ALL, fetch="view")        # records land in the engine's page-locked buffer
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
@@ -562,13 +575,15 @@ def main():
         return el, region, ul_
 
     pipelined = not args.no_pipeline
-    el, region_times, ul = run_leg(engs, args.unet, args.steps, args.warmup, pipelined, stream)
+    el, region_times, ul = run_leg(engs, args.unet, args.steps, args.warmup, pipelined, stream, timing=2 if args.full else 0)
+    last = None if leg_info["last"] is None else leg_info["last"].copy()      # (before any later run reuses the lane's buffer)
 
-    eng.enable_timing(1)
-    eng.run(_lib.STAGE_ALL, fetch=False)      # profiling pass outside the timed region, one lane alone: every kernel between events
-    extra_times = {name: eng.kernel_time_ms(name) for name in GEOM_KERNELS + ["k_synth_batch", "k_pack_w_bf16"]}
-    alone_times = {name: eng.kernel_time_ms(name) for name in ul}
-    eng.enable_timing(0)
+    if args.full:
+        eng.enable_timing(1)
+        eng.run(_lib.STAGE_ALL, fetch=False)      # profiling pass outside the timed region, one lane alone: every kernel between events
+        extra_times = {name: eng.kernel_time_ms(name) for name in GEOM_KERNELS + ["k_synth_batch", "k_pack_w_bf16"]}
+        alone_times = {name: eng.kernel_time_ms(name) for name in ul}
+        eng.enable_timing(0)
 
     gather_check = None
     if use_dist and rank == 0:      # what rank 0 holds after the last gather: every rank's records, in rank order
@@ -577,15 +592,20 @@ def main():
         if args.check_gather:
             own = eng.run(_lib.STAGE_ALL)
             gather_check = {"records": int(len(lm)), "own_shard_equal_to_local_run": bool(lm[:B].tobytes() == own.tobytes())}
-    else:
+        last = lm
+    elif args.full:
         lm = eng.run(_lib.STAGE_ALL)
-    n_bad = int((lm["status"] != 0).sum())
+    else:
+        lm = last      # the last timed step's records (None on the other ranks of a process group: they print nothing)
+    n_bad = None if lm is None else int((lm["status"] != 0).sum())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     # Extra legs, N=1 only (the driver's SCALE runs keep to the headline leg): the tolerance-conformant configuration -- f32
     # UNet, landmarks within 1e-4 mm of the oracle (tests/test_gpu_end_to_end.py) -- timed by the same protocol in the same
     # invocation, and the headline configuration on ONE lane (what a caller without the two-context schedule gets).
     extra = {}
-    if world == 1 and not use_dist and not args.no_extra_legs and host_batch is None:
+    if world == 1 and not use_dist and args.full and not args.no_extra_legs and host_batch is None:
         k32 = max(3, min(args.steps, 10))
         el32, reg32, ul32 = run_leg(engs, "f32", k32, 1, pipelined)
         c32 = unet_couts(unet_spec.BASE, unet_spec.DEPTH)
@@ -724,137 +744,138 @@ def main():
                 del strm
 
     if rank == 0:
-        ul_cout = unet_couts(unet_spec.BASE, unet_spec.DEPTH)
-        gb = geom_bytes(B, V, F)
-        times = {}
-        host_ms = {k: (lambda t: t[0] * t[1] / args.steps)(region_times[k]) for k in ("host.verts_d2h", "host.hull")}
-        for name in list(ul) + ["unet.pool"]:                 # averaged over the launches of the timed steps
-            ms, n = region_times[name]
-            if n:
-                times[name] = (ms, n)
-        for name, (ms, n) in extra_times.items():              # one pass: scaled to the same per-step accounting
-            if n:
-                times[name] = (ms, n * args.steps)
-        total_dev = sum(ms * n for ms, n in times.values())
-        # group the launches by kernel symbol (what rocprofv3 --stats reports)
-        sym, sym_of = {}, {}
-        for name, (ms, n) in times.items():
-            key = sym_key(name, args.unet, ul_cout[name]) if (name in ul and name in ul_cout) else name
-            sym_of[name] = key
-            g = sym.setdefault(key, dict(ms=0.0, n=0, flops=0.0, bytes=0.0))
-            g["ms"] += ms * n
-            g["n"] += n
-            if name in ul:
-                g["flops"] += ul[name][0] * B * n
-                g["bytes"] += ul[name][1] * B * n
-            else:
-                g["bytes"] += gb.get(name, (0, None))[0] * (n / max(1, extra_times.get(name, (0, 1))[1]))      # (per-step bytes x steps)
-        dom = max(sym, key=lambda k: sym[k]["ms"]) if sym else None
-        roof = None
-        if dom:
-            g = sym[dom]
-            common = dict(kernel=dom, avg_ms=round(g["ms"] / g["n"], 4), launches=g["n"], share_of_device_time=round(g["ms"] / total_dev, 3), traffic=None)
-            if g["flops"] > 0:
-                peak = mfma_peak_tf(args.unet)
-                ach = g["flops"] / (g["ms"] * 1e-3) / 1e12
-                roof = dict(bound="mfma", achieved=round(ach, 2), peak=peak, unit="TFLOP/s", frac=round(ach / peak, 4),
-                            algorithmic_gbytes_per_launch=round(g["bytes"] / g["n"] / 1e9, 4), **common)
-                if lanes > 1:
-                    # the same launches with one lane alone on the device (profiling pass after the timed region): what the
-                    # kernel does when no other stream shares the CUs with it
-                    members = [nm for nm in ul if nm in times and sym_of.get(nm) == dom]
-                    a_ms = sum(alone_times[nm][0] * alone_times[nm][1] for nm in members)
-                    a_fl = sum(ul[nm][0] * B * alone_times[nm][1] for nm in members)
-                    if a_ms > 0:
-                        roof["one_lane_alone"] = dict(avg_ms=round(a_ms / sum(alone_times[nm][1] for nm in members), 4),
-                                                      achieved=round(a_fl / (a_ms * 1e-3) / 1e12, 2), frac=round(a_fl / (a_ms * 1e-3) / 1e12 / peak, 4),
-                                                      note="HIP events around every launch of ONE profiling pass on a grid of all 256 CUs; an event pair spans the launch's "
-                                                           "dispatch as well (~10-20 us of a ~0.3 ms launch), so rocprofv3's kernel-trace duration of the same launches "
-                                                           "(profiles/*_kernel_stats_*_one_lane.csv) reads 5-8 % shorter")
-                        for rnd in ROUNDS:      # the same symbol in the committed one-lane kernel trace
-                            csvp = os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats_b{B}_{args.unet}_one_lane.csv")
-                            if os.path.exists(csvp):
-                                import csv
-                                want = rocprof_name(dom).replace("sh::", "")
-                                for row in csv.DictReader(open(csvp)):
-                                    if want in row["Name"]:
-                                        r_ms = float(row["AverageNs"]) * 1e-6
-                                        roof["one_lane_alone"].update(rocprof_avg_ms=round(r_ms, 4), rocprof_frac=round(a_fl / sum(alone_times[nm][1] for nm in members) / (r_ms * 1e-3) / 1e12 / peak, 4),
-                                                                      rocprof_source=os.path.relpath(csvp, ROOT))
-                                        break
-                                break
-            else:
-                ach = g["bytes"] / (g["ms"] * 1e-3) / 1e9
-                roof = dict(bound="hbm", achieved=round(ach, 2), peak=PEAK_HBM_GBS, unit="GB/s", frac=round(ach / PEAK_HBM_GBS, 4), **common)
-        # HBM traffic and MFMA-busy fraction of the dominant kernel from the committed PMC profiles of this same command
-        # (rocprofv3 cannot run inside the bench); null when no profile matches the configuration
-        if roof:
+        if args.full:      # per-kernel figures: HIP events of the timed region + the one-lane profiling pass
+            ul_cout = unet_couts(unet_spec.BASE, unet_spec.DEPTH)
+            gb = geom_bytes(B, V, F)
+            times = {}
+            host_ms = {k: (lambda t: t[0] * t[1] / args.steps)(region_times[k]) for k in ("host.verts_d2h", "host.hull")}
+            for name in list(ul) + ["unet.pool"]:                 # averaged over the launches of the timed steps
+                ms, n = region_times[name]
+                if n:
+                    times[name] = (ms, n)
+            for name, (ms, n) in extra_times.items():              # one pass: scaled to the same per-step accounting
+                if n:
+                    times[name] = (ms, n * args.steps)
+            total_dev = sum(ms * n for ms, n in times.values())
+            # group the launches by kernel symbol (what rocprofv3 --stats reports)
+            sym, sym_of = {}, {}
+            for name, (ms, n) in times.items():
+                key = sym_key(name, args.unet, ul_cout[name]) if (name in ul and name in ul_cout) else name
+                sym_of[name] = key
+                g = sym.setdefault(key, dict(ms=0.0, n=0, flops=0.0, bytes=0.0))
+                g["ms"] += ms * n
+                g["n"] += n
+                if name in ul:
+                    g["flops"] += ul[name][0] * B * n
+                    g["bytes"] += ul[name][1] * B * n
+                else:
+                    g["bytes"] += gb.get(name, (0, None))[0] * (n / max(1, extra_times.get(name, (0, 1))[1]))      # (per-step bytes x steps)
+            dom = max(sym, key=lambda k: sym[k]["ms"]) if sym else None
+            roof = None
+            if dom:
+                g = sym[dom]
+                common = dict(kernel=dom, avg_ms=round(g["ms"] / g["n"], 4), launches=g["n"], share_of_device_time=round(g["ms"] / total_dev, 3), traffic=None)
+                if g["flops"] > 0:
+                    peak = mfma_peak_tf(args.unet)
+                    ach = g["flops"] / (g["ms"] * 1e-3) / 1e12
+                    roof = dict(bound="mfma", achieved=round(ach, 2), peak=peak, unit="TFLOP/s", frac=round(ach / peak, 4),
+                                algorithmic_gbytes_per_launch=round(g["bytes"] / g["n"] / 1e9, 4), **common)
+                    if lanes > 1:
+                        # the same launches with one lane alone on the device (profiling pass after the timed region): what the
+                        # kernel does when no other stream shares the CUs with it
+                        members = [nm for nm in ul if nm in times and sym_of.get(nm) == dom]
+                        a_ms = sum(alone_times[nm][0] * alone_times[nm][1] for nm in members)
+                        a_fl = sum(ul[nm][0] * B * alone_times[nm][1] for nm in members)
+                        if a_ms > 0:
+                            roof["one_lane_alone"] = dict(avg_ms=round(a_ms / sum(alone_times[nm][1] for nm in members), 4),
+                                                          achieved=round(a_fl / (a_ms * 1e-3) / 1e12, 2), frac=round(a_fl / (a_ms * 1e-3) / 1e12 / peak, 4),
+                                                          note="HIP events around every launch of ONE profiling pass on a grid of all 256 CUs; an event pair spans the launch's "
+                                                               "dispatch as well (~10-20 us of a ~0.3 ms launch), so rocprofv3's kernel-trace duration of the same launches "
+                                                               "(profiles/*_kernel_stats_*_one_lane.csv) reads 5-8 % shorter")
+                            for rnd in ROUNDS:      # the same symbol in the committed one-lane kernel trace
+                                csvp = os.path.join(ROOT, "profiles", f"{rnd}_kernel_stats_b{B}_{args.unet}_one_lane.csv")
+                                if os.path.exists(csvp):
+                                    import csv
+                                    want = rocprof_name(dom).replace("sh::", "")
+                                    for row in csv.DictReader(open(csvp)):
+                                        if want in row["Name"]:
+                                            r_ms = float(row["AverageNs"]) * 1e-6
+                                            roof["one_lane_alone"].update(rocprof_avg_ms=round(r_ms, 4), rocprof_frac=round(a_fl / sum(alone_times[nm][1] for nm in members) / (r_ms * 1e-3) / 1e12 / peak, 4),
+                                                                          rocprof_source=os.path.relpath(csvp, ROOT))
+                                            break
+                                    break
+                else:
+                    ach = g["bytes"] / (g["ms"] * 1e-3) / 1e9
+                    roof = dict(bound="hbm", achieved=round(ach, 2), peak=PEAK_HBM_GBS, unit="GB/s", frac=round(ach / PEAK_HBM_GBS, 4), **common)
+            # HBM traffic and MFMA-busy fraction of the dominant kernel from the committed PMC profiles of this same command
+            # (rocprofv3 cannot run inside the bench); null when no profile matches the configuration
+            if roof:
+                for rnd in ROUNDS:
+                    pmc_path = os.path.join(ROOT, "profiles", f"{rnd}_pmc_traffic_b{B}_{args.unet}.json")
+                    if os.path.exists(pmc_path):
+                        pk = json.load(open(pmc_path))["kernels"]
+                        key = rocprof_name(dom)
+                        if key in pk:
+                            roof["traffic"] = pk[key]["hbm_bytes_per_launch"]
+                            roof["traffic_source"] = os.path.relpath(pmc_path, ROOT)
+                            break
+                for rnd in ROUNDS:
+                    sq_path = os.path.join(ROOT, "profiles", f"{rnd}_pmc_sq_b{B}_{args.unet}.json")
+                    if os.path.exists(sq_path):
+                        pk = json.load(open(sq_path))["kernels"]
+                        key = rocprof_name(dom)
+                        if key in pk and "mfma_busy_frac" in pk[key]:
+                            roof["mfma_busy_frac"] = pk[key]["mfma_busy_frac"]
+                            roof["mfma_busy_source"] = os.path.relpath(sq_path, ROOT)
+                            break
+            # Level 0 of the network (the three fused full-resolution kernels): algorithmic flops and bytes per launch, time inside the timed
+            # region, and the fraction of their COMBINED roofline -- the larger of flops / MFMA peak and bytes / HBM peak is the time the
+            # launch cannot beat (these kernels sit furthest below any roofline)
+            level0 = None
+            if args.unet in ("bf16", "f16") and all(k in times for k in ("unet.enc0b", "unet.dec0a", "unet.dec0b")) and "unet.up0" not in times and "unet.enc0a" not in times:
+                HW = 512 * 512
+                spec = {"unet.enc0b": ("enc0a + enc0b + 2x2 pool", ul["unet.enc0a"][0] + ul["unet.enc0b"][0], HW * (4 + 2 * 32 + 2 * 32 // 4)),
+                        "unet.dec0a": ("up0 + dec0a", ul["unet.up0"][0] + ul["unet.dec0a"][0], HW * (2 * 32 + 2 * 64 // 4 + 2 * 32)),
+                        "unet.dec0b": ("dec0b + head", ul["unet.dec0b"][0] + ul["unet.head"][0], HW * (2 * 32 + 4))}
+                level0 = {"kernels": {}}
+                l0_ms = l0_floor = 0.0
+                for nm, (what, fl, by) in spec.items():
+                    ms = times[nm][0]
+                    t_mfma, t_hbm = fl * B / (PEAK_MFMA_BF16_TF * 1e12) * 1e3, by * B / (PEAK_HBM_GBS * 1e9) * 1e3
+                    level0["kernels"][sym_of.get(nm, nm)] = {"layers": what, "gflop_per_launch": round(fl * B / 1e9, 1), "gbytes_per_launch": round(by * B / 1e9, 3), "avg_ms": round(ms, 4),
+                                                             "frac_of_mfma_peak": round(t_mfma / ms, 3), "frac_of_hbm_peak": round(t_hbm / ms, 3),
+                                                             "frac_of_combined_roofline": round(max(t_mfma, t_hbm) / ms, 3)}
+                    l0_ms += ms
+                    l0_floor += max(t_mfma, t_hbm)
+                level0.update(ms_per_pass=round(l0_ms, 3), frac_of_combined_roofline=round(l0_floor / l0_ms, 3),
+                              share_of_unet_ms=round(l0_ms / sum(times[k][0] for k in times if k.startswith("unet.")), 3))
+            unet_ms = sum(times[k][0] for k in times if k.startswith("unet."))
+            unet_tf = sum(v[0] for v in ul.values()) * B / (unet_ms * 1e-3) / 1e12 if unet_ms else None
+            top = sorted(((k, round(v["ms"] / args.steps, 3)) for k, v in sym.items()), key=lambda kv: -kv[1])[:10]
+            # Per-kernel table of the geometry stage, per STEP: every launch of a kernel name in one step (the four plane sets go
+            # through k_slice_emit / k_slice_link, the large-capacity instantiations have names of their own) -> time per step,
+            # this implementation's algorithmic bytes for exactly those launches, SURVEY 8(d)'s bytes where it names them, and the
+            # memory-side bytes rocprofv3 counted for the same kernel (profiles/, null without a matching profile).
+            pmc_geom = {}
             for rnd in ROUNDS:
-                pmc_path = os.path.join(ROOT, "profiles", f"{rnd}_pmc_traffic_b{B}_{args.unet}.json")
-                if os.path.exists(pmc_path):
-                    pk = json.load(open(pmc_path))["kernels"]
-                    key = rocprof_name(dom)
-                    if key in pk:
-                        roof["traffic"] = pk[key]["hbm_bytes_per_launch"]
-                        roof["traffic_source"] = os.path.relpath(pmc_path, ROOT)
-                        break
-            for rnd in ROUNDS:
-                sq_path = os.path.join(ROOT, "profiles", f"{rnd}_pmc_sq_b{B}_{args.unet}.json")
-                if os.path.exists(sq_path):
-                    pk = json.load(open(sq_path))["kernels"]
-                    key = rocprof_name(dom)
-                    if key in pk and "mfma_busy_frac" in pk[key]:
-                        roof["mfma_busy_frac"] = pk[key]["mfma_busy_frac"]
-                        roof["mfma_busy_source"] = os.path.relpath(sq_path, ROOT)
-                        break
-        # Level 0 of the network (the three fused full-resolution kernels): algorithmic flops and bytes per launch, time inside the timed
-        # region, and the fraction of their COMBINED roofline -- the larger of flops / MFMA peak and bytes / HBM peak is the time the
-        # launch cannot beat (these kernels sit furthest below any roofline)
-        level0 = None
-        if args.unet in ("bf16", "f16") and all(k in times for k in ("unet.enc0b", "unet.dec0a", "unet.dec0b")) and "unet.up0" not in times and "unet.enc0a" not in times:
-            HW = 512 * 512
-            spec = {"unet.enc0b": ("enc0a + enc0b + 2x2 pool", ul["unet.enc0a"][0] + ul["unet.enc0b"][0], HW * (4 + 2 * 32 + 2 * 32 // 4)),
-                    "unet.dec0a": ("up0 + dec0a", ul["unet.up0"][0] + ul["unet.dec0a"][0], HW * (2 * 32 + 2 * 64 // 4 + 2 * 32)),
-                    "unet.dec0b": ("dec0b + head", ul["unet.dec0b"][0] + ul["unet.head"][0], HW * (2 * 32 + 4))}
-            level0 = {"kernels": {}}
-            l0_ms = l0_floor = 0.0
-            for nm, (what, fl, by) in spec.items():
-                ms = times[nm][0]
-                t_mfma, t_hbm = fl * B / (PEAK_MFMA_BF16_TF * 1e12) * 1e3, by * B / (PEAK_HBM_GBS * 1e9) * 1e3
-                level0["kernels"][sym_of.get(nm, nm)] = {"layers": what, "gflop_per_launch": round(fl * B / 1e9, 1), "gbytes_per_launch": round(by * B / 1e9, 3), "avg_ms": round(ms, 4),
-                                                         "frac_of_mfma_peak": round(t_mfma / ms, 3), "frac_of_hbm_peak": round(t_hbm / ms, 3),
-                                                         "frac_of_combined_roofline": round(max(t_mfma, t_hbm) / ms, 3)}
-                l0_ms += ms
-                l0_floor += max(t_mfma, t_hbm)
-            level0.update(ms_per_pass=round(l0_ms, 3), frac_of_combined_roofline=round(l0_floor / l0_ms, 3),
-                          share_of_unet_ms=round(l0_ms / sum(times[k][0] for k in times if k.startswith("unet.")), 3))
-        unet_ms = sum(times[k][0] for k in times if k.startswith("unet."))
-        unet_tf = sum(v[0] for v in ul.values()) * B / (unet_ms * 1e-3) / 1e12 if unet_ms else None
-        top = sorted(((k, round(v["ms"] / args.steps, 3)) for k, v in sym.items()), key=lambda kv: -kv[1])[:10]
-        # Per-kernel table of the geometry stage, per STEP: every launch of a kernel name in one step (the four plane sets go
-        # through k_slice_emit / k_slice_link, the large-capacity instantiations have names of their own) -> time per step,
-        # this implementation's algorithmic bytes for exactly those launches, SURVEY 8(d)'s bytes where it names them, and the
-        # memory-side bytes rocprofv3 counted for the same kernel (profiles/, null without a matching profile).
-        pmc_geom = {}
-        for rnd in ROUNDS:
-            pth = os.path.join(ROOT, "profiles", f"{rnd}_pmc_traffic_b{B}_{args.unet}.json")
-            if os.path.exists(pth):
-                pmc_geom = json.load(open(pth))["kernels"]
-                break
-        geom_tab = {}
-        for name, (ms, n) in extra_times.items():
-            if n and ms > 0 and name in gb and gb[name][0] > 0:
-                per_step = ms * n
-                gbs = gb[name][0] / (per_step * 1e-3) / 1e9
-                row = {"ms_per_step": round(per_step, 4), "launches_per_step": n, "algorithmic_mb_per_step": round(gb[name][0] / 1e6, 2),
-                       "gb_per_s": round(gbs, 1), "frac_of_hbm_peak": round(gbs / PEAK_HBM_GBS, 4)}
-                if gb[name][1]:
-                    row["survey_mb_per_step"] = round(gb[name][1] / 1e6, 2)
-                    row["frac_of_hbm_peak_survey_bytes"] = round(gb[name][1] / (per_step * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)
-                pk = pmc_geom.get("sh::" + name)
-                row["pmc_mb_per_step"] = round(pk["hbm_bytes_per_launch"] * pk.get("launches_per_step", n) / 1e6, 2) if pk and "hbm_bytes_per_launch" in pk else None
-                geom_tab[name] = row
-        geom_ms = sum(ms * n for name, (ms, n) in extra_times.items() if n and not name.startswith("unet.") and name not in ("k_synth_batch", "k_pack_w_bf16"))
+                pth = os.path.join(ROOT, "profiles", f"{rnd}_pmc_traffic_b{B}_{args.unet}.json")
+                if os.path.exists(pth):
+                    pmc_geom = json.load(open(pth))["kernels"]
+                    break
+            geom_tab = {}
+            for name, (ms, n) in extra_times.items():
+                if n and ms > 0 and name in gb and gb[name][0] > 0:
+                    per_step = ms * n
+                    gbs = gb[name][0] / (per_step * 1e-3) / 1e9
+                    row = {"ms_per_step": round(per_step, 4), "launches_per_step": n, "algorithmic_mb_per_step": round(gb[name][0] / 1e6, 2),
+                           "gb_per_s": round(gbs, 1), "frac_of_hbm_peak": round(gbs / PEAK_HBM_GBS, 4)}
+                    if gb[name][1]:
+                        row["survey_mb_per_step"] = round(gb[name][1] / 1e6, 2)
+                        row["frac_of_hbm_peak_survey_bytes"] = round(gb[name][1] / (per_step * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)
+                    pk = pmc_geom.get("sh::" + name)
+                    row["pmc_mb_per_step"] = round(pk["hbm_bytes_per_launch"] * pk.get("launches_per_step", n) / 1e6, 2) if pk and "hbm_bytes_per_launch" in pk else None
+                    geom_tab[name] = row
+            geom_ms = sum(ms * n for name, (ms, n) in extra_times.items() if n and not name.startswith("unet.") and name not in ("k_synth_batch", "k_pack_w_bf16"))
         value = world * B * args.steps / el
         out = {"metric": "humerus meshes/s end-to-end (all 4 landmarks)", "value": round(value, 3), "unit": "meshes/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * el / args.steps, 3), "higher_is_better": True,
@@ -868,18 +889,20 @@ def main():
                           "records": {"format": "packed (sh_set_record_rows)" if args.record_rows else "full sh_landmarks", "anp_rows": args.record_rows or 4096, "bytes_per_record": REC.itemsize,
                                       "bytes_per_step_to_rank0": world * B * REC.itemsize, "humeri_with_more_points_than_rows": int((lm["n_anp"] > (args.record_rows or 4096)).sum())},
                           "meshes_with_error_status": n_bad},
-               "parity": PARITY_NOTE[args.unet],
-               "roofline": roof, "cpu_baseline": cpu}
-        out.update(extra)
-        if level0 is not None:
-            out["level0"] = level0
+               "parity": PARITY_NOTE[args.unet]}
+        if args.full:
+            out.update({"roofline": roof, "cpu_baseline": cpu})
+            out.update(extra)
+            if level0 is not None:
+                out["level0"] = level0
         if gather_check is not None:
             out["gather_check"] = gather_check
-        out.update({"unet_tflops": None if unet_tf is None else round(unet_tf, 2), "device_ms_per_step_top": top,
-                    "device_ms_per_step_total": round(total_dev / args.steps, 3), "host_ms_per_step": {k: round(v, 3) for k, v in host_ms.items()},
-                    "geometry_ms_per_step_one_lane": round(geom_ms, 3),
-                    "geometry_launches_per_step": int(sum(n for name, (ms, n) in extra_times.items() if n and not name.startswith("unet.") and name not in ("k_synth_batch", "k_pack_w_bf16"))),
-                    "geometry_kernels": geom_tab})
+        if args.full:
+            out.update({"unet_tflops": None if unet_tf is None else round(unet_tf, 2), "device_ms_per_step_top": top,
+                        "device_ms_per_step_total": round(total_dev / args.steps, 3), "host_ms_per_step": {k: round(v, 3) for k, v in host_ms.items()},
+                        "geometry_ms_per_step_one_lane": round(geom_ms, 3),
+                        "geometry_launches_per_step": int(sum(n for name, (ms, n) in extra_times.items() if n and not name.startswith("unet.") and name not in ("k_synth_batch", "k_pack_w_bf16"))),
+                        "geometry_kernels": geom_tab})
         print(json.dumps(out))
     for e in engs:
         e.close()
@@ -953,6 +976,32 @@ def single_humerus_leg(device, weights, verts, faces, reps=10):
             "facade_readme_flow_ms": round(med(fw), 3), "facade_readme_flow_ms_min": round(min(fw), 3),
             "facade_flow": "Humerus(stl) -> apply_csys_canal_transepiconylar() -> canal.axis(), trans_epiconylar.axis(), anatomic_neck.points(), bicipital_groove.axis(); file read + parse included",
             "landmarks_checked": int(len(got)), "parity": PARITY_NOTE["f32"]}
+
+
+DUMP_MAX_BYTES = 64_000_000      # --dump-outputs: files in all, .npy headers included
+NPY_HEADER_BYTES = 256           # allowance per file (np.save writes 128 bytes of header for these shapes)
+
+
+def dump_outputs(path, rec, max_bytes=DUMP_MAX_BYTES, seed=1234):
+    """--dump-outputs: landmark records (what a caller of the timed path receives) -> path/<field>.npy, one array per record
+    field, humeri along axis 0, float64 (the int32 fields are exact in it).  When the files would exceed `max_bytes` in all, a
+    fixed seeded sample of humeri (ascending) is written instead and its record indices go to path/humerus_index.npy."""
+    names = rec.dtype.names
+    per = 8 * sum(int(np.prod(rec.dtype.fields[f][0].shape, dtype=np.int64)) for f in names)
+    n = len(rec)
+    os.makedirs(path, exist_ok=True)
+    idx_path = os.path.join(path, "humerus_index.npy")
+    if n * per + NPY_HEADER_BYTES * len(names) <= max_bytes:
+        idx = np.arange(n)
+        if os.path.exists(idx_path):
+            os.remove(idx_path)      # (left by an earlier, sampled dump)
+    else:
+        k = max(1, (max_bytes - NPY_HEADER_BYTES * (len(names) + 1)) // (per + 8))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=min(k, n), replace=False))
+        np.save(idx_path, idx.astype(np.float64))
+    for f in names:
+        np.save(os.path.join(path, f + ".npy"), np.ascontiguousarray(rec[f][idx], dtype=np.float64))
+    return idx
 
 
 def make_stream(kind, verts, faces, B, nbatches, start=0):

@@ -1,5 +1,6 @@
 """bench.py's one-line JSON contract (a short run in a child process): the keys and value types the driver reads, the
-`roofline` and `cpu_baseline` objects, `vs_baseline` null, weak scaling, no mesh with an error status."""
+`roofline` and `cpu_baseline` objects of --full, `vs_baseline` null, weak scaling, no mesh with an error status; a plain run
+(the headline alone) and the records it dumps with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -14,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "8",
-                          "--cpu-meshes", "1", "--cpu-pool", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--cpu-meshes", "1", "--cpu-pool", "0", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                    # ONE JSON line
@@ -72,14 +73,14 @@ def test_rccl_leg_single_rank():
     run of its own engine."""
     env = dict(os.environ, SH_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "8",
-                          "--no-cpu-baseline", "--check-gather"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--no-cpu-baseline", "--check-gather", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["meshes_with_error_status"] == 0
     assert d["gather_check"] == {"records": 8, "own_shard_equal_to_local_run": True}
-    assert "f32_unet" not in d            # extra legs belong to the plain N=1 run
+    assert "f32_unet" not in d            # extra legs belong to the N=1 run without a process group
 
 
 def test_rccl_leg_as_one_of_eight_ranks():
@@ -90,7 +91,7 @@ def test_rccl_leg_as_one_of_eight_ranks():
     env = dict(os.environ, SH_BENCH_FORCE_DIST="1", LOCAL_WORLD_SIZE="8", MASTER_ADDR="127.0.0.1", MASTER_PORT="29578")
     env.pop("SHOULDER_HULL", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1", "--batch", "8",
-                          "--no-cpu-baseline", "--check-gather"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--no-cpu-baseline", "--check-gather", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     assert len([ln for ln in out.stdout.splitlines() if ln.strip()]) == 1, out.stdout[:500]
     d = json.loads(out.stdout)
@@ -100,3 +101,77 @@ def test_rccl_leg_as_one_of_eight_ranks():
         assert d["host_ms_per_step"] == {"host.verts_d2h": 0.0, "host.hull": 0.0}
     assert d["value"] > 0 and d["config"]["meshes_with_error_status"] == 0
     assert d["gather_check"] == {"records": 8, "own_shard_equal_to_local_run": True}
+
+
+def _plain_bench(out_dir, *extra, env=None):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                          "--dump-outputs", str(out_dir), *extra], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def _dumped(out_dir):
+    import numpy as np
+    from shoulder_amd import _lib
+    rec = _lib.record_dtype(2560)
+    return {f: np.load(os.path.join(str(out_dir), f + ".npy")) for f in rec.names}, rec
+
+
+def test_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times the headline steps only and prints the headline keys; --dump-outputs writes the records of
+    its last timed step, one float64 array per record field.  The same run through the process-group code path
+    (SH_BENCH_FORCE_DIST=1: records written to device send buffers and gathered to rank 0) dumps the gathered records: the same
+    arrays."""
+    import numpy as np
+    d = _plain_bench(tmp_path / "a")
+    assert d["metric"].startswith("humerus meshes/s") and d["unit"] == "meshes/s" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and "bf16" in d["dtype"] and d["n_gpus"] == 1
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["config"]["meshes_with_error_status"] == 0
+    assert not {"roofline", "cpu_baseline", "f32_unet", "one_lane", "geometry_kernels"} & set(d)      # (--full only)
+    a, rec = _dumped(tmp_path / "a")
+    for f, v in a.items():
+        assert v.dtype == np.float64 and v.shape == (8,) + rec.fields[f][0].shape, f
+    assert not (tmp_path / "a" / "humerus_index.npy").exists()
+    assert (a["status"] == 0).all() and (a["n_anp"] > 0).all() and np.isfinite(a["canal_axis"]).all()
+    env = dict(os.environ, SH_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29579")
+    dd = _plain_bench(tmp_path / "b", env=env)
+    assert dd["config"]["meshes_with_error_status"] == 0 and "f32_unet" not in dd
+    b, _ = _dumped(tmp_path / "b")
+    for f, v in a.items():
+        assert np.array_equal(v, b[f]), f
+
+
+def test_dump_holds_the_last_timed_step(tmp_path):
+    """--from-host --stream-batches 4: every step works on a batch of its own (warm-up: batch 3, timed steps 0, 1, 2: batches 0,
+    1, 2), so the dump must be batch 2's records -- not a warm-up step's, not an earlier step's.  Checked against an engine of
+    this process that runs each of the four batches (mask-independent landmarks, 1e-9 mm)."""
+    import numpy as np
+    import bench
+    from shoulder_amd import _lib, unet_spec
+    from shoulder_amd.engine import Engine
+    from shoulder_amd.stl import load_stl
+    d = _plain_bench(tmp_path / "s", "--from-host", "--stream-batches", "4")
+    assert d["steps"] == 3 and d["config"]["meshes_with_error_status"] == 0
+    got, _ = _dumped(tmp_path / "s")
+    verts, faces = load_stl(os.path.join(ROOT, "tests", "golden", "bones", "humerus_left.stl"))
+    strm = bench.make_stream("host", verts, faces, 8, 4)
+    e = Engine(0)
+    try:
+        e.load_rfc()
+        e.load_unet(unet_spec.make_teacher_weights(), unet_spec.BASE, unet_spec.DEPTH)
+        e.set_params(unet_dtype=_lib.UNET_BF16)
+        e.set_record_rows(2560)
+        want = []
+        for batch in strm["batches"]:
+            e.upload_packed(batch)
+            want.append(e.run(_lib.STAGE_ALL).copy())
+    finally:
+        e.close()
+    keys = ("obb_transform", "canal_axis", "te_axis", "groove_axis", "csys")
+    dev = [max(float(np.abs(got[k] - w[k]).max()) for k in keys) for w in want]
+    assert dev[2] <= 1e-9, dev
+    assert min(dev[0], dev[1], dev[3]) > 1e-3, dev          # (the other batches' humeri are elsewhere)
+    assert (got["status"] == 0).all() and np.array_equal(got["n_anp"] > 0, np.ones(8, bool))

@@ -16,7 +16,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     acc[n][r["Counter_Name"]] += float(r["Counter_Value"])
     cnt[n][r["Counter_Name"]] += 1
 out = {"_note": "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY "
-                "SQ_INSTS_VALU_MFMA_MOPS_* GRBM_GUI_ACTIVE -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs --lanes 1 "
+                "SQ_INSTS_VALU_MFMA_MOPS_* GRBM_GUI_ACTIVE -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs --lanes 1 "
                 "(one lane: the counters of a dispatch are not mixed with another stream's kernels). Values are per launch. "
                 "mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 * 1024 SIMDs).",
        "config": {"batch": int(sys.argv[2]), "unet": sys.argv[3]}, "kernels": {}}

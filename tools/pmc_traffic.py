@@ -19,7 +19,7 @@ def load(path, counter):
 
 
 f, w = load(sys.argv[1], "FETCH_SIZE"), load(sys.argv[2], "WRITE_SIZE")
-out = {"_note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline`. "
+out = {"_note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline`. "
                 "Counter unit KB. hbm_bytes_per_launch = (2*FETCH_SIZE + WRITE_SIZE)*1024: on gfx950 FETCH_SIZE reports half of the bytes of "
                 "16-B/lane streaming reads (MI355X_MICROARCH.md, HBM). Narrower access patterns (the fp64 geometry kernels) are uncalibrated.",
        "config": {"batch": int(sys.argv[3]), "unet": sys.argv[4]}, "kernels": {}}
