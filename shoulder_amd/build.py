@@ -56,7 +56,7 @@ def _deps(path, seen=None):
 
 def _flags():
     return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-gpu-rdc", "-Wall", "-Wmisleading-indentation",
-            "-Wno-unused-function"] + os.environ.get("SHOULDER_HIPCC_FLAGS", "").split()      # (the variable: experiments only)
+            "-Wno-unused-function"]
 
 
 def _obj(src):

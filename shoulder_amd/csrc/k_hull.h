@@ -265,12 +265,6 @@ k_hull_rounds(const float* __restrict__ kept, const long long* __restrict__ koff
   __syncthreads();
 
   constexpr int RNG = HD_SLOTS / HD_NW;                     // slots a wave scans in R0 (192 = 3 x 64)
-#ifdef SH_HULL_PROF
-  unsigned long long pt0 = __builtin_amdgcn_s_memrealtime(), pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define HD_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); pacc[i] += t_ - pt0; pt0 = t_; } while (0)
-#else
-#define HD_STAMP(i) do { } while (0)
-#endif
   for (int round = 0; round < HD_MAXROUNDS; ++round) {
     // ---- R0: candidates.  Every wave scans its own slot range; counts and the smallest priority meet in LDS
     if (tid == 0) { s_ncand = 0; s_minp = 0xFFFFFFFFu; }
@@ -324,7 +318,6 @@ k_hull_rounds(const float* __restrict__ kept, const long long* __restrict__ koff
     }
     stamp = (unsigned long long)(round + 1) << 26;
     __syncthreads();
-    HD_STAMP(0);
     // ---- R1: visible faces + edge claims; wave w serves candidates w, w + 16, ... (the same wave in every phase).  A candidate
     // that sees at most 21 faces (63 directed edges: the rule, a later round's apex sees ~6) keeps one edge per lane in
     // registers from here to R5; larger ones go through the global scratch.
@@ -416,7 +409,6 @@ k_hull_rounds(const float* __restrict__ kept, const long long* __restrict__ koff
       }
     }
     __syncthreads();
-    HD_STAMP(1);
     if (s_fail) break;
     // ---- R2 + R3: ownership, horizon
     unsigned tv[HD_NJ];
@@ -504,7 +496,6 @@ k_hull_rounds(const float* __restrict__ kept, const long long* __restrict__ koff
       if (lane == 0) { c_nh[ci] = nh; c_ok[ci] = 1; }
     }
     __syncthreads();
-    HD_STAMP(2);
     if (s_fail) break;
     // ---- R4: slots.  Wave 0: offsets of the new faces / of the dead faces per candidate (candidate order: one per lane)
     if (wave == 0) {
@@ -529,7 +520,6 @@ k_hull_rounds(const float* __restrict__ kept, const long long* __restrict__ koff
       if (total_new > HD_NSL) newslot[jn] = sl;
     }
     __syncthreads();
-    HD_STAMP(3);
     // ---- R5: kill, create
 #pragma unroll
     for (int j = 0; j < HD_NJ; ++j) {
@@ -554,7 +544,6 @@ k_hull_rounds(const float* __restrict__ kept, const long long* __restrict__ koff
       }
     }
     __syncthreads();
-    HD_STAMP(4);
     // ---- R6: the points of the dead faces move
     for (int q = tid; q < n; q += HD_THREADS) {
       const int f = s_conf[q];
@@ -582,11 +571,7 @@ k_hull_rounds(const float* __restrict__ kept, const long long* __restrict__ koff
       for (int i = lane; i < nvis; i += 64) s_alive[i < HD_VL ? (int)s_visl[ci][i] : visg[ci * HD_VMAX + i]] = 0;
     }
     nslots = nslots_new; nfree = nfree_mid + total_dead;
-    HD_STAMP(5);
   }
-#ifdef SH_HULL_PROF
-  if (tid == 0 && b == 0) printf("hull prof (100 MHz ticks): R0 %llu R1 %llu R2R3 %llu R4 %llu R5 %llu R6+ %llu rounds %d\n", pacc[0], pacc[1], pacc[2], pacc[3], pacc[4], pacc[5], rounds);
-#endif
   __syncthreads();
   if (s_fail) HD_FAIL(s_fail);
   if (rounds >= HD_MAXROUNDS) HD_FAIL(28);

@@ -395,11 +395,6 @@ obb_candidates_tile(const int Lid, const double* __restrict__ hv, const int* __r
       for (int w = 0; w < NW; ++w) hull2 += g_hull2[w][tid];
       const double lb = 0.5 * fabs(hull2) * (hhi[g0 + tid] - hlo[g0 + tid]);
       if (skip_on && ub != ~0ull && lb * (1.0 - 1e-9) > __longlong_as_double((long long)ub)) g_skip[tid] = 1;
-#if defined(SH_ABL_OBB) && SH_ABL_OBB == 1
-      g_skip[tid] = 0;      // ablation: no pruning
-#elif defined(SH_ABL_OBB) && SH_ABL_OBB == 2
-      g_skip[tid] = 1;      // ablation (wrong results): no rectangle scan at all -> the cost of the sweeps
-#endif
     }
     __syncthreads();
     if constexpr (GLOB) {

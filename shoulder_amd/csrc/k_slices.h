@@ -326,9 +326,6 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     bufA[i] = ((unsigned long long)s.e_lo << 32) | s.e_hi;
   }
   __syncthreads();
-#if defined(SH_ABL_LINK) && SH_ABL_LINK == 1
-  return;
-#endif
   if (n < 3) {
     if (tid == 0) {
       centroids[2 * (size_t)pl] = 0; centroids[2 * (size_t)pl + 1] = 0; areas[pl] = 0; nloops[pl] = 0; ring_n[pl] = 0;
@@ -354,9 +351,6 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     nxt[i] = found;
   }
   __syncthreads();
-#if defined(SH_ABL_LINK) && SH_ABL_LINK == 2
-  return;
-#endif
   // One pointer-jumping pass gives both what the walk needs (round 2; two passes before: labels, then ranks): every node carries,
   // for the stretch of 2^k successors starting at itself, the smallest start key on it and the distance to that key's node.
   // Joining a stretch with the one behind it keeps the smaller key (its own on a tie: a stretch longer than the loop meets
@@ -382,9 +376,6 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     int* tj = ja; ja = jb; jb = tj;
     int* tr = ra; ra = rb; rb = tr;
   }
-#if defined(SH_ABL_LINK) && SH_ABL_LINK == 3
-  return;
-#endif
   // labA[i] = start key of i's loop, ra[i] = forward steps from i to the start node (0: i is a start node)
   for (int i = tid; i < n; i += SH_LINK_THREADS)
     if (ra[i] == 0) {
@@ -442,9 +433,6 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
       if (my_pos[c] >= 0 && my_pos[c] < n) { const Seg sg = sp[i]; seg_start_point(vb, sg.s_lo, sg.s_hi, zpl, &rx[my_pos[c]], &ry[my_pos[c]]); }
   }
   __syncthreads();
-#if defined(SH_ABL_LINK) && SH_ABL_LINK == 4
-  return;
-#endif
   // AABB over every loop vertex (trimesh Path2D.centroid, slice.py:38) by the last wave, while the other three take the loops
   // (all four waves reducing four doubles each through the LDS crossbar, then 64-bit LDS atomics, was a quarter of the kernel).
   // The ordered ring in LDS holds every crossing point once -- min / max do not care about the order; a section with
@@ -481,9 +469,6 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
       }
     }
   }
-#if defined(SH_ABL_LINK) && SH_ABL_LINK == 7
-  return;
-#endif
   __syncthreads();
   // the chosen loop: every lane picks it for itself (at most a handful of broadcast reads) -- one lane choosing it for all,
   // between two barriers and in front of its scalar stores, was a quarter of the kernel
@@ -508,9 +493,6 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     ring_n[pl] = l_len[best];
     if (bad) atomicCAS(&err[b], 0, SH_ERR_GEOMETRY_DEV);
   }
-#if defined(SH_ABL_LINK) && SH_ABL_LINK == 5
-  return;
-#endif
   if (ring) {
     int l = best, o = l_off[l], L = l_len[l];
     bool rev = l_area[l] < 0;           // clockwise loop: traverse backwards from the same start
@@ -614,9 +596,6 @@ __device__ inline void resample_polar_plane(const int pl, int N, int M, const in
     for (; q <= L; ++q) { acc += d[q]; d[q] = acc; }
   }
   __syncthreads();
-#if defined(SH_ABL_RS) && SH_ABL_RS == 2
-  return;
-#endif
   const double dmax = d[L];
   double sx[NS], sy[NS];
 #pragma unroll
@@ -644,14 +623,8 @@ __device__ inline void resample_polar_plane(const int pl, int N, int M, const in
 #pragma unroll
     for (int u = 0; u < NS; ++u) { const int j = tid + u * SH_RS_THREADS; oxy[j] = sx[u]; oxy[M + j] = sy[u]; }
   }
-#if defined(SH_ABL_RS) && SH_ABL_RS == 3
-  return;
-#endif
   const double cx = centroids[2 * (size_t)pl], cy = centroids[2 * (size_t)pl + 1];
   for (int pass = 0; pass < 2; ++pass) {
-#if defined(SH_ABL_RS) && SH_ABL_RS == 4
-    if (pass == 1) return;
-#endif
     if (pass == 0 ? !want_st : !want_cs) continue;
     const double ox = pass ? cx : 0.0, oy = pass ? cy : 0.0;
     double best = 1e300;
@@ -661,13 +634,8 @@ __device__ inline void resample_polar_plane(const int pl, int N, int M, const in
     for (int u = 0; u < NS; ++u) {
       const int j = tid + u * SH_RS_THREADS;
       const double x = sx[u] - ox, y = sy[u] - oy;
-#if defined(SH_ABL_RS) && SH_ABL_RS == 1
-      th[u] = y + x;      // ablation (wrong results): what the kernel costs without its atan2 / sqrt
-      rr[u] = x * x + y * y;
-#else
       th[u] = atan2(y, x);
       rr[u] = sqrt(x * x + y * y);
-#endif
       if (th[u] < best || (th[u] == best && j < bi)) { best = th[u]; bi = j; }
     }
     for (int off = 32; off > 0; off >>= 1) {

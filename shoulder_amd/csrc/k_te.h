@@ -14,64 +14,6 @@ namespace sh {
 #define SH_TE_ROW0 2
 #define SH_TE_NROWS 37          // int((1-.99)*200)=2 .. int((1-.8)*200)=39 (slice.py:157-164)
 
-// Convex hull of a ring by one wave: gift wrapping with a 64-lane tournament per step.  Melkman's deque walk (one lane,
-// ~20 dependent LDS round trips per vertex: ~300 us for a 300-point ring -- the whole kernel was one slice's walk long) gives the
-// strictly convex vertices in counter-clockwise order starting at the hull vertex with the highest ring index; so does this:
-// start at the lowest point (lowest y, then x: extreme, hence on the hull), from the current vertex p take the point q with every
-// other point on the left of p -> q (of collinear candidates the farthest: collinear points are dropped, as Melkman's `<= 0`
-// pops do), until the start comes round again; then rotate.  The two disagree only where an orientation determinant is
-// within rounding of zero; the minimum-area rectangle does not notice (extents move by ~1e-13).
-// xy: n points in LDS; hull: LDS, >= n ints.  Returns the hull size (every lane); hull[(k + *rot) % nh], k = 0.., is Melkman's list.
-__device__ inline int wave_hull_wrap(const double* xy, int n, int* hull, int lane, int* rot) {
-  // lowest point
-  double by = 1e300, bx = 1e300; int bi = 0x7fffffff;
-  for (int i = lane; i < n; i += 64) {
-    const double x = xy[2 * i], y = xy[2 * i + 1];
-    if (y < by || (y == by && (x < bx || (x == bx && i < bi)))) { by = y; bx = x; bi = i; }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const double oy = __shfl_xor(by, off), ox = __shfl_xor(bx, off); const int oi = __shfl_xor(bi, off);
-    if (oy < by || (oy == by && (ox < bx || (ox == bx && oi < bi)))) { by = oy; bx = ox; bi = oi; }
-  }
-  const int p0 = bi;
-  int p = p0, nh = 0;
-  double px = bx, py = by;
-  for (;;) {
-    if (lane == 0) hull[nh] = p;
-    ++nh;
-    if (nh > n) break;                               // (cannot happen on a ring of distinct points; keeps a degenerate input bounded)
-    // this lane's best candidate among its points
-    int q = -1; double qx = 0.0, qy = 0.0, qd = 0.0;
-    for (int i = lane; i < n; i += 64) {
-      const double x = xy[2 * i], y = xy[2 * i + 1];
-      const double dx = x - px, dy = y - py, d = dx * dx + dy * dy;
-      if (d == 0.0) continue;                        // p itself
-      if (q < 0) { q = i; qx = x; qy = y; qd = d; continue; }
-      const double o = (qx - px) * (y - py) - (qy - py) * (x - px);      // orient2(p, q, r)
-      if (o < 0.0 || (o == 0.0 && d > qd)) { q = i; qx = x; qy = y; qd = d; }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      const int oq = __shfl_xor(q, off);
-      const double ox = __shfl_xor(qx, off), oy = __shfl_xor(qy, off), od = __shfl_xor(qd, off);
-      if (oq < 0) continue;
-      if (q < 0) { q = oq; qx = ox; qy = oy; qd = od; continue; }
-      const double o = (qx - px) * (oy - py) - (qy - py) * (ox - px);
-      // (both lanes of a pair must come to the same winner: on an exact tie of direction and distance the lower ring index)
-      if (o < 0.0 || (o == 0.0 && (od > qd || (od == qd && oq < q)))) { q = oq; qx = ox; qy = oy; qd = od; }
-    }
-    if (q < 0 || q == p0) break;
-    p = q; px = qx; py = qy;
-  }
-  if (nh > n) nh = n;
-  __syncthreads();                                   // lane 0's hull[] stores are visible
-  // Melkman's list starts at the hull vertex with the highest ring index: the caller reads hull[(k + rot) % nh]
-  int mi = -1, mk = 0;
-  for (int k = lane; k < nh; k += 64) { const int v = hull[k]; if (v > mi) { mi = v; mk = k; } }
-  for (int off = 32; off > 0; off >>= 1) { const int oi = __shfl_xor(mi, off), ok = __shfl_xor(mk, off); if (oi > mi) { mi = oi; mk = ok; } }
-  *rot = mk;
-  return nh;
-}
-
 // sh::convex_hull_simple_polygon (sh_scalar.h) for one lane that has to wait for every LDS answer.  The plain form reads two deque
 // slots and then their points for every orientation test: ~20 dependent LDS round trips per vertex, 1 us per vertex, the whole
 // kernel one slice's walk long (0.35 ms).  Here the deque holds COORDINATES (dqx, dqy: slots 0 .. 2n + 1, the hull ends up in
@@ -96,23 +38,13 @@ __device__ inline int hull_simple_polygon_cached(const double* xy, int n, double
   double t1x = o > 0 ? v1x : v0x, t1y = o > 0 ? v1y : v0y;
   double b2x = t1x, b2y = t1y, t2x = b1x, t2y = b1y;
   dqx[bot] = v2x; dqy[bot] = v2y; dqx[bot + 1] = b1x; dqy[bot + 1] = b1y; dqx[bot + 2] = t1x; dqy[bot + 2] = t1y; dqx[top] = v2x; dqy[top] = v2y;
-#ifdef SH_TE_CLOCK
-  long long c_int = 0, c_hull = 0; int n_int = 0, n_hull = 0;
-#endif
   double nx = n > 3 ? xy[6] : 0.0, ny = n > 3 ? xy[7] : 0.0;
   for (int i = 3; i < n; ++i) {
-#ifdef SH_TE_CLOCK
-    const long long cs_ = clock64();
-#endif
     const double vx = nx, vy = ny;
     if (i + 1 < n) { nx = xy[2 * i + 2]; ny = xy[2 * i + 3]; }      // (in flight during the tests below)
     double ob = orient2v(b0x, b0y, b1x, b1y, vx, vy);
     double ot = orient2v(t1x, t1y, t0x, t0y, vx, vy);
-#ifdef SH_TE_CLOCK
-    if (ob > 0 && ot > 0) { c_int += clock64() - cs_; ++n_int; continue; }
-#else
     if (ob > 0 && ot > 0) continue;
-#endif
     while (top - bot >= 2 && ob <= 0) {
       ++bot;
       b0x = b1x; b0y = b1y; b1x = b2x; b1y = b2y;
@@ -134,13 +66,7 @@ __device__ inline int hull_simple_polygon_cached(const double* xy, int n, double
     dqx[top] = vx; dqy[top] = vy;
     t2x = t1x; t2y = t1y; t1x = t0x; t1y = t0y; t0x = vx; t0y = vy;
     if (top - bot == 2) { b2x = vx; b2y = vy; }      // the new top slot is the bottom's third
-#ifdef SH_TE_CLOCK
-    c_hull += clock64() - cs_; ++n_hull;
-#endif
   }
-#ifdef SH_TE_CLOCK
-  dqx[2 * n + 4] = (double)c_int; dqx[2 * n + 5] = (double)n_int; dqx[2 * n + 6] = (double)c_hull; dqx[2 * n + 7] = (double)n_hull;
-#endif
   *first = bot;
   return top - bot;
 }
@@ -150,14 +76,6 @@ __device__ inline int hull_simple_polygon_cached(const double* xy, int n, double
 // in hull order wins, as in the sequential routine).
 // Two capacity tiers share the grid like k_slice_link (CAP = SH_SMALLSEG: 24 KB of LDS; the ring is staged in LDS first --
 // lane 0's hull walk is latency-bound when every point comes from global memory).
-// -DSH_TE_WRAP selects wave_hull_wrap (measured round 3: 0.21 ms for the hull phase either way -- the 64-lane tournament pays ~40
-// ds_bpermute per step for its reduction -- so the established one-lane walk stays the default)
-#ifdef SH_TE_WRAP
-constexpr bool getenv_te_melkman = false;
-#else
-constexpr bool getenv_te_melkman = true;
-#endif
-
 template <int CAP>
 __global__ void __launch_bounds__(64)
 k_te_rows(const double* __restrict__ ring, const int* __restrict__ ring_n, double* __restrict__ rects /*[B][37][7]*/, int B,
@@ -176,50 +94,23 @@ k_te_rows(const double* __restrict__ ring, const int* __restrict__ ring_n, doubl
   if (n < 3) { if (lane < 7) o[lane] = 0.0; return; }
   for (int q = lane; q < 2 * (n + 1); q += 64) s_xy[q] = gxy[q];
   __syncthreads();
-#if defined(SH_ABL_TE) && SH_ABL_TE == 1
-  return;
-#endif
   const double* xy = s_xy;
   const double *hx = dqx, *hy = dqy;
   int nh;
-  if (getenv_te_melkman) {
-    if (lane == 0) {
-      int first = 0;
-#ifdef SH_TE_CLOCK
-      const long long c0_ = clock64();
-#endif
-      int h = hull_simple_polygon_cached(xy, n, dqx, dqy, &first);   // rings are simple polygons in boundary order
-#ifdef SH_TE_CLOCK
-      dqx[2 * CAP + 7] = (double)(clock64() - c0_); dqy[2 * CAP + 7] = (double)n + 1e-3 * h;
-      dqy[2 * CAP + 3] = dqx[2 * n + 4]; dqy[2 * CAP + 4] = dqx[2 * n + 5]; dqy[2 * CAP + 5] = dqx[2 * n + 6]; dqy[2 * CAP + 6] = dqx[2 * n + 7];
-#endif
-      if (h < 0) {      // first three vertices collinear: the sort-based hull, its index arrays in the (idle) upper half of the deque
-        int* idx = (int*)(dqx + CAP + 4);
-        int* hl = (int*)(dqy + CAP + 4);
-        h = convex_hull_simple_polygon(xy, n, idx, hl);
-        for (int k = 0; k < h; ++k) { dqx[k] = xy[2 * hl[k]]; dqy[k] = xy[2 * hl[k] + 1]; }
-      }
-      nh_s = h; first_s = first;
+  if (lane == 0) {
+    int first = 0;
+    int h = hull_simple_polygon_cached(xy, n, dqx, dqy, &first);   // rings are simple polygons in boundary order
+    if (h < 0) {      // first three vertices collinear: the sort-based hull, its index arrays in the (idle) upper half of the deque
+      int* idx = (int*)(dqx + CAP + 4);
+      int* hl = (int*)(dqy + CAP + 4);
+      h = convex_hull_simple_polygon(xy, n, idx, hl);
+      for (int k = 0; k < h; ++k) { dqx[k] = xy[2 * hl[k]]; dqy[k] = xy[2 * hl[k] + 1]; }
     }
-    __syncthreads();
-    nh = nh_s;
-    hx = dqx + first_s; hy = dqy + first_s;
-  } else {
-    int rot = 0;
-    int* hull = (int*)(dqx + CAP + 4);
-    nh = wave_hull_wrap(xy, n, hull, lane, &rot);
-    __syncthreads();
-    double px[(CAP + 63) / 64], py[(CAP + 63) / 64];      // (gather through registers: hull[] lives in the arrays being written)
-#pragma unroll
-    for (int t = 0; t < (CAP + 63) / 64; ++t) { const int k = lane + 64 * t; if (k < nh) { int src = k + rot; if (src >= nh) src -= nh; px[t] = xy[2 * hull[src]]; py[t] = xy[2 * hull[src] + 1]; } }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < (CAP + 63) / 64; ++t) { const int k = lane + 64 * t; if (k < nh) { dqx[k] = px[t]; dqy[k] = py[t]; } }
-    __syncthreads();
+    nh_s = h; first_s = first;
   }
-#if defined(SH_ABL_TE) && SH_ABL_TE == 2
-  if (nh >= 0) return;
-#endif
+  __syncthreads();
+  nh = nh_s;
+  hx = dqx + first_s; hy = dqy + first_s;
   double best = 1e300;
   int bi = 0x7fffffff;
   Rect2 r;
@@ -257,10 +148,6 @@ k_te_rows(const double* __restrict__ ring, const int* __restrict__ ring_n, doubl
   wi = __shfl(wi, 0);
   if (bi == wi && wi != 0x7fffffff) { o[0] = r.cx; o[1] = r.cy; o[2] = r.mx; o[3] = r.my; o[4] = r.L; o[5] = r.W; o[6] = r.area; }
   else if (wi == 0x7fffffff && lane < 7) o[lane] = 0.0;
-#ifdef SH_TE_CLOCK
-  __syncthreads();
-  if (lane == 0) { o[5] = dqx[2 * CAP + 7]; o[6] = dqy[2 * CAP + 7]; o[0] = dqy[2 * CAP + 3]; o[1] = dqy[2 * CAP + 4]; o[2] = dqy[2 * CAP + 5]; o[3] = dqy[2 * CAP + 6]; }      // debug build: cycles of the walk, n + h / 1000, cycles / count of untouched and of hull-changing vertices
-#endif
   (void)B;
 }
 

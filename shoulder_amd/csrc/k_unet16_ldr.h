@@ -35,24 +35,14 @@ namespace sh {
 #define UL_NCW 4                          // compute waves; waves UL_NCW .. 7 load
 #define UL_LTHREADS 256                   // lanes of the loader half
 
-// The second source as an UP-CONVOLUTION computed in place (UPL = chunks of the low-resolution input, 0 = off): the decoder's
-// conv reads concat(skip, up(low)); instead of fetching the "up" chunks of a halo tile from a tensor that a launch of its own wrote
-// (0.54 GB out, 0.54 GB back in at level 1), the four LOADER waves -- which hold the registers of a compute wave and use a fifth of
-// them -- compute them: wave lw owns output phase (dy, dx) = (lw >> 1, lw & 1), 9 x 17 of the 18 x 34 halo pixels, ten groups of 16;
-// pixel fragments (18 x 10 low-resolution pixels x UPL chunks) and weight fragments come straight from L2 into registers, 8 UPL MFMAs
-// per group on the matrix pipe the compute wave of the SIMD is using, the rounded result goes to the halo rows the DMA would have
-// filled (zeros outside the image).  Same arithmetic in the same order as k_upconv16g (bias in the accumulator, chunks in order), so
-// the conv sees the same 16-bit values.  For layers with ONE cout group only (level 1): every group of a tile would compute the chunk again.
-struct UpSrc { const u16* low; const u16* w /*packed [4][UPL][C1][32]*/; const float* b; };
-
 // FUSE: 0 or UF_POOL.  WRES: 0 = weights staged with every step; 1 = one cout group whose packed weights fit behind the two
 // input buffers (nchunk <= 2): loaded once per workgroup.
-template <int EK, int FUSE, int WRES, int UPL = 0>
+template <int EK, int FUSE, int WRES>
 __global__ void __launch_bounds__(UD_THREADS)
 k_conv3_ldr16(const u16* __restrict__ src0_, const u16* __restrict__ src1_, int C0, int C1,
               const u16* __restrict__ wgt_, const float* __restrict__ bias, u16* __restrict__ dst_,
               int H, int W, int Cout, int relu, int nimg, const u16* __restrict__ zero_page_, u16* __restrict__ pooled_,
-              unsigned* __restrict__ ticket /*zero at launch*/, const int* __restrict__ tk_tab /*[ntk + 1] item bounds*/, int ntk, const UpSrc up) {
+              unsigned* __restrict__ ticket /*zero at launch*/, const int* __restrict__ tk_tab /*[ntk + 1] item bounds*/, int ntk) {
   using ET = typename EKT<EK>::type;
   const ET* src0 = (const ET*)src0_;
   const ET* src1 = (const ET*)src1_;
@@ -150,87 +140,25 @@ k_conv3_ldr16(const u16* __restrict__ src0_, const u16* __restrict__ src1_, int 
     const unsigned lbase = lds0 + (unsigned)(buf * BUFB + lw * 1024);      // (LDS byte address: the pieces are inline assembly, k_unet16_base.h)
     int r0v = r0;
     if constexpr (LAZY) asm volatile("" : "+v"(r0v));      // (opaque per call: nothing of the recomputation is hoisted out of the loop)
-    const bool upstep = UPL != 0 && !first;      // the halo rows of this step are computed (up_chunk below), only its weights are fetched
 #pragma unroll
     for (int k = 0; k < NPIECE; ++k) {
       if (k < NHALO - 1) {
-        if (!upstep) {
-          const int po = LAZY ? halo_pixel(r0v, k) : pixoff[LAZY ? 0 : k];
-          const ET* p = po >= 0 ? simg + (unsigned)((cb + po) * 32 + q8) : zero_page;
-          ud_dma16(lbase + k * 4096, p);
-        }
+        const int po = LAZY ? halo_pixel(r0v, k) : pixoff[LAZY ? 0 : k];
+        const ET* p = po >= 0 ? simg + (unsigned)((cb + po) * 32 + q8) : zero_page;
+        ud_dma16(lbase + k * 4096, p);
       } else if (k == NHALO - 1) {      // rows 640..703: 8 halo rows, then the first 56 weight rows
         const int po = LAZY ? halo_pixel(r0v, k) : pixoff[LAZY ? 0 : k];
         const ET* pi = po >= 0 ? simg + (unsigned)((cb + po) * 32 + q8) : zero_page;
         if constexpr (WRES != 0) {
-          if (wlow && !upstep) ud_dma16(lbase + k * 4096, pi);
+          if (wlow) ud_dma16(lbase + k * 4096, pi);
         } else {
           const ET* p = wlow ? pi : wbase + (wlane + k * wtap_stride);
-          if (!(wlow && upstep)) ud_dma16(lbase + k * 4096, p);
+          ud_dma16(lbase + k * 4096, p);
         }
       } else if (k < NPIECE - 1) {
         ud_dma16(lbase + k * 4096, (wbase + (wlane + k * wtap_stride)));
       } else {                          // the last piece: rows 1216..1223 only (tap 8, rows 56..63)
         if (wlow) ud_dma16(lbase + k * 4096, (wbase + (wlane + k * wtap_stride)));
-      }
-    }
-    if constexpr (UPL != 0) {
-      if (upstep) {
-        // ---- the halo rows of up chunk u = 32 channels of up(low): this wave's phase, ten groups of 16 pixels
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        using v2 = typename E16<ET>::v2;
-        const int u = (c0 - C0) >> 5;
-        const int H2 = H >> 1, W2 = W >> 1;
-        const int pdy = lw >> 1, pdx = lw & 1, oy = pdy == 0 ? 1 : 0, ox = pdx == 0 ? 1 : 0;
-        const ET* limg = (const ET*)up.low + (size_t)i_img * H2 * W2 * (UPL * 32);
-        const ET* uwp = (const ET*)up.w + ((size_t)(lw * UPL) * C1 + u * 32 + 8 * (li >> 2) + (li & 3)) * 32 + 8 * lk;
-        v8 uw[UPL][2];
-#pragma unroll
-        for (int kc = 0; kc < UPL; ++kc)
-#pragma unroll
-          for (int n = 0; n < 2; ++n) uw[kc][n] = *(const v8*)(uwp + ((size_t)kc * C1 + 4 * n) * 32);
-        f32x4 ubv[2];
-#pragma unroll
-        for (int n = 0; n < 2; ++n) ubv[n] = *(const f32x4*)(up.b + u * 32 + 8 * lk + 4 * n);
-        unsigned char* hb = smem + buf * BUFB;
-        const int ly0 = i_ty * 8 - 1 + oy, lx0 = i_tx * 16 - 1 + ox;
-        // a rolling window of five groups' pixel fragments: the loads of group g + 5 go out behind the MFMAs of group g, so a step
-        // pays one L2 latency, not one per batch (all ten at once do not fit the loader's registers)
-        constexpr int WIN = 5;
-        v8 xf[WIN][UPL];
-        bool inside[WIN];
-        auto request = [&](int g) __attribute__((always_inline)) {
-          const int t = 16 * g + li, a = t / 17, bc = t - a * 17;
-          const int ly = ly0 + a, lx = lx0 + bc;
-          inside[g % WIN] = ly >= 0 && ly < H2 && lx >= 0 && lx < W2;
-          const unsigned po = (unsigned)(min(max(ly, 0), H2 - 1) * W2 + min(max(lx, 0), W2 - 1));      // (unconditional, clamped: a load in a branch is waited for at its join)
-#pragma unroll
-          for (int kc = 0; kc < UPL; ++kc) xf[g % WIN][kc] = *(const v8*)(limg + ((size_t)kc * H2 * W2 + po) * 32 + 8 * lk);
-        };
-#pragma unroll
-        for (int g = 0; g < WIN; ++g) request(g);
-#pragma unroll
-        for (int g = 0; g < 10; ++g) {
-          f32x4 ua[2];
-#pragma unroll
-          for (int n = 0; n < 2; ++n) {
-            ua[n] = ubv[n];
-#pragma unroll
-            for (int kc = 0; kc < UPL; ++kc) ua[n] = E16<ET>::mfma(uw[kc][n], xf[g % WIN][kc], ua[n]);
-          }
-          const bool in_g = inside[g % WIN];
-          if (g + WIN < 10) request(g + WIN);
-          u32x4 o;
-#pragma unroll
-          for (int n = 0; n < 2; ++n) {
-            const f32x2 a01 = {ua[n][0], ua[n][1]}, a23 = {ua[n][2], ua[n][3]};
-            o[2 * n] = __builtin_bit_cast(unsigned, __builtin_convertvector(a01, v2));
-            o[2 * n + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(a23, v2));
-          }
-          if (!in_g) o = u32x4{0u, 0u, 0u, 0u};      // outside the image: the conv's zero padding
-          const int t = 16 * g + li, a = t / 17, bc = t - a * 17;
-          if (t < 153) *(u32x4*)(hb + UB_OFF((2 * a + oy) * UD_PW + 2 * bc + ox, lk) * 2) = o;
-        }
       }
     }
   };
@@ -344,55 +272,6 @@ k_conv3_ldr16(const u16* __restrict__ src0_, const u16* __restrict__ src1_, int 
         }
       }
   };
-
-  if constexpr (UPL != 0) {
-    // The two jobs as two loops (the same walk, the same barriers): with one loop for both, the compute wave's 128 accumulators are
-    // live in the loader's branch as well, and the fragments of the up-convolution do not fit beside them.
-    if (loader) {
-      item_lane_setup();
-      stage(0, 0);
-      int buf = 0;
-      for (;;) {
-        bool more = true;
-        for (int cc = 0; cc < nchunk; ++cc) {
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // this wave's pieces of the step have landed, what it computed of them is written
-          __builtin_amdgcn_s_barrier();
-          int n_cc; bool has_next, new_item;
-          walk(cc, n_cc, has_next, new_item, more);
-          if (has_next) {
-            if (new_item) item_lane_setup();
-            stage(n_cc, buf ^ 1);
-          }
-          buf ^= 1;
-        }
-        if (!more) break;
-      }
-    } else {
-      int buf = 0;
-      for (;;) {
-        bool more = true;
-        const int c_x0 = i_tx * 32, c_y0 = i_ty * 16, c_img = i_img, c_n0 = i_g * WR;
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          const f32x4 bv = *(const f32x4*)(s_bias + c_n0 + 16 * lk + 4 * n);
-#pragma unroll
-          for (int m = 0; m < 8; ++m) acc[m][n] = bv;
-        }
-        for (int cc = 0; cc < nchunk; ++cc) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          int n_cc; bool has_next, new_item;
-          walk(cc, n_cc, has_next, new_item, more);
-          multiply(acc, cc, buf);
-          buf ^= 1;
-        }
-        epilogue(acc, c_x0, c_y0, c_img, c_n0);
-        if (!more) break;
-      }
-    }
-    return;
-  }
 
   if (loader) {
     item_lane_setup();

@@ -31,15 +31,9 @@ namespace sh {
 #define PP_GTHREADS 256                      // lanes of a group (4 waves)
 #define PP_NPIECE 11                         // LDS-DMA pieces per staging wave and tile: 256 lanes x 11 = 2816 slots of 16 B >= 648 rows x 4
 #define PP_BUFB (PP_NPIECE * 4096)           // 45 056 bytes per halo buffer: piece k of staging wave v at k * 4096 + v * 1024
-#ifndef PP_K1
 #define PP_K1 11                             // pieces 0 .. PP_K1 - 1 of a tile are issued by the OFF group, the rest by the ON group behind its MFMAs
-#endif
-#ifndef PP_G1PRIO
 #define PP_G1PRIO 0                          // static s_setprio of the second-dispatched group (waves 4 .. 7: the loser of every age-based arbitration)
-#endif
-#ifndef PP_OFFPRIO
 #define PP_OFFPRIO 0                         // s_setprio of a wave in its OFF phase
-#endif
 
 template <int N> __device__ inline void pp_wait_vm() {      // s_waitcnt takes an immediate
   if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -188,9 +182,6 @@ k_dec0b_head_pp(const u16* __restrict__ src_ /*[img][H W][32]*/, const u16* __re
   }
   auto stage = [&](int bf, auto KB, auto KE) __attribute__((always_inline)) {      // pieces KB .. KE - 1 of the cursor's tile -> buffer bf; the four waves of the calling group
     constexpr int kb = decltype(KB)::value, ke = decltype(KE)::value;
-#if defined(PP_ABL) && (PP_ABL & 2)      // diagnostic (wrong results): no LDS-DMA
-    return;
-#endif
     const ET* simg = src + (size_t)cu.img * H * W * 32;
     const unsigned lb = lds0 + (unsigned)(bf * PP_BUFB) + wv1024;
     if (cu.tx > 0 && cu.tx + 1 < tiles_x && cu.ty > 0 && cu.ty + 1 < tiles_y) {      // interior tile: every halo pixel is inside the image
@@ -253,11 +244,7 @@ k_dec0b_head_pp(const u16* __restrict__ src_ /*[img][H W][32]*/, const u16* __re
     const int bf2 = bf == 0 ? 2 : bf - 1;      // (p + 2) % 3
     PP_T(ta_);
     if (on) {
-#if defined(PP_ABL) && (PP_ABL & 1)      // diagnostic (wrong results): no fragment reads, no MFMAs
-      if (false) {
-#else
       if (blive) {
-#endif
         const unsigned char* sb = smem + bf * PP_BUFB;
 #pragma unroll
         for (int n = 0; n < 2; ++n)
@@ -292,12 +279,7 @@ k_dec0b_head_pp(const u16* __restrict__ src_ /*[img][H W][32]*/, const u16* __re
       PP_T(tb_);
       PP_ADD(3, ta_, tb_);
       had_stores = false;
-#if defined(PP_ABL) && (PP_ABL & 4)      // diagnostic (wrong results): no epilogue
-      asm volatile("" :: "v"(acc[0][0]), "v"(acc[7][1]));
-      if (false) {
-#else
       if (alive) {
-#endif
         // logit = head_b + sum over the 32 channels of relu(conv) * head_w: 8 in the lane (the fma chain of k_conv3_dma16), then
         // (lane groups 0 + 1) + (lane groups 2 + 3) as a reduce-scatter
         // (the eight rows' chains side by side: hipcc keeps the source order, and one chain alone is 16 dependent instructions)
@@ -383,9 +365,7 @@ k_dec0b_head_pp(const u16* __restrict__ src_ /*[img][H W][32]*/, const u16* __re
 #define E0_POFF (2 * E0_HB)                 // 82 944
 #define E0_WOFF (E0_POFF + 2 * E0_PSLOT)    // 106 496: enc0b weights [9 taps][32 rows] of 64 B (in LDS: the OFF phase needs the registers)
 #define E0_SMEM (E0_WOFF + 9 * 32 * 64)     // 124 928
-#ifndef E0_OFFPRIO
 #define E0_OFFPRIO 1                        // s_setprio of a wave in its OFF phase: the OFF side (~500 instructions) is this kernel's critical path (measured: 0.398 -> 0.383 ms)
-#endif
 #define E0_NGRP 41                          // groups of 16 halo rows (648 = 40.5 x 16)
 
 // groups T0 .. T1 - 1 of a wave's share of the first conv (k_enc0_pp): all fragment reads of the batch, then its MFMAs, then its
@@ -747,9 +727,7 @@ k_enc0_pp(const float* __restrict__ image, const float* __restrict__ w0 /*[9][32
 #define DA_SMEM (DA_W + 2 * 9 * 32 * 64)     // 156 672
 #define DA_NSP 6                             // LDS-DMA pieces per staging wave: skip halo (1 440 slots of 16 B) ...
 #define DA_NLP 4                             // ... and low tile (864 slots)
-#ifndef DA_ONPRIO
 #define DA_ONPRIO 0                          // s_setprio of a wave while it multiplies
-#endif
 
 template <int EK>
 __global__ void __launch_bounds__(PP_THREADS)

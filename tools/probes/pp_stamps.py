@@ -1,4 +1,4 @@
-"""Where a ping-pong kernel's cycles go (library built with SHOULDER_HIPCC_FLAGS=-DPP_STAMP into another path: SHOULDER_LIB=...).
+"""Where a ping-pong kernel's cycles go (a -DPP_STAMP library: tools/probes/pp_variant.sh pp_stamp -DPP_STAMP -> ab/libpp_stamp.so).
 Runs the network alone a few times on 64 x 512 x 512 and prints, per part of a phase, the mean cycles per phase of the ON / OFF waves.
   SHOULDER_LIB=ab/libpp_stamp.so python tools/probes/pp_stamps.py"""
 import ctypes, os, sys
