@@ -36,7 +36,7 @@ typedef enum sh_status {
                            is repeated inside sh_collect) -- what is left: a caller-sized output that is too small (the
                            counts returned say how large), more than 1 024 closed loops in ONE section, and a growth
                            that is needed while a second run is in flight (collect it, run again) */
-  SH_ERR_GEOMETRY = -5, /* degenerate input: open contour, empty slice, ray miss, ... */
+  SH_ERR_GEOMETRY = -5, /* degenerate input: open contour (SH_OPEN_ERROR mode; see sh_set_open_contours), empty slice, ray miss, ... */
   SH_ERR_NOMEM = -6
 } sh_status;
 
@@ -187,6 +187,28 @@ int  sh_batch_size(const sh_ctx*);
  * `Slices.ixy / itr_start / itr_centered_start`).  A run of SH_STAGE_GROOVE without SH_STAGE_PROXIMAL after groove_cutoff changed
  * returns SH_ERR_STATE: the rows it needs were not written. */
 int  sh_set_keep_products(sh_ctx*, int on);
+
+/* Meshes that are not watertight.  The reference warns and carries on (humerus/mesh.py:24-27 `if not mesh.is_watertight:
+ * warnings.warn(...)`) and resamples `slice.discrete[0]` whether that path is closed or not (slice.py:65-80).
+ * SH_OPEN_ERROR (the default): a section with an open chain of crossing segments is SH_ERR_GEOMETRY for that humerus.
+ * SH_OPEN_BRIDGE: in every plane of every slice set (slice.py:21-60 full / distal / proximal sets, surgical_neck.py:37-39 neck
+ * contour, mesh.py:157-160 ProxObb area scan) a chain's tail t is joined to a chain's head h by a virtual segment when the gap
+ * |end(t) - start(h)| <= max_gap (mm, box-frame xy), smallest (gap, end key of t, start key of h) first; the bridge adds one
+ * ring vertex, the crossing on t's end edge.  Loops are the cycles of three or more vertices; segments on no loop are dropped
+ * (max_gap = 0: oracle/section.py's "drop open chains").  A plane left without a loop is SH_ERR_GEOMETRY as before (an empty
+ * area-scan section stays legal).  A single missing triangle is bridged by its own segment: the intact mesh's records.
+ * max_gap: finite and >= 0, else SH_ERR_ARG; default SH_OPEN_GAP_DEFAULT (the longest edge of the test meshes, 11.46 mm, rounded
+ * up).  Not while runs are in flight (SH_ERR_STATE).  Multi-hit rays, non-manifold edges and sh_clip's open contours stay errors. */
+enum { SH_OPEN_ERROR = 0, SH_OPEN_BRIDGE = 1 };
+#define SH_OPEN_GAP_DEFAULT 12.0
+int  sh_set_open_contours(sh_ctx*, int mode, double max_gap);
+int  sh_get_open_contours(const sh_ctx*, int* mode, double* max_gap);
+/* Per humerus of the last run: open chains closed by bridges and open chains dropped (bridged + dropped = the chains of every
+ * section; 0 / 0 after a run in SH_OPEN_ERROR mode).  bridged, dropped: B int32 each. */
+int  sh_open_contour_stats(sh_ctx*, int32_t* bridged /* B */, int32_t* dropped /* B */);
+/* `not mesh.is_watertight` (humerus/mesh.py:24) as a count: per resident mesh, the undirected edges used by a number of faces
+ * other than two (0: every edge has two faces).  On demand, outside sh_run.  out: B int64. */
+int  sh_mesh_open_edges(sh_ctx*, int64_t* out /* B */);
 
 /* Records on the wire.  A full sh_landmarks record is 104 KB, 96 KB of it the padded anatomic-neck point list (4 096 rows; a
  * humerus has about a thousand).  sh_set_record_rows(R), R > 0: every record a run hands out through `out` of sh_run /

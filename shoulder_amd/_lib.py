@@ -16,6 +16,8 @@ STAGE_APPLY = 1024
 STAGE_ALL = 0x7FF
 UNET_F32, UNET_BF16, UNET_F16, UNET_F32X = 0, 1, 2, 3
 BONE_HUMERUS, BONE_PROXIMAL = 0, 1
+OPEN_ERROR, OPEN_BRIDGE = 0, 1
+OPEN_GAP_DEFAULT = 12.0      # mm, SH_OPEN_GAP_DEFAULT
 
 
 class Landmarks(ctypes.Structure):
@@ -79,7 +81,8 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_kernel_time_ms", "sh_enable_timing", "sh_set_overlap", "sh_discard_prepared", "sh_unet_infer", "sh_host_alloc", "sh_host_free", "sh_upload_stl", "sh_submit", "sh_collect",
            "sh_stage_meshes", "sh_stage_stl", "sh_commit_staged", "sh_staged", "sh_set_record_rows", "sh_record_bytes", "sh_anp_points",
            "sh_comm_init_all", "sh_bcast_weights", "sh_gather_landmarks", "sh_set_keep_products",
-           "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring"]
+           "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring",
+           "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges"]
 
 _lib = None
 
@@ -162,5 +165,9 @@ def load(build_if_missing=True):
     L.sh_bcast_weights.argtypes = [ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int]
     L.sh_gather_landmarks.argtypes = [ctypes.POINTER(vp), ctypes.c_int, vp]
     L.sh_unet_infer.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp]
+    L.sh_set_open_contours.argtypes = [vp, ctypes.c_int, ctypes.c_double]
+    L.sh_get_open_contours.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+    L.sh_open_contour_stats.argtypes = [vp, vp, vp]
+    L.sh_mesh_open_edges.argtypes = [vp, vp]
     _lib = L
     return L

@@ -297,7 +297,16 @@ class ProximalHumerus(Bone):
     _EARLY = EARLY
     _LATE = _lib.STAGE_PROXIMAL | _lib.STAGE_GROOVE | _lib.STAGE_ANP | _lib.STAGE_CSYS | _lib.STAGE_APPLY
 
-    def __init__(self, stl_file, engine=None):
+    def __init__(self, stl_file, engine=None, open_contours="error", max_gap=_lib.OPEN_GAP_DEFAULT):
+        """open_contours="bridge": a mesh that is not watertight is measured with its section gaps up to max_gap mm bridged
+        (Engine.set_open_contours, include/shoulder_hip.h) and warns as the reference does (mesh.py:24-27); "error" (the
+        default): an open section fails the humerus."""
+        if open_contours not in ("error", "bridge"):
+            raise ValueError(f'open_contours is "error" or "bridge", not {open_contours!r}')
+        gap = float(max_gap)
+        if not np.isfinite(gap) or gap < 0:
+            raise ValueError(f"max_gap must be finite and >= 0, not {max_gap!r}")
+        self._open = (open_contours, gap)
         self._tfrm = Transform()
         self.transform = self._tfrm.matrix
         self.stl_file = stl_file if isinstance(stl_file, pathlib.Path) else pathlib.Path(stl_file)
@@ -305,11 +314,14 @@ class ProximalHumerus(Bone):
         verts, faces = load_stl(self.stl_file)
         self._verts, self._faces = verts, faces
         self._engine.upload([(verts, faces)])
+        self._engine._resident_bone = id(self)      # (two bones with the same vertices have the same box: _ensure_loaded tells them apart by this)
         self._engine.set_params(bone_kind=self._BONE_KIND)      # (read-modify-write: the engine's UNet dtype and cut-offs stay as configured)
+        if open_contours == "bridge" and int(self._engine.open_edges()[0]) > 0:
+            warnings.warn(f"{self.stl_file.name} is not watertight!", UserWarning)      # mesh.py:26
         self._lm_all = None
         self._groove_params = None      # (cutoff_pcts, deg_window) this bone's late stages ran with
         # eager part of the reference constructor: OBB, full slices, surgical neck, canal axis
-        self._early = self._engine.run(self._EARLY)[0].copy()
+        self._early = self._run(self._EARLY)[0].copy()
         self._canal_cutoff = tuple(float(x) for x in self._early["canal_cutoff"])
         self._obb_transform = np.array(self._early["obb_transform"], dtype=np.float64)
         self._z_bounds = tuple(self._engine.fetch("z_bounds", np.float64, (1, 2))[0])
@@ -330,16 +342,22 @@ class ProximalHumerus(Bone):
         self.cutoff_pcts = [float(x) for x in self._canal_cutoff]           # ProxObb.cutoff_pcts (mesh.py:190)
         self.cutoff_bot = int(e.fetch("pobb.cutoff_idx", np.int32, (1, 2))[0][0])      # mesh.py:187
 
+    def _run(self, stages, fetch=True):
+        """Every run of this bone on the (possibly shared) engine takes this bone's open-contour setting."""
+        self._engine.set_open_contours(*self._open)
+        return self._engine.run(stages, fetch=fetch)
+
     def _ensure_loaded(self):
         """The shared engine may have been used for another bone since: bring this one back."""
         e = self._engine
-        if e.B != 1 or not np.array_equal(e.fetch("obb_transform", np.float64, (1, 4, 4))[0], self._obb_transform):
+        if e.B != 1 or getattr(e, "_resident_bone", id(self)) != id(self) or not np.array_equal(e.fetch("obb_transform", np.float64, (1, 4, 4))[0], self._obb_transform):
             e.upload([(self._verts, self._faces)])
+            e._resident_bone = id(self)
             e.set_params(bone_kind=self._BONE_KIND, canal_cutoff=self._canal_cutoff if self._BONE_KIND == _lib.BONE_HUMERUS else None)
-            e.run(self._EARLY, fetch=False)
+            self._run(self._EARLY, fetch=False)
             if self._lm_all is not None:      # device buffers fetched later (e.g. anp.points_obb beyond 4096 rows) must match the cached record
                 e.set_params(groove_cutoff=self._groove_params[0], groove_deg_window=self._groove_params[1])
-                e.run(self._LATE, fetch=False)
+                self._run(self._LATE, fetch=False)
 
     # -- the late stages, once ------------------------------------------------------------------------
     def _all(self, groove_cutoff=(0.2, 0.75), deg_window=7):
@@ -351,7 +369,7 @@ class ProximalHumerus(Bone):
             except Exception as ex:
                 raise ValueError(f"bicipital_groove cutoff_pcts {groove_cutoff} is not supported: {ex}") from ex
             self._groove_params = (tuple(float(x) for x in groove_cutoff), float(deg_window))
-            self._lm_all = e.run(self._LATE)[0].copy()
+            self._lm_all = self._run(self._LATE)[0].copy()
             if int(self._lm_all["status"]) != 0:
                 raise ValueError(f"landmark stage failed with status {int(self._lm_all['status'])}")
         return self._lm_all

@@ -25,7 +25,10 @@ struct OvfPools {
   unsigned long long seg_cap, ring_cap, work_cap;      // in segments / ring points / bytes
   unsigned long long* ctr;                             // [0] segments used (per set) [1] ring points used (per run) [2] work bytes used (per set)
                                                        // [3..5] high-water marks of what the run would have needed
+  int open_mode;                                       // sh_set_open_contours: bridging, a plane's join may add up to one node per segment
 };
+// nodes a plane's join workspace and ring range are sized for: its segments, and as many bridges again in bridge mode
+__host__ __device__ inline int ovf_nodes(int cnt, int open_mode) { return open_mode ? 2 * cnt : cnt; }
 
 // per-set plan arrays, one entry per (humerus, plane): ranges in the pools (-1: not an overflow plane)
 struct OvfSet { long long* soff; long long* roff; long long* woff; int* fill; int* list; int* nlist /*[0] listed planes, [1] planes with many loops*/; int* list2; };
@@ -46,12 +49,13 @@ __global__ void k_ovf_plan(int N, int nplanes, const int* __restrict__ seg_count
   const int cnt = seg_count[pl];
   S.soff[pl] = -1; S.roff[pl] = -1; S.woff[pl] = -1; S.fill[pl] = 0;
   if (cnt <= SH_MAXSEG) return;
-  const unsigned long long wb = ovf_work_bytes(cnt);
+  const int nn = ovf_nodes(cnt, P.open_mode);
+  const unsigned long long wb = ovf_work_bytes(nn);
   const unsigned long long s = atomicAdd(&P.ctr[0], (unsigned long long)cnt);
-  const unsigned long long r = atomicAdd(&P.ctr[1], (unsigned long long)cnt + 1ull);
+  const unsigned long long r = atomicAdd(&P.ctr[1], (unsigned long long)nn + 1ull);
   const unsigned long long w = atomicAdd(&P.ctr[2], wb);
-  atomicMax(&P.ctr[3], s + cnt); atomicMax(&P.ctr[4], r + cnt + 1ull); atomicMax(&P.ctr[5], w + wb);
-  if (s + cnt > P.seg_cap || r + cnt + 1ull > P.ring_cap || w + wb > P.work_cap) { atomicExch(&err[pl / N], SH_ERR_CAPACITY_DEV); return; }
+  atomicMax(&P.ctr[3], s + cnt); atomicMax(&P.ctr[4], r + nn + 1ull); atomicMax(&P.ctr[5], w + wb);
+  if (s + cnt > P.seg_cap || r + nn + 1ull > P.ring_cap || w + wb > P.work_cap) { atomicExch(&err[pl / N], SH_ERR_CAPACITY_DEV); return; }
   S.soff[pl] = (long long)s; S.roff[pl] = (long long)r; S.woff[pl] = (long long)w;
   S.list[atomicAdd(S.nlist, 1)] = pl;
 }
@@ -122,12 +126,13 @@ k_ovf_plan_loops(int N, const int* __restrict__ seg_count, const Seg* __restrict
     const int pl = S.list2[i];
     const int cnt = seg_count[pl];
     if (threadIdx.x == 0) {
-      const unsigned long long wb = ovf_work_bytes(cnt);
+      const int nn = ovf_nodes(cnt, P.open_mode);
+      const unsigned long long wb = ovf_work_bytes(nn);
       const unsigned long long s = atomicAdd(&P.ctr[0], (unsigned long long)cnt);
-      const unsigned long long r = atomicAdd(&P.ctr[1], (unsigned long long)cnt + 1ull);
+      const unsigned long long r = atomicAdd(&P.ctr[1], (unsigned long long)nn + 1ull);
       const unsigned long long w = atomicAdd(&P.ctr[2], wb);
-      atomicMax(&P.ctr[3], s + cnt); atomicMax(&P.ctr[4], r + cnt + 1ull); atomicMax(&P.ctr[5], w + wb);
-      if (s + cnt > P.seg_cap || r + cnt + 1ull > P.ring_cap || w + wb > P.work_cap) { atomicExch(&err[pl / N], SH_ERR_CAPACITY_DEV); so = -1; }
+      atomicMax(&P.ctr[3], s + cnt); atomicMax(&P.ctr[4], r + nn + 1ull); atomicMax(&P.ctr[5], w + wb);
+      if (s + cnt > P.seg_cap || r + nn + 1ull > P.ring_cap || w + wb > P.work_cap) { atomicExch(&err[pl / N], SH_ERR_CAPACITY_DEV); so = -1; }
       else { so = (long long)s; ro = (long long)r; wo = (long long)w; }
     }
     __syncthreads();
@@ -144,27 +149,29 @@ k_ovf_plan_loops(int N, const int* __restrict__ seg_count, const Seg* __restrict
 #define SH_MAXLOOPS_G 1024      // loops per plane in the overflow tier's join (the LDS tiers: SH_MAXLOOPS = 32, more go here)
 
 // slice_link_plane (k_slices.h) with its arrays in the plane's workspace; every step in the same order with the same arithmetic
+template <bool OPEN>      // (as slice_link_plane: bridge mode's code only in OPEN = true)
 __device__ inline void slice_link_plane_g(const int pl, int N, const int* __restrict__ seg_count, const Seg* __restrict__ sp, const double* __restrict__ vb /*verts_obb of the plane's mesh*/,
              const double zpl /*the plane's height*/, unsigned char* __restrict__ wk,
              double* __restrict__ centroids, double* __restrict__ areas, int* __restrict__ nloops, int* __restrict__ ring_n, double* __restrict__ ring_out /*nullable*/,
-             int select, int* __restrict__ err, double* __restrict__ areas_total) {
+             int select, int* __restrict__ err, double* __restrict__ areas_total, const OpenCfg oc) {
   constexpr int T = SH_HUGE_THREADS;
   __shared__ unsigned long long l_key[SH_MAXLOOPS_G];
   __shared__ int l_start[SH_MAXLOOPS_G], l_len[SH_MAXLOOPS_G], l_off[SH_MAXLOOPS_G];
   __shared__ double l_area[SH_MAXLOOPS_G], l_sel[SH_MAXLOOPS_G];
-  __shared__ int n_loops, bad;
+  __shared__ int n_loops, bad, octl[4];
   __shared__ double bbw[T / 64][4];
   const int b = pl / N, tid = threadIdx.x;
   const int n = seg_count[pl];
-  const unsigned HASH = ovf_hash_size(n);
+  const int cap = ovf_nodes(n, OPEN ? oc.mode : 0);      // (k_ovf_plan sized the workspace for it)
+  const unsigned HASH = ovf_hash_size(cap);
   unsigned long long* skey = (unsigned long long*)wk;
-  unsigned long long* bufA = skey + n;
-  unsigned long long* bufB = bufA + n;
-  double* rx = (double*)(bufB + n);
-  double* ry = rx + n;
-  int* table = (int*)(ry + n);
+  unsigned long long* bufA = skey + cap;
+  unsigned long long* bufB = bufA + cap;
+  double* rx = (double*)(bufB + cap);
+  double* ry = rx + cap;
+  int* table = (int*)(ry + cap);
   int* nxt = table + HASH;
-  int* jmpA = nxt + n; int* jmpB = jmpA + n; int* offA = jmpB + n; int* offB = offA + n; int* posv = offB + n;
+  int* jmpA = nxt + cap; int* jmpB = jmpA + cap; int* offA = jmpB + cap; int* offB = offA + cap; int* posv = offB + cap;
   if (tid == 0) { n_loops = 0; bad = 0; }
   for (unsigned i = tid; i < HASH; i += T) table[i] = -1;
   for (int i = tid; i < n; i += T) {
@@ -190,14 +197,23 @@ __device__ inline void slice_link_plane_g(const int pl, int N, const int* __rest
     nxt[i] = found;
   }
   __syncthreads();
+  // open contours, bridge mode (k_open.h): every chain end of the plane takes part (scratch: the arrays the steps below fill anew;
+  // the hash table, 2 cap entries, holds the matches)
+  const bool bridging = OPEN && (bad || n < 3);
+  int n2 = n;
+  if (bridging) {
+    n2 = bridge_open_chains<T>(n, cap, n, skey, bufA, nxt, offB, octl, jmpA, jmpB, offA, posv, table, table + cap, rx, ry,
+                               (double*)bufB, (double*)bufB + n, vb, zpl, oc.max_gap);
+    if (tid == 0) bad = 0;      // (n2 >= 0: at most n chain ends, at most n bridges)
+  }
   unsigned long long* labA = bufA;
   unsigned long long* labB = bufB;
   int* ja = jmpA; int* jb = jmpB;
   int* ra = offA; int* rb = offB;
-  for (int i = tid; i < n; i += T) { labA[i] = skey[i]; ja[i] = nxt[i]; ra[i] = 0; }
+  for (int i = tid; i < n2; i += T) { labA[i] = skey[i]; ja[i] = nxt[i]; ra[i] = 0; }
   __syncthreads();
-  for (int span = 1; span < n; span <<= 1) {
-    for (int i = tid; i < n; i += T) {
+  for (int span = 1; span < n2; span <<= 1) {
+    for (int i = tid; i < n2; i += T) {
       const int j = ja[i];
       const unsigned long long a = labA[i], c = labA[j];
       const bool own = a <= c;
@@ -210,8 +226,8 @@ __device__ inline void slice_link_plane_g(const int pl, int N, const int* __rest
     int* tj = ja; ja = jb; jb = tj;
     int* tr = ra; ra = rb; rb = tr;
   }
-  for (int i = tid; i < n; i += T)
-    if (ra[i] == 0) {
+  for (int i = tid; i < n2; i += T)
+    if (ra[i] == 0 && (!bridging || (nxt[ja[i]] != ja[i] && ra[nxt[i]] >= 2))) {      // (bridging: on no chain, three vertices or more)
       const int l = atomicAdd(&n_loops, 1);
       if (l < SH_MAXLOOPS_G) l_start[l] = i;
     }
@@ -231,10 +247,17 @@ __device__ inline void slice_link_plane_g(const int pl, int N, const int* __rest
       l_len[l] = L; l_off[l] = off; off += L;
       l_key[l] = skey[s];
     }
-    if (off != n) bad = 1;        // some segments are on no closed loop
+    if (off != n && !bridging) bad = 1;        // some segments are on no closed loop
   }
   __syncthreads();
-  for (int i = tid; i < n; i += T) {      // ring placement: position from start = (L - r) mod L
+  if (bridging && oc.stats)      // chains bridged / dropped, counted at their tails (k_slices.h)
+    for (int i = tid; i < n; i += T)
+      if (nxt[i] == i || nxt[i] >= n) {
+        bool kept = false;
+        for (int q = 0; q < nl; ++q) kept |= l_key[q] == labA[i];
+        atomicAdd(&oc.stats[2 * b + (kept ? 0 : 1)], 1);
+      }
+  for (int i = tid; i < n2; i += T) {      // ring placement: position from start = (L - r) mod L
     const unsigned long long key = labA[i];
     int l = -1;
     for (int q = 0; q < nl; ++q) if (l_key[q] == key) { l = q; break; }
@@ -245,14 +268,18 @@ __device__ inline void slice_link_plane_g(const int pl, int N, const int* __rest
   }
   __syncthreads();
   // (rx / ry do not alias the label buffers here, so no barrier is needed between reading labA and writing them)
-  for (int i = tid; i < n; i += T)
-    if (posv[i] >= 0 && posv[i] < n) { const Seg sg = sp[i]; seg_start_point(vb, sg.s_lo, sg.s_hi, zpl, &rx[posv[i]], &ry[posv[i]]); }
+  for (int i = tid; i < n2; i += T)
+    if (posv[i] >= 0 && posv[i] < n2) {
+      if (!OPEN || i < n) { const Seg sg = sp[i]; seg_start_point(vb, sg.s_lo, sg.s_hi, zpl, &rx[posv[i]], &ry[posv[i]]); }
+      else { const unsigned long long kv = skey[i]; seg_start_point(vb, (uint32_t)(kv >> 32), (uint32_t)kv, zpl, &rx[posv[i]], &ry[posv[i]]); }      // a bridge
+    }
   __syncthreads();
   // AABB over every loop vertex by all waves (min / max: order free), the per-loop sums by one wave per loop as in the LDS tiers
   const int lane = tid & 63, wave = tid >> 6;
   {
+    const int nv = bridging ? (nl > 0 ? l_off[nl - 1] + l_len[nl - 1] : 0) : n;      // ring vertices placed (bridging: the loops' only)
     double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
-    for (int i = tid; i < n; i += T) {
+    for (int i = tid; i < nv; i += T) {
       const double qx = rx[i], qy = ry[i];
       x0 = fmin(x0, qx); x1 = fmax(x1, qx); y0 = fmin(y0, qy); y1 = fmax(y1, qy);
     }
@@ -298,7 +325,7 @@ __device__ inline void slice_link_plane_g(const int pl, int N, const int* __rest
     }
     nloops[pl] = nl;
     ring_n[pl] = nl > 0 ? l_len[best] : 0;
-    if (bad || nl == 0) atomicCAS(&err[b], 0, SH_ERR_GEOMETRY_DEV);
+    if (bad || (nl == 0 && !(bridging && areas_total))) atomicCAS(&err[b], 0, SH_ERR_GEOMETRY_DEV);      // (bridged to nothing: an empty section, legal in the area scan)
   }
   if (ring_out && nl > 0) {
     const int l = best, o = l_off[l], L = l_len[l];
@@ -313,15 +340,16 @@ __device__ inline void slice_link_plane_g(const int pl, int N, const int* __rest
   __syncthreads();
 }
 
+template <bool OPEN>
 __global__ void __launch_bounds__(SH_HUGE_THREADS)
 k_slice_link_huge(int N, const int* __restrict__ seg_count, OvfPools P, OvfSet S, double* __restrict__ centroids, double* __restrict__ areas,
                   int* __restrict__ nloops, int* __restrict__ ring_n, int want_ring, int select, int* __restrict__ err, double* __restrict__ areas_total,
-                  const double* __restrict__ vobb, const long long* __restrict__ voff, const double* __restrict__ zeff) {
+                  const double* __restrict__ vobb, const long long* __restrict__ voff, const double* __restrict__ zeff, const OpenCfg oc) {
   const int nl = *S.nlist;
   for (int i = blockIdx.x; i < nl; i += gridDim.x) {
     const int pl = S.list[i];
-    slice_link_plane_g(pl, N, seg_count, P.segs + S.soff[pl], vobb + 3 * voff[pl / N], zeff[pl], P.work + S.woff[pl], centroids, areas, nloops, ring_n,
-                       want_ring ? P.ring + 2 * S.roff[pl] : (double*)nullptr, select, err, areas_total);
+    slice_link_plane_g<OPEN>(pl, N, seg_count, P.segs + S.soff[pl], vobb + 3 * voff[pl / N], zeff[pl], P.work + S.woff[pl], centroids, areas, nloops, ring_n,
+                       want_ring ? P.ring + 2 * S.roff[pl] : (double*)nullptr, select, err, areas_total, oc);
   }
 }
 

@@ -123,7 +123,12 @@ struct SliceSetDev {
   int* nlarge; ManyLoops many; unsigned long long* ovf_missed;
   PlaneAux aux;
 };
-struct SliceSets { SliceSetDev s[2]; int n; const double* vobb; const long long* voff; };      // (vobb / voff: the join recomputes the crossing points)
+// Open contours (sh_set_open_contours; the rule: k_open.h).  mode 0: an open chain is SH_ERR_GEOMETRY for
+// the humerus; mode 1 (SH_OPEN_BRIDGE): gaps up to max_gap are bridged, segments on no loop dropped.  stats: [B][2] chains bridged /
+// chains dropped by the last run (window-offset like every [B] buffer; nullptr with mode 0).
+struct OpenCfg { int mode; double max_gap; int* stats; };
+
+struct SliceSets { SliceSetDev s[2]; int n; const double* vobb; const long long* voff; OpenCfg open; };      // (vobb / voff: the join recomputes the crossing points)
 
 __global__ void k_make_planes(SliceSets sets, const double* __restrict__ neck_z, int B) {
   const SliceSetDev& S = sets.s[blockIdx.y];
@@ -276,6 +281,80 @@ __device__ inline uint32_t hash_key64(unsigned long long k) {
   return (uint32_t)k;
 }
 
+// Greedy matching by the smallest candidate first equals the matching of locally dominant pairs (a pair that is the smallest
+// candidate of its tail AND of its head) taken round after round, when the order is total: it is here, (gap, tail key, head
+// key) names one pair.  Every lane of the workgroup calls this, after the hash join (nxt[i] == i: i is a tail).
+//   pred: >= n ints; ctl: 4 ints; tl, hd, bt, bh, mt, mh: >= maxe ints each; tx, ty, hx, hy: >= maxe doubles each.
+// Returns the node count with the bridges appended at n.. (their skey and nxt set, nxt of their tails pointed at them), or -1
+// when the plane has more than maxe chain ends or the bridges do not fit below cap: the caller hands the plane on.
+template <int T>
+__device__ inline int bridge_open_chains(const int n, const int cap, const int maxe, unsigned long long* __restrict__ skey,
+                                         const unsigned long long* __restrict__ ekey, int* __restrict__ nxt, int* __restrict__ pred,
+                                         int* __restrict__ ctl, int* tl, int* hd, int* bt, int* bh, int* mt, int* mh,
+                                         double* tx, double* ty, double* hx, double* hy,
+                                         const double* __restrict__ vb, const double z, const double max_gap) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += T) pred[i] = 0;
+  if (tid < 4) ctl[tid] = 0;      // [0] tails [1] heads [2] matched this round [3] bridges
+  __syncthreads();
+  for (int i = tid; i < n; i += T) if (nxt[i] != i) atomicAdd(&pred[nxt[i]], 1);
+  __syncthreads();
+  for (int i = tid; i < n; i += T) {
+    if (nxt[i] == i) { const int q = atomicAdd(&ctl[0], 1); if (q < maxe) tl[q] = i; }
+    if (pred[i] == 0) { const int q = atomicAdd(&ctl[1], 1); if (q < maxe) hd[q] = i; }
+  }
+  __syncthreads();
+  const int nt = ctl[0], nh = ctl[1];
+  if (nt > maxe || nh > maxe) return -1;      // (uniform)
+  for (int q = tid; q < nt; q += T) { const unsigned long long k = ekey[tl[q]]; seg_start_point(vb, (uint32_t)(k >> 32), (uint32_t)k, z, &tx[q], &ty[q]); mt[q] = -1; }
+  for (int q = tid; q < nh; q += T) { const unsigned long long k = skey[hd[q]]; seg_start_point(vb, (uint32_t)(k >> 32), (uint32_t)k, z, &hx[q], &hy[q]); mh[q] = -1; }
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) ctl[2] = 0;
+    for (int q = tid; q < nt; q += T) {      // each free tail: its smallest candidate among the free heads
+      int best = -1; double bd = 0.0; unsigned long long bk = 0;
+      if (mt[q] < 0)
+        for (int h = 0; h < nh; ++h) {
+          if (mh[h] >= 0) continue;
+          const double dx = tx[q] - hx[h], dy = ty[q] - hy[h];
+          const double d = sqrt(dx * dx + dy * dy);
+          if (!(d <= max_gap)) continue;
+          const unsigned long long k = skey[hd[h]];
+          if (best < 0 || d < bd || (d == bd && k < bk)) { best = h; bd = d; bk = k; }
+        }
+      bt[q] = best;
+    }
+    for (int q = tid; q < nh; q += T) {      // each free head: its smallest candidate among the free tails
+      int best = -1; double bd = 0.0; unsigned long long bk = 0;
+      if (mh[q] < 0)
+        for (int t = 0; t < nt; ++t) {
+          if (mt[t] >= 0) continue;
+          const double dx = tx[t] - hx[q], dy = ty[t] - hy[q];
+          const double d = sqrt(dx * dx + dy * dy);
+          if (!(d <= max_gap)) continue;
+          const unsigned long long k = ekey[tl[t]];
+          if (best < 0 || d < bd || (d == bd && k < bk)) { best = t; bd = d; bk = k; }
+        }
+      bh[q] = best;
+    }
+    __syncthreads();
+    for (int q = tid; q < nt; q += T) {
+      const int h = bt[q];
+      if (h >= 0 && bh[h] == q) { mt[q] = h; mh[h] = q; ctl[2] = 1; }
+    }
+    __syncthreads();
+    if (ctl[2] == 0) break;      // (uniform: no pair left that is both ends' smallest candidate -- no candidate left)
+  }
+  for (int q = tid; q < nt; q += T)
+    if (mt[q] >= 0) {
+      const int v = n + atomicAdd(&ctl[3], 1);
+      if (v < cap) { skey[v] = ekey[tl[q]]; nxt[v] = hd[mt[q]]; nxt[tl[q]] = v; }
+    }
+  __syncthreads();
+  const int nb = ctl[3];
+  return n + nb > cap ? -1 : n + nb;
+}
+
 // select: 0 = largest loop (slice.py:53-59), 1 = loop whose closed-ring vertex mean is nearest
 // the origin in L1 (surgical_neck.py:40-48)
 // Two instantiations share the grid: CAP = SH_SMALLSEG (17.5 KB of LDS, 8 workgroups = every wave slot of a CU) takes the planes
@@ -285,12 +364,14 @@ __device__ inline uint32_t hash_key64(unsigned long long k) {
 // cavities) is handed to the overflow tier's join (k_ovf.h: loop tables of 1 024 entries): listed (ManyLoops), given pool ranges by
 // k_ovf_plan_loops.  With that tier skipped for a resident batch (no list): `missed` tells sh_collect to run again with it.
 
-template <int CAP>
+// OPEN: the kernels of bridge mode (k_open.h).  The default mode launches OPEN = false, whose code is the join without them.
+template <int CAP, bool OPEN>
 __device__ inline void slice_link_plane(const int pl, int N, const int* __restrict__ seg_count, const Seg* __restrict__ segs,
              const double* __restrict__ vobb, const long long* __restrict__ voff, const double* __restrict__ zeff,
              double* __restrict__ centroids, double* __restrict__ areas, int* __restrict__ nloops,
              int* __restrict__ ring_n, double* __restrict__ ring /*nullable*/, int select, int* __restrict__ err,
-             double* __restrict__ areas_total /*nullable: |sum of the signed loop areas| = Path2D.area*/, ManyLoops many, int* __restrict__ nlarge = nullptr) {
+             double* __restrict__ areas_total /*nullable: |sum of the signed loop areas| = Path2D.area*/, ManyLoops many, const OpenCfg oc,
+             int* __restrict__ nlarge = nullptr) {
   // LDS per plane decides how many planes a CU joins at once (the join is a chain of short dependent steps): 44 bytes per
   // segment.  bufB holds the hash table until the label ping-pong starts; the crossing points stay in HBM (read twice, L2 hits).
   constexpr int HASH = CAP <= 384 ? 512 : 2048;
@@ -326,7 +407,7 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     bufA[i] = ((unsigned long long)s.e_lo << 32) | s.e_hi;
   }
   __syncthreads();
-  if (n < 3) {
+  if (n < 3 && !(OPEN && n > 0)) {      // (bridged, two segments can make a ring of three)
     if (tid == 0) {
       centroids[2 * (size_t)pl] = 0; centroids[2 * (size_t)pl + 1] = 0; areas[pl] = 0; nloops[pl] = 0; ring_n[pl] = 0;
       if (areas_total) areas_total[pl] = 0;      // an empty section of the area scan is legal (plane past a ragged cut)
@@ -351,6 +432,25 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     nxt[i] = found;
   }
   __syncthreads();
+  // Open contours, bridge mode (k_open.h): only a plane with a dead end goes this way.  The scratch is what the jumping below
+  // initialises anew -- jmpA (chain ends, matches), jmpB (counters), offB (predecessor counts), bufB (the hash table: end points).
+  const bool bridging = OPEN && (bad || n < 3);      // (uniform; fewer than three segments without a dead end: a cycle of one or two)
+  int n2 = n;                                     // nodes of the graph: the segments, then the bridges
+  if (bridging) {
+    constexpr int E = SH_MAXLOOPS;
+    double* pts = (double*)bufB;
+    n2 = bridge_open_chains<SH_LINK_THREADS>(n, CAP, E, skey, bufA, nxt, offB, jmpB, jmpA, jmpA + E, jmpA + 2 * E, jmpA + 3 * E, jmpA + 4 * E,
+                                             jmpA + 5 * E, pts, pts + E, pts + 2 * E, pts + 3 * E, vb, zpl, oc.max_gap);
+    if (n2 < 0) {      // more chain ends than one wave matches, or no room for the bridges: the overflow tier's join takes the plane
+      if (tid == 0) {
+        if (many.list) many.list[atomicAdd(many.n, 1)] = pl;
+        else if (many.missed) atomicExch(many.missed, 1ull);
+        else atomicExch(&err[b], SH_ERR_CAPACITY_DEV);
+      }
+      return;
+    }
+    if (tid == 0) bad = 0;      // (every lane has read it: bridge_open_chains has barriers)
+  }
   // One pointer-jumping pass gives both what the walk needs (round 2; two passes before: labels, then ranks): every node carries,
   // for the stretch of 2^k successors starting at itself, the smallest start key on it and the distance to that key's node.
   // Joining a stretch with the one behind it keeps the smaller key (its own on a tie: a stretch longer than the loop meets
@@ -360,10 +460,10 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
   unsigned long long* labB = bufB;
   int* ja = jmpA; int* jb = jmpB;
   int* ra = offA; int* rb = offB;
-  for (int i = tid; i < n; i += SH_LINK_THREADS) { labA[i] = skey[i]; ja[i] = nxt[i]; ra[i] = 0; }
+  for (int i = tid; i < n2; i += SH_LINK_THREADS) { labA[i] = skey[i]; ja[i] = nxt[i]; ra[i] = 0; }
   __syncthreads();
-  for (int span = 1; span < n; span <<= 1) {
-    for (int i = tid; i < n; i += SH_LINK_THREADS) {
+  for (int span = 1; span < n2; span <<= 1) {
+    for (int i = tid; i < n2; i += SH_LINK_THREADS) {
       const int j = ja[i];
       const unsigned long long a = labA[i], c = labA[j];
       const bool own = a <= c;
@@ -376,9 +476,10 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     int* tj = ja; ja = jb; jb = tj;
     int* tr = ra; ra = rb; rb = tr;
   }
-  // labA[i] = start key of i's loop, ra[i] = forward steps from i to the start node (0: i is a start node)
-  for (int i = tid; i < n; i += SH_LINK_THREADS)
-    if (ra[i] == 0) {
+  // labA[i] = start key of i's loop, ra[i] = forward steps from i to the start node (0: i is a start node).  Bridging: ja[i] has
+  // saturated at the tail of i's chain if i is on one (the tail keeps its self-loop), and a cycle of fewer than three is no loop.
+  for (int i = tid; i < n2; i += SH_LINK_THREADS)
+    if (ra[i] == 0 && (!bridging || (nxt[ja[i]] != ja[i] && ra[nxt[i]] >= 2))) {
       int l = atomicAdd(&n_loops, 1);
       if (l < SH_MAXLOOPS) l_start[l] = i;
     }
@@ -406,9 +507,28 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
       l_len[l] = L; l_off[l] = off; off += L;
       l_key[l] = skey[s];
     }
-    if (off != n) bad = 1;        // some segments are on no closed loop
+    if (off != n && !bridging) bad = 1;        // some segments are on no closed loop
   }
   __syncthreads();
+  if (bridging) {
+    // chains bridged / dropped: every chain has one tail (a segment without a successor of its own: self-loop or bridge)
+    if (oc.stats)
+      for (int i = tid; i < n; i += SH_LINK_THREADS)
+        if (nxt[i] == i || nxt[i] >= n) {
+          bool kept = false;
+          for (int q = 0; q < nl; ++q) kept |= l_key[q] == labA[i];
+          atomicAdd(&oc.stats[2 * b + (kept ? 0 : 1)], 1);
+        }
+    if (nl == 0) {      // nothing left: as a section without segments
+      if (tid == 0) {
+        centroids[2 * (size_t)pl] = 0; centroids[2 * (size_t)pl + 1] = 0; areas[pl] = 0; nloops[pl] = 0; ring_n[pl] = 0;
+        if (areas_total) areas_total[pl] = 0;
+        else atomicCAS(&err[b], 0, SH_ERR_GEOMETRY_DEV);
+      }
+      return;
+    }
+    __syncthreads();      // (labA is the ring's x from here on)
+  }
   // ring placement: position from start = (L - r) mod L
   // label buffers are dead from here on: reuse them for the ordered ring
   double* rx = (double*)bufA;
@@ -416,7 +536,7 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
   int my_pos[(CAP + SH_LINK_THREADS - 1) / SH_LINK_THREADS];
   {
     int c = 0;
-    for (int i = tid; i < n; i += SH_LINK_THREADS, ++c) {
+    for (int i = tid; i < n2; i += SH_LINK_THREADS, ++c) {
       const unsigned long long key = labA[i];
       int l = -1;
       for (int q = 0; q < nl; ++q) if (l_key[q] == key) { l = q; break; }      // (one or two loops per section)
@@ -429,8 +549,11 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
   __syncthreads();
   {
     int c = 0;
-    for (int i = tid; i < n; i += SH_LINK_THREADS, ++c)
-      if (my_pos[c] >= 0 && my_pos[c] < n) { const Seg sg = sp[i]; seg_start_point(vb, sg.s_lo, sg.s_hi, zpl, &rx[my_pos[c]], &ry[my_pos[c]]); }
+    for (int i = tid; i < n2; i += SH_LINK_THREADS, ++c)
+      if (my_pos[c] >= 0 && my_pos[c] < n2) {
+        if (!OPEN || i < n) { const Seg sg = sp[i]; seg_start_point(vb, sg.s_lo, sg.s_hi, zpl, &rx[my_pos[c]], &ry[my_pos[c]]); }
+        else { const unsigned long long kv = skey[i]; seg_start_point(vb, (uint32_t)(kv >> 32), (uint32_t)kv, zpl, &rx[my_pos[c]], &ry[my_pos[c]]); }      // a bridge
+      }
   }
   __syncthreads();
   // AABB over every loop vertex (trimesh Path2D.centroid, slice.py:38) by the last wave, while the other three take the loops
@@ -438,9 +561,10 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
   // The ordered ring in LDS holds every crossing point once -- min / max do not care about the order; a section with
   // segments on no closed loop is flagged above and its numbers are void anyway.
   const int lane = tid & 63, wave = tid >> 6;
+  const int nv = bridging ? l_off[nl - 1] + l_len[nl - 1] : n;      // ring vertices placed (bridging: the loops' only)
   if (wave == SH_LINK_THREADS / 64 - 1) {
     double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
-    for (int i = lane; i < n; i += 64) {
+    for (int i = lane; i < nv; i += 64) {
       const double qx = rx[i], qy = ry[i];
       x0 = fmin(x0, qx); x1 = fmax(x1, qx); y0 = fmin(y0, qy); y1 = fmax(y1, qy);
     }
@@ -508,6 +632,7 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
 
 // small tier: one workgroup per plane.  Large tier: a small grid sweeps all planes and works on the few (usually none)
 // with more than SH_SMALLSEG segments -- a workgroup per plane would pay its 70 KB LDS allocation 40 000 times for nothing.
+template <bool OPEN>
 __global__ void __launch_bounds__(SH_LINK_THREADS)
 k_slice_link(SliceSets sets, int B, int* __restrict__ err) {
   // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 names a group of workgroups that share an L2): with the batch a
@@ -519,9 +644,10 @@ k_slice_link(SliceSets sets, int B, int* __restrict__ err) {
   const int b = id / ntot, kk = id - b * ntot;
   const int si = kk >= sets.s[0].N ? 1 : 0;
   const SliceSetDev& S = sets.s[si];
-  slice_link_plane<SH_SMALLSEG>(b * S.N + (kk - (si ? sets.s[0].N : 0)), S.N, S.seg_count, S.segs, sets.vobb, sets.voff, S.zeff, S.centroids, S.areas, S.nloops, S.ring_n,
-                                S.ring, S.select, err, S.areas_total, S.many, S.nlarge);
+  slice_link_plane<SH_SMALLSEG, OPEN>(b * S.N + (kk - (si ? sets.s[0].N : 0)), S.N, S.seg_count, S.segs, sets.vobb, sets.voff, S.zeff, S.centroids, S.areas, S.nloops, S.ring_n,
+                                S.ring, S.select, err, S.areas_total, S.many, sets.open, S.nlarge);
 }
+template <bool OPEN>
 __global__ void __launch_bounds__(SH_LINK_THREADS)
 k_slice_link_large(SliceSets sets, int B, int* __restrict__ err) {
   for (int si = 0; si < sets.n; ++si) {
@@ -535,7 +661,7 @@ k_slice_link_large(SliceSets sets, int B, int* __restrict__ err) {
       const int cnt = S.seg_count[pl];
       if (cnt > SH_MAXSEG && S.ovf_missed && threadIdx.x == 0) atomicExch(S.ovf_missed, 1ull);
       if (cnt <= SH_SMALLSEG || cnt > SH_MAXSEG) continue;
-      slice_link_plane<SH_MAXSEG>(pl, S.N, S.seg_count, S.segs, sets.vobb, sets.voff, S.zeff, S.centroids, S.areas, S.nloops, S.ring_n, S.ring, S.select, err, S.areas_total, S.many);
+      slice_link_plane<SH_MAXSEG, OPEN>(pl, S.N, S.seg_count, S.segs, sets.vobb, sets.voff, S.zeff, S.centroids, S.areas, S.nloops, S.ring_n, S.ring, S.select, err, S.areas_total, S.many, sets.open);
       __syncthreads();
     }
   }

@@ -15,6 +15,7 @@
 
 #include "k_slices.h"
 #include "k_ovf.h"
+#include "k_open.h"
 #include "k_stages.h"
 #include "k_groove.h"
 #include "k_anp.h"
@@ -102,6 +103,11 @@ struct sh_ctx {
   // a run of the resident batch that planned no overflow plane in any set (ctr[4] == 0 at collect) lets later runs of the SAME batch
   // and parameters skip the overflow tier's launches (they would all return at once: ~17 launches, ~60 us per step)
   unsigned long long ovf_none_gen = ~0ull;
+  // sh_set_open_contours (k_open.h): SH_OPEN_ERROR / SH_OPEN_BRIDGE and the largest gap bridged (mm); open_stats_run: the mode of the
+  // last sh_submit ("open.stats" is cleared, and counts, only in bridge mode)
+  int open_mode = SH_OPEN_ERROR;
+  double open_gap = SH_OPEN_GAP_DEFAULT;
+  int open_stats_run = SH_OPEN_ERROR;
   int end_cap = SH_ENDCAP;                   // points per end section "obb.endpts" holds (grown by sh_collect like the pools)
   unsigned long long obb_gen = ~0ull;        // the batch generation the three fields below belong to
   HullCap hcap = {SH_HV, SH_HF, SH_HE};      // per-humerus capacity (= stride) of the hull record and the per-face obb.* arrays; a batch with a larger
@@ -517,6 +523,7 @@ static int alloc_batch(sh_ctx* c) {
   ENS("z_bounds", B * 2 * 8, 8);
   ENS("z_length", B * 8, 8);
   ENS("err", B * 4, 4);
+  ENS("open.stats", B * 2 * 4, 4);          // chains bridged / dropped per humerus (sh_open_contour_stats)
   ENS("neck_z", B * 8, 8);
   ENS("neck_index", B * 4, 4);
   ENS("canal.points_obb", B * SH_CANAL_MAXPTS * 3 * 8, 8);
@@ -1573,6 +1580,7 @@ static int ovf_pools(sh_ctx* c, OvfPools* P) {
   P->segs = (Seg*)c->bufs["ovf.segs"].p; P->ring = (double*)c->bufs["ovf.ring"].p; P->work = (unsigned char*)c->bufs["ovf.work"].p;
   P->seg_cap = c->ovf_seg_cap; P->ring_cap = c->ovf_ring_cap; P->work_cap = c->ovf_work_cap;
   P->ctr = (unsigned long long*)c->bufs["ovf.ctr"].p;
+  P->open_mode = c->open_mode;
   return SH_OK;
 }
 // the plan arrays of slice set `pfx` (N planes per humerus), window-relative like every [B][...] buffer
@@ -1610,6 +1618,7 @@ static int run_slice_sets(sh_ctx* c, const SliceSpec* specs, int nspec) {
   SliceSets sets{};
   sets.n = nspec;
   sets.vobb = buf<double>(c, "verts_obb"); sets.voff = buf<long long>(c, "voff");
+  sets.open = OpenCfg{c->open_mode, c->open_gap, c->open_mode ? buf<int>(c, "open.stats") : (int*)nullptr};
   for (int i = 0; i < nspec; ++i) {
     const SliceSpec& sp = specs[i];
     const std::string p = sp.pfx;
@@ -1644,15 +1653,25 @@ static int run_slice_sets(sh_ctx* c, const SliceSpec* specs, int nspec) {
              buf<long long>(c, "foff"), (const double*)S.zeff, S.N, OP, OS[i]);
     }
   // two capacity tiers share the grid (k_slices.h): the planes of the other tier exit at once
-  LAUNCH(c, "k_slice_link", k_slice_link, dim3(B * ntot), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
-  LAUNCH(c, "k_slice_link_large", k_slice_link_large, dim3(std::min(B * ntot, 512)), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
+  // (bridge mode: the joins with the open-contour code, k_open.h; the default mode's joins are built without it)
+  if (c->open_mode != SH_OPEN_ERROR) {
+    LAUNCH(c, "k_slice_link", k_slice_link<true>, dim3(B * ntot), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
+    LAUNCH(c, "k_slice_link_large", k_slice_link_large<true>, dim3(std::min(B * ntot, 512)), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
+  } else {
+    LAUNCH(c, "k_slice_link", k_slice_link<false>, dim3(B * ntot), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
+    LAUNCH(c, "k_slice_link_large", k_slice_link_large<false>, dim3(std::min(B * ntot, 512)), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
+  }
   for (int i = 0; i < nspec; ++i) {
     const SliceSpec& sp = specs[i];
     const SliceSetDev& S = sets.s[i];
     if (ovf_on) {
       LAUNCH(c, "k_ovf_plan_loops", k_ovf_plan_loops, dim3(16), dim3(256), S.N, (const int*)S.seg_count, (const Seg*)S.segs, OP, OS[i], buf<int>(c, "err"));
-      LAUNCH(c, "k_slice_link_huge", k_slice_link_huge, dim3(64), dim3(SH_HUGE_THREADS), S.N, (const int*)S.seg_count, OP, OS[i], S.centroids, S.areas, S.nloops, S.ring_n,
-             sp.ring ? 1 : 0, S.select, buf<int>(c, "err"), S.areas_total, (const double*)buf<double>(c, "verts_obb"), (const long long*)buf<long long>(c, "voff"), (const double*)S.zeff);
+      if (c->open_mode != SH_OPEN_ERROR)
+        LAUNCH(c, "k_slice_link_huge", k_slice_link_huge<true>, dim3(64), dim3(SH_HUGE_THREADS), S.N, (const int*)S.seg_count, OP, OS[i], S.centroids, S.areas, S.nloops, S.ring_n,
+             sp.ring ? 1 : 0, S.select, buf<int>(c, "err"), S.areas_total, (const double*)buf<double>(c, "verts_obb"), (const long long*)buf<long long>(c, "voff"), (const double*)S.zeff, sets.open);
+      else
+        LAUNCH(c, "k_slice_link_huge", k_slice_link_huge<false>, dim3(64), dim3(SH_HUGE_THREADS), S.N, (const int*)S.seg_count, OP, OS[i], S.centroids, S.areas, S.nloops, S.ring_n,
+             sp.ring ? 1 : 0, S.select, buf<int>(c, "err"), S.areas_total, (const double*)buf<double>(c, "verts_obb"), (const long long*)buf<long long>(c, "voff"), (const double*)S.zeff, sets.open);
     }
     if (sp.resample) {
       RsWant want{c->keep_products ? 1 : 0, SH_ANP_ROW0, 0, 0};
@@ -2826,6 +2845,7 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const std::string& tslot
     HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hull.ne") + b, &counts[2], 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hulld.skip") + b, &one, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(buf<int>(c, "err") + b, 0, 4, c->stream));
+    if (c->open_mode != SH_OPEN_ERROR) HIPCHK(c, hipMemsetAsync(buf<int>(c, "open.stats") + 2 * (size_t)b, 0, 8, c->stream));      // (the void first pass counted too)
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the sources above are locals
     c->skip_nfmax = std::max(c->skip_nfmax, fn);
     c->b0 = b; c->Bwin = 1; c->redo_records = true; c->redo_nf = fn;
@@ -2915,6 +2935,8 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
     if (prc != SH_OK) return prc;
   }
   { OvfPools OP; int orc = ovf_pools(c, &OP); if (orc != SH_OK) return orc; FILL(c, {buf<int>(c, "err"), (size_t)B * 4, 0}, {OP.ctr, 128, 0}); }      // overflow pools: empty, no demand recorded
+  if (c->open_mode != SH_OPEN_ERROR) FILL(c, {buf<int>(c, "open.stats"), (size_t)B * 8, 0});      // (bridge mode only: the default run has no extra fill)
+  c->open_stats_run = c->open_mode;
   if ((mask & SH_STAGE_APPLY) && !(mask & SH_STAGE_CSYS)) return fail(c, SH_ERR_ARG, "sh_run: SH_STAGE_APPLY needs SH_STAGE_CSYS in the same run");
   // a proximal humerus' frame is canal / articular (bone.py:53-62): k_pack builds it from the anatomic-neck axes of THIS run
   if (c->params.bone_kind == SH_BONE_PROXIMAL && (mask & SH_STAGE_CSYS) && !(mask & SH_STAGE_ANP))
@@ -3117,6 +3139,80 @@ int sh_set_keep_products(sh_ctx* c, int on) {
   if (!c) return SH_ERR_ARG;
   if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_set_keep_products: runs are in flight");
   c->keep_products = on != 0;
+  return SH_OK;
+}
+
+// ---- open contours (k_open.h) ---------------------------------------------------------------------------
+int sh_set_open_contours(sh_ctx* c, int mode, double max_gap) {
+  if (!c) return SH_ERR_ARG;
+  if (mode != SH_OPEN_ERROR && mode != SH_OPEN_BRIDGE) return fail(c, SH_ERR_ARG, "sh_set_open_contours: mode is SH_OPEN_ERROR or SH_OPEN_BRIDGE");
+  if (!std::isfinite(max_gap) || max_gap < 0.0) return fail(c, SH_ERR_ARG, "sh_set_open_contours: max_gap must be finite and >= 0");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_set_open_contours: runs are in flight");
+  c->open_mode = mode; c->open_gap = max_gap;
+  return SH_OK;
+}
+int sh_get_open_contours(const sh_ctx* c, int* mode, double* max_gap) {
+  if (!c) return SH_ERR_ARG;
+  if (mode) *mode = c->open_mode;
+  if (max_gap) *max_gap = c->open_gap;
+  return SH_OK;
+}
+int sh_open_contour_stats(sh_ctx* c, int32_t* bridged, int32_t* dropped) {
+  if (!c || !bridged || !dropped) return fail(c, SH_ERR_ARG, "sh_open_contour_stats: bad argument");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_open_contour_stats: no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_open_contour_stats: runs are in flight (sh_collect them first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<int32_t> h((size_t)c->B * 2, 0);
+  if (c->open_stats_run != SH_OPEN_ERROR) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(h.data(), c->bufs["open.stats"].p, h.size() * 4, hipMemcpyDeviceToHost));
+  }
+  for (int b = 0; b < c->B; ++b) { bridged[b] = h[2 * (size_t)b]; dropped[b] = h[2 * (size_t)b + 1]; }
+  return SH_OK;
+}
+int sh_mesh_open_edges(sh_ctx* c, int64_t* out) {
+  if (!c || !out) return fail(c, SH_ERR_ARG, "sh_mesh_open_edges: bad argument");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_mesh_open_edges: no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_mesh_open_edges: runs are in flight (sh_collect them first)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B;
+  std::vector<long long> toff((size_t)B + 1, 0);      // per mesh a power of two >= 4 F_b slots (k_edge_insert)
+  for (int b = 0; b < B; ++b) {
+    const long long nf = c->h_foff[b + 1] - c->h_foff[b];
+    long long t = 64;
+    while (t < 4 * nf) t <<= 1;
+    toff[b + 1] = toff[b] + t;
+  }
+  int rc;
+  if ((rc = ensure(c, "open.ekeys", (size_t)toff[B] * 8, 8)) != SH_OK) return rc;
+  if ((rc = ensure(c, "open.euses", (size_t)toff[B] * 4, 4)) != SH_OK) return rc;
+  if ((rc = ensure(c, "open.etoff", ((size_t)B + 1) * 8, 8)) != SH_OK) return rc;
+  if ((rc = ensure(c, "open.ecount", (size_t)B * 8, 8)) != SH_OK) return rc;
+  for (const char* n : {"open.ekeys", "open.euses", "open.etoff", "open.ecount"}) c->bufs[n].per_mesh = 0;
+  unsigned long long* keys = (unsigned long long*)c->bufs["open.ekeys"].p;
+  int* uses = (int*)c->bufs["open.euses"].p;
+  long long* dtoff = (long long*)c->bufs["open.etoff"].p;
+  unsigned long long* cnt = (unsigned long long*)c->bufs["open.ecount"].p;
+  HIPCHK(c, hipMemcpyAsync(dtoff, toff.data(), toff.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(keys, 0xFF, (size_t)toff[B] * 8, c->stream));
+  HIPCHK(c, hipMemsetAsync(uses, 0, (size_t)toff[B] * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(cnt, 0, (size_t)B * 8, c->stream));
+  const int b0 = c->b0; c->b0 = 0;      // (whole batch)
+  LAUNCH(c, "k_edge_insert", k_edge_insert, dim3((unsigned)std::min<long long>((c->maxF + 255) / 256, 1024), (unsigned)B), dim3(256),
+         (const int*)c->bufs["faces"].p, (const long long*)c->bufs["foff"].p, (const long long*)dtoff, keys, uses);
+  long long tmax = 0;
+  for (int b = 0; b < B; ++b) tmax = std::max(tmax, toff[b + 1] - toff[b]);
+  LAUNCH(c, "k_edge_count_open", k_edge_count_open, dim3((unsigned)std::min<long long>((tmax + 255) / 256, 1024), (unsigned)B), dim3(256),
+         (const long long*)dtoff, (const unsigned long long*)keys, (const int*)uses, cnt);
+  c->b0 = b0;
+  std::vector<unsigned long long> h((size_t)B);
+  HIPCHK(c, hipMemcpyAsync(h.data(), cnt, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int b = 0; b < B; ++b) out[b] = (int64_t)h[b];
+  for (const char* n : {"open.ekeys", "open.euses", "open.etoff", "open.ecount"}) {      // on demand: the tables (12 B per slot) do not stay
+    auto it = c->bufs.find(n);
+    if (it != c->bufs.end()) { if (it->second.p) (void)hipFree(it->second.p); c->bufs.erase(it); }
+  }
   return SH_OK;
 }
 

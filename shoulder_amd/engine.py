@@ -73,6 +73,43 @@ class Engine:
         if rc != 0:
             raise ShoulderHipError(rc, self.L.sh_last_error(self.h).decode())
 
+    def _chk_records(self, rc, out, strict):
+        """strict=False: a return code that some record's `status` carries is that humerus' failure, not the batch's -- the
+        records come back and `status` says which humeri failed.  Anything else (context-level errors) raises."""
+        if rc == 0 or strict or out is None or "status" not in (out.dtype.names or ()) or not np.any(out["status"] == rc):
+            self._chk(rc)
+
+    # ---- open contours (include/shoulder_hip.h sh_set_open_contours) ------------------------------------------------
+    _OPEN_MODES = {"error": _lib.OPEN_ERROR, "bridge": _lib.OPEN_BRIDGE}
+
+    def set_open_contours(self, mode="error", max_gap=_lib.OPEN_GAP_DEFAULT):
+        """mode "error" (default): an open section fails its humerus (SH_ERR_GEOMETRY); "bridge": chain gaps up to max_gap mm
+        are bridged, segments on no loop dropped."""
+        if mode not in self._OPEN_MODES:
+            raise ValueError(f'open contour mode is "error" or "bridge", not {mode!r}')
+        gap = float(max_gap)
+        if not np.isfinite(gap) or gap < 0:
+            raise ValueError(f"max_gap must be finite and >= 0, not {max_gap!r}")
+        self._chk(self.L.sh_set_open_contours(self.h, self._OPEN_MODES[mode], gap))
+
+    def get_open_contours(self):
+        """(mode, max_gap) of the next run."""
+        m, g = ctypes.c_int(), ctypes.c_double()
+        self._chk(self.L.sh_get_open_contours(self.h, ctypes.byref(m), ctypes.byref(g)))
+        return {v: k for k, v in self._OPEN_MODES.items()}[m.value], g.value
+
+    def open_contour_stats(self):
+        """Per humerus of the last run: (bridged, dropped) open chains, two int32 arrays (zeros after an "error"-mode run)."""
+        br, dr = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+        self._chk(self.L.sh_open_contour_stats(self.h, _ptr(br), _ptr(dr)))
+        return br, dr
+
+    def open_edges(self):
+        """Per resident mesh: undirected edges used by a number of faces other than two (0: watertight), int64."""
+        out = np.zeros(self.B, np.int64)
+        self._chk(self.L.sh_mesh_open_edges(self.h, _ptr(out)))
+        return out
+
     # ---- parameters ----------------------------------------------------------------------------
     def load_rfc(self, npz_path=None):
         z = np.load(npz_path or os.path.join(_MODELS, "rfc_bg3.npz"))
@@ -254,14 +291,15 @@ class Engine:
         return out[: n.value]
 
     # ---- run ---------------------------------------------------------------------------------------
-    def run(self, stages=_lib.STAGE_ALL, fetch=True):
+    def run(self, stages=_lib.STAGE_ALL, fetch=True, strict=True):
         """One sh_run over the resident batch.  fetch=True: a fresh record array; fetch="view": the engine's page-locked
-        record buffer (no allocation, direct D2H), valid until the next run; fetch=False: records stay on the device."""
+        record buffer (no allocation, direct D2H), valid until the next run; fetch=False: records stay on the device.
+        strict=False: humeri that failed do not raise, their records' `status` says so (needs fetched records)."""
         if fetch == "view":
             out = self._pinned_records()
         else:
             out = np.zeros(self.B, dtype=self.record_dtype) if fetch else None
-        self._chk(self.L.sh_run(self.h, int(stages), _ptr(out) if out is not None else None))
+        self._chk_records(self.L.sh_run(self.h, int(stages), _ptr(out) if out is not None else None), out, strict)
         return out
 
     def submit(self, stages=_lib.STAGE_ALL, fetch="view", out_ptr=None):
@@ -286,9 +324,9 @@ class Engine:
             self._inflight.pop()
             raise
 
-    def collect(self):
+    def collect(self, strict=True):
         out = self._inflight.pop(0) if self._inflight else None      # (nothing in flight: sh_collect reports it)
-        self._chk(self.L.sh_collect(self.h))
+        self._chk_records(self.L.sh_collect(self.h), out, strict)
         return out
 
     def _pinned_records(self, slot=0):
