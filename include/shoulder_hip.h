@@ -291,6 +291,62 @@ int  sh_slice_mesh_planes(sh_ctx*, const double* verts /* nv x 3 */, int nv, con
                           double* out_verts /* P x cap_v x 3 */, int cap_v, int32_t* out_faces /* P x cap_f x 3 */, int cap_f,
                           int32_t* out_edges /* P x cap_e x 2 */, int cap_e, int32_t* counts /* P x 3 */);
 
+/* ---- batched head resection: B resident humeri x P planes in one device pass ----------------------------------------
+ * `HumeralHeadOsteotomy` (arthroplasty.py:13-175) for a cohort: what a planning sweep reads off a cut -- the cut contour, its
+ * area, the volume and height of the resected head -- as one fixed-size record per (humerus, plane), from the vertices and
+ * faces that are resident on the device (nothing is uploaded again, no mesh comes back).  The mesh of a humerus is read once
+ * for all of its P planes (k_resect.h).  Records and rings are reproducible bit for bit and do not depend on the batch a
+ * humerus is measured in, its position there or P (per-tile partial sums stored and added in a fixed order, no float atomics).
+ *
+ * Cut semantics are sh_slice_mesh_planes' (`Trimesh.slice_plane`, arthroplasty.py:80-87; oracle/clip.py): sign of a vertex
+ * with tolerance 1e-8 on dot(v - point, normal) -- the normal is used AS GIVEN, not rescaled, like trimesh does -- class of a
+ * face from its three signs, crossing point a + (num / den) d per face edge, faces lying in the plane decided by their own
+ * normal.  The section is joined on mesh-edge keys (a crossing that is a mesh vertex, |dot| <= 1e-8: on that vertex' id); of two
+ * faces that compute the crossing of one edge the one `slice_plane`'s vertex merge keeps is taken.  Meshes are taken to be
+ * consistently oriented, as everywhere in the slice layer.
+ *   status SH_ERR_GEOMETRY  a section with an open chain / a vertex used by other than two segments (`points()` would not get
+ *                           closed loops from it); the face sums (head_*, n_cut_faces) stay valid, ring fields are zero.  Resection
+ *                           contours are not bridged (sh_set_open_contours does not apply here).
+ *   status SH_ERR_CAPACITY  a section with more than 1 024 crossing segments (SH_MAXSEG) or more than 32 loops: NOT joined through
+ *                           the overflow pool; the face sums stay valid, ring fields are zero.  Never a wrong ring, never a failed batch. */
+typedef struct sh_cut_offset {          /* one planned cut relative to a humerus' native anatomic-neck plane; applied in this order: */
+  double retroversion_deg;              /* HumeralHeadOsteotomy.offset_retroversion   (arthroplasty.py:90-104)   */
+  double neckshaft_deg;                 /* .offest_neckshaft                          (:106-118)                 */
+  double depth_canal_mm, depth_anp_mm, depth_resection_mm;   /* .offset_depth(mm, "canal" / "anp" / "resection") (:120-145) */
+  double anterior_mm;                   /* .offset_anterior_posterior                 (:147-162)                 */
+  double medial_mm;                     /* .offset_medial_lateral                     (:164-175)                 */
+} sh_cut_offset;                        /* a field that is exactly 0 is a call that is not made: all zeros = the native plane (into the csys and back) */
+
+typedef struct sh_resection {           /* one (humerus, plane); CT coordinates */
+  double plane_point[3], plane_normal[3];  /* the plane that was cut; the normal as it was cut with (sh_resect_offsets: unit up to
+                                              rounding, sh_resect_planes: the caller's) -- feeding them back gives the same record */
+  double head_volume;    /* mm^3: sum over the faces of the normal's side, cut faces re-triangulated as slice_plane does, of
+                            det(a-o, b-o, c-o)/6 about o = plane_point -- the flat cap contributes nothing about o */
+  double head_area;      /* mm^2: area of those faces (no cap) */
+  double head_height;    /* mm: largest distance dot(v - o, n) / |n| of a vertex of a face from the plane on the normal's side; 0 if none */
+  double cut_area, cut_perimeter, cut_centroid[3];  /* of the LARGEST loop (= points(), arthroplasty.py:69-78): |shoelace area| in
+                            base.Section's in-plane basis (u = n x e_x, or n x e_y when |n_x| >= 0.9, normalised; w = n x u) with
+                            coordinates taken about o; length of the closed ring; area centroid of the polygon */
+  double cap_area;       /* |sum of the signed areas of all loops| (outer loops minus holes) */
+  int32_t n_loops, n_ring, n_cut_faces, status;     /* loops; vertices of the largest (open count); faces the plane cuts;
+                                                       0 or a negative sh_status for this cut */
+} sh_resection;
+
+/* P explicit planes per humerus.  Needs a resident batch only (no run).  P in 1..4096; a zero or non-finite normal or a
+ * non-finite point: SH_ERR_ARG.  Not while runs are in flight (SH_ERR_STATE).  One device-to-host copy of the B x P records. */
+int sh_resect_planes (sh_ctx*, const double* planes /* B x P x (point, normal), CT */, int P, sh_resection* out /* B x P, host */);
+/* The same P offsets for every humerus; the plane of cut p of humerus b is built ON THE DEVICE from b's record of the last run
+ * (anp_plane_*, csys_articular, side): what a fresh HumeralHeadOsteotomy of that humerus gives after the calls named in
+ * sh_cut_offset, in that order, mapped back to CT (sh_scalar.h resect_plane_from_offsets; oracle/osteotomy.py).  Needs a
+ * collected run of the resident batch that included SH_STAGE_ANP and SH_STAGE_CSYS (SH_ERR_STATE otherwise).  A humerus whose
+ * record has status != 0 gets that status in all of its cuts (other fields zero); the batch does not fail.  Both bone kinds. */
+int sh_resect_offsets(sh_ctx*, const sh_cut_offset* offs /* P, the same for every humerus */, int P, sh_resection* out /* B x P, host */);
+/* The largest loop of cut p of humerus b of the last sh_resect_*: n_ring + 1 points, CT, closed (first = last), counter-clockwise
+ * seen from the tip of the normal, starting at the crossing on the mesh edge with the smallest (min vid, max vid) key (rule B-1).
+ * The cut is joined again for the call (the batch's rings are not kept: 24 KB per cut).  out == NULL or cap < n + 1: only
+ * *n_out = n + 1 is set; a cut without a ring (status != 0, no loop): *n_out = 0. */
+int sh_resect_ring   (sh_ctx*, int b, int p, double* out /* cap x 3, CT */, int cap, int* n_out);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

@@ -70,6 +70,31 @@ def record_dtype(anp_rows=0):
     return np.dtype(fields)
 
 
+class CutOffset(ctypes.Structure):
+    """sh_cut_offset: one planned cut relative to the native anatomic-neck plane (arthroplasty.py:90-175)."""
+    _fields_ = [(n, ctypes.c_double) for n in ("retroversion_deg", "neckshaft_deg", "depth_canal_mm", "depth_anp_mm",
+                                               "depth_resection_mm", "anterior_mm", "medial_mm")]
+
+
+CUT_OFFSET_DTYPE = np.dtype([(n, "<f8") for n, _ in CutOffset._fields_])
+assert CUT_OFFSET_DTYPE.itemsize == ctypes.sizeof(CutOffset)
+
+
+class Resection(ctypes.Structure):
+    """sh_resection: the measurements of one (humerus, plane) cut."""
+    _fields_ = [("plane_point", ctypes.c_double * 3), ("plane_normal", ctypes.c_double * 3), ("head_volume", ctypes.c_double),
+                ("head_area", ctypes.c_double), ("head_height", ctypes.c_double), ("cut_area", ctypes.c_double),
+                ("cut_perimeter", ctypes.c_double), ("cut_centroid", ctypes.c_double * 3), ("cap_area", ctypes.c_double),
+                ("n_loops", ctypes.c_int32), ("n_ring", ctypes.c_int32), ("n_cut_faces", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+RESECTION_DTYPE = np.dtype([
+    ("plane_point", "<f8", (3,)), ("plane_normal", "<f8", (3,)), ("head_volume", "<f8"), ("head_area", "<f8"), ("head_height", "<f8"),
+    ("cut_area", "<f8"), ("cut_perimeter", "<f8"), ("cut_centroid", "<f8", (3,)), ("cap_area", "<f8"),
+    ("n_loops", "<i4"), ("n_ring", "<i4"), ("n_cut_faces", "<i4"), ("status", "<i4")])
+assert RESECTION_DTYPE.itemsize == ctypes.sizeof(Resection)
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -82,7 +107,8 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_stage_meshes", "sh_stage_stl", "sh_commit_staged", "sh_staged", "sh_set_record_rows", "sh_record_bytes", "sh_anp_points",
            "sh_comm_init_all", "sh_bcast_weights", "sh_gather_landmarks", "sh_set_keep_products",
            "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring",
-           "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges"]
+           "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
+           "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring"]
 
 _lib = None
 
@@ -169,5 +195,9 @@ def load(build_if_missing=True):
     L.sh_get_open_contours.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
     L.sh_open_contour_stats.argtypes = [vp, vp, vp]
     L.sh_mesh_open_edges.argtypes = [vp, vp]
+    if not alt or hasattr(L, "sh_resect_planes"):      # (an A/B arm may be an older build: tools/time_resect.py parent)
+        L.sh_resect_planes.argtypes = [vp, vp, ctypes.c_int, vp]
+        L.sh_resect_offsets.argtypes = [vp, vp, ctypes.c_int, vp]
+        L.sh_resect_ring.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     _lib = L
     return L

@@ -89,6 +89,19 @@ class HumeralHeadOsteotomy:
         halves = bone._engine.slice_mesh_planes(bone.vertices, bone.faces, [cut.point, cut.point], [cut.normal, -cut.normal])
         return tuple(Mesh(v, f, bone._engine) for v, f in halves)
 
+    def measure(self) -> dict:
+        """What a planning sweep reads off the current cut, from the mesh resident on the device (sh_resect_planes with
+        B = P = 1; nothing is uploaded, no mesh comes back): `head_volume`, `head_area`, `head_height`, `cut_area`,
+        `cut_perimeter`, `cut_centroid`, `cap_area`, `n_loops`, `n_ring`, `n_cut_faces`, `status` and the plane that was cut,
+        all in CT (the plane is mapped there through the inverse of the humerus' current matrix).  The reference has no
+        accessor for these; its users call trimesh on `resect_mesh()`'s result."""
+        cut = self.plane
+        bone = self._humerus
+        p, n = transform_plane_pn(cut.point, cut.normal, inv_transform(np.array(bone._tfrm.matrix, dtype=np.float64)))
+        bone._ensure_loaded()
+        rec = bone._engine.resect(planes=np.concatenate([p, n]).reshape(1, 1, 6))[0, 0]
+        return {k: (rec[k].copy() if rec[k].ndim else rec[k].item()) for k in rec.dtype.names}
+
     # ---- offsets (arthroplasty.py:89-175) ------------------------------------------------------------------
     def offset_retroversion(self, deg: float) -> None:
         """more retroversion for positive `deg` (the azimuth decreases on a left humerus, increases on a right one)"""

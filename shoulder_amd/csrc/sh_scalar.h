@@ -692,4 +692,41 @@ SH_HD int clip_halfplane_pieces(const double* pts, int n, double cx, double cy, 
   return npieces;
 }
 
+// ---- HumeralHeadOsteotomy's plane bookkeeping (arthroplasty.py:13-175; oracle/osteotomy.py operation for operation) -------
+// utils.unitxyz_to_spherical (utils.py:321-332): [r, azimuth, polar angle], degrees
+SH_HD void unitxyz_to_spherical(const double* v, double* s) {
+  s[0] = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+  s[1] = atan2(v[1], v[0]) * (180.0 / M_PI);
+  s[2] = acos(v[2] / s[0]) * (180.0 / M_PI);
+}
+// utils.spherical_to_unitxyz (utils.py:333-339)
+SH_HD void spherical_to_unitxyz(const double* s, double* v) {
+  const double th = s[1] * (M_PI / 180.0), ph = s[2] * (M_PI / 180.0);
+  v[0] = s[0] * sin(ph) * cos(th);
+  v[1] = s[0] * sin(ph) * sin(th);
+  v[2] = s[0] * cos(ph);
+}
+// The resection plane in CT of a humerus with the anatomic-neck plane (p_ct, n_ct), the CT -> canal / articular matrix T_anp
+// (bone.py:53-62) and side (0 left, 1 right) after the calls of `off` (the seven fields of sh_cut_offset in their order:
+// offset_retroversion, offest_neckshaft, offset_depth canal / anp / resection, offset_anterior_posterior,
+// offset_medial_lateral; arthroplasty.py:90-175), read back as `plane` with the humerus in CT (:33-40).  A field that is
+// exactly 0 is a call that is not made.  False: T_anp is singular.
+SH_HD bool resect_plane_from_offsets(const double* T_anp, const double* p_ct, const double* n_ct, int side, const double* off,
+                                     double* out_p, double* out_n) {
+  double p[3], n[3], an[3], s[3], Ti[16];
+  xform_pt(T_anp, p_ct[0], p_ct[1], p_ct[2], p);                      // transform_plane (utils.py:191-206): point, then T[:3,:3] @ normal
+  for (int i = 0; i < 3; ++i) { n[i] = (T_anp[4 * i] * n_ct[0] + T_anp[4 * i + 1] * n_ct[1]) + T_anp[4 * i + 2] * n_ct[2]; an[i] = n[i]; }
+  if (off[0] != 0.0) { unitxyz_to_spherical(n, s); s[1] += side == 0 ? -off[0] : off[0]; spherical_to_unitxyz(s, n); }
+  if (off[1] != 0.0) { unitxyz_to_spherical(n, s); s[2] += -off[1]; spherical_to_unitxyz(s, n); }
+  if (off[2] != 0.0) p[2] += off[2];
+  if (off[3] != 0.0) for (int i = 0; i < 3; ++i) p[i] = p[i] + off[3] * an[i];
+  if (off[4] != 0.0) for (int i = 0; i < 3; ++i) p[i] = p[i] + off[4] * n[i];
+  if (off[5] != 0.0) p[0] += side == 0 ? -off[5] : off[5];
+  if (off[6] != 0.0) p[1] -= off[6];
+  if (!inv_transform(T_anp, Ti)) return false;
+  xform_pt(Ti, p[0], p[1], p[2], out_p);
+  for (int i = 0; i < 3; ++i) out_n[i] = (Ti[4 * i] * n[0] + Ti[4 * i + 1] * n[1]) + Ti[4 * i + 2] * n[2];
+  return true;
+}
+
 }  // namespace sh

@@ -27,6 +27,7 @@
 #include "unet16_pp.h"
 #include "k_stl.h"
 #include "k_clip.h"
+#include "k_resect.h"
 #include "k_hullpre.h"
 #include "k_te.h"
 #include "k_obb.h"
@@ -172,6 +173,11 @@ struct sh_ctx {
   bool unet_turn = false;                // sh_set_unet_turns: UNet passes of the contexts of one device run one after another
   hipEvent_t unet_done_ev = nullptr;
   unsigned long long batch_gen = 0;
+  // sh_resect_* (k_resect.h): the stages and the batch of the last submitted run (sh_resect_offsets reads its records), and the
+  // planes per humerus and the batch of the last resection ("resect.planes": sh_resect_ring joins one of its cuts again)
+  uint32_t rec_mask = 0;
+  unsigned long long rec_gen = ~0ull, resect_gen = ~0ull;
+  int resect_P = 0;
   hipStream_t copy_stream = nullptr;
   hipEvent_t stl_counted_ev = nullptr;      // sh_stage_stl: the device has counted the merged vertices / faces
   // side stream of the stage runner: the distal slice set and the rectangles of the trans-epicondylar stage hang on nothing but the
@@ -1096,6 +1102,111 @@ int sh_slice_mesh_planes(sh_ctx* c, const double* verts, int nv, const int32_t* 
     if (out_edges && cn[p].n_edges) HIPCHK(c, hipMemcpyAsync(out_edges + 2 * (size_t)p * cap_e, (int*)d_oe + 2 * (size_t)p * cap_e, (size_t)cn[p].n_edges * 8, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- batched head resection (k_resect.h) -------------------------------------------------------------------------------
+// Planes per pass: the slot ranges (4 KB per cut) and the slab (32 B per cut and tile) stay below 32 MB / 128 MB; a sweep larger
+// than that takes several passes over the mesh.  The pass a plane falls into does not change its record (the slab of a cut is its own).
+static int resect_buffers(sh_ctx* c, int P, int* pc_out, int* tmax_out) {
+  const int B = c->B;
+  const long long tmax = std::max<long long>(1, (c->maxF + SH_RS_TILE - 1) / SH_RS_TILE);
+  long long pc = std::min<long long>(8192 / B, (128LL << 20) / (32LL * B * tmax));
+  pc = std::max<long long>(1, std::min<long long>(pc, P));
+  int rc;
+  if ((rc = ensure(c, "resect.planes", (size_t)B * P * 48, 8)) || (rc = ensure(c, "resect.status", (size_t)B * P * 4, 4)) ||
+      (rc = ensure(c, "resect.slab", (size_t)B * pc * tmax * sizeof(ResectPart), 8)) || (rc = ensure(c, "resect.segcnt", (size_t)B * pc * 4, 4)) ||
+      (rc = ensure(c, "resect.segs", (size_t)B * pc * SH_MAXSEG * 4, 4)) || (rc = ensure(c, "resect.out", (size_t)B * P * sizeof(sh_resection), 8)) ||
+      (rc = ensure(c, "resect.one", sizeof(sh_resection), 8)) || (rc = ensure(c, "resect.ring", (size_t)(SH_MAXSEG + 1) * 24, 8)))
+    return rc;
+  for (const char* n : {"resect.planes", "resect.status", "resect.slab", "resect.segcnt", "resect.segs", "resect.out", "resect.one", "resect.ring"}) c->bufs[n].per_mesh = 0;
+  *pc_out = (int)pc; *tmax_out = (int)tmax;
+  return SH_OK;
+}
+
+// face pass + join of planes [p0, p0 + pc) of humeri [b0, b0 + nb); one: the record and ring of a single cut (sh_resect_ring)
+static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tmax, bool one) {
+  int* segcnt = (int*)c->bufs["resect.segcnt"].p;
+  HIPCHK(c, hipMemsetAsync(segcnt, 0, (size_t)nb * pc * 4, c->stream));
+  const float* verts = (const float*)c->bufs["verts"].p; const int* faces = (const int*)c->bufs["faces"].p;
+  const long long* voff = (const long long*)c->bufs["voff"].p; const long long* foff = (const long long*)c->bufs["foff"].p;
+  const double* planes = (const double*)c->bufs["resect.planes"].p;
+  LAUNCH(c, "k_resect_faces", k_resect_faces, dim3((unsigned)tmax, (unsigned)nb), dim3(SH_RS_TILE), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
+         (ResectPart*)c->bufs["resect.slab"].p, segcnt, (int*)c->bufs["resect.segs"].p);
+  LAUNCH(c, "k_resect_join", k_resect_join, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
+         (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
+         (sh_resection*)c->bufs["resect.out"].p, one ? (sh_resection*)c->bufs["resect.one"].p : (sh_resection*)nullptr,
+         one ? (double*)c->bufs["resect.ring"].p : (double*)nullptr);
+  return SH_OK;
+}
+
+static int resect_all(sh_ctx* c, int P, int pc, int tmax, sh_resection* out) {
+  for (int p0 = 0; p0 < P; p0 += pc)
+    if (int rc = resect_pass(c, P, p0, std::min(pc, P - p0), 0, c->B, tmax, false)) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, c->bufs["resect.out"].p, (size_t)c->B * P * sizeof(sh_resection), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->resect_P = P; c->resect_gen = c->batch_gen;
+  return SH_OK;
+}
+
+int sh_resect_planes(sh_ctx* c, const double* planes, int P, sh_resection* out) {
+  if (!c || !planes || !out || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, "sh_resect_planes: bad argument (P in 1..4096)");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_resect_planes: no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_planes: runs are in flight (sh_collect them first)");
+  const size_t n = (size_t)c->B * P;
+  for (size_t i = 0; i < n; ++i) {
+    const double* q = planes + 6 * i;
+    bool fin = true;
+    for (int k = 0; k < 6; ++k) fin = fin && std::isfinite(q[k]);
+    if (!fin || !((q[3] * q[3] + q[4] * q[4]) + q[5] * q[5] > 0.0)) return fail(c, SH_ERR_ARG, "sh_resect_planes: zero normal or non-finite plane");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  int pc, tmax;
+  if (int rc = resect_buffers(c, P, &pc, &tmax)) return rc;
+  c->resect_gen = ~0ull;
+  HIPCHK(c, hipMemcpyAsync(c->bufs["resect.planes"].p, planes, n * 48, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->bufs["resect.status"].p, 0, n * 4, c->stream));
+  return resect_all(c, P, pc, tmax, out);
+}
+
+int sh_resect_offsets(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out) {
+  if (!c || !offs || !out || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, "sh_resect_offsets: bad argument (P in 1..4096)");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_resect_offsets: no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_offsets: runs are in flight (sh_collect them first)");
+  const uint32_t need = SH_STAGE_ANP | SH_STAGE_CSYS;
+  if (c->rec_gen != c->batch_gen || (c->rec_mask & need) != need || c->bufs.find("landmarks") == c->bufs.end())
+    return fail(c, SH_ERR_STATE, "sh_resect_offsets: needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
+  static_assert(sizeof(sh_cut_offset) == 7 * sizeof(double), "sh_cut_offset is seven doubles");
+  for (int i = 0; i < 7 * P; ++i)
+    if (!std::isfinite(((const double*)offs)[i])) return fail(c, SH_ERR_ARG, "sh_resect_offsets: non-finite offset");
+  HIPCHK(c, hipSetDevice(c->device));
+  int pc, tmax, rc;
+  if ((rc = resect_buffers(c, P, &pc, &tmax))) return rc;
+  if ((rc = ensure(c, "resect.offs", (size_t)P * 56, 8))) return rc;
+  c->bufs["resect.offs"].per_mesh = 0;
+  c->resect_gen = ~0ull;
+  HIPCHK(c, hipMemcpyAsync(c->bufs["resect.offs"].p, offs, (size_t)P * 56, hipMemcpyHostToDevice, c->stream));
+  LAUNCH(c, "k_resect_make_planes", k_resect_make_planes, dim3((unsigned)c->B), dim3(64), (const sh_landmarks*)c->bufs["landmarks"].p,
+         (const double*)c->bufs["resect.offs"].p, P, (double*)c->bufs["resect.planes"].p, (int*)c->bufs["resect.status"].p);
+  return resect_all(c, P, pc, tmax, out);
+}
+
+int sh_resect_ring(sh_ctx* c, int b, int p, double* out, int cap, int* n_out) {
+  if (!c || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, SH_ERR_ARG, "sh_resect_ring: bad argument");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_ring: runs are in flight (sh_collect them first)");
+  if (c->resect_gen != c->batch_gen || c->resect_P < 1) return fail(c, SH_ERR_STATE, "sh_resect_ring: no resection of the resident batch");
+  if (b < 0 || b >= c->B || p < 0 || p >= c->resect_P) return fail(c, SH_ERR_ARG, "sh_resect_ring: index out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  const long long nf = c->h_foff[b + 1] - c->h_foff[b];
+  const int tiles = (int)std::max<long long>(1, (nf + SH_RS_TILE - 1) / SH_RS_TILE);
+  if (int rc = resect_pass(c, c->resect_P, p, 1, b, 1, tiles, true)) return rc;
+  sh_resection r;
+  HIPCHK(c, hipMemcpyAsync(&r, c->bufs["resect.one"].p, sizeof r, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (r.status != 0 || r.n_loops < 1) { *n_out = 0; return SH_OK; }
+  *n_out = r.n_ring + 1;
+  if (!out || cap < r.n_ring + 1) return SH_OK;
+  HIPCHK(c, hipMemcpy(out, c->bufs["resect.ring"].p, (size_t)(r.n_ring + 1) * 24, hipMemcpyDeviceToHost));
   return SH_OK;
 }
 
@@ -3003,6 +3114,7 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
          dev_hull ? (const int*)buf<int>(c, "hulld.fail") : (const int*)nullptr, (char*)err_stage, B, status_ovf_off(B));
   HIPCHK(c, hipEventRecord(tk.ev, c->stream));
   tk.B = B; tk.pending = true; tk.mask = mask; tk.out_arg = out; tk.dev_hull = dev_hull; tk.gen = c->batch_gen;
+  c->rec_mask = mask; c->rec_gen = c->batch_gen;
   c->t_head ^= 1; ++c->n_pending;
   return SH_OK;
 }

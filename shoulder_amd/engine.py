@@ -433,6 +433,50 @@ class Engine:
             out.append((ov[p, :nv_].copy(), of[p, :nf_].copy()) + ((oe[p, :ne_].copy(),) if edges else ()))
         return out
 
+    # ---- batched head resection (include/shoulder_hip.h sh_resect_*) -------------------------------------------------
+    def resect(self, planes=None, offsets=None):
+        """B resident humeri x P resection planes in one device pass -> structured array (B, P) of _lib.RESECTION_DTYPE.
+        planes: (B, P, 6) or (B, P, 2, 3) float64, (point, normal) in CT per humerus (sh_resect_planes; needs no run).
+        offsets: P cuts relative to every humerus' own anatomic-neck plane -- a list of dicts or a structured array with the
+        sh_cut_offset field names (_lib.CUT_OFFSET_DTYPE; missing keys are 0) -- planes built on the device from the records of
+        the last run (sh_resect_offsets; needs a run with STAGE_ANP and STAGE_CSYS).  A cut's `status` tells its own failure."""
+        if (planes is None) == (offsets is None):
+            raise ValueError("resect() takes planes or offsets")
+        B = self.B
+        if planes is not None:
+            pl = np.ascontiguousarray(planes, dtype=np.float64)
+            if pl.ndim < 2 or pl.shape[0] != B or pl.size % (6 * max(B, 1)) or pl.size == 0:
+                raise ValueError("planes must have shape (B, P, 6)")
+            P = pl.size // (6 * B)
+            out = np.zeros((B, P), dtype=_lib.RESECTION_DTYPE)
+            self._chk(self.L.sh_resect_planes(self.h, _ptr(pl), P, _ptr(out)))
+            return out
+        if isinstance(offsets, np.ndarray) and offsets.dtype.names:
+            off = np.zeros(offsets.shape, dtype=_lib.CUT_OFFSET_DTYPE).reshape(-1)
+            for n in offsets.dtype.names:
+                off[n] = offsets[n].reshape(-1)      # (an unknown field name raises)
+        else:
+            offsets = list(offsets)
+            off = np.zeros(len(offsets), dtype=_lib.CUT_OFFSET_DTYPE)
+            for i, d in enumerate(offsets):
+                for k, v in dict(d).items():
+                    off[k][i] = v
+        if len(off) == 0:
+            raise ValueError("at least one offset")
+        out = np.zeros((B, len(off)), dtype=_lib.RESECTION_DTYPE)
+        self._chk(self.L.sh_resect_offsets(self.h, _ptr(off), len(off), _ptr(out)))
+        return out
+
+    def resect_ring(self, b, p):
+        """The largest loop of cut p of humerus b of the last resect(): (n + 1, 3) float64 in CT, closed, counter-clockwise seen
+        from the tip of the normal, canonical start (sh_resect_ring); (0, 3) for a cut without a ring."""
+        n = ctypes.c_int()
+        self._chk(self.L.sh_resect_ring(self.h, int(b), int(p), None, 0, ctypes.byref(n)))
+        out = np.empty((max(1, n.value), 3), dtype=np.float64)
+        if n.value:
+            self._chk(self.L.sh_resect_ring(self.h, int(b), int(p), _ptr(out), len(out), ctypes.byref(n)))
+        return out[: n.value]
+
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):
         n, e = ctypes.c_size_t(), ctypes.c_int()
