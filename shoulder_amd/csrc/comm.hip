@@ -1,4 +1,4 @@
-// sh_comm.h -- the three collective entry points of the C-ABI: one HOST PROCESS drives several GPUs, one sh_ctx
+// comm.hip -- the three collective entry points of the C-ABI: one HOST PROCESS drives several GPUs, one sh_ctx
 // per device, and shards a cohort of humeri over them.  The humeri are independent (the reference runs one `Humerus(stl)` at a
 // time, bone.py:110-131), so the data path has no exchange step; what crosses the xGMI links is
 //   * the parameter block, once (the reference loads the same pickled forest / ONNX blob in every process: bicipital_groove.py:21-25,
@@ -7,10 +7,12 @@
 // RCCL is bound at run time (dlopen of librccl.so.1 on the first sh_comm_init_all): a host that runs one GPU, and the CPU-side
 // symbol check of tests/test_abi_exports.py, never load it.  The multi-PROCESS launch (one rank per GPU under torch.distributed,
 // bench.py --gpus N) does the same two transfers over torch's RCCL binding: shoulder_amd/dist.py.
-// Included by shoulder_hip.hip inside its extern "C" block, after the context and the record emitters.
-#pragma once
-// (shoulder_hip.hip includes <dlfcn.h> and <rccl/rccl.h> at file scope -- the latter for its TYPES only: every call goes through
-// the table below)
+#include "sh_ctx.h"
+
+#include <dlfcn.h>
+#include <rccl/rccl.h>      // its TYPES only: librccl itself is bound at run time, every call goes through the table below
+
+using namespace sh;
 
 struct RcclApi {
   void* lib = nullptr;
@@ -71,11 +73,13 @@ static int comm_group_check(sh_ctx** ctxs, int n, const char* who) {
   return SH_OK;
 }
 
-static void comm_forget(sh_ctx* c) {
+void sh::comm_forget(sh_ctx* c) {
   if (!c->comm) return;
   if (RcclApi* api = rccl_api()) { (void)hipSetDevice(c->device); (void)api->CommDestroy((ncclComm_t)c->comm); }
   c->comm = nullptr; c->comm_rank = -1; c->comm_n = 0;
 }
+
+extern "C" {
 
 // One communicator per context, rank i = ctxs[i] (ncclCommInitAll over the contexts' devices).  The contexts sit on DISTINCT
 // devices; a context leaves its group when it is destroyed or joins another.  Errors are left on ctxs[0].
@@ -196,3 +200,5 @@ int sh_gather_landmarks(sh_ctx** ctxs, int n, sh_landmarks* out_root) {
   }
   return SH_OK;
 }
+
+}  // extern "C"

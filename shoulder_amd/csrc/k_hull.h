@@ -25,7 +25,8 @@
 // host quickhull writes its normals the same way, so both paths hand k_obb_candidates the same bits), edges (va, vb, f, g).
 #pragma once
 #include "k_hullpre.h"
-#include "k_obb.h"      // HullCap: the per-humerus strides of the hull record
+#include "sh_scalar.h"
+#include "sh_hullcap.h"      // HullCap: the per-humerus strides of the hull record
 
 namespace sh {
 

@@ -12,7 +12,6 @@
 // A humerus whose polytope cannot be built (flat input, > SH_HP_MAXPL planes) keeps all its vertices.
 #pragma once
 #include "sh_common.h"
-#include "k_stl.h"
 
 namespace sh {
 

@@ -6,7 +6,7 @@
 //   k_pack      bone.py:146-157 construct_csys(canal, TE) + fill sh_landmarks (CT coordinates)
 #pragma once
 #include "../../include/shoulder_hip.h"
-#include "k_unet.h"
+#include "k_anp.h"
 #include "k_ovf.h"
 
 namespace sh {

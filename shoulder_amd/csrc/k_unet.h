@@ -16,7 +16,7 @@
 // Roofline: MFMA-bound at f32 (157 TFLOP/s dense peak); bytes are small (activations of a
 // 64-image batch stay in the 256 MB Infinity Cache between layers).
 #pragma once
-#include "k_anp.h"
+#include "sh_common.h"
 #include "k_unet16_base.h"
 
 namespace sh {

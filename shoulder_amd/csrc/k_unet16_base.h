@@ -1,5 +1,5 @@
 // k_unet16_base.h -- element types, fragment layout and LDS-DMA helpers shared by the 16-bit UNet kernels.  No kernels in here: the
-// translation units of the library (shoulder_hip.hip, unet16_pp.hip) both include it.
+// translation units of the library (unet.hip, unet16_pp.hip) both include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,0 +1,307 @@
+// sh_ctx.h -- what the host units of libshoulder_hip.so share: the context, the named-buffer helpers, the launch macros and the
+// few functions that cross units.  No kernels here: every k_*.h is included by exactly one unit (-fno-gpu-rdc), the one whose
+// host code launches it.
+//   shoulder_hip.hip  context, C-ABI plumbing, meshes, the stage runner, submit / collect   (geometry kernels)
+//   hull.hip          hull prefilter, host hull phase and its worker pool, device hull      (k_hullpre.h, k_hull.h)
+//   unet.hip          the UNet runners, UNet turns, sh_unet_infer                          (k_unet*.h; unet16_pp.hip: k_unet16_pp.h)
+//   comm.hip          the RCCL collectives
+#pragma once
+#include "../../include/shoulder_hip.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <condition_variable>
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+#include <deque>
+#include <functional>
+#include <initializer_list>
+#include <map>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <tuple>
+#include <vector>
+
+#include "sh_hullcap.h"
+
+// ---------------------------------------------------------------------------------------------
+struct Buf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int elem = 1;
+  size_t per_mesh = 0;     // bytes per humerus for [B][...] buffers (0: shared / ragged / scratch)
+};
+
+struct KTimer {
+  double ms = 0;
+  int n = 0;
+};
+
+struct sh_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  std::string err;
+  sh_params params;
+  int B = 0;
+  long long sumV = 0, sumF = 0, maxV = 0, maxF = 0;
+  std::vector<long long> h_voff, h_foff;
+  std::map<std::string, Buf> bufs;
+  bool have_rfc = false, have_unet = false;
+  int rfc_nodes = 0, rfc_trees = 0;
+  int unet_base = 0, unet_depth = 0;
+  std::vector<float> h_unet;                 // packed UNet parameters (host copy)
+  std::vector<int32_t> h_feat, h_ti, h_fi, h_roots;
+  std::vector<float> h_thr, h_lw;
+  struct ULayer { size_t w_off, b_off; int cin, cout, taps; };
+  std::map<std::string, ULayer> ulayers;
+  size_t unet_floats = 0;
+  bool obb_injected = false;
+  void* comm = nullptr;                      // sh_comm_init_all: this context's RCCL communicator (comm.hip), its rank and the group's size
+  int comm_rank = -1, comm_n = 0;
+  // sh_set_keep_products: every plane's resampled contour and polar rows leave k_resample_polar (k_slices.h, RsWant); off: the rows
+  // the later stages read.  rs_*: what the last SH_STAGE_PROXIMAL run of the resident batch wrote (SH_STAGE_GROOVE checks it covers its rows)
+  bool keep_products = false;
+  const double* unet_raw = nullptr;          // run_window -> unet_forward16: the unscaled image and its encoded range, when the first kernel scales it itself
+  const unsigned long long* unet_mm = nullptr;
+  int rs_cs_lo = 0, rs_cs_hi = 0;
+  bool rs_all = false;
+  unsigned long long rs_gen = ~0ull;
+  int rec_rows = 0;                          // sh_set_record_rows: 0 = full sh_landmarks records, R > 0 = packed records with R anatomic-neck rows
+  bool bounds_cleared = false;               // run_obb's first fill of this window covered zb_enc / anp.mm_enc (run_window skips its own)
+  // hull of SH_STAGE_OBB: 1 = on the device (k_hull.h), 0 = host quickhull (sh_hull.h).  sh_set_hull_mode / SHOULDER_HULL=host|device|auto.
+  // A humerus the device hull gives up (pinched horizon on nearly coplanar clouds, capacities) is re-done ALONE by sh_collect:
+  // host quickhull for that humerus, its record patched into the device buffers, its stages re-run as a window of one behind
+  // whatever else is in flight on the stream (redo_given_up).  `hulld.skip[b]` then keeps the device hull off that humerus for
+  // as long as the batch stays resident (skip_gen == batch_gen).
+  int hull_mode = 1;
+  unsigned long long skip_gen = ~0ull;
+  int skip_nfmax = 0;                      // most hull faces among the humeri of this batch that are on the host hull (hulld.skip)
+  // overflow pools of the slice layer (k_ovf.h): capacities in segments / ring points / bytes; grown by sh_collect on demand
+  unsigned long long ovf_seg_cap = 1ull << 18, ovf_ring_cap = 1ull << 18, ovf_work_cap = 32ull << 20;
+  // a run of the resident batch that planned no overflow plane in any set (ctr[4] == 0 at collect) lets later runs of the SAME batch
+  // and parameters skip the overflow tier's launches (they would all return at once: ~17 launches, ~60 us per step)
+  unsigned long long ovf_none_gen = ~0ull;
+  // sh_set_open_contours (k_open.h): SH_OPEN_ERROR / SH_OPEN_BRIDGE and the largest gap bridged (mm); open_stats_run: the mode of the
+  // last sh_submit ("open.stats" is cleared, and counts, only in bridge mode)
+  int open_mode = SH_OPEN_ERROR;
+  double open_gap = SH_OPEN_GAP_DEFAULT;
+  int open_stats_run = SH_OPEN_ERROR;
+  int end_cap = SH_ENDCAP;                   // points per end section "obb.endpts" holds (grown by sh_collect like the pools)
+  unsigned long long obb_gen = ~0ull;        // the batch generation the three fields below belong to
+  sh::HullCap hcap = {SH_HV, SH_HF, SH_HE};      // per-humerus capacity (= stride) of the hull record and the per-face obb.* arrays; a batch with a larger
+                                             // hull grows it (grow_hull_records) -- every kernel takes the strides as an argument
+  int obb_sil_need = 0;                      // the longest silhouette (edges) a direction of the resident batch had when it overflowed a tier of
+                                             // k_obb_candidates: later runs take the tier that holds it (reset with the batch)
+  bool obb_nf_over = false;                  // a device-hull run met a hull with more faces than its candidates tier masks: the next run takes the workspace tier
+  bool hull_force_host = false;              // the resident batch has a hull above the device hull's record: its hulls come from the host (reset with the batch)
+  bool redo_records = false;               // run_obb: the hull records of the window are in place already (redo_given_up)
+  int redo_nf = 0;
+  std::vector<float> h_verts;                // host copy of the vertices (hull stage)
+  bool h_verts_valid = false;
+  // device-generated batches: the hull's points come back through the prefilter (k_hullpre.h) into pinned memory
+  float* h_kept = nullptr; long long h_kept_cap = 0;
+  int* h_nkept = nullptr; int h_nkept_cap = 0;
+  struct HullPts { const float* src = nullptr;            // what hull_host_phase reads: h_verts.data() or the pinned survivors
+                   std::vector<long long> off;            // first point of humerus b in src
+                   std::vector<int> cnt; };               // points of humerus b in src
+  HullPts hull_in;                           // ... of the resident batch
+  long long* h_koff = nullptr;               // pinned: offsets of the survivors (B + 1)
+  // The STAGING SIDE of the mesh slot (sh_stage_meshes / sh_stage_stl / sh_commit_staged): the next batch is copied into buffers of
+  // its own ("verts.s", "faces.s", "voff.s", "foff.s") on the copy stream while a run of the resident batch executes, its hull
+  // points come back through a prefilter scratch of its own ("hullpre.*.s") and its hulls are computed by the background thread
+  // (`prep`, gen = batch_gen + 1) -- sh_commit_staged then only swaps the buffer entries and the next sh_submit finds its hulls.
+  struct StageSide {
+    bool active = false, from_stl = false;
+    int B = 0; long long sumV = 0, sumF = 0, maxV = 0, maxF = 0;
+    std::vector<long long> voff, foff;
+    void* h_src = nullptr; size_t h_src_cap = 0;            // pinned staging of the caller's arrays / files
+    int* h_flag = nullptr;                                  // pinned: validation word (+ STL: counts and non-finite words behind it)
+    size_t h_flag_cap = 0;
+    float* h_kept = nullptr; long long h_kept_cap = 0;      // pinned: prefilter survivors of the staged batch
+    long long* h_koff = nullptr; int h_koff_cap = 0;
+    HullPts pts;
+    hipEvent_t ready_ev = nullptr;                          // everything the commit needs is on the device
+    std::mutex m; std::condition_variable cv; bool meta_ready = true; int meta_rc = 0; std::string meta_err;      // STL: sizes known
+  } stg;
+  // Window of the batch the stage runner is working on: sh_run walks the batch in windows so that the
+  // host hull of window k+1 overlaps the device work of window k.  buf<T>() applies the offset.
+  int b0 = 0, Bwin = 0;
+  struct HullStage { double* hv = nullptr; double* nr = nullptr; int* ed = nullptr; int* cnt = nullptr; int cap = 0; hipEvent_t ev = nullptr; bool used = false;
+                     int pv = 4096, pf = 8192, pe = 12288; };      // per-humerus pitch of the pinned staging (elements): the usual hull fits the small
+                                                                 // one; a batch with a larger hull re-allocates the slot at SH_HV / SH_HF / SH_HE
+  HullStage hstage[2];                       // pinned host staging, double buffered
+  int hslot = 0;                             // slot the next hull goes to
+  // Overlap (sh_set_overlap): while the device works on run k, a background thread computes the hulls run k+1 will
+  // need (same resident batch -- invalidated by any upload) into the other pinned slot.
+  struct Prepared {
+    std::thread th; bool active = false; int slot = 0, B = 0, rc = SH_OK, bad_mesh = -1; unsigned long long gen = 0;
+    double d2h_ms = 0, hull_ms = 0; std::string err;
+    bool uploaded = false;      // the hull records are already in the device buffers (copied by the background thread)
+    bool staged = false;        // the thread works for the STAGED batch (gen = the generation the batch gets at sh_commit_staged)
+  } prep;
+  hipEvent_t obb_done_ev = nullptr;      // recorded after the last kernel of a run that reads the hull.* device buffers
+  // sh_submit / sh_collect: up to two runs in flight (the second one is enqueued while the first still executes)
+  struct Ticket { hipEvent_t ev = nullptr; int* h_err = nullptr; int* h_fail = nullptr; unsigned long long* h_ovf = nullptr; int cap = 0, B = 0; bool pending = false; sh_landmarks* host_out = nullptr;
+                  uint32_t mask = 0; sh_landmarks* out_arg = nullptr; bool dev_hull = false; unsigned long long gen = 0; size_t rec = sizeof(sh_landmarks); int rows = 0; };
+  Ticket tickets[2];
+  int t_head = 0, t_tail = 0, n_pending = 0;
+  hipStream_t out_stream = nullptr;      // sh_collect copies the records / status words of a finished run to the host on this stream
+  bool overlap = false;
+  bool unet_turn = false;                // sh_set_unet_turns: UNet passes of the contexts of one device run one after another
+  hipEvent_t unet_done_ev = nullptr;
+  unsigned long long batch_gen = 0;
+  // sh_resect_* (k_resect.h): the stages and the batch of the last submitted run (sh_resect_offsets reads its records), and the
+  // planes per humerus and the batch of the last resection ("resect.planes": sh_resect_ring joins one of its cuts again)
+  uint32_t rec_mask = 0;
+  unsigned long long rec_gen = ~0ull, resect_gen = ~0ull;
+  int resect_P = 0;
+  hipStream_t copy_stream = nullptr;
+  hipEvent_t stl_counted_ev = nullptr;      // sh_stage_stl: the device has counted the merged vertices / faces
+  // side stream of the stage runner: the distal slice set and the rectangles of the trans-epicondylar stage hang on nothing but the
+  // box frame, so they run beside the full -> neck -> proximal chain
+  hipStream_t side_stream = nullptr;
+  hipEvent_t side_fork_ev = nullptr, side_join_ev = nullptr;
+  bool side_pending = false;
+  // timing
+  bool zero_page_ready = false;
+  // Switches of equivalent paths (the A/B arms of tests/), read from the environment ONCE, when the context is created -- no launch
+  // path consults the environment.  (Read elsewhere, process-wide: SHOULDER_HULL's default, SHOULDER_HULL_THREADS and
+  // LOCAL_WORLD_SIZE for the hull pool, SHOULDER_RCCL_LIB.)
+  struct Switches {
+    int window = 0;            // SHOULDER_WINDOW=n: humeri per window of the host-hull walk (0: SH_WINDOW)
+    bool obb_prune = true;     // SHOULDER_OBB_PRUNE=0: every hull-face direction is evaluated
+    bool slice_merge = true;   // SHOULDER_SLICE_MERGE=0: one slice set per launch group
+    bool hull_prefilter = true; // SHOULDER_HULL_PREFILTER=0: host hulls read every vertex back instead of the prefilter's survivors
+    bool debug = false;        // SH_DEBUG: host-phase timings on stderr
+  } sw;
+  bool unet_reference = false;      // SHOULDER_UNET_REFERENCE=1 at context creation: the 16-bit network layer by layer on the generic kernels
+  int ticket_next = 0;              // next free work counter of "unet16.tickets" (one per persistent conv launch of a forward pass)
+  std::map<std::tuple<int, int, int>, std::pair<int, int>> tk_tabs;      // (items, workgroups, cout groups) -> (offset, tickets) in "unet16.tk_tab"
+  int tk_tab_used = 0;
+  bool packtab_ready = false;      // layer table of k_pack_w_bf16_all uploaded (reset by sh_load_unet)
+  bool packed_rfc = false;         // "rfc.nodes" holds the packed forest of the CURRENT parameter block
+  bool packed_x3 = false;          // "params_x3h/l" hold the split weights of the CURRENT parameter block (reset with packed_kind)
+  int packed_kind = -1;            // element kind (0 bf16, 1 f16) "params_bf16" was packed for from the CURRENT parameter block; -1: repack.
+                                   // Reset wherever the block can change: sh_load_*, sh_param_block (the pointer goes to the caller), sh_param_block_commit
+  int num_cus = 0;
+  int timing = 0;      // 0 off, 1 every launch, 2 UNet layers only
+  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
+  std::map<std::string, KTimer> timers;
+};
+
+#define HIPCHK(ctx, call)                                                                   \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess) {                                                                 \
+      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                       \
+      return SH_ERR_HIP;                                                                    \
+    }                                                                                       \
+  } while (0)
+
+// the same for code that has no context to write to (the background threads): the text goes to *errtxt
+#define HIPCHK_TXT(errtxt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *(errtxt) = std::string(#call) + ": " + hipGetErrorString(e_); return SH_ERR_HIP; } } while (0)
+
+static inline int fail(sh_ctx* c, int code, const std::string& msg) {
+  if (c) c->err = msg;
+  return code;
+}
+
+static inline int ensure(sh_ctx* c, const char* name, size_t bytes, int elem, void** out = nullptr) {
+  Buf& b = c->bufs[name];
+  if (b.bytes < bytes || b.p == nullptr) {
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr;
+    hipError_t e = hipMalloc(&b.p, bytes ? bytes : 16);
+    if (e != hipSuccess) {
+      c->err = std::string("hipMalloc(") + name + "): " + hipGetErrorString(e);
+      b.bytes = 0;
+      return SH_ERR_NOMEM;
+    }
+    b.bytes = bytes;
+  }
+  b.elem = elem;
+  if (out) *out = b.p;
+  return SH_OK;
+}
+
+template <typename T>
+static inline T* buf(sh_ctx* c, const char* name) {
+  auto it = c->bufs.find(name);
+  if (it == c->bufs.end() || !it->second.p) return nullptr;
+  return (T*)((char*)it->second.p + (size_t)c->b0 * it->second.per_mesh);
+}
+
+// ensure() inside a function with `int rc`, and the buffer's window stride: ENS for [B][...] buffers (bytes / B per humerus),
+// ENS_SHARED for shared / ragged / scratch ones (stride 0)
+#define ENS_(name, bytes, elem, per_mesh_)                                          \
+  do {                                                                              \
+    if ((rc = ensure(c, name, (size_t)(bytes), elem)) != SH_OK) return rc;          \
+    c->bufs[name].per_mesh = (per_mesh_);                                           \
+  } while (0)
+#define ENS(name, bytes, elem) ENS_(name, bytes, elem, (size_t)(bytes) / (size_t)c->B)
+#define ENS_SHARED(name, bytes, elem) ENS_(name, bytes, elem, 0)
+
+// kernel launch with optional HIP-event timing on the ctx stream
+// timing level 1: events around every launch; 2: around the UNet layers only ("unet.*": ~25 launches per run, so the
+// measurement does not stretch the run it measures -- events around all ~150 launches cost ~0.7 ms per run at B = 64)
+static inline bool timed_launch(const sh_ctx* c, const char* name) {
+  return c->timing == 1 || (c->timing == 2 && name[0] == 'u' && name[1] == 'n' && name[2] == 'e' && name[3] == 't' && name[4] == '.');
+}
+
+// the bookkeeping around a launch: a kernel (LAUNCH) or a launcher function of another translation unit (unet16_pp.h)
+#define LAUNCH_FN(ctx, name, call)                                                           \
+  do {                                                                                      \
+    hipEvent_t e0_ = nullptr, e1_ = nullptr;                                                \
+    const bool timed_ = timed_launch(ctx, name);                                            \
+    if (timed_) {                                                                           \
+      (void)hipEventCreate(&e0_); (void)hipEventCreate(&e1_);                               \
+      (void)hipEventRecord(e0_, (ctx)->stream);                                             \
+    }                                                                                       \
+    call;                                                                                   \
+    if (timed_) {                                                                           \
+      (void)hipEventRecord(e1_, (ctx)->stream);                                             \
+      (ctx)->pending.emplace_back(name, e0_, e1_);                                          \
+    }                                                                                       \
+    HIPCHK(ctx, hipGetLastError());                                                         \
+  } while (0)
+#define LAUNCH(ctx, name, kernel, grid, block, ...) LAUNCH_FN(ctx, name, hipLaunchKernelGGL(kernel, grid, block, 0, (ctx)->stream, __VA_ARGS__))
+
+// records on the wire (shoulder_hip.hip): a full sh_landmarks, or packed with R anatomic-neck rows
+#define SH_REC_HEAD offsetof(sh_landmarks, anp_points)
+#define SH_REC_TAIL (sizeof(sh_landmarks) - SH_REC_HEAD - sizeof(((sh_landmarks*)0)->anp_points))
+static inline size_t rec_bytes_rows(int rows) { return rows > 0 ? SH_REC_HEAD + SH_REC_TAIL + (size_t)rows * 24 : sizeof(sh_landmarks); }
+
+// ---- functions that cross units ------------------------------------------------------------------------------------------------
+struct HullPre { const float* verts; const long long* voff; int* ext; double* planes; int* npl; float* kept; int* nkept; long long* koff; double* pval; int* pidx; int* pcnt; long long* poff; };      // device pointers of the hull prefilter (hull.hip)
+struct FillEnt { void* p; size_t bytes; unsigned char byte; };      // bytes: a multiple of 4, p 4-byte aligned
+namespace sh {
+// shoulder_hip.hip
+int fill_list(sh_ctx* c, std::initializer_list<FillEnt> ents);      // buffer clears of a run as one launch (k_fill_list)
+int emit_records(sh_ctx* c, void* dst, int b0, int n, int rows, size_t rec);
+unsigned threads_per_local_rank(bool sustained = true);
+// hull.hip
+HullPre hullpre_ptrs(sh_ctx* c, const char* sfx = "");      // calling thread only (buffer map); sfx ".s": the staging side
+hipError_t fetch_prefiltered(const HullPre& hp, int B, long long sumV, long long* h_koff, float* h_kept, sh_ctx::HullPts* out, hipStream_t st);
+hipError_t fetch_hull_points(sh_ctx* c, const HullPre& hp, hipStream_t st);
+int hull_host_phase(sh_ctx* c, const sh_ctx::HullPts& in, int slot, int b0, int B, int* bad_mesh, double* ms, std::string* errtxt, bool background = false);
+hipError_t hull_upload(sh_ctx* c, int slot, int B, void* const dst[6], hipStream_t st);
+int run_device_hull(sh_ctx* c, int B, int* nfmax);
+int alloc_hullpre(sh_ctx* c, int B, long long sumV, const char* sfx);
+// unet.hip
+int unet_turn_enter(sh_ctx* c);
+int unet_turn_leave(sh_ctx* c);
+void unet_turn_forget(sh_ctx* c);
+bool unet16_level0_fused(const sh_ctx* c, int H, int W);
+int unet_dispatch(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W);
+// comm.hip
+void comm_forget(sh_ctx* c);
+}  // namespace sh
+
+#define FILL(ctx, ...) do { int frc_ = sh::fill_list(ctx, {__VA_ARGS__}); if (frc_ != SH_OK) return frc_; } while (0)

@@ -1,17 +1,6 @@
-// shoulder_hip.hip -- libshoulder_hip.so: context, buffers, C-ABI (include/shoulder_hip.h) and the
-// stage runner.  gfx950 only.  Kernels live in k_*.h next to this file.
-#include "../../include/shoulder_hip.h"
-
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstring>
-#include <map>
-#include <tuple>
-#include <mutex>
-#include <string>
-#include <vector>
+// shoulder_hip.hip -- libshoulder_hip.so: context, buffers, C-ABI (include/shoulder_hip.h), meshes and the stage runner.  gfx950 only.
+// The geometry kernels live in k_*.h next to this file; the UNet is unet.hip's, the collectives comm.hip's (sh_ctx.h: who owns what).
+#include "sh_ctx.h"
 
 #include "k_slices.h"
 #include "k_ovf.h"
@@ -19,277 +8,16 @@
 #include "k_stages.h"
 #include "k_groove.h"
 #include "k_anp.h"
-#include "k_unet.h"
-#include "k_unet_bf16.h"
-#include "k_unet16_ldr.h"
-#include "k_unet_x3.h"
-#include "k_unet16_up.h"
-#include "unet16_pp.h"
 #include "k_stl.h"
 #include "k_clip.h"
 #include "k_resect.h"
-#include "k_hullpre.h"
 #include "k_te.h"
 #include "k_obb.h"
-#include "k_hull.h"
 #include "sh_hull.h"
 
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <functional>
-#include <thread>
 #include <sched.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h>      // types for sh_comm.h; librccl itself is bound at run time
 
 using namespace sh;
-
-// ---------------------------------------------------------------------------------------------
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  int elem = 1;
-  size_t per_mesh = 0;     // bytes per humerus for [B][...] buffers (0: shared / ragged / scratch)
-};
-
-struct KTimer {
-  double ms = 0;
-  int n = 0;
-};
-
-struct sh_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  std::string err;
-  sh_params params;
-  int B = 0;
-  long long sumV = 0, sumF = 0, maxV = 0, maxF = 0;
-  std::vector<long long> h_voff, h_foff;
-  std::map<std::string, Buf> bufs;
-  bool have_rfc = false, have_unet = false;
-  int rfc_nodes = 0, rfc_trees = 0;
-  int unet_base = 0, unet_depth = 0;
-  std::vector<float> h_unet;                 // packed UNet parameters (host copy)
-  std::vector<int32_t> h_feat, h_ti, h_fi, h_roots;
-  std::vector<float> h_thr, h_lw;
-  struct ULayer { size_t w_off, b_off; int cin, cout, taps; };
-  std::map<std::string, ULayer> ulayers;
-  size_t unet_floats = 0;
-  bool obb_injected = false;
-  void* comm = nullptr;                      // sh_comm_init_all: this context's RCCL communicator (sh_comm.h), its rank and the group's size
-  int comm_rank = -1, comm_n = 0;
-  // sh_set_keep_products: every plane's resampled contour and polar rows leave k_resample_polar (k_slices.h, RsWant); off: the rows
-  // the later stages read.  rs_*: what the last SH_STAGE_PROXIMAL run of the resident batch wrote (SH_STAGE_GROOVE checks it covers its rows)
-  bool keep_products = false;
-  const double* unet_raw = nullptr;          // run_window -> unet_forward16: the unscaled image and its encoded range, when the first kernel scales it itself
-  const unsigned long long* unet_mm = nullptr;
-  int rs_cs_lo = 0, rs_cs_hi = 0;
-  bool rs_all = false;
-  unsigned long long rs_gen = ~0ull;
-  int rec_rows = 0;                          // sh_set_record_rows: 0 = full sh_landmarks records, R > 0 = packed records with R anatomic-neck rows
-  bool bounds_cleared = false;               // run_obb's first fill of this window covered zb_enc / anp.mm_enc (run_window skips its own)
-  // hull of SH_STAGE_OBB: 1 = on the device (k_hull.h), 0 = host quickhull (sh_hull.h).  sh_set_hull_mode / SHOULDER_HULL=host|device|auto.
-  // A humerus the device hull gives up (pinched horizon on nearly coplanar clouds, capacities) is re-done ALONE by sh_collect:
-  // host quickhull for that humerus, its record patched into the device buffers, its stages re-run as a window of one behind
-  // whatever else is in flight on the stream (redo_given_up).  `hulld.skip[b]` then keeps the device hull off that humerus for
-  // as long as the batch stays resident (skip_gen == batch_gen).
-  int hull_mode = 1;
-  unsigned long long skip_gen = ~0ull;
-  int skip_nfmax = 0;                      // most hull faces among the humeri of this batch that are on the host hull (hulld.skip)
-  // overflow pools of the slice layer (k_ovf.h): capacities in segments / ring points / bytes; grown by sh_collect on demand
-  unsigned long long ovf_seg_cap = 1ull << 18, ovf_ring_cap = 1ull << 18, ovf_work_cap = 32ull << 20;
-  // a run of the resident batch that planned no overflow plane in any set (ctr[4] == 0 at collect) lets later runs of the SAME batch
-  // and parameters skip the overflow tier's launches (they would all return at once: ~17 launches, ~60 us per step)
-  unsigned long long ovf_none_gen = ~0ull;
-  // sh_set_open_contours (k_open.h): SH_OPEN_ERROR / SH_OPEN_BRIDGE and the largest gap bridged (mm); open_stats_run: the mode of the
-  // last sh_submit ("open.stats" is cleared, and counts, only in bridge mode)
-  int open_mode = SH_OPEN_ERROR;
-  double open_gap = SH_OPEN_GAP_DEFAULT;
-  int open_stats_run = SH_OPEN_ERROR;
-  int end_cap = SH_ENDCAP;                   // points per end section "obb.endpts" holds (grown by sh_collect like the pools)
-  unsigned long long obb_gen = ~0ull;        // the batch generation the three fields below belong to
-  HullCap hcap = {SH_HV, SH_HF, SH_HE};      // per-humerus capacity (= stride) of the hull record and the per-face obb.* arrays; a batch with a larger
-                                             // hull grows it (grow_hull_records) -- every kernel takes the strides as an argument
-  int obb_sil_need = 0;                      // the longest silhouette (edges) a direction of the resident batch had when it overflowed a tier of
-                                             // k_obb_candidates: later runs take the tier that holds it (reset with the batch)
-  bool obb_nf_over = false;                  // a device-hull run met a hull with more faces than its candidates tier masks: the next run takes the workspace tier
-  bool hull_force_host = false;              // the resident batch has a hull above the device hull's record: its hulls come from the host (reset with the batch)
-  bool redo_records = false;               // run_obb: the hull records of the window are in place already (redo_given_up)
-  int redo_nf = 0;
-  std::vector<float> h_verts;                // host copy of the vertices (hull stage)
-  bool h_verts_valid = false;
-  // device-generated batches: the hull's points come back through the prefilter (k_hullpre.h) into pinned memory
-  float* h_kept = nullptr; long long h_kept_cap = 0;
-  int* h_nkept = nullptr; int h_nkept_cap = 0;
-  struct HullPts { const float* src = nullptr;            // what hull_host_phase reads: h_verts.data() or the pinned survivors
-                   std::vector<long long> off;            // first point of humerus b in src
-                   std::vector<int> cnt; };               // points of humerus b in src
-  HullPts hull_in;                           // ... of the resident batch
-  long long* h_koff = nullptr;               // pinned: offsets of the survivors (B + 1)
-  // The STAGING SIDE of the mesh slot (sh_stage_meshes / sh_stage_stl / sh_commit_staged): the next batch is copied into buffers of
-  // its own ("verts.s", "faces.s", "voff.s", "foff.s") on the copy stream while a run of the resident batch executes, its hull
-  // points come back through a prefilter scratch of its own ("hullpre.*.s") and its hulls are computed by the background thread
-  // (`prep`, gen = batch_gen + 1) -- sh_commit_staged then only swaps the buffer entries and the next sh_submit finds its hulls.
-  struct StageSide {
-    bool active = false, from_stl = false;
-    int B = 0; long long sumV = 0, sumF = 0, maxV = 0, maxF = 0;
-    std::vector<long long> voff, foff;
-    void* h_src = nullptr; size_t h_src_cap = 0;            // pinned staging of the caller's arrays / files
-    int* h_flag = nullptr;                                  // pinned: validation word (+ STL: counts and non-finite words behind it)
-    size_t h_flag_cap = 0;
-    float* h_kept = nullptr; long long h_kept_cap = 0;      // pinned: prefilter survivors of the staged batch
-    long long* h_koff = nullptr; int h_koff_cap = 0;
-    HullPts pts;
-    hipEvent_t ready_ev = nullptr;                          // everything the commit needs is on the device
-    std::mutex m; std::condition_variable cv; bool meta_ready = true; int meta_rc = 0; std::string meta_err;      // STL: sizes known
-  } stg;
-  // Window of the batch the stage runner is working on: sh_run walks the batch in windows so that the
-  // host hull of window k+1 overlaps the device work of window k.  buf<T>() applies the offset.
-  int b0 = 0, Bwin = 0;
-  struct HullStage { double* hv = nullptr; double* nr = nullptr; int* ed = nullptr; int* cnt = nullptr; int cap = 0; hipEvent_t ev = nullptr; bool used = false;
-                     int pv = 4096, pf = 8192, pe = 12288; };      // per-humerus pitch of the pinned staging (elements): the usual hull fits the small
-                                                                 // one; a batch with a larger hull re-allocates the slot at SH_HV / SH_HF / SH_HE
-  HullStage hstage[2];                       // pinned host staging, double buffered
-  int hslot = 0;                             // slot the next hull goes to
-  // Overlap (sh_set_overlap): while the device works on run k, a background thread computes the hulls run k+1 will
-  // need (same resident batch -- invalidated by any upload) into the other pinned slot.
-  struct Prepared {
-    std::thread th; bool active = false; int slot = 0, B = 0, rc = SH_OK, bad_mesh = -1; unsigned long long gen = 0;
-    double d2h_ms = 0, hull_ms = 0; std::string err;
-    bool uploaded = false;      // the hull records are already in the device buffers (copied by the background thread)
-    bool staged = false;        // the thread works for the STAGED batch (gen = the generation the batch gets at sh_commit_staged)
-  } prep;
-  hipEvent_t obb_done_ev = nullptr;      // recorded after the last kernel of a run that reads the hull.* device buffers
-  // sh_submit / sh_collect: up to two runs in flight (the second one is enqueued while the first still executes)
-  struct Ticket { hipEvent_t ev = nullptr; int* h_err = nullptr; int* h_fail = nullptr; unsigned long long* h_ovf = nullptr; int cap = 0, B = 0; bool pending = false; sh_landmarks* host_out = nullptr;
-                  uint32_t mask = 0; sh_landmarks* out_arg = nullptr; bool dev_hull = false; unsigned long long gen = 0; size_t rec = sizeof(sh_landmarks); int rows = 0; };
-  Ticket tickets[2];
-  int t_head = 0, t_tail = 0, n_pending = 0;
-  hipStream_t out_stream = nullptr;      // sh_collect copies the records / status words of a finished run to the host on this stream
-  bool overlap = false;
-  bool unet_turn = false;                // sh_set_unet_turns: UNet passes of the contexts of one device run one after another
-  hipEvent_t unet_done_ev = nullptr;
-  unsigned long long batch_gen = 0;
-  // sh_resect_* (k_resect.h): the stages and the batch of the last submitted run (sh_resect_offsets reads its records), and the
-  // planes per humerus and the batch of the last resection ("resect.planes": sh_resect_ring joins one of its cuts again)
-  uint32_t rec_mask = 0;
-  unsigned long long rec_gen = ~0ull, resect_gen = ~0ull;
-  int resect_P = 0;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t stl_counted_ev = nullptr;      // sh_stage_stl: the device has counted the merged vertices / faces
-  // side stream of the stage runner: the distal slice set and the rectangles of the trans-epicondylar stage hang on nothing but the
-  // box frame, so they run beside the full -> neck -> proximal chain
-  hipStream_t side_stream = nullptr;
-  hipEvent_t side_fork_ev = nullptr, side_join_ev = nullptr;
-  bool side_pending = false;
-  // timing
-  bool zero_page_ready = false;
-  // Switches of equivalent paths (the A/B arms of tests/), read from the environment ONCE, when the context is created -- no launch
-  // path consults the environment.  (Read elsewhere, process-wide: SHOULDER_HULL's default, SHOULDER_HULL_THREADS and
-  // LOCAL_WORLD_SIZE for the hull pool, SHOULDER_RCCL_LIB.)
-  struct Switches {
-    int window = 0;            // SHOULDER_WINDOW=n: humeri per window of the host-hull walk (0: SH_WINDOW)
-    bool obb_prune = true;     // SHOULDER_OBB_PRUNE=0: every hull-face direction is evaluated
-    bool slice_merge = true;   // SHOULDER_SLICE_MERGE=0: one slice set per launch group
-    bool hull_prefilter = true; // SHOULDER_HULL_PREFILTER=0: host hulls read every vertex back instead of the prefilter's survivors
-    bool debug = false;        // SH_DEBUG: host-phase timings on stderr
-  } sw;
-  bool unet_reference = false;      // SHOULDER_UNET_REFERENCE=1 at context creation: the 16-bit network layer by layer on the generic kernels
-  int ticket_next = 0;              // next free work counter of "unet16.tickets" (one per persistent conv launch of a forward pass)
-  std::map<std::tuple<int, int, int>, std::pair<int, int>> tk_tabs;      // (items, workgroups, cout groups) -> (offset, tickets) in "unet16.tk_tab"
-  int tk_tab_used = 0;
-  bool packtab_ready = false;      // layer table of k_pack_w_bf16_all uploaded (reset by sh_load_unet)
-  bool packed_rfc = false;         // "rfc.nodes" holds the packed forest of the CURRENT parameter block
-  bool packed_x3 = false;          // "params_x3h/l" hold the split weights of the CURRENT parameter block (reset with packed_kind)
-  int packed_kind = -1;            // element kind (0 bf16, 1 f16) "params_bf16" was packed for from the CURRENT parameter block; -1: repack.
-                                   // Reset wherever the block can change: sh_load_*, sh_param_block (the pointer goes to the caller), sh_param_block_commit
-  int num_cus = 0;
-  int timing = 0;      // 0 off, 1 every launch, 2 UNet layers only
-  std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
-  std::map<std::string, KTimer> timers;
-};
-
-#define HIPCHK(ctx, call)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                       \
-      return SH_ERR_HIP;                                                                    \
-    }                                                                                       \
-  } while (0)
-
-static int fail(sh_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
-}
-
-static int ensure(sh_ctx* c, const char* name, size_t bytes, int elem, void** out = nullptr) {
-  Buf& b = c->bufs[name];
-  if (b.bytes < bytes || b.p == nullptr) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    hipError_t e = hipMalloc(&b.p, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-      c->err = std::string("hipMalloc(") + name + "): " + hipGetErrorString(e);
-      b.bytes = 0;
-      return SH_ERR_NOMEM;
-    }
-    b.bytes = bytes;
-  }
-  b.elem = elem;
-  if (out) *out = b.p;
-  return SH_OK;
-}
-
-template <typename T>
-static T* buf(sh_ctx* c, const char* name) {
-  auto it = c->bufs.find(name);
-  if (it == c->bufs.end() || !it->second.p) return nullptr;
-  return (T*)((char*)it->second.p + (size_t)c->b0 * it->second.per_mesh);
-}
-
-// kernel launch with optional HIP-event timing on the ctx stream
-// timing level 1: events around every launch; 2: around the UNet layers only ("unet.*": ~25 launches per run, so the
-// measurement does not stretch the run it measures -- events around all ~150 launches cost ~0.7 ms per run at B = 64)
-static inline bool timed_launch(const sh_ctx* c, const char* name) {
-  return c->timing == 1 || (c->timing == 2 && name[0] == 'u' && name[1] == 'n' && name[2] == 'e' && name[3] == 't' && name[4] == '.');
-}
-
-#define LAUNCH(ctx, name, kernel, grid, block, ...)                                         \
-  do {                                                                                      \
-    hipEvent_t e0_ = nullptr, e1_ = nullptr;                                                \
-    const bool timed_ = timed_launch(ctx, name);                                            \
-    if (timed_) {                                                                           \
-      (void)hipEventCreate(&e0_); (void)hipEventCreate(&e1_);                               \
-      (void)hipEventRecord(e0_, (ctx)->stream);                                             \
-    }                                                                                       \
-    hipLaunchKernelGGL(kernel, grid, block, 0, (ctx)->stream, __VA_ARGS__);                 \
-    if (timed_) {                                                                           \
-      (void)hipEventRecord(e1_, (ctx)->stream);                                             \
-      (ctx)->pending.emplace_back(name, e0_, e1_);                                          \
-    }                                                                                       \
-    HIPCHK(ctx, hipGetLastError());                                                         \
-  } while (0)
-
-// the same bookkeeping around a launcher function of another translation unit (unet16_pp.h)
-#define LAUNCH_FN(ctx, name, call)                                                           \
-  do {                                                                                      \
-    hipEvent_t e0_ = nullptr, e1_ = nullptr;                                                \
-    const bool timed_ = timed_launch(ctx, name);                                            \
-    if (timed_) {                                                                           \
-      (void)hipEventCreate(&e0_); (void)hipEventCreate(&e1_);                               \
-      (void)hipEventRecord(e0_, (ctx)->stream);                                             \
-    }                                                                                       \
-    call;                                                                                   \
-    if (timed_) {                                                                           \
-      (void)hipEventRecord(e1_, (ctx)->stream);                                             \
-      (ctx)->pending.emplace_back(name, e0_, e1_);                                          \
-    }                                                                                       \
-    HIPCHK(ctx, hipGetLastError());                                                         \
-  } while (0)
 
 // Buffer clears of a run as ONE kernel launch per group of adjacent clears.  hipMemsetAsync costs the enqueuing thread ~60 us per
 // call on this stack (rocprofv3 trace of bench.py: the five clears that open a step spread over 0.3 ms before its first kernel;
@@ -301,8 +29,7 @@ __global__ void k_fill_list(FillList L) {
   const unsigned v = L.v[blockIdx.y];
   for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < nw; i += (unsigned long long)gridDim.x * blockDim.x) p[i] = v;
 }
-struct FillEnt { void* p; size_t bytes; unsigned char byte; };      // bytes: a multiple of 4, p 4-byte aligned
-static int fill_list(sh_ctx* c, std::initializer_list<FillEnt> ents) {
+int sh::fill_list(sh_ctx* c, std::initializer_list<FillEnt> ents) {
   FillList L{};
   int k = 0; size_t nmax = 0;
   for (const FillEnt& e : ents) {
@@ -316,7 +43,6 @@ static int fill_list(sh_ctx* c, std::initializer_list<FillEnt> ents) {
   LAUNCH(c, "fill", k_fill_list, dim3(gx, (unsigned)k), dim3(256), L);
   return SH_OK;
 }
-#define FILL(ctx, ...) do { int frc_ = fill_list(ctx, {__VA_ARGS__}); if (frc_ != SH_OK) return frc_; } while (0)
 
 static void drain_timers(sh_ctx* c) {
   for (auto& t : c->pending) {
@@ -333,6 +59,25 @@ static void drain_timers(sh_ctx* c) {
   c->pending.clear();
 }
 
+static int join_prepared(sh_ctx* c) {
+  if (!c->prep.active) return SH_OK;
+  if (c->prep.th.joinable()) c->prep.th.join();
+  c->prep.active = false;
+  if (c->timing) {
+    KTimer& h = c->timers["host.hull"]; h.ms += c->prep.hull_ms; h.n += 1;
+    if (c->prep.d2h_ms > 0) { KTimer& a = c->timers["host.verts_d2h"]; a.ms += c->prep.d2h_ms; a.n += 1; }
+  }
+  return c->prep.rc;      // a failed preparation is simply not used: the run repeats the host phase and reports the error itself
+}
+
+static void discard_staged(sh_ctx* c) {
+  sh_ctx::StageSide& S = c->stg;
+  if (!S.active) return;
+  if (c->prep.staged) { (void)join_prepared(c); c->prep.gen = ~0ull; c->prep.staged = false; }
+  (void)hipEventSynchronize(S.ready_ev);      // nothing reads the pinned staging or writes the staging side any more
+  S.active = false;
+}
+
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -345,6 +90,8 @@ int sh_default_params(sh_params* p) {
   p->bone_kind = SH_BONE_HUMERUS;
   return SH_OK;
 }
+
+}  // extern "C"
 
 // "host" | "device" | "auto" (default).  auto: the host quickhull while this rank has enough usable hardware threads to itself -- 16 when it is
 // the only rank of its host, 48 per rank otherwise -- (it
@@ -377,7 +124,7 @@ static unsigned affinity_threads() {
 // `sustained`: count a CPU quota (it caps the AVERAGE cpu time -- what decides whether a rank can afford host hulls at all); the size
 // of the worker pool goes by the affinity mask alone: a quota does not stop 32 threads from running a 4 ms burst side by side
 // (measured under a 16-CPU quota: hull phase of a 64-batch 4.1 ms with 32 workers, 6.3 ms with 16).
-static unsigned threads_per_local_rank(bool sustained = true) {
+unsigned sh::threads_per_local_rank(bool sustained) {
   unsigned hw = sustained ? usable_threads() : affinity_threads();
   if (const char* w = getenv("LOCAL_WORLD_SIZE")) { int v = atoi(w); if (v > 1) hw = std::max(1u, hw / (unsigned)v); }
   return hw;
@@ -393,6 +140,8 @@ static int hull_mode_from(const char* e) {
   const bool alone = !(w && atoi(w) > 1);
   return threads_per_local_rank() >= (alone ? 16u : 48u) ? 0 : 1;
 }
+
+extern "C" {
 
 int sh_set_hull_mode(sh_ctx* c, const char* mode) {
   if (!c || !mode) return SH_ERR_ARG;
@@ -435,9 +184,6 @@ int sh_ctx_create(int device, void* hip_stream, sh_ctx** out) {
   return SH_OK;
 }
 
-static void unet_turn_forget(sh_ctx* c);
-static void comm_forget(sh_ctx* c);
-
 void sh_ctx_destroy(sh_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -474,9 +220,6 @@ void sh_ctx_destroy(sh_ctx* c) {
   delete c;
 }
 
-static int join_prepared(sh_ctx* c);
-static void discard_staged(sh_ctx* c);
-
 const char* sh_last_error(const sh_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
 
 int sh_set_params(sh_ctx* c, const sh_params* p) {
@@ -512,15 +255,8 @@ int sh_batch_size(const sh_ctx* c) { return c ? c->B : 0; }
 static int alloc_batch(sh_ctx* c) {
   const int B = c->B;
   int rc;
-#define ENS(name, bytes, elem)                                              \
-  do {                                                                      \
-    if ((rc = ensure(c, name, (size_t)(bytes), elem)) != SH_OK) return rc;  \
-    c->bufs[name].per_mesh = (size_t)(bytes) / (size_t)B;                   \
-  } while (0)
-  ENS("verts_obb", c->sumV * 3 * 8, 8);
-  c->bufs["verts_obb"].per_mesh = 0;        // ragged: indexed through voff
-  ENS("verts_csys", c->sumV * 3 * 8, 8);
-  c->bufs["verts_csys"].per_mesh = 0;
+  ENS_SHARED("verts_obb", c->sumV * 3 * 8, 8);        // ragged: indexed through voff
+  ENS_SHARED("verts_csys", c->sumV * 3 * 8, 8);
   c->bufs["voff"].per_mesh = 8;             // a window sees voff[b0 + b] (absolute vertex offsets) as voff[b]
   c->bufs["foff"].per_mesh = 8;
   c->b0 = 0; c->Bwin = B;
@@ -550,8 +286,7 @@ static int alloc_batch(sh_ctx* c) {
     ENS((p + ".ring_n").c_str(), (size_t)B * s.N * 4, 4);
     if (s.ring) ENS((p + ".ring").c_str(), (size_t)B * s.N * (SH_MAXSEG + 1) * 2 * 8, 8);
   }
-  ENS("slices.nlarge", 64, 4);
-  c->bufs["slices.nlarge"].per_mesh = 0;
+  ENS_SHARED("slices.nlarge", 64, 4);
   ENS("prox.ixy", (size_t)B * SH_NPROX * 2 * SH_MPROX * 8, 8);
   ENS("prox.itr_start", (size_t)B * SH_NPROX * 2 * SH_MPROX * 8, 8);
   ENS("prox.itr_centered_start", (size_t)B * SH_NPROX * 2 * SH_MPROX * 8, 8);
@@ -599,16 +334,7 @@ static int alloc_batch(sh_ctx* c) {
   ENS("hull.nv", (size_t)B * 4, 4);
   ENS("hull.nf", (size_t)B * 4, 4);
   ENS("hull.ne", (size_t)B * 4, 4);
-  ENS("hullpre.ext", (size_t)B * SH_HP_NDIR * 4, 4);
-  ENS("hullpre.planes", (size_t)B * SH_HP_MAXPL * 4 * 8, 8);
-  ENS("hullpre.npl", (size_t)B * 4, 4);
-  ENS("hullpre.nkept", (size_t)B * 4, 4);
-  ENS("hullpre.pval", (size_t)B * SH_HP_PARTS * SH_HP_NDIR * 8, 8);
-  ENS("hullpre.pidx", (size_t)B * SH_HP_PARTS * SH_HP_NDIR * 4, 4);
-  ENS("hullpre.pcnt", (size_t)B * SH_HP_PARTS * 4, 4);
-  ENS("hullpre.poff", (size_t)B * SH_HP_PARTS * 8, 8);
-  ENS("hullpre.koff", (size_t)(B + 1) * 8, 8);
-  ENS("hullpre.kept", (size_t)c->sumV * 12, 4);
+  if ((rc = alloc_hullpre(c, B, c->sumV, "")) != SH_OK) return rc;
   if (c->h_kept_cap < c->sumV) {
     if (c->h_kept) (void)hipHostFree(c->h_kept);
     c->h_kept = nullptr; c->h_kept_cap = 0;
@@ -637,37 +363,7 @@ static int alloc_batch(sh_ctx* c) {
   ENS("obb.endpts", (size_t)B * 2 * c->end_cap * 2 * 8, 8);
   ENS("obb.endcnt", (size_t)B * 2 * 4, 4);
   ENS("obb.resid", (size_t)B * 2 * 8, 8);
-#undef ENS
   c->obb_injected = false;
-  return SH_OK;
-}
-
-// Scratch of the device hull (k_hull.h), ~1.6 MB per humerus, allocated on the first run that uses it.
-static int alloc_hulld(sh_ctx* c) {
-  const int B = c->B;
-  int rc;
-#define ENS(name, bytes, elem)                                              \
-  do {                                                                      \
-    if ((rc = ensure(c, name, (size_t)(bytes), elem)) != SH_OK) return rc;  \
-    c->bufs[name].per_mesh = (size_t)(bytes) / (size_t)B;                   \
-  } while (0)
-  ENS("hulld.fv", (size_t)B * HD_SLOTS * 3 * 4, 4);
-  ENS("hulld.vis", (size_t)B * HD_KC * HD_VMAX * 4, 4);
-  ENS("hulld.ev", (size_t)B * HD_KC * 3 * HD_VMAX * 2 * 4, 4);
-  ENS("hulld.hor", (size_t)B * HD_KC * (HD_VMAX + 2) * 2 * 4, 4);
-  ENS("hulld.newslot", (size_t)B * HD_SLOTS * 4, 4);
-  ENS("hulld.freestack", (size_t)B * HD_SLOTS * 4, 4);
-  ENS("hulld.tkeys", (size_t)B * HD_TBL * 8, 8);
-  ENS("hulld.tvals", (size_t)B * HD_TBL * 4, 4);
-  ENS("hulld.fail", (size_t)B * 4, 4);
-  ENS("hulld.rounds", (size_t)B * 4, 4);
-  ENS("hulld.skip", (size_t)B * 4, 4);
-#undef ENS
-  if (c->skip_gen != c->batch_gen) {      // a new batch: the device hull takes every humerus again
-    HIPCHK(c, hipMemsetAsync(c->bufs["hulld.skip"].p, 0, (size_t)B * 4, c->stream));
-    c->skip_gen = c->batch_gen;
-    c->skip_nfmax = 0;
-  }
   return SH_OK;
 }
 
@@ -676,11 +372,6 @@ static int alloc_hulld(sh_ctx* c) {
 static int alloc_prox(sh_ctx* c) {
   const int B = c->B;
   int rc;
-#define ENS(name, bytes, elem)                                              \
-  do {                                                                      \
-    if ((rc = ensure(c, name, (size_t)(bytes), elem)) != SH_OK) return rc;  \
-    c->bufs[name].per_mesh = (size_t)(bytes) / (size_t)B;                   \
-  } while (0)
   const int N = SH_NPSCAN;
   ENS("pobb.zs", (size_t)B * N * 8, 8);
   ENS("pobb.zeff", (size_t)B * N * 8, 8);
@@ -694,7 +385,6 @@ static int alloc_prox(sh_ctx* c) {
   ENS("pobb.cutoff", (size_t)B * 2 * 8, 8);
   ENS("pobb.cutoff_idx", (size_t)B * 2 * 4, 4);
   ENS("neck.gram", (size_t)B * SH_NFULL * SH_NFULL * 8, 8);
-#undef ENS
   return SH_OK;
 }
 
@@ -1226,459 +916,6 @@ int sh_mesh_transformed(sh_ctx* c, int b, const double* T, double* out) {
   return SH_OK;
 }
 
-// ---- UNet forward (f32 MFMA path) ----------------------------------------------------------------------
-static int conv_layer(sh_ctx* c, const char* lname, const sh_ctx::ULayer& L, const float* src0, const float* src1, int C0, int C1, float* dst,
-                      int H, int W, int nimg, int relu, int fuse = 0, float* pooled = nullptr, const float* head_w = nullptr, const float* head_b = nullptr,
-                      float* logits = nullptr, const float* image = nullptr, const float* w0 = nullptr, const float* b0 = nullptr) {
-  if (H % UN_TH || W % UN_TW) return fail(c, SH_ERR_ARG, "unet: feature map is not a multiple of 16");
-  const float* P = buf<float>(c, "params");
-  const float* w = P + L.w_off; const float* b = P + L.b_off;
-  const int tiles = (H / UN_TH) * (W / UN_TW);
-  if (c->params.unet_dtype == SH_UNET_F32X && C0 % 32 == 0 && C1 % 32 == 0 && L.cout % 32 == 0) {
-    // split-f16 operands on the 16-bit matrix pipe (k_unet_x3.h); weights split once per parameter block by unet_forward
-    const u16* wh = buf<u16>(c, "params_x3h") + L.w_off;
-    const u16* wl = buf<u16>(c, "params_x3l") + L.w_off;
-    float* np_ = nullptr; const float* nf_ = nullptr;
-    if (L.taps == 9 && fuse == (UF_FIRST | UF_POOL) && L.cout == 32 && C0 == 32 && C1 == 0) {      // enc0b with enc0a computed while its halo tile is staged
-      LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, UF_FIRST | UF_POOL, 0>), dim3(tiles, 1, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, pooled, nf_, nf_, np_, image, w0, b0);
-    }
-    else if (L.taps == 9 && fuse == UF_HEAD && L.cout == 32) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, UF_HEAD>), dim3(tiles, 1, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, np_, head_w, head_b, logits, nf_, nf_, nf_); }
-    else if (L.taps == 9 && fuse == UF_POOL && L.cout % 64 == 0) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 4, UF_POOL>), dim3(tiles, L.cout / 64, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, pooled, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (L.taps == 9 && fuse == UF_POOL) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, UF_POOL, 0>), dim3(tiles, L.cout / 32, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, pooled, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (fuse != 0) return fail(c, SH_ERR_ARG, "unet: unsupported fusion");
-    else if (L.taps == 9 && L.cout % 64 == 0) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 4>), dim3(tiles, L.cout / 64, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (L.taps == 9) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, 0, 0>), dim3(tiles, L.cout / 32, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (C1 == 0 && W % 32 == 0 && H % 16 == 0 && (C0 == 64 || C0 == 128 || C0 == 256 || C0 == 512)) {
-      // up-convolutions with the source pixels resident in registers (k_upconv_x3r)
-      if (C0 == 64) { LAUNCH(c, lname, (k_upconv_x3r<2, 4>), dim3((W / 32) * (H / 16), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-      else if (C0 == 128) { LAUNCH(c, lname, (k_upconv_x3r<4, 4>), dim3((W / 32) * (H / 16), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-      else if (C0 == 256) { LAUNCH(c, lname, (k_upconv_x3r<8, 2>), dim3((W / 32) * (H / 8), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-      else { LAUNCH(c, lname, (k_upconv_x3r<16, 1>), dim3((W / 32) * (H / 4), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-    }
-    else if (L.cout % 64 == 0) { LAUNCH(c, lname, (k_conv_mfma_x3<1, 4>), dim3(tiles, L.cout / 64, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, 0, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    else { LAUNCH(c, lname, (k_conv_mfma_x3<1, 2>), dim3(tiles, L.cout / 32, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, 0, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    return SH_OK;
-  }
-  if (L.taps == 9) {
-    if (L.cout % 64 == 0) {
-      LAUNCH(c, lname, (k_conv_mfma_f32<9, 4>), dim3(tiles, L.cout / 64, nimg), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu);
-    } else {
-      LAUNCH(c, lname, (k_conv_mfma_f32<9, 2>), dim3(tiles, L.cout / 32, nimg), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu);
-    }
-  } else {
-    if (L.cout % 64 == 0) {
-      LAUNCH(c, lname, (k_conv_mfma_f32<1, 4>), dim3(tiles, L.cout / 64, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0);
-    } else {
-      LAUNCH(c, lname, (k_conv_mfma_f32<1, 2>), dim3(tiles, L.cout / 32, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0);
-    }
-  }
-  return SH_OK;
-}
-
-// ---- UNet turns ----------------------------------------------------------------------------------------
-// Several contexts on one device overlap well when the launch-bound geometry kernels of one run beside the chip-filling
-// UNet kernels of another -- and badly when two UNet passes share the CUs (each just takes twice as long).  Contexts
-// that opted in (sh_set_unet_turns) therefore chain their UNet passes with events, in the order the host enqueued them.
-static std::mutex g_turn_mu;
-static hipEvent_t g_turn_last[64] = {};      // per device: recorded at the end of the most recently enqueued UNet pass
-static sh_ctx* g_turn_owner[64] = {};
-
-static int unet_turn_enter(sh_ctx* c) {
-  if (!c->unet_turn || c->device < 0 || c->device >= 64) return SH_OK;
-  std::lock_guard<std::mutex> lk(g_turn_mu);
-  if (g_turn_last[c->device] && g_turn_owner[c->device] != c) HIPCHK(c, hipStreamWaitEvent(c->stream, g_turn_last[c->device], 0));
-  return SH_OK;
-}
-
-static int unet_turn_leave(sh_ctx* c) {
-  if (!c->unet_turn || c->device < 0 || c->device >= 64) return SH_OK;
-  std::lock_guard<std::mutex> lk(g_turn_mu);
-  if (!c->unet_done_ev) HIPCHK(c, hipEventCreateWithFlags(&c->unet_done_ev, hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(c->unet_done_ev, c->stream));
-  g_turn_last[c->device] = c->unet_done_ev;
-  g_turn_owner[c->device] = c;
-  return SH_OK;
-}
-
-static void unet_turn_forget(sh_ctx* c) {
-  std::lock_guard<std::mutex> lk(g_turn_mu);
-  if (c->device >= 0 && c->device < 64 && g_turn_owner[c->device] == c) { g_turn_last[c->device] = nullptr; g_turn_owner[c->device] = nullptr; }
-}
-
-static int unet_forward(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W) {
-  const int D = c->unet_depth, base = c->unet_base;
-  if ((H >> D) % 16 || (W >> D) % 16) return fail(c, SH_ERR_ARG, "unet: input size must be a multiple of 16 << depth");
-  int rc;
-  const size_t full = (size_t)nimg * H * W * base * 4;
-  if ((rc = ensure(c, "unet.a", full, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "unet.b", full, 4)) != SH_OK) return rc;
-  std::vector<float*> skip(D);
-  for (int i = 0; i < D; ++i) {
-    std::string nm = "unet.skip" + std::to_string(i);
-    if ((rc = ensure(c, nm.c_str(), full >> i, 4)) != SH_OK) return rc;     // H*W/4^i * base*2^i
-    skip[i] = buf<float>(c, nm.c_str());
-  }
-  float* A = buf<float>(c, "unet.a");
-  float* Bq = buf<float>(c, "unet.b");
-  const float* P = buf<float>(c, "params");
-  if (c->params.unet_dtype == SH_UNET_F32X) {      // split the MFMA layers' weights into f16 high / low parts: one launch, once per parameter block
-    if ((rc = ensure(c, "params_x3h", c->unet_floats * 2, 2)) != SH_OK) return rc;
-    if ((rc = ensure(c, "params_x3l", c->unet_floats * 2, 2)) != SH_OK) return rc;
-    if (!c->packed_x3) {
-      std::vector<PackEntry> tab;
-      long long total = 0;
-      for (auto& kv : c->ulayers) {
-        const sh_ctx::ULayer& l = kv.second;
-        if (l.cin < 32 || l.cout < 32) continue;
-        tab.push_back(PackEntry{total, (long long)l.w_off, l.taps, l.cin, l.cout, 0});
-        total += (long long)l.taps * l.cin * l.cout;
-        // range of the split: 64 w must be a finite f16 (|w| < 65504 / 64); beyond it the high part is an infinity and the layer's
-        // outputs NaN, silently (include/shoulder_hip.h, SH_UNET_F32X)
-        if (c->h_unet.size() >= l.w_off + (size_t)l.taps * l.cin * l.cout) {
-          const float* wl = c->h_unet.data() + l.w_off;
-          for (size_t i = 0, n = (size_t)l.taps * l.cin * l.cout; i < n; ++i)
-            if (!(fabsf(wl[i]) < 65504.0f / X3_WSCALE)) {
-              char m[200];
-              snprintf(m, sizeof m, "SH_UNET_F32X: layer %s has a weight of magnitude %g; the split-f16 operands hold |w| < %g (use SH_UNET_F32 for this network)",
-                       kv.first.c_str(), (double)fabsf(wl[i]), (double)(65504.0f / X3_WSCALE));
-              return fail(c, SH_ERR_ARG, m);
-            }
-        }
-      }
-      if ((rc = ensure(c, "unet16.packtab", tab.size() * sizeof(PackEntry), 8)) != SH_OK) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->bufs["unet16.packtab"].p, tab.data(), tab.size() * sizeof(PackEntry), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
-      c->packtab_ready = true;
-      LAUNCH(c, "k_pack_w_x3", k_pack_w_x3, dim3(2048), dim3(256), P, buf<u16>(c, "params_x3h"), buf<u16>(c, "params_x3l"), (const PackEntry*)c->bufs["unet16.packtab"].p, (int)tab.size(), total);
-      c->packed_x3 = true;
-    }
-  }
-  auto L = [&](const std::string& n) -> const sh_ctx::ULayer& { return c->ulayers[n]; };
-  int h = H, w = W;
-  // SH_UNET_F32X: the 2x2 pools ride in the epilogue of the conv before them (k_unet_x3.h), and with 32 base channels the first
-  // conv is computed inside enc0b's staging
-  const bool x3 = c->params.unet_dtype == SH_UNET_F32X && base % 32 == 0;
-  const bool x3_first = x3 && base == 32;
-  if (!x3_first) {
-    const sh_ctx::ULayer& l = L("enc0a");
-    size_t npx = (size_t)nimg * h * w;
-    LAUNCH(c, "unet.enc0a", k_conv_first, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), image, P + l.w_off, P + l.b_off, A, h, w, l.cout, nimg);
-  }
-  if (x3_first) {
-    const sh_ctx::ULayer& l = L("enc0a");
-    if ((rc = conv_layer(c, "unet.enc0b", L("enc0b"), A, nullptr, base, 0, skip[0], h, w, nimg, 1, UF_FIRST | UF_POOL, Bq, nullptr, nullptr, nullptr, image, P + l.w_off, P + l.b_off)) != SH_OK) return rc;
-  } else if ((rc = conv_layer(c, "unet.enc0b", L("enc0b"), A, nullptr, base, 0, skip[0], h, w, nimg, 1, x3 ? UF_POOL : 0, Bq)) != SH_OK) return rc;
-  if (x3) std::swap(A, Bq);      // (the pooled tensor is the next level's input, which the loop below reads from A)
-  int ch = base;
-  for (int i = 1; i <= D; ++i) {
-    if (!x3) {
-      size_t e = (size_t)nimg * (h / 2) * (w / 2) * (ch / 4);
-      LAUNCH(c, "unet.pool", k_maxpool2, dim3((unsigned)std::min<size_t>((e + 255) / 256, 8192)), dim3(256), skip[i - 1], A, h, w, ch, nimg);
-    }
-    h /= 2; w /= 2;
-    std::string na = i < D ? "enc" + std::to_string(i) + "a" : "bota", nb = i < D ? "enc" + std::to_string(i) + "b" : "botb";
-    if ((rc = conv_layer(c, ("unet." + na).c_str(), L(na), A, nullptr, ch, 0, Bq, h, w, nimg, 1)) != SH_OK) return rc;
-    ch *= 2;
-    float* dst = i < D ? skip[i] : A;
-    // (A was consumed by the conv above: with the fused pool it receives the next level's input)
-    if ((rc = conv_layer(c, ("unet." + nb).c_str(), L(nb), Bq, nullptr, ch, 0, dst, h, w, nimg, 1, (x3 && i < D) ? UF_POOL : 0, A)) != SH_OK) return rc;
-  }
-  // decoder: x lives in A
-  float* x = A; float* y = Bq;
-  for (int i = D - 1; i >= 0; --i) {
-    std::string nu = "up" + std::to_string(i), na = "dec" + std::to_string(i) + "a", nb = "dec" + std::to_string(i) + "b";
-    if ((rc = conv_layer(c, ("unet." + nu).c_str(), L(nu), x, nullptr, ch, 0, y, h, w, nimg, 0)) != SH_OK) return rc;
-    h *= 2; w *= 2; ch /= 2;
-    if ((rc = conv_layer(c, ("unet." + na).c_str(), L(na), skip[i], y, ch, ch, x, h, w, nimg, 1)) != SH_OK) return rc;
-    // (the head stays on k_head: its sequential f32 chain over the channels is the exact path's; fused into dec0b's epilogue the
-    //  logits move by another ~1e-6 and one mask pixel of the 64-humerus bench batch flips)
-    if ((rc = conv_layer(c, ("unet." + nb).c_str(), L(nb), x, nullptr, ch, 0, y, h, w, nimg, 1)) != SH_OK) return rc;
-    std::swap(x, y);
-  }
-  {
-    const sh_ctx::ULayer& l = L("head");
-    size_t npx = (size_t)nimg * H * W;
-    if (l.cin <= 32) { LAUNCH(c, "unet.head", k_head<32>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 16384)), dim3(256), x, P + l.w_off, P + l.b_off, logits, l.cin, npx); }
-    else { LAUNCH(c, "unet.head", k_head<64>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), x, P + l.w_off, P + l.b_off, logits, l.cin, npx); }
-  }
-  return SH_OK;
-}
-
-}  // extern "C" (the templates below need C++ linkage)
-
-// ---- UNet forward (16-bit MFMA paths: EK = 0 __bf16, 1 _Float16; tensors as raw u16) -----------------------------------------
-#define SH_UNET_TICKETS 64
-#define SH_UNET_TKTAB (1 << 18)
-// Workgroups of a persistent UNet launch.  Each takes a whole CU (its LDS, all of its registers), so while one is resident no
-// other kernel can start there: beside the UNet pass of one lane, every launch of the other lane's geometry chain (~40 per step)
-// waited ~50 us for a workgroup to end, and the chain took 7-8 ms instead of 3.2.  Contexts that take turns on a device
-// (sh_set_unet_turns: there IS another lane) therefore leave 32 CUs (4 per XCD) out of the grid; the work tickets spread the
-// items over whatever grid there is.  Measured on the two-lane headline: 0 / 8 / 16 / 32 / 48 / 64 / 96 reserved -> 8.72 / 8.80 /
-// 8.73 / 8.27 / 8.54 / 8.56 / 9.35 ms per step.
-static int persistent_grid(sh_ctx* c) {
-  constexpr int cu_reserve = 32;
-  if (c->num_cus <= 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) v = 0; c->num_cus = v > 0 ? v : 256; }
-  return c->unet_turn ? std::max(8, c->num_cus - cu_reserve) : c->num_cus;
-}
-
-// work tickets of a persistent launch: the next free counter of this forward pass and the table of item bounds of runs of decreasing
-// length for (items, workgroups, cout groups) -- every ticket a third of what would be a fair share of the remaining items, whole
-// cout-group sets of a tile (its input tile comes from HBM once) -- built once per shape
-static int unet_tickets(sh_ctx* c, int total, int nwg, int ngrp, unsigned** tk, const int** tk_tab, int* ntk) {
-  const auto key = std::make_tuple(total, nwg, ngrp);
-  auto it = c->tk_tabs.find(key);
-  if (it == c->tk_tabs.end()) {
-    std::vector<int> tab;
-    int pos = 0;
-    while (pos < total) {
-      int sz = std::max(1, (int)std::ceil((total - pos) / (3.0 * (double)nwg)));
-      if (sz >= ngrp) sz = sz / ngrp * ngrp;
-      tab.push_back(pos);
-      pos += std::min(sz, total - pos);
-    }
-    tab.push_back(total);
-    if ((int)tab.size() > SH_UNET_TKTAB) return fail(c, SH_ERR_CAPACITY, "unet: ticket table larger than its buffer");
-    if (c->tk_tab_used + (int)tab.size() > SH_UNET_TKTAB) {      // many different shapes (sh_unet_infer with varying n): start the cache over
-      HIPCHK(c, hipStreamSynchronize(c->stream));                  // (launches that read the old tables are done)
-      c->tk_tabs.clear();
-      c->tk_tab_used = 0;
-    }
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, "unet16.tk_tab") + c->tk_tab_used, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
-    it = c->tk_tabs.emplace(key, std::make_pair(c->tk_tab_used, (int)tab.size() - 1)).first;
-    c->tk_tab_used += (int)tab.size();
-  }
-  if (c->ticket_next >= SH_UNET_TICKETS) return fail(c, SH_ERR_CAPACITY, "unet: out of work counters");
-  *tk = buf<unsigned>(c, "unet16.tickets") + c->ticket_next++;
-  *tk_tab = buf<int>(c, "unet16.tk_tab") + it->second.first;
-  *ntk = it->second.second;
-  return SH_OK;
-}
-
-// One layer of the 16-bit network.  3x3 convs with a multiple of 64 output channels on 32 x 16-tileable maps run on the persistent
-// LDS-DMA kernel (k_unet16_ldr.h; UF_POOL: the 2x2 max pool written beside the output); 2x2 transposed convs on k_upconv16g /
-// k_upconv16; everything else on the generic two-barrier kernel k_conv_mfma16 (k_unet_bf16.h), which is also the whole of the
-// REFERENCE network (sh_ctx::unet_reference: layer by layer, nothing fused, no persistent kernel -- what the tests hold the
-// production kernels against).
-template <int EK>
-static int conv_layer16(sh_ctx* c, const char* lname, const sh_ctx::ULayer& L, const u16* src0, const u16* src1, int C0, int C1,
-                           u16* dst, int H, int W, int nimg, int relu, int fuse = 0, ConvFuse fz = ConvFuse{}) {
-  if (H % UN_TH || W % UN_TW) return fail(c, SH_ERR_ARG, "unet: feature map is not a multiple of 16");
-  const u16* w = buf<u16>(c, "params_bf16") + L.w_off;
-  const float* b = buf<float>(c, "params") + L.b_off;
-  const int tiles = (H / UN_TH) * (W / UN_TW);
-  const dim3 blk(UN_THREADS);
-  const bool ldr = !c->unet_reference && L.taps == 9 && L.cout % 64 == 0 && L.cout <= 512 && W % 32 == 0 && H % 16 == 0 && C0 % 32 == 0 && C1 % 32 == 0 &&
-                   (fuse == 0 || (fuse == UF_POOL && relu));      // (its fused pool works on ReLU'd values)
-  if (ldr) {
-    int rc0;
-    if ((rc0 = ensure(c, "unet16.zero", 256, 2)) != SH_OK) return rc0;
-    if (!c->zero_page_ready) { HIPCHK(c, hipMemsetAsync(buf<char>(c, "unet16.zero"), 0, 256, c->stream)); c->zero_page_ready = true; }
-    const int total = nimg * (W / 32) * (H / 16) * (L.cout / 64);
-    const dim3 g((unsigned)std::min(total, persistent_grid(c)));
-    unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-    if ((rc0 = unet_tickets(c, total, (int)g.x, L.cout / 64, &tk, &tk_tab, &ntk)) != SH_OK) return rc0;
-    const u16* zp = (const u16*)c->bufs["unet16.zero"].p;
-    u16* pl = fuse == UF_POOL ? (u16*)fz.pooled : (u16*)nullptr;
-    // weights resident in LDS: one cout group whose packed weights fit behind the two input buffers (32 -> 64 and 64 -> 64 layers)
-    const bool wres = L.cout == 64 && ((C0 + C1) / 32) * 64 <= 128;
-    if (fuse == UF_POOL && wres) { LAUNCH(c, lname, (k_conv3_ldr16<EK, UF_POOL, 1>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-    else if (fuse == UF_POOL) { LAUNCH(c, lname, (k_conv3_ldr16<EK, UF_POOL, 0>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-    else if (wres) { LAUNCH(c, lname, (k_conv3_ldr16<EK, 0, 1>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-    else { LAUNCH(c, lname, (k_conv3_ldr16<EK, 0, 0>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-  } else if (L.taps == 9 && L.cout % 64 == 0) {
-    const dim3 g(tiles, L.cout / 64, nimg);
-    if (fuse == 0) { LAUNCH(c, lname, (k_conv_mfma16<EK, 9, 4, 0>), g, blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, fz); }
-    else if (fuse == UF_POOL) { LAUNCH(c, lname, (k_conv_mfma16<EK, 9, 4, UF_POOL>), g, blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, fz); }
-    else return fail(c, SH_ERR_ARG, "unet: unsupported fusion");
-  } else if (L.taps == 9) {
-    const dim3 g(tiles, L.cout / 32, nimg);
-    if (fuse == 0) { LAUNCH(c, lname, (k_conv_mfma16<EK, 9, 2, 0>), g, blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, fz); }
-    else return fail(c, SH_ERR_ARG, "unet: unsupported fusion");
-  } else if (!c->unet_reference && L.cout % 32 == 0 && C1 == 0 && C0 % 32 == 0) {
-    // 2x2 transposed conv (k_unet16_up.h): source pixels in registers, the weights of a 32-cout group by LDS-DMA, one barrier per
-    // group (Cin = 512: per two phases); the staged form otherwise
-    const bool upg = W % 32 == 0 && H % 16 == 0 && (C0 == 128 || C0 == 256 || C0 == 512) && L.cout <= 512;
-    if (upg) {
-      // items = (image, source tile of 32 x 4 MT pixels) on the grid of the persistent convolutions, handed out by work tickets; up3 has
-      // about one item per CU: one workgroup per item
-      const int mt = C0 == 128 ? 4 : 2, nitems = (W / 32) * (H / (4 * mt)) * nimg;
-      const int grid = C0 == 512 ? nitems : std::min(nitems, persistent_grid(c));
-      unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-      if (C0 != 512) { const int trc = unet_tickets(c, nitems, grid, 1, &tk, &tk_tab, &ntk); if (trc != SH_OK) return trc; }
-      if (C0 == 128) { LAUNCH(c, lname, (k_upconv16g<EK, 4, 4, 4, true>), dim3((unsigned)grid), dim3(UPR_THREADS), src0, w, b, dst, H, W, L.cout, nimg, tk, tk_tab, ntk); }
-      else if (C0 == 256) { LAUNCH(c, lname, (k_upconv16g<EK, 8, 2, 4, true>), dim3((unsigned)grid), dim3(UPR_THREADS), src0, w, b, dst, H, W, L.cout, nimg, tk, tk_tab, ntk); }
-      else { LAUNCH(c, lname, (k_upconv16g<EK, 16, 2, 2, false>), dim3((unsigned)grid), dim3(UPR_THREADS), src0, w, b, dst, H, W, L.cout, nimg, tk, tk_tab, ntk); }
-    }
-    else { LAUNCH(c, lname, (k_upconv16<EK>), dim3(tiles, L.cout / 32, nimg * 2), dim3(UPC_THREADS), src0, C0, w, b, dst, H, W, L.cout); }
-  } else if (L.cout % 64 == 0) {
-    LAUNCH(c, lname, (k_conv_mfma16<EK, 1, 4, 0>), dim3(tiles, L.cout / 64, nimg * 4), blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0, fz);
-  } else {
-    LAUNCH(c, lname, (k_conv_mfma16<EK, 1, 2, 0>), dim3(tiles, L.cout / 32, nimg * 4), blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0, fz);
-  }
-  return SH_OK;
-}
-
-// does the 16-bit forward run its fused level-0 kernels (k_unet16_pp.h)?  (run_window asks: k_enc0_pp can read the unscaled image)
-static bool unet16_level0_fused(const sh_ctx* c, int H, int W) {
-  return !c->unet_reference && c->unet_base == 32 && c->unet_depth >= 1 && W % 32 == 0 && H % 16 == 0 && (H >> c->unet_depth) % 16 == 0 && (W >> c->unet_depth) % 16 == 0;
-}
-static bool unet16_starts_fused(const sh_ctx* c, int H, int W) { return unet16_level0_fused(c, H, W); }
-
-// Double-conv UNet, 16-bit.  With 32 base channels the full-resolution level runs as three fused ping-pong kernels (k_unet16_pp.h:
-// image -> enc0a -> enc0b -> skip0 + pool; up0 + dec0a; dec0b + head) and every 2x2 max pool rides in the epilogue of the conv before
-// it.  Other widths, maps that do not tile, and the reference network run layer by layer.
-template <int EK>
-static int unet_forward16(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W) {
-  const int D = c->unet_depth, base = c->unet_base;
-  if ((H >> D) % 16 || (W >> D) % 16) return fail(c, SH_ERR_ARG, "unet: input size must be a multiple of 16 << depth");
-  int rc;
-  if ((rc = ensure(c, "params_bf16", c->unet_floats * 2, 2)) != SH_OK) return rc;
-  const float* P = buf<float>(c, "params");
-  u16* PW = buf<u16>(c, "params_bf16");
-  if (c->packed_kind != EK) {     // pack the MFMA layers' weights for this element type: one launch for all layers, once per parameter block
-    std::vector<PackEntry> tab;
-    long long total = 0;
-    for (auto& kv : c->ulayers) {
-      const sh_ctx::ULayer& l = kv.second;
-      if (l.cin < 32 || l.cout < 32) continue;
-      tab.push_back(PackEntry{total, (long long)l.w_off, l.taps, l.cin, l.cout, 0});
-      total += (long long)l.taps * l.cin * l.cout;
-    }
-    if ((rc = ensure(c, "unet16.packtab", tab.size() * sizeof(PackEntry), 8)) != SH_OK) return rc;
-    if (!c->packtab_ready) {
-      HIPCHK(c, hipMemcpyAsync(c->bufs["unet16.packtab"].p, tab.data(), tab.size() * sizeof(PackEntry), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
-      c->packtab_ready = true;
-    }
-    LAUNCH(c, "k_pack_w_bf16", k_pack_w16_all<EK>, dim3(2048), dim3(256), P, PW, (const PackEntry*)c->bufs["unet16.packtab"].p, (int)tab.size(), total);
-    c->packed_kind = EK;
-  }
-  if ((rc = ensure(c, "unet16.tickets", SH_UNET_TICKETS * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "unet16.tk_tab", SH_UNET_TKTAB * 4, 4)) != SH_OK) return rc;
-  FILL(c, {buf<unsigned>(c, "unet16.tickets"), (size_t)SH_UNET_TICKETS * 4, 0});
-  c->ticket_next = 0;
-  const bool fused = unet16_level0_fused(c, H, W);      // level 0 on the ping-pong kernels, pools in the conv epilogues
-  const size_t full = (size_t)nimg * H * W * base * 2;
-  if ((rc = ensure(c, "unet16.a", full, 2)) != SH_OK) return rc;
-  if ((rc = ensure(c, "unet16.b", full, 2)) != SH_OK) return rc;
-  std::vector<u16*> skip(D);
-  for (int i = 0; i < D; ++i) {
-    std::string nm = "unet16.skip" + std::to_string(i);
-    if ((rc = ensure(c, nm.c_str(), full >> i, 2)) != SH_OK) return rc;
-    skip[i] = buf<u16>(c, nm.c_str());
-  }
-  u16* A = buf<u16>(c, "unet16.a");
-  u16* Bq = buf<u16>(c, "unet16.b");
-  auto L = [&](const std::string& n) -> const sh_ctx::ULayer& { return c->ulayers[n]; };
-  if ((rc = ensure(c, "unet16.zero", 256, 2)) != SH_OK) return rc;
-  if (!c->zero_page_ready) { HIPCHK(c, hipMemsetAsync(buf<char>(c, "unet16.zero"), 0, 256, c->stream)); c->zero_page_ready = true; }
-  const u16* zp = (const u16*)c->bufs["unet16.zero"].p;
-  int h = H, w = W;
-  if (fused) {
-    // level-0 encoder (k_enc0_pp): image -> enc0a -> LDS -> enc0b -> skip0 + pooled
-    const sh_ctx::ULayer& la = L("enc0a");
-    const sh_ctx::ULayer& lb = L("enc0b");
-    const int total = nimg * (w / 32) * (h / 16);
-    const unsigned grid = (unsigned)std::min(total, persistent_grid(c));
-    unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-    if ((rc = unet_tickets(c, total, (int)grid, 1, &tk, &tk_tab, &ntk)) != SH_OK) return rc;
-    LAUNCH_FN(c, "unet.enc0b", launch_enc0_pp(EK, grid, c->stream, image, P + la.w_off, P + la.b_off, PW + lb.w_off, P + lb.b_off, skip[0], A, h, w, nimg,
-                                              c->unet_raw, c->unet_mm, tk, tk_tab, ntk));
-  } else {
-    const sh_ctx::ULayer& l = L("enc0a");
-    size_t npx = (size_t)nimg * h * w;
-    LAUNCH(c, "unet.enc0a", k_conv_first16<EK>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), image, P + l.w_off, P + l.b_off, A, h, w, l.cout, nimg);
-    if ((rc = conv_layer16<EK>(c, "unet.enc0b", L("enc0b"), A, nullptr, base, 0, skip[0], h, w, nimg, 1)) != SH_OK) return rc;
-  }
-  int ch = base;
-  for (int i = 1; i <= D; ++i) {
-    if (!fused) {
-      size_t e = (size_t)nimg * (h / 2) * (w / 2) * (ch / 8);
-      LAUNCH(c, "unet.pool", k_maxpool2_16<EK>, dim3((unsigned)std::min<size_t>((e + 255) / 256, 8192)), dim3(256), skip[i - 1], A, h, w, ch, nimg);
-    }
-    h /= 2; w /= 2;
-    std::string na = i < D ? "enc" + std::to_string(i) + "a" : "bota", nb = i < D ? "enc" + std::to_string(i) + "b" : "botb";
-    if ((rc = conv_layer16<EK>(c, ("unet." + na).c_str(), L(na), A, nullptr, ch, 0, Bq, h, w, nimg, 1)) != SH_OK) return rc;
-    ch *= 2;
-    u16* dst = i < D ? skip[i] : A;
-    ConvFuse fz{};
-    fz.pooled = A;      // (A was consumed by the conv above; the next level reads it)
-    if ((rc = conv_layer16<EK>(c, ("unet." + nb).c_str(), L(nb), Bq, nullptr, ch, 0, dst, h, w, nimg, 1, (fused && i < D) ? UF_POOL : 0, fz)) != SH_OK) return rc;
-  }
-  u16* x = A; u16* y = Bq;
-  for (int i = D - 1; i >= 0; --i) {
-    std::string nu = "up" + std::to_string(i), na = "dec" + std::to_string(i) + "a", nb = "dec" + std::to_string(i) + "b";
-    if (fused && i == 0) {
-      // level 0: the up-convolution computed inside dec0a (k_dec0a_up_pp: x = low-resolution input, y = dec0a's output), then
-      // dec0b with the 1x1 head in its epilogue (k_dec0b_head_pp: only the logits leave the kernel)
-      h *= 2; w *= 2; ch /= 2;
-      const sh_ctx::ULayer& lu = L(nu);
-      const sh_ctx::ULayer& la = L(na);
-      const sh_ctx::ULayer& lb = L(nb);
-      const sh_ctx::ULayer& lh = L("head");
-      {
-        const int total = nimg * (w / 32) * (h / 8);
-        const unsigned grid = (unsigned)std::min(total, persistent_grid(c));
-        unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-        if ((rc = unet_tickets(c, total, (int)grid, 1, &tk, &tk_tab, &ntk)) != SH_OK) return rc;
-        LAUNCH_FN(c, "unet.dec0a", launch_dec0a_up_pp(EK, grid, c->stream, skip[0], x, PW + la.w_off, P + la.b_off, PW + lu.w_off, P + lu.b_off, y, h, w, nimg,
-                                                      zp, tk, tk_tab, ntk));
-      }
-      {
-        const int total = nimg * (w / 32) * (h / 16);
-        const unsigned grid = (unsigned)std::min(total, persistent_grid(c));
-        unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-        if ((rc = unet_tickets(c, total, (int)grid, 1, &tk, &tk_tab, &ntk)) != SH_OK) return rc;
-        LAUNCH_FN(c, "unet.dec0b", launch_dec0b_head_pp(EK, grid, c->stream, y, PW + lb.w_off, P + lb.b_off, P + lh.w_off, P + lh.b_off, logits, h, w, nimg,
-                                                        zp, tk, tk_tab, ntk));
-      }
-      return SH_OK;
-    }
-    if ((rc = conv_layer16<EK>(c, ("unet." + nu).c_str(), L(nu), x, nullptr, ch, 0, y, h, w, nimg, 0)) != SH_OK) return rc;
-    h *= 2; w *= 2; ch /= 2;
-    if ((rc = conv_layer16<EK>(c, ("unet." + na).c_str(), L(na), skip[i], y, ch, ch, x, h, w, nimg, 1)) != SH_OK) return rc;
-    if ((rc = conv_layer16<EK>(c, ("unet." + nb).c_str(), L(nb), x, nullptr, ch, 0, y, h, w, nimg, 1)) != SH_OK) return rc;
-    std::swap(x, y);
-  }
-  {
-    const sh_ctx::ULayer& l = L("head");
-    size_t npx = (size_t)nimg * H * W;
-    LAUNCH(c, "unet.head", k_head16<EK>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), x, P + l.w_off, P + l.b_off, logits, l.cin, npx, (size_t)H * W);
-  }
-  return SH_OK;
-}
-
-static int unet_dispatch(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W) {
-  switch (c->params.unet_dtype) {
-    case SH_UNET_BF16: return unet_forward16<0>(c, image, logits, nimg, H, W);
-    case SH_UNET_F16: return unet_forward16<1>(c, image, logits, nimg, H, W);
-    default: return unet_forward(c, image, logits, nimg, H, W);
-  }
-}
-
-extern "C" {
-
-// The network alone (the `ort.InferenceSession.run` call of anatomic_neck.py:67-76): n images
-// [n][H][W] float32 on the host -> logits [n][H][W] float32 on the host, in the precision sh_params.unet_dtype selects.
-int sh_unet_infer(sh_ctx* c, const float* images, int n, int H, int W, float* logits) {
-  if (!c || !images || !logits || n <= 0 || H <= 0 || W <= 0) return fail(c, SH_ERR_ARG, "sh_unet_infer: bad argument");
-  if (c->ulayers.empty()) return fail(c, SH_ERR_STATE, "sh_unet_infer: no UNet weights loaded");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)n * H * W * 4;
-  int rc;
-  if ((rc = ensure(c, "infer.image", bytes, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "infer.logits", bytes, 4)) != SH_OK) return rc;
-  const int b0 = c->b0; c->b0 = 0;      // named buffers below are whole-batch
-  HIPCHK(c, hipMemcpyAsync(buf<float>(c, "infer.image"), images, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = unet_dispatch(c, buf<float>(c, "infer.image"), buf<float>(c, "infer.logits"), n, H, W);
-  c->b0 = b0;
-  if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-  HIPCHK(c, hipMemcpyAsync(logits, buf<float>(c, "infer.logits"), bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
 // ---- stage runner ----------------------------------------------------------------------------------
 // ---- overflow planes of the slice layer (k_ovf.h) --------------------------------------------------------
 static int ovf_pools(sh_ctx* c, OvfPools* P) {
@@ -1805,238 +1042,6 @@ static int run_slice_set(sh_ctx* c, const char* pfx, int kind, int N, bool ring,
   return run_slice_sets(c, &sp, 1);
 }
 
-// The hull's input points.  Host-provided batch: the caller's vertices.  Device-generated batch: the prefilter
-// (k_hullpre.h) drops the vertices strictly inside a 26-direction polytope on the device and only the rest comes back
-// (39 % of a humerus, into pinned memory).  Callable from the background thread: no buffer-map access, no timers.
-struct HullPre { const float* verts; const long long* voff; int* ext; double* planes; int* npl; float* kept; int* nkept; long long* koff; double* pval; int* pidx; int* pcnt; long long* poff; };
-static HullPre hullpre_ptrs(sh_ctx* c) {      // calling thread only (buffer map)
-  return HullPre{(const float*)c->bufs["verts"].p, (const long long*)c->bufs["voff"].p, (int*)c->bufs["hullpre.ext"].p, (double*)c->bufs["hullpre.planes"].p,
-                 (int*)c->bufs["hullpre.npl"].p, (float*)c->bufs["hullpre.kept"].p, (int*)c->bufs["hullpre.nkept"].p, (long long*)c->bufs["hullpre.koff"].p,
-                 (double*)c->bufs["hullpre.pval"].p, (int*)c->bufs["hullpre.pidx"].p, (int*)c->bufs["hullpre.pcnt"].p, (long long*)c->bufs["hullpre.poff"].p};
-}
-// the five launches of the device prefilter (k_hullpre.h): survivors of all B humeri compacted into hp.kept at hp.koff
-static void launch_prefilter(const HullPre& hp, int B, hipStream_t st) {
-  hipLaunchKernelGGL(k_hullpre_extremes, dim3(SH_HP_PARTS, B), dim3(256), 0, st, hp.verts, hp.voff, hp.pval, hp.pidx);
-  hipLaunchKernelGGL(k_hullpre_polytope, dim3(B), dim3(256), 0, st, hp.verts, hp.voff, (const double*)hp.pval, (const int*)hp.pidx, hp.ext, hp.planes, hp.npl);
-  hipLaunchKernelGGL(k_hullpre_filter<false>, dim3(SH_HP_PARTS, B), dim3(256), 0, st, hp.verts, hp.voff, (const double*)hp.planes, (const int*)hp.npl,
-                     (const long long*)hp.poff, hp.kept, hp.pcnt);
-  hipLaunchKernelGGL(k_hullpre_offsets, dim3(1), dim3(64), 0, st, (const int*)hp.pcnt, hp.koff, hp.poff, hp.nkept, B);
-  hipLaunchKernelGGL(k_hullpre_filter<true>, dim3(SH_HP_PARTS, B), dim3(256), 0, st, hp.verts, hp.voff, (const double*)hp.planes, (const int*)hp.npl,
-                     (const long long*)hp.poff, hp.kept, hp.pcnt);
-}
-
-// survivors of the device prefilter of a batch of B humeri (sumV vertices in all) -> pinned h_kept / h_koff, described by *out
-static hipError_t fetch_prefiltered(const HullPre& hp, int B, long long sumV, long long* h_koff, float* h_kept, sh_ctx::HullPts* out, hipStream_t st) {
-  hipError_t e;
-  launch_prefilter(hp, B, st);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(h_koff, hp.koff, (size_t)(B + 1) * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-  const long long total = h_koff[B];
-  if (total < 0 || total > sumV) return hipErrorUnknown;
-  if (total > 0 && (e = hipMemcpyAsync(h_kept, hp.kept, (size_t)total * 12, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;      // one copy for the batch
-  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-  out->off.resize(B); out->cnt.resize(B);
-  for (int b = 0; b < B; ++b) { out->off[b] = h_koff[b]; out->cnt[b] = (int)(h_koff[b + 1] - h_koff[b]); }
-  out->src = h_kept;
-  return hipSuccess;
-}
-
-static hipError_t fetch_hull_points(sh_ctx* c, const HullPre& hp, hipStream_t st) {
-  const int B = c->B;
-  sh_ctx::HullPts& in = c->hull_in;
-  in.cnt.resize(B);
-  if (c->h_verts_valid) {
-    in.off.assign(c->h_voff.begin(), c->h_voff.begin() + B);
-    for (int b = 0; b < B; ++b) in.cnt[b] = (int)(c->h_voff[b + 1] - c->h_voff[b]);
-    in.src = c->h_verts.data();
-    return hipSuccess;
-  }
-  hipError_t e;
-  if (!c->sw.hull_prefilter || !hp.kept) {
-    c->h_verts.resize(3 * (size_t)c->sumV);
-    if ((e = hipMemcpyAsync(c->h_verts.data(), hp.verts, c->sumV * 3 * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
-    in.off.assign(c->h_voff.begin(), c->h_voff.begin() + B);
-    for (int b = 0; b < B; ++b) in.cnt[b] = (int)(c->h_voff[b + 1] - c->h_voff[b]);
-    in.src = c->h_verts.data();
-    return hipSuccess;
-  }
-  return fetch_prefiltered(hp, B, c->sumV, c->h_koff, c->h_kept, &in, st);
-}
-
-// Process-wide worker pool of the host hull phase.  A job is a callable every participating thread runs to completion
-// (the callable itself hands out mesh indices through an atomic counter); run() returns when all workers that picked
-// the job up have left it.  Jobs of different contexts queue up FIFO and are served by the same threads.
-class HullPool {
- public:
-  static HullPool& instance() { static HullPool p; return p; }
-  static unsigned thread_count() {
-    unsigned nt = std::min(threads_per_local_rank(false), 32u);      // (affinity mask / LOCAL_WORLD_SIZE aware)
-    if (const char* e = getenv("SHOULDER_HULL_THREADS")) { int v = atoi(e); if (v > 0) nt = (unsigned)v; }
-    return nt;
-  }
-  void run(const std::function<void()>& fn, int items) {
-    Job job;
-    job.fn = fn;
-    job.want = (int)std::min<unsigned>(std::max(1, items), (unsigned)workers_.size() + 1) - 1;      // helpers besides the caller
-    if (job.want > 0) {
-      { std::lock_guard<std::mutex> lk(mu_); queue_.push_back(&job); }
-      cv_.notify_all();
-    }
-    fn();                                    // the caller takes part
-    if (job.want > 0) {
-      std::unique_lock<std::mutex> lk(mu_);
-      // helpers that have not started yet are no longer needed (the counter inside fn is exhausted): withdraw the job
-      auto it = std::find(queue_.begin(), queue_.end(), &job);
-      if (it != queue_.end()) queue_.erase(it);
-      done_cv_.wait(lk, [&] { return job.active == 0; });
-    }
-  }
-
- private:
-  struct Job { std::function<void()> fn; int want = 0, taken = 0, active = 0; };
-  HullPool() {
-    const unsigned nt = thread_count();
-    for (unsigned t = 1; t < nt; ++t) workers_.emplace_back([this] { loop(); });
-  }
-  ~HullPool() {
-    { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
-    cv_.notify_all();
-    for (auto& t : workers_) t.join();
-  }
-  void loop() {
-    std::unique_lock<std::mutex> lk(mu_);
-    for (;;) {
-      cv_.wait(lk, [&] { return stop_ || !queue_.empty(); });
-      if (stop_) return;
-      Job* j = queue_.front();
-      ++j->taken; ++j->active;
-      if (j->taken >= j->want) queue_.pop_front();
-      lk.unlock();
-      j->fn();
-      lk.lock();
-      if (--j->active == 0) done_cv_.notify_all();
-    }
-  }
-  std::mutex mu_;
-  std::condition_variable cv_, done_cv_;
-  std::deque<Job*> queue_;
-  std::vector<std::thread> workers_;
-  bool stop_ = false;
-};
-
-// mesh.py:63-125.  Host: one quickhull per humerus on worker threads (sh_hull.h).  Device: candidate
-// boxes for every hull face, pick + frame, end sections, circle fits, flip (k_obb.h).
-// Host phase of the OBB stage for meshes [b0, b0 + B): one quickhull per humerus on worker threads into pinned slot
-// `slot`.  Callable from the background thread: touches no error string, no timers; HIP errors come back as text.
-// One hull phase at a time per process, the one a run is WAITING for first.  The pool is shared by the lanes of a process; two
-// phases at once (a run's own and another lane's background preparation) interleaved on the same workers and both came late:
-// measured at the start of a timed region, lanes idle -- the second lane's first hull phase took 12.8 ms instead of 5.1 beside
-// the first lane's preparation of its NEXT step, the first UNet passes were 10-17 ms apart and 20 steps carried 0.5-0.8 ms each
-// of it.  A background preparation now waits while a foreground phase is running or waiting, and one that is under way hands the
-// pool over at the next hull boundary (its workers take no further humerus; it finishes the rest after the foreground phase).
-struct HullPhaseGate {
-  std::mutex m; std::condition_variable cv; bool busy = false; std::atomic<int> fg_waiting{0};
-  void enter(bool background) {
-    std::unique_lock<std::mutex> l(m);
-    if (!background) ++fg_waiting;
-    cv.wait(l, [&] { return !busy && (!background || fg_waiting.load() == 0); });
-    if (!background) --fg_waiting;
-    busy = true;
-  }
-  bool foreground_waits() const { return fg_waiting.load(std::memory_order_relaxed) > 0; }
-  void leave() { { std::lock_guard<std::mutex> l(m); busy = false; } cv.notify_all(); }
-  static HullPhaseGate& instance() { static HullPhaseGate g; return g; }
-};
-
-static int hull_host_phase(sh_ctx* c, const sh_ctx::HullPts& in, int slot, int b0, int B, int* bad_mesh, double* ms, std::string* errtxt, bool background = false) {
-  auto t0 = std::chrono::steady_clock::now();
-  sh_ctx::HullStage& hs = c->hstage[slot];
-#define HULLCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *errtxt = std::string(#call) + ": " + hipGetErrorString(e_); return SH_ERR_HIP; } } while (0)
-  bool grown = false;
-again:
-  if (hs.cap < B || grown) {
-    if (hs.hv) { (void)hipHostFree(hs.hv); (void)hipHostFree(hs.nr); (void)hipHostFree(hs.ed); (void)hipHostFree(hs.cnt); }
-    hs.hv = nullptr; hs.cap = 0;
-    HULLCHK(hipHostMalloc((void**)&hs.hv, (size_t)B * hs.pv * 3 * 8));
-    HULLCHK(hipHostMalloc((void**)&hs.nr, (size_t)B * hs.pf * 3 * 8));
-    HULLCHK(hipHostMalloc((void**)&hs.ed, (size_t)B * hs.pe * 4 * 4));
-    HULLCHK(hipHostMalloc((void**)&hs.cnt, (size_t)B * 3 * 4));
-    hs.cap = B;
-  }
-  if (!hs.ev) HULLCHK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-  if (hs.used) HULLCHK(hipEventSynchronize(hs.ev));     // the previous copies out of this slot are done
-  {
-    // the other slot of the double buffer is allocated with the first one: pinning its 31 MB costs ~7 ms, and a context that had run
-    // once (a warm-up step) paid that in its SECOND run -- the first timed step of a lane (round 3: 12 ms instead of 5 for that hull
-    // phase, the first UNet passes of a 20-step region 14 ms apart)
-    sh_ctx::HullStage& ho = c->hstage[slot ^ 1];
-    if (!ho.hv && !grown) {
-      ho.pv = hs.pv; ho.pf = hs.pf; ho.pe = hs.pe;
-      HULLCHK(hipHostMalloc((void**)&ho.hv, (size_t)B * ho.pv * 3 * 8));
-      HULLCHK(hipHostMalloc((void**)&ho.nr, (size_t)B * ho.pf * 3 * 8));
-      HULLCHK(hipHostMalloc((void**)&ho.ed, (size_t)B * ho.pe * 4 * 4));
-      HULLCHK(hipHostMalloc((void**)&ho.cnt, (size_t)B * 3 * 4));
-      ho.cap = B;
-    }
-  }
-#undef HULLCHK
-  double* hv = hs.hv; double* nr = hs.nr; int* ed = hs.ed; int* counts = hs.cnt;
-  std::vector<int> status(B, 0);
-  std::vector<int> demand(3 * (size_t)B, 0);      // of the humeri whose hull does not fit the staging pitch
-  std::atomic<int> next(0);
-  auto work = [&]() {
-    std::vector<double> P;
-    shhull::Hull H;
-    for (;;) {
-      if (background && HullPhaseGate::instance().foreground_waits()) break;      // a run is waiting for ITS hulls: hand the pool over
-      int b = next.fetch_add(1);
-      if (b >= B) break;
-      counts[b] = counts[B + b] = counts[2 * B + b] = 0;
-      long long v0 = in.off[b0 + b], nv = in.cnt[b0 + b];
-      P.resize(3 * (size_t)nv);
-      const float* src = in.src + 3 * v0;
-      for (long long i = 0; i < 3 * nv; ++i) P[i] = (double)src[i];
-      if (!shhull::convex_hull(P.data(), (int)nv, H)) { status[b] = SH_ERR_GEOMETRY; continue; }
-      int hn = (int)H.vert_ids.size(), fn = (int)H.tris.size() / 3, en = (int)H.edges.size() / 4;
-      if (hn > hs.pv || fn > hs.pf || en > hs.pe) { status[b] = 1; demand[3 * (size_t)b] = hn; demand[3 * (size_t)b + 1] = fn; demand[3 * (size_t)b + 2] = en; continue; }      // does not fit the staging pitch: see below
-      for (int i = 0; i < hn; ++i)
-        for (int k = 0; k < 3; ++k) hv[((size_t)b * hs.pv + i) * 3 + k] = P[3 * (size_t)H.vert_ids[i] + k];
-      std::copy(H.normals.begin(), H.normals.end(), nr + (size_t)b * hs.pf * 3);
-      std::copy(H.edges.begin(), H.edges.end(), ed + (size_t)b * hs.pe * 4);
-      counts[b] = hn; counts[B + b] = fn; counts[2 * B + b] = en;
-    }
-  };
-  // One pool of worker threads per process, started once and shared by every context (lane) of the process: the host's
-  // hardware threads divided between the ranks of this node (torchrun exports LOCAL_WORLD_SIZE), at most 32 per process;
-  // SHOULDER_HULL_THREADS overrides.  The calling thread works on its own batch too.  (Round 1 started up to 32 threads
-  // per batch: a third of the 4.8 ms hull phase was thread start-up, and two lanes doubled the thread count.)
-  do {
-    HullPhaseGate::instance().enter(background);
-    HullPool::instance().run(work, B);
-    HullPhaseGate::instance().leave();
-  } while (next.load() < B);      // (a background phase that handed the pool over: the remaining humeri)
-  if (!grown && std::find(status.begin(), status.end(), 1) != status.end()) {
-    // a hull larger than the staging pitch (a dense mesh): this slot gets the record capacity -- or, above it, what the largest hull
-    // of the batch needs (the device record grows at the upload: grow_hull_records) -- and the phase runs again
-    int dv = SH_HV, df = SH_HF, de = SH_HE;
-    for (int b = 0; b < B; ++b) { dv = std::max(dv, demand[3 * (size_t)b]); df = std::max(df, demand[3 * (size_t)b + 1]); de = std::max(de, demand[3 * (size_t)b + 2]); }
-    auto up = [](int x) { return (x + 1023) / 1024 * 1024; };
-    hs.pv = up(dv); hs.pf = up(df); hs.pe = up(de);
-    grown = true;
-    std::fill(status.begin(), status.end(), 0);
-    next = 0;
-    goto again;
-  }
-  *ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  for (int b = 0; b < B; ++b)
-    if (status[b] != 0) { *bad_mesh = b0 + b; return status[b] == 1 ? SH_ERR_CAPACITY : status[b]; }      // (1 survives only if the re-sized staging still did not hold a hull)
-  return SH_OK;
-}
-
-// Hull records of pinned slot `slot` -> device buffers on stream `st`: only the used head of every fixed-capacity record
-// crosses PCIe (one strided copy per array).  `dst` = {hull.hv, hull.normals, hull.edges, hull.nv, hull.nf, hull.ne}.
 // do the hulls of pinned slot `slot` fit the device record?  (the background threads upload only when they do: growing re-allocates)
 static bool hull_fits(const sh_ctx* c, int slot, int B, int* need /*[3] or null*/) {
   const int* counts = c->hstage[slot].cnt;
@@ -2066,23 +1071,6 @@ static int grow_hull_records(sh_ctx* c, int nv, int nf, int ne) {
   if (c->sw.debug) fprintf(stderr, "[sh] hull record grown to %d vertices / %d faces / %d edges per humerus\n", c->hcap.v, c->hcap.f, c->hcap.e);
   return SH_OK;
 }
-static hipError_t hull_upload(sh_ctx* c, int slot, int B, void* const dst[6], hipStream_t st) {
-  sh_ctx::HullStage& hs = c->hstage[slot];
-  const int* counts = hs.cnt;
-  int nvmax = 1, nfmax = 1, nemax = 1;
-  for (int b = 0; b < B; ++b) { nvmax = std::max(nvmax, counts[b]); nfmax = std::max(nfmax, counts[B + b]); nemax = std::max(nemax, counts[2 * B + b]); }
-  if (nvmax > c->hcap.v || nfmax > c->hcap.f || nemax > c->hcap.e) return hipErrorInvalidValue;      // (callers check hull_fits / grow first)
-  hipError_t e;
-  if ((e = hipMemcpy2DAsync(dst[0], (size_t)c->hcap.v * 24, hs.hv, (size_t)hs.pv * 24, (size_t)nvmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpy2DAsync(dst[1], (size_t)c->hcap.f * 24, hs.nr, (size_t)hs.pf * 24, (size_t)nfmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpy2DAsync(dst[2], (size_t)c->hcap.e * 16, hs.ed, (size_t)hs.pe * 16, (size_t)nemax * 16, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(dst[3], counts, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(dst[4], counts + B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(dst[5], counts + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipEventRecord(hs.ev, st)) != hipSuccess) return e;      // pinned slot is free again once these copies have run
-  hs.used = true;
-  return hipSuccess;
-}
 
 // mesh.py:63-125.  Host: convex hulls (hull_host_phase; already done by the background thread when `prepared_slot`
 // >= 0).  Device: candidate boxes for every hull face, pick + frame, end sections, circle fits, flip (k_obb.h).
@@ -2095,18 +1083,7 @@ static int run_obb(sh_ctx* c, int prepared_slot) {
   if (c->redo_records) {
     nfmax = std::max(1, c->redo_nf);      // (redo_given_up put the host quickhull's records of this window into hull.*)
   } else if (device_hull_now(c)) {
-    // hull on the device: prefilter -> round-based quickhull (k_hull.h), all on this context's stream; nothing comes to the host
-    { int arc = alloc_hulld(c); if (arc != SH_OK) return arc; }
-    launch_prefilter(hullpre_ptrs(c), B, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HullScratch hs{buf<int>(c, "hulld.fv"), buf<int>(c, "hulld.vis"), buf<int>(c, "hulld.ev"), buf<int>(c, "hulld.hor"), buf<int>(c, "hulld.newslot"),
-                   buf<int>(c, "hulld.freestack"), buf<unsigned long long>(c, "hulld.tkeys"), buf<unsigned>(c, "hulld.tvals")};
-    LAUNCH(c, "k_hull_rounds", k_hull_rounds, dim3(B), dim3(HD_THREADS), (const float*)c->bufs["hullpre.kept"].p, (const long long*)c->bufs["hullpre.koff"].p, hs,
-           buf<double>(c, "hull.hv"), buf<double>(c, "hull.normals"), buf<int>(c, "hull.edges"), buf<int>(c, "hull.nv"), buf<int>(c, "hull.nf"), buf<int>(c, "hull.ne"),
-           buf<int>(c, "hulld.fail"), buf<int>(c, "hulld.rounds"), (const int*)buf<int>(c, "hulld.skip"), c->hcap);
-    LAUNCH(c, "k_hull_flag", k_hull_flag, dim3((B + 63) / 64), dim3(64), buf<int>(c, "hulld.fail"), buf<int>(c, "err"), B);
-    nfmax = std::max((int)HD_SLOTS, c->skip_nfmax);      // (the face counts stay on the device: the candidate kernel's tiles beyond a hull's faces return at once;
-                                                         //  a humerus kept on the host hull may have more faces than the device hull has slots)
+    { int drc = run_device_hull(c, B, &nfmax); if (drc != SH_OK) return drc; }
   } else {
   int slot = prepared_slot;
   if (slot < 0) {
@@ -2363,7 +1340,7 @@ static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot) {
            buf<unsigned long long>(c, "anp.mm_enc"));      // (+ the image's minimum / maximum: no second pass over it)
     // MinMaxScaler (anatomic_neck.py:56-58): the 16-bit network's first kernel applies it where it reads its patches (k_unet16_l0.h) --
     // no f32 image, 201 MB less traffic and a launch less per step; the other forms of the network and sh_set_keep_products get "anp.image"
-    const bool scale_in_net = (c->params.unet_dtype == SH_UNET_BF16 || c->params.unet_dtype == SH_UNET_F16) && unet16_starts_fused(c, SH_ANP_ROWS, SH_MPROX);
+    const bool scale_in_net = (c->params.unet_dtype == SH_UNET_BF16 || c->params.unet_dtype == SH_UNET_F16) && unet16_level0_fused(c, SH_ANP_ROWS, SH_MPROX);
     if (!scale_in_net || c->keep_products)
       LAUNCH(c, "k_anp_scale", k_anp_scale, dim3(64, B), dim3(256), buf<double>(c, "anp.raw"), buf<unsigned long long>(c, "anp.mm_enc"), buf<float>(c, "anp.image"));
     if ((rc = unet_turn_enter(c)) != SH_OK) return rc;
@@ -2417,17 +1394,6 @@ static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot) {
 #define SH_WINDOW (1 << 30)
 
 // ---- overlap of the host hulls with the device work of the previous run ----------------------------------
-static int join_prepared(sh_ctx* c) {
-  if (!c->prep.active) return SH_OK;
-  if (c->prep.th.joinable()) c->prep.th.join();
-  c->prep.active = false;
-  if (c->timing) {
-    KTimer& h = c->timers["host.hull"]; h.ms += c->prep.hull_ms; h.n += 1;
-    if (c->prep.d2h_ms > 0) { KTimer& a = c->timers["host.verts_d2h"]; a.ms += c->prep.d2h_ms; a.n += 1; }
-  }
-  return c->prep.rc;      // a failed preparation is simply not used: the run repeats the host phase and reports the error itself
-}
-
 static void start_prepare(sh_ctx* c) {
   sh_ctx::Prepared& p = c->prep;
   p.active = true; p.slot = c->hslot; p.B = c->B; p.gen = c->batch_gen; p.rc = SH_OK; p.bad_mesh = -1; p.d2h_ms = p.hull_ms = 0; p.err.clear();
@@ -2480,9 +1446,6 @@ int sh_discard_prepared(sh_ctx* c) {
 // sh_set_record_rows(R) the records a run hands out (`out` of sh_run / sh_submit: host memory or a gather's device send buffer)
 // are PACKED: [the bytes of sh_landmarks in front of anp_points][its six trailing int32 fields][R rows of anp_points] -- the
 // first min(n_anp, R) rows, zeros behind them; n_anp keeps the true count, sh_anp_points returns every row.
-#define SH_REC_HEAD offsetof(sh_landmarks, anp_points)
-#define SH_REC_TAIL (sizeof(sh_landmarks) - SH_REC_HEAD - sizeof(((sh_landmarks*)0)->anp_points))
-static inline size_t rec_bytes_rows(int rows) { return rows > 0 ? SH_REC_HEAD + SH_REC_TAIL + (size_t)rows * 24 : sizeof(sh_landmarks); }
 
 __global__ void __launch_bounds__(256)
 k_wire_records(const sh_landmarks* __restrict__ lm, unsigned char* __restrict__ dst, int R, size_t rec) {
@@ -2497,13 +1460,19 @@ k_wire_records(const sh_landmarks* __restrict__ lm, unsigned char* __restrict__ 
   for (int i = tid; i < 3 * R; i += 256) d[HEAD + TAIL + i] = i < 3 * n ? src[HEAD + i] : 0ull;
 }
 
+}  // extern "C"
+
+namespace sh {
 // records [b0, b0 + n) of the run just enqueued -> dst (device memory, record b at dst + b * rec) on the context's stream
-static int emit_records(sh_ctx* c, void* dst, int b0, int n, int rows, size_t rec) {
+int emit_records(sh_ctx* c, void* dst, int b0, int n, int rows, size_t rec) {
   const sh_landmarks* src = (const sh_landmarks*)c->bufs["landmarks"].p + b0;
   if (rows <= 0) { HIPCHK(c, hipMemcpyAsync((char*)dst + (size_t)b0 * rec, src, (size_t)n * rec, hipMemcpyDeviceToDevice, c->stream)); return SH_OK; }
   LAUNCH(c, "k_wire_records", k_wire_records, dim3(n), dim3(256), src, (unsigned char*)dst + (size_t)b0 * rec, rows, rec);
   return SH_OK;
 }
+}  // namespace sh
+
+extern "C" {
 
 // every anatomic-neck point of humerus b (CT) of the last run: the rows a packed record cut off, or all of them
 __global__ void k_anp_points_ct(const double* __restrict__ pts_obb, const double* __restrict__ T_obb, int b, int n, double* __restrict__ out) {
@@ -2528,14 +1497,6 @@ __global__ void k_anp_points_ct(const double* __restrict__ pts_obb, const double
 // One batch can be staged at a time; commit needs the context idle (sh_collect first): the buffers that become the staging side
 // are the ones the collected run read.  A rejected batch (bad index, NaN, not an STL) is reported by sh_commit_staged and leaves
 // the resident batch untouched.  Records are identical to sh_upload_* + sh_run: same device buffers, same kernels.
-static void discard_staged(sh_ctx* c) {
-  sh_ctx::StageSide& S = c->stg;
-  if (!S.active) return;
-  if (c->prep.staged) { (void)join_prepared(c); c->prep.gen = ~0ull; c->prep.staged = false; }
-  (void)hipEventSynchronize(S.ready_ev);      // nothing reads the pinned staging or writes the staging side any more
-  S.active = false;
-}
-
 // The caller's (pageable) memory -> page-locked staging -> device, chunk by chunk on a few threads of their own (the hull pool's
 // workers may all be inside another lane's hull phase): a thread copies a chunk and enqueues its H2D copy at once, so the PCIe
 // transfer runs behind the memcpy instead of after it.  37 MB of arrays / 104 MB of files per batch.
@@ -2593,30 +1554,13 @@ static int stage_common_alloc(sh_ctx* c, int B, long long sumV_cap, long long su
     HIPCHK(c, hipHostMalloc((void**)&S.h_koff, (size_t)(B + 1) * 8));
     S.h_koff_cap = B + 1;
   }
-#define ENSS(name, bytes, elem) do { if ((rc = ensure(c, name, (size_t)(bytes), elem)) != SH_OK) return rc; c->bufs[name].per_mesh = 0; } while (0)
-  ENSS("verts.s", sumV_cap * 12, 4);
-  ENSS("faces.s", sumF_cap * 12, 4);
-  ENSS("voff.s", (size_t)(B + 1) * 8, 8);
-  ENSS("foff.s", (size_t)(B + 1) * 8, 8);
-  ENSS("stage.flag", 64, 4);
-  ENSS("hullpre.ext.s", (size_t)B * SH_HP_NDIR * 4, 4);
-  ENSS("hullpre.planes.s", (size_t)B * SH_HP_MAXPL * 4 * 8, 8);
-  ENSS("hullpre.npl.s", (size_t)B * 4, 4);
-  ENSS("hullpre.nkept.s", (size_t)B * 4, 4);
-  ENSS("hullpre.pval.s", (size_t)B * SH_HP_PARTS * SH_HP_NDIR * 8, 8);
-  ENSS("hullpre.pidx.s", (size_t)B * SH_HP_PARTS * SH_HP_NDIR * 4, 4);
-  ENSS("hullpre.pcnt.s", (size_t)B * SH_HP_PARTS * 4, 4);
-  ENSS("hullpre.poff.s", (size_t)B * SH_HP_PARTS * 8, 8);
-  ENSS("hullpre.koff.s", (size_t)(B + 1) * 8, 8);
-  ENSS("hullpre.kept.s", (size_t)sumV_cap * 12, 4);
-#undef ENSS
+  ENS_SHARED("verts.s", sumV_cap * 12, 4);
+  ENS_SHARED("faces.s", sumF_cap * 12, 4);
+  ENS_SHARED("voff.s", (size_t)(B + 1) * 8, 8);
+  ENS_SHARED("foff.s", (size_t)(B + 1) * 8, 8);
+  ENS_SHARED("stage.flag", 64, 4);
+  if ((rc = alloc_hullpre(c, B, sumV_cap, ".s")) != SH_OK) return rc;
   return SH_OK;
-}
-
-static HullPre hullpre_ptrs_staged(sh_ctx* c) {      // calling thread only (buffer map)
-  return HullPre{(const float*)c->bufs["verts.s"].p, (const long long*)c->bufs["voff.s"].p, (int*)c->bufs["hullpre.ext.s"].p, (double*)c->bufs["hullpre.planes.s"].p,
-                 (int*)c->bufs["hullpre.npl.s"].p, (float*)c->bufs["hullpre.kept.s"].p, (int*)c->bufs["hullpre.nkept.s"].p, (long long*)c->bufs["hullpre.koff.s"].p,
-                 (double*)c->bufs["hullpre.pval.s"].p, (int*)c->bufs["hullpre.pidx.s"].p, (int*)c->bufs["hullpre.pcnt.s"].p, (long long*)c->bufs["hullpre.poff.s"].p};
 }
 
 // what the STL variant's thread does first (phase 1): sizes of the merged meshes -> offsets -> k_stl_emit
@@ -2629,7 +1573,7 @@ static void start_prepare_staged(sh_ctx* c, bool hulls, const StlPhase stl, std:
   sh_ctx::StageSide& S = c->stg;
   p.active = true; p.staged = true; p.slot = c->hslot; p.B = S.B; p.gen = hulls ? c->batch_gen + 1 : ~0ull; p.rc = SH_OK; p.bad_mesh = -1; p.d2h_ms = p.hull_ms = 0; p.err.clear();
   p.uploaded = false;
-  const HullPre hp = hullpre_ptrs_staged(c);
+  const HullPre hp = hullpre_ptrs(c, ".s");
   struct Dst { void* p[6]; } dst = {{c->bufs["hull.hv"].p, c->bufs["hull.normals"].p, c->bufs["hull.edges"].p, c->bufs["hull.nv"].p, c->bufs["hull.nf"].p, c->bufs["hull.ne"].p}};
   // early upload only into buffers that will not be re-allocated by the commit (alloc_batch grows them for a larger batch)
   const size_t nB = (size_t)S.B;
@@ -2739,20 +1683,18 @@ int sh_stage_meshes(sh_ctx* c, const float* verts, const int32_t* faces, const i
   auto phase0 = [a](std::string* et) -> int {
     sh_ctx::StageSide& S = a.c->stg;
     hipStream_t st = a.c->copy_stream;
-#define P0CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *et = std::string(#call) + ": " + hipGetErrorString(e_); return SH_ERR_HIP; } } while (0)
-    if (a.vpin) P0CHK(hipMemcpyAsync(a.dv, a.verts, a.vb, hipMemcpyHostToDevice, st));
-    else P0CHK(staged_h2d(a.dv, S.h_src, a.verts, a.vb, st));
-    if (a.fpin) P0CHK(hipMemcpyAsync(a.df, a.faces, a.fb, hipMemcpyHostToDevice, st));
-    else P0CHK(staged_h2d(a.df, (char*)S.h_src + (a.vpin ? 0 : a.vpad), a.faces, a.fb, st));
-    P0CHK(hipMemcpyAsync(a.dvo, S.voff.data(), (size_t)(a.B + 1) * 8, hipMemcpyHostToDevice, st));
-    P0CHK(hipMemcpyAsync(a.dfo, S.foff.data(), (size_t)(a.B + 1) * 8, hipMemcpyHostToDevice, st));
-    P0CHK(hipMemsetAsync(a.flag, 0, 4, st));
+    if (a.vpin) HIPCHK_TXT(et, hipMemcpyAsync(a.dv, a.verts, a.vb, hipMemcpyHostToDevice, st));
+    else HIPCHK_TXT(et, staged_h2d(a.dv, S.h_src, a.verts, a.vb, st));
+    if (a.fpin) HIPCHK_TXT(et, hipMemcpyAsync(a.df, a.faces, a.fb, hipMemcpyHostToDevice, st));
+    else HIPCHK_TXT(et, staged_h2d(a.df, (char*)S.h_src + (a.vpin ? 0 : a.vpad), a.faces, a.fb, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(a.dvo, S.voff.data(), (size_t)(a.B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(a.dfo, S.foff.data(), (size_t)(a.B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK_TXT(et, hipMemsetAsync(a.flag, 0, 4, st));
     hipLaunchKernelGGL(k_validate_meshes, dim3((unsigned)std::min<long long>((3 * std::max(a.maxV, a.maxF) + 255) / 256, 256), (unsigned)a.B), dim3(256), 0, st,
                        (const float*)a.dv, (const int*)a.df, (const long long*)a.dvo, (const long long*)a.dfo, a.flag);
-    P0CHK(hipGetLastError());
-    P0CHK(hipMemcpyAsync(S.h_flag, a.flag, 4, hipMemcpyDeviceToHost, st));
-    P0CHK(hipEventRecord(S.ready_ev, st));
-#undef P0CHK
+    HIPCHK_TXT(et, hipGetLastError());
+    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag, a.flag, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK_TXT(et, hipEventRecord(S.ready_ev, st));
     return SH_OK;
   };
   HIPCHK(c, hipEventRecord(S.ready_ev, c->copy_stream));      // (a discard before the thread gets there waits for this one)
@@ -2786,19 +1728,17 @@ int sh_stage_stl(sh_ctx* c, const void* const* files, const size_t* nbytes, int 
   // the merged meshes are at most as large as the corner lists: the staging side is sized by that bound, the true offsets are
   // made by the thread once the device has counted
   if ((rc = stage_common_alloc(c, B, sumC, sumC / 3, 16 + 3 * (size_t)B)) != SH_OK) return rc;
-#define ENSS(name, bytes, elem) do { if ((rc = ensure(c, name, (size_t)(bytes), elem)) != SH_OK) return rc; c->bufs[name].per_mesh = 0; } while (0)
-  ENSS("stl.raw", (size_t)file_off[B], 1);
-  ENSS("stl.file_off", (B + 1) * 8, 8);
-  ENSS("stl.coff", (B + 1) * 8, 8);
-  ENSS("stl.corners", (size_t)sumC * 12, 4);
-  ENSS("stl.table", (size_t)B * tsize * 8, 4);
-  ENSS("stl.slot", (size_t)sumC * 4, 4);
-  ENSS("stl.vid", (size_t)sumC * 4, 4);
-  ENSS("stl.fpos", (size_t)(sumC / 3) * 4, 4);
-  ENSS("stl.counts", (size_t)B * 8, 4);
-  ENSS("stl.bsum", stl_rank_scratch_ints(B, maxc) * 4, 4);
-  ENSS("stl.nonfinite", (size_t)B * 4, 4);
-#undef ENSS
+  ENS_SHARED("stl.raw", (size_t)file_off[B], 1);
+  ENS_SHARED("stl.file_off", (B + 1) * 8, 8);
+  ENS_SHARED("stl.coff", (B + 1) * 8, 8);
+  ENS_SHARED("stl.corners", (size_t)sumC * 12, 4);
+  ENS_SHARED("stl.table", (size_t)B * tsize * 8, 4);
+  ENS_SHARED("stl.slot", (size_t)sumC * 4, 4);
+  ENS_SHARED("stl.vid", (size_t)sumC * 4, 4);
+  ENS_SHARED("stl.fpos", (size_t)(sumC / 3) * 4, 4);
+  ENS_SHARED("stl.counts", (size_t)B * 8, 4);
+  ENS_SHARED("stl.bsum", stl_rank_scratch_ints(B, maxc) * 4, 4);
+  ENS_SHARED("stl.nonfinite", (size_t)B * 4, 4);
   // files -> one page-locked image (file starts 4-byte aligned) + the two offset tables behind it
   const size_t raw_bytes = (size_t)file_off[B], tab_off = (raw_bytes + 255) & ~(size_t)255, need = tab_off + 2 * (size_t)(B + 1) * 8;
   if (S.h_src_cap < need) {
@@ -2829,7 +1769,6 @@ int sh_stage_stl(sh_ctx* c, const void* const* files, const size_t* nbytes, int 
     sh_ctx::StageSide& S = c->stg;
     hipStream_t st = c->copy_stream;
     const int B = a->B;
-#define P0CHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *et = std::string(#call) + ": " + hipGetErrorString(e_); return SH_ERR_HIP; } } while (0)
     {      // file by file: page-locked files go as they are, the others through the staging image; each file's H2D follows its memcpy at once
       std::atomic<int> next(0);
       std::atomic<int> err((int)hipSuccess);
@@ -2847,21 +1786,20 @@ int sh_stage_stl(sh_ctx* c, const void* const* files, const size_t* nbytes, int 
       for (int t = 1; t < SH_COPY_THREADS && t < B; ++t) th.emplace_back(work);
       work();
       for (auto& t : th) t.join();
-      P0CHK((hipError_t)err.load());
+      HIPCHK_TXT(et, (hipError_t)err.load());
     }
-    P0CHK(hipMemcpyAsync(a->d_file_off, a->h_tabs, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
-    P0CHK(hipMemcpyAsync(a->d_coff, a->h_tabs + B + 1, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
-    P0CHK(hipMemsetAsync(a->nonfin, 0, (size_t)B * 4, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(a->d_file_off, a->h_tabs, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(a->d_coff, a->h_tabs + B + 1, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK_TXT(et, hipMemsetAsync(a->nonfin, 0, (size_t)B * 4, st));
     const dim3 gc((unsigned)std::min<long long>((a->maxc + 255) / 256, 1024), (unsigned)B);
     hipLaunchKernelGGL(k_stl_corners, gc, dim3(256), 0, st, (const unsigned char*)a->raw, (const long long*)a->d_file_off, (const long long*)a->d_coff, (float*)a->corners, (int*)a->nonfin);
     hipLaunchKernelGGL(k_stl_table_init, dim3(1024), dim3(256), 0, st, (int2*)a->table, (size_t)B * a->tsize);
     hipLaunchKernelGGL(k_stl_hash, gc, dim3(256), 0, st, (const float*)a->corners, (const long long*)a->d_coff, (int2*)a->table, a->tsize, (int*)a->slot);
     stl_rank_launch(st, B, a->maxc, (const long long*)a->d_coff, (const int2*)a->table, a->tsize, (const int*)a->slot, (int*)a->vid, (int*)a->fpos, (int*)a->counts, (int*)a->bsum);
-    P0CHK(hipGetLastError());
-    P0CHK(hipMemcpyAsync(S.h_flag + 16, a->counts, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-    P0CHK(hipMemcpyAsync(S.h_flag + 16 + 2 * B, a->nonfin, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    P0CHK(hipEventRecord(c->stl_counted_ev, st));
-#undef P0CHK
+    HIPCHK_TXT(et, hipGetLastError());
+    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag + 16, a->counts, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag + 16 + 2 * B, a->nonfin, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK_TXT(et, hipEventRecord(c->stl_counted_ev, st));
     return SH_OK;
   };
   StlPhase ph;
@@ -2910,6 +1848,17 @@ int sh_commit_staged(sh_ctx* c, int64_t* v_off_out, int64_t* f_off_out) {
 }
 
 int sh_staged(const sh_ctx* c) { return c ? (c->stg.active ? 1 : 0) : SH_ERR_ARG; }
+
+static inline size_t status_ovf_off(int B) { return ((size_t)B * 4 + 7) & ~(size_t)7; }
+#define SH_NCTR 16
+static inline size_t status_bytes(int B) { return status_ovf_off(B) + SH_NCTR * 8 + (size_t)B * 4; }
+// the status block of a run (layout: sh_submit) from the live words, one launch
+__global__ void k_stage_status(const int* __restrict__ err, const unsigned long long* __restrict__ ovf_ctr, const int* __restrict__ hull_fail /*or null*/,
+                               char* __restrict__ dst, int B, size_t ovf_off) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < B) { ((int*)dst)[i] = err[i]; ((int*)(dst + ovf_off + SH_NCTR * 8))[i] = hull_fail ? hull_fail[i] : 0; }
+  if (i < SH_NCTR) ((unsigned long long*)(dst + ovf_off))[i] = ovf_ctr[i];
+}
 
 // The device hull gave the humeri in `list` up during the run of ticket `tk` (k_hull.h writes a unit tetrahedron for them, so
 // everything queued behind ran on finite data and their records are void).  Each of them gets the host quickhull -- which
@@ -2965,8 +1914,6 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const std::string& tslot
     c->b0 = 0; c->Bwin = B;
     if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     // the record and the status word of this humerus -> where the run's results were parked (or the caller's device buffer)
-    const sh_landmarks* src = buf<sh_landmarks>(c, "landmarks") + b;
-    (void)src;
     if (tk.host_out) { int erc = emit_records(c, c->bufs["out.landmarks" + tslot].p, b, 1, tk.rows, tk.rec); if (erc != SH_OK) return erc; }
     else if (tk.out_arg) { int erc = emit_records(c, tk.out_arg, b, 1, tk.rows, tk.rec); if (erc != SH_OK) return erc; }
     HIPCHK(c, hipMemcpyAsync((int*)c->bufs["out.err" + tslot].p + b, buf<int>(c, "err") + b, 4, hipMemcpyDeviceToDevice, c->stream));
@@ -2990,17 +1937,6 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const std::string& tslot
   HIPCHK(c, hipMemcpyAsync(tk.h_err, c->bufs["out.err" + tslot].p, (size_t)B * 4, hipMemcpyDeviceToHost, c->out_stream));
   HIPCHK(c, hipStreamSynchronize(c->out_stream));
   return SH_OK;
-}
-
-static inline size_t status_ovf_off(int B) { return ((size_t)B * 4 + 7) & ~(size_t)7; }
-#define SH_NCTR 16
-static inline size_t status_bytes(int B) { return status_ovf_off(B) + SH_NCTR * 8 + (size_t)B * 4; }
-// the status block of a run (layout: sh_submit) from the live words, one launch
-__global__ void k_stage_status(const int* __restrict__ err, const unsigned long long* __restrict__ ovf_ctr, const int* __restrict__ hull_fail /*or null*/,
-                               char* __restrict__ dst, int B, size_t ovf_off) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B) { ((int*)dst)[i] = err[i]; ((int*)(dst + ovf_off + SH_NCTR * 8))[i] = hull_fail ? hull_fail[i] : 0; }
-  if (i < SH_NCTR) ((unsigned long long*)(dst + ovf_off))[i] = ovf_ctr[i];
 }
 
 int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
@@ -3524,7 +2460,5 @@ int sh_param_block(sh_ctx* c, void** p, size_t* n) {
   *n = c->unet_floats * 4 + c->h_feat.size() * 20 + c->h_roots.size() * 4;
   return SH_OK;
 }
-
-#include "sh_comm.h"
 
 }  // extern "C"
