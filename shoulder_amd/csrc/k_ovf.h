@@ -13,7 +13,7 @@
 //                    into the ring pool;
 //   k_resample_polar_huge, k_te_rows_huge, te_final's ring: the consumers of a ring, for listed planes, from the pool.
 // All of them return at once when the set's list is empty (the normal case: ~2 us per launch).  Pools are sized by the host
-// (`ovf.*` buffers); a run that needs more records how much (ctr[3..5]), flags the humerus SH_ERR_CAPACITY_DEV, and
+// (`ovf.*` buffers); a run that needs more records how much (sh_demand.h: SH_CTR_*_NEED), flags the humerus SH_ERR_CAPACITY_DEV, and
 // sh_collect grows the pools and runs the batch again.
 #pragma once
 #include "k_slices.h"
@@ -23,8 +23,7 @@ namespace sh {
 struct OvfPools {
   Seg* segs; double* ring; unsigned char* work;
   unsigned long long seg_cap, ring_cap, work_cap;      // in segments / ring points / bytes
-  unsigned long long* ctr;                             // [0] segments used (per set) [1] ring points used (per run) [2] work bytes used (per set)
-                                                       // [3..5] high-water marks of what the run would have needed
+  unsigned long long* ctr;                             // the demand block (sh_demand.h): SH_CTR_*_USED cursors, SH_CTR_*_NEED high-water marks
   int open_mode;                                       // sh_set_open_contours: bridging, a plane's join may add up to one node per segment
 };
 // nodes a plane's join workspace and ring range are sized for: its segments, and as many bridges again in bridge mode
@@ -51,10 +50,10 @@ __global__ void k_ovf_plan(int N, int nplanes, const int* __restrict__ seg_count
   if (cnt <= SH_MAXSEG) return;
   const int nn = ovf_nodes(cnt, P.open_mode);
   const unsigned long long wb = ovf_work_bytes(nn);
-  const unsigned long long s = atomicAdd(&P.ctr[0], (unsigned long long)cnt);
-  const unsigned long long r = atomicAdd(&P.ctr[1], (unsigned long long)nn + 1ull);
-  const unsigned long long w = atomicAdd(&P.ctr[2], wb);
-  atomicMax(&P.ctr[3], s + cnt); atomicMax(&P.ctr[4], r + nn + 1ull); atomicMax(&P.ctr[5], w + wb);
+  const unsigned long long s = atomicAdd(&P.ctr[SH_CTR_SEG_USED], (unsigned long long)cnt);
+  const unsigned long long r = atomicAdd(&P.ctr[SH_CTR_RING_USED], (unsigned long long)nn + 1ull);
+  const unsigned long long w = atomicAdd(&P.ctr[SH_CTR_WORK_USED], wb);
+  atomicMax(&P.ctr[SH_CTR_SEG_NEED], s + cnt); atomicMax(&P.ctr[SH_CTR_RING_NEED], r + nn + 1ull); atomicMax(&P.ctr[SH_CTR_WORK_NEED], w + wb);
   if (s + cnt > P.seg_cap || r + nn + 1ull > P.ring_cap || w + wb > P.work_cap) { atomicExch(&err[pl / N], SH_ERR_CAPACITY_DEV); return; }
   S.soff[pl] = (long long)s; S.roff[pl] = (long long)r; S.woff[pl] = (long long)w;
   S.list[atomicAdd(S.nlist, 1)] = pl;
@@ -128,10 +127,10 @@ k_ovf_plan_loops(int N, const int* __restrict__ seg_count, const Seg* __restrict
     if (threadIdx.x == 0) {
       const int nn = ovf_nodes(cnt, P.open_mode);
       const unsigned long long wb = ovf_work_bytes(nn);
-      const unsigned long long s = atomicAdd(&P.ctr[0], (unsigned long long)cnt);
-      const unsigned long long r = atomicAdd(&P.ctr[1], (unsigned long long)nn + 1ull);
-      const unsigned long long w = atomicAdd(&P.ctr[2], wb);
-      atomicMax(&P.ctr[3], s + cnt); atomicMax(&P.ctr[4], r + nn + 1ull); atomicMax(&P.ctr[5], w + wb);
+      const unsigned long long s = atomicAdd(&P.ctr[SH_CTR_SEG_USED], (unsigned long long)cnt);
+      const unsigned long long r = atomicAdd(&P.ctr[SH_CTR_RING_USED], (unsigned long long)nn + 1ull);
+      const unsigned long long w = atomicAdd(&P.ctr[SH_CTR_WORK_USED], wb);
+      atomicMax(&P.ctr[SH_CTR_SEG_NEED], s + cnt); atomicMax(&P.ctr[SH_CTR_RING_NEED], r + nn + 1ull); atomicMax(&P.ctr[SH_CTR_WORK_NEED], w + wb);
       if (s + cnt > P.seg_cap || r + nn + 1ull > P.ring_cap || w + wb > P.work_cap) { atomicExch(&err[pl / N], SH_ERR_CAPACITY_DEV); so = -1; }
       else { so = (long long)s; ro = (long long)r; wo = (long long)w; }
     }

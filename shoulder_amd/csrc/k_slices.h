@@ -12,6 +12,7 @@
 //   ixy / itr_start / itr_centered_start  float64 [B][N][2][M]   (proximal set only)
 // All kernels are HBM/latency bound integer + fp64 work; no MFMA here.
 #pragma once
+#include "sh_demand.h"
 #include "sh_scalar.h"
 
 namespace sh {
@@ -108,7 +109,7 @@ __device__ inline double np_pairwise_sum(const double* a, int n) {
 struct PlaneAux {
   const unsigned long long* zb_enc; double* zb_out;      // nullable: z bounds from the encoded atomics of k_transform_verts, also written to zb_out
   int* seg_count; int* nlarge;                           // [B][N] crossing counters of this set; its large-tier counter
-  int* ovf_nlist; unsigned long long* ovf_ctr;           // nullable: overflow tier (k_ovf.h): list length of the set, pool counters [0] and [2]
+  int* ovf_nlist; unsigned long long* ovf_ctr;           // nullable: overflow tier (k_ovf.h): list length of the set, the demand block, for its per-set cursors
 };
 // Up to two slice sets that hang on the same inputs go through the set's launches TOGETHER (round 4: full + distal behind the box
 // frame, neck contour + proximal behind neck_z; they were four launch groups per step): one launch for their plane heights, one
@@ -141,7 +142,7 @@ __global__ void k_make_planes(SliceSets sets, const double* __restrict__ neck_z,
   for (int k = threadIdx.x; k < N; k += blockDim.x) A.seg_count[(size_t)b * N + k] = 0;
   if (b == 0 && threadIdx.x == 0) {
     *A.nlarge = 0;
-    if (A.ovf_nlist) { A.ovf_nlist[0] = 0; A.ovf_nlist[1] = 0 /*planes with many loops*/; if (A.ovf_ctr) { A.ovf_ctr[0] = 0ull; A.ovf_ctr[2] = 0ull; } }
+    if (A.ovf_nlist) { A.ovf_nlist[0] = 0; A.ovf_nlist[1] = 0 /*planes with many loops*/; if (A.ovf_ctr) { A.ovf_ctr[SH_CTR_SEG_USED] = 0ull; A.ovf_ctr[SH_CTR_WORK_USED] = 0ull; } }
   }
   if (kind == 3) {   // one plane at neck_z: `mesh.section(plane_origin=[0,0,neck_z])` (surgical_neck.py:37-39)
     if (threadIdx.x == 0) { zs[b] = neck_z[b]; zeff[b] = neck_z[b]; }

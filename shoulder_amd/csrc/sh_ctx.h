@@ -28,6 +28,7 @@
 #include <tuple>
 #include <vector>
 
+#include "sh_demand.h"
 #include "sh_hullcap.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -76,16 +77,14 @@ struct sh_ctx {
   int rec_rows = 0;                          // sh_set_record_rows: 0 = full sh_landmarks records, R > 0 = packed records with R anatomic-neck rows
   bool bounds_cleared = false;               // run_obb's first fill of this window covered zb_enc / anp.mm_enc (run_window skips its own)
   // hull of SH_STAGE_OBB: 1 = on the device (k_hull.h), 0 = host quickhull (sh_hull.h).  sh_set_hull_mode / SHOULDER_HULL=host|device|auto.
-  // A humerus the device hull gives up (pinched horizon on nearly coplanar clouds, capacities) is re-done ALONE by sh_collect:
-  // host quickhull for that humerus, its record patched into the device buffers, its stages re-run as a window of one behind
-  // whatever else is in flight on the stream (redo_given_up).  `hulld.skip[b]` then keeps the device hull off that humerus for
-  // as long as the batch stays resident (skip_gen == batch_gen).
+  // A humerus the device hull gives up (pinched horizon on nearly coplanar clouds, capacities) is re-done ALONE by sh_collect
+  // (redo_given_up); `hulld.skip[b]` then keeps the device hull off it for as long as the batch stays resident (skip_gen == batch_gen).
   int hull_mode = 1;
   unsigned long long skip_gen = ~0ull;
   int skip_nfmax = 0;                      // most hull faces among the humeri of this batch that are on the host hull (hulld.skip)
   // overflow pools of the slice layer (k_ovf.h): capacities in segments / ring points / bytes; grown by sh_collect on demand
   unsigned long long ovf_seg_cap = 1ull << 18, ovf_ring_cap = 1ull << 18, ovf_work_cap = 32ull << 20;
-  // a run of the resident batch that planned no overflow plane in any set (ctr[4] == 0 at collect) lets later runs of the SAME batch
+  // a run of the resident batch that planned no overflow plane in any set (no ring-point or segment demand at collect: SH_CTR_RING_NEED, SH_CTR_SEG_NEED) lets later runs of the SAME batch
   // and parameters skip the overflow tier's launches (they would all return at once: ~17 launches, ~60 us per step)
   unsigned long long ovf_none_gen = ~0ull;
   // sh_set_open_contours (k_open.h): SH_OPEN_ERROR / SH_OPEN_BRIDGE and the largest gap bridged (mm); open_stats_run: the mode of the
@@ -101,8 +100,6 @@ struct sh_ctx {
                                              // k_obb_candidates: later runs take the tier that holds it (reset with the batch)
   bool obb_nf_over = false;                  // a device-hull run met a hull with more faces than its candidates tier masks: the next run takes the workspace tier
   bool hull_force_host = false;              // the resident batch has a hull above the device hull's record: its hulls come from the host (reset with the batch)
-  bool redo_records = false;               // run_obb: the hull records of the window are in place already (redo_given_up)
-  int redo_nf = 0;
   std::vector<float> h_verts;                // host copy of the vertices (hull stage)
   bool h_verts_valid = false;
   // device-generated batches: the hull's points come back through the prefilter (k_hullpre.h) into pinned memory
@@ -148,7 +145,7 @@ struct sh_ctx {
   } prep;
   hipEvent_t obb_done_ev = nullptr;      // recorded after the last kernel of a run that reads the hull.* device buffers
   // sh_submit / sh_collect: up to two runs in flight (the second one is enqueued while the first still executes)
-  struct Ticket { hipEvent_t ev = nullptr; int* h_err = nullptr; int* h_fail = nullptr; unsigned long long* h_ovf = nullptr; int cap = 0, B = 0; bool pending = false; sh_landmarks* host_out = nullptr;
+  struct Ticket { hipEvent_t ev = nullptr; char* status = nullptr /*pinned sh::StatusBlock for `cap` humeri*/; int cap = 0, B = 0; bool pending = false; sh_landmarks* host_out = nullptr;
                   uint32_t mask = 0; sh_landmarks* out_arg = nullptr; bool dev_hull = false; unsigned long long gen = 0; size_t rec = sizeof(sh_landmarks); int rows = 0; };
   Ticket tickets[2];
   int t_head = 0, t_tail = 0, n_pending = 0;
@@ -207,6 +204,14 @@ struct sh_ctx {
 
 // the same for code that has no context to write to (the background threads): the text goes to *errtxt
 #define HIPCHK_TXT(errtxt, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { *(errtxt) = std::string(#call) + ": " + hipGetErrorString(e_); return SH_ERR_HIP; } } while (0)
+
+// The window [b0, b0 + Bwin) for a scope; the previous one comes back when the scope is left (on its error returns too)
+struct WindowScope {
+  sh_ctx* c; int b0, Bwin;
+  WindowScope(sh_ctx* c_, int nb0, int nBwin) : c(c_), b0(c_->b0), Bwin(c_->Bwin) { c->b0 = nb0; c->Bwin = nBwin; }
+  ~WindowScope() { c->b0 = b0; c->Bwin = Bwin; }
+  WindowScope(const WindowScope&) = delete; WindowScope& operator=(const WindowScope&) = delete;
+};
 
 static inline int fail(sh_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;

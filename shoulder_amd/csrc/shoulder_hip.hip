@@ -208,7 +208,7 @@ void sh_ctx_destroy(sh_ctx* c) {
   if (c->h_nkept) (void)hipHostFree(c->h_nkept);
   if (c->h_koff) (void)hipHostFree(c->h_koff);
   if (c->obb_done_ev) (void)hipEventDestroy(c->obb_done_ev);
-  for (auto& tk : c->tickets) { if (tk.ev) (void)hipEventDestroy(tk.ev); if (tk.h_err) (void)hipHostFree(tk.h_err); }      // (one pinned block: h_ovf and h_fail point into it)
+  for (auto& tk : c->tickets) { if (tk.ev) (void)hipEventDestroy(tk.ev); if (tk.status) (void)hipHostFree(tk.status); }
   if (c->out_stream) (void)hipStreamDestroy(c->out_stream);
   for (auto& kv : c->bufs)
     if (kv.second.p) (void)hipFree(kv.second.p);
@@ -923,7 +923,7 @@ static int ovf_pools(sh_ctx* c, OvfPools* P) {
   if ((rc = ensure(c, "ovf.segs", c->ovf_seg_cap * sizeof(Seg), 1)) != SH_OK) return rc;
   if ((rc = ensure(c, "ovf.ring", c->ovf_ring_cap * 16, 8)) != SH_OK) return rc;
   if ((rc = ensure(c, "ovf.work", c->ovf_work_cap, 1)) != SH_OK) return rc;
-  if ((rc = ensure(c, "ovf.ctr", 128, 8)) != SH_OK) return rc;      // words 0..7: the slice layer's pools (k_ovf.h) and the end sections; 8, 9: k_obb_candidates (ObbWs::need)
+  if ((rc = ensure(c, "ovf.ctr", SH_NCTR * 8, 8)) != SH_OK) return rc;      // the demand block of a run (sh_demand.h names its words)
   for (const char* n : {"ovf.segs", "ovf.ring", "ovf.work", "ovf.ctr"}) c->bufs[n].per_mesh = 0;
   P->segs = (Seg*)c->bufs["ovf.segs"].p; P->ring = (double*)c->bufs["ovf.ring"].p; P->work = (unsigned char*)c->bufs["ovf.work"].p;
   P->seg_cap = c->ovf_seg_cap; P->ring_cap = c->ovf_ring_cap; P->work_cap = c->ovf_work_cap;
@@ -982,8 +982,8 @@ static int run_slice_sets(sh_ctx* c, const SliceSpec* specs, int nspec) {
     S.areas_total = sp.total_area ? buf<double>(c, (p + ".area_total").c_str()) : (double*)nullptr;
     S.nlarge = (int*)c->bufs["slices.nlarge"].p + (sp.kind & 7);      // (one counter per kind of set)
     // planes with more than SH_MAXLOOPS loops: listed for the overflow tier's join (tier skipped: flagged, sh_collect runs again with it)
-    S.many = ManyLoops{ovf_on ? OS[i].list2 : (int*)nullptr, ovf_on ? OS[i].nlist + 1 : (int*)nullptr, ovf_on ? (unsigned long long*)nullptr : OP.ctr + 6};
-    S.ovf_missed = ovf_on ? (unsigned long long*)nullptr : OP.ctr + 6;
+    S.many = ManyLoops{ovf_on ? OS[i].list2 : (int*)nullptr, ovf_on ? OS[i].nlist + 1 : (int*)nullptr, ovf_on ? (unsigned long long*)nullptr : OP.ctr + SH_CTR_TIER_MISSED};
+    S.ovf_missed = ovf_on ? (unsigned long long*)nullptr : OP.ctr + SH_CTR_TIER_MISSED;
     // the plane-height launch also zeroes the set's crossing counters and its large-tier counter, resets the overflow tier's words
     // (segments / workspace used: per launch group, by its first set; ring points stay for the run) and, for the first set behind
     // k_transform_verts, decodes the z bounds (run_window)
@@ -1076,13 +1076,13 @@ static int grow_hull_records(sh_ctx* c, int nv, int nf, int ne) {
 // >= 0).  Device: candidate boxes for every hull face, pick + frame, end sections, circle fits, flip (k_obb.h).
 static bool device_hull_now(const sh_ctx* c) { return c->hull_mode == 1 && !(c->hull_force_host && c->obb_gen == c->batch_gen); }
 
-static int run_obb(sh_ctx* c, int prepared_slot) {
+// redo_nf > 0: a redo -- redo_given_up put the host quickhull's record of this window (of one humerus) into hull.*, with that many faces
+static int run_obb(sh_ctx* c, int prepared_slot, int redo_nf) {
   const int B = c->Bwin, b0 = c->b0;
   int nfmax = 1;
   if (c->obb_gen != c->batch_gen) { c->obb_gen = c->batch_gen; c->obb_sil_need = 0; c->obb_nf_over = false; c->hull_force_host = false; }
-  if (c->redo_records) {
-    nfmax = std::max(1, c->redo_nf);      // (redo_given_up put the host quickhull's records of this window into hull.*)
-  } else if (device_hull_now(c)) {
+  if (redo_nf > 0) nfmax = redo_nf;
+  else if (device_hull_now(c)) {
     { int drc = run_device_hull(c, B, &nfmax); if (drc != SH_OK) return drc; }
   } else {
   int slot = prepared_slot;
@@ -1132,7 +1132,7 @@ static int run_obb(sh_ctx* c, int prepared_slot) {
     const int TT = (big || huge) ? 8 : SH_OBB_TILE;
     const int ntiles = (nfmax + TT - 1) / TT;
     ObbWs ws{};
-    ws.need = (unsigned long long*)c->bufs["ovf.ctr"].p + 8;
+    ws.need = (unsigned long long*)c->bufs["ovf.ctr"].p + SH_CTR_SIL_NEED;
     if (huge) {
       ws.nwg = 256;
       ws.silcap = std::max(hc.v + 64, c->obb_sil_need + c->obb_sil_need / 8);      // (a silhouette is a cycle of the hull's graph; more only on degenerate input: then the demand is recorded)
@@ -1191,7 +1191,7 @@ static int run_obb(sh_ctx* c, int prepared_slot) {
          buf<long long>(c, "foff"), buf<double>(c, "obb.T_pre"), buf<double>(c, "obb.zb_pre"), buf<double>(c, "obb.endpts"), buf<int>(c, "obb.endcnt"), c->end_cap);
   LAUNCH(c, "k_obb_ends", k_obb_ends, dim3(B), dim3(128), buf<double>(c, "obb.endpts"), buf<int>(c, "obb.endcnt"),
          buf<double>(c, "obb.T_pre"), buf<double>(c, "obb.resid"), buf<double>(c, "obb_transform"), buf<int>(c, "flipped"), buf<int>(c, "err"), B, c->end_cap,
-         (unsigned long long*)c->bufs["ovf.ctr"].p + 7);
+         (unsigned long long*)c->bufs["ovf.ctr"].p + SH_CTR_END_NEED);
   c->obb_injected = true;
   return SH_OK;
 }
@@ -1217,12 +1217,12 @@ static int run_te_rows(sh_ctx* c) {
 
 // All stages for the window [c->b0, c->b0 + c->Bwin) of the batch; everything is enqueued on the stream,
 // nothing here waits for the device.
-static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot) {
+static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot, int redo_nf = 0) {
   const int B = c->Bwin;
   int rc;
   c->bounds_cleared = false;
   if (mask & SH_STAGE_OBB)
-    if ((rc = run_obb(c, prepared_slot)) != SH_OK) return rc;
+    if ((rc = run_obb(c, prepared_slot, redo_nf)) != SH_OK) return rc;
   // the encoded minima / maxima (z bounds of the box frame, the anatomic-neck image's range) start as all ones: one fill for both,
   // in run_obb's first fill when that stage runs (they were a launch each)
   if (!c->bounds_cleared && (mask & (SH_STAGE_OBB | SH_STAGE_FULL | SH_STAGE_ANP)))
@@ -1246,7 +1246,7 @@ static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot) {
   // proximal -> groove chain.  Larger batches: the distal set and the trans-epicondylar rows stay in the chain (DESIGN.md section 9:
   // the rows forked beside the lane's UNet pass, or run behind it, made the step slower).  Fork only when the overflow tier is known
   // to be idle for this batch (its pool counters are per set) and no per-launch timing is on.
-  const bool can_fork = (mask & SH_STAGE_DISTAL) && c->ovf_none_gen == c->batch_gen && c->timing != 1 && !c->redo_records;
+  const bool can_fork = (mask & SH_STAGE_DISTAL) && c->ovf_none_gen == c->batch_gen && c->timing != 1 && redo_nf == 0;
   const bool side = can_fork && B <= 16;
   bool te_rows_done = false;
   c->side_pending = false;
@@ -1849,48 +1849,45 @@ int sh_commit_staged(sh_ctx* c, int64_t* v_off_out, int64_t* f_off_out) {
 
 int sh_staged(const sh_ctx* c) { return c ? (c->stg.active ? 1 : 0) : SH_ERR_ARG; }
 
-static inline size_t status_ovf_off(int B) { return ((size_t)B * 4 + 7) & ~(size_t)7; }
-#define SH_NCTR 16
-static inline size_t status_bytes(int B) { return status_ovf_off(B) + SH_NCTR * 8 + (size_t)B * 4; }
-// the status block of a run (layout: sh_submit) from the live words, one launch
-__global__ void k_stage_status(const int* __restrict__ err, const unsigned long long* __restrict__ ovf_ctr, const int* __restrict__ hull_fail /*or null*/,
-                               char* __restrict__ dst, int B, size_t ovf_off) {
+// the status block of a run (sh_demand.h StatusBlock) from the live words, one launch
+__global__ void k_stage_status(const int* __restrict__ err, const unsigned long long* __restrict__ ovf_ctr, const int* __restrict__ hull_fail /*or null*/, StatusBlock dst) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < B) { ((int*)dst)[i] = err[i]; ((int*)(dst + ovf_off + SH_NCTR * 8))[i] = hull_fail ? hull_fail[i] : 0; }
-  if (i < SH_NCTR) ((unsigned long long*)(dst + ovf_off))[i] = ovf_ctr[i];
+  if (i < dst.B) { dst.err()[i] = err[i]; dst.gave_up()[i] = hull_fail ? hull_fail[i] : 0; }
+  if (i < SH_NCTR) dst.words()[i] = ovf_ctr[i];
 }
 
-// The device hull gave the humeri in `list` up during the run of ticket `tk` (k_hull.h writes a unit tetrahedron for them, so
+static DemandCaps demand_caps(const sh_ctx* c) { return DemandCaps{c->ovf_seg_cap, c->ovf_ring_cap, c->ovf_work_cap, c->end_cap, c->obb_sil_need, c->obb_nf_over}; }
+
+// The device hull gave humeri up during the run of ticket `tk` (st.gave_up(); k_hull.h writes a unit tetrahedron for them, so
 // everything queued behind ran on finite data and their records are void).  Each of them gets the host quickhull -- which
 // has the retry / joggle logic -- its record goes into the device buffers where the device hull would have put it, and its
 // stages run again as a window of one humerus.  All of it is enqueued on the context's stream: behind a second run that may
 // be in flight (which finished with this batch's scratch buffers by then, and has parked its own results per ticket).
 // hulld.skip[b] is set, so later runs of the resident batch get these humeri right the first time.
-static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const std::string& tslot, const std::vector<int>& list, unsigned long long* need /*[4]: pool demand, [3] = rerun*/) {
+// *again: SH_RERUN_NONE when the records are complete, else why the whole batch has to run again (and with which capacities).
+static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, const std::string& tslot, Verdict* again) {
   const int B = tk.B;
+  if (std::none_of(st.gave_up(), st.gave_up() + B, [](int f) { return f != 0; })) return SH_OK;
   std::vector<float> hv32;
   std::vector<double> P;
   shhull::Hull H;
   int rc = SH_OK;
-  for (int b : list) {
+  for (int b = 0; b < B; ++b) {
+    if (st.gave_up()[b] == 0) continue;
     const long long v0 = c->h_voff[b], nv = c->h_voff[b + 1] - v0;
     hv32.resize(3 * (size_t)nv);
     HIPCHK(c, hipMemcpyAsync(hv32.data(), (const float*)c->bufs["verts"].p + 3 * v0, (size_t)nv * 12, hipMemcpyDeviceToHost, c->out_stream));
     HIPCHK(c, hipStreamSynchronize(c->out_stream));
     P.assign(hv32.begin(), hv32.end());
-    int status = 0, hn = 0, fn = 0, en = 0;
-    if (!shhull::convex_hull(P.data(), (int)nv, H)) status = SH_ERR_GEOMETRY;
-    else {
-      hn = (int)H.vert_ids.size(); fn = (int)H.tris.size() / 3; en = (int)H.edges.size() / 4;
-      if (hn > c->hcap.v || fn > c->hcap.f || en > c->hcap.e) {
-        // above the record: growing it here would drop the other humeri's records -- the batch runs again with its hulls from the
-        // host (hull_host_phase sizes the staging, run_obb grows the record), and stays there while it is resident
-        c->hull_force_host = true;
-        if (need) need[3] = 1;
-        return SH_OK;
-      }
+    if (!shhull::convex_hull(P.data(), (int)nv, H)) { char m[96]; snprintf(m, sizeof m, "mesh %d: convex hull failed (%d)", b, SH_ERR_GEOMETRY); return fail(c, SH_ERR_GEOMETRY, m); }
+    const int hn = (int)H.vert_ids.size(), fn = (int)H.tris.size() / 3, en = (int)H.edges.size() / 4;
+    if (hn > c->hcap.v || fn > c->hcap.f || en > c->hcap.e) {
+      // above the record: growing it here would drop the other humeri's records -- the batch runs again with its hulls from the
+      // host (hull_host_phase sizes the staging, run_obb grows the record), and stays there while it is resident
+      c->hull_force_host = true;
+      again->rerun = SH_RERUN_FORCE_HOST;
+      return SH_OK;
     }
-    if (status != 0) { char m[96]; snprintf(m, sizeof m, "mesh %d: convex hull failed (%d)", b, status); return fail(c, status, m); }
     std::vector<double> hvd(3 * (size_t)hn);
     for (int i = 0; i < hn; ++i)
       for (int k = 0; k < 3; ++k) hvd[3 * (size_t)i + k] = P[3 * (size_t)H.vert_ids[i] + k];
@@ -1908,34 +1905,38 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const std::string& tslot
     if (c->open_mode != SH_OPEN_ERROR) HIPCHK(c, hipMemsetAsync(buf<int>(c, "open.stats") + 2 * (size_t)b, 0, 8, c->stream));      // (the void first pass counted too)
     HIPCHK(c, hipStreamSynchronize(c->stream));      // the sources above are locals
     c->skip_nfmax = std::max(c->skip_nfmax, fn);
-    c->b0 = b; c->Bwin = 1; c->redo_records = true; c->redo_nf = fn;
-    rc = run_window(c, tk.mask, -1);
-    c->redo_records = false;
-    c->b0 = 0; c->Bwin = B;
+    { WindowScope one(c, b, 1); rc = run_window(c, tk.mask, -1, fn); }
     if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     // the record and the status word of this humerus -> where the run's results were parked (or the caller's device buffer)
-    if (tk.host_out) { int erc = emit_records(c, c->bufs["out.landmarks" + tslot].p, b, 1, tk.rows, tk.rec); if (erc != SH_OK) return erc; }
-    else if (tk.out_arg) { int erc = emit_records(c, tk.out_arg, b, 1, tk.rows, tk.rec); if (erc != SH_OK) return erc; }
+    if (void* dst = tk.host_out ? c->bufs["out.landmarks" + tslot].p : (void*)tk.out_arg) { int erc = emit_records(c, dst, b, 1, tk.rows, tk.rec); if (erc != SH_OK) return erc; }
     HIPCHK(c, hipMemcpyAsync((int*)c->bufs["out.err" + tslot].p + b, buf<int>(c, "err") + b, 4, hipMemcpyDeviceToDevice, c->stream));
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  {
-    // The one-humerus windows above took their overflow ranges from the pools the void first pass had already drawn on, past
-    // sh_collect's grow-and-rerun check.  A dense humerus (the kind the device hull gives up) may have asked for more than the
-    // pools hold: k_ovf_plan flagged it SH_ERR_CAPACITY_DEV.  Report the demand; sh_collect grows the pools and runs the whole
-    // batch again (hulld.skip keeps the device hull off these humeri by then).
-    unsigned long long ctr[8];
-    HIPCHK(c, hipMemcpyAsync(ctr, c->bufs["ovf.ctr"].p, 64, hipMemcpyDeviceToHost, c->out_stream));
-    HIPCHK(c, hipStreamSynchronize(c->out_stream));
-    if (ctr[3] > c->ovf_seg_cap || ctr[4] > c->ovf_ring_cap || ctr[5] > c->ovf_work_cap || ctr[6] != 0) {
-      if (need) { need[0] = ctr[3]; need[1] = ctr[4]; need[2] = ctr[5]; need[3] = 1; }
-      return SH_OK;
-    }
-  }
+  // The one-humerus windows above drew on the pools past sh_collect's check of the status block.  A dense humerus (the kind the device
+  // hull gives up) may have asked for more than they hold (k_ovf_plan flagged it SH_ERR_CAPACITY_DEV), or its host hull for more than
+  // the k_obb_candidates tier does: the live words get the same verdict, sh_collect raises the capacities and runs the whole batch
+  // again (hulld.skip keeps the device hull off these humeri by then).
+  unsigned long long ctr[SH_NCTR];
+  HIPCHK(c, hipMemcpyAsync(ctr, c->bufs["ovf.ctr"].p, sizeof ctr, hipMemcpyDeviceToHost, c->out_stream));
+  HIPCHK(c, hipStreamSynchronize(c->out_stream));
+  *again = demand_verdict(ctr, demand_caps(c), (tk.mask & SH_STAGE_OBB) != 0, tk.gen == c->batch_gen);
+  if (again->rerun != SH_RERUN_NONE) return SH_OK;
   if (tk.host_out)
     HIPCHK(c, hipMemcpyAsync(tk.host_out, c->bufs["out.landmarks" + tslot].p, (size_t)B * tk.rec, hipMemcpyDeviceToHost, c->out_stream));
-  HIPCHK(c, hipMemcpyAsync(tk.h_err, c->bufs["out.err" + tslot].p, (size_t)B * 4, hipMemcpyDeviceToHost, c->out_stream));
+  HIPCHK(c, hipMemcpyAsync(tk.status, c->bufs["out.err" + tslot].p, (size_t)B * 4, hipMemcpyDeviceToHost, c->out_stream));
   HIPCHK(c, hipStreamSynchronize(c->out_stream));
+  return SH_OK;
+}
+
+// the pinned status block of a ticket (StatusBlock: ONE device-to-host copy and one wait in sh_collect) and its event
+static int ticket_setup(sh_ctx* c, sh_ctx::Ticket& tk, int B) {
+  if (tk.cap < B) {
+    if (tk.status) (void)hipHostFree(tk.status);
+    tk.status = nullptr; tk.cap = 0;
+    HIPCHK(c, hipHostMalloc((void**)&tk.status, StatusBlock::bytes(B)));
+    tk.cap = B;
+  }
+  if (!tk.ev) HIPCHK(c, hipEventCreateWithFlags(&tk.ev, hipEventDisableTiming));
   return SH_OK;
 }
 
@@ -1946,33 +1947,14 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
   HIPCHK(c, hipSetDevice(c->device));
   const int B = c->B;
   sh_ctx::Ticket& tk = c->tickets[c->t_head];
-  if (tk.cap < B) {
-    // the status words of a run as ONE pinned block = one device-to-host copy and one wait in sh_collect (they were three copies and
-    // three waits: each a blit kernel that queues for a CU beside the other lane's UNet): [err: B ints | pad to 8 | overflow pool
-    // counters: 8 x u64 | device hull's give-up words: B ints]
-    if (tk.h_err) (void)hipHostFree(tk.h_err);
-    tk.h_err = nullptr; tk.h_fail = nullptr; tk.h_ovf = nullptr; tk.cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&tk.h_err, status_bytes(B)));
-    tk.cap = B;
-  }
-  tk.h_ovf = (unsigned long long*)((char*)tk.h_err + status_ovf_off(B));      // (the layout follows THIS run's batch size)
-  tk.h_fail = (int*)((char*)tk.h_err + status_ovf_off(B) + SH_NCTR * 8);
-  if (!tk.ev) HIPCHK(c, hipEventCreateWithFlags(&tk.ev, hipEventDisableTiming));
-  {      // the other ticket's pinned block, event and device staging with the first one (else the context's SECOND run pays for them)
-    sh_ctx::Ticket& to = c->tickets[c->t_head ^ 1];
-    if (!to.pending && to.cap < B) {
-      if (to.h_err) (void)hipHostFree(to.h_err);
-      to.h_err = nullptr; to.h_fail = nullptr; to.h_ovf = nullptr; to.cap = 0;
-      HIPCHK(c, hipHostMalloc((void**)&to.h_err, status_bytes(B)));
-      to.cap = B;
-    }
-    if (!to.ev) HIPCHK(c, hipEventCreateWithFlags(&to.ev, hipEventDisableTiming));
+  if (int e = ticket_setup(c, tk, B)) return e;
+  // the other ticket's pinned block, event and device staging with the first one (else the context's SECOND run pays for them)
+  if (sh_ctx::Ticket& to = c->tickets[c->t_head ^ 1]; !to.pending) {
+    if (int e = ticket_setup(c, to, B)) return e;
     const std::string oslot = std::to_string(c->t_head ^ 1);
-    if (!to.pending) {
-      if (int e = ensure(c, ("out.err" + oslot).c_str(), status_bytes(B), 4)) return e;
-      if (out) { hipPointerAttribute_t at{}; const bool dev = hipPointerGetAttributes(&at, out) == hipSuccess && at.type == hipMemoryTypeDevice; (void)hipGetLastError();
-                 if (!dev) { if (int e = ensure(c, ("out.landmarks" + oslot).c_str(), (size_t)B * rec_bytes_rows(c->rec_rows), 1)) return e; } }
-    }
+    if (int e = ensure(c, ("out.err" + oslot).c_str(), StatusBlock::bytes(B), 4)) return e;
+    if (out) { hipPointerAttribute_t at{}; const bool dev = hipPointerGetAttributes(&at, out) == hipSuccess && at.type == hipMemoryTypeDevice; (void)hipGetLastError();
+               if (!dev) { if (int e = ensure(c, ("out.landmarks" + oslot).c_str(), (size_t)B * rec_bytes_rows(c->rec_rows), 1)) return e; } }
   }
   if (!c->out_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->out_stream, hipStreamNonBlocking));
   c->b0 = 0; c->Bwin = B;
@@ -1981,7 +1963,7 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
     int prc = alloc_prox(c);
     if (prc != SH_OK) return prc;
   }
-  { OvfPools OP; int orc = ovf_pools(c, &OP); if (orc != SH_OK) return orc; FILL(c, {buf<int>(c, "err"), (size_t)B * 4, 0}, {OP.ctr, 128, 0}); }      // overflow pools: empty, no demand recorded
+  { OvfPools OP; int orc = ovf_pools(c, &OP); if (orc != SH_OK) return orc; FILL(c, {buf<int>(c, "err"), (size_t)B * 4, 0}, {OP.ctr, SH_NCTR * 8, 0}); }      // overflow pools: empty, no demand recorded
   if (c->open_mode != SH_OPEN_ERROR) FILL(c, {buf<int>(c, "open.stats"), (size_t)B * 8, 0});      // (bridge mode only: the default run has no extra fill)
   c->open_stats_run = c->open_mode;
   if ((mask & SH_STAGE_APPLY) && !(mask & SH_STAGE_CSYS)) return fail(c, SH_ERR_ARG, "sh_run: SH_STAGE_APPLY needs SH_STAGE_CSYS in the same run");
@@ -2015,11 +1997,10 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
   }
   int rc = SH_OK, widx = 0;
   for (int b0 = 0; b0 < B && rc == SH_OK; b0 += win, ++widx) {
-    c->b0 = b0; c->Bwin = std::min(win, B - b0);
+    WindowScope w(c, b0, std::min(win, B - b0));
     rc = run_window(c, mask, widx == 0 ? prepared : -1);
   }
-  // everything of this run is enqueued: the host is free until the device is done -> hulls of the next run
-  c->b0 = 0; c->Bwin = B;      // (in front of start_prepare: it looks the device buffers up through the window offset)
+  // everything of this run is enqueued: the host is free until the device is done -> hulls of the next run (of the whole batch again)
   if (rc == SH_OK && c->overlap && (mask & SH_STAGE_OBB) && win == B && !dev_hull && !c->stg.active) start_prepare(c);
   if (mask & SH_STAGE_OBB) c->obb_injected = true;
   if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
@@ -2034,7 +2015,7 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
   (void)hipGetLastError();
   const std::string tslot = std::to_string(c->t_head);
   void *lm_stage = nullptr, *err_stage = nullptr;
-  if (int e = ensure(c, ("out.err" + tslot).c_str(), status_bytes(B), 4, &err_stage)) return e;      // (the whole status block: the status words lead it)
+  if (int e = ensure(c, ("out.err" + tslot).c_str(), StatusBlock::bytes(B), 4, &err_stage)) return e;      // (the whole status block: the status words lead it)
   tk.host_out = nullptr;
   tk.rows = c->rec_rows; tk.rec = rec_bytes_rows(c->rec_rows);
   if (out_on_device) {
@@ -2046,8 +2027,8 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
   }
   // status words, what the run asked of the overflow pools (k_ovf.h: sh_collect grows them and runs again if it was more than they
   // hold) and which humeri the device hull gave up (its own word per humerus: the status word can be overwritten by a later stage)
-  LAUNCH(c, "k_stage_status", k_stage_status, dim3((unsigned)((std::max(B, SH_NCTR) + 255) / 256)), dim3(256), (const int*)buf<int>(c, "err"), (const unsigned long long*)c->bufs["ovf.ctr"].p,
-         dev_hull ? (const int*)buf<int>(c, "hulld.fail") : (const int*)nullptr, (char*)err_stage, B, status_ovf_off(B));
+  LAUNCH(c, "k_stage_status", k_stage_status, dim3((unsigned)((std::max(B, (int)SH_NCTR) + 255) / 256)), dim3(256), (const int*)buf<int>(c, "err"), (const unsigned long long*)c->bufs["ovf.ctr"].p,
+         dev_hull ? (const int*)buf<int>(c, "hulld.fail") : (const int*)nullptr, StatusBlock{(char*)err_stage, B});
   HIPCHK(c, hipEventRecord(tk.ev, c->stream));
   tk.B = B; tk.pending = true; tk.mask = mask; tk.out_arg = out; tk.dev_hull = dev_hull; tk.gen = c->batch_gen;
   c->rec_mask = mask; c->rec_gen = c->batch_gen;
@@ -2065,95 +2046,51 @@ int sh_collect(sh_ctx* c) {
   HIPCHK(c, hipEventSynchronize(tk.ev));
   if (tk.host_out)
     HIPCHK(c, hipMemcpyAsync(tk.host_out, buf<char>(c, ("out.landmarks" + tslot).c_str()), (size_t)tk.B * tk.rec, hipMemcpyDeviceToHost, c->out_stream));
-  HIPCHK(c, hipMemcpyAsync(tk.h_err, buf<char>(c, ("out.err" + tslot).c_str()), status_bytes(tk.B), hipMemcpyDeviceToHost, c->out_stream));      // status, pool counters, give-up words
+  HIPCHK(c, hipMemcpyAsync(tk.status, buf<char>(c, ("out.err" + tslot).c_str()), StatusBlock::bytes(tk.B), hipMemcpyDeviceToHost, c->out_stream));      // status, demand block, give-up words
   HIPCHK(c, hipStreamSynchronize(c->out_stream));
-  {
-    const unsigned long long need_s = tk.h_ovf[3], need_r = tk.h_ovf[4], need_w = tk.h_ovf[5];
-    const uint32_t slice_stages = SH_STAGE_FULL | SH_STAGE_DISTAL | SH_STAGE_NECK | SH_STAGE_PROXIMAL;
-    // (only a run that computed its own frame may vouch for the batch: a run on an injected frame says nothing about the planes of
-    // the next SH_STAGE_OBB, and the `pobb` set of a proximal humerus runs inside that stage)
-    if (need_r == 0 && need_s == 0 && (tk.mask & SH_STAGE_OBB) &&
-        (tk.mask & slice_stages) == (c->params.bone_kind == SH_BONE_PROXIMAL ? (slice_stages & ~(uint32_t)SH_STAGE_DISTAL) : slice_stages) &&
-        tk.gen == c->batch_gen)
-      c->ovf_none_gen = c->batch_gen;
-    if (tk.h_ovf[6] != 0) {
-      // the overflow tier was skipped and a plane needed it (k_slice_link_large): the planes moved after the run that vouched for the
-      // batch.  The records of this run are void -- run it again with the tier on.
-      c->ovf_none_gen = ~0ull;
-      if (c->n_pending != 0)
-        return fail(c, SH_ERR_CAPACITY, "a section needs the overflow tier while another run is in flight: collect it, then run the batch again (the tier is on by then)");
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      const uint32_t mask = tk.mask; sh_landmarks* out = tk.out_arg;
-      int rc2 = sh_submit(c, mask, out);
-      if (rc2 != SH_OK) return rc2;
-      return sh_collect(c);
+  const StatusBlock st{tk.status, tk.B};
+  const unsigned long long* w = st.words();
+  const uint32_t slice_stages = SH_STAGE_FULL | SH_STAGE_DISTAL | SH_STAGE_NECK | SH_STAGE_PROXIMAL;
+  // (only a run that computed its own frame may vouch for the batch: a run on an injected frame says nothing about the planes of
+  // the next SH_STAGE_OBB, and the `pobb` set of a proximal humerus runs inside that stage)
+  if (w[SH_CTR_RING_NEED] == 0 && w[SH_CTR_SEG_NEED] == 0 && (tk.mask & SH_STAGE_OBB) &&
+      (tk.mask & slice_stages) == (c->params.bone_kind == SH_BONE_PROXIMAL ? (slice_stages & ~(uint32_t)SH_STAGE_DISTAL) : slice_stages) &&
+      tk.gen == c->batch_gen)
+    c->ovf_none_gen = c->batch_gen;
+  if (c->sw.debug) fprintf(stderr, "[sh] collect: ovf need %llu %llu %llu cap %llu %llu %llu err0 %d\n", w[SH_CTR_SEG_NEED], w[SH_CTR_RING_NEED], w[SH_CTR_WORK_NEED], c->ovf_seg_cap, c->ovf_ring_cap, c->ovf_work_cap, st.err()[0]);
+  // Are the records valid as far as capacity goes?  The status block's demand words first; then the humeri the device hull gave up
+  // are done again alone, and their one-humerus windows may raise a demand of their own.
+  Verdict v = demand_verdict(w, demand_caps(c), (tk.mask & SH_STAGE_OBB) != 0, tk.gen == c->batch_gen);
+  const bool redo = v.rerun == SH_RERUN_NONE && tk.dev_hull;
+  if (redo) { if (int e = redo_given_up(c, tk, st, tslot, &v)) return e; }
+  if (v.rerun != SH_RERUN_NONE) {
+    // The records of this run are void: the whole batch again, with what it asked for -- here, synchronously, when nothing else is
+    // in flight.  (The overflow tier is on for it when a plane needed it while it was skipped, and behind a redo: its hulls change.)
+    if (v.rerun == SH_RERUN_TIER || redo) c->ovf_none_gen = ~0ull;
+    if (c->n_pending != 0)
+      return fail(c, SH_ERR_CAPACITY,
+                  v.rerun == SH_RERUN_TIER ? "a section needs the overflow tier while another run is in flight: collect it, then run the batch again (the tier is on by then)" :
+                  v.rerun == SH_RERUN_OBB_TIER ? "the OBB stage needs a larger tier while another run is in flight: collect it, then run the batch again (the tier is chosen by then)" :
+                  v.rerun == SH_RERUN_FORCE_HOST ? "a hull is above the device hull's record while another run is in flight: collect it, then run the batch again (its hulls come from the host by then)" :
+                  "slice overflow pools too small while another run is in flight: collect it, then run the batch again (the pools are grown by then)");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ovf_seg_cap = v.caps.seg; c->ovf_ring_cap = v.caps.ring; c->ovf_work_cap = v.caps.work;
+    c->obb_sil_need = v.caps.sil_need; c->obb_nf_over = v.caps.nf_over;
+    if (v.error) return fail(c, SH_ERR_CAPACITY, v.error);
+    if (v.caps.end != c->end_cap) {
+      c->end_cap = v.caps.end;
+      const size_t eb = (size_t)c->B * 2 * c->end_cap * 2 * 8;
+      if (int e = ensure(c, "obb.endpts", eb, 8)) return e;
+      c->bufs["obb.endpts"].per_mesh = eb / (size_t)c->B;
     }
-    if (c->sw.debug) fprintf(stderr, "[sh] collect: ovf need %llu %llu %llu cap %llu %llu %llu err0 %d\n", need_s, need_r, need_w, c->ovf_seg_cap, c->ovf_ring_cap, c->ovf_work_cap, tk.h_err[0]);
-    if ((tk.h_ovf[8] != 0 || tk.h_ovf[9] != 0) && (tk.mask & SH_STAGE_OBB) && tk.gen == c->batch_gen) {
-      // k_obb_candidates met a direction with more silhouette edges than its tier's lists hold (or, behind a device hull, a record with
-      // more faces than its masks): the records of this run are void -- the batch again, on the tier that holds it (run_obb)
-      if (c->n_pending != 0)
-        return fail(c, SH_ERR_CAPACITY, "the OBB stage needs a larger tier while another run is in flight: collect it, then run the batch again (the tier is chosen by then)");
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      if ((int)tk.h_ovf[8] <= c->obb_sil_need && !(tk.h_ovf[9] != 0 && !c->obb_nf_over))
-        return fail(c, SH_ERR_CAPACITY, "k_obb_candidates: silhouette demand did not shrink on the workspace tier");      // (cannot happen: its lists hold what the last run asked for)
-      c->obb_sil_need = std::max(c->obb_sil_need, (int)std::min<unsigned long long>(tk.h_ovf[8], 1ull << 30));
-      if (tk.h_ovf[9] != 0) c->obb_nf_over = true;
-      const uint32_t mask = tk.mask; sh_landmarks* out = tk.out_arg;
-      int rc2 = sh_submit(c, mask, out);
-      if (rc2 != SH_OK) return rc2;
-      return sh_collect(c);
-    }
-    const unsigned long long need_e = tk.h_ovf[7];
-    if (need_s > c->ovf_seg_cap || need_r > c->ovf_ring_cap || need_w > c->ovf_work_cap || need_e > (unsigned long long)c->end_cap) {
-      // The batch has more overflow planes than the pools hold (a first dense mesh): grow them to what the run asked for,
-      // with headroom, and run the batch again -- here, synchronously, when nothing else is in flight.
-      if (c->n_pending != 0)
-        return fail(c, SH_ERR_CAPACITY, "slice overflow pools too small while another run is in flight: collect it, then run the batch again (the pools are grown by then)");
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      c->ovf_seg_cap = std::max(c->ovf_seg_cap, need_s + need_s / 4);
-      c->ovf_ring_cap = std::max(c->ovf_ring_cap, need_r + need_r / 4);
-      c->ovf_work_cap = std::max(c->ovf_work_cap, need_w + need_w / 4);
-      if (need_e > (unsigned long long)c->end_cap) {      // an end section of the box with more crossing points than "obb.endpts" holds (a very dense mesh)
-        if (need_e > (1ull << 26)) return fail(c, SH_ERR_CAPACITY, "an end section has more than 2^26 crossing points");
-        c->end_cap = (int)(need_e + need_e / 4);
-        const size_t eb = (size_t)c->B * 2 * c->end_cap * 2 * 8;
-        if (int e = ensure(c, "obb.endpts", eb, 8)) return e;
-        c->bufs["obb.endpts"].per_mesh = eb / (size_t)c->B;
-      }
-      const uint32_t mask = tk.mask; sh_landmarks* out = tk.out_arg;
-      int rc2 = sh_submit(c, mask, out);
-      if (rc2 != SH_OK) return rc2;
-      return sh_collect(c);
-    }
-  }
-  if (tk.dev_hull) {
-    std::vector<int> gave_up;
-    for (int b = 0; b < tk.B; ++b) if (tk.h_fail[b] != 0) gave_up.push_back(b);
-    if (!gave_up.empty()) {
-      unsigned long long need[4] = {0, 0, 0, 0};
-      int rc2 = redo_given_up(c, tk, tslot, gave_up, need);
-      if (rc2 != SH_OK) return rc2;
-      if (need[3]) {
-        if (c->n_pending != 0)
-          return fail(c, SH_ERR_CAPACITY, "slice overflow pools too small while another run is in flight: collect it, then run the batch again (the pools are grown by then)");
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->ovf_none_gen = ~0ull;
-        c->ovf_seg_cap = std::max(c->ovf_seg_cap, need[0] + need[0] / 4);
-        c->ovf_ring_cap = std::max(c->ovf_ring_cap, need[1] + need[1] / 4);
-        c->ovf_work_cap = std::max(c->ovf_work_cap, need[2] + need[2] / 4);
-        const uint32_t mask = tk.mask; sh_landmarks* out = tk.out_arg;
-        int rc3 = sh_submit(c, mask, out);
-        if (rc3 != SH_OK) return rc3;
-        return sh_collect(c);
-      }
-    }
+    if (int e = sh_submit(c, tk.mask, tk.out_arg)) return e;
+    return sh_collect(c);
   }
   for (int b = 0; b < tk.B; ++b)
-    if (tk.h_err[b] != 0) {
+    if (st.err()[b] != 0) {
       char m[128];
-      snprintf(m, sizeof m, "mesh %d: device stage error %d (capacity=-4, geometry=-5)", b, tk.h_err[b]);
-      return fail(c, tk.h_err[b], m);
+      snprintf(m, sizeof m, "mesh %d: device stage error %d (capacity=-4, geometry=-5)", b, st.err()[b]);
+      return fail(c, st.err()[b], m);
     }
   return SH_OK;
 }
@@ -2245,14 +2182,13 @@ int sh_mesh_open_edges(sh_ctx* c, int64_t* out) {
   HIPCHK(c, hipMemsetAsync(keys, 0xFF, (size_t)toff[B] * 8, c->stream));
   HIPCHK(c, hipMemsetAsync(uses, 0, (size_t)toff[B] * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(cnt, 0, (size_t)B * 8, c->stream));
-  const int b0 = c->b0; c->b0 = 0;      // (whole batch)
+  WindowScope whole(c, 0, c->Bwin);      // (whole batch)
   LAUNCH(c, "k_edge_insert", k_edge_insert, dim3((unsigned)std::min<long long>((c->maxF + 255) / 256, 1024), (unsigned)B), dim3(256),
          (const int*)c->bufs["faces"].p, (const long long*)c->bufs["foff"].p, (const long long*)dtoff, keys, uses);
   long long tmax = 0;
   for (int b = 0; b < B; ++b) tmax = std::max(tmax, toff[b + 1] - toff[b]);
   LAUNCH(c, "k_edge_count_open", k_edge_count_open, dim3((unsigned)std::min<long long>((tmax + 255) / 256, 1024), (unsigned)B), dim3(256),
          (const long long*)dtoff, (const unsigned long long*)keys, (const int*)uses, cnt);
-  c->b0 = b0;
   std::vector<unsigned long long> h((size_t)B);
   HIPCHK(c, hipMemcpyAsync(h.data(), cnt, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

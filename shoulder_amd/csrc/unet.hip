@@ -459,10 +459,9 @@ int sh_unet_infer(sh_ctx* c, const float* images, int n, int H, int W, float* lo
   int rc;
   if ((rc = ensure(c, "infer.image", bytes, 4)) != SH_OK) return rc;
   if ((rc = ensure(c, "infer.logits", bytes, 4)) != SH_OK) return rc;
-  const int b0 = c->b0; c->b0 = 0;      // named buffers below are whole-batch
+  WindowScope whole(c, 0, c->Bwin);      // named buffers below are whole-batch
   HIPCHK(c, hipMemcpyAsync(buf<float>(c, "infer.image"), images, bytes, hipMemcpyHostToDevice, c->stream));
   rc = unet_dispatch(c, buf<float>(c, "infer.image"), buf<float>(c, "infer.logits"), n, H, W);
-  c->b0 = b0;
   if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
   HIPCHK(c, hipMemcpyAsync(logits, buf<float>(c, "infer.logits"), bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import BONES
+from conftest import BONES, GOLDEN
 from oracle.humerus import OracleHumerus
 from shoulder_amd import _lib
 from shoulder_amd.engine import ShoulderHipError
@@ -383,6 +383,56 @@ def test_a_silhouette_longer_than_the_tier_lists(nrim, size, tier):
         e.upload([(small_v, small_f)])                                        # the next batch starts on the small tier again
         alone = e.run(_lib.STAGE_OBB).copy()
         np.testing.assert_array_equal(alone[0]["obb_transform"], lm[0]["obb_transform"])
+    finally:
+        e.close()
+
+
+def test_a_given_up_humerus_whose_redo_overflows_the_candidates_tier():
+    """The device hull gives a lens with 8 672 points up (all on the hull: above the 8 192 it takes), its host hull fits the default
+    record (so this is not the force-host path) and has 17 340 faces -- the large tier of k_obb_candidates, 2 048 silhouette edges per
+    direction -- but along the short axis the silhouette is the equator, 2 600 edges.  The demand is raised by the redo's one-humerus
+    window, behind sh_collect's check of the status block: the redo reads the whole demand block back and the batch runs again on the
+    workspace tier (it ended in SH_ERR_CAPACITY).  Asserts what test_a_silhouette_longer_than_the_tier_lists asserts.
+    The input is chosen so that the host quickhull of the redo returns the mesh's own hull, face for face, which the comparison with
+    the oracle at 1e-6 presupposes: with 8 000 of the points on the equator (lens_surface(8000, 600)) neighbours on the rim are
+    collinear to float32 rounding, sh_hull.h keeps 8 138 of the 8 552 vertices and the box differs from the oracle's by 1.3 mm."""
+    import ctypes
+    import subprocess
+    from conftest import ROOT, lens_surface
+    from shoulder_amd.engine import Engine
+    v, f = lens_surface(2600, 6600, seed=2, size=4.0)
+    # the path, established on the host: given up (points), default record (16 384 v / 32 768 f / 49 152 e), large tier, its lists too short
+    assert 8192 < len(v) <= 16384 and 8192 < len(f) <= 32768 and 3 * len(f) // 2 <= 49152
+    p = np.ascontiguousarray(v.astype(np.float64))
+    n = np.cross(p[f[:, 1]] - p[f[:, 0]], p[f[:, 2]] - p[f[:, 0]])
+    front = n @ n[np.argmax(np.linalg.norm(n, axis=1))] > 0      # seen along the normal of the largest face (on a cap: near the short axis)
+    edges = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)
+    order = np.lexsort((edges[:, 1], edges[:, 0]))
+    face = np.tile(np.arange(len(f)), 3)[order]
+    assert (edges[order][0::2] == edges[order][1::2]).all()
+    assert int((front[face[0::2]] != front[face[1::2]]).sum()) > 2048
+    # ... and the host quickhull (sh_hull.h through the host shim) gives the faces of the mesh
+    hc = os.path.join(ROOT, "tests", "hostcheck")
+    if not os.path.exists(os.path.join(hc, "libhostcheck.so")):
+        subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-o", os.path.join(hc, "libhostcheck.so"), os.path.join(hc, "hostcheck.cpp")])
+    tris = np.zeros(3 * 32768, np.int32)
+    nf = ctypes.CDLL(os.path.join(hc, "libhostcheck.so")).hc_hull_tris_pts(p.ctypes.data_as(ctypes.c_void_p), len(p), tris.ctypes.data_as(ctypes.c_void_p), 32768)
+    assert nf == len(f) and {tuple(sorted(t)) for t in tris[:3 * nf].reshape(-1, 3).tolist()} == {tuple(sorted(t)) for t in f.tolist()}
+    # obb.oriented_bounds_large(p)[0], recorded (tests/golden/make_lens_box_frame.py): 17 340 directions with silhouettes of up to
+    # 2 600 edges take the oracle minutes
+    T_box = np.load(os.path.join(GOLDEN, "lens_box_frame.npy"))
+    small_v, small_f = load_stl(os.path.join(BONES, "humerus_left.stl"))
+    e = Engine(0)
+    try:
+        e.set_hull_mode("device")
+        e.upload([(small_v, small_f), (v, f)])
+        lm = e.run(_lib.STAGE_OBB).copy()
+        assert (lm["status"] == 0).all()
+        np.testing.assert_allclose(e.fetch("obb.T_pre", np.float64, (2, 4, 4))[1], T_box, rtol=0, atol=1e-6)
+        e.fetch("obb.ws_fmask", np.uint8, (16,))                              # the workspace tier ran
+        again = e.run(_lib.STAGE_OBB).copy()                                  # the resident batch: on the right tier the first time now
+        assert again[0].tobytes() == lm[0].tobytes()
+        np.testing.assert_allclose(e.fetch("obb.T_pre", np.float64, (2, 4, 4))[1], T_box, rtol=0, atol=1e-6)
     finally:
         e.close()
 
