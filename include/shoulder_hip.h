@@ -347,6 +347,50 @@ int sh_resect_offsets(sh_ctx*, const sh_cut_offset* offs /* P, the same for ever
  * *n_out = n + 1 is set; a cut without a ring (status != 0, no loop): *n_out = 0. */
 int sh_resect_ring   (sh_ctx*, int b, int p, double* out /* cap x 3, CT */, int cap, int* n_out);
 
+/* ---- head sizing of a cut: the spherical cap that replaces the resected head and the ellipse of the cut it sits on --------
+ * The reference stops in front of this step (arthroplasty.py:178-182, a commented-out `HumeralImplantation`); its
+ * `RadiusCurvature` (bone_props.py:114-148) fits one sphere to the articular points of the NATIVE head.  Here every cut of a
+ * batched resection gets the sphere of ITS head piece and the two diameters of ITS cut, in the same device pass (k_headfit.h).
+ *
+ * For a cut (o = plane_point, n = plane_normal) let T be the triangles whose terms enter head_volume / head_area: whole faces
+ * on the normal's side, the two triangles (a, b, n0), (n0, n1, a) of a cut quad, the one triangle of a cut corner, as
+ * `slice_plane` re-triangulates them (oracle/clip.py).
+ *   samples   every corner p of every triangle of T, weight w = A / 3 (A the triangle's area: the surface lumped onto its
+ *             vertices, so the fit does not follow mesh density), coordinates q = p - o (the terms stay small, as head_volume's)
+ *   moments   sixteen doubles per cut: S0 = sum w | S1 = sum w q (3) | S2 = sum w q q^T (xx, xy, xz, yy, yz, zz) | S3 = sum w |q|^2 q
+ *             (3) | S4 = sum w |q|^4 | two zero words.  Per (humerus, plane, tile of 256 faces) they are reduced in a fixed order
+ *             and stored, the tiles are added in tile order: the moments, and with them the whole record, are the same bits
+ *             whatever the batch, the humerus' position in it or P.  Named buffer "resect.fit_moments" (B x P x 16 doubles, sh_fetch).
+ *   sphere    weighted algebraic least squares: minimise sum w (|q|^2 - 2 c.q - t)^2, normal equations
+ *             [[4 S2, 2 S1], [2 S1^T, S0]] [c; t] = [2 S3; tr S2], r = sqrt(t + |c|^2), centre o + c; solved after a shift to the
+ *             weighted centroid (sh_scalar.h head_sphere_from_moments, the same source on host and device).
+ *             sphere_rms = sqrt(max(E, 0) / S0) / (2 r), E = S4 - rhs.[c; t] the minimum of the objective: the radial rms to
+ *             first order, mm.  cap_height = r + c.n / |n|: thickness of the sphere's cap above the plane.
+ *   ellipse   of the LARGEST loop (the one cut_area / cut_centroid describe): the polygon's area second moments about its area
+ *             centroid in base.Section's basis (u, w) (see sh_resection), divided by the polygon area, eigenvalues l1 >= l2;
+ *             cut_semi_major = 2 sqrt(l1), cut_semi_minor = 2 sqrt(l2): the semi-axes of the ellipse with the same area moments.
+ *             cut_major_dir: unit eigenvector of l1 in CT, its first non-zero component (x, y, z order) positive.
+ *   offsets   center_articular = csys_articular of the humerus' record applied to the sphere centre: origin at the canal-axis
+ *             midpoint, z the canal, so x / y are the posterior-anterior / lateral-medial offsets in the conventions of
+ *             sh_cut_offset's anterior_mm / medial_mm.  NaN when the resident batch has no collected run with SH_STAGE_ANP |
+ *             SH_STAGE_CSYS (possible with sh_resect_planes_fit) or the humerus' record failed.
+ * sphere_status: 0 with all sphere fields 0 for an empty piece (S0 = 0); SH_ERR_GEOMETRY with sphere fields 0 when the normal
+ * matrix is not safely positive definite (all samples coplanar, ...: pivot threshold in sh_scalar.h).  ring_status: the cut's
+ * own status (sh_resection.status); ring fields are zero when it is non-zero or the cut has no loop.  A humerus whose record
+ * failed (sh_resect_offsets_fit) carries that status in both.  A bad fit never fails the batch. */
+typedef struct sh_head_fit {
+  double sphere_center[3], sphere_radius, sphere_rms, cap_height, fit_area /* = S0 */;
+  double center_articular[3];
+  double cut_semi_major, cut_semi_minor, cut_major_dir[3];
+  int32_t sphere_status, ring_status;   /* 0 or a negative sh_status, each for its half */
+} sh_head_fit;
+/* sh_resect_planes / sh_resect_offsets with the head fit of every cut: same preconditions, argument checks and state errors;
+ * `out` is byte-equal to what the un-fitted call writes for the same cuts (the same kernels write it); fit_out: B x P, host.
+ * A sweep is split into passes of at most 4 096 cuts (the un-fitted calls: 8 192) and 128 MB of moment slab (128 B per cut
+ * and tile); the pass a cut falls into does not change its records. */
+int sh_resect_planes_fit (sh_ctx*, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out);
+int sh_resect_offsets_fit(sh_ctx*, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

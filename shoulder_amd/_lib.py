@@ -95,6 +95,21 @@ RESECTION_DTYPE = np.dtype([
 assert RESECTION_DTYPE.itemsize == ctypes.sizeof(Resection)
 
 
+class HeadFit(ctypes.Structure):
+    """sh_head_fit: the sphere of the resected head piece and the ellipse of the cut, one (humerus, plane)."""
+    _fields_ = [("sphere_center", ctypes.c_double * 3), ("sphere_radius", ctypes.c_double), ("sphere_rms", ctypes.c_double),
+                ("cap_height", ctypes.c_double), ("fit_area", ctypes.c_double), ("center_articular", ctypes.c_double * 3),
+                ("cut_semi_major", ctypes.c_double), ("cut_semi_minor", ctypes.c_double), ("cut_major_dir", ctypes.c_double * 3),
+                ("sphere_status", ctypes.c_int32), ("ring_status", ctypes.c_int32)]
+
+
+HEAD_FIT_DTYPE = np.dtype([
+    ("sphere_center", "<f8", (3,)), ("sphere_radius", "<f8"), ("sphere_rms", "<f8"), ("cap_height", "<f8"), ("fit_area", "<f8"),
+    ("center_articular", "<f8", (3,)), ("cut_semi_major", "<f8"), ("cut_semi_minor", "<f8"), ("cut_major_dir", "<f8", (3,)),
+    ("sphere_status", "<i4"), ("ring_status", "<i4")])
+assert HEAD_FIT_DTYPE.itemsize == ctypes.sizeof(HeadFit)
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -108,7 +123,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_comm_init_all", "sh_bcast_weights", "sh_gather_landmarks", "sh_set_keep_products",
            "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring",
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
-           "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring"]
+           "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit"]
 
 _lib = None
 
@@ -199,5 +214,8 @@ def load(build_if_missing=True):
         L.sh_resect_planes.argtypes = [vp, vp, ctypes.c_int, vp]
         L.sh_resect_offsets.argtypes = [vp, vp, ctypes.c_int, vp]
         L.sh_resect_ring.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    if not alt or hasattr(L, "sh_resect_planes_fit"):      # (tools/time_head_fit.py parent)
+        L.sh_resect_planes_fit.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+        L.sh_resect_offsets_fit.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     _lib = L
     return L

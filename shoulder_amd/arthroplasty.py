@@ -102,6 +102,24 @@ class HumeralHeadOsteotomy:
         rec = bone._engine.resect(planes=np.concatenate([p, n]).reshape(1, 1, 6))[0, 0]
         return {k: (rec[k].copy() if rec[k].ndim else rec[k].item()) for k in rec.dtype.names}
 
+    def _plane_ct(self):
+        cut = self.plane
+        return transform_plane_pn(cut.point, cut.normal, inv_transform(np.array(self._humerus._tfrm.matrix, dtype=np.float64)))
+
+    def head_fit(self) -> dict:
+        """The sphere of the current cut's head piece and the ellipse of its cut (sh_resect_planes_fit with B = P = 1, the
+        counterpart of `measure()`): the fields of sh_head_fit as a dict, in CT.  `center_articular` needs the humerus' landmarks on
+        the device (NaN otherwise)."""
+        p, n = self._plane_ct()
+        bone = self._humerus
+        bone._ensure_loaded()
+        fit = bone._engine.resect(planes=np.concatenate([p, n]).reshape(1, 1, 6), fit=True)[1][0, 0]
+        return {k: (fit[k].copy() if fit[k].ndim else fit[k].item()) for k in fit.dtype.names}
+
+    def implant_head(self, catalogue=None) -> dict:
+        """The planned spherical cap for the current cut, from `head_fit()` (the step the reference leaves open, arthroplasty.py:178-182)."""
+        return implant_from_fit(self.head_fit(), self._humerus.side(), catalogue)
+
     # ---- offsets (arthroplasty.py:89-175) ------------------------------------------------------------------
     def offset_retroversion(self, deg: float) -> None:
         """more retroversion for positive `deg` (the azimuth decreases on a left humerus, increases on a right one)"""
@@ -125,3 +143,23 @@ class HumeralHeadOsteotomy:
     def offset_medial_lateral(self, mm):
         """medial (+) / lateral (-): -y of the anp csys"""
         self._shift([0.0, -mm, 0.0])
+
+
+def implant_from_fit(fit, side, catalogue=None) -> dict:
+    """A head-fit record (dict or structured scalar with sh_head_fit's fields) -> the cap a planner picks: `radius` of curvature,
+    `thickness` (= cap_height), `base_diameters` (2 x the cut's semi-axes, major first), `center` (CT), and the centre's offsets from
+    the canal axis in the canal / articular frame signed as offset_medial_lateral / offset_anterior_posterior count them
+    (`medial_offset` = -y; `posterior_offset` = -x on a right humerus, +x on a left one).  catalogue: (diameter, thickness) pairs;
+    `catalogue_index` is the pair nearest in (2 radius, thickness).  Pure NumPy."""
+    if fit["sphere_status"] != 0 or not fit["sphere_radius"] > 0:
+        raise ValueError("the cut has no head sphere (sphere_status %d)" % fit["sphere_status"])
+    ca = np.asarray(fit["center_articular"], dtype=np.float64)
+    sign = 1.0 if side == "right" else -1.0
+    out = dict(radius=float(fit["sphere_radius"]), thickness=float(fit["cap_height"]),
+               base_diameters=(2.0 * float(fit["cut_semi_major"]), 2.0 * float(fit["cut_semi_minor"])),
+               medial_offset=float(-ca[1]), posterior_offset=float(-sign * ca[0]), center=np.array(fit["sphere_center"], dtype=np.float64))
+    if catalogue is not None:
+        cat = np.asarray(catalogue, dtype=np.float64).reshape(-1, 2)
+        d = (cat[:, 0] - 2.0 * out["radius"]) ** 2 + (cat[:, 1] - out["thickness"]) ** 2
+        out["catalogue_index"] = int(np.argmin(d))
+    return out

@@ -729,4 +729,83 @@ SH_HD bool resect_plane_from_offsets(const double* T_anp, const double* p_ct, co
   return true;
 }
 
+// ---- head sizing of a cut (include/shoulder_hip.h sh_head_fit; k_headfit.h) ------------------------------------------------
+// The weighted algebraic least-squares sphere (bone_props.py:114-148 `_spherefit`, with weights) from the sixteen moment words
+// of a cut: m[0] = S0, m[1..3] = S1, m[4..9] = S2 (xx, xy, xz, yy, yz, zz), m[10..12] = S3, m[13] = S4, coordinates q about
+// the plane point.  The moments are shifted to the weighted centroid g = S1 / S0 first: there sum w p = 0, so the normal
+// equations [[4 S2, 2 S1], [2 S1^T, S0]] [c; t] = [2 S3; tr S2] fall apart into 4 C c' = 2 K3 (C the covariance, K3 = E |p|^2 p)
+// and t' = tr C; C is solved by a 3 x 3 Cholesky factorisation.  c = g + c' (about the plane point), r = sqrt(t' + |c'|^2),
+// rms = sqrt(max(E, 0)) / (2 r) with E = K4 - 2 K3 . c' - (tr C)^2 the minimum of the objective per unit weight.
+// A pivot at or below SH_HEADFIT_PIVOT x tr(S2) / S0 is not told from zero (false): the moments are sums of n <= 2^21 terms
+// added in some fixed order, so each carries up to 4 n 2^-53 = 2^-30 of its sum of magnitudes, and the shift to the centroid
+// subtracts numbers of the size tr(S2) / S0; 2^-26 leaves a factor 16 on that bound.  One operation order, sqrt and divisions
+// only: the host instantiation (tests/hostcheck/headfit_check.cpp) gives the device's bits.
+#define SH_HEADFIT_PIVOT 1.4901161193847656e-08      /* 2^-26 */
+SH_HD bool head_sphere_from_moments(const double* m, double* c, double* r, double* rms) {
+  c[0] = c[1] = c[2] = 0.0; *r = 0.0; *rms = 0.0;
+  const double S0 = m[0];
+  if (!(S0 > 0.0)) return false;
+  const double g[3] = {m[1] / S0, m[2] / S0, m[3] / S0};
+  const double M2[6] = {m[4] / S0, m[5] / S0, m[6] / S0, m[7] / S0, m[8] / S0, m[9] / S0};
+  const double M3[3] = {m[10] / S0, m[11] / S0, m[12] / S0};
+  const double M4 = m[13] / S0;
+  const double tr = (M2[0] + M2[3]) + M2[5];
+  const double gg = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+  // covariance, third and fourth moments about the centroid
+  const double Cxx = M2[0] - g[0] * g[0], Cxy = M2[1] - g[0] * g[1], Cxz = M2[2] - g[0] * g[2];
+  const double Cyy = M2[3] - g[1] * g[1], Cyz = M2[4] - g[1] * g[2], Czz = M2[5] - g[2] * g[2];
+  const double Mg[3] = {(M2[0] * g[0] + M2[1] * g[1]) + M2[2] * g[2], (M2[1] * g[0] + M2[3] * g[1]) + M2[4] * g[2],
+                        (M2[2] * g[0] + M2[4] * g[1]) + M2[5] * g[2]};
+  double K3[3];
+  for (int i = 0; i < 3; ++i) K3[i] = ((M3[i] - 2.0 * Mg[i]) - tr * g[i]) + 2.0 * gg * g[i];
+  const double gM3 = (g[0] * M3[0] + g[1] * M3[1]) + g[2] * M3[2], gMg = (g[0] * Mg[0] + g[1] * Mg[1]) + g[2] * Mg[2];
+  const double K4 = (((M4 - 4.0 * gM3) + 4.0 * gMg) + 2.0 * gg * tr) - 3.0 * gg * gg;
+  const double trC = (Cxx + Cyy) + Czz;
+  // Cholesky C = L L^T, pivots against the size of the numbers the shift subtracted
+  const double tiny = SH_HEADFIT_PIVOT * tr;
+  if (!(Cxx > tiny)) return false;
+  const double l00 = sqrt(Cxx), l10 = Cxy / l00, l20 = Cxz / l00;
+  const double d1 = Cyy - l10 * l10;
+  if (!(d1 > tiny)) return false;
+  const double l11 = sqrt(d1), l21 = (Cyz - l20 * l10) / l11;
+  const double d2 = (Czz - l20 * l20) - l21 * l21;
+  if (!(d2 > tiny)) return false;
+  const double l22 = sqrt(d2);
+  // 4 C c' = 2 K3
+  const double y0 = (0.5 * K3[0]) / l00, y1 = (0.5 * K3[1] - l10 * y0) / l11, y2 = ((0.5 * K3[2] - l20 * y0) - l21 * y1) / l22;
+  const double c2 = y2 / l22, c1 = (y1 - l21 * c2) / l11, c0 = ((y0 - l10 * c1) - l20 * c2) / l00;
+  const double r2 = trC + ((c0 * c0 + c1 * c1) + c2 * c2);
+  if (!(r2 > 0.0) || !(r2 < 1e300)) return false;
+  const double E = (K4 - 2.0 * ((K3[0] * c0 + K3[1] * c1) + K3[2] * c2)) - trC * trC;
+  c[0] = g[0] + c0; c[1] = g[1] + c1; c[2] = g[2] + c2;
+  *r = sqrt(r2);
+  *rms = sqrt(E > 0.0 ? E : 0.0) / (2.0 * *r);
+  return true;
+}
+
+// The ellipse with the area second moments of a polygon from its six shoelace sums about the in-plane origin: rm[0] = sum cr
+// (cr = x0 y1 - x1 y0; twice the signed area), rm[1] = sum (x0 + x1) cr, rm[2] = sum (y0 + y1) cr, rm[3] = sum cr (x0^2 + x0 x1
+// + x1^2), rm[4] = the same in y, rm[5] = sum cr (x0 y1 + 2 x0 y0 + 2 x1 y1 + x1 y0).  The second-moment tensor about the area
+// centroid divided by the area has eigenvalues l1 >= l2; semi-axes 2 sqrt(l1), 2 sqrt(l2); dir = unit eigenvector of l1 in the
+// (x, y) basis ((1, 0) when the two are equal).  False: no area or a tensor that is not positive.
+SH_HD bool ellipse_from_moments(const double* rm, double* semi_major, double* semi_minor, double* dir) {
+  *semi_major = 0.0; *semi_minor = 0.0; dir[0] = 0.0; dir[1] = 0.0;
+  const double a2 = rm[0];
+  if (!(a2 != 0.0)) return false;
+  const double cx = rm[1] / (3.0 * a2), cy = rm[2] / (3.0 * a2);
+  const double mxx = rm[3] / (6.0 * a2) - cx * cx, myy = rm[4] / (6.0 * a2) - cy * cy, mxy = rm[5] / (12.0 * a2) - cx * cy;
+  const double mean = 0.5 * (mxx + myy), d = 0.5 * (mxx - myy), rad = sqrt(d * d + mxy * mxy);
+  const double l1 = mean + rad, l2 = mean - rad;
+  if (!(l2 > 0.0) || !(l1 < 1e300)) return false;
+  double vx = 1.0, vy = 0.0;
+  if (rad > 0.0) {
+    if (d >= 0.0) { vx = d + rad; vy = mxy; } else { vx = mxy; vy = rad - d; }
+    const double vl = sqrt(vx * vx + vy * vy);
+    vx /= vl; vy /= vl;
+  }
+  *semi_major = 2.0 * sqrt(l1); *semi_minor = 2.0 * sqrt(l2);
+  dir[0] = vx; dir[1] = vy;
+  return true;
+}
+
 }  // namespace sh

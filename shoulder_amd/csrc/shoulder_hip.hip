@@ -11,6 +11,7 @@
 #include "k_stl.h"
 #include "k_clip.h"
 #include "k_resect.h"
+#include "k_headfit.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -814,8 +815,24 @@ static int resect_buffers(sh_ctx* c, int P, int* pc_out, int* tmax_out) {
   return SH_OK;
 }
 
-// face pass + join of planes [p0, p0 + pc) of humeri [b0, b0 + nb); one: the record and ring of a single cut (sh_resect_ring)
-static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tmax, bool one) {
+// The head fit's buffers (k_headfit.h) on top of resect_buffers': its moment slab (128 B per cut and tile) has 128 MB of its own and
+// a pass takes at most 4 096 cuts, so the planes per pass of a fitted sweep are at most the un-fitted ones -- which keep their split.
+static int headfit_buffers(sh_ctx* c, int P, int pc, int tmax, int* pcf_out) {
+  const int B = c->B;
+  long long pcf = std::min<long long>(4096 / B, (128LL << 20) / (8LL * SH_HF_WORDS * B * tmax));
+  pcf = std::max<long long>(1, std::min<long long>(pcf, pc));
+  int rc;
+  if ((rc = ensure(c, "resect.fit_slab", (size_t)B * pcf * tmax * SH_HF_WORDS * 8, 8)) || (rc = ensure(c, "resect.fit_moments", (size_t)B * P * 16 * 8, 8)) ||
+      (rc = ensure(c, "resect.fit_ring", (size_t)B * P * 8 * 8, 8)) || (rc = ensure(c, "resect.fit_out", (size_t)B * P * sizeof(sh_head_fit), 8)))
+    return rc;
+  for (const char* n : {"resect.fit_slab", "resect.fit_moments", "resect.fit_ring", "resect.fit_out"}) c->bufs[n].per_mesh = 0;
+  *pcf_out = (int)pcf;
+  return SH_OK;
+}
+
+// face pass + join of planes [p0, p0 + pc) of humeri [b0, b0 + nb); one: the record and ring of a single cut (sh_resect_ring);
+// fit: the moment pass beside the face pass and the join that adds its slab and the ring's second moments
+static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tmax, bool one, bool fit = false) {
   int* segcnt = (int*)c->bufs["resect.segcnt"].p;
   HIPCHK(c, hipMemsetAsync(segcnt, 0, (size_t)nb * pc * 4, c->stream));
   const float* verts = (const float*)c->bufs["verts"].p; const int* faces = (const int*)c->bufs["faces"].p;
@@ -823,6 +840,15 @@ static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tma
   const double* planes = (const double*)c->bufs["resect.planes"].p;
   LAUNCH(c, "k_resect_faces", k_resect_faces, dim3((unsigned)tmax, (unsigned)nb), dim3(SH_RS_TILE), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
          (ResectPart*)c->bufs["resect.slab"].p, segcnt, (int*)c->bufs["resect.segs"].p);
+  if (fit) {
+    LAUNCH(c, "k_headfit_faces", k_headfit_faces, dim3((unsigned)tmax, (unsigned)nb), dim3(SH_RS_TILE), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
+           (double*)c->bufs["resect.fit_slab"].p);
+    LAUNCH(c, "k_resect_join_fit", k_resect_join_fit, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
+           (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
+           (sh_resection*)c->bufs["resect.out"].p, (const double*)c->bufs["resect.fit_slab"].p, (double*)c->bufs["resect.fit_moments"].p,
+           (double*)c->bufs["resect.fit_ring"].p);
+    return SH_OK;
+  }
   LAUNCH(c, "k_resect_join", k_resect_join, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
          (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
          (sh_resection*)c->bufs["resect.out"].p, one ? (sh_resection*)c->bufs["resect.one"].p : (sh_resection*)nullptr,
@@ -830,55 +856,82 @@ static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tma
   return SH_OK;
 }
 
-static int resect_all(sh_ctx* c, int P, int pc, int tmax, sh_resection* out) {
+static bool resect_has_records(sh_ctx* c) {
+  const uint32_t need = SH_STAGE_ANP | SH_STAGE_CSYS;
+  return c->rec_gen == c->batch_gen && (c->rec_mask & need) == need && c->bufs.find("landmarks") != c->bufs.end();
+}
+
+static int resect_all(sh_ctx* c, int P, int pc, int tmax, sh_resection* out, sh_head_fit* fit_out) {
+  const size_t n = (size_t)c->B * P;
+  if (fit_out) {      // (a cut whose humerus' record failed writes neither: zeros)
+    HIPCHK(c, hipMemsetAsync(c->bufs["resect.fit_moments"].p, 0, n * 16 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->bufs["resect.fit_ring"].p, 0, n * 8 * 8, c->stream));
+  }
   for (int p0 = 0; p0 < P; p0 += pc)
-    if (int rc = resect_pass(c, P, p0, std::min(pc, P - p0), 0, c->B, tmax, false)) return rc;
-  HIPCHK(c, hipMemcpyAsync(out, c->bufs["resect.out"].p, (size_t)c->B * P * sizeof(sh_resection), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = resect_pass(c, P, p0, std::min(pc, P - p0), 0, c->B, tmax, false, fit_out != nullptr)) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, c->bufs["resect.out"].p, n * sizeof(sh_resection), hipMemcpyDeviceToHost, c->stream));
+  if (fit_out) {
+    LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((n + 63) / 64)), dim3(64), (const sh_resection*)c->bufs["resect.out"].p,
+           (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p, (const double*)c->bufs["resect.fit_ring"].p,
+           resect_has_records(c) ? (const sh_landmarks*)c->bufs["landmarks"].p : (const sh_landmarks*)nullptr, P, (int)n, (sh_head_fit*)c->bufs["resect.fit_out"].p);
+    HIPCHK(c, hipMemcpyAsync(fit_out, c->bufs["resect.fit_out"].p, n * sizeof(sh_head_fit), hipMemcpyDeviceToHost, c->stream));
+  }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->resect_P = P; c->resect_gen = c->batch_gen;
   return SH_OK;
 }
 
-int sh_resect_planes(sh_ctx* c, const double* planes, int P, sh_resection* out) {
-  if (!c || !planes || !out || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, "sh_resect_planes: bad argument (P in 1..4096)");
-  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_resect_planes: no meshes uploaded");
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_planes: runs are in flight (sh_collect them first)");
+static int resect_planes_impl(sh_ctx* c, const char* fn, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out, bool fit) {
+  const std::string f(fn);
+  if (!c || !planes || !out || (fit && !fit_out) || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
   const size_t n = (size_t)c->B * P;
   for (size_t i = 0; i < n; ++i) {
     const double* q = planes + 6 * i;
     bool fin = true;
     for (int k = 0; k < 6; ++k) fin = fin && std::isfinite(q[k]);
-    if (!fin || !((q[3] * q[3] + q[4] * q[4]) + q[5] * q[5] > 0.0)) return fail(c, SH_ERR_ARG, "sh_resect_planes: zero normal or non-finite plane");
+    if (!fin || !((q[3] * q[3] + q[4] * q[4]) + q[5] * q[5] > 0.0)) return fail(c, SH_ERR_ARG, f + ": zero normal or non-finite plane");
   }
-  HIPCHK(c, hipSetDevice(c->device));
-  int pc, tmax;
-  if (int rc = resect_buffers(c, P, &pc, &tmax)) return rc;
-  c->resect_gen = ~0ull;
-  HIPCHK(c, hipMemcpyAsync(c->bufs["resect.planes"].p, planes, n * 48, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->bufs["resect.status"].p, 0, n * 4, c->stream));
-  return resect_all(c, P, pc, tmax, out);
-}
-
-int sh_resect_offsets(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out) {
-  if (!c || !offs || !out || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, "sh_resect_offsets: bad argument (P in 1..4096)");
-  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_resect_offsets: no meshes uploaded");
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_offsets: runs are in flight (sh_collect them first)");
-  const uint32_t need = SH_STAGE_ANP | SH_STAGE_CSYS;
-  if (c->rec_gen != c->batch_gen || (c->rec_mask & need) != need || c->bufs.find("landmarks") == c->bufs.end())
-    return fail(c, SH_ERR_STATE, "sh_resect_offsets: needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
-  static_assert(sizeof(sh_cut_offset) == 7 * sizeof(double), "sh_cut_offset is seven doubles");
-  for (int i = 0; i < 7 * P; ++i)
-    if (!std::isfinite(((const double*)offs)[i])) return fail(c, SH_ERR_ARG, "sh_resect_offsets: non-finite offset");
   HIPCHK(c, hipSetDevice(c->device));
   int pc, tmax, rc;
   if ((rc = resect_buffers(c, P, &pc, &tmax))) return rc;
+  if (fit && (rc = headfit_buffers(c, P, pc, tmax, &pc))) return rc;
+  c->resect_gen = ~0ull;
+  HIPCHK(c, hipMemcpyAsync(c->bufs["resect.planes"].p, planes, n * 48, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->bufs["resect.status"].p, 0, n * 4, c->stream));
+  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr);
+}
+
+static int resect_offsets_impl(sh_ctx* c, const char* fn, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out, bool fit) {
+  const std::string f(fn);
+  if (!c || !offs || !out || (fit && !fit_out) || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
+  if (!resect_has_records(c)) return fail(c, SH_ERR_STATE, f + ": needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
+  static_assert(sizeof(sh_cut_offset) == 7 * sizeof(double), "sh_cut_offset is seven doubles");
+  for (int i = 0; i < 7 * P; ++i)
+    if (!std::isfinite(((const double*)offs)[i])) return fail(c, SH_ERR_ARG, f + ": non-finite offset");
+  HIPCHK(c, hipSetDevice(c->device));
+  int pc, tmax, rc;
+  if ((rc = resect_buffers(c, P, &pc, &tmax))) return rc;
+  if (fit && (rc = headfit_buffers(c, P, pc, tmax, &pc))) return rc;
   if ((rc = ensure(c, "resect.offs", (size_t)P * 56, 8))) return rc;
   c->bufs["resect.offs"].per_mesh = 0;
   c->resect_gen = ~0ull;
   HIPCHK(c, hipMemcpyAsync(c->bufs["resect.offs"].p, offs, (size_t)P * 56, hipMemcpyHostToDevice, c->stream));
   LAUNCH(c, "k_resect_make_planes", k_resect_make_planes, dim3((unsigned)c->B), dim3(64), (const sh_landmarks*)c->bufs["landmarks"].p,
          (const double*)c->bufs["resect.offs"].p, P, (double*)c->bufs["resect.planes"].p, (int*)c->bufs["resect.status"].p);
-  return resect_all(c, P, pc, tmax, out);
+  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr);
+}
+
+int sh_resect_planes(sh_ctx* c, const double* planes, int P, sh_resection* out) { return resect_planes_impl(c, "sh_resect_planes", planes, P, out, nullptr, false); }
+int sh_resect_offsets(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out) { return resect_offsets_impl(c, "sh_resect_offsets", offs, P, out, nullptr, false); }
+int sh_resect_planes_fit(sh_ctx* c, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out) {
+  return resect_planes_impl(c, "sh_resect_planes_fit", planes, P, out, fit_out, true);
+}
+int sh_resect_offsets_fit(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out) {
+  return resect_offsets_impl(c, "sh_resect_offsets_fit", offs, P, out, fit_out, true);
 }
 
 int sh_resect_ring(sh_ctx* c, int b, int p, double* out, int cap, int* n_out) {

@@ -434,12 +434,14 @@ class Engine:
         return out
 
     # ---- batched head resection (include/shoulder_hip.h sh_resect_*) -------------------------------------------------
-    def resect(self, planes=None, offsets=None):
+    def resect(self, planes=None, offsets=None, fit=False):
         """B resident humeri x P resection planes in one device pass -> structured array (B, P) of _lib.RESECTION_DTYPE.
         planes: (B, P, 6) or (B, P, 2, 3) float64, (point, normal) in CT per humerus (sh_resect_planes; needs no run).
         offsets: P cuts relative to every humerus' own anatomic-neck plane -- a list of dicts or a structured array with the
         sh_cut_offset field names (_lib.CUT_OFFSET_DTYPE; missing keys are 0) -- planes built on the device from the records of
-        the last run (sh_resect_offsets; needs a run with STAGE_ANP and STAGE_CSYS).  A cut's `status` tells its own failure."""
+        the last run (sh_resect_offsets; needs a run with STAGE_ANP and STAGE_CSYS).  A cut's `status` tells its own failure.
+        fit=True: -> (records, fits), fits a structured array (B, P) of _lib.HEAD_FIT_DTYPE -- the sphere of every cut's head piece and
+        the ellipse of its cut (sh_resect_*_fit; the records are the same bytes)."""
         if (planes is None) == (offsets is None):
             raise ValueError("resect() takes planes or offsets")
         B = self.B
@@ -449,6 +451,10 @@ class Engine:
                 raise ValueError("planes must have shape (B, P, 6)")
             P = pl.size // (6 * B)
             out = np.zeros((B, P), dtype=_lib.RESECTION_DTYPE)
+            if fit:
+                fits = np.zeros((B, P), dtype=_lib.HEAD_FIT_DTYPE)
+                self._chk(self.L.sh_resect_planes_fit(self.h, _ptr(pl), P, _ptr(out), _ptr(fits)))
+                return out, fits
             self._chk(self.L.sh_resect_planes(self.h, _ptr(pl), P, _ptr(out)))
             return out
         if isinstance(offsets, np.ndarray) and offsets.dtype.names:
@@ -464,6 +470,10 @@ class Engine:
         if len(off) == 0:
             raise ValueError("at least one offset")
         out = np.zeros((B, len(off)), dtype=_lib.RESECTION_DTYPE)
+        if fit:
+            fits = np.zeros((B, len(off)), dtype=_lib.HEAD_FIT_DTYPE)
+            self._chk(self.L.sh_resect_offsets_fit(self.h, _ptr(off), len(off), _ptr(out), _ptr(fits)))
+            return out, fits
         self._chk(self.L.sh_resect_offsets(self.h, _ptr(off), len(off), _ptr(out)))
         return out
 

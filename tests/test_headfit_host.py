@@ -1,0 +1,148 @@
+"""Head fit of a cut (include/shoulder_hip.h sh_head_fit), the parts that need no GPU: record layout, the two solves the device
+runs (sh_scalar.h head_sphere_from_moments / ellipse_from_moments, host-compiled with -ffp-contract=off) against the lstsq / eigh
+oracle of tests/headfit_oracle.py, the degenerate-fit flag, and the arithmetic of implant_head.
+
+Bound for centre, radius, rms and semi-axes against the oracle: 1e-6 mm, the level the project's landmarks agree with their oracle
+at (README); the two CPU routes differ by ~3e-13 mm on the fixtures (condition number of the normal matrix 3 200 .. 5 000)."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import headfit_oracle as H
+from conftest import BONES, ROOT
+from shoulder_amd import _lib
+from shoulder_amd.arthroplasty import implant_from_fit
+from shoulder_amd.stl import load_stl
+
+MM = 1e-6
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return H.build_shim(tmp_path_factory.mktemp("headfit_check"))
+
+
+def test_head_fit_record_layout_matches_header(tmp_path):
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(sh_head_fit), offsetof(sh_head_fit, sphere_radius), '
+                   'offsetof(sh_head_fit, center_articular), offsetof(sh_head_fit, cut_major_dir), offsetof(sh_head_fit, sphere_status), '
+                   'offsetof(sh_head_fit, ring_status)); return 0; }\n')
+    exe = tmp_path / "probe"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
+    dt, R = _lib.HEAD_FIT_DTYPE, _lib.HeadFit
+    assert got[0] == dt.itemsize == ctypes.sizeof(R) == 128
+    for g, name in zip(got[1:], ("sphere_radius", "center_articular", "cut_major_dir", "sphere_status", "ring_status")):
+        assert g == dt.fields[name][1] == getattr(R, name).offset
+    assert [n for n, _ in R._fields_] == list(dt.names)
+
+
+def test_fit_entry_points_check_their_arguments_without_a_gpu():
+    L = _lib.load()
+    buf = np.zeros(64)
+    ptr = ctypes.c_void_p(buf.ctypes.data)
+    for P in (1, 0, -1, 4097):
+        assert L.sh_resect_planes_fit(None, ptr, P, ptr, ptr) == -1
+        assert L.sh_resect_offsets_fit(None, ptr, P, ptr, ptr) == -1
+    assert "sh_resect_planes_fit" in _lib.EXPORTS and "sh_resect_offsets_fit" in _lib.EXPORTS
+
+
+@pytest.fixture(scope="module")
+def humerus_cuts():
+    """humerus_left cut by four planes across its head end (normal along the first principal axis, towards the head or away)"""
+    v, f = load_stl(os.path.join(BONES, "humerus_left.stl"))
+    v64 = np.asarray(v, np.float32).astype(np.float64)
+    f = np.asarray(f, np.int32)
+    ctr = v64.mean(axis=0)
+    ax = np.linalg.svd(v64 - ctr, full_matrices=False)[2][0]
+    s = (v64 - ctr) @ ax
+    cuts = []
+    for frac, sign, tilt in ((0.88, 1.0, (0.0, 0.0, 0.0)), (0.80, 1.0, (0.2, -0.1, 0.0)), (0.12, -1.0, (0.0, 0.0, 0.0)), (0.2, -1.0, (-0.1, 0.15, 0.05))):
+        o = ctr + ax * (s.min() + frac * (s.max() - s.min()))
+        n = sign * ax + np.array(tilt)
+        cuts.append((o, n, H.OracleFit(v64, f, o, n)))
+    return v64, f, cuts
+
+
+def test_sphere_from_moments_against_lstsq_on_a_humerus(shim, humerus_cuts):
+    for o, n, O in humerus_cuts[2]:
+        assert len(O.q) > 3000
+        rc, c, r, rms = H.host_sphere(shim, O.moments)
+        assert rc == 0
+        print("centre", np.abs(o + c - O.center).max(), "radius", abs(r - O.radius), "rms", rms, O.rms)
+        assert np.abs(o + c - O.center).max() <= MM and abs(r - O.radius) <= MM and abs(rms - O.rms) <= MM
+        rc, a, b, d = H.host_ellipse(shim, H.ring_sums(O.ring, o, n))
+        assert rc == 0 and abs(a - O.ellipse[0]) <= MM and abs(b - O.ellipse[1]) <= MM
+        u, w = H.basis(n)
+        d3 = d[0] * u + d[1] * w
+        assert min(np.abs(d3 - O.ellipse[2]).max(), np.abs(d3 + O.ellipse[2]).max()) <= 1e-6
+
+
+def test_translation_invariance_of_the_shifted_solve(shim, humerus_cuts):
+    """the same samples with o moved 300 mm along the plane: the same sphere in CT"""
+    v64, f, cuts = humerus_cuts
+    o, n, O = cuts[0]
+    u, w = H.basis(n)
+    o2 = o + 300.0 * u
+    O2 = H.OracleFit(v64, f, o2, n)
+    assert len(O2.q) == len(O.q)
+    rc, c, r, rms = H.host_sphere(shim, O.moments)
+    rc2, c2, r2, rms2 = H.host_sphere(shim, O2.moments)
+    assert rc == 0 and rc2 == 0
+    assert np.abs((o2 + c2) - (o + c)).max() <= MM and abs(r2 - r) <= MM and abs(rms2 - rms) <= MM
+
+
+def test_exact_cases(shim):
+    # samples on a sphere: centre, radius, zero rms
+    rng = np.random.default_rng(5)
+    p = rng.normal(size=(400, 3))
+    p = p[p[:, 2] > -0.3]
+    ctr, R = np.array([3.0, -2.0, 7.0]), 23.5
+    q = ctr + R * p / np.linalg.norm(p, axis=1)[:, None]
+    w = rng.uniform(0.5, 2.0, len(q))
+    rc, c, r, rms = H.host_sphere(shim, H.moments16(q, w))
+    assert rc == 0 and np.abs(c - ctr).max() <= 1e-10 and abs(r - R) <= 1e-10 and rms <= 1e-6
+    # the unit square about one of its corners: both semi-axes 2 sqrt(1/12)
+    sq = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0], [0, 0, 0]], dtype=np.float64)
+    rc, a, b, d = H.host_ellipse(shim, H.ring_sums(sq, np.zeros(3), np.array([0.0, 0.0, 1.0])))
+    assert rc == 0 and abs(a - 2 * np.sqrt(1 / 12)) <= 1e-15 and abs(b - 2 * np.sqrt(1 / 12)) <= 1e-15
+    # a regular 64-gon stretched 3 : 2 along a direction 30 degrees from u, about a far origin: axis ratio and direction
+    t = np.arange(65) * (2 * np.pi / 64)
+    n = np.array([0.0, 0.0, 1.0])
+    u, w = H.basis(n)
+    e1, e2 = np.cos(np.pi / 6) * u + np.sin(np.pi / 6) * w, -np.sin(np.pi / 6) * u + np.cos(np.pi / 6) * w
+    ring = np.array([40.0, 25.0, 0.0]) + 30.0 * np.cos(t)[:, None] * e1 + 20.0 * np.sin(t)[:, None] * e2
+    rc, a, b, d = H.host_ellipse(shim, H.ring_sums(ring, np.zeros(3), n))
+    assert rc == 0
+    assert abs(a / b - 1.5) <= 1e-12
+    d3 = d[0] * u + d[1] * w
+    assert min(np.abs(d3 - e1).max(), np.abs(d3 + e1).max()) <= 1e-12
+    assert H.host_ellipse(shim, np.zeros(6))[0] == -5
+
+
+def test_a_coplanar_sheet_is_flagged(shim):
+    rng = np.random.default_rng(2)
+    q = np.c_[rng.uniform(-20, 20, (200, 2)), np.zeros(200)] @ np.linalg.qr(rng.normal(size=(3, 3)))[0].T + np.array([5.0, 1.0, -3.0])
+    rc, c, r, rms = H.host_sphere(shim, H.moments16(q, np.ones(200)))
+    assert rc == -5 and r == 0.0 and rms == 0.0 and not c.any()
+    assert H.host_sphere(shim, np.zeros(16))[0] == -5                                 # (no weight: the caller reports the empty piece itself)
+
+
+def test_implant_head_arithmetic_and_catalogue():
+    fit = np.zeros((), dtype=_lib.HEAD_FIT_DTYPE)
+    fit["sphere_center"], fit["sphere_radius"], fit["cap_height"] = [1.0, 2.0, 3.0], 24.0, 18.5
+    fit["center_articular"], fit["cut_semi_major"], fit["cut_semi_minor"] = [2.5, -4.0, 30.0], 23.0, 21.0
+    cat = [(44.0, 15.0), (48.0, 18.0), (48.0, 21.0), (52.0, 18.0)]
+    r = implant_from_fit(fit, "right", cat)
+    assert r["radius"] == 24.0 and r["thickness"] == 18.5 and r["base_diameters"] == (46.0, 42.0)
+    assert r["medial_offset"] == 4.0 and r["posterior_offset"] == -2.5 and np.array_equal(r["center"], [1.0, 2.0, 3.0])
+    assert r["catalogue_index"] == 1
+    left = implant_from_fit(fit, "left")
+    assert left["posterior_offset"] == 2.5 and left["medial_offset"] == 4.0 and "catalogue_index" not in left
+    fit["sphere_status"] = -5
+    with pytest.raises(ValueError):
+        implant_from_fit(fit, "left")
