@@ -391,6 +391,69 @@ typedef struct sh_head_fit {
 int sh_resect_planes_fit (sh_ctx*, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out);
 int sh_resect_offsets_fit(sh_ctx*, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out);
 
+/* ---- seating a catalogue of implant heads on every cut -----------------------------------------------------------------------
+ * How each head of a catalogue sits on each cut of a fitted resection, computed on the device in the same pass (k_seat.h): the
+ * ring of a cut never goes to the host.
+ *
+ * An implant head k is (R_k, h_k): radius of curvature and thickness, valid for 0 < h_k < 2 R_k.  Its base is a disk of radius
+ * rho_k = sqrt(h_k (2 R_k - h_k)).  Geometry is taken in the cut's in-plane basis (u, w) of base.Section about o = plane_point,
+ * exactly as cut_area / cut_centroid are (see sh_resection); the polygon is the LARGEST loop, the one cut_area describes, in
+ * sh_resect_ring's order (counter-clockwise seen from the tip of the normal, canonical start); n^ = n / |n|.
+ *   seat centre s   SH_SEAT_CUT_CENTROID: the cut's area centroid (cut_centroid).  SH_SEAT_SPHERE_AXIS: the fitted sphere's centre
+ *                   projected onto the plane; a cut whose sphere_status != 0 gets that status in its seats (a ring over an empty
+ *                   head piece, which has no sphere: SH_ERR_GEOMETRY).  seat_center = o + s_u u + s_w w with (s_u, s_w) the
+ *                   in-plane coordinates of that point about o.
+ *   covered_area    area(polygon n disk), exact, edge by edge by Green's theorem about s: for the directed edge p -> q with a = p - s,
+ *                   d = q - p solve |a + t d|^2 = rho^2; with a positive discriminant and roots t_lo < t_hi the part of [0, 1] inside
+ *                   [t_lo, t_hi] is the chord piece and contributes cross(x, y) / 2 (x, y the piece's ends about s); every other
+ *                   piece contributes the sector rho^2 atan2(cross(x, y), dot(x, y)) / 2, and so does the whole edge when the
+ *                   discriminant is <= 0 (a tangent edge counts as outside).  Pieces are classified by the roots, never by testing
+ *                   a midpoint.  |sum over the ring|.  (sh_scalar.h seat_edge_term.)
+ *   coverage = covered_area / cut_area (0 for a loop without area), overhang_area = pi rho^2 - covered_area (disk beyond the bone),
+ *   uncovered_area = cut_area - covered_area (bone beyond the disk).
+ *   rim_min         the smallest point-to-segment distance from s to the ring, the first segment in ring order winning a tie;
+ *   rim_max         the largest vertex distance from s (the distance is convex along a segment), the first vertex winning a tie;
+ *                   max_overhang = max(0, rho - rim_min), max_uncovered = max(0, rim_max - rho); overhang_dir / uncovered_dir: unit
+ *                   CT vectors from s to that nearest point / farthest vertex (zero when s lies on it).  These are RADIAL measures
+ *                   about s -- how far the disk's rim lies from the ring along rays from s -- NOT Hausdorff distances between
+ *                   the two outlines.
+ *   center_inside   1 when the winding number of s in the ring is non-zero, else 0.
+ *   implant_center = s + (h - R) n^ (CT): the centre of the implant's sphere when its base lies in the plane, the dome on the
+ *                   normal's side.  cor_shift = implant_center - sphere_center (CT; zero when the cut has no sphere);
+ *                   cor_shift_articular = that vector rotated by csys_articular (rotation part), NaN exactly where
+ *                   sh_head_fit.center_articular is.
+ *   surface_rms     sqrt(sum w (|p - c|^2 - R^2)^2 / S0) / (2 R) over the head piece's samples (see sh_head_fit) against the implant
+ *                   sphere (c = implant_center, R): the first-order radial rms, sphere_rms' formula, evaluated from the sixteen
+ *                   moments only and about their weighted centroid (sh_scalar.h seat_surface_rms); 0 for an empty piece.
+ *   status          the cut's ring status (sh_resection.status), the humerus' failed record, or in SH_SEAT_SPHERE_AXIS mode the
+ *                   sphere's status.  ALL other fields are zero when it is non-zero, and also for a cut without a loop (status 0).
+ *                   A bad seat never fails the batch.
+ * A seat record depends on its cut and its head alone: not on B, P, K, the humerus' position in the batch or the head's in the
+ * catalogue (sums are taken lane-strided in ring order and reduced by one fixed tree; no floating-point atomics). */
+#define SH_SEAT_CUT_CENTROID 0
+#define SH_SEAT_SPHERE_AXIS 1
+#define SH_SEAT_MAX_HEADS 64
+typedef struct sh_implant_head { double radius, thickness; } sh_implant_head;
+typedef struct sh_seat {
+  double base_radius, seat_center[3];
+  double covered_area, coverage, overhang_area, uncovered_area;
+  double rim_min, rim_max, max_overhang, max_uncovered;
+  double overhang_dir[3], uncovered_dir[3];
+  double implant_center[3], cor_shift[3], cor_shift_articular[3];
+  double surface_rms;
+  int32_t center_inside, status;
+} sh_seat;
+/* sh_resect_planes_fit / sh_resect_offsets_fit with K heads seated on every cut: same preconditions, argument checks and state
+ * errors; `out` and `fit_out` are byte-equal to what the _fit calls write.  seat_out: B x P x K, host.  SH_ERR_ARG for K outside
+ * 1..SH_SEAT_MAX_HEADS, a head that is not valid (non-finite, or thickness outside (0, 2 radius)) or a center_mode other than
+ * the two above.  The passes of a sweep are the fitted calls' (4 096 / B planes, at least one; the ring coordinates of a pass take
+ * 16 KB per cut: 64 MB for B <= 4 096, 16 KB per humerus beyond); the pass a cut falls into does not change its records.  The
+ * B x P x K records (232 B each) are held on the device as well and are not limited: SH_ERR_NOMEM when they do not fit. */
+int sh_resect_planes_seat (sh_ctx*, const double* planes, int P, const sh_implant_head* heads, int K, int center_mode,
+                           sh_resection* out, sh_head_fit* fit_out, sh_seat* seat_out /* B x P x K */);
+int sh_resect_offsets_seat(sh_ctx*, const sh_cut_offset* offs, int P, const sh_implant_head* heads, int K, int center_mode,
+                           sh_resection* out, sh_head_fit* fit_out, sh_seat* seat_out /* B x P x K */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

@@ -110,6 +110,33 @@ HEAD_FIT_DTYPE = np.dtype([
 assert HEAD_FIT_DTYPE.itemsize == ctypes.sizeof(HeadFit)
 
 
+class ImplantHead(ctypes.Structure):
+    """sh_implant_head: radius of curvature and thickness of one catalogue head."""
+    _fields_ = [("radius", ctypes.c_double), ("thickness", ctypes.c_double)]
+
+
+IMPLANT_HEAD_DTYPE = np.dtype([("radius", "<f8"), ("thickness", "<f8")])
+SEAT_CUT_CENTROID, SEAT_SPHERE_AXIS, SEAT_MAX_HEADS = 0, 1, 64
+
+
+class Seat(ctypes.Structure):
+    """sh_seat: how one implant head sits on one (humerus, plane) cut."""
+    _fields_ = [("base_radius", ctypes.c_double), ("seat_center", ctypes.c_double * 3), ("covered_area", ctypes.c_double),
+                ("coverage", ctypes.c_double), ("overhang_area", ctypes.c_double), ("uncovered_area", ctypes.c_double),
+                ("rim_min", ctypes.c_double), ("rim_max", ctypes.c_double), ("max_overhang", ctypes.c_double),
+                ("max_uncovered", ctypes.c_double), ("overhang_dir", ctypes.c_double * 3), ("uncovered_dir", ctypes.c_double * 3),
+                ("implant_center", ctypes.c_double * 3), ("cor_shift", ctypes.c_double * 3), ("cor_shift_articular", ctypes.c_double * 3),
+                ("surface_rms", ctypes.c_double), ("center_inside", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+SEAT_DTYPE = np.dtype([
+    ("base_radius", "<f8"), ("seat_center", "<f8", (3,)), ("covered_area", "<f8"), ("coverage", "<f8"), ("overhang_area", "<f8"),
+    ("uncovered_area", "<f8"), ("rim_min", "<f8"), ("rim_max", "<f8"), ("max_overhang", "<f8"), ("max_uncovered", "<f8"),
+    ("overhang_dir", "<f8", (3,)), ("uncovered_dir", "<f8", (3,)), ("implant_center", "<f8", (3,)), ("cor_shift", "<f8", (3,)),
+    ("cor_shift_articular", "<f8", (3,)), ("surface_rms", "<f8"), ("center_inside", "<i4"), ("status", "<i4")])
+assert SEAT_DTYPE.itemsize == ctypes.sizeof(Seat) and IMPLANT_HEAD_DTYPE.itemsize == ctypes.sizeof(ImplantHead)
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -123,7 +150,8 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_comm_init_all", "sh_bcast_weights", "sh_gather_landmarks", "sh_set_keep_products",
            "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring",
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
-           "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit"]
+           "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
+           "sh_resect_planes_seat", "sh_resect_offsets_seat"]
 
 _lib = None
 
@@ -217,5 +245,8 @@ def load(build_if_missing=True):
     if not alt or hasattr(L, "sh_resect_planes_fit"):      # (tools/time_head_fit.py parent)
         L.sh_resect_planes_fit.argtypes = [vp, vp, ctypes.c_int, vp, vp]
         L.sh_resect_offsets_fit.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    if not alt or hasattr(L, "sh_resect_planes_seat"):      # (tools/time_seat.py parent)
+        L.sh_resect_planes_seat.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+        L.sh_resect_offsets_seat.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
     _lib = L
     return L

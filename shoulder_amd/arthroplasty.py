@@ -120,6 +120,18 @@ class HumeralHeadOsteotomy:
         """The planned spherical cap for the current cut, from `head_fit()` (the step the reference leaves open, arthroplasty.py:178-182)."""
         return implant_from_fit(self.head_fit(), self._humerus.side(), catalogue)
 
+    def seat(self, catalogue, center="centroid") -> list:
+        """How each head of `catalogue` -- (diameter, thickness) pairs, as `implant_from_fit` takes them -- sits on the current cut
+        (sh_resect_planes_seat with B = P = 1): K dicts with the fields of sh_seat, in CT.  center: "centroid" (the cut's area
+        centroid) or "sphere" (the foot of the fitted sphere's centre)."""
+        cat = np.asarray(catalogue, dtype=np.float64).reshape(-1, 2)
+        p, n = self._plane_ct()
+        bone = self._humerus
+        bone._ensure_loaded()
+        heads = np.c_[0.5 * cat[:, 0], cat[:, 1]]
+        seats = bone._engine.resect(planes=np.concatenate([p, n]).reshape(1, 1, 6), fit=True, heads=heads, seat_center=center)[2][0, 0]
+        return [{k: (s[k].copy() if s[k].ndim else s[k].item()) for k in s.dtype.names} for s in seats]
+
     # ---- offsets (arthroplasty.py:89-175) ------------------------------------------------------------------
     def offset_retroversion(self, deg: float) -> None:
         """more retroversion for positive `deg` (the azimuth decreases on a left humerus, increases on a right one)"""
@@ -163,3 +175,14 @@ def implant_from_fit(fit, side, catalogue=None) -> dict:
         d = (cat[:, 0] - 2.0 * out["radius"]) ** 2 + (cat[:, 1] - out["thickness"]) ** 2
         out["catalogue_index"] = int(np.argmin(d))
     return out
+
+
+def best_seat(seats, max_overhang_mm):
+    """Index of the seat with the largest `coverage` among those with `status` == 0 and `max_overhang` <= max_overhang_mm (the first
+    of equals), or None.  seats: a 1-D structured array of _lib.SEAT_DTYPE or a list of dicts with its fields.  Pure NumPy."""
+    if isinstance(seats, np.ndarray) and seats.dtype.names:
+        st, ov, cov = seats["status"].reshape(-1), seats["max_overhang"].reshape(-1), seats["coverage"].reshape(-1)
+    else:
+        st, ov, cov = (np.array([s[k] for s in seats]) for k in ("status", "max_overhang", "coverage"))
+    ok = np.nonzero((st == 0) & (ov <= max_overhang_mm))[0]
+    return int(ok[np.argmax(cov[ok])]) if len(ok) else None

@@ -10,8 +10,9 @@
 //                     14 x 6 -- a fixed tree; the four waves are added in order and the slab entry of (humerus, plane, tile) is
 //                     STORED.  No floating-point atomics.
 //   k_resect_join_fit (k_resect.h) adds a cut's slab in tile order and the largest loop's second-moment shoelace sums in ring order.
-//   k_headfit_solve   one lane per cut: sh_scalar.h head_sphere_from_moments / ellipse_from_moments (the source the host check
-//                     instantiates), cap height, the centre in the humerus' canal / articular frame, the record.
+//   k_headfit_solve   one lane per cut (of the batch, or of one pass when k_seat.h follows pass by pass): sh_scalar.h
+//                     head_sphere_from_moments / ellipse_from_moments (the source the host check instantiates), cap height, the
+//                     centre in the humerus' canal / articular frame, the record.
 #pragma once
 #include "k_resect.h"
 #include "sh_scalar.h"
@@ -113,13 +114,15 @@ k_headfit_faces(const float* __restrict__ verts, const int* __restrict__ faces, 
   }
 }
 
-// one lane per cut of the batch: the record from the cut's moments, its ring sums and its sh_resection
+// one lane per cut of planes [p0, p0 + pc) of every humerus (n = B x pc lanes; p0 = 0, pc = P: the batch): the record from the cut's
+// moments, its ring sums and its sh_resection
 __global__ void k_headfit_solve(const sh_resection* __restrict__ recs /* B x P */, const int* __restrict__ cut_status /* B x P */,
                                 const double* __restrict__ moments /* B x P x 16 */, const double* __restrict__ ringm /* B x P x 8 */,
-                                const sh_landmarks* __restrict__ lm /* nullable: no run with the anatomic neck and the csys */, int P, int n,
-                                sh_head_fit* __restrict__ out /* B x P */) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+                                const sh_landmarks* __restrict__ lm /* nullable: no run with the anatomic neck and the csys */, int P, int p0, int pc,
+                                int n, sh_head_fit* __restrict__ out /* B x P */) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int i = (j / pc) * P + p0 + j % pc;
   sh_head_fit r;
   memset(&r, 0, sizeof r);
   const int st0 = cut_status[i];
@@ -151,12 +154,8 @@ __global__ void k_headfit_solve(const sh_resection* __restrict__ recs /* B x P *
   if (rec.status == 0 && rec.n_loops > 0) {
     double dir[2];
     if (ellipse_from_moments(ringm + (size_t)i * 8, &r.cut_semi_major, &r.cut_semi_minor, dir)) {
-      double u[3], w[3];      // base.Section's in-plane basis, as k_resect_join builds it
-      const double ex[3] = {1.0, 0.0, 0.0}, ey[3] = {0.0, 1.0, 0.0};
-      cross3(un, fabs(un[0]) < 0.9 ? ex : ey, u);
-      const double ul = norm3(u);
-      u[0] /= ul; u[1] /= ul; u[2] /= ul;
-      cross3(un, u, w);
+      double u[3], w[3];
+      resect_basis(un, u, w);
       double dd[3];
       for (int k = 0; k < 3; ++k) dd[k] = dir[0] * u[k] + dir[1] * w[k];
       const double lead = dd[0] != 0.0 ? dd[0] : (dd[1] != 0.0 ? dd[1] : dd[2]);

@@ -199,8 +199,19 @@ __device__ inline void resect_point(const double* V, const int* id, int j, unsig
   } else clip_cross(V, j, pl, out);
 }
 
+// base.Section's in-plane basis for the unit normal un (see sh_resection): u = un x e_x, or un x e_y when |un_x| >= 0.9, normalised;
+// w = un x u.  The one statement of it: the join's areas, the ring coordinates it stores, k_headfit_solve and k_seat all use this.
+__device__ inline void resect_basis(const double* un, double* u, double* w) {
+  const double ex[3] = {1.0, 0.0, 0.0}, ey[3] = {0.0, 1.0, 0.0};
+  cross3(un, fabs(un[0]) < 0.9 ? ex : ey, u);
+  const double ul = norm3(u);
+  u[0] /= ul; u[1] /= ul; u[2] /= ul;
+  cross3(un, u, w);
+}
+
 #define SH_RJ_NAME k_resect_join
 #define SH_RJ_FIT 0
+#define SH_RJ_SEAT 0
 #include "k_resect_join.h"
 #undef SH_RJ_NAME
 #undef SH_RJ_FIT
@@ -208,6 +219,12 @@ __device__ inline void resect_point(const double* V, const int* id, int j, unsig
 #define SH_RJ_FIT 1
 #include "k_resect_join.h"
 #undef SH_RJ_NAME
+#undef SH_RJ_SEAT
+#define SH_RJ_NAME k_resect_join_seat
+#define SH_RJ_SEAT 1
+#include "k_resect_join.h"
+#undef SH_RJ_NAME
 #undef SH_RJ_FIT
+#undef SH_RJ_SEAT
 
 }  // namespace sh

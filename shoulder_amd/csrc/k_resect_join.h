@@ -1,15 +1,23 @@
-// k_resect_join.h -- the body of k_resect_join (k_resect.h), included once per mode: SH_RJ_NAME the kernel's name, SH_RJ_FIT 0 / 1.
+// k_resect_join.h -- the body of k_resect_join (k_resect.h), included once per mode: SH_RJ_NAME the kernel's name, SH_RJ_FIT 0 / 1,
+// SH_RJ_SEAT 0 / 1 (only with SH_RJ_FIT).
 // SH_RJ_FIT = 1 (k_resect_join_fit, the head fit of k_headfit.h): the cut's moment slab is added in tile order as well
 // ("resect.fit_moments"), and the largest loop's loop carries the three second-moment shoelace sums beside the area's ("resect.fit_ring":
 // sum cr, the two centroid sums, then sum cr (x0^2 + x0 x1 + x1^2), the same in y, sum cr (x0 y1 + 2 x0 y0 + 2 x1 y1 + x1 y0)), same tree.
-// SH_RJ_FIT = 0 is k_resect_join as it was: the preprocessor leaves the other mode's statements out.  (No include guard.)
+// SH_RJ_SEAT = 1 (k_resect_join_seat, the seats of k_seat.h): the fitted join that also stores the largest loop's in-plane coordinates
+// about the plane point -- the (x0, y0) its shoelace terms are made of -- in sh_resect_ring's order to the pass' ring buffer
+// ("resect.seat_ring": per cut of the pass SH_MAXSEG u's, then SH_MAXSEG w's; n_ring of the record tells how many).
+// SH_RJ_FIT = 0 is k_resect_join as it was: the preprocessor leaves the other modes' statements out.  (No include guard.)
 __global__ void __launch_bounds__(SH_RS_JOIN_THREADS)
 SH_RJ_NAME(const float* __restrict__ verts, const int* __restrict__ faces, const long long* __restrict__ voff, const long long* __restrict__ foff,
               const double* __restrict__ planes, int P, int p0, int pc, int b0, int tstride, const int* __restrict__ cut_status /* B x P */,
               const ResectPart* __restrict__ slab, const int* __restrict__ seg_count, const int* __restrict__ segs,
 #if SH_RJ_FIT
               sh_resection* __restrict__ out /* B x P */, const double* __restrict__ fit_slab /* [grid][tstride][16] */,
-              double* __restrict__ fit_moments /* B x P x 16 */, double* __restrict__ fit_ring /* B x P x 8 */) {
+              double* __restrict__ fit_moments /* B x P x 16 */, double* __restrict__ fit_ring /* B x P x 8 */
+#if SH_RJ_SEAT
+              , double* __restrict__ ring_uw /* [cuts of the pass][2][SH_MAXSEG] */
+#endif
+              ) {
   sh_resection* const out_one = nullptr;
   double* const ring_out = nullptr;
 #else
@@ -74,15 +82,8 @@ SH_RJ_NAME(const float* __restrict__ verts, const int* __restrict__ faces, const
   const int n = seg_count[cut];
   __syncthreads();
   const double nlen = sqrt((pl[3] * pl[3] + pl[4] * pl[4]) + pl[5] * pl[5]);
-  // base.Section's in-plane basis
   double un[3] = {pl[3] / nlen, pl[4] / nlen, pl[5] / nlen}, u[3], w[3];
-  {
-    const double ex[3] = {1.0, 0.0, 0.0}, ey[3] = {0.0, 1.0, 0.0};
-    cross3(un, fabs(un[0]) < 0.9 ? ex : ey, u);
-    const double ul = norm3(u);
-    u[0] /= ul; u[1] /= ul; u[2] /= ul;
-    cross3(un, u, w);
-  }
+  resect_basis(un, u, w);
   int status = 0, nl = 0, best = 0;
   const float* vb = verts + 3 * voff[b];
   const int* fb = faces + 3 * f0;
@@ -283,6 +284,19 @@ SH_RJ_NAME(const float* __restrict__ verts, const int* __restrict__ faces, const
     }
     *rec = r;
   }
+#if SH_RJ_SEAT
+  if (nl > 0) {
+    const double* rx = (const double*)bufA; const double* ry = (const double*)bufB; const double* rz = (const double*)skey;
+    const int o = l_off[best], L = l_len[best];
+    const bool rev = l_area[best] < 0;
+    double* dst = ring_uw + (size_t)cut * 2 * SH_MAXSEG;
+    for (int k = tid; k < L; k += T) {
+      const int src = rev ? (k == 0 ? 0 : L - k) : k;
+      const double ax = rx[o + src] - pl[0], ay = ry[o + src] - pl[1], az = rz[o + src] - pl[2];
+      dst[k] = (ax * u[0] + ay * u[1]) + az * u[2]; dst[SH_MAXSEG + k] = (ax * w[0] + ay * w[1]) + az * w[2];
+    }
+  }
+#endif
   if (ring_out && nl > 0) {
     const double* rx = (const double*)bufA; const double* ry = (const double*)bufB; const double* rz = (const double*)skey;
     const int o = l_off[best], L = l_len[best];

@@ -741,25 +741,32 @@ SH_HD bool resect_plane_from_offsets(const double* T_anp, const double* p_ct, co
 // subtracts numbers of the size tr(S2) / S0; 2^-26 leaves a factor 16 on that bound.  One operation order, sqrt and divisions
 // only: the host instantiation (tests/hostcheck/headfit_check.cpp) gives the device's bits.
 #define SH_HEADFIT_PIVOT 1.4901161193847656e-08      /* 2^-26 */
-SH_HD bool head_sphere_from_moments(const double* m, double* c, double* r, double* rms) {
-  c[0] = c[1] = c[2] = 0.0; *r = 0.0; *rms = 0.0;
+// The moments per unit weight about the weighted centroid g = S1 / S0 (S0 > 0): C the covariance (xx, xy, xz, yy, yz, zz),
+// K3 = E |p|^2 p, K4 = E |p|^4, tr = tr(S2) / S0 (the size of the numbers the shift subtracts).
+SH_HD void head_central_moments(const double* m, double* g, double* C, double* K3, double* K4, double* tr_out) {
   const double S0 = m[0];
-  if (!(S0 > 0.0)) return false;
-  const double g[3] = {m[1] / S0, m[2] / S0, m[3] / S0};
+  g[0] = m[1] / S0; g[1] = m[2] / S0; g[2] = m[3] / S0;
   const double M2[6] = {m[4] / S0, m[5] / S0, m[6] / S0, m[7] / S0, m[8] / S0, m[9] / S0};
   const double M3[3] = {m[10] / S0, m[11] / S0, m[12] / S0};
   const double M4 = m[13] / S0;
   const double tr = (M2[0] + M2[3]) + M2[5];
   const double gg = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
-  // covariance, third and fourth moments about the centroid
-  const double Cxx = M2[0] - g[0] * g[0], Cxy = M2[1] - g[0] * g[1], Cxz = M2[2] - g[0] * g[2];
-  const double Cyy = M2[3] - g[1] * g[1], Cyz = M2[4] - g[1] * g[2], Czz = M2[5] - g[2] * g[2];
+  C[0] = M2[0] - g[0] * g[0]; C[1] = M2[1] - g[0] * g[1]; C[2] = M2[2] - g[0] * g[2];
+  C[3] = M2[3] - g[1] * g[1]; C[4] = M2[4] - g[1] * g[2]; C[5] = M2[5] - g[2] * g[2];
   const double Mg[3] = {(M2[0] * g[0] + M2[1] * g[1]) + M2[2] * g[2], (M2[1] * g[0] + M2[3] * g[1]) + M2[4] * g[2],
                         (M2[2] * g[0] + M2[4] * g[1]) + M2[5] * g[2]};
-  double K3[3];
   for (int i = 0; i < 3; ++i) K3[i] = ((M3[i] - 2.0 * Mg[i]) - tr * g[i]) + 2.0 * gg * g[i];
   const double gM3 = (g[0] * M3[0] + g[1] * M3[1]) + g[2] * M3[2], gMg = (g[0] * Mg[0] + g[1] * Mg[1]) + g[2] * Mg[2];
-  const double K4 = (((M4 - 4.0 * gM3) + 4.0 * gMg) + 2.0 * gg * tr) - 3.0 * gg * gg;
+  *K4 = (((M4 - 4.0 * gM3) + 4.0 * gMg) + 2.0 * gg * tr) - 3.0 * gg * gg;
+  *tr_out = tr;
+}
+SH_HD bool head_sphere_from_moments(const double* m, double* c, double* r, double* rms) {
+  c[0] = c[1] = c[2] = 0.0; *r = 0.0; *rms = 0.0;
+  const double S0 = m[0];
+  if (!(S0 > 0.0)) return false;
+  double g[3], C[6], K3[3], K4, tr;
+  head_central_moments(m, g, C, K3, &K4, &tr);
+  const double Cxx = C[0], Cxy = C[1], Cxz = C[2], Cyy = C[3], Cyz = C[4], Czz = C[5];
   const double trC = (Cxx + Cyy) + Czz;
   // Cholesky C = L L^T, pivots against the size of the numbers the shift subtracted
   const double tiny = SH_HEADFIT_PIVOT * tr;
@@ -806,6 +813,60 @@ SH_HD bool ellipse_from_moments(const double* rm, double* semi_major, double* se
   *semi_major = 2.0 * sqrt(l1); *semi_minor = 2.0 * sqrt(l2);
   dir[0] = vx; dir[1] = vy;
   return true;
+}
+
+// ---- seating an implant head on a cut (include/shoulder_hip.h sh_seat; k_seat.h) -------------------------------------------
+// All in the cut's in-plane basis, coordinates about the seat centre s: a = p - s, b = q - s for the directed ring edge p -> q.
+// The edge's term of area(polygon n disk of radius rho about s) by Green's theorem: the roots t_lo < t_hi of |a + t (b - a)|^2 =
+// rho^2 cut [0, 1] into at most three pieces; the piece inside [t_lo, t_hi] is a chord of the polygon inside the disk and gives
+// cross(x, y) / 2, every other piece follows the circle and gives the sector rho^2 atan2(cross(x, y), dot(x, y)) / 2 (x, y the
+// piece's ends).  Pieces are told apart by the roots alone: a discriminant <= 0 (the line misses or touches the circle) is a
+// sector over the whole edge.  The sum over the ring is the signed area.
+SH_HD double seat_edge_term(double ax, double ay, double bx, double by, double rho2) {
+  const double dx = bx - ax, dy = by - ay;
+  const double A = dx * dx + dy * dy, Bh = ax * dx + ay * dy, Cc = (ax * ax + ay * ay) - rho2;
+  const double disc = Bh * Bh - A * Cc;
+  double c0 = 0.0, c1 = 0.0;      // the chord piece [c0, c1] of [0, 1]; empty when c0 >= c1
+  if (disc > 0.0) {
+    const double sq = sqrt(disc), tlo = (-Bh - sq) / A, thi = (-Bh + sq) / A;
+    c0 = tlo > 0.0 ? tlo : 0.0; c1 = thi < 1.0 ? thi : 1.0;
+  }
+  if (!(c0 < c1)) return (0.5 * rho2) * atan2(ax * by - ay * bx, ax * bx + ay * by);
+  const double x0 = ax + c0 * dx, y0 = ay + c0 * dy, x1 = c1 < 1.0 ? ax + c1 * dx : bx, y1 = c1 < 1.0 ? ay + c1 * dy : by;
+  double t = 0.5 * (x0 * y1 - y0 * x1);
+  if (c0 > 0.0) t += (0.5 * rho2) * atan2(ax * y0 - ay * x0, ax * x0 + ay * y0);
+  if (c1 < 1.0) t += (0.5 * rho2) * atan2(x1 * by - y1 * bx, x1 * bx + y1 * by);
+  return t;
+}
+// squared distance from the origin (the seat centre) to the segment a -> b, and the nearest point
+SH_HD double seat_seg_dist2(double ax, double ay, double bx, double by, double* nx, double* ny) {
+  const double dx = bx - ax, dy = by - ay, dd = dx * dx + dy * dy;
+  double t = dd > 0.0 ? -(ax * dx + ay * dy) / dd : 0.0;
+  t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+  const double x = t < 1.0 ? ax + t * dx : bx, y = t < 1.0 ? ay + t * dy : by;
+  *nx = x; *ny = y;
+  return x * x + y * y;
+}
+// the edge's term of the winding number of the ring about the origin (crossings of the positive x axis' line y = 0, signed)
+SH_HD int seat_winding_term(double ax, double ay, double bx, double by) {
+  const double cr = ax * by - ay * bx;
+  if (ay <= 0.0) return (by > 0.0 && cr > 0.0) ? 1 : 0;
+  return (by <= 0.0 && cr < 0.0) ? -1 : 0;
+}
+// sqrt(sum w (|q - c|^2 - R^2)^2 / S0) / (2 R) from the sixteen moment words of a cut (head_sphere_from_moments' layout, c about
+// the plane point): the first-order radial rms of the head piece's samples against the sphere (c, R).  Formed about the weighted
+// centroid: with c' = c - g and t = R^2 - |c'|^2 the mean of (|p|^2 - 2 c'.p - t)^2 is K4 - 4 c'.K3 + 4 c'^T C c' - 2 t tr C + t^2
+// (E p = 0), which for the fitted sphere (4 C c' = 2 K3, t = tr C) is head_sphere_from_moments' E.  0 for an empty piece.
+SH_HD double seat_surface_rms(const double* m, const double* c, double R) {
+  if (!(m[0] > 0.0) || !(R > 0.0)) return 0.0;
+  double g[3], C[6], K3[3], K4, tr;
+  head_central_moments(m, g, C, K3, &K4, &tr);
+  const double c0 = c[0] - g[0], c1 = c[1] - g[1], c2 = c[2] - g[2];
+  const double trC = (C[0] + C[3]) + C[5];
+  const double t = R * R - ((c0 * c0 + c1 * c1) + c2 * c2);
+  const double Cc[3] = {(C[0] * c0 + C[1] * c1) + C[2] * c2, (C[1] * c0 + C[3] * c1) + C[4] * c2, (C[2] * c0 + C[4] * c1) + C[5] * c2};
+  const double E = (((K4 - 4.0 * ((K3[0] * c0 + K3[1] * c1) + K3[2] * c2)) + 4.0 * ((Cc[0] * c0 + Cc[1] * c1) + Cc[2] * c2)) - 2.0 * t * trC) + t * t;
+  return sqrt(E > 0.0 ? E : 0.0) / (2.0 * R);
 }
 
 }  // namespace sh

@@ -12,6 +12,7 @@
 #include "k_clip.h"
 #include "k_resect.h"
 #include "k_headfit.h"
+#include "k_seat.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -830,9 +831,32 @@ static int headfit_buffers(sh_ctx* c, int P, int pc, int tmax, int* pcf_out) {
   return SH_OK;
 }
 
+// The seats' buffers (k_seat.h) on top of headfit_buffers': the ring coordinates of one pass (16 KB per cut; a fitted pass takes
+// 4 096 / B planes but at least one, so max(B, 4 096) cuts: 64 MB up to B = 4 096 and the fitted split is kept), the catalogue and
+// the B x P x K records, which have no limit of their own (SH_ERR_NOMEM when they do not fit).
+struct SeatArgs { const sh_implant_head* heads; int K, mode; sh_seat* out; };
+static int seat_buffers(sh_ctx* c, int P, int pc, int K) {
+  const int B = c->B;
+  int rc;
+  if ((rc = ensure(c, "resect.seat_ring", (size_t)B * pc * 2 * SH_MAXSEG * 8, 8)) || (rc = ensure(c, "resect.seat_heads", (size_t)K * sizeof(sh_implant_head), 8)) ||
+      (rc = ensure(c, "resect.seat_out", (size_t)B * P * K * sizeof(sh_seat), 8)))
+    return rc;
+  for (const char* n : {"resect.seat_ring", "resect.seat_heads", "resect.seat_out"}) c->bufs[n].per_mesh = 0;
+  return SH_OK;
+}
+static bool seat_args_ok(const sh_implant_head* heads, int K, int mode, sh_seat* out) {
+  if (!heads || !out || K < 1 || K > SH_SEAT_MAX_HEADS || (mode != SH_SEAT_CUT_CENTROID && mode != SH_SEAT_SPHERE_AXIS)) return false;
+  for (int k = 0; k < K; ++k) {
+    const double R = heads[k].radius, h = heads[k].thickness;
+    if (!std::isfinite(R) || !std::isfinite(h) || !(h > 0.0) || !(h < 2.0 * R)) return false;
+  }
+  return true;
+}
+
 // face pass + join of planes [p0, p0 + pc) of humeri [b0, b0 + nb); one: the record and ring of a single cut (sh_resect_ring);
-// fit: the moment pass beside the face pass and the join that adds its slab and the ring's second moments
-static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tmax, bool one, bool fit = false) {
+// fit: the moment pass beside the face pass and the join that adds its slab and the ring's second moments; seat: that join also
+// stores the ring's in-plane coordinates of the pass
+static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tmax, bool one, bool fit = false, bool seat = false) {
   int* segcnt = (int*)c->bufs["resect.segcnt"].p;
   HIPCHK(c, hipMemsetAsync(segcnt, 0, (size_t)nb * pc * 4, c->stream));
   const float* verts = (const float*)c->bufs["verts"].p; const int* faces = (const int*)c->bufs["faces"].p;
@@ -843,6 +867,13 @@ static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tma
   if (fit) {
     LAUNCH(c, "k_headfit_faces", k_headfit_faces, dim3((unsigned)tmax, (unsigned)nb), dim3(SH_RS_TILE), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
            (double*)c->bufs["resect.fit_slab"].p);
+    if (seat) {
+      LAUNCH(c, "k_resect_join_seat", k_resect_join_seat, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
+             (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
+             (sh_resection*)c->bufs["resect.out"].p, (const double*)c->bufs["resect.fit_slab"].p, (double*)c->bufs["resect.fit_moments"].p,
+             (double*)c->bufs["resect.fit_ring"].p, (double*)c->bufs["resect.seat_ring"].p);
+      return SH_OK;
+    }
     LAUNCH(c, "k_resect_join_fit", k_resect_join_fit, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
            (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
            (sh_resection*)c->bufs["resect.out"].p, (const double*)c->bufs["resect.fit_slab"].p, (double*)c->bufs["resect.fit_moments"].p,
@@ -861,29 +892,46 @@ static bool resect_has_records(sh_ctx* c) {
   return c->rec_gen == c->batch_gen && (c->rec_mask & need) == need && c->bufs.find("landmarks") != c->bufs.end();
 }
 
-static int resect_all(sh_ctx* c, int P, int pc, int tmax, sh_resection* out, sh_head_fit* fit_out) {
+static int resect_all(sh_ctx* c, int P, int pc, int tmax, sh_resection* out, sh_head_fit* fit_out, const SeatArgs* seat = nullptr) {
   const size_t n = (size_t)c->B * P;
   if (fit_out) {      // (a cut whose humerus' record failed writes neither: zeros)
     HIPCHK(c, hipMemsetAsync(c->bufs["resect.fit_moments"].p, 0, n * 16 * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(c->bufs["resect.fit_ring"].p, 0, n * 8 * 8, c->stream));
   }
-  for (int p0 = 0; p0 < P; p0 += pc)
-    if (int rc = resect_pass(c, P, p0, std::min(pc, P - p0), 0, c->B, tmax, false, fit_out != nullptr)) return rc;
+  const sh_landmarks* lm = resect_has_records(c) ? (const sh_landmarks*)c->bufs["landmarks"].p : (const sh_landmarks*)nullptr;
+  if (seat) HIPCHK(c, hipMemcpyAsync(c->bufs["resect.seat_heads"].p, seat->heads, (size_t)seat->K * sizeof(sh_implant_head), hipMemcpyHostToDevice, c->stream));
+  for (int p0 = 0; p0 < P; p0 += pc) {
+    const int pn = std::min(pc, P - p0), cuts = c->B * pn;
+    if (int rc = resect_pass(c, P, p0, pn, 0, c->B, tmax, false, fit_out != nullptr, seat != nullptr)) return rc;
+    if (seat) {      // the ring coordinates are the pass': its fits and its seats before the next pass overwrites them
+      LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((cuts + 63) / 64)), dim3(64), (const sh_resection*)c->bufs["resect.out"].p,
+             (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p, (const double*)c->bufs["resect.fit_ring"].p,
+             lm, P, p0, pn, cuts, (sh_head_fit*)c->bufs["resect.fit_out"].p);
+      LAUNCH(c, "k_seat", k_seat, dim3((unsigned)cuts), dim3(SH_SEAT_THREADS), (const sh_resection*)c->bufs["resect.out"].p,
+             (const sh_head_fit*)c->bufs["resect.fit_out"].p, (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p,
+             (const double*)c->bufs["resect.seat_ring"].p, lm, (const sh_implant_head*)c->bufs["resect.seat_heads"].p, seat->K, seat->mode, P, p0, pn,
+             (sh_seat*)c->bufs["resect.seat_out"].p);
+    }
+  }
   HIPCHK(c, hipMemcpyAsync(out, c->bufs["resect.out"].p, n * sizeof(sh_resection), hipMemcpyDeviceToHost, c->stream));
   if (fit_out) {
-    LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((n + 63) / 64)), dim3(64), (const sh_resection*)c->bufs["resect.out"].p,
-           (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p, (const double*)c->bufs["resect.fit_ring"].p,
-           resect_has_records(c) ? (const sh_landmarks*)c->bufs["landmarks"].p : (const sh_landmarks*)nullptr, P, (int)n, (sh_head_fit*)c->bufs["resect.fit_out"].p);
+    if (!seat)
+      LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((n + 63) / 64)), dim3(64), (const sh_resection*)c->bufs["resect.out"].p,
+             (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p, (const double*)c->bufs["resect.fit_ring"].p,
+             lm, P, 0, P, (int)n, (sh_head_fit*)c->bufs["resect.fit_out"].p);
     HIPCHK(c, hipMemcpyAsync(fit_out, c->bufs["resect.fit_out"].p, n * sizeof(sh_head_fit), hipMemcpyDeviceToHost, c->stream));
   }
+  if (seat) HIPCHK(c, hipMemcpyAsync(seat->out, c->bufs["resect.seat_out"].p, n * seat->K * sizeof(sh_seat), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->resect_P = P; c->resect_gen = c->batch_gen;
   return SH_OK;
 }
 
-static int resect_planes_impl(sh_ctx* c, const char* fn, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out, bool fit) {
+static int resect_planes_impl(sh_ctx* c, const char* fn, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out, bool fit,
+                              const SeatArgs* seat = nullptr) {
   const std::string f(fn);
   if (!c || !planes || !out || (fit && !fit_out) || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
+  if (seat && !seat_args_ok(seat->heads, seat->K, seat->mode, seat->out)) return fail(c, SH_ERR_ARG, f + ": bad catalogue (K in 1..64, 0 < thickness < 2 radius) or centre mode");
   if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
   if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
   const size_t n = (size_t)c->B * P;
@@ -897,15 +945,18 @@ static int resect_planes_impl(sh_ctx* c, const char* fn, const double* planes, i
   int pc, tmax, rc;
   if ((rc = resect_buffers(c, P, &pc, &tmax))) return rc;
   if (fit && (rc = headfit_buffers(c, P, pc, tmax, &pc))) return rc;
+  if (seat && (rc = seat_buffers(c, P, pc, seat->K))) return rc;
   c->resect_gen = ~0ull;
   HIPCHK(c, hipMemcpyAsync(c->bufs["resect.planes"].p, planes, n * 48, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->bufs["resect.status"].p, 0, n * 4, c->stream));
-  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr);
+  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr, seat);
 }
 
-static int resect_offsets_impl(sh_ctx* c, const char* fn, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out, bool fit) {
+static int resect_offsets_impl(sh_ctx* c, const char* fn, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out, bool fit,
+                               const SeatArgs* seat = nullptr) {
   const std::string f(fn);
   if (!c || !offs || !out || (fit && !fit_out) || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
+  if (seat && !seat_args_ok(seat->heads, seat->K, seat->mode, seat->out)) return fail(c, SH_ERR_ARG, f + ": bad catalogue (K in 1..64, 0 < thickness < 2 radius) or centre mode");
   if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
   if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
   if (!resect_has_records(c)) return fail(c, SH_ERR_STATE, f + ": needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
@@ -916,13 +967,14 @@ static int resect_offsets_impl(sh_ctx* c, const char* fn, const sh_cut_offset* o
   int pc, tmax, rc;
   if ((rc = resect_buffers(c, P, &pc, &tmax))) return rc;
   if (fit && (rc = headfit_buffers(c, P, pc, tmax, &pc))) return rc;
+  if (seat && (rc = seat_buffers(c, P, pc, seat->K))) return rc;
   if ((rc = ensure(c, "resect.offs", (size_t)P * 56, 8))) return rc;
   c->bufs["resect.offs"].per_mesh = 0;
   c->resect_gen = ~0ull;
   HIPCHK(c, hipMemcpyAsync(c->bufs["resect.offs"].p, offs, (size_t)P * 56, hipMemcpyHostToDevice, c->stream));
   LAUNCH(c, "k_resect_make_planes", k_resect_make_planes, dim3((unsigned)c->B), dim3(64), (const sh_landmarks*)c->bufs["landmarks"].p,
          (const double*)c->bufs["resect.offs"].p, P, (double*)c->bufs["resect.planes"].p, (int*)c->bufs["resect.status"].p);
-  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr);
+  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr, seat);
 }
 
 int sh_resect_planes(sh_ctx* c, const double* planes, int P, sh_resection* out) { return resect_planes_impl(c, "sh_resect_planes", planes, P, out, nullptr, false); }
@@ -932,6 +984,17 @@ int sh_resect_planes_fit(sh_ctx* c, const double* planes, int P, sh_resection* o
 }
 int sh_resect_offsets_fit(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out) {
   return resect_offsets_impl(c, "sh_resect_offsets_fit", offs, P, out, fit_out, true);
+}
+
+int sh_resect_planes_seat(sh_ctx* c, const double* planes, int P, const sh_implant_head* heads, int K, int center_mode, sh_resection* out,
+                          sh_head_fit* fit_out, sh_seat* seat_out) {
+  const SeatArgs seat{heads, K, center_mode, seat_out};
+  return resect_planes_impl(c, "sh_resect_planes_seat", planes, P, out, fit_out, true, &seat);
+}
+int sh_resect_offsets_seat(sh_ctx* c, const sh_cut_offset* offs, int P, const sh_implant_head* heads, int K, int center_mode, sh_resection* out,
+                           sh_head_fit* fit_out, sh_seat* seat_out) {
+  const SeatArgs seat{heads, K, center_mode, seat_out};
+  return resect_offsets_impl(c, "sh_resect_offsets_seat", offs, P, out, fit_out, true, &seat);
 }
 
 int sh_resect_ring(sh_ctx* c, int b, int p, double* out, int cap, int* n_out) {

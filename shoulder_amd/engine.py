@@ -434,17 +434,28 @@ class Engine:
         return out
 
     # ---- batched head resection (include/shoulder_hip.h sh_resect_*) -------------------------------------------------
-    def resect(self, planes=None, offsets=None, fit=False):
+    def resect(self, planes=None, offsets=None, fit=False, heads=None, seat_center="centroid"):
         """B resident humeri x P resection planes in one device pass -> structured array (B, P) of _lib.RESECTION_DTYPE.
         planes: (B, P, 6) or (B, P, 2, 3) float64, (point, normal) in CT per humerus (sh_resect_planes; needs no run).
         offsets: P cuts relative to every humerus' own anatomic-neck plane -- a list of dicts or a structured array with the
         sh_cut_offset field names (_lib.CUT_OFFSET_DTYPE; missing keys are 0) -- planes built on the device from the records of
         the last run (sh_resect_offsets; needs a run with STAGE_ANP and STAGE_CSYS).  A cut's `status` tells its own failure.
         fit=True: -> (records, fits), fits a structured array (B, P) of _lib.HEAD_FIT_DTYPE -- the sphere of every cut's head piece and
-        the ellipse of its cut (sh_resect_*_fit; the records are the same bytes)."""
+        the ellipse of its cut (sh_resect_*_fit; the records are the same bytes).
+        fit=True, heads=[(R, h), ...]: -> (records, fits, seats), seats a structured array (B, P, K) of _lib.SEAT_DTYPE -- how each of
+        the K implant heads (radius of curvature, thickness) sits on each cut, about the cut's area centroid (seat_center="centroid")
+        or the foot of the fitted sphere's centre ("sphere") (sh_resect_*_seat; records and fits are the same bytes)."""
         if (planes is None) == (offsets is None):
             raise ValueError("resect() takes planes or offsets")
         B = self.B
+        hd = None
+        if heads is not None:
+            if not fit:
+                raise ValueError("heads needs fit=True")
+            if seat_center not in ("centroid", "sphere"):
+                raise ValueError("seat_center must be 'centroid' or 'sphere'")
+            hd = np.ascontiguousarray(np.asarray(heads, dtype=np.float64).reshape(-1, 2))
+            mode = _lib.SEAT_SPHERE_AXIS if seat_center == "sphere" else _lib.SEAT_CUT_CENTROID
         if planes is not None:
             pl = np.ascontiguousarray(planes, dtype=np.float64)
             if pl.ndim < 2 or pl.shape[0] != B or pl.size % (6 * max(B, 1)) or pl.size == 0:
@@ -453,6 +464,10 @@ class Engine:
             out = np.zeros((B, P), dtype=_lib.RESECTION_DTYPE)
             if fit:
                 fits = np.zeros((B, P), dtype=_lib.HEAD_FIT_DTYPE)
+                if hd is not None:
+                    seats = np.zeros((B, P, len(hd)), dtype=_lib.SEAT_DTYPE)
+                    self._chk(self.L.sh_resect_planes_seat(self.h, _ptr(pl), P, _ptr(hd), len(hd), mode, _ptr(out), _ptr(fits), _ptr(seats)))
+                    return out, fits, seats
                 self._chk(self.L.sh_resect_planes_fit(self.h, _ptr(pl), P, _ptr(out), _ptr(fits)))
                 return out, fits
             self._chk(self.L.sh_resect_planes(self.h, _ptr(pl), P, _ptr(out)))
@@ -472,6 +487,10 @@ class Engine:
         out = np.zeros((B, len(off)), dtype=_lib.RESECTION_DTYPE)
         if fit:
             fits = np.zeros((B, len(off)), dtype=_lib.HEAD_FIT_DTYPE)
+            if hd is not None:
+                seats = np.zeros((B, len(off), len(hd)), dtype=_lib.SEAT_DTYPE)
+                self._chk(self.L.sh_resect_offsets_seat(self.h, _ptr(off), len(off), _ptr(hd), len(hd), mode, _ptr(out), _ptr(fits), _ptr(seats)))
+                return out, fits, seats
             self._chk(self.L.sh_resect_offsets_fit(self.h, _ptr(off), len(off), _ptr(out), _ptr(fits)))
             return out, fits
         self._chk(self.L.sh_resect_offsets(self.h, _ptr(off), len(off), _ptr(out)))
