@@ -15,10 +15,9 @@
 #pragma once
 #include "sh_common.h"
 #include "k_stl.h"
+#include "sh_cutmath.h"
 
 namespace sh {
-
-#define SH_CLIP_TOL 1e-8      // trimesh.constants.tol.merge
 
 struct ClipCounts { int n_in, n_quad, n_tri, n_pre, n_verts, n_faces, n_edges, pad; };      // per plane
 
@@ -31,14 +30,6 @@ __global__ void k_clip_sign(const double* __restrict__ verts, int nv, const doub
     const double d = (dx * pl[3] + dy * pl[4]) + dz * pl[5];
     sign[(size_t)p * nv + i] = d < -SH_CLIP_TOL ? 1 : (d > SH_CLIP_TOL ? -1 : 0);      // -1 = kept side (slice_faces_plane's convention)
   }
-}
-
-// class of a face from its three signs: 0 dropped, 1 kept, 2 quad, 3 triangle, 4 = lies in the plane (decided by its normal)
-__device__ inline int clip_class(int s0, int s1, int s2) {
-  const int sum = s0 + s1 + s2, asum = abs(s0) + abs(s1) + abs(s2);
-  if (asum == 0) return 4;
-  if (asum >= 2 && abs(sum) <= 1) return sum < 0 ? 2 : 3;
-  return sum == -asum ? 1 : 0;
 }
 
 __global__ void __launch_bounds__(SH_STL_SCAN_THREADS)
@@ -79,17 +70,6 @@ k_clip_class(const double* __restrict__ verts, const int* __restrict__ faces, in
     ClipCounts& o = counts[p];
     o.n_in = t1; o.n_quad = t2; o.n_tri = t3; o.n_pre = nv + 2 * t2 + 2 * t3; o.n_verts = 0; o.n_faces = t1 + 2 * t2 + t3; o.n_edges = t2 + t3; o.pad = 0;
   }
-}
-
-// crossing point of edge j (o[j] -> o[(j+1)%3]) with the plane: slice_faces_plane's  dist = num / denom;  point = dist * d + o
-__device__ inline void clip_cross(const double* O /* 3 x 3 */, int j, const double* pl, double* out) {
-  const double* o = O + 3 * j; const double* o1 = O + 3 * ((j + 1) % 3);
-  const double dx = o1[0] - o[0], dy = o1[1] - o[1], dz = o1[2] - o[2];
-  const double num = ((pl[0] - o[0]) * pl[3] + (pl[1] - o[1]) * pl[4]) + (pl[2] - o[2]) * pl[5];
-  double den = (dx * pl[3] + dy * pl[4]) + dz * pl[5];
-  if (den == 0.0) den = 1e-12;
-  const double dist = num / den;
-  out[0] = dist * dx + o[0]; out[1] = dist * dy + o[1]; out[2] = dist * dz + o[2];
 }
 
 // pre-merge numbering: original vertices [0, nv), quad points nv + 2q + {0,1}, triangle points nv + 2 n_quad + 2t + {0,1}

@@ -62,20 +62,8 @@ k_headfit_faces(const float* __restrict__ verts, const int* __restrict__ faces, 
                 double* __restrict__ fslab /* [grid.y][pc][tstride][SH_HF_WORDS] */) {
   __shared__ double s_red[2][SH_RS_TILE / 64][SH_HF_WORDS];
   const int bi = blockIdx.y, b = b0 + bi, t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long f0 = foff[b], nf = foff[b + 1] - f0;
-  if ((long long)t * SH_RS_TILE >= nf) return;      // (uniform)
-  const long long fi = (long long)t * SH_RS_TILE + tid;
-  const bool live = fi < nf;
-  double V[9];
-  {
-    const int* f = faces + 3 * (f0 + (live ? fi : 0));
-    const float* vb = verts + 3 * voff[b];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float* v = vb + 3 * (size_t)f[j];
-      V[3 * j] = (double)v[0]; V[3 * j + 1] = (double)v[1]; V[3 * j + 2] = (double)v[2];
-    }
-  }
+  bool live; long long fi; double V[9];
+  if (!resect_tile_face(verts, faces, voff, foff, b, t, tid, &live, &fi, V)) return;      // (uniform)
   const int word = headfit_word(lane);
   for (int q = 0; q < pc; ++q) {
     const double* plg = planes + ((size_t)b * P + (p0 + q)) * 6;

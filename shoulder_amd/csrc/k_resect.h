@@ -19,8 +19,8 @@
 // The mesh is read once for all P planes: bytes per humerus = faces (12 B) + gathered vertices, not times P.
 #pragma once
 #include "../../include/shoulder_hip.h"
-#include "k_slices.h"
-#include "k_clip.h"
+#include "sh_scalar.h"
+#include "sh_cutmath.h"
 
 namespace sh {
 
@@ -78,6 +78,24 @@ __device__ inline void resect_tri_terms(const double* a, const double* b, const 
   *ar += sqrt((nx * nx + ny * ny) + nz * nz);
 }
 
+// a lane's face of tile t of humerus b for k_resect_faces and k_headfit_faces: false when the tile lies behind the humerus' faces (uniform);
+// else *live: the lane has a face, *fi its index in the humerus, V its float32 vertices widened (a lane without a face holds face 0)
+__device__ __forceinline__ bool resect_tile_face(const float* __restrict__ verts, const int* __restrict__ faces, const long long* __restrict__ voff,
+                                                 const long long* __restrict__ foff, int b, int t, int tid, bool* live, long long* fi, double* V /* 3 x 3 */) {
+  const long long f0 = foff[b], nf = foff[b + 1] - f0;
+  if ((long long)t * SH_RS_TILE >= nf) return false;
+  *fi = (long long)t * SH_RS_TILE + tid;
+  *live = *fi < nf;
+  const int* f = faces + 3 * (f0 + (*live ? *fi : 0));
+  const float* vb = verts + 3 * voff[b];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float* v = vb + 3 * (size_t)f[j];
+    V[3 * j] = (double)v[0]; V[3 * j + 1] = (double)v[1]; V[3 * j + 2] = (double)v[2];
+  }
+  return true;
+}
+
 __global__ void __launch_bounds__(SH_RS_TILE)
 k_resect_faces(const float* __restrict__ verts, const int* __restrict__ faces, const long long* __restrict__ voff, const long long* __restrict__ foff,
                const double* __restrict__ planes /* B x P x 6 */, int P, int p0, int pc /* planes p0 .. p0 + pc of this pass */,
@@ -88,20 +106,8 @@ k_resect_faces(const float* __restrict__ verts, const int* __restrict__ faces, c
   __shared__ int s_cnt[2][SH_RS_TILE / 64];
   __shared__ int s_base[2];
   const int bi = blockIdx.y, b = b0 + bi, t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long f0 = foff[b], nf = foff[b + 1] - f0;
-  if ((long long)t * SH_RS_TILE >= nf) return;      // (uniform)
-  const long long fi = (long long)t * SH_RS_TILE + tid;
-  const bool live = fi < nf;
-  double V[9];
-  {
-    const int* f = faces + 3 * (f0 + (live ? fi : 0));
-    const float* vb = verts + 3 * voff[b];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float* v = vb + 3 * (size_t)f[j];
-      V[3 * j] = (double)v[0]; V[3 * j + 1] = (double)v[1]; V[3 * j + 2] = (double)v[2];
-    }
-  }
+  bool live; long long fi; double V[9];
+  if (!resect_tile_face(verts, faces, voff, foff, b, t, tid, &live, &fi, V)) return;      // (uniform)
   for (int q = 0; q < pc; ++q) {
     const double* plg = planes + ((size_t)b * P + (p0 + q)) * 6;
     const double pl[6] = {plg[0], plg[1], plg[2], plg[3], plg[4], plg[5]};      // (the same address in every lane)

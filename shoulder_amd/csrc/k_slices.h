@@ -14,6 +14,7 @@
 #pragma once
 #include "sh_demand.h"
 #include "sh_scalar.h"
+#include "sh_cutmath.h"
 
 namespace sh {
 
@@ -274,13 +275,7 @@ k_slice_emit(const double* __restrict__ vobb, const int* __restrict__ faces,
 // jumping for (a) the minimum edge key of each loop (canonical start, B-1) and (b) the rank of
 // every segment from that start.
 #define SH_LINK_THREADS 256
-#define SH_MAXLOOPS 32
 #define SH_SMALLSEG 384      // tier boundary: planes with at most this many segments take the small-LDS instantiation (humerus sections: mean 140-210, max ~330)
-
-__device__ inline uint32_t hash_key64(unsigned long long k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33;
-  return (uint32_t)k;
-}
 
 // Greedy matching by the smallest candidate first equals the matching of locally dominant pairs (a pair that is the smallest
 // candidate of its tail AND of its head) taken round after round, when the order is total: it is here, (gap, tail key, head

@@ -797,53 +797,86 @@ int sh_slice_mesh_planes(sh_ctx* c, const double* verts, int nv, const int32_t* 
   return SH_OK;
 }
 
-// ---- batched head resection (k_resect.h) -------------------------------------------------------------------------------
-// Planes per pass: the slot ranges (4 KB per cut) and the slab (32 B per cut and tile) stay below 32 MB / 128 MB; a sweep larger
-// than that takes several passes over the mesh.  The pass a plane falls into does not change its record (the slab of a cut is its own).
-static int resect_buffers(sh_ctx* c, int P, int* pc_out, int* tmax_out) {
-  const int B = c->B;
+// ---- batched head resection (k_resect.h, k_headfit.h, k_seat.h): the sh_resect_* entry points and the one pipeline behind them ----
+// what a call computes per cut: the record; the head fit beside it (the moment pass and the join that adds its slab and the ring's
+// second moments); the seats of a catalogue on top (that join also stores the ring's in-plane coordinates of the pass)
+enum ResectLevel { RS_RECORDS, RS_FIT, RS_SEAT };
+
+struct ResectRequest {
+  const char* fn;                    // the caller's name, for error texts
+  ResectLevel level;
+  const double* planes;              // B x P x (point, normal), or
+  const sh_cut_offset* offs;         // P offsets, the same for every humerus (the one that is set is the source)
+  int P;
+  sh_resection* out;
+  sh_head_fit* fit_out = nullptr;    // RS_FIT and up
+  const sh_implant_head* heads = nullptr;      // RS_SEAT: the catalogue, its size, the centre mode and the records
+  int K = 0, mode = 0;
+  sh_seat* seat_out = nullptr;
+};
+
+// the named buffers of a call as typed pointers, resolved once (null: not there)
+struct ResectView {
+  const float* verts; const int* faces; const long long* voff; const long long* foff;
+  const sh_landmarks* lm;            // null: no run of the resident batch with the anatomic neck and the csys
+  double* planes; int* status; ResectPart* slab; int* segcnt; int* segs; sh_resection* out; sh_resection* one; double* ring; double* offs;
+  double* fit_slab; double* fit_moments; double* fit_ring; sh_head_fit* fit_out;
+  double* seat_ring; sh_implant_head* seat_heads; sh_seat* seat_out;
+};
+
+struct ResectPass { int P, p0, pc, b0, nb, tmax; };      // planes [p0, p0 + pc) of humeri [b0, b0 + nb), tmax tiles per humerus in the slabs
+
+static bool resect_has_records(sh_ctx* c) {
+  const uint32_t need = SH_STAGE_ANP | SH_STAGE_CSYS;
+  return c->rec_gen == c->batch_gen && (c->rec_mask & need) == need && c->bufs.find("landmarks") != c->bufs.end();
+}
+
+static ResectView resect_view(sh_ctx* c) {
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  ResectView v;
+  v.verts = (const float*)at("verts"); v.faces = (const int*)at("faces"); v.voff = (const long long*)at("voff"); v.foff = (const long long*)at("foff");
+  v.lm = resect_has_records(c) ? (const sh_landmarks*)at("landmarks") : nullptr;
+  v.planes = (double*)at("resect.planes"); v.status = (int*)at("resect.status"); v.slab = (ResectPart*)at("resect.slab");
+  v.segcnt = (int*)at("resect.segcnt"); v.segs = (int*)at("resect.segs"); v.out = (sh_resection*)at("resect.out");
+  v.one = (sh_resection*)at("resect.one"); v.ring = (double*)at("resect.ring"); v.offs = (double*)at("resect.offs");
+  v.fit_slab = (double*)at("resect.fit_slab"); v.fit_moments = (double*)at("resect.fit_moments"); v.fit_ring = (double*)at("resect.fit_ring");
+  v.fit_out = (sh_head_fit*)at("resect.fit_out");
+  v.seat_ring = (double*)at("resect.seat_ring"); v.seat_heads = (sh_implant_head*)at("resect.seat_heads"); v.seat_out = (sh_seat*)at("resect.seat_out");
+  return v;
+}
+
+// The buffers of a request and its planes per pass.  Records: the slot ranges (4 KB per cut) and the slab (32 B per cut and tile)
+// stay below 32 MB / 128 MB, so a pass takes at most 8 192 cuts; a sweep larger than that takes several passes over the mesh.  The
+// pass a plane falls into does not change its record (the slab of a cut is its own).  Fit: the moment slab (128 B per cut and tile)
+// has 128 MB of its own and a pass takes at most 4 096 cuts, so the planes per pass of a fitted sweep are at most the un-fitted
+// ones -- which keep their split.  Seat: the ring coordinates of one pass (16 KB per cut; a fitted pass takes 4 096 / B planes but
+// at least one, so max(B, 4 096) cuts: 64 MB up to B = 4 096 and the fitted split is kept), the catalogue and the B x P x K
+// records, which have no limit of their own (SH_ERR_NOMEM when they do not fit).
+static int resect_ensure(sh_ctx* c, const ResectRequest& q, int* pc_out, int* tmax_out) {
+  const int B = c->B, P = q.P;
   const long long tmax = std::max<long long>(1, (c->maxF + SH_RS_TILE - 1) / SH_RS_TILE);
   long long pc = std::min<long long>(8192 / B, (128LL << 20) / (32LL * B * tmax));
   pc = std::max<long long>(1, std::min<long long>(pc, P));
   int rc;
-  if ((rc = ensure(c, "resect.planes", (size_t)B * P * 48, 8)) || (rc = ensure(c, "resect.status", (size_t)B * P * 4, 4)) ||
-      (rc = ensure(c, "resect.slab", (size_t)B * pc * tmax * sizeof(ResectPart), 8)) || (rc = ensure(c, "resect.segcnt", (size_t)B * pc * 4, 4)) ||
-      (rc = ensure(c, "resect.segs", (size_t)B * pc * SH_MAXSEG * 4, 4)) || (rc = ensure(c, "resect.out", (size_t)B * P * sizeof(sh_resection), 8)) ||
-      (rc = ensure(c, "resect.one", sizeof(sh_resection), 8)) || (rc = ensure(c, "resect.ring", (size_t)(SH_MAXSEG + 1) * 24, 8)))
-    return rc;
-  for (const char* n : {"resect.planes", "resect.status", "resect.slab", "resect.segcnt", "resect.segs", "resect.out", "resect.one", "resect.ring"}) c->bufs[n].per_mesh = 0;
+  ENS_SHARED("resect.planes", (size_t)B * P * 48, 8); ENS_SHARED("resect.status", (size_t)B * P * 4, 4);
+  ENS_SHARED("resect.slab", (size_t)B * pc * tmax * sizeof(ResectPart), 8); ENS_SHARED("resect.segcnt", (size_t)B * pc * 4, 4);
+  ENS_SHARED("resect.segs", (size_t)B * pc * SH_MAXSEG * 4, 4); ENS_SHARED("resect.out", (size_t)B * P * sizeof(sh_resection), 8);
+  ENS_SHARED("resect.one", sizeof(sh_resection), 8); ENS_SHARED("resect.ring", (size_t)(SH_MAXSEG + 1) * 24, 8);
+  if (q.level >= RS_FIT) {
+    const long long pcf = std::min<long long>(4096 / B, (128LL << 20) / (8LL * SH_HF_WORDS * B * tmax));
+    pc = std::max<long long>(1, std::min<long long>(pcf, pc));
+    ENS_SHARED("resect.fit_slab", (size_t)B * pc * tmax * SH_HF_WORDS * 8, 8); ENS_SHARED("resect.fit_moments", (size_t)B * P * 16 * 8, 8);
+    ENS_SHARED("resect.fit_ring", (size_t)B * P * 8 * 8, 8); ENS_SHARED("resect.fit_out", (size_t)B * P * sizeof(sh_head_fit), 8);
+  }
+  if (q.level == RS_SEAT) {
+    ENS_SHARED("resect.seat_ring", (size_t)B * pc * 2 * SH_MAXSEG * 8, 8); ENS_SHARED("resect.seat_heads", (size_t)q.K * sizeof(sh_implant_head), 8);
+    ENS_SHARED("resect.seat_out", (size_t)B * P * q.K * sizeof(sh_seat), 8);
+  }
+  if (q.offs) ENS_SHARED("resect.offs", (size_t)P * 56, 8);
   *pc_out = (int)pc; *tmax_out = (int)tmax;
   return SH_OK;
 }
 
-// The head fit's buffers (k_headfit.h) on top of resect_buffers': its moment slab (128 B per cut and tile) has 128 MB of its own and
-// a pass takes at most 4 096 cuts, so the planes per pass of a fitted sweep are at most the un-fitted ones -- which keep their split.
-static int headfit_buffers(sh_ctx* c, int P, int pc, int tmax, int* pcf_out) {
-  const int B = c->B;
-  long long pcf = std::min<long long>(4096 / B, (128LL << 20) / (8LL * SH_HF_WORDS * B * tmax));
-  pcf = std::max<long long>(1, std::min<long long>(pcf, pc));
-  int rc;
-  if ((rc = ensure(c, "resect.fit_slab", (size_t)B * pcf * tmax * SH_HF_WORDS * 8, 8)) || (rc = ensure(c, "resect.fit_moments", (size_t)B * P * 16 * 8, 8)) ||
-      (rc = ensure(c, "resect.fit_ring", (size_t)B * P * 8 * 8, 8)) || (rc = ensure(c, "resect.fit_out", (size_t)B * P * sizeof(sh_head_fit), 8)))
-    return rc;
-  for (const char* n : {"resect.fit_slab", "resect.fit_moments", "resect.fit_ring", "resect.fit_out"}) c->bufs[n].per_mesh = 0;
-  *pcf_out = (int)pcf;
-  return SH_OK;
-}
-
-// The seats' buffers (k_seat.h) on top of headfit_buffers': the ring coordinates of one pass (16 KB per cut; a fitted pass takes
-// 4 096 / B planes but at least one, so max(B, 4 096) cuts: 64 MB up to B = 4 096 and the fitted split is kept), the catalogue and
-// the B x P x K records, which have no limit of their own (SH_ERR_NOMEM when they do not fit).
-struct SeatArgs { const sh_implant_head* heads; int K, mode; sh_seat* out; };
-static int seat_buffers(sh_ctx* c, int P, int pc, int K) {
-  const int B = c->B;
-  int rc;
-  if ((rc = ensure(c, "resect.seat_ring", (size_t)B * pc * 2 * SH_MAXSEG * 8, 8)) || (rc = ensure(c, "resect.seat_heads", (size_t)K * sizeof(sh_implant_head), 8)) ||
-      (rc = ensure(c, "resect.seat_out", (size_t)B * P * K * sizeof(sh_seat), 8)))
-    return rc;
-  for (const char* n : {"resect.seat_ring", "resect.seat_heads", "resect.seat_out"}) c->bufs[n].per_mesh = 0;
-  return SH_OK;
-}
 static bool seat_args_ok(const sh_implant_head* heads, int K, int mode, sh_seat* out) {
   if (!heads || !out || K < 1 || K > SH_SEAT_MAX_HEADS || (mode != SH_SEAT_CUT_CENTROID && mode != SH_SEAT_SPHERE_AXIS)) return false;
   for (int k = 0; k < K; ++k) {
@@ -853,148 +886,114 @@ static bool seat_args_ok(const sh_implant_head* heads, int K, int mode, sh_seat*
   return true;
 }
 
-// face pass + join of planes [p0, p0 + pc) of humeri [b0, b0 + nb); one: the record and ring of a single cut (sh_resect_ring);
-// fit: the moment pass beside the face pass and the join that adds its slab and the ring's second moments; seat: that join also
-// stores the ring's in-plane coordinates of the pass
-static int resect_pass(sh_ctx* c, int P, int p0, int pc, int b0, int nb, int tmax, bool one, bool fit = false, bool seat = false) {
-  int* segcnt = (int*)c->bufs["resect.segcnt"].p;
-  HIPCHK(c, hipMemsetAsync(segcnt, 0, (size_t)nb * pc * 4, c->stream));
-  const float* verts = (const float*)c->bufs["verts"].p; const int* faces = (const int*)c->bufs["faces"].p;
-  const long long* voff = (const long long*)c->bufs["voff"].p; const long long* foff = (const long long*)c->bufs["foff"].p;
-  const double* planes = (const double*)c->bufs["resect.planes"].p;
-  LAUNCH(c, "k_resect_faces", k_resect_faces, dim3((unsigned)tmax, (unsigned)nb), dim3(SH_RS_TILE), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
-         (ResectPart*)c->bufs["resect.slab"].p, segcnt, (int*)c->bufs["resect.segs"].p);
-  if (fit) {
-    LAUNCH(c, "k_headfit_faces", k_headfit_faces, dim3((unsigned)tmax, (unsigned)nb), dim3(SH_RS_TILE), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
-           (double*)c->bufs["resect.fit_slab"].p);
-    if (seat) {
-      LAUNCH(c, "k_resect_join_seat", k_resect_join_seat, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
-             (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
-             (sh_resection*)c->bufs["resect.out"].p, (const double*)c->bufs["resect.fit_slab"].p, (double*)c->bufs["resect.fit_moments"].p,
-             (double*)c->bufs["resect.fit_ring"].p, (double*)c->bufs["resect.seat_ring"].p);
-      return SH_OK;
-    }
-    LAUNCH(c, "k_resect_join_fit", k_resect_join_fit, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
-           (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
-           (sh_resection*)c->bufs["resect.out"].p, (const double*)c->bufs["resect.fit_slab"].p, (double*)c->bufs["resect.fit_moments"].p,
-           (double*)c->bufs["resect.fit_ring"].p);
-    return SH_OK;
-  }
-  LAUNCH(c, "k_resect_join", k_resect_join, dim3((unsigned)(nb * pc)), dim3(SH_RS_JOIN_THREADS), verts, faces, voff, foff, planes, P, p0, pc, b0, tmax,
-         (const int*)c->bufs["resect.status"].p, (const ResectPart*)c->bufs["resect.slab"].p, (const int*)segcnt, (const int*)c->bufs["resect.segs"].p,
-         (sh_resection*)c->bufs["resect.out"].p, one ? (sh_resection*)c->bufs["resect.one"].p : (sh_resection*)nullptr,
-         one ? (double*)c->bufs["resect.ring"].p : (double*)nullptr);
+// the join of a pass at a level; one / ring: the one-cut outputs of the records level (sh_resect_ring)
+static int launch_join(sh_ctx* c, const ResectView& v, ResectLevel level, const ResectPass& s, sh_resection* one = nullptr, double* ring = nullptr) {
+  const dim3 grid((unsigned)(s.nb * s.pc)), block(SH_RS_JOIN_THREADS);
+#define RJ_ARGS v.verts, v.faces, v.voff, v.foff, (const double*)v.planes, s.P, s.p0, s.pc, s.b0, s.tmax, (const int*)v.status, (const ResectPart*)v.slab, \
+                (const int*)v.segcnt, (const int*)v.segs, v.out
+  if (level == RS_SEAT) LAUNCH(c, "k_resect_join_seat", k_resect_join_seat, grid, block, RJ_ARGS, (const double*)v.fit_slab, v.fit_moments, v.fit_ring, v.seat_ring);
+  else if (level == RS_FIT) LAUNCH(c, "k_resect_join_fit", k_resect_join_fit, grid, block, RJ_ARGS, (const double*)v.fit_slab, v.fit_moments, v.fit_ring);
+  else LAUNCH(c, "k_resect_join", k_resect_join, grid, block, RJ_ARGS, one, ring);
+#undef RJ_ARGS
   return SH_OK;
 }
 
-static bool resect_has_records(sh_ctx* c) {
-  const uint32_t need = SH_STAGE_ANP | SH_STAGE_CSYS;
-  return c->rec_gen == c->batch_gen && (c->rec_mask & need) == need && c->bufs.find("landmarks") != c->bufs.end();
+// the fits of planes [p0, p0 + pn) of every humerus from their moments, ring sums and records
+static int launch_solve(sh_ctx* c, const ResectView& v, int P, int p0, int pn) {
+  const int n = c->B * pn;
+  LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((n + 63) / 64)), dim3(64), (const sh_resection*)v.out, (const int*)v.status,
+         (const double*)v.fit_moments, (const double*)v.fit_ring, v.lm, P, p0, pn, n, v.fit_out);
+  return SH_OK;
 }
 
-static int resect_all(sh_ctx* c, int P, int pc, int tmax, sh_resection* out, sh_head_fit* fit_out, const SeatArgs* seat = nullptr) {
+// face pass(es) and join of one pass
+static int resect_pass(sh_ctx* c, const ResectView& v, ResectLevel level, const ResectPass& s, sh_resection* one = nullptr, double* ring = nullptr) {
+  HIPCHK(c, hipMemsetAsync(v.segcnt, 0, (size_t)s.nb * s.pc * 4, c->stream));
+  const dim3 grid((unsigned)s.tmax, (unsigned)s.nb), block(SH_RS_TILE);
+  LAUNCH(c, "k_resect_faces", k_resect_faces, grid, block, v.verts, v.faces, v.voff, v.foff, (const double*)v.planes, s.P, s.p0, s.pc, s.b0, s.tmax, v.slab,
+         v.segcnt, v.segs);
+  if (level >= RS_FIT)
+    LAUNCH(c, "k_headfit_faces", k_headfit_faces, grid, block, v.verts, v.faces, v.voff, v.foff, (const double*)v.planes, s.P, s.p0, s.pc, s.b0, s.tmax,
+           v.fit_slab);
+  return launch_join(c, v, level, s, one, ring);
+}
+
+static int resect_run(sh_ctx* c, const ResectRequest& q) {
+  const std::string f(q.fn);
+  const int P = q.P;
+  if (!c || (!q.offs && !q.planes) || !q.out || (q.level >= RS_FIT && !q.fit_out) || P < 1 || P > 4096)
+    return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
+  if (q.level == RS_SEAT && !seat_args_ok(q.heads, q.K, q.mode, q.seat_out))
+    return fail(c, SH_ERR_ARG, f + ": bad catalogue (K in 1..64, 0 < thickness < 2 radius) or centre mode");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
   const size_t n = (size_t)c->B * P;
-  if (fit_out) {      // (a cut whose humerus' record failed writes neither: zeros)
-    HIPCHK(c, hipMemsetAsync(c->bufs["resect.fit_moments"].p, 0, n * 16 * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->bufs["resect.fit_ring"].p, 0, n * 8 * 8, c->stream));
-  }
-  const sh_landmarks* lm = resect_has_records(c) ? (const sh_landmarks*)c->bufs["landmarks"].p : (const sh_landmarks*)nullptr;
-  if (seat) HIPCHK(c, hipMemcpyAsync(c->bufs["resect.seat_heads"].p, seat->heads, (size_t)seat->K * sizeof(sh_implant_head), hipMemcpyHostToDevice, c->stream));
-  for (int p0 = 0; p0 < P; p0 += pc) {
-    const int pn = std::min(pc, P - p0), cuts = c->B * pn;
-    if (int rc = resect_pass(c, P, p0, pn, 0, c->B, tmax, false, fit_out != nullptr, seat != nullptr)) return rc;
-    if (seat) {      // the ring coordinates are the pass': its fits and its seats before the next pass overwrites them
-      LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((cuts + 63) / 64)), dim3(64), (const sh_resection*)c->bufs["resect.out"].p,
-             (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p, (const double*)c->bufs["resect.fit_ring"].p,
-             lm, P, p0, pn, cuts, (sh_head_fit*)c->bufs["resect.fit_out"].p);
-      LAUNCH(c, "k_seat", k_seat, dim3((unsigned)cuts), dim3(SH_SEAT_THREADS), (const sh_resection*)c->bufs["resect.out"].p,
-             (const sh_head_fit*)c->bufs["resect.fit_out"].p, (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p,
-             (const double*)c->bufs["resect.seat_ring"].p, lm, (const sh_implant_head*)c->bufs["resect.seat_heads"].p, seat->K, seat->mode, P, p0, pn,
-             (sh_seat*)c->bufs["resect.seat_out"].p);
+  if (q.offs) {
+    if (!resect_has_records(c)) return fail(c, SH_ERR_STATE, f + ": needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
+    static_assert(sizeof(sh_cut_offset) == 7 * sizeof(double), "sh_cut_offset is seven doubles");
+    for (int i = 0; i < 7 * P; ++i)
+      if (!std::isfinite(((const double*)q.offs)[i])) return fail(c, SH_ERR_ARG, f + ": non-finite offset");
+  } else {
+    for (size_t i = 0; i < n; ++i) {
+      const double* pl = q.planes + 6 * i;
+      bool fin = true;
+      for (int k = 0; k < 6; ++k) fin = fin && std::isfinite(pl[k]);
+      if (!fin || !((pl[3] * pl[3] + pl[4] * pl[4]) + pl[5] * pl[5] > 0.0)) return fail(c, SH_ERR_ARG, f + ": zero normal or non-finite plane");
     }
   }
-  HIPCHK(c, hipMemcpyAsync(out, c->bufs["resect.out"].p, n * sizeof(sh_resection), hipMemcpyDeviceToHost, c->stream));
-  if (fit_out) {
-    if (!seat)
-      LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((n + 63) / 64)), dim3(64), (const sh_resection*)c->bufs["resect.out"].p,
-             (const int*)c->bufs["resect.status"].p, (const double*)c->bufs["resect.fit_moments"].p, (const double*)c->bufs["resect.fit_ring"].p,
-             lm, P, 0, P, (int)n, (sh_head_fit*)c->bufs["resect.fit_out"].p);
-    HIPCHK(c, hipMemcpyAsync(fit_out, c->bufs["resect.fit_out"].p, n * sizeof(sh_head_fit), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipSetDevice(c->device));
+  int pc, tmax;
+  if (int rc = resect_ensure(c, q, &pc, &tmax)) return rc;
+  const ResectView v = resect_view(c);
+  c->resect_gen = ~0ull;
+  if (q.offs) {
+    HIPCHK(c, hipMemcpyAsync(v.offs, q.offs, (size_t)P * 56, hipMemcpyHostToDevice, c->stream));
+    LAUNCH(c, "k_resect_make_planes", k_resect_make_planes, dim3((unsigned)c->B), dim3(64), v.lm, (const double*)v.offs, P, v.planes, v.status);
+  } else {
+    HIPCHK(c, hipMemcpyAsync(v.planes, q.planes, n * 48, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(v.status, 0, n * 4, c->stream));
   }
-  if (seat) HIPCHK(c, hipMemcpyAsync(seat->out, c->bufs["resect.seat_out"].p, n * seat->K * sizeof(sh_seat), hipMemcpyDeviceToHost, c->stream));
+  if (q.level >= RS_FIT) {      // (a cut whose humerus' record failed writes neither: zeros)
+    HIPCHK(c, hipMemsetAsync(v.fit_moments, 0, n * 16 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(v.fit_ring, 0, n * 8 * 8, c->stream));
+  }
+  if (q.level == RS_SEAT) HIPCHK(c, hipMemcpyAsync(v.seat_heads, q.heads, (size_t)q.K * sizeof(sh_implant_head), hipMemcpyHostToDevice, c->stream));
+  for (int p0 = 0; p0 < P; p0 += pc) {
+    const int pn = std::min(pc, P - p0);
+    if (int rc = resect_pass(c, v, q.level, ResectPass{P, p0, pn, 0, c->B, tmax})) return rc;
+    if (q.level == RS_SEAT) {      // the ring coordinates are the pass': its fits and its seats before the next pass overwrites them
+      if (int rc = launch_solve(c, v, P, p0, pn)) return rc;
+      LAUNCH(c, "k_seat", k_seat, dim3((unsigned)(c->B * pn)), dim3(SH_SEAT_THREADS), (const sh_resection*)v.out, (const sh_head_fit*)v.fit_out,
+             (const int*)v.status, (const double*)v.fit_moments, (const double*)v.seat_ring, v.lm, (const sh_implant_head*)v.seat_heads, q.K, q.mode, P, p0, pn,
+             v.seat_out);
+    }
+  }
+  HIPCHK(c, hipMemcpyAsync(q.out, v.out, n * sizeof(sh_resection), hipMemcpyDeviceToHost, c->stream));
+  if (q.level >= RS_FIT) {
+    if (int rc = q.level == RS_FIT ? launch_solve(c, v, P, 0, P) : SH_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(q.fit_out, v.fit_out, n * sizeof(sh_head_fit), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (q.level == RS_SEAT) HIPCHK(c, hipMemcpyAsync(q.seat_out, v.seat_out, n * q.K * sizeof(sh_seat), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->resect_P = P; c->resect_gen = c->batch_gen;
   return SH_OK;
 }
 
-static int resect_planes_impl(sh_ctx* c, const char* fn, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out, bool fit,
-                              const SeatArgs* seat = nullptr) {
-  const std::string f(fn);
-  if (!c || !planes || !out || (fit && !fit_out) || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
-  if (seat && !seat_args_ok(seat->heads, seat->K, seat->mode, seat->out)) return fail(c, SH_ERR_ARG, f + ": bad catalogue (K in 1..64, 0 < thickness < 2 radius) or centre mode");
-  if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
-  const size_t n = (size_t)c->B * P;
-  for (size_t i = 0; i < n; ++i) {
-    const double* q = planes + 6 * i;
-    bool fin = true;
-    for (int k = 0; k < 6; ++k) fin = fin && std::isfinite(q[k]);
-    if (!fin || !((q[3] * q[3] + q[4] * q[4]) + q[5] * q[5] > 0.0)) return fail(c, SH_ERR_ARG, f + ": zero normal or non-finite plane");
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  int pc, tmax, rc;
-  if ((rc = resect_buffers(c, P, &pc, &tmax))) return rc;
-  if (fit && (rc = headfit_buffers(c, P, pc, tmax, &pc))) return rc;
-  if (seat && (rc = seat_buffers(c, P, pc, seat->K))) return rc;
-  c->resect_gen = ~0ull;
-  HIPCHK(c, hipMemcpyAsync(c->bufs["resect.planes"].p, planes, n * 48, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(c->bufs["resect.status"].p, 0, n * 4, c->stream));
-  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr, seat);
-}
-
-static int resect_offsets_impl(sh_ctx* c, const char* fn, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out, bool fit,
-                               const SeatArgs* seat = nullptr) {
-  const std::string f(fn);
-  if (!c || !offs || !out || (fit && !fit_out) || P < 1 || P > 4096) return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
-  if (seat && !seat_args_ok(seat->heads, seat->K, seat->mode, seat->out)) return fail(c, SH_ERR_ARG, f + ": bad catalogue (K in 1..64, 0 < thickness < 2 radius) or centre mode");
-  if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
-  if (!resect_has_records(c)) return fail(c, SH_ERR_STATE, f + ": needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
-  static_assert(sizeof(sh_cut_offset) == 7 * sizeof(double), "sh_cut_offset is seven doubles");
-  for (int i = 0; i < 7 * P; ++i)
-    if (!std::isfinite(((const double*)offs)[i])) return fail(c, SH_ERR_ARG, f + ": non-finite offset");
-  HIPCHK(c, hipSetDevice(c->device));
-  int pc, tmax, rc;
-  if ((rc = resect_buffers(c, P, &pc, &tmax))) return rc;
-  if (fit && (rc = headfit_buffers(c, P, pc, tmax, &pc))) return rc;
-  if (seat && (rc = seat_buffers(c, P, pc, seat->K))) return rc;
-  if ((rc = ensure(c, "resect.offs", (size_t)P * 56, 8))) return rc;
-  c->bufs["resect.offs"].per_mesh = 0;
-  c->resect_gen = ~0ull;
-  HIPCHK(c, hipMemcpyAsync(c->bufs["resect.offs"].p, offs, (size_t)P * 56, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_resect_make_planes", k_resect_make_planes, dim3((unsigned)c->B), dim3(64), (const sh_landmarks*)c->bufs["landmarks"].p,
-         (const double*)c->bufs["resect.offs"].p, P, (double*)c->bufs["resect.planes"].p, (int*)c->bufs["resect.status"].p);
-  return resect_all(c, P, pc, tmax, out, fit ? fit_out : nullptr, seat);
-}
-
-int sh_resect_planes(sh_ctx* c, const double* planes, int P, sh_resection* out) { return resect_planes_impl(c, "sh_resect_planes", planes, P, out, nullptr, false); }
-int sh_resect_offsets(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out) { return resect_offsets_impl(c, "sh_resect_offsets", offs, P, out, nullptr, false); }
+int sh_resect_planes(sh_ctx* c, const double* planes, int P, sh_resection* out) { return resect_run(c, ResectRequest{"sh_resect_planes", RS_RECORDS, planes, nullptr, P, out}); }
+int sh_resect_offsets(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out) { return resect_run(c, ResectRequest{"sh_resect_offsets", RS_RECORDS, nullptr, offs, P, out}); }
 int sh_resect_planes_fit(sh_ctx* c, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out) {
-  return resect_planes_impl(c, "sh_resect_planes_fit", planes, P, out, fit_out, true);
+  return resect_run(c, ResectRequest{"sh_resect_planes_fit", RS_FIT, planes, nullptr, P, out, fit_out});
 }
 int sh_resect_offsets_fit(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out) {
-  return resect_offsets_impl(c, "sh_resect_offsets_fit", offs, P, out, fit_out, true);
+  return resect_run(c, ResectRequest{"sh_resect_offsets_fit", RS_FIT, nullptr, offs, P, out, fit_out});
 }
-
 int sh_resect_planes_seat(sh_ctx* c, const double* planes, int P, const sh_implant_head* heads, int K, int center_mode, sh_resection* out,
                           sh_head_fit* fit_out, sh_seat* seat_out) {
-  const SeatArgs seat{heads, K, center_mode, seat_out};
-  return resect_planes_impl(c, "sh_resect_planes_seat", planes, P, out, fit_out, true, &seat);
+  return resect_run(c, ResectRequest{"sh_resect_planes_seat", RS_SEAT, planes, nullptr, P, out, fit_out, heads, K, center_mode, seat_out});
 }
 int sh_resect_offsets_seat(sh_ctx* c, const sh_cut_offset* offs, int P, const sh_implant_head* heads, int K, int center_mode, sh_resection* out,
                            sh_head_fit* fit_out, sh_seat* seat_out) {
-  const SeatArgs seat{heads, K, center_mode, seat_out};
-  return resect_offsets_impl(c, "sh_resect_offsets_seat", offs, P, out, fit_out, true, &seat);
+  return resect_run(c, ResectRequest{"sh_resect_offsets_seat", RS_SEAT, nullptr, offs, P, out, fit_out, heads, K, center_mode, seat_out});
 }
 
 int sh_resect_ring(sh_ctx* c, int b, int p, double* out, int cap, int* n_out) {
@@ -1005,14 +1004,15 @@ int sh_resect_ring(sh_ctx* c, int b, int p, double* out, int cap, int* n_out) {
   HIPCHK(c, hipSetDevice(c->device));
   const long long nf = c->h_foff[b + 1] - c->h_foff[b];
   const int tiles = (int)std::max<long long>(1, (nf + SH_RS_TILE - 1) / SH_RS_TILE);
-  if (int rc = resect_pass(c, c->resect_P, p, 1, b, 1, tiles, true)) return rc;
+  const ResectView v = resect_view(c);
+  if (int rc = resect_pass(c, v, RS_RECORDS, ResectPass{c->resect_P, p, 1, b, 1, tiles}, v.one, v.ring)) return rc;
   sh_resection r;
-  HIPCHK(c, hipMemcpyAsync(&r, c->bufs["resect.one"].p, sizeof r, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&r, v.one, sizeof r, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (r.status != 0 || r.n_loops < 1) { *n_out = 0; return SH_OK; }
   *n_out = r.n_ring + 1;
   if (!out || cap < r.n_ring + 1) return SH_OK;
-  HIPCHK(c, hipMemcpy(out, c->bufs["resect.ring"].p, (size_t)(r.n_ring + 1) * 24, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(out, v.ring, (size_t)(r.n_ring + 1) * 24, hipMemcpyDeviceToHost));
   return SH_OK;
 }
 

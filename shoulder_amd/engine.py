@@ -457,44 +457,36 @@ class Engine:
             hd = np.ascontiguousarray(np.asarray(heads, dtype=np.float64).reshape(-1, 2))
             mode = _lib.SEAT_SPHERE_AXIS if seat_center == "sphere" else _lib.SEAT_CUT_CENTROID
         if planes is not None:
-            pl = np.ascontiguousarray(planes, dtype=np.float64)
-            if pl.ndim < 2 or pl.shape[0] != B or pl.size % (6 * max(B, 1)) or pl.size == 0:
+            src = np.ascontiguousarray(planes, dtype=np.float64)
+            if src.ndim < 2 or src.shape[0] != B or src.size % (6 * max(B, 1)) or src.size == 0:
                 raise ValueError("planes must have shape (B, P, 6)")
-            P = pl.size // (6 * B)
-            out = np.zeros((B, P), dtype=_lib.RESECTION_DTYPE)
-            if fit:
-                fits = np.zeros((B, P), dtype=_lib.HEAD_FIT_DTYPE)
-                if hd is not None:
-                    seats = np.zeros((B, P, len(hd)), dtype=_lib.SEAT_DTYPE)
-                    self._chk(self.L.sh_resect_planes_seat(self.h, _ptr(pl), P, _ptr(hd), len(hd), mode, _ptr(out), _ptr(fits), _ptr(seats)))
-                    return out, fits, seats
-                self._chk(self.L.sh_resect_planes_fit(self.h, _ptr(pl), P, _ptr(out), _ptr(fits)))
-                return out, fits
-            self._chk(self.L.sh_resect_planes(self.h, _ptr(pl), P, _ptr(out)))
-            return out
-        if isinstance(offsets, np.ndarray) and offsets.dtype.names:
-            off = np.zeros(offsets.shape, dtype=_lib.CUT_OFFSET_DTYPE).reshape(-1)
-            for n in offsets.dtype.names:
-                off[n] = offsets[n].reshape(-1)      # (an unknown field name raises)
+            P = src.size // (6 * B)
         else:
-            offsets = list(offsets)
-            off = np.zeros(len(offsets), dtype=_lib.CUT_OFFSET_DTYPE)
-            for i, d in enumerate(offsets):
-                for k, v in dict(d).items():
-                    off[k][i] = v
-        if len(off) == 0:
-            raise ValueError("at least one offset")
-        out = np.zeros((B, len(off)), dtype=_lib.RESECTION_DTYPE)
-        if fit:
-            fits = np.zeros((B, len(off)), dtype=_lib.HEAD_FIT_DTYPE)
-            if hd is not None:
-                seats = np.zeros((B, len(off), len(hd)), dtype=_lib.SEAT_DTYPE)
-                self._chk(self.L.sh_resect_offsets_seat(self.h, _ptr(off), len(off), _ptr(hd), len(hd), mode, _ptr(out), _ptr(fits), _ptr(seats)))
-                return out, fits, seats
-            self._chk(self.L.sh_resect_offsets_fit(self.h, _ptr(off), len(off), _ptr(out), _ptr(fits)))
-            return out, fits
-        self._chk(self.L.sh_resect_offsets(self.h, _ptr(off), len(off), _ptr(out)))
-        return out
+            if isinstance(offsets, np.ndarray) and offsets.dtype.names:
+                src = np.zeros(offsets.shape, dtype=_lib.CUT_OFFSET_DTYPE).reshape(-1)
+                for n in offsets.dtype.names:
+                    src[n] = offsets[n].reshape(-1)      # (an unknown field name raises)
+            else:
+                offsets = list(offsets)
+                src = np.zeros(len(offsets), dtype=_lib.CUT_OFFSET_DTYPE)
+                for i, d in enumerate(offsets):
+                    for k, v in dict(d).items():
+                        src[k][i] = v
+            P = len(src)
+            if P == 0:
+                raise ValueError("at least one offset")
+        level = "seat" if hd is not None else ("fit" if fit else "records")
+        res = [np.zeros((B, P), dtype=_lib.RESECTION_DTYPE)]
+        if level != "records":
+            res.append(np.zeros((B, P), dtype=_lib.HEAD_FIT_DTYPE))
+        if level == "seat":
+            res.append(np.zeros((B, P, len(hd)), dtype=_lib.SEAT_DTYPE))
+        fn = {("planes", "records"): self.L.sh_resect_planes, ("offsets", "records"): self.L.sh_resect_offsets,
+              ("planes", "fit"): self.L.sh_resect_planes_fit, ("offsets", "fit"): self.L.sh_resect_offsets_fit,
+              ("planes", "seat"): self.L.sh_resect_planes_seat, ("offsets", "seat"): self.L.sh_resect_offsets_seat}
+        catalogue = (_ptr(hd), len(hd), mode) if level == "seat" else ()
+        self._chk(fn["planes" if planes is not None else "offsets", level](self.h, _ptr(src), P, *catalogue, *(_ptr(a) for a in res)))
+        return res[0] if level == "records" else tuple(res)
 
     def resect_ring(self, b, p):
         """The largest loop of cut p of humerus b of the last resect(): (n + 1, 3) float64 in CT, closed, counter-clockwise seen
