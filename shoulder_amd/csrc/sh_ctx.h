@@ -5,6 +5,8 @@
 //   hull.hip          hull prefilter, host hull phase and its worker pool, device hull      (k_hullpre.h, k_hull.h)
 //   unet.hip          the UNet runners, UNet turns, sh_unet_infer                          (k_unet*.h; unet16_pp.hip: k_unet16_pp.h)
 //   comm.hip          the RCCL collectives
+// Kernel-free and HIP-free beside it (a plain g++ compiles them for the host tests): sh_demand.h (a run's capacity demands and the
+// verdict on them), sh_ingest.h (what mesh ingest checks and plans on the host before a batch becomes resident).
 #pragma once
 #include "../../include/shoulder_hip.h"
 
@@ -22,6 +24,7 @@
 #include <functional>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -30,6 +33,7 @@
 
 #include "sh_demand.h"
 #include "sh_hullcap.h"
+#include "sh_ingest.h"
 
 // ---------------------------------------------------------------------------------------------
 struct Buf {
@@ -109,7 +113,7 @@ struct sh_ctx {
                    std::vector<long long> off;            // first point of humerus b in src
                    std::vector<int> cnt; };               // points of humerus b in src
   HullPts hull_in;                           // ... of the resident batch
-  long long* h_koff = nullptr;               // pinned: offsets of the survivors (B + 1)
+  long long* h_koff = nullptr; int h_koff_cap = 0;      // pinned: offsets of the survivors (B + 1)
   // The STAGING SIDE of the mesh slot (sh_stage_meshes / sh_stage_stl / sh_commit_staged): the next batch is copied into buffers of
   // its own ("verts.s", "faces.s", "voff.s", "foff.s") on the copy stream while a run of the resident batch executes, its hull
   // points come back through a prefilter scratch of its own ("hullpre.*.s") and its hulls are computed by the background thread

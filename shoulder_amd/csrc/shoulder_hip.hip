@@ -143,6 +143,39 @@ static int hull_mode_from(const char* e) {
   return threads_per_local_rank() >= (alone ? 16u : 48u) ? 0 : 1;
 }
 
+// A page-locked block of the context that holds `need` elements of `bytes_per` bytes: kept when it does, else freed and allocated
+// anew with `extra` elements of headroom.  A failure leaves it empty.
+template <typename T, typename N>
+static int grow_pinned(sh_ctx* c, T** p, N* cap, size_t need, size_t bytes_per, size_t extra = 0) {
+  if ((size_t)*cap >= need) return SH_OK;
+  if (*p) (void)hipHostFree(*p);
+  *p = nullptr; *cap = 0;
+  HIPCHK(c, hipHostMalloc((void**)p, (need + extra) * bytes_per));
+  *cap = (N)(need + extra);
+  return SH_OK;
+}
+
+// The n pieces of a copy dealt to SH_COPY_THREADS threads of their own (the caller is one; the hull pool's workers may all be inside
+// another lane's hull phase): fn(k) copies piece k into page-locked memory and enqueues its H2D copy at once, so the PCIe transfer
+// runs behind the memcpy instead of after it.  -> the last error of a piece.
+#define SH_COPY_THREADS 4
+template <typename F>
+static hipError_t copy_pool(size_t n, F fn) {
+  std::atomic<size_t> next(0);
+  std::atomic<int> err((int)hipSuccess);
+  auto work = [&]() {
+    for (size_t k; (k = next.fetch_add(1)) < n;) {
+      const hipError_t e = fn(k);
+      if (e != hipSuccess) err.store((int)e);
+    }
+  };
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < SH_COPY_THREADS && t < n; ++t) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+  return (hipError_t)err.load();
+}
+
 extern "C" {
 
 int sh_set_hull_mode(sh_ctx* c, const char* mode) {
@@ -337,20 +370,9 @@ static int alloc_batch(sh_ctx* c) {
   ENS("hull.nf", (size_t)B * 4, 4);
   ENS("hull.ne", (size_t)B * 4, 4);
   if ((rc = alloc_hullpre(c, B, c->sumV, "")) != SH_OK) return rc;
-  if (c->h_kept_cap < c->sumV) {
-    if (c->h_kept) (void)hipHostFree(c->h_kept);
-    c->h_kept = nullptr; c->h_kept_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_kept, (size_t)c->sumV * 12));
-    c->h_kept_cap = c->sumV;
-  }
-  if (c->h_nkept_cap < B) {
-    if (c->h_nkept) (void)hipHostFree(c->h_nkept);
-    if (c->h_koff) (void)hipHostFree(c->h_koff);
-    c->h_nkept = nullptr; c->h_koff = nullptr; c->h_nkept_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->h_nkept, (size_t)B * 4));
-    HIPCHK(c, hipHostMalloc((void**)&c->h_koff, (size_t)(B + 1) * 8));
-    c->h_nkept_cap = B;
-  }
+  if ((rc = grow_pinned(c, &c->h_kept, &c->h_kept_cap, (size_t)c->sumV, 12)) != SH_OK) return rc;
+  if ((rc = grow_pinned(c, &c->h_nkept, &c->h_nkept_cap, (size_t)B, 4)) != SH_OK) return rc;
+  if ((rc = grow_pinned(c, &c->h_koff, &c->h_koff_cap, (size_t)B + 1, 8)) != SH_OK) return rc;
   ENS("obb.cand_vol", (size_t)B * c->hcap.f * 8, 8);
   ENS("obb.cand_edge", (size_t)B * c->hcap.f * 4, 4);
   ENS("obb.best_enc", (size_t)B * 8, 8);
@@ -390,43 +412,109 @@ static int alloc_prox(sh_ctx* c) {
   return SH_OK;
 }
 
+// ---- ingest: one STL scratch view, one parse chain, one commit (the decisions are sh_ingest.h's) ---------------------------------
+// the eleven stl.* scratch buffers of a plan as typed device pointers, resolved once
+struct StlView { unsigned char* raw; long long *file_off, *coff; float* corners; int2* table; int *slot, *vid, *fpos, *counts, *bsum, *nonfinite; };
+
+static int stl_scratch(sh_ctx* c, int B, const StlPlan& p, StlView* v) {
+  int rc;
+  ENS_SHARED("stl.raw", (size_t)p.file_off[B], 1);
+  ENS_SHARED("stl.file_off", (B + 1) * 8, 8);
+  ENS_SHARED("stl.coff", (B + 1) * 8, 8);
+  ENS_SHARED("stl.corners", (size_t)p.sumC * 12, 4);
+  ENS_SHARED("stl.table", (size_t)B * p.tsize * 8, 4);
+  ENS_SHARED("stl.slot", (size_t)p.sumC * 4, 4);
+  ENS_SHARED("stl.vid", (size_t)p.sumC * 4, 4);
+  ENS_SHARED("stl.fpos", (size_t)(p.sumC / 3) * 4, 4);
+  ENS_SHARED("stl.counts", (size_t)B * 8, 4);
+  ENS_SHARED("stl.bsum", stl_rank_scratch_ints(B, p.maxc) * 4, 4);
+  ENS_SHARED("stl.nonfinite", (size_t)B * 4, 4);
+  auto at = [c](const char* name) { return c->bufs[name].p; };
+  *v = StlView{(unsigned char*)at("stl.raw"), (long long*)at("stl.file_off"), (long long*)at("stl.coff"), (float*)at("stl.corners"), (int2*)at("stl.table"), (int*)at("stl.slot"),
+               (int*)at("stl.vid"), (int*)at("stl.fpos"), (int*)at("stl.counts"), (int*)at("stl.bsum"), (int*)at("stl.nonfinite")};
+  return SH_OK;
+}
+
+// A launch of the parse chain on stream `st`.  `timed` = the context whose stream `st` is (sh_upload_stl): the launch goes through
+// LAUNCH_FN, so with timing on it is recorded under its name; null (the staged batch's thread, on the copy stream): a bare launch that
+// touches nothing of the context -- `pending` belongs to the caller's thread -- and whose error the enqueueing function collects once.
+#define STL_LAUNCH(name, kernel, grid, ...)                                                                          \
+  do {                                                                                                               \
+    if (timed) LAUNCH_FN(timed, name, hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, __VA_ARGS__));              \
+    else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, __VA_ARGS__);                                            \
+  } while (0)
+static dim3 stl_corner_grid(int B, const StlPlan& p) { return dim3((unsigned)std::min<long long>((p.maxc + 255) / 256, 1024), (unsigned)B); }
+
+// raw files -> corners -> hash table -> ranks: afterwards "stl.counts" holds the merged sizes and "stl.nonfinite" the NaN / inf words
+static int stl_enqueue_parse(sh_ctx* timed, hipStream_t st, int B, const StlPlan& p, const StlView& v, std::string* et) {
+  HIPCHK_TXT(et, hipMemsetAsync(v.nonfinite, 0, (size_t)B * 4, st));
+  const dim3 gc = stl_corner_grid(B, p);
+  STL_LAUNCH("k_stl_corners", k_stl_corners, gc, (const unsigned char*)v.raw, (const long long*)v.file_off, (const long long*)v.coff, v.corners, v.nonfinite);
+  STL_LAUNCH("k_stl_table_init", k_stl_table_init, dim3(1024), v.table, (size_t)B * p.tsize);
+  STL_LAUNCH("k_stl_hash", k_stl_hash, gc, (const float*)v.corners, (const long long*)v.coff, v.table, p.tsize, v.slot);
+  stl_rank_launch(st, B, p.maxc, v.coff, v.table, p.tsize, v.slot, v.vid, v.fpos, v.counts, v.bsum);
+  HIPCHK_TXT(et, hipGetLastError());
+  return SH_OK;
+}
+
+// the merged meshes to their batch offsets (already on the device behind voff / foff)
+static int stl_enqueue_emit(sh_ctx* timed, hipStream_t st, int B, const StlPlan& p, const StlView& v, const long long* voff, const long long* foff, float* verts, int* faces, std::string* et) {
+  STL_LAUNCH("k_stl_emit", k_stl_emit, stl_corner_grid(B, p), (const float*)v.corners, (const long long*)v.coff, (const int2*)v.table, p.tsize, (const int*)v.slot,
+             (const int*)v.vid, (const int*)v.fpos, voff, foff, verts, faces);
+  HIPCHK_TXT(et, hipGetLastError());
+  return SH_OK;
+}
+#undef STL_LAUNCH
+
+// Where the meshes of a batch that becomes resident are: host arrays to upload (sh_upload_meshes) | `fill` writes "verts" / "faces" on
+// the context's stream once they and the offsets are in place (STL, synth) | `staged`: the ".s" side holds them, swap it in.
+struct ResidentSource { const float* verts = nullptr; const int32_t* faces = nullptr; std::function<int()> fill; bool staged = false; };
+
+// The commit of every way in.  voff / foff are swapped into the context.  A failure behind `c->B = 0` leaves "no meshes uploaded",
+// never a half-committed batch; h_verts_valid only for host arrays (else the hull stage downloads the vertices).
+static int make_resident(sh_ctx* c, int B, const MeshSizes& sz, std::vector<long long>& voff, std::vector<long long>& foff, const ResidentSource& src) {
+  static const char* const names[4] = {"verts", "faces", "voff", "foff"};
+  if (src.staged) for (const char* nm : names) std::swap(c->bufs[nm], c->bufs[std::string(nm) + ".s"]);      // (the staged batch's own thread keeps running)
+  else { discard_staged(c); (void)join_prepared(c); }      // (sh_upload_stl dropped a staged batch already, before it took the stl.* scratch: nothing left to do for it here)
+  ++c->batch_gen;      // hulls prepared for the previous batch are void
+  c->B = 0;
+  c->h_voff.swap(voff); c->h_foff.swap(foff);
+  c->sumV = sz.sumV; c->sumF = sz.sumF; c->maxV = sz.maxV; c->maxF = sz.maxF;
+  c->h_verts_valid = src.verts != nullptr;
+  if (src.verts) c->h_verts.assign(src.verts, src.verts + 3 * sz.sumV);
+  int rc;
+  if (!src.staged) {
+    const size_t nb[4] = {(size_t)sz.sumV * 12, (size_t)sz.sumF * 12, (size_t)(B + 1) * 8, (size_t)(B + 1) * 8};
+    for (int k = 0; k < 4; ++k) if ((rc = ensure(c, names[k], nb[k], k < 2 ? 4 : 8)) != SH_OK) return rc;
+    if (src.verts) {
+      HIPCHK(c, hipMemcpyAsync(c->bufs["verts"].p, src.verts, nb[0], hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->bufs["faces"].p, src.faces, nb[1], hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(c->bufs["voff"].p, c->h_voff.data(), nb[2], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->bufs["foff"].p, c->h_foff.data(), nb[3], hipMemcpyHostToDevice, c->stream));
+    if (src.fill && (rc = src.fill()) != SH_OK) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  for (const char* nm : {"verts", "faces", "verts.s", "faces.s", "voff.s", "foff.s"}) { auto it = c->bufs.find(nm); if (it != c->bufs.end()) it->second.per_mesh = 0; }
+  c->B = B;
+  if ((rc = alloc_batch(c)) != SH_OK) c->B = 0;      // (voff / foff get their window stride there)
+  return rc;
+}
+
+static int ingest_fail(sh_ctx* c, const char* entry, const IngestError& e) { return fail(c, e.code, std::string(entry) + ": " + e.text); }
+static void offsets_out(const std::vector<long long>& off, int64_t* out) { if (out) std::copy(off.begin(), off.end(), out); }
+
 int sh_upload_meshes(sh_ctx* c, const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int B) {
   if (!c || !verts || !faces || !v_off || !f_off || B <= 0) return fail(c, SH_ERR_ARG, "sh_upload_meshes: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
   // Validate first, into locals: a rejected upload leaves the resident batch (B, offsets, device buffers) untouched.
-  if (v_off[0] != 0 || f_off[0] != 0) return fail(c, SH_ERR_ARG, "sh_upload_meshes: offsets must start at 0");
-  long long maxV = 0, maxF = 0;
-  for (int b = 0; b < B; ++b) {
-    long long nv = v_off[b + 1] - v_off[b], nf = f_off[b + 1] - f_off[b];
-    if (nv < 4 || nf < 4) return fail(c, SH_ERR_ARG, "sh_upload_meshes: a mesh has fewer than 4 vertices/faces");
-    if (nv > 0x7fffffffLL / 3 || nf > 0x7fffffffLL / 3) return fail(c, SH_ERR_ARG, "sh_upload_meshes: a mesh is too large");
-    maxV = std::max(maxV, nv); maxF = std::max(maxF, nf);
-    for (long long i = 3 * f_off[b]; i < 3 * f_off[b + 1]; ++i)
-      if (faces[i] < 0 || faces[i] >= nv) return fail(c, SH_ERR_ARG, "sh_upload_meshes: face index out of range");
-  }
-  const long long sumV = v_off[B], sumF = f_off[B];
-  for (long long i = 0; i < 3 * sumV; ++i)
-    if (!std::isfinite(verts[i])) return fail(c, SH_ERR_ARG, "sh_upload_meshes: NaN / infinite vertex coordinate");
-  discard_staged(c); (void)join_prepared(c); ++c->batch_gen;      // hulls prepared for the previous batch are void
-  c->B = 0;                                     // (a HIP / allocation failure below leaves "no meshes uploaded", never a half-committed batch)
-  c->h_voff.assign(v_off, v_off + B + 1);
-  c->h_foff.assign(f_off, f_off + B + 1);
-  c->sumV = sumV; c->sumF = sumF; c->maxV = maxV; c->maxF = maxF;
-  c->h_verts.assign(verts, verts + 3 * c->sumV);
-  c->h_verts_valid = true;
-  int rc;
-  if ((rc = ensure(c, "verts", c->sumV * 3 * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "faces", c->sumF * 3 * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "voff", (B + 1) * 8, 8)) != SH_OK) return rc;
-  if ((rc = ensure(c, "foff", (B + 1) * 8, 8)) != SH_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(buf<float>(c, "verts"), verts, c->sumV * 3 * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<int>(c, "faces"), faces, c->sumF * 3 * 4, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "voff"), c->h_voff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "foff"), c->h_foff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->B = B;
-  if ((rc = alloc_batch(c)) != SH_OK) c->B = 0;
-  return rc;
+  MeshSizes sz;
+  const IngestError e = check_mesh_arrays(v_off, f_off, B, faces, verts, &sz);
+  if (e.code != SH_OK) return ingest_fail(c, "sh_upload_meshes", e);
+  std::vector<long long> voff(v_off, v_off + B + 1), foff(f_off, f_off + B + 1);
+  ResidentSource src;
+  src.verts = verts; src.faces = faces;
+  return make_resident(c, B, sz, voff, foff, src);
 }
 
 // Binary STL files -> merged meshes, on the device (k_stl.h; replaces `trimesh.load_mesh(stl)` of mesh.py:22-27 incl. the
@@ -435,92 +523,37 @@ int sh_upload_stl(sh_ctx* c, const void* const* files, const size_t* nbytes, int
   if (!c || !files || !nbytes || B <= 0) return fail(c, SH_ERR_ARG, "sh_upload_stl: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
   discard_staged(c);      // (a staged STL batch works in the same stl.* scratch)
-  std::vector<long long> file_off(B + 1, 0), coff(B + 1, 0);
-  long long maxc = 0;
-  for (int b = 0; b < B; ++b) {
-    if (!files[b] || nbytes[b] < 84) return fail(c, SH_ERR_ARG, "sh_upload_stl: a file is too short for a binary STL");
-    uint32_t nt;
-    memcpy(&nt, (const char*)files[b] + 80, 4);
-    if (nbytes[b] != 84 + 50ull * nt) return fail(c, SH_ERR_ARG, "sh_upload_stl: not a binary STL (size does not match the triangle count)");
-    if (nt < 4 || nt > 0x7fffffffu / 3) return fail(c, SH_ERR_ARG, "sh_upload_stl: a mesh has fewer than 4 (or too many) triangles");
-    file_off[b + 1] = file_off[b] + (long long)((nbytes[b] + 3) & ~(size_t)3);
-    coff[b + 1] = coff[b] + 3ll * nt;
-    maxc = std::max(maxc, 3ll * nt);
-  }
-  int tsize = 1024;
-  while (tsize < 2 * maxc) tsize <<= 1;
-  const long long sumC = coff[B];
+  StlPlan plan;
+  IngestError e = stl_plan(files, nbytes, B, &plan);
+  if (e.code != SH_OK) return ingest_fail(c, "sh_upload_stl", e);
+  StlView v;
   int rc;
-  if ((rc = ensure(c, "stl.raw", (size_t)file_off[B], 1)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.file_off", (B + 1) * 8, 8)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.coff", (B + 1) * 8, 8)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.corners", (size_t)sumC * 12, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.table", (size_t)B * tsize * 8, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.slot", (size_t)sumC * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.vid", (size_t)sumC * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.fpos", (size_t)(sumC / 3) * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.counts", (size_t)B * 8, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "stl.bsum", stl_rank_scratch_ints(B, maxc) * 4, 4)) != SH_OK) return rc;
-  c->bufs["stl.bsum"].per_mesh = 0;
-  if ((rc = ensure(c, "stl.nonfinite", (size_t)B * 4, 4)) != SH_OK) return rc;
-  c->bufs["stl.nonfinite"].per_mesh = 0;
-  HIPCHK(c, hipMemsetAsync(c->bufs["stl.nonfinite"].p, 0, (size_t)B * 4, c->stream));
-  for (const char* nm : {"stl.raw", "stl.file_off", "stl.coff", "stl.corners", "stl.table", "stl.slot", "stl.vid", "stl.fpos", "stl.counts"}) c->bufs[nm].per_mesh = 0;
-  c->b0 = 0;
-  unsigned char* raw = buf<unsigned char>(c, "stl.raw");
-  for (int b = 0; b < B; ++b) HIPCHK(c, hipMemcpyAsync(raw + file_off[b], files[b], nbytes[b], hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "stl.file_off"), file_off.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "stl.coff"), coff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  const dim3 gc((unsigned)std::min<long long>((maxc + 255) / 256, 1024), (unsigned)B);
-  LAUNCH(c, "k_stl_corners", k_stl_corners, gc, dim3(256), raw, buf<long long>(c, "stl.file_off"), buf<long long>(c, "stl.coff"), buf<float>(c, "stl.corners"), (int*)c->bufs["stl.nonfinite"].p);
-  LAUNCH(c, "k_stl_table_init", k_stl_table_init, dim3(1024), dim3(256), buf<int2>(c, "stl.table"), (size_t)B * tsize);
-  LAUNCH(c, "k_stl_hash", k_stl_hash, gc, dim3(256), buf<float>(c, "stl.corners"), buf<long long>(c, "stl.coff"), buf<int2>(c, "stl.table"), tsize, buf<int>(c, "stl.slot"));
-  stl_rank_launch(c->stream, B, maxc, buf<long long>(c, "stl.coff"), buf<int2>(c, "stl.table"), tsize, buf<int>(c, "stl.slot"), buf<int>(c, "stl.vid"), buf<int>(c, "stl.fpos"),
-                  buf<int>(c, "stl.counts"), buf<int>(c, "stl.bsum"));
-  HIPCHK(c, hipGetLastError());
+  if ((rc = stl_scratch(c, B, plan, &v)) != SH_OK) return rc;
+  for (int b = 0; b < B; ++b) HIPCHK(c, hipMemcpyAsync(v.raw + plan.file_off[b], files[b], nbytes[b], hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(v.file_off, plan.file_off.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(v.coff, plan.coff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  if ((rc = stl_enqueue_parse(c, c->stream, B, plan, v, &c->err)) != SH_OK) return rc;
   std::vector<int> counts(2 * B), nonfin(B);
-  HIPCHK(c, hipMemcpyAsync(counts.data(), buf<int>(c, "stl.counts"), (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(nonfin.data(), c->bufs["stl.nonfinite"].p, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(counts.data(), v.counts, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(nonfin.data(), v.nonfinite, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // Validate into locals: a rejected file set leaves the resident batch (B, offsets, "verts" / "faces") untouched -- only
   // the stl.* scratch buffers were written so far.
-  std::vector<long long> n_voff(B + 1, 0), n_foff(B + 1, 0);
-  long long maxV = 0, maxF = 0;
-  for (int b = 0; b < B; ++b) {
-    if (nonfin[b]) return fail(c, SH_ERR_ARG, "sh_upload_stl: a file holds NaN / infinite coordinates");
-    if (counts[2 * b] < 4 || counts[2 * b + 1] < 4) return fail(c, SH_ERR_ARG, "sh_upload_stl: a mesh has fewer than 4 vertices/faces after merging");
-    n_voff[b + 1] = n_voff[b] + counts[2 * b];
-    n_foff[b + 1] = n_foff[b] + counts[2 * b + 1];
-    maxV = std::max<long long>(maxV, counts[2 * b]); maxF = std::max<long long>(maxF, counts[2 * b + 1]);
-  }
-  discard_staged(c); (void)join_prepared(c); ++c->batch_gen;
-  c->B = 0;                        // (a HIP / allocation failure below leaves "no meshes uploaded")
-  c->h_voff.swap(n_voff); c->h_foff.swap(n_foff);
-  c->maxV = maxV; c->maxF = maxF;
-  c->sumV = c->h_voff[B]; c->sumF = c->h_foff[B];
-  c->h_verts_valid = false;      // the hull stage downloads the merged vertices (as for a device-generated batch)
-  if ((rc = ensure(c, "verts", c->sumV * 3 * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "faces", c->sumF * 3 * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "voff", (B + 1) * 8, 8)) != SH_OK) return rc;
-  if ((rc = ensure(c, "foff", (B + 1) * 8, 8)) != SH_OK) return rc;
-  c->bufs["verts"].per_mesh = 0; c->bufs["faces"].per_mesh = 0;
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "voff"), c->h_voff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "foff"), c->h_foff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_stl_emit", k_stl_emit, gc, dim3(256), buf<float>(c, "stl.corners"), buf<long long>(c, "stl.coff"), buf<int2>(c, "stl.table"), tsize, buf<int>(c, "stl.slot"),
-         buf<int>(c, "stl.vid"), buf<int>(c, "stl.fpos"), buf<long long>(c, "voff"), buf<long long>(c, "foff"), buf<float>(c, "verts"), buf<int>(c, "faces"));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (v_off_out) for (int b = 0; b <= B; ++b) v_off_out[b] = c->h_voff[b];
-  if (f_off_out) for (int b = 0; b <= B; ++b) f_off_out[b] = c->h_foff[b];
-  c->B = B;
-  if ((rc = alloc_batch(c)) != SH_OK) c->B = 0;
-  return rc;
+  std::vector<long long> voff, foff;
+  MeshSizes sz;
+  e = stl_counted(counts.data(), nonfin.data(), B, &voff, &foff, &sz);
+  if (e.code != SH_OK) return ingest_fail(c, "sh_upload_stl", e);
+  ResidentSource src;
+  src.fill = [&]() -> int { return stl_enqueue_emit(c, c->stream, B, plan, v, (const long long*)c->bufs["voff"].p, (const long long*)c->bufs["foff"].p, (float*)c->bufs["verts"].p, (int*)c->bufs["faces"].p, &c->err); };
+  if ((rc = make_resident(c, B, sz, voff, foff, src)) != SH_OK) return rc;
+  offsets_out(c->h_voff, v_off_out); offsets_out(c->h_foff, f_off_out);
+  return SH_OK;
 }
 
 int sh_synth_batch(sh_ctx* c, const double* T, int B) {
   if (!c || !T || B <= 0) return fail(c, SH_ERR_ARG, "sh_synth_batch: bad argument");
   if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_synth_batch: upload a template mesh first");
   HIPCHK(c, hipSetDevice(c->device));
-  discard_staged(c); (void)join_prepared(c); ++c->batch_gen;
   const long long V = c->h_voff[1] - c->h_voff[0], F = c->h_foff[1] - c->h_foff[0];
   // keep the template aside
   int rc;
@@ -529,26 +562,21 @@ int sh_synth_batch(sh_ctx* c, const double* T, int B) {
   HIPCHK(c, hipMemcpyAsync(buf<float>(c, "tmpl_verts"), buf<float>(c, "verts") + 3 * c->h_voff[0], V * 3 * 4, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(buf<int>(c, "tmpl_faces"), buf<int>(c, "faces") + 3 * c->h_foff[0], F * 3 * 4, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->B = 0;                        // (a failure below leaves "no meshes uploaded", never a half-committed batch)
-  c->h_verts_valid = false;
-  c->sumV = V * B; c->sumF = F * B; c->maxV = V; c->maxF = F;
-  c->h_voff.resize(B + 1); c->h_foff.resize(B + 1);
-  for (int b = 0; b <= B; ++b) { c->h_voff[b] = V * b; c->h_foff[b] = F * b; }
-  if ((rc = ensure(c, "verts", c->sumV * 3 * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "faces", c->sumF * 3 * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "voff", (B + 1) * 8, 8)) != SH_OK) return rc;
-  if ((rc = ensure(c, "foff", (B + 1) * 8, 8)) != SH_OK) return rc;
-  if ((rc = ensure(c, "synth_T", B * 16 * 8, 8)) != SH_OK) return rc;
-  HIPCHK(c, hipMemcpyAsync(buf<double>(c, "synth_T"), T, B * 16 * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "voff"), c->h_voff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(buf<long long>(c, "foff"), c->h_foff.data(), (B + 1) * 8, hipMemcpyHostToDevice, c->stream));
-  dim3 grid((unsigned)((V + 255) / 256), (unsigned)B);
-  LAUNCH(c, "k_synth_batch", k_synth_batch, grid, dim3(256), buf<float>(c, "tmpl_verts"), buf<int>(c, "tmpl_faces"),
-         (long long)V, (long long)F, buf<double>(c, "synth_T"), buf<float>(c, "verts"), buf<int>(c, "faces"));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->B = B;
-  if ((rc = alloc_batch(c)) != SH_OK) c->B = 0;
-  return rc;
+  std::vector<long long> voff(B + 1), foff(B + 1);
+  for (int b = 0; b <= B; ++b) { voff[b] = V * b; foff[b] = F * b; }
+  MeshSizes sz;
+  sz.sumV = V * B; sz.sumF = F * B; sz.maxV = V; sz.maxF = F;
+  ResidentSource src;
+  src.fill = [&]() -> int {
+    int rc;
+    if ((rc = ensure(c, "synth_T", B * 16 * 8, 8)) != SH_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(buf<double>(c, "synth_T"), T, B * 16 * 8, hipMemcpyHostToDevice, c->stream));
+    dim3 grid((unsigned)((V + 255) / 256), (unsigned)B);
+    LAUNCH(c, "k_synth_batch", k_synth_batch, grid, dim3(256), buf<float>(c, "tmpl_verts"), buf<int>(c, "tmpl_faces"),
+           (long long)V, (long long)F, buf<double>(c, "synth_T"), buf<float>(c, "verts"), buf<int>(c, "faces"));
+    return SH_OK;
+  };
+  return make_resident(c, B, sz, voff, foff, src);
 }
 
 // ---- named buffers -----------------------------------------------------------------------------
@@ -1613,31 +1641,14 @@ __global__ void k_anp_points_ct(const double* __restrict__ pts_obb, const double
 // One batch can be staged at a time; commit needs the context idle (sh_collect first): the buffers that become the staging side
 // are the ones the collected run read.  A rejected batch (bad index, NaN, not an STL) is reported by sh_commit_staged and leaves
 // the resident batch untouched.  Records are identical to sh_upload_* + sh_run: same device buffers, same kernels.
-// The caller's (pageable) memory -> page-locked staging -> device, chunk by chunk on a few threads of their own (the hull pool's
-// workers may all be inside another lane's hull phase): a thread copies a chunk and enqueues its H2D copy at once, so the PCIe
-// transfer runs behind the memcpy instead of after it.  37 MB of arrays / 104 MB of files per batch.
-#define SH_COPY_THREADS 4
+// The caller's (pageable) memory -> page-locked staging -> device in 4 MiB pieces (copy_pool): 37 MB of arrays / 104 MB of files per batch.
 static hipError_t staged_h2d(void* dev, void* pinned, const void* src, size_t n, hipStream_t st) {
   const size_t chunk = (size_t)4 << 20;
-  const size_t nch = (n + chunk - 1) / chunk;
-  if (nch == 0) return hipSuccess;
-  std::atomic<size_t> next(0);
-  std::atomic<int> err((int)hipSuccess);
-  auto work = [&]() {
-    for (;;) {
-      const size_t k = next.fetch_add(1);
-      if (k >= nch) break;
-      const size_t o = k * chunk, m = std::min(chunk, n - o);
-      memcpy((char*)pinned + o, (const char*)src + o, m);
-      const hipError_t e = hipMemcpyAsync((char*)dev + o, (char*)pinned + o, m, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) err.store((int)e);
-    }
-  };
-  std::vector<std::thread> th;
-  for (int t = 1; t < SH_COPY_THREADS && (size_t)t < nch; ++t) th.emplace_back(work);
-  work();
-  for (auto& t : th) t.join();
-  return (hipError_t)err.load();
+  return copy_pool((n + chunk - 1) / chunk, [=](size_t k) {
+    const size_t o = k * chunk, m = std::min(chunk, n - o);
+    memcpy((char*)pinned + o, (const char*)src + o, m);
+    return hipMemcpyAsync((char*)dev + o, (char*)pinned + o, m, hipMemcpyHostToDevice, st);
+  });
 }
 
 static bool is_pinned_host(const void* p) {
@@ -1647,29 +1658,19 @@ static bool is_pinned_host(const void* p) {
   return pinned;
 }
 
-static int stage_common_alloc(sh_ctx* c, int B, long long sumV_cap, long long sumF_cap, size_t flag_ints) {
+// The staging side for a batch of at most sumV_cap vertices / sumF_cap faces, `src_bytes` of page-locked staging for the caller's
+// memory; the previous staged batch is dropped and the one background job of the context joined first.
+static int stage_begin(sh_ctx* c, int B, long long sumV_cap, long long sumF_cap, size_t flag_ints, size_t src_bytes) {
+  discard_staged(c);
+  (void)join_prepared(c);      // one background job per context
   sh_ctx::StageSide& S = c->stg;
   int rc;
   if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   if (!S.ready_ev) HIPCHK(c, hipEventCreateWithFlags(&S.ready_ev, hipEventDisableTiming));
-  if (S.h_flag_cap < flag_ints) {
-    if (S.h_flag) (void)hipHostFree(S.h_flag);
-    S.h_flag = nullptr; S.h_flag_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&S.h_flag, flag_ints * 4));
-    S.h_flag_cap = flag_ints;
-  }
-  if (S.h_kept_cap < sumV_cap) {
-    if (S.h_kept) (void)hipHostFree(S.h_kept);
-    S.h_kept = nullptr; S.h_kept_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&S.h_kept, (size_t)sumV_cap * 12));
-    S.h_kept_cap = sumV_cap;
-  }
-  if (S.h_koff_cap < B + 1) {
-    if (S.h_koff) (void)hipHostFree(S.h_koff);
-    S.h_koff = nullptr; S.h_koff_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&S.h_koff, (size_t)(B + 1) * 8));
-    S.h_koff_cap = B + 1;
-  }
+  if ((rc = grow_pinned(c, &S.h_flag, &S.h_flag_cap, flag_ints, 4)) != SH_OK) return rc;
+  if ((rc = grow_pinned(c, &S.h_kept, &S.h_kept_cap, (size_t)sumV_cap, 12)) != SH_OK) return rc;
+  if ((rc = grow_pinned(c, &S.h_koff, &S.h_koff_cap, (size_t)B + 1, 8)) != SH_OK) return rc;
+  if ((rc = grow_pinned(c, &S.h_src, &S.h_src_cap, src_bytes, 1, src_bytes / 8)) != SH_OK) return rc;
   ENS_SHARED("verts.s", sumV_cap * 12, 4);
   ENS_SHARED("faces.s", sumF_cap * 12, 4);
   ENS_SHARED("voff.s", (size_t)(B + 1) * 8, 8);
@@ -1679,31 +1680,39 @@ static int stage_common_alloc(sh_ctx* c, int B, long long sumV_cap, long long su
   return SH_OK;
 }
 
-// what the STL variant's thread does first (phase 1): sizes of the merged meshes -> offsets -> k_stl_emit
-struct StlPhase { bool on = false; int tsize = 0; long long maxc = 0; void *corners, *coff, *table, *slot, *vid, *fpos, *voff_d, *foff_d, *verts_d, *faces_d; hipEvent_t counted = nullptr; };
+// what the thread of a staged STL batch works from: the plan, the scratch view and the caller's files (read until the commit returns)
+struct StlJob { StlPlan plan; StlView v; std::vector<const void*> files; std::vector<size_t> nbytes; std::vector<char> pinned; };
 
-// The background thread of a staged batch: (STL: phase 1,) hull points through the prefilter, host hulls into pinned slot
-// `prep.slot`, records to the device as soon as the run in flight no longer reads hull.*.  `hulls` false (device hull): phase 1 only.
-static void start_prepare_staged(sh_ctx* c, bool hulls, const StlPhase stl, std::function<int(std::string*)> phase0) {
+// The background thread of a staged batch: phase 0 (the caller's memory to the device, the first kernels), for STL files the sizes
+// of the merged meshes -> offsets -> k_stl_emit, then hull points through the prefilter, host hulls into pinned slot `prep.slot`,
+// records to the device as soon as the run in flight no longer reads hull.*.  `hulls` false (device hull): no hull work.
+static int start_prepare_staged(sh_ctx* c, int B, std::shared_ptr<const StlJob> stl /*null: arrays*/, std::function<int(std::string*)> phase0) {
   sh_ctx::Prepared& p = c->prep;
   sh_ctx::StageSide& S = c->stg;
+  const bool hulls = !device_hull_now(c);
+  S.B = B;
+  S.meta_ready = false; S.meta_rc = SH_OK; S.meta_err.clear();
+  S.h_flag[0] = 0;
+  HIPCHK(c, hipEventRecord(S.ready_ev, c->copy_stream));      // (recorded again by the thread behind the last copy / k_stl_emit; this one covers an early discard)
+  S.active = true;
   p.active = true; p.staged = true; p.slot = c->hslot; p.B = S.B; p.gen = hulls ? c->batch_gen + 1 : ~0ull; p.rc = SH_OK; p.bad_mesh = -1; p.d2h_ms = p.hull_ms = 0; p.err.clear();
   p.uploaded = false;
   const HullPre hp = hullpre_ptrs(c, ".s");
   struct Dst { void* p[6]; } dst = {{c->bufs["hull.hv"].p, c->bufs["hull.normals"].p, c->bufs["hull.edges"].p, c->bufs["hull.nv"].p, c->bufs["hull.nf"].p, c->bufs["hull.ne"].p}};
+  struct Side { long long *voff, *foff; float* verts; int* faces; } side = {(long long*)c->bufs["voff.s"].p, (long long*)c->bufs["foff.s"].p, (float*)c->bufs["verts.s"].p, (int*)c->bufs["faces.s"].p};
   // early upload only into buffers that will not be re-allocated by the commit (alloc_batch grows them for a larger batch)
   const size_t nB = (size_t)S.B;
   const bool can_upload = c->obb_done_ev != nullptr && dst.p[0] && c->bufs["hull.hv"].bytes >= nB * c->hcap.v * 24 && c->bufs["hull.normals"].bytes >= nB * c->hcap.f * 24 &&
                           c->bufs["hull.edges"].bytes >= nB * c->hcap.e * 16 && c->bufs["hull.nv"].bytes >= nB * 4 && c->bufs["hull.nf"].bytes >= nB * 4 && c->bufs["hull.ne"].bytes >= nB * 4;
-  const int B = S.B;
-  p.th = std::thread([c, hp, dst, can_upload, hulls, stl, B, phase0]() {
+  p.th = std::thread([c, hp, dst, side, can_upload, hulls, stl, B, phase0]() {
     sh_ctx::Prepared& q = c->prep;
     sh_ctx::StageSide& S = c->stg;
-    auto meta = [&](int rc, const char* msg) {
-      { std::lock_guard<std::mutex> lk(S.m); S.meta_rc = rc; if (msg) S.meta_err = msg; S.meta_ready = true; }
+    auto meta = [&](int rc, const std::string& msg) {
+      { std::lock_guard<std::mutex> lk(S.m); S.meta_rc = rc; if (rc != SH_OK) S.meta_err = msg; S.meta_ready = true; }
       S.cv.notify_all();
     };
-    if (hipSetDevice(c->device) != hipSuccess) { q.rc = SH_ERR_HIP; meta(SH_ERR_HIP, "hipSetDevice"); return; }
+    auto refuse = [&](int rc, const std::string& msg) { q.rc = rc; meta(rc, msg); };
+    if (hipSetDevice(c->device) != hipSuccess) return refuse(SH_ERR_HIP, "hipSetDevice");
     const bool dbg = c->sw.debug;
     const auto tt0 = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tt0).count(); };
@@ -1711,47 +1720,33 @@ static void start_prepare_staged(sh_ctx* c, bool hulls, const StlPhase stl, std:
     {      // phase 0: the caller's memory -> page-locked staging, the copies and the first kernels enqueued (the staging call has returned)
       std::string et;
       const int rc0 = phase0(&et);
-      if (rc0 != SH_OK) { q.rc = rc0; meta(rc0, et.c_str()); return; }
-      if (!stl.on) meta(SH_OK, nullptr);
+      if (rc0 != SH_OK) return refuse(rc0, et);
+      if (!stl) meta(SH_OK, "");
       t_p0 = since();
     }
-    long long sumV = S.sumV;
-    if (stl.on) {
-      if (hipEventSynchronize(stl.counted) != hipSuccess) { q.rc = SH_ERR_HIP; meta(SH_ERR_HIP, "sh_stage_stl: the parse kernels failed"); return; }
-      const int* counts = S.h_flag + 16;            // [2 B] merged vertices, faces per file
-      const int* nonfin = S.h_flag + 16 + 2 * B;    // [B]
-      S.voff.assign(B + 1, 0); S.foff.assign(B + 1, 0);
-      long long maxV = 0, maxF = 0;
-      for (int b = 0; b < B; ++b) {
-        if (nonfin[b]) { q.rc = SH_ERR_ARG; meta(SH_ERR_ARG, "sh_stage_stl: a file holds NaN / infinite coordinates"); return; }
-        if (counts[2 * b] < 4 || counts[2 * b + 1] < 4) { q.rc = SH_ERR_ARG; meta(SH_ERR_ARG, "sh_stage_stl: a mesh has fewer than 4 vertices/faces after merging"); return; }
-        S.voff[b + 1] = S.voff[b] + counts[2 * b];
-        S.foff[b + 1] = S.foff[b] + counts[2 * b + 1];
-        maxV = std::max<long long>(maxV, counts[2 * b]); maxF = std::max<long long>(maxF, counts[2 * b + 1]);
-      }
-      S.maxV = maxV; S.maxF = maxF; S.sumV = S.voff[B]; S.sumF = S.foff[B];
-      sumV = S.sumV;
+    if (stl) {
+      if (hipEventSynchronize(c->stl_counted_ev) != hipSuccess) return refuse(SH_ERR_HIP, "sh_stage_stl: the parse kernels failed");
+      MeshSizes sz;      // S.h_flag + 16: [2 B] merged vertices, faces per file, [B] non-finite words behind them
+      const IngestError e = stl_counted(S.h_flag + 16, S.h_flag + 16 + 2 * B, B, &S.voff, &S.foff, &sz);
+      if (e.code != SH_OK) return refuse(e.code, std::string("sh_stage_stl: ") + e.text);
+      S.maxV = sz.maxV; S.maxF = sz.maxF; S.sumV = sz.sumV; S.sumF = sz.sumF;
       hipStream_t st = c->copy_stream;
-      bool ok = hipMemcpyAsync(stl.voff_d, S.voff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st) == hipSuccess &&
-                hipMemcpyAsync(stl.foff_d, S.foff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st) == hipSuccess;
-      if (ok) {
-        const dim3 gc((unsigned)std::min<long long>((stl.maxc + 255) / 256, 1024), (unsigned)B);
-        hipLaunchKernelGGL(k_stl_emit, gc, dim3(256), 0, st, (const float*)stl.corners, (const long long*)stl.coff, (const int2*)stl.table, stl.tsize, (const int*)stl.slot,
-                           (const int*)stl.vid, (const int*)stl.fpos, (const long long*)stl.voff_d, (const long long*)stl.foff_d, (float*)stl.verts_d, (int*)stl.faces_d);
-        ok = hipGetLastError() == hipSuccess && hipEventRecord(S.ready_ev, st) == hipSuccess;
-      }
-      if (!ok) { q.rc = SH_ERR_HIP; meta(SH_ERR_HIP, "sh_stage_stl: enqueueing the merge failed"); return; }
-      meta(SH_OK, nullptr);
+      std::string et;
+      if (hipMemcpyAsync(side.voff, S.voff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+          hipMemcpyAsync(side.foff, S.foff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+          stl_enqueue_emit(nullptr, st, B, stl->plan, stl->v, side.voff, side.foff, side.verts, side.faces, &et) != SH_OK || hipEventRecord(S.ready_ev, st) != hipSuccess)
+        return refuse(SH_ERR_HIP, "sh_stage_stl: enqueueing the merge failed");
+      meta(SH_OK, "");
       t_meta = since();
     }
     if (!hulls) return;
     {
       auto t0 = std::chrono::steady_clock::now();
-      if (fetch_prefiltered(hp, B, sumV, S.h_koff, S.h_kept, &S.pts, c->copy_stream) != hipSuccess) { q.rc = SH_ERR_HIP; return; }
+      if (fetch_prefiltered(hp, B, S.sumV, S.h_koff, S.h_kept, &S.pts, c->copy_stream) != hipSuccess) { q.rc = SH_ERR_HIP; return; }
       q.d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     t_pts = since();
-    if (!stl.on && S.h_flag[0] != 0) { q.rc = SH_ERR_ARG; return; }      // (the validation word came back in front of the survivors; the commit reports it)
+    if (!stl && S.h_flag[0] != 0) { q.rc = SH_ERR_ARG; return; }      // (the validation word came back in front of the survivors; the commit reports it)
     q.rc = hull_host_phase(c, S.pts, q.slot, 0, B, &q.bad_mesh, &q.hull_ms, &q.err, true);
     if (dbg) fprintf(stderr, "[sh] staged batch: copies enqueued %.2f ms, sizes known %.2f, hull points back %.2f, hulls done %.2f (hull phase %.2f)\n", t_p0, t_meta, t_pts, since(), q.hull_ms);
     if (q.rc == SH_OK && can_upload) {
@@ -1760,174 +1755,91 @@ static void start_prepare_staged(sh_ctx* c, bool hulls, const StlPhase stl, std:
         q.uploaded = true;
     }
   });
+  return SH_OK;
 }
 
 int sh_stage_meshes(sh_ctx* c, const float* verts, const int32_t* faces, const int64_t* v_off, const int64_t* f_off, int B) {
   if (!c || !verts || !faces || !v_off || !f_off || B <= 0) return fail(c, SH_ERR_ARG, "sh_stage_meshes: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
-  if (v_off[0] != 0 || f_off[0] != 0) return fail(c, SH_ERR_ARG, "sh_stage_meshes: offsets must start at 0");
-  long long maxV = 0, maxF = 0;
-  for (int b = 0; b < B; ++b) {
-    const long long nv = v_off[b + 1] - v_off[b], nf = f_off[b + 1] - f_off[b];
-    if (nv < 4 || nf < 4) return fail(c, SH_ERR_ARG, "sh_stage_meshes: a mesh has fewer than 4 vertices/faces");
-    if (nv > 0x7fffffffLL / 3 || nf > 0x7fffffffLL / 3) return fail(c, SH_ERR_ARG, "sh_stage_meshes: a mesh is too large");
-    maxV = std::max(maxV, nv); maxF = std::max(maxF, nf);
-  }
-  discard_staged(c);
-  (void)join_prepared(c);      // one background job per context
-  sh_ctx::StageSide& S = c->stg;
-  const long long sumV = v_off[B], sumF = f_off[B];
-  int rc;
-  if ((rc = stage_common_alloc(c, B, sumV, sumF, 64)) != SH_OK) return rc;
+  MeshSizes sz;
+  const IngestError e = check_mesh_arrays(v_off, f_off, B, nullptr, nullptr, &sz);      // (the elements are checked on the device)
+  if (e.code != SH_OK) return ingest_fail(c, "sh_stage_meshes", e);
   // the caller's arrays -> page-locked memory (unless they are page-locked already) -> device, all by the background thread: the
   // caller keeps its arrays unchanged until sh_commit_staged has returned
-  const size_t vb = (size_t)sumV * 12, fb = (size_t)sumF * 12, vpad = (vb + 255) & ~(size_t)255;
+  const size_t vb = (size_t)sz.sumV * 12, fb = (size_t)sz.sumF * 12, vpad = (vb + 255) & ~(size_t)255;
   const bool vpin = is_pinned_host(verts), fpin = is_pinned_host(faces);
-  const size_t need = (vpin ? 0 : vpad) + (fpin ? 0 : fb);
-  if (S.h_src_cap < need) {
-    if (S.h_src) (void)hipHostFree(S.h_src);
-    S.h_src = nullptr; S.h_src_cap = 0;
-    HIPCHK(c, hipHostMalloc(&S.h_src, need + need / 8));
-    S.h_src_cap = need + need / 8;
-  }
-  S.B = B; S.sumV = sumV; S.sumF = sumF; S.maxV = maxV; S.maxF = maxF; S.from_stl = false;
+  int rc;
+  if ((rc = stage_begin(c, B, sz.sumV, sz.sumF, 64, (vpin ? 0 : vpad) + (fpin ? 0 : fb))) != SH_OK) return rc;
+  sh_ctx::StageSide& S = c->stg;
+  S.sumV = sz.sumV; S.sumF = sz.sumF; S.maxV = sz.maxV; S.maxF = sz.maxF; S.from_stl = false;
   S.voff.assign(v_off, v_off + B + 1); S.foff.assign(f_off, f_off + B + 1);
-  S.meta_ready = false; S.meta_rc = SH_OK; S.meta_err.clear();
-  S.h_flag[0] = 0;
-  struct P0 { sh_ctx* c; const float* verts; const int32_t* faces; size_t vb, fb, vpad; bool vpin, fpin; void *dv, *df, *dvo, *dfo; int* flag; int B; long long maxV, maxF; } a =
-      {c, verts, faces, vb, fb, vpad, vpin, fpin, c->bufs["verts.s"].p, c->bufs["faces.s"].p, c->bufs["voff.s"].p, c->bufs["foff.s"].p, (int*)c->bufs["stage.flag"].p, B, maxV, maxF};
-  auto phase0 = [a](std::string* et) -> int {
-    sh_ctx::StageSide& S = a.c->stg;
-    hipStream_t st = a.c->copy_stream;
-    if (a.vpin) HIPCHK_TXT(et, hipMemcpyAsync(a.dv, a.verts, a.vb, hipMemcpyHostToDevice, st));
-    else HIPCHK_TXT(et, staged_h2d(a.dv, S.h_src, a.verts, a.vb, st));
-    if (a.fpin) HIPCHK_TXT(et, hipMemcpyAsync(a.df, a.faces, a.fb, hipMemcpyHostToDevice, st));
-    else HIPCHK_TXT(et, staged_h2d(a.df, (char*)S.h_src + (a.vpin ? 0 : a.vpad), a.faces, a.fb, st));
-    HIPCHK_TXT(et, hipMemcpyAsync(a.dvo, S.voff.data(), (size_t)(a.B + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK_TXT(et, hipMemcpyAsync(a.dfo, S.foff.data(), (size_t)(a.B + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK_TXT(et, hipMemsetAsync(a.flag, 0, 4, st));
-    hipLaunchKernelGGL(k_validate_meshes, dim3((unsigned)std::min<long long>((3 * std::max(a.maxV, a.maxF) + 255) / 256, 256), (unsigned)a.B), dim3(256), 0, st,
-                       (const float*)a.dv, (const int*)a.df, (const long long*)a.dvo, (const long long*)a.dfo, a.flag);
+  void *dv = c->bufs["verts.s"].p, *df = c->bufs["faces.s"].p, *dvo = c->bufs["voff.s"].p, *dfo = c->bufs["foff.s"].p;
+  int* flag = (int*)c->bufs["stage.flag"].p;
+  const dim3 grid((unsigned)std::min<long long>((3 * std::max(sz.maxV, sz.maxF) + 255) / 256, 256), (unsigned)B);
+  auto phase0 = [=](std::string* et) -> int {
+    sh_ctx::StageSide& S = c->stg;
+    hipStream_t st = c->copy_stream;
+    if (vpin) HIPCHK_TXT(et, hipMemcpyAsync(dv, verts, vb, hipMemcpyHostToDevice, st));
+    else HIPCHK_TXT(et, staged_h2d(dv, S.h_src, verts, vb, st));
+    if (fpin) HIPCHK_TXT(et, hipMemcpyAsync(df, faces, fb, hipMemcpyHostToDevice, st));
+    else HIPCHK_TXT(et, staged_h2d(df, (char*)S.h_src + (vpin ? 0 : vpad), faces, fb, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(dvo, S.voff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(dfo, S.foff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK_TXT(et, hipMemsetAsync(flag, 0, 4, st));
+    hipLaunchKernelGGL(k_validate_meshes, grid, dim3(256), 0, st, (const float*)dv, (const int*)df, (const long long*)dvo, (const long long*)dfo, flag);
     HIPCHK_TXT(et, hipGetLastError());
-    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag, a.flag, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag, flag, 4, hipMemcpyDeviceToHost, st));
     HIPCHK_TXT(et, hipEventRecord(S.ready_ev, st));
     return SH_OK;
   };
-  HIPCHK(c, hipEventRecord(S.ready_ev, c->copy_stream));      // (a discard before the thread gets there waits for this one)
-  S.active = true;
-  start_prepare_staged(c, !device_hull_now(c), StlPhase{}, phase0);
-  return SH_OK;
+  return start_prepare_staged(c, B, nullptr, phase0);
 }
 
 int sh_stage_stl(sh_ctx* c, const void* const* files, const size_t* nbytes, int B) {
   if (!c || !files || !nbytes || B <= 0) return fail(c, SH_ERR_ARG, "sh_stage_stl: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
-  std::vector<long long> file_off(B + 1, 0), coff(B + 1, 0);
-  long long maxc = 0;
-  for (int b = 0; b < B; ++b) {
-    if (!files[b] || nbytes[b] < 84) return fail(c, SH_ERR_ARG, "sh_stage_stl: a file is too short for a binary STL");
-    uint32_t nt;
-    memcpy(&nt, (const char*)files[b] + 80, 4);
-    if (nbytes[b] != 84 + 50ull * nt) return fail(c, SH_ERR_ARG, "sh_stage_stl: not a binary STL (size does not match the triangle count)");
-    if (nt < 4 || nt > 0x7fffffffu / 3) return fail(c, SH_ERR_ARG, "sh_stage_stl: a mesh has fewer than 4 (or too many) triangles");
-    file_off[b + 1] = file_off[b] + (long long)((nbytes[b] + 3) & ~(size_t)3);
-    coff[b + 1] = coff[b] + 3ll * nt;
-    maxc = std::max(maxc, 3ll * nt);
-  }
-  discard_staged(c);
-  (void)join_prepared(c);
-  sh_ctx::StageSide& S = c->stg;
-  int tsize = 1024;
-  while (tsize < 2 * maxc) tsize <<= 1;
-  const long long sumC = coff[B];
-  int rc;
+  auto job = std::make_shared<StlJob>();
+  StlPlan& plan = job->plan;
+  const IngestError e = stl_plan(files, nbytes, B, &plan);
+  if (e.code != SH_OK) return ingest_fail(c, "sh_stage_stl", e);
   // the merged meshes are at most as large as the corner lists: the staging side is sized by that bound, the true offsets are
-  // made by the thread once the device has counted
-  if ((rc = stage_common_alloc(c, B, sumC, sumC / 3, 16 + 3 * (size_t)B)) != SH_OK) return rc;
-  ENS_SHARED("stl.raw", (size_t)file_off[B], 1);
-  ENS_SHARED("stl.file_off", (B + 1) * 8, 8);
-  ENS_SHARED("stl.coff", (B + 1) * 8, 8);
-  ENS_SHARED("stl.corners", (size_t)sumC * 12, 4);
-  ENS_SHARED("stl.table", (size_t)B * tsize * 8, 4);
-  ENS_SHARED("stl.slot", (size_t)sumC * 4, 4);
-  ENS_SHARED("stl.vid", (size_t)sumC * 4, 4);
-  ENS_SHARED("stl.fpos", (size_t)(sumC / 3) * 4, 4);
-  ENS_SHARED("stl.counts", (size_t)B * 8, 4);
-  ENS_SHARED("stl.bsum", stl_rank_scratch_ints(B, maxc) * 4, 4);
-  ENS_SHARED("stl.nonfinite", (size_t)B * 4, 4);
-  // files -> one page-locked image (file starts 4-byte aligned) + the two offset tables behind it
-  const size_t raw_bytes = (size_t)file_off[B], tab_off = (raw_bytes + 255) & ~(size_t)255, need = tab_off + 2 * (size_t)(B + 1) * 8;
-  if (S.h_src_cap < need) {
-    if (S.h_src) (void)hipHostFree(S.h_src);
-    S.h_src = nullptr; S.h_src_cap = 0;
-    HIPCHK(c, hipHostMalloc(&S.h_src, need + need / 8));
-    S.h_src_cap = need + need / 8;
-  }
+  // made by the thread once the device has counted.  Page-locked staging: one image of the files (their starts 4-byte aligned) + the
+  // two offset tables behind it
+  const size_t tab_off = ((size_t)plan.file_off[B] + 255) & ~(size_t)255;
+  int rc;
+  if ((rc = stage_begin(c, B, plan.sumC, plan.sumC / 3, 16 + 3 * (size_t)B, tab_off + 2 * (size_t)(B + 1) * 8)) != SH_OK) return rc;
+  if ((rc = stl_scratch(c, B, plan, &job->v)) != SH_OK) return rc;
+  sh_ctx::StageSide& S = c->stg;
   long long* h_tabs = (long long*)((char*)S.h_src + tab_off);
-  memcpy(h_tabs, file_off.data(), (size_t)(B + 1) * 8);
-  memcpy(h_tabs + B + 1, coff.data(), (size_t)(B + 1) * 8);
-  S.B = B; S.from_stl = true; S.sumV = S.sumF = S.maxV = S.maxF = 0;
-  S.meta_ready = false; S.meta_rc = SH_OK; S.meta_err.clear();
-  S.h_flag[0] = 0;
+  memcpy(h_tabs, plan.file_off.data(), (size_t)(B + 1) * 8);
+  memcpy(h_tabs + B + 1, plan.coff.data(), (size_t)(B + 1) * 8);
+  S.from_stl = true; S.sumV = S.sumF = S.maxV = S.maxF = 0;
   if (!c->stl_counted_ev) HIPCHK(c, hipEventCreateWithFlags(&c->stl_counted_ev, hipEventDisableTiming));
   // the files themselves are read by the background thread: the caller keeps them unchanged until sh_commit_staged has returned
-  struct P0 { sh_ctx* c; std::vector<const void*> files; std::vector<size_t> nbytes; std::vector<long long> file_off; std::vector<char> pinned; size_t raw_bytes; long long* h_tabs; int B, tsize; long long maxc;
-              unsigned char* raw; void *d_file_off, *d_coff, *corners, *table, *slot, *vid, *fpos, *counts, *nonfin, *bsum; };
-  auto a = std::make_shared<P0>();
-  a->pinned.resize(B);
-  for (int b = 0; b < B; ++b) a->pinned[b] = is_pinned_host(files[b]) ? 1 : 0;
-  a->c = c; a->files.assign(files, files + B); a->nbytes.assign(nbytes, nbytes + B); a->file_off = file_off; a->raw_bytes = raw_bytes; a->h_tabs = h_tabs; a->B = B; a->tsize = tsize; a->maxc = maxc;
-  a->raw = (unsigned char*)c->bufs["stl.raw"].p; a->d_file_off = c->bufs["stl.file_off"].p; a->d_coff = c->bufs["stl.coff"].p; a->corners = c->bufs["stl.corners"].p;
-  a->table = c->bufs["stl.table"].p; a->slot = c->bufs["stl.slot"].p; a->vid = c->bufs["stl.vid"].p; a->fpos = c->bufs["stl.fpos"].p; a->counts = c->bufs["stl.counts"].p;
-  a->nonfin = c->bufs["stl.nonfinite"].p; a->bsum = c->bufs["stl.bsum"].p;
-  auto phase0 = [a](std::string* et) -> int {
-    sh_ctx* c = a->c;
+  job->files.assign(files, files + B); job->nbytes.assign(nbytes, nbytes + B); job->pinned.resize(B);
+  for (int b = 0; b < B; ++b) job->pinned[b] = is_pinned_host(files[b]) ? 1 : 0;
+  std::shared_ptr<const StlJob> a = job;
+  auto phase0 = [c, a, h_tabs, B](std::string* et) -> int {
     sh_ctx::StageSide& S = c->stg;
     hipStream_t st = c->copy_stream;
-    const int B = a->B;
-    {      // file by file: page-locked files go as they are, the others through the staging image; each file's H2D follows its memcpy at once
-      std::atomic<int> next(0);
-      std::atomic<int> err((int)hipSuccess);
-      auto work = [&]() {
-        for (;;) {
-          const int b = next.fetch_add(1);
-          if (b >= B) break;
-          const void* src = a->files[b];
-          if (!a->pinned[b]) { memcpy((char*)S.h_src + a->file_off[b], a->files[b], a->nbytes[b]); src = (char*)S.h_src + a->file_off[b]; }
-          const hipError_t e = hipMemcpyAsync(a->raw + a->file_off[b], src, a->nbytes[b], hipMemcpyHostToDevice, st);
-          if (e != hipSuccess) err.store((int)e);
-        }
-      };
-      std::vector<std::thread> th;
-      for (int t = 1; t < SH_COPY_THREADS && t < B; ++t) th.emplace_back(work);
-      work();
-      for (auto& t : th) t.join();
-      HIPCHK_TXT(et, (hipError_t)err.load());
-    }
-    HIPCHK_TXT(et, hipMemcpyAsync(a->d_file_off, a->h_tabs, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK_TXT(et, hipMemcpyAsync(a->d_coff, a->h_tabs + B + 1, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK_TXT(et, hipMemsetAsync(a->nonfin, 0, (size_t)B * 4, st));
-    const dim3 gc((unsigned)std::min<long long>((a->maxc + 255) / 256, 1024), (unsigned)B);
-    hipLaunchKernelGGL(k_stl_corners, gc, dim3(256), 0, st, (const unsigned char*)a->raw, (const long long*)a->d_file_off, (const long long*)a->d_coff, (float*)a->corners, (int*)a->nonfin);
-    hipLaunchKernelGGL(k_stl_table_init, dim3(1024), dim3(256), 0, st, (int2*)a->table, (size_t)B * a->tsize);
-    hipLaunchKernelGGL(k_stl_hash, gc, dim3(256), 0, st, (const float*)a->corners, (const long long*)a->d_coff, (int2*)a->table, a->tsize, (int*)a->slot);
-    stl_rank_launch(st, B, a->maxc, (const long long*)a->d_coff, (const int2*)a->table, a->tsize, (const int*)a->slot, (int*)a->vid, (int*)a->fpos, (int*)a->counts, (int*)a->bsum);
-    HIPCHK_TXT(et, hipGetLastError());
-    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag + 16, a->counts, (size_t)B * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag + 16 + 2 * B, a->nonfin, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    const StlView& v = a->v;
+    // file by file: page-locked files go as they are, the others through the staging image; each file's H2D follows its memcpy at once
+    HIPCHK_TXT(et, copy_pool((size_t)B, [&](size_t b) {
+      char* img = (char*)S.h_src + a->plan.file_off[b];
+      if (!a->pinned[b]) memcpy(img, a->files[b], a->nbytes[b]);
+      const void* src = a->pinned[b] ? a->files[b] : img;
+      return hipMemcpyAsync(v.raw + a->plan.file_off[b], src, a->nbytes[b], hipMemcpyHostToDevice, st);
+    }));
+    HIPCHK_TXT(et, hipMemcpyAsync(v.file_off, h_tabs, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(v.coff, h_tabs + B + 1, (size_t)(B + 1) * 8, hipMemcpyHostToDevice, st));
+    const int rc = stl_enqueue_parse(nullptr, st, B, a->plan, v, et);
+    if (rc != SH_OK) return rc;
+    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag + 16, v.counts, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK_TXT(et, hipMemcpyAsync(S.h_flag + 16 + 2 * B, v.nonfinite, (size_t)B * 4, hipMemcpyDeviceToHost, st));
     HIPCHK_TXT(et, hipEventRecord(c->stl_counted_ev, st));
     return SH_OK;
   };
-  StlPhase ph;
-  ph.on = true; ph.tsize = tsize; ph.maxc = maxc;
-  ph.corners = c->bufs["stl.corners"].p; ph.coff = c->bufs["stl.coff"].p; ph.table = c->bufs["stl.table"].p; ph.slot = c->bufs["stl.slot"].p;
-  ph.vid = c->bufs["stl.vid"].p; ph.fpos = c->bufs["stl.fpos"].p; ph.voff_d = c->bufs["voff.s"].p; ph.foff_d = c->bufs["foff.s"].p;
-  ph.verts_d = c->bufs["verts.s"].p; ph.faces_d = c->bufs["faces.s"].p;
-  HIPCHK(c, hipEventRecord(S.ready_ev, c->copy_stream));      // (recorded again behind k_stl_emit by the thread; this one covers an early discard)
-  ph.counted = c->stl_counted_ev;
-  S.active = true;
-  start_prepare_staged(c, !device_hull_now(c), ph, phase0);
-  return SH_OK;
+  return start_prepare_staged(c, B, a, phase0);
 }
 
 int sh_commit_staged(sh_ctx* c, int64_t* v_off_out, int64_t* f_off_out) {
@@ -1945,22 +1857,13 @@ int sh_commit_staged(sh_ctx* c, int64_t* v_off_out, int64_t* f_off_out) {
     return fail(c, SH_ERR_ARG, (f & 1) ? "sh_stage_meshes: face index out of range" : "sh_stage_meshes: NaN / infinite vertex coordinate");
   }
   // a resident-overlap preparation cannot be under way (staging joined it); the staged batch's own thread keeps running
-  for (const char* nm : {"verts", "faces", "voff", "foff"}) std::swap(c->bufs[nm], c->bufs[std::string(nm) + ".s"]);
-  c->B = 0;
-  c->h_voff.swap(S.voff); c->h_foff.swap(S.foff);
-  c->sumV = S.sumV; c->sumF = S.sumF; c->maxV = S.maxV; c->maxF = S.maxF;
-  c->h_verts_valid = false;
-  ++c->batch_gen;
-  c->bufs["verts"].per_mesh = 0; c->bufs["faces"].per_mesh = 0;
-  c->bufs["verts.s"].per_mesh = 0; c->bufs["faces.s"].per_mesh = 0; c->bufs["voff.s"].per_mesh = 0; c->bufs["foff.s"].per_mesh = 0;
-  const int B = S.B;
+  offsets_out(S.voff, v_off_out); offsets_out(S.foff, f_off_out);
+  MeshSizes sz;
+  sz.sumV = S.sumV; sz.sumF = S.sumF; sz.maxV = S.maxV; sz.maxF = S.maxF;
   S.active = false;
-  if (v_off_out) for (int b = 0; b <= B; ++b) v_off_out[b] = c->h_voff[b];
-  if (f_off_out) for (int b = 0; b <= B; ++b) f_off_out[b] = c->h_foff[b];
-  c->B = B;
-  int rc = alloc_batch(c);
-  if (rc != SH_OK) c->B = 0;
-  return rc;
+  ResidentSource src;
+  src.staged = true;
+  return make_resident(c, S.B, sz, S.voff, S.foff, src);
 }
 
 int sh_staged(const sh_ctx* c) { return c ? (c->stg.active ? 1 : 0) : SH_ERR_ARG; }
