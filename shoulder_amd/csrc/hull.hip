@@ -282,20 +282,20 @@ again:
 }
 
 // Hull records of pinned slot `slot` -> device buffers on stream `st`: only the used head of every fixed-capacity record
-// crosses PCIe (one strided copy per array).  `dst` = {hull.hv, hull.normals, hull.edges, hull.nv, hull.nf, hull.ne}.
-hipError_t sh::hull_upload(sh_ctx* c, int slot, int B, void* const dst[6], hipStream_t st) {
+// crosses PCIe (one strided copy per array).  `dst`: hull_rec() of the window (sh_ctx.h).
+hipError_t sh::hull_upload(sh_ctx* c, int slot, int B, const HullRec& dst, hipStream_t st) {
   sh_ctx::HullStage& hs = c->hstage[slot];
   const int* counts = hs.cnt;
   int nvmax = 1, nfmax = 1, nemax = 1;
   for (int b = 0; b < B; ++b) { nvmax = std::max(nvmax, counts[b]); nfmax = std::max(nfmax, counts[B + b]); nemax = std::max(nemax, counts[2 * B + b]); }
   if (nvmax > c->hcap.v || nfmax > c->hcap.f || nemax > c->hcap.e) return hipErrorInvalidValue;      // (callers check hull_fits / grow first)
   hipError_t e;
-  if ((e = hipMemcpy2DAsync(dst[0], (size_t)c->hcap.v * 24, hs.hv, (size_t)hs.pv * 24, (size_t)nvmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpy2DAsync(dst[1], (size_t)c->hcap.f * 24, hs.nr, (size_t)hs.pf * 24, (size_t)nfmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpy2DAsync(dst[2], (size_t)c->hcap.e * 16, hs.ed, (size_t)hs.pe * 16, (size_t)nemax * 16, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(dst[3], counts, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(dst[4], counts + B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpyAsync(dst[5], counts + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpy2DAsync(dst.hv, (size_t)c->hcap.v * 24, hs.hv, (size_t)hs.pv * 24, (size_t)nvmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpy2DAsync(dst.normals, (size_t)c->hcap.f * 24, hs.nr, (size_t)hs.pf * 24, (size_t)nfmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpy2DAsync(dst.edges, (size_t)c->hcap.e * 16, hs.ed, (size_t)hs.pe * 16, (size_t)nemax * 16, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(dst.nv, counts, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(dst.nf, counts + B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(dst.ne, counts + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
   if ((e = hipEventRecord(hs.ev, st)) != hipSuccess) return e;      // pinned slot is free again once these copies have run
   hs.used = true;
   return hipSuccess;
@@ -309,8 +309,9 @@ int sh::run_device_hull(sh_ctx* c, int B, int* nfmax) {
   HIPCHK(c, hipGetLastError());
   HullScratch hs{buf<int>(c, "hulld.fv"), buf<int>(c, "hulld.vis"), buf<int>(c, "hulld.ev"), buf<int>(c, "hulld.hor"), buf<int>(c, "hulld.newslot"),
                  buf<int>(c, "hulld.freestack"), buf<unsigned long long>(c, "hulld.tkeys"), buf<unsigned>(c, "hulld.tvals")};
+  const HullRec h = hull_rec(c);
   LAUNCH(c, "k_hull_rounds", k_hull_rounds, dim3(B), dim3(HD_THREADS), (const float*)c->bufs["hullpre.kept"].p, (const long long*)c->bufs["hullpre.koff"].p, hs,
-         buf<double>(c, "hull.hv"), buf<double>(c, "hull.normals"), buf<int>(c, "hull.edges"), buf<int>(c, "hull.nv"), buf<int>(c, "hull.nf"), buf<int>(c, "hull.ne"),
+         h.hv, h.normals, h.edges, h.nv, h.nf, h.ne,
          buf<int>(c, "hulld.fail"), buf<int>(c, "hulld.rounds"), (const int*)buf<int>(c, "hulld.skip"), c->hcap);
   LAUNCH(c, "k_hull_flag", k_hull_flag, dim3((B + 63) / 64), dim3(64), buf<int>(c, "hulld.fail"), buf<int>(c, "err"), B);
   *nfmax = std::max((int)HD_SLOTS, c->skip_nfmax);      // (the face counts stay on the device: the candidate kernel's tiles beyond a hull's faces return at once;

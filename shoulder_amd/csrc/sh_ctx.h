@@ -2,6 +2,8 @@
 // few functions that cross units.  No kernels here: every k_*.h is included by exactly one unit (-fno-gpu-rdc), the one whose
 // host code launches it.
 //   shoulder_hip.hip  context, C-ABI plumbing, meshes, the stage runner, submit / collect   (geometry kernels)
+//                     -- its per-batch buffers are declared once (WIN_*_BUFS: name, element type, elements per humerus); allocation
+//                     and the typed view of a window (WinView, resolved once per run_window) both come from that list
 //   hull.hip          hull prefilter, host hull phase and its worker pool, device hull      (k_hullpre.h, k_hull.h)
 //   unet.hip          the UNet runners, UNet turns, sh_unet_infer                          (k_unet*.h; unet16_pp.hip: k_unet16_pp.h)
 //   comm.hip          the RCCL collectives
@@ -79,7 +81,6 @@ struct sh_ctx {
   bool rs_all = false;
   unsigned long long rs_gen = ~0ull;
   int rec_rows = 0;                          // sh_set_record_rows: 0 = full sh_landmarks records, R > 0 = packed records with R anatomic-neck rows
-  bool bounds_cleared = false;               // run_obb's first fill of this window covered zb_enc / anp.mm_enc (run_window skips its own)
   // hull of SH_STAGE_OBB: 1 = on the device (k_hull.h), 0 = host quickhull (sh_hull.h).  sh_set_hull_mode / SHOULDER_HULL=host|device|auto.
   // A humerus the device hull gives up (pinched horizon on nearly coplanar clouds, capacities) is re-done ALONE by sh_collect
   // (redo_given_up); `hulld.skip[b]` then keeps the device hull off it for as long as the batch stays resident (skip_gen == batch_gen).
@@ -132,7 +133,9 @@ struct sh_ctx {
     std::mutex m; std::condition_variable cv; bool meta_ready = true; int meta_rc = 0; std::string meta_err;      // STL: sizes known
   } stg;
   // Window of the batch the stage runner is working on: sh_run walks the batch in windows so that the
-  // host hull of window k+1 overlaps the device work of window k.  buf<T>() applies the offset.
+  // host hull of window k+1 overlaps the device work of window k.  buf<T>() applies the offset.  (What only one window needs to
+  // know -- its typed buffer view, whether its bounds are cleared, whether its side branch is still to be joined -- is not here:
+  // WinView / WinState of shoulder_hip.hip, locals of run_window.)
   int b0 = 0, Bwin = 0;
   struct HullStage { double* hv = nullptr; double* nr = nullptr; int* ed = nullptr; int* cnt = nullptr; int cap = 0; hipEvent_t ev = nullptr; bool used = false;
                      int pv = 4096, pf = 8192, pe = 12288; };      // per-humerus pitch of the pinned staging (elements): the usual hull fits the small
@@ -169,7 +172,6 @@ struct sh_ctx {
   // box frame, so they run beside the full -> neck -> proximal chain
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork_ev = nullptr, side_join_ev = nullptr;
-  bool side_pending = false;
   // timing
   bool zero_page_ready = false;
   // Switches of equivalent paths (the A/B arms of tests/), read from the environment ONCE, when the context is created -- no launch
@@ -217,6 +219,14 @@ struct WindowScope {
   WindowScope(const WindowScope&) = delete; WindowScope& operator=(const WindowScope&) = delete;
 };
 
+// The stream the launches of a scope go to (the side branch of the stage runner); the context's own comes back like the window
+struct StreamScope {
+  sh_ctx* c; hipStream_t saved;
+  StreamScope(sh_ctx* c_, hipStream_t s) : c(c_), saved(c_->stream) { c->stream = s; }
+  ~StreamScope() { c->stream = saved; }
+  StreamScope(const StreamScope&) = delete; StreamScope& operator=(const StreamScope&) = delete;
+};
+
 static inline int fail(sh_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   return code;
@@ -247,6 +257,13 @@ static inline T* buf(sh_ctx* c, const char* name) {
   return (T*)((char*)it->second.p + (size_t)c->b0 * it->second.per_mesh);
 }
 
+// The hull record of the current window (what the host hull uploads, the device hull writes and the OBB stage reads), resolved in
+// one place.  Calling thread only (buffer map), and not across grow_hull_records / alloc_batch, which re-allocate it.
+struct HullRec { double *hv, *normals; int *edges, *nv, *nf, *ne; };
+static inline HullRec hull_rec(sh_ctx* c) {
+  return {buf<double>(c, "hull.hv"), buf<double>(c, "hull.normals"), buf<int>(c, "hull.edges"), buf<int>(c, "hull.nv"), buf<int>(c, "hull.nf"), buf<int>(c, "hull.ne")};
+}
+
 // ensure() inside a function with `int rc`, and the buffer's window stride: ENS for [B][...] buffers (bytes / B per humerus),
 // ENS_SHARED for shared / ragged / scratch ones (stride 0)
 #define ENS_(name, bytes, elem, per_mesh_)                                          \
@@ -256,6 +273,8 @@ static inline T* buf(sh_ctx* c, const char* name) {
   } while (0)
 #define ENS(name, bytes, elem) ENS_(name, bytes, elem, (size_t)(bytes) / (size_t)c->B)
 #define ENS_SHARED(name, bytes, elem) ENS_(name, bytes, elem, 0)
+// the element size sh_buffer_info reports for a buffer of T: records and segments count as bytes
+template <typename T> constexpr int elem_of() { return sizeof(T) <= 8 ? (int)sizeof(T) : 1; }
 
 // kernel launch with optional HIP-event timing on the ctx stream
 // timing level 1: events around every launch; 2: around the UNet layers only ("unet.*": ~25 launches per run, so the
@@ -300,7 +319,7 @@ HullPre hullpre_ptrs(sh_ctx* c, const char* sfx = "");      // calling thread on
 hipError_t fetch_prefiltered(const HullPre& hp, int B, long long sumV, long long* h_koff, float* h_kept, sh_ctx::HullPts* out, hipStream_t st);
 hipError_t fetch_hull_points(sh_ctx* c, const HullPre& hp, hipStream_t st);
 int hull_host_phase(sh_ctx* c, const sh_ctx::HullPts& in, int slot, int b0, int B, int* bad_mesh, double* ms, std::string* errtxt, bool background = false);
-hipError_t hull_upload(sh_ctx* c, int slot, int B, void* const dst[6], hipStream_t st);
+hipError_t hull_upload(sh_ctx* c, int slot, int B, const HullRec& dst, hipStream_t st);
 int run_device_hull(sh_ctx* c, int B, int* nfmax);
 int alloc_hullpre(sh_ctx* c, int B, long long sumV, const char* sfx);
 // unet.hip

@@ -286,107 +286,130 @@ int sh_get_params(const sh_ctx* c, sh_params* out) {
 
 int sh_batch_size(const sh_ctx* c) { return c ? c->B : 0; }
 
+// ---- the per-batch buffers of the stage runner: one statement each ---------------------------------------------------------------
+// X(field, "name", element type, elements per humerus).  The name is what sh_fetch / sh_store / sh_buffer_info see.  Allocation
+// (alloc_batch, alloc_prox, grow_hull_records: [B] x elements x sizeof(type), window stride = one humerus' bytes) and the typed view
+// of a window (WinView, below) both come from these lists, so a kernel argument has the type its buffer was sized with.
+// `c` is the context where a list is expanded (the hull record's and the end sections' capacities are its fields).
+#define WIN_HULLCAP_BUFS(X) /* strided by c->hcap: grow_hull_records re-allocates exactly these */                                  \
+  X(hull_hv, "hull.hv", double, (size_t)c->hcap.v * 3) X(hull_normals, "hull.normals", double, (size_t)c->hcap.f * 3)              \
+  X(hull_edges, "hull.edges", int, (size_t)c->hcap.e * 4) X(obb_cand_vol, "obb.cand_vol", double, c->hcap.f)                       \
+  X(obb_cand_edge, "obb.cand_edge", int, c->hcap.f) X(obb_area2, "obb.area2", double, c->hcap.f) X(obb_lb, "obb.lb", double, c->hcap.f) \
+  X(obb_dir_list, "obb.dir_list", int, c->hcap.f) X(obb_seeded, "obb.seeded", unsigned char, c->hcap.f)
+#define WIN_BATCH_BUFS(X)                                                                                                          \
+  X(obb_transform, "obb_transform", double, 16) X(zb_enc, "zb_enc", unsigned long long, 2) X(z_bounds, "z_bounds", double, 2)      \
+  X(z_length, "z_length", double, 1) X(err, "err", int, 1)                                                                         \
+  X(open_stats, "open.stats", int, 2) /* chains bridged / dropped per humerus (sh_open_contour_stats) */                           \
+  X(neck_z, "neck_z", double, 1) X(neck_index, "neck_index", int, 1)                                                               \
+  X(canal_points_obb, "canal.points_obb", double, SH_CANAL_MAXPTS * 3) X(canal_axis_obb, "canal.axis_obb", double, 6)              \
+  X(canal_axis_ct, "canal.axis_ct", double, 6) X(landmarks, "landmarks", sh_landmarks, 1)                                          \
+  X(prox_ixy, "prox.ixy", double, (size_t)SH_NPROX * 2 * SH_MPROX) X(prox_itr_start, "prox.itr_start", double, (size_t)SH_NPROX * 2 * SH_MPROX) \
+  X(prox_itr_centered_start, "prox.itr_centered_start", double, (size_t)SH_NPROX * 2 * SH_MPROX)                                   \
+  /* groove */                                                                                                                     \
+  X(groove_xraw, "groove.xraw", double, SH_GSLOTS * 9) X(groove_xs, "groove.xs", double, SH_GSLOTS * 9)                            \
+  X(groove_ptheta, "groove.ptheta", double, SH_GSLOTS) X(groove_npk, "groove.npk", int, SH_GROOVE_NROWS)                           \
+  X(groove_r0, "groove.r0", double, (size_t)SH_GROOVE_NROWS * SH_MPROX) X(groove_stats, "groove.stats", double, 18)                \
+  X(groove_proba, "groove.proba", float, SH_GSLOTS) X(groove_slots, "groove.slots", int, SH_GSLOTS)                                \
+  X(groove_nslot, "groove.nslot", int, 1) X(groove_bg_theta, "groove.bg_theta", double, 1)                                         \
+  X(groove_local_idx, "groove.local_idx", int, SH_GROOVE_NROWS) X(groove_points_obb, "groove.points_obb", double, SH_GROOVE_NROWS * 3) \
+  X(groove_points_ct, "groove.points_ct", double, SH_GROOVE_NROWS * 3) X(groove_axis_ct, "groove.axis_ct", double, 6)              \
+  /* anatomic neck */                                                                                                              \
+  X(anp_raw, "anp.raw", double, SH_IMG) X(anp_t01, "anp.t01", double, SH_ANP_ROWS * 2) X(anp_roll, "anp.roll", int, SH_ANP_ROWS)   \
+  X(anp_maskbits, "anp.maskbits", unsigned long long, SH_ANP_ROWS * (SH_MPROX / 64)) X(anp_mm_enc, "anp.mm_enc", unsigned long long, 2) \
+  X(metrics_partial, "metrics.partial", double, SH_SPH_PARTS * 14) X(anp_image, "anp.image", float, SH_IMG)                        \
+  X(anp_logits, "anp.logits", float, SH_IMG) X(anp_points_obb, "anp.points_obb", double, SH_ANP_CAP * 3)                           \
+  X(anp_counts, "anp.counts", int, 2) X(anp_rowcnt, "anp.rowcnt", int, SH_ANP_ROWS * 2) X(anp_ray_t, "anp.ray_t", unsigned long long, 4) \
+  X(anp_plane, "anp.plane", double, 6) X(anp_axes_obb, "anp.axes_obb", double, 12)                                                 \
+  /* trans-epicondylar */                                                                                                          \
+  X(te_rects, "te.rects", double, SH_TE_NROWS * 7) X(te_axis_ct, "te.axis_ct", double, 6) X(te_ends_ct, "te.ends_ct", double, 6)   \
+  X(te_row, "te.row", int, 1) X(flipped, "flipped", int, 1)                                                                        \
+  /* oriented bounding box */                                                                                                      \
+  WIN_HULLCAP_BUFS(X) X(hull_nv, "hull.nv", int, 1) X(hull_nf, "hull.nf", int, 1) X(hull_ne, "hull.ne", int, 1)                    \
+  X(obb_best_enc, "obb.best_enc", unsigned long long, 1) X(obb_lbmin_enc, "obb.lbmin_enc", unsigned long long, 1)                  \
+  X(obb_dir_count, "obb.dir_count", int, 1) X(obb_T_pre, "obb.T_pre", double, 16) X(obb_zb_pre, "obb.zb_pre", double, 2)           \
+  X(obb_endpts, "obb.endpts", double, (size_t)2 * c->end_cap * 2) X(obb_endcnt, "obb.endcnt", int, 2) X(obb_resid, "obb.resid", double, 2)
+// the SH_BONE_PROXIMAL path's own (alloc_prox, on first use; null in the view of a context that never took it): the cut-off of the
+// ProxObb area scan and the large Gram matrix of the neck change point
+#define WIN_PROX_BUFS(X)                                                                                                           \
+  X(pobb_cutoff, "pobb.cutoff", double, 2) X(pobb_cutoff_idx, "pobb.cutoff_idx", int, 2) X(neck_gram, "neck.gram", double, (size_t)SH_NFULL * SH_NFULL)
+// not per humerus (window stride 0) or allocated elsewhere (the mesh: upload / commit; the demand block: ovf_pools): X(field, "name", type)
+#define WIN_OTHER_BUFS(X)                                                                                                          \
+  X(verts, "verts", float) X(faces, "faces", int) X(voff, "voff", long long) X(foff, "foff", long long)                            \
+  X(verts_obb, "verts_obb", double) X(verts_csys, "verts_csys", double) X(slices_nlarge, "slices.nlarge", int)                     \
+  X(ovf_ctr, "ovf.ctr", unsigned long long)
+
+// The slice sets share one list of arrays: X(field, ".suffix", element type, elements per plane, which sets have it)
+#define SLICE_SET_ARRAYS(X)                                                                                                        \
+  X(zs, ".zs", double, 1, true) X(zeff, ".zeff", double, 1, true) X(seg_count, ".seg_count", int, 1, true)                         \
+  X(segs, ".segs", Seg, SH_MAXSEG, true) X(centroids, ".centroids", double, 2, true) X(areas, ".areas", double, 1, true)           \
+  X(nloops, ".nloops", int, 1, true) X(ring_n, ".ring_n", int, 1, true) X(ring, ".ring", double, (SH_MAXSEG + 1) * 2, s.ring)      \
+  X(area_total, ".area_total", double, 1, s.total_area)
+enum SetId { SET_FULL, SET_DISTAL, SET_PROX, SET_NECKC, SET_POBB, SET_COUNT };
+struct SliceSetDef { const char* pfx; int N; bool ring /*keeps the largest loop's ring*/, total_area, prox_only /*allocated by alloc_prox*/; };
+static const SliceSetDef SLICE_SETS[SET_COUNT] = {{"full", SH_NFULL, false, false, false}, {"distal", SH_NDIST, true, false, false},
+                                                  {"prox", SH_NPROX, true, false, false}, {"neckc", 1, true, false, false},
+                                                  {"pobb", SH_NPSCAN, false, true, true}};
+#define X(f, sfx, T, n, has) T* f = nullptr;
+struct SliceSetView { SLICE_SET_ARRAYS(X) };      // (an array the set does not have: null)
+#undef X
+
+// A window's buffers as typed pointers, the window offset applied as buf<T>() applies it (b0 * per_mesh).  RULE: resolved once, at
+// the top of run_window (alloc_prox, the pools' first allocation and anything between runs -- sh_collect's regrowth, sh_commit_staged,
+// alloc_batch -- lie in front of that), and resolved AGAIN behind the one thing that re-allocates its buffers inside a window:
+// grow_hull_records (run_obb does so; that is why it alone takes the view non-const).  What is ensured where it is used stays out of
+// the view and is resolved behind its ensure(): the overflow pools and plan arrays (ovf_pools / ovf_set), "obb.ws_*", "rfc.nodes";
+// so does the device hull's scratch, which run_device_hull owns.  The view is the calling thread's; background threads get pointers by value.
+#define X(f, name, T, ...) T* f = nullptr;
+struct WinView {
+  int B = 0;      // humeri in the window
+  WIN_OTHER_BUFS(X) WIN_BATCH_BUFS(X) WIN_PROX_BUFS(X)
+  SliceSetView set[SET_COUNT];
+  HullRec hull() const { return {hull_hv, hull_normals, hull_edges, hull_nv, hull_nf, hull_ne}; }
+};
+#undef X
+static WinView win_view(sh_ctx* c) {
+  WinView v;
+  v.B = c->Bwin;
+#define X(f, name, T, ...) v.f = buf<T>(c, name);
+  WIN_OTHER_BUFS(X) WIN_BATCH_BUFS(X) WIN_PROX_BUFS(X)
+#undef X
+  for (int i = 0; i < SET_COUNT; ++i) {
+    const std::string p = SLICE_SETS[i].pfx;
+#define X(f, sfx, T, n, has) v.set[i].f = buf<T>(c, (p + sfx).c_str());
+    SLICE_SET_ARRAYS(X)
+#undef X
+  }
+  return v;
+}
+
 // ---- meshes ------------------------------------------------------------------------------------
+#define WIN_ENS(f, name, T, n) ENS_(name, (size_t)c->B * (size_t)(n) * sizeof(T), elem_of<T>(), (size_t)(n) * sizeof(T));
+static int alloc_slice_set(sh_ctx* c, const SliceSetDef& s) {
+  int rc;
+  const std::string p = s.pfx;
+#define X(f, sfx, T, n, has) if (has) WIN_ENS(f, (p + sfx).c_str(), T, (size_t)s.N * (n))
+  SLICE_SET_ARRAYS(X)
+#undef X
+  return SH_OK;
+}
+
 static int alloc_batch(sh_ctx* c) {
   const int B = c->B;
   int rc;
   ENS_SHARED("verts_obb", c->sumV * 3 * 8, 8);        // ragged: indexed through voff
   ENS_SHARED("verts_csys", c->sumV * 3 * 8, 8);
+  ENS_SHARED("slices.nlarge", 64, 4);
   c->bufs["voff"].per_mesh = 8;             // a window sees voff[b0 + b] (absolute vertex offsets) as voff[b]
   c->bufs["foff"].per_mesh = 8;
   c->b0 = 0; c->Bwin = B;
-  ENS("obb_transform", B * 16 * 8, 8);
-  ENS("zb_enc", B * 2 * 8, 8);
-  ENS("z_bounds", B * 2 * 8, 8);
-  ENS("z_length", B * 8, 8);
-  ENS("err", B * 4, 4);
-  ENS("open.stats", B * 2 * 4, 4);          // chains bridged / dropped per humerus (sh_open_contour_stats)
-  ENS("neck_z", B * 8, 8);
-  ENS("neck_index", B * 4, 4);
-  ENS("canal.points_obb", B * SH_CANAL_MAXPTS * 3 * 8, 8);
-  ENS("canal.axis_obb", B * 6 * 8, 8);
-  ENS("canal.axis_ct", B * 6 * 8, 8);
-  ENS("landmarks", (size_t)B * sizeof(sh_landmarks), 1);
-  struct S { const char* p; int N; bool ring; };
-  const S sets[4] = {{"full", SH_NFULL, false}, {"distal", SH_NDIST, true}, {"prox", SH_NPROX, true}, {"neckc", 1, true}};
-  for (const S& s : sets) {
-    std::string p = s.p;
-    ENS((p + ".zs").c_str(), (size_t)B * s.N * 8, 8);
-    ENS((p + ".zeff").c_str(), (size_t)B * s.N * 8, 8);
-    ENS((p + ".seg_count").c_str(), (size_t)B * s.N * 4, 4);
-    ENS((p + ".segs").c_str(), (size_t)B * s.N * SH_MAXSEG * sizeof(Seg), 1);
-    ENS((p + ".centroids").c_str(), (size_t)B * s.N * 2 * 8, 8);
-    ENS((p + ".areas").c_str(), (size_t)B * s.N * 8, 8);
-    ENS((p + ".nloops").c_str(), (size_t)B * s.N * 4, 4);
-    ENS((p + ".ring_n").c_str(), (size_t)B * s.N * 4, 4);
-    if (s.ring) ENS((p + ".ring").c_str(), (size_t)B * s.N * (SH_MAXSEG + 1) * 2 * 8, 8);
-  }
-  ENS_SHARED("slices.nlarge", 64, 4);
-  ENS("prox.ixy", (size_t)B * SH_NPROX * 2 * SH_MPROX * 8, 8);
-  ENS("prox.itr_start", (size_t)B * SH_NPROX * 2 * SH_MPROX * 8, 8);
-  ENS("prox.itr_centered_start", (size_t)B * SH_NPROX * 2 * SH_MPROX * 8, 8);
-  // groove
-  ENS("groove.xraw", (size_t)B * SH_GSLOTS * 9 * 8, 8);
-  ENS("groove.xs", (size_t)B * SH_GSLOTS * 9 * 8, 8);
-  ENS("groove.ptheta", (size_t)B * SH_GSLOTS * 8, 8);
-  ENS("groove.npk", (size_t)B * SH_GROOVE_NROWS * 4, 4);
-  ENS("groove.r0", (size_t)B * SH_GROOVE_NROWS * SH_MPROX * 8, 8);
-  ENS("groove.stats", (size_t)B * 18 * 8, 8);
-  ENS("groove.proba", (size_t)B * SH_GSLOTS * 4, 4);
-  ENS("groove.slots", (size_t)B * SH_GSLOTS * 4, 4);
-  ENS("groove.nslot", (size_t)B * 4, 4);
-  ENS("groove.bg_theta", (size_t)B * 8, 8);
-  ENS("groove.local_idx", (size_t)B * SH_GROOVE_NROWS * 4, 4);
-  ENS("groove.points_obb", (size_t)B * SH_GROOVE_NROWS * 3 * 8, 8);
-  ENS("groove.points_ct", (size_t)B * SH_GROOVE_NROWS * 3 * 8, 8);
-  ENS("groove.axis_ct", (size_t)B * 6 * 8, 8);
-  // anatomic neck
-  ENS("anp.raw", (size_t)B * SH_IMG * 8, 8);
-  ENS("anp.t01", (size_t)B * SH_ANP_ROWS * 2 * 8, 8);
-  ENS("anp.roll", (size_t)B * SH_ANP_ROWS * 4, 4);
-  ENS("anp.maskbits", (size_t)B * SH_ANP_ROWS * (SH_MPROX / 64) * 8, 8);
-  ENS("anp.mm_enc", (size_t)B * 2 * 8, 8);
-  ENS("metrics.partial", (size_t)B * SH_SPH_PARTS * 14 * 8, 8);
-  ENS("anp.image", (size_t)B * SH_IMG * 4, 4);
-  ENS("anp.logits", (size_t)B * SH_IMG * 4, 4);
-  ENS("anp.points_obb", (size_t)B * SH_ANP_CAP * 3 * 8, 8);
-  ENS("anp.counts", (size_t)B * 2 * 4, 4);
-  ENS("anp.rowcnt", (size_t)B * SH_ANP_ROWS * 2 * 4, 4);
-  ENS("anp.ray_t", (size_t)B * 4 * 8, 8);
-  ENS("anp.plane", (size_t)B * 6 * 8, 8);
-  ENS("anp.axes_obb", (size_t)B * 12 * 8, 8);
-  // trans-epicondylar
-  ENS("te.rects", (size_t)B * SH_TE_NROWS * 7 * 8, 8);
-  ENS("te.axis_ct", (size_t)B * 6 * 8, 8);
-  ENS("te.ends_ct", (size_t)B * 6 * 8, 8);
-  ENS("te.row", (size_t)B * 4, 4);
-  ENS("flipped", (size_t)B * 4, 4);
+  WIN_BATCH_BUFS(WIN_ENS)
+  for (const SliceSetDef& s : SLICE_SETS)
+    if (!s.prox_only && (rc = alloc_slice_set(c, s)) != SH_OK) return rc;
   HIPCHK(c, hipMemsetAsync(buf<int>(c, "flipped"), 0, (size_t)B * 4, c->stream));
-  // oriented bounding box
-  ENS("hull.hv", (size_t)B * c->hcap.v * 3 * 8, 8);
-  ENS("hull.normals", (size_t)B * c->hcap.f * 3 * 8, 8);
-  ENS("hull.edges", (size_t)B * c->hcap.e * 4 * 4, 4);
-  ENS("hull.nv", (size_t)B * 4, 4);
-  ENS("hull.nf", (size_t)B * 4, 4);
-  ENS("hull.ne", (size_t)B * 4, 4);
   if ((rc = alloc_hullpre(c, B, c->sumV, "")) != SH_OK) return rc;
   if ((rc = grow_pinned(c, &c->h_kept, &c->h_kept_cap, (size_t)c->sumV, 12)) != SH_OK) return rc;
   if ((rc = grow_pinned(c, &c->h_nkept, &c->h_nkept_cap, (size_t)B, 4)) != SH_OK) return rc;
   if ((rc = grow_pinned(c, &c->h_koff, &c->h_koff_cap, (size_t)B + 1, 8)) != SH_OK) return rc;
-  ENS("obb.cand_vol", (size_t)B * c->hcap.f * 8, 8);
-  ENS("obb.cand_edge", (size_t)B * c->hcap.f * 4, 4);
-  ENS("obb.best_enc", (size_t)B * 8, 8);
-  ENS("obb.lbmin_enc", (size_t)B * 8, 8);
-  ENS("obb.area2", (size_t)B * c->hcap.f * 8, 8);
-  ENS("obb.lb", (size_t)B * c->hcap.f * 8, 8);
-  ENS("obb.dir_list", (size_t)B * c->hcap.f * 4, 4);
-  ENS("obb.dir_count", (size_t)B * 4, 4);
-  ENS("obb.seeded", (size_t)B * c->hcap.f, 1);
-  ENS("obb.T_pre", (size_t)B * 16 * 8, 8);
-  ENS("obb.zb_pre", (size_t)B * 2 * 8, 8);
-  ENS("obb.endpts", (size_t)B * 2 * c->end_cap * 2 * 8, 8);
-  ENS("obb.endcnt", (size_t)B * 2 * 4, 4);
-  ENS("obb.resid", (size_t)B * 2 * 8, 8);
   c->obb_injected = false;
   return SH_OK;
 }
@@ -394,21 +417,10 @@ static int alloc_batch(sh_ctx* c) {
 // Extra buffers of the SH_BONE_PROXIMAL path (allocated on first use): the ProxObb area scan and the large Gram matrix
 // of the neck change point.
 static int alloc_prox(sh_ctx* c) {
-  const int B = c->B;
   int rc;
-  const int N = SH_NPSCAN;
-  ENS("pobb.zs", (size_t)B * N * 8, 8);
-  ENS("pobb.zeff", (size_t)B * N * 8, 8);
-  ENS("pobb.seg_count", (size_t)B * N * 4, 4);
-  ENS("pobb.segs", (size_t)B * N * SH_MAXSEG * sizeof(Seg), 1);
-  ENS("pobb.centroids", (size_t)B * N * 2 * 8, 8);
-  ENS("pobb.areas", (size_t)B * N * 8, 8);
-  ENS("pobb.nloops", (size_t)B * N * 4, 4);
-  ENS("pobb.ring_n", (size_t)B * N * 4, 4);
-  ENS("pobb.area_total", (size_t)B * N * 8, 8);
-  ENS("pobb.cutoff", (size_t)B * 2 * 8, 8);
-  ENS("pobb.cutoff_idx", (size_t)B * 2 * 4, 4);
-  ENS("neck.gram", (size_t)B * SH_NFULL * SH_NFULL * 8, 8);
+  for (const SliceSetDef& s : SLICE_SETS)
+    if (s.prox_only && (rc = alloc_slice_set(c, s)) != SH_OK) return rc;
+  WIN_PROX_BUFS(WIN_ENS)
   return SH_OK;
 }
 
@@ -1097,94 +1109,84 @@ static int ovf_set(sh_ctx* c, const std::string& pfx, int N, OvfSet* S) {
 
 // One or two slice sets through the set's launches together (k_slices.h SliceSets): plane heights (+ counter clears, bound decode),
 // one pass over the mesh for their sections, one grid for their joins; the overflow tier and the resampling stay per set.
-struct SliceSpec { const char* pfx; int kind, N; bool ring, resample; int select; bool total_area, decode_bounds; };
-static int run_slice_sets(sh_ctx* c, const SliceSpec* specs, int nspec) {
-  const int B = c->Bwin;
+// (Planes per humerus, ring and total area: the set's, SLICE_SETS.)
+struct SliceSpec { SetId id; int kind; bool resample; int select; bool decode_bounds; };
+static int run_slice_sets(sh_ctx* c, const WinView& v, const SliceSpec* specs, int nspec) {
+  const int B = v.B;
   if (nspec < 1 || nspec > 2) return fail(c, SH_ERR_STATE, "run_slice_sets: one or two sets");
   int ntot = 0;
-  for (int i = 0; i < nspec; ++i) ntot += specs[i].N;
+  for (int i = 0; i < nspec; ++i) ntot += SLICE_SETS[specs[i].id].N;
   if (ntot > SH_EMIT_MAXN) return fail(c, SH_ERR_CAPACITY, "slice sets have more planes than k_slice_emit's LDS histogram");
   OvfPools OP; OvfSet OS[2];
   { int orc; if ((orc = ovf_pools(c, &OP)) != SH_OK) return orc; }
   const bool ovf_on = c->ovf_none_gen != c->batch_gen;      // (known from an earlier run of this batch: no plane overflows)
+  const bool bridge = c->open_mode != SH_OPEN_ERROR;
   SliceSets sets{};
   sets.n = nspec;
-  sets.vobb = buf<double>(c, "verts_obb"); sets.voff = buf<long long>(c, "voff");
-  sets.open = OpenCfg{c->open_mode, c->open_gap, c->open_mode ? buf<int>(c, "open.stats") : (int*)nullptr};
+  sets.vobb = v.verts_obb; sets.voff = v.voff;
+  sets.open = OpenCfg{c->open_mode, c->open_gap, c->open_mode ? v.open_stats : (int*)nullptr};
   for (int i = 0; i < nspec; ++i) {
     const SliceSpec& sp = specs[i];
-    const std::string p = sp.pfx;
-    { int orc; if ((orc = ovf_set(c, p, sp.N, &OS[i])) != SH_OK) return orc; }
+    const SliceSetDef& def = SLICE_SETS[sp.id];
+    const SliceSetView& a = v.set[sp.id];
+    { int orc; if ((orc = ovf_set(c, def.pfx, def.N, &OS[i])) != SH_OK) return orc; }
     SliceSetDev& S = sets.s[i];
-    S.N = sp.N; S.kind = sp.kind; S.select = sp.select;
-    S.zb = buf<double>(c, sp.kind == 4 ? "obb.zb_pre" : "z_bounds");
-    S.zs = buf<double>(c, (p + ".zs").c_str()); S.zeff = buf<double>(c, (p + ".zeff").c_str());
-    S.seg_count = buf<int>(c, (p + ".seg_count").c_str()); S.segs = buf<Seg>(c, (p + ".segs").c_str());
-    S.centroids = buf<double>(c, (p + ".centroids").c_str()); S.areas = buf<double>(c, (p + ".areas").c_str()); S.nloops = buf<int>(c, (p + ".nloops").c_str());
-    S.ring_n = buf<int>(c, (p + ".ring_n").c_str());
-    S.ring = sp.ring ? buf<double>(c, (p + ".ring").c_str()) : (double*)nullptr;
-    S.areas_total = sp.total_area ? buf<double>(c, (p + ".area_total").c_str()) : (double*)nullptr;
-    S.nlarge = (int*)c->bufs["slices.nlarge"].p + (sp.kind & 7);      // (one counter per kind of set)
+    S.N = def.N; S.kind = sp.kind; S.select = sp.select;
+    S.zb = sp.kind == 4 ? v.obb_zb_pre : v.z_bounds;
+    S.zs = a.zs; S.zeff = a.zeff; S.seg_count = a.seg_count; S.segs = a.segs;
+    S.centroids = a.centroids; S.areas = a.areas; S.nloops = a.nloops; S.ring_n = a.ring_n;
+    S.ring = a.ring; S.areas_total = a.area_total;      // (null where the set has none)
+    S.nlarge = v.slices_nlarge + (sp.kind & 7);      // (one counter per kind of set)
     // planes with more than SH_MAXLOOPS loops: listed for the overflow tier's join (tier skipped: flagged, sh_collect runs again with it)
     S.many = ManyLoops{ovf_on ? OS[i].list2 : (int*)nullptr, ovf_on ? OS[i].nlist + 1 : (int*)nullptr, ovf_on ? (unsigned long long*)nullptr : OP.ctr + SH_CTR_TIER_MISSED};
     S.ovf_missed = ovf_on ? (unsigned long long*)nullptr : OP.ctr + SH_CTR_TIER_MISSED;
     // the plane-height launch also zeroes the set's crossing counters and its large-tier counter, resets the overflow tier's words
     // (segments / workspace used: per launch group, by its first set; ring points stay for the run) and, for the first set behind
     // k_transform_verts, decodes the z bounds (run_window)
-    S.aux = PlaneAux{sp.decode_bounds ? (const unsigned long long*)buf<unsigned long long>(c, "zb_enc") : (const unsigned long long*)nullptr, buf<double>(c, "z_bounds"), S.seg_count, S.nlarge,
+    S.aux = PlaneAux{sp.decode_bounds ? (const unsigned long long*)v.zb_enc : (const unsigned long long*)nullptr, v.z_bounds, S.seg_count, S.nlarge,
                      ovf_on ? OS[i].nlist : (int*)nullptr, i == 0 ? OP.ctr : (unsigned long long*)nullptr};
   }
-  LAUNCH(c, "k_make_planes", k_make_planes, dim3(B, nspec), dim3(256), sets, (const double*)buf<double>(c, "neck_z"), B);
+  LAUNCH(c, "k_make_planes", k_make_planes, dim3(B, nspec), dim3(256), sets, (const double*)v.neck_z, B);
   dim3 g((unsigned)std::min<long long>((c->maxF + 255) / 256, 4096), (unsigned)B);
-  LAUNCH(c, "k_slice_emit", k_slice_emit, g, dim3(256), buf<double>(c, "verts_obb"), buf<int>(c, "faces"), buf<long long>(c, "voff"), buf<long long>(c, "foff"), sets);
+  LAUNCH(c, "k_slice_emit", k_slice_emit, g, dim3(256), v.verts_obb, v.faces, v.voff, v.foff, sets);
   if (ovf_on)      // planes with more crossings than slots (k_ovf.h): plan their pool ranges, section them again into the segment pool
     for (int i = 0; i < nspec; ++i) {
       const SliceSetDev& S = sets.s[i];
-      LAUNCH(c, "k_ovf_plan", k_ovf_plan, dim3((unsigned)((B * S.N + 255) / 256)), dim3(256), S.N, B * S.N, (const int*)S.seg_count, OP, OS[i], buf<int>(c, "err"));
-      LAUNCH(c, "k_slice_emit_ovf", k_slice_emit_ovf, g, dim3(256), buf<double>(c, "verts_obb"), buf<int>(c, "faces"), buf<long long>(c, "voff"),
-             buf<long long>(c, "foff"), (const double*)S.zeff, S.N, OP, OS[i]);
+      LAUNCH(c, "k_ovf_plan", k_ovf_plan, dim3((unsigned)((B * S.N + 255) / 256)), dim3(256), S.N, B * S.N, (const int*)S.seg_count, OP, OS[i], v.err);
+      LAUNCH(c, "k_slice_emit_ovf", k_slice_emit_ovf, g, dim3(256), v.verts_obb, v.faces, v.voff, v.foff, (const double*)S.zeff, S.N, OP, OS[i]);
     }
   // two capacity tiers share the grid (k_slices.h): the planes of the other tier exit at once
   // (bridge mode: the joins with the open-contour code, k_open.h; the default mode's joins are built without it)
-  if (c->open_mode != SH_OPEN_ERROR) {
-    LAUNCH(c, "k_slice_link", k_slice_link<true>, dim3(B * ntot), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
-    LAUNCH(c, "k_slice_link_large", k_slice_link_large<true>, dim3(std::min(B * ntot, 512)), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
-  } else {
-    LAUNCH(c, "k_slice_link", k_slice_link<false>, dim3(B * ntot), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
-    LAUNCH(c, "k_slice_link_large", k_slice_link_large<false>, dim3(std::min(B * ntot, 512)), dim3(SH_LINK_THREADS), sets, B, buf<int>(c, "err"));
-  }
+  LAUNCH(c, "k_slice_link", bridge ? k_slice_link<true> : k_slice_link<false>, dim3(B * ntot), dim3(SH_LINK_THREADS), sets, B, v.err);
+  LAUNCH(c, "k_slice_link_large", bridge ? k_slice_link_large<true> : k_slice_link_large<false>, dim3(std::min(B * ntot, 512)), dim3(SH_LINK_THREADS), sets, B, v.err);
   for (int i = 0; i < nspec; ++i) {
     const SliceSpec& sp = specs[i];
     const SliceSetDev& S = sets.s[i];
     if (ovf_on) {
-      LAUNCH(c, "k_ovf_plan_loops", k_ovf_plan_loops, dim3(16), dim3(256), S.N, (const int*)S.seg_count, (const Seg*)S.segs, OP, OS[i], buf<int>(c, "err"));
-      if (c->open_mode != SH_OPEN_ERROR)
-        LAUNCH(c, "k_slice_link_huge", k_slice_link_huge<true>, dim3(64), dim3(SH_HUGE_THREADS), S.N, (const int*)S.seg_count, OP, OS[i], S.centroids, S.areas, S.nloops, S.ring_n,
-             sp.ring ? 1 : 0, S.select, buf<int>(c, "err"), S.areas_total, (const double*)buf<double>(c, "verts_obb"), (const long long*)buf<long long>(c, "voff"), (const double*)S.zeff, sets.open);
-      else
-        LAUNCH(c, "k_slice_link_huge", k_slice_link_huge<false>, dim3(64), dim3(SH_HUGE_THREADS), S.N, (const int*)S.seg_count, OP, OS[i], S.centroids, S.areas, S.nloops, S.ring_n,
-             sp.ring ? 1 : 0, S.select, buf<int>(c, "err"), S.areas_total, (const double*)buf<double>(c, "verts_obb"), (const long long*)buf<long long>(c, "voff"), (const double*)S.zeff, sets.open);
+      LAUNCH(c, "k_ovf_plan_loops", k_ovf_plan_loops, dim3(16), dim3(256), S.N, (const int*)S.seg_count, (const Seg*)S.segs, OP, OS[i], v.err);
+      LAUNCH(c, "k_slice_link_huge", bridge ? k_slice_link_huge<true> : k_slice_link_huge<false>, dim3(64), dim3(SH_HUGE_THREADS), S.N, (const int*)S.seg_count, OP, OS[i],
+             S.centroids, S.areas, S.nloops, S.ring_n, SLICE_SETS[sp.id].ring ? 1 : 0, S.select, v.err, S.areas_total, (const double*)v.verts_obb, (const long long*)v.voff,
+             (const double*)S.zeff, sets.open);
     }
     if (sp.resample) {
       RsWant want{c->keep_products ? 1 : 0, SH_ANP_ROW0, 0, 0};
       cutoff_range(SH_NPROX, c->params.groove_cutoff[0], c->params.groove_cutoff[1], &want.cs_lo, &want.cs_hi);
       if (c->b0 == 0) { c->rs_cs_lo = want.cs_lo; c->rs_cs_hi = want.cs_hi; c->rs_all = c->keep_products; c->rs_gen = c->batch_gen; }
-      LAUNCH(c, "k_resample_polar", k_resample_polar, dim3(B * S.N), dim3(SH_RS_THREADS), S.N, SH_MPROX, S.ring_n, S.ring,
-             S.centroids, buf<double>(c, "prox.ixy"), buf<double>(c, "prox.itr_start"), buf<double>(c, "prox.itr_centered_start"), (const long long*)OS[i].roff, want);
-      LAUNCH(c, "k_resample_polar_large", k_resample_polar_large, dim3(std::min(B * S.N, 512)), dim3(SH_RS_THREADS), B * S.N, S.N, SH_MPROX, S.ring_n, S.ring,
-             S.centroids, buf<double>(c, "prox.ixy"), buf<double>(c, "prox.itr_start"), buf<double>(c, "prox.itr_centered_start"), (const int*)S.nlarge, (const long long*)OS[i].roff, want);
-      if (ovf_on) {
-        LAUNCH(c, "k_resample_polar_huge", k_resample_polar_huge, dim3(64), dim3(SH_RS_THREADS), S.N, SH_MPROX, (const int*)S.ring_n, OP, OS[i],
-               S.centroids, buf<double>(c, "prox.ixy"), buf<double>(c, "prox.itr_start"), buf<double>(c, "prox.itr_centered_start"), want);
-      }
+#define RS_ROWS S.centroids, v.prox_ixy, v.prox_itr_start, v.prox_itr_centered_start      /* what every tier reads and writes */
+      LAUNCH(c, "k_resample_polar", k_resample_polar, dim3(B * S.N), dim3(SH_RS_THREADS), S.N, SH_MPROX, S.ring_n, S.ring, RS_ROWS, (const long long*)OS[i].roff, want);
+      LAUNCH(c, "k_resample_polar_large", k_resample_polar_large, dim3(std::min(B * S.N, 512)), dim3(SH_RS_THREADS), B * S.N, S.N, SH_MPROX, S.ring_n, S.ring, RS_ROWS,
+             (const int*)S.nlarge, (const long long*)OS[i].roff, want);
+      if (ovf_on) LAUNCH(c, "k_resample_polar_huge", k_resample_polar_huge, dim3(64), dim3(SH_RS_THREADS), S.N, SH_MPROX, (const int*)S.ring_n, OP, OS[i], RS_ROWS, want);
+#undef RS_ROWS
     }
   }
   return SH_OK;
 }
-static int run_slice_set(sh_ctx* c, const char* pfx, int kind, int N, bool ring, bool resample, int select = 0, bool total_area = false, bool decode_bounds = false) {
-  const SliceSpec sp{pfx, kind, N, ring, resample, select, total_area, decode_bounds};
-  return run_slice_sets(c, &sp, 1);
-}
+static int run_slice_set(sh_ctx* c, const WinView& v, const SliceSpec& sp) { return run_slice_sets(c, v, &sp, 1); }
+// the five sets as the stages ask for them (kind, resampling, loop selection; decode: the first set behind k_transform_verts)
+static SliceSpec spec_full(bool decode) { return {SET_FULL, 0, false, 0, decode}; }
+static SliceSpec spec_distal(bool decode) { return {SET_DISTAL, 2, false, 0, decode}; }
+static const SliceSpec SPEC_PROX = {SET_PROX, 1, true, 0, false}, SPEC_NECKC = {SET_NECKC, 3, false, 1, false}, SPEC_POBB = {SET_POBB, 4, false, 0, false};
 
 // do the hulls of pinned slot `slot` fit the device record?  (the background threads upload only when they do: growing re-allocates)
 static bool hull_fits(const sh_ctx* c, int slot, int B, int* need /*[3] or null*/) {
@@ -1196,22 +1198,16 @@ static bool hull_fits(const sh_ctx* c, int slot, int B, int* need /*[3] or null*
 }
 // A hull above the record's capacity (a strictly convex surface keeps every vertex: 16 384 is not a bound of the reference's
 // `convex_hull`, mesh.py:82): the hull record and the per-face arrays of the OBB stage are re-allocated at strides that hold it.
-// Foreground only, nothing of this context in flight reads them afterwards (hipFree waits for the device).
+// Foreground only, nothing of this context in flight reads them afterwards (hipFree waits for the device).  A WinView resolved
+// before this call is stale behind it.
 static int grow_hull_records(sh_ctx* c, int nv, int nf, int ne) {
   auto up = [](int x) { return (x + x / 8 + 1023) / 1024 * 1024; };
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (nv > c->hcap.v) c->hcap.v = up(nv);
   if (nf > c->hcap.f) c->hcap.f = up(nf);
   if (ne > c->hcap.e) c->hcap.e = up(ne);
-  const size_t B = (size_t)c->B;
-  const struct { const char* n; size_t per; int elem; } arr[] = {
-      {"hull.hv", (size_t)c->hcap.v * 24, 8}, {"hull.normals", (size_t)c->hcap.f * 24, 8}, {"hull.edges", (size_t)c->hcap.e * 16, 4},
-      {"obb.cand_vol", (size_t)c->hcap.f * 8, 8}, {"obb.cand_edge", (size_t)c->hcap.f * 4, 4}, {"obb.area2", (size_t)c->hcap.f * 8, 8},
-      {"obb.lb", (size_t)c->hcap.f * 8, 8}, {"obb.dir_list", (size_t)c->hcap.f * 4, 4}, {"obb.seeded", (size_t)c->hcap.f, 1}};
-  for (const auto& a : arr) {
-    if (int e = ensure(c, a.n, B * a.per, a.elem)) return e;
-    c->bufs[a.n].per_mesh = a.per;
-  }
+  int rc;
+  WIN_HULLCAP_BUFS(WIN_ENS)
   if (c->sw.debug) fprintf(stderr, "[sh] hull record grown to %d vertices / %d faces / %d edges per humerus\n", c->hcap.v, c->hcap.f, c->hcap.e);
   return SH_OK;
 }
@@ -1220,9 +1216,17 @@ static int grow_hull_records(sh_ctx* c, int nv, int nf, int ne) {
 // >= 0).  Device: candidate boxes for every hull face, pick + frame, end sections, circle fits, flip (k_obb.h).
 static bool device_hull_now(const sh_ctx* c) { return c->hull_mode == 1 && !(c->hull_force_host && c->obb_gen == c->batch_gen); }
 
+// What one window's stages tell each other; lives in run_window
+struct WinState {
+  bool bounds_cleared = false;      // run_obb's first fill of this window covered zb_enc / anp.mm_enc (stage_frame skips its own)
+  bool side_pending = false;        // the side branch has been forked and not joined yet
+  bool te_rows_done = false;        // run_te_rows has run (beside or in front of the chain)
+};
+
 // redo_nf > 0: a redo -- redo_given_up put the host quickhull's record of this window (of one humerus) into hull.*, with that many faces
-static int run_obb(sh_ctx* c, int prepared_slot, int redo_nf) {
-  const int B = c->Bwin, b0 = c->b0;
+// `v` is resolved again when the hull record had to grow (the only re-allocation of a view's buffers inside a window).
+static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int redo_nf) {
+  const int B = v.B, b0 = c->b0;
   int nfmax = 1;
   if (c->obb_gen != c->batch_gen) { c->obb_gen = c->batch_gen; c->obb_sil_need = 0; c->obb_nf_over = false; c->hull_force_host = false; }
   if (redo_nf > 0) nfmax = redo_nf;
@@ -1246,37 +1250,34 @@ static int run_obb(sh_ctx* c, int prepared_slot, int redo_nf) {
     if (!hull_fits(c, slot, B, need)) {      // (never with an early upload: the background threads upload only what fits)
       int grc = grow_hull_records(c, need[0], need[1], need[2]);
       if (grc != SH_OK) return grc;
+      v = win_view(c);
     }
   }
-  if (!(prepared_slot >= 0 && c->prep.uploaded)) {
-    void* const dst[6] = {buf<double>(c, "hull.hv"), buf<double>(c, "hull.normals"), buf<int>(c, "hull.edges"), buf<int>(c, "hull.nv"), buf<int>(c, "hull.nf"), buf<int>(c, "hull.ne")};
-    HIPCHK(c, hull_upload(c, slot, B, dst, c->stream));
+  if (!(prepared_slot >= 0 && c->prep.uploaded)) HIPCHK(c, hull_upload(c, slot, B, v.hull(), c->stream));
   }
-  }
-  const int* cnt_nv = buf<int>(c, "hull.nv");
-  const int* cnt_nf = buf<int>(c, "hull.nf");
-  const int* cnt_ne = buf<int>(c, "hull.ne");
   {
-    FILL(c, {buf<unsigned long long>(c, "obb.best_enc"), (size_t)B * 8, 0xFF} /*"no candidate volume yet"*/, {buf<unsigned long long>(c, "obb.lbmin_enc"), (size_t)B * 8, 0xFF},
-         {buf<double>(c, "obb.area2"), (size_t)B * c->hcap.f * 8, 0}, {buf<int>(c, "obb.endcnt"), (size_t)B * 2 * 4, 0},
-         {buf<unsigned long long>(c, "zb_enc"), (size_t)B * 16, 0xFF} /*z bounds: "nothing seen yet"*/, {buf<unsigned long long>(c, "anp.mm_enc"), (size_t)B * 16, 0xFF});
-    c->bounds_cleared = true;
+    FILL(c, {v.obb_best_enc, (size_t)B * 8, 0xFF} /*"no candidate volume yet"*/, {v.obb_lbmin_enc, (size_t)B * 8, 0xFF},
+         {v.obb_area2, (size_t)B * c->hcap.f * 8, 0}, {v.obb_endcnt, (size_t)B * 2 * 4, 0},
+         {v.zb_enc, (size_t)B * 16, 0xFF} /*z bounds: "nothing seen yet"*/, {v.anp_mm_enc, (size_t)B * 16, 0xFF});
+    w->bounds_cleared = true;
     const int nemax = 3 * nfmax / 2 + 3;      // (a closed triangulated surface: 2 E = 3 F)
     const HullCap hc = c->hcap;
-    LAUNCH(c, "k_obb_face_area2", k_obb_face_area2, dim3((unsigned)((std::min(nemax, hc.e) + 255) / 256), (unsigned)B), dim3(256), buf<double>(c, "hull.hv"),
-           buf<double>(c, "hull.normals"), buf<int>(c, "hull.edges"), cnt_ne, buf<double>(c, "obb.area2"), hc);
+    LAUNCH(c, "k_obb_face_area2", k_obb_face_area2, dim3((unsigned)((std::min(nemax, hc.e) + 255) / 256), (unsigned)B), dim3(256), v.hull_hv,
+           v.hull_normals, v.hull_edges, (const int*)v.hull_ne, v.obb_area2, hc);
     const int bnd_tiles = (nfmax + SH_OBB_BND_DIRS - 1) / SH_OBB_BND_DIRS;
     LAUNCH(c, "k_obb_bounds", k_obb_bounds, dim3((unsigned)(bnd_tiles * ((B + 7) / 8) * 8)), dim3(SH_OBB_BND_THREADS),
-           buf<double>(c, "hull.hv"), cnt_nv, buf<double>(c, "hull.normals"), cnt_nf, buf<double>(c, "obb.area2"), buf<double>(c, "obb.lb"),
-           buf<unsigned long long>(c, "obb.lbmin_enc"), buf<double>(c, "obb.cand_vol"), buf<int>(c, "obb.cand_edge"), bnd_tiles, B, hc);
+           v.hull_hv, (const int*)v.hull_nv, v.hull_normals, (const int*)v.hull_nf, v.obb_area2, v.obb_lb,
+           v.obb_lbmin_enc, v.obb_cand_vol, v.obb_cand_edge, bnd_tiles, B, hc);
     // capacity tier of k_obb_candidates (k_obb.h): the small one unless a hull of this launch has more than 8 192 faces or a direction
     // of an earlier run of this batch had more than 512 silhouette edges; the workspace tier above 32 768 faces / 2 048 edges
     const bool huge = nfmax > 32768 || c->obb_sil_need > 2048 || c->obb_nf_over;
     const bool big = !huge && (nfmax > 8192 || c->obb_sil_need > 512);
     const int TT = (big || huge) ? 8 : SH_OBB_TILE;
     const int ntiles = (nfmax + TT - 1) / TT;
+    const auto candidates = huge ? k_obb_candidates<8, 1, 0, 0, unsigned, true>
+                            : big ? k_obb_candidates<8, 1, 2048, 32768, unsigned> : k_obb_candidates<SH_OBB_TILE, SH_OBB_GROUP, 512, 8192, unsigned short>;
     ObbWs ws{};
-    ws.need = (unsigned long long*)c->bufs["ovf.ctr"].p + SH_CTR_SIL_NEED;
+    ws.need = v.ovf_ctr + SH_CTR_SIL_NEED;
     if (huge) {
       ws.nwg = 256;
       ws.silcap = std::max(hc.v + 64, c->obb_sil_need + c->obb_sil_need / 8);      // (a silhouette is a cycle of the hull's graph; more only on degenerate input: then the demand is recorded)
@@ -1290,96 +1291,215 @@ static int run_obb(sh_ctx* c, int prepared_slot, int redo_nf) {
     // SHOULDER_OBB_PRUNE=0: every direction is evaluated (the A/B of the pruning bound: same frames, tests/test_gpu_hull.py)
     const bool prune = c->sw.obb_prune;
     for (int pass = 0; pass < 2; ++pass) {      // seed tile, then the directions its best volume cannot exclude
-      LAUNCH(c, "k_obb_select", k_obb_select, dim3(B), dim3(256), buf<double>(c, "obb.lb"), cnt_nf, buf<unsigned long long>(c, "obb.lbmin_enc"),
-             buf<unsigned long long>(c, "obb.best_enc"), (prune || pass == 0) ? pass : 2, buf<int>(c, "obb.dir_list"), buf<int>(c, "obb.dir_count"), buf<unsigned char>(c, "obb.seeded"), hc);
+      LAUNCH(c, "k_obb_select", k_obb_select, dim3(B), dim3(256), v.obb_lb, (const int*)v.hull_nf, v.obb_lbmin_enc,
+             v.obb_best_enc, (prune || pass == 0) ? pass : 2, v.obb_dir_list, v.obb_dir_count, v.obb_seeded, hc);
       const int nt_pass = pass == 0 ? SH_OBB_TILE / TT : ntiles;      // (the seed pass: up to SH_OBB_TILE directions)
-      const dim3 cg((unsigned)(nt_pass * ((B + 7) / 8) * 8));
-      if (huge) {
-        LAUNCH(c, pass == 0 ? "k_obb_seed" : "k_obb_candidates", (k_obb_candidates<8, 1, 0, 0, unsigned, true>), dim3((unsigned)std::min<unsigned>(cg.x, (unsigned)ws.nwg)), dim3(SH_OBB_THREADS),
-               buf<double>(c, "hull.hv"), cnt_nv, buf<double>(c, "hull.normals"), cnt_nf, buf<int>(c, "hull.edges"), cnt_ne, buf<double>(c, "obb.cand_vol"),
-               buf<int>(c, "obb.cand_edge"), buf<int>(c, "err"), buf<unsigned long long>(c, "obb.best_enc"), buf<int>(c, "obb.dir_list"), buf<int>(c, "obb.dir_count"),
-               nt_pass, B, prune ? 1 : 0, hc, ws);
-      } else if (big) {
-        LAUNCH(c, pass == 0 ? "k_obb_seed" : "k_obb_candidates", (k_obb_candidates<8, 1, 2048, 32768, unsigned>), cg, dim3(SH_OBB_THREADS),
-               buf<double>(c, "hull.hv"), cnt_nv, buf<double>(c, "hull.normals"), cnt_nf, buf<int>(c, "hull.edges"), cnt_ne, buf<double>(c, "obb.cand_vol"),
-               buf<int>(c, "obb.cand_edge"), buf<int>(c, "err"), buf<unsigned long long>(c, "obb.best_enc"), buf<int>(c, "obb.dir_list"), buf<int>(c, "obb.dir_count"),
-               nt_pass, B, prune ? 1 : 0, hc, ws);
-      } else {
-        LAUNCH(c, pass == 0 ? "k_obb_seed" : "k_obb_candidates", (k_obb_candidates<SH_OBB_TILE, SH_OBB_GROUP, 512, 8192, unsigned short>), cg, dim3(SH_OBB_THREADS),
-               buf<double>(c, "hull.hv"), cnt_nv, buf<double>(c, "hull.normals"), cnt_nf, buf<int>(c, "hull.edges"), cnt_ne, buf<double>(c, "obb.cand_vol"),
-               buf<int>(c, "obb.cand_edge"), buf<int>(c, "err"), buf<unsigned long long>(c, "obb.best_enc"), buf<int>(c, "obb.dir_list"), buf<int>(c, "obb.dir_count"),
-               nt_pass, B, prune ? 1 : 0, hc, ws);
-      }
+      dim3 cg((unsigned)(nt_pass * ((B + 7) / 8) * 8));
+      if (huge) cg.x = std::min<unsigned>(cg.x, (unsigned)ws.nwg);      // (the workspace tier: its ws.nwg workgroups walk the tiles)
+      LAUNCH(c, pass == 0 ? "k_obb_seed" : "k_obb_candidates", candidates, cg, dim3(SH_OBB_THREADS),
+             v.hull_hv, v.hull_nv, v.hull_normals, v.hull_nf, v.hull_edges, v.hull_ne, v.obb_cand_vol,
+             v.obb_cand_edge, v.err, v.obb_best_enc, v.obb_dir_list, v.obb_dir_count,
+             nt_pass, B, prune ? 1 : 0, hc, ws);
     }
   }
-  LAUNCH(c, "k_obb_pick", k_obb_pick, dim3(B), dim3(256), buf<double>(c, "hull.hv"), buf<double>(c, "hull.normals"), cnt_nf, buf<int>(c, "hull.edges"),
-         buf<double>(c, "obb.cand_vol"), buf<int>(c, "obb.cand_edge"), buf<float>(c, "verts"), buf<long long>(c, "voff"), buf<double>(c, "obb.T_pre"),
-         buf<double>(c, "obb.zb_pre"), buf<int>(c, "err"), c->hcap);
+  LAUNCH(c, "k_obb_pick", k_obb_pick, dim3(B), dim3(256), v.hull_hv, v.hull_normals, (const int*)v.hull_nf, v.hull_edges,
+         v.obb_cand_vol, v.obb_cand_edge, v.verts, v.voff, v.obb_T_pre, v.obb_zb_pre, v.err, c->hcap);
   if (!c->obb_done_ev) HIPCHK(c, hipEventCreateWithFlags(&c->obb_done_ev, hipEventDisableTiming));
   HIPCHK(c, hipEventRecord(c->obb_done_ev, c->stream));      // hull.* device buffers are free for the next run's records from here
   if (c->params.bone_kind == SH_BONE_PROXIMAL) {
     // mesh.py:134-192 ProxObb: 100 sections of the mesh in the raw box frame, head = largest area, canal range
     dim3 gv((unsigned)std::min<long long>((c->maxV + 255) / 256, 1024), (unsigned)B);
-    LAUNCH(c, "k_transform_verts", k_transform_verts, gv, dim3(256), buf<float>(c, "verts"), buf<long long>(c, "voff"),
-           buf<double>(c, "obb.T_pre"), buf<double>(c, "verts_obb"), buf<unsigned long long>(c, "zb_enc"));      // (zb_enc: cleared by the fill above; its values are not used here)
-    c->bounds_cleared = false;      // ... and run_window clears it again for the box frame's pass
+    LAUNCH(c, "k_transform_verts", k_transform_verts, gv, dim3(256), v.verts, v.voff, v.obb_T_pre, v.verts_obb, v.zb_enc);      // (zb_enc: cleared by the fill above; its values are not used here)
+    w->bounds_cleared = false;      // ... and stage_frame clears it again for the box frame's pass
     int rc2;
-    if ((rc2 = run_slice_set(c, "pobb", 4, SH_NPSCAN, false, false, 0, true)) != SH_OK) return rc2;
-    LAUNCH(c, "k_prox_obb", k_prox_obb, dim3((B + 63) / 64), dim3(64), buf<double>(c, "pobb.area_total"), buf<double>(c, "pobb.zs"), buf<double>(c, "obb.T_pre"),
-           buf<double>(c, "obb_transform"), buf<int>(c, "flipped"), buf<double>(c, "pobb.cutoff"), buf<int>(c, "pobb.cutoff_idx"), buf<int>(c, "err"), B);
+    if ((rc2 = run_slice_set(c, v, SPEC_POBB)) != SH_OK) return rc2;
+    LAUNCH(c, "k_prox_obb", k_prox_obb, dim3((B + 63) / 64), dim3(64), v.set[SET_POBB].area_total, v.set[SET_POBB].zs, v.obb_T_pre,
+           v.obb_transform, v.flipped, v.pobb_cutoff, v.pobb_cutoff_idx, v.err, B);
     c->obb_injected = true;
     return SH_OK;
   }
   dim3 g((unsigned)std::min<long long>((c->maxF + 255) / 256, 1024), (unsigned)B);
-  LAUNCH(c, "k_obb_end_points", k_obb_end_points, g, dim3(256), buf<float>(c, "verts"), buf<int>(c, "faces"), buf<long long>(c, "voff"),
-         buf<long long>(c, "foff"), buf<double>(c, "obb.T_pre"), buf<double>(c, "obb.zb_pre"), buf<double>(c, "obb.endpts"), buf<int>(c, "obb.endcnt"), c->end_cap);
-  LAUNCH(c, "k_obb_ends", k_obb_ends, dim3(B), dim3(128), buf<double>(c, "obb.endpts"), buf<int>(c, "obb.endcnt"),
-         buf<double>(c, "obb.T_pre"), buf<double>(c, "obb.resid"), buf<double>(c, "obb_transform"), buf<int>(c, "flipped"), buf<int>(c, "err"), B, c->end_cap,
-         (unsigned long long*)c->bufs["ovf.ctr"].p + SH_CTR_END_NEED);
+  LAUNCH(c, "k_obb_end_points", k_obb_end_points, g, dim3(256), v.verts, v.faces, v.voff, v.foff, v.obb_T_pre, v.obb_zb_pre, v.obb_endpts, v.obb_endcnt, c->end_cap);
+  LAUNCH(c, "k_obb_ends", k_obb_ends, dim3(B), dim3(128), v.obb_endpts, v.obb_endcnt, v.obb_T_pre, v.obb_resid, v.obb_transform, v.flipped, v.err, B, c->end_cap,
+         v.ovf_ctr + SH_CTR_END_NEED);
   c->obb_injected = true;
   return SH_OK;
 }
 
 // epicondyle.py:33-89, everything that needs the distal set only: the minimum-area rectangle of every distal slice in the cut (three
 // capacity tiers) and the two ends of the widest one
-static int run_te_rows(sh_ctx* c) {
-  const int B = c->Bwin;
+static int run_te_rows(sh_ctx* c, const WinView& v) {
+  const int B = v.B;
+  const SliceSetView& distal = v.set[SET_DISTAL];
   OvfPools OP; OvfSet OS;
   { int orc; if ((orc = ovf_pools(c, &OP)) != SH_OK || (orc = ovf_set(c, "distal", SH_NDIST, &OS)) != SH_OK) return orc; }
-  LAUNCH(c, "k_te_rows", k_te_rows<SH_SMALLSEG>, dim3(B * SH_TE_NROWS), dim3(64), buf<double>(c, "distal.ring"), buf<int>(c, "distal.ring_n"),
-         buf<double>(c, "te.rects"), B, (const long long*)OS.roff);
-  LAUNCH(c, "k_te_rows_large", k_te_rows<SH_MAXSEG>, dim3(B * SH_TE_NROWS), dim3(64), buf<double>(c, "distal.ring"), buf<int>(c, "distal.ring_n"),
-         buf<double>(c, "te.rects"), B, (const long long*)OS.roff);
-  if (c->ovf_none_gen != c->batch_gen) {
-    LAUNCH(c, "k_te_rows_huge", k_te_rows_huge, dim3(64), dim3(64), OP, OS, (const int*)buf<int>(c, "distal.ring_n"), buf<double>(c, "te.rects"));
-  }
+  LAUNCH(c, "k_te_rows", k_te_rows<SH_SMALLSEG>, dim3(B * SH_TE_NROWS), dim3(64), distal.ring, distal.ring_n, v.te_rects, B, (const long long*)OS.roff);
+  LAUNCH(c, "k_te_rows_large", k_te_rows<SH_MAXSEG>, dim3(B * SH_TE_NROWS), dim3(64), distal.ring, distal.ring_n, v.te_rects, B, (const long long*)OS.roff);
+  if (c->ovf_none_gen != c->batch_gen) LAUNCH(c, "k_te_rows_huge", k_te_rows_huge, dim3(64), dim3(64), OP, OS, (const int*)distal.ring_n, v.te_rects);
   // epicondyle.py:39-89: the widest slice's end slivers, their centroids, the farthest pair (CT coordinates, piece order)
-  LAUNCH(c, "k_te_ends", k_te_ends, dim3(B), dim3(64), buf<double>(c, "distal.ring"), buf<int>(c, "distal.ring_n"), buf<double>(c, "te.rects"),
-         buf<double>(c, "distal.zs"), buf<double>(c, "obb_transform"), buf<double>(c, "te.ends_ct"), buf<int>(c, "te.row"), buf<int>(c, "err"), B, OP, OS);
+  LAUNCH(c, "k_te_ends", k_te_ends, dim3(B), dim3(64), distal.ring, distal.ring_n, v.te_rects, distal.zs, v.obb_transform, v.te_ends_ct, v.te_row, v.err, B, OP, OS);
+  return SH_OK;
+}
+
+// ---- the stages of a window, in the order run_window calls them --------------------------------------------------------------------
+// the box frame: verts_obb + z bounds (mesh.py:85-86)
+static int stage_frame(sh_ctx* c, const WinView& v, uint32_t mask, const WinState& w) {
+  const int B = v.B;
+  // the encoded minima / maxima (z bounds of the box frame, the anatomic-neck image's range) start as all ones: one fill for both,
+  // in run_obb's first fill when that stage runs (they were a launch each)
+  if (!w.bounds_cleared && (mask & (SH_STAGE_OBB | SH_STAGE_FULL | SH_STAGE_ANP)))
+    FILL(c, {v.zb_enc, (size_t)B * 16, 0xFF}, {v.anp_mm_enc, (size_t)B * 16, 0xFF});
+  if (mask & (SH_STAGE_OBB | SH_STAGE_FULL)) {
+    dim3 g((unsigned)std::min<long long>((c->maxV + 255) / 256, 1024), (unsigned)B);
+    LAUNCH(c, "k_transform_verts", k_transform_verts, g, dim3(256), v.verts, v.voff, v.obb_transform, v.verts_obb, v.zb_enc);
+    if (!(mask & SH_STAGE_FULL))      // (with the full set in the run its k_make_planes decodes them)
+      LAUNCH(c, "k_decode_bounds", k_decode_bounds, dim3((2 * B + 63) / 64), dim3(64), v.zb_enc, v.z_bounds, B);
+  }
+  return SH_OK;
+}
+
+// the fork of the side branch: the side stream starts behind what the main stream has enqueued so far
+static int fork_side(sh_ctx* c) {
+  if (!c->side_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+  if (!c->side_fork_ev) { HIPCHK(c, hipEventCreateWithFlags(&c->side_fork_ev, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->side_join_ev, hipEventDisableTiming)); }
+  HIPCHK(c, hipEventRecord(c->side_fork_ev, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->side_fork_ev, 0));
+  return SH_OK;
+}
+
+// the distal set (unless it went with the full set's launches: `merged`) and the trans-epicondylar rows that hang on it alone --
+// on the side stream (`side`: forked here, joined by run_window) or in the chain
+static int stage_distal(sh_ctx* c, const WinView& v, uint32_t mask, bool merged, bool side, WinState* w) {
+  int rc;
+  if (side && (rc = fork_side(c)) != SH_OK) return rc;
+  {
+    StreamScope on(c, side ? c->side_stream : c->stream);
+    rc = merged ? SH_OK : run_slice_set(c, v, spec_distal(false));
+    // In the chain, the trans-epicondylar rows run HERE, in front of the UNet pass instead of behind it: the same kernels on the same
+    // stream, but the part of the step that follows the UNet -- what stands between the pass and the lane's next step -- is 0.3 ms
+    // (0.6 ms beside the other lane's UNet) shorter: 8.00 -> 7.74 ms per step sustained, 8.48 -> 8.35 at 20 steps.
+    const bool te_inline = !side && (mask & SH_STAGE_ANP);
+    if (rc == SH_OK && (side || te_inline) && (mask & SH_STAGE_TE)) { rc = run_te_rows(c, v); w->te_rows_done = rc == SH_OK; }
+  }
+  if (side && rc == SH_OK) { HIPCHK(c, hipEventRecord(c->side_join_ev, c->side_stream)); w->side_pending = true; }
+  return rc;
+}
+
+// surgical_neck.py:25-54: the change point of the full set's areas, then the contour at neck_z (loop whose vertex mean is nearest the
+// origin) -- with the proximal set (which starts from neck_z as well) in the same launches when both stages run (`with_prox`)
+static int stage_neck(sh_ctx* c, const WinView& v, bool with_prox) {
+  const bool prox = c->params.bone_kind == SH_BONE_PROXIMAL;      // surgical_neck.py:25-28
+  LAUNCH(c, "k_neck", prox ? k_neck<true> : k_neck<false>, dim3(v.B), dim3(64), v.set[SET_FULL].areas, v.set[SET_FULL].zs, v.neck_z, v.neck_index, v.B,
+         prox ? 0.2 : 0.70, 0.99, prox ? v.neck_gram : (double*)nullptr);
+  if (!with_prox) return run_slice_set(c, v, SPEC_NECKC);
+  const SliceSpec sp[2] = {SPEC_NECKC, SPEC_PROX};
+  return run_slice_sets(c, v, sp, 2);
+}
+
+static int stage_canal(sh_ctx* c, const WinView& v) {
+  LAUNCH(c, "k_canal", k_canal, dim3(v.B), dim3(64), v.set[SET_FULL].centroids, v.set[SET_FULL].zs, v.z_bounds, v.obb_transform, c->params.canal_cutoff[0],
+         c->params.canal_cutoff[1], c->params.bone_kind == SH_BONE_PROXIMAL ? v.pobb_cutoff : (const double*)nullptr,
+         v.canal_points_obb, v.canal_axis_obb, v.canal_axis_ct, v.err);
+  return SH_OK;
+}
+
+static int stage_groove(sh_ctx* c, const WinView& v, uint32_t mask) {
+  const int B = v.B;
+  int rc;
+  if (!c->have_rfc) return fail(c, SH_ERR_STATE, "sh_run: groove stage needs sh_load_rfc first");
+  int ga, gb;
+  cutoff_range(SH_NPROX, c->params.groove_cutoff[0], c->params.groove_cutoff[1], &ga, &gb);
+  // the centred polar rows [ga, gb) come from the proximal set's resampling, which writes the rows of ITS run's cut-off range (RsWant)
+  if (!(mask & SH_STAGE_PROXIMAL) && !(c->rs_gen == c->batch_gen && (c->rs_all || (ga >= c->rs_cs_lo && gb <= c->rs_cs_hi))))
+    return fail(c, SH_ERR_STATE, "sh_run: SH_STAGE_GROOVE without SH_STAGE_PROXIMAL, and the proximal slices of this batch were not made for this groove_cutoff (run SH_STAGE_PROXIMAL again)");
+  const char* pp = buf<char>(c, "params") + c->unet_floats * 4;
+  const size_t N = c->h_feat.size();
+  const int* feat = (const int*)pp; const float* thr = (const float*)(pp + N * 4); const int* ti = (const int*)(pp + N * 8);
+  const int* fi = (const int*)(pp + N * 12); const float* lw = (const float*)(pp + N * 16); const int* roots = (const int*)(pp + N * 20);
+  const double* prox_zs = v.set[SET_PROX].zs;
+  LAUNCH(c, "k_groove_rows", k_groove_rows, dim3(B * SH_GROOVE_NROWS), dim3(64), v.prox_itr_centered_start, prox_zs, v.canal_axis_ct, ga, v.groove_xraw,
+         v.groove_ptheta, v.groove_npk, v.groove_r0, v.err, B);
+  LAUNCH(c, "k_groove_scale", k_groove_scale, dim3(B), dim3(256), v.groove_xraw, v.groove_npk, v.groove_stats, B, v.groove_slots, v.groove_nslot, v.groove_proba);
+  if ((rc = ensure(c, "rfc.nodes", N * 16, 4)) != SH_OK) return rc;
+  int4* nodes = (int4*)c->bufs["rfc.nodes"].p;
+  if (!c->packed_rfc) {      // once per parameter block (it was a launch of every step's chain: 5 us alone, ~50 us beside a UNet pass)
+    LAUNCH(c, "k_rfc_pack", k_rfc_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), feat, thr, ti, fi, lw, nodes, (int)N);
+    c->packed_rfc = true;
+  }
+  LAUNCH(c, "k_groove_rfc", k_groove_rfc, dim3((unsigned)(B * ((SH_GSLOTS + 63) / 64))), dim3(64), v.groove_xraw, v.groove_slots, v.groove_nslot,
+         v.groove_stats, nodes, roots, c->rfc_trees, v.groove_xs, v.groove_proba, B);
+  LAUNCH(c, "k_groove_tail", k_groove_tail, dim3(B), dim3(256), v.groove_ptheta, v.groove_proba, v.groove_bg_theta, v.err,
+         v.prox_itr_centered_start, v.groove_r0, prox_zs, v.set[SET_PROX].centroids, ga, c->params.groove_deg_window,
+         v.groove_local_idx, v.groove_points_obb, v.obb_transform, v.groove_axis_ct, v.groove_points_ct);
+  return SH_OK;
+}
+
+static int stage_anp(sh_ctx* c, const WinView& v) {
+  const int B = v.B;
+  int rc;
+  if (!c->have_unet) return fail(c, SH_ERR_STATE, "sh_run: anatomic-neck stage needs sh_load_unet first");
+  LAUNCH(c, "k_anp_rows", k_anp_rows, dim3(B * SH_ANP_ROWS), dim3(64), v.prox_itr_start, v.groove_bg_theta, v.anp_raw, v.anp_t01, v.anp_roll, B,
+         v.anp_mm_enc);      // (+ the image's minimum / maximum: no second pass over it)
+  // MinMaxScaler (anatomic_neck.py:56-58): the 16-bit network's first kernel applies it where it reads its patches (k_unet16_l0.h) --
+  // no f32 image, 201 MB less traffic and a launch less per step; the other forms of the network and sh_set_keep_products get "anp.image"
+  const bool scale_in_net = (c->params.unet_dtype == SH_UNET_BF16 || c->params.unet_dtype == SH_UNET_F16) && unet16_level0_fused(c, SH_ANP_ROWS, SH_MPROX);
+  if (!scale_in_net || c->keep_products) LAUNCH(c, "k_anp_scale", k_anp_scale, dim3(64, B), dim3(256), v.anp_raw, v.anp_mm_enc, v.anp_image);
+  if ((rc = unet_turn_enter(c)) != SH_OK) return rc;
+  if (scale_in_net) { c->unet_raw = v.anp_raw; c->unet_mm = v.anp_mm_enc; }
+  rc = unet_dispatch(c, v.anp_image, v.anp_logits, B, SH_ANP_ROWS, SH_MPROX);
+  c->unet_raw = nullptr; c->unet_mm = nullptr;
+  (void)unet_turn_leave(c);      // also after a failed pass: whatever was enqueued is what the next context waits for
+  if (rc != SH_OK) return rc;
+  const double* prox_zs = v.set[SET_PROX].zs;
+  LAUNCH(c, "k_anp_edge_count", k_anp_edge_count, dim3(SH_ANP_ROWS / 8, B), dim3(512), v.anp_logits, v.anp_rowcnt, v.anp_maskbits);
+  LAUNCH(c, "k_anp_edges", k_anp_edges, dim3(SH_ANP_ROWS / 8, B), dim3(512), v.anp_maskbits, v.anp_raw, v.anp_t01, v.anp_roll, prox_zs, v.anp_rowcnt,
+         v.anp_points_obb, v.anp_counts, v.err);
+  LAUNCH(c, "k_anp_plane", k_anp_plane, dim3(B), dim3(256), v.anp_points_obb, v.anp_counts, v.anp_plane, v.err, v.anp_ray_t);      // (+ "no hit yet" for the rays)
+  LAUNCH(c, "k_rays_hit", k_rays_hit, dim3(SH_RAY_CHUNKS, B), dim3(256), v.verts_obb, v.faces, v.voff, v.foff, v.anp_plane, v.anp_ray_t);
+  return SH_OK;
+}
+
+// metrics of bone_props.py (side, retroversion, neck-shaft angle, radius of curvature; the sphere's sums need the mask and the neck
+// plane only), then ray points -> trans-epicondylar order -> record -> metrics: one launch, one workgroup per humerus (k_tail, k_te.h)
+static int stage_tail(sh_ctx* c, const WinView& v, uint32_t mask) {
+  const int B = v.B;
+  const bool prox = c->params.bone_kind == SH_BONE_PROXIMAL;
+  const uint32_t need = SH_STAGE_GROOVE | SH_STAGE_ANP | SH_STAGE_CSYS | (prox ? 0u : (uint32_t)SH_STAGE_TE);
+  const bool metrics = (mask & need) == need;
+  if (metrics)
+    LAUNCH(c, "k_sphere_partial", k_sphere_partial, dim3(SH_SPH_PARTS, B), dim3(256), v.anp_maskbits, v.anp_raw, v.anp_t01, v.anp_roll, v.set[SET_PROX].zs,
+           v.anp_plane, v.metrics_partial);
+  PackArgs A{};
+  A.lm = v.landmarks; A.T_obb = v.obb_transform; A.zb = v.z_bounds; A.neck_z = v.neck_z;
+  A.neck_index = v.neck_index; A.flipped = v.flipped; A.canal_axis_ct = v.canal_axis_ct; A.te_axis_ct = v.te_axis_ct;
+  A.groove_axis_ct = v.groove_axis_ct; A.bg_theta = v.groove_bg_theta; A.groove_pts_ct = v.groove_points_ct;
+  A.plane = v.anp_plane; A.axes_obb = v.anp_axes_obb; A.anp_pts_obb = v.anp_points_obb; A.anp_counts = v.anp_counts;
+  A.err = v.err; A.mask = mask; A.B = B; A.bone_kind = (int)c->params.bone_kind;
+  A.canal_cut = prox ? v.pobb_cutoff : (const double*)nullptr;
+  A.cc0 = c->params.canal_cutoff[0]; A.cc1 = c->params.canal_cutoff[1];
+  A.ray_t = v.anp_ray_t; A.te_ends_ct = v.te_ends_ct; A.sphere_partial = v.metrics_partial; A.metrics = metrics ? 1 : 0;
+  LAUNCH(c, "k_tail", k_tail, dim3(B), dim3(256), A);
+  return SH_OK;
+}
+
+// bone.py:155: the mesh of every humerus in its own canal / trans-epicondylar (or canal / articular) frame
+static int stage_apply(sh_ctx* c, const WinView& v) {
+  dim3 g((unsigned)std::min<long long>((c->maxV + 255) / 256, 1024), (unsigned)v.B);
+  LAUNCH(c, "k_apply_csys", k_apply_csys, g, dim3(256), v.landmarks, v.verts, v.voff, v.verts_csys);
   return SH_OK;
 }
 
 // All stages for the window [c->b0, c->b0 + c->Bwin) of the batch; everything is enqueued on the stream,
-// nothing here waits for the device.
+// nothing here waits for the device.  This function is the ORDER of the stages, which slice sets share their launches, the fork of
+// the side branch and its join; what a stage launches is its function's.
 static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot, int redo_nf = 0) {
-  const int B = c->Bwin;
+  auto has = [mask](uint32_t stages) { return (mask & stages) != 0; };
   int rc;
-  c->bounds_cleared = false;
-  if (mask & SH_STAGE_OBB)
-    if ((rc = run_obb(c, prepared_slot, redo_nf)) != SH_OK) return rc;
-  // the encoded minima / maxima (z bounds of the box frame, the anatomic-neck image's range) start as all ones: one fill for both,
-  // in run_obb's first fill when that stage runs (they were a launch each)
-  if (!c->bounds_cleared && (mask & (SH_STAGE_OBB | SH_STAGE_FULL | SH_STAGE_ANP)))
-    FILL(c, {buf<unsigned long long>(c, "zb_enc"), (size_t)B * 16, 0xFF}, {buf<unsigned long long>(c, "anp.mm_enc"), (size_t)B * 16, 0xFF});
-  const bool transformed = (mask & (SH_STAGE_OBB | SH_STAGE_FULL)) != 0;
-  if (transformed) {
-    // verts_obb + z bounds (mesh.py:85-86)
-    dim3 g((unsigned)std::min<long long>((c->maxV + 255) / 256, 1024), (unsigned)B);
-    LAUNCH(c, "k_transform_verts", k_transform_verts, g, dim3(256), buf<float>(c, "verts"), buf<long long>(c, "voff"),
-           buf<double>(c, "obb_transform"), buf<double>(c, "verts_obb"), buf<unsigned long long>(c, "zb_enc"));
-    if (!(mask & SH_STAGE_FULL))      // (with the full set in the run its k_make_planes decodes them)
-      LAUNCH(c, "k_decode_bounds", k_decode_bounds, dim3((2 * B + 63) / 64), dim3(64), buf<unsigned long long>(c, "zb_enc"), buf<double>(c, "z_bounds"), B);
-  }
+  WinView v = win_view(c);
+  WinState w;
+  if (has(SH_STAGE_OBB) && (rc = run_obb(c, v, &w, prepared_slot, redo_nf)) != SH_OK) return rc;
+  if ((rc = stage_frame(c, v, mask, w)) != SH_OK) return rc;
+  const bool transformed = has(SH_STAGE_OBB | SH_STAGE_FULL);
   // Slice sets that hang on the same inputs share their launches (run_slice_sets): full + distal behind the box frame, neck contour +
   // proximal behind neck_z -- 8 launches and two passes over the mesh less per step; same sections (SHOULDER_SLICE_MERGE=0: one
   // set per launch group, the A/B of tests/test_gpu_slices.py)
@@ -1390,145 +1510,31 @@ static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot, int redo_nf =
   // proximal -> groove chain.  Larger batches: the distal set and the trans-epicondylar rows stay in the chain (DESIGN.md section 9:
   // the rows forked beside the lane's UNet pass, or run behind it, made the step slower).  Fork only when the overflow tier is known
   // to be idle for this batch (its pool counters are per set) and no per-launch timing is on.
-  const bool can_fork = (mask & SH_STAGE_DISTAL) && c->ovf_none_gen == c->batch_gen && c->timing != 1 && redo_nf == 0;
-  const bool side = can_fork && B <= 16;
-  bool te_rows_done = false;
-  c->side_pending = false;
-  const bool merge_fd = merge_env && (mask & SH_STAGE_FULL) && (mask & SH_STAGE_DISTAL) && !side;
+  const bool can_fork = has(SH_STAGE_DISTAL) && c->ovf_none_gen == c->batch_gen && c->timing != 1 && redo_nf == 0;
+  const bool side = can_fork && v.B <= 16;
+  const bool merge_fd = merge_env && has(SH_STAGE_FULL) && has(SH_STAGE_DISTAL) && !side;
   if (merge_fd) {
     // (both sets decode the z bounds themselves: their plane heights are made by ONE launch, the distal workgroups cannot wait for the
     //  full set's to write "z_bounds")
-    const SliceSpec sp[2] = {{"full", 0, SH_NFULL, false, false, 0, false, transformed}, {"distal", 2, SH_NDIST, true, false, 0, false, transformed}};
-    if ((rc = run_slice_sets(c, sp, 2)) != SH_OK) return rc;
-  } else if (mask & SH_STAGE_FULL) {
-    if ((rc = run_slice_set(c, "full", 0, SH_NFULL, false, false, 0, false, transformed)) != SH_OK) return rc;
+    const SliceSpec sp[2] = {spec_full(transformed), spec_distal(transformed)};
+    if ((rc = run_slice_sets(c, v, sp, 2)) != SH_OK) return rc;
+  } else if (has(SH_STAGE_FULL)) {
+    if ((rc = run_slice_set(c, v, spec_full(transformed))) != SH_OK) return rc;
   }
-  if (mask & SH_STAGE_DISTAL) {
-    hipStream_t main_stream = c->stream;
-    if (side) {
-      if (!c->side_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-      if (!c->side_fork_ev) { HIPCHK(c, hipEventCreateWithFlags(&c->side_fork_ev, hipEventDisableTiming)); HIPCHK(c, hipEventCreateWithFlags(&c->side_join_ev, hipEventDisableTiming)); }
-      HIPCHK(c, hipEventRecord(c->side_fork_ev, main_stream));
-      HIPCHK(c, hipStreamWaitEvent(c->side_stream, c->side_fork_ev, 0));
-      c->stream = c->side_stream;
-    }
-    rc = merge_fd ? SH_OK : run_slice_set(c, "distal", 2, SH_NDIST, true, false);
-    // In the chain, the trans-epicondylar rows run HERE, in front of the UNet pass instead of behind it: the same kernels on the same
-    // stream, but the part of the step that follows the UNet -- what stands between the pass and the lane's next step -- is 0.3 ms
-    // (0.6 ms beside the other lane's UNet) shorter: 8.00 -> 7.74 ms per step sustained, 8.48 -> 8.35 at 20 steps.
-    const bool te_inline = !side && (mask & SH_STAGE_ANP);
-    if (rc == SH_OK && (side || te_inline) && (mask & SH_STAGE_TE)) { rc = run_te_rows(c); te_rows_done = rc == SH_OK; }
-    if (side) {
-      c->stream = main_stream;
-      if (rc == SH_OK) { HIPCHK(c, hipEventRecord(c->side_join_ev, c->side_stream)); c->side_pending = true; }
-    }
-    if (rc != SH_OK) return rc;
-  }
-  if (mask & SH_STAGE_NECK) {
-    const bool prox = c->params.bone_kind == SH_BONE_PROXIMAL;      // surgical_neck.py:25-28
-    if (prox) {
-      LAUNCH(c, "k_neck", k_neck<true>, dim3(B), dim3(64), buf<double>(c, "full.areas"), buf<double>(c, "full.zs"),
-             buf<double>(c, "neck_z"), buf<int>(c, "neck_index"), B, 0.2, 0.99, buf<double>(c, "neck.gram"));
-    } else {
-      LAUNCH(c, "k_neck", k_neck<false>, dim3(B), dim3(64), buf<double>(c, "full.areas"), buf<double>(c, "full.zs"),
-             buf<double>(c, "neck_z"), buf<int>(c, "neck_index"), B, 0.70, 0.99, (double*)nullptr);
-    }
-    // surgical_neck.py:37-54: the contour at neck_z (loop whose vertex mean is nearest the origin) -- with the proximal set (which
-    // starts from neck_z as well) in the same launches when both stages run
-    if (merge_env && (mask & SH_STAGE_PROXIMAL)) {
-      const SliceSpec sp[2] = {{"neckc", 3, 1, true, false, 1, false, false}, {"prox", 1, SH_NPROX, true, true, 0, false, false}};
-      if ((rc = run_slice_sets(c, sp, 2)) != SH_OK) return rc;
-    } else if ((rc = run_slice_set(c, "neckc", 3, 1, true, false, 1)) != SH_OK) return rc;
-  }
-  if (mask & SH_STAGE_CANAL) {
-    LAUNCH(c, "k_canal", k_canal, dim3(B), dim3(64), buf<double>(c, "full.centroids"), buf<double>(c, "full.zs"),
-           buf<double>(c, "z_bounds"), buf<double>(c, "obb_transform"), c->params.canal_cutoff[0], c->params.canal_cutoff[1],
-           c->params.bone_kind == SH_BONE_PROXIMAL ? buf<double>(c, "pobb.cutoff") : (const double*)nullptr,
-           buf<double>(c, "canal.points_obb"), buf<double>(c, "canal.axis_obb"), buf<double>(c, "canal.axis_ct"), buf<int>(c, "err"));
-  }
-  if ((mask & SH_STAGE_PROXIMAL) && !(merge_env && (mask & SH_STAGE_NECK)))
-    if ((rc = run_slice_set(c, "prox", 1, SH_NPROX, true, true)) != SH_OK) return rc;
-  if (mask & SH_STAGE_GROOVE) {
-    if (!c->have_rfc) return fail(c, SH_ERR_STATE, "sh_run: groove stage needs sh_load_rfc first");
-    int ga, gb;
-    cutoff_range(SH_NPROX, c->params.groove_cutoff[0], c->params.groove_cutoff[1], &ga, &gb);
-    // the centred polar rows [ga, gb) come from the proximal set's resampling, which writes the rows of ITS run's cut-off range (RsWant)
-    if (!(mask & SH_STAGE_PROXIMAL) && !(c->rs_gen == c->batch_gen && (c->rs_all || (ga >= c->rs_cs_lo && gb <= c->rs_cs_hi))))
-      return fail(c, SH_ERR_STATE, "sh_run: SH_STAGE_GROOVE without SH_STAGE_PROXIMAL, and the proximal slices of this batch were not made for this groove_cutoff (run SH_STAGE_PROXIMAL again)");
-    const char* pp = buf<char>(c, "params") + c->unet_floats * 4;
-    const size_t N = c->h_feat.size();
-    const int* feat = (const int*)pp; const float* thr = (const float*)(pp + N * 4); const int* ti = (const int*)(pp + N * 8);
-    const int* fi = (const int*)(pp + N * 12); const float* lw = (const float*)(pp + N * 16); const int* roots = (const int*)(pp + N * 20);
-    const int rows = B * SH_GROOVE_NROWS;
-    LAUNCH(c, "k_groove_rows", k_groove_rows, dim3(rows), dim3(64), buf<double>(c, "prox.itr_centered_start"),
-           buf<double>(c, "prox.zs"), buf<double>(c, "canal.axis_ct"), ga, buf<double>(c, "groove.xraw"),
-           buf<double>(c, "groove.ptheta"), buf<int>(c, "groove.npk"), buf<double>(c, "groove.r0"), buf<int>(c, "err"), B);
-    LAUNCH(c, "k_groove_scale", k_groove_scale, dim3(B), dim3(256), buf<double>(c, "groove.xraw"), buf<int>(c, "groove.npk"),
-           buf<double>(c, "groove.stats"), B, buf<int>(c, "groove.slots"), buf<int>(c, "groove.nslot"), buf<float>(c, "groove.proba"));
-    if ((rc = ensure(c, "rfc.nodes", N * 16, 4)) != SH_OK) return rc;
-    int4* nodes = (int4*)c->bufs["rfc.nodes"].p;
-    if (!c->packed_rfc) {      // once per parameter block (it was a launch of every step's chain: 5 us alone, ~50 us beside a UNet pass)
-      LAUNCH(c, "k_rfc_pack", k_rfc_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), feat, thr, ti, fi, lw, nodes, (int)N);
-      c->packed_rfc = true;
-    }
-    LAUNCH(c, "k_groove_rfc", k_groove_rfc, dim3((unsigned)(B * ((SH_GSLOTS + 63) / 64))), dim3(64), buf<double>(c, "groove.xraw"), buf<int>(c, "groove.slots"), buf<int>(c, "groove.nslot"),
-           buf<double>(c, "groove.stats"), nodes, roots, c->rfc_trees, buf<double>(c, "groove.xs"), buf<float>(c, "groove.proba"), B);
-    LAUNCH(c, "k_groove_tail", k_groove_tail, dim3(B), dim3(256), buf<double>(c, "groove.ptheta"), buf<float>(c, "groove.proba"), buf<double>(c, "groove.bg_theta"), buf<int>(c, "err"),
-           buf<double>(c, "prox.itr_centered_start"), buf<double>(c, "groove.r0"), buf<double>(c, "prox.zs"), buf<double>(c, "prox.centroids"), ga, c->params.groove_deg_window,
-           buf<int>(c, "groove.local_idx"), buf<double>(c, "groove.points_obb"), buf<double>(c, "obb_transform"), buf<double>(c, "groove.axis_ct"), buf<double>(c, "groove.points_ct"));
-  }
-  if (mask & SH_STAGE_ANP) {
-    if (!c->have_unet) return fail(c, SH_ERR_STATE, "sh_run: anatomic-neck stage needs sh_load_unet first");
-    LAUNCH(c, "k_anp_rows", k_anp_rows, dim3(B * SH_ANP_ROWS), dim3(64), buf<double>(c, "prox.itr_start"),
-           buf<double>(c, "groove.bg_theta"), buf<double>(c, "anp.raw"), buf<double>(c, "anp.t01"), buf<int>(c, "anp.roll"), B,
-           buf<unsigned long long>(c, "anp.mm_enc"));      // (+ the image's minimum / maximum: no second pass over it)
-    // MinMaxScaler (anatomic_neck.py:56-58): the 16-bit network's first kernel applies it where it reads its patches (k_unet16_l0.h) --
-    // no f32 image, 201 MB less traffic and a launch less per step; the other forms of the network and sh_set_keep_products get "anp.image"
-    const bool scale_in_net = (c->params.unet_dtype == SH_UNET_BF16 || c->params.unet_dtype == SH_UNET_F16) && unet16_level0_fused(c, SH_ANP_ROWS, SH_MPROX);
-    if (!scale_in_net || c->keep_products)
-      LAUNCH(c, "k_anp_scale", k_anp_scale, dim3(64, B), dim3(256), buf<double>(c, "anp.raw"), buf<unsigned long long>(c, "anp.mm_enc"), buf<float>(c, "anp.image"));
-    if ((rc = unet_turn_enter(c)) != SH_OK) return rc;
-    if (scale_in_net) { c->unet_raw = buf<double>(c, "anp.raw"); c->unet_mm = buf<unsigned long long>(c, "anp.mm_enc"); }
-    rc = unet_dispatch(c, buf<float>(c, "anp.image"), buf<float>(c, "anp.logits"), B, SH_ANP_ROWS, SH_MPROX);
-    c->unet_raw = nullptr; c->unet_mm = nullptr;
-    (void)unet_turn_leave(c);      // also after a failed pass: whatever was enqueued is what the next context waits for
-    if (rc != SH_OK) return rc;
-    LAUNCH(c, "k_anp_edge_count", k_anp_edge_count, dim3(SH_ANP_ROWS / 8, B), dim3(512), buf<float>(c, "anp.logits"), buf<int>(c, "anp.rowcnt"), buf<unsigned long long>(c, "anp.maskbits"));
-    LAUNCH(c, "k_anp_edges", k_anp_edges, dim3(SH_ANP_ROWS / 8, B), dim3(512), buf<unsigned long long>(c, "anp.maskbits"), buf<double>(c, "anp.raw"),
-           buf<double>(c, "anp.t01"), buf<int>(c, "anp.roll"), buf<double>(c, "prox.zs"), buf<int>(c, "anp.rowcnt"), buf<double>(c, "anp.points_obb"), buf<int>(c, "anp.counts"),
-           buf<int>(c, "err"));
-    LAUNCH(c, "k_anp_plane", k_anp_plane, dim3(B), dim3(256), buf<double>(c, "anp.points_obb"), buf<int>(c, "anp.counts"),
-           buf<double>(c, "anp.plane"), buf<int>(c, "err"), buf<unsigned long long>(c, "anp.ray_t"));      // (+ "no hit yet" for the rays)
-    LAUNCH(c, "k_rays_hit", k_rays_hit, dim3(SH_RAY_CHUNKS, B), dim3(256), buf<double>(c, "verts_obb"), buf<int>(c, "faces"), buf<long long>(c, "voff"),
-           buf<long long>(c, "foff"), buf<double>(c, "anp.plane"), buf<unsigned long long>(c, "anp.ray_t"));
-  }
-  if (mask & SH_STAGE_TE) {
-    if (c->side_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->side_join_ev, 0)); c->side_pending = false; }      // (rectangles and ends: done on the side stream)
-    if (!te_rows_done && (rc = run_te_rows(c)) != SH_OK) return rc;
-  }
-  if (c->side_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->side_join_ev, 0)); c->side_pending = false; }
-  // metrics of bone_props.py (side, retroversion, neck-shaft angle, radius of curvature): the sphere's sums need the mask and the neck plane only
-  const uint32_t need = SH_STAGE_GROOVE | SH_STAGE_ANP | SH_STAGE_CSYS | (c->params.bone_kind == SH_BONE_PROXIMAL ? 0u : (uint32_t)SH_STAGE_TE);
-  const bool metrics = (mask & need) == need;
-  if (metrics)
-    LAUNCH(c, "k_sphere_partial", k_sphere_partial, dim3(SH_SPH_PARTS, B), dim3(256), buf<unsigned long long>(c, "anp.maskbits"), buf<double>(c, "anp.raw"),
-           buf<double>(c, "anp.t01"), buf<int>(c, "anp.roll"), buf<double>(c, "prox.zs"), buf<double>(c, "anp.plane"), buf<double>(c, "metrics.partial"));
-  {      // ray points -> trans-epicondylar order -> record -> metrics: one launch, one workgroup per humerus (k_tail, k_te.h)
-    PackArgs A{};
-    A.lm = buf<sh_landmarks>(c, "landmarks"); A.T_obb = buf<double>(c, "obb_transform"); A.zb = buf<double>(c, "z_bounds"); A.neck_z = buf<double>(c, "neck_z");
-    A.neck_index = buf<int>(c, "neck_index"); A.flipped = buf<int>(c, "flipped"); A.canal_axis_ct = buf<double>(c, "canal.axis_ct"); A.te_axis_ct = buf<double>(c, "te.axis_ct");
-    A.groove_axis_ct = buf<double>(c, "groove.axis_ct"); A.bg_theta = buf<double>(c, "groove.bg_theta"); A.groove_pts_ct = buf<double>(c, "groove.points_ct");
-    A.plane = buf<double>(c, "anp.plane"); A.axes_obb = buf<double>(c, "anp.axes_obb"); A.anp_pts_obb = buf<double>(c, "anp.points_obb"); A.anp_counts = buf<int>(c, "anp.counts");
-    A.err = buf<int>(c, "err"); A.mask = mask; A.B = B; A.bone_kind = (int)c->params.bone_kind;
-    A.canal_cut = c->params.bone_kind == SH_BONE_PROXIMAL ? buf<double>(c, "pobb.cutoff") : (const double*)nullptr;
-    A.cc0 = c->params.canal_cutoff[0]; A.cc1 = c->params.canal_cutoff[1];
-    A.ray_t = buf<unsigned long long>(c, "anp.ray_t"); A.te_ends_ct = buf<double>(c, "te.ends_ct"); A.sphere_partial = buf<double>(c, "metrics.partial"); A.metrics = metrics ? 1 : 0;
-    LAUNCH(c, "k_tail", k_tail, dim3(B), dim3(256), A);
-  }
-  if (mask & SH_STAGE_APPLY) {      // bone.py:155: the mesh of every humerus in its own canal / trans-epicondylar (or canal / articular) frame
-    dim3 g((unsigned)std::min<long long>((c->maxV + 255) / 256, 1024), (unsigned)B);
-    LAUNCH(c, "k_apply_csys", k_apply_csys, g, dim3(256), buf<sh_landmarks>(c, "landmarks"), buf<float>(c, "verts"), buf<long long>(c, "voff"), buf<double>(c, "verts_csys"));
-  }
+  if (has(SH_STAGE_DISTAL) && (rc = stage_distal(c, v, mask, merge_fd, side, &w)) != SH_OK) return rc;
+  const bool merge_np = merge_env && has(SH_STAGE_NECK) && has(SH_STAGE_PROXIMAL);
+  if (has(SH_STAGE_NECK) && (rc = stage_neck(c, v, merge_np)) != SH_OK) return rc;
+  if (has(SH_STAGE_CANAL) && (rc = stage_canal(c, v)) != SH_OK) return rc;
+  if (has(SH_STAGE_PROXIMAL) && !merge_np && (rc = run_slice_set(c, v, SPEC_PROX)) != SH_OK) return rc;
+  if (has(SH_STAGE_GROOVE) && (rc = stage_groove(c, v, mask)) != SH_OK) return rc;
+  if (has(SH_STAGE_ANP) && (rc = stage_anp(c, v)) != SH_OK) return rc;
+  // The join of the side branch (its rectangles and ends are done there), in ONE place: in front of the trans-epicondylar block and
+  // of everything behind it.  (It used to stand a second time behind that block, for runs without SH_STAGE_TE; no launch lies between
+  // the two positions then, so the stream order is the same.)
+  if (w.side_pending) { HIPCHK(c, hipStreamWaitEvent(c->stream, c->side_join_ev, 0)); w.side_pending = false; }
+  if (has(SH_STAGE_TE) && !w.te_rows_done && (rc = run_te_rows(c, v)) != SH_OK) return rc;
+  if ((rc = stage_tail(c, v, mask)) != SH_OK) return rc;
+  if (has(SH_STAGE_APPLY) && (rc = stage_apply(c, v)) != SH_OK) return rc;
   return SH_OK;
 }
 
@@ -1544,7 +1550,7 @@ static void start_prepare(sh_ctx* c) {
   p.uploaded = false; p.staged = false;
   // device pointers are looked up here: the buffer map belongs to the calling thread
   const HullPre hp = hullpre_ptrs(c);
-  struct Dst { void* p[6]; } dst = {{buf<double>(c, "hull.hv"), buf<double>(c, "hull.normals"), buf<int>(c, "hull.edges"), buf<int>(c, "hull.nv"), buf<int>(c, "hull.nf"), buf<int>(c, "hull.ne")}};
+  const HullRec dst = hull_rec(c);
   const bool can_upload = c->obb_done_ev != nullptr;
   p.th = std::thread([c, hp, dst, can_upload]() {
     sh_ctx::Prepared& q = c->prep;
@@ -1558,7 +1564,7 @@ static void start_prepare(sh_ctx* c) {
     q.rc = hull_host_phase(c, c->hull_in, q.slot, 0, q.B, &q.bad_mesh, &q.hull_ms, &q.err, true);
     if (q.rc == SH_OK && can_upload) {
       // the records go to the device as soon as the running step no longer reads the hull.* buffers (after its k_obb_pick)
-      if (hipStreamWaitEvent(c->copy_stream, c->obb_done_ev, 0) == hipSuccess && hull_upload(c, q.slot, q.B, dst.p, c->copy_stream) == hipSuccess &&
+      if (hipStreamWaitEvent(c->copy_stream, c->obb_done_ev, 0) == hipSuccess && hull_upload(c, q.slot, q.B, dst, c->copy_stream) == hipSuccess &&
           hipStreamSynchronize(c->copy_stream) == hipSuccess)
         q.uploaded = true;
     }
@@ -1698,11 +1704,12 @@ static int start_prepare_staged(sh_ctx* c, int B, std::shared_ptr<const StlJob> 
   p.active = true; p.staged = true; p.slot = c->hslot; p.B = S.B; p.gen = hulls ? c->batch_gen + 1 : ~0ull; p.rc = SH_OK; p.bad_mesh = -1; p.d2h_ms = p.hull_ms = 0; p.err.clear();
   p.uploaded = false;
   const HullPre hp = hullpre_ptrs(c, ".s");
-  struct Dst { void* p[6]; } dst = {{c->bufs["hull.hv"].p, c->bufs["hull.normals"].p, c->bufs["hull.edges"].p, c->bufs["hull.nv"].p, c->bufs["hull.nf"].p, c->bufs["hull.ne"].p}};
+  const HullRec dst = {(double*)c->bufs["hull.hv"].p, (double*)c->bufs["hull.normals"].p, (int*)c->bufs["hull.edges"].p, (int*)c->bufs["hull.nv"].p, (int*)c->bufs["hull.nf"].p,
+                       (int*)c->bufs["hull.ne"].p};      // (the whole batch's, whatever window the context stands at)
   struct Side { long long *voff, *foff; float* verts; int* faces; } side = {(long long*)c->bufs["voff.s"].p, (long long*)c->bufs["foff.s"].p, (float*)c->bufs["verts.s"].p, (int*)c->bufs["faces.s"].p};
   // early upload only into buffers that will not be re-allocated by the commit (alloc_batch grows them for a larger batch)
   const size_t nB = (size_t)S.B;
-  const bool can_upload = c->obb_done_ev != nullptr && dst.p[0] && c->bufs["hull.hv"].bytes >= nB * c->hcap.v * 24 && c->bufs["hull.normals"].bytes >= nB * c->hcap.f * 24 &&
+  const bool can_upload = c->obb_done_ev != nullptr && dst.hv && c->bufs["hull.hv"].bytes >= nB * c->hcap.v * 24 && c->bufs["hull.normals"].bytes >= nB * c->hcap.f * 24 &&
                           c->bufs["hull.edges"].bytes >= nB * c->hcap.e * 16 && c->bufs["hull.nv"].bytes >= nB * 4 && c->bufs["hull.nf"].bytes >= nB * 4 && c->bufs["hull.ne"].bytes >= nB * 4;
   p.th = std::thread([c, hp, dst, side, can_upload, hulls, stl, B, phase0]() {
     sh_ctx::Prepared& q = c->prep;
@@ -1750,7 +1757,7 @@ static int start_prepare_staged(sh_ctx* c, int B, std::shared_ptr<const StlJob> 
     q.rc = hull_host_phase(c, S.pts, q.slot, 0, B, &q.bad_mesh, &q.hull_ms, &q.err, true);
     if (dbg) fprintf(stderr, "[sh] staged batch: copies enqueued %.2f ms, sizes known %.2f, hull points back %.2f, hulls done %.2f (hull phase %.2f)\n", t_p0, t_meta, t_pts, since(), q.hull_ms);
     if (q.rc == SH_OK && can_upload) {
-      if (hipStreamWaitEvent(c->copy_stream, c->obb_done_ev, 0) == hipSuccess && hull_upload(c, q.slot, B, dst.p, c->copy_stream) == hipSuccess &&
+      if (hipStreamWaitEvent(c->copy_stream, c->obb_done_ev, 0) == hipSuccess && hull_upload(c, q.slot, B, dst, c->copy_stream) == hipSuccess &&
           hipStreamSynchronize(c->copy_stream) == hipSuccess)
         q.uploaded = true;
     }
@@ -1891,6 +1898,7 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, c
   std::vector<double> P;
   shhull::Hull H;
   int rc = SH_OK;
+  WindowScope whole(c, 0, B);      // (the copies below index the batch's buffers by humerus)
   for (int b = 0; b < B; ++b) {
     if (st.gave_up()[b] == 0) continue;
     const long long v0 = c->h_voff[b], nv = c->h_voff[b + 1] - v0;
@@ -1910,21 +1918,24 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, c
     std::vector<double> hvd(3 * (size_t)hn);
     for (int i = 0; i < hn; ++i)
       for (int k = 0; k < 3; ++k) hvd[3 * (size_t)i + k] = P[3 * (size_t)H.vert_ids[i] + k];
-    c->b0 = 0; c->Bwin = B;
     const int counts[3] = {hn, fn, en}, one = 1;
-    // (pageable sources: hipMemcpyAsync stages them before it returns)
-    HIPCHK(c, hipMemcpyAsync(buf<double>(c, "hull.hv") + (size_t)b * c->hcap.v * 3, hvd.data(), hvd.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(buf<double>(c, "hull.normals") + (size_t)b * c->hcap.f * 3, H.normals.data(), (size_t)fn * 24, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hull.edges") + (size_t)b * c->hcap.e * 4, H.edges.data(), (size_t)en * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hull.nv") + b, &counts[0], 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hull.nf") + b, &counts[1], 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hull.ne") + b, &counts[2], 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hulld.skip") + b, &one, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(buf<int>(c, "err") + b, 0, 4, c->stream));
-    if (c->open_mode != SH_OPEN_ERROR) HIPCHK(c, hipMemsetAsync(buf<int>(c, "open.stats") + 2 * (size_t)b, 0, 8, c->stream));      // (the void first pass counted too)
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // the sources above are locals
-    c->skip_nfmax = std::max(c->skip_nfmax, fn);
-    { WindowScope one(c, b, 1); rc = run_window(c, tk.mask, -1, fn); }
+    {
+      WindowScope alone(c, b, 1);      // humerus b as a window of one: the hull record's rows, its status words and its stages
+      const HullRec h = hull_rec(c);
+      // (pageable sources: hipMemcpyAsync stages them before it returns)
+      HIPCHK(c, hipMemcpyAsync(h.hv, hvd.data(), hvd.size() * 8, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h.normals, H.normals.data(), (size_t)fn * 24, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h.edges, H.edges.data(), (size_t)en * 16, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h.nv, &counts[0], 4, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h.nf, &counts[1], 4, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(h.ne, &counts[2], 4, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hulld.skip"), &one, 4, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemsetAsync(buf<int>(c, "err"), 0, 4, c->stream));
+      if (c->open_mode != SH_OPEN_ERROR) HIPCHK(c, hipMemsetAsync(buf<int>(c, "open.stats"), 0, 8, c->stream));      // (the void first pass counted too)
+      HIPCHK(c, hipStreamSynchronize(c->stream));      // the sources above are locals
+      c->skip_nfmax = std::max(c->skip_nfmax, fn);
+      rc = run_window(c, tk.mask, -1, fn);
+    }
     if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
     // the record and the status word of this humerus -> where the run's results were parked (or the caller's device buffer)
     if (void* dst = tk.host_out ? c->bufs["out.landmarks" + tslot].p : (void*)tk.out_arg) { int erc = emit_records(c, dst, b, 1, tk.rows, tk.rec); if (erc != SH_OK) return erc; }
