@@ -454,6 +454,74 @@ int sh_resect_planes_seat (sh_ctx*, const double* planes, int P, const sh_implan
 int sh_resect_offsets_seat(sh_ctx*, const sh_cut_offset* offs, int P, const sh_implant_head* heads, int K, int center_mode,
                            sh_resection* out, sh_head_fit* fit_out, sh_seat* seat_out /* B x P x K */);
 
+/* ---- canal profiles and the fit of a catalogue of stems below every cut ----------------------------------------------------
+ * The other half of the step the reference leaves open (arthroplasty.py:178-182, the commented-out `HumeralImplantation` that
+ * "continues from the humeral head osteotomy and places the implant"): how wide the bone is around the canal axis below a cut,
+ * and which stems of a catalogue go down there.  Both on the device from the resident float32 mesh (k_stem.h); no section of the
+ * mesh goes to the host.
+ *
+ * Canal frame of humerus b: a rigid 4 x 4 matrix T (row-major, CT -> frame), the caller's or the record's csys_articular (origin
+ * at the canal-axis midpoint, z the canal pointing proximally, x / y posterior-anterior / lateral-medial).  A vertex is widened
+ * to float64 and mapped as ((T[4i] x + T[4i+1] y) + T[4i+2] z) + T[4i+3] (sh_scalar.h canal_map_point).
+ *   grid      level l is the plane z = z_l = z0 - l dz of the frame (dz > 0: levels run distally), l < L; ray (l, a) starts at
+ *             (0, 0, z_l) and goes along (cos t_a, sin t_a, 0), t_a = (2 pi a) / A, a < A.  The A directions are computed once
+ *             on the host and every kernel reads that table ("canal.dirs").
+ *   hit rule  Moller-Trumbore as SH_STAGE_ANP's rays state it (k_anp.h k_rays_hit; sh_scalar.h canal_ray_hit): |det| > 1e-12,
+ *             u >= 0, w >= 0, u + w <= 1 (closed), t > 1e-9.  near[b][l][a] is the smallest t over ALL faces of humerus b, far the
+ *             largest; no hit: near = +inf, far = 0.  Minimum and maximum do not depend on an order: a humerus' rows are the same
+ *             bits whatever the batch, its position in it, L or the tiling.  Named buffers "canal.near" / "canal.far"
+ *             (B x L x A doubles, sh_fetch), valid until the next upload / commit.
+ *   level     r_a = near[l][a], p_a = r_a (cos t_a, sin t_a).  r_min / r_max with their angle indices (the smaller index wins a
+ *             tie), r_mean = sum r_a / A, area = (0.5 sin(2 pi / A)) sum r_a r_(a+1), centroid = sum (p_a + p_(a+1)) c_a /
+ *             (3 sum c_a) with c_a = cross(p_a, p_(a+1)) (zero when sum c_a is), extent_x / extent_y = [min, max] of the p_a's
+ *             coordinates, wall_min = min (far - near), n_hit = rays with a hit.  Sums are taken lane-strided in angle order by
+ *             one wave and added by one fixed shuffle tree.  A level with n_hit < A has status SH_ERR_GEOMETRY, n_hit valid and
+ *             every other field zero; a humerus whose record failed (frames == NULL) has that status in all of its levels,
+ *             near = +inf and far = 0.  A bad level never fails the batch. */
+typedef struct sh_canal_grid { double z0, dz; int32_t L, A; } sh_canal_grid;
+typedef struct sh_canal_level {
+  double r_min, r_max, r_mean, area, centroid[2], extent_x[2], extent_y[2], wall_min;
+  int32_t a_min, a_max, n_hit, status;
+} sh_canal_level;
+/* L in 1..1024, A in 3..256; a non-finite value, dz <= 0 or a frame that is not rigid (non-finite, rotation rows not orthonormal
+ * to 1e-9, determinant not positive, last row not 0 0 0 1): SH_ERR_ARG.  frames == NULL needs a collected run of the resident
+ * batch with SH_STAGE_ANP | SH_STAGE_CSYS (SH_ERR_STATE otherwise, as sh_resect_offsets); explicit frames need a resident batch
+ * only.  Not while runs are in flight (SH_ERR_STATE).  Every output pointer may be NULL. */
+int sh_canal_profile(sh_ctx*, const sh_canal_grid* grid, const double* frames /* B x 16, or NULL: each record's csys_articular */,
+                     double* near_out /* B x L x A, host */, double* far_out /* B x L x A, host */, sh_canal_level* levels_out /* B x L, host */);
+
+/* A stem is a frustum about the canal axis: r(d) = r_prox + ((r_tip - r_prox) d) / length at depth 0 <= d <= length below its
+ * entry point (sh_scalar.h stem_radius_at).  sh_resect_stems fits K stems below each of the B x P planes of the LAST
+ * sh_resect_* call against the LAST sh_canal_profile of the same resident batch (SH_ERR_STATE when either is missing or a new
+ * batch was uploaded since); K in 1..SH_STEM_MAX, every number of a stem finite and > 0 (SH_ERR_ARG).  Per (b, p, k), with the
+ * plane (o, n) mapped into the frame and n^ = n / |n| there:
+ *   entry     where the frame's z axis pierces the plane: z_entry = o_z + (o_x n^_x + o_y n^_y) / n^_z, `entry` the point in CT.
+ *             |n^_z| < 1e-12: status SH_ERR_GEOMETRY.
+ *   levels    the levels with 0 <= d_l <= length, d_l = z_entry - z_l.  A grid that does not reach from z_entry down to
+ *             z_entry - length (z0 < z_entry or z_(L-1) > z_entry - length): status SH_ERR_ARG, nothing is extrapolated.
+ *   samples   (l, a) of a used level counts when the stem's surface point q = (r(d_l) cos t_a, r(d_l) sin t_a, z_l) lies on the
+ *             retained side, dot(q - o, n^) <= 0 (the head piece is on the normal's side, as everywhere in sh_resection).
+ *   min_clearance = min (near - r(d_l)) over the counted samples that have a hit, with its `depth` d_l, `angle_index` a and
+ *             `direction` (the ray's unit direction in CT); the smaller (l, a) wins a tie.  scale_max = min near / r(d_l): the
+ *             largest uniform radial scale of the stem that still clears.  Without such a sample: 0, 0, -1, zeros, 0.
+ *   n_samples counted samples, n_breach those with near - r < 0, n_open those without a hit.
+ *   fill      pi r(d_l)^2 / area_l over the used levels whose sh_canal_level.status is 0 and whose area is > 0: fill_mean (added
+ *             in level order by one lane), fill_max with fill_max_depth (the first level wins a tie); zeros without such a level.
+ *   fits      1 when n_breach = 0, n_open = 0 and n_samples > 0.
+ *   status    the humerus' failed record or profile frame, the cut's status (sh_resection.status) or one of the two above; every
+ *             other field is zero then.  A bad record never fails the batch.
+ * A record depends on its cut, its stem and the profile alone: not on B, P, K or the stem's place in the catalogue (lanes stride
+ * the samples in (l, a) order, minima carry their sample index through one fixed shuffle tree; no floating-point atomics). */
+#define SH_STEM_MAX 64
+typedef struct sh_stem { double length, r_prox, r_tip; } sh_stem;
+typedef struct sh_stem_fit {
+  double entry[3], z_entry;
+  double min_clearance, depth, direction[3], scale_max;
+  double fill_mean, fill_max, fill_max_depth;
+  int32_t angle_index, n_samples, n_breach, n_open, fits, status;
+} sh_stem_fit;
+int sh_resect_stems(sh_ctx*, const sh_stem* stems, int K, sh_stem_fit* out /* B x P x K, host */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

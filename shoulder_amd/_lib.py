@@ -137,6 +137,49 @@ SEAT_DTYPE = np.dtype([
 assert SEAT_DTYPE.itemsize == ctypes.sizeof(Seat) and IMPLANT_HEAD_DTYPE.itemsize == ctypes.sizeof(ImplantHead)
 
 
+class CanalGrid(ctypes.Structure):
+    """sh_canal_grid: levels z_l = z0 - l dz (l < L) and A rays per level in a humerus' canal frame."""
+    _fields_ = [("z0", ctypes.c_double), ("dz", ctypes.c_double), ("L", ctypes.c_int32), ("A", ctypes.c_int32)]
+
+
+class CanalLevel(ctypes.Structure):
+    """sh_canal_level: the polar profile of one (humerus, level) about the canal axis."""
+    _fields_ = [("r_min", ctypes.c_double), ("r_max", ctypes.c_double), ("r_mean", ctypes.c_double), ("area", ctypes.c_double),
+                ("centroid", ctypes.c_double * 2), ("extent_x", ctypes.c_double * 2), ("extent_y", ctypes.c_double * 2),
+                ("wall_min", ctypes.c_double), ("a_min", ctypes.c_int32), ("a_max", ctypes.c_int32), ("n_hit", ctypes.c_int32),
+                ("status", ctypes.c_int32)]
+
+
+CANAL_LEVEL_DTYPE = np.dtype([
+    ("r_min", "<f8"), ("r_max", "<f8"), ("r_mean", "<f8"), ("area", "<f8"), ("centroid", "<f8", (2,)), ("extent_x", "<f8", (2,)),
+    ("extent_y", "<f8", (2,)), ("wall_min", "<f8"), ("a_min", "<i4"), ("a_max", "<i4"), ("n_hit", "<i4"), ("status", "<i4")])
+assert CANAL_LEVEL_DTYPE.itemsize == ctypes.sizeof(CanalLevel)
+STEM_MAX = 64
+
+
+class Stem(ctypes.Structure):
+    """sh_stem: a frustum about the canal axis, r(d) = r_prox + (r_tip - r_prox) d / length."""
+    _fields_ = [("length", ctypes.c_double), ("r_prox", ctypes.c_double), ("r_tip", ctypes.c_double)]
+
+
+STEM_DTYPE = np.dtype([("length", "<f8"), ("r_prox", "<f8"), ("r_tip", "<f8")])
+
+
+class StemFit(ctypes.Structure):
+    """sh_stem_fit: how one stem of a catalogue sits in the canal below one (humerus, plane) cut."""
+    _fields_ = [("entry", ctypes.c_double * 3), ("z_entry", ctypes.c_double), ("min_clearance", ctypes.c_double), ("depth", ctypes.c_double),
+                ("direction", ctypes.c_double * 3), ("scale_max", ctypes.c_double), ("fill_mean", ctypes.c_double), ("fill_max", ctypes.c_double),
+                ("fill_max_depth", ctypes.c_double), ("angle_index", ctypes.c_int32), ("n_samples", ctypes.c_int32), ("n_breach", ctypes.c_int32),
+                ("n_open", ctypes.c_int32), ("fits", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+STEM_FIT_DTYPE = np.dtype([
+    ("entry", "<f8", (3,)), ("z_entry", "<f8"), ("min_clearance", "<f8"), ("depth", "<f8"), ("direction", "<f8", (3,)), ("scale_max", "<f8"),
+    ("fill_mean", "<f8"), ("fill_max", "<f8"), ("fill_max_depth", "<f8"), ("angle_index", "<i4"), ("n_samples", "<i4"), ("n_breach", "<i4"),
+    ("n_open", "<i4"), ("fits", "<i4"), ("status", "<i4")])
+assert STEM_FIT_DTYPE.itemsize == ctypes.sizeof(StemFit) and STEM_DTYPE.itemsize == ctypes.sizeof(Stem)
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -151,7 +194,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring",
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
-           "sh_resect_planes_seat", "sh_resect_offsets_seat"]
+           "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems"]
 
 _lib = None
 
@@ -248,5 +291,8 @@ def load(build_if_missing=True):
     if not alt or hasattr(L, "sh_resect_planes_seat"):      # (tools/time_seat.py parent)
         L.sh_resect_planes_seat.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
         L.sh_resect_offsets_seat.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+    if not alt or hasattr(L, "sh_canal_profile"):      # (tools/time_stem.py parent)
+        L.sh_canal_profile.argtypes = [vp, ctypes.POINTER(CanalGrid), vp, vp, vp, vp]
+        L.sh_resect_stems.argtypes = [vp, vp, ctypes.c_int, vp]
     _lib = L
     return L

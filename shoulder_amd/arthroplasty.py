@@ -132,6 +132,37 @@ class HumeralHeadOsteotomy:
         seats = bone._engine.resect(planes=np.concatenate([p, n]).reshape(1, 1, 6), fit=True, heads=heads, seat_center=center)[2][0, 0]
         return [{k: (s[k].copy() if s[k].ndim else s[k].item()) for k in s.dtype.names} for s in seats]
 
+    def _entry_height(self) -> float:
+        """height, in the canal / articular frame, at which the canal axis pierces the current plane"""
+        n = self._normal / np.linalg.norm(self._normal)
+        return float(self._point[2] + (self._point[0] * n[0] + self._point[1] * n[1]) / n[2])
+
+    def canal_profile(self, z0=None, dz=1.0, L=None, A=64, fetch=("levels",)):
+        """The polar profile of the humerus about its canal axis in the canal / articular frame (sh_canal_profile with the frame this
+        object read the anatomic-neck plane in): by default the grid starts 5 mm above the point where the axis enters the current
+        plane, has dz = 1 mm and spans 160 mm.  Returns what Engine.canal_profile returns, for this humerus alone; the profile stays on
+        the device for `stem_fit`."""
+        z0 = self._entry_height() + 5.0 if z0 is None else float(z0)
+        L = int(round(160.0 / dz)) + 1 if L is None else int(L)
+        bone = self._humerus
+        bone._ensure_loaded()
+        got = bone._engine.canal_profile(z0, dz, L, A, frames=self._to_anp.reshape(1, 4, 4), fetch=fetch)
+        self._profiled = bone._engine
+        return tuple(g[0] for g in got) if isinstance(got, tuple) else got[0]
+
+    def stem_fit(self, stems) -> list:
+        """How each stem of `stems` -- (length, r_prox, r_tip) rows -- sits in the canal below the current cut (sh_resect_planes with
+        B = P = 1, then sh_resect_stems against the last `canal_profile()`, which is taken with its defaults when there is none): K dicts
+        with the fields of sh_stem_fit, in CT."""
+        bone = self._humerus
+        bone._ensure_loaded()
+        if getattr(self, "_profiled", None) is not bone._engine:
+            self.canal_profile()
+        p, n = self._plane_ct()
+        bone._engine.resect(planes=np.concatenate([p, n]).reshape(1, 1, 6))
+        fits = bone._engine.resect_stems(stems)[0, 0]
+        return [{k: (s[k].copy() if s[k].ndim else s[k].item()) for k in s.dtype.names} for s in fits]
+
     # ---- offsets (arthroplasty.py:89-175) ------------------------------------------------------------------
     def offset_retroversion(self, deg: float) -> None:
         """more retroversion for positive `deg` (the azimuth decreases on a left humerus, increases on a right one)"""
@@ -186,3 +217,20 @@ def best_seat(seats, max_overhang_mm):
         st, ov, cov = (np.array([s[k] for s in seats]) for k in ("status", "max_overhang", "coverage"))
     ok = np.nonzero((st == 0) & (ov <= max_overhang_mm))[0]
     return int(ok[np.argmax(cov[ok])]) if len(ok) else None
+
+
+def best_stem(fits, stems):
+    """Index of the stem with the largest `r_prox`, then the largest `length` (the first of equals), among those with `status` == 0 and
+    `fits` == 1, or None.  fits: a 1-D structured array of _lib.STEM_FIT_DTYPE or a list of dicts with its fields; stems: the catalogue
+    they were fitted from, (length, r_prox, r_tip) rows.  Pure NumPy."""
+    if isinstance(fits, np.ndarray) and fits.dtype.names:
+        st, ok = fits["status"].reshape(-1), fits["fits"].reshape(-1)
+    else:
+        st, ok = (np.array([f[k] for f in fits]) for k in ("status", "fits"))
+    cat = np.asarray(stems)
+    cat = np.stack([cat[k] for k in ("length", "r_prox", "r_tip")], axis=-1) if cat.dtype.names else cat
+    cat = np.asarray(cat, dtype=np.float64).reshape(-1, 3)
+    idx = np.nonzero((st == 0) & (ok == 1))[0]
+    if len(idx) == 0:
+        return None
+    return int(min(idx, key=lambda i: (-cat[i, 1], -cat[i, 0], i)))

@@ -166,6 +166,9 @@ struct sh_ctx {
   uint32_t rec_mask = 0;
   unsigned long long rec_gen = ~0ull, resect_gen = ~0ull;
   int resect_P = 0;
+  // sh_canal_profile (k_stem.h): the grid and the batch of the last profile ("canal.*": sh_resect_stems reads them)
+  unsigned long long canal_gen = ~0ull;
+  sh_canal_grid canal_grid = {0.0, 0.0, 0, 0};
   hipStream_t copy_stream = nullptr;
   hipEvent_t stl_counted_ev = nullptr;      // sh_stage_stl: the device has counted the merged vertices / faces
   // side stream of the stage runner: the distal slice set and the rectangles of the trans-epicondylar stage hang on nothing but the

@@ -869,4 +869,111 @@ SH_HD double seat_surface_rms(const double* m, const double* c, double R) {
   return sqrt(E > 0.0 ? E : 0.0) / (2.0 * R);
 }
 
+// ---- canal profile and stems below a cut (include/shoulder_hip.h sh_canal_profile / sh_resect_stems; k_stem.h) -------------
+// A point into the canal frame T (row-major 4 x 4, CT -> frame), in this order of operations on host and device.
+SH_HD void canal_map_point(const double* T, double x, double y, double z, double* q) {
+  q[0] = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+  q[1] = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+  q[2] = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+}
+// a direction into the frame (rotation part), and a frame direction back into CT (its transpose)
+SH_HD void canal_map_dir(const double* T, const double* v, double* q) {
+  q[0] = (T[0] * v[0] + T[1] * v[1]) + T[2] * v[2];
+  q[1] = (T[4] * v[0] + T[5] * v[1]) + T[6] * v[2];
+  q[2] = (T[8] * v[0] + T[9] * v[1]) + T[10] * v[2];
+}
+SH_HD void canal_unmap_dir(const double* T, const double* v, double* q) {
+  q[0] = (T[0] * v[0] + T[4] * v[1]) + T[8] * v[2];
+  q[1] = (T[1] * v[0] + T[5] * v[1]) + T[9] * v[2];
+  q[2] = (T[2] * v[0] + T[6] * v[1]) + T[10] * v[2];
+}
+// Moller-Trumbore of the ray o + t d against the triangle (A, B, C), k_rays_hit's statement (k_anp.h) operation by operation:
+// |det| > 1e-12, u >= 0, w >= 0, u + w <= 1 closed, t > 1e-9
+SH_HD bool canal_ray_hit(const double* o, const double* d, const double* A, const double* B, const double* C, double* t_out) {
+  const double e1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+  const double e2[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+  const double tv[3] = {o[0] - A[0], o[1] - A[1], o[2] - A[2]};
+  double qv[3], pv[3];
+  cross3(tv, e1, qv);
+  cross3(d, e2, pv);
+  const double det = dot3(e1, pv);
+  if (!(fabs(det) > 1e-12)) return false;
+  const double inv = 1.0 / det;
+  const double uu = dot3(tv, pv) * inv;
+  const double ww = dot3(d, qv) * inv;
+  const double t = dot3(e2, qv) * inv;
+  if (!(uu >= 0 && ww >= 0 && uu + ww <= 1 && t > 1e-9)) return false;
+  *t_out = t;
+  return true;
+}
+// The levels a face with frame heights [zmin, zmax] can be hit at, z_l = z0 - l dz: z_l in [zmin, zmax] <=> (z0 - zmax) / dz <= l
+// <= (z0 - zmin) / dz, rounded outwards and widened by one level each side (the full test decides), clamped to [0, L - 1];
+// empty: *lo > *hi.  A superset of what canal_ray_hit accepts, never less.
+SH_HD void canal_level_range(double z0, double dz, int L, double zmin, double zmax, int* lo, int* hi) {
+  double a = floor((z0 - zmax) / dz) - 1.0, b = ceil((z0 - zmin) / dz) + 1.0;
+  if (!(a > 0.0)) a = 0.0;
+  if (!(b < (double)(L - 1))) b = (double)(L - 1);
+  *lo = a > (double)L ? L : (int)a;
+  *hi = b < -1.0 ? -1 : (int)b;
+}
+// The angle indices the projection (x, y)[3] of a face can be hit at from the axis, t_a = (2 pi a) / A: the arc of its three
+// vertex angles taken about the first one, rounded outwards and widened by one index each side; *a0 in [0, A) the first index,
+// *n the number of indices (they wrap: a0, a0 + 1, ... mod A).  A projection that holds the origin, has it on an edge or comes
+// close to that (an arc of 3 rad or more; pi for the origin on an edge) takes all A angles, and so does an arc of A indices or more.
+SH_HD void canal_angle_range(const double* x, const double* y, int A, int* a0, int* n) {
+  const double pi = 3.14159265358979323846, two_pi = 2.0 * pi;
+  const double p0 = atan2(y[0], x[0]);
+  double d1 = atan2(y[1], x[1]) - p0, d2 = atan2(y[2], x[2]) - p0;
+  d1 = d1 > pi ? d1 - two_pi : (d1 < -pi ? d1 + two_pi : d1);
+  d2 = d2 > pi ? d2 - two_pi : (d2 < -pi ? d2 + two_pi : d2);
+  const double lo = fmin(0.0, fmin(d1, d2)), hi = fmax(0.0, fmax(d1, d2));
+  *a0 = 0; *n = A;
+  if (!(hi - lo < 3.0)) return;
+  const double step = two_pi / (double)A;
+  const double s = floor((p0 + lo) / step) - 1.0, e = ceil((p0 + hi) / step) + 1.0;
+  const double cnt = (e - s) + 1.0;
+  if (!(cnt < (double)A)) return;
+  const int si = (int)s;
+  *a0 = ((si % A) + A) % A; *n = (int)cnt;
+}
+// radius of the frustum stem (length, r_prox, r_tip) at depth d below its entry
+SH_HD double stem_radius_at(double length, double r_prox, double r_tip, double d) { return r_prox + ((r_tip - r_prox) * d) / length; }
+// whether the stem's surface point (r ca, r sa, zl) lies on the retained side of the plane (of, un) given in the frame
+SH_HD bool stem_sample_counts(double r, double ca, double sa, double zl, const double* of, const double* un) {
+  const double dx = r * ca - of[0], dy = r * sa - of[1], dz = zl - of[2];
+  return (dx * un[0] + dy * un[1]) + dz * un[2] <= 0.0;
+}
+// The plane (o, n) of a cut (CT) in the frame T: of its point, un its unit normal there, *ze the height at which the frame's z axis
+// pierces it, entry that point in CT.  0, or SH_ERR_GEOMETRY when the plane does not meet the axis (|un_z| < 1e-12) or is not finite.
+SH_HD int stem_entry(const double* T, const double* o, const double* n, double* of, double* un, double* ze, double* entry) {
+  canal_map_point(T, o[0], o[1], o[2], of);
+  canal_map_dir(T, n, un);
+  const double len = norm3(un);
+  if (!(len > 0.0) || !(len < 1e300)) return SH_ERR_GEOMETRY_DEV;
+  un[0] /= len; un[1] /= len; un[2] /= len;
+  if (!(fabs(un[2]) >= 1e-12)) return SH_ERR_GEOMETRY_DEV;
+  const double z = of[2] + (of[0] * un[0] + of[1] * un[1]) / un[2];
+  if (!(fabs(z) < 1e300)) return SH_ERR_GEOMETRY_DEV;
+  *ze = z;
+  const double back[3] = {0.0 - T[3], 0.0 - T[7], z - T[11]};
+  canal_unmap_dir(T, back, entry);
+  return 0;
+}
+// first and last level of the grid with 0 <= d_l <= length, d_l = ze - (z0 - l dz) as every user computes it (monotone in l);
+// false when the grid does not reach from ze down to ze - length.  *l0 > *l1: no level falls inside.
+SH_HD double stem_level_depth(double z0, double dz, int l, double ze) { return ze - (z0 - (double)l * dz); }
+SH_HD bool stem_level_span(double z0, double dz, int L, double ze, double length, int* l0, int* l1) {
+  if (!(z0 >= ze) || !(z0 - (double)(L - 1) * dz <= ze - length)) return false;
+  double g = ceil((z0 - ze) / dz);
+  int a = g < 0.0 ? 0 : (g > (double)(L - 1) ? L - 1 : (int)g);
+  while (a > 0 && stem_level_depth(z0, dz, a - 1, ze) >= 0.0) --a;
+  while (a < L && stem_level_depth(z0, dz, a, ze) < 0.0) ++a;
+  g = floor((z0 - (ze - length)) / dz);
+  int b = g < 0.0 ? 0 : (g > (double)(L - 1) ? L - 1 : (int)g);
+  while (b < L - 1 && stem_level_depth(z0, dz, b + 1, ze) <= length) ++b;
+  while (b >= 0 && stem_level_depth(z0, dz, b, ze) > length) --b;
+  *l0 = a; *l1 = b;
+  return true;
+}
+
 }  // namespace sh

@@ -13,6 +13,7 @@
 #include "k_resect.h"
 #include "k_headfit.h"
 #include "k_seat.h"
+#include "k_stem.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -1053,6 +1054,94 @@ int sh_resect_ring(sh_ctx* c, int b, int p, double* out, int cap, int* n_out) {
   *n_out = r.n_ring + 1;
   if (!out || cap < r.n_ring + 1) return SH_OK;
   HIPCHK(c, hipMemcpy(out, v.ring, (size_t)(r.n_ring + 1) * 24, hipMemcpyDeviceToHost));
+  return SH_OK;
+}
+
+// ---- canal profiles and stems below the cuts of the last resection (k_stem.h) ------------------------------------------------------
+static bool canal_frame_ok(const double* T) {
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(T[i])) return false;
+  if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return false;
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j) {
+      const double d = (T[4 * i] * T[4 * j] + T[4 * i + 1] * T[4 * j + 1]) + T[4 * i + 2] * T[4 * j + 2];
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-9)) return false;
+    }
+  return det3_of4(T) > 0.0;
+}
+
+int sh_canal_profile(sh_ctx* c, const sh_canal_grid* g, const double* frames, double* near_out, double* far_out, sh_canal_level* levels_out) {
+  if (!c || !g || !std::isfinite(g->z0) || !std::isfinite(g->dz) || !(g->dz > 0.0) || g->L < 1 || g->L > 1024 || g->A < 3 || g->A > 256)
+    return fail(c, SH_ERR_ARG, "sh_canal_profile: bad grid (finite z0, dz > 0, L in 1..1024, A in 3..256)");
+  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_canal_profile: no meshes uploaded");
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_canal_profile: runs are in flight (sh_collect them first)");
+  const int B = c->B, L = g->L, A = g->A;
+  if (frames) {
+    for (int b = 0; b < B; ++b)
+      if (!canal_frame_ok(frames + 16 * (size_t)b)) return fail(c, SH_ERR_ARG, "sh_canal_profile: frame " + std::to_string(b) + " is not a rigid CT -> frame matrix");
+  } else if (!resect_has_records(c)) {
+    return fail(c, SH_ERR_STATE, "sh_canal_profile: frames == NULL needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)B * L * A;
+  int rc;
+  ENS_SHARED("canal.near", n * 8, 8); ENS_SHARED("canal.far", n * 8, 8); ENS_SHARED("canal.levels", (size_t)B * L * sizeof(sh_canal_level), 8);
+  ENS_SHARED("canal.frames", (size_t)B * 128, 8); ENS_SHARED("canal.status", (size_t)B * 4, 4); ENS_SHARED("canal.dirs", (size_t)A * 16, 8);
+  auto at = [c](const char* name) { return c->bufs.find(name)->second.p; };
+  double* d_near = (double*)at("canal.near"); double* d_far = (double*)at("canal.far"); sh_canal_level* d_lv = (sh_canal_level*)at("canal.levels");
+  double* d_fr = (double*)at("canal.frames"); int* d_st = (int*)at("canal.status"); double* d_dirs = (double*)at("canal.dirs");
+  c->canal_gen = ~0ull;
+  const double two_pi = 2.0 * 3.14159265358979323846;
+  std::vector<double> dirs(2 * (size_t)A);
+  for (int a = 0; a < A; ++a) { const double t = (two_pi * (double)a) / (double)A; dirs[2 * a] = std::cos(t); dirs[2 * a + 1] = std::sin(t); }
+  HIPCHK(c, hipMemcpyAsync(d_dirs, dirs.data(), dirs.size() * 8, hipMemcpyHostToDevice, c->stream));
+  if (frames) {
+    HIPCHK(c, hipMemcpyAsync(d_fr, frames, (size_t)B * 128, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_st, 0, (size_t)B * 4, c->stream));
+  } else {
+    LAUNCH(c, "k_canal_frames", k_canal_frames, dim3((unsigned)((B + 63) / 64)), dim3(64), (const sh_landmarks*)at("landmarks"), B, d_fr, d_st);
+  }
+  LAUNCH(c, "k_canal_clear", k_canal_clear, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), (unsigned long long*)d_near,
+         (unsigned long long*)d_far, (long long)n);
+  const long long tmax = std::max<long long>(1, (c->maxF + SH_CANAL_TILE - 1) / SH_CANAL_TILE);
+  LAUNCH(c, "k_canal_rays", k_canal_rays, dim3((unsigned)tmax, (unsigned)B), dim3(SH_CANAL_TILE), (const float*)at("verts"), (const int*)at("faces"),
+         (const long long*)at("voff"), (const long long*)at("foff"), (const double*)d_fr, (const int*)d_st, (const double*)d_dirs, g->z0, g->dz, L, A,
+         (unsigned long long*)d_near, (unsigned long long*)d_far);
+  LAUNCH(c, "k_canal_levels", k_canal_levels, dim3((unsigned)(B * L)), dim3(64), (const double*)d_near, (const double*)d_far, (const int*)d_st,
+         (const double*)d_dirs, 0.5 * std::sin(two_pi / (double)A), L, A, d_lv);
+  if (near_out) HIPCHK(c, hipMemcpyAsync(near_out, d_near, n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (far_out) HIPCHK(c, hipMemcpyAsync(far_out, d_far, n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (levels_out) HIPCHK(c, hipMemcpyAsync(levels_out, d_lv, (size_t)B * L * sizeof(sh_canal_level), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->canal_grid = *g; c->canal_gen = c->batch_gen;
+  return SH_OK;
+}
+
+int sh_resect_stems(sh_ctx* c, const sh_stem* stems, int K, sh_stem_fit* out) {
+  if (!c || !stems || !out || K < 1 || K > SH_STEM_MAX) return fail(c, SH_ERR_ARG, "sh_resect_stems: bad argument (K in 1..64)");
+  static_assert(sizeof(sh_stem) == 3 * sizeof(double), "sh_stem is three doubles");
+  for (int i = 0; i < 3 * K; ++i) {
+    const double x = ((const double*)stems)[i];
+    if (!std::isfinite(x) || !(x > 0.0)) return fail(c, SH_ERR_ARG, "sh_resect_stems: length, r_prox and r_tip of a stem must be finite and > 0");
+  }
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_stems: runs are in flight (sh_collect them first)");
+  if (c->B < 1 || c->resect_gen != c->batch_gen || c->resect_P < 1) return fail(c, SH_ERR_STATE, "sh_resect_stems: no resection of the resident batch");
+  if (c->canal_gen != c->batch_gen) return fail(c, SH_ERR_STATE, "sh_resect_stems: no canal profile of the resident batch");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B, P = c->resect_P;
+  const size_t n = (size_t)B * P * K;
+  int rc;
+  ENS_SHARED("stem.catalogue", (size_t)K * sizeof(sh_stem), 8); ENS_SHARED("stem.out", n * sizeof(sh_stem_fit), 8);
+  auto at = [c](const char* name) { return c->bufs.find(name)->second.p; };
+  const ResectView v = resect_view(c);
+  sh_stem* d_cat = (sh_stem*)at("stem.catalogue"); sh_stem_fit* d_out = (sh_stem_fit*)at("stem.out");
+  const sh_canal_grid& g = c->canal_grid;
+  HIPCHK(c, hipMemcpyAsync(d_cat, stems, (size_t)K * sizeof(sh_stem), hipMemcpyHostToDevice, c->stream));
+  LAUNCH(c, "k_stem_fit", k_stem_fit, dim3((unsigned)(B * P)), dim3(SH_STEM_THREADS), (const double*)v.planes, (const int*)v.status, (const sh_resection*)v.out,
+         (const double*)at("canal.frames"), (const int*)at("canal.status"), (const double*)at("canal.near"), (const sh_canal_level*)at("canal.levels"),
+         (const double*)at("canal.dirs"), g.z0, g.dz, g.L, g.A, (const sh_stem*)d_cat, K, P, d_out);
+  HIPCHK(c, hipMemcpyAsync(out, d_out, n * sizeof(sh_stem_fit), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }
 

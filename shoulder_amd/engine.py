@@ -56,6 +56,7 @@ class Engine:
         self.h = h
         self.device = device
         self._inflight, self._pin_slot = [], 0
+        self._resect_P = None      # planes per humerus of the last resect() (resect_stems sizes its output by it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -486,6 +487,7 @@ class Engine:
               ("planes", "seat"): self.L.sh_resect_planes_seat, ("offsets", "seat"): self.L.sh_resect_offsets_seat}
         catalogue = (_ptr(hd), len(hd), mode) if level == "seat" else ()
         self._chk(fn["planes" if planes is not None else "offsets", level](self.h, _ptr(src), P, *catalogue, *(_ptr(a) for a in res)))
+        self._resect_P = P
         return res[0] if level == "records" else tuple(res)
 
     def resect_ring(self, b, p):
@@ -497,6 +499,47 @@ class Engine:
         if n.value:
             self._chk(self.L.sh_resect_ring(self.h, int(b), int(p), _ptr(out), len(out), ctypes.byref(n)))
         return out[: n.value]
+
+    # ---- canal profiles and stems (include/shoulder_hip.h sh_canal_profile / sh_resect_stems) ------------------------------
+    def canal_profile(self, z0, dz, L, A, frames=None, fetch=("levels",)):
+        """The polar profile of every resident humerus about its canal axis: L levels z_l = z0 - l dz of the humerus' canal frame, A rays
+        per level.  frames: (B, 4, 4) or (B, 16) float64 rigid CT -> frame matrices, or None for every record's csys_articular (needs a
+        run with STAGE_ANP and STAGE_CSYS).  fetch: which of "levels" (structured (B, L) of _lib.CANAL_LEVEL_DTYPE), "near", "far"
+        ((B, L, A) float64; +inf / 0 where a ray hits nothing) come back -- one of them alone, or a tuple in the order asked for.  The
+        profile stays on the device for resect_stems() until the next upload."""
+        names = (fetch,) if isinstance(fetch, str) else tuple(fetch)
+        if any(n not in ("levels", "near", "far") for n in names):
+            raise ValueError("fetch takes 'levels', 'near' and 'far'")
+        B, L, A = self.B, int(L), int(A)
+        grid = _lib.CanalGrid(float(z0), float(dz), L, A)
+        fr = None
+        if frames is not None:
+            fr = np.ascontiguousarray(frames, dtype=np.float64)
+            if fr.size != 16 * B:
+                raise ValueError("frames must have shape (B, 4, 4)")
+        out = {}
+        if 1 <= L <= 1024 and 3 <= A <= 256:      # (the library reports a bad grid; nothing is sized by it here)
+            if "levels" in names:
+                out["levels"] = np.zeros((B, L), dtype=_lib.CANAL_LEVEL_DTYPE)
+            for n in ("near", "far"):
+                if n in names:
+                    out[n] = np.zeros((B, L, A), dtype=np.float64)
+        ptr = lambda n: _ptr(out[n]) if n in out else None
+        self._chk(self.L.sh_canal_profile(self.h, ctypes.byref(grid), _ptr(fr) if fr is not None else None, ptr("near"), ptr("far"), ptr("levels")))
+        return out[names[0]] if isinstance(fetch, str) or len(names) == 1 else tuple(out[n] for n in names)
+
+    def resect_stems(self, stems):
+        """K stems -- (length, r_prox, r_tip) rows or a structured array of _lib.STEM_DTYPE -- below every cut of the last resect()
+        against the last canal_profile() -> structured array (B, P, K) of _lib.STEM_FIT_DTYPE (sh_resect_stems)."""
+        st = np.asarray(stems)
+        st = np.ascontiguousarray(st, dtype=_lib.STEM_DTYPE).view(np.float64).reshape(-1, 3) if st.dtype.names else np.ascontiguousarray(st, dtype=np.float64).reshape(-1, 3)
+        K = len(st)
+        if K < 1 or K > _lib.STEM_MAX:
+            raise ValueError("1..%d stems" % _lib.STEM_MAX)
+        P = self._resect_P or 1      # (the planes per humerus of the last resect(); without one the library reports the state)
+        out = np.zeros((self.B, P, K), dtype=_lib.STEM_FIT_DTYPE)
+        self._chk(self.L.sh_resect_stems(self.h, _ptr(st), K, _ptr(out)))
+        return out
 
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):

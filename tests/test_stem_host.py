@@ -1,0 +1,230 @@
+"""Canal profiles and stems below a cut (include/shoulder_hip.h sh_canal_profile / sh_resect_stems), the parts that need no GPU: record
+layouts, argument checks, the arithmetic the device runs (sh_scalar.h canal_* / stem_*, host-compiled with -ffp-contract=off through
+tests/hostcheck/stem_check.cpp) against closed forms and the NumPy statement of tests/stem_oracle.py, the culling of k_canal_rays
+against the un-culled loop, and the arithmetic of best_stem.
+
+Bounds.  Closed forms: 1e-12 mm.  Host source against the NumPy brute force on humerus_left: 1e-6 mm on the rays the oracle keeps."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import stem_oracle as O
+from conftest import BONES, GOLDEN, ROOT
+from shoulder_amd import _lib
+from shoulder_amd.arthroplasty import best_stem
+
+TIGHT = 1e-12
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    return O.build_shim(tmp_path_factory.mktemp("stem_check"))
+
+
+def humerus_canal_frame():
+    """humerus_left and the frame of its canal axis (tests/golden/contours_left.npz): origin at the axis' midpoint, z along it towards
+    the head -- the origin and z of the record's csys_articular; x is any perpendicular (the share of doubtful rays does not hang on
+    the turn about z).  -> verts float32, faces, T, half length"""
+    from shoulder_amd.stl import load_stl
+    v, f = load_stl(os.path.join(BONES, "humerus_left.stl"))
+    ax = np.load(os.path.join(GOLDEN, "contours_left.npz"))["canal_axis_ct"]
+    z = (ax[0] - ax[1]) / np.linalg.norm(ax[0] - ax[1])
+    x = np.cross([0.0, 1.0, 0.0], z)
+    x /= np.linalg.norm(x)
+    R = np.stack([x, np.cross(z, x), z])
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, -R @ (0.5 * (ax[0] + ax[1]))
+    return np.ascontiguousarray(v, np.float32), np.ascontiguousarray(f, np.int32), T, 0.5 * float(np.linalg.norm(ax[0] - ax[1]))
+
+
+def axis_grid(half, dz=4.0):
+    """levels of spacing dz with |z| <= half"""
+    n = int(np.floor(half / dz))
+    return n * dz, dz, 2 * n + 1
+
+
+def test_stem_record_layouts_match_header(tmp_path):
+    lv = ("r_min", "r_max", "r_mean", "area", "centroid", "extent_x", "extent_y", "wall_min", "a_min", "a_max", "n_hit", "status")
+    sf = ("entry", "z_entry", "min_clearance", "depth", "direction", "scale_max", "fill_mean", "fill_max", "fill_max_depth", "angle_index",
+          "n_samples", "n_breach", "n_open", "fits", "status")
+    src = tmp_path / "probe.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %d", sizeof(sh_canal_grid), '
+                   'offsetof(sh_canal_grid, L), offsetof(sh_canal_grid, A), sizeof(sh_canal_level), sizeof(sh_stem), offsetof(sh_stem, r_tip), sizeof(sh_stem_fit), SH_STEM_MAX);\n'
+                   + "".join('printf(" %%zu", offsetof(sh_canal_level, %s));\n' % n for n in lv)
+                   + "".join('printf(" %%zu", offsetof(sh_stem_fit, %s));\n' % n for n in sf) + 'printf("\\n"); return 0; }\n')
+    exe = tmp_path / "probe"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
+    assert got[0] == ctypes.sizeof(_lib.CanalGrid) == 24 and got[1] == _lib.CanalGrid.L.offset == 16 and got[2] == _lib.CanalGrid.A.offset == 20
+    assert got[3] == _lib.CANAL_LEVEL_DTYPE.itemsize == ctypes.sizeof(_lib.CanalLevel) == 104
+    assert got[4] == _lib.STEM_DTYPE.itemsize == ctypes.sizeof(_lib.Stem) == 24 and got[5] == _lib.Stem.r_tip.offset == 16
+    assert got[6] == _lib.STEM_FIT_DTYPE.itemsize == ctypes.sizeof(_lib.StemFit) == 128 and got[7] == _lib.STEM_MAX == 64
+    for g, name in zip(got[8:8 + len(lv)], lv):
+        assert g == _lib.CANAL_LEVEL_DTYPE.fields[name][1] == getattr(_lib.CanalLevel, name).offset, name
+    for g, name in zip(got[8 + len(lv):], sf):
+        assert g == _lib.STEM_FIT_DTYPE.fields[name][1] == getattr(_lib.StemFit, name).offset, name
+    assert [n for n, _ in _lib.CanalLevel._fields_] == list(_lib.CANAL_LEVEL_DTYPE.names) and [n for n, _ in _lib.StemFit._fields_] == list(_lib.STEM_FIT_DTYPE.names)
+
+
+def test_stem_entry_points_check_their_arguments_without_a_gpu():
+    L = _lib.load()
+    buf = np.zeros(64 * 16)
+    ptr = ctypes.c_void_p(buf.ctypes.data)
+    for grid in ((0.0, 1.0, 8, 64), (0.0, 0.0, 8, 64), (np.nan, 1.0, 8, 64), (0.0, 1.0, 0, 64), (0.0, 1.0, 1025, 64), (0.0, 1.0, 8, 2), (0.0, 1.0, 8, 257)):
+        g = _lib.CanalGrid(*grid)
+        assert L.sh_canal_profile(None, ctypes.byref(g), None, None, None, None) == -1      # (the first: no context)
+    assert L.sh_canal_profile(None, None, None, None, None, None) == -1
+    good = np.tile([100.0, 7.0, 4.0], (65, 1))
+    for stems, K in ((good, 1), (good, 0), (good, 65), ([[100.0, 0.0, 4.0]], 1), ([[np.nan, 7.0, 4.0]], 1), ([[100.0, 7.0, -1.0]], 1), ([[np.inf, 7.0, 4.0]], 1)):
+        s = np.ascontiguousarray(stems, dtype=np.float64)
+        assert L.sh_resect_stems(None, ctypes.c_void_p(s.ctypes.data), K, ptr) == -1
+    assert "sh_canal_profile" in _lib.EXPORTS and "sh_resect_stems" in _lib.EXPORTS
+
+
+def rays_on_triangles(shim, tris, o, d):
+    """smallest and largest accepted t of one ray over float64 triangles (n, 3, 3) through the host-compiled canal_ray_hit"""
+    o, d = np.ascontiguousarray(o, np.float64), np.ascontiguousarray(d, np.float64)
+    t, ts = ctypes.c_double(), []
+    for tri in tris:
+        tri = np.ascontiguousarray(tri, np.float64)
+        if shim.sc_hit(o.ctypes.data, d.ctypes.data, tri.ctypes.data, ctypes.byref(t)):
+            ts.append(t.value)
+    return (min(ts), max(ts)) if ts else (np.inf, 0.0)
+
+
+def test_ray_against_a_regular_prism_in_closed_form(shim):
+    """near = apothem / cos(theta - theta_side) on a heptagon and a 130-gon in exact float64 vertices; every ray leaves through one side"""
+    for n, A, phase in ((7, 64, 0.3), (130, 65, 0.011), (5, 3, 0.2)):
+        v, f = O.prism(n, 10.0, -4.0, 6.0, phase)
+        tris = v[f]
+        c, s = O.dirs(A)
+        want = O.prism_near(n, 10.0, phase, A)
+        for z in (-3.5, 0.0, 5.75):
+            got = np.array([rays_on_triangles(shim, tris, [0, 0, z], [c[a], s[a], 0.0]) for a in range(A)])
+            print(n, A, z, "max |near - closed form|", np.abs(got[:, 0] - want).max())
+            assert np.abs(got[:, 0] - want).max() <= TIGHT and np.array_equal(got[:, 0], got[:, 1])
+        assert rays_on_triangles(shim, tris, [0, 0, 7.0], [1.0, 0.0, 0.0]) == (np.inf, 0.0)      # above the prism
+
+
+def test_a_ray_through_a_vertex_and_along_an_edge_level_hits(shim):
+    """the octagon's first vertex is exactly (10, 0): the ray of angle 0 meets the vertical edge there (u or w exactly 0), and at the level
+    of the top edge ring it meets the corner itself; the closed test keeps both, t = the circumradius"""
+    v, f = O.prism(8, 10.0, -4.0, 6.0, 0.0)
+    assert v[0, 0] == 10.0 and v[0, 1] == 0.0
+    for z in (1.0, 6.0, -4.0):
+        assert rays_on_triangles(shim, v[f], [0, 0, z], [1.0, 0.0, 0.0])[0] == 10.0
+
+
+def cone_profile(z0, dz, L, A, r_mid, slope):
+    """a synthetic profile: the canal is the cone r(z) = r_mid + slope z"""
+    near = np.repeat((r_mid + slope * (z0 - np.arange(L) * dz))[:, None], A, axis=1)
+    return np.ascontiguousarray(near), np.ascontiguousarray(near + 3.0)
+
+
+def test_frustum_stem_in_a_conical_canal(shim):
+    z0, dz, L, A = 45.0, 1.0, 160, 64
+    near, far = cone_profile(z0, dz, L, A, 9.0, 0.05)
+    lv = np.zeros(L, dtype=_lib.CANAL_LEVEL_DTYPE)
+    shim.sc_levels(near.ctypes.data, far.ctypes.data, L, A, lv.ctypes.data)
+    assert np.all(lv["status"] == 0) and np.abs(lv["r_min"] - near[:, 0]).max() == 0 and np.all(lv["a_min"] == 0) and np.abs(lv["wall_min"] - 3.0).max() <= TIGHT
+    assert np.abs(lv["area"] - 0.5 * A * np.sin(2 * np.pi / A) * near[:, 0] ** 2).max() <= 1e-10 and np.abs(lv["centroid"]).max() <= 1e-9
+    T = np.eye(4)
+    plane = np.array([0.0, 0.0, 40.0, 0.0, 0.0, 1.0])                                 # horizontal cut at z = 40: every sample counts
+    for (length, rp, rt), fits in (((100.0, 8.0, 4.0), 1), ((100.0, 11.5, 4.0), 0), ((100.0, 8.0, 6.5), 0)):
+        r = O.host_stem(shim, plane, T, near, lv, z0, dz, (length, rp, rt))
+        d = np.arange(0.0, length + 0.5, 1.0)                                         # the used depths: levels z = 40 ... -60
+        canal, stem = 9.0 + 0.05 * (40.0 - d), rp + (rt - rp) * d / length
+        k = int(np.argmin(canal - stem))
+        print((length, rp, rt), r["min_clearance"], (canal - stem)[k], r["scale_max"], (canal / stem).min())
+        assert r["status"] == 0 and r["n_samples"] == 101 * A and r["n_open"] == 0 and r["fits"] == fits
+        assert abs(r["min_clearance"] - (canal - stem)[k]) <= TIGHT and r["depth"] == d[k] and r["angle_index"] == 0
+        assert abs(r["scale_max"] - (canal / stem).min()) <= TIGHT and r["n_breach"] == A * int(((canal - stem) < 0).sum())
+        assert np.array_equal(r["direction"], [1.0, 0.0, 0.0]) and np.array_equal(r["entry"], [0.0, 0.0, 40.0]) and r["z_entry"] == 40.0
+        fill = stem ** 2 / (0.5 * A * np.sin(2 * np.pi / A) / np.pi * canal ** 2)
+        assert abs(r["fill_mean"] - fill.mean()) <= 1e-12 and abs(r["fill_max"] - fill.max()) <= 1e-12 and r["fill_max_depth"] == d[int(np.argmax(fill))]
+        W = O.stem_record(plane, T, near, lv, z0, dz, (length, rp, rt))
+        assert all(r[k] == W[k] for k in ("n_samples", "n_breach", "n_open", "fits", "angle_index", "status")) and abs(r["min_clearance"] - W["min_clearance"]) <= TIGHT
+    # a grid that does not reach the tip, or starts below the entry: SH_ERR_ARG and zeros, nothing is extrapolated
+    for pl, stem in ((plane, (160.0, 8.0, 4.0)), (np.array([0, 0, 45.5, 0, 0, 1.0]), (50.0, 8.0, 4.0))):
+        r = O.host_stem(shim, pl, T, near, lv, z0, dz, stem)
+        assert r["status"] == -1 and not any(np.any(r[k]) for k in r.dtype.names if k != "status")
+    # a plane that holds the axis: SH_ERR_GEOMETRY
+    assert O.host_stem(shim, np.array([0, 0, 40.0, 1.0, 0, 0]), T, near, lv, z0, dz, (50.0, 8.0, 4.0))["status"] == -5
+
+
+def test_samples_under_an_inclined_cut_counted_by_hand(shim):
+    """A = 4, a cylinder stem of radius 3 and length 10 under the 45-degree plane x + (z - 20) = 0, entry at z = 20 between two levels:
+    the used depths are 0.5, 1.5, ... 9.5.  The sample at angle 0 (x = 3) is on the retained side for d >= 3: seven levels; the samples
+    at angles 1, 2, 3 (x = 2e-16, -3, -6e-16) for every d >= 0.5: ten levels each.  37 samples."""
+    z0, dz, L, A = 25.5, 1.0, 40, 4
+    near, far = cone_profile(z0, dz, L, A, 5.0, 0.0)
+    lv = np.zeros(L, dtype=_lib.CANAL_LEVEL_DTYPE)
+    shim.sc_levels(near.ctypes.data, far.ctypes.data, L, A, lv.ctypes.data)
+    plane = np.array([0.0, 0.0, 20.0, 1.0, 0.0, 1.0])
+    r = O.host_stem(shim, plane, np.eye(4), near, lv, z0, dz, (10.0, 3.0, 3.0))
+    assert r["status"] == 0 and r["n_samples"] == 37 and r["n_breach"] == 0 and r["n_open"] == 0 and r["fits"] == 1
+    assert abs(r["min_clearance"] - 2.0) <= TIGHT and r["depth"] == 0.5 and r["angle_index"] == 1      # the first counted sample in (l, a) order
+    assert abs(r["scale_max"] - 5.0 / 3.0) <= TIGHT and r["z_entry"] == 20.0
+    assert O.stem_record(plane, np.eye(4), near, lv, z0, dz, (10.0, 3.0, 3.0))["n_samples"] == 37
+    assert shim.sc_radius(10.0, 8.0, 4.0, 0.0) == 8.0 and shim.sc_radius(10.0, 8.0, 4.0, 10.0) == 4.0 and shim.sc_radius(10.0, 8.0, 4.0, 2.5) == 7.0
+
+
+def test_culling_never_drops_a_pair_and_the_oracle_keeps_99_percent_of_the_humerus_rays(shim):
+    """humerus_left in its canal-axis frame, levels |z| <= half the canal axis, A = 64, dz = 4 mm (the input of tests/test_gpu_stem.py's
+    fixture test): the culled walk of k_canal_rays' host twin gives the bits of the un-culled one, and the NumPy brute force over all
+    faces agrees to 1e-6 mm on every ray it keeps.  Measured: the oracle sets aside 0 of the rays here (cap: 1 %)."""
+    v, f, T, half = humerus_canal_frame()
+    z0, dz, L = axis_grid(half)
+    A = 64
+    near, far, lv, n_cull = O.host_profile(shim, v, f, T, z0, dz, L, A, cull=True)
+    near0, far0, _, n_all = O.host_profile(shim, v, f, T, z0, dz, L, A, cull=False)
+    assert near.tobytes() == near0.tobytes() and far.tobytes() == far0.tobytes()
+    wn, wf, doubt = O.profile(O.map_points(T, v), f, z0, dz, L, A, margins=True)
+    share = doubt.mean()
+    print("levels", L, "faces", len(f), "tests culled / all", n_cull, n_all, "doubtful share", share, "levels with every ray hit", int((lv["status"] == 0).sum()))
+    assert share <= 0.01
+    keep = ~doubt
+    assert np.array_equal(np.isfinite(near[keep]), np.isfinite(wn[keep]))
+    hit = keep & np.isfinite(wn)
+    assert hit.sum() > 0.9 * L * A and np.abs(near[hit] - wn[hit]).max() <= 1e-6 and np.abs(far[hit] - wf[hit]).max() <= 1e-6
+    W = O.levels(near, far)
+    for l in range(L):
+        assert lv[l]["status"] == W[l]["status"] and lv[l]["n_hit"] == W[l]["n_hit"]
+        if W[l]["status"] == 0:
+            for k in ("r_min", "r_max", "r_mean", "wall_min", "centroid", "extent_x", "extent_y"):
+                assert np.abs(lv[l][k] - W[l][k]).max() <= 1e-9, k
+            assert abs(lv[l]["area"] - W[l]["area"]) <= 1e-9 * W[l]["area"] and lv[l]["a_min"] == W[l]["a_min"] and lv[l]["a_max"] == W[l]["a_max"]
+
+
+def test_culling_ranges_on_faces_at_the_axis_and_the_seam(shim):
+    """a face whose projection holds the origin, has it on an edge or at a vertex takes all A angles; a face across the -x axis wraps;
+    levels are widened by one each side and clamped"""
+    out = np.zeros(4, dtype=np.int32)
+
+    def ranges(tri, z0=10.0, dz=1.0, L=21, A=64):
+        t = np.ascontiguousarray(tri, np.float64)
+        shim.sc_ranges(t.ctypes.data, z0, dz, L, A, out.ctypes.data)
+        return tuple(int(x) for x in out)
+    assert ranges([[1, 1, 0], [-2, 1, 0], [0, -2, 0]])[2:] == (0, 64)                  # origin inside
+    assert ranges([[1, 0, 0], [-1, 0, 0], [0, 5, 0]])[2:] == (0, 64)                   # origin on an edge
+    assert ranges([[0, 0, 0], [5, 1, 0], [5, -1, 0]])[3] <= 64
+    l_lo, l_hi, a0, n = ranges([[-5, 1, 2.5], [-5, -1, 2.5], [-6, 0, 4.5]])
+    step = 2 * np.pi / 64
+    assert (l_lo, l_hi) == (4, 9) and a0 == int(np.floor((np.pi - np.arctan2(1, 5)) / step)) - 1 and n <= 9 and (a0 + n - 1) % 64 >= 33      # levels z = 4.5 .. 2.5 widened; wraps past pi
+    assert ranges([[3, 1, 50], [3, -1, 50], [4, 0, 60]])[:2][0] > ranges([[3, 1, 50], [3, -1, 50], [4, 0, 60]])[:2][1]      # above the grid: empty
+    assert ranges([[3, 1, -50], [3, -1, -50], [4, 0, 60]])[:2] == (0, 20)
+
+
+def test_best_stem_arithmetic():
+    stems = np.array([(100.0, 6.0, 4.0), (120.0, 7.0, 4.0), (100.0, 7.0, 4.0), (130.0, 8.0, 5.0), (90.0, 9.0, 5.0)])
+    fits = np.zeros(5, dtype=_lib.STEM_FIT_DTYPE)
+    fits["fits"], fits["status"] = [1, 1, 1, 0, 1], [0, 0, 0, 0, -1]
+    assert best_stem(fits, stems) == 1                                                # r_prox 7 twice: the longer one
+    fits["fits"][1] = 0
+    assert best_stem(fits, stems) == 2
+    fits["fits"][:] = 0
+    assert best_stem(fits, stems) is None
+    assert best_stem([dict(fits=1, status=0), dict(fits=1, status=0)], [(100.0, 6.0, 4.0), (90.0, 6.5, 4.0)]) == 1
