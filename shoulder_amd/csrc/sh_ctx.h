@@ -8,7 +8,8 @@
 //   unet.hip          the UNet runners, UNet turns, sh_unet_infer                          (k_unet*.h; unet16_pp.hip: k_unet16_pp.h)
 //   comm.hip          the RCCL collectives
 // Kernel-free and HIP-free beside it (a plain g++ compiles them for the host tests): sh_demand.h (a run's capacity demands and the
-// verdict on them), sh_ingest.h (what mesh ingest checks and plans on the host before a batch becomes resident).
+// verdict on them), sh_ingest.h (what mesh ingest checks and plans on the host before a batch becomes resident), sh_unet_plan.h (the
+// steps of a UNet pass: kernel, grid, tensors and work tickets of every launch; the ticket and weight-packing tables).
 #pragma once
 #include "../../include/shoulder_hip.h"
 
@@ -36,6 +37,7 @@
 #include "sh_demand.h"
 #include "sh_hullcap.h"
 #include "sh_ingest.h"
+#include "sh_unet_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 struct Buf {
@@ -66,8 +68,8 @@ struct sh_ctx {
   std::vector<float> h_unet;                 // packed UNet parameters (host copy)
   std::vector<int32_t> h_feat, h_ti, h_fi, h_roots;
   std::vector<float> h_thr, h_lw;
-  struct ULayer { size_t w_off, b_off; int cin, cout, taps; };
-  std::map<std::string, ULayer> ulayers;
+  typedef sh::UnetLayer ULayer;
+  sh::UnetLayers ulayers;
   size_t unet_floats = 0;
   bool obb_injected = false;
   void* comm = nullptr;                      // sh_comm_init_all: this context's RCCL communicator (comm.hip), its rank and the group's size
@@ -75,8 +77,6 @@ struct sh_ctx {
   // sh_set_keep_products: every plane's resampled contour and polar rows leave k_resample_polar (k_slices.h, RsWant); off: the rows
   // the later stages read.  rs_*: what the last SH_STAGE_PROXIMAL run of the resident batch wrote (SH_STAGE_GROOVE checks it covers its rows)
   bool keep_products = false;
-  const double* unet_raw = nullptr;          // run_window -> unet_forward16: the unscaled image and its encoded range, when the first kernel scales it itself
-  const unsigned long long* unet_mm = nullptr;
   int rs_cs_lo = 0, rs_cs_hi = 0;
   bool rs_all = false;
   unsigned long long rs_gen = ~0ull;
@@ -158,8 +158,6 @@ struct sh_ctx {
   int t_head = 0, t_tail = 0, n_pending = 0;
   hipStream_t out_stream = nullptr;      // sh_collect copies the records / status words of a finished run to the host on this stream
   bool overlap = false;
-  bool unet_turn = false;                // sh_set_unet_turns: UNet passes of the contexts of one device run one after another
-  hipEvent_t unet_done_ev = nullptr;
   unsigned long long batch_gen = 0;
   // sh_resect_* (k_resect.h): the stages and the batch of the last submitted run (sh_resect_offsets reads its records), and the
   // planes per humerus and the batch of the last resection ("resect.planes": sh_resect_ring joins one of its cuts again)
@@ -175,8 +173,6 @@ struct sh_ctx {
   // box frame, so they run beside the full -> neck -> proximal chain
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork_ev = nullptr, side_join_ev = nullptr;
-  // timing
-  bool zero_page_ready = false;
   // Switches of equivalent paths (the A/B arms of tests/), read from the environment ONCE, when the context is created -- no launch
   // path consults the environment.  (Read elsewhere, process-wide: SHOULDER_HULL's default, SHOULDER_HULL_THREADS and
   // LOCAL_WORLD_SIZE for the hull pool, SHOULDER_RCCL_LIB.)
@@ -187,16 +183,22 @@ struct sh_ctx {
     bool hull_prefilter = true; // SHOULDER_HULL_PREFILTER=0: host hulls read every vertex back instead of the prefilter's survivors
     bool debug = false;        // SH_DEBUG: host-phase timings on stderr
   } sw;
-  bool unet_reference = false;      // SHOULDER_UNET_REFERENCE=1 at context creation: the 16-bit network layer by layer on the generic kernels
-  int ticket_next = 0;              // next free work counter of "unet16.tickets" (one per persistent conv launch of a forward pass)
-  std::map<std::tuple<int, int, int>, std::pair<int, int>> tk_tabs;      // (items, workgroups, cout groups) -> (offset, tickets) in "unet16.tk_tab"
-  int tk_tab_used = 0;
-  bool packtab_ready = false;      // layer table of k_pack_w_bf16_all uploaded (reset by sh_load_unet)
-  bool packed_rfc = false;         // "rfc.nodes" holds the packed forest of the CURRENT parameter block
-  bool packed_x3 = false;          // "params_x3h/l" hold the split weights of the CURRENT parameter block (reset with packed_kind)
-  int packed_kind = -1;            // element kind (0 bf16, 1 f16) "params_bf16" was packed for from the CURRENT parameter block; -1: repack.
-                                   // Reset wherever the block can change: sh_load_*, sh_param_block (the pointer goes to the caller), sh_param_block_commit
-  int num_cus = 0;
+  // the UNet runner's state (unet.hip)
+  struct Unet {
+    bool reference = false;          // SHOULDER_UNET_REFERENCE=1 at context creation: the 16-bit network layer by layer on the generic kernels
+    bool turn = false;               // sh_set_unet_turns: UNet passes of the contexts of one device run one after another
+    hipEvent_t done_ev = nullptr;    // ... recorded at the end of this context's pass
+    int num_cus = 0;
+    int ticket_next = 0;             // next free work counter of "unet16.tickets" (one per persistent launch of a forward pass)
+    std::map<std::tuple<int, int, int>, std::pair<int, int>> tk_tabs;      // (items, workgroups, cout groups) -> (offset, tickets) in "unet16.tk_tab"
+    int tk_tab_used = 0;
+    bool zero_page_ready = false;    // "unet16.zero" is cleared
+    bool packtab_ready = false;      // "unet16.packtab" holds the layer table of the loaded network (reset by sh_load_unet)
+    bool packed_x3 = false;          // "params_x3h/l" hold the split weights of the CURRENT parameter block
+    int packed_kind = -1;            // element kind (0 bf16, 1 f16) "params_bf16" was packed for from the CURRENT parameter block; -1: repack
+  } unet;
+  bool packed_rfc = false;           // "rfc.nodes" holds the packed forest of the CURRENT parameter block
+  // timing
   int timing = 0;      // 0 off, 1 every launch, 2 UNet layers only
   std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
   std::map<std::string, KTimer> timers;
@@ -229,6 +231,9 @@ struct StreamScope {
   ~StreamScope() { c->stream = saved; }
   StreamScope(const StreamScope&) = delete; StreamScope& operator=(const StreamScope&) = delete;
 };
+
+// the parameter block can change: sh_load_*, sh_param_block (the pointer goes to the caller), sh_param_block_commit, a store to "params"
+static inline void params_changed(sh_ctx* c) { c->unet.packed_kind = -1; c->unet.packed_x3 = false; c->packed_rfc = false; }
 
 static inline int fail(sh_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
@@ -312,6 +317,8 @@ static inline size_t rec_bytes_rows(int rows) { return rows > 0 ? SH_REC_HEAD + 
 // ---- functions that cross units ------------------------------------------------------------------------------------------------
 struct HullPre { const float* verts; const long long* voff; int* ext; double* planes; int* npl; float* kept; int* nkept; long long* koff; double* pval; int* pidx; int* pcnt; long long* poff; };      // device pointers of the hull prefilter (hull.hip)
 struct FillEnt { void* p; size_t bytes; unsigned char byte; };      // bytes: a multiple of 4, p 4-byte aligned
+// a UNet pass reads `image` (f32, scaled) or, where its first kernel scales it itself (plan_level0_fused), `raw` with its encoded range `mm`
+struct UnetIO { const float* image; const double* raw; const unsigned long long* mm; float* logits; };
 namespace sh {
 // shoulder_hip.hip
 int fill_list(sh_ctx* c, std::initializer_list<FillEnt> ents);      // buffer clears of a run as one launch (k_fill_list)
@@ -329,8 +336,7 @@ int alloc_hullpre(sh_ctx* c, int B, long long sumV, const char* sfx);
 int unet_turn_enter(sh_ctx* c);
 int unet_turn_leave(sh_ctx* c);
 void unet_turn_forget(sh_ctx* c);
-bool unet16_level0_fused(const sh_ctx* c, int H, int W);
-int unet_dispatch(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W);
+int unet_dispatch(sh_ctx* c, const UnetIO& io, int nimg, int H, int W);
 // comm.hip
 void comm_forget(sh_ctx* c);
 }  // namespace sh

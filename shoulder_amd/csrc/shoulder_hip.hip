@@ -201,7 +201,7 @@ int sh_ctx_create(int device, void* hip_stream, sh_ctx** out) {
   if (!c) return SH_ERR_NOMEM;
   c->device = device;
   c->hull_mode = hull_mode_from(getenv("SHOULDER_HULL"));
-  c->unet_reference = getenv("SHOULDER_UNET_REFERENCE") && getenv("SHOULDER_UNET_REFERENCE")[0] == '1';
+  c->unet.reference = getenv("SHOULDER_UNET_REFERENCE") && getenv("SHOULDER_UNET_REFERENCE")[0] == '1';
   {
     auto off = [](const char* n) { const char* e = getenv(n); return e && e[0] == '0'; };
     if (const char* e = getenv("SHOULDER_WINDOW")) { const int v = atoi(e); if (v > 0) c->sw.window = v; }
@@ -227,7 +227,7 @@ void sh_ctx_destroy(sh_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   comm_forget(c);
   unet_turn_forget(c);
-  if (c->unet_done_ev) (void)hipEventDestroy(c->unet_done_ev);
+  if (c->unet.done_ev) (void)hipEventDestroy(c->unet.done_ev);
   drain_timers(c);
   if (c->stl_counted_ev) (void)hipEventDestroy(c->stl_counted_ev);
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -608,7 +608,7 @@ int sh_buffer_device(sh_ctx* c, const char* name, void** dev_ptr, size_t* nbytes
   if (it == c->bufs.end() || !it->second.p) return fail(c, SH_ERR_ARG, std::string("no buffer named ") + name);
   *dev_ptr = it->second.p;
   if (nbytes) *nbytes = it->second.bytes;
-  if (std::string(name) == "params") { c->packed_kind = -1; c->packed_x3 = false; c->packed_rfc = false; }      // (the caller may write it)
+  if (std::string(name) == "params") params_changed(c);      // (the caller may write it)
   c->ovf_none_gen = ~0ull;      // (... or a frame / an intermediate that moves the planes: the overflow tier runs again)
   return SH_OK;
 }
@@ -632,7 +632,7 @@ int sh_store(sh_ctx* c, const char* name, const void* host, size_t nbytes) {
   HIPCHK(c, hipSetDevice(c->device));
   if (std::string(name) == "verts") { discard_staged(c); (void)join_prepared(c); ++c->batch_gen; c->h_verts_valid = false; }
   c->ovf_none_gen = ~0ull;      // (an injected frame or intermediate moves the planes: the overflow tier runs again)
-  if (std::string(name) == "params") { c->packed_kind = -1; c->packed_x3 = false; c->packed_rfc = false; }
+  if (std::string(name) == "params") params_changed(c);
   HIPCHK(c, hipMemcpyAsync(it->second.p, host, nbytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (std::string(name) == "obb_transform") c->obb_injected = true;
@@ -1531,12 +1531,10 @@ static int stage_anp(sh_ctx* c, const WinView& v) {
          v.anp_mm_enc);      // (+ the image's minimum / maximum: no second pass over it)
   // MinMaxScaler (anatomic_neck.py:56-58): the 16-bit network's first kernel applies it where it reads its patches (k_unet16_l0.h) --
   // no f32 image, 201 MB less traffic and a launch less per step; the other forms of the network and sh_set_keep_products get "anp.image"
-  const bool scale_in_net = (c->params.unet_dtype == SH_UNET_BF16 || c->params.unet_dtype == SH_UNET_F16) && unet16_level0_fused(c, SH_ANP_ROWS, SH_MPROX);
+  const bool scale_in_net = plan_level0_fused(c->params.unet_dtype, c->unet.reference, c->unet_base, c->unet_depth, SH_ANP_ROWS, SH_MPROX);
   if (!scale_in_net || c->keep_products) LAUNCH(c, "k_anp_scale", k_anp_scale, dim3(64, B), dim3(256), v.anp_raw, v.anp_mm_enc, v.anp_image);
   if ((rc = unet_turn_enter(c)) != SH_OK) return rc;
-  if (scale_in_net) { c->unet_raw = v.anp_raw; c->unet_mm = v.anp_mm_enc; }
-  rc = unet_dispatch(c, v.anp_image, v.anp_logits, B, SH_ANP_ROWS, SH_MPROX);
-  c->unet_raw = nullptr; c->unet_mm = nullptr;
+  rc = unet_dispatch(c, {v.anp_image, scale_in_net ? v.anp_raw : nullptr, scale_in_net ? v.anp_mm_enc : nullptr, v.anp_logits}, B, SH_ANP_ROWS, SH_MPROX);
   (void)unet_turn_leave(c);      // also after a failed pass: whatever was enqueued is what the next context waits for
   if (rc != SH_OK) return rc;
   const double* prox_zs = v.set[SET_PROX].zs;
@@ -1668,8 +1666,8 @@ int sh_set_overlap(sh_ctx* c, int on) {
 
 int sh_set_unet_turns(sh_ctx* c, int on) {
   if (!c) return SH_ERR_ARG;
-  c->unet_turn = on != 0;
-  if (!c->unet_turn) unet_turn_forget(c);
+  c->unet.turn = on != 0;
+  if (!c->unet.turn) unet_turn_forget(c);
   return SH_OK;
 }
 
@@ -2360,7 +2358,7 @@ int sh_landmarks_device(sh_ctx* c, void** p, size_t* n) {
 
 // ---- parameters ------------------------------------------------------------------------------------
 static int upload_params(sh_ctx* c) {
-  c->packed_kind = -1; c->packed_x3 = false; c->packed_rfc = false;
+  params_changed(c);
   const size_t N = c->h_feat.size(), T = c->h_roots.size();
   const size_t bytes = c->unet_floats * 4 + N * 4 * 5 + T * 4;
   int rc = ensure(c, "params", bytes ? bytes : 16, 4);
@@ -2451,7 +2449,7 @@ int sh_load_unet(sh_ctx* c, int base, int depth, const float* packed, size_t n_f
     if (!std::isfinite(packed[i])) return fail(c, SH_ERR_ARG, "sh_load_unet: NaN / infinite parameter");
   (void)hipStreamSynchronize(c->stream);      // no forward of the previous network is still reading the block
   c->ulayers.swap(layers);
-  c->packtab_ready = false;
+  c->unet.packtab_ready = false;
   c->h_unet.assign(packed, packed + n_floats);
   c->unet_floats = n_floats; c->unet_base = base; c->unet_depth = depth; c->have_unet = true;
   int rc = upload_params(c);
@@ -2461,7 +2459,7 @@ int sh_load_unet(sh_ctx* c, int base, int depth, const float* packed, size_t n_f
 
 int sh_param_block_commit(sh_ctx* c) {
   if (!c) return SH_ERR_ARG;
-  c->packed_kind = -1; c->packed_x3 = false; c->packed_rfc = false;
+  params_changed(c);
   auto it = c->bufs.find("params");
   if (it == c->bufs.end()) return fail(c, SH_ERR_STATE, "sh_param_block_commit: no parameters loaded");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2508,7 +2506,7 @@ int sh_param_block_commit(sh_ctx* c) {
 
 int sh_param_block(sh_ctx* c, void** p, size_t* n) {
   if (!c || !p || !n) return SH_ERR_ARG;
-  c->packed_kind = -1; c->packed_x3 = false; c->packed_rfc = false;      // the caller may write the block from here on (and confirms with sh_param_block_commit)
+  params_changed(c);      // the caller may write the block from here on (and confirms with sh_param_block_commit)
   auto it = c->bufs.find("params");
   if (it == c->bufs.end()) return fail(c, SH_ERR_STATE, "sh_param_block: no parameters loaded");
   *p = it->second.p;

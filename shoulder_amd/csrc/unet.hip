@@ -1,5 +1,6 @@
-// unet.hip -- the UNet of the anatomic-neck stage: the f32 / split-f16 runner, the 16-bit runners (the level-0 ping-pong kernels are
-// unet16_pp.hip's), the work tickets of the persistent kernels, UNet turns between the contexts of a device, sh_unet_infer.
+// unet.hip -- the UNet of the anatomic-neck stage: one runner for the f32, split-f16 and 16-bit forms of the network (the level-0
+// ping-pong kernels are unet16_pp.hip's).  sh_unet_plan.h decides the steps of a pass; here are the buffers, the launch of a step, the
+// work tickets of the persistent kernels, weight packing, UNet turns between the contexts of a device, sh_unet_infer.
 #include "sh_ctx.h"
 
 #include "k_unet.h"
@@ -11,54 +12,13 @@
 
 using namespace sh;
 
-// ---- UNet forward (f32 MFMA path) ----------------------------------------------------------------------
-static int conv_layer(sh_ctx* c, const char* lname, const sh_ctx::ULayer& L, const float* src0, const float* src1, int C0, int C1, float* dst,
-                      int H, int W, int nimg, int relu, int fuse = 0, float* pooled = nullptr, const float* head_w = nullptr, const float* head_b = nullptr,
-                      float* logits = nullptr, const float* image = nullptr, const float* w0 = nullptr, const float* b0 = nullptr) {
-  if (H % UN_TH || W % UN_TW) return fail(c, SH_ERR_ARG, "unet: feature map is not a multiple of 16");
-  const float* P = buf<float>(c, "params");
-  const float* w = P + L.w_off; const float* b = P + L.b_off;
-  const int tiles = (H / UN_TH) * (W / UN_TW);
-  if (c->params.unet_dtype == SH_UNET_F32X && C0 % 32 == 0 && C1 % 32 == 0 && L.cout % 32 == 0) {
-    // split-f16 operands on the 16-bit matrix pipe (k_unet_x3.h); weights split once per parameter block by unet_forward
-    const u16* wh = buf<u16>(c, "params_x3h") + L.w_off;
-    const u16* wl = buf<u16>(c, "params_x3l") + L.w_off;
-    float* np_ = nullptr; const float* nf_ = nullptr;
-    if (L.taps == 9 && fuse == (UF_FIRST | UF_POOL) && L.cout == 32 && C0 == 32 && C1 == 0) {      // enc0b with enc0a computed while its halo tile is staged
-      LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, UF_FIRST | UF_POOL, 0>), dim3(tiles, 1, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, pooled, nf_, nf_, np_, image, w0, b0);
-    }
-    else if (L.taps == 9 && fuse == UF_HEAD && L.cout == 32) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, UF_HEAD>), dim3(tiles, 1, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, np_, head_w, head_b, logits, nf_, nf_, nf_); }
-    else if (L.taps == 9 && fuse == UF_POOL && L.cout % 64 == 0) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 4, UF_POOL>), dim3(tiles, L.cout / 64, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, pooled, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (L.taps == 9 && fuse == UF_POOL) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, UF_POOL, 0>), dim3(tiles, L.cout / 32, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, pooled, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (fuse != 0) return fail(c, SH_ERR_ARG, "unet: unsupported fusion");
-    else if (L.taps == 9 && L.cout % 64 == 0) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 4>), dim3(tiles, L.cout / 64, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (L.taps == 9) { LAUNCH(c, lname, (k_conv_mfma_x3<9, 2, 0, 0>), dim3(tiles, L.cout / 32, nimg), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, relu, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    else if (C1 == 0 && W % 32 == 0 && H % 16 == 0 && (C0 == 64 || C0 == 128 || C0 == 256 || C0 == 512)) {
-      // up-convolutions with the source pixels resident in registers (k_upconv_x3r)
-      if (C0 == 64) { LAUNCH(c, lname, (k_upconv_x3r<2, 4>), dim3((W / 32) * (H / 16), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-      else if (C0 == 128) { LAUNCH(c, lname, (k_upconv_x3r<4, 4>), dim3((W / 32) * (H / 16), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-      else if (C0 == 256) { LAUNCH(c, lname, (k_upconv_x3r<8, 2>), dim3((W / 32) * (H / 8), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-      else { LAUNCH(c, lname, (k_upconv_x3r<16, 1>), dim3((W / 32) * (H / 4), nimg), dim3(UXR_THREADS), src0, wh, wl, b, dst, H, W, L.cout); }
-    }
-    else if (L.cout % 64 == 0) { LAUNCH(c, lname, (k_conv_mfma_x3<1, 4>), dim3(tiles, L.cout / 64, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, 0, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    else { LAUNCH(c, lname, (k_conv_mfma_x3<1, 2>), dim3(tiles, L.cout / 32, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, wh, wl, b, dst, H, W, L.cout, 0, np_, nf_, nf_, np_, nf_, nf_, nf_); }
-    return SH_OK;
-  }
-  if (L.taps == 9) {
-    if (L.cout % 64 == 0) {
-      LAUNCH(c, lname, (k_conv_mfma_f32<9, 4>), dim3(tiles, L.cout / 64, nimg), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu);
-    } else {
-      LAUNCH(c, lname, (k_conv_mfma_f32<9, 2>), dim3(tiles, L.cout / 32, nimg), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu);
-    }
-  } else {
-    if (L.cout % 64 == 0) {
-      LAUNCH(c, lname, (k_conv_mfma_f32<1, 4>), dim3(tiles, L.cout / 64, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0);
-    } else {
-      LAUNCH(c, lname, (k_conv_mfma_f32<1, 2>), dim3(tiles, L.cout / 32, nimg * 4), dim3(UN_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0);
-    }
-  }
-  return SH_OK;
-}
+// what sh_unet_plan.h restates of the kernel headers
+static_assert(PL_TILE == UN_TH && PL_TILE == UN_TW && PL_UN_THREADS == UN_THREADS && PL_UD_THREADS == UD_THREADS && PL_UPR_THREADS == UPR_THREADS &&
+              PL_UPC_THREADS == UPC_THREADS && PL_UXR_THREADS == UXR_THREADS, "sh_unet_plan.h: tile / block sizes");
+static_assert(PL_FIRST == UF_FIRST && PL_HEAD == UF_HEAD && PL_POOL == UF_POOL && PL_X3_WSCALE == X3_WSCALE, "sh_unet_plan.h: fusion flags, weight scale");
+static_assert(sizeof(PackRow) == sizeof(PackEntry) && offsetof(PackRow, first) == offsetof(PackEntry, first) && offsetof(PackRow, w_off) == offsetof(PackEntry, w_off) &&
+              offsetof(PackRow, T) == offsetof(PackEntry, T) && offsetof(PackRow, Cin) == offsetof(PackEntry, Cin) && offsetof(PackRow, Cout) == offsetof(PackEntry, Cout),
+              "sh_unet_plan.h: PackRow is PackEntry");
 
 // ---- UNet turns ----------------------------------------------------------------------------------------
 // Several contexts on one device overlap well when the launch-bound geometry kernels of one run beside the chip-filling
@@ -71,18 +31,18 @@ static sh_ctx* g_turn_owner[64] = {};
 namespace sh {
 
 int unet_turn_enter(sh_ctx* c) {
-  if (!c->unet_turn || c->device < 0 || c->device >= 64) return SH_OK;
+  if (!c->unet.turn || c->device < 0 || c->device >= 64) return SH_OK;
   std::lock_guard<std::mutex> lk(g_turn_mu);
   if (g_turn_last[c->device] && g_turn_owner[c->device] != c) HIPCHK(c, hipStreamWaitEvent(c->stream, g_turn_last[c->device], 0));
   return SH_OK;
 }
 
 int unet_turn_leave(sh_ctx* c) {
-  if (!c->unet_turn || c->device < 0 || c->device >= 64) return SH_OK;
+  if (!c->unet.turn || c->device < 0 || c->device >= 64) return SH_OK;
   std::lock_guard<std::mutex> lk(g_turn_mu);
-  if (!c->unet_done_ev) HIPCHK(c, hipEventCreateWithFlags(&c->unet_done_ev, hipEventDisableTiming));
-  HIPCHK(c, hipEventRecord(c->unet_done_ev, c->stream));
-  g_turn_last[c->device] = c->unet_done_ev;
+  if (!c->unet.done_ev) HIPCHK(c, hipEventCreateWithFlags(&c->unet.done_ev, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(c->unet.done_ev, c->stream));
+  g_turn_last[c->device] = c->unet.done_ev;
   g_turn_owner[c->device] = c;
   return SH_OK;
 }
@@ -94,106 +54,6 @@ void unet_turn_forget(sh_ctx* c) {
 
 }  // namespace sh
 
-static int unet_forward(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W) {
-  const int D = c->unet_depth, base = c->unet_base;
-  if ((H >> D) % 16 || (W >> D) % 16) return fail(c, SH_ERR_ARG, "unet: input size must be a multiple of 16 << depth");
-  int rc;
-  const size_t full = (size_t)nimg * H * W * base * 4;
-  if ((rc = ensure(c, "unet.a", full, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "unet.b", full, 4)) != SH_OK) return rc;
-  std::vector<float*> skip(D);
-  for (int i = 0; i < D; ++i) {
-    std::string nm = "unet.skip" + std::to_string(i);
-    if ((rc = ensure(c, nm.c_str(), full >> i, 4)) != SH_OK) return rc;     // H*W/4^i * base*2^i
-    skip[i] = buf<float>(c, nm.c_str());
-  }
-  float* A = buf<float>(c, "unet.a");
-  float* Bq = buf<float>(c, "unet.b");
-  const float* P = buf<float>(c, "params");
-  if (c->params.unet_dtype == SH_UNET_F32X) {      // split the MFMA layers' weights into f16 high / low parts: one launch, once per parameter block
-    if ((rc = ensure(c, "params_x3h", c->unet_floats * 2, 2)) != SH_OK) return rc;
-    if ((rc = ensure(c, "params_x3l", c->unet_floats * 2, 2)) != SH_OK) return rc;
-    if (!c->packed_x3) {
-      std::vector<PackEntry> tab;
-      long long total = 0;
-      for (auto& kv : c->ulayers) {
-        const sh_ctx::ULayer& l = kv.second;
-        if (l.cin < 32 || l.cout < 32) continue;
-        tab.push_back(PackEntry{total, (long long)l.w_off, l.taps, l.cin, l.cout, 0});
-        total += (long long)l.taps * l.cin * l.cout;
-        // range of the split: 64 w must be a finite f16 (|w| < 65504 / 64); beyond it the high part is an infinity and the layer's
-        // outputs NaN, silently (include/shoulder_hip.h, SH_UNET_F32X)
-        if (c->h_unet.size() >= l.w_off + (size_t)l.taps * l.cin * l.cout) {
-          const float* wl = c->h_unet.data() + l.w_off;
-          for (size_t i = 0, n = (size_t)l.taps * l.cin * l.cout; i < n; ++i)
-            if (!(fabsf(wl[i]) < 65504.0f / X3_WSCALE)) {
-              char m[200];
-              snprintf(m, sizeof m, "SH_UNET_F32X: layer %s has a weight of magnitude %g; the split-f16 operands hold |w| < %g (use SH_UNET_F32 for this network)",
-                       kv.first.c_str(), (double)fabsf(wl[i]), (double)(65504.0f / X3_WSCALE));
-              return fail(c, SH_ERR_ARG, m);
-            }
-        }
-      }
-      if ((rc = ensure(c, "unet16.packtab", tab.size() * sizeof(PackEntry), 8)) != SH_OK) return rc;
-      HIPCHK(c, hipMemcpyAsync(c->bufs["unet16.packtab"].p, tab.data(), tab.size() * sizeof(PackEntry), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
-      c->packtab_ready = true;
-      LAUNCH(c, "k_pack_w_x3", k_pack_w_x3, dim3(2048), dim3(256), P, buf<u16>(c, "params_x3h"), buf<u16>(c, "params_x3l"), (const PackEntry*)c->bufs["unet16.packtab"].p, (int)tab.size(), total);
-      c->packed_x3 = true;
-    }
-  }
-  auto L = [&](const std::string& n) -> const sh_ctx::ULayer& { return c->ulayers[n]; };
-  int h = H, w = W;
-  // SH_UNET_F32X: the 2x2 pools ride in the epilogue of the conv before them (k_unet_x3.h), and with 32 base channels the first
-  // conv is computed inside enc0b's staging
-  const bool x3 = c->params.unet_dtype == SH_UNET_F32X && base % 32 == 0;
-  const bool x3_first = x3 && base == 32;
-  if (!x3_first) {
-    const sh_ctx::ULayer& l = L("enc0a");
-    size_t npx = (size_t)nimg * h * w;
-    LAUNCH(c, "unet.enc0a", k_conv_first, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), image, P + l.w_off, P + l.b_off, A, h, w, l.cout, nimg);
-  }
-  if (x3_first) {
-    const sh_ctx::ULayer& l = L("enc0a");
-    if ((rc = conv_layer(c, "unet.enc0b", L("enc0b"), A, nullptr, base, 0, skip[0], h, w, nimg, 1, UF_FIRST | UF_POOL, Bq, nullptr, nullptr, nullptr, image, P + l.w_off, P + l.b_off)) != SH_OK) return rc;
-  } else if ((rc = conv_layer(c, "unet.enc0b", L("enc0b"), A, nullptr, base, 0, skip[0], h, w, nimg, 1, x3 ? UF_POOL : 0, Bq)) != SH_OK) return rc;
-  if (x3) std::swap(A, Bq);      // (the pooled tensor is the next level's input, which the loop below reads from A)
-  int ch = base;
-  for (int i = 1; i <= D; ++i) {
-    if (!x3) {
-      size_t e = (size_t)nimg * (h / 2) * (w / 2) * (ch / 4);
-      LAUNCH(c, "unet.pool", k_maxpool2, dim3((unsigned)std::min<size_t>((e + 255) / 256, 8192)), dim3(256), skip[i - 1], A, h, w, ch, nimg);
-    }
-    h /= 2; w /= 2;
-    std::string na = i < D ? "enc" + std::to_string(i) + "a" : "bota", nb = i < D ? "enc" + std::to_string(i) + "b" : "botb";
-    if ((rc = conv_layer(c, ("unet." + na).c_str(), L(na), A, nullptr, ch, 0, Bq, h, w, nimg, 1)) != SH_OK) return rc;
-    ch *= 2;
-    float* dst = i < D ? skip[i] : A;
-    // (A was consumed by the conv above: with the fused pool it receives the next level's input)
-    if ((rc = conv_layer(c, ("unet." + nb).c_str(), L(nb), Bq, nullptr, ch, 0, dst, h, w, nimg, 1, (x3 && i < D) ? UF_POOL : 0, A)) != SH_OK) return rc;
-  }
-  // decoder: x lives in A
-  float* x = A; float* y = Bq;
-  for (int i = D - 1; i >= 0; --i) {
-    std::string nu = "up" + std::to_string(i), na = "dec" + std::to_string(i) + "a", nb = "dec" + std::to_string(i) + "b";
-    if ((rc = conv_layer(c, ("unet." + nu).c_str(), L(nu), x, nullptr, ch, 0, y, h, w, nimg, 0)) != SH_OK) return rc;
-    h *= 2; w *= 2; ch /= 2;
-    if ((rc = conv_layer(c, ("unet." + na).c_str(), L(na), skip[i], y, ch, ch, x, h, w, nimg, 1)) != SH_OK) return rc;
-    // (the head stays on k_head: its sequential f32 chain over the channels is the exact path's; fused into dec0b's epilogue the
-    //  logits move by another ~1e-6 and one mask pixel of the 64-humerus bench batch flips)
-    if ((rc = conv_layer(c, ("unet." + nb).c_str(), L(nb), x, nullptr, ch, 0, y, h, w, nimg, 1)) != SH_OK) return rc;
-    std::swap(x, y);
-  }
-  {
-    const sh_ctx::ULayer& l = L("head");
-    size_t npx = (size_t)nimg * H * W;
-    if (l.cin <= 32) { LAUNCH(c, "unet.head", k_head<32>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 16384)), dim3(256), x, P + l.w_off, P + l.b_off, logits, l.cin, npx); }
-    else { LAUNCH(c, "unet.head", k_head<64>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), x, P + l.w_off, P + l.b_off, logits, l.cin, npx); }
-  }
-  return SH_OK;
-}
-
-// ---- UNet forward (16-bit MFMA paths: EK = 0 __bf16, 1 _Float16; tensors as raw u16) -----------------------------------------
 #define SH_UNET_TICKETS 64
 #define SH_UNET_TKTAB (1 << 18)
 // Workgroups of a persistent UNet launch.  Each takes a whole CU (its LDS, all of its registers), so while one is resident no
@@ -204,246 +64,252 @@ static int unet_forward(sh_ctx* c, const float* image, float* logits, int nimg, 
 // 8.73 / 8.27 / 8.54 / 8.56 / 9.35 ms per step.
 static int persistent_grid(sh_ctx* c) {
   constexpr int cu_reserve = 32;
-  if (c->num_cus <= 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) v = 0; c->num_cus = v > 0 ? v : 256; }
-  return c->unet_turn ? std::max(8, c->num_cus - cu_reserve) : c->num_cus;
+  if (c->unet.num_cus <= 0) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) v = 0; c->unet.num_cus = v > 0 ? v : 256; }
+  return c->unet.turn ? std::max(8, c->unet.num_cus - cu_reserve) : c->unet.num_cus;
 }
 
-// work tickets of a persistent launch: the next free counter of this forward pass and the table of item bounds of runs of decreasing
-// length for (items, workgroups, cout groups) -- every ticket a third of what would be a fair share of the remaining items, whole
-// cout-group sets of a tile (its input tile comes from HBM once) -- built once per shape
-static int unet_tickets(sh_ctx* c, int total, int nwg, int ngrp, unsigned** tk, const int** tk_tab, int* ntk) {
-  const auto key = std::make_tuple(total, nwg, ngrp);
-  auto it = c->tk_tabs.find(key);
-  if (it == c->tk_tabs.end()) {
-    std::vector<int> tab;
-    int pos = 0;
-    while (pos < total) {
-      int sz = std::max(1, (int)std::ceil((total - pos) / (3.0 * (double)nwg)));
-      if (sz >= ngrp) sz = sz / ngrp * ngrp;
-      tab.push_back(pos);
-      pos += std::min(sz, total - pos);
-    }
-    tab.push_back(total);
-    if ((int)tab.size() > SH_UNET_TKTAB) return fail(c, SH_ERR_CAPACITY, "unet: ticket table larger than its buffer");
-    if (c->tk_tab_used + (int)tab.size() > SH_UNET_TKTAB) {      // many different shapes (sh_unet_infer with varying n): start the cache over
-      HIPCHK(c, hipStreamSynchronize(c->stream));                  // (launches that read the old tables are done)
-      c->tk_tabs.clear();
-      c->tk_tab_used = 0;
-    }
-    HIPCHK(c, hipMemcpyAsync(buf<int>(c, "unet16.tk_tab") + c->tk_tab_used, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
-    it = c->tk_tabs.emplace(key, std::make_pair(c->tk_tab_used, (int)tab.size() - 1)).first;
-    c->tk_tab_used += (int)tab.size();
-  }
-  if (c->ticket_next >= SH_UNET_TICKETS) return fail(c, SH_ERR_CAPACITY, "unet: out of work counters");
-  *tk = buf<unsigned>(c, "unet16.tickets") + c->ticket_next++;
-  *tk_tab = buf<int>(c, "unet16.tk_tab") + it->second.first;
-  *ntk = it->second.second;
-  return SH_OK;
-}
+// The buffers of a pass, resolved once (none of them is windowed).  act: the tensors by slot (US_IMAGE, US_A, US_B, US_LOGITS,
+// US_SKIP + level): float in the f32 forms, u16 in the 16-bit ones.
+struct UnetView {
+  UnetIO io;
+  int nimg;
+  const float* P;                      // "params"
+  u16 *PW, *wh, *wl;                   // "params_bf16" | "params_x3h", "params_x3l"
+  const u16* zero;                     // "unet16.zero"
+  unsigned* tickets; int* tk_tab;      // "unet16.tickets", "unet16.tk_tab"
+  void* act[US_SKIP + 6];              // (sh_load_unet: depth <= 6)
+  template <typename T> T* at(int slot) const { return slot < 0 ? nullptr : (T*)act[slot]; }
+};
 
-// One layer of the 16-bit network.  3x3 convs with a multiple of 64 output channels on 32 x 16-tileable maps run on the persistent
-// LDS-DMA kernel (k_unet16_ldr.h; UF_POOL: the 2x2 max pool written beside the output); 2x2 transposed convs on k_upconv16g /
-// k_upconv16; everything else on the generic two-barrier kernel k_conv_mfma16 (k_unet_bf16.h), which is also the whole of the
-// REFERENCE network (sh_ctx::unet_reference: layer by layer, nothing fused, no persistent kernel -- what the tests hold the
-// production kernels against).
-template <int EK>
-static int conv_layer16(sh_ctx* c, const char* lname, const sh_ctx::ULayer& L, const u16* src0, const u16* src1, int C0, int C1,
-                           u16* dst, int H, int W, int nimg, int relu, int fuse = 0, ConvFuse fz = ConvFuse{}) {
-  if (H % UN_TH || W % UN_TW) return fail(c, SH_ERR_ARG, "unet: feature map is not a multiple of 16");
-  const u16* w = buf<u16>(c, "params_bf16") + L.w_off;
-  const float* b = buf<float>(c, "params") + L.b_off;
-  const int tiles = (H / UN_TH) * (W / UN_TW);
-  const dim3 blk(UN_THREADS);
-  const bool ldr = !c->unet_reference && L.taps == 9 && L.cout % 64 == 0 && L.cout <= 512 && W % 32 == 0 && H % 16 == 0 && C0 % 32 == 0 && C1 % 32 == 0 &&
-                   (fuse == 0 || (fuse == UF_POOL && relu));      // (its fused pool works on ReLU'd values)
-  if (ldr) {
-    int rc0;
-    if ((rc0 = ensure(c, "unet16.zero", 256, 2)) != SH_OK) return rc0;
-    if (!c->zero_page_ready) { HIPCHK(c, hipMemsetAsync(buf<char>(c, "unet16.zero"), 0, 256, c->stream)); c->zero_page_ready = true; }
-    const int total = nimg * (W / 32) * (H / 16) * (L.cout / 64);
-    const dim3 g((unsigned)std::min(total, persistent_grid(c)));
-    unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-    if ((rc0 = unet_tickets(c, total, (int)g.x, L.cout / 64, &tk, &tk_tab, &ntk)) != SH_OK) return rc0;
-    const u16* zp = (const u16*)c->bufs["unet16.zero"].p;
-    u16* pl = fuse == UF_POOL ? (u16*)fz.pooled : (u16*)nullptr;
-    // weights resident in LDS: one cout group whose packed weights fit behind the two input buffers (32 -> 64 and 64 -> 64 layers)
-    const bool wres = L.cout == 64 && ((C0 + C1) / 32) * 64 <= 128;
-    if (fuse == UF_POOL && wres) { LAUNCH(c, lname, (k_conv3_ldr16<EK, UF_POOL, 1>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-    else if (fuse == UF_POOL) { LAUNCH(c, lname, (k_conv3_ldr16<EK, UF_POOL, 0>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-    else if (wres) { LAUNCH(c, lname, (k_conv3_ldr16<EK, 0, 1>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-    else { LAUNCH(c, lname, (k_conv3_ldr16<EK, 0, 0>), g, dim3(UD_THREADS), src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, nimg, zp, pl, tk, tk_tab, ntk); }
-  } else if (L.taps == 9 && L.cout % 64 == 0) {
-    const dim3 g(tiles, L.cout / 64, nimg);
-    if (fuse == 0) { LAUNCH(c, lname, (k_conv_mfma16<EK, 9, 4, 0>), g, blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, fz); }
-    else if (fuse == UF_POOL) { LAUNCH(c, lname, (k_conv_mfma16<EK, 9, 4, UF_POOL>), g, blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, fz); }
-    else return fail(c, SH_ERR_ARG, "unet: unsupported fusion");
-  } else if (L.taps == 9) {
-    const dim3 g(tiles, L.cout / 32, nimg);
-    if (fuse == 0) { LAUNCH(c, lname, (k_conv_mfma16<EK, 9, 2, 0>), g, blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, relu, fz); }
-    else return fail(c, SH_ERR_ARG, "unet: unsupported fusion");
-  } else if (!c->unet_reference && L.cout % 32 == 0 && C1 == 0 && C0 % 32 == 0) {
-    // 2x2 transposed conv (k_unet16_up.h): source pixels in registers, the weights of a 32-cout group by LDS-DMA, one barrier per
-    // group (Cin = 512: per two phases); the staged form otherwise
-    const bool upg = W % 32 == 0 && H % 16 == 0 && (C0 == 128 || C0 == 256 || C0 == 512) && L.cout <= 512;
-    if (upg) {
-      // items = (image, source tile of 32 x 4 MT pixels) on the grid of the persistent convolutions, handed out by work tickets; up3 has
-      // about one item per CU: one workgroup per item
-      const int mt = C0 == 128 ? 4 : 2, nitems = (W / 32) * (H / (4 * mt)) * nimg;
-      const int grid = C0 == 512 ? nitems : std::min(nitems, persistent_grid(c));
-      unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-      if (C0 != 512) { const int trc = unet_tickets(c, nitems, grid, 1, &tk, &tk_tab, &ntk); if (trc != SH_OK) return trc; }
-      if (C0 == 128) { LAUNCH(c, lname, (k_upconv16g<EK, 4, 4, 4, true>), dim3((unsigned)grid), dim3(UPR_THREADS), src0, w, b, dst, H, W, L.cout, nimg, tk, tk_tab, ntk); }
-      else if (C0 == 256) { LAUNCH(c, lname, (k_upconv16g<EK, 8, 2, 4, true>), dim3((unsigned)grid), dim3(UPR_THREADS), src0, w, b, dst, H, W, L.cout, nimg, tk, tk_tab, ntk); }
-      else { LAUNCH(c, lname, (k_upconv16g<EK, 16, 2, 2, false>), dim3((unsigned)grid), dim3(UPR_THREADS), src0, w, b, dst, H, W, L.cout, nimg, tk, tk_tab, ntk); }
-    }
-    else { LAUNCH(c, lname, (k_upconv16<EK>), dim3(tiles, L.cout / 32, nimg * 2), dim3(UPC_THREADS), src0, C0, w, b, dst, H, W, L.cout); }
-  } else if (L.cout % 64 == 0) {
-    LAUNCH(c, lname, (k_conv_mfma16<EK, 1, 4, 0>), dim3(tiles, L.cout / 64, nimg * 4), blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0, fz);
-  } else {
-    LAUNCH(c, lname, (k_conv_mfma16<EK, 1, 2, 0>), dim3(tiles, L.cout / 32, nimg * 4), blk, src0, src1, C0, C1, w, b, dst, H, W, L.cout, 0, fz);
-  }
-  return SH_OK;
-}
-
-// does the 16-bit forward run its fused level-0 kernels (k_unet16_pp.h)?  (run_window asks: k_enc0_pp can read the unscaled image)
-namespace sh {
-bool unet16_level0_fused(const sh_ctx* c, int H, int W) {
-  return !c->unet_reference && c->unet_base == 32 && c->unet_depth >= 1 && W % 32 == 0 && H % 16 == 0 && (H >> c->unet_depth) % 16 == 0 && (W >> c->unet_depth) % 16 == 0;
-}
-}  // namespace sh
-
-// Double-conv UNet, 16-bit.  With 32 base channels the full-resolution level runs as three fused ping-pong kernels (k_unet16_pp.h:
-// image -> enc0a -> enc0b -> skip0 + pool; up0 + dec0a; dec0b + head) and every 2x2 max pool rides in the epilogue of the conv before
-// it.  Other widths, maps that do not tile, and the reference network run layer by layer.
-template <int EK>
-static int unet_forward16(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W) {
-  const int D = c->unet_depth, base = c->unet_base;
-  if ((H >> D) % 16 || (W >> D) % 16) return fail(c, SH_ERR_ARG, "unet: input size must be a multiple of 16 << depth");
+static int unet_view(sh_ctx* c, const UnetIO& io, int nimg, int H, int W, UnetView* v) {
+  const int dtype = c->params.unet_dtype, es = unet_is16(dtype) ? 2 : 4;
+  const std::string pre = unet_is16(dtype) ? "unet16." : "unet.";
+  const size_t full = (size_t)nimg * H * W * c->unet_base * es;
+  *v = UnetView{};
+  v->io = io; v->nimg = nimg; v->P = buf<float>(c, "params");
+  v->act[US_IMAGE] = (void*)io.image; v->act[US_LOGITS] = io.logits;
   int rc;
-  if ((rc = ensure(c, "params_bf16", c->unet_floats * 2, 2)) != SH_OK) return rc;
-  const float* P = buf<float>(c, "params");
-  u16* PW = buf<u16>(c, "params_bf16");
-  if (c->packed_kind != EK) {     // pack the MFMA layers' weights for this element type: one launch for all layers, once per parameter block
-    std::vector<PackEntry> tab;
-    long long total = 0;
-    for (auto& kv : c->ulayers) {
-      const sh_ctx::ULayer& l = kv.second;
-      if (l.cin < 32 || l.cout < 32) continue;
-      tab.push_back(PackEntry{total, (long long)l.w_off, l.taps, l.cin, l.cout, 0});
-      total += (long long)l.taps * l.cin * l.cout;
-    }
-    if ((rc = ensure(c, "unet16.packtab", tab.size() * sizeof(PackEntry), 8)) != SH_OK) return rc;
-    if (!c->packtab_ready) {
-      HIPCHK(c, hipMemcpyAsync(c->bufs["unet16.packtab"].p, tab.data(), tab.size() * sizeof(PackEntry), hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
-      c->packtab_ready = true;
-    }
-    LAUNCH(c, "k_pack_w_bf16", k_pack_w16_all<EK>, dim3(2048), dim3(256), P, PW, (const PackEntry*)c->bufs["unet16.packtab"].p, (int)tab.size(), total);
-    c->packed_kind = EK;
-  }
-  if ((rc = ensure(c, "unet16.tickets", SH_UNET_TICKETS * 4, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "unet16.tk_tab", SH_UNET_TKTAB * 4, 4)) != SH_OK) return rc;
-  FILL(c, {buf<unsigned>(c, "unet16.tickets"), (size_t)SH_UNET_TICKETS * 4, 0});
-  c->ticket_next = 0;
-  const bool fused = unet16_level0_fused(c, H, W);      // level 0 on the ping-pong kernels, pools in the conv epilogues
-  const size_t full = (size_t)nimg * H * W * base * 2;
-  if ((rc = ensure(c, "unet16.a", full, 2)) != SH_OK) return rc;
-  if ((rc = ensure(c, "unet16.b", full, 2)) != SH_OK) return rc;
-  std::vector<u16*> skip(D);
-  for (int i = 0; i < D; ++i) {
-    std::string nm = "unet16.skip" + std::to_string(i);
-    if ((rc = ensure(c, nm.c_str(), full >> i, 2)) != SH_OK) return rc;
-    skip[i] = buf<u16>(c, nm.c_str());
-  }
-  u16* A = buf<u16>(c, "unet16.a");
-  u16* Bq = buf<u16>(c, "unet16.b");
-  auto L = [&](const std::string& n) -> const sh_ctx::ULayer& { return c->ulayers[n]; };
-  if ((rc = ensure(c, "unet16.zero", 256, 2)) != SH_OK) return rc;
-  if (!c->zero_page_ready) { HIPCHK(c, hipMemsetAsync(buf<char>(c, "unet16.zero"), 0, 256, c->stream)); c->zero_page_ready = true; }
-  const u16* zp = (const u16*)c->bufs["unet16.zero"].p;
-  int h = H, w = W;
-  if (fused) {
-    // level-0 encoder (k_enc0_pp): image -> enc0a -> LDS -> enc0b -> skip0 + pooled
-    const sh_ctx::ULayer& la = L("enc0a");
-    const sh_ctx::ULayer& lb = L("enc0b");
-    const int total = nimg * (w / 32) * (h / 16);
-    const unsigned grid = (unsigned)std::min(total, persistent_grid(c));
-    unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-    if ((rc = unet_tickets(c, total, (int)grid, 1, &tk, &tk_tab, &ntk)) != SH_OK) return rc;
-    LAUNCH_FN(c, "unet.enc0b", launch_enc0_pp(EK, grid, c->stream, image, P + la.w_off, P + la.b_off, PW + lb.w_off, P + lb.b_off, skip[0], A, h, w, nimg,
-                                              c->unet_raw, c->unet_mm, tk, tk_tab, ntk));
-  } else {
-    const sh_ctx::ULayer& l = L("enc0a");
-    size_t npx = (size_t)nimg * h * w;
-    LAUNCH(c, "unet.enc0a", k_conv_first16<EK>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), image, P + l.w_off, P + l.b_off, A, h, w, l.cout, nimg);
-    if ((rc = conv_layer16<EK>(c, "unet.enc0b", L("enc0b"), A, nullptr, base, 0, skip[0], h, w, nimg, 1)) != SH_OK) return rc;
-  }
-  int ch = base;
-  for (int i = 1; i <= D; ++i) {
-    if (!fused) {
-      size_t e = (size_t)nimg * (h / 2) * (w / 2) * (ch / 8);
-      LAUNCH(c, "unet.pool", k_maxpool2_16<EK>, dim3((unsigned)std::min<size_t>((e + 255) / 256, 8192)), dim3(256), skip[i - 1], A, h, w, ch, nimg);
-    }
-    h /= 2; w /= 2;
-    std::string na = i < D ? "enc" + std::to_string(i) + "a" : "bota", nb = i < D ? "enc" + std::to_string(i) + "b" : "botb";
-    if ((rc = conv_layer16<EK>(c, ("unet." + na).c_str(), L(na), A, nullptr, ch, 0, Bq, h, w, nimg, 1)) != SH_OK) return rc;
-    ch *= 2;
-    u16* dst = i < D ? skip[i] : A;
-    ConvFuse fz{};
-    fz.pooled = A;      // (A was consumed by the conv above; the next level reads it)
-    if ((rc = conv_layer16<EK>(c, ("unet." + nb).c_str(), L(nb), Bq, nullptr, ch, 0, dst, h, w, nimg, 1, (fused && i < D) ? UF_POOL : 0, fz)) != SH_OK) return rc;
-  }
-  u16* x = A; u16* y = Bq;
-  for (int i = D - 1; i >= 0; --i) {
-    std::string nu = "up" + std::to_string(i), na = "dec" + std::to_string(i) + "a", nb = "dec" + std::to_string(i) + "b";
-    if (fused && i == 0) {
-      // level 0: the up-convolution computed inside dec0a (k_dec0a_up_pp: x = low-resolution input, y = dec0a's output), then
-      // dec0b with the 1x1 head in its epilogue (k_dec0b_head_pp: only the logits leave the kernel)
-      h *= 2; w *= 2; ch /= 2;
-      const sh_ctx::ULayer& lu = L(nu);
-      const sh_ctx::ULayer& la = L(na);
-      const sh_ctx::ULayer& lb = L(nb);
-      const sh_ctx::ULayer& lh = L("head");
-      {
-        const int total = nimg * (w / 32) * (h / 8);
-        const unsigned grid = (unsigned)std::min(total, persistent_grid(c));
-        unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-        if ((rc = unet_tickets(c, total, (int)grid, 1, &tk, &tk_tab, &ntk)) != SH_OK) return rc;
-        LAUNCH_FN(c, "unet.dec0a", launch_dec0a_up_pp(EK, grid, c->stream, skip[0], x, PW + la.w_off, P + la.b_off, PW + lu.w_off, P + lu.b_off, y, h, w, nimg,
-                                                      zp, tk, tk_tab, ntk));
-      }
-      {
-        const int total = nimg * (w / 32) * (h / 16);
-        const unsigned grid = (unsigned)std::min(total, persistent_grid(c));
-        unsigned* tk = nullptr; const int* tk_tab = nullptr; int ntk = 0;
-        if ((rc = unet_tickets(c, total, (int)grid, 1, &tk, &tk_tab, &ntk)) != SH_OK) return rc;
-        LAUNCH_FN(c, "unet.dec0b", launch_dec0b_head_pp(EK, grid, c->stream, y, PW + lb.w_off, P + lb.b_off, P + lh.w_off, P + lh.b_off, logits, h, w, nimg,
-                                                        zp, tk, tk_tab, ntk));
-      }
-      return SH_OK;
-    }
-    if ((rc = conv_layer16<EK>(c, ("unet." + nu).c_str(), L(nu), x, nullptr, ch, 0, y, h, w, nimg, 0)) != SH_OK) return rc;
-    h *= 2; w *= 2; ch /= 2;
-    if ((rc = conv_layer16<EK>(c, ("unet." + na).c_str(), L(na), skip[i], y, ch, ch, x, h, w, nimg, 1)) != SH_OK) return rc;
-    if ((rc = conv_layer16<EK>(c, ("unet." + nb).c_str(), L(nb), x, nullptr, ch, 0, y, h, w, nimg, 1)) != SH_OK) return rc;
-    std::swap(x, y);
-  }
-  {
-    const sh_ctx::ULayer& l = L("head");
-    size_t npx = (size_t)nimg * H * W;
-    LAUNCH(c, "unet.head", k_head16<EK>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), x, P + l.w_off, P + l.b_off, logits, l.cin, npx, (size_t)H * W);
+  if ((rc = ensure(c, (pre + "a").c_str(), full, es, &v->act[US_A])) != SH_OK) return rc;
+  if ((rc = ensure(c, (pre + "b").c_str(), full, es, &v->act[US_B])) != SH_OK) return rc;
+  for (int i = 0; i < c->unet_depth; ++i)      // H*W/4^i * base*2^i
+    if ((rc = ensure(c, (pre + "skip" + std::to_string(i)).c_str(), full >> i, es, &v->act[US_SKIP + i])) != SH_OK) return rc;
+  if (dtype == SH_UNET_F32X) {
+    if ((rc = ensure(c, "params_x3h", c->unet_floats * 2, 2, (void**)&v->wh)) != SH_OK) return rc;
+    if ((rc = ensure(c, "params_x3l", c->unet_floats * 2, 2, (void**)&v->wl)) != SH_OK) return rc;
+  } else if (unet_is16(dtype)) {
+    if ((rc = ensure(c, "params_bf16", c->unet_floats * 2, 2, (void**)&v->PW)) != SH_OK) return rc;
+    if ((rc = ensure(c, "unet16.tickets", SH_UNET_TICKETS * 4, 4, (void**)&v->tickets)) != SH_OK) return rc;
+    if ((rc = ensure(c, "unet16.tk_tab", SH_UNET_TKTAB * 4, 4, (void**)&v->tk_tab)) != SH_OK) return rc;
+    if ((rc = ensure(c, "unet16.zero", 256, 2, (void**)&v->zero)) != SH_OK) return rc;
   }
   return SH_OK;
 }
 
-namespace sh {
-int unet_dispatch(sh_ctx* c, const float* image, float* logits, int nimg, int H, int W) {
-  switch (c->params.unet_dtype) {
-    case SH_UNET_BF16: return unet_forward16<0>(c, image, logits, nimg, H, W);
-    case SH_UNET_F16: return unet_forward16<1>(c, image, logits, nimg, H, W);
-    default: return unet_forward(c, image, logits, nimg, H, W);
+// The MFMA layers' weights in the form the kernels read -- 16-bit (kind 0 bf16, 1 f16) or split into f16 high / low parts (kind -1):
+// one launch for all layers, once per parameter block; the layer table goes up once per loaded network.
+static int pack_weights(sh_ctx* c, const UnetView& v, int kind) {
+  sh_ctx::Unet& u = c->unet;
+  if (kind < 0 ? u.packed_x3 : u.packed_kind == kind) return SH_OK;
+  std::vector<PackRow> tab;
+  long long total = 0;
+  const UnetError e = pack_table(c->ulayers, &tab, &total, kind < 0 ? c->h_unet.data() : nullptr, c->h_unet.size());
+  if (e.code != SH_OK) return fail(c, e.code, e.text);
+  int rc;
+  PackEntry* dtab = nullptr;
+  if ((rc = ensure(c, "unet16.packtab", tab.size() * sizeof(PackRow), 8, (void**)&dtab)) != SH_OK) return rc;
+  if (!u.packtab_ready) {
+    HIPCHK(c, hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(PackRow), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
+    u.packtab_ready = true;
   }
+  if (kind < 0) {
+    LAUNCH(c, "k_pack_w_x3", k_pack_w_x3, dim3(2048), dim3(256), v.P, v.wh, v.wl, (const PackEntry*)dtab, (int)tab.size(), total);
+    u.packed_x3 = true;
+  } else {
+    LAUNCH(c, "k_pack_w_bf16", (kind ? k_pack_w16_all<1> : k_pack_w16_all<0>), dim3(2048), dim3(256), v.P, v.PW, (const PackEntry*)dtab, (int)tab.size(), total);
+    u.packed_kind = kind;
+  }
+  return SH_OK;
+}
+
+// the page of zeros the LDS-DMA kernels read for pixels outside the image
+static int zero_page(sh_ctx* c, const UnetView& v) {
+  if (c->unet.zero_page_ready) return SH_OK;
+  HIPCHK(c, hipMemsetAsync((void*)v.zero, 0, 256, c->stream));
+  c->unet.zero_page_ready = true;
+  return SH_OK;
+}
+
+// work tickets of a persistent launch: the next free counter of this forward pass and the table of item bounds (ticket_table) for the
+// step's (items, workgroups, cout groups), built and uploaded once per shape
+struct Tickets { unsigned* tk = nullptr; const int* tab = nullptr; int n = 0; };
+static int take_tickets(sh_ctx* c, const UnetView& v, const UnetStep& s, Tickets* t) {
+  sh_ctx::Unet& u = c->unet;
+  const auto key = std::make_tuple(s.tk_items, s.tk_nwg, s.tk_ngrp);
+  auto it = u.tk_tabs.find(key);
+  if (it == u.tk_tabs.end()) {
+    const std::vector<int> tab = ticket_table(s.tk_items, s.tk_nwg, s.tk_ngrp);
+    if ((int)tab.size() > SH_UNET_TKTAB) return fail(c, SH_ERR_CAPACITY, "unet: ticket table larger than its buffer");
+    if (u.tk_tab_used + (int)tab.size() > SH_UNET_TKTAB) {      // many different shapes (sh_unet_infer with varying n): start the cache over
+      HIPCHK(c, hipStreamSynchronize(c->stream));                // (launches that read the old tables are done)
+      u.tk_tabs.clear();
+      u.tk_tab_used = 0;
+    }
+    HIPCHK(c, hipMemcpyAsync(v.tk_tab + u.tk_tab_used, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
+    it = u.tk_tabs.emplace(key, std::make_pair(u.tk_tab_used, (int)tab.size() - 1)).first;
+    u.tk_tab_used += (int)tab.size();
+  }
+  if (u.ticket_next >= SH_UNET_TICKETS) return fail(c, SH_ERR_CAPACITY, "unet: out of work counters");
+  t->tk = v.tickets + u.ticket_next++;
+  t->tab = v.tk_tab + it->second.first;
+  t->n = it->second.second;
+  return SH_OK;
+}
+
+// a launch on the persistent grid the plan sized: its work tickets (none: one workgroup per item), then `go`
+template <typename F>
+static int persistent_launch(sh_ctx* c, const UnetView& v, const UnetStep& s, F&& go) {
+  Tickets t;
+  if (s.tk_items) { const int rc = take_tickets(c, v, s, &t); if (rc != SH_OK) return rc; }
+  return go(t);
+}
+
+// ---- the instantiation a step names: one line each -------------------------------------------------------------------------
+#define PICK(a, b, c_, d, ...) if (s.t[0] == (a) && s.t[1] == (b) && s.t[2] == (c_) && s.t[3] == (d)) return (__VA_ARGS__)
+static auto pick_f32(const UnetStep& s) -> decltype(&k_conv_mfma_f32<9, 4>) {
+  PICK(9, 4, 0, 0, k_conv_mfma_f32<9, 4>); PICK(9, 2, 0, 0, k_conv_mfma_f32<9, 2>); PICK(1, 4, 0, 0, k_conv_mfma_f32<1, 4>); PICK(1, 2, 0, 0, k_conv_mfma_f32<1, 2>);
+  return nullptr;
+}
+static auto pick_x3(const UnetStep& s) -> decltype(&k_conv_mfma_x3<9, 4>) {
+  PICK(9, 2, UF_FIRST | UF_POOL, 0, k_conv_mfma_x3<9, 2, UF_FIRST | UF_POOL, 0>);      // enc0b with enc0a computed while its halo tile is staged
+  PICK(9, 2, UF_HEAD, 1, k_conv_mfma_x3<9, 2, UF_HEAD>);      // (no pass plans it: the head stays on k_head; the library keeps the parent's kernels)
+  PICK(9, 4, UF_POOL, 1, k_conv_mfma_x3<9, 4, UF_POOL>); PICK(9, 2, UF_POOL, 0, k_conv_mfma_x3<9, 2, UF_POOL, 0>);
+  PICK(9, 4, 0, 1, k_conv_mfma_x3<9, 4>); PICK(9, 2, 0, 0, k_conv_mfma_x3<9, 2, 0, 0>); PICK(1, 4, 0, 1, k_conv_mfma_x3<1, 4>); PICK(1, 2, 0, 1, k_conv_mfma_x3<1, 2>);
+  return nullptr;
+}
+static auto pick_x3r(const UnetStep& s) -> decltype(&k_upconv_x3r<2, 4>) {
+  PICK(2, 4, 0, 0, k_upconv_x3r<2, 4>); PICK(4, 4, 0, 0, k_upconv_x3r<4, 4>); PICK(8, 2, 0, 0, k_upconv_x3r<8, 2>); PICK(16, 1, 0, 0, k_upconv_x3r<16, 1>);
+  return nullptr;
+}
+template <int EK> static auto pick_conv16(const UnetStep& s) -> decltype(&k_conv_mfma16<EK, 9, 4, 0>) {
+  PICK(9, 4, 0, 0, k_conv_mfma16<EK, 9, 4, 0>); PICK(9, 4, UF_POOL, 0, k_conv_mfma16<EK, 9, 4, UF_POOL>); PICK(9, 2, 0, 0, k_conv_mfma16<EK, 9, 2, 0>);
+  PICK(1, 4, 0, 0, k_conv_mfma16<EK, 1, 4, 0>); PICK(1, 2, 0, 0, k_conv_mfma16<EK, 1, 2, 0>);
+  return nullptr;
+}
+template <int EK> static auto pick_ldr16(const UnetStep& s) -> decltype(&k_conv3_ldr16<EK, 0, 0>) {
+  PICK(UF_POOL, 1, 0, 0, k_conv3_ldr16<EK, UF_POOL, 1>); PICK(UF_POOL, 0, 0, 0, k_conv3_ldr16<EK, UF_POOL, 0>); PICK(0, 1, 0, 0, k_conv3_ldr16<EK, 0, 1>); PICK(0, 0, 0, 0, k_conv3_ldr16<EK, 0, 0>);
+  return nullptr;
+}
+template <int EK> static auto pick_upg16(const UnetStep& s) -> decltype(&k_upconv16g<EK, 4, 4, 4, true>) {
+  PICK(4, 4, 4, 1, k_upconv16g<EK, 4, 4, 4, true>); PICK(8, 2, 4, 1, k_upconv16g<EK, 8, 2, 4, true>); PICK(16, 2, 2, 0, k_upconv16g<EK, 16, 2, 2, false>);
+  return nullptr;
+}
+#undef PICK
+#define EK2(fn) (s.ek ? fn<1> : fn<0>)      // the bf16 / f16 pair of a 16-bit kernel or picker
+
+// One step of the plan: its pointers from the view, its kernel from the plan's kind and template arguments.  A kernel the plan names
+// and the library lacks is an error, never another kernel.
+static int launch_step(sh_ctx* c, const UnetView& v, const UnetStep& s) {
+  const char* nm = s.timer.c_str();
+  const dim3 g(s.grid[0], s.grid[1], s.grid[2]), blk(s.block);
+  const float *w = v.P + s.L.w_off, *b = v.P + s.L.b_off, *w2 = v.P + s.L2.w_off, *b2 = v.P + s.L2.b_off;      // (L2: the layer fused in)
+  const u16* w16 = v.PW ? v.PW + s.L.w_off : nullptr;
+  const int H = s.H, W = s.W, nimg = v.nimg;
+  const size_t npx = (size_t)nimg * H * W;
+  const float* nf = nullptr;
+  const int missing = SH_ERR_STATE;
+#define NEED(k) if (!(k)) return fail(c, missing, "unet: no kernel " + s.text() + " for " + s.timer)
+  switch (s.kind) {
+    case UK_CONV_FIRST: LAUNCH(c, nm, k_conv_first, g, blk, v.io.image, w, b, v.at<float>(s.dst), H, W, s.cout, nimg); break;
+    case UK_CONV_FIRST16: LAUNCH(c, nm, EK2(k_conv_first16), g, blk, v.io.image, w, b, v.at<u16>(s.dst), H, W, s.cout, nimg); break;
+    case UK_MAXPOOL2: LAUNCH(c, nm, k_maxpool2, g, blk, v.at<float>(s.src0), v.at<float>(s.dst), H, W, s.C0, nimg); break;
+    case UK_MAXPOOL2_16: LAUNCH(c, nm, EK2(k_maxpool2_16), g, blk, v.at<u16>(s.src0), v.at<u16>(s.dst), H, W, s.C0, nimg); break;
+    case UK_HEAD: LAUNCH(c, nm, (s.t[0] == 32 ? k_head<32> : k_head<64>), g, blk, v.at<float>(s.src0), w, b, v.io.logits, s.C0, npx); break;
+    case UK_HEAD16: LAUNCH(c, nm, EK2(k_head16), g, blk, v.at<u16>(s.src0), w, b, v.io.logits, s.C0, npx, (size_t)H * W); break;
+    case UK_CONV_F32: {
+      const auto k = pick_f32(s);
+      NEED(k);
+      LAUNCH(c, nm, k, g, blk, v.at<float>(s.src0), v.at<float>(s.src1), s.C0, s.C1, w, b, v.at<float>(s.dst), H, W, s.cout, s.relu);
+    } break;
+    case UK_CONV_X3: {      // weights split once per parameter block (pack_weights)
+      const auto k = pick_x3(s);
+      NEED(k);
+      const bool first = s.fuse & UF_FIRST, head = s.fuse & UF_HEAD;
+      LAUNCH(c, nm, k, g, blk, v.at<float>(s.src0), v.at<float>(s.src1), s.C0, s.C1, v.wh + s.L.w_off, v.wl + s.L.w_off, b, v.at<float>(s.dst), H, W, s.cout, s.relu,
+             v.at<float>(s.pool), head ? w2 : nf, head ? b2 : nf, head ? v.io.logits : nullptr, first ? v.io.image : nf, first ? w2 : nf, first ? b2 : nf);
+    } break;
+    case UK_UPCONV_X3R: {
+      const auto k = pick_x3r(s);
+      NEED(k);
+      LAUNCH(c, nm, k, g, blk, v.at<float>(s.src0), v.wh + s.L.w_off, v.wl + s.L.w_off, b, v.at<float>(s.dst), H, W, s.cout);
+    } break;
+    case UK_CONV16: {
+      const auto k = EK2(pick_conv16)(s);
+      NEED(k);
+      ConvFuse fz{};
+      fz.pooled = v.at<u16>(s.pool);
+      LAUNCH(c, nm, k, g, blk, v.at<u16>(s.src0), v.at<u16>(s.src1), s.C0, s.C1, w16, b, v.at<u16>(s.dst), H, W, s.cout, s.relu, fz);
+    } break;
+    case UK_CONV3_LDR16: {
+      const auto k = EK2(pick_ldr16)(s);
+      NEED(k);
+      return persistent_launch(c, v, s, [&](const Tickets& t) -> int {
+        LAUNCH(c, nm, k, g, blk, v.at<u16>(s.src0), v.at<u16>(s.src1), s.C0, s.C1, w16, b, v.at<u16>(s.dst), H, W, s.cout, s.relu, nimg, v.zero, v.at<u16>(s.pool), t.tk, t.tab, t.n);
+        return SH_OK;
+      });
+    }
+    case UK_UPCONV16G: {
+      const auto k = EK2(pick_upg16)(s);
+      NEED(k);
+      return persistent_launch(c, v, s, [&](const Tickets& t) -> int {
+        LAUNCH(c, nm, k, g, blk, v.at<u16>(s.src0), w16, b, v.at<u16>(s.dst), H, W, s.cout, nimg, t.tk, t.tab, t.n);
+        return SH_OK;
+      });
+    }
+    case UK_UPCONV16: LAUNCH(c, nm, EK2(k_upconv16), g, blk, v.at<u16>(s.src0), s.C0, w16, b, v.at<u16>(s.dst), H, W, s.cout); break;
+    case UK_ENC0_PP:      // L2 = enc0a
+      return persistent_launch(c, v, s, [&](const Tickets& t) -> int {
+        LAUNCH_FN(c, nm, launch_enc0_pp(s.ek, g.x, c->stream, v.io.image, w2, b2, w16, b, v.at<u16>(s.dst), v.at<u16>(s.pool), H, W, nimg, v.io.raw, v.io.mm, t.tk, t.tab, t.n));
+        return SH_OK;
+      });
+    case UK_DEC0A_UP_PP:      // L2 = up0
+      return persistent_launch(c, v, s, [&](const Tickets& t) -> int {
+        LAUNCH_FN(c, nm, launch_dec0a_up_pp(s.ek, g.x, c->stream, v.at<u16>(s.src0), v.at<u16>(s.src1), w16, b, v.PW + s.L2.w_off, b2, v.at<u16>(s.dst), H, W, nimg, v.zero, t.tk, t.tab, t.n));
+        return SH_OK;
+      });
+    case UK_DEC0B_HEAD_PP:      // L2 = head
+      return persistent_launch(c, v, s, [&](const Tickets& t) -> int {
+        LAUNCH_FN(c, nm, launch_dec0b_head_pp(s.ek, g.x, c->stream, v.at<u16>(s.src0), w16, b, w2, b2, v.io.logits, H, W, nimg, v.zero, t.tk, t.tab, t.n));
+        return SH_OK;
+      });
+    default: return fail(c, missing, "unet: no kernel " + s.text() + " for " + s.timer);
+  }
+#undef NEED
+  return SH_OK;
+}
+
+namespace sh {
+// One forward pass: plan, buffers, view, the steps.  The plan is built per call (tens of short strings and map lookups, as the walks
+// it replaces did).
+int unet_dispatch(sh_ctx* c, const UnetIO& io, int nimg, int H, int W) {
+  const int dtype = c->params.unet_dtype;
+  const bool b16 = unet_is16(dtype);
+  std::vector<UnetStep> steps;
+  const UnetError e = unet_plan(c->ulayers, c->unet_base, c->unet_depth, dtype, c->unet.reference, H, W, nimg, b16 ? persistent_grid(c) : 0, io.raw != nullptr, &steps);
+  if (e.code != SH_OK) return fail(c, e.code, e.text);
+  UnetView v;
+  int rc;
+  if ((rc = unet_view(c, io, nimg, H, W, &v)) != SH_OK) return rc;
+  if (b16 || dtype == SH_UNET_F32X) { if ((rc = pack_weights(c, v, b16 ? (dtype == SH_UNET_F16) : -1)) != SH_OK) return rc; }
+  if (b16) {
+    if ((rc = zero_page(c, v)) != SH_OK) return rc;
+    FILL(c, {v.tickets, (size_t)SH_UNET_TICKETS * 4, 0});
+    c->unet.ticket_next = 0;
+  }
+  for (const UnetStep& s : steps)
+    if ((rc = launch_step(c, v, s)) != SH_OK) return rc;
+  return SH_OK;
 }
 }  // namespace sh
 
@@ -457,13 +323,14 @@ int sh_unet_infer(sh_ctx* c, const float* images, int n, int H, int W, float* lo
   HIPCHK(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)n * H * W * 4;
   int rc;
-  if ((rc = ensure(c, "infer.image", bytes, 4)) != SH_OK) return rc;
-  if ((rc = ensure(c, "infer.logits", bytes, 4)) != SH_OK) return rc;
+  float *d_image = nullptr, *d_logits = nullptr;
+  if ((rc = ensure(c, "infer.image", bytes, 4, (void**)&d_image)) != SH_OK) return rc;
+  if ((rc = ensure(c, "infer.logits", bytes, 4, (void**)&d_logits)) != SH_OK) return rc;
   WindowScope whole(c, 0, c->Bwin);      // named buffers below are whole-batch
-  HIPCHK(c, hipMemcpyAsync(buf<float>(c, "infer.image"), images, bytes, hipMemcpyHostToDevice, c->stream));
-  rc = unet_dispatch(c, buf<float>(c, "infer.image"), buf<float>(c, "infer.logits"), n, H, W);
+  HIPCHK(c, hipMemcpyAsync(d_image, images, bytes, hipMemcpyHostToDevice, c->stream));
+  rc = unet_dispatch(c, {d_image, nullptr, nullptr, d_logits}, n, H, W);
   if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-  HIPCHK(c, hipMemcpyAsync(logits, buf<float>(c, "infer.logits"), bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(logits, d_logits, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -237,3 +237,34 @@ def test_first_kernel_scales_the_raw_image_itself(engine, oracle_bones, name):
     finally:
         engine.set_keep_products(False)
         engine.reset_params()
+
+
+LAYER_NAMES = (["enc%d%s" % (i, ab) for i in range(4) for ab in "ab"] + ["bota", "botb"] + ["up%d" % i for i in range(4)]
+               + ["dec%d%s" % (i, ab) for i in range(4) for ab in "ab"] + ["head"])
+
+
+@pytest.mark.parametrize("config", ["bf16", "f16", "bf16_reference", "f16_reference", "f32", "f32x"])
+def test_unet_launches_per_layer(config):
+    """Launches per "unet.*" timer of ONE pass over a 1 x 256 x 256 image (the smallest the default network accepts).  Production
+    16-bit: 20 names once each -- enc0a rides in enc0b, up0 in dec0a, the head in dec0b, every pool in the conv before it.  The
+    reference network and f32: all 23 layers once and four pools.  f32x: those without enc0a (inside enc0b) and without the pools."""
+    from conftest import engine_with_env
+    name, _, ref = config.partition("_")
+    dtype = {"bf16": _lib.UNET_BF16, "f16": _lib.UNET_F16, "f32": _lib.UNET_F32, "f32x": _lib.UNET_F32X}[name]
+    want = {n: 1 for n in LAYER_NAMES}
+    want["pool"] = 4
+    if name in ("bf16", "f16") and not ref:
+        want.update(enc0a=0, pool=0, up0=0, head=0)
+    elif name == "f32x":
+        want.update(enc0a=0, pool=0)
+    assert sum(want.values()) == {"bf16": 20, "f16": 20, "f32": 27, "f32x": 22}[name] + (7 if ref else 0)
+    img = np.random.default_rng(5).random((1, 256, 256), dtype=np.float32)
+    with engine_with_env(SHOULDER_UNET_REFERENCE=1 if ref else 0) as e:
+        e.set_params(unet_dtype=dtype)
+        e.enable_timing(2)
+        try:
+            e.unet_infer(img)
+            got = {n: e.kernel_time_ms("unet." + n)[1] for n in want}
+        finally:
+            e.enable_timing(0)
+    assert got == want
