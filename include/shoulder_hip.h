@@ -522,6 +522,89 @@ typedef struct sh_stem_fit {
 } sh_stem_fit;
 int sh_resect_stems(sh_ctx*, const sh_stem* stems, int K, sh_stem_fit* out /* B x P x K, host */);
 
+/* ---- implant plans: cuts, heads and stems joined and ranked -------------------------------------------------------------------
+ * The step the four calls above were built for (arthroplasty.py:178-182, the commented-out `HumeralImplantation` that "continues from
+ * the humeral head osteotomy and places the implant"): the N best (cut, head, stem) triples of every humerus under one rule, ranked
+ * on the device from the records of the LAST seated call (sh_resect_*_seat, K_h heads) and the LAST sh_resect_stems (K_s stems) of
+ * the resident batch (k_plan.h).  No record goes to the host for it, and the ranking is the same bytes wherever it is run.
+ *
+ * Frame of humerus b: "canal.frames"[b] of the last sh_canal_profile, the frame the stems were fitted in; a point maps as
+ * sh_canal_profile maps a vertex (sh_scalar.h canal_map_point), "the frame's z" is the third coordinate of that.
+ *
+ * sh_plan_ref, the reference of a humerus.  The reference plane (o_a, n_a) is row b of ref_planes or, with ref_planes == NULL, the
+ * anp_plane_point / anp_plane_normal of the humerus' record.  For each vertex v of the humerus, widened to float64:
+ * s_v = ((v_x - o_x) n_x + (v_y - o_y) n_y) + (v_z - o_z) n_z with the normal as given, z_v the frame's z of v.
+ *   head_apex        the vertex with s_v > 0 and the largest z_v; head_apex_z its z_v, head_apex_vid its index in the humerus
+ *   tuberosity_top   the vertex with s_v <= -(margin |n_a|) and the largest z_v (margin: sh_plan_rule, mm); tuberosity_z, tuberosity_vid
+ *                    Of equal z_v the smaller vertex index wins, on both sides.
+ *   head_height      head_apex_z - tuberosity_z
+ *   n_feasible       the number of ALL feasible candidates of the humerus (see below), not of the returned ones
+ *   status           SH_ERR_GEOMETRY when a side has no vertex; the status of a failed record (ref_planes == NULL; SH_ERR_GEOMETRY for a
+ *                    record whose plane is not finite) or of a failed "canal.status"[b].  With a non-zero status every other field is
+ *                    zero, the vids are -1, n_feasible is 0 and all N plans of the humerus carry the status.
+ * On an intact humerus with a true anatomic-neck plane, tuberosity_top is the top of the greater tuberosity: the highest point of
+ * the bone along the canal that is not head.  This is a GEOMETRIC definition.  Nobody has checked it against annotated anatomy, and
+ * the anatomic-neck network that ships with this library is a seeded stand-in, not a trained one.
+ *
+ * A candidate of humerus b is (p, k_h, k_s) with index i = (p K_h + k_h) K_s + k_s.  Its cost is the sum of three parts, every sum
+ * added left to right as written:
+ *   cut part (b, p)       entry: where the frame's z axis pierces the cut's plane, sh_resect_stems' `entry` (sh_scalar.h stem_entry).
+ *                         eccentricity = |seat_center - entry| (sh_seat.seat_center of the cut: how far the head's taper would sit
+ *                         from the stem's axis, in the plane); cut_cost = w_eccentricity eccentricity.  Feasible when
+ *                         sh_resection.status == 0, n_loops >= 1, the seat record k_h = 0 of the cut has status 0 (a seat's status and
+ *                         seat_center depend on the cut alone), the entry exists, sphere_status == 0 when w_cor > 0, and
+ *                         eccentricity <= max_eccentricity.
+ *   head part (b, p, k_h) uncovered = 1 - coverage, overhang = max_overhang, cor = |cor_shift| (all of sh_seat), apex = seat_center +
+ *                         (h n) / |n| with h the head's thickness and n the cut's normal, apex_z the frame's z of apex, height =
+ *                         |apex_z - head_apex_z|; head_cost = ((w_uncovered uncovered + w_overhang overhang) + w_cor cor) + w_height
+ *                         height.  Feasible when max_overhang <= rule.max_overhang and coverage >= min_coverage.
+ *   stem part (b, p, k_s) fill = |fill_mean - fill_target|, stem_cost = w_fill fill.  Feasible when status == 0, fits == 1 and
+ *                         min_clearance >= rule.min_clearance (all of sh_stem_fit).
+ *   cost = (head_cost + stem_cost) + cut_cost.  The candidate is feasible when its three parts are, its cost is not NaN and compat ==
+ *   NULL or bit k_s of compat[k_h] is set (which stems of a system a head goes with).
+ * Candidates sort ascending by (cost, i); plan r of a humerus is its r-th feasible candidate in that order.  A slot beyond
+ * n_feasible has cut = head = stem = -1, status SH_ERR_GEOMETRY and every other field zero.
+ *
+ * sh_plan: cost and its six UNWEIGHTED terms, the apex of the implant head (CT), its frame height, head_height = apex_z -
+ * tuberosity_z (the restored head height above the tuberosity, to be read against sh_plan_ref.head_height), the three indices.
+ *
+ * SH_ERR_ARG: N outside 1..SH_PLAN_MAX, a NULL rule or out, a NaN anywhere in the rule, a weight that is negative or infinite,
+ * margin < 0, a ref_planes row that is not finite or has a zero normal.  A limit of +-inf switches that limit off.
+ * SH_ERR_STATE (sh_last_error names what is missing): no seated resection of the resident batch; stems that were not fitted
+ * against exactly that resection and the current profile (a resection or a profile made after sh_resect_stems voids the stems FOR
+ * THIS CALL only: sh_resect_stems itself keeps its preconditions); ref_planes == NULL without a collected run with SH_STAGE_ANP |
+ * SH_STAGE_CSYS; runs in flight.  SH_ERR_NOMEM when the buffers do not fit.  A bad plan never fails the batch.
+ *
+ * Named buffers (sh_fetch), valid until the next upload / commit / sh_store("verts") as the profile is: "plan.ref" (B sh_plan_ref),
+ * "plan.out" (B x N sh_plan), and the compact parts of 16 bytes {double cost; int32 feasible; int32 pad}: "plan.cut_terms" (B x P),
+ * "plan.head_terms" (B x P x K_h), "plan.stem_terms" (B x P x K_s).
+ * Determinism: the vertex maxima are reduced per tile of 256 vertices by one fixed tree and the tiles in tile order; the ranking
+ * takes N rounds of an arg-min of the key (cost, i) over the keys greater than the previous round's.  Maxima and minima under a total
+ * order do not depend on the reduction order: a humerus' rows are the same bytes whatever B, its position in the batch or the launch
+ * shape.  No floating-point atomics, no floating-point sums across lanes.
+ * Cost: one pass over the vertices and N P K_h K_s / 256 two-load evaluations per lane of one workgroup per humerus -- nothing at
+ * a planning sweep (27 x 16 x 16, N = 8), slow at the limits (4 096 x 64 x 64, N = 64: 4e6 evaluations per lane).  There is one
+ * variant. */
+#define SH_PLAN_MAX 64
+typedef struct sh_plan_rule {            /* 12 doubles */
+  double max_overhang, min_coverage, min_clearance, max_eccentricity;   /* limits; +-inf switches one off */
+  double fill_target, margin;            /* margin >= 0, mm: see sh_plan_ref */
+  double w_uncovered, w_overhang, w_cor, w_height, w_eccentricity, w_fill;   /* finite, >= 0 */
+} sh_plan_rule;
+typedef struct sh_plan_ref {             /* one per humerus, 96 B */
+  double tuberosity_top[3], tuberosity_z, head_apex[3], head_apex_z, head_height;
+  int64_t n_feasible;
+  int32_t tuberosity_vid, head_apex_vid, status, pad;
+} sh_plan_ref;
+typedef struct sh_plan {                 /* one per (humerus, rank), 112 B: twelve doubles and four int32, no padding */
+  double cost, uncovered, overhang, cor, height, eccentricity, fill;    /* cost and its six UNWEIGHTED terms */
+  double apex[3], apex_z, head_height;
+  int32_t cut, head, stem, status;
+} sh_plan;
+int sh_resect_plan(sh_ctx*, const sh_plan_rule* rule, const uint64_t* compat /* K_h words or NULL */,
+                   const double* ref_planes /* B x (point, normal), CT, or NULL: each record's anp plane */,
+                   int N, sh_plan* out /* B x N, host */, sh_plan_ref* ref_out /* B, host, nullable */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

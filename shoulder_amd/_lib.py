@@ -180,6 +180,46 @@ STEM_FIT_DTYPE = np.dtype([
 assert STEM_FIT_DTYPE.itemsize == ctypes.sizeof(StemFit) and STEM_DTYPE.itemsize == ctypes.sizeof(Stem)
 
 
+PLAN_MAX = 64
+_PLAN_RULE_FIELDS = ("max_overhang", "min_coverage", "min_clearance", "max_eccentricity", "fill_target", "margin",
+                     "w_uncovered", "w_overhang", "w_cor", "w_height", "w_eccentricity", "w_fill")
+
+
+class PlanRule(ctypes.Structure):
+    """sh_plan_rule: the limits, the two constants and the weights one ranking of (cut, head, stem) triples runs under."""
+    _fields_ = [(n, ctypes.c_double) for n in _PLAN_RULE_FIELDS]
+
+
+PLAN_RULE_DTYPE = np.dtype([(n, "<f8") for n in _PLAN_RULE_FIELDS])
+
+
+class PlanRef(ctypes.Structure):
+    """sh_plan_ref: the height reference of one humerus -- native head apex and tuberosity top in its canal frame."""
+    _fields_ = [("tuberosity_top", ctypes.c_double * 3), ("tuberosity_z", ctypes.c_double), ("head_apex", ctypes.c_double * 3),
+                ("head_apex_z", ctypes.c_double), ("head_height", ctypes.c_double), ("n_feasible", ctypes.c_int64),
+                ("tuberosity_vid", ctypes.c_int32), ("head_apex_vid", ctypes.c_int32), ("status", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+PLAN_REF_DTYPE = np.dtype([
+    ("tuberosity_top", "<f8", (3,)), ("tuberosity_z", "<f8"), ("head_apex", "<f8", (3,)), ("head_apex_z", "<f8"), ("head_height", "<f8"),
+    ("n_feasible", "<i8"), ("tuberosity_vid", "<i4"), ("head_apex_vid", "<i4"), ("status", "<i4"), ("pad", "<i4")])
+
+
+class Plan(ctypes.Structure):
+    """sh_plan: one ranked (cut, head, stem) triple of one humerus, its cost and the six unweighted terms of it."""
+    _fields_ = [("cost", ctypes.c_double), ("uncovered", ctypes.c_double), ("overhang", ctypes.c_double), ("cor", ctypes.c_double),
+                ("height", ctypes.c_double), ("eccentricity", ctypes.c_double), ("fill", ctypes.c_double), ("apex", ctypes.c_double * 3),
+                ("apex_z", ctypes.c_double), ("head_height", ctypes.c_double), ("cut", ctypes.c_int32), ("head", ctypes.c_int32),
+                ("stem", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+PLAN_DTYPE = np.dtype([
+    ("cost", "<f8"), ("uncovered", "<f8"), ("overhang", "<f8"), ("cor", "<f8"), ("height", "<f8"), ("eccentricity", "<f8"), ("fill", "<f8"),
+    ("apex", "<f8", (3,)), ("apex_z", "<f8"), ("head_height", "<f8"), ("cut", "<i4"), ("head", "<i4"), ("stem", "<i4"), ("status", "<i4")])
+PLAN_TERM_DTYPE = np.dtype([("cost", "<f8"), ("feasible", "<i4"), ("pad", "<i4")])      # the elements of "plan.cut_terms" / "head_terms" / "stem_terms"
+assert PLAN_RULE_DTYPE.itemsize == ctypes.sizeof(PlanRule) and PLAN_REF_DTYPE.itemsize == ctypes.sizeof(PlanRef) and PLAN_DTYPE.itemsize == ctypes.sizeof(Plan)
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -194,7 +234,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring",
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
-           "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems"]
+           "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan"]
 
 _lib = None
 
@@ -294,5 +334,7 @@ def load(build_if_missing=True):
     if not alt or hasattr(L, "sh_canal_profile"):      # (tools/time_stem.py parent)
         L.sh_canal_profile.argtypes = [vp, ctypes.POINTER(CanalGrid), vp, vp, vp, vp]
         L.sh_resect_stems.argtypes = [vp, vp, ctypes.c_int, vp]
+    if not alt or hasattr(L, "sh_resect_plan"):      # (tools/time_plan.py and the benchmark's parent arm)
+        L.sh_resect_plan.argtypes = [vp, ctypes.POINTER(PlanRule), vp, vp, ctypes.c_int, vp, vp]
     _lib = L
     return L

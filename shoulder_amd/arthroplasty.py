@@ -188,6 +188,77 @@ class HumeralHeadOsteotomy:
         self._shift([0.0, -mm, 0.0])
 
 
+class HumeralImplantation:
+    """The implant below and on a `HumeralHeadOsteotomy`: the ranked (head, stem) pairs of its current cut.
+
+    The reference names this class and leaves it commented out (arthroplasty.py:178-182: it "continues from the humeral head
+    osteotomy and places the implant").  Here it drives the engine's chain for the osteotomy's current plane -- seated resection,
+    canal profile, stems, plan (sh_resect_planes_seat, sh_canal_profile, sh_resect_stems, sh_resect_plan with B = P = 1) -- in the
+    frame the osteotomy read the anatomic-neck plane in, with the native anatomic-neck plane as the plan's reference plane.
+    heads: (diameter, thickness) pairs, as `HumeralHeadOsteotomy.seat` takes them; stems: (length, r_prox, r_tip) rows; rule: a dict
+    with sh_plan_rule's field names (Engine.plan); seat_center: "centroid" or "sphere"; compat: (K_h, K_s) booleans or None."""
+
+    def __init__(self, osteotomy, heads, stems, rule=None, seat_center="centroid", compat=None) -> None:
+        self._ost = osteotomy
+        self._heads = [tuple(float(x) for x in h) for h in np.asarray(heads, dtype=np.float64).reshape(-1, 2)]
+        self._stems = [tuple(float(x) for x in s) for s in np.asarray(stems, dtype=np.float64).reshape(-1, 3)]
+        self._rule = dict(rule or {})
+        self._center = seat_center
+        self._compat = compat
+        self._last = None      # (the cut's plane, n, plans, refs) of the last chain
+
+    def _run(self, n):
+        """(plans (1, >= n), refs (1,)) of the current cut.  The chain -- profile, seated resection, stems, plan -- runs once per
+        plane: a call for the same plane with the same or a smaller n is answered from the last result, of which plan r is the same
+        record whatever n is; another plane, or a larger n, runs the chain again.  The result is a SNAPSHOT taken when the chain ran: it
+        is not refreshed when the engine's resident batch is replaced (another bone on the same engine) or the humerus is reloaded,
+        and the device buffers it was copied from may be gone by then; make a new HumeralImplantation after either."""
+        ost = self._ost
+        key = np.concatenate(ost._plane_ct()).tobytes()
+        if self._last is not None and self._last[0] == key and self._last[1] >= n:
+            return self._last[2][:, :n], self._last[3]
+        plans, refs = self._chain(n)
+        self._last = (key, n, plans, refs)
+        return plans, refs
+
+    def _chain(self, n):
+        ost = self._ost
+        bone = ost._humerus
+        bone._ensure_loaded()
+        eng = bone._engine
+        dz = 1.0      # the grid of HumeralHeadOsteotomy.canal_profile, long enough for the longest stem
+        L = min(1024, max(int(round(160.0 / dz)) + 1, int(np.ceil((max(s[0] for s in self._stems) + 5.0) / dz)) + 2))
+        ost.canal_profile(dz=dz, L=L)
+        p, nrm = ost._plane_ct()
+        heads = np.array([(0.5 * d, h) for d, h in self._heads])
+        eng.resect(planes=np.concatenate([p, nrm]).reshape(1, 1, 6), fit=True, heads=heads, seat_center=self._center)
+        eng.resect_stems(self._stems)
+        ref = np.concatenate(transform_plane_pn(ost._native_point, ost._native_normal, inv_transform(ost._to_anp))).reshape(1, 6)
+        return eng.plan(n=n, rule=self._rule, compat=self._compat, ref_planes=ref)
+
+    def plans(self, n=8) -> list:
+        """The n best (head, stem) pairs of the current cut, best first: dicts with the fields of sh_plan and the chosen `head_tuple`
+        (diameter, thickness) and `stem_tuple` (length, r_prox, r_tip).  Fewer than n when fewer are feasible.  `best()` and
+        `reference()` after it, on the same plane, cost no further engine call: they read the snapshot of that chain (`_run`)."""
+        got = self._run(n)[0][0]
+        out = []
+        for r in got[got["status"] == 0]:
+            d = {k: (r[k].copy() if r[k].ndim else r[k].item()) for k in r.dtype.names}
+            d["head_tuple"], d["stem_tuple"] = self._heads[d["head"]], self._stems[d["stem"]]
+            out.append(d)
+        return out
+
+    def best(self):
+        """the first of `plans()`, or None"""
+        got = self.plans(1)
+        return got[0] if got else None
+
+    def reference(self) -> dict:
+        """The height reference of the humerus (sh_plan_ref) as a dict: native head apex and tuberosity top, in CT and in the frame."""
+        r = self._run(1)[1][0]
+        return {k: (r[k].copy() if r[k].ndim else r[k].item()) for k in r.dtype.names if k != "pad"}
+
+
 def implant_from_fit(fit, side, catalogue=None) -> dict:
     """A head-fit record (dict or structured scalar with sh_head_fit's fields) -> the cap a planner picks: `radius` of curvature,
     `thickness` (= cap_height), `base_diameters` (2 x the cut's semi-axes, major first), `center` (CT), and the centre's offsets from

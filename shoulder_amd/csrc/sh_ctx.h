@@ -167,6 +167,12 @@ struct sh_ctx {
   // sh_canal_profile (k_stem.h): the grid and the batch of the last profile ("canal.*": sh_resect_stems reads them)
   unsigned long long canal_gen = ~0ull;
   sh_canal_grid canal_grid = {0.0, 0.0, 0, 0};
+  // sh_resect_plan (k_plan.h) joins the seats and the stems of ONE resection and ONE profile: every resect_run and every
+  // sh_canal_profile takes a sequence number; the seats remember their resection (with K_h), the stems the
+  // resection and the profile they were fitted against (with K_s).  Nothing else reads these.
+  unsigned long long resect_seq = 0, canal_seq = 0;
+  unsigned long long seat_resect_seq = ~0ull, stem_resect_seq = ~0ull, stem_canal_seq = ~0ull;
+  int seat_K = 0, stem_K = 0;
   hipStream_t copy_stream = nullptr;
   hipEvent_t stl_counted_ev = nullptr;      // sh_stage_stl: the device has counted the merged vertices / faces
   // side stream of the stage runner: the distal slice set and the rectangles of the trans-epicondylar stage hang on nothing but the

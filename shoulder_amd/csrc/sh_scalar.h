@@ -976,4 +976,68 @@ SH_HD bool stem_level_span(double z0, double dz, int L, double ze, double length
   return true;
 }
 
+// ---- implant plans: cuts, heads and stems joined and ranked (include/shoulder_hip.h sh_resect_plan; k_plan.h) ---------------
+// One part of a candidate's cost and whether the part passes its limits; the three compact arrays of k_plan_terms hold these.
+struct __attribute__((aligned(16))) PlanTerm { double cost; int32_t feasible, pad; };
+// signed distance, times |n|, of a vertex from the reference plane (o, n), the normal as given
+SH_HD double plan_side(const double* o, const double* n, double x, double y, double z) {
+  const double dx = x - o[0], dy = y - o[1], dz = z - o[2];
+  return (dx * n[0] + dy * n[1]) + dz * n[2];
+}
+// the bound of the tuberosity side: s_v <= -(margin |n|)
+SH_HD double plan_tuberosity_bound(double margin, const double* n) { return -(margin * norm3(n)); }
+// whether the vertex (z, vid), vid >= 0, replaces the best so far (bvid < 0: none yet): the larger frame height, of equals the smaller id
+SH_HD bool plan_ref_better(double z, int vid, double bz, int bvid) { return bvid < 0 || z > bz || (z == bz && vid < bvid); }
+// The cut part of a cost: eccentricity = |seat_center - entry|, entry the point where the frame's z axis pierces the cut's plane
+// (stem_entry, what k_stem_fit calls).  *ecc is 0 where the cut, its seat or its entry does not exist.
+SH_HD PlanTerm plan_cut_term(double w_eccentricity, double max_eccentricity, double w_cor, int humerus_status, int cut_status, int n_loops,
+                             int seat0_status, int sphere_status, const double* seat_center, const double* T, const double* o, const double* n,
+                             double* ecc) {
+  PlanTerm t = {0.0, 0, 0};
+  *ecc = 0.0;
+  double of[3], un[3], entry[3], ze = 0.0;
+  if (humerus_status != 0 || cut_status != 0 || n_loops < 1 || seat0_status != 0 || stem_entry(T, o, n, of, un, &ze, entry) != 0) return t;
+  const double d[3] = {seat_center[0] - entry[0], seat_center[1] - entry[1], seat_center[2] - entry[2]};
+  *ecc = norm3(d);
+  t.cost = w_eccentricity * *ecc;
+  t.feasible = (!(w_cor > 0.0) || sphere_status == 0) && *ecc <= max_eccentricity ? 1 : 0;
+  return t;
+}
+// The head part: vals = uncovered, overhang, cor, height, apex (3, CT), apex_z.  apex = seat_center + (h n) / |n|, h the head's
+// thickness; height = |apex_z - head_apex_z| against the native apex of the humerus' reference.
+SH_HD PlanTerm plan_head_term(double w_uncovered, double w_overhang, double w_cor, double w_height, double limit_overhang, double min_coverage,
+                              double coverage, double max_overhang, const double* cor_shift, const double* seat_center, const double* n, double h,
+                              const double* T, double head_apex_z, double* vals /* 8 */) {
+  const double len = norm3(n);
+  double q[3];
+  vals[0] = 1.0 - coverage; vals[1] = max_overhang; vals[2] = norm3(cor_shift);
+  for (int i = 0; i < 3; ++i) vals[4 + i] = seat_center[i] + (h * n[i]) / len;
+  canal_map_point(T, vals[4], vals[5], vals[6], q);
+  vals[7] = q[2];
+  vals[3] = fabs(vals[7] - head_apex_z);
+  PlanTerm t;
+  t.cost = ((w_uncovered * vals[0] + w_overhang * vals[1]) + w_cor * vals[2]) + w_height * vals[3];
+  t.feasible = (max_overhang <= limit_overhang && coverage >= min_coverage) ? 1 : 0;
+  t.pad = 0;
+  return t;
+}
+// The stem part: *fill = |fill_mean - fill_target|.
+SH_HD PlanTerm plan_stem_term(double w_fill, double fill_target, double limit_clearance, int status, int fits, double min_clearance, double fill_mean,
+                              double* fill) {
+  *fill = fabs(fill_mean - fill_target);
+  PlanTerm t;
+  t.cost = w_fill * *fill;
+  t.feasible = (status == 0 && fits == 1 && min_clearance >= limit_clearance) ? 1 : 0;
+  t.pad = 0;
+  return t;
+}
+// A candidate (p, k_h, k_s) from its three parts and its head's compatibility word: cost = (head + stem) + cut; feasible when the
+// parts are, the cost is not NaN and bit k_s of the word is set.
+SH_HD bool plan_candidate(const PlanTerm& cut, const PlanTerm& head, const PlanTerm& stem, unsigned long long compat_word, int ks, double* cost) {
+  *cost = (head.cost + stem.cost) + cut.cost;
+  return cut.feasible != 0 && head.feasible != 0 && stem.feasible != 0 && *cost == *cost && ((compat_word >> ks) & 1ull) != 0;
+}
+// the order of the ranking: ascending (cost, i), costs not NaN.  A total order: its minima do not depend on the reduction order.
+SH_HD bool plan_key_less(double ca, int ia, double cb, int ib) { return ca < cb || (ca == cb && ia < ib); }
+
 }  // namespace sh

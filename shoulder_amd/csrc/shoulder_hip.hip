@@ -14,6 +14,7 @@
 #include "k_headfit.h"
 #include "k_seat.h"
 #include "k_stem.h"
+#include "k_plan.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -987,6 +988,7 @@ static int resect_run(sh_ctx* c, const ResectRequest& q) {
   if (int rc = resect_ensure(c, q, &pc, &tmax)) return rc;
   const ResectView v = resect_view(c);
   c->resect_gen = ~0ull;
+  ++c->resect_seq;
   if (q.offs) {
     HIPCHK(c, hipMemcpyAsync(v.offs, q.offs, (size_t)P * 56, hipMemcpyHostToDevice, c->stream));
     LAUNCH(c, "k_resect_make_planes", k_resect_make_planes, dim3((unsigned)c->B), dim3(64), v.lm, (const double*)v.offs, P, v.planes, v.status);
@@ -1017,6 +1019,7 @@ static int resect_run(sh_ctx* c, const ResectRequest& q) {
   if (q.level == RS_SEAT) HIPCHK(c, hipMemcpyAsync(q.seat_out, v.seat_out, n * q.K * sizeof(sh_seat), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->resect_P = P; c->resect_gen = c->batch_gen;
+  if (q.level == RS_SEAT) { c->seat_resect_seq = c->resect_seq; c->seat_K = q.K; }
   return SH_OK;
 }
 
@@ -1091,6 +1094,7 @@ int sh_canal_profile(sh_ctx* c, const sh_canal_grid* g, const double* frames, do
   double* d_near = (double*)at("canal.near"); double* d_far = (double*)at("canal.far"); sh_canal_level* d_lv = (sh_canal_level*)at("canal.levels");
   double* d_fr = (double*)at("canal.frames"); int* d_st = (int*)at("canal.status"); double* d_dirs = (double*)at("canal.dirs");
   c->canal_gen = ~0ull;
+  ++c->canal_seq;
   const double two_pi = 2.0 * 3.14159265358979323846;
   std::vector<double> dirs(2 * (size_t)A);
   for (int a = 0; a < A; ++a) { const double t = (two_pi * (double)a) / (double)A; dirs[2 * a] = std::cos(t); dirs[2 * a + 1] = std::sin(t); }
@@ -1131,6 +1135,7 @@ int sh_resect_stems(sh_ctx* c, const sh_stem* stems, int K, sh_stem_fit* out) {
   const int B = c->B, P = c->resect_P;
   const size_t n = (size_t)B * P * K;
   int rc;
+  c->stem_resect_seq = ~0ull;      // (before "stem.out" can be resized or half rewritten: an early return leaves no stems for sh_resect_plan)
   ENS_SHARED("stem.catalogue", (size_t)K * sizeof(sh_stem), 8); ENS_SHARED("stem.out", n * sizeof(sh_stem_fit), 8);
   auto at = [c](const char* name) { return c->bufs.find(name)->second.p; };
   const ResectView v = resect_view(c);
@@ -1141,6 +1146,75 @@ int sh_resect_stems(sh_ctx* c, const sh_stem* stems, int K, sh_stem_fit* out) {
          (const double*)at("canal.frames"), (const int*)at("canal.status"), (const double*)at("canal.near"), (const sh_canal_level*)at("canal.levels"),
          (const double*)at("canal.dirs"), g.z0, g.dz, g.L, g.A, (const sh_stem*)d_cat, K, P, d_out);
   HIPCHK(c, hipMemcpyAsync(out, d_out, n * sizeof(sh_stem_fit), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->stem_resect_seq = c->resect_seq; c->stem_canal_seq = c->canal_seq; c->stem_K = K;
+  return SH_OK;
+}
+
+// ---- implant plans: the seats and the stems of the last resection joined and ranked (k_plan.h) -----------------------------------
+static bool plan_rule_ok(const sh_plan_rule* r) {
+  static_assert(sizeof(sh_plan_rule) == 12 * sizeof(double), "sh_plan_rule is twelve doubles");
+  for (int i = 0; i < 12; ++i)
+    if (std::isnan(((const double*)r)[i])) return false;
+  for (double w : {r->w_uncovered, r->w_overhang, r->w_cor, r->w_height, r->w_eccentricity, r->w_fill})
+    if (!std::isfinite(w) || w < 0.0) return false;
+  return r->margin >= 0.0;
+}
+
+int sh_resect_plan(sh_ctx* c, const sh_plan_rule* rule, const uint64_t* compat, const double* ref_planes, int N, sh_plan* out, sh_plan_ref* ref_out) {
+  if (!rule || !out || N < 1 || N > SH_PLAN_MAX) return fail(c, SH_ERR_ARG, "sh_resect_plan: bad argument (N in 1..64)");
+  if (!plan_rule_ok(rule)) return fail(c, SH_ERR_ARG, "sh_resect_plan: bad rule (no NaN, weights finite and >= 0, margin >= 0)");
+  if (!c) return SH_ERR_ARG;
+  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_plan: runs are in flight (sh_collect them first)");
+  if (c->B < 1 || c->resect_gen != c->batch_gen || c->resect_P < 1 || c->seat_resect_seq != c->resect_seq)
+    return fail(c, SH_ERR_STATE, "sh_resect_plan: no seated resection of the resident batch (sh_resect_planes_seat / sh_resect_offsets_seat)");
+  if (c->canal_gen != c->batch_gen || c->stem_resect_seq != c->resect_seq || c->stem_canal_seq != c->canal_seq)
+    return fail(c, SH_ERR_STATE, "sh_resect_plan: no stems fitted against the last resection and the current canal profile (sh_resect_stems)");
+  if (!ref_planes && !resect_has_records(c))
+    return fail(c, SH_ERR_STATE, "sh_resect_plan: ref_planes == NULL needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
+  const int B = c->B, P = c->resect_P, Kh = c->seat_K, Ks = c->stem_K;
+  if (ref_planes)
+    for (int b = 0; b < B; ++b) {
+      const double* pl = ref_planes + 6 * (size_t)b;
+      bool fin = true;
+      for (int k = 0; k < 6; ++k) fin = fin && std::isfinite(pl[k]);
+      if (!fin || !((pl[3] * pl[3] + pl[4] * pl[4]) + pl[5] * pl[5] > 0.0))
+        return fail(c, SH_ERR_ARG, "sh_resect_plan: reference plane " + std::to_string(b) + " has a zero normal or is not finite");
+    }
+  HIPCHK(c, hipSetDevice(c->device));
+  const long long tmax = std::max<long long>(1, (c->maxV + SH_PLAN_TILE - 1) / SH_PLAN_TILE);
+  const size_t cuts = (size_t)B * P;
+  int rc;
+  ENS_SHARED("plan.ref_planes", (size_t)B * 48, 8); ENS_SHARED("plan.compat", (size_t)SH_SEAT_MAX_HEADS * 8, 8);
+  ENS_SHARED("plan.ref_slab", (size_t)B * tmax * 2 * sizeof(PlanTop), 8); ENS_SHARED("plan.ref", (size_t)B * sizeof(sh_plan_ref), 8);
+  ENS_SHARED("plan.cut_terms", cuts * sizeof(PlanTerm), 8); ENS_SHARED("plan.head_terms", cuts * Kh * sizeof(PlanTerm), 8);
+  ENS_SHARED("plan.stem_terms", cuts * Ks * sizeof(PlanTerm), 8); ENS_SHARED("plan.cut_vals", cuts * 8, 8);
+  ENS_SHARED("plan.head_vals", cuts * Kh * 64, 8); ENS_SHARED("plan.stem_vals", cuts * Ks * 8, 8);
+  ENS_SHARED("plan.out", (size_t)B * N * sizeof(sh_plan), 8);
+  auto at = [c](const char* name) { return c->bufs.find(name)->second.p; };
+  const ResectView v = resect_view(c);
+  double* d_rp = ref_planes ? (double*)at("plan.ref_planes") : nullptr;
+  const sh_landmarks* d_lm = ref_planes ? nullptr : v.lm;
+  unsigned long long* d_compat = (unsigned long long*)at("plan.compat");
+  PlanTop* d_slab = (PlanTop*)at("plan.ref_slab"); sh_plan_ref* d_ref = (sh_plan_ref*)at("plan.ref"); sh_plan* d_out = (sh_plan*)at("plan.out");
+  PlanTerm* d_ct = (PlanTerm*)at("plan.cut_terms"); PlanTerm* d_ht = (PlanTerm*)at("plan.head_terms"); PlanTerm* d_st = (PlanTerm*)at("plan.stem_terms");
+  double* d_cv = (double*)at("plan.cut_vals"); double* d_hv = (double*)at("plan.head_vals"); double* d_sv = (double*)at("plan.stem_vals");
+  const double* d_frames = (const double*)at("canal.frames"); const int* d_hst = (const int*)at("canal.status");
+  uint64_t words[SH_SEAT_MAX_HEADS];
+  for (int k = 0; k < SH_SEAT_MAX_HEADS; ++k) words[k] = compat && k < Kh ? compat[k] : ~0ull;      // (pageable: the copy is staged before the call returns)
+  HIPCHK(c, hipMemcpyAsync(d_compat, words, sizeof words, hipMemcpyHostToDevice, c->stream));
+  if (ref_planes) HIPCHK(c, hipMemcpyAsync(d_rp, ref_planes, (size_t)B * 48, hipMemcpyHostToDevice, c->stream));
+  LAUNCH(c, "k_plan_ref", k_plan_ref, dim3((unsigned)tmax, (unsigned)B), dim3(SH_PLAN_TILE), v.verts, v.voff, d_frames, d_hst, d_lm, (const double*)d_rp,
+         rule->margin, (int)tmax, d_slab);
+  LAUNCH(c, "k_plan_ref_join", k_plan_ref_join, dim3((unsigned)B), dim3(64), v.verts, v.voff, d_hst, d_lm, (const double*)d_rp, (int)tmax,
+         (const PlanTop*)d_slab, d_ref);
+  LAUNCH(c, "k_plan_terms", k_plan_terms, dim3((unsigned)cuts), dim3(SH_PLAN_TERM_THREADS), (const double*)v.planes, (const int*)v.status,
+         (const sh_resection*)v.out, (const sh_head_fit*)v.fit_out, (const sh_seat*)v.seat_out, (const sh_implant_head*)v.seat_heads, Kh,
+         (const sh_stem_fit*)at("stem.out"), Ks, d_frames, (const sh_plan_ref*)d_ref, *rule, P, d_ct, d_ht, d_st, d_cv, d_hv, d_sv);
+  LAUNCH(c, "k_plan_select", k_plan_select, dim3((unsigned)B), dim3(SH_PLAN_THREADS), (const PlanTerm*)d_ct, (const PlanTerm*)d_ht, (const PlanTerm*)d_st,
+         (const double*)d_cv, (const double*)d_hv, (const double*)d_sv, (const unsigned long long*)d_compat, P, Kh, Ks, N, d_ref, d_out);
+  HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)B * N * sizeof(sh_plan), hipMemcpyDeviceToHost, c->stream));
+  if (ref_out) HIPCHK(c, hipMemcpyAsync(ref_out, d_ref, (size_t)B * sizeof(sh_plan_ref), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -541,6 +541,38 @@ class Engine:
         self._chk(self.L.sh_resect_stems(self.h, _ptr(st), K, _ptr(out)))
         return out
 
+    # ---- implant plans (include/shoulder_hip.h sh_resect_plan) --------------------------------------------------------------
+    def plan(self, n=8, rule=None, compat=None, ref_planes=None):
+        """The n best (cut, head, stem) triples of every humerus from the last seated resect() and the last resect_stems(), ranked on
+        the device under one rule -> (plans, refs): structured arrays (B, n) of _lib.PLAN_DTYPE and (B,) of _lib.PLAN_REF_DTYPE
+        (sh_resect_plan).  rule: a dict with sh_plan_rule's field names; a missing limit is off (+-inf), missing weights, `fill_target`
+        and `margin` are 0.  compat: (K_h, K_s) booleans, which stems each head goes with, or None for all.  ref_planes: (B, 6) or
+        (B, 2, 3) float64 (point, normal) in CT, the plane that parts head from tuberosity, or None for every record's anatomic-neck
+        plane (needs a run with STAGE_ANP and STAGE_CSYS)."""
+        r = _lib.PlanRule(max_overhang=np.inf, min_coverage=-np.inf, min_clearance=-np.inf, max_eccentricity=np.inf)
+        for k, v in dict(rule or {}).items():
+            if k not in _lib.PLAN_RULE_DTYPE.names:
+                raise ValueError("unknown rule field %r" % (k,))
+            setattr(r, k, float(v))
+        words = None
+        if compat is not None:
+            cm = np.asarray(compat, dtype=bool)
+            if cm.ndim != 2 or cm.shape[0] > _lib.SEAT_MAX_HEADS or cm.shape[1] > _lib.STEM_MAX:
+                raise ValueError("compat must have shape (K_h, K_s)")
+            words = np.zeros(_lib.SEAT_MAX_HEADS, dtype=np.uint64)
+            words[: cm.shape[0]] = (cm.astype(np.uint64) << np.arange(cm.shape[1], dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+        rp = None
+        if ref_planes is not None:
+            rp = np.ascontiguousarray(ref_planes, dtype=np.float64)
+            if rp.size != 6 * self.B:
+                raise ValueError("ref_planes must have shape (B, 6)")
+        n = int(n)
+        plans = np.zeros((self.B, max(n, 0)), dtype=_lib.PLAN_DTYPE)
+        refs = np.zeros(self.B, dtype=_lib.PLAN_REF_DTYPE)
+        self._chk(self.L.sh_resect_plan(self.h, ctypes.byref(r), _ptr(words) if words is not None else None, _ptr(rp) if rp is not None else None,
+                                        n, _ptr(plans), _ptr(refs)))
+        return plans, refs
+
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):
         n, e = ctypes.c_size_t(), ctypes.c_int()
