@@ -4,12 +4,17 @@
 //   shoulder_hip.hip  context, C-ABI plumbing, meshes, the stage runner, submit / collect   (geometry kernels)
 //                     -- its per-batch buffers are declared once (WIN_*_BUFS: name, element type, elements per humerus); allocation
 //                     and the typed view of a window (WinView, resolved once per run_window) both come from that list
+//                     -- the entry points of the arthroplasty chain are sh_arthro_host.h, included by this unit once (a header, not a
+//                     unit: the resection kernels keep their registers only in this unit); its buffers are declared once
+//                     as well (sh_arthro.h ARTHRO_BUFS: allocation from the pass plan's sizes, and the typed ArthroView)
 //   hull.hip          hull prefilter, host hull phase and its worker pool, device hull      (k_hullpre.h, k_hull.h)
 //   unet.hip          the UNet runners, UNet turns, sh_unet_infer                          (k_unet*.h; unet16_pp.hip: k_unet16_pp.h)
 //   comm.hip          the RCCL collectives
 // Kernel-free and HIP-free beside it (a plain g++ compiles them for the host tests): sh_demand.h (a run's capacity demands and the
 // verdict on them), sh_ingest.h (what mesh ingest checks and plans on the host before a batch becomes resident), sh_unet_plan.h (the
-// steps of a UNet pass: kernel, grid, tensors and work tickets of every launch; the ticket and weight-packing tables).
+// steps of a UNet pass: kernel, grid, tensors and work tickets of every launch; the ticket and weight-packing tables), sh_arthro.h
+// (the arthroplasty chain: its argument checks and which refusal comes first, the pass plan and the bytes of every resect.* / canal.* /
+// stem.* / plan.* buffer, and ArthroState, the one record of what is valid against what).
 #pragma once
 #include "../../include/shoulder_hip.h"
 
@@ -34,6 +39,7 @@
 #include <tuple>
 #include <vector>
 
+#include "sh_arthro.h"
 #include "sh_demand.h"
 #include "sh_hullcap.h"
 #include "sh_ingest.h"
@@ -159,20 +165,10 @@ struct sh_ctx {
   hipStream_t out_stream = nullptr;      // sh_collect copies the records / status words of a finished run to the host on this stream
   bool overlap = false;
   unsigned long long batch_gen = 0;
-  // sh_resect_* (k_resect.h): the stages and the batch of the last submitted run (sh_resect_offsets reads its records), and the
-  // planes per humerus and the batch of the last resection ("resect.planes": sh_resect_ring joins one of its cuts again)
-  uint32_t rec_mask = 0;
-  unsigned long long rec_gen = ~0ull, resect_gen = ~0ull;
-  int resect_P = 0;
-  // sh_canal_profile (k_stem.h): the grid and the batch of the last profile ("canal.*": sh_resect_stems reads them)
-  unsigned long long canal_gen = ~0ull;
-  sh_canal_grid canal_grid = {0.0, 0.0, 0, 0};
-  // sh_resect_plan (k_plan.h) joins the seats and the stems of ONE resection and ONE profile: every resect_run and every
-  // sh_canal_profile takes a sequence number; the seats remember their resection (with K_h), the stems the
-  // resection and the profile they were fitted against (with K_s).  Nothing else reads these.
-  unsigned long long resect_seq = 0, canal_seq = 0;
-  unsigned long long seat_resect_seq = ~0ull, stem_resect_seq = ~0ull, stem_canal_seq = ~0ull;
-  int seat_K = 0, stem_K = 0;
+  // the arthroplasty chain (sh_arthro_host.h: sh_resect_*, sh_canal_profile, sh_resect_stems, sh_resect_plan): what is valid against
+  // what -- the records of the last submitted run, the last resection with its seats, the last profile, the stems -- is this one
+  // member's (sh_arthro.h ArthroState: named events and queries; batch_gen above stays the context's and is handed to the queries)
+  sh::ArthroState arthro;
   hipStream_t copy_stream = nullptr;
   hipEvent_t stl_counted_ev = nullptr;      // sh_stage_stl: the device has counted the merged vertices / faces
   // side stream of the stage runner: the distal slice set and the rectangles of the trans-epicondylar stage hang on nothing but the

@@ -839,385 +839,8 @@ int sh_slice_mesh_planes(sh_ctx* c, const double* verts, int nv, const int32_t* 
   return SH_OK;
 }
 
-// ---- batched head resection (k_resect.h, k_headfit.h, k_seat.h): the sh_resect_* entry points and the one pipeline behind them ----
-// what a call computes per cut: the record; the head fit beside it (the moment pass and the join that adds its slab and the ring's
-// second moments); the seats of a catalogue on top (that join also stores the ring's in-plane coordinates of the pass)
-enum ResectLevel { RS_RECORDS, RS_FIT, RS_SEAT };
-
-struct ResectRequest {
-  const char* fn;                    // the caller's name, for error texts
-  ResectLevel level;
-  const double* planes;              // B x P x (point, normal), or
-  const sh_cut_offset* offs;         // P offsets, the same for every humerus (the one that is set is the source)
-  int P;
-  sh_resection* out;
-  sh_head_fit* fit_out = nullptr;    // RS_FIT and up
-  const sh_implant_head* heads = nullptr;      // RS_SEAT: the catalogue, its size, the centre mode and the records
-  int K = 0, mode = 0;
-  sh_seat* seat_out = nullptr;
-};
-
-// the named buffers of a call as typed pointers, resolved once (null: not there)
-struct ResectView {
-  const float* verts; const int* faces; const long long* voff; const long long* foff;
-  const sh_landmarks* lm;            // null: no run of the resident batch with the anatomic neck and the csys
-  double* planes; int* status; ResectPart* slab; int* segcnt; int* segs; sh_resection* out; sh_resection* one; double* ring; double* offs;
-  double* fit_slab; double* fit_moments; double* fit_ring; sh_head_fit* fit_out;
-  double* seat_ring; sh_implant_head* seat_heads; sh_seat* seat_out;
-};
-
-struct ResectPass { int P, p0, pc, b0, nb, tmax; };      // planes [p0, p0 + pc) of humeri [b0, b0 + nb), tmax tiles per humerus in the slabs
-
-static bool resect_has_records(sh_ctx* c) {
-  const uint32_t need = SH_STAGE_ANP | SH_STAGE_CSYS;
-  return c->rec_gen == c->batch_gen && (c->rec_mask & need) == need && c->bufs.find("landmarks") != c->bufs.end();
-}
-
-static ResectView resect_view(sh_ctx* c) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  ResectView v;
-  v.verts = (const float*)at("verts"); v.faces = (const int*)at("faces"); v.voff = (const long long*)at("voff"); v.foff = (const long long*)at("foff");
-  v.lm = resect_has_records(c) ? (const sh_landmarks*)at("landmarks") : nullptr;
-  v.planes = (double*)at("resect.planes"); v.status = (int*)at("resect.status"); v.slab = (ResectPart*)at("resect.slab");
-  v.segcnt = (int*)at("resect.segcnt"); v.segs = (int*)at("resect.segs"); v.out = (sh_resection*)at("resect.out");
-  v.one = (sh_resection*)at("resect.one"); v.ring = (double*)at("resect.ring"); v.offs = (double*)at("resect.offs");
-  v.fit_slab = (double*)at("resect.fit_slab"); v.fit_moments = (double*)at("resect.fit_moments"); v.fit_ring = (double*)at("resect.fit_ring");
-  v.fit_out = (sh_head_fit*)at("resect.fit_out");
-  v.seat_ring = (double*)at("resect.seat_ring"); v.seat_heads = (sh_implant_head*)at("resect.seat_heads"); v.seat_out = (sh_seat*)at("resect.seat_out");
-  return v;
-}
-
-// The buffers of a request and its planes per pass.  Records: the slot ranges (4 KB per cut) and the slab (32 B per cut and tile)
-// stay below 32 MB / 128 MB, so a pass takes at most 8 192 cuts; a sweep larger than that takes several passes over the mesh.  The
-// pass a plane falls into does not change its record (the slab of a cut is its own).  Fit: the moment slab (128 B per cut and tile)
-// has 128 MB of its own and a pass takes at most 4 096 cuts, so the planes per pass of a fitted sweep are at most the un-fitted
-// ones -- which keep their split.  Seat: the ring coordinates of one pass (16 KB per cut; a fitted pass takes 4 096 / B planes but
-// at least one, so max(B, 4 096) cuts: 64 MB up to B = 4 096 and the fitted split is kept), the catalogue and the B x P x K
-// records, which have no limit of their own (SH_ERR_NOMEM when they do not fit).
-static int resect_ensure(sh_ctx* c, const ResectRequest& q, int* pc_out, int* tmax_out) {
-  const int B = c->B, P = q.P;
-  const long long tmax = std::max<long long>(1, (c->maxF + SH_RS_TILE - 1) / SH_RS_TILE);
-  long long pc = std::min<long long>(8192 / B, (128LL << 20) / (32LL * B * tmax));
-  pc = std::max<long long>(1, std::min<long long>(pc, P));
-  int rc;
-  ENS_SHARED("resect.planes", (size_t)B * P * 48, 8); ENS_SHARED("resect.status", (size_t)B * P * 4, 4);
-  ENS_SHARED("resect.slab", (size_t)B * pc * tmax * sizeof(ResectPart), 8); ENS_SHARED("resect.segcnt", (size_t)B * pc * 4, 4);
-  ENS_SHARED("resect.segs", (size_t)B * pc * SH_MAXSEG * 4, 4); ENS_SHARED("resect.out", (size_t)B * P * sizeof(sh_resection), 8);
-  ENS_SHARED("resect.one", sizeof(sh_resection), 8); ENS_SHARED("resect.ring", (size_t)(SH_MAXSEG + 1) * 24, 8);
-  if (q.level >= RS_FIT) {
-    const long long pcf = std::min<long long>(4096 / B, (128LL << 20) / (8LL * SH_HF_WORDS * B * tmax));
-    pc = std::max<long long>(1, std::min<long long>(pcf, pc));
-    ENS_SHARED("resect.fit_slab", (size_t)B * pc * tmax * SH_HF_WORDS * 8, 8); ENS_SHARED("resect.fit_moments", (size_t)B * P * 16 * 8, 8);
-    ENS_SHARED("resect.fit_ring", (size_t)B * P * 8 * 8, 8); ENS_SHARED("resect.fit_out", (size_t)B * P * sizeof(sh_head_fit), 8);
-  }
-  if (q.level == RS_SEAT) {
-    ENS_SHARED("resect.seat_ring", (size_t)B * pc * 2 * SH_MAXSEG * 8, 8); ENS_SHARED("resect.seat_heads", (size_t)q.K * sizeof(sh_implant_head), 8);
-    ENS_SHARED("resect.seat_out", (size_t)B * P * q.K * sizeof(sh_seat), 8);
-  }
-  if (q.offs) ENS_SHARED("resect.offs", (size_t)P * 56, 8);
-  *pc_out = (int)pc; *tmax_out = (int)tmax;
-  return SH_OK;
-}
-
-static bool seat_args_ok(const sh_implant_head* heads, int K, int mode, sh_seat* out) {
-  if (!heads || !out || K < 1 || K > SH_SEAT_MAX_HEADS || (mode != SH_SEAT_CUT_CENTROID && mode != SH_SEAT_SPHERE_AXIS)) return false;
-  for (int k = 0; k < K; ++k) {
-    const double R = heads[k].radius, h = heads[k].thickness;
-    if (!std::isfinite(R) || !std::isfinite(h) || !(h > 0.0) || !(h < 2.0 * R)) return false;
-  }
-  return true;
-}
-
-// the join of a pass at a level; one / ring: the one-cut outputs of the records level (sh_resect_ring)
-static int launch_join(sh_ctx* c, const ResectView& v, ResectLevel level, const ResectPass& s, sh_resection* one = nullptr, double* ring = nullptr) {
-  const dim3 grid((unsigned)(s.nb * s.pc)), block(SH_RS_JOIN_THREADS);
-#define RJ_ARGS v.verts, v.faces, v.voff, v.foff, (const double*)v.planes, s.P, s.p0, s.pc, s.b0, s.tmax, (const int*)v.status, (const ResectPart*)v.slab, \
-                (const int*)v.segcnt, (const int*)v.segs, v.out
-  if (level == RS_SEAT) LAUNCH(c, "k_resect_join_seat", k_resect_join_seat, grid, block, RJ_ARGS, (const double*)v.fit_slab, v.fit_moments, v.fit_ring, v.seat_ring);
-  else if (level == RS_FIT) LAUNCH(c, "k_resect_join_fit", k_resect_join_fit, grid, block, RJ_ARGS, (const double*)v.fit_slab, v.fit_moments, v.fit_ring);
-  else LAUNCH(c, "k_resect_join", k_resect_join, grid, block, RJ_ARGS, one, ring);
-#undef RJ_ARGS
-  return SH_OK;
-}
-
-// the fits of planes [p0, p0 + pn) of every humerus from their moments, ring sums and records
-static int launch_solve(sh_ctx* c, const ResectView& v, int P, int p0, int pn) {
-  const int n = c->B * pn;
-  LAUNCH(c, "k_headfit_solve", k_headfit_solve, dim3((unsigned)((n + 63) / 64)), dim3(64), (const sh_resection*)v.out, (const int*)v.status,
-         (const double*)v.fit_moments, (const double*)v.fit_ring, v.lm, P, p0, pn, n, v.fit_out);
-  return SH_OK;
-}
-
-// face pass(es) and join of one pass
-static int resect_pass(sh_ctx* c, const ResectView& v, ResectLevel level, const ResectPass& s, sh_resection* one = nullptr, double* ring = nullptr) {
-  HIPCHK(c, hipMemsetAsync(v.segcnt, 0, (size_t)s.nb * s.pc * 4, c->stream));
-  const dim3 grid((unsigned)s.tmax, (unsigned)s.nb), block(SH_RS_TILE);
-  LAUNCH(c, "k_resect_faces", k_resect_faces, grid, block, v.verts, v.faces, v.voff, v.foff, (const double*)v.planes, s.P, s.p0, s.pc, s.b0, s.tmax, v.slab,
-         v.segcnt, v.segs);
-  if (level >= RS_FIT)
-    LAUNCH(c, "k_headfit_faces", k_headfit_faces, grid, block, v.verts, v.faces, v.voff, v.foff, (const double*)v.planes, s.P, s.p0, s.pc, s.b0, s.tmax,
-           v.fit_slab);
-  return launch_join(c, v, level, s, one, ring);
-}
-
-static int resect_run(sh_ctx* c, const ResectRequest& q) {
-  const std::string f(q.fn);
-  const int P = q.P;
-  if (!c || (!q.offs && !q.planes) || !q.out || (q.level >= RS_FIT && !q.fit_out) || P < 1 || P > 4096)
-    return fail(c, SH_ERR_ARG, f + ": bad argument (P in 1..4096)");
-  if (q.level == RS_SEAT && !seat_args_ok(q.heads, q.K, q.mode, q.seat_out))
-    return fail(c, SH_ERR_ARG, f + ": bad catalogue (K in 1..64, 0 < thickness < 2 radius) or centre mode");
-  if (c->B < 1) return fail(c, SH_ERR_STATE, f + ": no meshes uploaded");
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, f + ": runs are in flight (sh_collect them first)");
-  const size_t n = (size_t)c->B * P;
-  if (q.offs) {
-    if (!resect_has_records(c)) return fail(c, SH_ERR_STATE, f + ": needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
-    static_assert(sizeof(sh_cut_offset) == 7 * sizeof(double), "sh_cut_offset is seven doubles");
-    for (int i = 0; i < 7 * P; ++i)
-      if (!std::isfinite(((const double*)q.offs)[i])) return fail(c, SH_ERR_ARG, f + ": non-finite offset");
-  } else {
-    for (size_t i = 0; i < n; ++i) {
-      const double* pl = q.planes + 6 * i;
-      bool fin = true;
-      for (int k = 0; k < 6; ++k) fin = fin && std::isfinite(pl[k]);
-      if (!fin || !((pl[3] * pl[3] + pl[4] * pl[4]) + pl[5] * pl[5] > 0.0)) return fail(c, SH_ERR_ARG, f + ": zero normal or non-finite plane");
-    }
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  int pc, tmax;
-  if (int rc = resect_ensure(c, q, &pc, &tmax)) return rc;
-  const ResectView v = resect_view(c);
-  c->resect_gen = ~0ull;
-  ++c->resect_seq;
-  if (q.offs) {
-    HIPCHK(c, hipMemcpyAsync(v.offs, q.offs, (size_t)P * 56, hipMemcpyHostToDevice, c->stream));
-    LAUNCH(c, "k_resect_make_planes", k_resect_make_planes, dim3((unsigned)c->B), dim3(64), v.lm, (const double*)v.offs, P, v.planes, v.status);
-  } else {
-    HIPCHK(c, hipMemcpyAsync(v.planes, q.planes, n * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(v.status, 0, n * 4, c->stream));
-  }
-  if (q.level >= RS_FIT) {      // (a cut whose humerus' record failed writes neither: zeros)
-    HIPCHK(c, hipMemsetAsync(v.fit_moments, 0, n * 16 * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(v.fit_ring, 0, n * 8 * 8, c->stream));
-  }
-  if (q.level == RS_SEAT) HIPCHK(c, hipMemcpyAsync(v.seat_heads, q.heads, (size_t)q.K * sizeof(sh_implant_head), hipMemcpyHostToDevice, c->stream));
-  for (int p0 = 0; p0 < P; p0 += pc) {
-    const int pn = std::min(pc, P - p0);
-    if (int rc = resect_pass(c, v, q.level, ResectPass{P, p0, pn, 0, c->B, tmax})) return rc;
-    if (q.level == RS_SEAT) {      // the ring coordinates are the pass': its fits and its seats before the next pass overwrites them
-      if (int rc = launch_solve(c, v, P, p0, pn)) return rc;
-      LAUNCH(c, "k_seat", k_seat, dim3((unsigned)(c->B * pn)), dim3(SH_SEAT_THREADS), (const sh_resection*)v.out, (const sh_head_fit*)v.fit_out,
-             (const int*)v.status, (const double*)v.fit_moments, (const double*)v.seat_ring, v.lm, (const sh_implant_head*)v.seat_heads, q.K, q.mode, P, p0, pn,
-             v.seat_out);
-    }
-  }
-  HIPCHK(c, hipMemcpyAsync(q.out, v.out, n * sizeof(sh_resection), hipMemcpyDeviceToHost, c->stream));
-  if (q.level >= RS_FIT) {
-    if (int rc = q.level == RS_FIT ? launch_solve(c, v, P, 0, P) : SH_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(q.fit_out, v.fit_out, n * sizeof(sh_head_fit), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (q.level == RS_SEAT) HIPCHK(c, hipMemcpyAsync(q.seat_out, v.seat_out, n * q.K * sizeof(sh_seat), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->resect_P = P; c->resect_gen = c->batch_gen;
-  if (q.level == RS_SEAT) { c->seat_resect_seq = c->resect_seq; c->seat_K = q.K; }
-  return SH_OK;
-}
-
-int sh_resect_planes(sh_ctx* c, const double* planes, int P, sh_resection* out) { return resect_run(c, ResectRequest{"sh_resect_planes", RS_RECORDS, planes, nullptr, P, out}); }
-int sh_resect_offsets(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out) { return resect_run(c, ResectRequest{"sh_resect_offsets", RS_RECORDS, nullptr, offs, P, out}); }
-int sh_resect_planes_fit(sh_ctx* c, const double* planes, int P, sh_resection* out, sh_head_fit* fit_out) {
-  return resect_run(c, ResectRequest{"sh_resect_planes_fit", RS_FIT, planes, nullptr, P, out, fit_out});
-}
-int sh_resect_offsets_fit(sh_ctx* c, const sh_cut_offset* offs, int P, sh_resection* out, sh_head_fit* fit_out) {
-  return resect_run(c, ResectRequest{"sh_resect_offsets_fit", RS_FIT, nullptr, offs, P, out, fit_out});
-}
-int sh_resect_planes_seat(sh_ctx* c, const double* planes, int P, const sh_implant_head* heads, int K, int center_mode, sh_resection* out,
-                          sh_head_fit* fit_out, sh_seat* seat_out) {
-  return resect_run(c, ResectRequest{"sh_resect_planes_seat", RS_SEAT, planes, nullptr, P, out, fit_out, heads, K, center_mode, seat_out});
-}
-int sh_resect_offsets_seat(sh_ctx* c, const sh_cut_offset* offs, int P, const sh_implant_head* heads, int K, int center_mode, sh_resection* out,
-                           sh_head_fit* fit_out, sh_seat* seat_out) {
-  return resect_run(c, ResectRequest{"sh_resect_offsets_seat", RS_SEAT, nullptr, offs, P, out, fit_out, heads, K, center_mode, seat_out});
-}
-
-int sh_resect_ring(sh_ctx* c, int b, int p, double* out, int cap, int* n_out) {
-  if (!c || !n_out || cap < 0 || (cap > 0 && !out)) return fail(c, SH_ERR_ARG, "sh_resect_ring: bad argument");
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_ring: runs are in flight (sh_collect them first)");
-  if (c->resect_gen != c->batch_gen || c->resect_P < 1) return fail(c, SH_ERR_STATE, "sh_resect_ring: no resection of the resident batch");
-  if (b < 0 || b >= c->B || p < 0 || p >= c->resect_P) return fail(c, SH_ERR_ARG, "sh_resect_ring: index out of range");
-  HIPCHK(c, hipSetDevice(c->device));
-  const long long nf = c->h_foff[b + 1] - c->h_foff[b];
-  const int tiles = (int)std::max<long long>(1, (nf + SH_RS_TILE - 1) / SH_RS_TILE);
-  const ResectView v = resect_view(c);
-  if (int rc = resect_pass(c, v, RS_RECORDS, ResectPass{c->resect_P, p, 1, b, 1, tiles}, v.one, v.ring)) return rc;
-  sh_resection r;
-  HIPCHK(c, hipMemcpyAsync(&r, v.one, sizeof r, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (r.status != 0 || r.n_loops < 1) { *n_out = 0; return SH_OK; }
-  *n_out = r.n_ring + 1;
-  if (!out || cap < r.n_ring + 1) return SH_OK;
-  HIPCHK(c, hipMemcpy(out, v.ring, (size_t)(r.n_ring + 1) * 24, hipMemcpyDeviceToHost));
-  return SH_OK;
-}
-
-// ---- canal profiles and stems below the cuts of the last resection (k_stem.h) ------------------------------------------------------
-static bool canal_frame_ok(const double* T) {
-  for (int i = 0; i < 16; ++i)
-    if (!std::isfinite(T[i])) return false;
-  if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return false;
-  for (int i = 0; i < 3; ++i)
-    for (int j = i; j < 3; ++j) {
-      const double d = (T[4 * i] * T[4 * j] + T[4 * i + 1] * T[4 * j + 1]) + T[4 * i + 2] * T[4 * j + 2];
-      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-9)) return false;
-    }
-  return det3_of4(T) > 0.0;
-}
-
-int sh_canal_profile(sh_ctx* c, const sh_canal_grid* g, const double* frames, double* near_out, double* far_out, sh_canal_level* levels_out) {
-  if (!c || !g || !std::isfinite(g->z0) || !std::isfinite(g->dz) || !(g->dz > 0.0) || g->L < 1 || g->L > 1024 || g->A < 3 || g->A > 256)
-    return fail(c, SH_ERR_ARG, "sh_canal_profile: bad grid (finite z0, dz > 0, L in 1..1024, A in 3..256)");
-  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_canal_profile: no meshes uploaded");
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_canal_profile: runs are in flight (sh_collect them first)");
-  const int B = c->B, L = g->L, A = g->A;
-  if (frames) {
-    for (int b = 0; b < B; ++b)
-      if (!canal_frame_ok(frames + 16 * (size_t)b)) return fail(c, SH_ERR_ARG, "sh_canal_profile: frame " + std::to_string(b) + " is not a rigid CT -> frame matrix");
-  } else if (!resect_has_records(c)) {
-    return fail(c, SH_ERR_STATE, "sh_canal_profile: frames == NULL needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t n = (size_t)B * L * A;
-  int rc;
-  ENS_SHARED("canal.near", n * 8, 8); ENS_SHARED("canal.far", n * 8, 8); ENS_SHARED("canal.levels", (size_t)B * L * sizeof(sh_canal_level), 8);
-  ENS_SHARED("canal.frames", (size_t)B * 128, 8); ENS_SHARED("canal.status", (size_t)B * 4, 4); ENS_SHARED("canal.dirs", (size_t)A * 16, 8);
-  auto at = [c](const char* name) { return c->bufs.find(name)->second.p; };
-  double* d_near = (double*)at("canal.near"); double* d_far = (double*)at("canal.far"); sh_canal_level* d_lv = (sh_canal_level*)at("canal.levels");
-  double* d_fr = (double*)at("canal.frames"); int* d_st = (int*)at("canal.status"); double* d_dirs = (double*)at("canal.dirs");
-  c->canal_gen = ~0ull;
-  ++c->canal_seq;
-  const double two_pi = 2.0 * 3.14159265358979323846;
-  std::vector<double> dirs(2 * (size_t)A);
-  for (int a = 0; a < A; ++a) { const double t = (two_pi * (double)a) / (double)A; dirs[2 * a] = std::cos(t); dirs[2 * a + 1] = std::sin(t); }
-  HIPCHK(c, hipMemcpyAsync(d_dirs, dirs.data(), dirs.size() * 8, hipMemcpyHostToDevice, c->stream));
-  if (frames) {
-    HIPCHK(c, hipMemcpyAsync(d_fr, frames, (size_t)B * 128, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_st, 0, (size_t)B * 4, c->stream));
-  } else {
-    LAUNCH(c, "k_canal_frames", k_canal_frames, dim3((unsigned)((B + 63) / 64)), dim3(64), (const sh_landmarks*)at("landmarks"), B, d_fr, d_st);
-  }
-  LAUNCH(c, "k_canal_clear", k_canal_clear, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), (unsigned long long*)d_near,
-         (unsigned long long*)d_far, (long long)n);
-  const long long tmax = std::max<long long>(1, (c->maxF + SH_CANAL_TILE - 1) / SH_CANAL_TILE);
-  LAUNCH(c, "k_canal_rays", k_canal_rays, dim3((unsigned)tmax, (unsigned)B), dim3(SH_CANAL_TILE), (const float*)at("verts"), (const int*)at("faces"),
-         (const long long*)at("voff"), (const long long*)at("foff"), (const double*)d_fr, (const int*)d_st, (const double*)d_dirs, g->z0, g->dz, L, A,
-         (unsigned long long*)d_near, (unsigned long long*)d_far);
-  LAUNCH(c, "k_canal_levels", k_canal_levels, dim3((unsigned)(B * L)), dim3(64), (const double*)d_near, (const double*)d_far, (const int*)d_st,
-         (const double*)d_dirs, 0.5 * std::sin(two_pi / (double)A), L, A, d_lv);
-  if (near_out) HIPCHK(c, hipMemcpyAsync(near_out, d_near, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (far_out) HIPCHK(c, hipMemcpyAsync(far_out, d_far, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (levels_out) HIPCHK(c, hipMemcpyAsync(levels_out, d_lv, (size_t)B * L * sizeof(sh_canal_level), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->canal_grid = *g; c->canal_gen = c->batch_gen;
-  return SH_OK;
-}
-
-int sh_resect_stems(sh_ctx* c, const sh_stem* stems, int K, sh_stem_fit* out) {
-  if (!c || !stems || !out || K < 1 || K > SH_STEM_MAX) return fail(c, SH_ERR_ARG, "sh_resect_stems: bad argument (K in 1..64)");
-  static_assert(sizeof(sh_stem) == 3 * sizeof(double), "sh_stem is three doubles");
-  for (int i = 0; i < 3 * K; ++i) {
-    const double x = ((const double*)stems)[i];
-    if (!std::isfinite(x) || !(x > 0.0)) return fail(c, SH_ERR_ARG, "sh_resect_stems: length, r_prox and r_tip of a stem must be finite and > 0");
-  }
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_stems: runs are in flight (sh_collect them first)");
-  if (c->B < 1 || c->resect_gen != c->batch_gen || c->resect_P < 1) return fail(c, SH_ERR_STATE, "sh_resect_stems: no resection of the resident batch");
-  if (c->canal_gen != c->batch_gen) return fail(c, SH_ERR_STATE, "sh_resect_stems: no canal profile of the resident batch");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int B = c->B, P = c->resect_P;
-  const size_t n = (size_t)B * P * K;
-  int rc;
-  c->stem_resect_seq = ~0ull;      // (before "stem.out" can be resized or half rewritten: an early return leaves no stems for sh_resect_plan)
-  ENS_SHARED("stem.catalogue", (size_t)K * sizeof(sh_stem), 8); ENS_SHARED("stem.out", n * sizeof(sh_stem_fit), 8);
-  auto at = [c](const char* name) { return c->bufs.find(name)->second.p; };
-  const ResectView v = resect_view(c);
-  sh_stem* d_cat = (sh_stem*)at("stem.catalogue"); sh_stem_fit* d_out = (sh_stem_fit*)at("stem.out");
-  const sh_canal_grid& g = c->canal_grid;
-  HIPCHK(c, hipMemcpyAsync(d_cat, stems, (size_t)K * sizeof(sh_stem), hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_stem_fit", k_stem_fit, dim3((unsigned)(B * P)), dim3(SH_STEM_THREADS), (const double*)v.planes, (const int*)v.status, (const sh_resection*)v.out,
-         (const double*)at("canal.frames"), (const int*)at("canal.status"), (const double*)at("canal.near"), (const sh_canal_level*)at("canal.levels"),
-         (const double*)at("canal.dirs"), g.z0, g.dz, g.L, g.A, (const sh_stem*)d_cat, K, P, d_out);
-  HIPCHK(c, hipMemcpyAsync(out, d_out, n * sizeof(sh_stem_fit), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->stem_resect_seq = c->resect_seq; c->stem_canal_seq = c->canal_seq; c->stem_K = K;
-  return SH_OK;
-}
-
-// ---- implant plans: the seats and the stems of the last resection joined and ranked (k_plan.h) -----------------------------------
-static bool plan_rule_ok(const sh_plan_rule* r) {
-  static_assert(sizeof(sh_plan_rule) == 12 * sizeof(double), "sh_plan_rule is twelve doubles");
-  for (int i = 0; i < 12; ++i)
-    if (std::isnan(((const double*)r)[i])) return false;
-  for (double w : {r->w_uncovered, r->w_overhang, r->w_cor, r->w_height, r->w_eccentricity, r->w_fill})
-    if (!std::isfinite(w) || w < 0.0) return false;
-  return r->margin >= 0.0;
-}
-
-int sh_resect_plan(sh_ctx* c, const sh_plan_rule* rule, const uint64_t* compat, const double* ref_planes, int N, sh_plan* out, sh_plan_ref* ref_out) {
-  if (!rule || !out || N < 1 || N > SH_PLAN_MAX) return fail(c, SH_ERR_ARG, "sh_resect_plan: bad argument (N in 1..64)");
-  if (!plan_rule_ok(rule)) return fail(c, SH_ERR_ARG, "sh_resect_plan: bad rule (no NaN, weights finite and >= 0, margin >= 0)");
-  if (!c) return SH_ERR_ARG;
-  if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_resect_plan: runs are in flight (sh_collect them first)");
-  if (c->B < 1 || c->resect_gen != c->batch_gen || c->resect_P < 1 || c->seat_resect_seq != c->resect_seq)
-    return fail(c, SH_ERR_STATE, "sh_resect_plan: no seated resection of the resident batch (sh_resect_planes_seat / sh_resect_offsets_seat)");
-  if (c->canal_gen != c->batch_gen || c->stem_resect_seq != c->resect_seq || c->stem_canal_seq != c->canal_seq)
-    return fail(c, SH_ERR_STATE, "sh_resect_plan: no stems fitted against the last resection and the current canal profile (sh_resect_stems)");
-  if (!ref_planes && !resect_has_records(c))
-    return fail(c, SH_ERR_STATE, "sh_resect_plan: ref_planes == NULL needs a run of the resident batch with SH_STAGE_ANP and SH_STAGE_CSYS");
-  const int B = c->B, P = c->resect_P, Kh = c->seat_K, Ks = c->stem_K;
-  if (ref_planes)
-    for (int b = 0; b < B; ++b) {
-      const double* pl = ref_planes + 6 * (size_t)b;
-      bool fin = true;
-      for (int k = 0; k < 6; ++k) fin = fin && std::isfinite(pl[k]);
-      if (!fin || !((pl[3] * pl[3] + pl[4] * pl[4]) + pl[5] * pl[5] > 0.0))
-        return fail(c, SH_ERR_ARG, "sh_resect_plan: reference plane " + std::to_string(b) + " has a zero normal or is not finite");
-    }
-  HIPCHK(c, hipSetDevice(c->device));
-  const long long tmax = std::max<long long>(1, (c->maxV + SH_PLAN_TILE - 1) / SH_PLAN_TILE);
-  const size_t cuts = (size_t)B * P;
-  int rc;
-  ENS_SHARED("plan.ref_planes", (size_t)B * 48, 8); ENS_SHARED("plan.compat", (size_t)SH_SEAT_MAX_HEADS * 8, 8);
-  ENS_SHARED("plan.ref_slab", (size_t)B * tmax * 2 * sizeof(PlanTop), 8); ENS_SHARED("plan.ref", (size_t)B * sizeof(sh_plan_ref), 8);
-  ENS_SHARED("plan.cut_terms", cuts * sizeof(PlanTerm), 8); ENS_SHARED("plan.head_terms", cuts * Kh * sizeof(PlanTerm), 8);
-  ENS_SHARED("plan.stem_terms", cuts * Ks * sizeof(PlanTerm), 8); ENS_SHARED("plan.cut_vals", cuts * 8, 8);
-  ENS_SHARED("plan.head_vals", cuts * Kh * 64, 8); ENS_SHARED("plan.stem_vals", cuts * Ks * 8, 8);
-  ENS_SHARED("plan.out", (size_t)B * N * sizeof(sh_plan), 8);
-  auto at = [c](const char* name) { return c->bufs.find(name)->second.p; };
-  const ResectView v = resect_view(c);
-  double* d_rp = ref_planes ? (double*)at("plan.ref_planes") : nullptr;
-  const sh_landmarks* d_lm = ref_planes ? nullptr : v.lm;
-  unsigned long long* d_compat = (unsigned long long*)at("plan.compat");
-  PlanTop* d_slab = (PlanTop*)at("plan.ref_slab"); sh_plan_ref* d_ref = (sh_plan_ref*)at("plan.ref"); sh_plan* d_out = (sh_plan*)at("plan.out");
-  PlanTerm* d_ct = (PlanTerm*)at("plan.cut_terms"); PlanTerm* d_ht = (PlanTerm*)at("plan.head_terms"); PlanTerm* d_st = (PlanTerm*)at("plan.stem_terms");
-  double* d_cv = (double*)at("plan.cut_vals"); double* d_hv = (double*)at("plan.head_vals"); double* d_sv = (double*)at("plan.stem_vals");
-  const double* d_frames = (const double*)at("canal.frames"); const int* d_hst = (const int*)at("canal.status");
-  uint64_t words[SH_SEAT_MAX_HEADS];
-  for (int k = 0; k < SH_SEAT_MAX_HEADS; ++k) words[k] = compat && k < Kh ? compat[k] : ~0ull;      // (pageable: the copy is staged before the call returns)
-  HIPCHK(c, hipMemcpyAsync(d_compat, words, sizeof words, hipMemcpyHostToDevice, c->stream));
-  if (ref_planes) HIPCHK(c, hipMemcpyAsync(d_rp, ref_planes, (size_t)B * 48, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_plan_ref", k_plan_ref, dim3((unsigned)tmax, (unsigned)B), dim3(SH_PLAN_TILE), v.verts, v.voff, d_frames, d_hst, d_lm, (const double*)d_rp,
-         rule->margin, (int)tmax, d_slab);
-  LAUNCH(c, "k_plan_ref_join", k_plan_ref_join, dim3((unsigned)B), dim3(64), v.verts, v.voff, d_hst, d_lm, (const double*)d_rp, (int)tmax,
-         (const PlanTop*)d_slab, d_ref);
-  LAUNCH(c, "k_plan_terms", k_plan_terms, dim3((unsigned)cuts), dim3(SH_PLAN_TERM_THREADS), (const double*)v.planes, (const int*)v.status,
-         (const sh_resection*)v.out, (const sh_head_fit*)v.fit_out, (const sh_seat*)v.seat_out, (const sh_implant_head*)v.seat_heads, Kh,
-         (const sh_stem_fit*)at("stem.out"), Ks, d_frames, (const sh_plan_ref*)d_ref, *rule, P, d_ct, d_ht, d_st, d_cv, d_hv, d_sv);
-  LAUNCH(c, "k_plan_select", k_plan_select, dim3((unsigned)B), dim3(SH_PLAN_THREADS), (const PlanTerm*)d_ct, (const PlanTerm*)d_ht, (const PlanTerm*)d_st,
-         (const double*)d_cv, (const double*)d_hv, (const double*)d_sv, (const unsigned long long*)d_compat, P, Kh, Ks, N, d_ref, d_out);
-  HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)B * N * sizeof(sh_plan), hipMemcpyDeviceToHost, c->stream));
-  if (ref_out) HIPCHK(c, hipMemcpyAsync(ref_out, d_ref, (size_t)B * sizeof(sh_plan_ref), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
+// ---- the arthroplasty chain: sh_resect_*, sh_canal_profile, sh_resect_stems, sh_resect_plan (host code; the decisions are sh_arthro.h's) ----
+#include "sh_arthro_host.h"
 
 int sh_mesh_transformed(sh_ctx* c, int b, const double* T, double* out) {
   if (!c || !T || !out || b < 0 || b >= c->B) return fail(c, SH_ERR_ARG, "sh_mesh_transformed: bad argument");
@@ -2222,7 +1845,7 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
          dev_hull ? (const int*)buf<int>(c, "hulld.fail") : (const int*)nullptr, StatusBlock{(char*)err_stage, B});
   HIPCHK(c, hipEventRecord(tk.ev, c->stream));
   tk.B = B; tk.pending = true; tk.mask = mask; tk.out_arg = out; tk.dev_hull = dev_hull; tk.gen = c->batch_gen;
-  c->rec_mask = mask; c->rec_gen = c->batch_gen;
+  c->arthro.run_submitted(mask, c->batch_gen);
   c->t_head ^= 1; ++c->n_pending;
   return SH_OK;
 }
