@@ -605,6 +605,49 @@ int sh_resect_plan(sh_ctx*, const sh_plan_rule* rule, const uint64_t* compat /* 
                    const double* ref_planes /* B x (point, normal), CT, or NULL: each record's anp plane */,
                    int N, sh_plan* out /* B x N, host */, sh_plan_ref* ref_out /* B, host, nullable */);
 
+/* ---- rays against the resident batch: every hit, ordered ----------------------------------------------------------------------
+ * The reference asks `ray.intersects_location` (anatomic_neck.py:184-192, 217-224), which returns every hit; SH_STAGE_ANP keeps the
+ * nearest forward hit of its four rays (canonical rule B-6) and sh_canal_profile the nearest and the farthest.  These two calls
+ * return all of them: B resident humeri x R rays in one device pass (k_rays.h), brute force over the faces.
+ *   ray       sh_ray: origin and direction in CT.  The direction need not be a unit vector: t counts in units of |dir|.  A
+ *             non-finite number or a zero direction: SH_ERR_ARG.
+ *   hit rule  sh_scalar.h canal_ray_hit operation by operation (which restates k_rays_hit), through ray_tri_hit, the statement
+ *             that also returns det's sign: |det| > 1e-12, u >= 0, w >= 0, u + w <= 1 (closed), t > 1e-9, against the resident
+ *             float32 vertices widened to float64.
+ *   hit       sh_ray_hit (40 B): t; point[k] = origin[k] + dir[k] * t (the form of SH_STAGE_ANP's axis points); face, the
+ *             humerus-local face id; side = +1 when det > 0 -- the ray runs against the face's normal, so it ENTERS a mesh whose
+ *             normals point outward -- and -1 otherwise.  A ray through a shared edge or vertex hits every face the closed rule
+ *             accepts, and all of those hits are kept.
+ *   order     ascending by (t, face): a total order, so the result does not depend on the order the hits were found in (rule B-6
+ *             extended: "ascending t, then face").
+ *   counts    counts[b][r] is the exact number of hits over all faces whatever `cap` is; the first min(count, cap) hits in order
+ *             are stored and the slots behind them are zero with face = -1, so a smaller cap gives a byte prefix of a larger one.
+ *             cap in 1..SH_RAY_MAX_HITS, R in 1..SH_RAY_MAX (SH_ERR_ARG).
+ * A (humerus, ray) result depends on that mesh and that ray alone: not on B, the humerus' position in the batch, R, the ray's
+ * place in the list, cap, the tiling or the launch shape.  Integer atomics only choose slots of a pool and the sort removes their
+ * order; no floating-point atomics, no floating-point sums across lanes.
+ *
+ * sh_ray_cast needs a resident batch only, not a run: SH_ERR_STATE without one or while runs are in flight, SH_ERR_NOMEM when the
+ * hit pool (16 B per hit of the call) or the results do not fit.  rays: R rays shared by all humeri, or B x R with per_humerus != 0.
+ * The results stay resident in the named buffers "ray.hits" (B x R x cap sh_ray_hit) and "ray.counts" (B x R int32) until the next
+ * upload / commit / sh_store("verts"), as the canal profile does; both host pointers may be NULL.
+ *
+ * sh_anp_axis_hits casts the four rays of SH_STAGE_ANP (0 = +normal, 1 = -normal, 2 = +central, 3 = -central; k_anp.h ray_dir)
+ * for every humerus of the last collected run, in the box frame, from "anp.plane", against the vertices as that stage read them:
+ * each corner is "obb_transform" applied to the float32 vertex by the expression of the kernel that fills "verts_obb".  t is the
+ * box-frame parameter and equals "anp.ray_t" for the first hit; points are mapped to CT exactly as the record's anp_axis_normal /
+ * anp_axis_central rows are, so hits[b][ray][0].point equals the record's row bit for bit.  A humerus whose record failed gets its
+ * status and zero counts; it never fails the batch.  Without a collected run of the resident batch that had SH_STAGE_ANP:
+ * SH_ERR_STATE.  status must not be NULL; hits and counts may be. */
+#define SH_RAY_MAX 65536
+#define SH_RAY_MAX_HITS 1024
+typedef struct sh_ray { double origin[3], dir[3]; } sh_ray;
+typedef struct sh_ray_hit { double t; double point[3]; int32_t face; int32_t side; } sh_ray_hit;
+int sh_ray_cast(sh_ctx*, const sh_ray* rays /* R, or B x R when per_humerus */, int R, int per_humerus, int cap,
+                sh_ray_hit* hits /* B x R x cap, host, nullable */, int32_t* counts /* B x R, host, nullable */);
+int sh_anp_axis_hits(sh_ctx*, int cap, sh_ray_hit* hits /* B x 4 x cap, host, nullable */, int32_t* counts /* B x 4, host, nullable */,
+                     int32_t* status /* B, host */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

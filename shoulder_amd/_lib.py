@@ -220,6 +220,24 @@ PLAN_TERM_DTYPE = np.dtype([("cost", "<f8"), ("feasible", "<i4"), ("pad", "<i4")
 assert PLAN_RULE_DTYPE.itemsize == ctypes.sizeof(PlanRule) and PLAN_REF_DTYPE.itemsize == ctypes.sizeof(PlanRef) and PLAN_DTYPE.itemsize == ctypes.sizeof(Plan)
 
 
+RAY_MAX, RAY_MAX_HITS = 65536, 1024
+
+
+class Ray(ctypes.Structure):
+    """sh_ray: origin and direction (CT; t counts in units of |dir|)."""
+    _fields_ = [("origin", ctypes.c_double * 3), ("dir", ctypes.c_double * 3)]
+
+
+class RayHit(ctypes.Structure):
+    """sh_ray_hit: one hit of one ray -- t, the point, the humerus-local face and +1 where the ray runs against the face's normal."""
+    _fields_ = [("t", ctypes.c_double), ("point", ctypes.c_double * 3), ("face", ctypes.c_int32), ("side", ctypes.c_int32)]
+
+
+RAY_DTYPE = np.dtype([("origin", "<f8", (3,)), ("dir", "<f8", (3,))])
+RAY_HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("face", "<i4"), ("side", "<i4")])
+assert RAY_DTYPE.itemsize == ctypes.sizeof(Ray) and RAY_HIT_DTYPE.itemsize == ctypes.sizeof(RayHit) == 40
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -234,7 +252,8 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_slice_mesh_planes", "sh_set_unet_turns", "sh_get_params", "sh_buffer_device", "sh_param_block_commit", "sh_set_hull_mode", "sh_get_hull_mode", "sh_auto_hull_mode", "sh_ring",
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
-           "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan"]
+           "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan",
+           "sh_ray_cast", "sh_anp_axis_hits"]
 
 _lib = None
 
@@ -336,5 +355,8 @@ def load(build_if_missing=True):
         L.sh_resect_stems.argtypes = [vp, vp, ctypes.c_int, vp]
     if not alt or hasattr(L, "sh_resect_plan"):      # (tools/time_plan.py and the benchmark's parent arm)
         L.sh_resect_plan.argtypes = [vp, ctypes.POINTER(PlanRule), vp, vp, ctypes.c_int, vp, vp]
+    if not alt or hasattr(L, "sh_ray_cast"):      # (tools/time_rays.py and the benchmark's parent arm)
+        L.sh_ray_cast.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+        L.sh_anp_axis_hits.argtypes = [vp, ctypes.c_int, vp, vp, vp]
     _lib = L
     return L

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib, unet_spec
 from .base import Bone, Landmark, Mesh, Plane, Transform
-from .engine import Engine
+from .engine import Engine, ShoulderHipError
 from .stl import load_stl
 
 _DEFAULT_ENGINE = None
@@ -199,6 +199,7 @@ class AnatomicNeck(_Lm):
         super().__init__(bone)
         self._points_ct = self._plane_ct = self._plane_points_ct = None
         self._central_axis_ct = self._normal_axis_ct = None
+        self._axis_hits_ct = None      # every hit of the four rays (CT), for hits="all" / "outermost"
 
     def points(self) -> np.ndarray:
         if self._points_ct is None:
@@ -231,14 +232,47 @@ class AnatomicNeck(_Lm):
         self._plane_points = self._t(self._plane_points_ct)
         return self._plane_points
 
-    def axis_normal(self) -> np.ndarray:
+    def _axis_hits(self, first, hits):
+        """The rays `first` (upper) and `first + 1` (lower) with every hit (Engine.anp_axis_hits): hits="all" is the reference's
+        `np.r_[upper_loc, bottom_loc]` (anatomic_neck.py:184-192, 217-224) with each direction ascending by (t, face), "outermost"
+        the last hit of each direction.  Neither touches the cached nearest-hit axes, so metrics and coordinate systems stay."""
+        if hits not in ("all", "outermost"):
+            raise ValueError(f'hits is "nearest", "all" or "outermost", not {hits!r}')
+        if self._axis_hits_ct is None:
+            self.plane()
+            b, e = self._b, self._b._engine
+            b._ensure_loaded()
+            cap = 16
+            while True:
+                try:
+                    h, n, st = e.anp_axis_hits(cap)
+                except ShoulderHipError as ex:
+                    if ex.code != -3:
+                        raise
+                    e.set_params(groove_cutoff=b._groove_params[0], groove_deg_window=b._groove_params[1])      # the engine's last run was not this bone's late one
+                    b._run(b._LATE, fetch=False)
+                    h, n, st = e.anp_axis_hits(cap)
+                if int(n.max()) <= cap or cap >= _lib.RAY_MAX_HITS:
+                    break
+                cap = min(int(n.max()), _lib.RAY_MAX_HITS)
+            if int(st[0]) != 0:
+                raise ValueError(f"landmark stage failed with status {int(st[0])}")
+            self._axis_hits_ct = [np.array(h[0, r, :min(int(n[0, r]), cap)]["point"], dtype=np.float64) for r in range(4)]
+        up, lo = self._axis_hits_ct[first], self._axis_hits_ct[first + 1]
+        return self._t(np.r_[up, lo] if hits == "all" else np.r_[up[-1:], lo[-1:]])
+
+    def axis_normal(self, hits="nearest") -> np.ndarray:
+        if hits != "nearest":
+            return self._axis_hits(0, hits)
         if self._normal_axis_ct is None:
             self.plane()
             self._normal_axis_ct = np.array(self._b._all()["anp_axis_normal"], dtype=np.float64)
         self._normal_axis = self._t(self._normal_axis_ct)
         return self._normal_axis
 
-    def axis_central(self) -> np.ndarray:
+    def axis_central(self, hits="nearest") -> np.ndarray:
+        if hits != "nearest":
+            return self._axis_hits(2, hits)
         if self._central_axis_ct is None:
             self.plane()
             self._central_axis_ct = np.array(self._b._all()["anp_axis_central"], dtype=np.float64)
@@ -403,6 +437,24 @@ class ProximalHumerus(Bone):
         v = (q[0] - q[1]) / np.linalg.norm(q[0] - q[1])
         theta = float(np.rad2deg(np.arctan2(v[1], -1 * v[0])))
         return -theta if int(lm["side"]) == 1 else theta
+
+    # -- rays against the mesh --------------------------------------------------------------------------------
+    def ray_hits(self, origins, directions):
+        """`mesh.ray.intersects_location(origins, directions)` in the CURRENT coordinate system on the device (Engine.ray_cast):
+        -> (locations (n, 3), index_ray (n,), index_tri (n,)), sorted by ray and then by (t, face).  The rays go to CT through the
+        inverse of the current transform (points by the full matrix, directions by its linear part), the locations come back through it."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        if len(o) != len(d) or len(o) < 1:
+            raise ValueError("origins and directions must both have shape (n, 3), n >= 1")
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        Ti = np.linalg.inv(T)
+        self._ensure_loaded()
+        hits, counts = self._engine.ray_cast(self._engine.transform_points(o, Ti), d @ Ti[:3, :3].T, cap=None)
+        keep = np.arange(hits.shape[2])[None, :] < counts[0][:, None]
+        loc_ct = np.ascontiguousarray(hits[0]["point"][keep])
+        loc = self._engine.transform_points(loc_ct, T) if len(loc_ct) else np.zeros((0, 3))
+        return loc, np.nonzero(keep)[0], np.array(hits[0]["face"][keep], dtype=np.int64)
 
     # -- coordinate systems (bone.py:53-105, :146-157) --------------------------------------------------
     def _mesh_in(self, T):

@@ -36,6 +36,11 @@ namespace sh {
   X(plan_stem_terms, "plan.stem_terms", PlanTerm, 8) X(plan_cut_vals, "plan.cut_vals", double, 8)                                  \
   X(plan_head_vals, "plan.head_vals", double, 8) X(plan_stem_vals, "plan.stem_vals", double, 8) X(plan_out, "plan.out", sh_plan, 8)
 #define ARTHRO_BUFS(X) ARTHRO_RESECT_BUFS(X) ARTHRO_CANAL_BUFS(X) ARTHRO_STEM_BUFS(X) ARTHRO_PLAN_BUFS(X)
+// the rays against the resident batch (sh_ray_cast / sh_anp_axis_hits) are not a link of the chain: buffers, sizes and view of their own
+#define RAY_BUFS(X)                                                                                                                \
+  X(ray_rays, "ray.rays", double, 8) X(ray_status, "ray.status", int, 4) X(ray_counts, "ray.counts", int, 4)                       \
+  X(ray_offs, "ray.offs", unsigned long long, 8) X(ray_cursor, "ray.cursor", int, 4) X(ray_pool, "ray.pool", RayKey, 8)            \
+  X(ray_hits, "ray.hits", sh_ray_hit, 8) X(ray_blockhit, "ray.blockhit", int, 4)
 // what the chain reads and does not own (the mesh: upload / commit; the records of a run: alloc_batch): X(field, "name", type)
 #define ARTHRO_INPUT_BUFS(X)                                                                                                       \
   X(verts, "verts", const float) X(faces, "faces", const int) X(voff, "voff", const long long) X(foff, "foff", const long long)    \
@@ -44,12 +49,14 @@ namespace sh {
 // bytes of every buffer a call ensures; 0: not this call's (every size of a call is > 0: B, P, K, L, A, N >= 1)
 #define X(f, name, T, elem) size_t f = 0;
 struct ArthroBytes { ARTHRO_BUFS(X) };
+struct RayBytes { RAY_BUFS(X) };
 #undef X
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RS_TILE = 256, AR_HF_WORDS = 16, AR_RESECT_PART_BYTES = 32;      // SH_RS_TILE, SH_HF_WORDS, sizeof(ResectPart)
 constexpr int AR_CANAL_TILE = 256, AR_PLAN_TILE = 256;                            // SH_CANAL_TILE, SH_PLAN_TILE
 constexpr int AR_PLAN_TOP_BYTES = 16, AR_PLAN_TERM_BYTES = 16;                    // sizeof(PlanTop), sizeof(PlanTerm)
+constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
 
 struct ArthroError { int code; std::string text; };      // code SH_OK: accepted (text empty)
 inline ArthroError arthro_ok() { return {SH_OK, std::string()}; }
@@ -134,6 +141,17 @@ inline int first_bad_frame(const double* frames, int B) {
 
 inline bool stem_catalogue_ok(const sh_stem* stems, int K) { return all_doubles(stems, K, [](double x) { return std::isfinite(x) && x > 0.0; }); }
 
+// n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
+inline long long first_bad_ray(const sh_ray* rays, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    const sh_ray& r = rays[i];
+    bool fin = true;
+    for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(r.origin[k]) && std::isfinite(r.dir[k]);
+    if (!fin || (r.dir[0] == 0.0 && r.dir[1] == 0.0 && r.dir[2] == 0.0)) return (long long)i;
+  }
+  return -1;
+}
+
 inline bool plan_rule_ok(const sh_plan_rule* r) {
   if (!all_doubles(r, 1, [](double x) { return !std::isnan(x); })) return false;
   for (double w : {r->w_uncovered, r->w_overhang, r->w_cor, r->w_height, r->w_eccentricity, r->w_fill})
@@ -201,6 +219,21 @@ inline PlanPlan plan_plan(int B, int P, int Kh, int Ks, int N, long long maxV) {
   return {(int)tmax, cuts, z};
 }
 
+// a cast of R rays per humerus with room for cap hits each: everything but the pool, which the counts size ("ray.pool", ray_pool_bytes)
+struct RayPlan { int tmax, chunks; size_t rays; RayBytes bytes; };      // face tiles per humerus, ray chunks, B x R
+inline RayPlan ray_plan(int B, int R, bool per_humerus, int cap, long long maxF, bool with_status) {
+  const size_t n = (size_t)B * R;
+  RayBytes z;
+  z.ray_rays = (per_humerus ? n : (size_t)R) * sizeof(sh_ray); z.ray_counts = n * 4; z.ray_offs = (n + 1) * 8; z.ray_cursor = n * 4;
+  z.ray_hits = n * cap * sizeof(sh_ray_hit);
+  if (with_status) z.ray_status = (size_t)B * 4;
+  const long long tmax = tiles_of(maxF, AR_RAY_TILE);
+  const int chunks = (R + AR_RAY_CHUNK - 1) / AR_RAY_CHUNK;
+  z.ray_blockhit = (size_t)tmax * B * chunks * 4;      // one word per workgroup of the walk
+  return {(int)tmax, chunks, n, z};
+}
+inline size_t ray_pool_bytes(unsigned long long total) { return (size_t)(total > 0 ? total : 1) * AR_RAY_KEY_BYTES; }
+
 // ---- what is valid against what -----------------------------------------------------------------------------------------------------
 // One member of sh_ctx.  The resident batch is the context's (batch_gen: every upload / commit / store to "verts" takes a new one);
 // the queries take it as an argument.  RULE: void first, commit on success -- a *_begin voids what the call is about to overwrite and
@@ -225,6 +258,7 @@ class ArthroState {
     const uint32_t need = SH_STAGE_ANP | SH_STAGE_CSYS;
     return rec_gen_ == batch_gen && (rec_mask_ & need) == need;
   }
+  bool has_anp(unsigned long long batch_gen) const { return rec_gen_ == batch_gen && (rec_mask_ & SH_STAGE_ANP) != 0; }      // the last submitted run: this batch, with the anatomic neck
   bool resected(unsigned long long batch_gen) const { return resect_gen_ == batch_gen && P_ >= 1; }
   bool seated(unsigned long long batch_gen) const { return resected(batch_gen) && seated_; }
   bool profiled(unsigned long long batch_gen) const { return canal_gen_ == batch_gen; }
@@ -314,6 +348,23 @@ inline ArthroError precheck_plan(const sh_plan_rule* rule, const double* ref_pla
     const long long b = first_bad_plane(ref_planes, (size_t)f.B);
     if (b >= 0) return {SH_ERR_ARG, "reference plane " + std::to_string(b) + " has a zero normal or is not finite"};
   }
+  return arthro_ok();
+}
+
+inline ArthroError precheck_ray_cast(const sh_ray* rays, int R, int per_humerus, int cap, const ArthroFacts& f) {
+  if (!f.ctx || !rays || R < 1 || R > SH_RAY_MAX || cap < 1 || cap > SH_RAY_MAX_HITS) return {SH_ERR_ARG, "bad argument (R in 1..65536, cap in 1..1024)"};
+  if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
+  if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
+  const long long i = first_bad_ray(rays, per_humerus ? (size_t)f.B * R : (size_t)R);
+  if (i >= 0) return {SH_ERR_ARG, "ray " + std::to_string(i) + " has a non-finite number or a zero direction"};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_anp_hits(int cap, const int32_t* status, const ArthroFacts& f) {
+  if (!f.ctx || !status || cap < 1 || cap > SH_RAY_MAX_HITS) return {SH_ERR_ARG, "bad argument (cap in 1..1024)"};
+  if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
+  if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
+  if (!f.st->has_anp(f.batch_gen) || !f.landmarks) return {SH_ERR_STATE, "needs a collected run of the resident batch with SH_STAGE_ANP"};
   return arthro_ok();
 }
 

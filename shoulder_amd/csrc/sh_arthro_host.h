@@ -1,5 +1,5 @@
 // sh_arthro_host.h -- the entry points of the arthroplasty chain: sh_resect_* (k_resect.h, k_headfit.h, k_seat.h), sh_canal_profile and
-// sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
+// sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h), and the rays against the resident batch, sh_ray_cast / sh_anp_axis_hits (k_rays.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
 // headers and inside its extern "C" block.  A header and not a unit of its own: compiled in a unit that holds only the resection
 // headers, the unchanged k_resect_faces takes 100 VGPRs instead of 92, four waves per SIMD instead of five, so the kernels
 // stay in shoulder_hip.hip and the code that launches them with them.
@@ -10,6 +10,7 @@
 static_assert(AR_RS_TILE == SH_RS_TILE && AR_HF_WORDS == SH_HF_WORDS && AR_RESECT_PART_BYTES == sizeof(ResectPart), "sh_arthro.h: resection tile, moment words, slab entry");
 static_assert(AR_CANAL_TILE == SH_CANAL_TILE && AR_PLAN_TILE == SH_PLAN_TILE && AR_PLAN_TOP_BYTES == sizeof(PlanTop) && AR_PLAN_TERM_BYTES == sizeof(PlanTerm),
               "sh_arthro.h: canal and plan tiles, PlanTop, PlanTerm");
+static_assert(AR_RAY_TILE == SH_RAY_TILE && AR_RAY_CHUNK == SH_RAY_CHUNK && AR_RAY_KEY_BYTES == sizeof(RayKey), "sh_arthro.h: ray tile, ray chunk, RayKey");
 
 // The named buffers of a call as typed pointers (ARTHRO_BUFS, ARTHRO_INPUT_BUFS), resolved once per call BEHIND the call's
 // arthro_ensure (which may re-allocate them); a buffer that is not there is null.  No window offset: the chain works on the whole batch.
@@ -242,6 +243,86 @@ int sh_resect_plan(sh_ctx* c, const sh_plan_rule* rule, const uint64_t* compat, 
          (const unsigned long long*)v.plan_compat, P, Kh, Ks, N, v.plan_ref, v.plan_out);
   HIPCHK(c, hipMemcpyAsync(out, v.plan_out, (size_t)B * N * sizeof(sh_plan), hipMemcpyDeviceToHost, c->stream));
   if (ref_out) HIPCHK(c, hipMemcpyAsync(ref_out, v.plan_ref, (size_t)B * sizeof(sh_plan_ref), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- rays against the resident batch, every hit (k_rays.h); reads the mesh (and, for the anatomic-neck rays, the last run), changes no state ----
+#define X(f, name, T, ...) T* f = nullptr;
+struct RayView { ARTHRO_INPUT_BUFS(X) RAY_BUFS(X) };
+#undef X
+static RayView ray_view(sh_ctx* c) {
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  RayView v;
+#define X(f, name, T, ...) v.f = (T*)at(name);
+  ARTHRO_INPUT_BUFS(X) RAY_BUFS(X)
+#undef X
+  return v;
+}
+static int ray_ensure(sh_ctx* c, const RayBytes& z) {
+  int rc;
+#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
+  RAY_BUFS(X)
+#undef X
+  return SH_OK;
+}
+
+// count -> scan -> the total to the host -> "ray.pool" -> fill -> sort -> copies back.  "ray.rays" (and "ray.status" with `box`) are filled
+// by the caller on the stream; T_obb / hstatus: the box transforms and the humeri to leave out (sh_anp_axis_hits), or null.
+static int ray_run(sh_ctx* c, const RayPlan& plan, int R, int per_humerus, int cap, const double* T_obb, const int* hstatus, sh_ray_hit* hits, int32_t* counts) {
+  int rc;
+  const int B = c->B;
+  const size_t n = plan.rays;
+  RayView v = ray_view(c);
+  const bool box = T_obb != nullptr;
+  HIPCHK(c, hipMemsetAsync(v.ray_counts, 0, n * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.ray_cursor, 0, n * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.ray_blockhit, 0, plan.bytes.ray_blockhit, c->stream));
+  const dim3 grid((unsigned)plan.tmax, (unsigned)B, (unsigned)plan.chunks), block(SH_RAY_TILE);
+  LAUNCH(c, "k_ray_count", box ? k_ray_count<true> : k_ray_count<false>, grid, block, v.verts, v.faces, v.voff, v.foff, T_obb, hstatus, (const double*)v.ray_rays, R,
+         per_humerus, v.ray_counts, v.ray_blockhit);
+  LAUNCH(c, "k_ray_scan", k_ray_scan, dim3(1), dim3(1024), (const int*)v.ray_counts, (long long)n, v.ray_offs);
+  unsigned long long total = 0;
+  HIPCHK(c, hipMemcpyAsync(&total, v.ray_offs + n, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ENS_SHARED("ray.pool", ray_pool_bytes(total), 8);
+  v = ray_view(c);
+  LAUNCH(c, "k_ray_fill", box ? k_ray_fill<true> : k_ray_fill<false>, grid, block, v.verts, v.faces, v.voff, v.foff, T_obb, hstatus, (const double*)v.ray_rays, R,
+         per_humerus, (const unsigned long long*)v.ray_offs, v.ray_cursor, v.ray_pool, v.ray_blockhit);
+  LAUNCH(c, "k_ray_sort", box ? k_ray_sort<true> : k_ray_sort<false>, dim3((unsigned)n), dim3(64), (const double*)v.ray_rays, R, per_humerus,
+         (const unsigned long long*)v.ray_offs, (const int*)v.ray_cursor, (const RayKey*)v.ray_pool, T_obb, cap, v.ray_hits);
+  if (hits) HIPCHK(c, hipMemcpyAsync(hits, v.ray_hits, n * cap * sizeof(sh_ray_hit), hipMemcpyDeviceToHost, c->stream));
+  if (counts) HIPCHK(c, hipMemcpyAsync(counts, v.ray_counts, n * 4, hipMemcpyDeviceToHost, c->stream));
+  return SH_OK;
+}
+
+int sh_ray_cast(sh_ctx* c, const sh_ray* rays, int R, int per_humerus, int cap, sh_ray_hit* hits, int32_t* counts) {
+  if (const ArthroError e = precheck_ray_cast(rays, R, per_humerus, cap, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_ray_cast", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const RayPlan plan = ray_plan(c->B, R, per_humerus != 0, cap, c->maxF, false);
+  if (int rc = ray_ensure(c, plan.bytes)) return rc;
+  const RayView v = ray_view(c);
+  HIPCHK(c, hipMemcpyAsync(v.ray_rays, rays, plan.bytes.ray_rays, hipMemcpyHostToDevice, c->stream));
+  if (int rc = ray_run(c, plan, R, per_humerus != 0, cap, nullptr, nullptr, hits, counts)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+int sh_anp_axis_hits(sh_ctx* c, int cap, sh_ray_hit* hits, int32_t* counts, int32_t* status) {
+  if (const ArthroError e = precheck_anp_hits(cap, status, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_anp_axis_hits", e);
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  const double* plane = (const double*)at("anp.plane");
+  const double* T_obb = (const double*)at("obb_transform");
+  const sh_landmarks* lm = (const sh_landmarks*)at("landmarks");
+  if (!plane || !T_obb || !lm) return fail(c, SH_ERR_STATE, "sh_anp_axis_hits: the buffers of the anatomic-neck stage are not there");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B;
+  const RayPlan plan = ray_plan(B, 4, true, cap, c->maxF, true);
+  if (int rc = ray_ensure(c, plan.bytes)) return rc;
+  const RayView v = ray_view(c);
+  LAUNCH(c, "k_ray_anp_rays", k_ray_anp_rays, dim3((unsigned)((B + 63) / 64)), dim3(64), lm, plane, B, v.ray_rays, v.ray_status);
+  if (int rc = ray_run(c, plan, 4, 1, cap, T_obb, (const int*)v.ray_status, hits, counts)) return rc;
+  HIPCHK(c, hipMemcpyAsync(status, v.ray_status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

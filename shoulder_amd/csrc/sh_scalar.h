@@ -906,6 +906,32 @@ SH_HD bool canal_ray_hit(const double* o, const double* d, const double* A, cons
   *t_out = t;
   return true;
 }
+// The same statement for a triangle kept as (A, e1 = B - A, e2 = C - A), which also returns det's sign (include/shoulder_hip.h
+// sh_ray_hit.side: +1 when det > 0, the ray runs against the face's normal; -1 otherwise).  Verdict and t are canal_ray_hit's bits:
+// the edges are the differences it takes first, everything behind them is its operations in its order (k_rays.h; -ffp-contract=off).
+SH_HD bool ray_tri_hit(const double* o, const double* d, const double* A, const double* e1, const double* e2, double* t_out, int* side_out) {
+  const double tv[3] = {o[0] - A[0], o[1] - A[1], o[2] - A[2]};
+  double qv[3], pv[3];
+  cross3(tv, e1, qv);
+  cross3(d, e2, pv);
+  const double det = dot3(e1, pv);
+  if (!(fabs(det) > 1e-12)) return false;
+  const double inv = 1.0 / det;
+  const double uu = dot3(tv, pv) * inv;
+  const double ww = dot3(d, qv) * inv;
+  const double t = dot3(e2, qv) * inv;
+  if (!(uu >= 0 && ww >= 0 && uu + ww <= 1 && t > 1e-9)) return false;
+  *t_out = t;
+  *side_out = det > 0 ? 1 : -1;
+  return true;
+}
+SH_HD bool canal_ray_hit_side(const double* o, const double* d, const double* A, const double* B, const double* C, double* t_out, int* side_out) {
+  const double e1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+  const double e2[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+  return ray_tri_hit(o, d, A, e1, e2, t_out, side_out);
+}
+// hits of a ray order ascending by (t, face): total, a face is hit once (t is never NaN: it passed t > 1e-9)
+SH_HD bool ray_key_less(double ta, int fa, double tb, int fb) { return ta < tb || (ta == tb && fa < fb); }
 // The levels a face with frame heights [zmin, zmax] can be hit at, z_l = z0 - l dz: z_l in [zmin, zmax] <=> (z0 - zmax) / dz <= l
 // <= (z0 - zmin) / dz, rounded outwards and widened by one level each side (the full test decides), clamped to [0, L - 1];
 // empty: *lo > *hi.  A superset of what canal_ray_hit accepts, never less.

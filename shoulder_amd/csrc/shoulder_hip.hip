@@ -15,6 +15,7 @@
 #include "k_seat.h"
 #include "k_stem.h"
 #include "k_plan.h"
+#include "k_rays.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"

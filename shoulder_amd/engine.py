@@ -573,6 +573,44 @@ class Engine:
                                         n, _ptr(plans), _ptr(refs)))
         return plans, refs
 
+    # ---- rays against the resident batch, every hit (include/shoulder_hip.h sh_ray_cast / sh_anp_axis_hits) ----------------------
+    def ray_cast(self, origins, directions, cap=16):
+        """Every hit of R rays with every resident humerus, ascending by (t, face) -> (hits, counts): a structured array (B, R, cap)
+        of _lib.RAY_HIT_DTYPE and the exact counts (B, R) int32, whatever cap is; slots behind a ray's count are zero with face = -1.
+        origins / directions: (R, 3), shared by all humeri, or (B, R, 3), in CT; a direction need not be a unit vector (t counts in
+        units of its length).  cap=None: room for 16 hits, and the call is made again with the largest count when that is more."""
+        o = np.ascontiguousarray(origins, dtype=np.float64)
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+        if o.shape != d.shape or o.ndim not in (2, 3) or o.shape[-1] != 3 or (o.ndim == 3 and o.shape[0] != self.B):
+            raise ValueError("origins and directions must both have shape (R, 3) or (B, R, 3)")
+        R, per = o.shape[-2], int(o.ndim == 3)
+        rays = np.empty(o.shape[:-1], dtype=_lib.RAY_DTYPE)
+        rays["origin"], rays["dir"] = o, d
+        grow, cap = cap is None, 16 if cap is None else int(cap)
+        while True:
+            ok = 1 <= R <= _lib.RAY_MAX and 1 <= cap <= _lib.RAY_MAX_HITS      # (the library reports the rest; nothing is sized by it here)
+            hits = np.zeros((self.B, R, cap) if ok else (0,), dtype=_lib.RAY_HIT_DTYPE)
+            counts = np.zeros((self.B, R) if ok else (0,), dtype=np.int32)
+            self._chk(self.L.sh_ray_cast(self.h, _ptr(rays), R, per, cap, _ptr(hits), _ptr(counts)))
+            most = int(counts.max()) if counts.size else 0
+            if grow and most > cap and cap < _lib.RAY_MAX_HITS:
+                cap = min(most, _lib.RAY_MAX_HITS)
+                continue
+            return hits, counts
+
+    def anp_axis_hits(self, cap=16):
+        """Every hit of the four anatomic-neck rays (0 = +normal, 1 = -normal, 2 = +central, 3 = -central) of every humerus of the last
+        run with STAGE_ANP -> (hits (B, 4, cap) of _lib.RAY_HIT_DTYPE, counts (B, 4) int32, status (B,) int32).  t is the box-frame
+        parameter, the points are in CT; the first hit of a ray is the record's anp_axis_normal / anp_axis_central row, bit for bit.
+        A humerus whose record failed has its status and zero counts."""
+        cap = int(cap)
+        ok = 1 <= cap <= _lib.RAY_MAX_HITS
+        hits = np.zeros((self.B, 4, cap) if ok else (0,), dtype=_lib.RAY_HIT_DTYPE)
+        counts = np.zeros((self.B, 4), dtype=np.int32)
+        status = np.zeros(max(self.B, 1), dtype=np.int32)
+        self._chk(self.L.sh_anp_axis_hits(self.h, cap, _ptr(hits), _ptr(counts), _ptr(status)))
+        return hits, counts, status[: self.B]
+
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):
         n, e = ctypes.c_size_t(), ctypes.c_int()
