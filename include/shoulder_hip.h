@@ -648,6 +648,34 @@ int sh_ray_cast(sh_ctx*, const sh_ray* rays /* R, or B x R when per_humerus */, 
 int sh_anp_axis_hits(sh_ctx*, int cap, sh_ray_hit* hits /* B x 4 x cap, host, nullable */, int32_t* counts /* B x 4, host, nullable */,
                      int32_t* status /* B, host */);
 
+/* ---- closest surface points of the resident batch ------------------------------------------------------------------------------
+ * The counterpart of `trimesh.proximity.closest_point(mesh, points)`: for Q query points, shared by all humeri or Q per humerus, the
+ * nearest point of each of the B resident meshes, in one device pass (k_closest.h), brute force over the faces with a conservative cull.
+ *   rule      sh_scalar.h closest_pt_tri: the Voronoi-region walk of Ericson, Real-Time Collision Detection 5.1.5, on the resident
+ *             float32 vertices widened to float64, the triangle kept as (A, ab, ac); the regions are tested in the fixed order vertex A,
+ *             vertex B, edge AB, vertex C, edge CA, edge BC, interior.
+ *   winner    the smallest (d2, face) over the faces of the humerus (closest_key_less): a total order, so the result does not depend on
+ *             the order the faces were walked in.  A point whose nearest feature is an edge or a vertex sees the same d2 from every
+ *             incident face: the smallest face id wins.  A d2 that is not finite never wins.
+ *   sh_closest (48 B)  dist = sqrt(d2) of the winner; point = A + ab u + ac w, recomputed from the winning face alone, in CT; face, the
+ *             humerus-local face id; region: 0 interior, 1 / 2 / 3 edge AB / BC / CA, 4 / 5 / 6 vertex A / B / C of that face;
+ *             side = +1 when (p - point) . (ab x ac) >= 0 and -1 otherwise.  With region == 0 side says outside (+1) or inside (-1) a
+ *             mesh whose normals point outward.  For an edge or a vertex winner it is the WINNING FACE's verdict, which can be wrong at
+ *             sharp or saddle features (Baerentzen & Aanaes, Signed distance computation using the angle weighted pseudonormal, 2005);
+ *             a robust inside test (parity, winding number) is not part of this call.
+ *             status 0; SH_ERR_GEOMETRY (the kernels' SH_ERR_GEOMETRY_DEV) with face = -1 and every other field zero when no face of the humerus gave a finite d2.
+ * A (humerus, point) result depends on that mesh and that point alone: not on B, the humerus' position in the batch, Q, the point's
+ * place in the list, or how the faces were split or tiled.  No floating-point atomics, no floating-point sums across lanes.
+ *
+ * Arguments in this order: the context, points != NULL and Q in 1..SH_CLOSEST_MAX (SH_ERR_ARG); a resident batch and no runs in flight
+ * (SH_ERR_STATE; a run is not needed); every coordinate finite (SH_ERR_ARG).  SH_ERR_NOMEM when the results or the partials do not fit.
+ * The results stay resident in the named buffer "cp.out" (B x Q sh_closest) until the next upload / commit / sh_store("verts"), which
+ * removes it.  The call changes nothing else: the records of a run and the buffers of the arthroplasty chain keep their bytes. */
+#define SH_CLOSEST_MAX 1048576
+typedef struct sh_closest { double dist; double point[3]; int32_t face, region, side, status; } sh_closest;   /* 48 B */
+int sh_closest_points(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when per_humerus; CT */, int Q, int per_humerus,
+                      sh_closest* out /* B x Q, host, nullable */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

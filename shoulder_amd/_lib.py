@@ -238,6 +238,20 @@ RAY_HIT_DTYPE = np.dtype([("t", "<f8"), ("point", "<f8", (3,)), ("face", "<i4"),
 assert RAY_DTYPE.itemsize == ctypes.sizeof(Ray) and RAY_HIT_DTYPE.itemsize == ctypes.sizeof(RayHit) == 40
 
 
+CLOSEST_MAX = 1048576
+
+
+class Closest(ctypes.Structure):
+    """sh_closest: the closest surface point of one humerus to one query point -- distance, point (CT), the humerus-local face, the
+    region of that face (0 interior, 1 / 2 / 3 edge AB / BC / CA, 4 / 5 / 6 vertex A / B / C), +1 on the side the face's normal points to."""
+    _fields_ = [("dist", ctypes.c_double), ("point", ctypes.c_double * 3), ("face", ctypes.c_int32), ("region", ctypes.c_int32),
+                ("side", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+CLOSEST_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", (3,)), ("face", "<i4"), ("region", "<i4"), ("side", "<i4"), ("status", "<i4")])
+assert CLOSEST_DTYPE.itemsize == ctypes.sizeof(Closest) == 48
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -253,7 +267,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
            "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan",
-           "sh_ray_cast", "sh_anp_axis_hits"]
+           "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points"]
 
 _lib = None
 
@@ -358,5 +372,7 @@ def load(build_if_missing=True):
     if not alt or hasattr(L, "sh_ray_cast"):      # (tools/time_rays.py and the benchmark's parent arm)
         L.sh_ray_cast.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
         L.sh_anp_axis_hits.argtypes = [vp, ctypes.c_int, vp, vp, vp]
+    if not alt or hasattr(L, "sh_closest_points"):      # (tools/time_closest.py and the benchmark's parent arm)
+        L.sh_closest_points.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
     _lib = L
     return L

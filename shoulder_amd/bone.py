@@ -456,6 +456,37 @@ class ProximalHumerus(Bone):
         loc = self._engine.transform_points(loc_ct, T) if len(loc_ct) else np.zeros((0, 3))
         return loc, np.nonzero(keep)[0], np.array(hits[0]["face"][keep], dtype=np.int64)
 
+    # -- closest surface points ---------------------------------------------------------------------------------
+    def _closest_ct(self, points):
+        """the records of Engine.closest_points for points given in the CURRENT coordinate system, and the current matrix"""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        if len(p) < 1:
+            raise ValueError("points must have shape (n, 3), n >= 1")
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        self._ensure_loaded()
+        return self._engine.closest_points(self._engine.transform_points(p, np.linalg.inv(T)))[0], T
+
+    def closest_point(self, points):
+        """`trimesh.proximity.closest_point(mesh, points)` in the CURRENT coordinate system on the device (Engine.closest_points):
+        -> (closest (n, 3), distance (n,), triangle_id (n,)).  The points go to CT through the inverse of the current transform, the
+        closest points come back through it (the transforms are rigid: the distance is CT's).  Among triangles at the same distance
+        the smallest id is returned."""
+        rec, T = self._closest_ct(points)
+        if np.any(rec["status"] != 0):
+            raise ValueError(f"closest_point failed with status {int(rec['status'][rec['status'] != 0][0])}: no face of the mesh gave a finite distance")
+        return self._engine.transform_points(np.ascontiguousarray(rec["point"]), T), np.array(rec["dist"]), np.array(rec["face"], dtype=np.int64)
+
+    def surface_distance(self, other):
+        """How far `other` lies from this bone's surface: `other` is an (n, 3) array of points or anything with `.vertices` (a Mesh,
+        another bone's mesh, a half from `resect_mesh()`), in the CURRENT coordinate system.  -> dict with `mean`, `rms`, `max` (the
+        one-sided Hausdorff distance), `p95`, `n` and `argmax` (the index of the farthest point), from one closest_point call.
+        ONE-SIDED by design: the distances run from the points of `other` to this surface.  For the symmetric figures call
+        `b.surface_distance(a.mesh)` on the other bone as well and take the larger `max` (Hausdorff) or pool the two sets of distances."""
+        pts = other.vertices if hasattr(other, "vertices") else other
+        d = self.closest_point(pts)[1]
+        return dict(mean=float(d.mean()), rms=float(np.sqrt(np.mean(d * d))), max=float(d.max()), p95=float(np.percentile(d, 95)),
+                    n=int(len(d)), argmax=int(np.argmax(d)))
+
     # -- coordinate systems (bone.py:53-105, :146-157) --------------------------------------------------
     def _mesh_in(self, T):
         """`mesh_ct.copy().apply_transform(T)` (bone.py:155) on the device."""

@@ -41,6 +41,8 @@ namespace sh {
   X(ray_rays, "ray.rays", double, 8) X(ray_status, "ray.status", int, 4) X(ray_counts, "ray.counts", int, 4)                       \
   X(ray_offs, "ray.offs", unsigned long long, 8) X(ray_cursor, "ray.cursor", int, 4) X(ray_pool, "ray.pool", RayKey, 8)            \
   X(ray_hits, "ray.hits", sh_ray_hit, 8) X(ray_blockhit, "ray.blockhit", int, 4)
+// the closest surface points (sh_closest_points) are no link of the chain either
+#define CP_BUFS(X) X(cp_points, "cp.points", double, 8) X(cp_part, "cp.part", CpPart, 8) X(cp_out, "cp.out", sh_closest, 8)
 // what the chain reads and does not own (the mesh: upload / commit; the records of a run: alloc_batch): X(field, "name", type)
 #define ARTHRO_INPUT_BUFS(X)                                                                                                       \
   X(verts, "verts", const float) X(faces, "faces", const int) X(voff, "voff", const long long) X(foff, "foff", const long long)    \
@@ -50,6 +52,7 @@ namespace sh {
 #define X(f, name, T, elem) size_t f = 0;
 struct ArthroBytes { ARTHRO_BUFS(X) };
 struct RayBytes { RAY_BUFS(X) };
+struct CpBytes { CP_BUFS(X) };
 #undef X
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
@@ -57,6 +60,8 @@ constexpr int AR_RS_TILE = 256, AR_HF_WORDS = 16, AR_RESECT_PART_BYTES = 32;    
 constexpr int AR_CANAL_TILE = 256, AR_PLAN_TILE = 256;                            // SH_CANAL_TILE, SH_PLAN_TILE
 constexpr int AR_PLAN_TOP_BYTES = 16, AR_PLAN_TERM_BYTES = 16;                    // sizeof(PlanTop), sizeof(PlanTerm)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
+constexpr int AR_CP_TILE = 256, AR_CP_CHUNK = 256, AR_CP_PART_BYTES = 16;         // SH_CP_TILE, SH_CP_CHUNK, sizeof(CpPart)
+constexpr int AR_CP_FILL = 1024;      // workgroups of k_cp_walk that fill the chip: four of 256 lanes on each of 256 compute units
 
 struct ArthroError { int code; std::string text; };      // code SH_OK: accepted (text empty)
 inline ArthroError arthro_ok() { return {SH_OK, std::string()}; }
@@ -152,6 +157,13 @@ inline long long first_bad_ray(const sh_ray* rays, size_t n) {
   return -1;
 }
 
+// n points: the index of the first one with a coordinate that is not finite, or -1
+inline long long first_bad_point(const double* pts, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(pts[3 * i]) || !std::isfinite(pts[3 * i + 1]) || !std::isfinite(pts[3 * i + 2])) return (long long)i;
+  return -1;
+}
+
 inline bool plan_rule_ok(const sh_plan_rule* r) {
   if (!all_doubles(r, 1, [](double x) { return !std::isnan(x); })) return false;
   for (double w : {r->w_uncovered, r->w_overhang, r->w_cor, r->w_height, r->w_eccentricity, r->w_fill})
@@ -233,6 +245,26 @@ inline RayPlan ray_plan(int B, int R, bool per_humerus, int cap, long long maxF,
   return {(int)tmax, chunks, n, z};
 }
 inline size_t ray_pool_bytes(unsigned long long total) { return (size_t)(total > 0 ? total : 1) * AR_RAY_KEY_BYTES; }
+
+// Closest points, Q per humerus.  The grid of k_cp_walk is (chunks of 256 points, B, S face splits): split s of a humerus with T tiles
+// walks the tiles cp_split_range(T, S, s) (sh_scalar.h).  S is the host's choice and no knob: as many splits as bring the grid to
+// AR_CP_FILL workgroups when B x chunks is small, never more than the tiles of the largest humerus, at least one.  A minimum under a
+// total order does not depend on how its candidates are grouped, so S changes no result.
+inline int cp_splits(long long groups /* B x chunks */, long long tiles /* of the largest humerus */) {
+  const long long g = groups > 1 ? groups : 1, want = (AR_CP_FILL + g - 1) / g;
+  const long long s = want < tiles ? want : tiles;
+  return (int)(s > 1 ? s : 1);
+}
+struct CpPlan { int tmax, chunks, S; size_t points; CpBytes bytes; };      // face tiles of the largest humerus, point chunks, face splits, B x Q
+inline CpPlan cp_plan(int B, int Q, bool per_humerus, long long maxF) {
+  const size_t n = (size_t)B * Q;
+  const long long tmax = tiles_of(maxF, AR_CP_TILE);
+  const int chunks = (Q + AR_CP_CHUNK - 1) / AR_CP_CHUNK;
+  const int S = cp_splits((long long)B * chunks, tmax);
+  CpBytes z;
+  z.cp_points = (per_humerus ? n : (size_t)Q) * 24; z.cp_part = n * S * AR_CP_PART_BYTES; z.cp_out = n * sizeof(sh_closest);
+  return {(int)tmax, chunks, S, n, z};
+}
 
 // ---- what is valid against what -----------------------------------------------------------------------------------------------------
 // One member of sh_ctx.  The resident batch is the context's (batch_gen: every upload / commit / store to "verts" takes a new one);
@@ -357,6 +389,15 @@ inline ArthroError precheck_ray_cast(const sh_ray* rays, int R, int per_humerus,
   if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
   const long long i = first_bad_ray(rays, per_humerus ? (size_t)f.B * R : (size_t)R);
   if (i >= 0) return {SH_ERR_ARG, "ray " + std::to_string(i) + " has a non-finite number or a zero direction"};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_closest(const double* points, int Q, int per_humerus, const ArthroFacts& f) {
+  if (!f.ctx || !points || Q < 1 || Q > SH_CLOSEST_MAX) return {SH_ERR_ARG, "bad argument (Q in 1..1048576)"};
+  if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
+  if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
+  const long long i = first_bad_point(points, per_humerus ? (size_t)f.B * Q : (size_t)Q);
+  if (i >= 0) return {SH_ERR_ARG, "point " + std::to_string(i) + " has a coordinate that is not finite"};
   return arthro_ok();
 }
 

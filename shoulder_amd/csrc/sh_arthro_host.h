@@ -1,5 +1,6 @@
 // sh_arthro_host.h -- the entry points of the arthroplasty chain: sh_resect_* (k_resect.h, k_headfit.h, k_seat.h), sh_canal_profile and
-// sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h), and the rays against the resident batch, sh_ray_cast / sh_anp_axis_hits (k_rays.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
+// sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h), the rays against the resident batch, sh_ray_cast / sh_anp_axis_hits (k_rays.h),
+// and its closest surface points, sh_closest_points (k_closest.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
 // headers and inside its extern "C" block.  A header and not a unit of its own: compiled in a unit that holds only the resection
 // headers, the unchanged k_resect_faces takes 100 VGPRs instead of 92, four waves per SIMD instead of five, so the kernels
 // stay in shoulder_hip.hip and the code that launches them with them.
@@ -11,6 +12,7 @@ static_assert(AR_RS_TILE == SH_RS_TILE && AR_HF_WORDS == SH_HF_WORDS && AR_RESEC
 static_assert(AR_CANAL_TILE == SH_CANAL_TILE && AR_PLAN_TILE == SH_PLAN_TILE && AR_PLAN_TOP_BYTES == sizeof(PlanTop) && AR_PLAN_TERM_BYTES == sizeof(PlanTerm),
               "sh_arthro.h: canal and plan tiles, PlanTop, PlanTerm");
 static_assert(AR_RAY_TILE == SH_RAY_TILE && AR_RAY_CHUNK == SH_RAY_CHUNK && AR_RAY_KEY_BYTES == sizeof(RayKey), "sh_arthro.h: ray tile, ray chunk, RayKey");
+static_assert(AR_CP_TILE == SH_CP_TILE && AR_CP_CHUNK == SH_CP_CHUNK && AR_CP_PART_BYTES == sizeof(CpPart), "sh_arthro.h: closest-point tile, chunk, CpPart");
 
 // The named buffers of a call as typed pointers (ARTHRO_BUFS, ARTHRO_INPUT_BUFS), resolved once per call BEHIND the call's
 // arthro_ensure (which may re-allocate them); a buffer that is not there is null.  No window offset: the chain works on the whole batch.
@@ -323,6 +325,42 @@ int sh_anp_axis_hits(sh_ctx* c, int cap, sh_ray_hit* hits, int32_t* counts, int3
   LAUNCH(c, "k_ray_anp_rays", k_ray_anp_rays, dim3((unsigned)((B + 63) / 64)), dim3(64), lm, plane, B, v.ray_rays, v.ray_status);
   if (int rc = ray_run(c, plan, 4, 1, cap, T_obb, (const int*)v.ray_status, hits, counts)) return rc;
   HIPCHK(c, hipMemcpyAsync(status, v.ray_status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- closest surface points of the resident batch (k_closest.h); reads the mesh, changes no state of the chain ----
+#define X(f, name, T, ...) T* f = nullptr;
+struct CpView { ARTHRO_INPUT_BUFS(X) CP_BUFS(X) };
+#undef X
+static CpView cp_view(sh_ctx* c) {
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  CpView v;
+#define X(f, name, T, ...) v.f = (T*)at(name);
+  ARTHRO_INPUT_BUFS(X) CP_BUFS(X)
+#undef X
+  return v;
+}
+static int cp_ensure(sh_ctx* c, const CpBytes& z) {
+  int rc;
+#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
+  CP_BUFS(X)
+#undef X
+  return SH_OK;
+}
+
+int sh_closest_points(sh_ctx* c, const double* points, int Q, int per_humerus, sh_closest* out) {
+  if (const ArthroError e = precheck_closest(points, Q, per_humerus, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_closest_points", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const CpPlan plan = cp_plan(c->B, Q, per_humerus != 0, c->maxF);
+  if (int rc = cp_ensure(c, plan.bytes)) return rc;
+  const CpView v = cp_view(c);
+  HIPCHK(c, hipMemcpyAsync(v.cp_points, points, plan.bytes.cp_points, hipMemcpyHostToDevice, c->stream));
+  LAUNCH(c, "k_cp_walk", k_cp_walk, dim3((unsigned)plan.chunks, (unsigned)c->B, (unsigned)plan.S), dim3(SH_CP_CHUNK), v.verts, v.faces, v.voff, v.foff,
+         (const double*)v.cp_points, Q, per_humerus != 0 ? 1 : 0, plan.S, v.cp_part);
+  LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.verts, v.faces, v.voff, v.foff, (const double*)v.cp_points, Q,
+         per_humerus != 0 ? 1 : 0, plan.S, (const CpPart*)v.cp_part, (long long)plan.points, v.cp_out);
+  if (out) HIPCHK(c, hipMemcpyAsync(out, v.cp_out, plan.bytes.cp_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

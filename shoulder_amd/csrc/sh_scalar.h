@@ -932,6 +932,67 @@ SH_HD bool canal_ray_hit_side(const double* o, const double* d, const double* A,
 }
 // hits of a ray order ascending by (t, face): total, a face is hit once (t is never NaN: it passed t > 1e-9)
 SH_HD bool ray_key_less(double ta, int fa, double tb, int fb) { return ta < tb || (ta == tb && fa < fb); }
+// The closest point of a triangle kept as (A, ab = B - A, ac = C - A) to p (include/shoulder_hip.h sh_closest_points, k_closest.h):
+// the Voronoi-region walk of Ericson, Real-Time Collision Detection 5.1.5, the six dot products and the three products tested in his
+// order -- vertex A, vertex B, edge AB, vertex C, edge CA, edge BC, interior.  bp = ap - ab and cp = ap - ac (B and C are never
+// formed).  The point is q = A + ab u + ac w (tri_point); *region: 0 interior, 1 / 2 / 3 edge AB / BC / CA, 4 / 5 / 6 vertex A / B / C.
+// Returns (p - q) . (p - q).  Every branch but the interior one gives a convex combination by its own guards; the interior branch of a
+// collinear triangle divides by a sum of rounding noise and may return a number that is not finite, which closest_key_less never
+// selects.  Operation by operation the statement of tests/closest_oracle.py (-ffp-contract=off).
+SH_HD void tri_point(const double* A, const double* ab, const double* ac, double u, double w, double* q) {
+  q[0] = (A[0] + ab[0] * u) + ac[0] * w;
+  q[1] = (A[1] + ab[1] * u) + ac[1] * w;
+  q[2] = (A[2] + ab[2] * u) + ac[2] * w;
+}
+SH_HD double closest_pt_tri(const double* p, const double* A, const double* ab, const double* ac, double* u_out, double* w_out, int* region_out) {
+  const double ap[3] = {p[0] - A[0], p[1] - A[1], p[2] - A[2]};
+  const double bp[3] = {ap[0] - ab[0], ap[1] - ab[1], ap[2] - ab[2]};
+  const double cp[3] = {ap[0] - ac[0], ap[1] - ac[1], ap[2] - ac[2]};
+  const double d1 = dot3(ab, ap), d2 = dot3(ac, ap), d3 = dot3(ab, bp), d4 = dot3(ac, bp), d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+  double u, w;
+  int region;
+  if (d1 <= 0 && d2 <= 0) { u = 0.0; w = 0.0; region = 4; }
+  else if (d3 >= 0 && d4 <= d3) { u = 1.0; w = 0.0; region = 5; }
+  else {
+    const double vc = d1 * d4 - d3 * d2;
+    if (vc <= 0 && d1 >= 0 && d3 <= 0) { u = d1 / (d1 - d3); w = 0.0; region = 1; }
+    else if (d6 >= 0 && d5 <= d6) { u = 0.0; w = 1.0; region = 6; }
+    else {
+      const double vb = d5 * d2 - d1 * d6;
+      if (vb <= 0 && d2 >= 0 && d6 <= 0) { u = 0.0; w = d2 / (d2 - d6); region = 3; }
+      else {
+        const double va = d3 * d6 - d5 * d4, e = d4 - d3, g = d5 - d6;
+        if (va <= 0 && e >= 0 && g >= 0) { w = e / (e + g); u = 1.0 - w; region = 2; }
+        else { const double denom = 1.0 / ((va + vb) + vc); u = vb * denom; w = vc * denom; region = 0; }
+      }
+    }
+  }
+  double q[3];
+  tri_point(A, ab, ac, u, w, q);
+  const double r[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+  *u_out = u; *w_out = w; *region_out = region;
+  return dot3(r, r);
+}
+// candidates order by (d2, face): total.  A d2 that is not finite (NaN or infinite) is below nothing and above everything: it never
+// wins, whichever side it stands on
+SH_HD bool closest_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+SH_HD bool closest_key_less(double d2a, int fa, double d2b, int fb) {
+  if (!closest_finite(d2a)) return false;
+  if (!closest_finite(d2b)) return true;
+  return d2a < d2b || (d2a == d2b && fa < fb);
+}
+// the tiles [*t0, *t1) of split s of S of a humerus with `tiles` tiles: consecutive ranges that cover every tile exactly once (empty
+// where S > tiles)
+SH_HD void cp_split_range(int tiles, int S, int s, int* t0, int* t1) {
+  *t0 = (int)(((long long)s * tiles) / S);
+  *t1 = (int)(((long long)(s + 1) * tiles) / S);
+}
+// +1 when p lies on the side of the face its normal ab x ac points to (or in its plane), -1 otherwise; r = p - q
+SH_HD int closest_side(const double* r, const double* ab, const double* ac) {
+  double n[3];
+  cross3(ab, ac, n);
+  return dot3(r, n) >= 0 ? 1 : -1;
+}
 // The levels a face with frame heights [zmin, zmax] can be hit at, z_l = z0 - l dz: z_l in [zmin, zmax] <=> (z0 - zmax) / dz <= l
 // <= (z0 - zmin) / dz, rounded outwards and widened by one level each side (the full test decides), clamped to [0, L - 1];
 // empty: *lo > *hi.  A superset of what canal_ray_hit accepts, never less.

@@ -16,6 +16,7 @@
 #include "k_stem.h"
 #include "k_plan.h"
 #include "k_rays.h"
+#include "k_closest.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -481,6 +482,14 @@ static int stl_enqueue_emit(sh_ctx* timed, hipStream_t st, int B, const StlPlan&
 }
 #undef STL_LAUNCH
 
+// "cp.out" (sh_closest_points) answers for the batch it was asked about: a new batch removes it
+static void drop_closest(sh_ctx* c) {
+  auto it = c->bufs.find("cp.out");
+  if (it == c->bufs.end()) return;
+  if (it->second.p) (void)hipFree(it->second.p);
+  c->bufs.erase(it);
+}
+
 // Where the meshes of a batch that becomes resident are: host arrays to upload (sh_upload_meshes) | `fill` writes "verts" / "faces" on
 // the context's stream once they and the offsets are in place (STL, synth) | `staged`: the ".s" side holds them, swap it in.
 struct ResidentSource { const float* verts = nullptr; const int32_t* faces = nullptr; std::function<int()> fill; bool staged = false; };
@@ -492,6 +501,7 @@ static int make_resident(sh_ctx* c, int B, const MeshSizes& sz, std::vector<long
   if (src.staged) for (const char* nm : names) std::swap(c->bufs[nm], c->bufs[std::string(nm) + ".s"]);      // (the staged batch's own thread keeps running)
   else { discard_staged(c); (void)join_prepared(c); }      // (sh_upload_stl dropped a staged batch already, before it took the stl.* scratch: nothing left to do for it here)
   ++c->batch_gen;      // hulls prepared for the previous batch are void
+  drop_closest(c);
   c->B = 0;
   c->h_voff.swap(voff); c->h_foff.swap(foff);
   c->sumV = sz.sumV; c->sumF = sz.sumF; c->maxV = sz.maxV; c->maxF = sz.maxF;
@@ -632,7 +642,7 @@ int sh_store(sh_ctx* c, const char* name, const void* host, size_t nbytes) {
   if (it == c->bufs.end()) return fail(c, SH_ERR_ARG, std::string("no buffer named ") + name);
   if (nbytes > it->second.bytes) return fail(c, SH_ERR_ARG, std::string("sh_store: size exceeds buffer ") + name);
   HIPCHK(c, hipSetDevice(c->device));
-  if (std::string(name) == "verts") { discard_staged(c); (void)join_prepared(c); ++c->batch_gen; c->h_verts_valid = false; }
+  if (std::string(name) == "verts") { discard_staged(c); (void)join_prepared(c); ++c->batch_gen; c->h_verts_valid = false; drop_closest(c); }
   c->ovf_none_gen = ~0ull;      // (an injected frame or intermediate moves the planes: the overflow tier runs again)
   if (std::string(name) == "params") params_changed(c);
   HIPCHK(c, hipMemcpyAsync(it->second.p, host, nbytes, hipMemcpyHostToDevice, c->stream));

@@ -611,6 +611,21 @@ class Engine:
         self._chk(self.L.sh_anp_axis_hits(self.h, cap, _ptr(hits), _ptr(counts), _ptr(status)))
         return hits, counts, status[: self.B]
 
+    # ---- closest surface points of the resident batch (include/shoulder_hip.h sh_closest_points) -------------------------------
+    def closest_points(self, points):
+        """The closest point of every resident humerus to every query point -> a structured array (B, Q) of _lib.CLOSEST_DTYPE: dist,
+        point (CT), face (humerus-local), region (0 interior, 1 / 2 / 3 edge AB / BC / CA, 4 / 5 / 6 vertex A / B / C of that face), side
+        (+1 on the side the winning face's normal points to) and status.  points: (Q, 3), shared by all humeri, or (B, Q, 3), in CT.
+        Among faces at the same distance the smallest face id wins.  A call costs what a multiple of 256 points costs."""
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
+            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
+        Q, per = p.shape[-2], int(p.ndim == 3)
+        ok = 1 <= Q <= _lib.CLOSEST_MAX      # (the library reports the rest; nothing is sized by it here)
+        out = np.zeros((self.B, Q) if ok else (0,), dtype=_lib.CLOSEST_DTYPE)
+        self._chk(self.L.sh_closest_points(self.h, _ptr(p), Q, per, _ptr(out)))
+        return out
+
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):
         n, e = ctypes.c_size_t(), ctypes.c_int()
