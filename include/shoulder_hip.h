@@ -662,7 +662,7 @@ int sh_anp_axis_hits(sh_ctx*, int cap, sh_ray_hit* hits /* B x 4 x cap, host, nu
  *             side = +1 when (p - point) . (ab x ac) >= 0 and -1 otherwise.  With region == 0 side says outside (+1) or inside (-1) a
  *             mesh whose normals point outward.  For an edge or a vertex winner it is the WINNING FACE's verdict, which can be wrong at
  *             sharp or saddle features (Baerentzen & Aanaes, Signed distance computation using the angle weighted pseudonormal, 2005);
- *             a robust inside test (parity, winding number) is not part of this call.
+ *             a robust inside test (parity, winding number) is sh_winding_numbers, below.
  *             status 0; SH_ERR_GEOMETRY (the kernels' SH_ERR_GEOMETRY_DEV) with face = -1 and every other field zero when no face of the humerus gave a finite d2.
  * A (humerus, point) result depends on that mesh and that point alone: not on B, the humerus' position in the batch, Q, the point's
  * place in the list, or how the faces were split or tiled.  No floating-point atomics, no floating-point sums across lanes.
@@ -675,6 +675,39 @@ int sh_anp_axis_hits(sh_ctx*, int cap, sh_ray_hit* hits /* B x 4 x cap, host, nu
 typedef struct sh_closest { double dist; double point[3]; int32_t face, region, side, status; } sh_closest;   /* 48 B */
 int sh_closest_points(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when per_humerus; CT */, int Q, int per_humerus,
                       sh_closest* out /* B x Q, host, nullable */);
+
+/* ---- generalized winding numbers of the resident batch: inside tests --------------------------------------------------------------
+ * The counterpart of `mesh.contains(points)`, and with sh_closest_points of `trimesh.proximity.signed_distance`: for Q query points,
+ * shared by all humeri or Q per humerus, the generalized winding number (Jacobson, Kavan, Sorkine-Hornung, Robust inside-outside
+ * segmentation using generalized winding numbers, 2013) of each of the B resident meshes, in one device pass (k_winding.h).  Every face
+ * contributes: no cull, no far-field approximation.
+ *   rule      sh_scalar.h solid_angle_tri (Van Oosterom & Strackee 1983) on the resident float32 corners widened to float64: with
+ *             a = A - p, b = B - p, c = C - p and la, lb, lc their lengths (sqrt of dot3),
+ *               num = a . (b x c)      den = ((la lb) lc + (a . b) lc) + ((a . c) lb + (b . c) la)      omega = 2.0 atan2(num, den),
+ *             and omega = 0 when num == 0.0 (either zero): a point in the plane of a face gets nothing from that face.
+ *   sum       w = (sum over blocks (sum over the faces of the block omega_f)) / (4 pi).  A block is SH_WIND_BLOCK = 2048 consecutive
+ *             faces; a block sum starts at 0 and adds its faces in face order; the block sums are added in block order, starting at
+ *             0; 4 pi is 4.0 * M_PI.  This one summation tree is part of the definition: it does not depend on B, Q, the launch shape
+ *             or the face split.  No floating-point atomics, no floating-point sums across lanes.
+ *   sh_winding (16 B)  winding = w.  On a closed, consistently oriented mesh w is an integer up to rounding (1 inside a mesh whose
+ *             normals point outward, -1 inside one stored inside-out, 0 outside, 0 in a cavity whose wall faces inward, 2 inside a mesh
+ *             stored twice); on an open mesh it is a fraction.  inside = 1 when |w| >= 0.5, else 0: the non-zero rule of
+ *             sh_seat.center_inside, so a mesh stored inside-out still answers "inside".  ON THE SURFACE ITSELF w is about 0.5 and
+ *             inside is undefined.  status 0; SH_ERR_GEOMETRY (the kernels' SH_ERR_GEOMETRY_DEV) with winding = 0 and inside = 0 when
+ *             the sum is not finite (a point 1e200 mm away along a diagonal: the products of b x c overflow to inf - inf.  Along one
+ *             axis only the lengths overflow: den is +inf, every term is 0 and w = 0 with status 0, the right answer out there).
+ * A (humerus, point) result depends on that mesh and that point alone, byte for byte.  The device's atan2 is its math library's: against
+ * another library's the sum differs within (2 F + 16) 2^-53 max(1, sum |omega_f| / 4 pi), F the faces.
+ *
+ * Arguments in this order: the context, points != NULL and Q in 1..SH_WINDING_MAX (SH_ERR_ARG); a resident batch and no runs in flight
+ * (SH_ERR_STATE; a run is not needed); every coordinate finite (SH_ERR_ARG).  SH_ERR_NOMEM when the results or the partials do not fit.
+ * The results stay resident in the named buffer "wn.out" (B x Q sh_winding) until the next upload / commit / sh_store("verts"), which
+ * removes it.  The call changes nothing else: the records of a run and the buffers of the arthroplasty chain keep their bytes. */
+#define SH_WINDING_MAX 1048576
+#define SH_WIND_BLOCK 2048
+typedef struct sh_winding { double winding; int32_t inside, status; } sh_winding;   /* 16 B */
+int sh_winding_numbers(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when per_humerus; CT */, int Q, int per_humerus,
+                       sh_winding* out /* B x Q, host, nullable */);
 
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"

@@ -252,6 +252,20 @@ CLOSEST_DTYPE = np.dtype([("dist", "<f8"), ("point", "<f8", (3,)), ("face", "<i4
 assert CLOSEST_DTYPE.itemsize == ctypes.sizeof(Closest) == 48
 
 
+WINDING_MAX = 1048576
+WIND_BLOCK = 2048
+
+
+class Winding(ctypes.Structure):
+    """sh_winding: the generalized winding number of one humerus about one query point, inside = 1 when |winding| >= 0.5 (undefined on
+    the surface itself, where winding is about 0.5), status 0 or SH_ERR_GEOMETRY with zeros when the sum was not finite."""
+    _fields_ = [("winding", ctypes.c_double), ("inside", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+WINDING_DTYPE = np.dtype([("winding", "<f8"), ("inside", "<i4"), ("status", "<i4")])
+assert WINDING_DTYPE.itemsize == ctypes.sizeof(Winding) == 16
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -267,7 +281,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
            "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan",
-           "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points"]
+           "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points", "sh_winding_numbers"]
 
 _lib = None
 
@@ -374,5 +388,7 @@ def load(build_if_missing=True):
         L.sh_anp_axis_hits.argtypes = [vp, ctypes.c_int, vp, vp, vp]
     if not alt or hasattr(L, "sh_closest_points"):      # (tools/time_closest.py and the benchmark's parent arm)
         L.sh_closest_points.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
+    if not alt or hasattr(L, "sh_winding_numbers"):      # (tools/time_winding.py and the benchmark's parent arm)
+        L.sh_winding_numbers.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
     _lib = L
     return L

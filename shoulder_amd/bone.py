@@ -457,14 +457,19 @@ class ProximalHumerus(Bone):
         return loc, np.nonzero(keep)[0], np.array(hits[0]["face"][keep], dtype=np.int64)
 
     # -- closest surface points ---------------------------------------------------------------------------------
-    def _closest_ct(self, points):
-        """the records of Engine.closest_points for points given in the CURRENT coordinate system, and the current matrix"""
+    def _points_ct(self, points):
+        """points given in the CURRENT coordinate system -> (the points in CT, the current matrix); the bone is resident afterwards"""
         p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         if len(p) < 1:
             raise ValueError("points must have shape (n, 3), n >= 1")
         T = np.array(self._tfrm.matrix, dtype=np.float64)
         self._ensure_loaded()
-        return self._engine.closest_points(self._engine.transform_points(p, np.linalg.inv(T)))[0], T
+        return self._engine.transform_points(p, np.linalg.inv(T)), T
+
+    def _closest_ct(self, points):
+        """the records of Engine.closest_points for points given in the CURRENT coordinate system, and the current matrix"""
+        p, T = self._points_ct(points)
+        return self._engine.closest_points(p)[0], T
 
     def closest_point(self, points):
         """`trimesh.proximity.closest_point(mesh, points)` in the CURRENT coordinate system on the device (Engine.closest_points):
@@ -486,6 +491,27 @@ class ProximalHumerus(Bone):
         d = self.closest_point(pts)[1]
         return dict(mean=float(d.mean()), rms=float(np.sqrt(np.mean(d * d))), max=float(d.max()), p95=float(np.percentile(d, 95)),
                     n=int(len(d)), argmax=int(np.argmax(d)))
+
+    # -- inside tests: generalized winding numbers -------------------------------------------------------------
+    def winding_number(self, points):
+        """The generalized winding number of the mesh about `points` (n, 3) in the CURRENT coordinate system -> float64 (n,), on the
+        device (Engine.winding_numbers).  1 inside and 0 outside a closed bone; an OPEN mesh (a half from `resect_mesh()` has no cap)
+        returns a fraction; a CAVITY whose wall faces inward returns 0; on the surface itself the value is about 0.5."""
+        rec = self._engine.winding_numbers(self._points_ct(points)[0])[0]
+        if np.any(rec["status"] != 0):
+            raise ValueError(f"winding_number failed with status {int(rec['status'][rec['status'] != 0][0])}: a sum is not finite")
+        return np.array(rec["winding"])
+
+    def contains(self, points):
+        """`mesh.contains(points)` in the CURRENT coordinate system -> bool (n,): |winding_number| >= 0.5.  An open mesh answers by its
+        thresholded fraction, a cavity whose wall faces inward is outside, and a point on the surface itself is undefined."""
+        return self._engine.contains(self._points_ct(points)[0])[0]
+
+    def signed_distance(self, points):
+        """`trimesh.proximity.signed_distance(mesh, points)` in the CURRENT coordinate system -> float64 (n,): the distance to the
+        surface, POSITIVE INSIDE and negative outside (the transforms are rigid: the distance is CT's).  Open meshes, cavities and
+        the surface itself as in `contains`."""
+        return self._engine.signed_distance(self._points_ct(points)[0])[0]
 
     # -- coordinate systems (bone.py:53-105, :146-157) --------------------------------------------------
     def _mesh_in(self, T):

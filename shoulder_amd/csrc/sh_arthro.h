@@ -43,6 +43,8 @@ namespace sh {
   X(ray_hits, "ray.hits", sh_ray_hit, 8) X(ray_blockhit, "ray.blockhit", int, 4)
 // the closest surface points (sh_closest_points) are no link of the chain either
 #define CP_BUFS(X) X(cp_points, "cp.points", double, 8) X(cp_part, "cp.part", CpPart, 8) X(cp_out, "cp.out", sh_closest, 8)
+// nor are the generalized winding numbers (sh_winding_numbers)
+#define WN_BUFS(X) X(wn_points, "wn.points", double, 8) X(wn_part, "wn.part", double, 8) X(wn_out, "wn.out", sh_winding, 8)
 // what the chain reads and does not own (the mesh: upload / commit; the records of a run: alloc_batch): X(field, "name", type)
 #define ARTHRO_INPUT_BUFS(X)                                                                                                       \
   X(verts, "verts", const float) X(faces, "faces", const int) X(voff, "voff", const long long) X(foff, "foff", const long long)    \
@@ -53,6 +55,7 @@ namespace sh {
 struct ArthroBytes { ARTHRO_BUFS(X) };
 struct RayBytes { RAY_BUFS(X) };
 struct CpBytes { CP_BUFS(X) };
+struct WnBytes { WN_BUFS(X) };
 #undef X
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
@@ -62,6 +65,8 @@ constexpr int AR_PLAN_TOP_BYTES = 16, AR_PLAN_TERM_BYTES = 16;                  
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
 constexpr int AR_CP_TILE = 256, AR_CP_CHUNK = 256, AR_CP_PART_BYTES = 16;         // SH_CP_TILE, SH_CP_CHUNK, sizeof(CpPart)
 constexpr int AR_CP_FILL = 1024;      // workgroups of k_cp_walk that fill the chip: four of 256 lanes on each of 256 compute units
+constexpr int AR_WN_TILE = 256, AR_WN_CHUNK = 256, AR_WN_BLOCK = 2048;            // SH_WN_TILE, SH_WN_CHUNK, SH_WIND_BLOCK
+constexpr int AR_WN_FILL = 1024;      // workgroups of k_wn_walk that fill the chip, as AR_CP_FILL
 
 struct ArthroError { int code; std::string text; };      // code SH_OK: accepted (text empty)
 inline ArthroError arthro_ok() { return {SH_OK, std::string()}; }
@@ -266,6 +271,29 @@ inline CpPlan cp_plan(int B, int Q, bool per_humerus, long long maxF) {
   return {(int)tmax, chunks, S, n, z};
 }
 
+// Winding numbers, Q per humerus.  The grid of k_wn_walk is (chunks of 256 points, B, S splits): split s of a humerus with K blocks of
+// AR_WN_BLOCK faces walks the blocks cp_split_range(K, S, s) (sh_scalar.h) -- whole blocks, a split never cuts one, because the block
+// sums are the fixed inner level of the summation tree.  S is the host's choice and no knob: as many splits as bring the grid to
+// AR_WN_FILL workgroups when B x chunks is small, never more than the blocks of the largest humerus, at least one.  With S == 1 a
+// workgroup owns all blocks of its humerus and adds the block sums itself, in block order ("wn.part" holds one total per point);
+// with S > 1 "wn.part" holds the block sums (kmax per point) and k_wn_join adds them in the same order.  S changes no byte.
+inline int wn_splits(long long groups /* B x chunks */, long long blocks /* of the largest humerus */) {
+  const long long g = groups > 1 ? groups : 1, want = (AR_WN_FILL + g - 1) / g;
+  const long long s = want < blocks ? want : blocks;
+  return (int)(s > 1 ? s : 1);
+}
+struct WnPlan { int kmax, chunks, S, stride; size_t points; WnBytes bytes; };      // blocks of the largest humerus, point chunks, splits, doubles of "wn.part" per point, B x Q
+inline WnPlan wn_plan(int B, int Q, bool per_humerus, long long maxF) {
+  const size_t n = (size_t)B * Q;
+  const long long kmax = tiles_of(maxF, AR_WN_BLOCK);
+  const int chunks = (Q + AR_WN_CHUNK - 1) / AR_WN_CHUNK;
+  const int S = wn_splits((long long)B * chunks, kmax);
+  const int stride = S == 1 ? 1 : (int)kmax;
+  WnBytes z;
+  z.wn_points = (per_humerus ? n : (size_t)Q) * 24; z.wn_part = n * stride * sizeof(double); z.wn_out = n * sizeof(sh_winding);
+  return {(int)kmax, chunks, S, stride, n, z};
+}
+
 // ---- what is valid against what -----------------------------------------------------------------------------------------------------
 // One member of sh_ctx.  The resident batch is the context's (batch_gen: every upload / commit / store to "verts" takes a new one);
 // the queries take it as an argument.  RULE: void first, commit on success -- a *_begin voids what the call is about to overwrite and
@@ -394,6 +422,15 @@ inline ArthroError precheck_ray_cast(const sh_ray* rays, int R, int per_humerus,
 
 inline ArthroError precheck_closest(const double* points, int Q, int per_humerus, const ArthroFacts& f) {
   if (!f.ctx || !points || Q < 1 || Q > SH_CLOSEST_MAX) return {SH_ERR_ARG, "bad argument (Q in 1..1048576)"};
+  if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
+  if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
+  const long long i = first_bad_point(points, per_humerus ? (size_t)f.B * Q : (size_t)Q);
+  if (i >= 0) return {SH_ERR_ARG, "point " + std::to_string(i) + " has a coordinate that is not finite"};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_winding(const double* points, int Q, int per_humerus, const ArthroFacts& f) {
+  if (!f.ctx || !points || Q < 1 || Q > SH_WINDING_MAX) return {SH_ERR_ARG, "bad argument (Q in 1..1048576)"};
   if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
   if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
   const long long i = first_bad_point(points, per_humerus ? (size_t)f.B * Q : (size_t)Q);

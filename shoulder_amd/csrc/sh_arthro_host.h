@@ -1,6 +1,6 @@
 // sh_arthro_host.h -- the entry points of the arthroplasty chain: sh_resect_* (k_resect.h, k_headfit.h, k_seat.h), sh_canal_profile and
 // sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h), the rays against the resident batch, sh_ray_cast / sh_anp_axis_hits (k_rays.h),
-// and its closest surface points, sh_closest_points (k_closest.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
+// its closest surface points, sh_closest_points (k_closest.h), and its winding numbers, sh_winding_numbers (k_winding.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
 // headers and inside its extern "C" block.  A header and not a unit of its own: compiled in a unit that holds only the resection
 // headers, the unchanged k_resect_faces takes 100 VGPRs instead of 92, four waves per SIMD instead of five, so the kernels
 // stay in shoulder_hip.hip and the code that launches them with them.
@@ -13,6 +13,7 @@ static_assert(AR_CANAL_TILE == SH_CANAL_TILE && AR_PLAN_TILE == SH_PLAN_TILE && 
               "sh_arthro.h: canal and plan tiles, PlanTop, PlanTerm");
 static_assert(AR_RAY_TILE == SH_RAY_TILE && AR_RAY_CHUNK == SH_RAY_CHUNK && AR_RAY_KEY_BYTES == sizeof(RayKey), "sh_arthro.h: ray tile, ray chunk, RayKey");
 static_assert(AR_CP_TILE == SH_CP_TILE && AR_CP_CHUNK == SH_CP_CHUNK && AR_CP_PART_BYTES == sizeof(CpPart), "sh_arthro.h: closest-point tile, chunk, CpPart");
+static_assert(AR_WN_TILE == SH_WN_TILE && AR_WN_CHUNK == SH_WN_CHUNK && AR_WN_BLOCK == SH_WIND_BLOCK, "sh_arthro.h: winding tile, chunk, block");
 
 // The named buffers of a call as typed pointers (ARTHRO_BUFS, ARTHRO_INPUT_BUFS), resolved once per call BEHIND the call's
 // arthro_ensure (which may re-allocate them); a buffer that is not there is null.  No window offset: the chain works on the whole batch.
@@ -361,6 +362,42 @@ int sh_closest_points(sh_ctx* c, const double* points, int Q, int per_humerus, s
   LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.verts, v.faces, v.voff, v.foff, (const double*)v.cp_points, Q,
          per_humerus != 0 ? 1 : 0, plan.S, (const CpPart*)v.cp_part, (long long)plan.points, v.cp_out);
   if (out) HIPCHK(c, hipMemcpyAsync(out, v.cp_out, plan.bytes.cp_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- generalized winding numbers of the resident batch (k_winding.h); reads the mesh, changes no state of the chain ----
+#define X(f, name, T, ...) T* f = nullptr;
+struct WnView { ARTHRO_INPUT_BUFS(X) WN_BUFS(X) };
+#undef X
+static WnView wn_view(sh_ctx* c) {
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  WnView v;
+#define X(f, name, T, ...) v.f = (T*)at(name);
+  ARTHRO_INPUT_BUFS(X) WN_BUFS(X)
+#undef X
+  return v;
+}
+static int wn_ensure(sh_ctx* c, const WnBytes& z) {
+  int rc;
+#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
+  WN_BUFS(X)
+#undef X
+  return SH_OK;
+}
+
+int sh_winding_numbers(sh_ctx* c, const double* points, int Q, int per_humerus, sh_winding* out) {
+  if (const ArthroError e = precheck_winding(points, Q, per_humerus, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_winding_numbers", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const WnPlan plan = wn_plan(c->B, Q, per_humerus != 0, c->maxF);
+  if (int rc = wn_ensure(c, plan.bytes)) return rc;
+  const WnView v = wn_view(c);
+  HIPCHK(c, hipMemcpyAsync(v.wn_points, points, plan.bytes.wn_points, hipMemcpyHostToDevice, c->stream));
+  LAUNCH(c, "k_wn_walk", k_wn_walk, dim3((unsigned)plan.chunks, (unsigned)c->B, (unsigned)plan.S), dim3(SH_WN_CHUNK), v.verts, v.faces, v.voff, v.foff,
+         (const double*)v.wn_points, Q, per_humerus != 0 ? 1 : 0, plan.S, plan.stride, v.wn_part);
+  LAUNCH(c, "k_wn_join", k_wn_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.foff, Q, plan.S, plan.stride, (const double*)v.wn_part,
+         (long long)plan.points, v.wn_out);
+  if (out) HIPCHK(c, hipMemcpyAsync(out, v.wn_out, plan.bytes.wn_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -993,6 +993,34 @@ SH_HD int closest_side(const double* r, const double* ab, const double* ac) {
   cross3(ab, ac, n);
   return dot3(r, n) >= 0 ? 1 : -1;
 }
+// The signed solid angle of the triangle (A, B, C) seen from p (include/shoulder_hip.h sh_winding_numbers, k_winding.h), Van Oosterom &
+// Strackee, The solid angle of a plane triangle, 1983: with a = A - p, b = B - p, c = C - p, la = sqrt(a . a), lb, lc alike,
+//   num = a . (b x c)          den = ((la * lb) * lc + (a . b) * lc) + ((a . c) * lb + (b . c) * la)          omega = 2.0 * atan2(num, den)
+// in exactly this parenthesisation (dot3 and cross3 of sh_common.h), and omega = 0 when num == 0.0, whatever the sign of the zero and
+// whatever den is: a point in the plane of a face gets nothing from that face.  Positive when p sees the corners clockwise, i.e. from
+// behind a face whose normal (B - A) x (C - A) points away from p: a point inside an outward-oriented closed mesh collects + 4 pi.
+// Operation by operation the statement of tests/winding_oracle.py (-ffp-contract=off); atan2 is the math library's.
+SH_HD void solid_angle_terms(const double* p, const double* A, const double* B, const double* C, double* num, double* den) {
+  const double a[3] = {A[0] - p[0], A[1] - p[1], A[2] - p[2]};
+  const double b[3] = {B[0] - p[0], B[1] - p[1], B[2] - p[2]};
+  const double c[3] = {C[0] - p[0], C[1] - p[1], C[2] - p[2]};
+  const double la = sqrt(dot3(a, a)), lb = sqrt(dot3(b, b)), lc = sqrt(dot3(c, c));
+  double bc[3];
+  cross3(b, c, bc);
+  *num = dot3(a, bc);
+  *den = ((la * lb) * lc + dot3(a, b) * lc) + (dot3(a, c) * lb + dot3(b, c) * la);
+}
+SH_HD double solid_angle_tri(const double* p, const double* A, const double* B, const double* C) {
+  double num, den;
+  solid_angle_terms(p, A, B, C, &num, &den);
+  return num == 0.0 ? 0.0 : 2.0 * atan2(num, den);
+}
+// the sum of the solid angles -> winding number, inside, status (the statement of k_wn_join): 4 pi is 4.0 * M_PI
+SH_HD void winding_record(double sum, double* winding, int* inside, int* status, int err_geometry) {
+  if (!(fabs(sum) <= 1.7976931348623157e308)) { *winding = 0.0; *inside = 0; *status = err_geometry; return; }      // (not finite)
+  const double w = sum / (4.0 * M_PI);
+  *winding = w; *inside = fabs(w) >= 0.5 ? 1 : 0; *status = 0;
+}
 // The levels a face with frame heights [zmin, zmax] can be hit at, z_l = z0 - l dz: z_l in [zmin, zmax] <=> (z0 - zmax) / dz <= l
 // <= (z0 - zmin) / dz, rounded outwards and widened by one level each side (the full test decides), clamped to [0, L - 1];
 // empty: *lo > *hi.  A superset of what canal_ray_hit accepts, never less.

@@ -17,6 +17,7 @@
 #include "k_plan.h"
 #include "k_rays.h"
 #include "k_closest.h"
+#include "k_winding.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -482,12 +483,14 @@ static int stl_enqueue_emit(sh_ctx* timed, hipStream_t st, int B, const StlPlan&
 }
 #undef STL_LAUNCH
 
-// "cp.out" (sh_closest_points) answers for the batch it was asked about: a new batch removes it
+// "cp.out" (sh_closest_points) and "wn.out" (sh_winding_numbers) answer for the batch they were asked about: a new batch removes them
 static void drop_closest(sh_ctx* c) {
-  auto it = c->bufs.find("cp.out");
-  if (it == c->bufs.end()) return;
-  if (it->second.p) (void)hipFree(it->second.p);
-  c->bufs.erase(it);
+  for (const char* name : {"cp.out", "wn.out"}) {
+    auto it = c->bufs.find(name);
+    if (it == c->bufs.end()) continue;
+    if (it->second.p) (void)hipFree(it->second.p);
+    c->bufs.erase(it);
+  }
 }
 
 // Where the meshes of a batch that becomes resident are: host arrays to upload (sh_upload_meshes) | `fill` writes "verts" / "faces" on

@@ -626,6 +626,43 @@ class Engine:
         self._chk(self.L.sh_closest_points(self.h, _ptr(p), Q, per, _ptr(out)))
         return out
 
+    # ---- generalized winding numbers of the resident batch (include/shoulder_hip.h sh_winding_numbers) --------------------------
+    def winding_numbers(self, points):
+        """The generalized winding number of every resident humerus about every query point -> a structured array (B, Q) of
+        _lib.WINDING_DTYPE: winding, inside (1 when |winding| >= 0.5) and status.  points: (Q, 3), shared by all humeri, or (B, Q, 3),
+        in CT.  A closed mesh with outward normals gives 1 inside and 0 outside (up to rounding), one stored inside-out -1 inside; an
+        OPEN mesh gives a fraction (a cube without one of its six sides: 5/6 at its centre); a CAVITY whose wall faces inward gives 0.
+        ON THE SURFACE ITSELF the winding number is about 0.5 and `inside` is undefined.  Every face contributes (no approximation);
+        a call costs what a multiple of 256 points costs."""
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
+            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
+        Q, per = p.shape[-2], int(p.ndim == 3)
+        ok = 1 <= Q <= _lib.WINDING_MAX      # (the library reports the rest; nothing is sized by it here)
+        out = np.zeros((self.B, Q) if ok else (0,), dtype=_lib.WINDING_DTYPE)
+        self._chk(self.L.sh_winding_numbers(self.h, _ptr(p), Q, per, _ptr(out)))
+        return out
+
+    def contains(self, points):
+        """`mesh.contains(points)` for every resident humerus -> bool (B, Q): |winding number| >= 0.5 (Engine.winding_numbers).  True
+        in the solid of a closed mesh whichever way it is oriented, False outside it and in a cavity whose wall faces inward; for an
+        open mesh the threshold cuts a graded answer; undefined for a point on the surface itself.  Raises when a sum was not finite."""
+        rec = self.winding_numbers(points)
+        if np.any(rec["status"] != 0):
+            raise ShoulderHipError(int(rec["status"][rec["status"] != 0][0]), "contains: a winding number is not finite (a point too far away)")
+        return rec["inside"] != 0
+
+    def signed_distance(self, points):
+        """`trimesh.proximity.signed_distance(mesh, points)` for every resident humerus -> float64 (B, Q): the distance to the surface
+        (Engine.closest_points), POSITIVE INSIDE and negative outside (Engine.contains).  Two device calls joined here.  For an open
+        mesh the sign is the thresholded fraction, in a cavity whose wall faces inward it is negative, and on the surface itself the
+        value is 0 up to rounding with an undefined sign."""
+        inside = self.contains(points)
+        rec = self.closest_points(points)
+        if np.any(rec["status"] != 0):
+            raise ShoulderHipError(int(rec["status"][rec["status"] != 0][0]), "signed_distance: no face of a mesh gave a finite distance")
+        return np.where(inside, rec["dist"], -rec["dist"])
+
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):
         n, e = ctypes.c_size_t(), ctypes.c_int()
