@@ -709,6 +709,63 @@ typedef struct sh_winding { double winding; int32_t inside, status; } sh_winding
 int sh_winding_numbers(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when per_humerus; CT */, int Q, int per_humerus,
                        sh_winding* out /* B x Q, host, nullable */);
 
+/* ---- rigid registration of point sets onto the resident batch (ICP) ----------------------------------------------------------------
+ * The counterpart of `trimesh.registration.icp(points, mesh)` / `mesh.register`: for B humeri x Q points, up to max_iter rigid ICP
+ * iterations per humerus, the whole loop on the device (k_icp.h, with the unchanged k_cp_walk / k_cp_join), one transform per humerus
+ * with its evidence.  ICP is LOCAL: it needs an initial pose inside its basin of convergence; no global search is made.
+ *   options   metric SH_ICP_POINT (Horn's closed form per iteration, linear convergence) or SH_ICP_PLANE (linearised point-to-plane,
+ *             quadratic near the solution); max_iter in 1..64; reject in mm, > 0, +inf accepts every pair; tol >= 0, 0 runs every
+ *             iteration.
+ *   T0        B x 16 row-major CT -> CT, NULL for the identity.  Must be rigid: last row exactly (0, 0, 0, 1), |R^T R - I|_inf <= 1e-9
+ *             (the 1e-9 is part of the definition), det > 0.
+ * ONE EVALUATION k = 0 .. max_iter of humerus b at its current T (everything float64, -ffp-contract=off; sh_scalar.h):
+ *   move      p'_i = T p_i, row r: ((T[4r] x + T[4r+1] y) + T[4r+2] z) + T[4r+3] (canal_map_point).
+ *   pair      the sh_closest of p'_i on mesh b, the rule of sh_closest_points unchanged (ties to the smallest face id).
+ *             e_i = q_i - p'_i, e2_i = dot3(e_i, e_i).  ACCEPTED when its status is 0 and sqrt(e2_i) <= reject.  Plane metric:
+ *             n_i = (ab x ac) / sqrt(dot3(ab x ac, ab x ac)) of the winning face whatever the region; a face of zero area is not accepted.
+ *   sum       a pair that is not accepted contributes +0.0 to every term.  THE TREE IS PART OF THE DEFINITION: points in blocks of
+ *             SH_ICP_BLOCK = 256 consecutive indices; in a block slot[i] += slot[i + h] for h = 128, 64, .., 1 (missing points of the
+ *             last block are +0.0); the block sums added in block order starting at 0.0.  No floating-point atomics, nothing that
+ *             depends on B, the launch shape or the split of the walk.  Terms: n, sum e2; point metric sum p', sum q, sum p'_i q_j
+ *             (9); plane metric, with d_i = p'_i - c, J_i = (d_i x n_i, n_i), r_i = dot3(e_i, n_i): the 21 upper terms of sum J J^T
+ *             and the 6 of sum J r.  The pivot c = T cbar, cbar = (sum p_i) / Q over ALL Q input points of the humerus by the same
+ *             tree, once, before the first evaluation.
+ *   report    rms_k = sqrt(sum e2 / n) (0 when n = 0), pairs_k = n.
+ *   stop/step in this order: k > 0 and |rms_{k-1} - rms_k| <= tol: converged = 1, stop; k == max_iter: stop; n < 6 or the solve fails:
+ *             SH_ERR_GEOMETRY, stop; else T <- (dR, dt) T (icp_compose).  The reported rms and pairs always belong to the returned T:
+ *             no update is applied after the last evaluation, and after a failure T is the transform that evaluation was made at
+ *             (T0 when the first one failed).
+ *   solve, point   icp_horn_solve: pbar = sum p' / n, qbar = sum q / n, S_ij = sum p'_i q_j - (sum p'_i) qbar_j, Horn's symmetric 4 x 4,
+ *             its largest eigenvector by sym4_jacobi (12 cyclic sweeps, pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3),
+ *             t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)); among equal eigenvalues the first), the quaternion normalised with
+ *             w >= 0, dt = qbar - R pbar.  A matrix that is not finite is a failure.
+ *   solve, plane   chol6_solve: Cholesky of the 6 x 6 in index order; a pivot <= 0 or not finite is a failure.  x = (w, t); dR is the
+ *             rotation of the quaternion (1, w / 2) normalised (no sin, no cos: the chain is + - x / sqrt), dt = (c - dR c) + t.
+ *             min_pivot = min_j (L_jj^2 / A_jj) of the LAST solve made, in (0, 1]: small where the target lets the points slide (a
+ *             plane, a sphere, a cylinder).  ONLY EXACT SINGULARITY IS A STATUS; a nearly singular system is solved and shows in
+ *             min_pivot alone.  1.0 under the point metric and before any solve.
+ *   sh_registration (168 B)  T; rms, pairs of the last evaluation; rms_first of evaluation 0; min_pivot; iterations, the number of
+ *             updates applied; converged; status 0 or SH_ERR_GEOMETRY.  history (optional): B x (max_iter + 1) x (rms, pairs), row k
+ *             of every evaluation made, zeros behind.
+ * A result for (humerus, point set, T0, options) depends on those alone, byte for byte: not on B, the humerus' place, shared or
+ * per-humerus points, or the walk's split.
+ *
+ * Arguments in this order: the context and the pointers points and options (SH_ERR_ARG); Q in 1..SH_CLOSEST_MAX; the options;
+ * a resident batch and no runs in flight (SH_ERR_STATE; a run is not needed); every coordinate finite, naming the first bad point; T0,
+ * naming the humerus (all SH_ERR_ARG).  SH_ERR_NOMEM when the buffers do not fit.  Resident afterwards: "icp.out" (B sh_registration),
+ * "icp.near" (B x Q sh_closest, the pairs of the last evaluation: per-point residuals), "icp.moved", "icp.part", "icp.T", "icp.hist",
+ * "icp.flags"; upload / commit / sh_store("verts") remove "icp.out" and "icp.near".  The call changes nothing else: "cp.out", "wn.out",
+ * the records of a run and the buffers of the arthroplasty chain keep their bytes. */
+#define SH_ICP_POINT 0
+#define SH_ICP_PLANE 1
+#define SH_ICP_BLOCK 256
+#define SH_ICP_MAX_ITER 64
+typedef struct sh_icp_options { int32_t metric; int32_t max_iter; double reject; double tol; } sh_icp_options;   /* 24 B */
+typedef struct sh_registration { double T[16]; double rms; double rms_first; double min_pivot; int32_t pairs, iterations, converged, status; } sh_registration;   /* 168 B */
+int sh_register_points(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when per_humerus; CT */, int Q, int per_humerus,
+                       const double* T0 /* B x 16, nullable */, const sh_icp_options* options, sh_registration* out /* B, host, nullable */,
+                       double* history /* B x (max_iter + 1) x 2, host, nullable */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

@@ -266,6 +266,28 @@ WINDING_DTYPE = np.dtype([("winding", "<f8"), ("inside", "<i4"), ("status", "<i4
 assert WINDING_DTYPE.itemsize == ctypes.sizeof(Winding) == 16
 
 
+ICP_POINT, ICP_PLANE, ICP_BLOCK, ICP_MAX_ITER = 0, 1, 256, 64
+
+
+class IcpOptions(ctypes.Structure):
+    """sh_icp_options: the metric (ICP_POINT / ICP_PLANE), max_iter in 1..64, the rejection distance in mm (inf: none) and the rms
+    change at or below which a humerus has converged (0: every iteration runs)."""
+    _fields_ = [("metric", ctypes.c_int32), ("max_iter", ctypes.c_int32), ("reject", ctypes.c_double), ("tol", ctypes.c_double)]
+
+
+class Registration(ctypes.Structure):
+    """sh_registration: the rigid CT -> CT transform of one humerus' point set onto its mesh, the rms and the accepted pairs at that
+    transform, the rms at the start, the smallest Cholesky pivot ratio of the last solve (1.0 under the point metric), the updates
+    applied, whether the rms settled within tol, and the status."""
+    _fields_ = [("T", ctypes.c_double * 16), ("rms", ctypes.c_double), ("rms_first", ctypes.c_double), ("min_pivot", ctypes.c_double),
+                ("pairs", ctypes.c_int32), ("iterations", ctypes.c_int32), ("converged", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+REGISTRATION_DTYPE = np.dtype([("T", "<f8", (4, 4)), ("rms", "<f8"), ("rms_first", "<f8"), ("min_pivot", "<f8"), ("pairs", "<i4"),
+                               ("iterations", "<i4"), ("converged", "<i4"), ("status", "<i4")])
+assert REGISTRATION_DTYPE.itemsize == ctypes.sizeof(Registration) == 168 and ctypes.sizeof(IcpOptions) == 24
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -281,7 +303,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
            "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan",
-           "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points", "sh_winding_numbers"]
+           "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points", "sh_winding_numbers", "sh_register_points"]
 
 _lib = None
 
@@ -390,5 +412,7 @@ def load(build_if_missing=True):
         L.sh_closest_points.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
     if not alt or hasattr(L, "sh_winding_numbers"):      # (tools/time_winding.py and the benchmark's parent arm)
         L.sh_winding_numbers.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
+    if not alt or hasattr(L, "sh_register_points"):      # (the benchmark's parent arm has no registration)
+        L.sh_register_points.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     _lib = L
     return L

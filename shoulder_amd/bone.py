@@ -513,6 +513,43 @@ class ProximalHumerus(Bone):
         the surface itself as in `contains`."""
         return self._engine.signed_distance(self._points_ct(points)[0])[0]
 
+    # -- rigid registration (ICP) -------------------------------------------------------------------------------
+    def register(self, other, initial=None, mirror=None, **options):
+        """`trimesh.registration.icp(other, mesh)` / `mesh.register(other)` on the device (Engine.register): the rigid matrix that
+        moves `other` onto this bone's surface.  `other` is an (n, 3) array of points or anything with `.vertices`, in the CURRENT
+        coordinate system; `initial` a rigid (4, 4) starting matrix in that system (default: the identity); `mirror` = "x" | "y" | "z"
+        reflects the points in that coordinate plane FIRST (a contralateral bone) -- the reflection is the caller's and is not part of
+        the returned matrix.  options: metric ("plane" | "point"), max_iter, reject (mm), tol as in Engine.register.
+        -> (matrix (4, 4) in the current system, info) with info = dict(rms, rms_first, pairs, iterations, converged, min_pivot);
+        raises ValueError where the registration set a status (fewer than six accepted pairs, a singular system).
+
+        ICP IS LOCAL: it finds the nearest minimum and needs an initial pose within its basin, whose size has not been measured (the
+        tests start 3 and 4 degrees and a few millimetres off).  The bone's own coordinate system is the intended common ground: call
+        `apply_csys_canal_transepiconylar()` on both bones first.  The point metric converges linearly (many iterations, each a small
+        step), the plane metric quadratically near the solution but lets the points slide where the surface does not hold them
+        (see `min_pivot`: near 0 on a plane, a sphere, a cylinder)."""
+        pts = np.array(other.vertices if hasattr(other, "vertices") else other, dtype=np.float64).reshape(-1, 3)
+        if mirror is not None:
+            if mirror not in ("x", "y", "z"):
+                raise ValueError('mirror must be "x", "y", "z" or None')
+            pts[:, "xyz".index(mirror)] *= -1.0
+        p_ct, M = self._points_ct(pts)
+        Mi = np.linalg.inv(M)
+        T0 = None
+        if initial is not None:
+            initial = np.asarray(initial, dtype=np.float64).reshape(4, 4)
+            if not np.array_equal(initial[3], (0.0, 0.0, 0.0, 1.0)):
+                raise ValueError("initial must be a rigid matrix with the last row (0, 0, 0, 1)")
+            T0 = (Mi @ initial @ M)[None]
+            T0[0, 3] = (0.0, 0.0, 0.0, 1.0)      # (the product of three such rows, free of the inverse's rounding)
+        rec = self._engine.register(p_ct, T0=T0, **options)[0]
+        if rec["status"] != 0:
+            raise ValueError(f"register failed with status {int(rec['status'])}: fewer than six accepted pairs or a singular system "
+                             f"(pairs {int(rec['pairs'])}, iterations {int(rec['iterations'])})")
+        info = dict(rms=float(rec["rms"]), rms_first=float(rec["rms_first"]), pairs=int(rec["pairs"]), iterations=int(rec["iterations"]),
+                    converged=bool(rec["converged"]), min_pivot=float(rec["min_pivot"]))
+        return M @ np.array(rec["T"]) @ Mi, info
+
     # -- coordinate systems (bone.py:53-105, :146-157) --------------------------------------------------
     def _mesh_in(self, T):
         """`mesh_ct.copy().apply_transform(T)` (bone.py:155) on the device."""

@@ -45,6 +45,11 @@ namespace sh {
 #define CP_BUFS(X) X(cp_points, "cp.points", double, 8) X(cp_part, "cp.part", CpPart, 8) X(cp_out, "cp.out", sh_closest, 8)
 // nor are the generalized winding numbers (sh_winding_numbers)
 #define WN_BUFS(X) X(wn_points, "wn.points", double, 8) X(wn_part, "wn.part", double, 8) X(wn_out, "wn.out", sh_winding, 8)
+// nor is the registration of point sets (sh_register_points): the walk runs on buffers of its own ("icp.cp_part", "icp.near")
+#define ICP_BUFS(X)                                                                                                                \
+  X(icp_points, "icp.points", double, 8) X(icp_moved, "icp.moved", double, 8) X(icp_cp_part, "icp.cp_part", CpPart, 8)             \
+  X(icp_near, "icp.near", sh_closest, 8) X(icp_part, "icp.part", double, 8) X(icp_T, "icp.T", double, 8)                           \
+  X(icp_hist, "icp.hist", double, 8) X(icp_flags, "icp.flags", int, 4) X(icp_out, "icp.out", sh_registration, 8)
 // what the chain reads and does not own (the mesh: upload / commit; the records of a run: alloc_batch): X(field, "name", type)
 #define ARTHRO_INPUT_BUFS(X)                                                                                                       \
   X(verts, "verts", const float) X(faces, "faces", const int) X(voff, "voff", const long long) X(foff, "foff", const long long)    \
@@ -56,6 +61,7 @@ struct ArthroBytes { ARTHRO_BUFS(X) };
 struct RayBytes { RAY_BUFS(X) };
 struct CpBytes { CP_BUFS(X) };
 struct WnBytes { WN_BUFS(X) };
+struct IcpBytes { ICP_BUFS(X) };
 #undef X
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
@@ -67,6 +73,7 @@ constexpr int AR_CP_TILE = 256, AR_CP_CHUNK = 256, AR_CP_PART_BYTES = 16;       
 constexpr int AR_CP_FILL = 1024;      // workgroups of k_cp_walk that fill the chip: four of 256 lanes on each of 256 compute units
 constexpr int AR_WN_TILE = 256, AR_WN_CHUNK = 256, AR_WN_BLOCK = 2048;            // SH_WN_TILE, SH_WN_CHUNK, SH_WIND_BLOCK
 constexpr int AR_WN_FILL = 1024;      // workgroups of k_wn_walk that fill the chip, as AR_CP_FILL
+constexpr int AR_ICP_TERMS = 32, AR_ICP_TSTRIDE = 20;                             // SH_ICP_TERMS, SH_ICP_TSTRIDE
 
 struct ArthroError { int code; std::string text; };      // code SH_OK: accepted (text empty)
 inline ArthroError arthro_ok() { return {SH_OK, std::string()}; }
@@ -147,6 +154,24 @@ inline int first_bad_frame(const double* frames, int B) {
   for (int b = 0; b < B; ++b)
     if (!rigid_frame_ok(frames + 16 * (size_t)b)) return b;
   return -1;
+}
+
+// a rigid CT -> CT start of a registration: finite, last row exactly 0 0 0 1, |R^T R - I| <= 1e-9 in every entry (the columns: a shear
+// of 1e-6 fails), determinant positive (a reflection fails)
+inline bool rigid_start_ok(const double* T) {
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(T[i])) return false;
+  if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return false;
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j) {
+      const double d = (T[i] * T[j] + T[4 + i] * T[4 + j]) + T[8 + i] * T[8 + j];
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-9)) return false;
+    }
+  return det3_of4(T) > 0.0;
+}
+inline bool icp_options_ok(const sh_icp_options* o) {
+  return (o->metric == SH_ICP_POINT || o->metric == SH_ICP_PLANE) && o->max_iter >= 1 && o->max_iter <= SH_ICP_MAX_ITER && o->reject > 0.0 &&
+         o->tol >= 0.0 && std::isfinite(o->tol);
 }
 
 inline bool stem_catalogue_ok(const sh_stem* stems, int K) { return all_doubles(stems, K, [](double x) { return std::isfinite(x) && x > 0.0; }); }
@@ -294,6 +319,19 @@ inline WnPlan wn_plan(int B, int Q, bool per_humerus, long long maxF) {
   return {(int)kmax, chunks, S, stride, n, z};
 }
 
+// Registration, Q points per humerus.  The walk of an evaluation is the closest-point walk on the moved points, always per humerus:
+// its chunks and its split S are cp_plan's, unchanged.  The sums take the points in blocks of SH_ICP_BLOCK = the walk's chunk, one
+// row of AR_ICP_TERMS doubles per (humerus, block) in "icp.part"; "icp.T" holds the transform and the mean of the input points.
+struct IcpPlan { int chunks, S; size_t points; IcpBytes bytes; };      // point chunks = blocks of the sums, face splits of the walk, B x Q
+inline IcpPlan icp_plan(int B, int Q, bool per_humerus, long long maxF, int max_iter) {
+  const CpPlan cp = cp_plan(B, Q, true, maxF);
+  IcpBytes z;
+  z.icp_points = (per_humerus ? cp.points : (size_t)Q) * 24; z.icp_moved = cp.points * 24; z.icp_cp_part = cp.bytes.cp_part; z.icp_near = cp.bytes.cp_out;
+  z.icp_part = (size_t)B * cp.chunks * AR_ICP_TERMS * 8; z.icp_T = (size_t)B * AR_ICP_TSTRIDE * 8; z.icp_hist = (size_t)B * (max_iter + 1) * 16;
+  z.icp_flags = (size_t)B * 4; z.icp_out = (size_t)B * sizeof(sh_registration);
+  return {cp.chunks, cp.S, cp.points, z};
+}
+
 // ---- what is valid against what -----------------------------------------------------------------------------------------------------
 // One member of sh_ctx.  The resident batch is the context's (batch_gen: every upload / commit / store to "verts" takes a new one);
 // the queries take it as an argument.  RULE: void first, commit on success -- a *_begin voids what the call is about to overwrite and
@@ -435,6 +473,20 @@ inline ArthroError precheck_winding(const double* points, int Q, int per_humerus
   if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
   const long long i = first_bad_point(points, per_humerus ? (size_t)f.B * Q : (size_t)Q);
   if (i >= 0) return {SH_ERR_ARG, "point " + std::to_string(i) + " has a coordinate that is not finite"};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_register(const double* points, int Q, int per_humerus, const double* T0, const sh_icp_options* opt, const ArthroFacts& f) {
+  if (!f.ctx || !points || !opt) return {SH_ERR_ARG, "bad argument (context, points and options must be given)"};
+  if (Q < 1 || Q > SH_CLOSEST_MAX) return {SH_ERR_ARG, "bad argument (Q in 1..1048576)"};
+  if (!icp_options_ok(opt)) return {SH_ERR_ARG, "bad options (metric 0 or 1, max_iter in 1..64, reject > 0, tol >= 0 and finite)"};
+  if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
+  if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
+  const long long i = first_bad_point(points, per_humerus ? (size_t)f.B * Q : (size_t)Q);
+  if (i >= 0) return {SH_ERR_ARG, "point " + std::to_string(i) + " has a coordinate that is not finite"};
+  if (T0)
+    for (int b = 0; b < f.B; ++b)
+      if (!rigid_start_ok(T0 + 16 * (size_t)b)) return {SH_ERR_ARG, "T0 of humerus " + std::to_string(b) + " is not a rigid matrix (last row 0 0 0 1, |R^T R - I| <= 1e-9, det > 0)"};
   return arthro_ok();
 }
 

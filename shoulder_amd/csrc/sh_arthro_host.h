@@ -1,6 +1,6 @@
 // sh_arthro_host.h -- the entry points of the arthroplasty chain: sh_resect_* (k_resect.h, k_headfit.h, k_seat.h), sh_canal_profile and
 // sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h), the rays against the resident batch, sh_ray_cast / sh_anp_axis_hits (k_rays.h),
-// its closest surface points, sh_closest_points (k_closest.h), and its winding numbers, sh_winding_numbers (k_winding.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
+// its closest surface points, sh_closest_points (k_closest.h), its winding numbers, sh_winding_numbers (k_winding.h), and the registration of point sets onto it, sh_register_points (k_icp.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
 // headers and inside its extern "C" block.  A header and not a unit of its own: compiled in a unit that holds only the resection
 // headers, the unchanged k_resect_faces takes 100 VGPRs instead of 92, four waves per SIMD instead of five, so the kernels
 // stay in shoulder_hip.hip and the code that launches them with them.
@@ -398,6 +398,68 @@ int sh_winding_numbers(sh_ctx* c, const double* points, int Q, int per_humerus, 
   LAUNCH(c, "k_wn_join", k_wn_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.foff, Q, plan.S, plan.stride, (const double*)v.wn_part,
          (long long)plan.points, v.wn_out);
   if (out) HIPCHK(c, hipMemcpyAsync(out, v.wn_out, plan.bytes.wn_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- rigid registration of point sets onto the resident batch (k_icp.h); reads the mesh, changes no state of the chain ----
+static_assert(AR_ICP_TERMS == SH_ICP_TERMS && AR_ICP_TSTRIDE == SH_ICP_TSTRIDE, "sh_arthro.h: registration terms, stride of icp.T");
+#define X(f, name, T, ...) T* f = nullptr;
+struct IcpView { ARTHRO_INPUT_BUFS(X) ICP_BUFS(X) };
+#undef X
+static IcpView icp_view(sh_ctx* c) {
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  IcpView v;
+#define X(f, name, T, ...) v.f = (T*)at(name);
+  ARTHRO_INPUT_BUFS(X) ICP_BUFS(X)
+#undef X
+  return v;
+}
+static int icp_ensure(sh_ctx* c, const IcpBytes& z) {
+  int rc;
+#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
+  ICP_BUFS(X)
+#undef X
+  return SH_OK;
+}
+
+int sh_register_points(sh_ctx* c, const double* points, int Q, int per_humerus, const double* T0, const sh_icp_options* opt, sh_registration* out,
+                       double* history) {
+  if (const ArthroError e = precheck_register(points, Q, per_humerus, T0, opt, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_register_points", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B, per = per_humerus != 0 ? 1 : 0, K = opt->max_iter;
+  const IcpPlan plan = icp_plan(B, Q, per != 0, c->maxF, K);
+  if (int rc = icp_ensure(c, plan.bytes)) return rc;
+  const IcpView v = icp_view(c);
+  std::vector<double> start((size_t)B * SH_ICP_TSTRIDE, 0.0);
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < 16; ++i) start[(size_t)b * SH_ICP_TSTRIDE + i] = T0 ? T0[16 * (size_t)b + i] : (i % 5 == 0 ? 1.0 : 0.0);
+  HIPCHK(c, hipMemcpyAsync(v.icp_T, start.data(), plan.bytes.icp_T, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(v.icp_points, points, plan.bytes.icp_points, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.icp_flags, 0, plan.bytes.icp_flags, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.icp_hist, 0, plan.bytes.icp_hist, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.icp_out, 0, plan.bytes.icp_out, c->stream));
+  const dim3 blocks((unsigned)plan.chunks, (unsigned)B), lanes(SH_ICP_BLOCK);
+  // one pass over the blocks: phase 0 the mean of the input points, phase 1 evaluation k
+  // (LAUNCH ends in HIPCHK(hipGetLastError()): a launch that fails returns SH_ERR_HIP from the lambda, which the callers pass on)
+  auto sum_step = [&](int phase, int k) -> int {
+    LAUNCH(c, "k_icp_sum", k_icp_sum, blocks, lanes, v.verts, v.faces, v.voff, v.foff, (const double*)v.icp_points, (const double*)v.icp_moved,
+           (const sh_closest*)v.icp_near, Q, per, phase, (int)opt->metric, opt->reject, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_part);
+    LAUNCH(c, "k_icp_step", k_icp_step, dim3((unsigned)B), dim3(64), (const double*)v.icp_part, plan.chunks, Q, phase, (int)opt->metric, k, K, opt->tol,
+           v.icp_T, v.icp_flags, v.icp_hist, v.icp_out);
+    return SH_OK;
+  };
+  if (int rc = sum_step(0, 0)) return rc;
+  for (int k = 0; k <= K; ++k) {
+    LAUNCH(c, "k_icp_move", k_icp_move, blocks, lanes, (const double*)v.icp_points, Q, per, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_moved);
+    LAUNCH(c, "k_cp_walk", k_cp_walk, dim3((unsigned)plan.chunks, (unsigned)B, (unsigned)plan.S), dim3(SH_CP_CHUNK), v.verts, v.faces, v.voff, v.foff,
+           (const double*)v.icp_moved, Q, 1, plan.S, v.icp_cp_part);
+    LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.verts, v.faces, v.voff, v.foff, (const double*)v.icp_moved, Q, 1,
+           plan.S, (const CpPart*)v.icp_cp_part, (long long)plan.points, v.icp_near);
+    if (int rc = sum_step(1, k)) return rc;
+  }
+  if (out) HIPCHK(c, hipMemcpyAsync(out, v.icp_out, plan.bytes.icp_out, hipMemcpyDeviceToHost, c->stream));
+  if (history) HIPCHK(c, hipMemcpyAsync(history, v.icp_hist, plan.bytes.icp_hist, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -1155,4 +1155,228 @@ SH_HD bool plan_candidate(const PlanTerm& cut, const PlanTerm& head, const PlanT
 // the order of the ranking: ascending (cost, i), costs not NaN.  A total order: its minima do not depend on the reduction order.
 SH_HD bool plan_key_less(double ca, int ia, double cb, int ib) { return ca < cb || (ca == cb && ia < ib); }
 
+// ---- rigid registration of point sets onto the resident batch (include/shoulder_hip.h sh_register_points; k_icp.h) ----------
+// Everything below is + - x / sqrt on float64 in the written order (-ffp-contract=off), restated by tests/icp_oracle.py.
+// A row of sums has SH_ICP_TERMS doubles: [0] n, [1] sum e2; point metric [2..4] sum p', [5..7] sum q, [8 + 3 i + j] sum p'_i q_j;
+// plane metric [2..22] the upper triangle of sum J J^T row by row (i <= j), [23..28] sum J r; the rest +0.0.  The centroid pass uses
+// [0] and [2..4] (sum p over all input points).
+#define SH_ICP_TERMS 32
+#define SH_ICP_SWEEPS 12      // cyclic Jacobi sweeps of sym4_jacobi: fixed, converged or not
+#define SH_ICP_METRIC_POINT 0
+#define SH_ICP_METRIC_PLANE 1
+
+// the terms of one pair: pm the moved point, q its closest point with its status, (ab, ac) the winning face (plane metric), c the pivot.
+// A pair that is not accepted leaves +0.0 everywhere.
+SH_HD void icp_pair_terms(int metric, const double* pm, const double* q, int status, double reject, const double* ab, const double* ac,
+                          const double* c, double* t /* SH_ICP_TERMS */) {
+  for (int i = 0; i < SH_ICP_TERMS; ++i) t[i] = 0.0;
+  const double e[3] = {q[0] - pm[0], q[1] - pm[1], q[2] - pm[2]};
+  const double e2 = dot3(e, e);
+  bool acc = status == 0 && sqrt(e2) <= reject;
+  double n[3] = {0.0, 0.0, 0.0};
+  if (acc && metric == SH_ICP_METRIC_PLANE) {
+    double nn[3];
+    cross3(ab, ac, nn);
+    const double len = sqrt(dot3(nn, nn));
+    if (!(len > 0.0) || !(len <= 1.7976931348623157e308)) acc = false;
+    else { n[0] = nn[0] / len; n[1] = nn[1] / len; n[2] = nn[2] / len; }
+  }
+  if (!acc) return;
+  t[0] = 1.0; t[1] = e2;
+  if (metric == SH_ICP_METRIC_PLANE) {
+    const double d[3] = {pm[0] - c[0], pm[1] - c[1], pm[2] - c[2]};
+    double J[6];
+    cross3(d, n, J);
+    J[3] = n[0]; J[4] = n[1]; J[5] = n[2];
+    const double r = dot3(e, n);
+    int idx = 2;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j) t[idx++] = J[i] * J[j];
+    for (int i = 0; i < 6; ++i) t[23 + i] = J[i] * r;
+  } else {
+    for (int i = 0; i < 3; ++i) { t[2 + i] = pm[i]; t[5 + i] = q[i]; }
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) t[8 + 3 * i + j] = pm[i] * q[j];
+  }
+}
+
+// Cyclic Jacobi on a symmetric 4 x 4 (row-major, destroyed: its diagonal becomes the eigenvalues), V the eigenvectors in columns.
+// SH_ICP_SWEEPS sweeps over the pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a pair whose a_pq is 0.0 is left alone; otherwise
+// theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) (sgn(0) = +1), c = 1 / sqrt(t^2 + 1), s = t c,
+// a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, and for the other k: a_kp' = c a_kp - s a_kq, a_kq' = s a_kp + c a_kq (mirrored);
+// the same column update on V.
+SH_HD void sym4_jacobi(double* A, double* V) {
+  for (int i = 0; i < 16; ++i) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < SH_ICP_SWEEPS; ++sweep)
+    for (int p = 0; p < 3; ++p)
+      for (int q = p + 1; q < 4; ++q) {
+        const double apq = A[4 * p + q];
+        if (apq == 0.0) continue;
+        const double theta = (A[4 * q + q] - A[4 * p + p]) / (2.0 * apq);
+        const double at = fabs(theta);
+        double t = 1.0 / (at + sqrt(theta * theta + 1.0));
+        if (theta < 0.0) t = -t;
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        A[4 * p + p] = A[4 * p + p] - t * apq;
+        A[4 * q + q] = A[4 * q + q] + t * apq;
+        A[4 * p + q] = 0.0; A[4 * q + p] = 0.0;
+        for (int k = 0; k < 4; ++k) {
+          if (k != p && k != q) {
+            const double akp = A[4 * k + p], akq = A[4 * k + q];
+            const double np_ = c * akp - s * akq, nq_ = s * akp + c * akq;
+            A[4 * k + p] = np_; A[4 * p + k] = np_;
+            A[4 * k + q] = nq_; A[4 * q + k] = nq_;
+          }
+          const double vkp = V[4 * k + p], vkq = V[4 * k + q];
+          V[4 * k + p] = c * vkp - s * vkq;
+          V[4 * k + q] = s * vkp + c * vkq;
+        }
+      }
+}
+
+SH_HD bool icp_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// the rotation of a unit quaternion (w, x, y, z), row-major 3 x 3
+SH_HD void quat_rot(double w, double x, double y, double z, double* R) {
+  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z); R[2] = 2.0 * (x * z + w * y);
+  R[3] = 2.0 * (x * y + w * z); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+  R[6] = 2.0 * (x * z - w * y); R[7] = 2.0 * (y * z + w * x); R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+// (R, t) as a row-major 4 x 4
+SH_HD void icp_pack(const double* R, const double* t, double* D) {
+  for (int i = 0; i < 3; ++i) { D[4 * i] = R[3 * i]; D[4 * i + 1] = R[3 * i + 1]; D[4 * i + 2] = R[3 * i + 2]; D[4 * i + 3] = t[i]; }
+  D[12] = 0.0; D[13] = 0.0; D[14] = 0.0; D[15] = 1.0;
+}
+
+// Horn's closed form (Closed-form solution of absolute orientation using unit quaternions, 1987) from a row of point-metric sums:
+// pbar = sum p' / n, qbar = sum q / n, S_ij = sum p'_i q_j - (sum p'_i) qbar_j, the symmetric N of S, its eigenvector of the largest
+// eigenvalue (the first among equals) normalised with w >= 0, dt = qbar - R pbar.  false: N or the result is not finite.
+SH_HD bool icp_horn_solve(const double* tot, double* D /* 16 */) {
+  const double n = tot[0];
+  double pb[3], qb[3], S[9];
+  for (int i = 0; i < 3; ++i) { pb[i] = tot[2 + i] / n; qb[i] = tot[5 + i] / n; }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) S[3 * i + j] = tot[8 + 3 * i + j] - tot[2 + i] * qb[j];
+  double N[16], V[16];
+  N[0] = (S[0] + S[4]) + S[8]; N[1] = S[5] - S[7]; N[2] = S[6] - S[2]; N[3] = S[1] - S[3];
+  N[5] = (S[0] - S[4]) - S[8]; N[6] = S[1] + S[3]; N[7] = S[6] + S[2];
+  N[10] = (S[4] - S[0]) - S[8]; N[11] = S[5] + S[7];
+  N[15] = (S[8] - S[0]) - S[4];
+  N[4] = N[1]; N[8] = N[2]; N[12] = N[3]; N[9] = N[6]; N[13] = N[7]; N[14] = N[11];
+  for (int i = 0; i < 16; ++i)
+    if (!icp_finite(N[i])) return false;
+  sym4_jacobi(N, V);
+  int best = 0;
+  for (int i = 1; i < 4; ++i)
+    if (N[5 * i] > N[5 * best]) best = i;
+  double w = V[best], x = V[4 + best], y = V[8 + best], z = V[12 + best];
+  const double len = sqrt(((w * w + x * x) + y * y) + z * z);
+  if (!(len > 0.0) || !icp_finite(len)) return false;
+  w = w / len; x = x / len; y = y / len; z = z / len;
+  if (w < 0.0) { w = -w; x = -x; y = -y; z = -z; }
+  double R[9], t[3];
+  quat_rot(w, x, y, z, R);
+  for (int i = 0; i < 3; ++i) t[i] = qb[i] - ((R[3 * i] * pb[0] + R[3 * i + 1] * pb[1]) + R[3 * i + 2] * pb[2]);
+  icp_pack(R, t, D);
+  return true;
+}
+
+// Cholesky of a symmetric 6 x 6 given by its upper triangle row by row (21 doubles), in index order, and the solve of A x = b.
+// Column j: s = A_jj - L_j0^2 - ... - L_j,j-1^2 (left to right); a pivot s that is <= 0 or not finite fails; L_jj = sqrt(s);
+// below it L_ij = (A_ij - L_i0 L_j0 - ...) / L_jj.  Then L y = b forwards and L^T x = y backwards, the sums left to right with k
+// ascending.  *min_pivot = min_j min(1, (L_jj L_jj) / A_jj): near 0 where the system is nearly singular.
+SH_HD bool chol6_solve(const double* up, const double* b, double* x, double* min_pivot) {
+  double A[36], L[36], y[6];
+  int idx = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { A[6 * i + j] = up[idx]; A[6 * j + i] = up[idx]; ++idx; }
+  for (int i = 0; i < 36; ++i) L[i] = 0.0;
+  double mp = 1.0;
+  for (int j = 0; j < 6; ++j) {
+    double s = A[6 * j + j];
+    for (int k = 0; k < j; ++k) s = s - L[6 * j + k] * L[6 * j + k];
+    if (!(s > 0.0) || !icp_finite(s)) return false;
+    const double l = sqrt(s);
+    L[6 * j + j] = l;
+    const double ratio = (l * l) / A[6 * j + j];
+    if (ratio < mp) mp = ratio;
+    for (int i = j + 1; i < 6; ++i) {
+      double v = A[6 * i + j];
+      for (int k = 0; k < j; ++k) v = v - L[6 * i + k] * L[6 * j + k];
+      L[6 * i + j] = v / l;
+    }
+  }
+  for (int i = 0; i < 6; ++i) {
+    double v = b[i];
+    for (int k = 0; k < i; ++k) v = v - L[6 * i + k] * y[k];
+    y[i] = v / L[6 * i + i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double v = y[i];
+    for (int k = i + 1; k < 6; ++k) v = v - L[6 * k + i] * x[k];
+    x[i] = v / L[6 * i + i];
+  }
+  *min_pivot = mp;
+  return true;
+}
+
+// the plane-metric update from a row of sums and the pivot c: x = (w, t) by chol6_solve, the rotation of the quaternion (1, w / 2)
+// normalised, dt = (c - R c) + t
+SH_HD bool icp_plane_solve(const double* tot, const double* c, double* D /* 16 */, double* min_pivot) {
+  double x[6];
+  if (!chol6_solve(tot + 2, tot + 23, x, min_pivot)) return false;
+  const double hx = 0.5 * x[0], hy = 0.5 * x[1], hz = 0.5 * x[2];
+  const double len = sqrt(((1.0 + hx * hx) + hy * hy) + hz * hz);
+  if (!icp_finite(len)) return false;
+  double R[9], t[3];
+  quat_rot(1.0 / len, hx / len, hy / len, hz / len, R);
+  for (int i = 0; i < 3; ++i) t[i] = (c[i] - ((R[3 * i] * c[0] + R[3 * i + 1] * c[1]) + R[3 * i + 2] * c[2])) + x[3 + i];
+  icp_pack(R, t, D);
+  return true;
+}
+
+// Tn = D T for two rigid 4 x 4 (last rows 0 0 0 1): the sums left to right, the translation added last
+SH_HD void icp_compose(const double* D, const double* T, double* Tn) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 4; ++j) Tn[4 * i + j] = (D[4 * i] * T[j] + D[4 * i + 1] * T[4 + j]) + D[4 * i + 2] * T[8 + j];
+    Tn[4 * i + 3] = Tn[4 * i + 3] + D[4 * i + 3];
+  }
+  Tn[12] = 0.0; Tn[13] = 0.0; Tn[14] = 0.0; Tn[15] = 1.0;
+}
+
+// Evaluation k of one humerus from its joined row of sums: report, then stop or step (include/shoulder_hip.h).  rec = {rms, rms_first,
+// min_pivot} and irec = {pairs, iterations, converged, status} are the tail of its sh_registration: rec[0] comes in as the rms of
+// evaluation k - 1.  T is the transform the sums were taken at; it is replaced only when an update is applied.  Returns 1 when the
+// humerus is done.  rms = sqrt(sum e2 / n), and 0.0 when n = 0.
+SH_HD int icp_step(int metric, int k, int max_iter, double tol, const double* tot, const double* cbar, double* T, double* rec, int* irec,
+                   double* hist /* rms, pairs */) {
+  const double n = tot[0];
+  const double rms = n > 0.0 ? sqrt(tot[1] / n) : 0.0;
+  const double prev = rec[0];
+  hist[0] = rms; hist[1] = n;
+  rec[0] = rms;
+  if (k == 0) { rec[1] = rms; rec[2] = 1.0; }
+  irec[0] = (int)n; irec[1] = k; irec[2] = 0; irec[3] = 0;
+  if (k > 0 && fabs(prev - rms) <= tol) { irec[2] = 1; return 1; }
+  if (k == max_iter) return 1;
+  if (n < 6.0) { irec[3] = SH_ERR_GEOMETRY_DEV; return 1; }
+  double D[16], Tn[16], mp = 1.0;
+  bool ok;
+  if (metric == SH_ICP_METRIC_PLANE) {
+    double c[3];
+    canal_map_point(T, cbar[0], cbar[1], cbar[2], c);
+    ok = icp_plane_solve(tot, c, D, &mp);
+  } else {
+    ok = icp_horn_solve(tot, D);
+  }
+  if (ok) {
+    icp_compose(D, T, Tn);
+    for (int i = 0; i < 12; ++i) ok = ok && icp_finite(Tn[i]);
+  }
+  if (!ok) { irec[3] = SH_ERR_GEOMETRY_DEV; return 1; }
+  rec[2] = mp;
+  for (int i = 0; i < 16; ++i) T[i] = Tn[i];
+  return 0;
+}
+
 }  // namespace sh

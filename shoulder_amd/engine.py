@@ -663,6 +663,37 @@ class Engine:
             raise ShoulderHipError(int(rec["status"][rec["status"] != 0][0]), "signed_distance: no face of a mesh gave a finite distance")
         return np.where(inside, rec["dist"], -rec["dist"])
 
+    # ---- rigid registration of point sets onto the resident batch (include/shoulder_hip.h sh_register_points) -------------------
+    def register(self, points, T0=None, metric="plane", max_iter=20, reject=np.inf, tol=0.0, history=False):
+        """Rigid ICP of a point set onto every resident humerus, the whole loop on the device -> a structured array (B,) of
+        _lib.REGISTRATION_DTYPE: T (4, 4), CT -> CT, moving the points onto the bone; rms and pairs at T; rms_first; min_pivot;
+        iterations (updates applied); converged; status.  With history=True also a (B, max_iter + 1, 2) array of (rms, pairs) per
+        evaluation made, zeros behind.  points: (Q, 3), shared by all humeri, or (B, Q, 3), in CT -- the convention of closest_points.
+        T0: (B, 4, 4) rigid starting transforms (default: identity).  metric "plane" (point-to-plane, converges quadratically near
+        the solution; `min_pivot` near 0 tells of a surface that lets the points slide) or "point" (Horn's closed form, converges
+        linearly).  reject: pairs farther apart than this many mm are left out; tol: stop once the rms changes by no more than this.
+        tol ends a humerus' updates, NOT the call's work: the host enqueues all max_iter + 1 closest-point walks and does not look at the
+        flags in between, so a batch that converges early still pays for max_iter (about 10 ms per walk for 64 bones x 4 096 points).
+        ICP is local: the start must lie within its basin of convergence.  The pairs of the last evaluation stay in "icp.near"."""
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
+            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
+        if metric not in ("point", "plane"):
+            raise ValueError('metric must be "point" or "plane"')
+        Q, per = p.shape[-2], int(p.ndim == 3)
+        t0 = None
+        if T0 is not None:
+            t0 = np.ascontiguousarray(T0, dtype=np.float64)
+            if t0.shape != (self.B, 4, 4):
+                raise ValueError("T0 must have shape (B, 4, 4)")
+        opt = _lib.IcpOptions(_lib.ICP_PLANE if metric == "plane" else _lib.ICP_POINT, int(max_iter), float(reject), float(tol))
+        rows = int(max_iter) + 1 if 1 <= int(max_iter) <= _lib.ICP_MAX_ITER else 0      # (the library reports the rest)
+        out = np.zeros(self.B, dtype=_lib.REGISTRATION_DTYPE)
+        hist = np.zeros((self.B, rows, 2)) if history else None
+        self._chk(self.L.sh_register_points(self.h, _ptr(p), Q, per, _ptr(t0) if t0 is not None else None, ctypes.byref(opt), _ptr(out),
+                                            _ptr(hist) if hist is not None else None))
+        return (out, hist) if history else out
+
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):
         n, e = ctypes.c_size_t(), ctypes.c_int()
