@@ -712,7 +712,8 @@ int sh_winding_numbers(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when
 /* ---- rigid registration of point sets onto the resident batch (ICP) ----------------------------------------------------------------
  * The counterpart of `trimesh.registration.icp(points, mesh)` / `mesh.register`: for B humeri x Q points, up to max_iter rigid ICP
  * iterations per humerus, the whole loop on the device (k_icp.h, with the unchanged k_cp_walk / k_cp_join), one transform per humerus
- * with its evidence.  ICP is LOCAL: it needs an initial pose inside its basin of convergence; no global search is made.
+ * with its evidence.  ICP is LOCAL: it needs an initial pose inside its basin of convergence; no global search is made here
+ * (sh_register_multistart, below, makes one on top of this call).
  *   options   metric SH_ICP_POINT (Horn's closed form per iteration, linear convergence) or SH_ICP_PLANE (linearised point-to-plane,
  *             quadratic near the solution); max_iter in 1..64; reject in mm, > 0, +inf accepts every pair; tol >= 0, 0 runs every
  *             iteration.
@@ -765,6 +766,76 @@ typedef struct sh_registration { double T[16]; double rms; double rms_first; dou
 int sh_register_points(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when per_humerus; CT */, int Q, int per_humerus,
                        const double* T0 /* B x 16, nullable */, const sh_icp_options* options, sh_registration* out /* B, host, nullable */,
                        double* history /* B x (max_iter + 1) x 2, host, nullable */);
+
+/* ---- mass properties of the resident batch: surface and volume integrals ----------------------------------------------------------
+ * The counterpart of `mesh.area`, `volume`, `center_mass`, `moment_inertia`, `principal_inertia_components` and
+ * `principal_inertia_vectors`, and the frame of the surface itself: for each of the B resident meshes the exact integrals over its
+ * triangles, in one device pass (k_mass.h).  Everything float64, -ffp-contract=off, + - x / sqrt only (sh_scalar.h).
+ *   corners   the float32 vertices widened to float64.  The pivot o is vertex 0 of the humerus' vertex array, widened: it keeps the
+ *             sums from cancelling at CT coordinates.  a = A - o, b = B - o, c = C - o; ab = B - A, ac = C - A; n = cross3(ab, ac);
+ *             A2 = sqrt(dot3(n, n)); s = (a + b) + c; d = dot3(a, cross3(b, c));
+ *             m_ij = ((s_i s_j + a_i a_j) + b_i b_j) + c_i c_j for ij = 00, 01, 02, 11, 12, 22.
+ *   terms     24 per face: [0] A2, [1..3] A2 s_k, [4..9] A2 m_ij, [10..12] n_k, [13] d, [14..16] d s_k, [17..22] d m_ij,
+ *             [23] 1.0 when A2 == 0.0, else 0.0.
+ *   sum       THE TREE IS PART OF THE DEFINITION and is that of sh_register_points: faces in blocks of SH_MASS_BLOCK = 256 consecutive
+ *             indices; in a block slot[i] += slot[i + h] for h = 128, 64, .., 1 (missing faces of the last block are +0.0); the block
+ *             sums added in block order starting at 0.0.  No floating-point atomics, nothing that depends on B, the launch shape or
+ *             the humerus' place in the batch.
+ *   finish    (mass_finish) with T the totals and a primed quantity relative to o.  Shell: area = T0 / 2, cs'_k = T[1 + k] / (3 T0),
+ *             shell_cov C_ij = T[4 + ij] / (12 T0) - cs'_i cs'_j, closure = sqrt(dot3(N, N)) / T0 with N = T[10..12] -- 0 on a closed
+ *             mesh and about cap area / area on an open one: a NECESSARY sign of closedness, not a sufficient one.  Volume:
+ *             volume = T13 / 6, SIGNED (a mesh stored inside-out gives a negative one), cm'_k = T[14 + k] / (4 T13),
+ *             P_ij = T[17 + ij] / 120, S_ij = P_ij - (volume cm'_i) cm'_j, the inertia tensor at density 1 about the centre of mass
+ *             I_00 = S_11 + S_22, I_11 = S_00 + S_22, I_22 = S_00 + S_11, I_ij = -S_ij.  Centroids are reported in CT (+ o).
+ *   frames    sym3_jacobi, the conventions of sym4_jacobi: 12 cyclic sweeps, pairs (0,1) (0,2) (1,2), the same t, among equal
+ *             eigenvalues the first.  principal: the moments of I ascending with their axes; shell_eig / shell_axes: the eigenvalues
+ *             of C DESCENDING with their axes, the long axis first.  Axes are rows.  Each of the first two is signed so that its
+ *             component of largest magnitude is positive (the first among equals); the third is cross3(first, second).
+ *   sh_mass (400 B)  faces; degenerate = T23, the faces of zero area; status SH_ERR_GEOMETRY when there are no faces, T0 == 0 or a
+ *             shell quantity is not finite (the shell fields are then zero); vstatus the same for T13 == 0 or a volume quantity that is
+ *             not finite (the volume fields -- volume, center_mass, inertia, principal, principal_axes -- are then zero).
+ * A record depends on that mesh alone, byte for byte: not on B or the humerus' place in the batch.
+ *
+ * Needs the context (SH_ERR_ARG), a resident batch and no runs in flight (SH_ERR_STATE; a run is not needed).  SH_ERR_NOMEM when the
+ * buffers do not fit.  The results stay resident in "mass.out" (B sh_mass) and "mass.part" (B x blocks of the largest humerus x 24
+ * doubles, the block rows; zeros behind a smaller humerus' blocks) until the next upload / commit / sh_store("verts"), which removes
+ * them.  The call changes nothing else. */
+#define SH_MASS_BLOCK 256
+typedef struct sh_mass {
+  double area, volume, closure;
+  double shell_centroid[3], shell_cov[6], shell_eig[3], shell_axes[9];
+  double center_mass[3], inertia[9], principal[3], principal_axes[9];
+  int32_t faces, degenerate, status, vstatus;
+} sh_mass;   /* 400 B */
+int sh_mass_properties(sh_ctx*, sh_mass* out /* B, host, nullable */);
+
+/* ---- global registration: K starts per humerus, a short ICP on each, a final ICP from the best ---------------------------------------
+ * The counterpart of `trimesh.registration.mesh_other`: where sh_register_points needs a start within its basin, this call takes K
+ * starts per humerus (Engine.principal_starts makes them from the principal frames of sh_mass_properties), runs a coarse registration
+ * from each and a fine one from the best.  THE RESULT IS DEFINED ENTIRELY BY CALLS OF sh_register_points, so its bytes are defined there:
+ *   coarse set   Qc = min(coarse_points, Q) points (coarse_points == 0: all Q); point j of it is input point floor(j Q / Qc) in integer
+ *             arithmetic (of the humerus' own Q points when per_humerus).
+ *   candidate k  coarse_out[b][k] equals what sh_register_points(coarse set, T0 = T0s[b][k], coarse) returns for humerus b, byte for
+ *             byte -- the pivot's mean is taken over the coarse set.
+ *   winner    the smallest (rms, k) among the candidates with status 0, pairs >= min_pairs and an rms that is not NaN; min_pairs >= 6.
+ *   no winner out[b] is zero but for status = SH_ERR_GEOMETRY and T = T0s[b][0]; winner[b] = -1.  The humerus takes no part in the
+ *             fine stage and never fails the batch.
+ *   fine      out[b] equals what sh_register_points(all Q points, T0 = coarse_out[b][winner[b]].T, fine) returns, byte for byte.
+ * The K starts run one after the other on the context's stream, each the unchanged chain of sh_register_points, and the host looks
+ * at nothing in between (k_ms.h: k_ms_seed puts start k in place, k_ms_pick keeps the candidate and folds it into the best).
+ *
+ * Arguments in this order: the context and the pointers points, T0s, coarse, fine (SH_ERR_ARG); Q in 1..SH_CLOSEST_MAX; K in
+ * 1..SH_MS_MAX_STARTS, coarse_points >= 0 and min_pairs >= 6; the coarse options, then the fine ones; a resident batch and no runs in
+ * flight (SH_ERR_STATE); every coordinate finite, naming the first bad point; every T0s[b][k] under the rule of T0, naming the humerus
+ * and the start (all SH_ERR_ARG).  SH_ERR_NOMEM when the buffers do not fit.  Resident afterwards: "ms.coarse" (B x K
+ * sh_registration), "ms.winner" (B int32), "ms.best" (B doubles: the winners' coarse rms), and the "icp.*" buffers of the FINE stage as
+ * sh_register_points leaves them ("icp.near" of a humerus without a winner is not defined).  An earlier call's "icp.*" are
+ * overwritten; "cp.out", "wn.out", "mass.out", the records of a run and the buffers of the arthroplasty chain keep their bytes. */
+#define SH_MS_MAX_STARTS 64
+int sh_register_multistart(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 when per_humerus; CT */, int Q, int per_humerus,
+                           const double* T0s /* B x K x 16 */, int K, const sh_icp_options* coarse, int coarse_points, int min_pairs,
+                           const sh_icp_options* fine, sh_registration* out /* B, host, nullable */,
+                           sh_registration* coarse_out /* B x K, host, nullable */, int32_t* winner /* B, host, nullable */);
 
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"

@@ -288,6 +288,28 @@ REGISTRATION_DTYPE = np.dtype([("T", "<f8", (4, 4)), ("rms", "<f8"), ("rms_first
 assert REGISTRATION_DTYPE.itemsize == ctypes.sizeof(Registration) == 168 and ctypes.sizeof(IcpOptions) == 24
 
 
+MASS_BLOCK, MS_MAX_STARTS = 256, 64
+
+
+class Mass(ctypes.Structure):
+    """sh_mass: the surface and volume integrals of one resident humerus -- area, signed volume, closure (|sum of face normals| / (2 area):
+    0 on a closed mesh); the shell's centroid (CT), covariance (00, 01, 02, 11, 12, 22), its eigenvalues descending and their axes as
+    rows, long axis first; the centre of mass (CT), the inertia tensor at density 1 about it, its principal moments ascending and their
+    axes as rows; faces, the faces of zero area, status (shell) and vstatus (volume)."""
+    _fields_ = [("area", ctypes.c_double), ("volume", ctypes.c_double), ("closure", ctypes.c_double), ("shell_centroid", ctypes.c_double * 3),
+                ("shell_cov", ctypes.c_double * 6), ("shell_eig", ctypes.c_double * 3), ("shell_axes", ctypes.c_double * 9),
+                ("center_mass", ctypes.c_double * 3), ("inertia", ctypes.c_double * 9), ("principal", ctypes.c_double * 3),
+                ("principal_axes", ctypes.c_double * 9), ("faces", ctypes.c_int32), ("degenerate", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("vstatus", ctypes.c_int32)]
+
+
+MASS_DTYPE = np.dtype([("area", "<f8"), ("volume", "<f8"), ("closure", "<f8"), ("shell_centroid", "<f8", (3,)), ("shell_cov", "<f8", (6,)),
+                       ("shell_eig", "<f8", (3,)), ("shell_axes", "<f8", (3, 3)), ("center_mass", "<f8", (3,)), ("inertia", "<f8", (3, 3)),
+                       ("principal", "<f8", (3,)), ("principal_axes", "<f8", (3, 3)), ("faces", "<i4"), ("degenerate", "<i4"), ("status", "<i4"),
+                       ("vstatus", "<i4")])
+assert MASS_DTYPE.itemsize == ctypes.sizeof(Mass) == 400
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -303,7 +325,8 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_set_open_contours", "sh_get_open_contours", "sh_open_contour_stats", "sh_mesh_open_edges",
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
            "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan",
-           "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points", "sh_winding_numbers", "sh_register_points"]
+           "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points", "sh_winding_numbers", "sh_register_points",
+           "sh_mass_properties", "sh_register_multistart"]
 
 _lib = None
 
@@ -414,5 +437,8 @@ def load(build_if_missing=True):
         L.sh_winding_numbers.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp]
     if not alt or hasattr(L, "sh_register_points"):      # (the benchmark's parent arm has no registration)
         L.sh_register_points.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    if not alt or hasattr(L, "sh_mass_properties"):      # (tools/time_register_global.py and the benchmark's parent arm)
+        L.sh_mass_properties.argtypes = [vp, vp]
+        L.sh_register_multistart.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     _lib = L
     return L

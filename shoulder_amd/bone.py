@@ -513,6 +513,30 @@ class ProximalHumerus(Bone):
         the surface itself as in `contains`."""
         return self._engine.signed_distance(self._points_ct(points)[0])[0]
 
+    # -- mass properties ----------------------------------------------------------------------------------------
+    def mass_properties(self):
+        """`mesh.area`, `volume`, `center_mass`, `moment_inertia`, `principal_inertia_components`, `principal_inertia_vectors` and the
+        frame of the surface itself, in the CURRENT coordinate system, on the device (Engine.mass_properties) -> dict: the scalars
+        (area, volume, closure, principal, shell_eig, faces, degenerate, vstatus) are CT's, unchanged by a rigid transform;
+        center_mass and shell_centroid are mapped as points, principal_axes and shell_axes (rows) as directions, inertia and shell_cov
+        (3, 3) as tensors.  Raises ValueError for a mesh without a surface; a mesh that encloses no volume has vstatus set and zeros
+        in the volume fields."""
+        self._ensure_loaded()
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        R = T[:3, :3]
+        m = self._engine.mass_properties()[0]
+        if m["status"] != 0:
+            raise ValueError(f"mass_properties failed with status {int(m['status'])}: the mesh has no faces or no area")
+        C = np.zeros((3, 3))
+        C[np.triu_indices(3)] = m["shell_cov"]
+        C = C + np.triu(C, 1).T
+        pts = self._engine.transform_points(np.ascontiguousarray(np.stack([m["center_mass"], m["shell_centroid"]])), T)
+        has_volume = m["vstatus"] == 0
+        return dict(area=float(m["area"]), volume=float(m["volume"]), closure=float(m["closure"]), center_mass=pts[0] if has_volume else np.zeros(3),
+                    inertia=R @ m["inertia"] @ R.T, principal=np.array(m["principal"]), principal_axes=m["principal_axes"] @ R.T,
+                    shell_centroid=pts[1], shell_cov=R @ C @ R.T, shell_eig=np.array(m["shell_eig"]), shell_axes=m["shell_axes"] @ R.T,
+                    faces=int(m["faces"]), degenerate=int(m["degenerate"]), vstatus=int(m["vstatus"]))
+
     # -- rigid registration (ICP) -------------------------------------------------------------------------------
     def register(self, other, initial=None, mirror=None, **options):
         """`trimesh.registration.icp(other, mesh)` / `mesh.register(other)` on the device (Engine.register): the rigid matrix that
@@ -527,7 +551,14 @@ class ProximalHumerus(Bone):
         tests start 3 and 4 degrees and a few millimetres off).  The bone's own coordinate system is the intended common ground: call
         `apply_csys_canal_transepiconylar()` on both bones first.  The point metric converges linearly (many iterations, each a small
         step), the plane metric quadratically near the solution but lets the points slide where the surface does not hold them
-        (see `min_pivot`: near 0 on a plane, a sphere, a cylinder)."""
+        (see `min_pivot`: near 0 on a plane, a sphere, a cylinder).
+
+        `initial="principal"` makes the GLOBAL search of `trimesh.registration.mesh_other` instead (Engine.register_global): starts
+        from the principal frames of the bone and of the points -- both directions of the long axis times `rolls` turns about it --,
+        a short registration of a subsample from each and the full one from the best; for a scan, a contralateral bone or a second
+        segmentation in an unknown pose.  options then also take rolls, coarse_points, coarse_iter and min_pairs, and info also holds
+        winner, coarse_rms (one per start), mesh_ratio and points_ratio (the two largest shell eigenvalues' ratio: near 1 the shape
+        has no long axis and the starts are arbitrary)."""
         pts = np.array(other.vertices if hasattr(other, "vertices") else other, dtype=np.float64).reshape(-1, 3)
         if mirror is not None:
             if mirror not in ("x", "y", "z"):
@@ -535,6 +566,18 @@ class ProximalHumerus(Bone):
             pts[:, "xyz".index(mirror)] *= -1.0
         p_ct, M = self._points_ct(pts)
         Mi = np.linalg.inv(M)
+        if isinstance(initial, str):
+            if initial != "principal":
+                raise ValueError('initial must be a (4, 4) matrix, None or "principal"')
+            rec, more = self._engine.register_global(p_ct, **options)
+            rec = rec[0]
+            if rec["status"] != 0:
+                raise ValueError(f"register failed with status {int(rec['status'])}: no start qualified (winner {int(more['winner'][0])}), fewer than six "
+                                 f"accepted pairs or a singular system (pairs {int(rec['pairs'])}, iterations {int(rec['iterations'])})")
+            info = dict(rms=float(rec["rms"]), rms_first=float(rec["rms_first"]), pairs=int(rec["pairs"]), iterations=int(rec["iterations"]),
+                        converged=bool(rec["converged"]), min_pivot=float(rec["min_pivot"]), winner=int(more["winner"][0]),
+                        coarse_rms=np.array(more["coarse"][0]["rms"]), mesh_ratio=float(more["mesh_ratio"][0]), points_ratio=float(more["points_ratio"][0]))
+            return M @ np.array(rec["T"]) @ Mi, info
         T0 = None
         if initial is not None:
             initial = np.asarray(initial, dtype=np.float64).reshape(4, 4)

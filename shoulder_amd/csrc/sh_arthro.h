@@ -50,6 +50,12 @@ namespace sh {
   X(icp_points, "icp.points", double, 8) X(icp_moved, "icp.moved", double, 8) X(icp_cp_part, "icp.cp_part", CpPart, 8)             \
   X(icp_near, "icp.near", sh_closest, 8) X(icp_part, "icp.part", double, 8) X(icp_T, "icp.T", double, 8)                           \
   X(icp_hist, "icp.hist", double, 8) X(icp_flags, "icp.flags", int, 4) X(icp_out, "icp.out", sh_registration, 8)
+// the mass properties (sh_mass_properties): the block rows and the records
+#define MASS_BUFS(X) X(mass_part, "mass.part", double, 8) X(mass_out, "mass.out", sh_mass, 8)
+// the multi-start registration (sh_register_multistart) runs the chain of sh_register_points on the "icp.*" buffers; these are its own
+#define MS_BUFS(X)                                                                                                                 \
+  X(ms_T0s, "ms.T0s", double, 8) X(ms_points, "ms.points", double, 8) X(ms_coarse, "ms.coarse", sh_registration, 8)                \
+  X(ms_best, "ms.best", double, 8) X(ms_winner, "ms.winner", int, 4)
 // what the chain reads and does not own (the mesh: upload / commit; the records of a run: alloc_batch): X(field, "name", type)
 #define ARTHRO_INPUT_BUFS(X)                                                                                                       \
   X(verts, "verts", const float) X(faces, "faces", const int) X(voff, "voff", const long long) X(foff, "foff", const long long)    \
@@ -62,6 +68,8 @@ struct RayBytes { RAY_BUFS(X) };
 struct CpBytes { CP_BUFS(X) };
 struct WnBytes { WN_BUFS(X) };
 struct IcpBytes { ICP_BUFS(X) };
+struct MassBytes { MASS_BUFS(X) };
+struct MsBytes { MS_BUFS(X) };
 #undef X
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
@@ -74,6 +82,7 @@ constexpr int AR_CP_FILL = 1024;      // workgroups of k_cp_walk that fill the c
 constexpr int AR_WN_TILE = 256, AR_WN_CHUNK = 256, AR_WN_BLOCK = 2048;            // SH_WN_TILE, SH_WN_CHUNK, SH_WIND_BLOCK
 constexpr int AR_WN_FILL = 1024;      // workgroups of k_wn_walk that fill the chip, as AR_CP_FILL
 constexpr int AR_ICP_TERMS = 32, AR_ICP_TSTRIDE = 20;                             // SH_ICP_TERMS, SH_ICP_TSTRIDE
+constexpr int AR_MASS_TERMS = 24;                                                 // SH_MASS_TERMS
 
 struct ArthroError { int code; std::string text; };      // code SH_OK: accepted (text empty)
 inline ArthroError arthro_ok() { return {SH_OK, std::string()}; }
@@ -332,6 +341,39 @@ inline IcpPlan icp_plan(int B, int Q, bool per_humerus, long long maxF, int max_
   return {cp.chunks, cp.S, cp.points, z};
 }
 
+// Mass properties: one row of AR_MASS_TERMS doubles per (humerus, block of SH_MASS_BLOCK faces) in "mass.part", the blocks of the largest
+// humerus for every humerus
+struct MassPlan { int blocks; MassBytes bytes; };
+inline MassPlan mass_plan(int B, long long maxF) {
+  const long long blocks = tiles_of(maxF, SH_MASS_BLOCK);
+  MassBytes z;
+  z.mass_part = (size_t)B * blocks * AR_MASS_TERMS * 8; z.mass_out = (size_t)B * sizeof(sh_mass);
+  return {(int)blocks, z};
+}
+
+// Multi-start registration: the coarse stage is sh_register_points on Qc points, the fine stage on all Q, both on the "icp.*" buffers,
+// which take the larger of the two sizes field by field (the split of the walk, and so "icp.cp_part", may be larger for the fewer points).
+inline int ms_coarse_count(int Q, int coarse_points) { return coarse_points == 0 || coarse_points > Q ? Q : coarse_points; }
+inline long long ms_coarse_index(long long j, int Q, int Qc) { return j * Q / Qc; }      // point j of the coarse set
+struct MsPlan { int Qc; IcpPlan coarse, fine; IcpBytes icp; MsBytes bytes; };
+inline MsPlan ms_plan(int B, int Q, bool per_humerus, long long maxF, int K, int coarse_points, int coarse_iter, int fine_iter) {
+  const int Qc = ms_coarse_count(Q, coarse_points);
+  MsPlan p{Qc, icp_plan(B, Qc, per_humerus, maxF, coarse_iter), icp_plan(B, Q, per_humerus, maxF, fine_iter), IcpBytes(), MsBytes()};
+#define X(f, name, T, elem) p.icp.f = std::max(p.coarse.bytes.f, p.fine.bytes.f);
+  ICP_BUFS(X)
+#undef X
+  p.bytes.ms_T0s = (size_t)B * K * 128; p.bytes.ms_points = (per_humerus ? (size_t)B * Qc : (size_t)Qc) * 24;
+  p.bytes.ms_coarse = (size_t)B * K * sizeof(sh_registration); p.bytes.ms_best = (size_t)B * 8; p.bytes.ms_winner = (size_t)B * 4;
+  return p;
+}
+
+// The pick rule: does candidate k (its status, pairs and rms) replace the best so far (winner < 0: none yet)?  The candidates come in
+// ascending k, so "strictly smaller rms" is the order (rms, k).  A candidate with a status, too few pairs or a NaN rms never wins.
+SH_HD bool ms_candidate_wins(int status, int pairs, double rms, int min_pairs, int winner, double best_rms) {
+  if (status != 0 || pairs < min_pairs || !(rms == rms)) return false;
+  return winner < 0 || rms < best_rms;
+}
+
 // ---- what is valid against what -----------------------------------------------------------------------------------------------------
 // One member of sh_ctx.  The resident batch is the context's (batch_gen: every upload / commit / store to "verts" takes a new one);
 // the queries take it as an argument.  RULE: void first, commit on success -- a *_begin voids what the call is about to overwrite and
@@ -487,6 +529,31 @@ inline ArthroError precheck_register(const double* points, int Q, int per_humeru
   if (T0)
     for (int b = 0; b < f.B; ++b)
       if (!rigid_start_ok(T0 + 16 * (size_t)b)) return {SH_ERR_ARG, "T0 of humerus " + std::to_string(b) + " is not a rigid matrix (last row 0 0 0 1, |R^T R - I| <= 1e-9, det > 0)"};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_mass(const ArthroFacts& f) {
+  if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
+  if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
+  if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_multistart(const double* points, int Q, int per_humerus, const double* T0s, int K, const sh_icp_options* coarse,
+                                       int coarse_points, int min_pairs, const sh_icp_options* fine, const ArthroFacts& f) {
+  if (!f.ctx || !points || !T0s || !coarse || !fine) return {SH_ERR_ARG, "bad argument (context, points, T0s and both options must be given)"};
+  if (Q < 1 || Q > SH_CLOSEST_MAX) return {SH_ERR_ARG, "bad argument (Q in 1..1048576)"};
+  if (K < 1 || K > SH_MS_MAX_STARTS || coarse_points < 0 || min_pairs < 6) return {SH_ERR_ARG, "bad argument (K in 1..64, coarse_points >= 0, min_pairs >= 6)"};
+  if (!icp_options_ok(coarse)) return {SH_ERR_ARG, "bad coarse options (metric 0 or 1, max_iter in 1..64, reject > 0, tol >= 0 and finite)"};
+  if (!icp_options_ok(fine)) return {SH_ERR_ARG, "bad fine options (metric 0 or 1, max_iter in 1..64, reject > 0, tol >= 0 and finite)"};
+  if (f.B < 1) return {SH_ERR_STATE, AR_NO_MESHES};
+  if (f.n_pending != 0) return {SH_ERR_STATE, AR_IN_FLIGHT};
+  const long long i = first_bad_point(points, per_humerus ? (size_t)f.B * Q : (size_t)Q);
+  if (i >= 0) return {SH_ERR_ARG, "point " + std::to_string(i) + " has a coordinate that is not finite"};
+  for (int b = 0; b < f.B; ++b)
+    for (int k = 0; k < K; ++k)
+      if (!rigid_start_ok(T0s + 16 * ((size_t)b * K + k)))
+        return {SH_ERR_ARG, "start " + std::to_string(k) + " of humerus " + std::to_string(b) + " is not a rigid matrix (last row 0 0 0 1, |R^T R - I| <= 1e-9, det > 0)"};
   return arthro_ok();
 }
 

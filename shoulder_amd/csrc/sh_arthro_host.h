@@ -1,6 +1,7 @@
 // sh_arthro_host.h -- the entry points of the arthroplasty chain: sh_resect_* (k_resect.h, k_headfit.h, k_seat.h), sh_canal_profile and
 // sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h), the rays against the resident batch, sh_ray_cast / sh_anp_axis_hits (k_rays.h),
-// its closest surface points, sh_closest_points (k_closest.h), its winding numbers, sh_winding_numbers (k_winding.h), and the registration of point sets onto it, sh_register_points (k_icp.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
+// its closest surface points, sh_closest_points (k_closest.h), its winding numbers, sh_winding_numbers (k_winding.h), the registration of point sets onto it, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), and its mass
+// properties, sh_mass_properties (k_mass.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
 // headers and inside its extern "C" block.  A header and not a unit of its own: compiled in a unit that holds only the resection
 // headers, the unchanged k_resect_faces takes 100 VGPRs instead of 92, four waves per SIMD instead of five, so the kernels
 // stay in shoulder_hip.hip and the code that launches them with them.
@@ -423,6 +424,33 @@ static int icp_ensure(sh_ctx* c, const IcpBytes& z) {
   return SH_OK;
 }
 
+// The chain of one registration, enqueued on the context's stream: the mean of the input points (phase 0), then max_iter + 1 evaluations
+// of move -> walk -> join -> sums -> step.  `pts` are the device points (Q, shared or per humerus); "icp.T", "icp.flags", "icp.out" and
+// "icp.hist" are in place.  Both entry points below run exactly this.
+static int icp_chain(sh_ctx* c, const IcpView& v, const double* pts, int Q, int per, const IcpPlan& plan, const sh_icp_options* opt) {
+  const int B = c->B, K = opt->max_iter;
+  const dim3 blocks((unsigned)plan.chunks, (unsigned)B), lanes(SH_ICP_BLOCK);
+  // one pass over the blocks: phase 0 the mean of the input points, phase 1 evaluation k
+  // (LAUNCH ends in HIPCHK(hipGetLastError()): a launch that fails returns SH_ERR_HIP from the lambda, which the callers pass on)
+  auto sum_step = [&](int phase, int k) -> int {
+    LAUNCH(c, "k_icp_sum", k_icp_sum, blocks, lanes, v.verts, v.faces, v.voff, v.foff, pts, (const double*)v.icp_moved,
+           (const sh_closest*)v.icp_near, Q, per, phase, (int)opt->metric, opt->reject, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_part);
+    LAUNCH(c, "k_icp_step", k_icp_step, dim3((unsigned)B), dim3(64), (const double*)v.icp_part, plan.chunks, Q, phase, (int)opt->metric, k, K, opt->tol,
+           v.icp_T, v.icp_flags, v.icp_hist, v.icp_out);
+    return SH_OK;
+  };
+  if (int rc = sum_step(0, 0)) return rc;
+  for (int k = 0; k <= K; ++k) {
+    LAUNCH(c, "k_icp_move", k_icp_move, blocks, lanes, pts, Q, per, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_moved);
+    LAUNCH(c, "k_cp_walk", k_cp_walk, dim3((unsigned)plan.chunks, (unsigned)B, (unsigned)plan.S), dim3(SH_CP_CHUNK), v.verts, v.faces, v.voff, v.foff,
+           (const double*)v.icp_moved, Q, 1, plan.S, v.icp_cp_part);
+    LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.verts, v.faces, v.voff, v.foff, (const double*)v.icp_moved, Q, 1,
+           plan.S, (const CpPart*)v.icp_cp_part, (long long)plan.points, v.icp_near);
+    if (int rc = sum_step(1, k)) return rc;
+  }
+  return SH_OK;
+}
+
 int sh_register_points(sh_ctx* c, const double* points, int Q, int per_humerus, const double* T0, const sh_icp_options* opt, sh_registration* out,
                        double* history) {
   if (const ArthroError e = precheck_register(points, Q, per_humerus, T0, opt, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_register_points", e);
@@ -439,27 +467,109 @@ int sh_register_points(sh_ctx* c, const double* points, int Q, int per_humerus, 
   HIPCHK(c, hipMemsetAsync(v.icp_flags, 0, plan.bytes.icp_flags, c->stream));
   HIPCHK(c, hipMemsetAsync(v.icp_hist, 0, plan.bytes.icp_hist, c->stream));
   HIPCHK(c, hipMemsetAsync(v.icp_out, 0, plan.bytes.icp_out, c->stream));
-  const dim3 blocks((unsigned)plan.chunks, (unsigned)B), lanes(SH_ICP_BLOCK);
-  // one pass over the blocks: phase 0 the mean of the input points, phase 1 evaluation k
-  // (LAUNCH ends in HIPCHK(hipGetLastError()): a launch that fails returns SH_ERR_HIP from the lambda, which the callers pass on)
-  auto sum_step = [&](int phase, int k) -> int {
-    LAUNCH(c, "k_icp_sum", k_icp_sum, blocks, lanes, v.verts, v.faces, v.voff, v.foff, (const double*)v.icp_points, (const double*)v.icp_moved,
-           (const sh_closest*)v.icp_near, Q, per, phase, (int)opt->metric, opt->reject, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_part);
-    LAUNCH(c, "k_icp_step", k_icp_step, dim3((unsigned)B), dim3(64), (const double*)v.icp_part, plan.chunks, Q, phase, (int)opt->metric, k, K, opt->tol,
-           v.icp_T, v.icp_flags, v.icp_hist, v.icp_out);
-    return SH_OK;
-  };
-  if (int rc = sum_step(0, 0)) return rc;
-  for (int k = 0; k <= K; ++k) {
-    LAUNCH(c, "k_icp_move", k_icp_move, blocks, lanes, (const double*)v.icp_points, Q, per, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_moved);
-    LAUNCH(c, "k_cp_walk", k_cp_walk, dim3((unsigned)plan.chunks, (unsigned)B, (unsigned)plan.S), dim3(SH_CP_CHUNK), v.verts, v.faces, v.voff, v.foff,
-           (const double*)v.icp_moved, Q, 1, plan.S, v.icp_cp_part);
-    LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.verts, v.faces, v.voff, v.foff, (const double*)v.icp_moved, Q, 1,
-           plan.S, (const CpPart*)v.icp_cp_part, (long long)plan.points, v.icp_near);
-    if (int rc = sum_step(1, k)) return rc;
-  }
+  if (int rc = icp_chain(c, v, (const double*)v.icp_points, Q, per, plan, opt)) return rc;
   if (out) HIPCHK(c, hipMemcpyAsync(out, v.icp_out, plan.bytes.icp_out, hipMemcpyDeviceToHost, c->stream));
   if (history) HIPCHK(c, hipMemcpyAsync(history, v.icp_hist, plan.bytes.icp_hist, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- multi-start registration (k_ms.h around the chain above); reads the mesh, changes no state of the chain ----
+#define X(f, name, T, ...) T* f = nullptr;
+struct MsView { MS_BUFS(X) };
+#undef X
+static MsView ms_view(sh_ctx* c) {
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  MsView v;
+#define X(f, name, T, ...) v.f = (T*)at(name);
+  MS_BUFS(X)
+#undef X
+  return v;
+}
+static int ms_ensure(sh_ctx* c, const MsBytes& z) {
+  int rc;
+#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
+  MS_BUFS(X)
+#undef X
+  return SH_OK;
+}
+
+int sh_register_multistart(sh_ctx* c, const double* points, int Q, int per_humerus, const double* T0s, int K, const sh_icp_options* coarse,
+                           int coarse_points, int min_pairs, const sh_icp_options* fine, sh_registration* out, sh_registration* coarse_out,
+                           int32_t* winner) {
+  if (const ArthroError e = precheck_multistart(points, Q, per_humerus, T0s, K, coarse, coarse_points, min_pairs, fine, arthro_facts(c)); e.code)
+    return arthro_refuse(c, "sh_register_multistart", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B, per = per_humerus != 0 ? 1 : 0;
+  const MsPlan plan = ms_plan(B, Q, per != 0, c->maxF, K, coarse_points, coarse->max_iter, fine->max_iter);
+  const int Qc = plan.Qc;
+  if (int rc = icp_ensure(c, plan.icp)) return rc;
+  if (int rc = ms_ensure(c, plan.bytes)) return rc;
+  const IcpView v = icp_view(c);
+  const MsView m = ms_view(c);
+  const size_t sets = per ? (size_t)B : 1;
+  std::vector<double> cpts(sets * Qc * 3);      // (pageable: the copy is staged before the call returns)
+  for (size_t s = 0; s < sets; ++s)
+    for (int j = 0; j < Qc; ++j) {
+      const double* p = points + 3 * (s * Q + (size_t)ms_coarse_index(j, Q, Qc));
+      double* q = &cpts[3 * (s * Qc + j)];
+      q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
+    }
+  HIPCHK(c, hipMemcpyAsync(m.ms_points, cpts.data(), plan.bytes.ms_points, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(m.ms_T0s, T0s, plan.bytes.ms_T0s, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(v.icp_points, points, plan.fine.bytes.icp_points, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.icp_moved, 0, plan.icp.icp_moved, c->stream));      // (a humerus without a winner is walked, never moved, in the fine stage)
+  HIPCHK(c, hipMemsetAsync(v.icp_hist, 0, plan.icp.icp_hist, c->stream));
+  const dim3 per_b((unsigned)((B + 63) / 64)), wave(64);
+  for (int k = 0; k < K; ++k) {
+    LAUNCH(c, "k_ms_seed", k_ms_seed, per_b, wave, (const double*)m.ms_T0s, B, K, k, (const sh_registration*)m.ms_coarse, (const int*)m.ms_winner, v.icp_T,
+           v.icp_flags, v.icp_out);
+    if (int rc = icp_chain(c, v, (const double*)m.ms_points, Qc, per, plan.coarse, coarse)) return rc;
+    LAUNCH(c, "k_ms_pick", k_ms_pick, per_b, wave, (const sh_registration*)v.icp_out, B, K, k, min_pairs, m.ms_coarse, m.ms_best, m.ms_winner);
+  }
+  HIPCHK(c, hipMemsetAsync(v.icp_hist, 0, plan.icp.icp_hist, c->stream));
+  LAUNCH(c, "k_ms_seed", k_ms_seed, per_b, wave, (const double*)m.ms_T0s, B, K, -1, (const sh_registration*)m.ms_coarse, (const int*)m.ms_winner, v.icp_T,
+         v.icp_flags, v.icp_out);
+  if (int rc = icp_chain(c, v, (const double*)v.icp_points, Q, per, plan.fine, fine)) return rc;
+  if (out) HIPCHK(c, hipMemcpyAsync(out, v.icp_out, plan.fine.bytes.icp_out, hipMemcpyDeviceToHost, c->stream));
+  if (coarse_out) HIPCHK(c, hipMemcpyAsync(coarse_out, m.ms_coarse, plan.bytes.ms_coarse, hipMemcpyDeviceToHost, c->stream));
+  if (winner) HIPCHK(c, hipMemcpyAsync(winner, m.ms_winner, plan.bytes.ms_winner, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- mass properties of the resident batch (k_mass.h); reads the mesh, changes no state of the chain ----
+static_assert(AR_MASS_TERMS == SH_MASS_TERMS, "sh_arthro.h: mass terms");
+#define X(f, name, T, ...) T* f = nullptr;
+struct MassView { ARTHRO_INPUT_BUFS(X) MASS_BUFS(X) };
+#undef X
+static MassView mass_view(sh_ctx* c) {
+  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
+  MassView v;
+#define X(f, name, T, ...) v.f = (T*)at(name);
+  ARTHRO_INPUT_BUFS(X) MASS_BUFS(X)
+#undef X
+  return v;
+}
+static int mass_ensure(sh_ctx* c, const MassBytes& z) {
+  int rc;
+#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
+  MASS_BUFS(X)
+#undef X
+  return SH_OK;
+}
+
+int sh_mass_properties(sh_ctx* c, sh_mass* out) {
+  if (const ArthroError e = precheck_mass(arthro_facts(c)); e.code) return arthro_refuse(c, "sh_mass_properties", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B;
+  const MassPlan plan = mass_plan(B, c->maxF);
+  if (int rc = mass_ensure(c, plan.bytes)) return rc;
+  const MassView v = mass_view(c);
+  HIPCHK(c, hipMemsetAsync(v.mass_part, 0, plan.bytes.mass_part, c->stream));
+  LAUNCH(c, "k_mass_sum", k_mass_sum, dim3((unsigned)plan.blocks, (unsigned)B), dim3(SH_MASS_BLOCK), v.verts, v.faces, v.voff, v.foff, v.mass_part);
+  LAUNCH(c, "k_mass_join", k_mass_join, dim3((unsigned)B), dim3(64), v.verts, v.voff, v.foff, (const double*)v.mass_part, plan.blocks, v.mass_out);
+  if (out) HIPCHK(c, hipMemcpyAsync(out, v.mass_out, plan.bytes.mass_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -1379,4 +1379,146 @@ SH_HD int icp_step(int metric, int k, int max_iter, double tol, const double* to
   return 0;
 }
 
+// ---- mass properties of the resident batch (include/shoulder_hip.h sh_mass_properties; k_mass.h) ------------------------------
+// Everything below is + - x / sqrt on float64 in the written order (-ffp-contract=off), restated by tests/mass_oracle.py.
+// A row of sums has SH_MASS_TERMS doubles: [0] A2, [1..3] A2 s, [4..9] A2 m, [10..12] n, [13] d, [14..16] d s, [17..22] d m,
+// [23] faces with A2 == 0.0; m runs over ij = 00, 01, 02, 11, 12, 22.
+#define SH_MASS_TERMS 24
+#define SH_MASS_DOUBLES 48      // the doubles of an sh_mass, in its order
+#define SH_MASS_SWEEPS 12       // cyclic Jacobi sweeps of sym3_jacobi: fixed, converged or not
+
+// the terms of one face with the widened corners A, B, C, relative to the pivot o
+SH_HD void mass_face_terms(const double* o, const double* A, const double* B, const double* C, double* t /* SH_MASS_TERMS */) {
+  const double a[3] = {A[0] - o[0], A[1] - o[1], A[2] - o[2]};
+  const double b[3] = {B[0] - o[0], B[1] - o[1], B[2] - o[2]};
+  const double c[3] = {C[0] - o[0], C[1] - o[1], C[2] - o[2]};
+  const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+  const double ac[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+  double n[3], bc[3], m[6];
+  cross3(ab, ac, n);
+  const double A2 = sqrt(dot3(n, n));
+  const double s[3] = {(a[0] + b[0]) + c[0], (a[1] + b[1]) + c[1], (a[2] + b[2]) + c[2]};
+  cross3(b, c, bc);
+  const double d = dot3(a, bc);
+  int idx = 0;
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j) m[idx++] = ((s[i] * s[j] + a[i] * a[j]) + b[i] * b[j]) + c[i] * c[j];
+  t[0] = A2; t[13] = d;
+  for (int k = 0; k < 3; ++k) { t[1 + k] = A2 * s[k]; t[10 + k] = n[k]; t[14 + k] = d * s[k]; }
+  for (int q = 0; q < 6; ++q) { t[4 + q] = A2 * m[q]; t[17 + q] = d * m[q]; }
+  t[23] = A2 == 0.0 ? 1.0 : 0.0;
+}
+
+// sym4_jacobi for a symmetric 3 x 3 (row-major, destroyed: its diagonal becomes the eigenvalues), V the eigenvectors in columns:
+// SH_MASS_SWEEPS sweeps over the pairs (0,1) (0,2) (1,2), the same theta, t, c and s, a pair whose a_pq is 0.0 left alone.
+SH_HD void sym3_jacobi(double* A, double* V) {
+  for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < SH_MASS_SWEEPS; ++sweep)
+    for (int p = 0; p < 2; ++p)
+      for (int q = p + 1; q < 3; ++q) {
+        const double apq = A[3 * p + q];
+        if (apq == 0.0) continue;
+        const double theta = (A[3 * q + q] - A[3 * p + p]) / (2.0 * apq);
+        const double at = fabs(theta);
+        double t = 1.0 / (at + sqrt(theta * theta + 1.0));
+        if (theta < 0.0) t = -t;
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        A[3 * p + p] = A[3 * p + p] - t * apq;
+        A[3 * q + q] = A[3 * q + q] + t * apq;
+        A[3 * p + q] = 0.0; A[3 * q + p] = 0.0;
+        for (int k = 0; k < 3; ++k) {
+          if (k != p && k != q) {
+            const double akp = A[3 * k + p], akq = A[3 * k + q];
+            const double np_ = c * akp - s * akq, nq_ = s * akp + c * akq;
+            A[3 * k + p] = np_; A[3 * p + k] = np_;
+            A[3 * k + q] = nq_; A[3 * q + k] = nq_;
+          }
+          const double vkp = V[3 * k + p], vkq = V[3 * k + q];
+          V[3 * k + p] = c * vkp - s * vkq;
+          V[3 * k + q] = s * vkp + c * vkq;
+        }
+      }
+}
+
+// The frame of a symmetric 3 x 3 given by its upper triangle (00, 01, 02, 11, 12, 22): eigenvalues ascending or descending, among equal
+// ones the first; axes[3 r + k] is component k of axis r.  Each of the first two axes is signed so that its component of largest
+// magnitude is positive (the first among equals), the third is cross3(first, second).  false: something is not finite.
+SH_HD bool mass_frame(const double* up, bool descending, double* eig /* 3 */, double* axes /* 9 */) {
+  double A[9] = {up[0], up[1], up[2], up[1], up[3], up[4], up[2], up[4], up[5]}, V[9];
+  for (int i = 0; i < 9; ++i)
+    if (!icp_finite(A[i])) return false;
+  sym3_jacobi(A, V);
+  int ord[3] = {0, 1, 2};
+  for (int i = 1; i < 3; ++i)      // insertion sort, stable: ties keep their order
+    for (int j = i; j > 0; --j) {
+      const double x = A[4 * ord[j]], y = A[4 * ord[j - 1]];
+      if (!(descending ? x > y : x < y)) break;
+      const int tmp = ord[j]; ord[j] = ord[j - 1]; ord[j - 1] = tmp;
+    }
+  for (int r = 0; r < 3; ++r) {
+    eig[r] = A[4 * ord[r]];
+    for (int k = 0; k < 3; ++k) axes[3 * r + k] = V[3 * k + ord[r]];
+  }
+  for (int r = 0; r < 2; ++r) {
+    int big = 0;
+    for (int k = 1; k < 3; ++k)
+      if (fabs(axes[3 * r + k]) > fabs(axes[3 * r + big])) big = k;
+    if (axes[3 * r + big] < 0.0)
+      for (int k = 0; k < 3; ++k) axes[3 * r + k] = -axes[3 * r + k];
+  }
+  cross3(axes, axes + 3, axes + 6);
+  bool ok = true;
+  for (int r = 0; r < 3; ++r) ok = ok && icp_finite(eig[r]);
+  for (int i = 0; i < 9; ++i) ok = ok && icp_finite(axes[i]);
+  return ok;
+}
+
+// The record of one humerus from its totals T, the pivot o and its number of faces (include/shoulder_hip.h): rec is the doubles of
+// an sh_mass in its order -- [0] area, [1] volume, [2] closure, [3..5] shell_centroid, [6..11] shell_cov, [12..14] shell_eig,
+// [15..23] shell_axes, [24..26] center_mass, [27..35] inertia, [36..38] principal, [39..47] principal_axes -- and irec its int32:
+// faces, degenerate, status, vstatus.  A part that fails leaves its fields +0.0.
+SH_HD void mass_finish(const double* T, const double* o, int nf, double* rec /* SH_MASS_DOUBLES */, int* irec /* 4 */) {
+  for (int i = 0; i < SH_MASS_DOUBLES; ++i) rec[i] = 0.0;
+  irec[0] = nf; irec[1] = (int)T[23]; irec[2] = 0; irec[3] = 0;
+  const double T0 = T[0], T13 = T[13];
+  bool ok = nf > 0 && T0 != 0.0;
+  if (ok) {
+    const double area = T0 / 2.0;
+    double cs[3], C[6], eig[3], axes[9];
+    for (int k = 0; k < 3; ++k) cs[k] = T[1 + k] / (3.0 * T0);
+    int q = 0;
+    for (int i = 0; i < 3; ++i)
+      for (int j = i; j < 3; ++j, ++q) C[q] = T[4 + q] / (12.0 * T0) - cs[i] * cs[j];
+    const double closure = sqrt(dot3(T + 10, T + 10)) / T0;
+    ok = icp_finite(area) && icp_finite(closure) && mass_frame(C, true, eig, axes);
+    for (int k = 0; k < 3; ++k) ok = ok && icp_finite(cs[k] + o[k]);
+    if (ok) {
+      rec[0] = area; rec[2] = closure;
+      for (int k = 0; k < 3; ++k) { rec[3 + k] = cs[k] + o[k]; rec[12 + k] = eig[k]; }
+      for (int i = 0; i < 6; ++i) rec[6 + i] = C[i];
+      for (int i = 0; i < 9; ++i) rec[15 + i] = axes[i];
+    }
+  }
+  if (!ok) irec[2] = SH_ERR_GEOMETRY_DEV;
+  bool vok = nf > 0 && T13 != 0.0;
+  if (vok) {
+    const double volume = T13 / 6.0;
+    double cm[3], S[6], I[6], eig[3], axes[9];
+    for (int k = 0; k < 3; ++k) cm[k] = T[14 + k] / (4.0 * T13);
+    int q = 0;
+    for (int i = 0; i < 3; ++i)
+      for (int j = i; j < 3; ++j, ++q) S[q] = T[17 + q] / 120.0 - (volume * cm[i]) * cm[j];
+    I[0] = S[3] + S[5]; I[1] = -S[1]; I[2] = -S[2]; I[3] = S[0] + S[5]; I[4] = -S[4]; I[5] = S[0] + S[3];
+    vok = icp_finite(volume) && mass_frame(I, false, eig, axes);
+    for (int k = 0; k < 3; ++k) vok = vok && icp_finite(cm[k] + o[k]);
+    if (vok) {
+      rec[1] = volume;
+      for (int k = 0; k < 3; ++k) { rec[24 + k] = cm[k] + o[k]; rec[36 + k] = eig[k]; }
+      rec[27] = I[0]; rec[28] = I[1]; rec[29] = I[2]; rec[30] = I[1]; rec[31] = I[3]; rec[32] = I[4]; rec[33] = I[2]; rec[34] = I[4]; rec[35] = I[5];
+      for (int i = 0; i < 9; ++i) rec[39 + i] = axes[i];
+    }
+  }
+  if (!vok) irec[3] = SH_ERR_GEOMETRY_DEV;
+}
+
 }  // namespace sh

@@ -19,6 +19,8 @@
 #include "k_closest.h"
 #include "k_winding.h"
 #include "k_icp.h"
+#include "k_ms.h"
+#include "k_mass.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -484,10 +486,10 @@ static int stl_enqueue_emit(sh_ctx* timed, hipStream_t st, int B, const StlPlan&
 }
 #undef STL_LAUNCH
 
-// "cp.out" (sh_closest_points), "wn.out" (sh_winding_numbers), "icp.out" and "icp.near" (sh_register_points) answer for the batch they
-// were asked about: a new batch removes them
+// "cp.out" (sh_closest_points), "wn.out" (sh_winding_numbers), "icp.out" and "icp.near" (sh_register_points), "mass.out" and "mass.part"
+// (sh_mass_properties) answer for the batch they were asked about: a new batch removes them
 static void drop_closest(sh_ctx* c) {
-  for (const char* name : {"cp.out", "wn.out", "icp.out", "icp.near"}) {
+  for (const char* name : {"cp.out", "wn.out", "icp.out", "icp.near", "mass.out", "mass.part"}) {
     auto it = c->bufs.find(name);
     if (it == c->bufs.end()) continue;
     if (it->second.p) (void)hipFree(it->second.p);

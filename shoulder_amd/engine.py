@@ -46,6 +46,29 @@ def _mat4(T):
     return T
 
 
+def principal_start_matrices(cm, axes, points, rolls=8):
+    """The starts of Engine.principal_starts for one humerus -> ((2 * rolls, 4, 4), the ratio of the two largest covariance
+    eigenvalues of the points).  cm, axes: the centroid and the frame of the mesh (rows are axes, the long one first, right-handed)."""
+    cm, Xm = np.asarray(cm, np.float64), np.asarray(axes, np.float64).reshape(3, 3).T
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    cp = p.mean(axis=0)
+    d = p - cp
+    w, V = np.linalg.eigh(d.T @ d / float(len(p)))
+    Xp = np.ascontiguousarray(V[:, ::-1])
+    Xp[:, 2] = np.cross(Xp[:, 0], Xp[:, 1])
+    T = np.zeros((2 * rolls, 4, 4))
+    for phi, F in enumerate((np.identity(3), np.diag([-1.0, 1.0, -1.0]))):
+        for r in range(rolls):
+            a = 2.0 * np.pi * r / rolls
+            Rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(a), -np.sin(a)], [0.0, np.sin(a), np.cos(a)]])
+            R = Xm @ Rx @ F @ Xp.T
+            k = phi * rolls + r
+            T[k, :3, :3], T[k, :3, 3], T[k, 3, 3] = R, cm - R @ cp, 1.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = float(w[2] / w[1])
+    return T, ratio
+
+
 class Engine:
     def __init__(self, device=0, stream=None):
         self.L = _lib.load()
@@ -693,6 +716,89 @@ class Engine:
         self._chk(self.L.sh_register_points(self.h, _ptr(p), Q, per, _ptr(t0) if t0 is not None else None, ctypes.byref(opt), _ptr(out),
                                             _ptr(hist) if hist is not None else None))
         return (out, hist) if history else out
+
+    # ---- mass properties of the resident batch (include/shoulder_hip.h sh_mass_properties) -------------------------------------
+    def mass_properties(self):
+        """`mesh.area`, `volume`, `center_mass`, `moment_inertia`, `principal_inertia_components` and `principal_inertia_vectors` of
+        every resident humerus in one device pass -> a structured array (B,) of _lib.MASS_DTYPE: area, volume (signed: negative for a
+        mesh stored inside-out), closure (0 on a closed mesh, about cap area / area on an open one), shell_centroid / shell_cov /
+        shell_eig (descending) / shell_axes (rows, long axis first) of the surface itself, center_mass / inertia (density 1, about the
+        centre of mass) / principal (ascending) / principal_axes (rows) of the solid, faces, degenerate (faces of zero area), status
+        (shell) and vstatus (volume: set, with zeros, for a mesh that encloses nothing).  Points in CT.  Needs no run."""
+        out = np.zeros(max(self.B, 0), dtype=_lib.MASS_DTYPE)
+        self._chk(self.L.sh_mass_properties(self.h, _ptr(out)))
+        return out
+
+    # ---- multi-start registration (include/shoulder_hip.h sh_register_multistart) -----------------------------------------------
+    def _points_arg(self, points):
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
+            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
+        return p
+
+    def principal_starts(self, points, rolls=8, with_ratios=False):
+        """Starting transforms for register_multistart from principal frames -> (B, 2 * rolls, 4, 4).  The mesh frame is shell_centroid
+        and shell_axes of mass_properties (device); the point frame is the mean and the covariance eigenvectors of the points,
+        descending, the third set to the cross product.  Start k = phi * rolls + r is R = Xm Rx(2 pi r / rolls) F_phi Xp^T,
+        t = cm - R cp, with F_0 the identity and F_1 = diag(-1, 1, -1), which reverses the long axis and stays proper: both directions
+        of the long axis times a sweep of rolls about it, because a humerus' long axis is sharp and its transverse axes are not.
+        Ordinary NumPy.  with_ratios=True also returns the ratio of the two largest shell eigenvalues of every mesh (B,) and of its
+        points (B,): near 1 the shape has no long axis and the starts are arbitrary."""
+        p = self._points_arg(points)
+        if int(rolls) < 1 or 2 * int(rolls) > _lib.MS_MAX_STARTS:
+            raise ValueError("rolls must be in 1..32")
+        m = self.mass_properties()
+        if np.any(m["status"] != 0):
+            raise ShoulderHipError(int(m["status"][m["status"] != 0][0]), "principal_starts: a mesh has no surface frame (no faces, no area)")
+        T, rp = np.zeros((self.B, 2 * int(rolls), 4, 4)), np.zeros(self.B)
+        for b in range(self.B):
+            T[b], rp[b] = principal_start_matrices(m[b]["shell_centroid"], m[b]["shell_axes"], p[b] if p.ndim == 3 else p, int(rolls))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rm = m["shell_eig"][:, 0] / m["shell_eig"][:, 1]
+        return (T, rm, rp) if with_ratios else T
+
+    def register_multistart(self, points, T0s, coarse=None, coarse_points=0, min_pairs=6, fine=None):
+        """sh_register_multistart: K starts per humerus (T0s: (B, K, 4, 4)), a coarse registration of the subsampled points from each, the
+        fine registration of all points from the best -> (records (B,), coarse records (B, K), winner (B,) int32, -1 where no start
+        qualified: that record has status SH_ERR_GEOMETRY and T = T0s[b][0]).  coarse / fine: dicts of metric, max_iter, reject, tol as
+        in register.  Every record is what register returns for those points, that start and those options, byte for byte."""
+        p = self._points_arg(points)
+        t0 = np.ascontiguousarray(T0s, dtype=np.float64)
+        if t0.ndim != 4 or t0.shape[0] != self.B or t0.shape[2:] != (4, 4):
+            raise ValueError("T0s must have shape (B, K, 4, 4)")
+
+        def options(o):
+            o = dict(dict(metric="plane", max_iter=20, reject=np.inf, tol=0.0), **(o or {}))
+            if o["metric"] not in ("point", "plane"):
+                raise ValueError('metric must be "point" or "plane"')
+            return _lib.IcpOptions(_lib.ICP_PLANE if o["metric"] == "plane" else _lib.ICP_POINT, int(o["max_iter"]), float(o["reject"]), float(o["tol"]))
+        co, fo = options(coarse), options(fine)
+        K = t0.shape[1]
+        out = np.zeros(self.B, dtype=_lib.REGISTRATION_DTYPE)
+        cand = np.zeros((self.B, K) if 1 <= K <= _lib.MS_MAX_STARTS else (0,), dtype=_lib.REGISTRATION_DTYPE)
+        winner = np.zeros(self.B, dtype=np.int32)
+        self._chk(self.L.sh_register_multistart(self.h, _ptr(p), p.shape[-2], int(p.ndim == 3), _ptr(t0), K, ctypes.byref(co), int(coarse_points),
+                                                int(min_pairs), ctypes.byref(fo), _ptr(out), _ptr(cand), _ptr(winner)))
+        return out, cand, winner
+
+    def register_global(self, points, rolls=8, coarse_points=512, coarse_iter=4, min_pairs=None, **fine_options):
+        """`trimesh.registration.mesh_other` for points in an UNKNOWN pose: principal_starts (2 * rolls starts per humerus), coarse_iter
+        plane-metric updates on coarse_points of the points from each, the registration of all points from the best (fine_options:
+        metric, max_iter, reject, tol as in register; the coarse stage shares `reject`) -> (records (B,) of _lib.REGISTRATION_DTYPE,
+        info) with info = dict(winner (B,), coarse (B, 2 * rolls) records, mesh_ratio (B,), points_ratio (B,): the ratio of the two
+        largest shell eigenvalues of each mesh and of its points).  min_pairs=None: half the coarse set, at least 6; a start with
+        fewer accepted pairs cannot win.  A humerus none of whose starts qualified has status SH_ERR_GEOMETRY and winner -1.
+        The starts rest on the long axis: A NEAR-ROUND SHAPE (a ratio near 1: a resected head, a sphere) HAS NO LONG AXIS AND ITS
+        STARTS ARE ARBITRARY -- the call then is a multi-start from 2 * rolls unrelated poses and nothing more."""
+        p = self._points_arg(points)
+        T0s, rm, rp = self.principal_starts(p, rolls, with_ratios=True)
+        Q = p.shape[-2]
+        Qc = Q if coarse_points == 0 or coarse_points > Q else int(coarse_points)
+        if min_pairs is None:
+            min_pairs = max(6, Qc // 2)
+        coarse = dict(metric="plane", max_iter=int(coarse_iter), reject=fine_options.get("reject", np.inf), tol=0.0)
+        out, cand, winner = self.register_multistart(p, T0s, coarse=coarse, coarse_points=coarse_points, min_pairs=min_pairs, fine=fine_options)
+        return out, dict(winner=winner, coarse=cand, mesh_ratio=rm, points_ratio=rp, starts=T0s)
 
     # ---- named buffers -----------------------------------------------------------------------------
     def fetch(self, name, dtype, shape=None):
