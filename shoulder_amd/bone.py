@@ -64,6 +64,12 @@ def _inv(T):
     return np.linalg.inv(R) @ np.linalg.inv(t)
 
 
+def _registration_info(rec):
+    """what Bone.register reports of one _lib.REGISTRATION_DTYPE record beside the matrix"""
+    return dict(rms=float(rec["rms"]), rms_first=float(rec["rms_first"]), pairs=int(rec["pairs"]), iterations=int(rec["iterations"]),
+                converged=bool(rec["converged"]), min_pivot=float(rec["min_pivot"]))
+
+
 def _scatter(pts, name, **kw):
     """One plotly trace per landmark, as the reference's `_graph_obj` methods build them (e.g. canal.py:132-142)."""
     import plotly.graph_objects as go
@@ -574,9 +580,8 @@ class ProximalHumerus(Bone):
             if rec["status"] != 0:
                 raise ValueError(f"register failed with status {int(rec['status'])}: no start qualified (winner {int(more['winner'][0])}), fewer than six "
                                  f"accepted pairs or a singular system (pairs {int(rec['pairs'])}, iterations {int(rec['iterations'])})")
-            info = dict(rms=float(rec["rms"]), rms_first=float(rec["rms_first"]), pairs=int(rec["pairs"]), iterations=int(rec["iterations"]),
-                        converged=bool(rec["converged"]), min_pivot=float(rec["min_pivot"]), winner=int(more["winner"][0]),
-                        coarse_rms=np.array(more["coarse"][0]["rms"]), mesh_ratio=float(more["mesh_ratio"][0]), points_ratio=float(more["points_ratio"][0]))
+            info = dict(_registration_info(rec), winner=int(more["winner"][0]), coarse_rms=np.array(more["coarse"][0]["rms"]),
+                        mesh_ratio=float(more["mesh_ratio"][0]), points_ratio=float(more["points_ratio"][0]))
             return M @ np.array(rec["T"]) @ Mi, info
         T0 = None
         if initial is not None:
@@ -589,9 +594,7 @@ class ProximalHumerus(Bone):
         if rec["status"] != 0:
             raise ValueError(f"register failed with status {int(rec['status'])}: fewer than six accepted pairs or a singular system "
                              f"(pairs {int(rec['pairs'])}, iterations {int(rec['iterations'])})")
-        info = dict(rms=float(rec["rms"]), rms_first=float(rec["rms_first"]), pairs=int(rec["pairs"]), iterations=int(rec["iterations"]),
-                    converged=bool(rec["converged"]), min_pivot=float(rec["min_pivot"]))
-        return M @ np.array(rec["T"]) @ Mi, info
+        return M @ np.array(rec["T"]) @ Mi, _registration_info(rec)
 
     # -- coordinate systems (bone.py:53-105, :146-157) --------------------------------------------------
     def _mesh_in(self, T):

@@ -158,7 +158,7 @@ int sh_gather_landmarks(sh_ctx** ctxs, int n, sh_landmarks* out_root) {
   for (int i = 0; i < n; ++i) {
     sh_ctx* c = ctxs[i];
     if (c->rec_rows != rows) return fail(c0, SH_ERR_STATE, "sh_gather_landmarks: the contexts are set to different record formats (sh_set_record_rows)");
-    if (c->B <= 0 || c->bufs.find("landmarks") == c->bufs.end() || !c->bufs["landmarks"].p)
+    if (c->B <= 0 || !c->at("landmarks"))
       return fail(c0, SH_ERR_STATE, "sh_gather_landmarks: a context has no run to report");
     total += c->B;
     off[i + 1] = total;

@@ -1,10 +1,9 @@
 // sh_arthro_host.h -- the entry points of the arthroplasty chain: sh_resect_* (k_resect.h, k_headfit.h, k_seat.h), sh_canal_profile and
-// sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h), the rays against the resident batch, sh_ray_cast / sh_anp_axis_hits (k_rays.h),
-// its closest surface points, sh_closest_points (k_closest.h), its winding numbers, sh_winding_numbers (k_winding.h), the registration of point sets onto it, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), and its mass
-// properties, sh_mass_properties (k_mass.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
-// headers and inside its extern "C" block.  A header and not a unit of its own: compiled in a unit that holds only the resection
-// headers, the unchanged k_resect_faces takes 100 VGPRs instead of 92, four waves per SIMD instead of five, so the kernels
-// stay in shoulder_hip.hip and the code that launches them with them.
+// sh_resect_stems (k_stem.h), sh_resect_plan (k_plan.h).  Host code of shoulder_hip.hip, included there EXACTLY ONCE, behind the kernel
+// headers and inside its extern "C" block, with sh_query_host.h (the queries of the resident batch) right behind it.  Headers and not
+// units of their own: compiled in a unit that holds only the resection headers, the unchanged k_resect_faces takes 100 VGPRs instead
+// of 92, four waves per SIMD instead of five, so the kernels stay in shoulder_hip.hip and the code that launches them
+// with them.
 // What the chain DECIDES is sh_arthro.h (checks, first refusal, pass plan, buffer sizes, ArthroState).  Every entry point here reads:
 // precheck -> ensure -> view -> state begin -> enqueue -> copies back -> synchronise -> state end.
 #pragma once
@@ -12,46 +11,27 @@
 static_assert(AR_RS_TILE == SH_RS_TILE && AR_HF_WORDS == SH_HF_WORDS && AR_RESECT_PART_BYTES == sizeof(ResectPart), "sh_arthro.h: resection tile, moment words, slab entry");
 static_assert(AR_CANAL_TILE == SH_CANAL_TILE && AR_PLAN_TILE == SH_PLAN_TILE && AR_PLAN_TOP_BYTES == sizeof(PlanTop) && AR_PLAN_TERM_BYTES == sizeof(PlanTerm),
               "sh_arthro.h: canal and plan tiles, PlanTop, PlanTerm");
-static_assert(AR_RAY_TILE == SH_RAY_TILE && AR_RAY_CHUNK == SH_RAY_CHUNK && AR_RAY_KEY_BYTES == sizeof(RayKey), "sh_arthro.h: ray tile, ray chunk, RayKey");
-static_assert(AR_CP_TILE == SH_CP_TILE && AR_CP_CHUNK == SH_CP_CHUNK && AR_CP_PART_BYTES == sizeof(CpPart), "sh_arthro.h: closest-point tile, chunk, CpPart");
-static_assert(AR_WN_TILE == SH_WN_TILE && AR_WN_CHUNK == SH_WN_CHUNK && AR_WN_BLOCK == SH_WIND_BLOCK, "sh_arthro.h: winding tile, chunk, block");
-
-// The named buffers of a call as typed pointers (ARTHRO_BUFS, ARTHRO_INPUT_BUFS), resolved once per call BEHIND the call's
-// arthro_ensure (which may re-allocate them); a buffer that is not there is null.  No window offset: the chain works on the whole batch.
-#define X(f, name, T, ...) T* f = nullptr;
-struct ArthroView { ARTHRO_INPUT_BUFS(X) ARTHRO_BUFS(X) };
-#undef X
 
 static ArthroFacts arthro_facts(const sh_ctx* c) {
   if (!c) return ArthroFacts{false, 0, 0, 0, false, nullptr};
-  return ArthroFacts{true, c->B, c->n_pending, c->batch_gen, c->bufs.find("landmarks") != c->bufs.end(), &c->arthro};
+  return ArthroFacts{true, c->B, c->n_pending, c->batch_gen, c->at("landmarks") != nullptr, &c->arthro};
 }
 
 static int arthro_refuse(sh_ctx* c, const char* fn, const ArthroError& e) { return fail(c, e.code, std::string(fn) + ": " + e.text); }
 
-// `groups`: which of the chain's own buffers the call touches (the inputs always); the others stay null and cost no lookup
+// The view of a call of the chain (sh_ctx.h view_of, behind the call's ensure_bytes), with its two rules.  `groups`: which of the
+// chain's own lists the call touches (the mesh always); the others stay null and cost no lookup.  `lm` is null without a run of the
+// resident batch with the anatomic neck and the csys.
 enum : unsigned { AV_RESECT = 1, AV_CANAL = 2, AV_STEM = 4, AV_PLAN = 8 };
 static ArthroView arthro_view(sh_ctx* c, unsigned groups) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
   ArthroView v;
-#define X(f, name, T, ...) v.f = (T*)at(name);
-  ARTHRO_INPUT_BUFS(X)
-  if (groups & AV_RESECT) { ARTHRO_RESECT_BUFS(X) }
-  if (groups & AV_CANAL) { ARTHRO_CANAL_BUFS(X) }
-  if (groups & AV_STEM) { ARTHRO_STEM_BUFS(X) }
-  if (groups & AV_PLAN) { ARTHRO_PLAN_BUFS(X) }
-#undef X
+  static_cast<MeshBufs&>(v) = view_of<MeshBufs>(c);
+  if (groups & AV_RESECT) static_cast<ResectBufs&>(v) = view_of<ResectBufs>(c);
+  if (groups & AV_CANAL) static_cast<CanalBufs&>(v) = view_of<CanalBufs>(c);
+  if (groups & AV_STEM) static_cast<StemBufs&>(v) = view_of<StemBufs>(c);
+  if (groups & AV_PLAN) static_cast<PlanBufs&>(v) = view_of<PlanBufs>(c);
   if (!c->arthro.has_records(c->batch_gen)) v.lm = nullptr;
   return v;
-}
-
-// the buffers of a call at the sizes of its plan (0: not this call's), shared / scratch stride
-static int arthro_ensure(sh_ctx* c, const ArthroBytes& z) {
-  int rc;
-#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
-  ARTHRO_BUFS(X)
-#undef X
-  return SH_OK;
 }
 
 struct ResectPass { int P, p0, pc, b0, nb, tmax; };      // planes [p0, p0 + pc) of humeri [b0, b0 + nb), tmax tiles per humerus in the slabs
@@ -95,7 +75,7 @@ static int resect_run(sh_ctx* c, const ResectRequest& q) {
   const int B = c->B, P = q.P;
   const size_t n = (size_t)B * P;
   const ResectPlan plan = resect_plan(B, P, c->maxF, q.level, q.K, q.offs != nullptr);
-  if (int rc = arthro_ensure(c, plan.bytes)) return rc;
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
   const ArthroView v = arthro_view(c, AV_RESECT);
   c->arthro.resect_begin();
   if (q.offs) {
@@ -172,7 +152,7 @@ int sh_canal_profile(sh_ctx* c, const sh_canal_grid* g, const double* frames, do
   const int B = c->B, L = g->L, A = g->A;
   const CanalPlan plan = canal_plan(B, L, A, c->maxF);
   const size_t n = plan.rays;
-  if (int rc = arthro_ensure(c, plan.bytes)) return rc;
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
   const ArthroView v = arthro_view(c, AV_CANAL);
   c->arthro.profile_begin();
   const double two_pi = 2.0 * 3.14159265358979323846;
@@ -206,7 +186,7 @@ int sh_resect_stems(sh_ctx* c, const sh_stem* stems, int K, sh_stem_fit* out) {
   const int B = c->B, P = c->arthro.P();
   const size_t n = (size_t)B * P * K;
   c->arthro.stems_begin();      // in front of the ensure: "stem.out" may be resized
-  if (int rc = arthro_ensure(c, stem_bytes(B, P, K))) return rc;
+  if (int rc = ensure_bytes(c, stem_bytes(B, P, K))) return rc;
   const ArthroView v = arthro_view(c, AV_RESECT | AV_CANAL | AV_STEM);
   const sh_canal_grid& g = c->arthro.grid();
   HIPCHK(c, hipMemcpyAsync(v.stem_catalogue, stems, (size_t)K * sizeof(sh_stem), hipMemcpyHostToDevice, c->stream));
@@ -226,7 +206,7 @@ int sh_resect_plan(sh_ctx* c, const sh_plan_rule* rule, const uint64_t* compat, 
   const int B = c->B, P = c->arthro.P(), Kh = c->arthro.Kh(), Ks = c->arthro.Ks();
   const PlanPlan plan = plan_plan(B, P, Kh, Ks, N, c->maxV);
   const int tmax = plan.tmax;
-  if (int rc = arthro_ensure(c, plan.bytes)) return rc;
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
   const ArthroView v = arthro_view(c, AV_RESECT | AV_CANAL | AV_STEM | AV_PLAN);
   const double* d_rp = ref_planes ? v.plan_ref_planes : nullptr;      // the reference planes are the caller's or the records'
   const sh_landmarks* d_lm = ref_planes ? nullptr : v.lm;
@@ -247,329 +227,6 @@ int sh_resect_plan(sh_ctx* c, const sh_plan_rule* rule, const uint64_t* compat, 
          (const unsigned long long*)v.plan_compat, P, Kh, Ks, N, v.plan_ref, v.plan_out);
   HIPCHK(c, hipMemcpyAsync(out, v.plan_out, (size_t)B * N * sizeof(sh_plan), hipMemcpyDeviceToHost, c->stream));
   if (ref_out) HIPCHK(c, hipMemcpyAsync(ref_out, v.plan_ref, (size_t)B * sizeof(sh_plan_ref), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
-// ---- rays against the resident batch, every hit (k_rays.h); reads the mesh (and, for the anatomic-neck rays, the last run), changes no state ----
-#define X(f, name, T, ...) T* f = nullptr;
-struct RayView { ARTHRO_INPUT_BUFS(X) RAY_BUFS(X) };
-#undef X
-static RayView ray_view(sh_ctx* c) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  RayView v;
-#define X(f, name, T, ...) v.f = (T*)at(name);
-  ARTHRO_INPUT_BUFS(X) RAY_BUFS(X)
-#undef X
-  return v;
-}
-static int ray_ensure(sh_ctx* c, const RayBytes& z) {
-  int rc;
-#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
-  RAY_BUFS(X)
-#undef X
-  return SH_OK;
-}
-
-// count -> scan -> the total to the host -> "ray.pool" -> fill -> sort -> copies back.  "ray.rays" (and "ray.status" with `box`) are filled
-// by the caller on the stream; T_obb / hstatus: the box transforms and the humeri to leave out (sh_anp_axis_hits), or null.
-static int ray_run(sh_ctx* c, const RayPlan& plan, int R, int per_humerus, int cap, const double* T_obb, const int* hstatus, sh_ray_hit* hits, int32_t* counts) {
-  int rc;
-  const int B = c->B;
-  const size_t n = plan.rays;
-  RayView v = ray_view(c);
-  const bool box = T_obb != nullptr;
-  HIPCHK(c, hipMemsetAsync(v.ray_counts, 0, n * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.ray_cursor, 0, n * 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.ray_blockhit, 0, plan.bytes.ray_blockhit, c->stream));
-  const dim3 grid((unsigned)plan.tmax, (unsigned)B, (unsigned)plan.chunks), block(SH_RAY_TILE);
-  LAUNCH(c, "k_ray_count", box ? k_ray_count<true> : k_ray_count<false>, grid, block, v.verts, v.faces, v.voff, v.foff, T_obb, hstatus, (const double*)v.ray_rays, R,
-         per_humerus, v.ray_counts, v.ray_blockhit);
-  LAUNCH(c, "k_ray_scan", k_ray_scan, dim3(1), dim3(1024), (const int*)v.ray_counts, (long long)n, v.ray_offs);
-  unsigned long long total = 0;
-  HIPCHK(c, hipMemcpyAsync(&total, v.ray_offs + n, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  ENS_SHARED("ray.pool", ray_pool_bytes(total), 8);
-  v = ray_view(c);
-  LAUNCH(c, "k_ray_fill", box ? k_ray_fill<true> : k_ray_fill<false>, grid, block, v.verts, v.faces, v.voff, v.foff, T_obb, hstatus, (const double*)v.ray_rays, R,
-         per_humerus, (const unsigned long long*)v.ray_offs, v.ray_cursor, v.ray_pool, v.ray_blockhit);
-  LAUNCH(c, "k_ray_sort", box ? k_ray_sort<true> : k_ray_sort<false>, dim3((unsigned)n), dim3(64), (const double*)v.ray_rays, R, per_humerus,
-         (const unsigned long long*)v.ray_offs, (const int*)v.ray_cursor, (const RayKey*)v.ray_pool, T_obb, cap, v.ray_hits);
-  if (hits) HIPCHK(c, hipMemcpyAsync(hits, v.ray_hits, n * cap * sizeof(sh_ray_hit), hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIPCHK(c, hipMemcpyAsync(counts, v.ray_counts, n * 4, hipMemcpyDeviceToHost, c->stream));
-  return SH_OK;
-}
-
-int sh_ray_cast(sh_ctx* c, const sh_ray* rays, int R, int per_humerus, int cap, sh_ray_hit* hits, int32_t* counts) {
-  if (const ArthroError e = precheck_ray_cast(rays, R, per_humerus, cap, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_ray_cast", e);
-  HIPCHK(c, hipSetDevice(c->device));
-  const RayPlan plan = ray_plan(c->B, R, per_humerus != 0, cap, c->maxF, false);
-  if (int rc = ray_ensure(c, plan.bytes)) return rc;
-  const RayView v = ray_view(c);
-  HIPCHK(c, hipMemcpyAsync(v.ray_rays, rays, plan.bytes.ray_rays, hipMemcpyHostToDevice, c->stream));
-  if (int rc = ray_run(c, plan, R, per_humerus != 0, cap, nullptr, nullptr, hits, counts)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
-int sh_anp_axis_hits(sh_ctx* c, int cap, sh_ray_hit* hits, int32_t* counts, int32_t* status) {
-  if (const ArthroError e = precheck_anp_hits(cap, status, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_anp_axis_hits", e);
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  const double* plane = (const double*)at("anp.plane");
-  const double* T_obb = (const double*)at("obb_transform");
-  const sh_landmarks* lm = (const sh_landmarks*)at("landmarks");
-  if (!plane || !T_obb || !lm) return fail(c, SH_ERR_STATE, "sh_anp_axis_hits: the buffers of the anatomic-neck stage are not there");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int B = c->B;
-  const RayPlan plan = ray_plan(B, 4, true, cap, c->maxF, true);
-  if (int rc = ray_ensure(c, plan.bytes)) return rc;
-  const RayView v = ray_view(c);
-  LAUNCH(c, "k_ray_anp_rays", k_ray_anp_rays, dim3((unsigned)((B + 63) / 64)), dim3(64), lm, plane, B, v.ray_rays, v.ray_status);
-  if (int rc = ray_run(c, plan, 4, 1, cap, T_obb, (const int*)v.ray_status, hits, counts)) return rc;
-  HIPCHK(c, hipMemcpyAsync(status, v.ray_status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
-// ---- closest surface points of the resident batch (k_closest.h); reads the mesh, changes no state of the chain ----
-#define X(f, name, T, ...) T* f = nullptr;
-struct CpView { ARTHRO_INPUT_BUFS(X) CP_BUFS(X) };
-#undef X
-static CpView cp_view(sh_ctx* c) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  CpView v;
-#define X(f, name, T, ...) v.f = (T*)at(name);
-  ARTHRO_INPUT_BUFS(X) CP_BUFS(X)
-#undef X
-  return v;
-}
-static int cp_ensure(sh_ctx* c, const CpBytes& z) {
-  int rc;
-#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
-  CP_BUFS(X)
-#undef X
-  return SH_OK;
-}
-
-int sh_closest_points(sh_ctx* c, const double* points, int Q, int per_humerus, sh_closest* out) {
-  if (const ArthroError e = precheck_closest(points, Q, per_humerus, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_closest_points", e);
-  HIPCHK(c, hipSetDevice(c->device));
-  const CpPlan plan = cp_plan(c->B, Q, per_humerus != 0, c->maxF);
-  if (int rc = cp_ensure(c, plan.bytes)) return rc;
-  const CpView v = cp_view(c);
-  HIPCHK(c, hipMemcpyAsync(v.cp_points, points, plan.bytes.cp_points, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_cp_walk", k_cp_walk, dim3((unsigned)plan.chunks, (unsigned)c->B, (unsigned)plan.S), dim3(SH_CP_CHUNK), v.verts, v.faces, v.voff, v.foff,
-         (const double*)v.cp_points, Q, per_humerus != 0 ? 1 : 0, plan.S, v.cp_part);
-  LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.verts, v.faces, v.voff, v.foff, (const double*)v.cp_points, Q,
-         per_humerus != 0 ? 1 : 0, plan.S, (const CpPart*)v.cp_part, (long long)plan.points, v.cp_out);
-  if (out) HIPCHK(c, hipMemcpyAsync(out, v.cp_out, plan.bytes.cp_out, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
-// ---- generalized winding numbers of the resident batch (k_winding.h); reads the mesh, changes no state of the chain ----
-#define X(f, name, T, ...) T* f = nullptr;
-struct WnView { ARTHRO_INPUT_BUFS(X) WN_BUFS(X) };
-#undef X
-static WnView wn_view(sh_ctx* c) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  WnView v;
-#define X(f, name, T, ...) v.f = (T*)at(name);
-  ARTHRO_INPUT_BUFS(X) WN_BUFS(X)
-#undef X
-  return v;
-}
-static int wn_ensure(sh_ctx* c, const WnBytes& z) {
-  int rc;
-#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
-  WN_BUFS(X)
-#undef X
-  return SH_OK;
-}
-
-int sh_winding_numbers(sh_ctx* c, const double* points, int Q, int per_humerus, sh_winding* out) {
-  if (const ArthroError e = precheck_winding(points, Q, per_humerus, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_winding_numbers", e);
-  HIPCHK(c, hipSetDevice(c->device));
-  const WnPlan plan = wn_plan(c->B, Q, per_humerus != 0, c->maxF);
-  if (int rc = wn_ensure(c, plan.bytes)) return rc;
-  const WnView v = wn_view(c);
-  HIPCHK(c, hipMemcpyAsync(v.wn_points, points, plan.bytes.wn_points, hipMemcpyHostToDevice, c->stream));
-  LAUNCH(c, "k_wn_walk", k_wn_walk, dim3((unsigned)plan.chunks, (unsigned)c->B, (unsigned)plan.S), dim3(SH_WN_CHUNK), v.verts, v.faces, v.voff, v.foff,
-         (const double*)v.wn_points, Q, per_humerus != 0 ? 1 : 0, plan.S, plan.stride, v.wn_part);
-  LAUNCH(c, "k_wn_join", k_wn_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.foff, Q, plan.S, plan.stride, (const double*)v.wn_part,
-         (long long)plan.points, v.wn_out);
-  if (out) HIPCHK(c, hipMemcpyAsync(out, v.wn_out, plan.bytes.wn_out, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
-// ---- rigid registration of point sets onto the resident batch (k_icp.h); reads the mesh, changes no state of the chain ----
-static_assert(AR_ICP_TERMS == SH_ICP_TERMS && AR_ICP_TSTRIDE == SH_ICP_TSTRIDE, "sh_arthro.h: registration terms, stride of icp.T");
-#define X(f, name, T, ...) T* f = nullptr;
-struct IcpView { ARTHRO_INPUT_BUFS(X) ICP_BUFS(X) };
-#undef X
-static IcpView icp_view(sh_ctx* c) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  IcpView v;
-#define X(f, name, T, ...) v.f = (T*)at(name);
-  ARTHRO_INPUT_BUFS(X) ICP_BUFS(X)
-#undef X
-  return v;
-}
-static int icp_ensure(sh_ctx* c, const IcpBytes& z) {
-  int rc;
-#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
-  ICP_BUFS(X)
-#undef X
-  return SH_OK;
-}
-
-// The chain of one registration, enqueued on the context's stream: the mean of the input points (phase 0), then max_iter + 1 evaluations
-// of move -> walk -> join -> sums -> step.  `pts` are the device points (Q, shared or per humerus); "icp.T", "icp.flags", "icp.out" and
-// "icp.hist" are in place.  Both entry points below run exactly this.
-static int icp_chain(sh_ctx* c, const IcpView& v, const double* pts, int Q, int per, const IcpPlan& plan, const sh_icp_options* opt) {
-  const int B = c->B, K = opt->max_iter;
-  const dim3 blocks((unsigned)plan.chunks, (unsigned)B), lanes(SH_ICP_BLOCK);
-  // one pass over the blocks: phase 0 the mean of the input points, phase 1 evaluation k
-  // (LAUNCH ends in HIPCHK(hipGetLastError()): a launch that fails returns SH_ERR_HIP from the lambda, which the callers pass on)
-  auto sum_step = [&](int phase, int k) -> int {
-    LAUNCH(c, "k_icp_sum", k_icp_sum, blocks, lanes, v.verts, v.faces, v.voff, v.foff, pts, (const double*)v.icp_moved,
-           (const sh_closest*)v.icp_near, Q, per, phase, (int)opt->metric, opt->reject, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_part);
-    LAUNCH(c, "k_icp_step", k_icp_step, dim3((unsigned)B), dim3(64), (const double*)v.icp_part, plan.chunks, Q, phase, (int)opt->metric, k, K, opt->tol,
-           v.icp_T, v.icp_flags, v.icp_hist, v.icp_out);
-    return SH_OK;
-  };
-  if (int rc = sum_step(0, 0)) return rc;
-  for (int k = 0; k <= K; ++k) {
-    LAUNCH(c, "k_icp_move", k_icp_move, blocks, lanes, pts, Q, per, (const double*)v.icp_T, (const int*)v.icp_flags, v.icp_moved);
-    LAUNCH(c, "k_cp_walk", k_cp_walk, dim3((unsigned)plan.chunks, (unsigned)B, (unsigned)plan.S), dim3(SH_CP_CHUNK), v.verts, v.faces, v.voff, v.foff,
-           (const double*)v.icp_moved, Q, 1, plan.S, v.icp_cp_part);
-    LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((plan.points + 255) / 256)), dim3(256), v.verts, v.faces, v.voff, v.foff, (const double*)v.icp_moved, Q, 1,
-           plan.S, (const CpPart*)v.icp_cp_part, (long long)plan.points, v.icp_near);
-    if (int rc = sum_step(1, k)) return rc;
-  }
-  return SH_OK;
-}
-
-int sh_register_points(sh_ctx* c, const double* points, int Q, int per_humerus, const double* T0, const sh_icp_options* opt, sh_registration* out,
-                       double* history) {
-  if (const ArthroError e = precheck_register(points, Q, per_humerus, T0, opt, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_register_points", e);
-  HIPCHK(c, hipSetDevice(c->device));
-  const int B = c->B, per = per_humerus != 0 ? 1 : 0, K = opt->max_iter;
-  const IcpPlan plan = icp_plan(B, Q, per != 0, c->maxF, K);
-  if (int rc = icp_ensure(c, plan.bytes)) return rc;
-  const IcpView v = icp_view(c);
-  std::vector<double> start((size_t)B * SH_ICP_TSTRIDE, 0.0);
-  for (int b = 0; b < B; ++b)
-    for (int i = 0; i < 16; ++i) start[(size_t)b * SH_ICP_TSTRIDE + i] = T0 ? T0[16 * (size_t)b + i] : (i % 5 == 0 ? 1.0 : 0.0);
-  HIPCHK(c, hipMemcpyAsync(v.icp_T, start.data(), plan.bytes.icp_T, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(v.icp_points, points, plan.bytes.icp_points, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.icp_flags, 0, plan.bytes.icp_flags, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.icp_hist, 0, plan.bytes.icp_hist, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.icp_out, 0, plan.bytes.icp_out, c->stream));
-  if (int rc = icp_chain(c, v, (const double*)v.icp_points, Q, per, plan, opt)) return rc;
-  if (out) HIPCHK(c, hipMemcpyAsync(out, v.icp_out, plan.bytes.icp_out, hipMemcpyDeviceToHost, c->stream));
-  if (history) HIPCHK(c, hipMemcpyAsync(history, v.icp_hist, plan.bytes.icp_hist, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
-// ---- multi-start registration (k_ms.h around the chain above); reads the mesh, changes no state of the chain ----
-#define X(f, name, T, ...) T* f = nullptr;
-struct MsView { MS_BUFS(X) };
-#undef X
-static MsView ms_view(sh_ctx* c) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  MsView v;
-#define X(f, name, T, ...) v.f = (T*)at(name);
-  MS_BUFS(X)
-#undef X
-  return v;
-}
-static int ms_ensure(sh_ctx* c, const MsBytes& z) {
-  int rc;
-#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
-  MS_BUFS(X)
-#undef X
-  return SH_OK;
-}
-
-int sh_register_multistart(sh_ctx* c, const double* points, int Q, int per_humerus, const double* T0s, int K, const sh_icp_options* coarse,
-                           int coarse_points, int min_pairs, const sh_icp_options* fine, sh_registration* out, sh_registration* coarse_out,
-                           int32_t* winner) {
-  if (const ArthroError e = precheck_multistart(points, Q, per_humerus, T0s, K, coarse, coarse_points, min_pairs, fine, arthro_facts(c)); e.code)
-    return arthro_refuse(c, "sh_register_multistart", e);
-  HIPCHK(c, hipSetDevice(c->device));
-  const int B = c->B, per = per_humerus != 0 ? 1 : 0;
-  const MsPlan plan = ms_plan(B, Q, per != 0, c->maxF, K, coarse_points, coarse->max_iter, fine->max_iter);
-  const int Qc = plan.Qc;
-  if (int rc = icp_ensure(c, plan.icp)) return rc;
-  if (int rc = ms_ensure(c, plan.bytes)) return rc;
-  const IcpView v = icp_view(c);
-  const MsView m = ms_view(c);
-  const size_t sets = per ? (size_t)B : 1;
-  std::vector<double> cpts(sets * Qc * 3);      // (pageable: the copy is staged before the call returns)
-  for (size_t s = 0; s < sets; ++s)
-    for (int j = 0; j < Qc; ++j) {
-      const double* p = points + 3 * (s * Q + (size_t)ms_coarse_index(j, Q, Qc));
-      double* q = &cpts[3 * (s * Qc + j)];
-      q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
-    }
-  HIPCHK(c, hipMemcpyAsync(m.ms_points, cpts.data(), plan.bytes.ms_points, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(m.ms_T0s, T0s, plan.bytes.ms_T0s, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(v.icp_points, points, plan.fine.bytes.icp_points, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(v.icp_moved, 0, plan.icp.icp_moved, c->stream));      // (a humerus without a winner is walked, never moved, in the fine stage)
-  HIPCHK(c, hipMemsetAsync(v.icp_hist, 0, plan.icp.icp_hist, c->stream));
-  const dim3 per_b((unsigned)((B + 63) / 64)), wave(64);
-  for (int k = 0; k < K; ++k) {
-    LAUNCH(c, "k_ms_seed", k_ms_seed, per_b, wave, (const double*)m.ms_T0s, B, K, k, (const sh_registration*)m.ms_coarse, (const int*)m.ms_winner, v.icp_T,
-           v.icp_flags, v.icp_out);
-    if (int rc = icp_chain(c, v, (const double*)m.ms_points, Qc, per, plan.coarse, coarse)) return rc;
-    LAUNCH(c, "k_ms_pick", k_ms_pick, per_b, wave, (const sh_registration*)v.icp_out, B, K, k, min_pairs, m.ms_coarse, m.ms_best, m.ms_winner);
-  }
-  HIPCHK(c, hipMemsetAsync(v.icp_hist, 0, plan.icp.icp_hist, c->stream));
-  LAUNCH(c, "k_ms_seed", k_ms_seed, per_b, wave, (const double*)m.ms_T0s, B, K, -1, (const sh_registration*)m.ms_coarse, (const int*)m.ms_winner, v.icp_T,
-         v.icp_flags, v.icp_out);
-  if (int rc = icp_chain(c, v, (const double*)v.icp_points, Q, per, plan.fine, fine)) return rc;
-  if (out) HIPCHK(c, hipMemcpyAsync(out, v.icp_out, plan.fine.bytes.icp_out, hipMemcpyDeviceToHost, c->stream));
-  if (coarse_out) HIPCHK(c, hipMemcpyAsync(coarse_out, m.ms_coarse, plan.bytes.ms_coarse, hipMemcpyDeviceToHost, c->stream));
-  if (winner) HIPCHK(c, hipMemcpyAsync(winner, m.ms_winner, plan.bytes.ms_winner, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SH_OK;
-}
-
-// ---- mass properties of the resident batch (k_mass.h); reads the mesh, changes no state of the chain ----
-static_assert(AR_MASS_TERMS == SH_MASS_TERMS, "sh_arthro.h: mass terms");
-#define X(f, name, T, ...) T* f = nullptr;
-struct MassView { ARTHRO_INPUT_BUFS(X) MASS_BUFS(X) };
-#undef X
-static MassView mass_view(sh_ctx* c) {
-  auto at = [c](const char* name) { auto it = c->bufs.find(name); return it == c->bufs.end() ? nullptr : it->second.p; };
-  MassView v;
-#define X(f, name, T, ...) v.f = (T*)at(name);
-  ARTHRO_INPUT_BUFS(X) MASS_BUFS(X)
-#undef X
-  return v;
-}
-static int mass_ensure(sh_ctx* c, const MassBytes& z) {
-  int rc;
-#define X(f, name, T, elem) if (z.f) ENS_SHARED(name, z.f, elem);
-  MASS_BUFS(X)
-#undef X
-  return SH_OK;
-}
-
-int sh_mass_properties(sh_ctx* c, sh_mass* out) {
-  if (const ArthroError e = precheck_mass(arthro_facts(c)); e.code) return arthro_refuse(c, "sh_mass_properties", e);
-  HIPCHK(c, hipSetDevice(c->device));
-  const int B = c->B;
-  const MassPlan plan = mass_plan(B, c->maxF);
-  if (int rc = mass_ensure(c, plan.bytes)) return rc;
-  const MassView v = mass_view(c);
-  HIPCHK(c, hipMemsetAsync(v.mass_part, 0, plan.bytes.mass_part, c->stream));
-  LAUNCH(c, "k_mass_sum", k_mass_sum, dim3((unsigned)plan.blocks, (unsigned)B), dim3(SH_MASS_BLOCK), v.verts, v.faces, v.voff, v.foff, v.mass_part);
-  LAUNCH(c, "k_mass_join", k_mass_join, dim3((unsigned)B), dim3(64), v.verts, v.voff, v.foff, (const double*)v.mass_part, plan.blocks, v.mass_out);
-  if (out) HIPCHK(c, hipMemcpyAsync(out, v.mass_out, plan.bytes.mass_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -4,9 +4,10 @@
 //   shoulder_hip.hip  context, C-ABI plumbing, meshes, the stage runner, submit / collect   (geometry kernels)
 //                     -- its per-batch buffers are declared once (WIN_*_BUFS: name, element type, elements per humerus); allocation
 //                     and the typed view of a window (WinView, resolved once per run_window) both come from that list
-//                     -- the entry points of the arthroplasty chain are sh_arthro_host.h, included by this unit once (a header, not a
-//                     unit: the resection kernels keep their registers only in this unit); its buffers are declared once
-//                     as well (sh_arthro.h ARTHRO_BUFS: allocation from the pass plan's sizes, and the typed ArthroView)
+//                     -- the entry points of the arthroplasty chain are sh_arthro_host.h, those of the queries of the resident batch
+//                     sh_query_host.h, each included by this unit once (headers, not units: the resection kernels keep their
+//                     registers only in this unit); their buffers are declared once as well (sh_arthro.h ARTHRO_BUFS,
+//                     sh_query.h RAY_BUFS ..: allocation from a plan's sizes, ensure_bytes, and the typed view of a call, view_of)
 //   hull.hip          hull prefilter, host hull phase and its worker pool, device hull      (k_hullpre.h, k_hull.h)
 //   unet.hip          the UNet runners, UNet turns, sh_unet_infer                          (k_unet*.h; unet16_pp.hip: k_unet16_pp.h)
 //   comm.hip          the RCCL collectives
@@ -14,7 +15,8 @@
 // verdict on them), sh_ingest.h (what mesh ingest checks and plans on the host before a batch becomes resident), sh_unet_plan.h (the
 // steps of a UNet pass: kernel, grid, tensors and work tickets of every launch; the ticket and weight-packing tables), sh_arthro.h
 // (the arthroplasty chain: its argument checks and which refusal comes first, the pass plan and the bytes of every resect.* / canal.* /
-// stem.* / plan.* buffer, and ArthroState, the one record of what is valid against what).
+// stem.* / plan.* buffer, and ArthroState, the one record of what is valid against what), sh_query.h (the queries of the resident batch:
+// rays, closest points, winding numbers, registration, mass properties -- their argument checks, plans and the bytes of their buffers).
 #pragma once
 #include "../../include/shoulder_hip.h"
 
@@ -37,12 +39,13 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
-#include "sh_arthro.h"
 #include "sh_demand.h"
 #include "sh_hullcap.h"
 #include "sh_ingest.h"
+#include "sh_query.h"      // (and sh_arthro.h below it)
 #include "sh_unet_plan.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -68,6 +71,8 @@ struct sh_ctx {
   long long sumV = 0, sumF = 0, maxV = 0, maxF = 0;
   std::vector<long long> h_voff, h_foff;
   std::map<std::string, Buf> bufs;
+  // a named buffer's pointer, null when it is not there (inlined like the lambdas it replaces)
+  __attribute__((always_inline)) void* at(const char* name) const { auto it = bufs.find(name); return it == bufs.end() ? nullptr : it->second.p; }
   bool have_rfc = false, have_unet = false;
   int rfc_nodes = 0, rfc_trees = 0;
   int unet_base = 0, unet_depth = 0;
@@ -283,6 +288,24 @@ static inline HullRec hull_rec(sh_ctx* c) {
   } while (0)
 #define ENS(name, bytes, elem) ENS_(name, bytes, elem, (size_t)(bytes) / (size_t)c->B)
 #define ENS_SHARED(name, bytes, elem) ENS_(name, bytes, elem, 0)
+static inline int ensure_shared(sh_ctx* c, const char* name, size_t bytes, int elem) { int rc; ENS_SHARED(name, bytes, elem); return SH_OK; }
+
+// The buffers of a list (sh_arthro.h SH_BUF_LIST) at the sizes of a call's plan, shared / scratch stride; 0: not this call's.
+template <typename Bytes>
+static inline int ensure_bytes(sh_ctx* c, const Bytes& z) {
+  int rc = SH_OK;
+  z.each([&](size_t bytes, const char*, const char* name, int elem) { if (bytes && rc == SH_OK) rc = ensure_shared(c, name, bytes, elem); });
+  return rc;
+}
+// The named buffers of a list as typed pointers, no window offset; a buffer that is not there is null.  A VIEW IS RESOLVED BEHIND EVERY
+// ENSURE THAT CAN RE-ALLOCATE ITS BUFFERS: once per call behind the call's ensure_bytes (a call that ensures two plans ensures their
+// field-wise maximum first: sh_register_multistart), and again behind any later one (ray_run, where "ray.pool" is sized by the counts).
+template <typename View>
+static inline View view_of(const sh_ctx* c) {
+  View v;
+  v.each([c](auto*& p, const char*, const char* name, auto...) { p = static_cast<std::remove_reference_t<decltype(p)>>(c->at(name)); });
+  return v;
+}
 // the element size sh_buffer_info reports for a buffer of T: records and segments count as bytes
 template <typename T> constexpr int elem_of() { return sizeof(T) <= 8 ? (int)sizeof(T) : 1; }
 

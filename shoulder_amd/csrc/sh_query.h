@@ -1,0 +1,254 @@
+// sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
+// points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
+// sh_register_multistart) and the mass properties (sh_mass_properties).  A query reads the mesh and changes no state of the
+// arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass}_check.cpp).
+// The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
+// rays ask the chain's state for the last run), `resident`, tiles_of.
+#pragma once
+#include "sh_arthro.h"
+
+namespace sh {
+
+// ---- the named buffers of the queries, one statement each: X(field, "name", element type, elem), and one line for their structs ----
+struct RayKey; struct CpPart;
+#define RAY_BUFS(X)                                                                                                                \
+  X(ray_rays, "ray.rays", double, 8) X(ray_status, "ray.status", int, 4) X(ray_counts, "ray.counts", int, 4)                       \
+  X(ray_offs, "ray.offs", unsigned long long, 8) X(ray_cursor, "ray.cursor", int, 4) X(ray_pool, "ray.pool", RayKey, 8)            \
+  X(ray_hits, "ray.hits", sh_ray_hit, 8) X(ray_blockhit, "ray.blockhit", int, 4)
+#define CP_BUFS(X) X(cp_points, "cp.points", double, 8) X(cp_part, "cp.part", CpPart, 8) X(cp_out, "cp.out", sh_closest, 8)
+#define WN_BUFS(X) X(wn_points, "wn.points", double, 8) X(wn_part, "wn.part", double, 8) X(wn_out, "wn.out", sh_winding, 8)
+// the walk of a registration runs on buffers of its own ("icp.cp_part", "icp.near")
+#define ICP_BUFS(X)                                                                                                                \
+  X(icp_points, "icp.points", double, 8) X(icp_moved, "icp.moved", double, 8) X(icp_cp_part, "icp.cp_part", CpPart, 8)             \
+  X(icp_near, "icp.near", sh_closest, 8) X(icp_part, "icp.part", double, 8) X(icp_T, "icp.T", double, 8)                           \
+  X(icp_hist, "icp.hist", double, 8) X(icp_flags, "icp.flags", int, 4) X(icp_out, "icp.out", sh_registration, 8)
+// the block rows and the records
+#define MASS_BUFS(X) X(mass_part, "mass.part", double, 8) X(mass_out, "mass.out", sh_mass, 8)
+// the multi-start registration runs the chain of sh_register_points on the "icp.*" buffers; these are its own
+#define MS_BUFS(X)                                                                                                                 \
+  X(ms_T0s, "ms.T0s", double, 8) X(ms_points, "ms.points", double, 8) X(ms_coarse, "ms.coarse", sh_registration, 8)                \
+  X(ms_best, "ms.best", double, 8) X(ms_winner, "ms.winner", int, 4)
+// (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
+#define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
+SH_QUERY_LIST(Ray, RAY_BUFS)
+SH_QUERY_LIST(Cp, CP_BUFS)
+SH_QUERY_LIST(Wn, WN_BUFS)
+SH_QUERY_LIST(Icp, ICP_BUFS)
+SH_QUERY_LIST(Mass, MASS_BUFS)
+SH_BUF_LIST(Ms, MS_BUFS)      // (beside an IcpView: no mesh of its own)
+
+// what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
+constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
+constexpr int AR_CP_TILE = 256, AR_CP_CHUNK = 256, AR_CP_PART_BYTES = 16;         // SH_CP_TILE, SH_CP_CHUNK, sizeof(CpPart)
+constexpr int AR_CP_FILL = 1024;      // workgroups of k_cp_walk that fill the chip: four of 256 lanes on each of 256 compute units
+constexpr int AR_WN_TILE = 256, AR_WN_CHUNK = 256, AR_WN_BLOCK = 2048;            // SH_WN_TILE, SH_WN_CHUNK, SH_WIND_BLOCK
+constexpr int AR_WN_FILL = 1024;      // workgroups of k_wn_walk that fill the chip, as AR_CP_FILL
+constexpr int AR_ICP_TERMS = 32, AR_ICP_TSTRIDE = 20;                             // SH_ICP_TERMS, SH_ICP_TSTRIDE
+constexpr int AR_MASS_TERMS = 24;                                                 // SH_MASS_TERMS
+
+// ---- the checks, each once --------------------------------------------------------------------------------------------------------
+// n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
+inline long long first_bad_ray(const sh_ray* rays, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    const sh_ray& r = rays[i];
+    bool fin = true;
+    for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(r.origin[k]) && std::isfinite(r.dir[k]);
+    if (!fin || (r.dir[0] == 0.0 && r.dir[1] == 0.0 && r.dir[2] == 0.0)) return (long long)i;
+  }
+  return -1;
+}
+
+// n points: the index of the first one with a coordinate that is not finite, or -1 (one scan loop for all callers, not inlined into each)
+__attribute__((noinline)) inline long long first_bad_point(const double* pts, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(pts[3 * i]) || !std::isfinite(pts[3 * i + 1]) || !std::isfinite(pts[3 * i + 2])) return (long long)i;
+  return -1;
+}
+
+// a rigid CT -> CT start of a registration: finite, last row exactly 0 0 0 1, |R^T R - I| <= 1e-9 in every entry (the columns: a shear
+// of 1e-6 fails), determinant positive (a reflection fails)
+inline bool rigid_start_ok(const double* T) {
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(T[i])) return false;
+  if (T[12] != 0.0 || T[13] != 0.0 || T[14] != 0.0 || T[15] != 1.0) return false;
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j) {
+      const double d = (T[i] * T[j] + T[4 + i] * T[4 + j]) + T[8 + i] * T[8 + j];
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-9)) return false;
+    }
+  return det3_of4(T) > 0.0;
+}
+inline bool icp_options_ok(const sh_icp_options* o) {
+  return (o->metric == SH_ICP_POINT || o->metric == SH_ICP_PLANE) && o->max_iter >= 1 && o->max_iter <= SH_ICP_MAX_ITER && o->reject > 0.0 &&
+         o->tol >= 0.0 && std::isfinite(o->tol);
+}
+
+// A set of Q query points, shared or per humerus, in the order every call that takes one refuses it: Q in 1..Qmax; `args`, the call's
+// verdict on its other arguments, which ranks here; the state (`resident`); the first point that is not finite.  (Always inlined: a
+// precheck stays the one function it was, in the library's symbol table too.)
+__attribute__((always_inline)) inline ArthroError point_set(const double* points, int Q, int Qmax, int per_humerus, const ArthroFacts& f, const ArthroError& args = arthro_ok()) {
+  if (!f.ctx || !points || Q < 1 || Q > Qmax) return {SH_ERR_ARG, "bad argument (Q in 1.." + std::to_string(Qmax) + ")"};
+  if (args.code) return args;
+  if (const ArthroError e = resident(f); e.code) return e;
+  const long long i = first_bad_point(points, per_humerus ? (size_t)f.B * Q : (size_t)Q);
+  if (i >= 0) return {SH_ERR_ARG, "point " + std::to_string(i) + " has a coordinate that is not finite"};
+  return arthro_ok();
+}
+
+// ---- the plans and the bytes of every buffer ----------------------------------------------------------------------------------------
+// a cast of R rays per humerus with room for cap hits each: everything but the pool, which the counts size ("ray.pool", ray_pool_bytes)
+struct RayPlan { int tmax, chunks; size_t rays; RayBytes bytes; };      // face tiles per humerus, ray chunks, B x R
+inline RayPlan ray_plan(int B, int R, bool per_humerus, int cap, long long maxF, bool with_status) {
+  const size_t n = (size_t)B * R;
+  RayBytes z;
+  z.ray_rays = (per_humerus ? n : (size_t)R) * sizeof(sh_ray); z.ray_counts = n * 4; z.ray_offs = (n + 1) * 8; z.ray_cursor = n * 4;
+  z.ray_hits = n * cap * sizeof(sh_ray_hit);
+  if (with_status) z.ray_status = (size_t)B * 4;
+  const long long tmax = tiles_of(maxF, AR_RAY_TILE);
+  const int chunks = (R + AR_RAY_CHUNK - 1) / AR_RAY_CHUNK;
+  z.ray_blockhit = (size_t)tmax * B * chunks * 4;      // one word per workgroup of the walk
+  return {(int)tmax, chunks, n, z};
+}
+inline size_t ray_pool_bytes(unsigned long long total) { return (size_t)(total > 0 ? total : 1) * AR_RAY_KEY_BYTES; }
+
+// The splits of a walk over the units (face tiles, face blocks) of the largest humerus.  S is the host's choice and no knob: as many
+// splits as bring a grid of `groups` (B x point chunks) workgroups to `fill` when it is small, never more than the units, at least one.
+inline int fill_splits(long long groups, long long units, int fill) {
+  const long long g = groups > 1 ? groups : 1, want = (fill + g - 1) / g;
+  const long long s = want < units ? want : units;
+  return (int)(s > 1 ? s : 1);
+}
+
+// Closest points, Q per humerus.  The grid of k_cp_walk is (chunks of 256 points, B, S face splits): split s of a humerus with T tiles
+// walks the tiles cp_split_range(T, S, s) (sh_scalar.h).  A minimum under a total order does not depend on how its candidates are
+// grouped, so S changes no result.
+inline int cp_splits(long long groups /* B x chunks */, long long tiles /* of the largest humerus */) { return fill_splits(groups, tiles, AR_CP_FILL); }
+struct CpPlan { int tmax, chunks, S; size_t points; CpBytes bytes; };      // face tiles of the largest humerus, point chunks, face splits, B x Q
+inline CpPlan cp_plan(int B, int Q, bool per_humerus, long long maxF) {
+  const size_t n = (size_t)B * Q;
+  const long long tmax = tiles_of(maxF, AR_CP_TILE);
+  const int chunks = (Q + AR_CP_CHUNK - 1) / AR_CP_CHUNK;
+  const int S = cp_splits((long long)B * chunks, tmax);
+  CpBytes z;
+  z.cp_points = (per_humerus ? n : (size_t)Q) * 24; z.cp_part = n * S * AR_CP_PART_BYTES; z.cp_out = n * sizeof(sh_closest);
+  return {(int)tmax, chunks, S, n, z};
+}
+
+// Winding numbers, Q per humerus.  The grid of k_wn_walk is (chunks of 256 points, B, S splits): split s of a humerus with K blocks of
+// AR_WN_BLOCK faces walks the blocks cp_split_range(K, S, s) (sh_scalar.h) -- whole blocks, a split never cuts one, because the block
+// sums are the fixed inner level of the summation tree.  With S == 1 a workgroup owns all blocks of its humerus and adds the block sums
+// itself, in block order ("wn.part" holds one total per point); with S > 1 "wn.part" holds the block sums (kmax per point) and
+// k_wn_join adds them in the same order.  S changes no byte.
+inline int wn_splits(long long groups /* B x chunks */, long long blocks /* of the largest humerus */) { return fill_splits(groups, blocks, AR_WN_FILL); }
+struct WnPlan { int kmax, chunks, S, stride; size_t points; WnBytes bytes; };      // blocks of the largest humerus, point chunks, splits, doubles of "wn.part" per point, B x Q
+inline WnPlan wn_plan(int B, int Q, bool per_humerus, long long maxF) {
+  const size_t n = (size_t)B * Q;
+  const long long kmax = tiles_of(maxF, AR_WN_BLOCK);
+  const int chunks = (Q + AR_WN_CHUNK - 1) / AR_WN_CHUNK;
+  const int S = wn_splits((long long)B * chunks, kmax);
+  const int stride = S == 1 ? 1 : (int)kmax;
+  WnBytes z;
+  z.wn_points = (per_humerus ? n : (size_t)Q) * 24; z.wn_part = n * stride * sizeof(double); z.wn_out = n * sizeof(sh_winding);
+  return {(int)kmax, chunks, S, stride, n, z};
+}
+
+// Registration, Q points per humerus.  The walk of an evaluation is the closest-point walk on the moved points, always per humerus:
+// its chunks and its split S are cp_plan's, unchanged.  The sums take the points in blocks of SH_ICP_BLOCK = the walk's chunk, one
+// row of AR_ICP_TERMS doubles per (humerus, block) in "icp.part"; "icp.T" holds the transform and the mean of the input points.
+struct IcpPlan { int chunks, S; size_t points; IcpBytes bytes; };      // point chunks = blocks of the sums, face splits of the walk, B x Q
+inline IcpPlan icp_plan(int B, int Q, bool per_humerus, long long maxF, int max_iter) {
+  const CpPlan cp = cp_plan(B, Q, true, maxF);
+  IcpBytes z;
+  z.icp_points = (per_humerus ? cp.points : (size_t)Q) * 24; z.icp_moved = cp.points * 24; z.icp_cp_part = cp.bytes.cp_part; z.icp_near = cp.bytes.cp_out;
+  z.icp_part = (size_t)B * cp.chunks * AR_ICP_TERMS * 8; z.icp_T = (size_t)B * AR_ICP_TSTRIDE * 8; z.icp_hist = (size_t)B * (max_iter + 1) * 16;
+  z.icp_flags = (size_t)B * 4; z.icp_out = (size_t)B * sizeof(sh_registration);
+  return {cp.chunks, cp.S, cp.points, z};
+}
+
+// Mass properties: one row of AR_MASS_TERMS doubles per (humerus, block of SH_MASS_BLOCK faces) in "mass.part", the blocks of the largest
+// humerus for every humerus
+struct MassPlan { int blocks; MassBytes bytes; };
+inline MassPlan mass_plan(int B, long long maxF) {
+  const long long blocks = tiles_of(maxF, SH_MASS_BLOCK);
+  MassBytes z;
+  z.mass_part = (size_t)B * blocks * AR_MASS_TERMS * 8; z.mass_out = (size_t)B * sizeof(sh_mass);
+  return {(int)blocks, z};
+}
+
+// Multi-start registration: the coarse stage is sh_register_points on Qc points, the fine stage on all Q, both on the "icp.*" buffers,
+// which take the larger of the two sizes field by field (the split of the walk, and so "icp.cp_part", may be larger for the fewer points).
+inline int ms_coarse_count(int Q, int coarse_points) { return coarse_points == 0 || coarse_points > Q ? Q : coarse_points; }
+inline long long ms_coarse_index(long long j, int Q, int Qc) { return j * Q / Qc; }      // point j of the coarse set
+struct MsPlan { int Qc; IcpPlan coarse, fine; IcpBytes icp; MsBytes bytes; };
+inline MsPlan ms_plan(int B, int Q, bool per_humerus, long long maxF, int K, int coarse_points, int coarse_iter, int fine_iter) {
+  const int Qc = ms_coarse_count(Q, coarse_points);
+  MsPlan p{Qc, icp_plan(B, Qc, per_humerus, maxF, coarse_iter), icp_plan(B, Q, per_humerus, maxF, fine_iter), IcpBytes(), MsBytes()};
+#define X(f, name, T, elem) p.icp.f = std::max(p.coarse.bytes.f, p.fine.bytes.f);
+  ICP_BUFS(X)
+#undef X
+  p.bytes.ms_T0s = (size_t)B * K * 128; p.bytes.ms_points = (per_humerus ? (size_t)B * Qc : (size_t)Qc) * 24;
+  p.bytes.ms_coarse = (size_t)B * K * sizeof(sh_registration); p.bytes.ms_best = (size_t)B * 8; p.bytes.ms_winner = (size_t)B * 4;
+  return p;
+}
+
+// The pick rule: does candidate k (its status, pairs and rms) replace the best so far (winner < 0: none yet)?  The candidates come in
+// ascending k, so "strictly smaller rms" is the order (rms, k).  A candidate with a status, too few pairs or a NaN rms never wins.
+SH_HD bool ms_candidate_wins(int status, int pairs, double rms, int min_pairs, int winner, double best_rms) {
+  if (status != 0 || pairs < min_pairs || !(rms == rms)) return false;
+  return winner < 0 || rms < best_rms;
+}
+
+// ---- one ordered precheck per entry point: the first refusal, or SH_OK ------------------------------------------------------------------
+inline ArthroError precheck_ray_cast(const sh_ray* rays, int R, int per_humerus, int cap, const ArthroFacts& f) {
+  if (!f.ctx || !rays || R < 1 || R > SH_RAY_MAX || cap < 1 || cap > SH_RAY_MAX_HITS) return {SH_ERR_ARG, "bad argument (R in 1..65536, cap in 1..1024)"};
+  if (const ArthroError e = resident(f); e.code) return e;
+  const long long i = first_bad_ray(rays, per_humerus ? (size_t)f.B * R : (size_t)R);
+  if (i >= 0) return {SH_ERR_ARG, "ray " + std::to_string(i) + " has a non-finite number or a zero direction"};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_anp_hits(int cap, const int32_t* status, const ArthroFacts& f) {
+  if (!f.ctx || !status || cap < 1 || cap > SH_RAY_MAX_HITS) return {SH_ERR_ARG, "bad argument (cap in 1..1024)"};
+  if (const ArthroError e = resident(f); e.code) return e;
+  if (!f.st->has_anp(f.batch_gen) || !f.landmarks) return {SH_ERR_STATE, "needs a collected run of the resident batch with SH_STAGE_ANP"};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_closest(const double* points, int Q, int per_humerus, const ArthroFacts& f) { return point_set(points, Q, SH_CLOSEST_MAX, per_humerus, f); }
+inline ArthroError precheck_winding(const double* points, int Q, int per_humerus, const ArthroFacts& f) { return point_set(points, Q, SH_WINDING_MAX, per_humerus, f); }
+
+inline ArthroError precheck_mass(const ArthroFacts& f) {
+  if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
+  return resident(f);
+}
+
+static const char* const AR_ICP_OPTIONS = "options (metric 0 or 1, max_iter in 1..64, reject > 0, tol >= 0 and finite)";
+static const char* const AR_NOT_RIGID = " is not a rigid matrix (last row 0 0 0 1, |R^T R - I| <= 1e-9, det > 0)";
+
+inline ArthroError precheck_register(const double* points, int Q, int per_humerus, const double* T0, const sh_icp_options* opt, const ArthroFacts& f) {
+  if (!f.ctx || !points || !opt) return {SH_ERR_ARG, "bad argument (context, points and options must be given)"};
+  const ArthroError args = icp_options_ok(opt) ? arthro_ok() : ArthroError{SH_ERR_ARG, std::string("bad ") + AR_ICP_OPTIONS};
+  if (const ArthroError e = point_set(points, Q, SH_CLOSEST_MAX, per_humerus, f, args); e.code) return e;
+  if (T0)
+    for (int b = 0; b < f.B; ++b)
+      if (!rigid_start_ok(T0 + 16 * (size_t)b)) return {SH_ERR_ARG, "T0 of humerus " + std::to_string(b) + AR_NOT_RIGID};
+  return arthro_ok();
+}
+
+inline ArthroError precheck_multistart(const double* points, int Q, int per_humerus, const double* T0s, int K, const sh_icp_options* coarse,
+                                       int coarse_points, int min_pairs, const sh_icp_options* fine, const ArthroFacts& f) {
+  if (!f.ctx || !points || !T0s || !coarse || !fine) return {SH_ERR_ARG, "bad argument (context, points, T0s and both options must be given)"};
+  const bool sizes = K >= 1 && K <= SH_MS_MAX_STARTS && coarse_points >= 0 && min_pairs >= 6;
+  const ArthroError args = !sizes                   ? ArthroError{SH_ERR_ARG, "bad argument (K in 1..64, coarse_points >= 0, min_pairs >= 6)"}
+                           : !icp_options_ok(coarse) ? ArthroError{SH_ERR_ARG, std::string("bad coarse ") + AR_ICP_OPTIONS}
+                           : !icp_options_ok(fine)   ? ArthroError{SH_ERR_ARG, std::string("bad fine ") + AR_ICP_OPTIONS}
+                                                     : arthro_ok();
+  if (const ArthroError e = point_set(points, Q, SH_CLOSEST_MAX, per_humerus, f, args); e.code) return e;
+  for (int b = 0; b < f.B; ++b)
+    for (int k = 0; k < K; ++k)
+      if (!rigid_start_ok(T0s + 16 * ((size_t)b * K + k))) return {SH_ERR_ARG, "start " + std::to_string(k) + " of humerus " + std::to_string(b) + AR_NOT_RIGID};
+  return arthro_ok();
+}
+
+}  // namespace sh

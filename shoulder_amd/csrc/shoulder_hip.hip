@@ -449,9 +449,8 @@ static int stl_scratch(sh_ctx* c, int B, const StlPlan& p, StlView* v) {
   ENS_SHARED("stl.counts", (size_t)B * 8, 4);
   ENS_SHARED("stl.bsum", stl_rank_scratch_ints(B, p.maxc) * 4, 4);
   ENS_SHARED("stl.nonfinite", (size_t)B * 4, 4);
-  auto at = [c](const char* name) { return c->bufs[name].p; };
-  *v = StlView{(unsigned char*)at("stl.raw"), (long long*)at("stl.file_off"), (long long*)at("stl.coff"), (float*)at("stl.corners"), (int2*)at("stl.table"), (int*)at("stl.slot"),
-               (int*)at("stl.vid"), (int*)at("stl.fpos"), (int*)at("stl.counts"), (int*)at("stl.bsum"), (int*)at("stl.nonfinite")};
+  *v = StlView{(unsigned char*)c->at("stl.raw"), (long long*)c->at("stl.file_off"), (long long*)c->at("stl.coff"), (float*)c->at("stl.corners"), (int2*)c->at("stl.table"),
+               (int*)c->at("stl.slot"), (int*)c->at("stl.vid"), (int*)c->at("stl.fpos"), (int*)c->at("stl.counts"), (int*)c->at("stl.bsum"), (int*)c->at("stl.nonfinite")};
   return SH_OK;
 }
 
@@ -736,8 +735,7 @@ int sh_ring(sh_ctx* c, const char* set, int b, int k, double* out, int cap, int*
   *n_out = n + 1;
   if (!out || cap < n + 1) return SH_OK;
   long long roff = -1;
-  auto ito = c->bufs.find(p + ".ovf_roff");
-  if (ito != c->bufs.end() && ito->second.p) HIPCHK(c, hipMemcpy(&roff, (const long long*)ito->second.p + pl, 8, hipMemcpyDeviceToHost));
+  if (const long long* d_roff = (const long long*)c->at((p + ".ovf_roff").c_str())) HIPCHK(c, hipMemcpy(&roff, d_roff + pl, 8, hipMemcpyDeviceToHost));
   const double* src = roff >= 0 ? (const double*)c->bufs["ovf.ring"].p + 2 * roff : (const double*)itr->second.p + pl * (SH_MAXSEG + 1) * 2;
   HIPCHK(c, hipMemcpy(out, src, (size_t)(n + 1) * 16, hipMemcpyDeviceToHost));
   return SH_OK;
@@ -859,6 +857,8 @@ int sh_slice_mesh_planes(sh_ctx* c, const double* verts, int nv, const int32_t* 
 
 // ---- the arthroplasty chain: sh_resect_*, sh_canal_profile, sh_resect_stems, sh_resect_plan (host code; the decisions are sh_arthro.h's) ----
 #include "sh_arthro_host.h"
+// ---- the queries of the resident batch: rays, closest points, winding numbers, registration, mass properties (the decisions are sh_query.h's) ----
+#include "sh_query_host.h"
 
 int sh_mesh_transformed(sh_ctx* c, int b, const double* T, double* out) {
   if (!c || !T || !out || b < 0 || b >= c->B) return fail(c, SH_ERR_ARG, "sh_mesh_transformed: bad argument");

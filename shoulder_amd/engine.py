@@ -46,6 +46,13 @@ def _mat4(T):
     return T
 
 
+def _icp_options(metric="plane", max_iter=20, reject=np.inf, tol=0.0, **_):
+    """the options of a registration as the C struct; the defaults are register's (other keys of an options dict are not looked at)"""
+    if metric not in ("point", "plane"):
+        raise ValueError('metric must be "point" or "plane"')
+    return _lib.IcpOptions(_lib.ICP_PLANE if metric == "plane" else _lib.ICP_POINT, int(max_iter), float(reject), float(tol))
+
+
 def principal_start_matrices(cm, axes, points, rolls=8):
     """The starts of Engine.principal_starts for one humerus -> ((2 * rolls, 4, 4), the ratio of the two largest covariance
     eigenvalues of the points).  cm, axes: the centroid and the frame of the mesh (rows are axes, the long one first, right-handed)."""
@@ -635,14 +642,19 @@ class Engine:
         return hits, counts, status[: self.B]
 
     # ---- closest surface points of the resident batch (include/shoulder_hip.h sh_closest_points) -------------------------------
+    def _points_arg(self, points):
+        """the query points of a call as the C side reads them: (Q, 3), shared by all humeri, or (B, Q, 3)"""
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
+            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
+        return p
+
     def closest_points(self, points):
         """The closest point of every resident humerus to every query point -> a structured array (B, Q) of _lib.CLOSEST_DTYPE: dist,
         point (CT), face (humerus-local), region (0 interior, 1 / 2 / 3 edge AB / BC / CA, 4 / 5 / 6 vertex A / B / C of that face), side
         (+1 on the side the winning face's normal points to) and status.  points: (Q, 3), shared by all humeri, or (B, Q, 3), in CT.
         Among faces at the same distance the smallest face id wins.  A call costs what a multiple of 256 points costs."""
-        p = np.ascontiguousarray(points, dtype=np.float64)
-        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
-            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
+        p = self._points_arg(points)
         Q, per = p.shape[-2], int(p.ndim == 3)
         ok = 1 <= Q <= _lib.CLOSEST_MAX      # (the library reports the rest; nothing is sized by it here)
         out = np.zeros((self.B, Q) if ok else (0,), dtype=_lib.CLOSEST_DTYPE)
@@ -657,9 +669,7 @@ class Engine:
         OPEN mesh gives a fraction (a cube without one of its six sides: 5/6 at its centre); a CAVITY whose wall faces inward gives 0.
         ON THE SURFACE ITSELF the winding number is about 0.5 and `inside` is undefined.  Every face contributes (no approximation);
         a call costs what a multiple of 256 points costs."""
-        p = np.ascontiguousarray(points, dtype=np.float64)
-        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
-            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
+        p = self._points_arg(points)
         Q, per = p.shape[-2], int(p.ndim == 3)
         ok = 1 <= Q <= _lib.WINDING_MAX      # (the library reports the rest; nothing is sized by it here)
         out = np.zeros((self.B, Q) if ok else (0,), dtype=_lib.WINDING_DTYPE)
@@ -698,18 +708,14 @@ class Engine:
         tol ends a humerus' updates, NOT the call's work: the host enqueues all max_iter + 1 closest-point walks and does not look at the
         flags in between, so a batch that converges early still pays for max_iter (about 10 ms per walk for 64 bones x 4 096 points).
         ICP is local: the start must lie within its basin of convergence.  The pairs of the last evaluation stay in "icp.near"."""
-        p = np.ascontiguousarray(points, dtype=np.float64)
-        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
-            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
-        if metric not in ("point", "plane"):
-            raise ValueError('metric must be "point" or "plane"')
+        p = self._points_arg(points)
+        opt = _icp_options(metric, max_iter, reject, tol)
         Q, per = p.shape[-2], int(p.ndim == 3)
         t0 = None
         if T0 is not None:
             t0 = np.ascontiguousarray(T0, dtype=np.float64)
             if t0.shape != (self.B, 4, 4):
                 raise ValueError("T0 must have shape (B, 4, 4)")
-        opt = _lib.IcpOptions(_lib.ICP_PLANE if metric == "plane" else _lib.ICP_POINT, int(max_iter), float(reject), float(tol))
         rows = int(max_iter) + 1 if 1 <= int(max_iter) <= _lib.ICP_MAX_ITER else 0      # (the library reports the rest)
         out = np.zeros(self.B, dtype=_lib.REGISTRATION_DTYPE)
         hist = np.zeros((self.B, rows, 2)) if history else None
@@ -730,12 +736,6 @@ class Engine:
         return out
 
     # ---- multi-start registration (include/shoulder_hip.h sh_register_multistart) -----------------------------------------------
-    def _points_arg(self, points):
-        p = np.ascontiguousarray(points, dtype=np.float64)
-        if p.ndim not in (2, 3) or p.shape[-1] != 3 or (p.ndim == 3 and p.shape[0] != self.B):
-            raise ValueError("points must have shape (Q, 3) or (B, Q, 3)")
-        return p
-
     def principal_starts(self, points, rolls=8, with_ratios=False):
         """Starting transforms for register_multistart from principal frames -> (B, 2 * rolls, 4, 4).  The mesh frame is shell_centroid
         and shell_axes of mass_properties (device); the point frame is the mean and the covariance eigenvectors of the points,
@@ -766,13 +766,7 @@ class Engine:
         t0 = np.ascontiguousarray(T0s, dtype=np.float64)
         if t0.ndim != 4 or t0.shape[0] != self.B or t0.shape[2:] != (4, 4):
             raise ValueError("T0s must have shape (B, K, 4, 4)")
-
-        def options(o):
-            o = dict(dict(metric="plane", max_iter=20, reject=np.inf, tol=0.0), **(o or {}))
-            if o["metric"] not in ("point", "plane"):
-                raise ValueError('metric must be "point" or "plane"')
-            return _lib.IcpOptions(_lib.ICP_PLANE if o["metric"] == "plane" else _lib.ICP_POINT, int(o["max_iter"]), float(o["reject"]), float(o["tol"]))
-        co, fo = options(coarse), options(fine)
+        co, fo = _icp_options(**(coarse or {})), _icp_options(**(fine or {}))
         K = t0.shape[1]
         out = np.zeros(self.B, dtype=_lib.REGISTRATION_DTYPE)
         cand = np.zeros((self.B, K) if 1 <= K <= _lib.MS_MAX_STARTS else (0,), dtype=_lib.REGISTRATION_DTYPE)

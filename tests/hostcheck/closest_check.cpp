@@ -1,5 +1,5 @@
 // Test shim (NOT product): the closest-point arithmetic of shoulder_amd/csrc/sh_scalar.h (closest_pt_tri, tri_point, closest_key_less,
-// closest_side, cp_split_range -- the source k_closest.h runs on the device) and the argument checks and the face split of sh_arthro.h
+// closest_side, cp_split_range -- the source k_closest.h runs on the device) and the argument checks and the face split of sh_query.h
 // (precheck_closest, cp_splits) on the host, for tests/test_closest_host.py.  cc_mesh answers one point against a mesh as the two
 // kernels do: the tiles of the mesh dealt to S splits by cp_split_range, each split folded into a partial with closest_key_less (the
 // faces of a split walked backwards when asked: the order must not matter), the partials joined as k_cp_join joins them and the
@@ -10,7 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/shoulder_hip.h"
-#include "../../shoulder_amd/csrc/sh_arthro.h"
+#include "../../shoulder_amd/csrc/sh_query.h"
 #include "../../shoulder_amd/csrc/sh_scalar.h"
 
 static void face_of(const float* verts, const int* faces, int f, double* A, double* ab, double* ac) {

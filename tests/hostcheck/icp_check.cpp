@@ -1,6 +1,6 @@
 // Test shim (NOT product): the registration arithmetic of shoulder_amd/csrc/sh_scalar.h (icp_pair_terms, sym4_jacobi, icp_horn_solve,
 // chol6_solve, icp_plane_solve, icp_compose, icp_step -- the source k_icp.h runs on the device) and the argument checks and buffer
-// plan of sh_arthro.h (precheck_register, icp_plan) on the host, for tests/test_icp_host.py.  ic_evaluate makes one evaluation as the
+// plan of sh_query.h (precheck_register, icp_plan) on the host, for tests/test_icp_host.py.  ic_evaluate makes one evaluation as the
 // kernels do: the points moved, paired against every face (closest_pt_tri under closest_key_less, as k_cp_walk / k_cp_join), the terms
 // of each block of 256 put through the tree slot[i] += slot[i + h]; ic_register runs the whole loop.  Its own main() registers points
 // onto a scalene box with both metrics and walks the failure cases, so that the file can be built as a stand-alone program with
@@ -10,7 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/shoulder_hip.h"
-#include "../../shoulder_amd/csrc/sh_arthro.h"
+#include "../../shoulder_amd/csrc/sh_query.h"
 #include "../../shoulder_amd/csrc/sh_scalar.h"
 
 static void face_of(const float* verts, const int* faces, int f, double* A, double* ab, double* ac) {

@@ -1,5 +1,5 @@
 // Test shim (NOT product): the mass-property arithmetic of shoulder_amd/csrc/sh_scalar.h (mass_face_terms, sym3_jacobi, mass_frame,
-// mass_finish -- the source k_mass.h runs on the device) and, of sh_arthro.h, the argument checks of sh_mass_properties and
+// mass_finish -- the source k_mass.h runs on the device) and, of sh_query.h, the argument checks of sh_mass_properties and
 // sh_register_multistart, its pick rule, its subsample rule and its buffer plan, on the host, for tests/test_mass_host.py and
 // tests/test_multistart_host.py.  mc_mass makes the record of one mesh as the kernels do: the terms of each block of 256 faces put
 // through the tree slot[i] += slot[i + h], the block rows added in block order.  Its own main() measures a box, an open box and
@@ -9,7 +9,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/shoulder_hip.h"
-#include "../../shoulder_amd/csrc/sh_arthro.h"
+#include "../../shoulder_amd/csrc/sh_query.h"
 #include "../../shoulder_amd/csrc/sh_scalar.h"
 
 static_assert(sizeof(sh_mass) == SH_MASS_DOUBLES * 8 + 16, "sh_mass: 48 doubles and four int32");

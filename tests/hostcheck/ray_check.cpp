@@ -1,5 +1,5 @@
 // Test shim (NOT product): the ray arithmetic of shoulder_amd/csrc/sh_scalar.h (ray_tri_hit, canal_ray_hit_side, ray_key_less -- the
-// source k_rays.h runs on the device) and the argument checks of sh_arthro.h (precheck_ray_cast) on the host, for
+// source k_rays.h runs on the device) and the argument checks of sh_query.h (precheck_ray_cast) on the host, for
 // tests/test_ray_host.py.  rc_sort ranks a segment as k_ray_sort does (64 lanes striding the keys, each counting the keys below its
 // own, the ranks below cap stored, the slots behind them zero with face = -1); rc_cast walks the faces of a mesh BACKWARDS into the
 // pool (the device's slot order is arbitrary: the sort must remove it) with the CT or the box-frame loader and sorts.  Its own
@@ -10,7 +10,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/shoulder_hip.h"
-#include "../../shoulder_amd/csrc/sh_arthro.h"
+#include "../../shoulder_amd/csrc/sh_query.h"
 #include "../../shoulder_amd/csrc/sh_scalar.h"
 
 extern "C" int rc_hit(const double* o, const double* d, const double* tri /* 3 x 3 */, double* t, int* side) {

@@ -1,5 +1,5 @@
 // Test shim (NOT product): the winding-number arithmetic of shoulder_amd/csrc/sh_scalar.h (solid_angle_terms, solid_angle_tri,
-// winding_record, cp_split_range -- the source k_winding.h runs on the device) and the argument checks and the split of sh_arthro.h
+// winding_record, cp_split_range -- the source k_winding.h runs on the device) and the argument checks and the split of sh_query.h
 // (precheck_winding, wn_splits, wn_plan) on the host, for tests/test_winding_host.py.  wc_mesh answers points against a mesh as the
 // two kernels do: the blocks of 2048 faces dealt to S splits by cp_split_range, each block summed from 0 in face order, and the block
 // sums either stored and added in block order by the join (S > 1) or added by the walk itself (S == 1).  Its own main() runs all of it
@@ -9,7 +9,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/shoulder_hip.h"
-#include "../../shoulder_amd/csrc/sh_arthro.h"
+#include "../../shoulder_amd/csrc/sh_query.h"
 #include "../../shoulder_amd/csrc/sh_scalar.h"
 
 static void corners_of(const float* verts, const int* faces, int f, double* V) {

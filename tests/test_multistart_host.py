@@ -1,5 +1,5 @@
 """Multi-start registration (include/shoulder_hip.h sh_register_multistart), the parts that need no GPU, through the shim
-tests/hostcheck/mass_check.cpp: the ordered argument checks of sh_arthro.h, the pick rule that k_ms_pick folds the candidates under,
+tests/hostcheck/mass_check.cpp: the ordered argument checks of sh_query.h, the pick rule that k_ms_pick folds the candidates under,
 the subsample rule and the buffer plan; and Engine.principal_starts' arithmetic, which is plain NumPy."""
 import ctypes
 
