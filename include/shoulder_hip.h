@@ -837,6 +837,52 @@ int sh_register_multistart(sh_ctx*, const double* points /* Q x 3, or B x Q x 3 
                            const sh_icp_options* fine, sh_registration* out /* B, host, nullable */,
                            sh_registration* coarse_out /* B x K, host, nullable */, int32_t* winner /* B, host, nullable */);
 
+/* ---- surface samples of the resident batch: area-weighted, thinned to a minimum spacing if asked ------------------------------------
+ * The counterpart of `trimesh.sample.sample_surface` and `sample_surface_even`: N points on the surface of each of the B resident
+ * meshes, every face drawn in proportion to its area, and with radius > 0 the greedy thinning of `remove_close` on top, in one device
+ * pass (k_sample.h).  The producer of the points that the closest-point, winding and registration calls take.  Everything float64,
+ * -ffp-contract=off, + - x sqrt only (sh_scalar.h); corners are the float32 vertices widened to float64.
+ *   areas     A2_f = sqrt(dot3(n, n)), n = cross3(B - A, C - A): the expression of sh_mass_properties (face_area2).
+ *   cdf       "samp.cdf", nf doubles per humerus (humerus b at its face offset).  THE ORDER IS PART OF THE DEFINITION: faces in blocks
+ *             of SH_SAMPLE_BLOCK = 256 consecutive indices; in a block s[0] = A2[0], s[i] = s[i - 1] + A2[i], strictly in index order;
+ *             base_0 = 0.0, base_(k+1) = base_k + s_k[255] ("samp.base", one double per block); cdf[f] = base_k + s_k[i];
+ *             total = cdf[nf - 1].  Sequential on purpose: cdf is then non-decreasing in floating point, which the search needs and a
+ *             tree or a Hillis-Steele scan does not give; a face of zero area has cdf[f] == cdf[f - 1] exactly.
+ *   words     SplitMix64 as a counter generator: w(seed, n) = mix(seed + (n + 1) 0x9E3779B97F4A7C15) mod 2^64 with
+ *             mix(z): z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB; z ^ z >> 31, and
+ *             unit(w) = (w >> 11) 2^-53 in [0, 1).  Sample j of humerus b uses seeds[b] and the words 3j, 3j + 1, 3j + 2, nothing
+ *             else: a record depends on its mesh, its seed and j alone, not on B, N, the humerus' place or the launch shape.
+ *   face      target = unit(w(3j)) total; face = the smallest f with cdf[f] > target (nf - 1 when there is none, which target < total
+ *             rules out: the definition's guard).  A face of zero area is never drawn.
+ *   point     r1 = unit(w(3j + 1)), r2 = unit(w(3j + 2)); when r1 + r2 > 1.0: r1 = 1.0 - r1, r2 = 1.0 - r2;
+ *             point_k = A_k + (r1 ab_k + r2 ac_k); u = r1, v = r2 (barycentric weights of B and C); keep = 1 without thinning.
+ *   thinning  (radius > 0) the sequential greedy rule: keep_j = 1 iff no i < j has keep_i = 1 and d2(i, j) < radius radius, with
+ *             d2 = (dx dx + dy dy) + dz dz on the stored points.  The set is unique, so any schedule gives these bytes; the device runs
+ *             Jacobi rounds on double-buffered states: an undecided j becomes removed when a lower neighbour was kept at the start of
+ *             the round, kept when all its lower neighbours were removed (or it has none).  rounds = the rounds until none is
+ *             undecided (deterministic: the rounds are Jacobi).  The host enqueues max_rounds launches and looks at nothing in
+ *             between; an integer count of the undecided per humerus and round lets a workgroup return at once.  A humerus with
+ *             undecided samples after max_rounds: status SH_ERR_CAPACITY, rounds = max_rounds, those samples keep = -1; never the
+ *             batch.  All pairs i < j are looked at (brute force, tiles of 256 through LDS): N <= SH_SAMPLE_THIN_MAX with a radius.
+ *   info      area = total / 2; kept = the samples with keep == 1; status SH_ERR_GEOMETRY when there are no faces, total == 0 or total
+ *             is not finite: the humerus' records are then all zero and the batch goes on.
+ *
+ * Arguments in this order: the context and the pointers seeds and options (SH_ERR_ARG); N in 1..SH_SAMPLE_MAX; the options (radius
+ * finite and >= 0, max_rounds in 1..SH_THIN_MAX_ROUNDS, reserved == 0, N <= SH_SAMPLE_THIN_MAX when radius > 0); a resident batch and
+ * no runs in flight (SH_ERR_STATE; a run is not needed).  SH_ERR_NOMEM when the buffers do not fit.  Resident afterwards: "samp.cdf",
+ * "samp.base", "samp.out" (B x N sh_sample), "samp.info" (B sh_sample_info) and "samp.state" (per humerus 64 int32 -- the undecided at
+ * the start of round r in word r, the seed in words 62 and 63 -- and with a radius the two state arrays of N int32), until the next upload / commit /
+ * sh_store("verts"), which removes them as it removes "mass.*".  Every other buffer keeps its bytes. */
+#define SH_SAMPLE_MAX        1048576   /* N, without thinning */
+#define SH_SAMPLE_THIN_MAX   65536     /* N, with thinning (all pairs are looked at) */
+#define SH_SAMPLE_BLOCK      256
+#define SH_THIN_MAX_ROUNDS   32
+typedef struct sh_sample_options { double radius; int32_t max_rounds; int32_t reserved; } sh_sample_options;   /* 16 B; radius 0: no thinning */
+typedef struct sh_sample      { double point[3]; double u, v; int32_t face; int32_t keep; } sh_sample;          /* 48 B */
+typedef struct sh_sample_info { double area; int32_t kept, rounds, status, reserved; } sh_sample_info;          /* 24 B */
+int sh_sample_surface(sh_ctx*, int N, const uint64_t* seeds /* B, host */, const sh_sample_options* options,
+                      sh_sample* out /* B x N, host, nullable */, sh_sample_info* info /* B, host, nullable */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

@@ -310,6 +310,31 @@ MASS_DTYPE = np.dtype([("area", "<f8"), ("volume", "<f8"), ("closure", "<f8"), (
 assert MASS_DTYPE.itemsize == ctypes.sizeof(Mass) == 400
 
 
+SAMPLE_MAX, SAMPLE_THIN_MAX, SAMPLE_BLOCK, THIN_MAX_ROUNDS = 1048576, 65536, 256, 32
+
+
+class SampleOptions(ctypes.Structure):
+    """sh_sample_options: the minimum spacing of the thinning in mm (0: no thinning) and the rounds it may take (1..32)."""
+    _fields_ = [("radius", ctypes.c_double), ("max_rounds", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class Sample(ctypes.Structure):
+    """sh_sample: one surface sample of a resident humerus -- the point (CT), the barycentric weights u, v of corners B and C of its
+    face (humerus-local), and keep: 1 kept, 0 removed by the thinning, -1 undecided when max_rounds ran out."""
+    _fields_ = [("point", ctypes.c_double * 3), ("u", ctypes.c_double), ("v", ctypes.c_double), ("face", ctypes.c_int32), ("keep", ctypes.c_int32)]
+
+
+class SampleInfo(ctypes.Structure):
+    """sh_sample_info: the humerus' area, its samples with keep == 1, the rounds the thinning took, and the status."""
+    _fields_ = [("area", ctypes.c_double), ("kept", ctypes.c_int32), ("rounds", ctypes.c_int32), ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+SAMPLE_DTYPE = np.dtype([("point", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"), ("face", "<i4"), ("keep", "<i4")])
+SAMPLE_INFO_DTYPE = np.dtype([("area", "<f8"), ("kept", "<i4"), ("rounds", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+assert SAMPLE_DTYPE.itemsize == ctypes.sizeof(Sample) == 48 and SAMPLE_INFO_DTYPE.itemsize == ctypes.sizeof(SampleInfo) == 24
+assert ctypes.sizeof(SampleOptions) == 16
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -326,7 +351,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
            "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan",
            "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points", "sh_winding_numbers", "sh_register_points",
-           "sh_mass_properties", "sh_register_multistart"]
+           "sh_mass_properties", "sh_register_multistart", "sh_sample_surface"]
 
 _lib = None
 
@@ -440,5 +465,7 @@ def load(build_if_missing=True):
     if not alt or hasattr(L, "sh_mass_properties"):      # (tools/time_register_global.py and the benchmark's parent arm)
         L.sh_mass_properties.argtypes = [vp, vp]
         L.sh_register_multistart.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    if not alt or hasattr(L, "sh_sample_surface"):      # (tools/time_sample.py and the benchmark's parent arm)
+        L.sh_sample_surface.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(SampleOptions), vp, vp]
     _lib = L
     return L

@@ -487,16 +487,49 @@ class ProximalHumerus(Bone):
             raise ValueError(f"closest_point failed with status {int(rec['status'][rec['status'] != 0][0])}: no face of the mesh gave a finite distance")
         return self._engine.transform_points(np.ascontiguousarray(rec["point"]), T), np.array(rec["dist"]), np.array(rec["face"], dtype=np.int64)
 
-    def surface_distance(self, other):
+    def _other_points(self, other, sample, seed):
+        """the points of `other` that register / surface_distance use: an (n, 3) array, `.vertices`, or with sample=n and a bone n
+        area-weighted surface samples of it (`other.sample_surface(n, seed)`), read in the CURRENT coordinate system like the others"""
+        if sample is not None:
+            if not hasattr(other, "sample_surface"):
+                raise ValueError("sample=n needs a bone (something with sample_surface) as `other`")
+            return other.sample_surface(int(sample), seed=seed)[0]
+        return other.vertices if hasattr(other, "vertices") else other
+
+    def surface_distance(self, other, sample=None, seed=0, symmetric=False):
         """How far `other` lies from this bone's surface: `other` is an (n, 3) array of points or anything with `.vertices` (a Mesh,
         another bone's mesh, a half from `resect_mesh()`), in the CURRENT coordinate system.  -> dict with `mean`, `rms`, `max` (the
         one-sided Hausdorff distance), `p95`, `n` and `argmax` (the index of the farthest point), from one closest_point call.
         ONE-SIDED by design: the distances run from the points of `other` to this surface.  For the symmetric figures call
-        `b.surface_distance(a.mesh)` on the other bone as well and take the larger `max` (Hausdorff) or pool the two sets of distances."""
-        pts = other.vertices if hasattr(other, "vertices") else other
-        d = self.closest_point(pts)[1]
-        return dict(mean=float(d.mean()), rms=float(np.sqrt(np.mean(d * d))), max=float(d.max()), p95=float(np.percentile(d, 95)),
-                    n=int(len(d)), argmax=int(np.argmax(d)))
+        `b.surface_distance(a.mesh)` on the other bone as well and take the larger `max` (Hausdorff) or pool the two sets of distances.
+
+        Vertices follow the mesher's density, not the surface.  With `sample=n` and a bone as `other` the points are n area-weighted
+        samples of its surface instead (`other.sample_surface(n, seed)`); `symmetric=True` (needs `sample`) also measures n samples of
+        this bone against `other` and adds `max_back`, `rms_back` and `hausdorff`, the larger of the two `max`."""
+        if symmetric and sample is None:
+            raise ValueError("symmetric=True needs sample=n and a bone as `other`")
+        d = self.closest_point(self._other_points(other, sample, seed))[1]
+        out = dict(mean=float(d.mean()), rms=float(np.sqrt(np.mean(d * d))), max=float(d.max()), p95=float(np.percentile(d, 95)),
+                   n=int(len(d)), argmax=int(np.argmax(d)))
+        if symmetric:
+            back = other.closest_point(self.sample_surface(int(sample), seed=seed)[0])[1]
+            out.update(max_back=float(back.max()), rms_back=float(np.sqrt(np.mean(back * back))), hausdorff=max(out["max"], float(back.max())))
+        return out
+
+    # -- surface samples ------------------------------------------------------------------------------------------
+    def sample_surface(self, n, seed=0, radius=None):
+        """`trimesh.sample.sample_surface(mesh, n)` in the CURRENT coordinate system on the device (Engine.sample_surface): n points
+        on the surface, every face drawn in proportion to its area -> (points (n, 3), face_index (n,)).  With `radius` (mm) it is
+        `sample_surface_even`: only the samples that keep that spacing are returned (m <= n of them; n at most 65 536).  The same seed
+        gives the same points.  Raises ValueError for a mesh without area or a thinning that did not finish."""
+        self._ensure_loaded()
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        rec, info = self._engine.sample_surface(n, seed=seed, radius=radius)
+        if info[0]["status"] != 0:
+            raise ValueError(f"sample_surface failed with status {int(info[0]['status'])}: the mesh has no area, or the thinning was not decided "
+                             f"within its rounds (rounds {int(info[0]['rounds'])})")
+        rec = rec[0][rec[0]["keep"] == 1]
+        return self._engine.transform_points(np.ascontiguousarray(rec["point"]), T), np.array(rec["face"], dtype=np.int64)
 
     # -- inside tests: generalized winding numbers -------------------------------------------------------------
     def winding_number(self, points):
@@ -544,7 +577,7 @@ class ProximalHumerus(Bone):
                     faces=int(m["faces"]), degenerate=int(m["degenerate"]), vstatus=int(m["vstatus"]))
 
     # -- rigid registration (ICP) -------------------------------------------------------------------------------
-    def register(self, other, initial=None, mirror=None, **options):
+    def register(self, other, initial=None, mirror=None, sample=None, seed=0, **options):
         """`trimesh.registration.icp(other, mesh)` / `mesh.register(other)` on the device (Engine.register): the rigid matrix that
         moves `other` onto this bone's surface.  `other` is an (n, 3) array of points or anything with `.vertices`, in the CURRENT
         coordinate system; `initial` a rigid (4, 4) starting matrix in that system (default: the identity); `mirror` = "x" | "y" | "z"
@@ -564,8 +597,11 @@ class ProximalHumerus(Bone):
         a short registration of a subsample from each and the full one from the best; for a scan, a contralateral bone or a second
         segmentation in an unknown pose.  options then also take rolls, coarse_points, coarse_iter and min_pairs, and info also holds
         winner, coarse_rms (one per start), mesh_ratio and points_ratio (the two largest shell eigenvalues' ratio: near 1 the shape
-        has no long axis and the starts are arbitrary)."""
-        pts = np.array(other.vertices if hasattr(other, "vertices") else other, dtype=np.float64).reshape(-1, 3)
+        has no long axis and the starts are arbitrary).
+
+        THE POINTS MUST COVER THE BONE.  Vertices follow the mesher's density; with `sample=n` and a bone as `other` the points are n
+        area-weighted samples of its surface instead (`other.sample_surface(n, seed)`)."""
+        pts = np.array(self._other_points(other, sample, seed), dtype=np.float64).reshape(-1, 3)
         if mirror is not None:
             if mirror not in ("x", "y", "z"):
                 raise ValueError('mirror must be "x", "y", "z" or None')

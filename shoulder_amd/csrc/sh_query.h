@@ -1,8 +1,8 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart) and the mass properties (sh_mass_properties).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties) and the surface samples (sh_sample_surface).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
@@ -29,6 +29,10 @@ struct RayKey; struct CpPart;
 #define MS_BUFS(X)                                                                                                                 \
   X(ms_T0s, "ms.T0s", double, 8) X(ms_points, "ms.points", double, 8) X(ms_coarse, "ms.coarse", sh_registration, 8)                \
   X(ms_best, "ms.best", double, 8) X(ms_winner, "ms.winner", int, 4)
+// the cumulative areas and the block bases, the records, and the states of the thinning (per humerus AR_SAMP_HEAD counters, then 2 x N)
+#define SAMP_BUFS(X)                                                                                                               \
+  X(samp_cdf, "samp.cdf", double, 8) X(samp_base, "samp.base", double, 8) X(samp_out, "samp.out", sh_sample, 8)                    \
+  X(samp_info, "samp.info", sh_sample_info, 8) X(samp_state, "samp.state", int, 4)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -37,6 +41,7 @@ SH_QUERY_LIST(Wn, WN_BUFS)
 SH_QUERY_LIST(Icp, ICP_BUFS)
 SH_QUERY_LIST(Mass, MASS_BUFS)
 SH_BUF_LIST(Ms, MS_BUFS)      // (beside an IcpView: no mesh of its own)
+SH_QUERY_LIST(Samp, SAMP_BUFS)
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -46,6 +51,7 @@ constexpr int AR_WN_TILE = 256, AR_WN_CHUNK = 256, AR_WN_BLOCK = 2048;          
 constexpr int AR_WN_FILL = 1024;      // workgroups of k_wn_walk that fill the chip, as AR_CP_FILL
 constexpr int AR_ICP_TERMS = 32, AR_ICP_TSTRIDE = 20;                             // SH_ICP_TERMS, SH_ICP_TSTRIDE
 constexpr int AR_MASS_TERMS = 24;                                                 // SH_MASS_TERMS
+constexpr int AR_SAMP_CHUNK = 256, AR_SAMP_HEAD = 64;                             // SH_SAMP_CHUNK, SH_SAMP_HEAD
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -176,6 +182,21 @@ inline MassPlan mass_plan(int B, long long maxF) {
   return {(int)blocks, z};
 }
 
+// Surface samples, N per humerus.  "samp.cdf" follows the faces (humerus b at foff[b]); "samp.base" has one double per block of
+// SH_SAMPLE_BLOCK faces of the largest humerus for every humerus; "samp.state" per humerus AR_SAMP_HEAD int32 (word r: the undecided at
+// the start of round r) and, with a radius, the two state arrays of N int32 that the rounds alternate between.
+struct SampPlan { int blocks, chunks, thin, stride; SampBytes bytes; };      // face blocks of the largest humerus, sample chunks, radius > 0, int32 of "samp.state" per humerus
+inline SampPlan samp_plan(int B, int N, bool thin, long long maxF, long long sumF) {
+  static_assert(AR_SAMP_HEAD > SH_THIN_MAX_ROUNDS, "samp.state: a counter per round and one behind the last");
+  const long long blocks = tiles_of(maxF, SH_SAMPLE_BLOCK);
+  const int chunks = (N + AR_SAMP_CHUNK - 1) / AR_SAMP_CHUNK;
+  const int stride = AR_SAMP_HEAD + (thin ? 2 * N : 0);
+  SampBytes z;
+  z.samp_cdf = (size_t)(sumF > 0 ? sumF : 1) * 8; z.samp_base = (size_t)B * blocks * 8; z.samp_out = (size_t)B * N * sizeof(sh_sample);
+  z.samp_info = (size_t)B * sizeof(sh_sample_info); z.samp_state = (size_t)B * stride * 4;
+  return {(int)blocks, chunks, thin ? 1 : 0, stride, z};
+}
+
 // Multi-start registration: the coarse stage is sh_register_points on Qc points, the fine stage on all Q, both on the "icp.*" buffers,
 // which take the larger of the two sizes field by field (the split of the walk, and so "icp.cp_part", may be larger for the fewer points).
 inline int ms_coarse_count(int Q, int coarse_points) { return coarse_points == 0 || coarse_points > Q ? Q : coarse_points; }
@@ -220,6 +241,17 @@ inline ArthroError precheck_winding(const double* points, int Q, int per_humerus
 
 inline ArthroError precheck_mass(const ArthroFacts& f) {
   if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
+  return resident(f);
+}
+
+inline bool sample_options_ok(const sh_sample_options* o) {
+  return std::isfinite(o->radius) && o->radius >= 0.0 && o->max_rounds >= 1 && o->max_rounds <= SH_THIN_MAX_ROUNDS && o->reserved == 0;
+}
+inline ArthroError precheck_sample(int N, const uint64_t* seeds, const sh_sample_options* opt, const ArthroFacts& f) {
+  if (!f.ctx || !seeds || !opt) return {SH_ERR_ARG, "bad argument (context, seeds and options must be given)"};
+  if (N < 1 || N > SH_SAMPLE_MAX) return {SH_ERR_ARG, "bad argument (N in 1..1048576)"};
+  if (!sample_options_ok(opt)) return {SH_ERR_ARG, "bad options (radius finite and >= 0, max_rounds in 1..32, reserved 0)"};
+  if (opt->radius > 0.0 && N > SH_SAMPLE_THIN_MAX) return {SH_ERR_ARG, "bad argument (N in 1..65536 with a radius: the thinning looks at all pairs)"};
   return resident(f);
 }
 

@@ -1,6 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
-// point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), and the mass properties, sh_mass_properties (k_mass.h).
+// point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), and the surface samples, sh_sample_surface
+// (k_sample.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -12,6 +13,7 @@ static_assert(AR_CP_TILE == SH_CP_TILE && AR_CP_CHUNK == SH_CP_CHUNK && AR_CP_PA
 static_assert(AR_WN_TILE == SH_WN_TILE && AR_WN_CHUNK == SH_WN_CHUNK && AR_WN_BLOCK == SH_WIND_BLOCK, "sh_query.h: winding tile, chunk, block");
 static_assert(AR_ICP_TERMS == SH_ICP_TERMS && AR_ICP_TSTRIDE == SH_ICP_TSTRIDE, "sh_query.h: registration terms, stride of icp.T");
 static_assert(AR_MASS_TERMS == SH_MASS_TERMS, "sh_query.h: mass terms");
+static_assert(AR_SAMP_CHUNK == SH_SAMP_CHUNK && AR_SAMP_HEAD == SH_SAMP_HEAD, "sh_query.h: sample chunk, head of samp.state");
 
 // ---- rays, every hit (k_rays.h); the anatomic-neck rays also read the last run ----
 // count -> scan -> the total to the host -> "ray.pool" -> fill -> sort -> copies back.  "ray.rays" (and "ray.status" with `box`) are filled
@@ -217,6 +219,35 @@ int sh_mass_properties(sh_ctx* c, sh_mass* out) {
   LAUNCH(c, "k_mass_sum", k_mass_sum, dim3((unsigned)plan.blocks, (unsigned)B), dim3(SH_MASS_BLOCK), v.verts, v.faces, v.voff, v.foff, v.mass_part);
   LAUNCH(c, "k_mass_join", k_mass_join, dim3((unsigned)B), dim3(64), v.verts, v.voff, v.foff, (const double*)v.mass_part, plan.blocks, v.mass_out);
   if (out) HIPCHK(c, hipMemcpyAsync(out, v.mass_out, plan.bytes.mass_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- surface samples (k_sample.h) ----
+// heads (the seeds, every counter 0) -> scan -> base -> draw -> max_rounds x thin -> finish; the host looks at nothing in between
+int sh_sample_surface(sh_ctx* c, int N, const uint64_t* seeds, const sh_sample_options* opt, sh_sample* out, sh_sample_info* info) {
+  if (const ArthroError e = precheck_sample(N, seeds, opt, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_sample_surface", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B, thin = opt->radius > 0.0 ? 1 : 0;
+  const SampPlan plan = samp_plan(B, N, thin != 0, c->maxF, c->sumF);
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  const SampView v = view_of<SampView>(c);
+  std::vector<int32_t> heads((size_t)B * SH_SAMP_HEAD, 0);      // (pageable: the call synchronises before it returns)
+  for (int b = 0; b < B; ++b) memcpy(&heads[(size_t)b * SH_SAMP_HEAD + SH_SAMP_SEED_WORD], seeds + b, 8);
+  HIPCHK(c, hipMemcpy2DAsync(v.samp_state, (size_t)plan.stride * 4, heads.data(), SH_SAMP_HEAD * 4, SH_SAMP_HEAD * 4, (size_t)B, hipMemcpyHostToDevice, c->stream));
+  const dim3 chunks((unsigned)plan.chunks, (unsigned)B), lanes(SH_SAMP_CHUNK);
+  LAUNCH(c, "k_samp_scan", k_samp_scan, dim3((unsigned)plan.blocks, (unsigned)B), dim3(SH_SAMPLE_BLOCK), v.verts, v.faces, v.voff, v.foff, v.samp_cdf, v.samp_base);
+  LAUNCH(c, "k_samp_base", k_samp_base, dim3((unsigned)B), dim3(256), v.foff, plan.blocks, N, thin, v.samp_base, v.samp_cdf, v.samp_info, v.samp_state, plan.stride);
+  LAUNCH(c, "k_samp_draw", k_samp_draw, chunks, lanes, v.verts, v.faces, v.voff, v.foff, (const double*)v.samp_cdf, (const sh_sample_info*)v.samp_info, N, thin,
+         v.samp_out, v.samp_state, plan.stride);
+  if (thin) {
+    const double r2 = opt->radius * opt->radius;
+    for (int r = 0; r < opt->max_rounds; ++r)
+      LAUNCH(c, "k_samp_thin", k_samp_thin, chunks, lanes, (const sh_sample*)v.samp_out, N, r2, r, v.samp_state, plan.stride);
+    LAUNCH(c, "k_samp_finish", k_samp_finish, dim3((unsigned)B), dim3(256), N, (int)opt->max_rounds, (const int*)v.samp_state, plan.stride, v.samp_out, v.samp_info);
+  }
+  if (out) HIPCHK(c, hipMemcpyAsync(out, v.samp_out, plan.bytes.samp_out, hipMemcpyDeviceToHost, c->stream));
+  if (info) HIPCHK(c, hipMemcpyAsync(info, v.samp_info, plan.bytes.samp_info, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -1387,6 +1387,12 @@ SH_HD int icp_step(int metric, int k, int max_iter, double tol, const double* to
 #define SH_MASS_DOUBLES 48      // the doubles of an sh_mass, in its order
 #define SH_MASS_SWEEPS 12       // cyclic Jacobi sweeps of sym3_jacobi: fixed, converged or not
 
+// twice the area of a face from its edges ab = B - A and ac = C - A, and its normal n = cross3(ab, ac) (mass properties, surface samples)
+SH_HD double face_area2(const double* ab, const double* ac, double* n) {
+  cross3(ab, ac, n);
+  return sqrt(dot3(n, n));
+}
+
 // the terms of one face with the widened corners A, B, C, relative to the pivot o
 SH_HD void mass_face_terms(const double* o, const double* A, const double* B, const double* C, double* t /* SH_MASS_TERMS */) {
   const double a[3] = {A[0] - o[0], A[1] - o[1], A[2] - o[2]};
@@ -1395,8 +1401,7 @@ SH_HD void mass_face_terms(const double* o, const double* A, const double* B, co
   const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
   const double ac[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
   double n[3], bc[3], m[6];
-  cross3(ab, ac, n);
-  const double A2 = sqrt(dot3(n, n));
+  const double A2 = face_area2(ab, ac, n);
   const double s[3] = {(a[0] + b[0]) + c[0], (a[1] + b[1]) + c[1], (a[2] + b[2]) + c[2]};
   cross3(b, c, bc);
   const double d = dot3(a, bc);
@@ -1520,5 +1525,66 @@ SH_HD void mass_finish(const double* T, const double* o, int nf, double* rec /* 
   }
   if (!vok) irec[3] = SH_ERR_GEOMETRY_DEV;
 }
+
+// ---- surface samples of the resident batch (include/shoulder_hip.h sh_sample_surface; k_sample.h) ----------------------------------
+// Integer words, and + - x sqrt on float64 in the written order (-ffp-contract=off), restated by tests/sample_oracle.py.
+#define SH_SAMP_REMOVED 0        // the states of the thinning are the values of sh_sample.keep
+#define SH_SAMP_KEPT 1
+#define SH_SAMP_UNDECIDED (-1)
+
+// SplitMix64 as a counter generator: word n of a seed, and a word as a double in [0, 1) (its top 53 bits: the product is exact)
+SH_HD unsigned long long samp_mix(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+SH_HD unsigned long long samp_word(unsigned long long seed, unsigned long long n) { return samp_mix(seed + (n + 1ull) * 0x9E3779B97F4A7C15ull); }
+SH_HD double samp_unit(unsigned long long w) { return (double)(w >> 11) * 1.1102230246251565e-16; }
+
+// twice the area of the face with the widened corners A, B, C
+SH_HD double samp_area2(const double* A, const double* B, const double* C) {
+  const double ab[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+  const double ac[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]};
+  double n[3];
+  return face_area2(ab, ac, n);
+}
+
+// the scan of one block, in place and strictly in index order: s[0] = a[0], s[i] = s[i - 1] + a[i]
+SH_HD void samp_scan_block(double* s, int n) {
+  for (int i = 1; i < n; ++i) s[i] = s[i - 1] + s[i];
+}
+
+// the smallest f in [0, nf - 1] with cdf[f] > target, nf - 1 when there is none (nf >= 1, cdf non-decreasing)
+SH_HD long long samp_search(const double* cdf, long long nf, double target) {
+  long long lo = 0, hi = nf;
+  while (lo < hi) {
+    const long long mid = lo + ((hi - lo) >> 1);
+    if (cdf[mid] > target) hi = mid; else lo = mid + 1;
+  }
+  return lo < nf ? lo : nf - 1;
+}
+
+// the point of the words' r1, r2 on the face with the widened corners A, B, C, folded into the triangle: out[0..2] the point, out[3] u, out[4] v
+SH_HD void samp_point(const double* A, const double* B, const double* C, double r1, double r2, double* out /* 5 */) {
+  if (r1 + r2 > 1.0) { r1 = 1.0 - r1; r2 = 1.0 - r2; }
+  for (int k = 0; k < 3; ++k) {
+    const double ab = B[k] - A[k], ac = C[k] - A[k];
+    out[k] = A[k] + (r1 * ab + r2 * ac);
+  }
+  out[3] = r1; out[4] = r2;
+}
+
+// The round rule of the thinning for one undecided sample j.  samp_thin_see folds one candidate i < j -- its state at the start of the
+// round and its squared distance to j -- into the flags (bit 0: a kept neighbour, bit 1: an undecided one); samp_thin_verdict is j's
+// state after the round.  A kept neighbour decides j: the caller may stop looking.
+SH_HD double samp_d2(const double* p, const double* q) {
+  const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+  return (dx * dx + dy * dy) + dz * dz;
+}
+SH_HD int samp_thin_see(int flags, int state_i, double d2, double r2) {
+  if (state_i == SH_SAMP_REMOVED || !(d2 < r2)) return flags;
+  return flags | (state_i == SH_SAMP_KEPT ? 1 : 2);
+}
+SH_HD int samp_thin_verdict(int flags) { return (flags & 1) ? SH_SAMP_REMOVED : (flags & 2) ? SH_SAMP_UNDECIDED : SH_SAMP_KEPT; }
 
 }  // namespace sh

@@ -735,6 +735,28 @@ class Engine:
         self._chk(self.L.sh_mass_properties(self.h, _ptr(out)))
         return out
 
+    # ---- surface samples of the resident batch (include/shoulder_hip.h sh_sample_surface) ---------------------------------------
+    def sample_surface(self, n, seed=0, radius=None, max_rounds=32):
+        """`trimesh.sample.sample_surface` / `sample_surface_even` for every resident humerus in one device pass -> (samples, info):
+        a structured array (B, n) of _lib.SAMPLE_DTYPE -- point (CT), u, v (the barycentric weights of corners B and C), face
+        (humerus-local), keep -- and (B,) of _lib.SAMPLE_INFO_DTYPE: area, kept, rounds, status.  Every face is drawn in proportion to
+        its area.  seed: an int for all humeri or a sequence of B ints; a sample depends on its mesh, its seed and its index alone, so
+        the first n samples of a larger call are these.  radius (mm): the greedy thinning of `remove_close` on top -- keep is 1 for a
+        sample with no kept sample of lower index nearer than radius, else 0; n at most 65 536 then, and a humerus not decided within
+        max_rounds has status SH_ERR_CAPACITY and keep = -1 where undecided.  A mesh without area has status SH_ERR_GEOMETRY and zero
+        records.  Needs no run."""
+        nb = max(self.B, 1)      # (without a batch the library refuses; it still gets a pointer)
+        seeds = np.full(nb, seed, dtype=np.uint64) if np.ndim(seed) == 0 else np.ascontiguousarray(seed, dtype=np.uint64)
+        if seeds.shape != (nb,):
+            raise ValueError("seed must be an int or a sequence of B ints")
+        opt = _lib.SampleOptions(0.0 if radius is None else float(radius), int(max_rounds), 0)
+        n = int(n)
+        ok = 1 <= n <= _lib.SAMPLE_MAX      # (the library reports the rest; nothing is sized by it here)
+        out = np.zeros((self.B, n) if ok else (0,), dtype=_lib.SAMPLE_DTYPE)
+        info = np.zeros(max(self.B, 0), dtype=_lib.SAMPLE_INFO_DTYPE)
+        self._chk(self.L.sh_sample_surface(self.h, n, _ptr(seeds), ctypes.byref(opt), _ptr(out), _ptr(info)))
+        return out, info
+
     # ---- multi-start registration (include/shoulder_hip.h sh_register_multistart) -----------------------------------------------
     def principal_starts(self, points, rolls=8, with_ratios=False):
         """Starting transforms for register_multistart from principal frames -> (B, 2 * rolls, 4, 4).  The mesh frame is shell_centroid
