@@ -883,6 +883,64 @@ typedef struct sh_sample_info { double area; int32_t kept, rounds, status, reser
 int sh_sample_surface(sh_ctx*, int N, const uint64_t* seeds /* B, host */, const sh_sample_options* options,
                       sh_sample* out /* B x N, host, nullable */, sh_sample_info* info /* B, host, nullable */);
 
+/* ---- mesh topology of the resident batch: incidence, face adjacency, shells, counts -------------------------------------------------
+ * How the triangles of each of the B resident meshes hang together, in one device pass (k_topo.h): the vertex -> face incidence, trimesh's
+ * `face_adjacency`, the connected components of `mesh.split(only_watertight=False)` ("shells") and the counts that go with them.  Indices
+ * are local to the mesh; all arithmetic is integer except the box corners, which are float32 minima and maxima.
+ *   degenerate  a face is degenerate when two of its three vertex INDICES are equal.  It takes no part in anything below except
+ *               faces_degenerate, its three adjacency slots (SH_ADJ_DEGENERATE) and its label (-1).
+ *   incidence   "topo.vrow", int32, V_b + 1 entries per mesh at voff[b] + b: the exclusive prefix sums of the number of non-degenerate
+ *               faces using each vertex.  "topo.vface", int32, 3 F_b entries per mesh at 3 foff[b]: row v = vface[vrow[v] .. vrow[v + 1])
+ *               lists the faces using v in ASCENDING face index; the entries behind vrow[V_b] are -1.
+ *   adjacency   "topo.adj", int32, 3 per face at 3 foff[b].  Slot e of face f concerns the undirected edge {f[e], f[(e + 1) % 3]} among the
+ *               non-degenerate faces: the other face's index when exactly two faces use the edge (pairs only, as face_adjacency),
+ *               SH_ADJ_BORDER when f alone uses it, SH_ADJ_NONMANIFOLD when three or more do, SH_ADJ_DEGENERATE in all three slots of a
+ *               degenerate face.  A manifold edge (two uses) is INCONSISTENT when both faces traverse it in the same direction.
+ *   shells      the connected components of the graph with one node per non-degenerate face and one edge per slot >= 0: faces that meet
+ *               only in a vertex, or only in a non-manifold edge, are in different shells.  Shell k is the one with the k-th smallest
+ *               first (lowest) face.  "topo.label", int32 per face at foff[b]: the shell index, -1 for a degenerate face.
+ *   rounds      the labels are unique, so any schedule gives them; the ROUNDS are part of the record, so the schedule is fixed: Jacobi
+ *               rounds of FastSV on two arrays.  p[f] = f at the start.  A round reads only the old array, forms g[u] = p[p[u]], and the
+ *               new p[u] is the minimum of g[u], of every g[v] with v a neighbour of u (slot >= 0), and of every g[v] with v a neighbour
+ *               of some u' that has p[u'] = u.  `rounds` counts the rounds up to and including the first one that changes nothing.  The
+ *               host enqueues max_rounds launches and looks at nothing in between; the workgroups of a finished mesh return at once.  A
+ *               mesh not finished after max_rounds: status SH_ERR_CAPACITY, rounds = max_rounds, n_shells = shells_written = 0,
+ *               largest_shell = -1, largest_faces = 0, all its labels -1, no shell records; its incidence, adjacency and the other
+ *               counts stay valid.  Never the batch.
+ *   sh_topology per mesh, resident in "topo.info": vertices_used = the vertices with a non-empty row; edges = the distinct undirected edges;
+ *               border_edges = those with one use; nonmanifold_edges = those with three or more; inconsistent_edges; euler =
+ *               vertices_used - edges + non-degenerate faces; max_valence = the longest row; n_shells, exact whatever max_shells;
+ *               shells_written = min(n_shells, max_shells); largest_shell and largest_faces, ties to the smaller index (-1 and 0 without a
+ *               shell); flags bit 0 (SH_TOPO_WATERTIGHT): border_edges == 0 && nonmanifold_edges == 0 && faces_degenerate == 0, bit 1
+ *               (SH_TOPO_CONSISTENT): inconsistent_edges == 0.
+ *   sh_shell    the first max_shells shells of each mesh, resident in "topo.shells" (B x max_shells; the records behind shells_written are
+ *               zero): first_face, faces, border_slots, nonmanifold_slots, manifold_edges = (slots >= 0) / 2, inconsistent_edges, and
+ *               lo / hi, the float32 box of its faces' corners (under the order in which -0 < +0: exact under any schedule).
+ *
+ * Arguments in this order: the context and options (SH_ERR_ARG); max_shells in 1..SH_TOPO_MAX_SHELLS, max_rounds in 1..SH_TOPO_MAX_ROUNDS,
+ * reserved == 0; a resident batch and no runs in flight (SH_ERR_STATE; a run is not needed).  SH_ERR_NOMEM when the buffers do not fit.
+ * Reads "verts", "faces" and the offsets.  Resident afterwards: "topo.vrow", "topo.vface", "topo.adj", "topo.label", "topo.info",
+ * "topo.shells" and the scratch "topo.state", "topo.cursor", "topo.tmp", "topo.p", until the next upload / commit / sh_store("verts"),
+ * which removes them as it removes "mass.*" and "samp.*".  Every other buffer keeps its bytes. */
+#define SH_ADJ_BORDER        (-1)
+#define SH_ADJ_NONMANIFOLD   (-2)
+#define SH_ADJ_DEGENERATE    (-3)
+#define SH_TOPO_MAX_SHELLS   65536
+#define SH_TOPO_MAX_ROUNDS   32
+#define SH_TOPO_WATERTIGHT   1
+#define SH_TOPO_CONSISTENT   2
+typedef struct sh_topology_options { int32_t max_shells, max_rounds, reserved; } sh_topology_options;          /* 12 B */
+typedef struct sh_topology {
+  int32_t status, rounds, faces_degenerate, vertices_used, edges, border_edges, nonmanifold_edges, inconsistent_edges;
+  int32_t euler, max_valence, n_shells, shells_written, largest_shell, largest_faces, flags, reserved;
+} sh_topology;                                                                                                 /* 64 B */
+typedef struct sh_shell {
+  int32_t first_face, faces, border_slots, nonmanifold_slots, manifold_edges, inconsistent_edges;
+  float lo[3], hi[3];
+} sh_shell;                                                                                                    /* 48 B */
+int sh_mesh_topology(sh_ctx*, const sh_topology_options* options, sh_topology* info /* B, host, nullable */,
+                     sh_shell* shells /* B x max_shells, host, nullable */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

@@ -335,6 +335,35 @@ assert SAMPLE_DTYPE.itemsize == ctypes.sizeof(Sample) == 48 and SAMPLE_INFO_DTYP
 assert ctypes.sizeof(SampleOptions) == 16
 
 
+ADJ_BORDER, ADJ_NONMANIFOLD, ADJ_DEGENERATE = -1, -2, -3
+TOPO_MAX_SHELLS, TOPO_MAX_ROUNDS, TOPO_WATERTIGHT, TOPO_CONSISTENT = 65536, 32, 1, 2
+_TOPOLOGY_FIELDS = ("status", "rounds", "faces_degenerate", "vertices_used", "edges", "border_edges", "nonmanifold_edges", "inconsistent_edges",
+                    "euler", "max_valence", "n_shells", "shells_written", "largest_shell", "largest_faces", "flags", "reserved")
+_SHELL_COUNTS = ("first_face", "faces", "border_slots", "nonmanifold_slots", "manifold_edges", "inconsistent_edges")
+
+
+class TopologyOptions(ctypes.Structure):
+    """sh_topology_options: the shell records kept per mesh (1..65536) and the rounds the labelling may take (1..32)."""
+    _fields_ = [("max_shells", ctypes.c_int32), ("max_rounds", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class Topology(ctypes.Structure):
+    """sh_topology: the counts of one resident mesh (include/shoulder_hip.h); flags bit 0 watertight, bit 1 winding-consistent."""
+    _fields_ = [(n, ctypes.c_int32) for n in _TOPOLOGY_FIELDS]
+
+
+class Shell(ctypes.Structure):
+    """sh_shell: one connected component over manifold edges -- its first face, its faces, its slot counts and its float32 box."""
+    _fields_ = [(n, ctypes.c_int32) for n in _SHELL_COUNTS] + [("lo", ctypes.c_float * 3), ("hi", ctypes.c_float * 3)]
+
+
+TOPOLOGY_OPTIONS = TopologyOptions
+TOPOLOGY_DTYPE = np.dtype([(n, "<i4") for n in _TOPOLOGY_FIELDS])
+SHELL_DTYPE = np.dtype([(n, "<i4") for n in _SHELL_COUNTS] + [("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
+assert TOPOLOGY_DTYPE.itemsize == ctypes.sizeof(Topology) == 64 and SHELL_DTYPE.itemsize == ctypes.sizeof(Shell) == 48
+assert ctypes.sizeof(TopologyOptions) == 12
+
+
 class Params(ctypes.Structure):
     _fields_ = [("canal_cutoff", ctypes.c_double * 2), ("groove_cutoff", ctypes.c_double * 2),
                 ("groove_deg_window", ctypes.c_double), ("unet_dtype", ctypes.c_int32), ("bone_kind", ctypes.c_int32)]
@@ -351,7 +380,7 @@ EXPORTS = ["sh_ctx_create", "sh_ctx_destroy", "sh_last_error", "sh_default_param
            "sh_resect_planes", "sh_resect_offsets", "sh_resect_ring", "sh_resect_planes_fit", "sh_resect_offsets_fit",
            "sh_resect_planes_seat", "sh_resect_offsets_seat", "sh_canal_profile", "sh_resect_stems", "sh_resect_plan",
            "sh_ray_cast", "sh_anp_axis_hits", "sh_closest_points", "sh_winding_numbers", "sh_register_points",
-           "sh_mass_properties", "sh_register_multistart", "sh_sample_surface"]
+           "sh_mass_properties", "sh_register_multistart", "sh_sample_surface", "sh_mesh_topology"]
 
 _lib = None
 
@@ -467,5 +496,7 @@ def load(build_if_missing=True):
         L.sh_register_multistart.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     if not alt or hasattr(L, "sh_sample_surface"):      # (tools/time_sample.py and the benchmark's parent arm)
         L.sh_sample_surface.argtypes = [vp, ctypes.c_int, vp, ctypes.POINTER(SampleOptions), vp, vp]
+    if not alt or hasattr(L, "sh_mesh_topology"):      # (tools/time_topology.py and the benchmark's parent arm)
+        L.sh_mesh_topology.argtypes = [vp, ctypes.POINTER(TopologyOptions), vp, vp]
     _lib = L
     return L

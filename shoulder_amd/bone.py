@@ -531,6 +531,35 @@ class ProximalHumerus(Bone):
         rec = rec[0][rec[0]["keep"] == 1]
         return self._engine.transform_points(np.ascontiguousarray(rec["point"]), T), np.array(rec["face"], dtype=np.int64)
 
+    # -- topology: adjacency, shells, counts -------------------------------------------------------------------------
+    def topology(self, max_shells=64, max_rounds=32):
+        """How this bone's triangles hang together, on the device (Engine.topology) -> dict of the mesh's record: faces_degenerate,
+        vertices_used, edges, border_edges, nonmanifold_edges, inconsistent_edges, euler, max_valence, n_shells, shells_written,
+        largest_shell, largest_faces, rounds, plus watertight and winding_consistent (the two flags), shells (the first max_shells
+        shell records; their boxes are CT's) and, for a watertight mesh, genus = (2 n_shells - euler) / 2: the handles of all shells
+        together (1: one tunnel).  Raises ValueError when the labelling did not finish within max_rounds."""
+        self._ensure_loaded()
+        info, shells = self._engine.topology(max_shells=max_shells, max_rounds=max_rounds)
+        r = info[0]
+        if r["status"] != 0:
+            raise ValueError(f"topology failed with status {int(r['status'])}: the shells were not labelled within {int(r['rounds'])} rounds")
+        out = {n: int(r[n]) for n in r.dtype.names if n not in ("status", "flags", "reserved")}
+        out["watertight"], out["winding_consistent"] = bool(r["flags"] & _lib.TOPO_WATERTIGHT), bool(r["flags"] & _lib.TOPO_CONSISTENT)
+        out["shells"] = shells[0][:out["shells_written"]].copy()
+        if out["watertight"]:
+            out["genus"] = (2 * out["n_shells"] - out["euler"]) // 2
+        return out
+
+    def shells(self, largest_only=False):
+        """`mesh.split(only_watertight=False)` of this bone (Engine.split) -> a list of (verts, faces) in CT, one per shell in shell
+        order (the largest alone with largest_only): the standard first step on a segmentation with islands of noise.  Each is ready
+        for Engine.upload."""
+        self._ensure_loaded()
+        info = self._engine.topology()[0][0]
+        if info["status"] != 0:
+            raise ValueError(f"shells failed with status {int(info['status'])}: the shells were not labelled within {int(info['rounds'])} rounds")
+        return self._engine.split(0, largest_only=largest_only)
+
     # -- inside tests: generalized winding numbers -------------------------------------------------------------
     def winding_number(self, points):
         """The generalized winding number of the mesh about `points` (n, 3) in the CURRENT coordinate system -> float64 (n,), on the

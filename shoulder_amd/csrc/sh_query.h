@@ -1,8 +1,8 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart), the mass properties (sh_mass_properties) and the surface samples (sh_sample_surface).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface) and the mesh topology (sh_mesh_topology).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
@@ -33,6 +33,12 @@ struct RayKey; struct CpPart;
 #define SAMP_BUFS(X)                                                                                                               \
   X(samp_cdf, "samp.cdf", double, 8) X(samp_base, "samp.base", double, 8) X(samp_out, "samp.out", sh_sample, 8)                    \
   X(samp_info, "samp.info", sh_sample_info, 8) X(samp_state, "samp.state", int, 4)
+// the incidence (row starts, rows), the adjacency, the labels and the records; scratch: the heads (AR_TOPO_HEAD int32 per mesh), the rows'
+// cursors, the unordered rows / shell indices / shell sizes, and the two arrays of the rounds
+#define TOPO_BUFS(X)                                                                                                               \
+  X(topo_vrow, "topo.vrow", int, 4) X(topo_vface, "topo.vface", int, 4) X(topo_adj, "topo.adj", int, 4) X(topo_label, "topo.label", int, 4) \
+  X(topo_info, "topo.info", sh_topology, 4) X(topo_shells, "topo.shells", sh_shell, 4) X(topo_state, "topo.state", int, 4)         \
+  X(topo_cursor, "topo.cursor", int, 4) X(topo_tmp, "topo.tmp", int, 4) X(topo_p, "topo.p", int, 4)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -42,6 +48,7 @@ SH_QUERY_LIST(Icp, ICP_BUFS)
 SH_QUERY_LIST(Mass, MASS_BUFS)
 SH_BUF_LIST(Ms, MS_BUFS)      // (beside an IcpView: no mesh of its own)
 SH_QUERY_LIST(Samp, SAMP_BUFS)
+SH_QUERY_LIST(Topo, TOPO_BUFS)
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -52,6 +59,7 @@ constexpr int AR_WN_FILL = 1024;      // workgroups of k_wn_walk that fill the c
 constexpr int AR_ICP_TERMS = 32, AR_ICP_TSTRIDE = 20;                             // SH_ICP_TERMS, SH_ICP_TSTRIDE
 constexpr int AR_MASS_TERMS = 24;                                                 // SH_MASS_TERMS
 constexpr int AR_SAMP_CHUNK = 256, AR_SAMP_HEAD = 64;                             // SH_SAMP_CHUNK, SH_SAMP_HEAD
+constexpr int AR_TOPO_BLOCK = 256, AR_TOPO_HEAD = 64;                             // SH_TOPO_BLOCK, SH_TOPO_HEAD
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -197,6 +205,20 @@ inline SampPlan samp_plan(int B, int N, bool thin, long long maxF, long long sum
   return {(int)blocks, chunks, thin ? 1 : 0, stride, z};
 }
 
+// Mesh topology.  "topo.vrow" and "topo.cursor" have V_b + 1 int32 per mesh (mesh b at voff[b] + b); "topo.vface", "topo.adj" and
+// "topo.tmp" three per face (mesh b at 3 foff[b]), "topo.label" one, "topo.p" two (the arrays of the rounds, mesh b at 2 foff[b]);
+// "topo.state" AR_TOPO_HEAD int32 per mesh: word r says whether round r - 1 changed something, the counts behind the rounds.
+struct TopoPlan { int blocks; TopoBytes bytes; };      // face blocks of the largest mesh
+inline TopoPlan topo_plan(int B, int max_shells, long long maxF, long long sumV, long long sumF) {
+  static_assert(AR_TOPO_HEAD > SH_TOPO_MAX_ROUNDS + 1, "topo.state: a word per round and one behind the last");
+  const size_t f = (size_t)(sumF > 0 ? sumF : 1), rows = ((size_t)sumV + B) * 4;
+  TopoBytes z;
+  z.topo_vrow = rows; z.topo_vface = 3 * f * 4; z.topo_adj = 3 * f * 4; z.topo_label = f * 4;
+  z.topo_info = (size_t)B * sizeof(sh_topology); z.topo_shells = (size_t)B * max_shells * sizeof(sh_shell);
+  z.topo_state = (size_t)B * AR_TOPO_HEAD * 4; z.topo_cursor = rows; z.topo_tmp = 3 * f * 4; z.topo_p = 2 * f * 4;
+  return {(int)tiles_of(maxF, AR_TOPO_BLOCK), z};
+}
+
 // Multi-start registration: the coarse stage is sh_register_points on Qc points, the fine stage on all Q, both on the "icp.*" buffers,
 // which take the larger of the two sizes field by field (the split of the walk, and so "icp.cp_part", may be larger for the fewer points).
 inline int ms_coarse_count(int Q, int coarse_points) { return coarse_points == 0 || coarse_points > Q ? Q : coarse_points; }
@@ -252,6 +274,13 @@ inline ArthroError precheck_sample(int N, const uint64_t* seeds, const sh_sample
   if (N < 1 || N > SH_SAMPLE_MAX) return {SH_ERR_ARG, "bad argument (N in 1..1048576)"};
   if (!sample_options_ok(opt)) return {SH_ERR_ARG, "bad options (radius finite and >= 0, max_rounds in 1..32, reserved 0)"};
   if (opt->radius > 0.0 && N > SH_SAMPLE_THIN_MAX) return {SH_ERR_ARG, "bad argument (N in 1..65536 with a radius: the thinning looks at all pairs)"};
+  return resident(f);
+}
+
+inline ArthroError precheck_topology(const sh_topology_options* opt, const ArthroFacts& f) {
+  if (!f.ctx || !opt) return {SH_ERR_ARG, "bad argument (context and options must be given)"};
+  if (opt->max_shells < 1 || opt->max_shells > SH_TOPO_MAX_SHELLS || opt->max_rounds < 1 || opt->max_rounds > SH_TOPO_MAX_ROUNDS || opt->reserved != 0)
+    return {SH_ERR_ARG, "bad options (max_shells in 1..65536, max_rounds in 1..32, reserved 0)"};
   return resident(f);
 }
 

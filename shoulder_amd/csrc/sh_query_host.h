@@ -1,7 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
-// point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), and the surface samples, sh_sample_surface
-// (k_sample.h).
+// point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), the surface samples, sh_sample_surface
+// (k_sample.h), and the mesh topology, sh_mesh_topology (k_topo.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -14,6 +14,7 @@ static_assert(AR_WN_TILE == SH_WN_TILE && AR_WN_CHUNK == SH_WN_CHUNK && AR_WN_BL
 static_assert(AR_ICP_TERMS == SH_ICP_TERMS && AR_ICP_TSTRIDE == SH_ICP_TSTRIDE, "sh_query.h: registration terms, stride of icp.T");
 static_assert(AR_MASS_TERMS == SH_MASS_TERMS, "sh_query.h: mass terms");
 static_assert(AR_SAMP_CHUNK == SH_SAMP_CHUNK && AR_SAMP_HEAD == SH_SAMP_HEAD, "sh_query.h: sample chunk, head of samp.state");
+static_assert(AR_TOPO_BLOCK == SH_TOPO_BLOCK && AR_TOPO_HEAD == SH_TOPO_HEAD, "sh_query.h: topology block, head of topo.state");
 
 // ---- rays, every hit (k_rays.h); the anatomic-neck rays also read the last run ----
 // count -> scan -> the total to the host -> "ray.pool" -> fill -> sort -> copies back.  "ray.rays" (and "ray.status" with `box`) are filled
@@ -248,6 +249,38 @@ int sh_sample_surface(sh_ctx* c, int N, const uint64_t* seeds, const sh_sample_o
   }
   if (out) HIPCHK(c, hipMemcpyAsync(out, v.samp_out, plan.bytes.samp_out, hipMemcpyDeviceToHost, c->stream));
   if (info) HIPCHK(c, hipMemcpyAsync(info, v.samp_info, plan.bytes.samp_info, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- mesh topology (k_topo.h) ----
+// zeroed heads and counts, rows of -1 -> count -> scan -> fill -> rows -> adj -> max_rounds x round -> rank -> label -> finish; the host
+// looks at nothing in between
+int sh_mesh_topology(sh_ctx* c, const sh_topology_options* opt, sh_topology* info, sh_shell* shells) {
+  if (const ArthroError e = precheck_topology(opt, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_mesh_topology", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B, max_shells = opt->max_shells;
+  const TopoPlan plan = topo_plan(B, max_shells, c->maxF, c->sumV, c->sumF);
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  const TopoView v = view_of<TopoView>(c);
+  HIPCHK(c, hipMemsetAsync(v.topo_state, 0, plan.bytes.topo_state, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.topo_cursor, 0, plan.bytes.topo_cursor, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.topo_vface, 0xff, plan.bytes.topo_vface, c->stream));
+  const dim3 blocks((unsigned)plan.blocks, (unsigned)B), lanes(SH_TOPO_BLOCK), meshes((unsigned)B);
+  LAUNCH(c, "k_topo_count", k_topo_count, blocks, lanes, v.faces, v.voff, v.foff, v.topo_cursor, v.topo_p, v.topo_state);
+  LAUNCH(c, "k_topo_scan", k_topo_scan, meshes, dim3(256), v.voff, v.topo_cursor, v.topo_vrow, v.topo_state);
+  LAUNCH(c, "k_topo_fill", k_topo_fill, blocks, lanes, v.faces, v.voff, v.foff, v.topo_cursor, v.topo_tmp);
+  LAUNCH(c, "k_topo_rows", k_topo_rows, blocks, lanes, v.faces, v.voff, v.foff, (const int*)v.topo_vrow, (const int*)v.topo_tmp, v.topo_vface);
+  LAUNCH(c, "k_topo_adj", k_topo_adj, blocks, lanes, v.faces, v.voff, v.foff, (const int*)v.topo_vrow, (const int*)v.topo_vface, v.topo_adj, v.topo_state);
+  for (int r = 0; r < opt->max_rounds; ++r)
+    LAUNCH(c, "k_topo_round", k_topo_round, blocks, lanes, v.foff, (const int*)v.topo_adj, v.topo_p, v.topo_state, r);
+  LAUNCH(c, "k_topo_rank", k_topo_rank, meshes, dim3(256), v.foff, (const int*)v.topo_adj, (const int*)v.topo_p, v.topo_state, v.topo_tmp, (int*)v.topo_shells,
+         max_shells, (int)opt->max_rounds);
+  LAUNCH(c, "k_topo_label", k_topo_label, blocks, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_adj, (const int*)v.topo_p, (const int*)v.topo_state,
+         v.topo_tmp, v.topo_label, (int*)v.topo_shells, max_shells);
+  LAUNCH(c, "k_topo_finish", k_topo_finish, meshes, dim3(256), v.foff, (const int*)v.topo_state, (const int*)v.topo_tmp, (int*)v.topo_shells, max_shells, v.topo_info);
+  if (info) HIPCHK(c, hipMemcpyAsync(info, v.topo_info, plan.bytes.topo_info, hipMemcpyDeviceToHost, c->stream));
+  if (shells) HIPCHK(c, hipMemcpyAsync(shells, v.topo_shells, plan.bytes.topo_shells, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -1587,4 +1587,86 @@ SH_HD int samp_thin_see(int flags, int state_i, double d2, double r2) {
 }
 SH_HD int samp_thin_verdict(int flags) { return (flags & 1) ? SH_SAMP_REMOVED : (flags & 2) ? SH_SAMP_UNDECIDED : SH_SAMP_KEPT; }
 
+// ---- mesh topology of the resident batch (include/shoulder_hip.h sh_mesh_topology; k_topo.h) ----------------------------------------
+// Integer rules, restated by tests/topo_oracle.py.  The adjacency codes are the header's SH_ADJ_* (k_topo.h holds them equal).
+#define SH_TOPO_BORDER (-1)
+#define SH_TOPO_NONMANIFOLD (-2)
+#define SH_TOPO_DEGENERATE (-3)
+#define SH_TOPO_NONE 0x7fffffff      // no neighbour's value: above every face index
+
+// a face that takes no part: two equal indices (or an index outside the mesh, which an upload refuses: nothing is ever indexed by it)
+SH_HD bool topo_degenerate(const int* f, int nv) {
+  return f[0] == f[1] || f[1] == f[2] || f[0] == f[2] || f[0] < 0 || f[1] < 0 || f[2] < 0 || f[0] >= nv || f[1] >= nv || f[2] >= nv;
+}
+
+// the slot of the non-degenerate face g whose undirected edge is {a, c}, or -1
+SH_HD int topo_edge_slot(const int* g, int a, int c) {
+  for (int e = 0; e < 3; ++e) {
+    const int x = g[e], y = g[e == 2 ? 0 : e + 1];
+    if ((x == a && y == c) || (x == c && y == a)) return e;
+  }
+  return -1;
+}
+
+// Slot e of the non-degenerate face f: the users of its edge {a, c} = {f[e], f[(e + 1) % 3]} among the faces of `row`, the ascending row
+// of a or of c (both hold every user).  -> the slot's adjacency value; *owner: f is the smallest user, at whose slot the edge is counted
+// once; *same: two users and both traverse the edge from a to c (an inconsistent edge).
+SH_HD int topo_slot(const int* faces, const int* row, int n, int f, int e, int* owner, int* same) {
+  const int a = faces[3 * (size_t)f + e], c = faces[3 * (size_t)f + (e == 2 ? 0 : e + 1)];
+  int users = 0, other = -1, first = -1;
+  for (int i = 0; i < n; ++i) {
+    const int g = row[i];
+    if (topo_edge_slot(faces + 3 * (size_t)g, a, c) < 0) continue;
+    if (users == 0) first = g;
+    if (g != f) other = g;
+    ++users;
+  }
+  *owner = first == f ? 1 : 0;
+  *same = 0;
+  if (users == 1) return SH_TOPO_BORDER;
+  if (users != 2) return SH_TOPO_NONMANIFOLD;
+  const int* g = faces + 3 * (size_t)other;
+  *same = g[topo_edge_slot(g, a, c)] == a ? 1 : 0;
+  return other;
+}
+
+// One face u in a Jacobi round of FastSV on the old array `in`: *self is the value for the new p[u] (g[u] and every g[v] of a neighbour),
+// *hook the value for the new p[p[u]] (every g[v] of a neighbour; SH_TOPO_NONE without one).  -> 1 when either lowers its target below
+// what the old array holds there (in[u], and in[p[u]] = g[u]): the round changed something.
+SH_HD int topo_round(const int* in, const int* adj /* the 3 slots of u */, int u, int* self, int* hook) {
+  const int pu = in[u], gu = in[pu];
+  int h = SH_TOPO_NONE;
+  for (int e = 0; e < 3; ++e) {
+    const int v = adj[e];
+    if (v < 0) continue;
+    const int gv = in[in[v]];
+    h = gv < h ? gv : h;
+  }
+  *self = gu < h ? gu : h;
+  *hook = h;
+  return (*self < pu || h < gu) ? 1 : 0;
+}
+
+// the rounds of a head (word r: round r - 1 changed something; word 0 is 1): the smallest R >= 1 with word R == 0, or max_rounds and
+// *full = 1 when there is none up to max_rounds
+SH_HD int topo_rounds(const int* head, int max_rounds, int* full) {
+  for (int r = 1; r <= max_rounds; ++r)
+    if (head[r] == 0) { *full = 0; return r; }
+  *full = 1;
+  return max_rounds;
+}
+
+// a float32 as an unsigned whose order is the floats' (-0 below +0), and back: minima and maxima by integer atomics
+SH_HD unsigned topo_enc(float x) {
+  unsigned u;
+  __builtin_memcpy(&u, &x, 4);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+SH_HD float topo_dec(unsigned k) {
+  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float x;
+  __builtin_memcpy(&x, &u, 4);
+  return x;
+}
+
 }  // namespace sh

@@ -757,6 +757,62 @@ class Engine:
         self._chk(self.L.sh_sample_surface(self.h, n, _ptr(seeds), ctypes.byref(opt), _ptr(out), _ptr(info)))
         return out, info
 
+    # ---- mesh topology of the resident batch (include/shoulder_hip.h sh_mesh_topology) -------------------------------------------
+    def topology(self, max_shells=64, max_rounds=32):
+        """How the triangles of every resident mesh hang together, in one device pass -> (info, shells): (B,) of _lib.TOPOLOGY_DTYPE --
+        status, rounds, faces_degenerate, vertices_used, edges, border_edges, nonmanifold_edges, inconsistent_edges, euler,
+        max_valence, n_shells (exact whatever max_shells), shells_written, largest_shell, largest_faces, flags (bit 0 watertight,
+        bit 1 winding-consistent) -- and (B, max_shells) of _lib.SHELL_DTYPE, the first max_shells shells of each mesh (the records
+        behind shells_written are zero).  A shell is a connected component over manifold edges, as `mesh.split(only_watertight=False)`
+        has them.  A mesh whose labelling did not finish within max_rounds has status SH_ERR_CAPACITY, n_shells 0 and labels -1; its
+        adjacency and counts stay valid.  Resident afterwards: "topo.vrow", "topo.vface", "topo.adj", "topo.label" (face_adjacency,
+        face_labels).  Needs no run."""
+        opt = _lib.TopologyOptions(int(max_shells), int(max_rounds), 0)
+        ok = 1 <= int(max_shells) <= _lib.TOPO_MAX_SHELLS      # (the library reports the rest; nothing is sized by it here)
+        info = np.zeros(max(self.B, 0), dtype=_lib.TOPOLOGY_DTYPE)
+        shells = np.zeros((self.B, int(max_shells)) if ok else (0,), dtype=_lib.SHELL_DTYPE)
+        self._chk(self.L.sh_mesh_topology(self.h, ctypes.byref(opt), _ptr(info), _ptr(shells)))
+        return info, shells
+
+    def _face_range(self, b):
+        if not 0 <= int(b) < self.B:
+            raise ValueError("mesh index out of range")
+        return int(self.foff[int(b)]), int(self.foff[int(b) + 1])
+
+    def face_adjacency(self, b):
+        """The resident adjacency of mesh b after topology() -> (F, 3) int32: per slot e the other face on the edge {f[e], f[(e+1)%3]},
+        or _lib.ADJ_BORDER / ADJ_NONMANIFOLD / ADJ_DEGENERATE."""
+        f0, f1 = self._face_range(b)
+        return self.fetch("topo.adj", np.int32, (int(self.foff[-1]), 3))[f0:f1].copy()
+
+    def face_labels(self, b):
+        """The resident shell index of every face of mesh b after topology() -> (F,) int32, -1 for a degenerate face."""
+        f0, f1 = self._face_range(b)
+        return self.fetch("topo.label", np.int32, (int(self.foff[-1]),))[f0:f1].copy()
+
+    def split(self, b, largest_only=False):
+        """`mesh.split(only_watertight=False)` of resident mesh b from the resident labels (topology() first) -> a list of (verts, faces),
+        one per shell in shell order, or the largest shell alone: vertices compacted in first-use order, faces in their order, each
+        ready for upload().  The gather runs on the host."""
+        label = self.face_labels(b)
+        v0, v1 = int(self.voff[int(b)]), int(self.voff[int(b) + 1])
+        f0, f1 = self._face_range(b)
+        verts = self.fetch("verts", np.float32, (int(self.voff[-1]), 3))[v0:v1]
+        faces = self.fetch("faces", np.int32, (int(self.foff[-1]), 3))[f0:f1]
+        n = int(label.max()) + 1 if len(label) else 0
+        ks = list(range(n))
+        if largest_only and n:
+            ks = [int(np.argmax(np.bincount(label[label >= 0], minlength=n)))]      # (argmax: ties to the smaller index)
+        out = []
+        for k in ks:
+            fk = faces[label == k]
+            uniq, first, inv = np.unique(fk.ravel(), return_index=True, return_inverse=True)
+            order = np.argsort(first, kind="stable")
+            rank = np.empty_like(order)
+            rank[order] = np.arange(len(order))
+            out.append((np.ascontiguousarray(verts[uniq[order]]), np.ascontiguousarray(rank[np.ravel(inv)].reshape(-1, 3).astype(np.int32))))
+        return out
+
     # ---- multi-start registration (include/shoulder_hip.h sh_register_multistart) -----------------------------------------------
     def principal_starts(self, points, rolls=8, with_ratios=False):
         """Starting transforms for register_multistart from principal frames -> (B, 2 * rolls, 4, 4).  The mesh frame is shell_centroid
