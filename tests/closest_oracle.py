@@ -5,12 +5,10 @@ closest_pt_tri, so that float64 NumPy gives the bits the host-compiled statement
 device gives (-ffp-contract=off).  Also an independent formulation of the distance (plane projection with an inside test, else the
 nearest of the three edges) and the ctypes side of the host twins."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_twin
 from ray_oracle import cross3, dot3, widen
 
 ARG, STATE, GEOMETRY = -1, -3, -5
@@ -111,14 +109,9 @@ TETRA = (np.array([(0.0, 0.0, 0.0), (4.0, 0.0, 0.0), (0.0, 4.0, 0.0), (0.0, 0.0,
 def build_shim(directory, sanitize=False):
     """tests/hostcheck/closest_check.cpp compiled as the device compiles it (-ffp-contract=off) -> ctypes library; sanitize=True: the
     stand-alone program with -fsanitize=address,undefined instead -> its path (it is run as a program, never loaded)"""
-    src = os.path.join(ROOT, "tests", "hostcheck", "closest_check.cpp")
+    L = host_twin.build_shim("closest", directory, sanitize, std="c++17")
     if sanitize:
-        exe = os.path.join(str(directory), "closest_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libclosest_check.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     vp, i = ctypes.c_void_p, ctypes.c_int
     L.cc_tri.argtypes, L.cc_tri.restype = [vp, vp, vp, vp, vp], ctypes.c_double
     L.cc_key_less.argtypes = [ctypes.c_double, i, ctypes.c_double, i]

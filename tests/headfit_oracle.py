@@ -3,12 +3,10 @@ tests/test_gpu_headfit.py.  The triangles come from oracle/clip.py slice_plane a
 sphere is solved by np.linalg.lstsq on the sqrt(w)-scaled rows [2 q, 1] against |q|^2 -- a route that never forms the moments --
 and the ellipse by np.linalg.eigh on the polygon moments of the oracle ring taken about its own centroid."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_twin
 from oracle import clip
 
 EPS = 2.0 ** -53
@@ -122,9 +120,7 @@ def sum_bound(terms):
 
 def build_shim(directory):
     """tests/hostcheck/headfit_check.cpp compiled as the device compiles it (-ffp-contract=off) -> ctypes library"""
-    so = os.path.join(str(directory), "libheadfit_check.so")
-    subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "tests", "hostcheck", "headfit_check.cpp")])
-    L = ctypes.CDLL(so)
+    L = host_twin.build_shim("headfit", directory)
     L.hf_sphere.argtypes = [ctypes.c_void_p] * 4
     L.hf_ellipse.argtypes = [ctypes.c_void_p] * 4
     return L

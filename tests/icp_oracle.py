@@ -7,13 +7,11 @@ per-point terms are NumPy element-wise expressions, the solves plain Python floa
 ndarray.sum: a second run of the same oracle that differs only in summation order, the yardstick of the tests' bound."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
 import closest_oracle as CO
-from conftest import ROOT
+import host_twin
 from ray_oracle import cross3, dot3, widen
 
 ARG, STATE, GEOMETRY = -1, -3, -5
@@ -350,14 +348,9 @@ BOX_MOVE = rigid((1.0, 2.0, 3.0), 3.0, (0.4, -0.3, 0.2))
 
 # ---- the ctypes side of the host twins (tests/hostcheck/icp_check.cpp) ----------------------------------------------------------
 def build_shim(directory, sanitize=False):
-    src = os.path.join(ROOT, "tests", "hostcheck", "icp_check.cpp")
+    L = host_twin.build_shim("icp", directory, sanitize, std="c++17")
     if sanitize:
-        exe = os.path.join(str(directory), "icp_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libicp_check.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     vp, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     L.ic_precheck.argtypes = [i, vp, i, i, vp, vp, i, i]
     L.ic_jacobi.argtypes, L.ic_jacobi.restype = [vp, vp], None

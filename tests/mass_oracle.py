@@ -6,13 +6,11 @@ The per-face terms are NumPy element-wise expressions, the finish plain Python f
 sh_register_multistart from icp_oracle.register, and the ctypes side of the host twins."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
+import host_twin
 import icp_oracle as IO
-from conftest import ROOT
 from ray_oracle import cross3, dot3, widen
 
 GEOMETRY = -5
@@ -194,14 +192,9 @@ def multistart(verts, faces, points, T0s, coarse, coarse_points, min_pairs, fine
 
 # ---- the ctypes side of the host twins (tests/hostcheck/mass_check.cpp) ----------------------------------------------------------
 def build_shim(directory, sanitize=False):
-    src = os.path.join(ROOT, "tests", "hostcheck", "mass_check.cpp")
+    L = host_twin.build_shim("mass", directory, sanitize, std="c++17")
     if sanitize:
-        exe = os.path.join(str(directory), "mass_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libmass_check.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     vp, i, d = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
     L.mc_mass.argtypes, L.mc_mass.restype = [vp, i, vp, i, vp, vp], None
     L.mc_jacobi.argtypes, L.mc_jacobi.restype = [vp, vp], None

@@ -4,12 +4,10 @@ frame and plane in canal_map_point's order of operations, the three parts of a c
 np.lexsort on (i, cost) -- and the ctypes side of tests/hostcheck/plan_check.cpp.  Every expression is written operation by
 operation as sh_scalar.h plan_* writes it, so that with contraction off the device's numbers are expected bit for bit."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_twin
 
 GEOMETRY, ARG, STATE = -5, -1, -3
 RULE_FIELDS = ("max_overhang", "min_coverage", "min_clearance", "max_eccentricity", "fill_target", "margin",
@@ -154,14 +152,9 @@ def compat_words(compat, Kh):
 def build_shim(directory, sanitize=False):
     """tests/hostcheck/plan_check.cpp compiled as the device compiles it (-ffp-contract=off) -> ctypes library; sanitize=True: the
     stand-alone program with -fsanitize=address,undefined instead -> its path (it is run as a program, never loaded)"""
-    src = os.path.join(ROOT, "tests", "hostcheck", "plan_check.cpp")
+    L = host_twin.build_shim("plan", directory, sanitize)
     if sanitize:
-        exe = os.path.join(str(directory), "plan_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libplan_check.so")
-    subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     d, vp, i = ctypes.c_double, ctypes.c_void_p, ctypes.c_int
     L.pc_ref.argtypes, L.pc_ref.restype = [vp, i, vp, vp, d, i, vp], None
     L.pc_cut_term.argtypes, L.pc_cut_term.restype = [vp, i, i, i, i, i, vp, vp, vp, vp], None

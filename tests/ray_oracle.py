@@ -3,12 +3,10 @@ of a ray with a mesh, ascending by (t, face).  Written operation by operation li
 ray_tri_hit, so that float64 NumPy gives the bits the host-compiled statement gives (tests/hostcheck/ray_check.cpp); against the device
 the tests still ask 1e-6 mm only.  Also the ctypes side of the host twins."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_twin
 
 ARG, STATE = -1, -3
 
@@ -103,14 +101,9 @@ TETRA = (np.array([(0.0, 0.0, 0.0), (4.0, 0.0, 0.0), (0.0, 4.0, 0.0), (0.0, 0.0,
 def build_shim(directory, sanitize=False):
     """tests/hostcheck/ray_check.cpp compiled as the device compiles it (-ffp-contract=off) -> ctypes library; sanitize=True: the
     stand-alone program with -fsanitize=address,undefined instead -> its path (it is run as a program, never loaded)"""
-    src = os.path.join(ROOT, "tests", "hostcheck", "ray_check.cpp")
+    L = host_twin.build_shim("ray", directory, sanitize, std="c++17")
     if sanitize:
-        exe = os.path.join(str(directory), "ray_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libray_check.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     vp, i = ctypes.c_void_p, ctypes.c_int
     L.rc_hit.argtypes = [vp, vp, vp, vp, vp]
     L.rc_hit_plain.argtypes = [vp, vp, vp, vp]

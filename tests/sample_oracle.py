@@ -6,12 +6,10 @@ statement gives (tests/hostcheck/sample_check.cpp, -ffp-contract=off) and the de
 Also the ctypes side of the host twin."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_twin
 from ray_oracle import cross3, dot3, widen
 
 ARG, STATE, CAPACITY, GEOMETRY = -1, -3, -4, -5
@@ -144,14 +142,9 @@ def zero_area_mesh(verts, faces, where):
 
 # ---- the ctypes side of the host twin (tests/hostcheck/sample_check.cpp) -------------------------------------------------------------
 def build_shim(directory, sanitize=False):
-    src = os.path.join(ROOT, "tests", "hostcheck", "sample_check.cpp")
+    L = host_twin.build_shim("sample", directory, sanitize, std="c++17")
     if sanitize:
-        exe = os.path.join(str(directory), "sample_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libsample_check.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     vp, i, d, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_uint64
     L.sc_words.argtypes, L.sc_words.restype = [u64, u64, i, vp], None
     L.sc_unit.argtypes, L.sc_unit.restype = [u64], d

@@ -4,12 +4,12 @@ the covered area -- Sutherland-Hodgman clipping of the ring by the regular N-gon
 method is valid for any simple ring), whose area falls short of the exact one by at most pi rho^2 (1 - sin(2 pi / N) / (2 pi / N))."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
 import headfit_oracle as H
-from conftest import BONES, ROOT
+import host_twin
+from conftest import BONES
 
 NGON = 4096
 
@@ -155,9 +155,7 @@ def humerus_cuts():
 
 def build_shim(directory):
     """tests/hostcheck/seat_check.cpp compiled as the device compiles it (-ffp-contract=off) -> ctypes library"""
-    so = os.path.join(str(directory), "libseat_check.so")
-    subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "tests", "hostcheck", "seat_check.cpp")])
-    L = ctypes.CDLL(so)
+    L = host_twin.build_shim("seat", directory)
     d, vp = ctypes.c_double, ctypes.c_void_p
     L.st_edge.argtypes, L.st_edge.restype = [d] * 5, d
     L.st_seg.argtypes, L.st_seg.restype = [d] * 4 + [vp], d

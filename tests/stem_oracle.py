@@ -3,12 +3,10 @@ infrastructure shared by tests/test_stem_host.py, tests/test_gpu_stem.py and too
 header's definitions -- the profile as a brute-force loop of every ray over ALL faces, without any culling -- closed forms of
 prisms, and the ctypes side of tests/hostcheck/stem_check.cpp."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_twin
 
 GEOMETRY, ARG = -5, -1
 
@@ -185,9 +183,7 @@ def mesh_in_ct(T, v_frame, faces):
 
 def build_shim(directory):
     """tests/hostcheck/stem_check.cpp compiled as the device compiles it (-ffp-contract=off) -> ctypes library"""
-    so = os.path.join(str(directory), "libstem_check.so")
-    subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "tests", "hostcheck", "stem_check.cpp")])
-    L = ctypes.CDLL(so)
+    L = host_twin.build_shim("stem", directory)
     d, vp, i = ctypes.c_double, ctypes.c_void_p, ctypes.c_int
     L.sc_hit.argtypes = [vp, vp, vp, vp]
     L.sc_radius.argtypes, L.sc_radius.restype = [d] * 4, d

@@ -1,20 +1,17 @@
-"""Closest surface points of the resident batch (include/shoulder_hip.h sh_closest_points), the parts that need no GPU: the record
-layout against a C compile of the header, the ordered argument checks, the region rule on numbers worked by hand, the host twins
+"""Closest surface points of the resident batch (include/shoulder_hip.h sh_closest_points), the parts that need no GPU (the record
+layout: test_abi_exports.py): the ordered argument checks, the region rule on numbers worked by hand, the host twins
 (closest_pt_tri, the key order, the walk-and-join of one mesh, host-compiled with -ffp-contract=off through
 tests/hostcheck/closest_check.cpp) against the NumPy statement of tests/closest_oracle.py, and the face-split formula.
 
 Bounds.  Hand-worked numbers are chosen exactly representable: equality.  Twins against the oracle: bytes (integers, and doubles that
 the same operations in the same order produce)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import closest_oracle as O
 import stem_oracle as SO
-from conftest import ROOT
 from shoulder_amd import _lib
 
 
@@ -25,22 +22,6 @@ def shim(tmp_path_factory):
 
 def bits(x):
     return np.float64(x).tobytes()
-
-
-def test_closest_record_layout_matches_header(tmp_path):
-    names = [n for n, _ in _lib.Closest._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %d", sizeof(sh_closest), SH_CLOSEST_MAX);\n'
-                   + "".join('printf(" %%zu", offsetof(sh_closest, %s));\n' % n for n in names) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[0] == ctypes.sizeof(_lib.Closest) == _lib.CLOSEST_DTYPE.itemsize == 48
-    assert got[1] == _lib.CLOSEST_MAX == 1048576
-    assert list(_lib.CLOSEST_DTYPE.names) == names == ["dist", "point", "face", "region", "side", "status"]
-    for k, name in enumerate(names):
-        assert got[2 + k] == _lib.CLOSEST_DTYPE.fields[name][1] == getattr(_lib.Closest, name).offset, name
-    assert got[2:] == [0, 8, 32, 36, 40, 44]
 
 
 def test_entry_point_checks_its_arguments_in_order_without_a_gpu(shim):

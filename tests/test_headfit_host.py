@@ -1,4 +1,4 @@
-"""Head fit of a cut (include/shoulder_hip.h sh_head_fit), the parts that need no GPU: record layout, the two solves the device
+"""Head fit of a cut (include/shoulder_hip.h sh_head_fit), the parts that need no GPU (record layout: test_abi_exports.py): the two solves the device
 runs (sh_scalar.h head_sphere_from_moments / ellipse_from_moments, host-compiled with -ffp-contract=off) against the lstsq / eigh
 oracle of tests/headfit_oracle.py, the degenerate-fit flag, and the arithmetic of implant_head.
 
@@ -6,13 +6,12 @@ Bound for centre, radius, rms and semi-axes against the oracle: 1e-6 mm, the lev
 at (README); the two CPU routes differ by ~3e-13 mm on the fixtures (condition number of the normal matrix 3 200 .. 5 000)."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import headfit_oracle as H
-from conftest import BONES, ROOT
+from conftest import BONES
 from shoulder_amd import _lib
 from shoulder_amd.arthroplasty import implant_from_fit
 from shoulder_amd.stl import load_stl
@@ -23,22 +22,6 @@ MM = 1e-6
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     return H.build_shim(tmp_path_factory.mktemp("headfit_check"))
-
-
-def test_head_fit_record_layout_matches_header(tmp_path):
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(sh_head_fit), offsetof(sh_head_fit, sphere_radius), '
-                   'offsetof(sh_head_fit, center_articular), offsetof(sh_head_fit, cut_major_dir), offsetof(sh_head_fit, sphere_status), '
-                   'offsetof(sh_head_fit, ring_status)); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    dt, R = _lib.HEAD_FIT_DTYPE, _lib.HeadFit
-    assert got[0] == dt.itemsize == ctypes.sizeof(R) == 128
-    for g, name in zip(got[1:], ("sphere_radius", "center_articular", "cut_major_dir", "sphere_status", "ring_status")):
-        assert g == dt.fields[name][1] == getattr(R, name).offset
-    assert [n for n, _ in R._fields_] == list(dt.names)
 
 
 def test_fit_entry_points_check_their_arguments_without_a_gpu():

@@ -1,5 +1,5 @@
-"""Rigid registration onto the resident batch (include/shoulder_hip.h sh_register_points), the parts that need no GPU: the record and
-options layout against a C compile of the header, the ordered argument checks, sym4_jacobi against numpy.linalg.eigh, chol6_solve
+"""Rigid registration onto the resident batch (include/shoulder_hip.h sh_register_points), the parts that need no GPU (the record and
+options layout: test_abi_exports.py): the ordered argument checks, sym4_jacobi against numpy.linalg.eigh, chol6_solve
 against numpy.linalg.solve, the summation tree, and the host twins of one evaluation and of the whole loop (the device source,
 host-compiled with -ffp-contract=off through tests/hostcheck/icp_check.cpp) against the NumPy statement of tests/icp_oracle.py.
 
@@ -8,14 +8,12 @@ stable, so an eigenvalue differs by a modest multiple of eps ||A||; 64 eps ||A||
 4 x 4 is converged to rounding, eigh's own error is a few eps ||A||).  chol6_solve against solve: the forward error of either is
 bounded by a small multiple of cond(A) eps |x|; 64 cond(A) eps max|x| is asserted."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import icp_oracle as O
-from conftest import ROOT
 from shoulder_amd import _lib
 
 EPS = 2.0 ** -52
@@ -28,26 +26,6 @@ def shim(tmp_path_factory):
 
 def ptr(a):
     return a.ctypes.data if a is not None else None
-
-
-def test_registration_record_and_options_layout_match_header(tmp_path):
-    rn, on = [n for n, _ in _lib.Registration._fields_], [n for n, _ in _lib.IcpOptions._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %zu %d %d %d %d", sizeof(sh_registration), '
-                   "sizeof(sh_icp_options), SH_ICP_POINT, SH_ICP_PLANE, SH_ICP_BLOCK, SH_ICP_MAX_ITER);\n"
-                   + "".join('printf(" %%zu", offsetof(sh_registration, %s));\n' % n for n in rn)
-                   + "".join('printf(" %%zu", offsetof(sh_icp_options, %s));\n' % n for n in on) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[0] == ctypes.sizeof(_lib.Registration) == _lib.REGISTRATION_DTYPE.itemsize == 168
-    assert got[1] == ctypes.sizeof(_lib.IcpOptions) == 24
-    assert got[2:6] == [_lib.ICP_POINT, _lib.ICP_PLANE, _lib.ICP_BLOCK, _lib.ICP_MAX_ITER] == [0, 1, 256, 64]
-    assert list(_lib.REGISTRATION_DTYPE.names) == rn == ["T", "rms", "rms_first", "min_pivot", "pairs", "iterations", "converged", "status"]
-    for k, name in enumerate(rn):
-        assert got[6 + k] == _lib.REGISTRATION_DTYPE.fields[name][1] == getattr(_lib.Registration, name).offset, name
-    assert got[6:14] == [0, 128, 136, 144, 152, 156, 160, 164]
-    assert on == ["metric", "max_iter", "reject", "tol"] and got[14:] == [getattr(_lib.IcpOptions, n).offset for n in on] == [0, 4, 8, 16]
 
 
 def test_entry_point_checks_its_arguments_in_order_without_a_gpu(shim):

@@ -1,11 +1,10 @@
-"""Mass properties of the resident batch (include/shoulder_hip.h sh_mass_properties), the parts that need no GPU: the record layout
-against a C compile of the header, the argument check, sym3_jacobi against numpy.linalg.eigh, the host twin of the kernels (the device
+"""Mass properties of the resident batch (include/shoulder_hip.h sh_mass_properties), the parts that need no GPU (the record layout:
+test_abi_exports.py): the argument check, sym3_jacobi against numpy.linalg.eigh, the host twin of the kernels (the device
 source, host-compiled with -ffp-contract=off through tests/hostcheck/mass_check.cpp) against the NumPy statement of
 tests/mass_oracle.py, and the closed forms of a box.
 
 Bounds.  Twin against the oracle: bytes (the same + - x / sqrt in the same order).  sym3_jacobi against eigh: 64 eps ||A||_F, as for
 sym4_jacobi in test_icp_host.py.  The box: derived in test_box_closed_forms."""
-import ctypes
 import os
 import subprocess
 
@@ -14,7 +13,7 @@ import pytest
 
 import icp_oracle as IO
 import mass_oracle as O
-from conftest import BONES, ROOT
+from conftest import BONES
 from shoulder_amd import _lib
 from shoulder_amd.stl import load_stl
 
@@ -39,23 +38,8 @@ def host_mass(shim, v, f):
     return rec[0], rows[:(len(f) + 255) // 256]
 
 
-def test_mass_record_layout_matches_header(tmp_path):
-    names = [n for n, _ in _lib.Mass._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %d %d", sizeof(sh_mass), SH_MASS_BLOCK, SH_MS_MAX_STARTS);\n'
-                   + "".join('printf(" %%zu", offsetof(sh_mass, %s));\n' % n for n in names) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[0] == ctypes.sizeof(_lib.Mass) == _lib.MASS_DTYPE.itemsize == 400
-    assert got[1:3] == [_lib.MASS_BLOCK, _lib.MS_MAX_STARTS] == [256, 64]
-    assert list(_lib.MASS_DTYPE.names) == names
-    for k, name in enumerate(names):
-        assert got[3 + k] == _lib.MASS_DTYPE.fields[name][1] == getattr(_lib.Mass, name).offset, name
-    assert "sh_mass_properties" in _lib.EXPORTS and "sh_register_multistart" in _lib.EXPORTS
-
-
 def test_entry_point_checks_its_arguments_without_a_gpu(shim):
+    assert "sh_mass_properties" in _lib.EXPORTS and "sh_register_multistart" in _lib.EXPORTS
     L = _lib.load()
     assert L.sh_mass_properties(None, None) == IO.ARG                                 # (no context)
     assert shim.mc_precheck_mass(1, 1, 0) == 0 and shim.mc_precheck_mass(0, 1, 0) == IO.ARG

@@ -1,48 +1,23 @@
-"""Rays against the resident batch (include/shoulder_hip.h sh_ray_cast / sh_anp_axis_hits), the parts that need no GPU: the record
-layout against a C compile of the header, the argument checks, the rule on numbers worked by hand, and the host twins (the
+"""Rays against the resident batch (include/shoulder_hip.h sh_ray_cast / sh_anp_axis_hits), the parts that need no GPU (the record
+layout: test_abi_exports.py): the argument checks, the rule on numbers worked by hand, and the host twins (the
 side-returning statement and the segment sort, host-compiled with -ffp-contract=off through tests/hostcheck/ray_check.cpp) against the
 NumPy statement of tests/ray_oracle.py.
 
 Bounds.  Hand-worked numbers are chosen exactly representable: equality.  Twins against the oracle: bytes (integers, and doubles that
 the same operations in the same order produce)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ray_oracle as O
 import stem_oracle as SO
-from conftest import ROOT
 from shoulder_amd import _lib
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
     return O.build_shim(tmp_path_factory.mktemp("ray_check"))
-
-
-def test_ray_record_layouts_match_header(tmp_path):
-    rf, hf = [n for n, _ in _lib.Ray._fields_], [n for n, _ in _lib.RayHit._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %zu %d %d", sizeof(sh_ray), '
-                   'sizeof(sh_ray_hit), SH_RAY_MAX, SH_RAY_MAX_HITS);\n'
-                   + "".join('printf(" %%zu", offsetof(sh_ray, %s));\n' % n for n in rf)
-                   + "".join('printf(" %%zu", offsetof(sh_ray_hit, %s));\n' % n for n in hf) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[0] == ctypes.sizeof(_lib.Ray) == _lib.RAY_DTYPE.itemsize == 48
-    assert got[1] == ctypes.sizeof(_lib.RayHit) == _lib.RAY_HIT_DTYPE.itemsize == 40
-    assert got[2] == _lib.RAY_MAX == 65536 and got[3] == _lib.RAY_MAX_HITS == 1024
-    k = 4
-    for names, ct, dt in ((rf, _lib.Ray, _lib.RAY_DTYPE), (hf, _lib.RayHit, _lib.RAY_HIT_DTYPE)):
-        assert list(dt.names) == names
-        for name in names:
-            assert got[k] == dt.fields[name][1] == getattr(ct, name).offset, name
-            k += 1
-    assert [_lib.RAY_HIT_DTYPE.fields[n][1] for n in hf] == [0, 8, 32, 36]
 
 
 def test_ray_entry_points_check_their_arguments_without_a_gpu(shim):

@@ -1,46 +1,23 @@
-"""Batched head resection (include/shoulder_hip.h sh_resect_*), the parts that need no GPU: record layout, the plane
+"""Batched head resection (include/shoulder_hip.h sh_resect_*), the parts that need no GPU (record layout: test_abi_exports.py): the plane
 bookkeeping the device runs (sh_scalar.h resect_plane_from_offsets) against oracle/osteotomy.py, argument checks."""
 import ctypes
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+import host_twin
+from conftest import GOLDEN
 from oracle.osteotomy import OracleOsteotomy
 from shoulder_amd import _lib
 
 FIELDS = [n for n, _ in _lib.CutOffset._fields_]
 
 
-def test_resection_record_layout_matches_header(tmp_path):
-    """sizeof / offsetof from a gcc-compiled probe of the public header equal the NumPy and ctypes mirrors."""
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(sh_resection), sizeof(sh_cut_offset), '
-                   'offsetof(sh_resection, head_volume), offsetof(sh_resection, cut_centroid), offsetof(sh_resection, status), '
-                   'offsetof(sh_cut_offset, anterior_mm)); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    dt, R, C = _lib.RESECTION_DTYPE, _lib.Resection, _lib.CutOffset
-    assert got[0] == dt.itemsize == ctypes.sizeof(R) == 136
-    assert got[1] == _lib.CUT_OFFSET_DTYPE.itemsize == ctypes.sizeof(C) == 56
-    assert got[2] == dt.fields["head_volume"][1] == R.head_volume.offset
-    assert got[3] == dt.fields["cut_centroid"][1] == R.cut_centroid.offset
-    assert got[4] == dt.fields["status"][1] == R.status.offset
-    assert got[5] == _lib.CUT_OFFSET_DTYPE.fields["anterior_mm"][1] == C.anterior_mm.offset
-    assert [n for n, _ in R._fields_] == list(dt.names)
-
-
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = tmp_path_factory.mktemp("resect_check") / "libresect_check.so"
-    subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-o", str(so),
-                           os.path.join(ROOT, "tests", "hostcheck", "resect_check.cpp")])
-    L = ctypes.CDLL(str(so))
+    L = host_twin.build_shim("resect", tmp_path_factory.mktemp("resect_check"))
     L.rc_plane_from_offsets.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 3
     return L
 

@@ -1,5 +1,5 @@
-"""Surface samples of the resident batch (include/shoulder_hip.h sh_sample_surface), the parts that need no GPU: the record layouts
-against a C compile of the header, the known answers of the word generator, the host twin of the kernels (the device source,
+"""Surface samples of the resident batch (include/shoulder_hip.h sh_sample_surface), the parts that need no GPU (the record layouts:
+test_abi_exports.py): the known answers of the word generator, the host twin of the kernels (the device source,
 host-compiled with -ffp-contract=off through tests/hostcheck/sample_check.cpp) against the NumPy statement of tests/sample_oracle.py,
 the argument checks, the buffer plan, the round rule of the thinning, and the quality of what the definition draws.
 
@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import sample_oracle as O
-from conftest import BONES, ROOT
+from conftest import BONES
 from mass_oracle import int_box
 from ray_oracle import widen
 from shoulder_amd import _lib
@@ -44,33 +44,6 @@ def meshes():
 def drawn(meshes):
     """the oracle's 4 096 samples of every fixture with seed 7, drawn once"""
     return {n: O.sample(v, f, 4096, 7) for n, (v, f) in meshes.items()}
-
-
-def test_record_layouts_match_header(tmp_path):
-    structs = (("sh_sample", _lib.Sample, _lib.SAMPLE_DTYPE, 48), ("sh_sample_info", _lib.SampleInfo, _lib.SAMPLE_INFO_DTYPE, 24),
-               ("sh_sample_options", _lib.SampleOptions, None, 16))
-    lines = ['printf("%d %d %d %d", SH_SAMPLE_MAX, SH_SAMPLE_THIN_MAX, SH_SAMPLE_BLOCK, SH_THIN_MAX_ROUNDS);\n']
-    for cname, cls, _, _ in structs:
-        lines.append('printf(" %%zu", sizeof(%s));\n' % cname)
-        lines += ['printf(" %%zu", offsetof(%s, %s));\n' % (cname, n) for n, _ in cls._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) {\n' + "".join(lines) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[:4] == [_lib.SAMPLE_MAX, _lib.SAMPLE_THIN_MAX, _lib.SAMPLE_BLOCK, _lib.THIN_MAX_ROUNDS] == [1048576, 65536, 256, 32]
-    k = 4
-    for cname, cls, dtype, size in structs:
-        assert got[k] == ctypes.sizeof(cls) == size, cname
-        names = [n for n, _ in cls._fields_]
-        if dtype is not None:
-            assert dtype.itemsize == size and list(dtype.names) == names
-        for i, n in enumerate(names):
-            assert got[k + 1 + i] == getattr(cls, n).offset, (cname, n)
-            if dtype is not None:
-                assert dtype.fields[n][1] == got[k + 1 + i], (cname, n)
-        k += 1 + len(names)
-    assert "sh_sample_surface" in _lib.EXPORTS
 
 
 def test_known_answers_of_the_word_generator(shim):
@@ -163,6 +136,7 @@ def test_arguments_are_checked_in_order(shim):
     L = _lib.load()
     opt, seeds = _lib.SampleOptions(0.0, 32, 0), np.zeros(1, np.uint64)
     assert L.sh_sample_surface(None, 10, seeds.ctypes.data, ctypes.byref(opt), None, None) == O.ARG      # (no context)
+    assert "sh_sample_surface" in _lib.EXPORTS
 
 
 def test_buffer_plan(shim):

@@ -1,4 +1,4 @@
-"""Seats of implant heads on a cut (include/shoulder_hip.h sh_seat), the parts that need no GPU: record layout, argument checks, the
+"""Seats of implant heads on a cut (include/shoulder_hip.h sh_seat), the parts that need no GPU (record layout: test_abi_exports.py): argument checks, the
 seat arithmetic the device runs (sh_scalar.h seat_edge_term / seat_seg_dist2 / seat_winding_term / seat_surface_rms, host-compiled
 with -ffp-contract=off through tests/hostcheck/seat_check.cpp) against closed forms, the NumPy statement and the N-gon clip of
 tests/seat_oracle.py, and the arithmetic of best_seat.
@@ -6,15 +6,12 @@ tests/seat_oracle.py, and the arithmetic of best_seat.
 Bounds.  Closed forms on the square: 1e-12 mm^2.  Covered area against the inscribed-N-gon clip: the clip's own deficit bound
 pi rho^2 (1 - sin(2 pi / N) / (2 pi / N)), N = 4096.  surface_rms: 1e-6 mm, the project's landmark bound (tests/test_headfit_host.py)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import headfit_oracle as H
 import seat_oracle as S
-from conftest import ROOT
 from shoulder_amd import _lib
 from shoulder_amd.arthroplasty import best_seat
 
@@ -35,26 +32,6 @@ def fit_shim(tmp_path_factory):
 @pytest.fixture(scope="module")
 def humerus_cuts():
     return S.humerus_cuts()
-
-
-def test_seat_record_layout_matches_header(tmp_path):
-    names = ("seat_center", "covered_area", "coverage", "overhang_area", "uncovered_area", "rim_min", "rim_max", "max_overhang", "max_uncovered",
-             "overhang_dir", "uncovered_dir", "implant_center", "cor_shift", "cor_shift_articular", "surface_rms", "center_inside", "status")
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %zu %zu", sizeof(sh_seat), '
-                   'sizeof(sh_implant_head), offsetof(sh_implant_head, thickness));\n'
-                   + "".join('printf(" %%zu", offsetof(sh_seat, %s));\n' % n for n in names)
-                   + 'printf(" %d %d %d\\n", SH_SEAT_CUT_CENTROID, SH_SEAT_SPHERE_AXIS, SH_SEAT_MAX_HEADS); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    dt, R = _lib.SEAT_DTYPE, _lib.Seat
-    assert got[0] == dt.itemsize == ctypes.sizeof(R) == 232
-    assert got[1] == _lib.IMPLANT_HEAD_DTYPE.itemsize == ctypes.sizeof(_lib.ImplantHead) == 16 and got[2] == _lib.ImplantHead.thickness.offset == 8
-    for g, name in zip(got[3:], names):
-        assert g == dt.fields[name][1] == getattr(R, name).offset, name
-    assert dt.fields["base_radius"][1] == 0 and [n for n, _ in R._fields_] == list(dt.names)
-    assert got[-3:] == [_lib.SEAT_CUT_CENTROID, _lib.SEAT_SPHERE_AXIS, _lib.SEAT_MAX_HEADS]
 
 
 def test_seat_entry_points_check_their_arguments_without_a_gpu():

@@ -1,18 +1,17 @@
-"""Canal profiles and stems below a cut (include/shoulder_hip.h sh_canal_profile / sh_resect_stems), the parts that need no GPU: record
-layouts, argument checks, the arithmetic the device runs (sh_scalar.h canal_* / stem_*, host-compiled with -ffp-contract=off through
+"""Canal profiles and stems below a cut (include/shoulder_hip.h sh_canal_profile / sh_resect_stems), the parts that need no GPU (record
+layouts: test_abi_exports.py): argument checks, the arithmetic the device runs (sh_scalar.h canal_* / stem_*, host-compiled with -ffp-contract=off through
 tests/hostcheck/stem_check.cpp) against closed forms and the NumPy statement of tests/stem_oracle.py, the culling of k_canal_rays
 against the un-culled loop, and the arithmetic of best_stem.
 
 Bounds.  Closed forms: 1e-12 mm.  Host source against the NumPy brute force on humerus_left: 1e-6 mm on the rays the oracle keeps."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import stem_oracle as O
-from conftest import BONES, GOLDEN, ROOT
+from conftest import BONES, GOLDEN
 from shoulder_amd import _lib
 from shoulder_amd.arthroplasty import best_stem
 
@@ -44,29 +43,6 @@ def axis_grid(half, dz=4.0):
     """levels of spacing dz with |z| <= half"""
     n = int(np.floor(half / dz))
     return n * dz, dz, 2 * n + 1
-
-
-def test_stem_record_layouts_match_header(tmp_path):
-    lv = ("r_min", "r_max", "r_mean", "area", "centroid", "extent_x", "extent_y", "wall_min", "a_min", "a_max", "n_hit", "status")
-    sf = ("entry", "z_entry", "min_clearance", "depth", "direction", "scale_max", "fill_mean", "fill_max", "fill_max_depth", "angle_index",
-          "n_samples", "n_breach", "n_open", "fits", "status")
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %d", sizeof(sh_canal_grid), '
-                   'offsetof(sh_canal_grid, L), offsetof(sh_canal_grid, A), sizeof(sh_canal_level), sizeof(sh_stem), offsetof(sh_stem, r_tip), sizeof(sh_stem_fit), SH_STEM_MAX);\n'
-                   + "".join('printf(" %%zu", offsetof(sh_canal_level, %s));\n' % n for n in lv)
-                   + "".join('printf(" %%zu", offsetof(sh_stem_fit, %s));\n' % n for n in sf) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[0] == ctypes.sizeof(_lib.CanalGrid) == 24 and got[1] == _lib.CanalGrid.L.offset == 16 and got[2] == _lib.CanalGrid.A.offset == 20
-    assert got[3] == _lib.CANAL_LEVEL_DTYPE.itemsize == ctypes.sizeof(_lib.CanalLevel) == 104
-    assert got[4] == _lib.STEM_DTYPE.itemsize == ctypes.sizeof(_lib.Stem) == 24 and got[5] == _lib.Stem.r_tip.offset == 16
-    assert got[6] == _lib.STEM_FIT_DTYPE.itemsize == ctypes.sizeof(_lib.StemFit) == 128 and got[7] == _lib.STEM_MAX == 64
-    for g, name in zip(got[8:8 + len(lv)], lv):
-        assert g == _lib.CANAL_LEVEL_DTYPE.fields[name][1] == getattr(_lib.CanalLevel, name).offset, name
-    for g, name in zip(got[8 + len(lv):], sf):
-        assert g == _lib.STEM_FIT_DTYPE.fields[name][1] == getattr(_lib.StemFit, name).offset, name
-    assert [n for n, _ in _lib.CanalLevel._fields_] == list(_lib.CANAL_LEVEL_DTYPE.names) and [n for n, _ in _lib.StemFit._fields_] == list(_lib.STEM_FIT_DTYPE.names)
 
 
 def test_stem_entry_points_check_their_arguments_without_a_gpu():

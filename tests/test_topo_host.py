@@ -1,5 +1,5 @@
-"""Mesh topology of the resident batch (include/shoulder_hip.h sh_mesh_topology), the parts that need no GPU: the record layouts against
-a C compile of the header, the NumPy statement of tests/topo_oracle.py against the figures a CPU run of the rule gave (conditions on
+"""Mesh topology of the resident batch (include/shoulder_hip.h sh_mesh_topology), the parts that need no GPU (the record layouts:
+test_abi_exports.py): the NumPy statement of tests/topo_oracle.py against the figures a CPU run of the rule gave (conditions on
 the oracle), the host twin of the kernels (the device source's scalar rules, host-compiled through tests/hostcheck/topo_check.cpp)
 against the oracle as bytes, the argument checks and the buffer plan.
 
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import topo_oracle as O
-from conftest import BONES, ROOT
+from conftest import BONES
 from mass_oracle import int_box
 from shoulder_amd import _lib
 from shoulder_amd.stl import load_stl
@@ -47,33 +47,6 @@ def oracle(table, meshes):
     out = {name: O.topology(*mesh) for name, (mesh, _) in table.items()}
     out.update({name: O.topology(*mesh) for name, mesh in O.further(meshes).items()})
     return out
-
-
-def test_record_layouts_match_header(tmp_path):
-    structs = (("sh_topology", _lib.Topology, _lib.TOPOLOGY_DTYPE, 64), ("sh_shell", _lib.Shell, _lib.SHELL_DTYPE, 48), ("sh_topology_options", _lib.TopologyOptions, None, 12))
-    lines = ['printf("%d %d %d %d %d %d %d", SH_ADJ_BORDER, SH_ADJ_NONMANIFOLD, SH_ADJ_DEGENERATE, SH_TOPO_MAX_SHELLS, SH_TOPO_MAX_ROUNDS, SH_TOPO_WATERTIGHT, SH_TOPO_CONSISTENT);\n']
-    for cname, cls, _, _ in structs:
-        lines.append('printf(" %%zu", sizeof(%s));\n' % cname)
-        lines += ['printf(" %%zu", offsetof(%s, %s));\n' % (cname, n) for n, _ in cls._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) {\n' + "".join(lines) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[:7] == [_lib.ADJ_BORDER, _lib.ADJ_NONMANIFOLD, _lib.ADJ_DEGENERATE, _lib.TOPO_MAX_SHELLS, _lib.TOPO_MAX_ROUNDS, _lib.TOPO_WATERTIGHT, _lib.TOPO_CONSISTENT]
-    assert got[:7] == [-1, -2, -3, 65536, 32, 1, 2]
-    k = 7
-    for cname, cls, dtype, size in structs:
-        assert got[k] == ctypes.sizeof(cls) == size, cname
-        names = [n for n, _ in cls._fields_]
-        if dtype is not None:
-            assert dtype.itemsize == size and list(dtype.names) == names
-        for i, n in enumerate(names):
-            assert got[k + 1 + i] == getattr(cls, n).offset, (cname, n)
-            if dtype is not None:
-                assert dtype.fields[n][1] == got[k + 1 + i], (cname, n)
-        k += 1 + len(names)
-    assert "sh_mesh_topology" in _lib.EXPORTS and _lib.TOPOLOGY_OPTIONS is _lib.TopologyOptions
 
 
 def test_the_oracle_shows_the_figures_of_the_table(table, oracle):
@@ -172,6 +145,7 @@ def test_arguments_are_checked_in_order(shim):
     L = _lib.load()
     opt = _lib.TopologyOptions(64, 32, 0)
     assert L.sh_mesh_topology(None, ctypes.byref(opt), None, None) == O.ARG      # (no context)
+    assert "sh_mesh_topology" in _lib.EXPORTS and _lib.TOPOLOGY_OPTIONS is _lib.TopologyOptions
 
 
 def test_buffer_plan(shim):

@@ -1,5 +1,5 @@
-"""Generalized winding numbers of the resident batch (include/shoulder_hip.h sh_winding_numbers), the parts that need no GPU: the
-record layout against a C compile of the header, the ordered argument checks, the solid angle of the host-compiled statement
+"""Generalized winding numbers of the resident batch (include/shoulder_hip.h sh_winding_numbers), the parts that need no GPU (the
+record layout: test_abi_exports.py): the ordered argument checks, the solid angle of the host-compiled statement
 (-ffp-contract=off, tests/hostcheck/winding_check.cpp) against the NumPy statement of tests/winding_oracle.py, hand-worked values on the
 cube of edge 2, the walk-and-join twin with any number of splits, the split formula, and the stand-alone sanitizer build of the twin.
 
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import winding_oracle as O
-from conftest import BONES, ROOT
+from conftest import BONES
 from shoulder_amd import _lib
 from shoulder_amd.stl import load_stl
 
@@ -36,23 +36,8 @@ def bits(x):
     return np.float64(x).tobytes()
 
 
-def test_winding_record_layout_matches_header(tmp_path):
-    names = [n for n, _ in _lib.Winding._fields_]
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "shoulder_hip.h"\nint main(void) { printf("%zu %d %d", sizeof(sh_winding), SH_WINDING_MAX, SH_WIND_BLOCK);\n'
-                   + "".join('printf(" %%zu", offsetof(sh_winding, %s));\n' % n for n in names) + 'printf("\\n"); return 0; }\n')
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(x) for x in subprocess.check_output([str(exe)], text=True).split()]
-    assert got[0] == ctypes.sizeof(_lib.Winding) == _lib.WINDING_DTYPE.itemsize == 16
-    assert got[1] == _lib.WINDING_MAX == 1048576 and got[2] == _lib.WIND_BLOCK == O.BLOCK == 2048
-    assert list(_lib.WINDING_DTYPE.names) == names == ["winding", "inside", "status"]
-    for k, name in enumerate(names):
-        assert got[3 + k] == _lib.WINDING_DTYPE.fields[name][1] == getattr(_lib.Winding, name).offset, name
-    assert got[3:] == [0, 8, 12]
-
-
 def test_entry_point_checks_its_arguments_in_order_without_a_gpu(shim):
+    assert _lib.WIND_BLOCK == O.BLOCK == 2048
     L = _lib.load()
     pts = np.zeros((4, 3))
     assert L.sh_winding_numbers(None, ctypes.c_void_p(pts.ctypes.data), 4, 0, None) == O.ARG      # (no context)

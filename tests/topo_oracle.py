@@ -5,14 +5,12 @@ computed a second way, with scipy.sparse.csgraph.connected_components, and the t
 box corners, which are minima and maxima under the order of the float32 in which -0 < +0.  Also the test meshes and the ctypes side of
 the host twin."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 
-from conftest import ROOT
+import host_twin
 
 ARG, STATE, CAPACITY = -1, -3, -4
 BORDER, NONMANIFOLD, DEGENERATE = -1, -2, -3
@@ -277,14 +275,9 @@ def tetrahedron():
 
 # ---- the ctypes side of the host twin (tests/hostcheck/topo_check.cpp) ----------------------------------------------------------------
 def build_shim(directory, sanitize=False):
-    src = os.path.join(ROOT, "tests", "hostcheck", "topo_check.cpp")
+    L = host_twin.build_shim("topo", directory, sanitize, std="c++17")
     if sanitize:
-        exe = os.path.join(str(directory), "topo_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libtopo_check.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     vp, i = ctypes.c_void_p, ctypes.c_int
     L.tc_topology.argtypes, L.tc_topology.restype = [vp, i, vp, i, i, i, vp, vp, vp, vp, vp, vp], None
     L.tc_precheck.argtypes = [i, i, i, i, i, i, i, vp, i]

@@ -10,12 +10,10 @@ so that num and den are the bits the host-compiled statement gives (tests/hostch
 each math library's own: omega, and with it the sum, is compared within a bound, `bound(F, A)`, never as bytes.  Also returns
 A = sum |omega_f| / 4 pi per point, which that bound needs, and the ctypes side of the host twins."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+import host_twin
 from ray_oracle import cross3, dot3, widen
 
 ARG, STATE, GEOMETRY = -1, -3, -5
@@ -122,14 +120,9 @@ def cube(kind="closed"):
 def build_shim(directory, sanitize=False):
     """tests/hostcheck/winding_check.cpp compiled as the device compiles it (-ffp-contract=off) -> ctypes library; sanitize=True: the
     stand-alone program with -fsanitize=address,undefined instead -> its path (it is run as a program, never loaded)"""
-    src = os.path.join(ROOT, "tests", "hostcheck", "winding_check.cpp")
+    L = host_twin.build_shim("winding", directory, sanitize, std="c++17")
     if sanitize:
-        exe = os.path.join(str(directory), "winding_check_san")
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, src])
-        return exe
-    so = os.path.join(str(directory), "libwinding_check.so")
-    subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    L = ctypes.CDLL(so)
+        return L
     vp, i = ctypes.c_void_p, ctypes.c_int
     L.wc_solid.argtypes, L.wc_solid.restype = [vp, vp, vp, vp], ctypes.c_double
     L.wc_mesh.argtypes, L.wc_mesh.restype = [vp, vp, i, vp, i, i, vp], None
