@@ -27,7 +27,7 @@ static int alloc_hulld(sh_ctx* c) {
   if (c->skip_gen != c->batch_gen) {      // a new batch: the device hull takes every humerus again
     HIPCHK(c, hipMemsetAsync(c->bufs["hulld.skip"].p, 0, (size_t)B * 4, c->stream));
     c->skip_gen = c->batch_gen;
-    c->skip_nfmax = 0;
+    c->batch.skip_list_cleared();
   }
   return SH_OK;
 }
@@ -314,7 +314,7 @@ int sh::run_device_hull(sh_ctx* c, int B, int* nfmax) {
          h.hv, h.normals, h.edges, h.nv, h.nf, h.ne,
          buf<int>(c, "hulld.fail"), buf<int>(c, "hulld.rounds"), (const int*)buf<int>(c, "hulld.skip"), c->hcap);
   LAUNCH(c, "k_hull_flag", k_hull_flag, dim3((B + 63) / 64), dim3(64), buf<int>(c, "hulld.fail"), buf<int>(c, "err"), B);
-  *nfmax = std::max((int)HD_SLOTS, c->skip_nfmax);      // (the face counts stay on the device: the candidate kernel's tiles beyond a hull's faces return at once;
+  *nfmax = std::max((int)HD_SLOTS, c->batch.skip_nfmax());      // (the face counts stay on the device: the candidate kernel's tiles beyond a hull's faces return at once;
                                                        //  a humerus kept on the host hull may have more faces than the device hull has slots)
   return SH_OK;
 }

@@ -16,7 +16,9 @@
 // steps of a UNet pass: kernel, grid, tensors and work tickets of every launch; the ticket and weight-packing tables), sh_arthro.h
 // (the arthroplasty chain: its argument checks and which refusal comes first, the pass plan and the bytes of every resect.* / canal.* /
 // stem.* / plan.* buffer, and ArthroState, the one record of what is valid against what), sh_query.h (the queries of the resident batch:
-// rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology -- their argument checks, plans and the bytes of their buffers).
+// rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology -- their argument checks, plans and the bytes of their buffers),
+// sh_run.h (the run: BatchState, the one record of what is known about the resident batch -- tier vouch, frame, capacities, OBB tier, hulls
+// from the host; PreparedKey, the caller's half of the prepared-hull record; the refusals of sh_submit in their order and its plan).
 #pragma once
 #include "../../include/shoulder_hip.h"
 
@@ -46,6 +48,7 @@
 #include "sh_hullcap.h"
 #include "sh_ingest.h"
 #include "sh_query.h"      // (and sh_arthro.h below it)
+#include "sh_run.h"
 #include "sh_unet_plan.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -82,7 +85,6 @@ struct sh_ctx {
   typedef sh::UnetLayer ULayer;
   sh::UnetLayers ulayers;
   size_t unet_floats = 0;
-  bool obb_injected = false;
   void* comm = nullptr;                      // sh_comm_init_all: this context's RCCL communicator (comm.hip), its rank and the group's size
   int comm_rank = -1, comm_n = 0;
   // sh_set_keep_products: every plane's resampled contour and polar rows leave k_resample_polar (k_slices.h, RsWant); off: the rows
@@ -97,25 +99,17 @@ struct sh_ctx {
   // (redo_given_up); `hulld.skip[b]` then keeps the device hull off it for as long as the batch stays resident (skip_gen == batch_gen).
   int hull_mode = 1;
   unsigned long long skip_gen = ~0ull;
-  int skip_nfmax = 0;                      // most hull faces among the humeri of this batch that are on the host hull (hulld.skip)
-  // overflow pools of the slice layer (k_ovf.h): capacities in segments / ring points / bytes; grown by sh_collect on demand
-  unsigned long long ovf_seg_cap = 1ull << 18, ovf_ring_cap = 1ull << 18, ovf_work_cap = 32ull << 20;
-  // a run of the resident batch that planned no overflow plane in any set (no ring-point or segment demand at collect: SH_CTR_RING_NEED, SH_CTR_SEG_NEED) lets later runs of the SAME batch
-  // and parameters skip the overflow tier's launches (they would all return at once: ~17 launches, ~60 us per step)
-  unsigned long long ovf_none_gen = ~0ull;
+  // What is known about the resident batch (sh_run.h BatchState: named events and queries): whether a run vouched that the overflow
+  // tier of the slice layer (k_ovf.h) is idle for it, whether it has a frame, the capacities a run's demands are measured against and
+  // sh_collect grows (pools, end sections, the k_obb_candidates tier), whether its hulls come from the host, the faces of redone hulls
+  sh::BatchState batch;
   // sh_set_open_contours (k_open.h): SH_OPEN_ERROR / SH_OPEN_BRIDGE and the largest gap bridged (mm); open_stats_run: the mode of the
   // last sh_submit ("open.stats" is cleared, and counts, only in bridge mode)
   int open_mode = SH_OPEN_ERROR;
   double open_gap = SH_OPEN_GAP_DEFAULT;
   int open_stats_run = SH_OPEN_ERROR;
-  int end_cap = SH_ENDCAP;                   // points per end section "obb.endpts" holds (grown by sh_collect like the pools)
-  unsigned long long obb_gen = ~0ull;        // the batch generation the three fields below belong to
   sh::HullCap hcap = {SH_HV, SH_HF, SH_HE};      // per-humerus capacity (= stride) of the hull record and the per-face obb.* arrays; a batch with a larger
                                              // hull grows it (grow_hull_records) -- every kernel takes the strides as an argument
-  int obb_sil_need = 0;                      // the longest silhouette (edges) a direction of the resident batch had when it overflowed a tier of
-                                             // k_obb_candidates: later runs take the tier that holds it (reset with the batch)
-  bool obb_nf_over = false;                  // a device-hull run met a hull with more faces than its candidates tier masks: the next run takes the workspace tier
-  bool hull_force_host = false;              // the resident batch has a hull above the device hull's record: its hulls come from the host (reset with the batch)
   std::vector<float> h_verts;                // host copy of the vertices (hull stage)
   bool h_verts_valid = false;
   // device-generated batches: the hull's points come back through the prefilter (k_hullpre.h) into pinned memory
@@ -154,12 +148,12 @@ struct sh_ctx {
   HullStage hstage[2];                       // pinned host staging, double buffered
   int hslot = 0;                             // slot the next hull goes to
   // Overlap (sh_set_overlap): while the device works on run k, a background thread computes the hulls run k+1 will
-  // need (same resident batch -- invalidated by any upload) into the other pinned slot.
+  // need (same resident batch -- invalidated by any upload) into the other pinned slot.  `key` is the caller's, the rest the thread's
+  // results (sh_run.h PreparedKey states the threading rule).
   struct Prepared {
-    std::thread th; bool active = false; int slot = 0, B = 0, rc = SH_OK, bad_mesh = -1; unsigned long long gen = 0;
-    double d2h_ms = 0, hull_ms = 0; std::string err;
+    std::thread th; sh::PreparedKey key;
+    int rc = SH_OK, bad_mesh = -1; double d2h_ms = 0, hull_ms = 0; std::string err;
     bool uploaded = false;      // the hull records are already in the device buffers (copied by the background thread)
-    bool staged = false;        // the thread works for the STAGED batch (gen = the generation the batch gets at sh_commit_staged)
   } prep;
   hipEvent_t obb_done_ev = nullptr;      // recorded after the last kernel of a run that reads the hull.* device buffers
   // sh_submit / sh_collect: up to two runs in flight (the second one is enqueued while the first still executes)

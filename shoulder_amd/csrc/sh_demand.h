@@ -28,7 +28,7 @@ struct StatusBlock {
   SH_HD int* gave_up() const { return (int*)(base + words_off(B) + SH_NCTR * 8); }
 };
 
-// what the demand words are measured against, and what a rerun raises (sh_ctx: ovf_*_cap, end_cap, obb_sil_need, obb_nf_over)
+// what the demand words are measured against, and what a rerun raises (held by sh_run.h BatchState)
 struct DemandCaps { unsigned long long seg, ring, work; int end; int sil_need; bool nf_over; };
 // why the records of a run are void and the batch runs again: with the overflow tier on | on the k_obb_candidates tier that holds the
 // silhouette / the faces | with larger pools / end sections | with its hulls from the host (redo_given_up: a hull above the device hull's record)

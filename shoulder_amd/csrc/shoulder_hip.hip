@@ -72,9 +72,9 @@ static void drain_timers(sh_ctx* c) {
 }
 
 static int join_prepared(sh_ctx* c) {
-  if (!c->prep.active) return SH_OK;
+  if (!c->prep.key.active) return SH_OK;
   if (c->prep.th.joinable()) c->prep.th.join();
-  c->prep.active = false;
+  c->prep.key.joined();
   if (c->timing) {
     KTimer& h = c->timers["host.hull"]; h.ms += c->prep.hull_ms; h.n += 1;
     if (c->prep.d2h_ms > 0) { KTimer& a = c->timers["host.verts_d2h"]; a.ms += c->prep.d2h_ms; a.n += 1; }
@@ -85,7 +85,7 @@ static int join_prepared(sh_ctx* c) {
 static void discard_staged(sh_ctx* c) {
   sh_ctx::StageSide& S = c->stg;
   if (!S.active) return;
-  if (c->prep.staged) { (void)join_prepared(c); c->prep.gen = ~0ull; c->prep.staged = false; }
+  if (c->prep.key.staged) { (void)join_prepared(c); c->prep.key.staged_dropped(); }
   (void)hipEventSynchronize(S.ready_ev);      // nothing reads the pinned staging or writes the staging side any more
   S.active = false;
 }
@@ -192,7 +192,7 @@ int sh_set_hull_mode(sh_ctx* c, const char* mode) {
   if (!c || !mode) return SH_ERR_ARG;
   if (strcmp(mode, "host") && strcmp(mode, "device") && strcmp(mode, "auto")) return fail(c, SH_ERR_ARG, "sh_set_hull_mode: host | device | auto");
   if (c->n_pending != 0) return fail(c, SH_ERR_STATE, "sh_set_hull_mode: runs are in flight");
-  if (c->prep.active) { if (c->prep.th.joinable()) c->prep.th.join(); c->prep.active = false; c->prep.gen = ~0ull; }
+  if (c->prep.key.active) { (void)join_prepared(c); c->prep.key.void_hulls(); }
   c->hull_mode = hull_mode_from(strcmp(mode, "auto") ? mode : nullptr);
   return SH_OK;
 }
@@ -232,7 +232,7 @@ int sh_ctx_create(int device, void* hip_stream, sh_ctx** out) {
 void sh_ctx_destroy(sh_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->prep.active && c->prep.th.joinable()) c->prep.th.join();
+  if (c->prep.key.active && c->prep.th.joinable()) c->prep.th.join();
   (void)hipStreamSynchronize(c->stream);
   comm_forget(c);
   unet_turn_forget(c);
@@ -282,9 +282,9 @@ int sh_set_params(sh_ctx* c, const sh_params* p) {
   if (p->unet_dtype != SH_UNET_F32 && p->unet_dtype != SH_UNET_BF16 && p->unet_dtype != SH_UNET_F16 && p->unet_dtype != SH_UNET_F32X)
     return fail(c, SH_ERR_ARG, "unet_dtype must be SH_UNET_F32, SH_UNET_F32X, SH_UNET_BF16 or SH_UNET_F16");
   if (p->bone_kind != SH_BONE_HUMERUS && p->bone_kind != SH_BONE_PROXIMAL) return fail(c, SH_ERR_ARG, "bone_kind must be SH_BONE_HUMERUS or SH_BONE_PROXIMAL");
-  if (c->prep.active && p->bone_kind != c->params.bone_kind) (void)join_prepared(c);
+  if (c->prep.key.active && p->bone_kind != c->params.bone_kind) (void)join_prepared(c);
   c->params = *p;
-  c->ovf_none_gen = ~0ull;      // (the plane sets depend on the parameters)
+  c->batch.params_set();
   return SH_OK;
 }
 
@@ -337,7 +337,7 @@ int sh_batch_size(const sh_ctx* c) { return c ? c->B : 0; }
   WIN_HULLCAP_BUFS(X) X(hull_nv, "hull.nv", int, 1) X(hull_nf, "hull.nf", int, 1) X(hull_ne, "hull.ne", int, 1)                    \
   X(obb_best_enc, "obb.best_enc", unsigned long long, 1) X(obb_lbmin_enc, "obb.lbmin_enc", unsigned long long, 1)                  \
   X(obb_dir_count, "obb.dir_count", int, 1) X(obb_T_pre, "obb.T_pre", double, 16) X(obb_zb_pre, "obb.zb_pre", double, 2)           \
-  X(obb_endpts, "obb.endpts", double, (size_t)2 * c->end_cap * 2) X(obb_endcnt, "obb.endcnt", int, 2) X(obb_resid, "obb.resid", double, 2)
+  X(obb_endpts, "obb.endpts", double, (size_t)2 * c->batch.caps().end * 2) X(obb_endcnt, "obb.endcnt", int, 2) X(obb_resid, "obb.resid", double, 2)
 // the SH_BONE_PROXIMAL path's own (alloc_prox, on first use; null in the view of a context that never took it): the cut-off of the
 // ProxObb area scan and the large Gram matrix of the neck change point
 #define WIN_PROX_BUFS(X)                                                                                                           \
@@ -420,7 +420,7 @@ static int alloc_batch(sh_ctx* c) {
   if ((rc = grow_pinned(c, &c->h_kept, &c->h_kept_cap, (size_t)c->sumV, 12)) != SH_OK) return rc;
   if ((rc = grow_pinned(c, &c->h_nkept, &c->h_nkept_cap, (size_t)B, 4)) != SH_OK) return rc;
   if ((rc = grow_pinned(c, &c->h_koff, &c->h_koff_cap, (size_t)B + 1, 8)) != SH_OK) return rc;
-  c->obb_injected = false;
+  c->batch.batch_resident();
   return SH_OK;
 }
 
@@ -630,7 +630,7 @@ int sh_buffer_device(sh_ctx* c, const char* name, void** dev_ptr, size_t* nbytes
   *dev_ptr = it->second.p;
   if (nbytes) *nbytes = it->second.bytes;
   if (std::string(name) == "params") params_changed(c);      // (the caller may write it)
-  c->ovf_none_gen = ~0ull;      // (... or a frame / an intermediate that moves the planes: the overflow tier runs again)
+  c->batch.buffer_touched(name, false);      // (... or a frame / an intermediate that moves the planes: the overflow tier runs again)
   return SH_OK;
 }
 
@@ -652,11 +652,11 @@ int sh_store(sh_ctx* c, const char* name, const void* host, size_t nbytes) {
   if (nbytes > it->second.bytes) return fail(c, SH_ERR_ARG, std::string("sh_store: size exceeds buffer ") + name);
   HIPCHK(c, hipSetDevice(c->device));
   if (std::string(name) == "verts") { discard_staged(c); (void)join_prepared(c); ++c->batch_gen; c->h_verts_valid = false; drop_closest(c); }
-  c->ovf_none_gen = ~0ull;      // (an injected frame or intermediate moves the planes: the overflow tier runs again)
+  c->batch.buffer_touched(name, false);      // (an injected frame or intermediate moves the planes: the overflow tier runs again)
   if (std::string(name) == "params") params_changed(c);
   HIPCHK(c, hipMemcpyAsync(it->second.p, host, nbytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (std::string(name) == "obb_transform") c->obb_injected = true;
+  c->batch.buffer_touched(name, true);
   return SH_OK;
 }
 
@@ -883,13 +883,14 @@ int sh_mesh_transformed(sh_ctx* c, int b, const double* T, double* out) {
 // ---- overflow planes of the slice layer (k_ovf.h) --------------------------------------------------------
 static int ovf_pools(sh_ctx* c, OvfPools* P) {
   int rc;
-  if ((rc = ensure(c, "ovf.segs", c->ovf_seg_cap * sizeof(Seg), 1)) != SH_OK) return rc;
-  if ((rc = ensure(c, "ovf.ring", c->ovf_ring_cap * 16, 8)) != SH_OK) return rc;
-  if ((rc = ensure(c, "ovf.work", c->ovf_work_cap, 1)) != SH_OK) return rc;
+  const DemandCaps& cap = c->batch.caps();
+  if ((rc = ensure(c, "ovf.segs", cap.seg * sizeof(Seg), 1)) != SH_OK) return rc;
+  if ((rc = ensure(c, "ovf.ring", cap.ring * 16, 8)) != SH_OK) return rc;
+  if ((rc = ensure(c, "ovf.work", cap.work, 1)) != SH_OK) return rc;
   if ((rc = ensure(c, "ovf.ctr", SH_NCTR * 8, 8)) != SH_OK) return rc;      // the demand block of a run (sh_demand.h names its words)
   for (const char* n : {"ovf.segs", "ovf.ring", "ovf.work", "ovf.ctr"}) c->bufs[n].per_mesh = 0;
   P->segs = (Seg*)c->bufs["ovf.segs"].p; P->ring = (double*)c->bufs["ovf.ring"].p; P->work = (unsigned char*)c->bufs["ovf.work"].p;
-  P->seg_cap = c->ovf_seg_cap; P->ring_cap = c->ovf_ring_cap; P->work_cap = c->ovf_work_cap;
+  P->seg_cap = cap.seg; P->ring_cap = cap.ring; P->work_cap = cap.work;
   P->ctr = (unsigned long long*)c->bufs["ovf.ctr"].p;
   P->open_mode = c->open_mode;
   return SH_OK;
@@ -926,7 +927,7 @@ static int run_slice_sets(sh_ctx* c, const WinView& v, const SliceSpec* specs, i
   if (ntot > SH_EMIT_MAXN) return fail(c, SH_ERR_CAPACITY, "slice sets have more planes than k_slice_emit's LDS histogram");
   OvfPools OP; OvfSet OS[2];
   { int orc; if ((orc = ovf_pools(c, &OP)) != SH_OK) return orc; }
-  const bool ovf_on = c->ovf_none_gen != c->batch_gen;      // (known from an earlier run of this batch: no plane overflows)
+  const bool ovf_on = c->batch.tier_on(c->batch_gen);     // (known from an earlier run of this batch: no plane overflows)
   const bool bridge = c->open_mode != SH_OPEN_ERROR;
   SliceSets sets{};
   sets.n = nspec;
@@ -1021,7 +1022,7 @@ static int grow_hull_records(sh_ctx* c, int nv, int nf, int ne) {
 
 // mesh.py:63-125.  Host: convex hulls (hull_host_phase; already done by the background thread when `prepared_slot`
 // >= 0).  Device: candidate boxes for every hull face, pick + frame, end sections, circle fits, flip (k_obb.h).
-static bool device_hull_now(const sh_ctx* c) { return c->hull_mode == 1 && !(c->hull_force_host && c->obb_gen == c->batch_gen); }
+static bool device_hull_now(const sh_ctx* c) { return c->batch.device_hull(c->hull_mode, c->batch_gen); }
 
 // What one window's stages tell each other; lives in run_window
 struct WinState {
@@ -1035,7 +1036,7 @@ struct WinState {
 static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int redo_nf) {
   const int B = v.B, b0 = c->b0;
   int nfmax = 1;
-  if (c->obb_gen != c->batch_gen) { c->obb_gen = c->batch_gen; c->obb_sil_need = 0; c->obb_nf_over = false; c->hull_force_host = false; }
+  c->batch.obb_begins(c->batch_gen);      // (a new batch: the small k_obb_candidates tier and the chosen hull mode again)
   if (redo_nf > 0) nfmax = redo_nf;
   else if (device_hull_now(c)) {
     { int drc = run_device_hull(c, B, &nfmax); if (drc != SH_OK) return drc; }
@@ -1077,8 +1078,9 @@ static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int re
            v.obb_lbmin_enc, v.obb_cand_vol, v.obb_cand_edge, bnd_tiles, B, hc);
     // capacity tier of k_obb_candidates (k_obb.h): the small one unless a hull of this launch has more than 8 192 faces or a direction
     // of an earlier run of this batch had more than 512 silhouette edges; the workspace tier above 32 768 faces / 2 048 edges
-    const bool huge = nfmax > 32768 || c->obb_sil_need > 2048 || c->obb_nf_over;
-    const bool big = !huge && (nfmax > 8192 || c->obb_sil_need > 512);
+    const int sil_need = c->batch.caps().sil_need;
+    const bool huge = nfmax > 32768 || sil_need > 2048 || c->batch.caps().nf_over;
+    const bool big = !huge && (nfmax > 8192 || sil_need > 512);
     const int TT = (big || huge) ? 8 : SH_OBB_TILE;
     const int ntiles = (nfmax + TT - 1) / TT;
     const auto candidates = huge ? k_obb_candidates<8, 1, 0, 0, unsigned, true>
@@ -1087,7 +1089,7 @@ static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int re
     ws.need = v.ovf_ctr + SH_CTR_SIL_NEED;
     if (huge) {
       ws.nwg = 256;
-      ws.silcap = std::max(hc.v + 64, c->obb_sil_need + c->obb_sil_need / 8);      // (a silhouette is a cycle of the hull's graph; more only on degenerate input: then the demand is recorded)
+      ws.silcap = std::max(hc.v + 64, sil_need + sil_need / 8);      // (a silhouette is a cycle of the hull's graph; more only on degenerate input: then the demand is recorded)
       int wrc;
       if ((wrc = ensure(c, "obb.ws_fmask", (size_t)ws.nwg * hc.f, 1)) != SH_OK || (wrc = ensure(c, "obb.ws_lists", (size_t)ws.nwg * 8 * ws.silcap * 4, 4)) != SH_OK ||
           (wrc = ensure(c, "obb.ws_sxy", (size_t)ws.nwg * ws.silcap * 16, 8)) != SH_OK || (wrc = ensure(c, "obb.ws_area", (size_t)ws.nwg * ws.silcap * 8, 8)) != SH_OK) return wrc;
@@ -1122,14 +1124,15 @@ static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int re
     if ((rc2 = run_slice_set(c, v, SPEC_POBB)) != SH_OK) return rc2;
     LAUNCH(c, "k_prox_obb", k_prox_obb, dim3((B + 63) / 64), dim3(64), v.set[SET_POBB].area_total, v.set[SET_POBB].zs, v.obb_T_pre,
            v.obb_transform, v.flipped, v.pobb_cutoff, v.pobb_cutoff_idx, v.err, B);
-    c->obb_injected = true;
+    c->batch.frame_computed();
     return SH_OK;
   }
   dim3 g((unsigned)std::min<long long>((c->maxF + 255) / 256, 1024), (unsigned)B);
-  LAUNCH(c, "k_obb_end_points", k_obb_end_points, g, dim3(256), v.verts, v.faces, v.voff, v.foff, v.obb_T_pre, v.obb_zb_pre, v.obb_endpts, v.obb_endcnt, c->end_cap);
-  LAUNCH(c, "k_obb_ends", k_obb_ends, dim3(B), dim3(128), v.obb_endpts, v.obb_endcnt, v.obb_T_pre, v.obb_resid, v.obb_transform, v.flipped, v.err, B, c->end_cap,
+  const int end_cap = c->batch.caps().end;
+  LAUNCH(c, "k_obb_end_points", k_obb_end_points, g, dim3(256), v.verts, v.faces, v.voff, v.foff, v.obb_T_pre, v.obb_zb_pre, v.obb_endpts, v.obb_endcnt, end_cap);
+  LAUNCH(c, "k_obb_ends", k_obb_ends, dim3(B), dim3(128), v.obb_endpts, v.obb_endcnt, v.obb_T_pre, v.obb_resid, v.obb_transform, v.flipped, v.err, B, end_cap,
          v.ovf_ctr + SH_CTR_END_NEED);
-  c->obb_injected = true;
+  c->batch.frame_computed();
   return SH_OK;
 }
 
@@ -1142,7 +1145,7 @@ static int run_te_rows(sh_ctx* c, const WinView& v) {
   { int orc; if ((orc = ovf_pools(c, &OP)) != SH_OK || (orc = ovf_set(c, "distal", SH_NDIST, &OS)) != SH_OK) return orc; }
   LAUNCH(c, "k_te_rows", k_te_rows<SH_SMALLSEG>, dim3(B * SH_TE_NROWS), dim3(64), distal.ring, distal.ring_n, v.te_rects, B, (const long long*)OS.roff);
   LAUNCH(c, "k_te_rows_large", k_te_rows<SH_MAXSEG>, dim3(B * SH_TE_NROWS), dim3(64), distal.ring, distal.ring_n, v.te_rects, B, (const long long*)OS.roff);
-  if (c->ovf_none_gen != c->batch_gen) LAUNCH(c, "k_te_rows_huge", k_te_rows_huge, dim3(64), dim3(64), OP, OS, (const int*)distal.ring_n, v.te_rects);
+  if (c->batch.tier_on(c->batch_gen)) LAUNCH(c, "k_te_rows_huge", k_te_rows_huge, dim3(64), dim3(64), OP, OS, (const int*)distal.ring_n, v.te_rects);
   // epicondyle.py:39-89: the widest slice's end slivers, their centroids, the farthest pair (CT coordinates, piece order)
   LAUNCH(c, "k_te_ends", k_te_ends, dim3(B), dim3(64), distal.ring, distal.ring_n, v.te_rects, distal.zs, v.obb_transform, v.te_ends_ct, v.te_row, v.err, B, OP, OS);
   return SH_OK;
@@ -1315,7 +1318,7 @@ static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot, int redo_nf =
   // proximal -> groove chain.  Larger batches: the distal set and the trans-epicondylar rows stay in the chain (DESIGN.md section 9:
   // the rows forked beside the lane's UNet pass, or run behind it, made the step slower).  Fork only when the overflow tier is known
   // to be idle for this batch (its pool counters are per set) and no per-launch timing is on.
-  const bool can_fork = has(SH_STAGE_DISTAL) && c->ovf_none_gen == c->batch_gen && c->timing != 1 && redo_nf == 0;
+  const bool can_fork = has(SH_STAGE_DISTAL) && !c->batch.tier_on(c->batch_gen) && c->timing != 1 && redo_nf == 0;
   const bool side = can_fork && v.B <= 16;
   const bool merge_fd = merge_env && has(SH_STAGE_FULL) && has(SH_STAGE_DISTAL) && !side;
   if (merge_fd) {
@@ -1343,16 +1346,30 @@ static int run_window(sh_ctx* c, uint32_t mask, int prepared_slot, int redo_nf =
   return SH_OK;
 }
 
-// Humeri per window.  Default: one window = the whole batch.  Measured on MI355X (bf16 UNet): B=256 as 4 windows of 64
+// Humeri per window (sh_run.h SH_WINDOW).  Default: one window = the whole batch.  Measured on MI355X (bf16 UNet): B=256 as 4 windows of 64
 // 2549 humeri/s vs 2744 as one window -- the kernels run ~15 % more efficiently on the larger launches, which is more
 // than the hidden host hull (13 % of the step) buys back.  SHOULDER_WINDOW=<n> enables windows of n.
-#define SH_WINDOW (1 << 30)
 
-// ---- overlap of the host hulls with the device work of the previous run ----------------------------------
+// ---- the background preparations of hulls (sh_ctx::Prepared; sh_run.h PreparedKey says who writes what) ----------------------------------
+// the results of a new thread: nothing yet (the caller has just written the key)
+static void prepared_reset(sh_ctx::Prepared& p) { p.rc = SH_OK; p.bad_mesh = -1; p.d2h_ms = p.hull_ms = 0; p.err.clear(); p.uploaded = false; }
+
+// The tail of both threads: the host hulls of `pts` into the key's pinned slot, then (`can_upload`) the records to the device as soon as
+// the running step no longer reads the hull.* buffers (after its k_obb_pick)
+static void prepared_hulls(sh_ctx* c, const sh_ctx::HullPts& pts, const HullRec& dst, bool can_upload) {
+  sh_ctx::Prepared& q = c->prep;
+  const int slot = q.key.slot, B = q.key.B;
+  q.rc = hull_host_phase(c, pts, slot, 0, B, &q.bad_mesh, &q.hull_ms, &q.err, true);
+  if (q.rc == SH_OK && can_upload && hipStreamWaitEvent(c->copy_stream, c->obb_done_ev, 0) == hipSuccess && hull_upload(c, slot, B, dst, c->copy_stream) == hipSuccess &&
+      hipStreamSynchronize(c->copy_stream) == hipSuccess)
+    q.uploaded = true;
+}
+
+// overlap of the host hulls with the device work of the previous run
 static void start_prepare(sh_ctx* c) {
   sh_ctx::Prepared& p = c->prep;
-  p.active = true; p.slot = c->hslot; p.B = c->B; p.gen = c->batch_gen; p.rc = SH_OK; p.bad_mesh = -1; p.d2h_ms = p.hull_ms = 0; p.err.clear();
-  p.uploaded = false; p.staged = false;
+  p.key.begin_resident(c->hslot, c->B, c->batch_gen);
+  prepared_reset(p);
   // device pointers are looked up here: the buffer map belongs to the calling thread
   const HullPre hp = hullpre_ptrs(c);
   const HullRec dst = hull_rec(c);
@@ -1366,13 +1383,7 @@ static void start_prepare(sh_ctx* c) {
       if (fetch_hull_points(c, hp, c->copy_stream) != hipSuccess) { q.rc = SH_ERR_HIP; return; }
       q.d2h_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    q.rc = hull_host_phase(c, c->hull_in, q.slot, 0, q.B, &q.bad_mesh, &q.hull_ms, &q.err, true);
-    if (q.rc == SH_OK && can_upload) {
-      // the records go to the device as soon as the running step no longer reads the hull.* buffers (after its k_obb_pick)
-      if (hipStreamWaitEvent(c->copy_stream, c->obb_done_ev, 0) == hipSuccess && hull_upload(c, q.slot, q.B, dst, c->copy_stream) == hipSuccess &&
-          hipStreamSynchronize(c->copy_stream) == hipSuccess)
-        q.uploaded = true;
-    }
+    prepared_hulls(c, c->hull_in, dst, can_upload);
   });
 }
 
@@ -1392,7 +1403,7 @@ int sh_set_unet_turns(sh_ctx* c, int on) {
 int sh_discard_prepared(sh_ctx* c) {
   if (!c) return SH_ERR_ARG;
   (void)join_prepared(c);
-  c->prep.gen = ~0ull;
+  c->prep.key.void_hulls();
   return SH_OK;
 }
 
@@ -1462,11 +1473,12 @@ static hipError_t staged_h2d(void* dev, void* pinned, const void* src, size_t n,
   });
 }
 
-static bool is_pinned_host(const void* p) {
+// where a caller's pointer lives: hipMemoryTypeHost (page-locked), hipMemoryTypeDevice; memory HIP does not know is neither
+static bool pointer_is(const void* p, hipMemoryType where) {
   hipPointerAttribute_t at{};
-  const bool pinned = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost;
+  const bool is = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == where;
   (void)hipGetLastError();
-  return pinned;
+  return is;
 }
 
 // The staging side for a batch of at most sumV_cap vertices / sumF_cap faces, `src_bytes` of page-locked staging for the caller's
@@ -1495,7 +1507,7 @@ static int stage_begin(sh_ctx* c, int B, long long sumV_cap, long long sumF_cap,
 struct StlJob { StlPlan plan; StlView v; std::vector<const void*> files; std::vector<size_t> nbytes; std::vector<char> pinned; };
 
 // The background thread of a staged batch: phase 0 (the caller's memory to the device, the first kernels), for STL files the sizes
-// of the merged meshes -> offsets -> k_stl_emit, then hull points through the prefilter, host hulls into pinned slot `prep.slot`,
+// of the merged meshes -> offsets -> k_stl_emit, then hull points through the prefilter, host hulls into pinned slot `prep.key.slot`,
 // records to the device as soon as the run in flight no longer reads hull.*.  `hulls` false (device hull): no hull work.
 static int start_prepare_staged(sh_ctx* c, int B, std::shared_ptr<const StlJob> stl /*null: arrays*/, std::function<int(std::string*)> phase0) {
   sh_ctx::Prepared& p = c->prep;
@@ -1506,8 +1518,8 @@ static int start_prepare_staged(sh_ctx* c, int B, std::shared_ptr<const StlJob> 
   S.h_flag[0] = 0;
   HIPCHK(c, hipEventRecord(S.ready_ev, c->copy_stream));      // (recorded again by the thread behind the last copy / k_stl_emit; this one covers an early discard)
   S.active = true;
-  p.active = true; p.staged = true; p.slot = c->hslot; p.B = S.B; p.gen = hulls ? c->batch_gen + 1 : ~0ull; p.rc = SH_OK; p.bad_mesh = -1; p.d2h_ms = p.hull_ms = 0; p.err.clear();
-  p.uploaded = false;
+  p.key.begin_staged(c->hslot, S.B, c->batch_gen, hulls);
+  prepared_reset(p);
   const HullPre hp = hullpre_ptrs(c, ".s");
   const HullRec dst = {(double*)c->bufs["hull.hv"].p, (double*)c->bufs["hull.normals"].p, (int*)c->bufs["hull.edges"].p, (int*)c->bufs["hull.nv"].p, (int*)c->bufs["hull.nf"].p,
                        (int*)c->bufs["hull.ne"].p};      // (the whole batch's, whatever window the context stands at)
@@ -1559,13 +1571,8 @@ static int start_prepare_staged(sh_ctx* c, int B, std::shared_ptr<const StlJob> 
     }
     t_pts = since();
     if (!stl && S.h_flag[0] != 0) { q.rc = SH_ERR_ARG; return; }      // (the validation word came back in front of the survivors; the commit reports it)
-    q.rc = hull_host_phase(c, S.pts, q.slot, 0, B, &q.bad_mesh, &q.hull_ms, &q.err, true);
-    if (dbg) fprintf(stderr, "[sh] staged batch: copies enqueued %.2f ms, sizes known %.2f, hull points back %.2f, hulls done %.2f (hull phase %.2f)\n", t_p0, t_meta, t_pts, since(), q.hull_ms);
-    if (q.rc == SH_OK && can_upload) {
-      if (hipStreamWaitEvent(c->copy_stream, c->obb_done_ev, 0) == hipSuccess && hull_upload(c, q.slot, B, dst, c->copy_stream) == hipSuccess &&
-          hipStreamSynchronize(c->copy_stream) == hipSuccess)
-        q.uploaded = true;
-    }
+    prepared_hulls(c, S.pts, dst, can_upload);
+    if (dbg) fprintf(stderr, "[sh] staged batch: copies enqueued %.2f ms, sizes known %.2f, hull points back %.2f, hulls done and uploaded %.2f (hull phase %.2f)\n", t_p0, t_meta, t_pts, since(), q.hull_ms);
   });
   return SH_OK;
 }
@@ -1579,7 +1586,7 @@ int sh_stage_meshes(sh_ctx* c, const float* verts, const int32_t* faces, const i
   // the caller's arrays -> page-locked memory (unless they are page-locked already) -> device, all by the background thread: the
   // caller keeps its arrays unchanged until sh_commit_staged has returned
   const size_t vb = (size_t)sz.sumV * 12, fb = (size_t)sz.sumF * 12, vpad = (vb + 255) & ~(size_t)255;
-  const bool vpin = is_pinned_host(verts), fpin = is_pinned_host(faces);
+  const bool vpin = pointer_is(verts, hipMemoryTypeHost), fpin = pointer_is(faces, hipMemoryTypeHost);
   int rc;
   if ((rc = stage_begin(c, B, sz.sumV, sz.sumF, 64, (vpin ? 0 : vpad) + (fpin ? 0 : fb))) != SH_OK) return rc;
   sh_ctx::StageSide& S = c->stg;
@@ -1629,7 +1636,7 @@ int sh_stage_stl(sh_ctx* c, const void* const* files, const size_t* nbytes, int 
   if (!c->stl_counted_ev) HIPCHK(c, hipEventCreateWithFlags(&c->stl_counted_ev, hipEventDisableTiming));
   // the files themselves are read by the background thread: the caller keeps them unchanged until sh_commit_staged has returned
   job->files.assign(files, files + B); job->nbytes.assign(nbytes, nbytes + B); job->pinned.resize(B);
-  for (int b = 0; b < B; ++b) job->pinned[b] = is_pinned_host(files[b]) ? 1 : 0;
+  for (int b = 0; b < B; ++b) job->pinned[b] = pointer_is(files[b], hipMemoryTypeHost) ? 1 : 0;
   std::shared_ptr<const StlJob> a = job;
   auto phase0 = [c, a, h_tabs, B](std::string* et) -> int {
     sh_ctx::StageSide& S = c->stg;
@@ -1687,8 +1694,6 @@ __global__ void k_stage_status(const int* __restrict__ err, const unsigned long 
   if (i < SH_NCTR) dst.words()[i] = ovf_ctr[i];
 }
 
-static DemandCaps demand_caps(const sh_ctx* c) { return DemandCaps{c->ovf_seg_cap, c->ovf_ring_cap, c->ovf_work_cap, c->end_cap, c->obb_sil_need, c->obb_nf_over}; }
-
 // The device hull gave humeri up during the run of ticket `tk` (st.gave_up(); k_hull.h writes a unit tetrahedron for them, so
 // everything queued behind ran on finite data and their records are void).  Each of them gets the host quickhull -- which
 // has the retry / joggle logic -- its record goes into the device buffers where the device hull would have put it, and its
@@ -1716,7 +1721,7 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, c
     if (hn > c->hcap.v || fn > c->hcap.f || en > c->hcap.e) {
       // above the record: growing it here would drop the other humeri's records -- the batch runs again with its hulls from the
       // host (hull_host_phase sizes the staging, run_obb grows the record), and stays there while it is resident
-      c->hull_force_host = true;
+      c->batch.hull_above_record();
       again->rerun = SH_RERUN_FORCE_HOST;
       return SH_OK;
     }
@@ -1738,7 +1743,7 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, c
       HIPCHK(c, hipMemsetAsync(buf<int>(c, "err"), 0, 4, c->stream));
       if (c->open_mode != SH_OPEN_ERROR) HIPCHK(c, hipMemsetAsync(buf<int>(c, "open.stats"), 0, 8, c->stream));      // (the void first pass counted too)
       HIPCHK(c, hipStreamSynchronize(c->stream));      // the sources above are locals
-      c->skip_nfmax = std::max(c->skip_nfmax, fn);
+      c->batch.redo_used_faces(fn);
       rc = run_window(c, tk.mask, -1, fn);
     }
     if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
@@ -1754,7 +1759,7 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, c
   unsigned long long ctr[SH_NCTR];
   HIPCHK(c, hipMemcpyAsync(ctr, c->bufs["ovf.ctr"].p, sizeof ctr, hipMemcpyDeviceToHost, c->out_stream));
   HIPCHK(c, hipStreamSynchronize(c->out_stream));
-  *again = demand_verdict(ctr, demand_caps(c), (tk.mask & SH_STAGE_OBB) != 0, tk.gen == c->batch_gen);
+  *again = demand_verdict(ctr, c->batch.caps(), (tk.mask & SH_STAGE_OBB) != 0, tk.gen == c->batch_gen);
   if (again->rerun != SH_RERUN_NONE) return SH_OK;
   if (tk.host_out)
     HIPCHK(c, hipMemcpyAsync(tk.host_out, c->bufs["out.landmarks" + tslot].p, (size_t)B * tk.rec, hipMemcpyDeviceToHost, c->out_stream));
@@ -1775,12 +1780,18 @@ static int ticket_setup(sh_ctx* c, sh_ctx::Ticket& tk, int B) {
   return SH_OK;
 }
 
+// A submit reads: precheck -> tickets and staging buffers -> clears -> prepared hand-over and plan (the plan needs the preparation's
+// rc, which exists behind the join; the join stays behind the clears so that the device has them while the host waits) -> windows ->
+// overlap -> park the results -> ticket.  The decisions are sh_run.h's.
 int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
   if (!c) return SH_ERR_ARG;
-  if (c->B < 1) return fail(c, SH_ERR_STATE, "sh_run: no meshes uploaded");
-  if (c->n_pending >= 2) return fail(c, SH_ERR_STATE, "sh_submit: two runs are in flight already (sh_collect first)");
+  // a refused submit enqueues nothing, allocates nothing and leaves "err", "ovf.ctr", "open.stats" and open_stats_run as they were
+  RunFacts facts{c->B, c->n_pending, (int)c->params.bone_kind, c->hull_mode, c->sw.window, c->overlap, c->stg.active, c->batch_gen, c->hslot, &c->batch, c->prep.key, SH_OK};
+  if (const RunError e = precheck_submit(mask, facts); e.code != SH_OK) return fail(c, e.code, e.text);
   HIPCHK(c, hipSetDevice(c->device));
   const int B = c->B;
+  // (`out` may also be device memory, e.g. the send buffer of a gather)
+  const bool out_on_device = out && pointer_is(out, hipMemoryTypeDevice);
   sh_ctx::Ticket& tk = c->tickets[c->t_head];
   if (int e = ticket_setup(c, tk, B)) return e;
   // the other ticket's pinned block, event and device staging with the first one (else the context's SECOND run pays for them)
@@ -1788,42 +1799,22 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
     if (int e = ticket_setup(c, to, B)) return e;
     const std::string oslot = std::to_string(c->t_head ^ 1);
     if (int e = ensure(c, ("out.err" + oslot).c_str(), StatusBlock::bytes(B), 4)) return e;
-    if (out) { hipPointerAttribute_t at{}; const bool dev = hipPointerGetAttributes(&at, out) == hipSuccess && at.type == hipMemoryTypeDevice; (void)hipGetLastError();
-               if (!dev) { if (int e = ensure(c, ("out.landmarks" + oslot).c_str(), (size_t)B * rec_bytes_rows(c->rec_rows), 1)) return e; } }
+    if (out && !out_on_device) { if (int e = ensure(c, ("out.landmarks" + oslot).c_str(), (size_t)B * rec_bytes_rows(c->rec_rows), 1)) return e; }
   }
   if (!c->out_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->out_stream, hipStreamNonBlocking));
   c->b0 = 0; c->Bwin = B;
-  if (c->params.bone_kind == SH_BONE_PROXIMAL) {
-    if (mask & (SH_STAGE_DISTAL | SH_STAGE_TE)) return fail(c, SH_ERR_ARG, "sh_run: a proximal humerus has no distal / trans-epicondylar stage (bone.py:24-64)");
-    int prc = alloc_prox(c);
-    if (prc != SH_OK) return prc;
-  }
+  if (c->params.bone_kind == SH_BONE_PROXIMAL) { if (int e = alloc_prox(c)) return e; }
   { OvfPools OP; int orc = ovf_pools(c, &OP); if (orc != SH_OK) return orc; FILL(c, {buf<int>(c, "err"), (size_t)B * 4, 0}, {OP.ctr, SH_NCTR * 8, 0}); }      // overflow pools: empty, no demand recorded
   if (c->open_mode != SH_OPEN_ERROR) FILL(c, {buf<int>(c, "open.stats"), (size_t)B * 8, 0});      // (bridge mode only: the default run has no extra fill)
   c->open_stats_run = c->open_mode;
-  if ((mask & SH_STAGE_APPLY) && !(mask & SH_STAGE_CSYS)) return fail(c, SH_ERR_ARG, "sh_run: SH_STAGE_APPLY needs SH_STAGE_CSYS in the same run");
-  // a proximal humerus' frame is canal / articular (bone.py:53-62): k_pack builds it from the anatomic-neck axes of THIS run
-  if (c->params.bone_kind == SH_BONE_PROXIMAL && (mask & SH_STAGE_CSYS) && !(mask & SH_STAGE_ANP))
-    return fail(c, SH_ERR_ARG, "sh_run: SH_STAGE_CSYS of a proximal humerus needs SH_STAGE_ANP in the same run (canal / articular frame)");
-  if (!(mask & SH_STAGE_OBB) && !c->obb_injected)
-    return fail(c, SH_ERR_STATE, "sh_run: no OBB transform (run SH_STAGE_OBB or sh_store(\"obb_transform\"))");
-  // Windows: with the host hull in play the batch can be walked in windows of SHOULDER_WINDOW humeri; all device work of
-  // a window is only enqueued, so the hulls of the next window are computed while it runs (off by default).
-  int wsize = SH_WINDOW;
-  if (c->sw.window > 0) wsize = c->sw.window;     // tests exercise small windows
-  const bool dev_hull = (mask & SH_STAGE_OBB) && device_hull_now(c);
-  const int win = ((mask & SH_STAGE_OBB) && B > wsize && !dev_hull) ? wsize : B;      // (windows exist to overlap HOST hulls with device work)
-  // hulls prepared by the background thread during the previous run (sh_set_overlap)?
-  int prepared = -1;
-  if (c->prep.active) {
-    int prc = join_prepared(c);
-    if ((mask & SH_STAGE_OBB) && win == B && prc == SH_OK && c->prep.gen == c->batch_gen && c->prep.B == B) { prepared = c->prep.slot; c->hslot = prepared ^ 1; }
-  }
-  // a run of the resident batch while hulls for the STAGED one are waiting: its own hull phase takes the same pinned slot and
-  // the same hull.* device buffers, so those hulls are void (the staged batch stays; its first run computes them again)
-  if ((mask & SH_STAGE_OBB) && c->prep.staged && c->prep.gen != c->batch_gen) c->prep.gen = ~0ull;
-  if (dev_hull) prepared = -1;
-  if ((mask & SH_STAGE_OBB) && prepared < 0 && !dev_hull) {
+  // hulls prepared by the background thread during the previous run (sh_set_overlap)?  Windows: with the host hull in play the batch
+  // can be walked in windows of SHOULDER_WINDOW humeri; all device work of a window is only enqueued, so the hulls of the next window
+  // are computed while it runs (off by default; tests exercise small windows).
+  facts.prep_rc = join_prepared(c);
+  const RunPlan plan = run_plan(mask, facts);
+  c->hslot = plan.next_hslot;
+  if (plan.void_staged_hulls) c->prep.key.void_hulls();
+  if (plan.fetch_points) {
     // the host hull needs its points (a device-generated batch: every run, a new batch is new data)
     auto t0 = std::chrono::steady_clock::now();
     HIPCHK(c, fetch_hull_points(c, hullpre_ptrs(c), c->stream));
@@ -1831,23 +1822,19 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
     if (c->timing && !c->h_verts_valid) { KTimer& a = c->timers["host.verts_d2h"]; a.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); a.n += 1; }
   }
   int rc = SH_OK, widx = 0;
-  for (int b0 = 0; b0 < B && rc == SH_OK; b0 += win, ++widx) {
-    WindowScope w(c, b0, std::min(win, B - b0));
-    rc = run_window(c, mask, widx == 0 ? prepared : -1);
+  for (int b0 = 0; b0 < B && rc == SH_OK; b0 += plan.win, ++widx) {
+    WindowScope w(c, b0, std::min(plan.win, B - b0));
+    rc = run_window(c, mask, widx == 0 ? plan.prepared_slot : -1);
   }
   // everything of this run is enqueued: the host is free until the device is done -> hulls of the next run (of the whole batch again)
-  if (rc == SH_OK && c->overlap && (mask & SH_STAGE_OBB) && win == B && !dev_hull && !c->stg.active) start_prepare(c);
-  if (mask & SH_STAGE_OBB) c->obb_injected = true;
+  if (rc == SH_OK && plan.start_overlap) start_prepare(c);
+  c->batch.run_enqueued(mask);
   if (rc != SH_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-  // (`out` may also be device memory, e.g. the send buffer of a gather: hipMemcpyDefault)
   // Results.  A device-to-host copy enqueued HERE would sit in a DMA queue until the kernels of this run are done and hold
   // up every later copy behind it - the vertex read-back of the background hull thread above all, which then loses its
   // overlap with the device (measured: 14.3 -> 19.2 ms per step at B=64).  So the records and status words are parked in a
   // per-ticket device buffer (a 16 us device-to-device copy at the end of the run) and sh_collect copies them to the host
   // once the run has finished.  Device `out` (the send buffer of a gather) is written directly.
-  hipPointerAttribute_t at{};
-  const bool out_on_device = out && hipPointerGetAttributes(&at, out) == hipSuccess && at.type == hipMemoryTypeDevice;
-  (void)hipGetLastError();
   const std::string tslot = std::to_string(c->t_head);
   void *lm_stage = nullptr, *err_stage = nullptr;
   if (int e = ensure(c, ("out.err" + tslot).c_str(), StatusBlock::bytes(B), 4, &err_stage)) return e;      // (the whole status block: the status words lead it)
@@ -1863,9 +1850,9 @@ int sh_submit(sh_ctx* c, uint32_t mask, sh_landmarks* out) {
   // status words, what the run asked of the overflow pools (k_ovf.h: sh_collect grows them and runs again if it was more than they
   // hold) and which humeri the device hull gave up (its own word per humerus: the status word can be overwritten by a later stage)
   LAUNCH(c, "k_stage_status", k_stage_status, dim3((unsigned)((std::max(B, (int)SH_NCTR) + 255) / 256)), dim3(256), (const int*)buf<int>(c, "err"), (const unsigned long long*)c->bufs["ovf.ctr"].p,
-         dev_hull ? (const int*)buf<int>(c, "hulld.fail") : (const int*)nullptr, StatusBlock{(char*)err_stage, B});
+         plan.dev_hull ? (const int*)buf<int>(c, "hulld.fail") : (const int*)nullptr, StatusBlock{(char*)err_stage, B});
   HIPCHK(c, hipEventRecord(tk.ev, c->stream));
-  tk.B = B; tk.pending = true; tk.mask = mask; tk.out_arg = out; tk.dev_hull = dev_hull; tk.gen = c->batch_gen;
+  tk.B = B; tk.pending = true; tk.mask = mask; tk.out_arg = out; tk.dev_hull = plan.dev_hull; tk.gen = c->batch_gen;
   c->arthro.run_submitted(mask, c->batch_gen);
   c->t_head ^= 1; ++c->n_pending;
   return SH_OK;
@@ -1885,36 +1872,24 @@ int sh_collect(sh_ctx* c) {
   HIPCHK(c, hipStreamSynchronize(c->out_stream));
   const StatusBlock st{tk.status, tk.B};
   const unsigned long long* w = st.words();
-  const uint32_t slice_stages = SH_STAGE_FULL | SH_STAGE_DISTAL | SH_STAGE_NECK | SH_STAGE_PROXIMAL;
-  // (only a run that computed its own frame may vouch for the batch: a run on an injected frame says nothing about the planes of
-  // the next SH_STAGE_OBB, and the `pobb` set of a proximal humerus runs inside that stage)
-  if (w[SH_CTR_RING_NEED] == 0 && w[SH_CTR_SEG_NEED] == 0 && (tk.mask & SH_STAGE_OBB) &&
-      (tk.mask & slice_stages) == (c->params.bone_kind == SH_BONE_PROXIMAL ? (slice_stages & ~(uint32_t)SH_STAGE_DISTAL) : slice_stages) &&
-      tk.gen == c->batch_gen)
-    c->ovf_none_gen = c->batch_gen;
-  if (c->sw.debug) fprintf(stderr, "[sh] collect: ovf need %llu %llu %llu cap %llu %llu %llu err0 %d\n", w[SH_CTR_SEG_NEED], w[SH_CTR_RING_NEED], w[SH_CTR_WORK_NEED], c->ovf_seg_cap, c->ovf_ring_cap, c->ovf_work_cap, st.err()[0]);
+  c->batch.run_collected(w, tk.mask, (int)c->params.bone_kind, tk.gen, c->batch_gen);      // (may it vouch that the overflow tier is idle?)
+  const DemandCaps& cap = c->batch.caps();
+  if (c->sw.debug) fprintf(stderr, "[sh] collect: ovf need %llu %llu %llu cap %llu %llu %llu err0 %d\n", w[SH_CTR_SEG_NEED], w[SH_CTR_RING_NEED], w[SH_CTR_WORK_NEED], cap.seg, cap.ring, cap.work, st.err()[0]);
   // Are the records valid as far as capacity goes?  The status block's demand words first; then the humeri the device hull gave up
   // are done again alone, and their one-humerus windows may raise a demand of their own.
-  Verdict v = demand_verdict(w, demand_caps(c), (tk.mask & SH_STAGE_OBB) != 0, tk.gen == c->batch_gen);
+  Verdict v = demand_verdict(w, cap, (tk.mask & SH_STAGE_OBB) != 0, tk.gen == c->batch_gen);
   const bool redo = v.rerun == SH_RERUN_NONE && tk.dev_hull;
   if (redo) { if (int e = redo_given_up(c, tk, st, tslot, &v)) return e; }
   if (v.rerun != SH_RERUN_NONE) {
     // The records of this run are void: the whole batch again, with what it asked for -- here, synchronously, when nothing else is
-    // in flight.  (The overflow tier is on for it when a plane needed it while it was skipped, and behind a redo: its hulls change.)
-    if (v.rerun == SH_RERUN_TIER || redo) c->ovf_none_gen = ~0ull;
-    if (c->n_pending != 0)
-      return fail(c, SH_ERR_CAPACITY,
-                  v.rerun == SH_RERUN_TIER ? "a section needs the overflow tier while another run is in flight: collect it, then run the batch again (the tier is on by then)" :
-                  v.rerun == SH_RERUN_OBB_TIER ? "the OBB stage needs a larger tier while another run is in flight: collect it, then run the batch again (the tier is chosen by then)" :
-                  v.rerun == SH_RERUN_FORCE_HOST ? "a hull is above the device hull's record while another run is in flight: collect it, then run the batch again (its hulls come from the host by then)" :
-                  "slice overflow pools too small while another run is in flight: collect it, then run the batch again (the pools are grown by then)");
+    // in flight.
+    c->batch.rerun_decided(v, redo);
+    if (c->n_pending != 0) return fail(c, SH_ERR_CAPACITY, rerun_refusal_text(v.rerun));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->ovf_seg_cap = v.caps.seg; c->ovf_ring_cap = v.caps.ring; c->ovf_work_cap = v.caps.work;
-    c->obb_sil_need = v.caps.sil_need; c->obb_nf_over = v.caps.nf_over;
+    const bool ends_grow = c->batch.rerun_granted(v);
     if (v.error) return fail(c, SH_ERR_CAPACITY, v.error);
-    if (v.caps.end != c->end_cap) {
-      c->end_cap = v.caps.end;
-      const size_t eb = (size_t)c->B * 2 * c->end_cap * 2 * 8;
+    if (ends_grow) {
+      const size_t eb = (size_t)c->B * 2 * cap.end * 2 * 8;
       if (int e = ensure(c, "obb.endpts", eb, 8)) return e;
       c->bufs["obb.endpts"].per_mesh = eb / (size_t)c->B;
     }

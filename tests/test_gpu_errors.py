@@ -248,3 +248,64 @@ def test_proximal_csys_needs_the_anatomic_neck_stage(engine, oracle_bones):
         assert err.value.code == -1 and "SH_STAGE_ANP" in str(err.value)
     finally:
         engine.set_params(bone_kind=_lib.BONE_HUMERUS)
+
+
+def test_refused_submit_touches_nothing(engine, oracle_bones):
+    """sh_submit decides before it acts: a refused submit enqueues nothing, allocates nothing and leaves "err", "ovf.ctr",
+    "open.stats" and the mode sh_open_contour_stats answers for as they were.  (Marks are stored into the three buffers behind
+    the good run: the clears of a submit would wipe them.)"""
+    from shoulder_amd import synth
+    from shoulder_amd.engine import Engine
+    h = oracle_bones("humerus_left")
+    T = synth.similarity_transforms(1, h.verts, seed=5)
+    prox = Engine(0)
+    try:
+        engine.reset_params()
+        engine.set_open_contours("bridge")
+        engine.upload([(h.verts, h.faces)]); engine.synth_batch(T)
+        first = engine.run(_lib.STAGE_ALL).copy()
+        assert first["status"][0] == 0
+        clean = [engine.fetch("err", np.int32, (1,)), engine.fetch("open.stats", np.int32, (2,)), engine.fetch("ovf.ctr", np.uint64, (16,))]
+        assert clean[0][0] == 0
+        marks = [np.array([7], np.int32), np.array([3, 4], np.int32), np.arange(16, dtype=np.uint64) + 11]
+        for name, m in zip(("err", "open.stats", "ovf.ctr"), marks):
+            engine.store(name, m)
+        engine.set_open_contours("error")      # (a submit would make this the mode sh_open_contour_stats answers for: zeros)
+
+        def unchanged():
+            assert [engine.fetch("err", np.int32, (1,)).tolist(), engine.fetch("open.stats", np.int32, (2,)).tolist(),
+                    engine.fetch("ovf.ctr", np.uint64, (16,)).tolist()] == [m.tolist() for m in marks]
+            assert [a.tolist() for a in engine.open_contour_stats()] == [[3], [4]]
+            with pytest.raises(ShoulderHipError, match="nothing in flight") as err:
+                engine.collect()
+            assert err.value.code == -3
+        with pytest.raises(ShoulderHipError, match="SH_STAGE_APPLY needs SH_STAGE_CSYS") as err:
+            engine.submit(_lib.STAGE_ALL & ~_lib.STAGE_CSYS)
+        assert err.value.code == -1
+        unchanged()
+        # a second context, proximal kind, that has never run: no frame, no demand block yet
+        prox.set_params(bone_kind=_lib.BONE_PROXIMAL)
+        prox.upload([(h.verts, h.faces)]); prox.synth_batch(T)
+        prox.store("err", marks[0])
+        with pytest.raises(ShoulderHipError, match="no distal / trans-epicondylar stage") as err:
+            prox.submit(_lib.STAGE_ALL)
+        assert err.value.code == -1
+        with pytest.raises(ShoulderHipError, match="no OBB transform") as err:
+            prox.submit(_lib.STAGE_FULL)
+        assert err.value.code == -3
+        assert prox.fetch("err", np.int32, (1,)).tolist() == [7]
+        for name in ("ovf.ctr", "out.err0", "out.err1"):      # nothing allocated
+            with pytest.raises(ShoulderHipError, match="no buffer named"):
+                prox.fetch(name, np.int32)
+        with pytest.raises(ShoulderHipError, match="nothing in flight"):
+            prox.collect()
+        unchanged()
+        engine.set_open_contours("bridge")
+        again = engine.run(_lib.STAGE_ALL)
+        assert again.tobytes() == first.tobytes()
+        for name, want in zip(("err", "open.stats"), clean):
+            assert engine.fetch(name, np.int32, want.shape).tolist() == want.tolist()
+    finally:
+        prox.close()
+        engine.set_open_contours("error")
+        engine.reset_params()
