@@ -27,13 +27,15 @@ struct __attribute__((aligned(16))) Seg {
 };
 static_assert(sizeof(Seg) == 16, "Seg must be 16 bytes");
 // crossing of mesh edge (lo, hi) with the plane at height z: oracle/section.py's formula, operation for operation
-__device__ inline void seg_start_point(const double* __restrict__ vb /*verts_obb of the mesh*/, uint32_t lo, uint32_t hi, double z, double* x, double* y) {
-  const double* pl = vb + 3 * (size_t)lo;
-  const double* ph = vb + 3 * (size_t)hi;
+// (two steps, so that a caller can ask for the vertices long before it needs the point: seg_point_of on loaded vertices)
+__device__ inline void seg_point_of(const double* pl /*[3] the edge's lower-id vertex*/, const double* ph /*[3]*/, double z, double* x, double* y) {
   const double dl = pl[2] - z, dh = ph[2] - z;
   const double t = dl / (dl - dh);
   *x = pl[0] + t * (ph[0] - pl[0]);
   *y = pl[1] + t * (ph[1] - pl[1]);
+}
+__device__ inline void seg_start_point(const double* __restrict__ vb /*verts_obb of the mesh*/, uint32_t lo, uint32_t hi, double z, double* x, double* y) {
+  seg_point_of(vb + 3 * (size_t)lo, vb + 3 * (size_t)hi, z, x, y);
 }
 
 // order-preserving double <-> uint64 for atomic min/max
@@ -274,7 +276,9 @@ k_slice_emit(const double* __restrict__ vobb, const int* __restrict__ faces,
 // One workgroup per (mesh, plane).  LDS hash join on edge keys -> successor list -> pointer
 // jumping for (a) the minimum edge key of each loop (canonical start, B-1) and (b) the rank of
 // every segment from that start.
-#define SH_LINK_THREADS 256
+// Two waves per plane: 65-75 % of a humerus' full and distal sections have at most 128 crossings (mean 129-143; proximal ~195, none
+// above 327), so two further waves only attended the barriers and held wave slots other planes could use.
+#define SH_LINK_THREADS 128
 #define SH_SMALLSEG 384      // tier boundary: planes with at most this many segments take the small-LDS instantiation (humerus sections: mean 140-210, max ~330)
 
 // Greedy matching by the smallest candidate first equals the matching of locally dominant pairs (a pair that is the smallest
@@ -353,8 +357,8 @@ __device__ inline int bridge_open_chains(const int n, const int cap, const int m
 
 // select: 0 = largest loop (slice.py:53-59), 1 = loop whose closed-ring vertex mean is nearest
 // the origin in L1 (surgical_neck.py:40-48)
-// Two instantiations share the grid: CAP = SH_SMALLSEG (17.5 KB of LDS, 8 workgroups = every wave slot of a CU) takes the planes
-// with up to 384 segments -- every section of a humerus at the fixture resolution -- and CAP = SH_MAXSEG (46 KB) the rest; the
+// Two instantiations share the grid: CAP = SH_SMALLSEG (11.7 KB of LDS: 13 planes = 26 of a CU's 32 wave slots) takes the planes
+// with up to 384 segments -- every section of a humerus at the fixture resolution -- and CAP = SH_MAXSEG (29 KB) the rest; the
 // other tier's planes exit at once.
 // A plane with more than SH_MAXLOOPS closed loops (a mesh with dozens of components in one section: fragments, trabecular
 // cavities) is handed to the overflow tier's join (k_ovf.h: loop tables of 1 024 entries): listed (ManyLoops), given pool ranges by
@@ -368,15 +372,20 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
              int* __restrict__ ring_n, double* __restrict__ ring /*nullable*/, int select, int* __restrict__ err,
              double* __restrict__ areas_total /*nullable: |sum of the signed loop areas| = Path2D.area*/, ManyLoops many, const OpenCfg oc,
              int* __restrict__ nlarge = nullptr) {
-  // LDS per plane decides how many planes a CU joins at once (the join is a chain of short dependent steps): 44 bytes per
-  // segment.  bufB holds the hash table until the label ping-pong starts; the crossing points stay in HBM (read twice, L2 hits).
+  // LDS per plane decides how many planes a CU joins at once (the join is a chain of short dependent steps): 28 bytes per
+  // segment, 13 planes of the small tier on a CU.  Nothing is double-buffered: a round of the pointer jumping reads into registers,
+  // then a barrier, then writes.  The crossing points wait in registers (computed once, from vertices asked for at the start) until
+  // the ring is placed, and the ring takes the two key arrays, which are dead by then.
   constexpr int HASH = CAP <= 384 ? 512 : 2048;
-  static_assert(HASH * 4 <= CAP * 8 && HASH > CAP, "the hash table lives in bufB");
-  __shared__ unsigned long long skey[CAP];
-  __shared__ unsigned long long bufA[CAP];   // ekey, then label ping, then rank arrays or loop map, then ring x
-  __shared__ unsigned long long bufB[CAP];   // hash table, then label pong, then rank arrays or loop map, then ring y
-  __shared__ int nxt[CAP], jmpA[CAP], jmpB[CAP], offA[CAP], offB[CAP];
-  int* const table = (int*)bufB;
+  static_assert(HASH * 4 <= CAP * 8 && HASH > CAP, "the hash table lives in jmp + rk");
+  constexpr int E = SH_MAXLOOPS;      // chain ends one plane bridges (bridge_open_chains)
+  static_assert(!OPEN || 6 * E + 4 <= CAP, "bridge mode's chain-end lists live in jmp");
+  __shared__ unsigned long long skey[CAP];   // start keys, then ring y
+  __shared__ unsigned long long lab[CAP];    // end keys, then labels, then ring x
+  __shared__ int nxt[CAP], jr[2 * CAP];
+  __shared__ double open_pts[OPEN ? 4 * E : 1];      // bridge mode: the end points of the chains
+  int* const jmp = jr; int* const rk = jr + CAP;
+  int* const table = jr;                     // the hash table, until the jumping starts
   __shared__ unsigned long long l_key[SH_MAXLOOPS];
   __shared__ int l_start[SH_MAXLOOPS], l_len[SH_MAXLOOPS], l_off[SH_MAXLOOPS];
   __shared__ double l_area[SH_MAXLOOPS], l_sel[SH_MAXLOOPS];
@@ -392,18 +401,16 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
   }
   if (cnt > SH_MAXSEG) return;      // an overflow plane: k_slice_link_huge (k_ovf.h)
   const int n = cnt;
-  if (tid == 0) { n_loops = 0; bad = 0; }
-  for (int i = tid; i < HASH; i += SH_LINK_THREADS) table[i] = -1;
+  constexpr int PER = (CAP + SH_LINK_THREADS - 1) / SH_LINK_THREADS;      // segments per lane
   const Seg* sp = segs + (size_t)pl * SH_MAXSEG;
   const double* vb = vobb + 3 * voff[b];
   const double zpl = zeff[pl];
-  for (int i = tid; i < n; i += SH_LINK_THREADS) {
-    Seg s = sp[i];
-    skey[i] = ((unsigned long long)s.s_lo << 32) | s.s_hi;
-    bufA[i] = ((unsigned long long)s.e_lo << 32) | s.e_hi;
-  }
-  __syncthreads();
-  if (n < 3 && !(OPEN && n > 0)) {      // (bridged, two segments can make a ring of three)
+  // Every record of the lane in one batch of loads, no branch between them (a loop would pay a round trip per trip): a lane past
+  // the count reads the last record again -- the slot is inside the plane's range whatever the count is.
+  Seg sg[PER];
+#pragma unroll
+  for (int c = 0; c < PER; ++c) { const int i = tid + c * SH_LINK_THREADS; sg[c] = sp[i < n ? i : (n > 0 ? n - 1 : 0)]; }
+  if (n < 3 && !(OPEN && n > 0)) {      // (uniform; bridged, two segments can make a ring of three)
     if (tid == 0) {
       centroids[2 * (size_t)pl] = 0; centroids[2 * (size_t)pl + 1] = 0; areas[pl] = 0; nloops[pl] = 0; ring_n[pl] = 0;
       if (areas_total) areas_total[pl] = 0;      // an empty section of the area scan is legal (plane past a ragged cut)
@@ -411,13 +418,38 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     }
     return;
   }
+  // The two vertices of every start edge are asked for here, behind the records and in front of the join, which never touches a
+  // coordinate: they arrive while the hash table fills.  (n >= 1 from here on: every sg[c] is a record of this run, its keys valid.)
+  double vl[PER][3], vh[PER][3];
+#pragma unroll
+  for (int c = 0; c < PER; ++c) {
+    const double* pl_ = vb + 3 * (size_t)sg[c].s_lo;
+    const double* ph_ = vb + 3 * (size_t)sg[c].s_hi;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { vl[c][k] = pl_[k]; vh[c][k] = ph_[k]; }
+  }
+  if (tid == 0) { n_loops = 0; bad = 0; }
+  for (int i = tid; i < HASH; i += SH_LINK_THREADS) table[i] = -1;
+#pragma unroll
+  for (int c = 0; c < PER; ++c) {
+    const int i = tid + c * SH_LINK_THREADS;
+    if (i < n) {
+      skey[i] = ((unsigned long long)sg[c].s_lo << 32) | sg[c].s_hi;
+      lab[i] = ((unsigned long long)sg[c].e_lo << 32) | sg[c].e_hi;
+    }
+  }
+  __syncthreads();
   for (int i = tid; i < n; i += SH_LINK_THREADS) {
     uint32_t h = hash_key64(skey[i]) & (HASH - 1);
     while (atomicCAS(&table[h], -1, i) != -1) h = (h + 1) & (HASH - 1);
   }
+  // the start points (seg_start_point's expression on the vertices asked for above), kept in registers until the ring is placed
+  double px[PER], py[PER];
+#pragma unroll
+  for (int c = 0; c < PER; ++c) seg_point_of(vl[c], vh[c], zpl, &px[c], &py[c]);
   __syncthreads();
   for (int i = tid; i < n; i += SH_LINK_THREADS) {
-    unsigned long long k = bufA[i];
+    unsigned long long k = lab[i];
     uint32_t h = hash_key64(k) & (HASH - 1);
     int t, found = -1;
     while ((t = table[h]) != -1) {
@@ -429,14 +461,13 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
   }
   __syncthreads();
   // Open contours, bridge mode (k_open.h): only a plane with a dead end goes this way.  The scratch is what the jumping below
-  // initialises anew -- jmpA (chain ends, matches), jmpB (counters), offB (predecessor counts), bufB (the hash table: end points).
+  // initialises anew -- jmp (chain ends, matches, counters; the hash table is done with), rk (predecessor counts) -- and open_pts.
   const bool bridging = OPEN && (bad || n < 3);      // (uniform; fewer than three segments without a dead end: a cycle of one or two)
   int n2 = n;                                     // nodes of the graph: the segments, then the bridges
   if (bridging) {
-    constexpr int E = SH_MAXLOOPS;
-    double* pts = (double*)bufB;
-    n2 = bridge_open_chains<SH_LINK_THREADS>(n, CAP, E, skey, bufA, nxt, offB, jmpB, jmpA, jmpA + E, jmpA + 2 * E, jmpA + 3 * E, jmpA + 4 * E,
-                                             jmpA + 5 * E, pts, pts + E, pts + 2 * E, pts + 3 * E, vb, zpl, oc.max_gap);
+    double* pts = open_pts;
+    n2 = bridge_open_chains<SH_LINK_THREADS>(n, CAP, E, skey, lab, nxt, rk, jmp + 6 * E, jmp, jmp + E, jmp + 2 * E, jmp + 3 * E, jmp + 4 * E,
+                                             jmp + 5 * E, pts, pts + E, pts + 2 * E, pts + 3 * E, vb, zpl, oc.max_gap);
     if (n2 < 0) {      // more chain ends than one wave matches, or no room for the bridges: the overflow tier's join takes the plane
       if (tid == 0) {
         if (many.list) many.list[atomicAdd(many.n, 1)] = pl;
@@ -452,30 +483,44 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
   // Joining a stretch with the one behind it keeps the smaller key (its own on a tie: a stretch longer than the loop meets
   // the same node again), so once the stretches cover the loop every node knows the loop's canonical start (B-1: the
   // minimum edge key) and its forward distance to it.
-  unsigned long long* labA = bufA;
-  unsigned long long* labB = bufB;
-  int* ja = jmpA; int* jb = jmpB;
-  int* ra = offA; int* rb = offB;
-  for (int i = tid; i < n2; i += SH_LINK_THREADS) { labA[i] = skey[i]; ja[i] = nxt[i]; ra[i] = 0; }
+  // A lane keeps the (label, jump, rank) of its own nodes in registers from round to round and reads only the triples of the nodes
+  // it jumps to; the arrays are single, so a round is: read, barrier, write, barrier -- one barrier more than with ping-pong copies,
+  // for 13 planes on a CU instead of 9 (measured: steps 1 and 2 alone were slower than the four-wave join, with this a fifth faster).
+  // (A slot past the node count reads node 0 and writes nothing, a slot no lane uses is skipped: a round's reads are one batch.)
+  unsigned long long la[PER];
+  int jc[PER], rc[PER];
+#pragma unroll
+  for (int c = 0; c < PER; ++c) {
+    const int i = tid + c * SH_LINK_THREADS;
+    la[c] = 0ull; jc[c] = 0; rc[c] = 0;
+    if (i < n2) { la[c] = skey[i]; jc[c] = nxt[i]; lab[i] = la[c]; jmp[i] = jc[c]; rk[i] = 0; }
+  }
   __syncthreads();
+  const int nper = (n2 + SH_LINK_THREADS - 1) / SH_LINK_THREADS;      // (uniform) slots of a lane in use: one for most planes
   for (int span = 1; span < n2; span <<= 1) {
-    for (int i = tid; i < n2; i += SH_LINK_THREADS) {
-      const int j = ja[i];
-      const unsigned long long a = labA[i], c = labA[j];
-      const bool own = a <= c;
-      labB[i] = own ? a : c;
-      rb[i] = own ? ra[i] : span + ra[j];
-      jb[i] = ja[j];
+    unsigned long long o[PER] = {};
+    int rj[PER] = {}, jj[PER] = {};
+#pragma unroll
+    for (int c = 0; c < PER; ++c)
+      if (c < nper) { const int j = jc[c]; o[c] = lab[j]; rj[c] = rk[j]; jj[c] = jmp[j]; }
+    __syncthreads();      // (the reads are waited for here, all at once)
+#pragma unroll
+    for (int c = 0; c < PER; ++c) {
+      const int i = tid + c * SH_LINK_THREADS;
+      if (i < n2) {
+        const bool own = la[c] <= o[c];
+        la[c] = own ? la[c] : o[c];
+        rc[c] = own ? rc[c] : span + rj[c];
+        jc[c] = jj[c];
+        lab[i] = la[c]; rk[i] = rc[c]; jmp[i] = jc[c];
+      }
     }
     __syncthreads();
-    unsigned long long* tl = labA; labA = labB; labB = tl;
-    int* tj = ja; ja = jb; jb = tj;
-    int* tr = ra; ra = rb; rb = tr;
   }
-  // labA[i] = start key of i's loop, ra[i] = forward steps from i to the start node (0: i is a start node).  Bridging: ja[i] has
+  // lab[i] = start key of i's loop, rk[i] = forward steps from i to the start node (0: i is a start node).  Bridging: jmp[i] has
   // saturated at the tail of i's chain if i is on one (the tail keeps its self-loop), and a cycle of fewer than three is no loop.
   for (int i = tid; i < n2; i += SH_LINK_THREADS)
-    if (ra[i] == 0 && (!bridging || (nxt[ja[i]] != ja[i] && ra[nxt[i]] >= 2))) {
+    if (rk[i] == 0 && (!bridging || (nxt[jmp[i]] != jmp[i] && rk[nxt[i]] >= 2))) {
       int l = atomicAdd(&n_loops, 1);
       if (l < SH_MAXLOOPS) l_start[l] = i;
     }
@@ -499,7 +544,7 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     int off = 0;
     for (int l = 0; l < nl; ++l) {
       int s = l_start[l];
-      int L = ra[nxt[s]] + 1;
+      int L = rk[nxt[s]] + 1;
       l_len[l] = L; l_off[l] = off; off += L;
       l_key[l] = skey[s];
     }
@@ -512,7 +557,7 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
       for (int i = tid; i < n; i += SH_LINK_THREADS)
         if (nxt[i] == i || nxt[i] >= n) {
           bool kept = false;
-          for (int q = 0; q < nl; ++q) kept |= l_key[q] == labA[i];
+          for (int q = 0; q < nl; ++q) kept |= l_key[q] == lab[i];
           atomicAdd(&oc.stats[2 * b + (kept ? 0 : 1)], 1);
         }
     if (nl == 0) {      // nothing left: as a section without segments
@@ -523,37 +568,38 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
       }
       return;
     }
-    __syncthreads();      // (labA is the ring's x from here on)
+    __syncthreads();      // (lab is the ring's x from here on)
   }
   // ring placement: position from start = (L - r) mod L
   // label buffers are dead from here on: reuse them for the ordered ring
-  double* rx = (double*)bufA;
-  double* ry = (double*)bufB;
-  int my_pos[(CAP + SH_LINK_THREADS - 1) / SH_LINK_THREADS];
-  {
-    int c = 0;
-    for (int i = tid; i < n2; i += SH_LINK_THREADS, ++c) {
-      const unsigned long long key = labA[i];
+  double* rx = (double*)lab;
+  double* ry = (double*)skey;
+  int my_pos[PER];
+#pragma unroll
+  for (int c = 0; c < PER; ++c) {
+    const int i = tid + c * SH_LINK_THREADS;
+    my_pos[c] = -1;
+    if (i < n2) {
+      const unsigned long long key = lab[i];
       int l = -1;
       for (int q = 0; q < nl; ++q) if (l_key[q] == key) { l = q; break; }      // (one or two loops per section)
       const int L = l >= 0 ? l_len[l] : 1;
-      const int r = ra[i];
+      const int r = rk[i];
       const int pos = r == 0 ? 0 : L - r;
       my_pos[c] = l < 0 ? -1 : l_off[l] + pos;
+      if (OPEN && i >= n) {      // a bridge starts where its tail ends: the point of its key, as the section computes it
+        const unsigned long long kv = skey[i];
+        seg_start_point(vb, (uint32_t)(kv >> 32), (uint32_t)kv, zpl, &px[c], &py[c]);
+      }
     }
   }
   __syncthreads();
-  {
-    int c = 0;
-    for (int i = tid; i < n2; i += SH_LINK_THREADS, ++c)
-      if (my_pos[c] >= 0 && my_pos[c] < n2) {
-        if (!OPEN || i < n) { const Seg sg = sp[i]; seg_start_point(vb, sg.s_lo, sg.s_hi, zpl, &rx[my_pos[c]], &ry[my_pos[c]]); }
-        else { const unsigned long long kv = skey[i]; seg_start_point(vb, (uint32_t)(kv >> 32), (uint32_t)kv, zpl, &rx[my_pos[c]], &ry[my_pos[c]]); }      // a bridge
-      }
-  }
+#pragma unroll
+  for (int c = 0; c < PER; ++c)
+    if (my_pos[c] >= 0 && my_pos[c] < n2) { rx[my_pos[c]] = px[c]; ry[my_pos[c]] = py[c]; }
   __syncthreads();
-  // AABB over every loop vertex (trimesh Path2D.centroid, slice.py:38) by the last wave, while the other three take the loops
-  // (all four waves reducing four doubles each through the LDS crossbar, then 64-bit LDS atomics, was a quarter of the kernel).
+  // AABB over every loop vertex (trimesh Path2D.centroid, slice.py:38) by the second wave, while the first takes the loops one
+  // after the other (every wave reducing four doubles through the LDS crossbar, then 64-bit LDS atomics, was a quarter of the kernel).
   // The ordered ring in LDS holds every crossing point once -- min / max do not care about the order; a section with
   // segments on no closed loop is flagged above and its numbers are void anyway.
   const int lane = tid & 63, wave = tid >> 6;
@@ -570,7 +616,7 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
     }
     if (lane == 0) { bbv[0] = x0; bbv[1] = x1; bbv[2] = y0; bbv[3] = y1; }
   } else {
-    // per-loop shoelace area and the selection score: one wave per loop, lane-strided terms in ring order, fixed shuffle
+    // per-loop shoelace area and the selection score: one 64-lane wave per loop, lane-strided terms in ring order, fixed shuffle
     // tree (deterministic; one lane walking the ring alone cost as much as the whole join)
     for (int l = wave; l < nl; l += SH_LINK_THREADS / 64 - 1) {
       const int o = l_off[l], L = l_len[l];
@@ -627,9 +673,9 @@ __device__ inline void slice_link_plane(const int pl, int N, const int* __restri
 }
 
 // small tier: one workgroup per plane.  Large tier: a small grid sweeps all planes and works on the few (usually none)
-// with more than SH_SMALLSEG segments -- a workgroup per plane would pay its 70 KB LDS allocation 40 000 times for nothing.
+// with more than SH_SMALLSEG segments -- a workgroup per plane would pay its 29 KB LDS allocation 40 000 times for nothing.
 template <bool OPEN>
-__global__ void __launch_bounds__(SH_LINK_THREADS)
+__global__ void __launch_bounds__(SH_LINK_THREADS, OPEN ? 6 : 7)      // (7 waves per SIMD = 72 VGPRs: the 13 planes the LDS admits are 26 waves on a CU; bridge mode's LDS admits 12)
 k_slice_link(SliceSets sets, int B, int* __restrict__ err) {
   // Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 names a group of workgroups that share an L2): with the batch a
   // multiple of 8, workgroup id joins a plane of humerus (id % 8) + 8 j, so the vertices of 1/8 of the batch -- what the crossing
