@@ -941,6 +941,52 @@ typedef struct sh_shell {
 int sh_mesh_topology(sh_ctx*, const sh_topology_options* options, sh_topology* info /* B, host, nullable */,
                      sh_shell* shells /* B x max_shells, host, nullable */);
 
+/* ---- vertex normals and discrete curvatures of the resident batch ---------------------------------------------------------------------
+ * What the incidence of sh_mesh_topology is for (k_vert.h): per face its normal, area and angles, per vertex a unit normal that is
+ * continuous across faces (trimesh's `vertex_normals`), the angle defect (`vertex_defects`), the Gaussian and the mean curvature, and
+ * both after Jacobi rounds of smoothing.  Everything is float64, operation by operation; corners are widened from the resident "verts"
+ * as sh_mass_properties widens them; indices are local to the mesh; "degenerate" and "row" mean what they mean in sh_mesh_topology.
+ *   face record  "vert.face", 10 doubles per face at 10 foff[b]: n[3], A2, angle[3], cot[3].  n = cross3(P1 - P0, P2 - P0),
+ *                A2 = sqrt(dot3(n, n)) (the expression of sh_mass_properties); at corner k, e1 = P[(k + 1) % 3] - P[k],
+ *                e2 = P[(k + 2) % 3] - P[k], d = dot3(e1, e2), angle[k] = atan2(A2, d), cot[k] = d / A2.  A degenerate face, or one whose
+ *                A2 is 0.0 or not finite, is FLAT: ten zeros, and it contributes to no vertex.
+ *   vertex sums  every accumulator starts at 0.0 and adds one term per non-flat face f of the row of v in ASCENDING face index (the
+ *                order is part of the definition); k is the corner of f that is v.  s = sum A2_f, area = s / 6.0; angle_sum = sum
+ *                angle_f[k]; N = sum n_f (SH_VERT_WEIGHT_AREA) or sum (n_f / A2_f) * angle_f[k] component by component
+ *                (SH_VERT_WEIGHT_ANGLE: trimesh's default); L = sum (cot_f[(k + 1) % 3] * (P_k - P_(k+2)) + cot_f[(k + 2) % 3] *
+ *                (P_k - P_(k+1))), in each component the two products added to each other first, then to the accumulator.
+ *   results      normal = N / sqrt(dot3(N, N)), three zeros when that root is 0.0 or not finite; defect = (border ? 3.141592653589793 :
+ *                6.283185307179586) - angle_sum; gauss = defect / area; mean = dot3(L, normal) / (4.0 * area); with area == 0.0 defect,
+ *                gauss and mean are 0.0.  With outward normals a sphere of radius R has mean = +1/R and gauss = +1/R^2.
+ *   flags        int32: SH_VERT_USED the row is not empty; SH_VERT_BORDER one of the two slots that touch v in a face of the row is
+ *                SH_ADJ_BORDER; SH_VERT_NONMANIFOLD the same for SH_ADJ_NONMANIFOLD; SH_VERT_FLAT a face of the row was skipped as flat.
+ *   smoothing    smooth_rounds Jacobi rounds on two arrays, for gauss and mean separately: s'[v] = (sum_f A2_f * (((s[f0] + s[f1]) +
+ *                s[f2]) / 3.0)) / (sum_f A2_f), both sums over the non-flat faces of the row in ascending order, 0.0 when the denominator
+ *                is 0.0.  The raw values are kept.  The host enqueues the rounds and looks at nothing in between.
+ *   only atan2   differs between two math libraries: n, A2, cot, area, the flags and, with SH_VERT_WEIGHT_AREA, the normals and mean are
+ *                the same bytes wherever the rule runs.
+ *
+ * Arguments in this order: the context (SH_ERR_ARG); weight SH_VERT_WEIGHT_AREA or SH_VERT_WEIGHT_ANGLE and smooth_rounds in
+ * 0..SH_VERT_MAX_SMOOTH (SH_ERR_ARG); a resident batch and no runs in flight (SH_ERR_STATE); the incidence of THIS batch resident
+ * (SH_ERR_STATE: call sh_mesh_topology first; a topology that ran out of rounds still has its incidence and adjacency and is
+ * accepted).  SH_ERR_NOMEM when the buffers do not fit.  Reads "verts", "faces", the offsets, "topo.vrow", "topo.vface", "topo.adj".
+ * Resident afterwards: "vert.face"; "vert.normal", 3 doubles per vertex at 3 voff[b]; "vert.fields", SH_VERT_FIELDS doubles per vertex:
+ * area, angle_sum, defect, gauss, mean, gauss_smooth, mean_smooth, 0.0 (without a round the smoothed fields equal the raw ones);
+ * "vert.flags"; "vert.status", B int32: SH_ERR_GEOMETRY for a mesh without a non-flat face, whose records are all zero -- never the
+ * batch; and the scratch "vert.a2", "vert.plane", "vert.state".  They are removed together with "topo.*" by the next upload / commit /
+ * sh_store("verts").  Every other buffer keeps its bytes. */
+#define SH_VERT_WEIGHT_AREA  0
+#define SH_VERT_WEIGHT_ANGLE 1
+#define SH_VERT_MAX_SMOOTH   64
+#define SH_VERT_FIELDS       8
+#define SH_VERT_USED         1
+#define SH_VERT_BORDER       2
+#define SH_VERT_NONMANIFOLD  4
+#define SH_VERT_FLAT         8
+int sh_vertex_fields(sh_ctx*, int weight, int smooth_rounds, double* normals /* sumV x 3, host, nullable */,
+                     double* fields /* sumV x SH_VERT_FIELDS, host, nullable */, int32_t* flags /* sumV, host, nullable */,
+                     int32_t* status /* B, host, nullable */);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

@@ -33,6 +33,8 @@ MASS_BLOCK, MS_MAX_STARTS = 256, 64
 SAMPLE_MAX, SAMPLE_THIN_MAX, SAMPLE_BLOCK, THIN_MAX_ROUNDS = 1048576, 65536, 256, 32
 ADJ_BORDER, ADJ_NONMANIFOLD, ADJ_DEGENERATE = -1, -2, -3
 TOPO_MAX_SHELLS, TOPO_MAX_ROUNDS, TOPO_WATERTIGHT, TOPO_CONSISTENT = 65536, 32, 1, 2
+VERT_WEIGHT_AREA, VERT_WEIGHT_ANGLE, VERT_MAX_SMOOTH, VERT_FIELDS = 0, 1, 64, 8
+VERT_USED, VERT_BORDER, VERT_NONMANIFOLD, VERT_FLAT = 1, 2, 4, 8
 
 # ---- the records ------------------------------------------------------------------------------------------------------------------------
 RECORDS = {}      # C name -> (ctypes.Structure, NumPy dtype), in the order of the header
@@ -294,6 +296,7 @@ SIGNATURES = {      # name -> (argtypes, restype, optional)
     "sh_register_multistart": _f(_vp, _vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, optional=True),
     "sh_sample_surface": _f(_vp, _i, _vp, _P(SampleOptions), _vp, _vp, optional=True),
     "sh_mesh_topology": _f(_vp, _P(TopologyOptions), _vp, _vp, optional=True),
+    "sh_vertex_fields": _f(_vp, _i, _i, _vp, _vp, _vp, _vp, optional=True),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -560,6 +560,28 @@ class ProximalHumerus(Bone):
             raise ValueError(f"shells failed with status {int(info['status'])}: the shells were not labelled within {int(info['rounds'])} rounds")
         return self._engine.split(0, largest_only=largest_only)
 
+    # -- vertex normals and discrete curvatures ------------------------------------------------------------------
+    def vertex_normals(self, weight="angle"):
+        """`mesh.vertex_normals` of this bone on the device (Engine.vertex_fields) -> (V, 3) unit normals in CT, weighted by the corners'
+        angles (trimesh's default) or by the faces' areas ("area"); zeros at a vertex no face of non-zero area uses."""
+        self._ensure_loaded()
+        return self._engine.vertex_fields(weight=weight)["normals"]
+
+    def curvature(self, smooth=0):
+        """The discrete curvatures of this bone's vertices (Engine.vertex_fields, area-weighted normals) -> dict: gauss and mean (after
+        `smooth` rounds of averaging when smooth > 0), k1 >= k2 = mean +- sqrt(max(mean^2 - gauss, 0)) the principal curvatures in
+        1/mm (computed here with NumPy), area, defect, normals, and border, the mask of the vertices on an open edge.  With outward
+        normals the head is where k1 and k2 are positive and about equal, the bicipital groove where k2 is negative along a line.
+        Raises ValueError for a mesh without a face of non-zero area."""
+        self._ensure_loaded()
+        r = self._engine.vertex_fields(weight="area", smooth=smooth)
+        if r["status"][0] != 0:
+            raise ValueError(f"curvature failed with status {int(r['status'][0])}: the mesh has no face of non-zero area")
+        gauss, mean = (r["gauss_smooth"], r["mean_smooth"]) if smooth > 0 else (r["gauss"], r["mean"])
+        root = np.sqrt(np.maximum(mean * mean - gauss, 0.0))
+        return dict(gauss=gauss, mean=mean, k1=mean + root, k2=mean - root, area=r["area"], defect=r["defect"], normals=r["normals"],
+                    border=(r["flags"] & _lib.VERT_BORDER) != 0)
+
     # -- inside tests: generalized winding numbers -------------------------------------------------------------
     def winding_number(self, points):
         """The generalized winding number of the mesh about `points` (n, 3) in the CURRENT coordinate system -> float64 (n,), on the

@@ -1,8 +1,8 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface) and the mesh topology (sh_mesh_topology).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology) and the vertex fields (sh_vertex_fields).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
@@ -39,6 +39,12 @@ struct RayKey; struct CpPart;
   X(topo_vrow, "topo.vrow", int, 4) X(topo_vface, "topo.vface", int, 4) X(topo_adj, "topo.adj", int, 4) X(topo_label, "topo.label", int, 4) \
   X(topo_info, "topo.info", sh_topology, 4) X(topo_shells, "topo.shells", sh_shell, 4) X(topo_state, "topo.state", int, 4)         \
   X(topo_cursor, "topo.cursor", int, 4) X(topo_tmp, "topo.tmp", int, 4) X(topo_p, "topo.p", int, 4)
+// the face records, the unit normals, the fields, the flags and the status per mesh; scratch: A2 per face, the four planes of the
+// smoothing (two arrays of gauss and mean), one int32 per mesh (a face that is not flat)
+#define VERT_BUFS(X)                                                                                                               \
+  X(vert_face, "vert.face", double, 8) X(vert_normal, "vert.normal", double, 8) X(vert_fields, "vert.fields", double, 8)           \
+  X(vert_flags, "vert.flags", int, 4) X(vert_status, "vert.status", int, 4) X(vert_a2, "vert.a2", double, 8)                       \
+  X(vert_plane, "vert.plane", double, 8) X(vert_state, "vert.state", int, 4)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -49,6 +55,8 @@ SH_QUERY_LIST(Mass, MASS_BUFS)
 SH_BUF_LIST(Ms, MS_BUFS)      // (beside an IcpView: no mesh of its own)
 SH_QUERY_LIST(Samp, SAMP_BUFS)
 SH_QUERY_LIST(Topo, TOPO_BUFS)
+SH_BUF_LIST(Vert, VERT_BUFS)
+using VertView = BufJoin<MeshBufs, TopoBufs, VertBufs>;      // (the mesh, the incidence and adjacency it reads, and its own)
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -60,6 +68,7 @@ constexpr int AR_ICP_TERMS = 32, AR_ICP_TSTRIDE = 20;                           
 constexpr int AR_MASS_TERMS = 24;                                                 // SH_MASS_TERMS
 constexpr int AR_SAMP_CHUNK = 256, AR_SAMP_HEAD = 64;                             // SH_SAMP_CHUNK, SH_SAMP_HEAD
 constexpr int AR_TOPO_BLOCK = 256, AR_TOPO_HEAD = 64;                             // SH_TOPO_BLOCK, SH_TOPO_HEAD
+constexpr int AR_VERT_BLOCK = 256, AR_VERT_FACE = 10;                             // SH_VERT_BLOCK, SH_VTX_FACE
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -219,6 +228,18 @@ inline TopoPlan topo_plan(int B, int max_shells, long long maxF, long long sumV,
   return {(int)tiles_of(maxF, AR_TOPO_BLOCK), z};
 }
 
+// Vertex fields.  "vert.face" has AR_VERT_FACE doubles per face (mesh b at 10 foff[b]) and "vert.a2" one; "vert.normal" three doubles per
+// vertex (mesh b at 3 voff[b]), "vert.fields" SH_VERT_FIELDS, "vert.flags" one int32; "vert.plane" four planes of sumV doubles: the two
+// arrays of the smoothing, gauss and mean each; "vert.status" and "vert.state" one int32 per mesh.
+struct VertPlan { int fblocks, vblocks; VertBytes bytes; };      // face and vertex blocks of the largest mesh
+inline VertPlan vert_plan(int B, long long maxV, long long maxF, long long sumV, long long sumF) {
+  const size_t f = (size_t)(sumF > 0 ? sumF : 1), v = (size_t)(sumV > 0 ? sumV : 1);
+  VertBytes z;
+  z.vert_face = f * AR_VERT_FACE * 8; z.vert_normal = v * 24; z.vert_fields = v * SH_VERT_FIELDS * 8; z.vert_flags = v * 4;
+  z.vert_status = (size_t)B * 4; z.vert_a2 = f * 8; z.vert_plane = 4 * v * 8; z.vert_state = (size_t)B * 4;
+  return {(int)tiles_of(maxF, AR_VERT_BLOCK), (int)tiles_of(maxV, AR_VERT_BLOCK), z};
+}
+
 // Multi-start registration: the coarse stage is sh_register_points on Qc points, the fine stage on all Q, both on the "icp.*" buffers,
 // which take the larger of the two sizes field by field (the split of the walk, and so "icp.cp_part", may be larger for the fewer points).
 inline int ms_coarse_count(int Q, int coarse_points) { return coarse_points == 0 || coarse_points > Q ? Q : coarse_points; }
@@ -282,6 +303,16 @@ inline ArthroError precheck_topology(const sh_topology_options* opt, const Arthr
   if (opt->max_shells < 1 || opt->max_shells > SH_TOPO_MAX_SHELLS || opt->max_rounds < 1 || opt->max_rounds > SH_TOPO_MAX_ROUNDS || opt->reserved != 0)
     return {SH_ERR_ARG, "bad options (max_shells in 1..65536, max_rounds in 1..32, reserved 0)"};
   return resident(f);
+}
+
+// incidence: "topo.vrow", "topo.vface" and "topo.adj" of the resident batch are there (a new batch removes them)
+inline ArthroError precheck_vertex_fields(int weight, int smooth_rounds, bool incidence, const ArthroFacts& f) {
+  if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
+  if ((weight != SH_VERT_WEIGHT_AREA && weight != SH_VERT_WEIGHT_ANGLE) || smooth_rounds < 0 || smooth_rounds > SH_VERT_MAX_SMOOTH)
+    return {SH_ERR_ARG, "bad argument (weight 0 or 1, smooth_rounds in 0..64)"};
+  if (const ArthroError e = resident(f); e.code) return e;
+  if (!incidence) return {SH_ERR_STATE, "no incidence of the resident batch: call sh_mesh_topology first"};
+  return arthro_ok();
 }
 
 static const char* const AR_ICP_OPTIONS = "options (metric 0 or 1, max_iter in 1..64, reject > 0, tol >= 0 and finite)";

@@ -1,7 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
 // point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), the surface samples, sh_sample_surface
-// (k_sample.h), and the mesh topology, sh_mesh_topology (k_topo.h).
+// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), and the vertex fields, sh_vertex_fields (k_vert.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -15,6 +15,7 @@ static_assert(AR_ICP_TERMS == SH_ICP_TERMS && AR_ICP_TSTRIDE == SH_ICP_TSTRIDE, 
 static_assert(AR_MASS_TERMS == SH_MASS_TERMS, "sh_query.h: mass terms");
 static_assert(AR_SAMP_CHUNK == SH_SAMP_CHUNK && AR_SAMP_HEAD == SH_SAMP_HEAD, "sh_query.h: sample chunk, head of samp.state");
 static_assert(AR_TOPO_BLOCK == SH_TOPO_BLOCK && AR_TOPO_HEAD == SH_TOPO_HEAD, "sh_query.h: topology block, head of topo.state");
+static_assert(AR_VERT_BLOCK == SH_VERT_BLOCK && AR_VERT_FACE == SH_VTX_FACE, "sh_query.h: vertex block, doubles of a face record");
 
 // ---- rays, every hit (k_rays.h); the anatomic-neck rays also read the last run ----
 // count -> scan -> the total to the host -> "ray.pool" -> fill -> sort -> copies back.  "ray.rays" (and "ray.status" with `box`) are filled
@@ -281,6 +282,34 @@ int sh_mesh_topology(sh_ctx* c, const sh_topology_options* opt, sh_topology* inf
   LAUNCH(c, "k_topo_finish", k_topo_finish, meshes, dim3(256), v.foff, (const int*)v.topo_state, (const int*)v.topo_tmp, (int*)v.topo_shells, max_shells, v.topo_info);
   if (info) HIPCHK(c, hipMemcpyAsync(info, v.topo_info, plan.bytes.topo_info, hipMemcpyDeviceToHost, c->stream));
   if (shells) HIPCHK(c, hipMemcpyAsync(shells, v.topo_shells, plan.bytes.topo_shells, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- vertex normals and discrete curvatures (k_vert.h) ----
+// a zeroed word per mesh -> face -> gather -> smooth_rounds x smooth -> pack; the host looks at nothing in between
+int sh_vertex_fields(sh_ctx* c, int weight, int smooth_rounds, double* normals, double* fields, int32_t* flags, int32_t* status) {
+  const bool incidence = c && c->at("topo.vrow") && c->at("topo.vface") && c->at("topo.adj");
+  if (const ArthroError e = precheck_vertex_fields(weight, smooth_rounds, incidence, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_vertex_fields", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B;
+  const VertPlan plan = vert_plan(B, c->maxV, c->maxF, c->sumV, c->sumF);
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  const VertView v = view_of<VertView>(c);
+  HIPCHK(c, hipMemsetAsync(v.vert_state, 0, plan.bytes.vert_state, c->stream));
+  const dim3 fblocks((unsigned)plan.fblocks, (unsigned)B), vblocks((unsigned)plan.vblocks, (unsigned)B), lanes(SH_VERT_BLOCK);
+  const long long sumV = c->sumV;
+  LAUNCH(c, "k_vert_face", k_vert_face, fblocks, lanes, v.verts, v.faces, v.voff, v.foff, v.vert_face, v.vert_a2, v.vert_state);
+  LAUNCH(c, "k_vert_gather", k_vert_gather, vblocks, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_vrow, (const int*)v.topo_vface, (const int*)v.topo_adj,
+         (const double*)v.vert_face, weight, sumV, v.vert_normal, v.vert_fields, v.vert_flags, v.vert_plane);
+  for (int r = 0; r < smooth_rounds; ++r)
+    LAUNCH(c, "k_vert_smooth", k_vert_smooth, vblocks, lanes, v.faces, v.voff, v.foff, (const int*)v.topo_vrow, (const int*)v.topo_vface, (const double*)v.vert_a2, sumV, r,
+           v.vert_plane);
+  LAUNCH(c, "k_vert_pack", k_vert_pack, vblocks, lanes, v.voff, (const double*)v.vert_plane, sumV, smooth_rounds, (const int*)v.vert_state, v.vert_fields, v.vert_status);
+  if (normals) HIPCHK(c, hipMemcpyAsync(normals, v.vert_normal, (size_t)sumV * 24, hipMemcpyDeviceToHost, c->stream));
+  if (fields) HIPCHK(c, hipMemcpyAsync(fields, v.vert_fields, (size_t)sumV * SH_VERT_FIELDS * 8, hipMemcpyDeviceToHost, c->stream));
+  if (flags) HIPCHK(c, hipMemcpyAsync(flags, v.vert_flags, (size_t)sumV * 4, hipMemcpyDeviceToHost, c->stream));
+  if (status) HIPCHK(c, hipMemcpyAsync(status, v.vert_status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -1669,4 +1669,104 @@ SH_HD float topo_dec(unsigned k) {
   return x;
 }
 
+// ---- vertex normals and discrete curvatures of the resident batch (include/shoulder_hip.h sh_vertex_fields; k_vert.h) ---------------
+// float64, operation by operation in the written order (-ffp-contract=off), restated by tests/vert_oracle.py.  Everything but atan2 is
+// + - x / sqrt, so only the fields an angle enters differ between two math libraries.  The flags and the weights are the header's
+// SH_VERT_* (k_vert.h holds them equal).
+#define SH_VTX_FACE 10          // doubles of a face record: n[3], A2, angle[3], cot[3]
+#define SH_VTX_FIELDS 8         // doubles of a vertex: area, angle_sum, defect, gauss, mean, gauss_smooth, mean_smooth, 0.0
+#define SH_VTX_USED 1
+#define SH_VTX_BORDER 2
+#define SH_VTX_NONMANIFOLD 4
+#define SH_VTX_FLAT 8
+#define SH_VTX_ANGLE 1          // the weight of the normals: 0 the faces' areas, 1 the corners' angles
+
+SH_HD bool vert_finite(double x) { return x - x == 0.0; }
+
+// the widened corners of face f of a mesh
+SH_HD void vert_corners(const float* verts, const int* f, double P[3][3]) {
+  for (int k = 0; k < 3; ++k)
+    for (int c = 0; c < 3; ++c) P[k][c] = (double)verts[3 * (size_t)f[k] + c];
+}
+
+// The record of a face with the widened corners P: n, A2, the three angles and cotangents.  -> 1 and ten zeros when the face is flat
+// (degenerate by its indices, or A2 zero or not finite).
+SH_HD int vert_face(const double P[3][3], bool degenerate, double* rec /* SH_VTX_FACE */) {
+  const double ab[3] = {P[1][0] - P[0][0], P[1][1] - P[0][1], P[1][2] - P[0][2]};
+  const double ac[3] = {P[2][0] - P[0][0], P[2][1] - P[0][1], P[2][2] - P[0][2]};
+  double n[3];
+  const double A2 = face_area2(ab, ac, n);
+  if (degenerate || A2 == 0.0 || !vert_finite(A2)) {
+    for (int i = 0; i < SH_VTX_FACE; ++i) rec[i] = 0.0;
+    return 1;
+  }
+  rec[0] = n[0]; rec[1] = n[1]; rec[2] = n[2]; rec[3] = A2;
+  for (int k = 0; k < 3; ++k) {
+    const int k1 = k == 2 ? 0 : k + 1, k2 = k == 0 ? 2 : k - 1;
+    const double e1[3] = {P[k1][0] - P[k][0], P[k1][1] - P[k][1], P[k1][2] - P[k][2]};
+    const double e2[3] = {P[k2][0] - P[k][0], P[k2][1] - P[k][1], P[k2][2] - P[k][2]};
+    const double d = dot3(e1, e2);
+    rec[4 + k] = atan2(A2, d);
+    rec[7 + k] = d / A2;
+  }
+  return 0;
+}
+
+// the corner of the non-degenerate face f that is v (v is one of them: f comes from v's row)
+SH_HD int vert_corner(const int* f, int v) { return f[0] == v ? 0 : f[1] == v ? 1 : 2; }
+
+// Vertex v of a mesh from its ascending row of n faces: the sums in the row's order, then normal[3], fields[0 .. 4] = area, angle_sum,
+// defect, gauss, mean, and the flags.  `adj` and `frec` are the mesh's "topo.adj" and "vert.face".
+SH_HD void vert_gather(const float* verts, const int* faces, const int* adj, const double* frec, const int* row, int n, int v, int weight,
+                       double* normal, double* fields, int* flags_out) {
+  double s = 0.0, angle_sum = 0.0, N[3] = {0.0, 0.0, 0.0}, L[3] = {0.0, 0.0, 0.0};
+  int flags = n > 0 ? SH_VTX_USED : 0;
+  const double Pv[3] = {(double)verts[3 * (size_t)v], (double)verts[3 * (size_t)v + 1], (double)verts[3 * (size_t)v + 2]};      // P_k of every face of the row
+  for (int i = 0; i < n; ++i) {
+    const int f = row[i];
+    const int* fc = faces + 3 * (size_t)f;
+    const int k = vert_corner(fc, v), k1 = k == 2 ? 0 : k + 1, k2 = k == 0 ? 2 : k - 1;
+    const int a0 = adj[3 * (size_t)f + k], a1 = adj[3 * (size_t)f + k2];      // the slots of the edges {v, next} and {previous, v}
+    if (a0 == SH_TOPO_BORDER || a1 == SH_TOPO_BORDER) flags |= SH_VTX_BORDER;
+    if (a0 == SH_TOPO_NONMANIFOLD || a1 == SH_TOPO_NONMANIFOLD) flags |= SH_VTX_NONMANIFOLD;
+    const double* r = frec + SH_VTX_FACE * (size_t)f;
+    const double A2 = r[3];
+    if (A2 == 0.0) { flags |= SH_VTX_FLAT; continue; }
+    s += A2;
+    angle_sum += r[4 + k];
+    const double w = r[4 + k];
+    for (int c = 0; c < 3; ++c) N[c] += weight == SH_VTX_ANGLE ? (r[c] / A2) * w : r[c];
+    const float *p1 = verts + 3 * (size_t)fc[k1], *p2 = verts + 3 * (size_t)fc[k2];      // the corners again, by index: no array indexed by k
+    const double c1 = r[7 + k1], c2 = r[7 + k2];
+    for (int c = 0; c < 3; ++c) L[c] += c1 * (Pv[c] - (double)p2[c]) + c2 * (Pv[c] - (double)p1[c]);
+  }
+  const double len = sqrt(dot3(N, N));
+  const bool unit = len != 0.0 && vert_finite(len);
+  for (int c = 0; c < 3; ++c) normal[c] = unit ? N[c] / len : 0.0;
+  const double area = s / 6.0;
+  const double defect = ((flags & SH_VTX_BORDER) ? 3.141592653589793 : 6.283185307179586) - angle_sum;
+  fields[0] = area; fields[1] = angle_sum;
+  fields[2] = area == 0.0 ? 0.0 : defect;
+  fields[3] = area == 0.0 ? 0.0 : defect / area;
+  fields[4] = area == 0.0 ? 0.0 : dot3(L, normal) / (4.0 * area);
+  *flags_out = flags;
+}
+
+// One Jacobi round of the smoothing at vertex v: the area-weighted mean over the non-flat faces of the row of the faces' means of the
+// old values, for two planes at once (g: gauss, m: mean).  `a2` is the mesh's "vert.a2" (0.0: flat).
+SH_HD void vert_smooth(const int* faces, const double* a2, const int* row, int n, const double* g, const double* m, double* g_out, double* m_out) {
+  double den = 0.0, sg = 0.0, sm = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const int f = row[i];
+    const double A2 = a2[f];
+    if (A2 == 0.0) continue;
+    const int* fc = faces + 3 * (size_t)f;
+    den += A2;
+    sg += A2 * (((g[fc[0]] + g[fc[1]]) + g[fc[2]]) / 3.0);
+    sm += A2 * (((m[fc[0]] + m[fc[1]]) + m[fc[2]]) / 3.0);
+  }
+  *g_out = den == 0.0 ? 0.0 : sg / den;
+  *m_out = den == 0.0 ? 0.0 : sm / den;
+}
+
 }  // namespace sh

@@ -813,6 +813,45 @@ class Engine:
             out.append((np.ascontiguousarray(verts[uniq[order]]), np.ascontiguousarray(rank[np.ravel(inv)].reshape(-1, 3).astype(np.int32))))
         return out
 
+    # ---- vertex normals and discrete curvatures of the resident batch (include/shoulder_hip.h sh_vertex_fields) -------------------
+    def _has_buffer(self, name):
+        n, e = ctypes.c_size_t(), ctypes.c_int()
+        return self.L.sh_buffer_info(self.h, name.encode(), ctypes.byref(n), ctypes.byref(e)) == 0
+
+    def vertex_fields(self, weight="area", smooth=0):
+        """Per vertex of every resident mesh, in one device pass over the incidence of topology() (run first when it is not resident
+        for this batch) -> dict: normals (sumV, 3) unit, weighted by the faces' areas or by the corners' angles (weight "area" /
+        "angle": trimesh's default), zeros where undefined; area (a third of the incident faces'), angle_sum, defect (2 pi, or pi on a
+        border, minus angle_sum: trimesh's vertex_defects), gauss = defect / area, mean (cotangent Laplacian along the normal: +1/R on
+        a sphere with outward normals), gauss_smooth and mean_smooth after `smooth` (0..64) Jacobi rounds of area-weighted averaging
+        (the raw fields without a round), flags (int32: _lib.VERT_USED, VERT_BORDER, VERT_NONMANIFOLD, VERT_FLAT), status (B,): 0 or
+        SH_ERR_GEOMETRY for a mesh without a face of non-zero area, and voff (B + 1,), the vertex offsets of the meshes in all of these.
+        Resident afterwards: "vert.face" (face_normals), "vert.normal", "vert.fields", "vert.flags", "vert.status"."""
+        weights = {"area": _lib.VERT_WEIGHT_AREA, "angle": _lib.VERT_WEIGHT_ANGLE}
+        w = weights.get(weight, weight)
+        if not isinstance(w, (int, np.integer)):
+            raise ValueError("weight must be 'area' or 'angle'")
+        if self.B >= 1 and not self._has_buffer("topo.vrow"):
+            self.topology()
+        V = int(self.voff[-1]) if self.B >= 1 else 0
+        normals, fields = np.zeros((V, 3)), np.zeros((V, _lib.VERT_FIELDS))
+        flags, status = np.zeros(V, np.int32), np.zeros(max(self.B, 0), np.int32)
+        self._chk(self.L.sh_vertex_fields(self.h, int(w), int(smooth), _ptr(normals), _ptr(fields), _ptr(flags), _ptr(status)))
+        out = dict(normals=normals, flags=flags, status=status, voff=np.array(self.voff, dtype=np.int64))
+        for i, n in enumerate(("area", "angle_sum", "defect", "gauss", "mean", "gauss_smooth", "mean_smooth")):
+            out[n] = np.ascontiguousarray(fields[:, i])
+        return out
+
+    def face_normals(self, b):
+        """The resident face records of mesh b after vertex_fields() -> (unit normals (F, 3), areas (F,), angles (F, 3)): trimesh's
+        face_normals, area_faces and face_angles; zeros for a face of no area."""
+        f0, f1 = self._face_range(b)
+        rec = self.fetch("vert.face", np.float64, (int(self.foff[-1]), 10))[f0:f1]
+        a2 = rec[:, 3]
+        with np.errstate(all="ignore"):
+            unit = np.where(a2[:, None] != 0.0, rec[:, :3] / a2[:, None], 0.0)
+        return unit, a2 / 2.0, rec[:, 4:7].copy()
+
     # ---- multi-start registration (include/shoulder_hip.h sh_register_multistart) -----------------------------------------------
     def principal_starts(self, points, rolls=8, with_ratios=False):
         """Starting transforms for register_multistart from principal frames -> (B, 2 * rolls, 4, 4).  The mesh frame is shell_centroid
