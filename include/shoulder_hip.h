@@ -37,7 +37,8 @@ typedef enum sh_status {
                            counts returned say how large), more than 1 024 closed loops in ONE section, and a growth
                            that is needed while a second run is in flight (collect it, run again) */
   SH_ERR_GEOMETRY = -5, /* degenerate input: open contour (SH_OPEN_ERROR mode; see sh_set_open_contours), empty slice, ray miss, ... */
-  SH_ERR_NOMEM = -6
+  SH_ERR_NOMEM = -6,
+  SH_ERR_INTERNAL = -8  /* an invariant of the library did not hold (sh_geodesic: a relaxation went past the rounds its rule allows) */
 } sh_status;
 
 /* Stages of sh_run, in evaluation order (bone.py:110-157). */
@@ -986,6 +987,70 @@ int sh_mesh_topology(sh_ctx*, const sh_topology_options* options, sh_topology* i
 int sh_vertex_fields(sh_ctx*, int weight, int smooth_rounds, double* normals /* sumV x 3, host, nullable */,
                      double* fields /* sumV x SH_VERT_FIELDS, host, nullable */, int32_t* flags /* sumV, host, nullable */,
                      int32_t* status /* B, host, nullable */);
+
+/* ---- geodesic distances and shortest paths on the resident batch -------------------------------------------------------------------------
+ * What a planner asks of landmarks that lie on a surface, measured ALONG it (k_geo.h): from K sets of source vertices per mesh, each
+ * source with a start offset, per set and vertex the shortest distance along the mesh graph, the predecessor on a shortest path and
+ * the source the path starts from (trimesh's `vertex_adjacency_graph` with a networkx shortest path), and one info record per (mesh,
+ * set).  Everything is float64, operation by operation; corners are widened from the resident "verts" as sh_mass_properties widens
+ * them; indices are local to the mesh; "degenerate" and "row" mean what they mean in sh_mesh_topology; dot3(a, b) = (a0 b0 + a1 b1) +
+ * a2 b2.  Nothing is transcendental: the result is the same bytes wherever the rule runs.
+ *   face record  "geo.face", 6 doubles per face at 6 foff[b]: len[3], unf[3].  Slot e concerns the edge {f[e], f[(e + 1) % 3]}, as in
+ *                "topo.adj".  len[e]: with lo = min and hi = max of the two indices and D = P_hi - P_lo, len[e] = sqrt(dot3(D, D)); the
+ *                canonical order makes both faces of an edge store the same bytes.  unf[e] is the length of the straight line between
+ *                the two vertices opposite the edge with the two faces unfolded into one plane, +inf unless g = adj[f][e] >= 0.  With a, b
+ *                the edge, p the third vertex of f and q the vertex of g that is neither a nor b: lo / hi = min / max(a, b), p' = min(p,
+ *                q), q' = max(p, q); E = P_hi - P_lo, l = sqrt(dot3(E, E)); for r in {p', q'}: d_r = P_r - P_lo, x_r = dot3(d_r, E) / l,
+ *                t = dot3(d_r, d_r) - x_r * x_r, y_r = sqrt(t < 0 ? 0 : t); s = y_p' + y_q', x_c = (x_p' * y_q' + x_q' * y_p') / s,
+ *                dx = x_p' - x_q', unf = sqrt(dx * dx + s * s).  It is valid only if p != q, s > 0, x_c > 0 and x_c < l -- the line
+ *                crosses the open shared edge; comparisons are false on NaN -- and +inf otherwise.  A degenerate face has six +inf.
+ *   graph        vertex v has one arc per non-degenerate face f of its row and per corner k with f[k] == v: to f[(k + 1) % 3] with
+ *                len[k]; to f[(k + 2) % 3] with len[(k + 2) % 3]; with SH_GEO_UNFOLD also to the vertex opposite slot (k + 1) % 3 with
+ *                unf[(k + 1) % 3].  Parallel arcs are harmless: the minimum takes one.  SH_GEO_EDGES is the vertex adjacency graph of
+ *                trimesh; SH_GEO_UNFOLD adds the unfolded diagonals.  Every arc has its reverse with the same bytes.
+ *   distance     set k of mesh b is a list of (vertex, d0) pairs, d0 >= 0 and finite.  d[v] is the minimum, over the listed pairs and all
+ *                arc paths from them, of the left fold fl(fl(d0 + w1) + w2) ...; a value above max_dist (+inf, or > 0) counts as +inf,
+ *                and a candidate that is not finite is ignored.  fl(a + w) is monotone in a and never below a, so this minimum is the
+ *                unique fixed point of d[v] = min(d0s of v, min over arcs u -> v of fl(d[u] + w)): ANY relaxation schedule run until
+ *                nothing changes gives the same bytes, and so does Dijkstra; a prefix of a path within max_dist is within it, so the
+ *                cut-off changes no kept value.  THEREFORE NO SCHEDULE IS PART OF THIS DEFINITION; `sweeps` of the info record says
+ *                how many rounds the library took, is informational and is to be compared with nothing.  The distance is symmetric
+ *                between two vertices up to rounding, not as bytes (the fold runs from the source).
+ *   roots, predecessors, sources   from the converged d alone.  v is a root when a listed d0 of v equals d[v]; its label is the
+ *                smallest position in the set's list with that d0.  Otherwise pred[v] is the smallest u with an arc u -> v, fl(d[u] + w)
+ *                == d[v] and d[u] < d[v].  pred[v] is SH_GEO_ROOT at a root, SH_GEO_UNREACHED when d[v] is +inf, and SH_GEO_NO_PRED when
+ *                v is reached but no such u exists: that happens only behind an arc of length 0 (two vertices at the same coordinates
+ *                joined by a face) or one that d[u] absorbs (fl(d[u] + w) == d[u]).  d falls strictly along pred, so the predecessors
+ *                form a forest.  source[v] is the label of the root of v's tree, -1 when v is unreached or its chain ends in SH_GEO_NO_PRED.
+ *   info         per (b, k) SH_GEO_INFO_BYTES = 32 bytes: double far_dist, the largest finite d (0.0 when none); int32 reached, roots,
+ *                no_pred, farthest (the vertex of far_dist, the smallest index among equals, -1 when none), sweeps, status (0).  The
+ *                layout is stated here and by shoulder_amd._lib.GEO_INFO_DTYPE; it is not a typedef of this header.
+ *
+ * Arguments in this order: the context (SH_ERR_ARG); mode SH_GEO_EDGES or SH_GEO_UNFOLD, K in 1..SH_GEO_MAX_SETS, max_dist +inf or > 0
+ * (SH_ERR_ARG); the lists: src_off (B K + 1 int32, ascending from 0; set k of mesh b is [src_off[b K + k], src_off[b K + k + 1])), src,
+ * d0 (null: zeros) -- every source index in [0, V_b), every d0 finite and >= 0, checked on the host before anything is enqueued
+ * (SH_ERR_ARG with the offending mesh, set and position in the text; without a resident batch there is no set to read and the state
+ * answers).  An empty set is allowed: nothing is reached.  Then a resident batch and no runs in flight (SH_ERR_STATE); the incidence of
+ * THIS batch resident (SH_ERR_STATE: call sh_mesh_topology first; a topology that ran out of rounds is accepted); SH_ERR_NOMEM when the
+ * buffers do not fit.  A (mesh, set) pair with V_b <= SH_GEO_LDS_VERTICES is relaxed by one workgroup with its distances in LDS; a
+ * larger mesh takes Jacobi rounds on two planes in memory, SH_GEO_CHUNK rounds between two looks of the host at one 4-byte word, at
+ * most max V_b + 1 rounds, which the rule cannot exceed: beyond them SH_ERR_INTERNAL.  Reads "verts", "faces", the offsets, "topo.vrow",
+ * "topo.vface", "topo.adj".  Resident afterwards: "geo.face"; "geo.dist", per mesh K planes of V_b doubles at K voff[b] + k V_b;
+ * "geo.pred" and "geo.source", int32 in the same places; "geo.info", B K records; and the scratch "geo.opp", "geo.plane", "geo.jump",
+ * "geo.src", "geo.d0", "geo.state".  They are removed together with "topo.*" by the next upload / commit / sh_store("verts").  Every
+ * other buffer keeps its bytes. */
+#define SH_GEO_EDGES        0
+#define SH_GEO_UNFOLD       1
+#define SH_GEO_MAX_SETS     16
+#define SH_GEO_LDS_VERTICES 20000      /* 160 000 B of distances; 3 840 B of the 163 840 B of LDS stay for flags */
+#define SH_GEO_CHUNK        32         /* rounds of the general path between two looks of the host */
+#define SH_GEO_INFO_BYTES   32
+#define SH_GEO_ROOT         (-1)
+#define SH_GEO_NO_PRED      (-2)
+#define SH_GEO_UNREACHED    (-3)
+int sh_geodesic(sh_ctx*, int mode, int K, double max_dist, const int32_t* src_off /* B K + 1, host */, const int32_t* src /* host */,
+                const double* d0 /* host, nullable */, double* dist /* K sumV, host, nullable */, int32_t* pred /* K sumV, host, nullable */,
+                int32_t* source /* K sumV, host, nullable */, void* info /* B K x SH_GEO_INFO_BYTES, host, nullable */);
 
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"

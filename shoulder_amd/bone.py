@@ -582,6 +582,55 @@ class ProximalHumerus(Bone):
         return dict(gauss=gauss, mean=mean, k1=mean + root, k2=mean - root, area=r["area"], defect=r["defect"], normals=r["normals"],
                     border=(r["flags"] & _lib.VERT_BORDER) != 0)
 
+    # -- distances along the surface -------------------------------------------------------------------------------
+    def _geodesic_seeds(self, where):
+        """a vertex index, or a 3-D point in the CURRENT coordinate system -> (vertices, d0): the vertex itself with 0.0, or the point
+        snapped with closest_point -- the three vertices of its closest face with their Euclidean distances from the snapped point"""
+        if isinstance(where, (int, np.integer)):
+            if not 0 <= int(where) < len(self._verts):
+                raise ValueError("vertex index out of range")
+            return np.array([int(where)], np.int64), np.zeros(1)
+        p = np.asarray(where, dtype=np.float64)
+        if p.shape != (3,):
+            raise ValueError("a source is a vertex index or one 3-D point")
+        rec, _ = self._closest_ct(p[None])
+        if int(rec["status"][0]) != 0:
+            raise ValueError(f"closest_point failed with status {int(rec['status'][0])}")
+        tri = np.asarray(self._faces[int(rec["face"][0])], np.int64)
+        return tri, np.linalg.norm(np.asarray(self._verts, np.float64)[tri] - np.asarray(rec["point"][0], np.float64), axis=1)
+
+    def geodesic_distance(self, points_or_vertices, mode="unfold", max_dist=None):
+        """How far every vertex lies from a vertex (an integer) or from a 3-D point in the CURRENT coordinate system, ALONG the bone
+        (Engine.geodesic) -> (V,) float64, +inf where nothing within max_dist leads.  A point is snapped to the surface and enters as
+        the three vertices of its closest face, each with its straight distance from the snapped point.  mode "edges": along mesh
+        edges, as networkx on trimesh's vertex_adjacency_graph; "unfold": also across pairs of faces unfolded into a plane, which
+        stays within a few per cent of the true geodesic."""
+        v, d0 = self._geodesic_seeds(points_or_vertices)
+        self._ensure_loaded()
+        out = self._engine.geodesic([[v]], d0=[[d0]], mode=mode, max_dist=max_dist)
+        return self._engine.geodesic_field(out, 0, 0)[0].copy()
+
+    def geodesic_path(self, a, b, mode="unfold"):
+        """The line on the bone from vertex a to vertex b -> (polyline (n, 3) in the CURRENT coordinate system, its length).  The
+        distances come from the device, the walk from b back along the predecessors runs on the host; where the path crosses a pair of
+        unfolded faces the polyline gets the crossing point on their shared edge, so it stays on the surface.  Raises ValueError when b
+        cannot be reached from a, or is reached only over an arc of length 0."""
+        for x in (a, b):
+            if not isinstance(x, (int, np.integer)) or not 0 <= int(x) < len(self._verts):
+                raise ValueError("geodesic_path runs between two vertex indices")
+        self._ensure_loaded()
+        pts, length = self._engine.geodesic_path(0, int(a), int(b), mode=mode)
+        return self._engine.transform_points(pts, np.array(self._tfrm.matrix, dtype=np.float64)), length
+
+    def surface_patch(self, center, radius):
+        """The faces around `center` (a vertex or a 3-D point) within `radius` mm along the surface -> bool mask (F,): the faces whose
+        three vertices all lie within it (one geodesic_distance call with max_dist = radius): the cap around the head apex, not
+        everything a sphere of that radius cuts out of the bone."""
+        if not float(radius) > 0.0:
+            raise ValueError("radius must be > 0")
+        d = self.geodesic_distance(center, max_dist=float(radius))
+        return np.isfinite(d)[np.asarray(self._faces)].all(axis=1)
+
     # -- inside tests: generalized winding numbers -------------------------------------------------------------
     def winding_number(self, points):
         """The generalized winding number of the mesh about `points` (n, 3) in the CURRENT coordinate system -> float64 (n,), on the

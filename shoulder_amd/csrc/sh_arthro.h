@@ -3,7 +3,7 @@
 // buffer is, and what is valid against what (ArthroState).  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++
 // (tests/hostcheck/arthro_check.cpp).  An error is a code plus the text BEHIND the entry point's name: the caller puts
 // "sh_resect_planes: " (or the name it was called under) in front.  The entry points themselves are sh_arthro_host.h.
-// The queries of the resident batch (rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology, vertex fields) are no links of the chain:
+// The queries of the resident batch (rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology, vertex fields, geodesics) are no links of the chain:
 // sh_query.h, on top of this header and included at its end.  What both use is here: how a buffer list declares its structs (SH_BUF_LIST), the mesh buffers
 // (MeshBufs), ArthroError with the shared refusal texts, ArthroFacts and the `resident` check.
 #pragma once

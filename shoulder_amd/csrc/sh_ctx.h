@@ -16,7 +16,7 @@
 // steps of a UNet pass: kernel, grid, tensors and work tickets of every launch; the ticket and weight-packing tables), sh_arthro.h
 // (the arthroplasty chain: its argument checks and which refusal comes first, the pass plan and the bytes of every resect.* / canal.* /
 // stem.* / plan.* buffer, and ArthroState, the one record of what is valid against what), sh_query.h (the queries of the resident batch:
-// rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology, vertex fields -- their argument checks, plans and the bytes of their buffers),
+// rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology, vertex fields, geodesics -- their argument checks, plans and the bytes of their buffers),
 // sh_run.h (the run: BatchState, the one record of what is known about the resident batch -- tier vouch, frame, capacities, OBB tier, hulls
 // from the host; PreparedKey, the caller's half of the prepared-hull record; the refusals of sh_submit in their order and its plan).
 #pragma once

@@ -1,8 +1,8 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology) and the vertex fields (sh_vertex_fields).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields) and the geodesics (sh_geodesic).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
@@ -11,7 +11,7 @@
 namespace sh {
 
 // ---- the named buffers of the queries, one statement each: X(field, "name", element type, elem), and one line for their structs ----
-struct RayKey; struct CpPart;
+struct RayKey; struct CpPart; struct GeoInfo;
 #define RAY_BUFS(X)                                                                                                                \
   X(ray_rays, "ray.rays", double, 8) X(ray_status, "ray.status", int, 4) X(ray_counts, "ray.counts", int, 4)                       \
   X(ray_offs, "ray.offs", unsigned long long, 8) X(ray_cursor, "ray.cursor", int, 4) X(ray_pool, "ray.pool", RayKey, 8)            \
@@ -45,6 +45,13 @@ struct RayKey; struct CpPart;
   X(vert_face, "vert.face", double, 8) X(vert_normal, "vert.normal", double, 8) X(vert_fields, "vert.fields", double, 8)           \
   X(vert_flags, "vert.flags", int, 4) X(vert_status, "vert.status", int, 4) X(vert_a2, "vert.a2", double, 8)                       \
   X(vert_plane, "vert.plane", double, 8) X(vert_state, "vert.state", int, 4)
+// the face records, the K planes of distances, predecessors and sources per mesh, the info records; scratch: the vertex across each slot,
+// the second plane of the general path, the pointer jumping, the lists of the call (offsets and vertices; d0) and SH_GEO_STATE int32 per
+// (mesh, set) pair and once more for the call
+#define GEO_BUFS(X)                                                                                                                \
+  X(geo_face, "geo.face", double, 8) X(geo_dist, "geo.dist", double, 8) X(geo_pred, "geo.pred", int, 4) X(geo_source, "geo.source", int, 4) \
+  X(geo_info, "geo.info", GeoInfo, 8) X(geo_opp, "geo.opp", int, 4) X(geo_plane, "geo.plane", double, 8) X(geo_jump, "geo.jump", int, 4)    \
+  X(geo_src, "geo.src", int, 4) X(geo_d0, "geo.d0", double, 8) X(geo_state, "geo.state", int, 4)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -57,6 +64,8 @@ SH_QUERY_LIST(Samp, SAMP_BUFS)
 SH_QUERY_LIST(Topo, TOPO_BUFS)
 SH_BUF_LIST(Vert, VERT_BUFS)
 using VertView = BufJoin<MeshBufs, TopoBufs, VertBufs>;      // (the mesh, the incidence and adjacency it reads, and its own)
+SH_BUF_LIST(Geo, GEO_BUFS)
+using GeoView = BufJoin<MeshBufs, TopoBufs, GeoBufs>;
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -69,6 +78,7 @@ constexpr int AR_MASS_TERMS = 24;                                               
 constexpr int AR_SAMP_CHUNK = 256, AR_SAMP_HEAD = 64;                             // SH_SAMP_CHUNK, SH_SAMP_HEAD
 constexpr int AR_TOPO_BLOCK = 256, AR_TOPO_HEAD = 64;                             // SH_TOPO_BLOCK, SH_TOPO_HEAD
 constexpr int AR_VERT_BLOCK = 256, AR_VERT_FACE = 10;                             // SH_VERT_BLOCK, SH_VTX_FACE
+constexpr int AR_GEO_BLOCK = 256, AR_GEO_FACE = 6, AR_GEO_STATE = 8;              // SH_GEO_BLOCK, SH_GEOD_FACE, SH_GEO_STATE
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -240,6 +250,23 @@ inline VertPlan vert_plan(int B, long long maxV, long long maxF, long long sumV,
   return {(int)tiles_of(maxF, AR_VERT_BLOCK), (int)tiles_of(maxV, AR_VERT_BLOCK), z};
 }
 
+// Geodesics.  "geo.face" has AR_GEO_FACE doubles per face and "geo.opp" three int32; "geo.dist", "geo.plane" (only with a mesh of the
+// general path), "geo.pred", "geo.source" and "geo.jump" K words per vertex (mesh b at K voff[b]); "geo.info" 32 bytes per pair; "geo.src"
+// the B K + 1 offsets and behind them the S vertices of the call, "geo.d0" its S offsets; "geo.state" AR_GEO_STATE int32 per pair and
+// once more for the call.  general: the largest mesh has more than lds_vertices vertices; rounds_max = that mesh's vertices + 1.
+struct GeoPlan { int fblocks, vblocks, jumps; bool general; long long rounds_max; GeoBytes bytes; };
+inline GeoPlan geo_plan(int B, int K, long long S, int lds_vertices, long long maxV, long long maxF, long long sumV, long long sumF) {
+  const size_t f = (size_t)(sumF > 0 ? sumF : 1), v = (size_t)(sumV > 0 ? sumV : 1) * (size_t)K, pairs = (size_t)B * (size_t)K;
+  const bool general = maxV > lds_vertices;
+  GeoBytes z;
+  z.geo_face = f * AR_GEO_FACE * 8; z.geo_dist = v * 8; z.geo_pred = v * 4; z.geo_source = v * 4; z.geo_info = pairs * SH_GEO_INFO_BYTES; z.geo_opp = f * 12;
+  z.geo_plane = general ? v * 8 : 0; z.geo_jump = v * 4; z.geo_src = (pairs + 1 + (size_t)S) * 4; z.geo_d0 = (size_t)(S > 0 ? S : 1) * 8;
+  z.geo_state = (pairs + 1) * AR_GEO_STATE * 4;
+  int jumps = 0;
+  while ((1ll << jumps) < maxV) ++jumps;      // a round of the pointer jumping at least halves what is left of a chain of at most maxV - 1 hops
+  return {(int)tiles_of(maxF, AR_GEO_BLOCK), (int)tiles_of(maxV, AR_GEO_BLOCK), jumps, general, general ? maxV + 1 : 0, z};
+}
+
 // Multi-start registration: the coarse stage is sh_register_points on Qc points, the fine stage on all Q, both on the "icp.*" buffers,
 // which take the larger of the two sizes field by field (the split of the walk, and so "icp.cp_part", may be larger for the fewer points).
 inline int ms_coarse_count(int Q, int coarse_points) { return coarse_points == 0 || coarse_points > Q ? Q : coarse_points; }
@@ -310,6 +337,36 @@ inline ArthroError precheck_vertex_fields(int weight, int smooth_rounds, bool in
   if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
   if ((weight != SH_VERT_WEIGHT_AREA && weight != SH_VERT_WEIGHT_ANGLE) || smooth_rounds < 0 || smooth_rounds > SH_VERT_MAX_SMOOTH)
     return {SH_ERR_ARG, "bad argument (weight 0 or 1, smooth_rounds in 0..64)"};
+  if (const ArthroError e = resident(f); e.code) return e;
+  if (!incidence) return {SH_ERR_STATE, "no incidence of the resident batch: call sh_mesh_topology first"};
+  return arthro_ok();
+}
+
+// The lists of sh_geodesic against the resident batch (voff: its B + 1 vertex offsets on the host): the offsets ascend from 0, every
+// source index lies in [0, V_b), every d0 is finite and >= 0.  -> the text of the first offence with its mesh, set and position, or "".
+inline std::string geo_first_bad(int B, int K, const long long* voff, const int32_t* src_off, const int32_t* src, const double* d0) {
+  if (src_off[0] != 0) return "src_off[0] is not 0";
+  for (int p = 0; p < B * K; ++p) {
+    const std::string where = "mesh " + std::to_string(p / K) + ", set " + std::to_string(p % K);
+    if (src_off[p + 1] < src_off[p]) return where + ": src_off does not ascend";
+    const long long nv = voff[p / K + 1] - voff[p / K];
+    for (int i = src_off[p]; i < src_off[p + 1]; ++i) {
+      const std::string at = where + ", position " + std::to_string(i - src_off[p]);
+      if (!src || src[i] < 0 || src[i] >= nv) return at + ": source vertex " + (src ? std::to_string(src[i]) : std::string("(null)")) + " is not in [0, " + std::to_string(nv) + ")";
+      if (d0 && !(std::isfinite(d0[i]) && d0[i] >= 0.0)) return at + ": d0 is not finite and >= 0";
+    }
+  }
+  return "";
+}
+
+// incidence as in precheck_vertex_fields; voff: the host's vertex offsets of the resident batch (unused without one)
+inline ArthroError precheck_geodesic(int mode, int K, double max_dist, const int32_t* src_off, const int32_t* src, const double* d0, const long long* voff, bool incidence,
+                                     const ArthroFacts& f) {
+  if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
+  if ((mode != SH_GEO_EDGES && mode != SH_GEO_UNFOLD) || K < 1 || K > SH_GEO_MAX_SETS || !(max_dist > 0.0) || !src_off)
+    return {SH_ERR_ARG, "bad argument (mode 0 or 1, K in 1..16, max_dist +inf or > 0, src_off)"};
+  if (f.B >= 1 && voff)
+    if (const std::string bad = geo_first_bad(f.B, K, voff, src_off, src, d0); !bad.empty()) return {SH_ERR_ARG, "bad argument (" + bad + ")"};
   if (const ArthroError e = resident(f); e.code) return e;
   if (!incidence) return {SH_ERR_STATE, "no incidence of the resident batch: call sh_mesh_topology first"};
   return arthro_ok();

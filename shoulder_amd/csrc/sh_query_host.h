@@ -1,7 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
 // point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), the surface samples, sh_sample_surface
-// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), and the vertex fields, sh_vertex_fields (k_vert.h).
+// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), and the geodesics, sh_geodesic (k_geo.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -312,4 +312,78 @@ int sh_vertex_fields(sh_ctx* c, int weight, int smooth_rounds, double* normals, 
   if (status) HIPCHK(c, hipMemcpyAsync(status, v.vert_status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
+}
+
+// ---- geodesic distances and shortest paths (k_geo.h) ----
+// the lists to the device -> face -> init -> seed -> lds (the pairs whose plane fits one workgroup's LDS) -> for a larger mesh chunks of
+// SH_GEO_CHUNK rounds, the host reading ONE word of "geo.state" after each (the only look: the number of rounds is not known beforehand)
+// -> root -> pred -> jumps x jump -> info.  lds_vertices: SH_GEO_LDS_VERTICES, or less from the lab entry point below.
+static_assert(AR_GEO_BLOCK == SH_GEO_BLOCK && AR_GEO_FACE == SH_GEOD_FACE && AR_GEO_STATE == SH_GEO_STATE, "sh_query.h: geodesic block, doubles of a face record, words of a pair");
+
+static int geodesic_run(sh_ctx* c, const char* fn, int lds_vertices, int mode, int K, double max_dist, const int32_t* src_off, const int32_t* src, const double* d0,
+                        double* dist, int32_t* pred, int32_t* source, void* info) {
+  const bool incidence = c && c->at("topo.vrow") && c->at("topo.vface") && c->at("topo.adj");
+  const bool lists = c && c->B >= 1 && (int)c->h_voff.size() == c->B + 1;
+  if (const ArthroError e = precheck_geodesic(mode, K, max_dist, src_off, src, d0, lists ? c->h_voff.data() : nullptr, incidence, arthro_facts(c)); e.code)
+    return arthro_refuse(c, fn, e);
+  if (lds_vertices < 0 || lds_vertices > SH_GEO_LDS_VERTICES) return fail(c, SH_ERR_ARG, std::string(fn) + ": bad argument (lds_vertices in 0..SH_GEO_LDS_VERTICES)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B, pairs = B * K;
+  const long long S = src_off[pairs], sumV = c->sumV;
+  const GeoPlan plan = geo_plan(B, K, S, lds_vertices, c->maxV, c->maxF, sumV, c->sumF);
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  const GeoView v = view_of<GeoView>(c);
+  HIPCHK(c, hipMemcpyAsync(v.geo_src, src_off, (size_t)(pairs + 1) * 4, hipMemcpyHostToDevice, c->stream));
+  if (S > 0) {
+    HIPCHK(c, hipMemcpyAsync(v.geo_src + pairs + 1, src, (size_t)S * 4, hipMemcpyHostToDevice, c->stream));
+    if (d0) HIPCHK(c, hipMemcpyAsync(v.geo_d0, d0, (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
+    else HIPCHK(c, hipMemsetAsync(v.geo_d0, 0, (size_t)S * 8, c->stream));
+  }
+  HIPCHK(c, hipMemsetAsync(v.geo_state, 0, plan.bytes.geo_state, c->stream));
+  const dim3 fblocks((unsigned)plan.fblocks, (unsigned)B), vblocks((unsigned)plan.vblocks, (unsigned)K, (unsigned)B), lanes(SH_GEO_BLOCK), each((unsigned)pairs);
+  const int *d_off = v.geo_src, *d_src = v.geo_src + pairs + 1;
+  const int *vrow = v.topo_vrow, *vface = v.topo_vface, *opp = v.geo_opp;
+  const double* frec = v.geo_face;
+  LAUNCH(c, "k_geo_face", k_geo_face, fblocks, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_adj, v.geo_face, v.geo_opp);
+  LAUNCH(c, "k_geo_init", k_geo_init, vblocks, lanes, v.voff, K, lds_vertices, v.geo_dist, v.geo_source, v.geo_state);
+  LAUNCH(c, "k_geo_seed", k_geo_seed, each, lanes, v.voff, K, d_off, d_src, (const double*)v.geo_d0, max_dist, v.geo_dist);
+  if (lds_vertices > 0)
+    LAUNCH(c, "k_geo_lds", k_geo_lds, dim3((unsigned)K, (unsigned)B), dim3(SH_GEO_LDS_BLOCK), v.faces, v.voff, v.foff, vrow, vface, frec, opp, K, mode, max_dist, lds_vertices,
+           v.geo_dist, v.geo_state);
+  if (plan.general) {
+    const int* call = v.geo_state + (size_t)pairs * SH_GEO_STATE;
+    long long r = 0;
+    for (int more = 1; more;) {
+      if (r >= plan.rounds_max) return fail(c, SH_ERR_INTERNAL, std::string(fn) + ": the relaxation did not settle within max V_b + 1 rounds");
+      for (int i = 0; i < SH_GEO_CHUNK && r < plan.rounds_max; ++i, ++r)
+        LAUNCH(c, "k_geo_round", k_geo_round, vblocks, lanes, v.faces, v.voff, v.foff, vrow, vface, frec, opp, K, mode, max_dist, lds_vertices, (int)r, v.geo_dist, v.geo_plane,
+               v.geo_state);
+      HIPCHK(c, hipMemcpyAsync(&more, call + r % 3, 4, hipMemcpyDeviceToHost, c->stream));      // round r - 1 changed something
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  LAUNCH(c, "k_geo_root", k_geo_root, each, lanes, v.voff, K, d_off, d_src, (const double*)v.geo_d0, (const double*)v.geo_dist, v.geo_source);
+  LAUNCH(c, "k_geo_pred", k_geo_pred, vblocks, lanes, v.faces, v.voff, v.foff, vrow, vface, frec, opp, K, mode, (const double*)v.geo_dist, v.geo_pred, v.geo_source, v.geo_jump);
+  for (int j = 0; j < plan.jumps; ++j) LAUNCH(c, "k_geo_jump", k_geo_jump, vblocks, lanes, v.voff, K, v.geo_jump);
+  LAUNCH(c, "k_geo_info", k_geo_info, dim3((unsigned)K, (unsigned)B), lanes, v.voff, K, (const double*)v.geo_dist, (const int*)v.geo_pred, (const int*)v.geo_jump,
+         (const int*)v.geo_state, v.geo_source, v.geo_info);
+  const size_t n = (size_t)sumV * (size_t)K;
+  if (dist) HIPCHK(c, hipMemcpyAsync(dist, v.geo_dist, n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (pred) HIPCHK(c, hipMemcpyAsync(pred, v.geo_pred, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (source) HIPCHK(c, hipMemcpyAsync(source, v.geo_source, n * 4, hipMemcpyDeviceToHost, c->stream));
+  if (info) HIPCHK(c, hipMemcpyAsync(info, v.geo_info, (size_t)pairs * SH_GEO_INFO_BYTES, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+int sh_geodesic(sh_ctx* c, int mode, int K, double max_dist, const int32_t* src_off, const int32_t* src, const double* d0, double* dist, int32_t* pred, int32_t* source,
+                void* info) {
+  return geodesic_run(c, "sh_geodesic", SH_GEO_LDS_VERTICES, mode, K, max_dist, src_off, src, d0, dist, pred, source, info);
+}
+
+// Lab entry point (not in the header; tools/time_geodesic.py and the tests of the general path): sh_geodesic with the threshold between
+// the two paths lowered to lds_vertices in 0..SH_GEO_LDS_VERTICES, so that a small mesh takes the general path.  The result is the same bytes.
+extern "C" int sh_lab_geodesic(sh_ctx* c, int lds_vertices, int mode, int K, double max_dist, const int32_t* src_off, const int32_t* src, const double* d0, double* dist,
+                               int32_t* pred, int32_t* source, void* info) {
+  return geodesic_run(c, "sh_lab_geodesic", lds_vertices, mode, K, max_dist, src_off, src, d0, dist, pred, source, info);
 }

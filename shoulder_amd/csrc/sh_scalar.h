@@ -1769,4 +1769,114 @@ SH_HD void vert_smooth(const int* faces, const double* a2, const int* row, int n
   *m_out = den == 0.0 ? 0.0 : sm / den;
 }
 
+// ---- geodesic distances and shortest paths on the resident batch (include/shoulder_hip.h sh_geodesic; k_geo.h) ----------------------
+// float64, operation by operation in the written order (-ffp-contract=off), restated by tests/geo_oracle.py.  Nothing is
+// transcendental: + - x / sqrt and comparisons, so the bytes are the same wherever the rule runs.  The modes and the codes of a
+// predecessor are the header's SH_GEO_* (k_geo.h holds them equal).
+#define SH_GEOD_FACE 6           // doubles of a face record: len[3], unf[3]
+#define SH_GEOD_UNFOLD 1         // the mode with the unfolded diagonals (0: the mesh edges alone)
+#define SH_GEOD_ROOT (-1)
+#define SH_GEOD_NO_PRED (-2)
+#define SH_GEOD_UNREACHED (-3)
+#define SH_GEOD_NO_LABEL 0x7fffffff      // no list position: above every one
+
+// the info record of a (mesh, set) pair as the device writes it: SH_GEO_INFO_BYTES of the header
+struct GeoInfo { double far_dist; int reached, roots, no_pred, farthest, sweeps, status; };
+static_assert(sizeof(GeoInfo) == 32, "GeoInfo");
+
+SH_HD double geo_inf() { return __builtin_huge_val(); }
+
+// The record of face f of a mesh and the vertex across each of its slots (-1 where the slot has no face behind it).  `faces` and `adj`
+// are the mesh's; a degenerate face has six +inf.
+SH_HD void geo_face(const float* verts, const int* faces, const int* adj, int f, bool degenerate, double* rec /* SH_GEOD_FACE */, int* opp /* 3 */) {
+  const double inf = geo_inf();
+  for (int e = 0; e < 3; ++e) { rec[e] = inf; rec[3 + e] = inf; opp[e] = -1; }
+  if (degenerate) return;
+  const int* fc = faces + 3 * (size_t)f;
+  for (int e = 0; e < 3; ++e) {
+    const int a = fc[e], b = fc[e == 2 ? 0 : e + 1], p = fc[e == 0 ? 2 : e - 1];
+    const int lo = a < b ? a : b, hi = a < b ? b : a;
+    const float *vl = verts + 3 * (size_t)lo, *vh = verts + 3 * (size_t)hi;
+    const double Pl[3] = {(double)vl[0], (double)vl[1], (double)vl[2]};
+    const double E[3] = {(double)vh[0] - Pl[0], (double)vh[1] - Pl[1], (double)vh[2] - Pl[2]};
+    const double l = sqrt(dot3(E, E));
+    rec[e] = l;
+    const int g = adj[3 * (size_t)f + e];
+    if (g < 0) continue;
+    const int* gc = faces + 3 * (size_t)g;
+    const int q = (int)((long long)gc[0] + gc[1] + gc[2] - a - b);      // g holds a and b: its third vertex
+    opp[e] = q;
+    const int r0 = p < q ? p : q, r1 = p < q ? q : p;
+    double x[2], y[2];
+    for (int i = 0; i < 2; ++i) {
+      const float* vr = verts + 3 * (size_t)(i == 0 ? r0 : r1);
+      const double d[3] = {(double)vr[0] - Pl[0], (double)vr[1] - Pl[1], (double)vr[2] - Pl[2]};
+      x[i] = dot3(d, E) / l;
+      const double t = dot3(d, d) - x[i] * x[i];
+      y[i] = sqrt(t < 0.0 ? 0.0 : t);
+    }
+    const double s = y[0] + y[1];
+    const double xc = (x[0] * y[1] + x[1] * y[0]) / s;
+    const double dx = x[0] - x[1];
+    const double unf = sqrt(dx * dx + s * s);
+    if (p != q && s > 0.0 && xc > 0.0 && xc < l) rec[3 + e] = unf;      // (false on NaN: the line crosses the open shared edge)
+  }
+}
+
+// One relaxation of vertex v over its ascending row of n faces: the minimum of dv and of fl(d[u] + w) over the arcs of v's faces that
+// are finite and at most max_dist.  `d` is the plane of the (mesh, set) pair -- global memory or LDS; `frec` and `opp` are the mesh's
+// "geo.face" and "geo.opp".  The arcs of the rule leave v; each has its reverse with the same bytes, so they are also the arcs that arrive.
+SH_HD double geo_relax(const int* faces, const double* frec, const int* opp, const int* row, int n, int v, int mode, double max_dist, double dv, const double* d) {
+  double best = dv;
+  for (int i = 0; i < n; ++i) {
+    const int f = row[i];
+    const int* fc = faces + 3 * (size_t)f;
+    const int k = vert_corner(fc, v), k1 = k == 2 ? 0 : k + 1, k2 = k == 0 ? 2 : k - 1;
+    const double* r = frec + SH_GEOD_FACE * (size_t)f;
+    double c = d[fc[k1]] + r[k];
+    if (c <= max_dist && c < best) best = c;
+    c = d[fc[k2]] + r[k2];
+    if (c <= max_dist && c < best) best = c;
+    if (mode == SH_GEOD_UNFOLD) {
+      const int q = opp[3 * (size_t)f + k1];
+      if (q >= 0) {
+        c = d[q] + r[3 + k1];
+        if (c <= max_dist && c < best) best = c;
+      }
+    }
+  }
+  return best;
+}
+
+// The predecessor of a reached vertex v that is no root, from the converged plane d: the smallest u with an arc to v, fl(d[u] + w) ==
+// d[v] and d[u] < d[v], or SH_GEOD_NO_PRED (only behind an arc of length 0, or one that d[u] absorbs).
+SH_HD int geo_pred(const int* faces, const double* frec, const int* opp, const int* row, int n, int v, int mode, const double* d) {
+  const double dv = d[v];
+  int best = SH_GEOD_NO_LABEL;
+  for (int i = 0; i < n; ++i) {
+    const int f = row[i];
+    const int* fc = faces + 3 * (size_t)f;
+    const int k = vert_corner(fc, v), k1 = k == 2 ? 0 : k + 1, k2 = k == 0 ? 2 : k - 1;
+    const double* r = frec + SH_GEOD_FACE * (size_t)f;
+    int u = fc[k1];
+    double du = d[u];
+    if (du + r[k] == dv && du < dv && u < best) best = u;
+    u = fc[k2]; du = d[u];
+    if (du + r[k2] == dv && du < dv && u < best) best = u;
+    if (mode == SH_GEOD_UNFOLD) {
+      u = opp[3 * (size_t)f + k1];
+      if (u >= 0) {
+        du = d[u];
+        if (du + r[3 + k1] == dv && du < dv && u < best) best = u;
+      }
+    }
+  }
+  return best == SH_GEOD_NO_LABEL ? SH_GEOD_NO_PRED : best;
+}
+
+// the better of two candidates for the farthest vertex: the larger distance, the smaller index among equals (v < 0: none)
+SH_HD void geo_far(double d, int v, double* best_d, int* best_v) {
+  if (v >= 0 && (*best_v < 0 || d > *best_d || (d == *best_d && v < *best_v))) { *best_d = d; *best_v = v; }
+}
+
 }  // namespace sh

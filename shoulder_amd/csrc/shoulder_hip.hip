@@ -24,6 +24,7 @@
 #include "k_sample.h"
 #include "k_topo.h"
 #include "k_vert.h"
+#include "k_geo.h"
 #include "k_te.h"
 #include "k_obb.h"
 #include "sh_hull.h"
@@ -489,11 +490,12 @@ static int stl_enqueue_emit(sh_ctx* timed, hipStream_t st, int B, const StlPlan&
 #undef STL_LAUNCH
 
 // "cp.out" (sh_closest_points), "wn.out" (sh_winding_numbers), "icp.out" and "icp.near" (sh_register_points), "mass.out" and "mass.part"
-// (sh_mass_properties), "samp.*" (sh_sample_surface), "topo.*" (sh_mesh_topology), "vert.*" (sh_vertex_fields) answer for the batch they were asked about: a new batch removes them
+// (sh_mass_properties), "samp.*" (sh_sample_surface), "topo.*" (sh_mesh_topology), "vert.*" (sh_vertex_fields), "geo.*" (sh_geodesic) answer for the batch they were asked about: a new batch removes them
 static void drop_closest(sh_ctx* c) {
   for (const char* name : {"cp.out", "wn.out", "icp.out", "icp.near", "mass.out", "mass.part", "samp.cdf", "samp.base", "samp.out", "samp.info", "samp.state",
                            "topo.vrow", "topo.vface", "topo.adj", "topo.label", "topo.info", "topo.shells", "topo.state", "topo.cursor", "topo.tmp", "topo.p",
-                           "vert.face", "vert.normal", "vert.fields", "vert.flags", "vert.status", "vert.a2", "vert.plane", "vert.state"}) {
+                           "vert.face", "vert.normal", "vert.fields", "vert.flags", "vert.status", "vert.a2", "vert.plane", "vert.state",
+                           "geo.face", "geo.dist", "geo.pred", "geo.source", "geo.info", "geo.opp", "geo.plane", "geo.jump", "geo.src", "geo.d0", "geo.state"}) {
     auto it = c->bufs.find(name);
     if (it == c->bufs.end()) continue;
     if (it->second.p) (void)hipFree(it->second.p);
@@ -862,7 +864,7 @@ int sh_slice_mesh_planes(sh_ctx* c, const double* verts, int nv, const int32_t* 
 
 // ---- the arthroplasty chain: sh_resect_*, sh_canal_profile, sh_resect_stems, sh_resect_plan (host code; the decisions are sh_arthro.h's) ----
 #include "sh_arthro_host.h"
-// ---- the queries of the resident batch: rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology, vertex fields (the decisions are sh_query.h's) ----
+// ---- the queries of the resident batch: rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology, vertex fields, geodesics (the decisions are sh_query.h's) ----
 #include "sh_query_host.h"
 
 int sh_mesh_transformed(sh_ctx* c, int b, const double* T, double* out) {

@@ -38,6 +38,58 @@ def _ptr(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
+def _is_index_array(s):
+    """one set of source vertices (an integer array, or a list of integers, possibly empty), as opposed to a list of sets"""
+    if isinstance(s, np.ndarray):
+        return s.dtype != object and s.ndim <= 1
+    return isinstance(s, (list, tuple)) and all(isinstance(x, (int, np.integer)) for x in s)
+
+
+def geodesic_polyline(verts, faces, rec, opp, d, pred, end):
+    """The walk back along pred from vertex `end` to its root on one mesh, on the host -> (points (n, 3) float64 from the root to `end`,
+    the summed length of the polyline).  verts (V, 3) float64, faces (F, 3); rec and opp are the mesh's "geo.face" (len[3], unf[3]) and
+    "geo.opp"; d and pred the planes of one set.  A hop that is no mesh edge runs over an unfolded diagonal and contributes the point
+    P_lo + (x_c / l) E where it crosses the edge the two faces share (the rule of include/shoulder_hip.h, restated here in NumPy)."""
+    if not 0 <= end < len(d):
+        raise ValueError("vertex index out of range")
+    if pred[end] == _lib.GEO_UNREACHED:
+        raise ValueError(f"vertex {end} is not reached")
+    pts, at = [verts[end]], int(end)
+    while pred[at] != _lib.GEO_ROOT:
+        u = int(pred[at])
+        if u == _lib.GEO_NO_PRED:
+            raise ValueError(f"vertex {at} is reached over an arc of length 0 and has no predecessor")
+        rows = np.nonzero((faces == at).any(axis=1) & (faces[:, 0] != faces[:, 1]) & (faces[:, 1] != faces[:, 2]) & (faces[:, 0] != faces[:, 2]))[0]
+        hop = None
+        for fi in rows:      # a mesh edge first: slot k is the edge to the next corner, slot (k + 2) % 3 the one to the previous
+            k = int(np.nonzero(faces[fi] == at)[0][0])
+            for other, slot in ((faces[fi, (k + 1) % 3], k), (faces[fi, (k + 2) % 3], (k + 2) % 3)):
+                if other == u and d[u] + rec[fi, slot] == d[at]:
+                    hop = ()
+        if hop is None:
+            for fi in rows:
+                e = (int(np.nonzero(faces[fi] == at)[0][0]) + 1) % 3
+                if opp[fi, e] == u and d[u] + rec[fi, 3 + e] == d[at]:
+                    a, b = int(faces[fi, e]), int(faces[fi, (e + 1) % 3])
+                    lo, hi, p, q = min(a, b), max(a, b), min(at, u), max(at, u)
+                    E = verts[hi] - verts[lo]
+                    l = np.sqrt(E @ E)
+                    x, y = [], []
+                    for r in (p, q):
+                        dr = verts[r] - verts[lo]
+                        x.append((dr @ E) / l)
+                        y.append(np.sqrt(max(dr @ dr - x[-1] * x[-1], 0.0)))
+                    hop = (verts[lo] + (((x[0] * y[1] + x[1] * y[0]) / (y[0] + y[1])) / l) * E,)
+                    break
+        if hop is None:
+            raise RuntimeError(f"no arc from {u} to {at} carries the distance")
+        pts.extend(hop)
+        pts.append(verts[u])
+        at = u
+    pts = np.array(pts[::-1])
+    return pts, float(np.linalg.norm(np.diff(pts, axis=0), axis=1).sum())
+
+
 def _mat4(T):
     """a C-contiguous float64 4x4 (the C side reads 16 doubles); anything else is the reference's ValueError (base.py:57-58)"""
     T = np.ascontiguousarray(T, dtype=np.float64)
@@ -851,6 +903,91 @@ class Engine:
         with np.errstate(all="ignore"):
             unit = np.where(a2[:, None] != 0.0, rec[:, :3] / a2[:, None], 0.0)
         return unit, a2 / 2.0, rec[:, 4:7].copy()
+
+    # ---- geodesic distances and shortest paths on the resident batch (include/shoulder_hip.h sh_geodesic) ------------------------
+    _GEO_MODES = {"edges": _lib.GEO_EDGES, "unfold": _lib.GEO_UNFOLD}
+
+    def geodesic(self, sources, d0=None, mode="unfold", max_dist=None, _lds_vertices=None):
+        """Distances ALONG the surface of every resident mesh from K sets of source vertices per mesh, on the device (the incidence of
+        topology() is made first when it is not resident for this batch).  sources[b][k] is an index array (vertices of mesh b; an
+        empty one reaches nothing); a flat list of B arrays means K = 1.  d0, shaped like sources, gives every source a start offset
+        >= 0 (None: zeros).  mode "edges" walks the mesh edges (trimesh's vertex_adjacency_graph), "unfold" also the diagonals of two
+        neighbouring faces unfolded into a plane; max_dist cuts off: what lies farther is +inf and unreached.  -> dict: dist (K sumV,)
+        float64, pred and source (K sumV,) int32 -- per mesh b K planes of V_b values at K voff[b] + k V_b (geodesic_field cuts one
+        out); pred is the vertex before v on a shortest path, _lib.GEO_ROOT at a source that starts one, GEO_NO_PRED behind an arc of
+        length 0, GEO_UNREACHED; source is the position in the set's list of the source v's path starts from, or -1 --, info (B, K) of
+        _lib.GEO_INFO_DTYPE (far_dist, reached, roots, no_pred, farthest, sweeps, status), voff (B + 1,) and K.  The result is the
+        fixed point of the relaxation: the same bytes whatever path the library takes.  Resident afterwards: "geo.face", "geo.dist",
+        "geo.pred", "geo.source", "geo.info"."""
+        m = self._GEO_MODES.get(mode, mode)
+        if not isinstance(m, (int, np.integer)):
+            raise ValueError("mode must be 'edges' or 'unfold'")
+        B = max(self.B, 0)
+        sets = list(sources)
+        if len(sets) != B:
+            raise ValueError("sources needs one entry per resident mesh")
+        flat = B > 0 and all(_is_index_array(s) for s in sets)
+        if flat:
+            sets = [[s] for s in sets]
+            d0 = None if d0 is None else [[z] for z in d0]
+        K = len(sets[0]) if B else 1
+        if any(len(s) != K for s in sets):
+            raise ValueError("every mesh needs the same number of sets")
+        src = [np.asarray(s, dtype=np.int64).reshape(-1) for per in sets for s in per]
+        if any(len(s) and (s.min() < -2**31 or s.max() >= 2**31) for s in src):
+            raise ValueError("a source index does not fit int32")
+        off = np.zeros(B * K + 1, np.int32)
+        off[1:] = np.cumsum([len(s) for s in src])
+        idx = np.ascontiguousarray(np.concatenate(src + [np.zeros(0, np.int64)]), np.int32)
+        z = None
+        if d0 is not None:
+            per = [[None] * K if row is None else list(row) for row in d0]
+            if len(per) != B or any(len(row) != K for row in per):
+                raise ValueError("d0 must be shaped like sources")
+            zs = [np.zeros(len(src[b * K + k])) if per[b][k] is None else np.asarray(per[b][k], np.float64).reshape(-1) for b in range(B) for k in range(K)]
+            if [len(x) for x in zs] != [len(s) for s in src]:
+                raise ValueError("d0 must be shaped like sources")
+            z = np.ascontiguousarray(np.concatenate(zs + [np.zeros(0)]), np.float64)
+        if B >= 1 and not self._has_buffer("topo.vrow"):
+            self.topology()
+        V = int(self.voff[-1]) if B >= 1 else 0
+        ok = 1 <= K <= _lib.GEO_MAX_SETS      # (the library reports the rest; nothing is sized by it here)
+        n = K * V if ok else 0
+        dist, pred, source = np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        info = np.zeros((B, K) if ok else (0,), dtype=_lib.GEO_INFO_DTYPE)
+        limit = np.inf if max_dist is None else float(max_dist)
+        args = (int(m), int(K), limit, _ptr(off), _ptr(idx), _ptr(z) if z is not None else None, _ptr(dist), _ptr(pred), _ptr(source), _ptr(info))
+        if _lds_vertices is None:
+            self._chk(self.L.sh_geodesic(self.h, *args))
+        else:      # the lab entry point: the threshold between the LDS path and the general path lowered (tools/time_geodesic.py, the tests)
+            fn = self.L.sh_lab_geodesic
+            fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int] + _lib.SIGNATURES["sh_geodesic"][0][1:], ctypes.c_int
+            self._chk(fn(self.h, int(_lds_vertices), *args))
+        return dict(dist=dist, pred=pred, source=source, info=info, voff=np.array(self.voff, dtype=np.int64), K=K)
+
+    def geodesic_field(self, out, b, k=0):
+        """The (V_b,) views of dist, pred and source of set k of mesh b in what geodesic() returned."""
+        K, voff = int(out["K"]), out["voff"]
+        if not 0 <= int(b) < len(voff) - 1 or not 0 <= int(k) < K:
+            raise ValueError("mesh or set index out of range")
+        nv = int(voff[b + 1] - voff[b])
+        at = K * int(voff[b]) + int(k) * nv
+        return out["dist"][at:at + nv], out["pred"][at:at + nv], out["source"][at:at + nv]
+
+    def geodesic_path(self, b, start, end, mode="unfold"):
+        """The shortest path on mesh b from vertex `start` to vertex `end` along the graph of geodesic() -> (polyline (n, 3) float64 in
+        CT from start to end, its length = the distance).  The distances come from the device; the walk back along pred runs here.  A
+        hop over an unfolded diagonal contributes the point where the unfolded line crosses the edge the two faces share, so the
+        polyline stays on the surface.  Raises ValueError when `end` is not reached or lies behind an arc of length 0 (GEO_NO_PRED)."""
+        f0, f1 = self._face_range(b)
+        v0, v1 = int(self.voff[b]), int(self.voff[b + 1])
+        out = self.geodesic([[[int(start)]] if i == int(b) else [[]] for i in range(self.B)], mode=mode)
+        d, pred, _ = self.geodesic_field(out, b, 0)
+        verts = self.fetch("verts", np.float32, (int(self.voff[-1]), 3))[v0:v1].astype(np.float64)
+        faces = self.fetch("faces", np.int32, (int(self.foff[-1]), 3))[f0:f1]
+        rec = self.fetch("geo.face", np.float64, (int(self.foff[-1]), 6))[f0:f1]
+        opp = self.fetch("geo.opp", np.int32, (int(self.foff[-1]), 3))[f0:f1]
+        return geodesic_polyline(verts, faces, rec, opp, d, pred, int(end))
 
     # ---- multi-start registration (include/shoulder_hip.h sh_register_multistart) -----------------------------------------------
     def principal_starts(self, points, rolls=8, with_ratios=False):
