@@ -5,7 +5,6 @@
 
 #include "k_hullpre.h"
 #include "k_hull.h"
-#include "sh_hull.h"
 
 using namespace sh;
 
@@ -198,60 +197,64 @@ struct HullPhaseGate {
   static HullPhaseGate& instance() { static HullPhaseGate g; return g; }
 };
 
+// One pinned slot for B humeri at `pitch` elements per humerus (what it held before is freed)
+static int hull_stage_alloc(sh_ctx::HullStage& hs, int B, HullCap pitch, std::string* errtxt) {
+  if (hs.hv) { (void)hipHostFree(hs.hv); (void)hipHostFree(hs.nr); (void)hipHostFree(hs.ed); (void)hipHostFree(hs.cnt); }
+  hs.hv = nullptr; hs.cap = 0;
+  hs.pv = pitch.v; hs.pf = pitch.f; hs.pe = pitch.e;
+  HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.hv, (size_t)B * hs.pv * 3 * 8));
+  HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.nr, (size_t)B * hs.pf * 3 * 8));
+  HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.ed, (size_t)B * hs.pe * 4 * 4));
+  HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.cnt, (size_t)B * 3 * 4));
+  hs.cap = B;
+  return SH_OK;
+}
+
+// The hull of one humerus: its float32 points widened into h.P, the quickhull (which has the retry / joggle logic) into h.H, the
+// counts into h.n.  false: no hull.
+bool sh::hull_of_points(const float* src, long long nv, HostHull& h) {
+  h.P.assign(src, src + 3 * nv);
+  if (!shhull::convex_hull(h.P.data(), (int)nv, h.H)) return false;
+  h.n = {(int)h.H.vert_ids.size(), (int)h.H.tris.size() / 3, (int)h.H.edges.size() / 4};
+  return true;
+}
+// the hull's vertices, in the order of the record
+static void hull_gather(const HostHull& h, double* hv) {
+  for (int i = 0; i < h.n.v; ++i)
+    for (int k = 0; k < 3; ++k) hv[3 * (size_t)i + k] = h.P[3 * (size_t)h.H.vert_ids[i] + k];
+}
+
 int sh::hull_host_phase(sh_ctx* c, const sh_ctx::HullPts& in, int slot, int b0, int B, int* bad_mesh, double* ms, std::string* errtxt, bool background) {
   auto t0 = std::chrono::steady_clock::now();
   sh_ctx::HullStage& hs = c->hstage[slot];
+  HullCap pitch = {hs.pv, hs.pf, hs.pe};
   bool grown = false;
+  int rc;
 again:
-  if (hs.cap < B || grown) {
-    if (hs.hv) { (void)hipHostFree(hs.hv); (void)hipHostFree(hs.nr); (void)hipHostFree(hs.ed); (void)hipHostFree(hs.cnt); }
-    hs.hv = nullptr; hs.cap = 0;
-    HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.hv, (size_t)B * hs.pv * 3 * 8));
-    HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.nr, (size_t)B * hs.pf * 3 * 8));
-    HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.ed, (size_t)B * hs.pe * 4 * 4));
-    HIPCHK_TXT(errtxt, hipHostMalloc((void**)&hs.cnt, (size_t)B * 3 * 4));
-    hs.cap = B;
-  }
+  if ((hs.cap < B || grown) && (rc = hull_stage_alloc(hs, B, pitch, errtxt)) != SH_OK) return rc;
   if (!hs.ev) HIPCHK_TXT(errtxt, hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
   if (hs.used) HIPCHK_TXT(errtxt, hipEventSynchronize(hs.ev));     // the previous copies out of this slot are done
-  {
-    // the other slot of the double buffer is allocated with the first one: pinning its 31 MB costs ~7 ms, and a context that had run
-    // once (a warm-up step) paid that in its SECOND run -- the first timed step of a lane (round 3: 12 ms instead of 5 for that hull
-    // phase, the first UNet passes of a 20-step region 14 ms apart)
-    sh_ctx::HullStage& ho = c->hstage[slot ^ 1];
-    if (!ho.hv && !grown) {
-      ho.pv = hs.pv; ho.pf = hs.pf; ho.pe = hs.pe;
-      HIPCHK_TXT(errtxt, hipHostMalloc((void**)&ho.hv, (size_t)B * ho.pv * 3 * 8));
-      HIPCHK_TXT(errtxt, hipHostMalloc((void**)&ho.nr, (size_t)B * ho.pf * 3 * 8));
-      HIPCHK_TXT(errtxt, hipHostMalloc((void**)&ho.ed, (size_t)B * ho.pe * 4 * 4));
-      HIPCHK_TXT(errtxt, hipHostMalloc((void**)&ho.cnt, (size_t)B * 3 * 4));
-      ho.cap = B;
-    }
-  }
+  // the other slot of the double buffer is allocated with the first one: pinning its 31 MB costs ~7 ms, and a context that had run
+  // once (a warm-up step) paid that in its SECOND run -- the first timed step of a lane (round 3: 12 ms instead of 5 for that hull
+  // phase, the first UNet passes of a 20-step region 14 ms apart)
+  if (!c->hstage[slot ^ 1].hv && !grown && (rc = hull_stage_alloc(c->hstage[slot ^ 1], B, pitch, errtxt)) != SH_OK) return rc;
   double* hv = hs.hv; double* nr = hs.nr; int* ed = hs.ed; int* counts = hs.cnt;
   std::vector<int> status(B, 0);
-  std::vector<int> demand(3 * (size_t)B, 0);      // of the humeri whose hull does not fit the staging pitch
+  std::vector<int> demand(3 * (size_t)B, 0);      // [3][B] as the count block: of the humeri whose hull does not fit the staging pitch
   std::atomic<int> next(0);
   auto work = [&]() {
-    std::vector<double> P;
-    shhull::Hull H;
+    HostHull h;
     for (;;) {
       if (background && HullPhaseGate::instance().foreground_waits()) break;      // a run is waiting for ITS hulls: hand the pool over
       int b = next.fetch_add(1);
       if (b >= B) break;
       counts[b] = counts[B + b] = counts[2 * B + b] = 0;
-      long long v0 = in.off[b0 + b], nv = in.cnt[b0 + b];
-      P.resize(3 * (size_t)nv);
-      const float* src = in.src + 3 * v0;
-      for (long long i = 0; i < 3 * nv; ++i) P[i] = (double)src[i];
-      if (!shhull::convex_hull(P.data(), (int)nv, H)) { status[b] = SH_ERR_GEOMETRY; continue; }
-      int hn = (int)H.vert_ids.size(), fn = (int)H.tris.size() / 3, en = (int)H.edges.size() / 4;
-      if (hn > hs.pv || fn > hs.pf || en > hs.pe) { status[b] = 1; demand[3 * (size_t)b] = hn; demand[3 * (size_t)b + 1] = fn; demand[3 * (size_t)b + 2] = en; continue; }      // does not fit the staging pitch: see below
-      for (int i = 0; i < hn; ++i)
-        for (int k = 0; k < 3; ++k) hv[((size_t)b * hs.pv + i) * 3 + k] = P[3 * (size_t)H.vert_ids[i] + k];
-      std::copy(H.normals.begin(), H.normals.end(), nr + (size_t)b * hs.pf * 3);
-      std::copy(H.edges.begin(), H.edges.end(), ed + (size_t)b * hs.pe * 4);
-      counts[b] = hn; counts[B + b] = fn; counts[2 * B + b] = en;
+      if (!hull_of_points(in.src + 3 * in.off[b0 + b], in.cnt[b0 + b], h)) { status[b] = SH_ERR_GEOMETRY; continue; }
+      if (!hull_fits(h.n, pitch)) { status[b] = 1; demand[b] = h.n.v; demand[B + b] = h.n.f; demand[2 * B + b] = h.n.e; continue; }      // the staging pitch is too small: see below
+      hull_gather(h, hv + (size_t)b * hs.pv * 3);
+      std::copy(h.H.normals.begin(), h.H.normals.end(), nr + (size_t)b * hs.pf * 3);
+      std::copy(h.H.edges.begin(), h.H.edges.end(), ed + (size_t)b * hs.pe * 4);
+      counts[b] = h.n.v; counts[B + b] = h.n.f; counts[2 * B + b] = h.n.e;
     }
   };
   // One pool of worker threads per process, started once and shared by every context (lane) of the process: the host's
@@ -266,10 +269,7 @@ again:
   if (!grown && std::find(status.begin(), status.end(), 1) != status.end()) {
     // a hull larger than the staging pitch (a dense mesh): this slot gets the record capacity -- or, above it, what the largest hull
     // of the batch needs (the device record grows at the upload: grow_hull_records) -- and the phase runs again
-    int dv = SH_HV, df = SH_HF, de = SH_HE;
-    for (int b = 0; b < B; ++b) { dv = std::max(dv, demand[3 * (size_t)b]); df = std::max(df, demand[3 * (size_t)b + 1]); de = std::max(de, demand[3 * (size_t)b + 2]); }
-    auto up = [](int x) { return (x + 1023) / 1024 * 1024; };
-    hs.pv = up(dv); hs.pf = up(df); hs.pe = up(de);
+    pitch = hull_pitch_grown(hull_need(demand.data(), B));
     grown = true;
     std::fill(status.begin(), status.end(), 0);
     next = 0;
@@ -286,13 +286,12 @@ again:
 hipError_t sh::hull_upload(sh_ctx* c, int slot, int B, const HullRec& dst, hipStream_t st) {
   sh_ctx::HullStage& hs = c->hstage[slot];
   const int* counts = hs.cnt;
-  int nvmax = 1, nfmax = 1, nemax = 1;
-  for (int b = 0; b < B; ++b) { nvmax = std::max(nvmax, counts[b]); nfmax = std::max(nfmax, counts[B + b]); nemax = std::max(nemax, counts[2 * B + b]); }
-  if (nvmax > c->hcap.v || nfmax > c->hcap.f || nemax > c->hcap.e) return hipErrorInvalidValue;      // (callers check hull_fits / grow first)
+  const HullNeed n = hull_need(counts, B);
+  if (!hull_fits(n, c->hcap)) return hipErrorInvalidValue;      // (the foreground grows the record first, a background thread leaves the upload to it)
   hipError_t e;
-  if ((e = hipMemcpy2DAsync(dst.hv, (size_t)c->hcap.v * 24, hs.hv, (size_t)hs.pv * 24, (size_t)nvmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpy2DAsync(dst.normals, (size_t)c->hcap.f * 24, hs.nr, (size_t)hs.pf * 24, (size_t)nfmax * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
-  if ((e = hipMemcpy2DAsync(dst.edges, (size_t)c->hcap.e * 16, hs.ed, (size_t)hs.pe * 16, (size_t)nemax * 16, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpy2DAsync(dst.hv, (size_t)c->hcap.v * 24, hs.hv, (size_t)hs.pv * 24, (size_t)n.v * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpy2DAsync(dst.normals, (size_t)c->hcap.f * 24, hs.nr, (size_t)hs.pf * 24, (size_t)n.f * 24, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpy2DAsync(dst.edges, (size_t)c->hcap.e * 16, hs.ed, (size_t)hs.pe * 16, (size_t)n.e * 16, B, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
   if ((e = hipMemcpyAsync(dst.nv, counts, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
   if ((e = hipMemcpyAsync(dst.nf, counts + B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
   if ((e = hipMemcpyAsync(dst.ne, counts + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
@@ -300,10 +299,23 @@ hipError_t sh::hull_upload(sh_ctx* c, int slot, int B, const HullRec& dst, hipSt
   hs.used = true;
   return hipSuccess;
 }
+// ... and the record of ONE humerus (redo_given_up) -> `dst`, the record of that humerus as a window of one.  The sources are h's,
+// pageable (hipMemcpyAsync stages them before it returns); the caller synchronises `st` before h goes out of scope all the same.
+hipError_t sh::hull_upload_one(HostHull& h, const HullRec& dst, hipStream_t st) {
+  h.hv.resize(3 * (size_t)h.n.v);
+  hull_gather(h, h.hv.data());
+  hipError_t e;
+  if ((e = hipMemcpyAsync(dst.hv, h.hv.data(), h.hv.size() * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(dst.normals, h.H.normals.data(), (size_t)h.n.f * 24, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(dst.edges, h.H.edges.data(), (size_t)h.n.e * 16, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(dst.nv, &h.n.v, 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(dst.nf, &h.n.f, 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  return hipMemcpyAsync(dst.ne, &h.n.e, 4, hipMemcpyHostToDevice, st);
+}
 
-// The hull on the device: prefilter -> round-based quickhull (k_hull.h), all on this context's stream; nothing comes to the host.
-// *nfmax: the face count run_obb sizes its grids by.
-int sh::run_device_hull(sh_ctx* c, int B, int* nfmax) {
+// The hull on the device: prefilter -> round-based quickhull (k_hull.h), all on this context's stream; nothing comes to the host
+// (the face count run_obb sizes its grids by is sh_obb_plan.h hull_nfmax).
+int sh::run_device_hull(sh_ctx* c, int B) {
   { int arc = alloc_hulld(c); if (arc != SH_OK) return arc; }
   launch_prefilter(hullpre_ptrs(c), B, c->stream);
   HIPCHK(c, hipGetLastError());
@@ -314,7 +326,5 @@ int sh::run_device_hull(sh_ctx* c, int B, int* nfmax) {
          h.hv, h.normals, h.edges, h.nv, h.nf, h.ne,
          buf<int>(c, "hulld.fail"), buf<int>(c, "hulld.rounds"), (const int*)buf<int>(c, "hulld.skip"), c->hcap);
   LAUNCH(c, "k_hull_flag", k_hull_flag, dim3((B + 63) / 64), dim3(64), buf<int>(c, "hulld.fail"), buf<int>(c, "err"), B);
-  *nfmax = std::max((int)HD_SLOTS, c->batch.skip_nfmax());      // (the face counts stay on the device: the candidate kernel's tiles beyond a hull's faces return at once;
-                                                       //  a humerus kept on the host hull may have more faces than the device hull has slots)
   return SH_OK;
 }

@@ -32,7 +32,7 @@ namespace sh {
 
 #define HD_THREADS 1024
 #define HD_NW (HD_THREADS / 64)
-#define HD_SLOTS 3072         // face slots (alive + not yet reused); a humerus ends with ~2 700 faces
+//      HD_SLOTS              // face slots: sh_hullcap.h (the OBB stage sizes its grids by it)
 #define HD_NMAX 8192          // input points (survivors of the prefilter: ~6 300 of a humerus's 16 222 vertices)
 #define HD_KC 64              // candidates per round (4 per wave)
 #define HD_NJ (HD_KC / HD_NW)

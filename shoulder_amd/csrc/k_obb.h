@@ -22,10 +22,7 @@ namespace sh {
 
 __device__ inline void obb_basis(const double* n, double* u, double* v) { plane_basis(n, u, v); }
 
-#define SH_OBB_THREADS 256
-#define SH_OBB_TILE 16           // hull faces (candidate directions) per workgroup
-#define SH_OBB_GROUP 4           // faces whose rectangle scans run together (2 would fit three workgroups per CU: measured slower)
-#define SH_SIL_MAX 512           // silhouette edges per direction
+// (SH_OBB_THREADS / _TILE / _GROUP, the k_obb_bounds shape and the tier limits of k_obb_candidates: sh_hullcap.h, the host plans by them)
 
 // ---- pruning bounds.  The box of direction n has volume height(n) x min-area rectangle(n), and the rectangle is at least as
 // large as the projection of the hull on the plane normal to n, whose area is 1/2 sum_f A_f |n . n_f| (Cauchy).  The bound is
@@ -53,9 +50,6 @@ k_obb_face_area2(const double* __restrict__ hv, const double* __restrict__ norma
 // faces (a contiguous slice each, combined in LDS in wave order), read through wave-uniform addresses: scalar loads, eight
 // records per trip so that a trip pays the scalar-cache latency once; many short waves hide the rest.  Also resets the
 // directions' candidate records ("not evaluated") and folds the smallest bound of the humerus.
-#define SH_OBB_BND_SPLIT 4
-#define SH_OBB_BND_DIRS 128
-#define SH_OBB_BND_THREADS (64 * SH_OBB_BND_SPLIT)
 __global__ void __launch_bounds__(SH_OBB_BND_THREADS)
 k_obb_bounds(const double* __restrict__ hv, const int* __restrict__ nv_, const double* __restrict__ normals, const int* __restrict__ nf_,
              const double* __restrict__ area2, double* __restrict__ lb_out /*[B][hc.f]*/, unsigned long long* __restrict__ lbmin_enc /*[B], ~0*/,
@@ -198,8 +192,8 @@ k_obb_select(const double* __restrict__ lb_, const int* __restrict__ nf_, const 
 //   scans     four directions at a time: project the silhouette start vertices (LDS), then every silhouette
 //             edge takes the extents of all of them (ns x ns, fp64) -> min-area rectangle
 // Two capacity tiers (the hull record in HBM is sized for the large one, hc.v / hc.f / hc.e; only this kernel keeps per-face
-// and per-silhouette state in LDS):  <16, 4, 512, 8192, unsigned short>  hulls of up to 8 192 faces -- every fixture (2 732) and
-// everything the device hull produces (3 072 slots) -- two workgroups per CU;  <8, 1, 2048, 32768, unsigned> the hull of a dense
+// and per-silhouette state in LDS):  <SH_OBB_TILE, SH_OBB_GROUP, SH_OBB_SIL_SMALL, SH_OBB_NF_SMALL, unsigned short>  hulls of up to 8 192 faces -- every fixture (2 732) and
+// everything the device hull produces (3 072 slots) -- two workgroups per CU;  <8, 1, SH_OBB_SIL_LARGE, SH_OBB_NF_LARGE, unsigned> the hull of a dense
 // mesh (a 519 k-triangle humerus: 8 414 faces), one workgroup per CU, chosen by the host when a hull of the launch needs it.
 // A third tier without limits, <8, 1, 0, 0, unsigned, true>: face masks, silhouette lists and projected start points in a workspace
 // in global memory (ObbWs: one slice per workgroup; a grid of ws.nwg workgroups walks the tiles), for hulls above 32 768 faces and

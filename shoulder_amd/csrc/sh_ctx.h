@@ -18,7 +18,9 @@
 // stem.* / plan.* buffer, and ArthroState, the one record of what is valid against what), sh_query.h (the queries of the resident batch:
 // rays, closest points, winding numbers, registration, mass properties, surface samples, mesh topology, vertex fields, geodesics -- their argument checks, plans and the bytes of their buffers),
 // sh_run.h (the run: BatchState, the one record of what is known about the resident batch -- tier vouch, frame, capacities, OBB tier, hulls
-// from the host; PreparedKey, the caller's half of the prepared-hull record; the refusals of sh_submit in their order and its plan).
+// from the host; PreparedKey, the caller's half of the prepared-hull record; the refusals of sh_submit in their order and its plan),
+// sh_obb_plan.h (the OBB stage: what hulls need of the record and of a pinned slot and how either grows, where a window's hulls come
+// from, the early-upload rule, and the tier, grids and workspace bytes of the stage's launches).
 #pragma once
 #include "../../include/shoulder_hip.h"
 
@@ -46,7 +48,9 @@
 
 #include "sh_demand.h"
 #include "sh_hullcap.h"
+#include "sh_hull.h"
 #include "sh_ingest.h"
+#include "sh_obb_plan.h"
 #include "sh_query.h"      // (and sh_arthro.h below it)
 #include "sh_run.h"
 #include "sh_unet_plan.h"
@@ -144,7 +148,8 @@ struct sh_ctx {
   int b0 = 0, Bwin = 0;
   struct HullStage { double* hv = nullptr; double* nr = nullptr; int* ed = nullptr; int* cnt = nullptr; int cap = 0; hipEvent_t ev = nullptr; bool used = false;
                      int pv = 4096, pf = 8192, pe = 12288; };      // per-humerus pitch of the pinned staging (elements): the usual hull fits the small
-                                                                 // one; a batch with a larger hull re-allocates the slot at SH_HV / SH_HF / SH_HE
+                                                                 // one; a batch with a larger hull re-allocates the slot at sh_obb_plan.h's
+                                                                 // hull_pitch_grown: the record's start capacity or, above it, what the largest hull asks
   HullStage hstage[2];                       // pinned host staging, double buffered
   int hslot = 0;                             // slot the next hull goes to
   // Overlap (sh_set_overlap): while the device works on run k, a background thread computes the hulls run k+1 will
@@ -269,9 +274,20 @@ static inline T* buf(sh_ctx* c, const char* name) {
 // The hull record of the current window (what the host hull uploads, the device hull writes and the OBB stage reads), resolved in
 // one place.  Calling thread only (buffer map), and not across grow_hull_records / alloc_batch, which re-allocate it.
 struct HullRec { double *hv, *normals; int *edges, *nv, *nf, *ne; };
-static inline HullRec hull_rec(sh_ctx* c) {
+static inline HullRec hull_rec_at(sh_ctx* c, int b0) {      // ... of the window that begins at humerus b0, wherever the context stands
+  WindowScope from(c, b0, c->Bwin);
   return {buf<double>(c, "hull.hv"), buf<double>(c, "hull.normals"), buf<int>(c, "hull.edges"), buf<int>(c, "hull.nv"), buf<int>(c, "hull.nf"), buf<int>(c, "hull.ne")};
 }
+static inline HullRec hull_rec(sh_ctx* c) { return hull_rec_at(c, c->b0); }
+// the bytes those six buffers hold (a missing one: 0), for sh_obb_plan.h early_upload_ok.  Calling thread only.
+static inline sh::HullRecBytes hull_rec_bytes(sh_ctx* c) {
+  auto z = [c](const char* n) { auto it = c->bufs.find(n); return it == c->bufs.end() || !it->second.p ? (size_t)0 : it->second.bytes; };
+  return {z("hull.hv"), z("hull.normals"), z("hull.edges"), z("hull.nv"), z("hull.nf"), z("hull.ne")};
+}
+// One humerus on the host hull (hull.hip hull_of_points): its points widened, the quickhull, its counts; `hv`: the hull's vertices
+// gathered for an upload of this humerus alone (hull_upload_one)
+struct HostHull { std::vector<double> P, hv; shhull::Hull H; sh::HullNeed n; };
+static inline std::string hull_failed_text(int mesh, int code) { char m[96]; snprintf(m, sizeof m, "mesh %d: convex hull failed (%d)", mesh, code); return m; }
 
 // ensure() inside a function with `int rc`, and the buffer's window stride: ENS for [B][...] buffers (bytes / B per humerus),
 // ENS_SHARED for shared / ragged / scratch ones (stride 0)
@@ -349,7 +365,9 @@ hipError_t fetch_prefiltered(const HullPre& hp, int B, long long sumV, long long
 hipError_t fetch_hull_points(sh_ctx* c, const HullPre& hp, hipStream_t st);
 int hull_host_phase(sh_ctx* c, const sh_ctx::HullPts& in, int slot, int b0, int B, int* bad_mesh, double* ms, std::string* errtxt, bool background = false);
 hipError_t hull_upload(sh_ctx* c, int slot, int B, const HullRec& dst, hipStream_t st);
-int run_device_hull(sh_ctx* c, int B, int* nfmax);
+bool hull_of_points(const float* src, long long nv, HostHull& h);
+hipError_t hull_upload_one(HostHull& h, const HullRec& dst, hipStream_t st);
+int run_device_hull(sh_ctx* c, int B);
 int alloc_hullpre(sh_ctx* c, int B, long long sumV, const char* sfx);
 // unet.hip
 int unet_turn_enter(sh_ctx* c);

@@ -27,7 +27,6 @@
 #include "k_geo.h"
 #include "k_te.h"
 #include "k_obb.h"
-#include "sh_hull.h"
 
 #include <sched.h>
 
@@ -368,7 +367,7 @@ struct SliceSetView { SLICE_SET_ARRAYS(X) };      // (an array the set does not 
 // A window's buffers as typed pointers, the window offset applied as buf<T>() applies it (b0 * per_mesh).  RULE: resolved once, at
 // the top of run_window (alloc_prox, the pools' first allocation and anything between runs -- sh_collect's regrowth, sh_commit_staged,
 // alloc_batch -- lie in front of that), and resolved AGAIN behind the one thing that re-allocates its buffers inside a window:
-// grow_hull_records (run_obb does so; that is why it alone takes the view non-const).  What is ensured where it is used stays out of
+// grow_hull_records (obb_hulls of run_obb does so; that is why they alone take the view non-const).  What is ensured where it is used stays out of
 // the view and is resolved behind its ensure(): the overflow pools and plan arrays (ovf_pools / ovf_set), "obb.ws_*", "rfc.nodes";
 // so does the device hull's scratch, which run_device_hull owns.  The view is the calling thread's; background threads get pointers by value.
 #define X(f, name, T, ...) T* f = nullptr;
@@ -1000,24 +999,13 @@ static SliceSpec spec_full(bool decode) { return {SET_FULL, 0, false, 0, decode}
 static SliceSpec spec_distal(bool decode) { return {SET_DISTAL, 2, false, 0, decode}; }
 static const SliceSpec SPEC_PROX = {SET_PROX, 1, true, 0, false}, SPEC_NECKC = {SET_NECKC, 3, false, 1, false}, SPEC_POBB = {SET_POBB, 4, false, 0, false};
 
-// do the hulls of pinned slot `slot` fit the device record?  (the background threads upload only when they do: growing re-allocates)
-static bool hull_fits(const sh_ctx* c, int slot, int B, int* need /*[3] or null*/) {
-  const int* counts = c->hstage[slot].cnt;
-  int nvmax = 1, nfmax = 1, nemax = 1;
-  for (int b = 0; b < B; ++b) { nvmax = std::max(nvmax, counts[b]); nfmax = std::max(nfmax, counts[B + b]); nemax = std::max(nemax, counts[2 * B + b]); }
-  if (need) { need[0] = nvmax; need[1] = nfmax; need[2] = nemax; }
-  return nvmax <= c->hcap.v && nfmax <= c->hcap.f && nemax <= c->hcap.e;
-}
 // A hull above the record's capacity (a strictly convex surface keeps every vertex: 16 384 is not a bound of the reference's
 // `convex_hull`, mesh.py:82): the hull record and the per-face arrays of the OBB stage are re-allocated at strides that hold it.
 // Foreground only, nothing of this context in flight reads them afterwards (hipFree waits for the device).  A WinView resolved
-// before this call is stale behind it.
-static int grow_hull_records(sh_ctx* c, int nv, int nf, int ne) {
-  auto up = [](int x) { return (x + x / 8 + 1023) / 1024 * 1024; };
+// before this call is stale behind it.  (How far it grows: sh_obb_plan.h hull_record_grown.)
+static int grow_hull_records(sh_ctx* c, HullNeed need) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (nv > c->hcap.v) c->hcap.v = up(nv);
-  if (nf > c->hcap.f) c->hcap.f = up(nf);
-  if (ne > c->hcap.e) c->hcap.e = up(ne);
+  c->hcap = hull_record_grown(c->hcap, need);
   int rc;
   WIN_HULLCAP_BUFS(WIN_ENS)
   if (c->sw.debug) fprintf(stderr, "[sh] hull record grown to %d vertices / %d faces / %d edges per humerus\n", c->hcap.v, c->hcap.f, c->hcap.e);
@@ -1035,86 +1023,95 @@ struct WinState {
   bool te_rows_done = false;        // run_te_rows has run (beside or in front of the chain)
 };
 
-// redo_nf > 0: a redo -- redo_given_up put the host quickhull's record of this window (of one humerus) into hull.*, with that many faces
+// ---- the OBB stage: run_obb is its order; where the hulls come from, how the record grows and every number of the launches are
+// sh_obb_plan.h's ----------------------------------------------------------------------------------------------------------------------
+// The hull record of the window, on its way into hull.* behind this; *nfmax: the face count the launches are sized by.
+// redo_nf > 0: a redo -- redo_given_up put the host quickhull's record of this window (of one humerus) into hull.*, with that many faces.
 // `v` is resolved again when the hull record had to grow (the only re-allocation of a view's buffers inside a window).
-static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int redo_nf) {
-  const int B = v.B, b0 = c->b0;
-  int nfmax = 1;
-  c->batch.obb_begins(c->batch_gen);      // (a new batch: the small k_obb_candidates tier and the chosen hull mode again)
-  if (redo_nf > 0) nfmax = redo_nf;
-  else if (device_hull_now(c)) {
-    { int drc = run_device_hull(c, B, &nfmax); if (drc != SH_OK) return drc; }
-  } else {
-  int slot = prepared_slot;
-  if (slot < 0) {
-    slot = c->hslot; c->hslot ^= 1;
-    int bad = -1; double ms = 0; std::string et;
-    int hrc = hull_host_phase(c, c->hull_in, slot, b0, B, &bad, &ms, &et);
-    if (c->sw.debug) fprintf(stderr, "[sh] run_obb: foreground hull phase %.2f ms\n", ms);
-    if (c->timing) { KTimer& h = c->timers["host.hull"]; h.ms += ms; h.n += 1; }
-    if (hrc == SH_ERR_HIP) { c->err = et; return hrc; }
-    if (hrc != SH_OK) { char m[96]; snprintf(m, sizeof m, "mesh %d: convex hull failed (%d)", bad, hrc); return fail(c, hrc, m); }
+static int obb_hulls(sh_ctx* c, WinView& v, int prepared_slot, int redo_nf, int* nfmax) {
+  const int B = v.B;
+  const HullSource src = hull_source(redo_nf, device_hull_now(c), prepared_slot);
+  int slot = prepared_slot, rc;
+  switch (src) {
+    case HULL_REDO: case HULL_PREPARED: break;
+    case HULL_DEVICE:
+      if ((rc = run_device_hull(c, B)) != SH_OK) return rc;
+      break;
+    case HULL_FOREGROUND: {
+      slot = c->hslot; c->hslot ^= 1;
+      int bad = -1; double ms = 0; std::string et;
+      rc = hull_host_phase(c, c->hull_in, slot, c->b0, B, &bad, &ms, &et);
+      if (c->sw.debug) fprintf(stderr, "[sh] run_obb: foreground hull phase %.2f ms\n", ms);
+      if (c->timing) { KTimer& h = c->timers["host.hull"]; h.ms += ms; h.n += 1; }
+      if (rc == SH_ERR_HIP) { c->err = et; return rc; }
+      if (rc != SH_OK) return fail(c, rc, hull_failed_text(bad, rc));
+      break;
+    }
   }
-  const int* counts = c->hstage[slot].cnt;
-  for (int b = 0; b < B; ++b) nfmax = std::max(nfmax, counts[B + b]);
-  {
-    int need[3];
-    if (!hull_fits(c, slot, B, need)) {      // (never with an early upload: the background threads upload only what fits)
-      int grc = grow_hull_records(c, need[0], need[1], need[2]);
-      if (grc != SH_OK) return grc;
+  HullNeed need = {1, 1, 1};
+  if (hull_from_host(src)) {
+    need = hull_need(c->hstage[slot].cnt, B);
+    if (!hull_fits(need, c->hcap)) {      // (never with an early upload: the background threads upload only what fits)
+      if ((rc = grow_hull_records(c, need)) != SH_OK) return rc;
       v = win_view(c);
     }
+    if (hull_upload_pending(src, c->prep.uploaded)) HIPCHK(c, hull_upload(c, slot, B, v.hull(), c->stream));
   }
-  if (!(prepared_slot >= 0 && c->prep.uploaded)) HIPCHK(c, hull_upload(c, slot, B, v.hull(), c->stream));
+  *nfmax = hull_nfmax(src, redo_nf, c->batch.skip_nfmax(), need);
+  return SH_OK;
+}
+
+// The workspace tier's buffers (k_obb.h ObbWs), ensured where the tier is used: X(field, "name", element type, element size as
+// sh_buffer_info reports it).  obb_workspace: at the plan's sizes, no window stride (another tier: none of them) -> the kernel's argument.
+#define OBB_WS_BUFS(X) X(fmask, "obb.ws_fmask", unsigned char, 1) X(lists, "obb.ws_lists", unsigned, 4) X(sxy, "obb.ws_sxy", double2, 8) X(area, "obb.ws_area", double, 8)
+static int obb_workspace(sh_ctx* c, const ObbPlan& p, unsigned long long* need, ObbWs* ws) {
+  *ws = ObbWs{};
+  ws->need = need; ws->nwg = p.nwg; ws->silcap = p.silcap;
+  if (p.tier != OBB_TIER_WORKSPACE) return SH_OK;
+  int rc;
+#define X(f, name, T, elem) ENS_SHARED(name, p.ws.f, elem);
+  OBB_WS_BUFS(X)
+#undef X
+#define X(f, name, T, elem) ws->f = (T*)c->bufs[name].p;
+  OBB_WS_BUFS(X)
+#undef X
+  return SH_OK;
+}
+
+// The clears of the stage, face areas and pruning bounds, then two passes of select + candidates: the seed tile, then the directions
+// its best volume cannot exclude.  Every grid and size is the plan's.
+static int obb_candidates(sh_ctx* c, const WinView& v, WinState* w, const ObbPlan& p) {
+  const int B = v.B;
+  const HullCap hc = c->hcap;
+  FILL(c, {v.obb_best_enc, (size_t)B * 8, 0xFF} /*"no candidate volume yet"*/, {v.obb_lbmin_enc, (size_t)B * 8, 0xFF},
+       {v.obb_area2, (size_t)B * hc.f * 8, 0}, {v.obb_endcnt, (size_t)B * 2 * 4, 0},
+       {v.zb_enc, (size_t)B * 16, 0xFF} /*z bounds: "nothing seen yet"*/, {v.anp_mm_enc, (size_t)B * 16, 0xFF});
+  w->bounds_cleared = true;
+  LAUNCH(c, "k_obb_face_area2", k_obb_face_area2, dim3(p.area2_grid, (unsigned)B), dim3(256), v.hull_hv,
+         v.hull_normals, v.hull_edges, (const int*)v.hull_ne, v.obb_area2, hc);
+  LAUNCH(c, "k_obb_bounds", k_obb_bounds, dim3(p.bounds_grid), dim3(SH_OBB_BND_THREADS),
+         v.hull_hv, (const int*)v.hull_nv, v.hull_normals, (const int*)v.hull_nf, v.obb_area2, v.obb_lb,
+         v.obb_lbmin_enc, v.obb_cand_vol, v.obb_cand_edge, p.bnd_tiles, B, hc);
+  const auto candidates = p.tier == OBB_TIER_WORKSPACE ? k_obb_candidates<SH_OBB_TILE_LARGE, 1, 0, 0, unsigned, true>
+                          : p.tier == OBB_TIER_LARGE   ? k_obb_candidates<SH_OBB_TILE_LARGE, 1, SH_OBB_SIL_LARGE, SH_OBB_NF_LARGE, unsigned>
+                                                       : k_obb_candidates<SH_OBB_TILE, SH_OBB_GROUP, SH_OBB_SIL_SMALL, SH_OBB_NF_SMALL, unsigned short>;
+  ObbWs ws;
+  if (int rc = obb_workspace(c, p, v.ovf_ctr + SH_CTR_SIL_NEED, &ws)) return rc;
+  for (int pass = 0; pass < 2; ++pass) {
+    const ObbPass& q = p.pass[pass];
+    LAUNCH(c, "k_obb_select", k_obb_select, dim3(B), dim3(256), v.obb_lb, (const int*)v.hull_nf, v.obb_lbmin_enc,
+           v.obb_best_enc, q.mode, v.obb_dir_list, v.obb_dir_count, v.obb_seeded, hc);
+    LAUNCH(c, pass == 0 ? "k_obb_seed" : "k_obb_candidates", candidates, dim3(q.grid), dim3(SH_OBB_THREADS),
+           v.hull_hv, v.hull_nv, v.hull_normals, v.hull_nf, v.hull_edges, v.hull_ne, v.obb_cand_vol,
+           v.obb_cand_edge, v.err, v.obb_best_enc, v.obb_dir_list, v.obb_dir_count,
+           q.nt_pass, B, c->sw.obb_prune ? 1 : 0, hc, ws);
   }
-  {
-    FILL(c, {v.obb_best_enc, (size_t)B * 8, 0xFF} /*"no candidate volume yet"*/, {v.obb_lbmin_enc, (size_t)B * 8, 0xFF},
-         {v.obb_area2, (size_t)B * c->hcap.f * 8, 0}, {v.obb_endcnt, (size_t)B * 2 * 4, 0},
-         {v.zb_enc, (size_t)B * 16, 0xFF} /*z bounds: "nothing seen yet"*/, {v.anp_mm_enc, (size_t)B * 16, 0xFF});
-    w->bounds_cleared = true;
-    const int nemax = 3 * nfmax / 2 + 3;      // (a closed triangulated surface: 2 E = 3 F)
-    const HullCap hc = c->hcap;
-    LAUNCH(c, "k_obb_face_area2", k_obb_face_area2, dim3((unsigned)((std::min(nemax, hc.e) + 255) / 256), (unsigned)B), dim3(256), v.hull_hv,
-           v.hull_normals, v.hull_edges, (const int*)v.hull_ne, v.obb_area2, hc);
-    const int bnd_tiles = (nfmax + SH_OBB_BND_DIRS - 1) / SH_OBB_BND_DIRS;
-    LAUNCH(c, "k_obb_bounds", k_obb_bounds, dim3((unsigned)(bnd_tiles * ((B + 7) / 8) * 8)), dim3(SH_OBB_BND_THREADS),
-           v.hull_hv, (const int*)v.hull_nv, v.hull_normals, (const int*)v.hull_nf, v.obb_area2, v.obb_lb,
-           v.obb_lbmin_enc, v.obb_cand_vol, v.obb_cand_edge, bnd_tiles, B, hc);
-    // capacity tier of k_obb_candidates (k_obb.h): the small one unless a hull of this launch has more than 8 192 faces or a direction
-    // of an earlier run of this batch had more than 512 silhouette edges; the workspace tier above 32 768 faces / 2 048 edges
-    const int sil_need = c->batch.caps().sil_need;
-    const bool huge = nfmax > 32768 || sil_need > 2048 || c->batch.caps().nf_over;
-    const bool big = !huge && (nfmax > 8192 || sil_need > 512);
-    const int TT = (big || huge) ? 8 : SH_OBB_TILE;
-    const int ntiles = (nfmax + TT - 1) / TT;
-    const auto candidates = huge ? k_obb_candidates<8, 1, 0, 0, unsigned, true>
-                            : big ? k_obb_candidates<8, 1, 2048, 32768, unsigned> : k_obb_candidates<SH_OBB_TILE, SH_OBB_GROUP, 512, 8192, unsigned short>;
-    ObbWs ws{};
-    ws.need = v.ovf_ctr + SH_CTR_SIL_NEED;
-    if (huge) {
-      ws.nwg = 256;
-      ws.silcap = std::max(hc.v + 64, sil_need + sil_need / 8);      // (a silhouette is a cycle of the hull's graph; more only on degenerate input: then the demand is recorded)
-      int wrc;
-      if ((wrc = ensure(c, "obb.ws_fmask", (size_t)ws.nwg * hc.f, 1)) != SH_OK || (wrc = ensure(c, "obb.ws_lists", (size_t)ws.nwg * 8 * ws.silcap * 4, 4)) != SH_OK ||
-          (wrc = ensure(c, "obb.ws_sxy", (size_t)ws.nwg * ws.silcap * 16, 8)) != SH_OK || (wrc = ensure(c, "obb.ws_area", (size_t)ws.nwg * ws.silcap * 8, 8)) != SH_OK) return wrc;
-      for (const char* n : {"obb.ws_fmask", "obb.ws_lists", "obb.ws_sxy", "obb.ws_area"}) c->bufs[n].per_mesh = 0;
-      ws.fmask = (unsigned char*)c->bufs["obb.ws_fmask"].p; ws.lists = (unsigned*)c->bufs["obb.ws_lists"].p;
-      ws.sxy = (double2*)c->bufs["obb.ws_sxy"].p; ws.area = (double*)c->bufs["obb.ws_area"].p;
-    }
-    // SHOULDER_OBB_PRUNE=0: every direction is evaluated (the A/B of the pruning bound: same frames, tests/test_gpu_hull.py)
-    const bool prune = c->sw.obb_prune;
-    for (int pass = 0; pass < 2; ++pass) {      // seed tile, then the directions its best volume cannot exclude
-      LAUNCH(c, "k_obb_select", k_obb_select, dim3(B), dim3(256), v.obb_lb, (const int*)v.hull_nf, v.obb_lbmin_enc,
-             v.obb_best_enc, (prune || pass == 0) ? pass : 2, v.obb_dir_list, v.obb_dir_count, v.obb_seeded, hc);
-      const int nt_pass = pass == 0 ? SH_OBB_TILE / TT : ntiles;      // (the seed pass: up to SH_OBB_TILE directions)
-      dim3 cg((unsigned)(nt_pass * ((B + 7) / 8) * 8));
-      if (huge) cg.x = std::min<unsigned>(cg.x, (unsigned)ws.nwg);      // (the workspace tier: its ws.nwg workgroups walk the tiles)
-      LAUNCH(c, pass == 0 ? "k_obb_seed" : "k_obb_candidates", candidates, cg, dim3(SH_OBB_THREADS),
-             v.hull_hv, v.hull_nv, v.hull_normals, v.hull_nf, v.hull_edges, v.hull_ne, v.obb_cand_vol,
-             v.obb_cand_edge, v.err, v.obb_best_enc, v.obb_dir_list, v.obb_dir_count,
-             nt_pass, B, prune ? 1 : 0, hc, ws);
-    }
-  }
+  return SH_OK;
+}
+
+// The smallest candidate -> the raw box frame; then the ProxObb scan of a proximal humerus, or the end sections, circle fits and flip
+static int obb_frame(sh_ctx* c, const WinView& v, WinState* w) {
+  const int B = v.B;
   LAUNCH(c, "k_obb_pick", k_obb_pick, dim3(B), dim3(256), v.hull_hv, v.hull_normals, (const int*)v.hull_nf, v.hull_edges,
          v.obb_cand_vol, v.obb_cand_edge, v.verts, v.voff, v.obb_T_pre, v.obb_zb_pre, v.err, c->hcap);
   if (!c->obb_done_ev) HIPCHK(c, hipEventCreateWithFlags(&c->obb_done_ev, hipEventDisableTiming));
@@ -1138,6 +1135,15 @@ static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int re
          v.ovf_ctr + SH_CTR_END_NEED);
   c->batch.frame_computed();
   return SH_OK;
+}
+
+static int run_obb(sh_ctx* c, WinView& v, WinState* w, int prepared_slot, int redo_nf) {
+  int rc, nfmax = 1;
+  c->batch.obb_begins(c->batch_gen);      // (a new batch: the small k_obb_candidates tier and the chosen hull mode again)
+  if ((rc = obb_hulls(c, v, prepared_slot, redo_nf, &nfmax)) != SH_OK) return rc;
+  const ObbPlan plan = obb_plan(v.B, nfmax, c->hcap, c->batch.caps().sil_need, c->batch.caps().nf_over, c->sw.obb_prune);
+  if ((rc = obb_candidates(c, v, w, plan)) != SH_OK) return rc;
+  return obb_frame(c, v, w);
 }
 
 // epicondyle.py:33-89, everything that needs the distal set only: the minimum-area rectangle of every distal slice in the cut (three
@@ -1377,7 +1383,7 @@ static void start_prepare(sh_ctx* c) {
   // device pointers are looked up here: the buffer map belongs to the calling thread
   const HullPre hp = hullpre_ptrs(c);
   const HullRec dst = hull_rec(c);
-  const bool can_upload = c->obb_done_ev != nullptr;
+  const bool can_upload = early_upload_ok(c->obb_done_ev != nullptr, c->B, c->hcap, hull_rec_bytes(c));      // (the size half: always true here, sh_obb_plan.h)
   p.th = std::thread([c, hp, dst, can_upload]() {
     sh_ctx::Prepared& q = c->prep;
     if (hipSetDevice(c->device) != hipSuccess) { q.rc = SH_ERR_HIP; return; }
@@ -1525,13 +1531,10 @@ static int start_prepare_staged(sh_ctx* c, int B, std::shared_ptr<const StlJob> 
   p.key.begin_staged(c->hslot, S.B, c->batch_gen, hulls);
   prepared_reset(p);
   const HullPre hp = hullpre_ptrs(c, ".s");
-  const HullRec dst = {(double*)c->bufs["hull.hv"].p, (double*)c->bufs["hull.normals"].p, (int*)c->bufs["hull.edges"].p, (int*)c->bufs["hull.nv"].p, (int*)c->bufs["hull.nf"].p,
-                       (int*)c->bufs["hull.ne"].p};      // (the whole batch's, whatever window the context stands at)
+  const HullRec dst = hull_rec_at(c, 0);      // (the whole batch's, whatever window the context stands at)
   struct Side { long long *voff, *foff; float* verts; int* faces; } side = {(long long*)c->bufs["voff.s"].p, (long long*)c->bufs["foff.s"].p, (float*)c->bufs["verts.s"].p, (int*)c->bufs["faces.s"].p};
   // early upload only into buffers that will not be re-allocated by the commit (alloc_batch grows them for a larger batch)
-  const size_t nB = (size_t)S.B;
-  const bool can_upload = c->obb_done_ev != nullptr && dst.hv && c->bufs["hull.hv"].bytes >= nB * c->hcap.v * 24 && c->bufs["hull.normals"].bytes >= nB * c->hcap.f * 24 &&
-                          c->bufs["hull.edges"].bytes >= nB * c->hcap.e * 16 && c->bufs["hull.nv"].bytes >= nB * 4 && c->bufs["hull.nf"].bytes >= nB * 4 && c->bufs["hull.ne"].bytes >= nB * 4;
+  const bool can_upload = early_upload_ok(c->obb_done_ev != nullptr, S.B, c->hcap, hull_rec_bytes(c));
   p.th = std::thread([c, hp, dst, side, can_upload, hulls, stl, B, phase0]() {
     sh_ctx::Prepared& q = c->prep;
     sh_ctx::StageSide& S = c->stg;
@@ -1709,8 +1712,7 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, c
   const int B = tk.B;
   if (std::none_of(st.gave_up(), st.gave_up() + B, [](int f) { return f != 0; })) return SH_OK;
   std::vector<float> hv32;
-  std::vector<double> P;
-  shhull::Hull H;
+  HostHull hh;
   int rc = SH_OK;
   WindowScope whole(c, 0, B);      // (the copies below index the batch's buffers by humerus)
   for (int b = 0; b < B; ++b) {
@@ -1719,30 +1721,19 @@ static int redo_given_up(sh_ctx* c, sh_ctx::Ticket& tk, const StatusBlock& st, c
     hv32.resize(3 * (size_t)nv);
     HIPCHK(c, hipMemcpyAsync(hv32.data(), (const float*)c->bufs["verts"].p + 3 * v0, (size_t)nv * 12, hipMemcpyDeviceToHost, c->out_stream));
     HIPCHK(c, hipStreamSynchronize(c->out_stream));
-    P.assign(hv32.begin(), hv32.end());
-    if (!shhull::convex_hull(P.data(), (int)nv, H)) { char m[96]; snprintf(m, sizeof m, "mesh %d: convex hull failed (%d)", b, SH_ERR_GEOMETRY); return fail(c, SH_ERR_GEOMETRY, m); }
-    const int hn = (int)H.vert_ids.size(), fn = (int)H.tris.size() / 3, en = (int)H.edges.size() / 4;
-    if (hn > c->hcap.v || fn > c->hcap.f || en > c->hcap.e) {
+    if (!hull_of_points(hv32.data(), nv, hh)) return fail(c, SH_ERR_GEOMETRY, hull_failed_text(b, SH_ERR_GEOMETRY));
+    const int fn = hh.n.f;
+    if (!hull_fits(hh.n, c->hcap)) {
       // above the record: growing it here would drop the other humeri's records -- the batch runs again with its hulls from the
       // host (hull_host_phase sizes the staging, run_obb grows the record), and stays there while it is resident
       c->batch.hull_above_record();
       again->rerun = SH_RERUN_FORCE_HOST;
       return SH_OK;
     }
-    std::vector<double> hvd(3 * (size_t)hn);
-    for (int i = 0; i < hn; ++i)
-      for (int k = 0; k < 3; ++k) hvd[3 * (size_t)i + k] = P[3 * (size_t)H.vert_ids[i] + k];
-    const int counts[3] = {hn, fn, en}, one = 1;
+    const int one = 1;
     {
       WindowScope alone(c, b, 1);      // humerus b as a window of one: the hull record's rows, its status words and its stages
-      const HullRec h = hull_rec(c);
-      // (pageable sources: hipMemcpyAsync stages them before it returns)
-      HIPCHK(c, hipMemcpyAsync(h.hv, hvd.data(), hvd.size() * 8, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h.normals, H.normals.data(), (size_t)fn * 24, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h.edges, H.edges.data(), (size_t)en * 16, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h.nv, &counts[0], 4, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h.nf, &counts[1], 4, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(c, hipMemcpyAsync(h.ne, &counts[2], 4, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hull_upload_one(hh, hull_rec(c), c->stream));      // (pageable sources, as `one`: hipMemcpyAsync stages them before it returns)
       HIPCHK(c, hipMemcpyAsync(buf<int>(c, "hulld.skip"), &one, 4, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, hipMemsetAsync(buf<int>(c, "err"), 0, 4, c->stream));
       if (c->open_mode != SH_OPEN_ERROR) HIPCHK(c, hipMemsetAsync(buf<int>(c, "open.stats"), 0, 8, c->stream));      // (the void first pass counted too)
