@@ -134,11 +134,13 @@ int  sh_load_rfc(sh_ctx*, const int32_t* feat, const float* thr, const int32_t* 
                  const int32_t* roots, int n_trees);
 /* UNet: `packed` = concatenation, in this order, of enc{i}a_w,enc{i}a_b,enc{i}b_w,enc{i}b_b (i=0..depth-1),
  * bota_w,bota_b,botb_w,botb_b, then for i=depth-1..0: up{i}_w,up{i}_b,dec{i}a_w,dec{i}a_b,dec{i}b_w,dec{i}b_b,
- * then head_w, head_b; conv weights laid out [ky][kx][cin][cout] float32.
- * base_channels: a multiple of 32, at most 256; depth 1..6. */
+ * then head_w, head_b; conv weights laid out [ky][kx][cin][cout] float32 (csrc/sh_unet_plan.h unet_layers_in_block_order
+ * states the order and the shapes).  base_channels: a multiple of 32, at most 256; depth 1..6. */
 int  sh_load_unet(sh_ctx*, int base_channels, int depth, const float* packed, size_t n_floats);
-/* Device address + size of the packed parameter block (UNet then RFC), for a collective
- * broadcast by the caller (torch.distributed over RCCL); valid until the next sh_load_*. */
+/* Device address + size of the packed parameter block, for a collective broadcast by the caller (torch.distributed over
+ * RCCL); valid until the next sh_load_*.  The block is `packed` as sh_load_unet took it, then the arrays of sh_load_rfc in
+ * the order of its arguments (n_nodes elements each, roots n_trees), 4-byte elements, nothing between them:
+ * csrc/sh_params.h (SH_PARAM_SECTIONS) is the statement of this layout. */
 int  sh_param_block(sh_ctx*, void** dev_ptr, size_t* nbytes);
 /* After the caller has overwritten the device parameter block (the receiving ranks of a broadcast): re-read the host
  * mirrors from it, so that a later sh_load_rfc / sh_load_unet -- which re-uploads the whole block from the mirrors --

@@ -118,8 +118,8 @@ int sh_bcast_weights(sh_ctx** ctxs, int n, int root) {
     size_t nb = 0;
     if ((rc = sh_param_block(ctxs[i], &blk[i], &nb)) != SH_OK) return fail(c0, rc, "sh_bcast_weights: a context has no parameters loaded");
     if (i == 0) bytes = nb;
-    const sh_ctx *a = ctxs[i], *r = ctxs[root];
-    if (nb != bytes || a->unet_base != r->unet_base || a->unet_depth != r->unet_depth || a->rfc_nodes != r->rfc_nodes || a->rfc_trees != r->rfc_trees)
+    const sh_ctx* a = ctxs[i];
+    if (!a->pstate.same_shape(ctxs[root]->pstate))
       return fail(c0, SH_ERR_STATE, "sh_bcast_weights: the contexts hold parameter blocks of different shapes");
     HIPCHK(c0, hipSetDevice(a->device));
     HIPCHK(c0, hipStreamSynchronize(a->stream));

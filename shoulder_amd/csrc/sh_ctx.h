@@ -20,7 +20,8 @@
 // sh_run.h (the run: BatchState, the one record of what is known about the resident batch -- tier vouch, frame, capacities, OBB tier, hulls
 // from the host; PreparedKey, the caller's half of the prepared-hull record; the refusals of sh_submit in their order and its plan),
 // sh_obb_plan.h (the OBB stage: what hulls need of the record and of a pinned slot and how either grows, where a window's hulls come
-// from, the early-upload rule, and the tier, grids and workspace bytes of the stage's launches).
+// from, the early-upload rule, and the tier, grids and workspace bytes of the stage's launches), sh_params.h (the parameters: the layout
+// of the block "params", the forest check, the checks of sh_set_params, ParamState: what is loaded, which packed copies are current).
 #pragma once
 #include "../../include/shoulder_hip.h"
 
@@ -51,6 +52,7 @@
 #include "sh_hull.h"
 #include "sh_ingest.h"
 #include "sh_obb_plan.h"
+#include "sh_params.h"
 #include "sh_query.h"      // (and sh_arthro.h below it)
 #include "sh_run.h"
 #include "sh_unet_plan.h"
@@ -80,15 +82,11 @@ struct sh_ctx {
   std::map<std::string, Buf> bufs;
   // a named buffer's pointer, null when it is not there (inlined like the lambdas it replaces)
   __attribute__((always_inline)) void* at(const char* name) const { auto it = bufs.find(name); return it == bufs.end() ? nullptr : it->second.p; }
-  bool have_rfc = false, have_unet = false;
-  int rfc_nodes = 0, rfc_trees = 0;
-  int unet_base = 0, unet_depth = 0;
-  std::vector<float> h_unet;                 // packed UNet parameters (host copy)
-  std::vector<int32_t> h_feat, h_ti, h_fi, h_roots;
-  std::vector<float> h_thr, h_lw;
-  typedef sh::UnetLayer ULayer;
+  // the parameters (sh_params.h): the host copy of every section of the block "params", what is loaded and which packed copies of
+  // the block are current (ParamState: named events and queries), the loaded network's layers by name
+  sh::ParamMirror mirror;
+  sh::ParamState pstate;
   sh::UnetLayers ulayers;
-  size_t unet_floats = 0;
   void* comm = nullptr;                      // sh_comm_init_all: this context's RCCL communicator (comm.hip), its rank and the group's size
   int comm_rank = -1, comm_n = 0;
   // sh_set_keep_products: every plane's resampled contour and polar rows leave k_resample_polar (k_slices.h, RsWant); off: the rows
@@ -199,11 +197,7 @@ struct sh_ctx {
     std::map<std::tuple<int, int, int>, std::pair<int, int>> tk_tabs;      // (items, workgroups, cout groups) -> (offset, tickets) in "unet16.tk_tab"
     int tk_tab_used = 0;
     bool zero_page_ready = false;    // "unet16.zero" is cleared
-    bool packtab_ready = false;      // "unet16.packtab" holds the layer table of the loaded network (reset by sh_load_unet)
-    bool packed_x3 = false;          // "params_x3h/l" hold the split weights of the CURRENT parameter block
-    int packed_kind = -1;            // element kind (0 bf16, 1 f16) "params_bf16" was packed for from the CURRENT parameter block; -1: repack
   } unet;
-  bool packed_rfc = false;           // "rfc.nodes" holds the packed forest of the CURRENT parameter block
   // timing
   int timing = 0;      // 0 off, 1 every launch, 2 UNet layers only
   std::vector<std::tuple<std::string, hipEvent_t, hipEvent_t>> pending;
@@ -237,9 +231,6 @@ struct StreamScope {
   ~StreamScope() { c->stream = saved; }
   StreamScope(const StreamScope&) = delete; StreamScope& operator=(const StreamScope&) = delete;
 };
-
-// the parameter block can change: sh_load_*, sh_param_block (the pointer goes to the caller), sh_param_block_commit, a store to "params"
-static inline void params_changed(sh_ctx* c) { c->unet.packed_kind = -1; c->unet.packed_x3 = false; c->packed_rfc = false; }
 
 static inline int fail(sh_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;

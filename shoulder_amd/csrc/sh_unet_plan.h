@@ -1,9 +1,10 @@
-// sh_unet_plan.h -- what the UNet runner decides on the host before it launches anything: the steps of one forward pass (which kernel
-// with which template arguments, grid, block, tensors, fusions, work tickets), the run-length table of a ticketed launch, and the
-// layer table of the weight-packing kernels.  No kernels, no HIP types: unet.hip includes it, and so does a plain g++
+// sh_unet_plan.h -- what the UNet runner decides on the host before it launches anything: the layers of a network in the order of the
+// parameter block (what sh_load_unet takes), the steps of one forward pass (which kernel with which template arguments, grid, block,
+// tensors, fusions, work tickets), the run-length table of a ticketed launch, and the layer table of the weight-packing kernels.  No kernels, no HIP types: unet.hip includes it, and so does a plain g++
 // (tests/hostcheck/unet_plan_check.cpp).  unet.hip holds the constants restated here against the kernel headers (static_assert).
 #pragma once
 #include "../../include/shoulder_hip.h"
+#include "sh_common.h"      // (SH_UNET_MAXBASE)
 
 #include <algorithm>
 #include <cmath>
@@ -17,6 +18,51 @@ namespace sh {
 struct UnetLayer { size_t w_off, b_off; int cin, cout, taps; };      // offsets in floats into the parameter block
 typedef std::map<std::string, UnetLayer> UnetLayers;
 struct UnetError { int code; std::string text; };      // code SH_OK: accepted
+
+// The layers of the double-conv UNet in the order their parameters lie in the block (each layer's weights [taps][cin][cout], then its
+// bias), with their offsets; *n_floats: the floats of the whole network.  The one statement of sh_load_unet's `packed` order.
+struct UnetNamedLayer { std::string name; UnetLayer L; };
+static inline std::vector<UnetNamedLayer> unet_layers_in_block_order(int base, int depth, size_t* n_floats) {
+  std::vector<UnetNamedLayer> out;
+  size_t o = 0;
+  auto add = [&](const std::string& name, int taps, int cin, int cout) {
+    const size_t nw = (size_t)taps * cin * cout;
+    out.push_back({name, UnetLayer{o, o + nw, cin, cout, taps}});
+    o += nw + cout;
+  };
+  auto ch = [base](int i) { return base << i; };
+  for (int i = 0; i < depth; ++i) {
+    add("enc" + std::to_string(i) + "a", 9, i ? ch(i - 1) : 1, ch(i));
+    add("enc" + std::to_string(i) + "b", 9, ch(i), ch(i));
+  }
+  add("bota", 9, ch(depth - 1), ch(depth));
+  add("botb", 9, ch(depth), ch(depth));
+  for (int i = depth - 1; i >= 0; --i) {
+    add("up" + std::to_string(i), 4, ch(i + 1), ch(i));
+    add("dec" + std::to_string(i) + "a", 9, 2 * ch(i), ch(i));
+    add("dec" + std::to_string(i) + "b", 9, ch(i), ch(i));
+  }
+  add("head", 1, ch(0), 1);
+  *n_floats = o;
+  return out;
+}
+// ... their names (the caller's arrays are <name>_w, <name>_b)
+static inline std::vector<std::string> unet_layer_names(int depth) {
+  size_t n;
+  std::vector<std::string> names;
+  for (const UnetNamedLayer& l : unet_layers_in_block_order(32, depth, &n)) names.push_back(l.name);
+  return names;
+}
+// ... by name, for the networks the kernels are sized for: what sh_load_unet takes
+#define SH_UNET_SHAPE_REFUSAL "sh_load_unet: bad argument (base must be a multiple of 32, at most 256; depth 1..6)"
+static inline UnetError unet_layer_table(int base, int depth, UnetLayers* out, size_t* n_floats) {
+  static_assert(SH_UNET_MAXBASE == 256, "SH_UNET_SHAPE_REFUSAL names the largest base");
+  out->clear();
+  *n_floats = 0;
+  if (depth < 1 || depth > 6 || base < 32 || base % 32 != 0 || base > SH_UNET_MAXBASE) return {SH_ERR_ARG, SH_UNET_SHAPE_REFUSAL};
+  for (const UnetNamedLayer& l : unet_layers_in_block_order(base, depth, n_floats)) (*out)[l.name] = l.L;
+  return {SH_OK, {}};
+}
 
 // restated from the kernel headers: tile and block sizes, fusion flags (k_unet_bf16.h), the weight scale of the split-f16 operands
 enum { PL_TILE = 16, PL_UN_THREADS = 256, PL_UD_THREADS = 512, PL_UPR_THREADS = 512, PL_UPC_THREADS = 256, PL_UXR_THREADS = 512 };

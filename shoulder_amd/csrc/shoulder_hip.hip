@@ -96,11 +96,7 @@ extern "C" {
 
 int sh_default_params(sh_params* p) {
   if (!p) return SH_ERR_ARG;
-  p->canal_cutoff[0] = 0.35; p->canal_cutoff[1] = 0.75;
-  p->groove_cutoff[0] = 0.2; p->groove_cutoff[1] = 0.75;
-  p->groove_deg_window = 7.0;
-  p->unet_dtype = SH_UNET_F32;
-  p->bone_kind = SH_BONE_HUMERUS;
+  *p = sh::default_run_params();
   return SH_OK;
 }
 
@@ -270,19 +266,8 @@ const char* sh_last_error(const sh_ctx* c) { return c ? c->err.c_str() : "null c
 
 int sh_set_params(sh_ctx* c, const sh_params* p) {
   if (!c || !p) return SH_ERR_ARG;
-  for (double x : {p->groove_cutoff[0], p->groove_cutoff[1], p->canal_cutoff[0], p->canal_cutoff[1]})
-    if (!(x >= 0.0 && x <= 1.0)) return fail(c, SH_ERR_ARG, "cut-off fractions must lie in [0, 1]");
-  int a, b;
-  cutoff_range(SH_NPROX, p->groove_cutoff[0], p->groove_cutoff[1], &a, &b);
-  if (b - a != SH_GROOVE_NROWS) return fail(c, SH_ERR_ARG, "groove_cutoff must select 330 proximal rows");
-  cutoff_range(SH_NFULL, p->canal_cutoff[0], p->canal_cutoff[1], &a, &b);
-  if (b - a < 2 || a < 0 || b > SH_NFULL) return fail(c, SH_ERR_ARG, "canal_cutoff selects fewer than 2 slices");
-  // the search window of the groove's local minimum is +-round(deg_window / (360 / 512)) samples of a 512-sample row
-  // (bicipital_groove.py:190-229); beyond half a turn the reference's negative indices run off the row (IndexError there)
-  if (!(p->groove_deg_window >= 0.0 && p->groove_deg_window <= 180.0)) return fail(c, SH_ERR_ARG, "groove_deg_window must lie in [0, 180] degrees");
-  if (p->unet_dtype != SH_UNET_F32 && p->unet_dtype != SH_UNET_BF16 && p->unet_dtype != SH_UNET_F16 && p->unet_dtype != SH_UNET_F32X)
-    return fail(c, SH_ERR_ARG, "unet_dtype must be SH_UNET_F32, SH_UNET_F32X, SH_UNET_BF16 or SH_UNET_F16");
-  if (p->bone_kind != SH_BONE_HUMERUS && p->bone_kind != SH_BONE_PROXIMAL) return fail(c, SH_ERR_ARG, "bone_kind must be SH_BONE_HUMERUS or SH_BONE_PROXIMAL");
+  const sh::ParamError e = sh::run_params_check(*p);
+  if (e.code != SH_OK) return fail(c, e.code, e.text);
   if (c->prep.key.active && p->bone_kind != c->params.bone_kind) (void)join_prepared(c);
   c->params = *p;
   c->batch.params_set();
@@ -632,7 +617,7 @@ int sh_buffer_device(sh_ctx* c, const char* name, void** dev_ptr, size_t* nbytes
   if (it == c->bufs.end() || !it->second.p) return fail(c, SH_ERR_ARG, std::string("no buffer named ") + name);
   *dev_ptr = it->second.p;
   if (nbytes) *nbytes = it->second.bytes;
-  if (std::string(name) == "params") params_changed(c);      // (the caller may write it)
+  if (std::string(name) == "params") c->pstate.block_exposed();      // (the caller may write it)
   c->batch.buffer_touched(name, false);      // (... or a frame / an intermediate that moves the planes: the overflow tier runs again)
   return SH_OK;
 }
@@ -656,7 +641,7 @@ int sh_store(sh_ctx* c, const char* name, const void* host, size_t nbytes) {
   HIPCHK(c, hipSetDevice(c->device));
   if (std::string(name) == "verts") { discard_staged(c); (void)join_prepared(c); ++c->batch_gen; c->h_verts_valid = false; drop_closest(c); }
   c->batch.buffer_touched(name, false);      // (an injected frame or intermediate moves the planes: the overflow tier runs again)
-  if (std::string(name) == "params") params_changed(c);
+  if (std::string(name) == "params") c->pstate.block_exposed();
   HIPCHK(c, hipMemcpyAsync(it->second.p, host, nbytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->batch.buffer_touched(name, true);
@@ -1226,28 +1211,27 @@ static int stage_canal(sh_ctx* c, const WinView& v) {
 static int stage_groove(sh_ctx* c, const WinView& v, uint32_t mask) {
   const int B = v.B;
   int rc;
-  if (!c->have_rfc) return fail(c, SH_ERR_STATE, "sh_run: groove stage needs sh_load_rfc first");
+  if (!c->pstate.has_rfc()) return fail(c, SH_ERR_STATE, "sh_run: groove stage needs sh_load_rfc first");
   int ga, gb;
   cutoff_range(SH_NPROX, c->params.groove_cutoff[0], c->params.groove_cutoff[1], &ga, &gb);
   // the centred polar rows [ga, gb) come from the proximal set's resampling, which writes the rows of ITS run's cut-off range (RsWant)
   if (!(mask & SH_STAGE_PROXIMAL) && !(c->rs_gen == c->batch_gen && (c->rs_all || (ga >= c->rs_cs_lo && gb <= c->rs_cs_hi))))
     return fail(c, SH_ERR_STATE, "sh_run: SH_STAGE_GROOVE without SH_STAGE_PROXIMAL, and the proximal slices of this batch were not made for this groove_cutoff (run SH_STAGE_PROXIMAL again)");
-  const char* pp = buf<char>(c, "params") + c->unet_floats * 4;
-  const size_t N = c->h_feat.size();
-  const int* feat = (const int*)pp; const float* thr = (const float*)(pp + N * 4); const int* ti = (const int*)(pp + N * 8);
-  const int* fi = (const int*)(pp + N * 12); const float* lw = (const float*)(pp + N * 16); const int* roots = (const int*)(pp + N * 20);
+  const ParamShape& ps = c->pstate.shape();
+  const ForestView forest(buf<char>(c, "params"), ParamLayout(ps));
+  const size_t N = ps.nodes;
   const double* prox_zs = v.set[SET_PROX].zs;
   LAUNCH(c, "k_groove_rows", k_groove_rows, dim3(B * SH_GROOVE_NROWS), dim3(64), v.prox_itr_centered_start, prox_zs, v.canal_axis_ct, ga, v.groove_xraw,
          v.groove_ptheta, v.groove_npk, v.groove_r0, v.err, B);
   LAUNCH(c, "k_groove_scale", k_groove_scale, dim3(B), dim3(256), v.groove_xraw, v.groove_npk, v.groove_stats, B, v.groove_slots, v.groove_nslot, v.groove_proba);
   if ((rc = ensure(c, "rfc.nodes", N * 16, 4)) != SH_OK) return rc;
   int4* nodes = (int4*)c->bufs["rfc.nodes"].p;
-  if (!c->packed_rfc) {      // once per parameter block (it was a launch of every step's chain: 5 us alone, ~50 us beside a UNet pass)
-    LAUNCH(c, "k_rfc_pack", k_rfc_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), feat, thr, ti, fi, lw, nodes, (int)N);
-    c->packed_rfc = true;
+  if (c->pstate.need_forest_pack()) {      // once per parameter block (it was a launch of every step's chain: 5 us alone, ~50 us beside a UNet pass)
+    LAUNCH(c, "k_rfc_pack", k_rfc_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), forest.feat, forest.thr, forest.ti, forest.fi, forest.lw, nodes, (int)N);
+    c->pstate.forest_packed();
   }
   LAUNCH(c, "k_groove_rfc", k_groove_rfc, dim3((unsigned)(B * ((SH_GSLOTS + 63) / 64))), dim3(64), v.groove_xraw, v.groove_slots, v.groove_nslot,
-         v.groove_stats, nodes, roots, c->rfc_trees, v.groove_xs, v.groove_proba, B);
+         v.groove_stats, nodes, forest.roots, (int)ps.trees, v.groove_xs, v.groove_proba, B);
   LAUNCH(c, "k_groove_tail", k_groove_tail, dim3(B), dim3(256), v.groove_ptheta, v.groove_proba, v.groove_bg_theta, v.err,
          v.prox_itr_centered_start, v.groove_r0, prox_zs, v.set[SET_PROX].centroids, ga, c->params.groove_deg_window,
          v.groove_local_idx, v.groove_points_obb, v.obb_transform, v.groove_axis_ct, v.groove_points_ct);
@@ -1257,12 +1241,12 @@ static int stage_groove(sh_ctx* c, const WinView& v, uint32_t mask) {
 static int stage_anp(sh_ctx* c, const WinView& v) {
   const int B = v.B;
   int rc;
-  if (!c->have_unet) return fail(c, SH_ERR_STATE, "sh_run: anatomic-neck stage needs sh_load_unet first");
+  if (!c->pstate.has_unet()) return fail(c, SH_ERR_STATE, "sh_run: anatomic-neck stage needs sh_load_unet first");
   LAUNCH(c, "k_anp_rows", k_anp_rows, dim3(B * SH_ANP_ROWS), dim3(64), v.prox_itr_start, v.groove_bg_theta, v.anp_raw, v.anp_t01, v.anp_roll, B,
          v.anp_mm_enc);      // (+ the image's minimum / maximum: no second pass over it)
   // MinMaxScaler (anatomic_neck.py:56-58): the 16-bit network's first kernel applies it where it reads its patches (k_unet16_l0.h) --
   // no f32 image, 201 MB less traffic and a launch less per step; the other forms of the network and sh_set_keep_products get "anp.image"
-  const bool scale_in_net = plan_level0_fused(c->params.unet_dtype, c->unet.reference, c->unet_base, c->unet_depth, SH_ANP_ROWS, SH_MPROX);
+  const bool scale_in_net = plan_level0_fused(c->params.unet_dtype, c->unet.reference, c->pstate.shape().base, c->pstate.shape().depth, SH_ANP_ROWS, SH_MPROX);
   if (!scale_in_net || c->keep_products) LAUNCH(c, "k_anp_scale", k_anp_scale, dim3(64, B), dim3(256), v.anp_raw, v.anp_mm_enc, v.anp_image);
   if ((rc = unet_turn_enter(c)) != SH_OK) return rc;
   rc = unet_dispatch(c, {v.anp_image, scale_in_net ? v.anp_raw : nullptr, scale_in_net ? v.anp_mm_enc : nullptr, v.anp_logits}, B, SH_ANP_ROWS, SH_MPROX);
@@ -2044,90 +2028,49 @@ int sh_landmarks_device(sh_ctx* c, void** p, size_t* n) {
   return *p ? SH_OK : SH_ERR_STATE;
 }
 
-// ---- parameters ------------------------------------------------------------------------------------
-static int upload_params(sh_ctx* c) {
-  params_changed(c);
-  const size_t N = c->h_feat.size(), T = c->h_roots.size();
-  const size_t bytes = c->unet_floats * 4 + N * 4 * 5 + T * 4;
-  int rc = ensure(c, "params", bytes ? bytes : 16, 4);
-  if (rc != SH_OK) return rc;
-  char* p = buf<char>(c, "params");
-  size_t o = 0;
-  auto put = [&](const void* src, size_t n) -> hipError_t {
-    hipError_t e = n ? hipMemcpyAsync(p + o, src, n, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-    o += n;
-    return e;
-  };
-  HIPCHK(c, put(c->h_unet.data(), c->unet_floats * 4));
-  HIPCHK(c, put(c->h_feat.data(), N * 4));
-  HIPCHK(c, put(c->h_thr.data(), N * 4));
-  HIPCHK(c, put(c->h_ti.data(), N * 4));
-  HIPCHK(c, put(c->h_fi.data(), N * 4));
-  HIPCHK(c, put(c->h_lw.data(), N * 4));
-  HIPCHK(c, put(c->h_roots.data(), T * 4));
+// ---- parameters (sh_params.h: the layout of the block, the forest check, ParamState) --------------------------------------------------
+// every section between the block at `p` and a mirror laid out for it; `up`: host to device
+static int copy_block(sh_ctx* c, char* p, ParamMirror& m, const ParamLayout& L, bool up) {
+  hipError_t copied = hipSuccess;
+  m.each(L, [&](void* host, size_t off, size_t n) {
+    if (n && copied == hipSuccess) copied = up ? hipMemcpyAsync(p + off, host, n, hipMemcpyHostToDevice, c->stream) : hipMemcpyAsync(host, p + off, n, hipMemcpyDeviceToHost, c->stream);
+  });
+  HIPCHK(c, copied);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
+}
+
+// the whole block again from the mirrors, at the loaded shape.  A failure leaves nothing loaded: the block may be gone (ensure frees
+// it before it allocates), so neither half may stay "loaded" over it
+static int upload_params(sh_ctx* c) {
+  c->pstate.block_exposed();
+  const ParamLayout L(c->pstate.shape());
+  int rc = ensure(c, "params", L.total ? L.total : 16, 4);
+  if (rc == SH_OK) rc = copy_block(c, buf<char>(c, "params"), c->mirror, L, true);
+  if (rc != SH_OK) { c->pstate.block_lost(); c->mirror = ParamMirror(); c->ulayers.clear(); }
+  return rc;
 }
 
 int sh_load_rfc(sh_ctx* c, const int32_t* feat, const float* thr, const int32_t* ti, const int32_t* fi, const float* lw, int n_nodes,
                 const int32_t* roots, int n_trees) {
   if (!c || !feat || !thr || !ti || !fi || !lw || !roots || n_nodes <= 0 || n_trees <= 0) return fail(c, SH_ERR_ARG, "sh_load_rfc: bad argument");
-  for (int i = 0; i < n_nodes; ++i) {
-    if (feat[i] < 0 || feat[i] >= 9) return fail(c, SH_ERR_ARG, "sh_load_rfc: feature id out of range");
-    if ((ti[i] < 0) != (fi[i] < 0) || ti[i] >= n_nodes || fi[i] >= n_nodes) return fail(c, SH_ERR_ARG, "sh_load_rfc: bad child index");
-  }
-  for (int t = 0; t < n_trees; ++t) if (roots[t] < 0 || roots[t] >= n_nodes) return fail(c, SH_ERR_ARG, "sh_load_rfc: bad root");
-  {      // the walk on the device loops until it meets a leaf: every node must be reached once at most (a forest, no cycle)
-    std::vector<char> seen(n_nodes, 0);
-    std::vector<int> stack;
-    for (int t = 0; t < n_trees; ++t) {
-      stack.push_back(roots[t]);
-      while (!stack.empty()) {
-        const int i = stack.back(); stack.pop_back();
-        if (seen[i]) return fail(c, SH_ERR_ARG, "sh_load_rfc: the node tables do not describe a forest (a node is reachable twice)");
-        seen[i] = 1;
-        if (ti[i] >= 0) { stack.push_back(ti[i]); stack.push_back(fi[i]); }
-      }
-    }
-  }
+  const ParamError e = forest_check(feat, ti, fi, n_nodes, roots, n_trees);
+  if (e.code != SH_OK) return fail(c, e.code, std::string("sh_load_rfc: ") + e.text);
   HIPCHK(c, hipSetDevice(c->device));
-  c->h_feat.assign(feat, feat + n_nodes); c->h_thr.assign(thr, thr + n_nodes); c->h_ti.assign(ti, ti + n_nodes);
-  c->h_fi.assign(fi, fi + n_nodes); c->h_lw.assign(lw, lw + n_nodes); c->h_roots.assign(roots, roots + n_trees);
-  c->rfc_nodes = n_nodes; c->rfc_trees = n_trees; c->have_rfc = true; c->packed_rfc = false;
+  ParamMirror& m = c->mirror;
+  m.feat.assign(feat, feat + n_nodes); m.thr.assign(thr, thr + n_nodes); m.ti.assign(ti, ti + n_nodes);
+  m.fi.assign(fi, fi + n_nodes); m.lw.assign(lw, lw + n_nodes); m.roots.assign(roots, roots + n_trees);
+  c->pstate.rfc_loaded(n_nodes, n_trees);
   return upload_params(c);
 }
 
 int sh_load_unet(sh_ctx* c, int base, int depth, const float* packed, size_t n_floats) {
-  if (!c || !packed || depth < 1 || depth > 6 || base < 32 || base % 32 != 0 || base > SH_UNET_MAXBASE)
-    return fail(c, SH_ERR_ARG, "sh_load_unet: bad argument (base must be a multiple of 32, at most 256; depth 1..6)");
-  HIPCHK(c, hipSetDevice(c->device));
   // The layer table is built aside and swapped in together with the parameters only after the size check: a rejected
   // call leaves the loaded network (table, host copy, device block) as it was.
-  std::map<std::string, sh_ctx::ULayer> layers;
+  UnetLayers layers;
   size_t o = 0;
-  auto add = [&](const std::string& name, int taps, int cin, int cout) {
-    sh_ctx::ULayer L;
-    L.taps = taps; L.cin = cin; L.cout = cout;
-    L.w_off = o; o += (size_t)taps * cin * cout;
-    L.b_off = o; o += cout;
-    layers[name] = L;
-  };
-  std::vector<int> ch(depth + 1);
-  for (int i = 0; i <= depth; ++i) ch[i] = base << i;
-  int cin = 1;
-  for (int i = 0; i < depth; ++i) {
-    add("enc" + std::to_string(i) + "a", 9, cin, ch[i]);
-    add("enc" + std::to_string(i) + "b", 9, ch[i], ch[i]);
-    cin = ch[i];
-  }
-  add("bota", 9, ch[depth - 1], ch[depth]);
-  add("botb", 9, ch[depth], ch[depth]);
-  for (int i = depth - 1; i >= 0; --i) {
-    add("up" + std::to_string(i), 4, ch[i + 1], ch[i]);
-    add("dec" + std::to_string(i) + "a", 9, 2 * ch[i], ch[i]);
-    add("dec" + std::to_string(i) + "b", 9, ch[i], ch[i]);
-  }
-  { sh_ctx::ULayer L; L.taps = 1; L.cin = ch[0]; L.cout = 1; L.w_off = o; o += ch[0]; L.b_off = o; o += 1; layers["head"] = L; }
+  if (!c || !packed || unet_layer_table(base, depth, &layers, &o).code != SH_OK) return fail(c, SH_ERR_ARG, SH_UNET_SHAPE_REFUSAL);
+  HIPCHK(c, hipSetDevice(c->device));
   if (o != n_floats) {
     char m[160];
     snprintf(m, sizeof m, "sh_load_unet: expected %zu floats for base=%d depth=%d, got %zu", o, base, depth, n_floats);
@@ -2137,68 +2080,36 @@ int sh_load_unet(sh_ctx* c, int base, int depth, const float* packed, size_t n_f
     if (!std::isfinite(packed[i])) return fail(c, SH_ERR_ARG, "sh_load_unet: NaN / infinite parameter");
   (void)hipStreamSynchronize(c->stream);      // no forward of the previous network is still reading the block
   c->ulayers.swap(layers);
-  c->unet.packtab_ready = false;
-  c->h_unet.assign(packed, packed + n_floats);
-  c->unet_floats = n_floats; c->unet_base = base; c->unet_depth = depth; c->have_unet = true;
-  int rc = upload_params(c);
-  if (rc != SH_OK) { c->have_unet = false; c->ulayers.clear(); }
-  return rc;
+  c->mirror.unet.assign(packed, packed + n_floats);
+  c->pstate.unet_loaded(base, depth, n_floats);
+  return upload_params(c);
 }
 
 int sh_param_block_commit(sh_ctx* c) {
   if (!c) return SH_ERR_ARG;
-  params_changed(c);
+  c->pstate.block_exposed();
   auto it = c->bufs.find("params");
   if (it == c->bufs.end()) return fail(c, SH_ERR_STATE, "sh_param_block_commit: no parameters loaded");
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t N = c->h_feat.size(), T = c->h_roots.size();
-  std::vector<float> unet(c->unet_floats), thr(N), lw(N);
-  std::vector<int32_t> feat(N), ti(N), fi(N), roots(T);
-  const char* p = (const char*)it->second.p;
-  size_t o = 0;
-  auto get = [&](void* dst, size_t n) -> hipError_t {
-    hipError_t e = n ? hipMemcpyAsync(dst, p + o, n, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    o += n;
-    return e;
-  };
-  HIPCHK(c, get(unet.data(), c->unet_floats * 4));
-  HIPCHK(c, get(feat.data(), N * 4));
-  HIPCHK(c, get(thr.data(), N * 4));
-  HIPCHK(c, get(ti.data(), N * 4));
-  HIPCHK(c, get(fi.data(), N * 4));
-  HIPCHK(c, get(lw.data(), N * 4));
-  HIPCHK(c, get(roots.data(), T * 4));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const ParamShape& s = c->pstate.shape();
+  ParamMirror m;
+  m.resize(s);
+  const int rc = copy_block(c, (char*)it->second.p, m, ParamLayout(s), false);
+  if (rc != SH_OK) return rc;
   // the device walks the forest until it meets a leaf: what arrived must still be a forest over the same node count
-  for (size_t i = 0; i < N; ++i) {
-    if (feat[i] < 0 || feat[i] >= 9) return fail(c, SH_ERR_ARG, "sh_param_block_commit: feature id out of range in the device block");
-    if ((ti[i] < 0) != (fi[i] < 0) || ti[i] >= (int)N || fi[i] >= (int)N) return fail(c, SH_ERR_ARG, "sh_param_block_commit: bad child index in the device block");
-  }
-  {
-    std::vector<char> seen(N, 0);
-    std::vector<int> stack;
-    for (size_t t = 0; t < T; ++t) {
-      if (roots[t] < 0 || roots[t] >= (int)N) return fail(c, SH_ERR_ARG, "sh_param_block_commit: bad root in the device block");
-      stack.push_back(roots[t]);
-      while (!stack.empty()) {
-        const int i = stack.back(); stack.pop_back();
-        if (seen[i]) return fail(c, SH_ERR_ARG, "sh_param_block_commit: the device block does not describe a forest");
-        seen[i] = 1;
-        if (ti[i] >= 0) { stack.push_back(ti[i]); stack.push_back(fi[i]); }
-      }
-    }
-  }
-  c->h_unet.swap(unet); c->h_feat.swap(feat); c->h_thr.swap(thr); c->h_ti.swap(ti); c->h_fi.swap(fi); c->h_lw.swap(lw); c->h_roots.swap(roots);
+  const ParamError e = forest_check(m.feat.data(), m.ti.data(), m.fi.data(), (int)s.nodes, m.roots.data(), (int)s.trees);
+  if (e.code != SH_OK) return fail(c, e.code, std::string("sh_param_block_commit: ") + e.text + " in the device block");
+  c->mirror = std::move(m);
   return SH_OK;
 }
 
 int sh_param_block(sh_ctx* c, void** p, size_t* n) {
   if (!c || !p || !n) return SH_ERR_ARG;
-  params_changed(c);      // the caller may write the block from here on (and confirms with sh_param_block_commit)
+  c->pstate.block_exposed();      // the caller may write the block from here on (and confirms with sh_param_block_commit)
   auto it = c->bufs.find("params");
   if (it == c->bufs.end()) return fail(c, SH_ERR_STATE, "sh_param_block: no parameters loaded");
   *p = it->second.p;
-  *n = c->unet_floats * 4 + c->h_feat.size() * 20 + c->h_roots.size() * 4;
+  *n = ParamLayout(c->pstate.shape()).total;
   return SH_OK;
 }
 

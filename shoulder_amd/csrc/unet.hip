@@ -84,20 +84,21 @@ struct UnetView {
 static int unet_view(sh_ctx* c, const UnetIO& io, int nimg, int H, int W, UnetView* v) {
   const int dtype = c->params.unet_dtype, es = unet_is16(dtype) ? 2 : 4;
   const std::string pre = unet_is16(dtype) ? "unet16." : "unet.";
-  const size_t full = (size_t)nimg * H * W * c->unet_base * es;
+  const ParamShape& ps = c->pstate.shape();
+  const size_t full = (size_t)nimg * H * W * ps.base * es;
   *v = UnetView{};
   v->io = io; v->nimg = nimg; v->P = buf<float>(c, "params");
   v->act[US_IMAGE] = (void*)io.image; v->act[US_LOGITS] = io.logits;
   int rc;
   if ((rc = ensure(c, (pre + "a").c_str(), full, es, &v->act[US_A])) != SH_OK) return rc;
   if ((rc = ensure(c, (pre + "b").c_str(), full, es, &v->act[US_B])) != SH_OK) return rc;
-  for (int i = 0; i < c->unet_depth; ++i)      // H*W/4^i * base*2^i
+  for (int i = 0; i < ps.depth; ++i)      // H*W/4^i * base*2^i
     if ((rc = ensure(c, (pre + "skip" + std::to_string(i)).c_str(), full >> i, es, &v->act[US_SKIP + i])) != SH_OK) return rc;
   if (dtype == SH_UNET_F32X) {
-    if ((rc = ensure(c, "params_x3h", c->unet_floats * 2, 2, (void**)&v->wh)) != SH_OK) return rc;
-    if ((rc = ensure(c, "params_x3l", c->unet_floats * 2, 2, (void**)&v->wl)) != SH_OK) return rc;
+    if ((rc = ensure(c, "params_x3h", ps.unet_floats * 2, 2, (void**)&v->wh)) != SH_OK) return rc;
+    if ((rc = ensure(c, "params_x3l", ps.unet_floats * 2, 2, (void**)&v->wl)) != SH_OK) return rc;
   } else if (unet_is16(dtype)) {
-    if ((rc = ensure(c, "params_bf16", c->unet_floats * 2, 2, (void**)&v->PW)) != SH_OK) return rc;
+    if ((rc = ensure(c, "params_bf16", ps.unet_floats * 2, 2, (void**)&v->PW)) != SH_OK) return rc;
     if ((rc = ensure(c, "unet16.tickets", SH_UNET_TICKETS * 4, 4, (void**)&v->tickets)) != SH_OK) return rc;
     if ((rc = ensure(c, "unet16.tk_tab", SH_UNET_TKTAB * 4, 4, (void**)&v->tk_tab)) != SH_OK) return rc;
     if ((rc = ensure(c, "unet16.zero", 256, 2, (void**)&v->zero)) != SH_OK) return rc;
@@ -108,26 +109,26 @@ static int unet_view(sh_ctx* c, const UnetIO& io, int nimg, int H, int W, UnetVi
 // The MFMA layers' weights in the form the kernels read -- 16-bit (kind 0 bf16, 1 f16) or split into f16 high / low parts (kind -1):
 // one launch for all layers, once per parameter block; the layer table goes up once per loaded network.
 static int pack_weights(sh_ctx* c, const UnetView& v, int kind) {
-  sh_ctx::Unet& u = c->unet;
-  if (kind < 0 ? u.packed_x3 : u.packed_kind == kind) return SH_OK;
+  ParamState& ps = c->pstate;
+  if (!(kind < 0 ? ps.need_pack_x3() : ps.need_pack16(kind))) return SH_OK;
   std::vector<PackRow> tab;
   long long total = 0;
-  const UnetError e = pack_table(c->ulayers, &tab, &total, kind < 0 ? c->h_unet.data() : nullptr, c->h_unet.size());
+  const UnetError e = pack_table(c->ulayers, &tab, &total, kind < 0 ? c->mirror.unet.data() : nullptr, c->mirror.unet.size());
   if (e.code != SH_OK) return fail(c, e.code, e.text);
   int rc;
   PackEntry* dtab = nullptr;
   if ((rc = ensure(c, "unet16.packtab", tab.size() * sizeof(PackRow), 8, (void**)&dtab)) != SH_OK) return rc;
-  if (!u.packtab_ready) {
+  if (ps.need_packtab()) {
     HIPCHK(c, hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(PackRow), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));      // `tab` is a local
-    u.packtab_ready = true;
+    ps.packtab_uploaded();
   }
   if (kind < 0) {
     LAUNCH(c, "k_pack_w_x3", k_pack_w_x3, dim3(2048), dim3(256), v.P, v.wh, v.wl, (const PackEntry*)dtab, (int)tab.size(), total);
-    u.packed_x3 = true;
+    ps.packed_x3();
   } else {
     LAUNCH(c, "k_pack_w_bf16", (kind ? k_pack_w16_all<1> : k_pack_w16_all<0>), dim3(2048), dim3(256), v.P, v.PW, (const PackEntry*)dtab, (int)tab.size(), total);
-    u.packed_kind = kind;
+    ps.packed16(kind);
   }
   return SH_OK;
 }
@@ -296,7 +297,7 @@ int unet_dispatch(sh_ctx* c, const UnetIO& io, int nimg, int H, int W) {
   const int dtype = c->params.unet_dtype;
   const bool b16 = unet_is16(dtype);
   std::vector<UnetStep> steps;
-  const UnetError e = unet_plan(c->ulayers, c->unet_base, c->unet_depth, dtype, c->unet.reference, H, W, nimg, b16 ? persistent_grid(c) : 0, io.raw != nullptr, &steps);
+  const UnetError e = unet_plan(c->ulayers, c->pstate.shape().base, c->pstate.shape().depth, dtype, c->unet.reference, H, W, nimg, b16 ? persistent_grid(c) : 0, io.raw != nullptr, &steps);
   if (e.code != SH_OK) return fail(c, e.code, e.text);
   UnetView v;
   int rc;

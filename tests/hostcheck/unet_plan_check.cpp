@@ -6,26 +6,9 @@
 #include "../../shoulder_amd/csrc/sh_unet_plan.h"
 #include <cstring>
 
-static sh::UnetLayers layer_table(int base, int depth, size_t* n_floats) {
+static sh::UnetLayers layer_table(int base, int depth, size_t* n_floats) {      // (the product's: a refused shape gives an empty table)
   sh::UnetLayers layers;
-  size_t o = 0;
-  auto add = [&](const std::string& name, int taps, int cin, int cout) {
-    layers[name] = sh::UnetLayer{o, o + (size_t)taps * cin * cout, cin, cout, taps};
-    o += (size_t)taps * cin * cout + cout;
-  };
-  for (int i = 0, cin = 1; i < depth; cin = base << i, ++i) {
-    add("enc" + std::to_string(i) + "a", 9, cin, base << i);
-    add("enc" + std::to_string(i) + "b", 9, base << i, base << i);
-  }
-  add("bota", 9, base << (depth - 1), base << depth);
-  add("botb", 9, base << depth, base << depth);
-  for (int i = depth - 1; i >= 0; --i) {
-    add("up" + std::to_string(i), 4, base << (i + 1), base << i);
-    add("dec" + std::to_string(i) + "a", 9, 2 * (base << i), base << i);
-    add("dec" + std::to_string(i) + "b", 9, base << i, base << i);
-  }
-  add("head", 1, base, 1);
-  *n_floats = o;
+  sh::unet_layer_table(base, depth, &layers, n_floats);
   return layers;
 }
 
