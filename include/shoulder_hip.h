@@ -1054,6 +1054,42 @@ int sh_geodesic(sh_ctx*, int mode, int K, double max_dist, const int32_t* src_of
                 const double* d0 /* host, nullable */, double* dist /* K sumV, host, nullable */, int32_t* pred /* K sumV, host, nullable */,
                 int32_t* source /* K sumV, host, nullable */, void* info /* B K x SH_GEO_INFO_BYTES, host, nullable */);
 
+/* ---- a face hierarchy of the resident batch, and the closest-point step through it -------------------------------------------------
+ * sh_mesh_bvh builds, per resident mesh, a bounding-box hierarchy over its faces (k_bvh.h; the rules are sh_scalar.h bvh_*, all float32
+ * min / max, one float64 quantisation and integer work, restated by tests/bvh_oracle.py):
+ *   loose     a face with !(g >= 2^-7), g = |ab x ac|^2 / Lmax^3 (bvh_loose: slivers, collinear and point triangles, the faces the cull of
+ *             sh_closest_points never skips) stays out of the tree: "bvh.loose" lists them ascending by face id, every query tests all.
+ *   order     the other ("tight") faces ascending by (code, face id), code the 30-bit interleave of the box centre quantised to 1024
+ *             cells per axis of the box of the tight faces (bvh_quant, bvh_code): "bvh.order".  "bvh.tri" holds their corners in that
+ *             order, 9 float32 each.
+ *   tree      implicit, no child pointers: a leaf is SH_BVH_LEAF consecutive entries of the order (the last may be short), node j of
+ *             level k + 1 covers the nodes [j W, (j + 1) W) of level k that exist, W = SH_BVH_WIDTH, until a level has one node.  A node
+ *             is its box, 6 float32 (lo, hi; minima and maxima in the order of bvh_fmin / bvh_fmax, -0 below +0): "bvh.box", the levels of
+ *             a mesh one after the other, mesh b at the node "bvh.off"[b][5].  A mesh without tight faces has no levels.
+ *   "bvh.off" per mesh 32 int32: tight, loose, leaves, levels, nodes, the mesh's first node in "bvh.box", 0, 0, then the first node of
+ *             each level relative to that and, behind the last level, nodes again.  The first node of a mesh is the sum of the nodes a
+ *             mesh of F_a tight faces would have over the meshes a before it: it depends on the face COUNTS before it, nothing else does.
+ *   sh_bvh_info (48 B, all int32 / float32) per mesh, resident in "bvh.info": tight, loose, leaves, levels, nodes, reserved = 0, and the
+ *             box of the tight faces lo[3], hi[3] (zeros without one).
+ * Arguments in this order: the context (SH_ERR_ARG); a resident batch and no runs in flight (SH_ERR_STATE; a run is not needed).
+ * SH_ERR_NOMEM when the buffers do not fit.  "bvh.order" and "bvh.loose" have F_b int32 per mesh at foff[b], the unused tail -1.  The
+ * "bvh.*" buffers answer for the batch they were built for: the next upload / commit / sh_store("verts") removes them.  The call
+ * changes nothing else: every other named buffer keeps its bytes.
+ *
+ * sh_set_query_accel(SH_ACCEL_BVH) routes the closest-point step of sh_closest_points, sh_register_points and sh_register_multistart
+ * through the hierarchy (k_cp_tree instead of k_cp_walk; the index is built first when "bvh.order" is not resident).  A node is skipped
+ * only when every face in it would compute a d2 strictly above the point's best (k_bvh.h states the argument), and the winner is the
+ * minimum of (d2, face) under a total order: THE RESULTS ARE THE SAME BYTES in either mode.  SH_ACCEL_OFF (0) is the default; a mode
+ * that is neither is SH_ERR_ARG.  sh_winding_numbers, the rays, the samples and the geodesics do not read the index. */
+#define SH_ACCEL_OFF      0
+#define SH_ACCEL_BVH      1
+#define SH_BVH_INFO_BYTES 48
+struct sh_bvh_info { int32_t tight, loose, leaves, levels, nodes, reserved; float lo[3], hi[3]; };             /* 48 B */
+typedef struct sh_bvh_info sh_bvh_info;
+int sh_mesh_bvh(sh_ctx*, sh_bvh_info* out /* B, host, nullable */);
+int sh_set_query_accel(sh_ctx*, int mode);
+int sh_get_query_accel(const sh_ctx*);
+
 /* ---- stage-level access for parity tests: named intermediate device buffers ----------
  * names: "verts_obb" "obb_transform" "full.zs" "full.centroids" "full.areas" "full.nloops"
  * "distal.*" "prox.*" "prox.ixy" "prox.itr_start" "prox.itr_centered_start" "canal.points"

@@ -6,6 +6,7 @@ return shapes, float64 NumPy arrays, lazy + memoised evaluation, landmarks cache
 re-expressed through one shared `Transform`.  Every number comes from libshoulder_hip.so through
 `Engine` (one sh_run over a batch of one); nothing here falls back to the CPU.
 """
+import contextlib
 import os
 import pathlib
 import threading
@@ -472,17 +473,32 @@ class ProximalHumerus(Bone):
         self._ensure_loaded()
         return self._engine.transform_points(p, np.linalg.inv(T)), T
 
-    def _closest_ct(self, points):
+    @contextlib.contextmanager
+    def _accel(self, accel):
+        """accel=None: the engine as it is configured; "off" | "bvh": its closest-point step switched for this call (Engine.query_accel:
+        the same results either way) and put back afterwards"""
+        if accel is None:
+            yield
+            return
+        before = self._engine.query_accel
+        self._engine.query_accel = accel
+        try:
+            yield
+        finally:
+            self._engine.query_accel = before
+
+    def _closest_ct(self, points, accel=None):
         """the records of Engine.closest_points for points given in the CURRENT coordinate system, and the current matrix"""
         p, T = self._points_ct(points)
-        return self._engine.closest_points(p)[0], T
+        with self._accel(accel):
+            return self._engine.closest_points(p)[0], T
 
-    def closest_point(self, points):
+    def closest_point(self, points, accel=None):
         """`trimesh.proximity.closest_point(mesh, points)` in the CURRENT coordinate system on the device (Engine.closest_points):
         -> (closest (n, 3), distance (n,), triangle_id (n,)).  The points go to CT through the inverse of the current transform, the
         closest points come back through it (the transforms are rigid: the distance is CT's).  Among triangles at the same distance
-        the smallest id is returned."""
-        rec, T = self._closest_ct(points)
+        the smallest id is returned.  accel="bvh": through the face hierarchy (Engine.query_accel), the same results."""
+        rec, T = self._closest_ct(points, accel)
         if np.any(rec["status"] != 0):
             raise ValueError(f"closest_point failed with status {int(rec['status'][rec['status'] != 0][0])}: no face of the mesh gave a finite distance")
         return self._engine.transform_points(np.ascontiguousarray(rec["point"]), T), np.array(rec["dist"]), np.array(rec["face"], dtype=np.int64)
@@ -496,7 +512,7 @@ class ProximalHumerus(Bone):
             return other.sample_surface(int(sample), seed=seed)[0]
         return other.vertices if hasattr(other, "vertices") else other
 
-    def surface_distance(self, other, sample=None, seed=0, symmetric=False):
+    def surface_distance(self, other, sample=None, seed=0, symmetric=False, accel=None):
         """How far `other` lies from this bone's surface: `other` is an (n, 3) array of points or anything with `.vertices` (a Mesh,
         another bone's mesh, a half from `resect_mesh()`), in the CURRENT coordinate system.  -> dict with `mean`, `rms`, `max` (the
         one-sided Hausdorff distance), `p95`, `n` and `argmax` (the index of the farthest point), from one closest_point call.
@@ -505,14 +521,14 @@ class ProximalHumerus(Bone):
 
         Vertices follow the mesher's density, not the surface.  With `sample=n` and a bone as `other` the points are n area-weighted
         samples of its surface instead (`other.sample_surface(n, seed)`); `symmetric=True` (needs `sample`) also measures n samples of
-        this bone against `other` and adds `max_back`, `rms_back` and `hausdorff`, the larger of the two `max`."""
+        this bone against `other` and adds `max_back`, `rms_back` and `hausdorff`, the larger of the two `max`.  accel as in closest_point."""
         if symmetric and sample is None:
             raise ValueError("symmetric=True needs sample=n and a bone as `other`")
-        d = self.closest_point(self._other_points(other, sample, seed))[1]
+        d = self.closest_point(self._other_points(other, sample, seed), accel=accel)[1]
         out = dict(mean=float(d.mean()), rms=float(np.sqrt(np.mean(d * d))), max=float(d.max()), p95=float(np.percentile(d, 95)),
                    n=int(len(d)), argmax=int(np.argmax(d)))
         if symmetric:
-            back = other.closest_point(self.sample_surface(int(sample), seed=seed)[0])[1]
+            back = other.closest_point(self.sample_surface(int(sample), seed=seed)[0], accel=accel)[1]
             out.update(max_back=float(back.max()), rms_back=float(np.sqrt(np.mean(back * back))), hausdorff=max(out["max"], float(back.max())))
         return out
 
@@ -646,11 +662,13 @@ class ProximalHumerus(Bone):
         thresholded fraction, a cavity whose wall faces inward is outside, and a point on the surface itself is undefined."""
         return self._engine.contains(self._points_ct(points)[0])[0]
 
-    def signed_distance(self, points):
+    def signed_distance(self, points, accel=None):
         """`trimesh.proximity.signed_distance(mesh, points)` in the CURRENT coordinate system -> float64 (n,): the distance to the
         surface, POSITIVE INSIDE and negative outside (the transforms are rigid: the distance is CT's).  Open meshes, cavities and
-        the surface itself as in `contains`."""
-        return self._engine.signed_distance(self._points_ct(points)[0])[0]
+        the surface itself as in `contains`.  accel as in closest_point (the winding numbers do not read the hierarchy)."""
+        p = self._points_ct(points)[0]
+        with self._accel(accel):
+            return self._engine.signed_distance(p)[0]
 
     # -- mass properties ----------------------------------------------------------------------------------------
     def mass_properties(self):
@@ -677,7 +695,7 @@ class ProximalHumerus(Bone):
                     faces=int(m["faces"]), degenerate=int(m["degenerate"]), vstatus=int(m["vstatus"]))
 
     # -- rigid registration (ICP) -------------------------------------------------------------------------------
-    def register(self, other, initial=None, mirror=None, sample=None, seed=0, **options):
+    def register(self, other, initial=None, mirror=None, sample=None, seed=0, accel=None, **options):
         """`trimesh.registration.icp(other, mesh)` / `mesh.register(other)` on the device (Engine.register): the rigid matrix that
         moves `other` onto this bone's surface.  `other` is an (n, 3) array of points or anything with `.vertices`, in the CURRENT
         coordinate system; `initial` a rigid (4, 4) starting matrix in that system (default: the identity); `mirror` = "x" | "y" | "z"
@@ -700,7 +718,12 @@ class ProximalHumerus(Bone):
         has no long axis and the starts are arbitrary).
 
         THE POINTS MUST COVER THE BONE.  Vertices follow the mesher's density; with `sample=n` and a bone as `other` the points are n
-        area-weighted samples of its surface instead (`other.sample_surface(n, seed)`)."""
+        area-weighted samples of its surface instead (`other.sample_surface(n, seed)`).  accel="bvh": the pair step of every
+        evaluation goes through the face hierarchy (Engine.query_accel), the same results."""
+        with self._accel(accel):
+            return self._register(other, initial, mirror, sample, seed, options)
+
+    def _register(self, other, initial, mirror, sample, seed, options):
         pts = np.array(self._other_points(other, sample, seed), dtype=np.float64).reshape(-1, 3)
         if mirror is not None:
             if mirror not in ("x", "y", "z"):

@@ -1,12 +1,15 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields) and the geodesics (sh_geodesic).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields), the geodesics (sh_geodesic) and the face hierarchy (sh_mesh_bvh, sh_set_query_accel).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo,bvh}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
 #include "sh_arthro.h"
+#include "sh_scalar.h"      // the level rule of the face hierarchy (bvh_levels_of, bvh_nodes_of)
+
+#include <vector>
 
 namespace sh {
 
@@ -52,6 +55,13 @@ struct RayKey; struct CpPart; struct GeoInfo;
   X(geo_face, "geo.face", double, 8) X(geo_dist, "geo.dist", double, 8) X(geo_pred, "geo.pred", int, 4) X(geo_source, "geo.source", int, 4) \
   X(geo_info, "geo.info", GeoInfo, 8) X(geo_opp, "geo.opp", int, 4) X(geo_plane, "geo.plane", double, 8) X(geo_jump, "geo.jump", int, 4)    \
   X(geo_src, "geo.src", int, 4) X(geo_d0, "geo.d0", double, 8) X(geo_state, "geo.state", int, 4)
+// the order, the loose list, the offsets, the boxes, the sorted corners and the records; scratch: SH_BVH_HEAD words per mesh (the box as
+// topo_enc words, the tight faces), each mesh's first node and first key (B + 1 each), the keys before and behind the sort
+#define BVH_BUFS(X)                                                                                                                \
+  X(bvh_order, "bvh.order", int, 4) X(bvh_loose, "bvh.loose", int, 4) X(bvh_off, "bvh.off", int, 4) X(bvh_box, "bvh.box", float, 4)  \
+  X(bvh_tri, "bvh.tri", float, 4) X(bvh_info, "bvh.info", sh_bvh_info, 4) X(bvh_state, "bvh.state", unsigned, 4)                   \
+  X(bvh_base, "bvh.base", int, 4) X(bvh_seg, "bvh.seg", unsigned, 4) X(bvh_key, "bvh.key", unsigned long long, 8)                  \
+  X(bvh_sorted, "bvh.sorted", unsigned long long, 8)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -66,6 +76,7 @@ SH_BUF_LIST(Vert, VERT_BUFS)
 using VertView = BufJoin<MeshBufs, TopoBufs, VertBufs>;      // (the mesh, the incidence and adjacency it reads, and its own)
 SH_BUF_LIST(Geo, GEO_BUFS)
 using GeoView = BufJoin<MeshBufs, TopoBufs, GeoBufs>;
+SH_QUERY_LIST(Bvh, BVH_BUFS)
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -79,6 +90,7 @@ constexpr int AR_SAMP_CHUNK = 256, AR_SAMP_HEAD = 64;                           
 constexpr int AR_TOPO_BLOCK = 256, AR_TOPO_HEAD = 64;                             // SH_TOPO_BLOCK, SH_TOPO_HEAD
 constexpr int AR_VERT_BLOCK = 256, AR_VERT_FACE = 10;                             // SH_VERT_BLOCK, SH_VTX_FACE
 constexpr int AR_GEO_BLOCK = 256, AR_GEO_FACE = 6, AR_GEO_STATE = 8;              // SH_GEO_BLOCK, SH_GEOD_FACE, SH_GEO_STATE
+constexpr int AR_BVH_BLOCK = 256, AR_BVH_HEAD = 8, AR_BVH_CHUNK = 64;             // SH_BVH_BLOCK, SH_BVH_HEAD, SH_BVH_CHUNK
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -267,6 +279,50 @@ inline GeoPlan geo_plan(int B, int K, long long S, int lds_vertices, long long m
   return {(int)tiles_of(maxF, AR_GEO_BLOCK), (int)tiles_of(maxV, AR_GEO_BLOCK), jumps, general, general ? maxV + 1 : 0, z};
 }
 
+// The face hierarchy (sh_scalar.h bvh_*).  "bvh.order", "bvh.loose", "bvh.key" and "bvh.sorted" follow the faces (mesh b at foff[b]) and
+// "bvh.tri" nine float32 per face; "bvh.box" has six float32 per node, mesh b from base[b] = the sum of bvh_nodes_of(F_a) over the meshes
+// before it -- room for a mesh without a loose face, known before the device has counted them; "bvh.off" SH_BVH_OFF_WORDS int32 and
+// "bvh.state" AR_BVH_HEAD words per mesh.  levels: those of the largest mesh were all its faces tight -- the launches of k_bvh_level are
+// levels - 1; leaf_blocks / node_blocks[k]: the workgroups per mesh that cover the leaves and level k of such a mesh.
+// Refused: a batch whose faces or nodes are no int32 (the sort and "bvh.off" count in 32 bits).
+struct BvhPlan {
+  int fblocks = 0, levels = 0, leaf_blocks = 0, node_blocks[SH_BVH_MAX_LEVELS] = {};
+  std::vector<int> base;            // B + 1: the first node of every mesh, the nodes of the batch behind the last
+  std::vector<unsigned> seg;        // B + 1: the first key of every mesh
+  std::vector<unsigned> state0;     // B x AR_BVH_HEAD: an empty box (lo above, hi below everything), no tight face
+  BvhBytes bytes;
+};
+inline ArthroError bvh_plan(int B, const long long* foff /* B + 1 */, BvhPlan* out) {
+  BvhPlan p;
+  long long nodes = 0, maxF = 0;
+  p.base.resize((size_t)B + 1); p.seg.resize((size_t)B + 1); p.state0.assign((size_t)B * AR_BVH_HEAD, 0u);
+  if (foff[B] > 0x7fffffffLL) return {SH_ERR_NOMEM, "the batch has more than 2^31 - 1 faces: its keys do not sort in one call"};
+  for (int b = 0; b < B; ++b) {
+    const long long nf = foff[b + 1] - foff[b];
+    if (nf < 0 || nf > SH_BVH_MAX_FACES) return {SH_ERR_ARG, "a mesh has more faces than an upload admits"};
+    maxF = nf > maxF ? nf : maxF;
+    p.base[b] = (int)nodes; p.seg[b] = (unsigned)foff[b];
+    nodes += bvh_nodes_of(nf);
+    if (nodes > 0x7fffffffLL) return {SH_ERR_NOMEM, "the batch has more than 2^31 - 1 nodes"};
+    for (int k = 0; k < 3; ++k) p.state0[(size_t)b * AR_BVH_HEAD + k] = 0xffffffffu;
+  }
+  p.base[B] = (int)nodes; p.seg[B] = (unsigned)foff[B];
+  p.fblocks = (int)tiles_of(maxF, AR_BVH_BLOCK);
+  p.levels = bvh_levels_of(maxF);
+  long long n = (maxF + SH_BVH_LEAF - 1) / SH_BVH_LEAF;
+  p.leaf_blocks = (int)tiles_of(n, AR_BVH_BLOCK);
+  for (int k = 0; k < p.levels; ++k) { p.node_blocks[k] = (int)tiles_of(n, AR_BVH_BLOCK); n = (n + SH_BVH_WIDTH - 1) / SH_BVH_WIDTH; }
+  const size_t f = (size_t)(foff[B] > 0 ? foff[B] : 1);
+  BvhBytes& z = p.bytes;
+  z.bvh_order = f * 4; z.bvh_loose = f * 4; z.bvh_off = (size_t)B * SH_BVH_OFF_WORDS * 4; z.bvh_box = (size_t)(nodes > 0 ? nodes : 1) * 24; z.bvh_tri = f * 36;
+  z.bvh_info = (size_t)B * sizeof(sh_bvh_info); z.bvh_state = (size_t)B * AR_BVH_HEAD * 4; z.bvh_base = ((size_t)B + 1) * 4; z.bvh_seg = ((size_t)B + 1) * 4;
+  z.bvh_key = f * 8; z.bvh_sorted = f * 8;
+  *out = std::move(p);
+  return arthro_ok();
+}
+// the grid of k_cp_tree over Q points per mesh: chunks of one wave
+inline int bvh_chunks(int Q) { return (Q + AR_BVH_CHUNK - 1) / AR_BVH_CHUNK; }
+
 // Multi-start registration: the coarse stage is sh_register_points on Qc points, the fine stage on all Q, both on the "icp.*" buffers,
 // which take the larger of the two sizes field by field (the split of the walk, and so "icp.cp_part", may be larger for the fewer points).
 inline int ms_coarse_count(int Q, int coarse_points) { return coarse_points == 0 || coarse_points > Q ? Q : coarse_points; }
@@ -330,6 +386,16 @@ inline ArthroError precheck_topology(const sh_topology_options* opt, const Arthr
   if (opt->max_shells < 1 || opt->max_shells > SH_TOPO_MAX_SHELLS || opt->max_rounds < 1 || opt->max_rounds > SH_TOPO_MAX_ROUNDS || opt->reserved != 0)
     return {SH_ERR_ARG, "bad options (max_shells in 1..65536, max_rounds in 1..32, reserved 0)"};
   return resident(f);
+}
+
+// (the order and the codes of precheck_topology without its options)
+inline ArthroError precheck_bvh(const ArthroFacts& f) {
+  if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
+  return resident(f);
+}
+inline ArthroError precheck_query_accel(bool ctx, int mode) {
+  if (!ctx || (mode != SH_ACCEL_OFF && mode != SH_ACCEL_BVH)) return {SH_ERR_ARG, "bad argument (mode SH_ACCEL_OFF or SH_ACCEL_BVH)"};
+  return arthro_ok();
 }
 
 // incidence: "topo.vrow", "topo.vface" and "topo.adj" of the resident batch are there (a new batch removes them)

@@ -1,7 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
 // point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), the surface samples, sh_sample_surface
-// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), and the geodesics, sh_geodesic (k_geo.h).
+// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), the geodesics, sh_geodesic (k_geo.h), and the face hierarchy, sh_mesh_bvh / sh_set_query_accel (k_bvh.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -77,9 +77,82 @@ int sh_anp_axis_hits(sh_ctx* c, int cap, sh_ray_hit* hits, int32_t* counts, int3
   return SH_OK;
 }
 
+// ---- the face hierarchy (k_bvh.h) ----
+static_assert(AR_BVH_BLOCK == SH_BVH_BLOCK && AR_BVH_HEAD == SH_BVH_HEAD && AR_BVH_CHUNK == SH_BVH_CHUNK, "sh_query.h: hierarchy block, head of bvh.state, chunk of the walk");
+
+// The build, enqueued on the context's stream: the offsets and the empty boxes to the device -> class -> key -> sort -> emit -> leaves ->
+// a launch per level above them; the host looks at nothing in between (the temporary storage of the sort is sized on the host).
+static int bvh_enqueue(sh_ctx* c, const char* fn) {
+  BvhPlan plan;
+  if (const ArthroError e = bvh_plan(c->B, c->h_foff.data(), &plan); e.code) return arthro_refuse(c, fn, e);
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  BvhView v = view_of<BvhView>(c);
+  const int B = c->B;
+  const unsigned nkeys = (unsigned)c->sumF;
+  size_t tmp_bytes = 0;
+  HIPCHK(c, rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, (const unsigned long long*)v.bvh_key, v.bvh_sorted, nkeys, (unsigned)B, (const unsigned*)v.bvh_seg,
+                                               (const unsigned*)v.bvh_seg + 1, 0u, 63u, c->stream));
+  if (int rc = ensure_shared(c, "bvh.tmp", tmp_bytes ? tmp_bytes : 16, 1)) return rc;
+  v = view_of<BvhView>(c);
+  void* tmp = c->at("bvh.tmp");
+  HIPCHK(c, hipMemcpyAsync(v.bvh_base, plan.base.data(), plan.bytes.bvh_base, hipMemcpyHostToDevice, c->stream));      // (pageable: staged before the call returns)
+  HIPCHK(c, hipMemcpyAsync(v.bvh_seg, plan.seg.data(), plan.bytes.bvh_seg, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(v.bvh_state, plan.state0.data(), plan.bytes.bvh_state, hipMemcpyHostToDevice, c->stream));
+  const dim3 fblocks((unsigned)plan.fblocks, (unsigned)B), lanes(SH_BVH_BLOCK);
+  LAUNCH(c, "k_bvh_class", k_bvh_class, fblocks, lanes, v.verts, v.faces, v.voff, v.foff, v.bvh_state);
+  LAUNCH(c, "k_bvh_key", k_bvh_key, fblocks, lanes, v.verts, v.faces, v.voff, v.foff, (const unsigned*)v.bvh_state, v.bvh_key);
+  HIPCHK(c, rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, (const unsigned long long*)v.bvh_key, v.bvh_sorted, nkeys, (unsigned)B, (const unsigned*)v.bvh_seg,
+                                               (const unsigned*)v.bvh_seg + 1, 0u, 63u, c->stream));
+  LAUNCH(c, "k_bvh_emit", k_bvh_emit, fblocks, lanes, v.verts, v.faces, v.voff, v.foff, (const unsigned long long*)v.bvh_sorted, (const unsigned*)v.bvh_state,
+         (const int*)v.bvh_base, v.bvh_order, v.bvh_loose, v.bvh_tri, v.bvh_off, v.bvh_info);
+  LAUNCH(c, "k_bvh_leaves", k_bvh_leaves, dim3((unsigned)plan.leaf_blocks, (unsigned)B), lanes, v.foff, (const float*)v.bvh_tri, (const int*)v.bvh_off, v.bvh_box);
+  for (int k = 1; k < plan.levels; ++k)
+    LAUNCH(c, "k_bvh_level", k_bvh_level, dim3((unsigned)plan.node_blocks[k], (unsigned)B), lanes, (const int*)v.bvh_off, v.bvh_box, k);
+  return SH_OK;
+}
+
+// ... and a build that did not get through leaves no "bvh.order" behind: that name is what says "the index of this batch is resident"
+static int bvh_build(sh_ctx* c, const char* fn) {
+  const int rc = bvh_enqueue(c, fn);
+  if (rc != SH_OK)
+    if (auto it = c->bufs.find("bvh.order"); it != c->bufs.end()) {
+      if (it->second.p) (void)hipFree(it->second.p);
+      c->bufs.erase(it);
+    }
+  return rc;
+}
+
+int sh_mesh_bvh(sh_ctx* c, sh_bvh_info* out) {
+  if (const ArthroError e = precheck_bvh(arthro_facts(c)); e.code) return arthro_refuse(c, "sh_mesh_bvh", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = bvh_build(c, "sh_mesh_bvh")) return rc;
+  if (out) HIPCHK(c, hipMemcpyAsync(out, c->at("bvh.info"), (size_t)c->B * sizeof(sh_bvh_info), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+int sh_set_query_accel(sh_ctx* c, int mode) {
+  if (const ArthroError e = precheck_query_accel(c != nullptr, mode); e.code) return arthro_refuse(c, "sh_set_query_accel", e);
+  c->query_accel = mode;
+  return SH_OK;
+}
+int sh_get_query_accel(const sh_ctx* c) { return c ? c->query_accel : SH_ACCEL_OFF; }
+
 // ---- closest surface points (k_closest.h) ----
-// The walk and its join for B x Q device points `pts` (per != 0: Q of its own for every humerus) over S face splits, from `part` into `out`
+// The walk and its join for B x Q device points `pts` (per != 0: Q of its own for every humerus) over S face splits, from `part` into `out`.
+// THE ONE PLACE sh_closest_points and the evaluations of a registration go through: with SH_ACCEL_BVH the walk is k_cp_tree over the
+// hierarchy (built here when "bvh.order" is not resident: a new batch removed it), one partial per point, and the same join with S = 1.
 static int cp_walk_join(sh_ctx* c, const MeshBufs& m, const double* pts, int Q, int per, int chunks, int S, size_t points, CpPart* part, sh_closest* out) {
+  if (c->query_accel == SH_ACCEL_BVH) {
+    if (!c->at("bvh.order"))
+      if (int rc = bvh_build(c, "the closest-point step")) return rc;
+    const BvhBufs t = view_of<BvhBufs>(c);
+    LAUNCH(c, "k_cp_tree", k_cp_tree, dim3((unsigned)bvh_chunks(Q), (unsigned)c->B), dim3(SH_BVH_CHUNK), m.verts, m.faces, m.voff, m.foff, (const int*)t.bvh_order,
+           (const int*)t.bvh_loose, (const int*)t.bvh_off, (const float*)t.bvh_box, (const float*)t.bvh_tri, pts, Q, per, part);
+    LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((points + 255) / 256)), dim3(256), m.verts, m.faces, m.voff, m.foff, pts, Q, per, 1, (const CpPart*)part,
+           (long long)points, out);
+    return SH_OK;
+  }
   LAUNCH(c, "k_cp_walk", k_cp_walk, dim3((unsigned)chunks, (unsigned)c->B, (unsigned)S), dim3(SH_CP_CHUNK), m.verts, m.faces, m.voff, m.foff, pts, Q, per, S, part);
   LAUNCH(c, "k_cp_join", k_cp_join, dim3((unsigned)((points + 255) / 256)), dim3(256), m.verts, m.faces, m.voff, m.foff, pts, Q, per, S, (const CpPart*)part,
          (long long)points, out);

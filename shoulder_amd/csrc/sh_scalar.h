@@ -424,7 +424,8 @@ SH_HD int eigvals3_real(const double* M, double* ev) {
   } else {
     double m = 2.0 * sqrt(-p / 3.0);
     double arg = 3.0 * q / (p * m);
-    if (arg > 1) arg = 1; if (arg < -1) arg = -1;
+    if (arg > 1) arg = 1;
+    if (arg < -1) arg = -1;
     double th = acos(arg) / 3.0;
     for (int k = 0; k < 3; ++k) ev[n++] = m * cos(th - 2.0 * M_PI * k / 3.0) + a;
   }
@@ -1877,6 +1878,199 @@ SH_HD int geo_pred(const int* faces, const double* frec, const int* opp, const i
 // the better of two candidates for the farthest vertex: the larger distance, the smaller index among equals (v < 0: none)
 SH_HD void geo_far(double d, int v, double* best_d, int* best_v) {
   if (v >= 0 && (*best_v < 0 || d > *best_d || (d == *best_d && v < *best_v))) { *best_d = d; *best_v = v; }
+}
+
+// ---- the face hierarchy of the resident batch (include/shoulder_hip.h sh_mesh_bvh; k_bvh.h) -------------------------------------------
+// float32 minima and maxima, one float64 quantisation and integer work, restated by tests/bvh_oracle.py: the device, the host twin
+// (tests/hostcheck/bvh_check.cpp) and the oracle give the same bytes.  LEAF and WIDTH are powers of two in 4..16, fixed after measuring
+// (4 x 4 was the fastest of six candidates on the bench batch); a lab build may set others (tools/time_bvh.py),
+// everything below follows.
+#ifndef SH_BVH_LEAF
+#define SH_BVH_LEAF 4            // entries of the order per leaf
+#endif
+#ifndef SH_BVH_WIDTH
+#define SH_BVH_WIDTH 4           // nodes of level k per node of level k + 1
+#endif
+#define SH_BVH_MAX_FACES (0x7fffffffLL / 3)      // the faces of the largest mesh an upload admits (sh_ingest.h check_mesh_arrays)
+#define SH_BVH_OFF_WORDS 32      // int32 of a mesh in "bvh.off": tight, loose, leaves, levels, nodes, base, 0, 0, then the level starts
+#define SH_BVH_OFF_LEVEL 8       // ... word of the start of level 0
+#define SH_BVH_LOOSE_CODE 0x40000000u      // the sort code of a loose face: above every 30-bit code
+
+// the levels of a tree over `tight` faces (0 without one) and the nodes of all of them
+SH_HD constexpr int bvh_levels_of(long long tight) {
+  if (tight <= 0) return 0;
+  long long n = (tight + SH_BVH_LEAF - 1) / SH_BVH_LEAF;
+  int k = 1;
+  while (n > 1) { n = (n + SH_BVH_WIDTH - 1) / SH_BVH_WIDTH; ++k; }
+  return k;
+}
+SH_HD constexpr long long bvh_nodes_of(long long tight) {
+  if (tight <= 0) return 0;
+  long long n = (tight + SH_BVH_LEAF - 1) / SH_BVH_LEAF, sum = n;
+  while (n > 1) { n = (n + SH_BVH_WIDTH - 1) / SH_BVH_WIDTH; sum += n; }
+  return sum;
+}
+constexpr int SH_BVH_MAX_LEVELS = bvh_levels_of(SH_BVH_MAX_FACES);
+constexpr int SH_BVH_STACK = SH_BVH_MAX_LEVELS * (SH_BVH_WIDTH - 1) + 1;      // a depth-first walk that replaces a node by its children holds no more
+static_assert(SH_BVH_LEAF >= 4 && SH_BVH_LEAF <= 16 && (SH_BVH_LEAF & (SH_BVH_LEAF - 1)) == 0, "SH_BVH_LEAF: a power of two in 4..16");
+static_assert(SH_BVH_WIDTH >= 4 && SH_BVH_WIDTH <= 16 && (SH_BVH_WIDTH & (SH_BVH_WIDTH - 1)) == 0, "SH_BVH_WIDTH: a power of two in 4..16");
+static_assert(SH_BVH_MAX_LEVELS <= 16 && (SH_BVH_MAX_FACES + SH_BVH_LEAF - 1) / SH_BVH_LEAF < (1LL << 28), "a stack entry is level << 28 | node");
+static_assert(SH_BVH_OFF_LEVEL + SH_BVH_MAX_LEVELS + 1 <= SH_BVH_OFF_WORDS, "bvh.off: a word per level and one behind the last");
+static_assert(bvh_nodes_of(SH_BVH_MAX_FACES) <= 0x7fffffffLL, "the nodes of a mesh are an int32");
+
+// The row of a mesh in "bvh.off" from its counts and its first node in "bvh.box"
+SH_HD void bvh_off_row(int tight, int loose, int base, int* row /* SH_BVH_OFF_WORDS */) {
+  for (int i = 0; i < SH_BVH_OFF_WORDS; ++i) row[i] = 0;
+  int levels = 0, nodes = 0, n = tight > 0 ? (tight + SH_BVH_LEAF - 1) / SH_BVH_LEAF : 0;
+  const int leaves = n;
+  while (n > 0) {
+    row[SH_BVH_OFF_LEVEL + levels] = nodes;
+    nodes += n; ++levels;
+    if (n == 1) break;
+    n = (n + SH_BVH_WIDTH - 1) / SH_BVH_WIDTH;
+  }
+  row[SH_BVH_OFF_LEVEL + levels] = nodes;
+  row[0] = tight; row[1] = loose; row[2] = leaves; row[3] = levels; row[4] = nodes; row[5] = base;
+}
+
+// THE LOOSE PREDICATE, once: g = |ab x ac|^2 / Lmax^3 of the widened edges, the number k_closest.h forms at staging (point (3) of its
+// cull).  !(g >= 2^-7): the face is loose -- also when g is NaN (a point triangle divides 0 by 0).
+SH_HD bool bvh_loose(const double* ab, const double* ac) {
+  const double bc[3] = {ac[0] - ab[0], ac[1] - ab[1], ac[2] - ab[2]};
+  double n[3];
+  cross3(ab, ac, n);
+  const double l2 = fmax(dot3(ab, ab), fmax(dot3(ac, ac), dot3(bc, bc)));
+  const double g = dot3(n, n) / (l2 * sqrt(l2));
+  return !(g >= 0x1p-7);
+}
+// the corners of a face widened as cp_face widens them -> loose or not
+SH_HD bool bvh_face_loose(const float* v0, const float* v1, const float* v2) {
+  const double A[3] = {(double)v0[0], (double)v0[1], (double)v0[2]};
+  const double ab[3] = {(double)v1[0] - A[0], (double)v1[1] - A[1], (double)v1[2] - A[2]}, ac[3] = {(double)v2[0] - A[0], (double)v2[1] - A[1], (double)v2[2] - A[2]};
+  return bvh_loose(ab, ac);
+}
+
+// minimum and maximum of two float32 in the order of topo_enc (total: -0 below +0), so that a box is the same bytes whatever the order
+// of its members
+SH_HD float bvh_fmin(float a, float b) { return topo_enc(b) < topo_enc(a) ? b : a; }
+SH_HD float bvh_fmax(float a, float b) { return topo_enc(b) > topo_enc(a) ? b : a; }
+
+// the cell of a face along one axis: mn, mx its smallest and largest corner coordinate, lo, hi those of the tight faces of the mesh.
+// s is twice the box centre and exact; ext > 0 fails for a flat mesh, whose cell is 0.
+SH_HD int bvh_quant(float mn, float mx, float lo, float hi) {
+  const double s = (double)mn + (double)mx, ext = 2.0 * ((double)hi - (double)lo);
+  if (!(ext > 0.0)) return 0;
+  const int q = (int)floor(((s - 2.0 * (double)lo) / ext) * 1024.0);
+  return q < 1023 ? q : 1023;
+}
+// bit i of a 10-bit cell to bit 3 i
+SH_HD unsigned bvh_spread(unsigned v) {
+  v &= 0x3ffu;
+  v = (v | (v << 16)) & 0x030000ffu;
+  v = (v | (v << 8)) & 0x0300f00fu;
+  v = (v | (v << 4)) & 0x030c30c3u;
+  v = (v | (v << 2)) & 0x09249249u;
+  return v;
+}
+SH_HD unsigned bvh_code(int qx, int qy, int qz) { return bvh_spread((unsigned)qx) | (bvh_spread((unsigned)qy) << 1) | (bvh_spread((unsigned)qz) << 2); }
+// the code of a tight face from its corners and the box (lo[3], hi[3]) of the tight faces
+SH_HD unsigned bvh_face_code(const float* v0, const float* v1, const float* v2, const float* lo, const float* hi) {
+  int q[3];
+  for (int k = 0; k < 3; ++k) q[k] = bvh_quant(bvh_fmin(v0[k], bvh_fmin(v1[k], v2[k])), bvh_fmax(v0[k], bvh_fmax(v1[k], v2[k])), lo[k], hi[k]);
+  return bvh_code(q[0], q[1], q[2]);
+}
+// the sort key: tight faces ascending by (code, id), the loose ones behind them ascending by id
+SH_HD unsigned long long bvh_key(bool loose, unsigned code, int face) {
+  return ((unsigned long long)(loose ? SH_BVH_LOOSE_CODE : code) << 32) | (unsigned long long)(unsigned)face;
+}
+
+// a box (lo[3], hi[3]) grown by a point, and by a box
+SH_HD void bvh_box_point(float* bx, const float* v) {
+  for (int k = 0; k < 3; ++k) { bx[k] = bvh_fmin(bx[k], v[k]); bx[3 + k] = bvh_fmax(bx[3 + k], v[k]); }
+}
+SH_HD void bvh_box_box(float* bx, const float* o) {
+  for (int k = 0; k < 3; ++k) { bx[k] = bvh_fmin(bx[k], o[k]); bx[3 + k] = bvh_fmax(bx[3 + k], o[3 + k]); }
+}
+
+// THE PRUNING RULE (k_bvh.h states the argument): may the node with the float32 box bx be skipped by a point p whose best distance
+// so far is best_r = sqrt(best d2) (1 + 2^-40), +inf without one?  near2: the squared distance from p to the widened box as computed.
+SH_HD bool bvh_box_skip(const double* p, const float* bx, double best_r, double* near2_out) {
+  double dn[3], df[3], m1 = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    const double lo = (double)bx[k], hi = (double)bx[3 + k];
+    const double a = lo - p[k], b = p[k] - hi;
+    dn[k] = fmax(fmax(a, b), 0.0);
+    df[k] = fmax(fabs(a), fabs(b));
+    m1 = m1 + fmax(fabs(lo), fabs(hi));
+  }
+  const double near2 = (dn[0] * dn[0] + dn[1] * dn[1]) + dn[2] * dn[2], far2 = (df[0] * df[0] + df[1] * df[1]) + df[2] * df[2];
+  const double thr = best_r + m1 * 0x1p-40;
+  *near2_out = near2;
+  return near2 > (thr * thr) * (1.0 + 0x1p-20) && far2 <= 1e8;
+}
+
+// d2 of entry i of "bvh.tri" (9 float32: the corners) to p: widened exactly as cp_face widens the mesh's vertices, so the same number
+SH_HD double bvh_tri_d2(const double* p, const float* t) {
+  const double A[3] = {(double)t[0], (double)t[1], (double)t[2]};
+  const double ab[3] = {(double)t[3] - A[0], (double)t[4] - A[1], (double)t[5] - A[2]}, ac[3] = {(double)t[6] - A[0], (double)t[7] - A[1], (double)t[8] - A[2]};
+  double u, w;
+  int region;
+  return closest_pt_tri(p, A, ab, ac, &u, &w, &region);
+}
+
+// THE DESCENT of one query point through the tree of one mesh (k_bvh.h k_cp_tree runs it with a stack in LDS, the host twin with an
+// array): row the mesh's words of "bvh.off", bx its boxes, tr and ord its entries of "bvh.tri" and "bvh.order".  Pop a node word
+// (level << 28 | node), test its box again -- the best may have fallen since it was pushed --; a leaf folds its entries into
+// (*best, *best_f) under closest_key_less; an inner node pushes the children whose box survives, the nearest one last, so that it is
+// descended first.  st.at(i) is word i of the stack: a walk that replaces a node by at most WIDTH children one level down never holds
+// more than (levels - 1) (WIDTH - 1) + 1 <= SH_BVH_STACK.  COUNT: count[0] += the nodes popped, count[1] += the faces tested.
+template <bool COUNT, typename Stack>
+SH_HD void bvh_descend(const double* p, const int* row, const float* bx, const float* tr, const int* ord, Stack& st, double* best_io, int* best_f_io, long long* count) {
+  const int T = row[0], levels = row[3];
+  const int* lv = row + SH_BVH_OFF_LEVEL;
+  double best = *best_io, best_r = sqrt(best) * (1.0 + 0x1p-40);
+  int best_f = *best_f_io, sp = 0;
+  if (levels > 0) st.at(sp++) = (unsigned)(levels - 1) << 28;
+  while (sp > 0) {
+    const unsigned e = st.at(--sp);
+    const int k = (int)(e >> 28), j = (int)(e & 0x0fffffffu);
+    double near2;
+    if (COUNT) ++count[0];
+    {
+      const float* nb = bx + 6 * ((size_t)lv[k] + (size_t)j);
+      const float bb[6] = {nb[0], nb[1], nb[2], nb[3], nb[4], nb[5]};
+      if (bvh_box_skip(p, bb, best_r, &near2)) continue;
+    }
+    if (k == 0) {
+      const int i0 = j * SH_BVH_LEAF, i1 = i0 + SH_BVH_LEAF < T ? i0 + SH_BVH_LEAF : T;
+      for (int i = i0; i < i1; ++i) {
+        const float* t = tr + 9 * (size_t)i;
+        const float tt[9] = {t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8]};
+        const double d2 = bvh_tri_d2(p, tt);
+        const int f = ord[i];
+        if (COUNT) ++count[1];
+        if (closest_key_less(d2, f, best, best_f)) { best = d2; best_f = f; best_r = sqrt(d2) * (1.0 + 0x1p-40); }
+      }
+    } else {
+      const int below = lv[k] - lv[k - 1];
+      const int c0 = j * SH_BVH_WIDTH, c1 = c0 + SH_BVH_WIDTH < below ? c0 + SH_BVH_WIDTH : below;
+      const float* ch = bx + 6 * (size_t)lv[k - 1];
+      const unsigned tag = (unsigned)(k - 1) << 28;
+      int nearest = -1;
+      double nearest_d = 0.0;
+      for (int c = c0; c < c1; ++c) {
+        const float* nb = ch + 6 * (size_t)c;
+        const float bb[6] = {nb[0], nb[1], nb[2], nb[3], nb[4], nb[5]};
+        if (bvh_box_skip(p, bb, best_r, &near2)) continue;
+        if (nearest < 0 || near2 < nearest_d) {
+          if (nearest >= 0) st.at(sp++) = tag | (unsigned)nearest;
+          nearest = c; nearest_d = near2;
+        } else st.at(sp++) = tag | (unsigned)c;
+      }
+      if (nearest >= 0) st.at(sp++) = tag | (unsigned)nearest;
+    }
+  }
+  *best_io = best; *best_f_io = best_f;
 }
 
 }  // namespace sh

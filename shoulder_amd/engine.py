@@ -713,6 +713,43 @@ class Engine:
         self._chk(self.L.sh_closest_points(self.h, _ptr(p), Q, per, _ptr(out)))
         return out
 
+    # ---- the face hierarchy of the resident batch (include/shoulder_hip.h sh_mesh_bvh, sh_set_query_accel) ------------------------
+    def build_bvh(self):
+        """Build the bounding-box hierarchy over the faces of every resident mesh -> (B,) of _lib.BVH_INFO_DTYPE: tight (the faces in
+        the tree), loose (slivers, collinear and point triangles: every query tests them), leaves, levels, nodes and the box lo, hi of
+        the tight faces.  Resident afterwards: "bvh.*" (bvh()); a new batch removes them.  Needs no run."""
+        info = np.zeros(max(self.B, 0), dtype=_lib.BVH_INFO_DTYPE)
+        self._chk(self.L.sh_mesh_bvh(self.h, _ptr(info)))
+        return info
+
+    def bvh(self):
+        """The resident hierarchy after build_bvh() (or a query in "bvh" mode) -> a list with one dict per mesh: `order` (the tight
+        faces ascending by (code, id)), `loose` (ascending), `off` (the mesh's 32 int32 of "bvh.off"), `box` ((nodes, 6) float32: lo,
+        hi; level k is box[off[8 + k]:off[8 + k + 1]]) and `tri` ((tight, 9) float32: the corners in the order)."""
+        F = int(self.foff[-1])
+        order, loose = self.fetch("bvh.order", np.int32, (F,)), self.fetch("bvh.loose", np.int32, (F,))
+        off = self.fetch("bvh.off", np.int32, (self.B, 32))
+        box, tri = self.fetch("bvh.box", np.float32).reshape(-1, 6), self.fetch("bvh.tri", np.float32, (F, 9))
+        out = []
+        for b in range(self.B):
+            f0 = int(self.foff[b])
+            t, nl, nodes, base = (int(off[b, i]) for i in (0, 1, 4, 5))
+            out.append(dict(order=order[f0:f0 + t].copy(), loose=loose[f0:f0 + nl].copy(), off=off[b].copy(), box=box[base:base + nodes].copy(),
+                            tri=tri[f0:f0 + t].copy()))
+        return out
+
+    @property
+    def query_accel(self):
+        """"off" (the default): the closest-point step of closest_points, register and register_multistart walks all faces; "bvh": it
+        descends the face hierarchy, which is built when it is not resident.  The results are the same bytes either way."""
+        return "bvh" if self.L.sh_get_query_accel(self.h) == _lib.ACCEL_BVH else "off"
+
+    @query_accel.setter
+    def query_accel(self, mode):
+        if mode not in ("off", "bvh"):
+            raise ValueError('query_accel must be "off" or "bvh"')
+        self._chk(self.L.sh_set_query_accel(self.h, _lib.ACCEL_BVH if mode == "bvh" else _lib.ACCEL_OFF))
+
     # ---- generalized winding numbers of the resident batch (include/shoulder_hip.h sh_winding_numbers) --------------------------
     def winding_numbers(self, points):
         """The generalized winding number of every resident humerus about every query point -> a structured array (B, Q) of
