@@ -641,7 +641,20 @@ int sh_resect_plan(sh_ctx*, const sh_plan_rule* rule, const uint64_t* compat /* 
  * box-frame parameter and equals "anp.ray_t" for the first hit; points are mapped to CT exactly as the record's anp_axis_normal /
  * anp_axis_central rows are, so hits[b][ray][0].point equals the record's row bit for bit.  A humerus whose record failed gets its
  * status and zero counts; it never fails the batch.  Without a collected run of the resident batch that had SH_STAGE_ANP:
- * SH_ERR_STATE.  status must not be NULL; hits and counts may be. */
+ * SH_ERR_STATE.  status must not be NULL; hits and counts may be.
+ *
+ * sh_ray_nearest returns the nearest hit only (`ray.intersects_first`, `intersects_location(multiple_hits=False)`): per (humerus,
+ * ray) the minimum of all hits under (t, face) -- the bytes of hits[b][r][0] of sh_ray_cast; a ray that hits nothing gets zero with
+ * face = -1.  Arguments, limits, refusals and their order are sh_ray_cast's (cap = 1).  The result stays resident as "ray.near"
+ * (B x R sh_ray_hit) until the next upload / commit / sh_store("verts").  With SH_ACCEL_OFF it is the chain of sh_ray_cast with cap = 1
+ * (and rewrites "ray.hits" / "ray.counts" at that cap); with SH_ACCEL_BVH it is one launch through the face hierarchy (k_raytree.h).
+ *
+ * With sh_set_query_accel(SH_ACCEL_BVH) sh_ray_cast and sh_ray_nearest descend the face hierarchy ("bvh.*", built first when it is not
+ * resident) instead of testing every face: one ray per lane, a node skipped only when the hit rule AS COMPUTED rejects every face in it
+ * (k_raytree.h states the argument).  THE RESULTS ARE THE SAME BYTES in either mode.  The rule must grow every box by what the hit
+ * rule's division admits, and as measured the descent is SLOWER than the walk over all faces for rays: the switch buys
+ * rays no time, only sh_ray_nearest without a host round trip.  sh_anp_axis_hits stays on the walk over all faces: its corners are the
+ * vertices under "obb_transform", which the index does not hold. */
 #define SH_RAY_MAX 65536
 #define SH_RAY_MAX_HITS 1024
 typedef struct sh_ray { double origin[3], dir[3]; } sh_ray;
@@ -650,6 +663,8 @@ int sh_ray_cast(sh_ctx*, const sh_ray* rays /* R, or B x R when per_humerus */, 
                 sh_ray_hit* hits /* B x R x cap, host, nullable */, int32_t* counts /* B x R, host, nullable */);
 int sh_anp_axis_hits(sh_ctx*, int cap, sh_ray_hit* hits /* B x 4 x cap, host, nullable */, int32_t* counts /* B x 4, host, nullable */,
                      int32_t* status /* B, host */);
+int sh_ray_nearest(sh_ctx*, const sh_ray* rays /* R, or B x R when per_humerus */, int R, int per_humerus,
+                   sh_ray_hit* hit /* B x R, host, nullable */);
 
 /* ---- closest surface points of the resident batch ------------------------------------------------------------------------------
  * The counterpart of `trimesh.proximity.closest_point(mesh, points)`: for Q query points, shared by all humeri or Q per humerus, the
@@ -1080,7 +1095,9 @@ int sh_geodesic(sh_ctx*, int mode, int K, double max_dist, const int32_t* src_of
  * through the hierarchy (k_cp_tree instead of k_cp_walk; the index is built first when "bvh.order" is not resident).  A node is skipped
  * only when every face in it would compute a d2 strictly above the point's best (k_bvh.h states the argument), and the winner is the
  * minimum of (d2, face) under a total order: THE RESULTS ARE THE SAME BYTES in either mode.  SH_ACCEL_OFF (0) is the default; a mode
- * that is neither is SH_ERR_ARG.  sh_winding_numbers, the rays, the samples and the geodesics do not read the index. */
+ * that is neither is SH_ERR_ARG.  The same switch routes sh_ray_cast and sh_ray_nearest through the hierarchy (see the rays above; the
+ * box-frame rays of sh_anp_axis_hits stay on the walk over all faces).  sh_winding_numbers, the samples and the geodesics do not read the
+ * index. */
 #define SH_ACCEL_OFF      0
 #define SH_ACCEL_BVH      1
 #define SH_BVH_INFO_BYTES 48

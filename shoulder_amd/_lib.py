@@ -299,6 +299,7 @@ SIGNATURES = {      # name -> (argtypes, restype, optional)
     "sh_resect_plan": _f(_vp, _P(PlanRule), _vp, _vp, _i, _vp, _vp, optional=True),
     "sh_ray_cast": _f(_vp, _vp, _i, _i, _i, _vp, _vp, optional=True),
     "sh_anp_axis_hits": _f(_vp, _i, _vp, _vp, _vp, optional=True),
+    "sh_ray_nearest": _f(_vp, _vp, _i, _i, _vp, optional=True),
     "sh_closest_points": _f(_vp, _vp, _i, _i, _vp, optional=True),
     "sh_winding_numbers": _f(_vp, _vp, _i, _i, _vp, optional=True),
     "sh_register_points": _f(_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, optional=True),

@@ -446,10 +446,9 @@ class ProximalHumerus(Bone):
         return -theta if int(lm["side"]) == 1 else theta
 
     # -- rays against the mesh --------------------------------------------------------------------------------
-    def ray_hits(self, origins, directions):
-        """`mesh.ray.intersects_location(origins, directions)` in the CURRENT coordinate system on the device (Engine.ray_cast):
-        -> (locations (n, 3), index_ray (n,), index_tri (n,)), sorted by ray and then by (t, face).  The rays go to CT through the
-        inverse of the current transform (points by the full matrix, directions by its linear part), the locations come back through it."""
+    def _rays_ct(self, origins, directions):
+        """rays given in the CURRENT coordinate system -> (origins and directions in CT, the current matrix); the bone is resident
+        afterwards.  Points go through the inverse of the current transform by the full matrix, directions by its linear part."""
         o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
         if len(o) != len(d) or len(o) < 1:
@@ -457,11 +456,64 @@ class ProximalHumerus(Bone):
         T = np.array(self._tfrm.matrix, dtype=np.float64)
         Ti = np.linalg.inv(T)
         self._ensure_loaded()
-        hits, counts = self._engine.ray_cast(self._engine.transform_points(o, Ti), d @ Ti[:3, :3].T, cap=None)
+        return self._engine.transform_points(o, Ti), d @ Ti[:3, :3].T, T
+
+    def ray_hits(self, origins, directions, accel=None):
+        """`mesh.ray.intersects_location(origins, directions)` in the CURRENT coordinate system on the device (Engine.ray_cast):
+        -> (locations (n, 3), index_ray (n,), index_tri (n,)), sorted by ray and then by (t, face).  The rays go to CT through the
+        inverse of the current transform (points by the full matrix, directions by its linear part), the locations come back through it.
+        accel="bvh": through the face hierarchy (Engine.query_accel), the same results."""
+        o, d, T = self._rays_ct(origins, directions)
+        with self._accel(accel):
+            hits, counts = self._engine.ray_cast(o, d, cap=None)
         keep = np.arange(hits.shape[2])[None, :] < counts[0][:, None]
         loc_ct = np.ascontiguousarray(hits[0]["point"][keep])
         loc = self._engine.transform_points(loc_ct, T) if len(loc_ct) else np.zeros((0, 3))
         return loc, np.nonzero(keep)[0], np.array(hits[0]["face"][keep], dtype=np.int64)
+
+    def ray_first(self, origins, directions, accel=None):
+        """`mesh.ray.intersects_location(origins, directions, multiple_hits=False)` / `intersects_first` in the CURRENT coordinate
+        system on the device (Engine.ray_nearest): the nearest hit of every ray that has one -> (locations (m, 3), index_ray (m,),
+        index_tri (m,)), by ray: the first location per ray of ray_hits.  accel as in ray_hits."""
+        o, d, T = self._rays_ct(origins, directions)
+        with self._accel(accel):
+            hit = self._engine.ray_nearest(o, d)[0]
+        keep = hit["face"] >= 0
+        loc_ct = np.ascontiguousarray(hit["point"][keep])
+        loc = self._engine.transform_points(loc_ct, T) if len(loc_ct) else np.zeros((0, 3))
+        return loc, np.nonzero(keep)[0], np.array(hit["face"][keep], dtype=np.int64)
+
+    def thickness(self, points=None, sample=None, seed=0, offset=1e-3, accel=None):
+        """`trimesh.proximity.thickness(mesh, points, method="ray")` in the CURRENT coordinate system on the device (Engine.thickness):
+        how much bone lies under a surface point along the inward normal -> (thickness (n,), opposite points (n, 3), opposite faces
+        (n,)); inf, a point of nan and face -1 where the ray meets nothing.  points (n, 3): each is snapped to the surface (closest_point) and takes the
+        unit normal of the winning face; or sample=n: the points and faces of sample_surface(n, seed).  offset (mm) starts the ray that
+        far under the point (Engine.thickness).  The normals follow the mesh's winding, as trimesh's do: on an inward-wound mesh the
+        rays leave the bone and the thickness is inf.  accel as in ray_hits (the snap of `points` goes the same way)."""
+        if (points is None) == (sample is None):
+            raise ValueError("give either points or sample=n")
+        self._ensure_loaded()
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        with self._accel(accel):
+            if points is not None:
+                rec, _ = self._closest_ct(points)
+                if np.any(rec["status"] != 0):
+                    raise ValueError("thickness: a point could not be snapped to the surface")
+                p_ct, face = np.ascontiguousarray(rec["point"]), np.array(rec["face"], dtype=np.int64)
+            else:
+                rec, info = self._engine.sample_surface(int(sample), seed=seed)
+                if info[0]["status"] != 0:
+                    raise ValueError(f"thickness: sample_surface failed with status {int(info[0]['status'])}")
+                p_ct, face = np.ascontiguousarray(rec[0]["point"]), np.array(rec[0]["face"], dtype=np.int64)
+            if not self._engine._has_buffer("vert.face"):
+                self._engine.vertex_fields()
+            normals = self._engine.face_normals(0)[0][face]
+            out = self._engine.thickness(p_ct, normals, offset=offset)[0]
+        hit = out["face"] >= 0
+        opp = np.full((len(out), 3), np.nan)
+        if hit.any():
+            opp[hit] = self._engine.transform_points(np.ascontiguousarray(out["point"][hit]), T)
+        return np.array(out["thickness"]), opp, np.array(out["face"], dtype=np.int64)
 
     # -- closest surface points ---------------------------------------------------------------------------------
     def _points_ct(self, points):
@@ -475,7 +527,7 @@ class ProximalHumerus(Bone):
 
     @contextlib.contextmanager
     def _accel(self, accel):
-        """accel=None: the engine as it is configured; "off" | "bvh": its closest-point step switched for this call (Engine.query_accel:
+        """accel=None: the engine as it is configured; "off" | "bvh": its closest-point step and its rays switched for this call (Engine.query_accel:
         the same results either way) and put back afterwards"""
         if accel is None:
             yield

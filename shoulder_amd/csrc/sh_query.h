@@ -143,17 +143,22 @@ __attribute__((always_inline)) inline ArthroError point_set(const double* points
 
 // ---- the plans and the bytes of every buffer ----------------------------------------------------------------------------------------
 // a cast of R rays per humerus with room for cap hits each: everything but the pool, which the counts size ("ray.pool", ray_pool_bytes)
-struct RayPlan { int tmax, chunks; size_t rays; RayBytes bytes; };      // face tiles per humerus, ray chunks, B x R
-inline RayPlan ray_plan(int B, int R, bool per_humerus, int cap, long long maxF, bool with_status) {
-  const size_t n = (size_t)B * R;
+// tree: the walk descends the face hierarchy (k_raytree.h) -- chunks of AR_BVH_CHUNK rays, one per lane, and no "ray.blockhit".
+// near: the call is sh_ray_nearest -- the bytes of "ray.near" (B x R sh_ray_hit; a buffer of its own beside the list, which stays the
+// chain's) and the chain's buffers at cap = 1, or with `tree` "ray.rays" and "ray.near" alone.
+struct RayPlan { int tmax, chunks; size_t rays; RayBytes bytes; size_t near; };      // face tiles per humerus, ray chunks, B x R, ..., bytes of "ray.near"
+inline RayPlan ray_plan(int B, int R, bool per_humerus, int cap, long long maxF, bool with_status, bool tree = false, bool near = false) {
+  const size_t n = (size_t)B * R, near_bytes = near ? n * sizeof(sh_ray_hit) : 0;
   RayBytes z;
-  z.ray_rays = (per_humerus ? n : (size_t)R) * sizeof(sh_ray); z.ray_counts = n * 4; z.ray_offs = (n + 1) * 8; z.ray_cursor = n * 4;
+  z.ray_rays = (per_humerus ? n : (size_t)R) * sizeof(sh_ray);
+  const long long tmax = tiles_of(maxF, AR_RAY_TILE);
+  if (tree && near) return {(int)tmax, (R + AR_BVH_CHUNK - 1) / AR_BVH_CHUNK, n, z, near_bytes};
+  z.ray_counts = n * 4; z.ray_offs = (n + 1) * 8; z.ray_cursor = n * 4;
   z.ray_hits = n * cap * sizeof(sh_ray_hit);
   if (with_status) z.ray_status = (size_t)B * 4;
-  const long long tmax = tiles_of(maxF, AR_RAY_TILE);
-  const int chunks = (R + AR_RAY_CHUNK - 1) / AR_RAY_CHUNK;
-  z.ray_blockhit = (size_t)tmax * B * chunks * 4;      // one word per workgroup of the walk
-  return {(int)tmax, chunks, n, z};
+  const int chunks = tree ? (R + AR_BVH_CHUNK - 1) / AR_BVH_CHUNK : (R + AR_RAY_CHUNK - 1) / AR_RAY_CHUNK;
+  if (!tree) z.ray_blockhit = (size_t)tmax * B * chunks * 4;      // one word per workgroup of the walk
+  return {(int)tmax, chunks, n, z, near_bytes};
 }
 inline size_t ray_pool_bytes(unsigned long long total) { return (size_t)(total > 0 ? total : 1) * AR_RAY_KEY_BYTES; }
 
@@ -353,6 +358,12 @@ inline ArthroError precheck_ray_cast(const sh_ray* rays, int R, int per_humerus,
   const long long i = first_bad_ray(rays, per_humerus ? (size_t)f.B * R : (size_t)R);
   if (i >= 0) return {SH_ERR_ARG, "ray " + std::to_string(i) + " has a non-finite number or a zero direction"};
   return arthro_ok();
+}
+
+// (the order and the codes of precheck_ray_cast with cap = 1)
+inline ArthroError precheck_ray_nearest(const sh_ray* rays, int R, int per_humerus, const ArthroFacts& f) {
+  if (!f.ctx || !rays || R < 1 || R > SH_RAY_MAX) return {SH_ERR_ARG, "bad argument (R in 1..65536)"};
+  return precheck_ray_cast(rays, R, per_humerus, 1, f);
 }
 
 inline ArthroError precheck_anp_hits(int cap, const int32_t* status, const ArthroFacts& f) {

@@ -17,15 +17,49 @@ static_assert(AR_SAMP_CHUNK == SH_SAMP_CHUNK && AR_SAMP_HEAD == SH_SAMP_HEAD, "s
 static_assert(AR_TOPO_BLOCK == SH_TOPO_BLOCK && AR_TOPO_HEAD == SH_TOPO_HEAD, "sh_query.h: topology block, head of topo.state");
 static_assert(AR_VERT_BLOCK == SH_VERT_BLOCK && AR_VERT_FACE == SH_VTX_FACE, "sh_query.h: vertex block, doubles of a face record");
 
-// ---- rays, every hit (k_rays.h); the anatomic-neck rays also read the last run ----
+// ---- rays, every hit (k_rays.h, k_raytree.h); the anatomic-neck rays also read the last run ----
+static int bvh_build(sh_ctx* c, const char* fn);
+
+// THE ONE PLACE the switch of sh_set_query_accel is read for rays, as cp_walk_join is for points: do the rays of this call descend the
+// hierarchy?  Not the box-frame rays of sh_anp_axis_hits (T_obb): their corners are the vertices under "obb_transform", which the index
+// does not hold.  The plan of a call and its run ask here, so they agree.
+static bool ray_tree_mode(const sh_ctx* c, bool box) { return !box && c->query_accel == SH_ACCEL_BVH; }
+// the index, built when "bvh.order" is not resident (a new batch removed it)
+static int ray_tree_index(sh_ctx* c, const char* fn) { return c->at("bvh.order") ? SH_OK : bvh_build(c, fn); }
+
 // count -> scan -> the total to the host -> "ray.pool" -> fill -> sort -> copies back.  "ray.rays" (and "ray.status" with `box`) are filled
-// by the caller on the stream; T_obb / hstatus: the box transforms and the humeri to leave out (sh_anp_axis_hits), or null.
+// by the caller on the stream; T_obb / hstatus: the box transforms and the humeri to leave out (sh_anp_axis_hits), or null.  In tree mode
+// count and fill are k_ray_tree (one ray per lane: plain stores, nothing to clear); scan, pool and sort are the same launches.
 static int ray_run(sh_ctx* c, const RayPlan& plan, int R, int per_humerus, int cap, const double* T_obb, const int* hstatus, sh_ray_hit* hits, int32_t* counts) {
   int rc;
   const int B = c->B;
   const size_t n = plan.rays;
-  RayView v = view_of<RayView>(c);
   const bool box = T_obb != nullptr;
+  if (ray_tree_mode(c, box)) {
+    if ((rc = ray_tree_index(c, "the ray walk")) != SH_OK) return rc;
+    RayView v = view_of<RayView>(c);
+    BvhBufs t = view_of<BvhBufs>(c);
+    const dim3 grid((unsigned)plan.chunks, (unsigned)B), block(SH_BVH_CHUNK);
+    LAUNCH(c, "k_ray_tree", k_ray_tree<false>, grid, block, v.verts, v.faces, v.voff, v.foff, (const int*)t.bvh_order, (const int*)t.bvh_loose, (const int*)t.bvh_off,
+           (const float*)t.bvh_box, (const float*)t.bvh_tri, (const double*)v.ray_rays, R, per_humerus, v.ray_counts, (const unsigned long long*)nullptr, (int*)nullptr,
+           (RayKey*)nullptr);
+    LAUNCH(c, "k_ray_scan", k_ray_scan, dim3(1), dim3(1024), (const int*)v.ray_counts, (long long)n, v.ray_offs);
+    unsigned long long total = 0;
+    HIPCHK(c, hipMemcpyAsync(&total, v.ray_offs + n, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ENS_SHARED("ray.pool", ray_pool_bytes(total), 8);
+    v = view_of<RayView>(c);
+    t = view_of<BvhBufs>(c);
+    LAUNCH(c, "k_ray_tree", k_ray_tree<true>, grid, block, v.verts, v.faces, v.voff, v.foff, (const int*)t.bvh_order, (const int*)t.bvh_loose, (const int*)t.bvh_off,
+           (const float*)t.bvh_box, (const float*)t.bvh_tri, (const double*)v.ray_rays, R, per_humerus, v.ray_counts, (const unsigned long long*)v.ray_offs, v.ray_cursor,
+           v.ray_pool);
+    LAUNCH(c, "k_ray_sort", k_ray_sort<false>, dim3((unsigned)n), dim3(64), (const double*)v.ray_rays, R, per_humerus, (const unsigned long long*)v.ray_offs,
+           (const int*)v.ray_cursor, (const RayKey*)v.ray_pool, T_obb, cap, v.ray_hits);
+    if (hits) HIPCHK(c, hipMemcpyAsync(hits, v.ray_hits, n * cap * sizeof(sh_ray_hit), hipMemcpyDeviceToHost, c->stream));
+    if (counts) HIPCHK(c, hipMemcpyAsync(counts, v.ray_counts, n * 4, hipMemcpyDeviceToHost, c->stream));
+    return SH_OK;
+  }
+  RayView v = view_of<RayView>(c);
   HIPCHK(c, hipMemsetAsync(v.ray_counts, 0, n * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(v.ray_cursor, 0, n * 4, c->stream));
   HIPCHK(c, hipMemsetAsync(v.ray_blockhit, 0, plan.bytes.ray_blockhit, c->stream));
@@ -50,11 +84,39 @@ static int ray_run(sh_ctx* c, const RayPlan& plan, int R, int per_humerus, int c
 int sh_ray_cast(sh_ctx* c, const sh_ray* rays, int R, int per_humerus, int cap, sh_ray_hit* hits, int32_t* counts) {
   if (const ArthroError e = precheck_ray_cast(rays, R, per_humerus, cap, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_ray_cast", e);
   HIPCHK(c, hipSetDevice(c->device));
-  const RayPlan plan = ray_plan(c->B, R, per_humerus != 0, cap, c->maxF, false);
+  const RayPlan plan = ray_plan(c->B, R, per_humerus != 0, cap, c->maxF, false, ray_tree_mode(c, false));
   if (int rc = ensure_bytes(c, plan.bytes)) return rc;
   const RayView v = view_of<RayView>(c);
   HIPCHK(c, hipMemcpyAsync(v.ray_rays, rays, plan.bytes.ray_rays, hipMemcpyHostToDevice, c->stream));
   if (int rc = ray_run(c, plan, R, per_humerus != 0, cap, nullptr, nullptr, hits, counts)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// The nearest hit of every ray: row 0 of sh_ray_cast's answer, resident as "ray.near".  SH_ACCEL_OFF: the chain above with cap = 1 and a
+// copy of its B x R x 1 records; SH_ACCEL_BVH: k_ray_near alone, and the host looks at nothing before the result.
+int sh_ray_nearest(sh_ctx* c, const sh_ray* rays, int R, int per_humerus, sh_ray_hit* hit) {
+  if (const ArthroError e = precheck_ray_nearest(rays, R, per_humerus, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_ray_nearest", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool tree = ray_tree_mode(c, false);
+  const RayPlan plan = ray_plan(c->B, R, per_humerus != 0, 1, c->maxF, false, tree, true);
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  if (int rc = ensure_shared(c, "ray.near", plan.near, 8)) return rc;
+  if (tree) {
+    if (int rc = ray_tree_index(c, "sh_ray_nearest")) return rc;
+    const RayView v = view_of<RayView>(c);
+    const BvhBufs t = view_of<BvhBufs>(c);
+    HIPCHK(c, hipMemcpyAsync(v.ray_rays, rays, plan.bytes.ray_rays, hipMemcpyHostToDevice, c->stream));
+    LAUNCH(c, "k_ray_near", k_ray_near, dim3((unsigned)plan.chunks, (unsigned)c->B), dim3(SH_BVH_CHUNK), v.verts, v.faces, v.voff, v.foff, (const int*)t.bvh_order,
+           (const int*)t.bvh_loose, (const int*)t.bvh_off, (const float*)t.bvh_box, (const float*)t.bvh_tri, (const double*)v.ray_rays, R, per_humerus != 0 ? 1 : 0,
+           (sh_ray_hit*)c->at("ray.near"));
+  } else {
+    const RayView v = view_of<RayView>(c);
+    HIPCHK(c, hipMemcpyAsync(v.ray_rays, rays, plan.bytes.ray_rays, hipMemcpyHostToDevice, c->stream));
+    if (int rc = ray_run(c, plan, R, per_humerus != 0, 1, nullptr, nullptr, nullptr, nullptr)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->at("ray.near"), c->at("ray.hits"), plan.near, hipMemcpyDeviceToDevice, c->stream));      // (cap = 1: row 0 is all of it)
+  }
+  if (hit) HIPCHK(c, hipMemcpyAsync(hit, c->at("ray.near"), plan.near, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }
@@ -112,7 +174,7 @@ static int bvh_enqueue(sh_ctx* c, const char* fn) {
 }
 
 // ... and a build that did not get through leaves no "bvh.order" behind: that name is what says "the index of this batch is resident"
-static int bvh_build(sh_ctx* c, const char* fn) {
+static int bvh_build(sh_ctx* c, const char* fn) {      // (declared above the rays, which build it too)
   const int rc = bvh_enqueue(c, fn);
   if (rc != SH_OK)
     if (auto it = c->bufs.find("bvh.order"); it != c->bufs.end()) {
@@ -142,6 +204,7 @@ int sh_get_query_accel(const sh_ctx* c) { return c ? c->query_accel : SH_ACCEL_O
 // The walk and its join for B x Q device points `pts` (per != 0: Q of its own for every humerus) over S face splits, from `part` into `out`.
 // THE ONE PLACE sh_closest_points and the evaluations of a registration go through: with SH_ACCEL_BVH the walk is k_cp_tree over the
 // hierarchy (built here when "bvh.order" is not resident: a new batch removed it), one partial per point, and the same join with S = 1.
+// (The rays read the switch in ray_tree_mode.)
 static int cp_walk_join(sh_ctx* c, const MeshBufs& m, const double* pts, int Q, int per, int chunks, int S, size_t points, CpPart* part, sh_closest* out) {
   if (c->query_accel == SH_ACCEL_BVH) {
     if (!c->at("bvh.order"))

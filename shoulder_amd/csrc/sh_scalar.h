@@ -2073,4 +2073,124 @@ SH_HD void bvh_descend(const double* p, const int* row, const float* bx, const f
   *best_io = best; *best_f_io = best_f;
 }
 
+// ---- rays through the face hierarchy (include/shoulder_hip.h sh_ray_cast with SH_ACCEL_BVH, sh_ray_nearest; k_raytree.h) ----------------
+// THE SKIP RULE OF A RAY (k_raytree.h states the argument): may the ray r (bvh_ray_set) skip the node with the float32 box bx?  tbest: the
+// t of the best hit so far, +inf for a walk that wants every hit.  The half-line {o + s d, s >= 0} is held against the box grown on
+// every side by
+//     pad = 2^-8 |d| D E^2 + 2^-40 m1,
+// D the distance from o to the box's far corner, E its diagonal, m1 the sum over the axes of the larger absolute bound.  Nothing is
+// skipped when |d|^2 or D^2 is above 2^40 (or is NaN).  Every comparison that skips is written so that it is false for a NaN.
+// *tn_out: the parameter at which the half-line enters the grown box, as computed (0 inside it; what the children are ordered by).
+#define SH_BVH_RAY_GUARD2 0x1p40
+// a ray as the skip rule reads it, formed once per ray: dd = d . d, dl = sqrt(dd), and the reciprocals of dl and of the components of d
+struct BvhRay { double o[3], d[3], inv[3], dd, dl, inv_dl; };
+SH_HD void bvh_ray_set(const double* o, const double* d, BvhRay* r) {
+  for (int k = 0; k < 3; ++k) { r->o[k] = o[k]; r->d[k] = d[k]; r->inv[k] = 1.0 / d[k]; }
+  r->dd = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+  r->dl = sqrt(r->dd);
+  r->inv_dl = 1.0 / r->dl;
+}
+SH_HD bool bvh_ray_box_skip(const BvhRay& r, const float* bx, double tbest, double* tn_out) {
+  double lo[3], hi[3], df[3], ex[3], m1 = 0.0;
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = (double)bx[k]; hi[k] = (double)bx[3 + k];
+    df[k] = fmax(fabs(lo[k] - r.o[k]), fabs(r.o[k] - hi[k]));
+    ex[k] = hi[k] - lo[k];
+    m1 = m1 + fmax(fabs(lo[k]), fabs(hi[k]));
+  }
+  const double far2 = (df[0] * df[0] + df[1] * df[1]) + df[2] * df[2], ext2 = (ex[0] * ex[0] + ex[1] * ex[1]) + ex[2] * ex[2];
+  *tn_out = 0.0;
+  if (!(r.dd <= SH_BVH_RAY_GUARD2 && far2 <= SH_BVH_RAY_GUARD2)) return false;
+  const double pad = (0x1p-8 * r.dl) * (sqrt(far2) * ext2) + m1 * 0x1p-40;      // (finite: every factor is bounded)
+  double tn = 0.0, tf = INFINITY;
+  bool beside = false;
+  for (int k = 0; k < 3; ++k) {
+    const double l = lo[k] - pad, h = hi[k] + pad;
+    if (r.d[k] == 0.0) {      // the ray keeps this coordinate: it is in the slab or it is not; no product, no quotient
+      if (r.o[k] < l || r.o[k] > h) beside = true;
+    } else if (fabs(r.inv[k]) < INFINITY) {      // a finite difference times a finite, non-zero reciprocal: +-inf at worst, never 0 * inf
+      const double t1 = (l - r.o[k]) * r.inv[k], t2 = (h - r.o[k]) * r.inv[k];
+      tn = fmax(tn, fmin(t1, t2));
+      tf = fmin(tf, fmax(t1, t2));
+    }                         // (a component so small that its reciprocal overflows: this axis decides nothing, which skips less)
+  }
+  *tn_out = tn;
+  if (beside) return true;
+  if (tn > tf + fabs(tf) * 0x1p-40) return true;      // (inf > inf, and anything against a NaN, is false)
+  return (tn - pad * r.inv_dl) * (1.0 - 0x1p-40) > tbest;      // behind the best hit; false for tbest = +inf and for dl = 0
+}
+
+// THE DESCENT OF ONE RAY through the tree of one mesh (k_raytree.h runs it with a stack in LDS, the host twin with an array), the
+// arguments as bvh_descend's.  Pop a node word (level << 28 | node); a walk that prunes by t tests its box again (the best may have
+// fallen since it was pushed), the others have tested it when they pushed it.  A leaf runs ray_tri_hit on its entries of "bvh.tri", the
+// corners widened as bvh_tri_d2 widens them with e1 = B - A and e2 = C - A taken first: t, side and the verdict are the bits ray_walk
+// (k_rays.h) computes from the mesh.  Every hit goes to hit(t, face = ord[i], side); Hit::PRUNE says whether hit.bound() (the best t so
+// far) may skip nodes.  An inner node pushes the children it may not skip, the one the ray enters first last.  The stack holds at most
+// (levels - 1) (WIDTH - 1) + 1 <= SH_BVH_STACK words, as bvh_descend's.  COUNT: count[0] += the nodes popped, count[1] += the faces tested.
+template <bool COUNT, typename Stack, typename Hit>
+SH_HD void bvh_ray_descend(const double* o, const double* d, const int* row, const float* bx, const float* tr, const int* ord, Stack& st, Hit& hit, long long* count) {
+  const int T = row[0], levels = row[3];
+  const int* lv = row + SH_BVH_OFF_LEVEL;
+  BvhRay ray;
+  bvh_ray_set(o, d, &ray);
+  int sp = 0;
+  if (levels > 0) st.at(sp++) = (unsigned)(levels - 1) << 28;
+  while (sp > 0) {
+    const unsigned e = st.at(--sp);
+    const int k = (int)(e >> 28), j = (int)(e & 0x0fffffffu);
+    double tn;
+    if (COUNT) ++count[0];
+    if (Hit::PRUNE || k == levels - 1) {      // (the root is tested here in every walk)
+      const float* nb = bx + 6 * ((size_t)lv[k] + (size_t)j);
+      const float bb[6] = {nb[0], nb[1], nb[2], nb[3], nb[4], nb[5]};
+      if (bvh_ray_box_skip(ray, bb, hit.bound(), &tn)) continue;
+    }
+    if (k == 0) {
+      const int i0 = j * SH_BVH_LEAF, i1 = i0 + SH_BVH_LEAF < T ? i0 + SH_BVH_LEAF : T;
+      for (int i = i0; i < i1; ++i) {
+        const float* t = tr + 9 * (size_t)i;
+        const double A[3] = {(double)t[0], (double)t[1], (double)t[2]};
+        const double e1[3] = {(double)t[3] - A[0], (double)t[4] - A[1], (double)t[5] - A[2]}, e2[3] = {(double)t[6] - A[0], (double)t[7] - A[1], (double)t[8] - A[2]};
+        double th = 0.0;
+        int side = 0;
+        if (COUNT) ++count[1];
+        if (ray_tri_hit(o, d, A, e1, e2, &th, &side)) hit(th, ord[i], side);
+      }
+    } else {
+      const int below = lv[k] - lv[k - 1];
+      const int c0 = j * SH_BVH_WIDTH, c1 = c0 + SH_BVH_WIDTH < below ? c0 + SH_BVH_WIDTH : below;
+      const float* ch = bx + 6 * (size_t)lv[k - 1];
+      const unsigned tag = (unsigned)(k - 1) << 28;
+      int first = -1;
+      double first_t = 0.0;
+      for (int c = c0; c < c1; ++c) {
+        const float* nb = ch + 6 * (size_t)c;
+        const float bb[6] = {nb[0], nb[1], nb[2], nb[3], nb[4], nb[5]};
+        if (bvh_ray_box_skip(ray, bb, hit.bound(), &tn)) continue;
+        if (first < 0 || tn < first_t) {
+          if (first >= 0) st.at(sp++) = tag | (unsigned)first;
+          first = c; first_t = tn;
+        } else st.at(sp++) = tag | (unsigned)c;
+      }
+      if (first >= 0) st.at(sp++) = tag | (unsigned)first;
+    }
+  }
+}
+
+// the three readers of a descent: the count, the fill of a ray's segment of the pool (room: its length -- a write is guarded, as the
+// brute fill's), the nearest hit under ray_key_less
+struct RayHitCount {
+  static constexpr bool PRUNE = false;
+  int n = 0;
+  SH_HD double bound() const { return INFINITY; }
+  SH_HD void operator()(double, int, int) { ++n; }
+};
+struct RayHitNear {
+  static constexpr bool PRUNE = true;
+  double t = INFINITY;
+  int face = -1, side = 0;
+  SH_HD double bound() const { return t; }
+  SH_HD void operator()(double th, int f, int s) { if (ray_key_less(th, f, t, face)) { t = th; face = f; side = s; } }
+};
+
 }  // namespace sh
