@@ -1069,6 +1069,78 @@ int sh_geodesic(sh_ctx*, int mode, int K, double max_dist, const int32_t* src_of
                 const double* d0 /* host, nullable */, double* dist /* K sumV, host, nullable */, int32_t* pred /* K sumV, host, nullable */,
                 int32_t* source /* K sumV, host, nullable */, void* info /* B K x SH_GEO_INFO_BYTES, host, nullable */);
 
+/* ---- smoothing of the vertices of the resident batch ----------------------------------------------------------------------------------------
+ * Surfaces segmented from CT carry the voxel staircase; this moves the vertices themselves (k_smooth.h): the vertex -> vertex rows of
+ * every mesh (trimesh's `vertex_neighbors`) and on them the Laplacian, Taubin and HC filters (trimesh.smoothing.filter_laplacian,
+ * filter_taubin, filter_humphrey).  Everything is float64, operation by operation, + - x / sqrt only; indices are local to the mesh;
+ * "degenerate" and "row" mean what they mean in sh_mesh_topology; dot3(a, b) = (a0 b0 + a1 b1) + a2 b2.  The result is the same bytes
+ * wherever the rule runs, and a mesh's result depends on that mesh and the arguments alone: not on B, its place in the batch or a launch.
+ *   start        P0 is the resident float32 "verts" widened to float64.
+ *   rows         "smooth.nrow", int32, V_b + 1 entries per mesh at voff[b] + b, exclusive prefix sums; "smooth.nbr", int32, mesh b from
+ *                6 foff[b] (room for two neighbours per corner; the mesh uses the first nrow[V_b] places): row v lists the DISTINCT
+ *                vertices u != v that share a non-degenerate face with v in ASCENDING index -- the order is part of the definition: it
+ *                is the order of every sum below.  As sets the rows are trimesh's vertex_neighbors on a mesh without degenerate faces.  A
+ *                vertex no face uses has an empty row; a row has no assumed length.  The rows depend on the faces alone, are built once
+ *                and stay resident for the batch.
+ *   weights      SH_SMOOTH_UNIFORM: w = 1.0 for every neighbour.  SH_SMOOTH_INVLEN: w_vu = 1.0 / l, l = sqrt(dot3(D, D)), D = P0_hi - P0_lo
+ *                with lo = min(v, u), hi = max(v, u): both directions hold the same bytes, as "geo.face" does.  They are taken ONCE, from
+ *                P0, and kept in "smooth.w" beside "smooth.nbr" (float64, the same places); a neighbour with l == 0.0 or l not finite is
+ *                stored as 0.0 and skipped under SH_SMOOTH_INVLEN: it enters neither sum.
+ *   mean         M(x)[v] of a field x of 3 doubles per vertex: S = sum w x[u], W = sum w, the accumulators starting at 0.0 and adding one
+ *                term per neighbour in the row's order, component by component (each term the product w * x[u][c], then the sum);
+ *                M(x)[v] = S / W.  M(x)[v] = x[v] instead when v is pinned, the row is empty, nothing was added or W is not finite.
+ *   step         step(P, c)[v] = P[v] + c * (M(P)[v] - P[v]): the difference, then the product, then the sum.
+ *   filters      all iterate from P = P0; with 0 iterations the result is P0 and the call only builds the rows.
+ *                SH_SMOOTH_LAPLACIAN (p0 = lambda): iterations x step(., lambda).
+ *                SH_SMOOTH_TAUBIN (p0 = lambda, p1 = mu <= 0): an iteration is step(., lambda), then step(., mu).
+ *                SH_SMOOTH_HC (p0 = alpha, p1 = beta; Vollmer's Humphrey's-classes filter), per iteration: q = P; p = M(q);
+ *                b = p - (alpha * P0 + (1.0 - alpha) * q), the bracket added left to right; P = p - (beta * b + (1.0 - beta) * M(b)),
+ *                M(b) with the same rows, weights and pins.  At a pinned vertex b is 0.0 by definition (alpha x + (1 - alpha) x need not
+ *                round to x), so p = q = P0 there and it stays put.
+ *   pins         a vertex is pinned when its byte of the optional host mask `pin` (sumV bytes) is non-zero, or when SH_SMOOTH_PIN_BORDER
+ *                is set and one of the two slots of "topo.adj" that touch it in a face of its incidence row is SH_ADJ_BORDER or
+ *                SH_ADJ_NONMANIFOLD: the test behind SH_VERT_BORDER | SH_VERT_NONMANIFOLD.
+ *   keep volume  SH_SMOOTH_KEEP_VOLUME: after the last iteration one uniform scaling about the centre of mass restores the volume of P0.
+ *                With T(X) the sums of terms 13 .. 16 of sh_mass_properties (d = dot3(a, cross3(b, c)) and d s, the pivot o = P0 of
+ *                vertex 0 for both) over ALL faces of the mesh on the vertices X, in THE TREE of that call (blocks of SH_MASS_BLOCK faces,
+ *                h = 128 .. 1, the block sums in block order): V0 = T13(P0) / 6.0, V1 = T13(P) / 6.0, c = T14..16(P) / (4.0 * T13(P)) + o,
+ *                r = V0 / V1, s ten Newton steps from s = 1.0 on s^3 = r, each s = s - ((s * s) * s - r) / (3.0 * (s * s));
+ *                P[v] = c + s * (P[v] - c).  A mesh gets status SH_ERR_GEOMETRY and NO scaling when V0 or V1 is 0.0 or not finite, r lies
+ *                outside [1/8, 8] or c is not finite -- never the batch.  The flag together with a pin (a mask pointer or
+ *                SH_SMOOTH_PIN_BORDER) is SH_ERR_ARG: a scaling moves pinned vertices.  In exact arithmetic the filters commute with a
+ *                uniform scaling, so one scaling at the end is what trimesh's per-iteration `volume_constraint` amounts to; equality with
+ *                trimesh is not claimed.
+ *   info         per mesh SH_SMOOTH_INFO_BYTES = 64 bytes, resident in "smooth.info": double volume_before (V0), volume_after (V1: before
+ *                the scaling), scale (s; 1.0 without the flag or with the status), max_disp, sum_sq_disp; int32 pinned, isolated (empty
+ *                rows), status, and three int32 of padding (0).  max_disp is the largest |P - P0| = sqrt(dot3(d, d)) of the result, a
+ *                value that is no number counting as 0.0; sum_sq_disp is the sum of dot3(d, d) over blocks of 256 consecutive vertices
+ *                in the same tree shape.  The layout is stated here and by shoulder_amd._lib.SMOOTH_INFO_DTYPE; it is not a typedef.
+ *
+ * Arguments in this order: the context (SH_ERR_ARG); filter, weight, iterations in 0..SH_SMOOTH_MAX_ITER and flags with known bits
+ * (SH_ERR_ARG); the two parameters, both finite whatever the filter, lambda in [0, 1], mu in [-1, 0], alpha and beta in [0, 1] (SH_ERR_ARG,
+ * the text names the argument; p1 of SH_SMOOTH_LAPLACIAN is not used); SH_SMOOTH_KEEP_VOLUME with a pin (SH_ERR_ARG); a resident batch
+ * and no runs in flight (SH_ERR_STATE); the incidence of THIS batch resident (SH_ERR_STATE: call sh_mesh_topology first; a topology
+ * that ran out of rounds is accepted).  SH_ERR_NOMEM when the buffers do not fit, or when the largest mesh has more than (2^31 - 1) / 6
+ * faces (its row starts are int32 and it has six places for neighbours per face).  The host enqueues every launch of the call (their
+ * number follows from the arguments: 3 for the rows when they are not resident, 1 + the M(.) evaluations + 5) and looks at nothing in
+ * between.  out (sumV x 3 doubles) and info may be NULL.  Reads "verts", "faces", the offsets, "topo.vrow", "topo.vface", "topo.adj";
+ * does NOT write "verts".  Resident afterwards: "smooth.pos" (3 doubles per vertex at 3 voff[b]), "smooth.nrow", "smooth.nbr",
+ * "smooth.w", "smooth.info" and the scratch "smooth.plane" (three planes: two of the iteration, one for b), "smooth.pin", "smooth.mask",
+ * "smooth.part".  They are removed together with "topo.*" by the next upload / commit / sh_store("verts").  Every other buffer keeps
+ * its bytes. */
+#define SH_SMOOTH_LAPLACIAN   0
+#define SH_SMOOTH_TAUBIN      1
+#define SH_SMOOTH_HC          2
+#define SH_SMOOTH_UNIFORM     0
+#define SH_SMOOTH_INVLEN      1
+#define SH_SMOOTH_PIN_BORDER  1
+#define SH_SMOOTH_KEEP_VOLUME 2
+#define SH_SMOOTH_MAX_ITER    256
+#define SH_SMOOTH_INFO_BYTES  64
+int sh_smooth_vertices(sh_ctx*, int filter, int weight, int iterations, int flags, double p0, double p1,
+                       const unsigned char* pin /* sumV, host, nullable */, double* out /* sumV x 3, host, nullable */,
+                       void* info /* B x SH_SMOOTH_INFO_BYTES, host, nullable */);
+
 /* ---- a face hierarchy of the resident batch, and the closest-point step through it -------------------------------------------------
  * sh_mesh_bvh builds, per resident mesh, a bounding-box hierarchy over its faces (k_bvh.h; the rules are sh_scalar.h bvh_*, all float32
  * min / max, one float64 quantisation and integer work, restated by tests/bvh_oracle.py):

@@ -37,6 +37,8 @@ VERT_WEIGHT_AREA, VERT_WEIGHT_ANGLE, VERT_MAX_SMOOTH, VERT_FIELDS = 0, 1, 64, 8
 VERT_USED, VERT_BORDER, VERT_NONMANIFOLD, VERT_FLAT = 1, 2, 4, 8
 GEO_EDGES, GEO_UNFOLD, GEO_MAX_SETS, GEO_LDS_VERTICES, GEO_CHUNK, GEO_INFO_BYTES = 0, 1, 16, 20000, 32, 32
 GEO_ROOT, GEO_NO_PRED, GEO_UNREACHED = -1, -2, -3
+SMOOTH_LAPLACIAN, SMOOTH_TAUBIN, SMOOTH_HC, SMOOTH_UNIFORM, SMOOTH_INVLEN = 0, 1, 2, 0, 1
+SMOOTH_PIN_BORDER, SMOOTH_KEEP_VOLUME, SMOOTH_MAX_ITER, SMOOTH_INFO_BYTES = 1, 2, 256, 64
 ACCEL_OFF, ACCEL_BVH, BVH_INFO_BYTES = 0, 1, 48
 
 # ---- the records ------------------------------------------------------------------------------------------------------------------------
@@ -218,6 +220,10 @@ Shell, SHELL_DTYPE = _record(
 # the info record of sh_geodesic per (mesh, set): the header states its 32 bytes in words, not as a typedef
 GEO_INFO_DTYPE = np.dtype([("far_dist", "<f8"), ("reached", "<i4"), ("roots", "<i4"), ("no_pred", "<i4"), ("farthest", "<i4"), ("sweeps", "<i4"), ("status", "<i4")])
 assert GEO_INFO_DTYPE.itemsize == GEO_INFO_BYTES
+# the info record of sh_smooth_vertices per mesh: stated in the header's text, as sh_geodesic's
+SMOOTH_INFO_DTYPE = np.dtype([(n, "<f8") for n in ("volume_before", "volume_after", "scale", "max_disp", "sum_sq_disp")]
+                             + [("pinned", "<i4"), ("isolated", "<i4"), ("status", "<i4"), ("pad", "<i4", (3,))])
+assert SMOOTH_INFO_DTYPE.itemsize == SMOOTH_INFO_BYTES
 # sh_bvh_info per mesh (sh_mesh_bvh): the header declares the struct and its typedef in two statements; stated here once, beside its bytes
 BVH_INFO_DTYPE = np.dtype([(n, "<i4") for n in ("tight", "loose", "leaves", "levels", "nodes", "reserved")] + [("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
 assert BVH_INFO_DTYPE.itemsize == BVH_INFO_BYTES
@@ -309,6 +315,7 @@ SIGNATURES = {      # name -> (argtypes, restype, optional)
     "sh_mesh_topology": _f(_vp, _P(TopologyOptions), _vp, _vp, optional=True),
     "sh_vertex_fields": _f(_vp, _i, _i, _vp, _vp, _vp, _vp, optional=True),
     "sh_geodesic": _f(_vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, optional=True),
+    "sh_smooth_vertices": _f(_vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, optional=True),
     "sh_mesh_bvh": _f(_vp, _vp, optional=True),
     "sh_set_query_accel": _f(_vp, _i, optional=True),
     "sh_get_query_accel": _f(_vp, optional=True),

@@ -650,6 +650,24 @@ class ProximalHumerus(Bone):
         return dict(gauss=gauss, mean=mean, k1=mean + root, k2=mean - root, area=r["area"], defect=r["defect"], normals=r["normals"],
                     border=(r["flags"] & _lib.VERT_BORDER) != 0)
 
+    # -- smoothing of the vertices ---------------------------------------------------------------------------------------
+    def smoothed_mesh(self, **options):
+        """This bone with its vertices smoothed on the device (Engine.smooth_vertices, whose options these are: filter, iterations,
+        lamb, mu, alpha, beta, weight, pin, pin_border, keep_volume; default ten Taubin iterations) -> (verts (V, 3) float64, faces) in
+        the CURRENT coordinate system, ready for Engine.upload: what `trimesh.smoothing.filter_taubin(mesh)` leaves in the mesh, before
+        the staircase of the CT voxels enters curvatures, thickness or a registration.  The resident mesh is not changed.  Two ways on:
+            engine.upload([(verts.astype(np.float32), faces)])            # a new batch of the float32-rounded vertices (from CT: call
+                                                                          # it while the bone is in CT)
+            engine.store("verts", verts_ct.astype(np.float32))            # or new vertices for the resident faces: the queries that
+                                                                          # follow (vertex_fields, mass_properties ...) measure them
+        Raises ValueError when keep_volume could not restore the volume."""
+        self._ensure_loaded()
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        r = self._engine.smooth_vertices(**options)
+        if r["info"][0]["status"] != 0:
+            raise ValueError(f"smoothed_mesh failed with status {int(r['info'][0]['status'])}: the volume could not be restored")
+        return self._engine.transform_points(np.ascontiguousarray(r["vertices"]), T), np.array(self._faces, dtype=np.int32)
+
     # -- distances along the surface -------------------------------------------------------------------------------
     def _geodesic_seeds(self, where):
         """a vertex index, or a 3-D point in the CURRENT coordinate system -> (vertices, d0): the vertex itself with 0.0, or the point

@@ -1,8 +1,8 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields), the geodesics (sh_geodesic) and the face hierarchy (sh_mesh_bvh, sh_set_query_accel).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields), the geodesics (sh_geodesic), the smoothing of the vertices (sh_smooth_vertices) and the face hierarchy (sh_mesh_bvh, sh_set_query_accel).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo,bvh}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo,bvh,smooth}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
@@ -62,6 +62,12 @@ struct RayKey; struct CpPart; struct GeoInfo;
   X(bvh_tri, "bvh.tri", float, 4) X(bvh_info, "bvh.info", sh_bvh_info, 4) X(bvh_state, "bvh.state", unsigned, 4)                   \
   X(bvh_base, "bvh.base", int, 4) X(bvh_seg, "bvh.seg", unsigned, 4) X(bvh_key, "bvh.key", unsigned long long, 8)                  \
   X(bvh_sorted, "bvh.sorted", unsigned long long, 8)
+// the vertex -> vertex rows (row starts, neighbours, the stored weights beside them), the result and the info records; scratch: three planes
+// of 3 sumV doubles (two for the iteration, one for b of the HC filter), the pins, the host's mask, the block rows and heads of the sums
+#define SMOOTH_BUFS(X)                                                                                                             \
+  X(smooth_nbr, "smooth.nbr", int, 4) X(smooth_w, "smooth.w", double, 8) X(smooth_pos, "smooth.pos", double, 8)                    \
+  X(smooth_info, "smooth.info", SmoothInfo, 8) X(smooth_plane, "smooth.plane", double, 8) X(smooth_pin, "smooth.pin", int, 4)      \
+  X(smooth_mask, "smooth.mask", unsigned char, 1) X(smooth_part, "smooth.part", double, 8) X(smooth_nrow, "smooth.nrow", int, 4)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -77,6 +83,8 @@ using VertView = BufJoin<MeshBufs, TopoBufs, VertBufs>;      // (the mesh, the i
 SH_BUF_LIST(Geo, GEO_BUFS)
 using GeoView = BufJoin<MeshBufs, TopoBufs, GeoBufs>;
 SH_QUERY_LIST(Bvh, BVH_BUFS)
+SH_BUF_LIST(Smooth, SMOOTH_BUFS)
+using SmoothView = BufJoin<MeshBufs, TopoBufs, SmoothBufs>;
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -91,6 +99,7 @@ constexpr int AR_TOPO_BLOCK = 256, AR_TOPO_HEAD = 64;                           
 constexpr int AR_VERT_BLOCK = 256, AR_VERT_FACE = 10;                             // SH_VERT_BLOCK, SH_VTX_FACE
 constexpr int AR_GEO_BLOCK = 256, AR_GEO_FACE = 6, AR_GEO_STATE = 8;              // SH_GEO_BLOCK, SH_GEOD_FACE, SH_GEO_STATE
 constexpr int AR_BVH_BLOCK = 256, AR_BVH_HEAD = 8, AR_BVH_CHUNK = 64;             // SH_BVH_BLOCK, SH_BVH_HEAD, SH_BVH_CHUNK
+constexpr int AR_SMOOTH_BLOCK = 256;                                              // SH_SMOOTH_BLOCK
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -284,6 +293,28 @@ inline GeoPlan geo_plan(int B, int K, long long S, int lds_vertices, long long m
   return {(int)tiles_of(maxF, AR_GEO_BLOCK), (int)tiles_of(maxV, AR_GEO_BLOCK), jumps, general, general ? maxV + 1 : 0, z};
 }
 
+// Smoothing of the vertices.  "smooth.nrow" has V_b + 1 int32 per mesh (mesh b at voff[b] + b); "smooth.nbr" and "smooth.w" room for two
+// neighbours per corner of a face (mesh b at 6 foff[b]; a mesh uses the first nrow[V_b] of its 6 F_b places); "smooth.pos" three doubles
+// per vertex and "smooth.plane" three such planes; "smooth.pin" one int32 and "smooth.mask" one byte per vertex; "smooth.part" the block
+// rows of the two volume sums (SH_SMO_TERMS doubles per face block of the largest mesh, for every mesh: at vol0 and vol1), the rows of
+// the displacement (two doubles per vertex block: at disp) and the heads (SH_SMO_HEAD doubles per mesh: at head).  Every size follows
+// from the batch alone, so a second call allocates nothing.  steps: the launches of k_smooth_round; last: the plane they leave P in.
+struct SmoothPlan { int fblocks, vblocks, steps, last; size_t plane, vol0, vol1, disp, head; SmoothBytes bytes; };      // (plane .. head: in doubles)
+inline SmoothPlan smooth_plan(int B, int filter, int iterations, long long maxV, long long maxF, long long sumV, long long sumF) {
+  const size_t f = (size_t)(sumF > 0 ? sumF : 1), v = (size_t)(sumV > 0 ? sumV : 1);
+  SmoothPlan p{};
+  p.fblocks = (int)tiles_of(maxF, AR_SMOOTH_BLOCK); p.vblocks = (int)tiles_of(maxV, AR_SMOOTH_BLOCK);
+  p.steps = filter == SH_SMOOTH_LAPLACIAN ? iterations : 2 * iterations;
+  p.last = filter == SH_SMOOTH_HC ? 0 : (p.steps & 1);      // (an HC iteration reads plane 0 and leaves P there)
+  p.plane = 3 * v;
+  p.vol0 = 0; p.vol1 = (size_t)B * p.fblocks * SH_SMO_TERMS; p.disp = 2 * p.vol1; p.head = p.disp + (size_t)B * p.vblocks * 2;
+  SmoothBytes& z = p.bytes;
+  z.smooth_nrow = ((size_t)sumV + B) * 4; z.smooth_nbr = 6 * f * 4; z.smooth_w = 6 * f * 8; z.smooth_pos = p.plane * 8;
+  z.smooth_info = (size_t)B * SH_SMOOTH_INFO_BYTES; z.smooth_plane = 3 * p.plane * 8; z.smooth_pin = v * 4; z.smooth_mask = (v + 3) / 4 * 4;
+  z.smooth_part = (p.head + (size_t)B * SH_SMO_HEAD) * 8;
+  return p;
+}
+
 // The face hierarchy (sh_scalar.h bvh_*).  "bvh.order", "bvh.loose", "bvh.key" and "bvh.sorted" follow the faces (mesh b at foff[b]) and
 // "bvh.tri" nine float32 per face; "bvh.box" has six float32 per node, mesh b from base[b] = the sum of bvh_nodes_of(F_a) over the meshes
 // before it -- room for a mesh without a loose face, known before the device has counted them; "bvh.off" SH_BVH_OFF_WORDS int32 and
@@ -446,6 +477,25 @@ inline ArthroError precheck_geodesic(int mode, int K, double max_dist, const int
     if (const std::string bad = geo_first_bad(f.B, K, voff, src_off, src, d0); !bad.empty()) return {SH_ERR_ARG, "bad argument (" + bad + ")"};
   if (const ArthroError e = resident(f); e.code) return e;
   if (!incidence) return {SH_ERR_STATE, "no incidence of the resident batch: call sh_mesh_topology first"};
+  return arthro_ok();
+}
+
+// incidence as in precheck_vertex_fields; has_pin: the call brings a mask; maxF: the faces of the largest resident mesh (its rows count in 32 bits)
+inline ArthroError precheck_smooth(int filter, int weight, int iterations, int flags, double p0, double p1, bool has_pin, bool incidence, long long maxF, const ArthroFacts& f) {
+  if (!f.ctx) return {SH_ERR_ARG, "bad argument (no context)"};
+  if (filter < SH_SMOOTH_LAPLACIAN || filter > SH_SMOOTH_HC || (weight != SH_SMOOTH_UNIFORM && weight != SH_SMOOTH_INVLEN) || iterations < 0 || iterations > SH_SMOOTH_MAX_ITER ||
+      (flags & ~(SH_SMOOTH_PIN_BORDER | SH_SMOOTH_KEEP_VOLUME)) != 0)
+    return {SH_ERR_ARG, "bad argument (filter 0, 1 or 2, weight 0 or 1, iterations in 0..256, flags 0..3)"};
+  const bool hc = filter == SH_SMOOTH_HC;
+  if (!std::isfinite(p0) || !(p0 >= 0.0 && p0 <= 1.0)) return {SH_ERR_ARG, std::string("bad argument (") + (hc ? "alpha" : "lambda") + " in 0..1)"};
+  if (!std::isfinite(p1)) return {SH_ERR_ARG, std::string("bad argument (") + (hc ? "beta" : "mu") + " is not finite)"};
+  if (hc && !(p1 >= 0.0 && p1 <= 1.0)) return {SH_ERR_ARG, "bad argument (beta in 0..1)"};
+  if (filter == SH_SMOOTH_TAUBIN && !(p1 >= -1.0 && p1 <= 0.0)) return {SH_ERR_ARG, "bad argument (mu in -1..0)"};
+  if ((flags & SH_SMOOTH_KEEP_VOLUME) && (has_pin || (flags & SH_SMOOTH_PIN_BORDER)))
+    return {SH_ERR_ARG, "bad argument (SH_SMOOTH_KEEP_VOLUME with a pin: the scaling would move pinned vertices)"};
+  if (const ArthroError e = resident(f); e.code) return e;
+  if (!incidence) return {SH_ERR_STATE, "no incidence of the resident batch: call sh_mesh_topology first"};
+  if (6 * maxF > 0x7fffffffLL) return {SH_ERR_NOMEM, "a mesh has more than 2^31 - 1 places for neighbours"};
   return arthro_ok();
 }
 

@@ -1,7 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
 // point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), the surface samples, sh_sample_surface
-// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), the geodesics, sh_geodesic (k_geo.h), and the face hierarchy, sh_mesh_bvh / sh_set_query_accel (k_bvh.h).
+// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), the geodesics, sh_geodesic (k_geo.h), the smoothing of the vertices, sh_smooth_vertices (k_smooth.h), and the face hierarchy, sh_mesh_bvh / sh_set_query_accel (k_bvh.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -446,6 +446,80 @@ int sh_vertex_fields(sh_ctx* c, int weight, int smooth_rounds, double* normals, 
   if (fields) HIPCHK(c, hipMemcpyAsync(fields, v.vert_fields, (size_t)sumV * SH_VERT_FIELDS * 8, hipMemcpyDeviceToHost, c->stream));
   if (flags) HIPCHK(c, hipMemcpyAsync(flags, v.vert_flags, (size_t)sumV * 4, hipMemcpyDeviceToHost, c->stream));
   if (status) HIPCHK(c, hipMemcpyAsync(status, v.vert_status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- smoothing of the vertices (k_smooth.h) ----
+// [count -> scan -> fill, when the rows of this batch are not resident] -> init -> one round per M(.) evaluation -> the volume of P0 and
+// of P -> scale -> apply -> info; the host looks at nothing in between.  "smooth.nrow" is what says "the rows of this batch are resident":
+// it is the last buffer of its list, so it exists only when every other one does, and a build that did not get through removes it.
+static_assert(AR_SMOOTH_BLOCK == SH_SMOOTH_BLOCK, "sh_query.h: smoothing block");
+
+static int smooth_rows(sh_ctx* c, const SmoothPlan& plan, const SmoothView& v) {
+  const dim3 vblocks((unsigned)plan.vblocks, (unsigned)c->B), lanes(SH_SMOOTH_BLOCK);
+  LAUNCH(c, "k_smooth_count", k_smooth_count, vblocks, lanes, v.faces, v.voff, v.foff, (const int*)v.topo_vrow, (const int*)v.topo_vface, v.smooth_nrow);
+  LAUNCH(c, "k_smooth_scan", k_smooth_scan, dim3((unsigned)c->B), lanes, v.voff, v.smooth_nrow);
+  LAUNCH(c, "k_smooth_fill", k_smooth_fill, vblocks, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_vrow, (const int*)v.topo_vface, (const int*)v.smooth_nrow,
+         v.smooth_nbr, v.smooth_w);
+  return SH_OK;
+}
+
+static int smooth_enqueue(sh_ctx* c, const SmoothPlan& plan, bool rows, int filter, int weight, int iterations, int flags, double p0, double p1, const unsigned char* pin) {
+  const SmoothView v = view_of<SmoothView>(c);
+  const int B = c->B;
+  if (!rows)
+    if (int rc = smooth_rows(c, plan, v)) return rc;
+  if (pin) HIPCHK(c, hipMemcpyAsync(v.smooth_mask, pin, (size_t)c->sumV, hipMemcpyHostToDevice, c->stream));      // (pageable: staged before the call returns)
+  const dim3 fblocks((unsigned)plan.fblocks, (unsigned)B), vblocks((unsigned)plan.vblocks, (unsigned)B), lanes(SH_SMOOTH_BLOCK), meshes((unsigned)B);
+  double* pl[3] = {v.smooth_plane, v.smooth_plane + plan.plane, v.smooth_plane + 2 * plan.plane};
+  const int *nrow = v.smooth_nrow, *nbr = v.smooth_nbr, *pins = v.smooth_pin;
+  const double* w = v.smooth_w;
+  LAUNCH(c, "k_smooth_init", k_smooth_init, vblocks, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_vrow, (const int*)v.topo_vface, (const int*)v.topo_adj,
+         pin ? (const unsigned char*)v.smooth_mask : (const unsigned char*)nullptr, flags & SH_SMOOTH_PIN_BORDER, pl[0], v.smooth_pin);
+  for (int it = 0; it < iterations; ++it) {
+    if (filter == SH_SMOOTH_HC) {
+      LAUNCH(c, "k_smooth_hc_b", k_smooth_round<1>, vblocks, lanes, v.verts, v.voff, v.foff, nrow, nbr, w, pins, weight, p0, (const double*)pl[0], (const double*)nullptr, pl[1], pl[2]);
+      LAUNCH(c, "k_smooth_hc_p", k_smooth_round<2>, vblocks, lanes, v.verts, v.voff, v.foff, nrow, nbr, w, pins, weight, p1, (const double*)pl[2], (const double*)pl[1], pl[0],
+             (double*)nullptr);
+      continue;
+    }
+    const int per = filter == SH_SMOOTH_TAUBIN ? 2 : 1;
+    for (int k = 0; k < per; ++k) {
+      const int s = it * per + k;
+      LAUNCH(c, "k_smooth_step", k_smooth_round<0>, vblocks, lanes, v.verts, v.voff, v.foff, nrow, nbr, w, pins, weight, k == 0 ? p0 : p1, (const double*)pl[s & 1],
+             (const double*)nullptr, pl[(s + 1) & 1], (double*)nullptr);
+    }
+  }
+  const double* fin = pl[plan.last];
+  double* part = v.smooth_part;
+  LAUNCH(c, "k_smooth_vol", k_smooth_vol<true>, fblocks, lanes, v.verts, v.faces, v.voff, v.foff, (const double*)nullptr, part + plan.vol0);
+  LAUNCH(c, "k_smooth_vol", k_smooth_vol<false>, fblocks, lanes, v.verts, v.faces, v.voff, v.foff, fin, part + plan.vol1);
+  LAUNCH(c, "k_smooth_scale", k_smooth_scale, meshes, dim3(64), v.verts, v.voff, v.foff, (const double*)(part + plan.vol0), (const double*)(part + plan.vol1), plan.fblocks,
+         flags & SH_SMOOTH_KEEP_VOLUME, part + plan.head, v.smooth_info);
+  LAUNCH(c, "k_smooth_apply", k_smooth_apply, vblocks, lanes, v.verts, v.voff, fin, (const double*)(part + plan.head), v.smooth_pos, part + plan.disp);
+  LAUNCH(c, "k_smooth_info", k_smooth_info, meshes, lanes, v.voff, nrow, pins, (const double*)(part + plan.disp), plan.vblocks, v.smooth_info);
+  return SH_OK;
+}
+
+int sh_smooth_vertices(sh_ctx* c, int filter, int weight, int iterations, int flags, double p0, double p1, const unsigned char* pin, double* out, void* info) {
+  const bool incidence = c && c->at("topo.vrow") && c->at("topo.vface") && c->at("topo.adj");
+  if (const ArthroError e = precheck_smooth(filter, weight, iterations, flags, p0, p1, pin != nullptr, incidence, c ? c->maxF : 0, arthro_facts(c)); e.code)
+    return arthro_refuse(c, "sh_smooth_vertices", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const SmoothPlan plan = smooth_plan(c->B, filter, iterations, c->maxV, c->maxF, c->sumV, c->sumF);
+  const bool rows = c->at("smooth.nrow") != nullptr;
+  int rc = ensure_bytes(c, plan.bytes);
+  if (rc == SH_OK) rc = smooth_enqueue(c, plan, rows, filter, weight, iterations, flags, p0, p1, pin);
+  if (rc != SH_OK) {
+    if (auto it = c->bufs.find("smooth.nrow"); !rows && it != c->bufs.end()) {
+      if (it->second.p) (void)hipFree(it->second.p);
+      c->bufs.erase(it);
+    }
+    return rc;
+  }
+  if (out) HIPCHK(c, hipMemcpyAsync(out, c->at("smooth.pos"), (size_t)c->sumV * 24, hipMemcpyDeviceToHost, c->stream));
+  if (info) HIPCHK(c, hipMemcpyAsync(info, c->at("smooth.info"), (size_t)c->B * SH_SMOOTH_INFO_BYTES, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

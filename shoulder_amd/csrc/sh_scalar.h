@@ -1880,6 +1880,114 @@ SH_HD void geo_far(double d, int v, double* best_d, int* best_v) {
   if (v >= 0 && (*best_v < 0 || d > *best_d || (d == *best_d && v < *best_v))) { *best_d = d; *best_v = v; }
 }
 
+// ---- smoothing of the vertices of the resident batch (include/shoulder_hip.h sh_smooth_vertices; k_smooth.h) ---------------------------
+// float64, operation by operation in the written order (-ffp-contract=off), restated by tests/smooth_oracle.py.  Nothing is
+// transcendental: + - x / sqrt and comparisons, so the bytes are the same wherever the rule runs.  The filters, the weights and the
+// flags are the header's SH_SMOOTH_* (k_smooth.h holds them equal).
+#define SH_SMO_LAPLACIAN 0
+#define SH_SMO_TAUBIN 1
+#define SH_SMO_HC 2
+#define SH_SMO_INVLEN 1          // the weight of a neighbour: 0 uniform, 1 one over the length of the edge in P0
+#define SH_SMO_PIN_BORDER 1
+#define SH_SMO_KEEP_VOLUME 2
+#define SH_SMO_TERMS 4           // doubles of a block row of a volume sum: terms 13 .. 16 of the mass sum (d, d s)
+#define SH_SMO_HEAD 8            // doubles of a mesh between the volume sums and the scaling: c[3], s, whether to scale, three unused
+#define SH_SMO_NEWTON 10
+
+// the info record of a mesh ("smooth.info"; the header states it in words)
+struct SmoothInfo { double volume_before, volume_after, scale, max_disp, sum_sq_disp; int pinned, isolated, status, pad[3]; };
+static_assert(sizeof(SmoothInfo) == 64, "SmoothInfo");
+
+// The neighbour of v behind `last` (-1: the first): the smallest u > last among the corners other than v of the faces of v's row, or
+// SH_TOPO_NONE.  Called until it says so it lists the distinct neighbours in ascending order, however often a neighbour turns up in the
+// row (twice in a manifold fan, once on a border, more often at a non-manifold edge) and however long the row is.
+SH_HD int smooth_next(const int* faces, const int* row, int n, int v, int last) {
+  int best = SH_TOPO_NONE;
+  for (int i = 0; i < n; ++i) {
+    const int* f = faces + 3 * (size_t)row[i];
+    for (int k = 0; k < 3; ++k) {
+      const int u = f[k];
+      if (u != v && u > last && u < best) best = u;
+    }
+  }
+  return best;
+}
+
+// the stored weight of the neighbour pair {v, u}: 1.0 / l with l the length of P0_hi - P0_lo in the canonical order of the two indices
+// (both directions hold the same bytes), 0.0 for a pair that is skipped (l == 0.0 or not finite)
+SH_HD double smooth_weight(const float* verts, int v, int u) {
+  const int lo = v < u ? v : u, hi = v < u ? u : v;
+  const float *a = verts + 3 * (size_t)lo, *b = verts + 3 * (size_t)hi;
+  const double D[3] = {(double)b[0] - (double)a[0], (double)b[1] - (double)a[1], (double)b[2] - (double)a[2]};
+  const double l = sqrt(dot3(D, D));
+  return (l == 0.0 || !vert_finite(l)) ? 0.0 : 1.0 / l;
+}
+
+// the test behind SH_VERT_BORDER | SH_VERT_NONMANIFOLD (vert_gather): one of the two slots that touch v in a face of its row
+SH_HD bool smooth_border(const int* faces, const int* adj, const int* row, int n, int v) {
+  bool hit = false;
+  for (int i = 0; i < n; ++i) {
+    const int f = row[i];
+    const int k = vert_corner(faces + 3 * (size_t)f, v), k2 = k == 0 ? 2 : k - 1;
+    const int a0 = adj[3 * (size_t)f + k], a1 = adj[3 * (size_t)f + k2];
+    hit = hit || a0 == SH_TOPO_BORDER || a1 == SH_TOPO_BORDER || a0 == SH_TOPO_NONMANIFOLD || a1 == SH_TOPO_NONMANIFOLD;
+  }
+  return hit;
+}
+
+// M(x)[v] from v's row of n neighbours (`w` beside it) on the mesh's plane x of three doubles per vertex: the sums in the row's order
+SH_HD void smooth_mean(const int* nbr, const double* w, int n, int weight, bool pinned, const double* x, int v, double* m) {
+  double S[3] = {0.0, 0.0, 0.0}, W = 0.0;
+  int added = 0;
+  if (!pinned)
+    for (int i = 0; i < n; ++i) {
+      const double wi = weight == SH_SMO_INVLEN ? w[i] : 1.0;
+      if (wi == 0.0) continue;
+      const double* xu = x + 3 * (size_t)nbr[i];
+      S[0] += wi * xu[0]; S[1] += wi * xu[1]; S[2] += wi * xu[2];
+      W += wi;
+      ++added;
+    }
+  const bool keep = pinned || added == 0 || !vert_finite(W);
+  for (int c = 0; c < 3; ++c) m[c] = keep ? x[3 * (size_t)v + c] : S[c] / W;
+}
+
+SH_HD double smooth_step(double p, double m, double c) { return p + c * (m - p); }
+// b of the HC filter at a vertex that is not pinned (a pinned one has 0.0: alpha x + (1 - alpha) x need not give x back), and P
+SH_HD double smooth_hc_b(double p, double p0, double q, double alpha) { return p - (alpha * p0 + (1.0 - alpha) * q); }
+SH_HD double smooth_hc_p(double p, double b, double mb, double beta) { return p - (beta * b + (1.0 - beta) * mb); }
+
+// s with s^3 = r: SH_SMO_NEWTON Newton steps from 1.0
+SH_HD double smooth_cbrt(double r) {
+  double s = 1.0;
+  for (int i = 0; i < SH_SMO_NEWTON; ++i) s = s - ((s * s) * s - r) / (3.0 * (s * s));
+  return s;
+}
+
+// The volumes and the scaling of a mesh from its two rows of sums (terms 13 .. 16 of P0 and of P about the pivot o): head = c[3], s,
+// 1.0 when the vertices are to be scaled.  -> the status.
+SH_HD int smooth_scale(const double* T0, const double* T1, const double* o, bool keep_volume, double* volume_before, double* volume_after, double* head /* SH_SMO_HEAD */) {
+  const double V0 = T0[0] / 6.0, V1 = T1[0] / 6.0;
+  *volume_before = V0; *volume_after = V1;
+  for (int i = 0; i < SH_SMO_HEAD; ++i) head[i] = 0.0;
+  head[3] = 1.0;
+  if (!keep_volume) return 0;
+  if (V0 == 0.0 || V1 == 0.0 || !vert_finite(V0) || !vert_finite(V1)) return SH_ERR_GEOMETRY_DEV;
+  const double r = V0 / V1;
+  if (!(r >= 0.125 && r <= 8.0)) return SH_ERR_GEOMETRY_DEV;
+  double c[3];
+  for (int k = 0; k < 3; ++k) c[k] = T1[1 + k] / (4.0 * T1[0]) + o[k];
+  if (!vert_finite(c[0]) || !vert_finite(c[1]) || !vert_finite(c[2])) return SH_ERR_GEOMETRY_DEV;
+  head[0] = c[0]; head[1] = c[1]; head[2] = c[2]; head[3] = smooth_cbrt(r); head[4] = 1.0;
+  return 0;
+}
+SH_HD double smooth_scaled(double p, double c, double s) { return c + s * (p - c); }
+// what a vertex gives to the largest displacement: its |P - P0|, 0.0 when that is no number
+SH_HD double smooth_disp(double d2) {
+  const double d = sqrt(d2);
+  return d > 0.0 ? d : 0.0;
+}
+
 // ---- the face hierarchy of the resident batch (include/shoulder_hip.h sh_mesh_bvh; k_bvh.h) -------------------------------------------
 // float32 minima and maxima, one float64 quantisation and integer work, restated by tests/bvh_oracle.py: the device, the host twin
 // (tests/hostcheck/bvh_check.cpp) and the oracle give the same bytes.  LEAF and WIDTH are powers of two in 4..16, fixed after measuring

@@ -987,6 +987,61 @@ class Engine:
             unit = np.where(a2[:, None] != 0.0, rec[:, :3] / a2[:, None], 0.0)
         return unit, a2 / 2.0, rec[:, 4:7].copy()
 
+    # ---- smoothing of the vertices of the resident batch (include/shoulder_hip.h sh_smooth_vertices) ------------------------------
+    _SMOOTH_FILTERS = {"laplacian": _lib.SMOOTH_LAPLACIAN, "taubin": _lib.SMOOTH_TAUBIN, "hc": _lib.SMOOTH_HC, "humphrey": _lib.SMOOTH_HC}
+    _SMOOTH_WEIGHTS = {"uniform": _lib.SMOOTH_UNIFORM, "invlen": _lib.SMOOTH_INVLEN}
+
+    def smooth_vertices(self, filter="taubin", iterations=10, lamb=0.5, mu=-0.53, alpha=0.1, beta=0.5, weight="uniform", pin=None, pin_border=False,
+                        keep_volume=False):
+        """The vertices of every resident mesh smoothed over their one-rings, on the device (the incidence of topology() is made first
+        when it is not resident for this batch): trimesh.smoothing's filter_laplacian ("laplacian": `iterations` steps of lamb towards
+        the neighbours' mean), filter_taubin ("taubin": a step of lamb, then one of mu <= 0, which keeps the volume nearly) and
+        filter_humphrey ("hc": alpha pulls back to the start, beta spreads the correction).  weight "uniform" or "invlen" (one over the
+        edge's length in the start); pin: an optional (sumV,) mask of vertices that stay; pin_border: the vertices on an open or
+        non-manifold edge stay; keep_volume: one scaling about the centre of mass at the end restores each mesh's volume (not together
+        with a pin).  -> dict: vertices (sumV, 3) float64, info (B,) of _lib.SMOOTH_INFO_DTYPE (volume_before, volume_after, scale,
+        max_disp, sum_sq_disp, pinned, isolated, status: SH_ERR_GEOMETRY for a mesh whose volume could not be restored, which is
+        then not scaled) and voff (B + 1,).  The same bytes wherever the rule runs.  "verts" is not written: upload the result, or
+        store("verts", vertices.astype(np.float32)) for the resident faces.  Resident afterwards: "smooth.pos", "smooth.nrow",
+        "smooth.nbr" (vertex_neighbors), "smooth.w", "smooth.info"."""
+        f = self._SMOOTH_FILTERS.get(filter, filter)
+        w = self._SMOOTH_WEIGHTS.get(weight, weight)
+        if not isinstance(f, (int, np.integer)):
+            raise ValueError("filter must be 'laplacian', 'taubin' or 'hc'")
+        if not isinstance(w, (int, np.integer)):
+            raise ValueError("weight must be 'uniform' or 'invlen'")
+        if self.B >= 1 and not self._has_buffer("topo.vrow"):
+            self.topology()
+        V = int(self.voff[-1]) if self.B >= 1 else 0
+        mask = None
+        if pin is not None:
+            mask = np.ascontiguousarray(np.asarray(pin).reshape(-1) != 0, dtype=np.uint8)
+            if len(mask) != V:
+                raise ValueError("pin must have one entry per vertex of the batch")
+        p0, p1 = (alpha, beta) if f == _lib.SMOOTH_HC else (lamb, mu)
+        flags = (_lib.SMOOTH_PIN_BORDER if pin_border else 0) | (_lib.SMOOTH_KEEP_VOLUME if keep_volume else 0)
+        vertices, info = np.zeros((V, 3)), np.zeros(max(self.B, 0), dtype=_lib.SMOOTH_INFO_DTYPE)
+        self._chk(self.L.sh_smooth_vertices(self.h, int(f), int(w), int(iterations), flags, float(p0), float(p1), None if mask is None else _ptr(mask), _ptr(vertices),
+                                            _ptr(info)))
+        return dict(vertices=vertices, info=info, voff=np.array(self.voff, dtype=np.int64))
+
+    def vertex_neighbors(self, b=None):
+        """trimesh's `vertex_neighbors` of resident mesh b from the resident rows (made by a smooth_vertices call without an iteration
+        when they are missing) -> (nrow (V + 1,), nbr): the neighbours of vertex v are nbr[nrow[v]:nrow[v + 1]], distinct and ascending.
+        b=None: a list of these pairs for all meshes, from ONE copy of the two buffers (each call copies the whole batch's rows)."""
+        if b is not None and not 0 <= int(b) < self.B:
+            raise ValueError("mesh index out of range")
+        if not self._has_buffer("smooth.nrow"):
+            self.smooth_vertices(iterations=0)
+        rows = self.fetch("smooth.nrow", np.int32, (int(self.voff[-1]) + self.B,))
+        places = self.fetch("smooth.nbr", np.int32, (6 * max(int(self.foff[-1]), 1),))
+
+        def one(k):
+            v0, v1, f0 = int(self.voff[k]), int(self.voff[k + 1]), int(self.foff[k])
+            nrow = rows[v0 + k:v1 + k + 1].copy()
+            return nrow, places[6 * f0:6 * f0 + int(nrow[-1])].copy()
+        return [one(k) for k in range(self.B)] if b is None else one(int(b))
+
     # ---- geodesic distances and shortest paths on the resident batch (include/shoulder_hip.h sh_geodesic) ------------------------
     _GEO_MODES = {"edges": _lib.GEO_EDGES, "unfold": _lib.GEO_UNFOLD}
 
