@@ -1141,6 +1141,105 @@ int sh_smooth_vertices(sh_ctx*, int filter, int weight, int iterations, int flag
                        const unsigned char* pin /* sumV, host, nullable */, double* out /* sumV x 3, host, nullable */,
                        void* info /* B x SH_SMOOTH_INFO_BYTES, host, nullable */);
 
+/* ---- repair of the resident batch: one winding, outward shells, filled holes ----------------------------------------------------------
+ * sh_mesh_topology counts what is wrong with a mesh; this puts it right (k_repair.h), as trimesh.repair's fix_winding, fix_inversion and
+ * fill_holes do, for holes of any length.  "verts" and "faces" are NOT written: the repaired meshes come back in "repair.faces" and
+ * "repair.verts", ready for an upload.  Every rule is per mesh with indices local to the mesh; "degenerate", "slot", "shell" and
+ * same(f, g) ("both faces traverse the edge in the same direction") mean what they mean in sh_mesh_topology; a result depends on the
+ * mesh and the options alone: not on B, the mesh's place in the batch or a schedule.  dot3(a, b) = (a0 b0 + a1 b1) + a2 b2, float64,
+ * no contraction.
+ *   winding      (orient >= SH_REPAIR_WINDING) per shell with first face r: parity(r) = 0 and, across every slot >= 0, parity(g) =
+ *                parity(f) XOR same(f, g).  The parities are unique exactly when the shell is orientable, so any schedule gives them: one
+ *                workgroup per mesh walks the face graph breadth first from all first faces at once, the state in LDS.  A shell in which
+ *                a manifold slot contradicts the parities is SH_REPAIR_NONORIENTABLE: no face of it is flipped, none of its holes is
+ *                filled and no parity of it is reported.  A face of parity 1 is flipped: (a, b, c) becomes (a, c, b), which exchanges its
+ *                slots 0 and 2.  Degenerate faces are copied and never flipped.  A mesh with more than SH_REPAIR_LDS_FACES faces, or whose
+ *                walk is deeper than max_rounds levels, gets status SH_ERR_CAPACITY and an unchanged copy, as does a mesh whose
+ *                topology did not finish -- never the batch.
+ *   outward      (orient >= SH_REPAIR_OUTWARD) per orientable shell among the shells_written of the topology: V6 = the sum of
+ *                det[A - o, B - o, C - o] = dot3(a, cross3(b, c)) over its parity-corrected faces, the float32 corners widened, o the
+ *                centre of the shell's box in "topo.shells", lo + (hi - lo) * 0.5 per coordinate in float64.  The order: the shell's
+ *                faces ascending, in blocks of 2 048 consecutive entries of that list; one after the other inside a block from 0.0, then
+ *                the block sums one after the other from 0.0.  V6 < 0: the shell is inverted and all its faces are flipped once more;
+ *                V6 == 0: nothing.  Shells behind shells_written get their winding alone, and bit 1 of the mesh's flags says so.
+ *   nested       (orient == SH_REPAIR_NESTED) every written shell is made outward as above; then for shell k, with p_k the first
+ *                corner of its first face, W_k = (the sum of solid_angle_tri(p_k, .) over the outward faces of all OTHER written shells
+ *                that are orientable and closed: no border slot, no non-manifold slot) / (4 pi), summed in the block order of
+ *                sh_winding_numbers over the mesh's face indices, the excluded faces skipped.  depth = rint(W_k); a shell of odd depth
+ *                is flipped inward; |W_k - depth| > 0.25: shell status SH_REPAIR_AMBIGUOUS and depth 0.  A mesh with more shells than
+ *                shells_written gets SH_ERR_CAPACITY and is treated as SH_REPAIR_OUTWARD.
+ *   holes        traced on the ORIENTED faces, after all flips.  A border half-edge is a (face f, slot e) whose adjacency is
+ *                SH_ADJ_BORDER; it runs from f[e] to f[(e + 1) % 3] and has the id 3 f + e.  Its successor: rotate about the head w;
+ *                slot (e + 1) % 3 of f starts at w; a border there is the successor; a face g there is entered through its slot that
+ *                runs the other way and the rotation goes on from that slot; SH_ADJ_NONMANIFOLD there, or a g that runs the same way
+ *                (only in a shell that is not orientable), blocks the chain.  The successor is injective, so the border half-edges fall
+ *                into cycles and blocked chains.  The half-edges of blocked chains are only counted (blocked_edges).  Where two holes
+ *                touch in a vertex the rotation leads from one into the other, so a cycle that passes a vertex more than once is CUT
+ *                there: each of its half-edges with that head takes the successor of the one with the same head before it along
+ *                the cycle (cyclically), which closes every stretch between two passes into a cycle of its own; half-edges of
+ *                different cycles (two sheets that touch in a vertex) are left alone.  The cut is made once.  A cycle is then a
+ *                hole: its start is its smallest id, its length L its edges; the holes of a mesh are ordered by start.  All of it is
+ *                found by pointer doubling over the compacted border half-edges, in a number of rounds fixed by their count.
+ *   fill         a hole is filled when its shell is orientable and 3 <= L <= max_hole_edges; else its status says why.  With the
+ *                tails u_0 (the start's), u_1, ... in successor order: SH_REPAIR_FAN adds the faces (u_0, u_{j+1}, u_j), j = 1 .. L - 2,
+ *                and no vertex; SH_REPAIR_CENTROID one vertex c and the faces (u_{j+1}, u_j, c), j = 0 .. L - 1, indices mod L, c per
+ *                coordinate the float64 sum of the float32 positions from u_0 in loop order, over (double) L, rounded once to float32;
+ *                SH_REPAIR_FILL_NONE reports the holes only.  New faces follow the mesh's own in hole order and in j order within a
+ *                hole; new vertices follow the mesh's in hole order.
+ *   records      sh_repair_info per mesh ("repair.info"): status; shells_nonorientable; shells_inverted; faces_flipped (final); holes
+ *                (exact whatever max_holes); holes_written; holes_filled; largest_hole (edges); blocked_edges; faces_added; verts_added;
+ *                faces_out; verts_out; flags (bit 0: anything changed, bit 1: shells behind shells_written were not made outward);
+ *                shell_records = the records per mesh of "repair.shells" (the max_shells of the topology); reserved.
+ *                sh_repair_shell per written shell ("repair.shells"): status 0, SH_REPAIR_NONORIENTABLE or SH_REPAIR_AMBIGUOUS;
+ *                parity_flips; inverted; depth (-1 when not asked); holes; holes_filled; V6; W.
+ *                sh_repair_hole for the first max_holes holes per mesh ("repair.holes"): shell; start_face; start_slot (of the oriented
+ *                face); edges; status SH_REPAIR_HOLE_*; first_face in the output, or -1; faces_added; vertex, or -1.
+ *   buffers      "repair.flip", uint8 per face at foff[b]: the final flip.  "repair.off", int64, 3 (B + 1): the starts of the meshes in
+ *                "repair.faces" (in faces), in "repair.verts" (in vertices) and in the border scratch; the host sizes them before the
+ *                first launch from "topo.info": F_b + border_edges faces and V_b + border_edges / 3 vertices per mesh, of which
+ *                faces_out and verts_out are used.
+ * Arguments in this order: the context and options (SH_ERR_ARG); orient in 0..3, fill in 0..2, max_hole_edges >= 3, max_holes in
+ * 1..SH_REPAIR_MAX_HOLES, max_rounds in 1..SH_REPAIR_MAX_ROUNDS, reserved == 0 (SH_ERR_ARG); a resident batch and no runs in flight
+ * (SH_ERR_STATE); the topology of THIS batch resident (SH_ERR_STATE: call sh_mesh_topology first).  SH_ERR_NOMEM when the buffers do not
+ * fit.  The host reads "topo.info" once, enqueues a fixed list of launches and looks at nothing in between.  Every output pointer may
+ * be NULL.  Reads "verts", "faces", the offsets, "topo.adj", "topo.label", "topo.vrow", "topo.vface", "topo.info", "topo.shells".  Resident afterwards: "repair.flip",
+ * "repair.faces", "repair.verts", "repair.info", "repair.shells", "repair.holes", "repair.off" and the scratch "repair.par", "repair.work",
+ * "repair.edge", "repair.term"; they are removed together with "topo.*" by the next upload / commit / sh_store("verts").  Every other
+ * buffer keeps its bytes. */
+#define SH_REPAIR_NONE            0
+#define SH_REPAIR_WINDING         1
+#define SH_REPAIR_OUTWARD         2
+#define SH_REPAIR_NESTED          3
+#define SH_REPAIR_FILL_NONE       0
+#define SH_REPAIR_FAN             1
+#define SH_REPAIR_CENTROID        2
+#define SH_REPAIR_NONORIENTABLE   1
+#define SH_REPAIR_AMBIGUOUS       2
+#define SH_REPAIR_HOLE_FILLED     0
+#define SH_REPAIR_HOLE_TOO_LONG   1
+#define SH_REPAIR_HOLE_SHELL      2
+#define SH_REPAIR_HOLE_OPEN       3
+#define SH_REPAIR_HOLE_TOO_SHORT  4
+#define SH_REPAIR_MAX_HOLES       65536
+#define SH_REPAIR_MAX_ROUNDS      1048576
+#define SH_REPAIR_LDS_FACES       131072
+#define SH_REPAIR_CHANGED         1
+#define SH_REPAIR_SHELLS_LEFT     2
+struct sh_repair_options { int32_t orient, fill, max_hole_edges, max_holes, max_rounds, reserved; };            /* 24 B */
+typedef struct sh_repair_options sh_repair_options;
+struct sh_repair_info {
+  int32_t status, shells_nonorientable, shells_inverted, faces_flipped, holes, holes_written, holes_filled, largest_hole;
+  int32_t blocked_edges, faces_added, verts_added, faces_out, verts_out, flags, shell_records, reserved;
+};                                                                                                             /* 64 B */
+typedef struct sh_repair_info sh_repair_info;
+struct sh_repair_shell { int32_t status, parity_flips, inverted, depth, holes, holes_filled; double V6, W; };   /* 40 B */
+typedef struct sh_repair_shell sh_repair_shell;
+struct sh_repair_hole { int32_t shell, start_face, start_slot, edges, status, first_face, faces_added, vertex; }; /* 32 B */
+typedef struct sh_repair_hole sh_repair_hole;
+int sh_mesh_repair(sh_ctx*, const sh_repair_options* options, sh_repair_info* info /* B, host, nullable */,
+                   sh_repair_shell* shells /* B x shell_records, host, nullable */, sh_repair_hole* holes /* B x max_holes, host, nullable */,
+                   unsigned char* flip /* sumF, host, nullable */);
+
 /* ---- a face hierarchy of the resident batch, and the closest-point step through it -------------------------------------------------
  * sh_mesh_bvh builds, per resident mesh, a bounding-box hierarchy over its faces (k_bvh.h; the rules are sh_scalar.h bvh_*, all float32
  * min / max, one float64 quantisation and integer work, restated by tests/bvh_oracle.py):

@@ -39,6 +39,10 @@ GEO_EDGES, GEO_UNFOLD, GEO_MAX_SETS, GEO_LDS_VERTICES, GEO_CHUNK, GEO_INFO_BYTES
 GEO_ROOT, GEO_NO_PRED, GEO_UNREACHED = -1, -2, -3
 SMOOTH_LAPLACIAN, SMOOTH_TAUBIN, SMOOTH_HC, SMOOTH_UNIFORM, SMOOTH_INVLEN = 0, 1, 2, 0, 1
 SMOOTH_PIN_BORDER, SMOOTH_KEEP_VOLUME, SMOOTH_MAX_ITER, SMOOTH_INFO_BYTES = 1, 2, 256, 64
+REPAIR_NONE, REPAIR_WINDING, REPAIR_OUTWARD, REPAIR_NESTED, REPAIR_FILL_NONE, REPAIR_FAN, REPAIR_CENTROID = 0, 1, 2, 3, 0, 1, 2
+REPAIR_NONORIENTABLE, REPAIR_AMBIGUOUS, REPAIR_CHANGED, REPAIR_SHELLS_LEFT = 1, 2, 1, 2
+REPAIR_HOLE_FILLED, REPAIR_HOLE_TOO_LONG, REPAIR_HOLE_SHELL, REPAIR_HOLE_OPEN, REPAIR_HOLE_TOO_SHORT = 0, 1, 2, 3, 4
+REPAIR_MAX_HOLES, REPAIR_MAX_ROUNDS, REPAIR_LDS_FACES = 65536, 1048576, 131072
 ACCEL_OFF, ACCEL_BVH, BVH_INFO_BYTES = 0, 1, 48
 
 # ---- the records ------------------------------------------------------------------------------------------------------------------------
@@ -224,6 +228,15 @@ assert GEO_INFO_DTYPE.itemsize == GEO_INFO_BYTES
 SMOOTH_INFO_DTYPE = np.dtype([(n, "<f8") for n in ("volume_before", "volume_after", "scale", "max_disp", "sum_sq_disp")]
                              + [("pinned", "<i4"), ("isolated", "<i4"), ("status", "<i4"), ("pad", "<i4", (3,))])
 assert SMOOTH_INFO_DTYPE.itemsize == SMOOTH_INFO_BYTES
+# the records of sh_mesh_repair: the header declares each struct and its typedef in two statements, as sh_bvh_info; stated here once.
+# tests/hostcheck/repair_check.cpp holds the sizes and offsets against a C compile of the header (rc_sizes)
+REPAIR_OPTIONS_DTYPE = np.dtype([(n, "<i4") for n in ("orient", "fill", "max_hole_edges", "max_holes", "max_rounds", "reserved")])
+REPAIR_INFO_DTYPE = np.dtype([(n, "<i4") for n in ("status", "shells_nonorientable", "shells_inverted", "faces_flipped", "holes", "holes_written", "holes_filled",
+                                                   "largest_hole", "blocked_edges", "faces_added", "verts_added", "faces_out", "verts_out", "flags", "shell_records",
+                                                   "reserved")])
+REPAIR_SHELL_DTYPE = np.dtype([(n, "<i4") for n in ("status", "parity_flips", "inverted", "depth", "holes", "holes_filled")] + [("V6", "<f8"), ("W", "<f8")])
+REPAIR_HOLE_DTYPE = np.dtype([(n, "<i4") for n in ("shell", "start_face", "start_slot", "edges", "status", "first_face", "faces_added", "vertex")])
+assert (REPAIR_OPTIONS_DTYPE.itemsize, REPAIR_INFO_DTYPE.itemsize, REPAIR_SHELL_DTYPE.itemsize, REPAIR_HOLE_DTYPE.itemsize) == (24, 64, 40, 32)
 # sh_bvh_info per mesh (sh_mesh_bvh): the header declares the struct and its typedef in two statements; stated here once, beside its bytes
 BVH_INFO_DTYPE = np.dtype([(n, "<i4") for n in ("tight", "loose", "leaves", "levels", "nodes", "reserved")] + [("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
 assert BVH_INFO_DTYPE.itemsize == BVH_INFO_BYTES
@@ -316,6 +329,7 @@ SIGNATURES = {      # name -> (argtypes, restype, optional)
     "sh_vertex_fields": _f(_vp, _i, _i, _vp, _vp, _vp, _vp, optional=True),
     "sh_geodesic": _f(_vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, optional=True),
     "sh_smooth_vertices": _f(_vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, optional=True),
+    "sh_mesh_repair": _f(_vp, _vp, _vp, _vp, _vp, _vp, optional=True),
     "sh_mesh_bvh": _f(_vp, _vp, optional=True),
     "sh_set_query_accel": _f(_vp, _i, optional=True),
     "sh_get_query_accel": _f(_vp, optional=True),

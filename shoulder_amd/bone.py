@@ -668,6 +668,21 @@ class ProximalHumerus(Bone):
             raise ValueError(f"smoothed_mesh failed with status {int(r['info'][0]['status'])}: the volume could not be restored")
         return self._engine.transform_points(np.ascontiguousarray(r["vertices"]), T), np.array(self._faces, dtype=np.int32)
 
+    # -- repair ---------------------------------------------------------------------------------------------------------
+    def repaired_mesh(self, **options):
+        """This bone with one winding, outward shells and filled holes (Engine.repair, whose options these are: orient, fill,
+        max_hole_edges, max_shells, max_holes, max_rounds) -> (verts (V', 3) float64, faces (F', 3) int32) in the CURRENT coordinate
+        system, ready for Engine.upload as smoothed_mesh's result is: what trimesh.repair's fix_winding, fix_inversion and fill_holes
+        leave in the mesh, before a volume, a winding number or a thickness is asked of it.  The resident mesh is not changed.
+        Raises ValueError when the mesh could not be repaired (a status in its info record)."""
+        self._ensure_loaded()
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        r = self._engine.repair(**options)
+        if r["info"][0]["status"] != 0:
+            raise ValueError(f"repaired_mesh failed with status {int(r['info'][0]['status'])}: the mesh was not repaired")
+        verts, faces = r["meshes"][0]
+        return self._engine.transform_points(np.ascontiguousarray(verts, dtype=np.float64), T), faces
+
     # -- distances along the surface -------------------------------------------------------------------------------
     def _geodesic_seeds(self, where):
         """a vertex index, or a 3-D point in the CURRENT coordinate system -> (vertices, d0): the vertex itself with 0.0, or the point

@@ -171,6 +171,7 @@ struct sh_ctx {
   // what -- the records of the last submitted run, the last resection with its seats, the last profile, the stems -- is this one
   // member's (sh_arthro.h ArthroState: named events and queries; batch_gen above stays the context's and is handed to the queries)
   sh::ArthroState arthro;
+  int topo_shell_records = 0;                // the max_shells of the last sh_mesh_topology: the records per mesh of "topo.shells" (sh_mesh_repair reads them)
   int query_accel = SH_ACCEL_OFF;            // sh_set_query_accel: the closest-point step walks all faces (k_cp_walk) or descends "bvh.*" (k_cp_tree); same bytes
   hipStream_t copy_stream = nullptr;
   hipEvent_t stl_counted_ev = nullptr;      // sh_stage_stl: the device has counted the merged vertices / faces

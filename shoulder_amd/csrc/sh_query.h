@@ -1,8 +1,8 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields), the geodesics (sh_geodesic), the smoothing of the vertices (sh_smooth_vertices) and the face hierarchy (sh_mesh_bvh, sh_set_query_accel).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields), the geodesics (sh_geodesic), the smoothing of the vertices (sh_smooth_vertices), the repair (sh_mesh_repair) and the face hierarchy (sh_mesh_bvh, sh_set_query_accel).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo,bvh,smooth}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo,bvh,smooth,repair}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
@@ -68,6 +68,14 @@ struct RayKey; struct CpPart; struct GeoInfo;
   X(smooth_nbr, "smooth.nbr", int, 4) X(smooth_w, "smooth.w", double, 8) X(smooth_pos, "smooth.pos", double, 8)                    \
   X(smooth_info, "smooth.info", SmoothInfo, 8) X(smooth_plane, "smooth.plane", double, 8) X(smooth_pin, "smooth.pin", int, 4)      \
   X(smooth_mask, "smooth.mask", unsigned char, 1) X(smooth_part, "smooth.part", double, 8) X(smooth_nrow, "smooth.nrow", int, 4)
+// the final flips, the repaired meshes (regions sized from "topo.info"), the records and the regions' starts; scratch: the outward
+// orientation, the int32 work of the walk and the lists (first, bad, two queues, lists: 5 sumF, and AR_REPAIR_HEAD per mesh), the
+// AR_REPAIR_EDGE_ARRAYS arrays of the border half-edges, the terms and block sums of V6
+#define REPAIR_BUFS(X)                                                                                                             \
+  X(repair_flip, "repair.flip", unsigned char, 1) X(repair_faces, "repair.faces", int, 4) X(repair_verts, "repair.verts", float, 4) \
+  X(repair_info, "repair.info", sh_repair_info, 4) X(repair_shells, "repair.shells", sh_repair_shell, 8)                           \
+  X(repair_holes, "repair.holes", sh_repair_hole, 4) X(repair_off, "repair.off", long long, 8) X(repair_par, "repair.par", unsigned char, 1) \
+  X(repair_work, "repair.work", int, 4) X(repair_edge, "repair.edge", int, 4) X(repair_term, "repair.term", double, 8)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -85,6 +93,8 @@ using GeoView = BufJoin<MeshBufs, TopoBufs, GeoBufs>;
 SH_QUERY_LIST(Bvh, BVH_BUFS)
 SH_BUF_LIST(Smooth, SMOOTH_BUFS)
 using SmoothView = BufJoin<MeshBufs, TopoBufs, SmoothBufs>;
+SH_BUF_LIST(Repair, REPAIR_BUFS)
+using RepairView = BufJoin<MeshBufs, TopoBufs, RepairBufs>;
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -100,6 +110,7 @@ constexpr int AR_VERT_BLOCK = 256, AR_VERT_FACE = 10;                           
 constexpr int AR_GEO_BLOCK = 256, AR_GEO_FACE = 6, AR_GEO_STATE = 8;              // SH_GEO_BLOCK, SH_GEOD_FACE, SH_GEO_STATE
 constexpr int AR_BVH_BLOCK = 256, AR_BVH_HEAD = 8, AR_BVH_CHUNK = 64;             // SH_BVH_BLOCK, SH_BVH_HEAD, SH_BVH_CHUNK
 constexpr int AR_SMOOTH_BLOCK = 256;                                              // SH_SMOOTH_BLOCK
+constexpr int AR_REPAIR_BLOCK = 256, AR_REPAIR_HEAD = 16, AR_REPAIR_EDGE_ARRAYS = 18;      // SH_REPAIR_BLOCK, SH_REPAIR_HEAD, SH_REPAIR_EDGE_ARRAYS
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -315,6 +326,33 @@ inline SmoothPlan smooth_plan(int B, int filter, int iterations, long long maxV,
   return p;
 }
 
+// The repair.  The regions of the repaired meshes follow from "topo.info", which the host reads before the first launch: mesh b has room
+// for F_b + border_edges faces and V_b + border_edges / 3 vertices (a hole of L edges adds at most L faces and one vertex, and has at
+// least three edges) and border_edges places in each array of "repair.edge".  off: the 3 (B + 1) starts of "repair.off".
+struct RepairPlan { int blocks; std::vector<long long> off; RepairBytes bytes; };      // blocks: of 256 faces or vertices of the largest mesh
+inline RepairPlan repair_plan(int B, int shell_records, int max_holes, long long maxV, long long maxF, long long sumF, const long long* voff, const long long* foff,
+                              const sh_topology* info) {
+  RepairPlan p;
+  p.blocks = (int)tiles_of(maxF > maxV ? maxF : maxV, AR_REPAIR_BLOCK);
+  p.off.assign(3 * ((size_t)B + 1), 0);
+  long long *rf = p.off.data(), *rv = rf + B + 1, *re = rv + B + 1;
+  for (int b = 0; b < B; ++b) {
+    const long long e = info[b].border_edges > 0 ? info[b].border_edges : 0;
+    rf[b + 1] = rf[b] + (foff[b + 1] - foff[b]) + e;
+    rv[b + 1] = rv[b] + (voff[b + 1] - voff[b]) + e / 3;
+    re[b + 1] = re[b] + e;
+  }
+  const size_t f = (size_t)(sumF > 0 ? sumF : 1);
+  RepairBytes& z = p.bytes;
+  z.repair_flip = (f + 3) / 4 * 4; z.repair_par = z.repair_flip;
+  z.repair_faces = (size_t)(rf[B] > 0 ? rf[B] : 1) * 12; z.repair_verts = (size_t)(rv[B] > 0 ? rv[B] : 1) * 12;
+  z.repair_info = (size_t)B * sizeof(sh_repair_info); z.repair_shells = (size_t)B * shell_records * sizeof(sh_repair_shell);
+  z.repair_holes = (size_t)B * max_holes * sizeof(sh_repair_hole); z.repair_off = p.off.size() * 8;
+  z.repair_work = (5 * f + (size_t)B * AR_REPAIR_HEAD) * 4; z.repair_edge = (size_t)AR_REPAIR_EDGE_ARRAYS * (size_t)(re[B] > 0 ? re[B] : 1) * 4;
+  z.repair_term = 2 * f * 8;
+  return p;
+}
+
 // The face hierarchy (sh_scalar.h bvh_*).  "bvh.order", "bvh.loose", "bvh.key" and "bvh.sorted" follow the faces (mesh b at foff[b]) and
 // "bvh.tri" nine float32 per face; "bvh.box" has six float32 per node, mesh b from base[b] = the sum of bvh_nodes_of(F_a) over the meshes
 // before it -- room for a mesh without a loose face, known before the device has counted them; "bvh.off" SH_BVH_OFF_WORDS int32 and
@@ -496,6 +534,17 @@ inline ArthroError precheck_smooth(int filter, int weight, int iterations, int f
   if (const ArthroError e = resident(f); e.code) return e;
   if (!incidence) return {SH_ERR_STATE, "no incidence of the resident batch: call sh_mesh_topology first"};
   if (6 * maxF > 0x7fffffffLL) return {SH_ERR_NOMEM, "a mesh has more than 2^31 - 1 places for neighbours"};
+  return arthro_ok();
+}
+
+// topology: "topo.adj", "topo.label", "topo.info" and "topo.shells" of the resident batch are there (a new batch removes them)
+inline ArthroError precheck_repair(const sh_repair_options* opt, bool topology, const ArthroFacts& f) {
+  if (!f.ctx || !opt) return {SH_ERR_ARG, "bad argument (context and options must be given)"};
+  if (opt->orient < SH_REPAIR_NONE || opt->orient > SH_REPAIR_NESTED || opt->fill < SH_REPAIR_FILL_NONE || opt->fill > SH_REPAIR_CENTROID || opt->max_hole_edges < 3 ||
+      opt->max_holes < 1 || opt->max_holes > SH_REPAIR_MAX_HOLES || opt->max_rounds < 1 || opt->max_rounds > SH_REPAIR_MAX_ROUNDS || opt->reserved != 0)
+    return {SH_ERR_ARG, "bad options (orient in 0..3, fill in 0..2, max_hole_edges >= 3, max_holes in 1..65536, max_rounds in 1..1048576, reserved 0)"};
+  if (const ArthroError e = resident(f); e.code) return e;
+  if (!topology) return {SH_ERR_STATE, "no topology of the resident batch: call sh_mesh_topology first"};
   return arthro_ok();
 }
 

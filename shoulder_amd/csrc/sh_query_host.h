@@ -1,7 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
 // point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), the surface samples, sh_sample_surface
-// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), the geodesics, sh_geodesic (k_geo.h), the smoothing of the vertices, sh_smooth_vertices (k_smooth.h), and the face hierarchy, sh_mesh_bvh / sh_set_query_accel (k_bvh.h).
+// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), the geodesics, sh_geodesic (k_geo.h), the smoothing of the vertices, sh_smooth_vertices (k_smooth.h), the repair, sh_mesh_repair (k_repair.h), and the face hierarchy, sh_mesh_bvh / sh_set_query_accel (k_bvh.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -399,6 +399,7 @@ int sh_mesh_topology(sh_ctx* c, const sh_topology_options* opt, sh_topology* inf
   const int B = c->B, max_shells = opt->max_shells;
   const TopoPlan plan = topo_plan(B, max_shells, c->maxF, c->sumV, c->sumF);
   if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  c->topo_shell_records = max_shells;
   const TopoView v = view_of<TopoView>(c);
   HIPCHK(c, hipMemsetAsync(v.topo_state, 0, plan.bytes.topo_state, c->stream));
   HIPCHK(c, hipMemsetAsync(v.topo_cursor, 0, plan.bytes.topo_cursor, c->stream));
@@ -520,6 +521,53 @@ int sh_smooth_vertices(sh_ctx* c, int filter, int weight, int iterations, int fl
   }
   if (out) HIPCHK(c, hipMemcpyAsync(out, c->at("smooth.pos"), (size_t)c->sumV * 24, hipMemcpyDeviceToHost, c->stream));
   if (info) HIPCHK(c, hipMemcpyAsync(info, c->at("smooth.info"), (size_t)c->B * SH_SMOOTH_INFO_BYTES, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- repair: one winding, outward shells, filled holes (k_repair.h) ----
+// "topo.info" to the host (the one look, before the first launch: it sizes the regions) -> the starts to the device, first = above every
+// face, bad = 0, zeroed shell and hole records -> seed -> parity -> shell -> [nest] -> emit -> holes; the host looks at nothing in between
+static_assert(AR_REPAIR_BLOCK == SH_REPAIR_BLOCK && AR_REPAIR_HEAD == SH_REPAIR_HEAD && AR_REPAIR_EDGE_ARRAYS == SH_REPAIR_EDGE_ARRAYS, "sh_query.h: repair block, head, border arrays");
+
+int sh_mesh_repair(sh_ctx* c, const sh_repair_options* opt, sh_repair_info* info, sh_repair_shell* shells, sh_repair_hole* holes, unsigned char* flip) {
+  const bool topology = c && c->at("topo.adj") && c->at("topo.label") && c->at("topo.vrow") && c->at("topo.vface") && c->at("topo.info") && c->at("topo.shells") && c->topo_shell_records > 0;
+  if (const ArthroError e = precheck_repair(opt, topology, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_mesh_repair", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B, S = c->topo_shell_records;
+  std::vector<sh_topology> tinfo((size_t)B);
+  HIPCHK(c, hipMemcpyAsync(tinfo.data(), c->at("topo.info"), (size_t)B * sizeof(sh_topology), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const RepairPlan plan = repair_plan(B, S, opt->max_holes, c->maxV, c->maxF, c->sumF, c->h_voff.data(), c->h_foff.data(), tinfo.data());
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  const RepairView v = view_of<RepairView>(c);
+  const long long sumF = c->sumF;
+  const size_t f = (size_t)(sumF > 0 ? sumF : 1);
+  HIPCHK(c, hipMemcpyAsync(v.repair_off, plan.off.data(), plan.bytes.repair_off, hipMemcpyHostToDevice, c->stream));      // (pageable: staged before the call returns)
+  HIPCHK(c, hipMemsetAsync(v.repair_work, 0x7f, f * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.repair_work + f, 0, f * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.repair_shells, 0, plan.bytes.repair_shells, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.repair_holes, 0, plan.bytes.repair_holes, c->stream));
+  const dim3 blocks((unsigned)plan.blocks, (unsigned)B), lanes(SH_REPAIR_BLOCK), meshes((unsigned)B), per_shell((unsigned)S, (unsigned)B);
+  const sh_topology* ti = v.topo_info;
+  const sh_shell* ts = v.topo_shells;
+  LAUNCH(c, "k_repair_seed", k_repair_seed, blocks, lanes, v.foff, (const int*)v.topo_label, ti, ts, S, sumF, v.repair_work);
+  LAUNCH(c, "k_repair_parity", k_repair_parity, meshes, dim3(SH_REPAIR_WALK), v.faces, v.foff, (const int*)v.topo_adj, (const int*)v.topo_label, ti, sumF, (int)opt->orient,
+         (int)opt->max_rounds, v.repair_work, v.repair_flip, v.repair_par);
+  LAUNCH(c, "k_repair_shell", k_repair_shell, per_shell, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_label, ti, ts, S, sumF, (int)opt->orient, v.repair_work,
+         v.repair_term, v.repair_flip, v.repair_par, v.repair_shells);
+  if (opt->orient == SH_REPAIR_NESTED)
+    LAUNCH(c, "k_repair_nest", k_repair_nest, per_shell, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_label, ti, ts, S, sumF, v.repair_work,
+           (const unsigned char*)v.repair_par, v.repair_flip, v.repair_shells);
+  LAUNCH(c, "k_repair_emit", k_repair_emit, blocks, lanes, v.verts, v.faces, v.voff, v.foff, (const unsigned char*)v.repair_flip, (const long long*)v.repair_off, B,
+         v.repair_faces, v.repair_verts);
+  LAUNCH(c, "k_repair_holes", k_repair_holes, meshes, lanes, v.verts, v.faces, v.voff, v.foff, (const int*)v.topo_adj, (const int*)v.topo_label, (const int*)v.topo_vrow,
+         (const int*)v.topo_vface, ti, (const unsigned char*)v.repair_flip, (const long long*)v.repair_off, B, S, sumF, (int)opt->orient, (int)opt->fill, (int)opt->max_hole_edges, (int)opt->max_holes,
+         v.repair_work, v.repair_edge, v.repair_faces, v.repair_verts, v.repair_info, v.repair_shells, v.repair_holes);
+  if (info) HIPCHK(c, hipMemcpyAsync(info, v.repair_info, plan.bytes.repair_info, hipMemcpyDeviceToHost, c->stream));
+  if (shells) HIPCHK(c, hipMemcpyAsync(shells, v.repair_shells, plan.bytes.repair_shells, hipMemcpyDeviceToHost, c->stream));
+  if (holes) HIPCHK(c, hipMemcpyAsync(holes, v.repair_holes, plan.bytes.repair_holes, hipMemcpyDeviceToHost, c->stream));
+  if (flip) HIPCHK(c, hipMemcpyAsync(flip, v.repair_flip, (size_t)sumF, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -1988,6 +1988,119 @@ SH_HD double smooth_disp(double d2) {
   return d > 0.0 ? d : 0.0;
 }
 
+// ---- repair of the resident batch (include/shoulder_hip.h sh_mesh_repair; k_repair.h) -------------------------------------------------
+// Integer rules on the faces and the adjacency of sh_mesh_topology, one float64 sum per shell and one per filled hole, restated by
+// tests/repair_oracle.py.  The modes and the statuses are the header's SH_REPAIR_* (k_repair.h holds them equal).
+#define SH_REP_ORIENT_NONE 0
+#define SH_REP_ORIENT_WINDING 1
+#define SH_REP_ORIENT_OUTWARD 2
+#define SH_REP_ORIENT_NESTED 3
+#define SH_REP_FILL_NONE 0
+#define SH_REP_FILL_FAN 1
+#define SH_REP_FILL_CENTROID 2
+#define SH_REP_SHELL_NONORIENTABLE 1
+#define SH_REP_SHELL_AMBIGUOUS 2
+#define SH_REP_HOLE_FILLED 0
+#define SH_REP_HOLE_TOO_LONG 1
+#define SH_REP_HOLE_SHELL 2
+#define SH_REP_HOLE_OPEN 3           // fill = NONE: reported, not filled
+#define SH_REP_HOLE_TOO_SHORT 4      // fewer than three edges
+#define SH_REP_V6_BLOCK 2048         // entries of a shell's face list that are summed one after the other
+
+// the corners of face f as it is oriented: (a, b, c), or (a, c, b) when it is flipped
+SH_HD void rep_face(const int* faces, int f, int flip, int* c) {
+  const int* p = faces + 3 * (size_t)f;
+  c[0] = p[0]; c[1] = flip ? p[2] : p[1]; c[2] = flip ? p[1] : p[2];
+}
+// corner k of face f as it is oriented, read where it is stored (no copy of the face)
+SH_HD int rep_corner(const int* faces, int f, int flip, int k) { return faces[3 * (size_t)f + (k == 0 || !flip ? k : 3 - k)]; }
+// slot e of an oriented face is this slot of the stored one: a flip exchanges slots 0 and 2
+SH_HD int rep_slot(int e, int flip) { return flip ? 2 - e : e; }
+
+// same(f, g) across the stored slot e of f, whose value in "topo.adj" is the face g: both traverse the edge in the same direction
+SH_HD int rep_same(const int* faces, int f, int e, int g) {
+  const int a = faces[3 * (size_t)f + e], c = faces[3 * (size_t)f + (e == 2 ? 0 : e + 1)];
+  const int* gf = faces + 3 * (size_t)g;
+  const int ge = topo_edge_slot(gf, a, c);
+  return ge >= 0 && gf[ge] == a ? 1 : 0;
+}
+
+// the centre of a shell's float32 box, per coordinate
+SH_HD double rep_center(float lo, float hi) { return (double)lo + ((double)hi - (double)lo) * 0.5; }
+
+// det[A - o, B - o, C - o] of an oriented face: a . (b x c), the numerator of solid_angle_tri
+SH_HD double rep_v6_term(const float* verts, const int* c, const double* o) {
+  double P[3][3];
+  for (int k = 0; k < 3; ++k)
+    for (int j = 0; j < 3; ++j) P[k][j] = (double)verts[3 * (size_t)c[k] + j] - o[j];
+  double bc[3];
+  cross3(P[1], P[2], bc);
+  return dot3(P[0], bc);
+}
+
+// The successor of the border half-edge (f, e) of the oriented faces: rotate about its head w.  Slot (e + 1) % 3 of f starts at w; a
+// border there is the successor; a face g there is entered through its slot that runs the other way, x -> w, and the rotation goes on
+// from it; a non-manifold slot, or a neighbour that runs the same way (no rotation about w), blocks the chain.  -> 1 and (*sf, *se), or 0.
+// A step enters a face through a manifold slot, so no (face, slot) comes twice and the walk ends within 3 nf steps.
+SH_HD int rep_succ(const int* faces, const int* adj, const unsigned char* flip, int nf, int f, int e, int* sf, int* se) {
+  int cf = f, ce = e;
+  for (long long step = 0; step <= 3 * (long long)nf; ++step) {
+    const int fc = flip[cf];
+    const int n = ce == 2 ? 0 : ce + 1;
+    const int w = rep_corner(faces, cf, fc, n), x = rep_corner(faces, cf, fc, n == 2 ? 0 : n + 1);
+    const int a = adj[3 * (size_t)cf + rep_slot(n, fc)];
+    if (a == SH_TOPO_BORDER) { *sf = cf; *se = n; return 1; }
+    if (a < 0) return 0;
+    const int fa = flip[a];
+    const int g0 = rep_corner(faces, a, fa, 0), g1 = rep_corner(faces, a, fa, 1), g2 = rep_corner(faces, a, fa, 2);
+    const int ge = g0 == x && g1 == w ? 0 : g1 == x && g2 == w ? 1 : g2 == x && g0 == w ? 2 : -1;
+    if (ge < 0) return 0;
+    cf = a; ce = ge;
+  }
+  return 0;
+}
+
+// the status of a hole of L edges; shell_ok: its shell is orientable
+SH_HD int rep_hole_status(int L, int shell_ok, int fill, int max_hole_edges) {
+  if (!shell_ok) return SH_REP_HOLE_SHELL;
+  if (L < 3) return SH_REP_HOLE_TOO_SHORT;
+  if (L > max_hole_edges) return SH_REP_HOLE_TOO_LONG;
+  return fill == SH_REP_FILL_NONE ? SH_REP_HOLE_OPEN : SH_REP_HOLE_FILLED;
+}
+// the faces and the vertices a filled hole of L edges adds
+SH_HD int rep_fill_faces(int L, int fill) { return fill == SH_REP_FILL_FAN ? L - 2 : L; }
+SH_HD int rep_fill_verts(int fill) { return fill == SH_REP_FILL_CENTROID ? 1 : 0; }
+
+// The fill face of the half-edge at place j of a hole of L edges (u_j -> u_j1, u_0 the start's tail, cv the new vertex): its place among
+// the hole's faces, or -1 when the half-edge adds none (the fan's places 0 and L - 1).  Each runs u_j1 -> u_j, against the border.
+SH_HD int rep_fill_face(int fill, int L, int j, int u0, int uj, int uj1, int cv, int* out) {
+  if (fill == SH_REP_FILL_FAN) {
+    if (j < 1 || j > L - 2) return -1;
+    out[0] = u0; out[1] = uj1; out[2] = uj;
+    return j - 1;
+  }
+  out[0] = uj1; out[1] = uj; out[2] = cv;
+  return j;
+}
+
+// the new vertex of a hole: per coordinate the float64 sum of the float32 positions of its tails in loop order from u_0, over (double) L
+SH_HD void rep_centroid(const float* verts, const int* order, int L, float* out) {
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int j = 0; j < L; ++j) {
+    const float* p = verts + 3 * (size_t)order[j];
+    s[0] += (double)p[0]; s[1] += (double)p[1]; s[2] += (double)p[2];
+  }
+  for (int k = 0; k < 3; ++k) out[k] = (float)(s[k] / (double)L);
+}
+
+// the nesting depth of a shell from its winding sum W (NESTED): rint(W), or 0 and *ambiguous when W is further than 0.25 from it
+SH_HD int rep_depth(double W, int* ambiguous) {
+  const double d = rint(W);
+  *ambiguous = !(fabs(W - d) <= 0.25) ? 1 : 0;
+  if (*ambiguous || !(fabs(d) < 1e9)) return 0;
+  return (int)d;
+}
+
 // ---- the face hierarchy of the resident batch (include/shoulder_hip.h sh_mesh_bvh; k_bvh.h) -------------------------------------------
 // float32 minima and maxima, one float64 quantisation and integer work, restated by tests/bvh_oracle.py: the device, the host twin
 // (tests/hostcheck/bvh_check.cpp) and the oracle give the same bytes.  LEAF and WIDTH are powers of two in 4..16, fixed after measuring

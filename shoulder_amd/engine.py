@@ -1042,6 +1042,44 @@ class Engine:
             return nrow, places[6 * f0:6 * f0 + int(nrow[-1])].copy()
         return [one(k) for k in range(self.B)] if b is None else one(int(b))
 
+    # ---- repair of the resident batch (include/shoulder_hip.h sh_mesh_repair) -----------------------------------------------------
+    _REPAIR_ORIENTS = {"none": _lib.REPAIR_NONE, "winding": _lib.REPAIR_WINDING, "outward": _lib.REPAIR_OUTWARD, "nested": _lib.REPAIR_NESTED}
+    _REPAIR_FILLS = {"none": _lib.REPAIR_FILL_NONE, "fan": _lib.REPAIR_FAN, "centroid": _lib.REPAIR_CENTROID}
+
+    def repair(self, orient="outward", fill="centroid", max_hole_edges=4096, max_shells=64, max_holes=64, max_rounds=_lib.REPAIR_MAX_ROUNDS):
+        """Every resident mesh with one winding per shell, its shells outward and its holes filled, on the device: trimesh.repair's
+        fix_winding ("winding"), fix_inversion ("outward"; "nested": by nesting depth, so that the wall of a cavity stays inward) and
+        fill_holes for loops of any length up to max_hole_edges ("fan": faces about the loop's first vertex, "centroid": one new
+        vertex per hole, "none": the holes are reported).  The topology() of this batch is made first, with max_shells, when it is not
+        resident.  -> dict: info (B,) of _lib.REPAIR_INFO_DTYPE, shells (B, shell records) of _lib.REPAIR_SHELL_DTYPE, holes
+        (B, max_holes) of _lib.REPAIR_HOLE_DTYPE, flip (sumF,) uint8, the final flip of every face, and meshes: a list of (verts
+        float32, faces int32), one per resident mesh, each ready for upload().  A mesh with a status (SH_ERR_CAPACITY: its labelling
+        did not finish, it has more than REPAIR_LDS_FACES faces or its face graph is deeper than max_rounds) comes back unchanged.
+        "verts" and "faces" are not written.  The same bytes wherever the rule runs."""
+        o, f = self._REPAIR_ORIENTS.get(orient, orient), self._REPAIR_FILLS.get(fill, fill)
+        if not isinstance(o, (int, np.integer)):
+            raise ValueError("orient must be 'none', 'winding', 'outward' or 'nested'")
+        if not isinstance(f, (int, np.integer)):
+            raise ValueError("fill must be 'none', 'fan' or 'centroid'")
+        if self.B >= 1 and not self._has_buffer("topo.adj"):
+            self.topology(max_shells=max_shells)
+        B = max(self.B, 0)
+        opt = np.array([int(o), int(f), int(max_hole_edges), int(max_holes), int(max_rounds), 0], dtype=np.int32)
+        ok = 1 <= int(max_holes) <= _lib.REPAIR_MAX_HOLES      # (the library reports the rest; nothing else is sized by the options here)
+        info = np.zeros(B, dtype=_lib.REPAIR_INFO_DTYPE)
+        holes = np.zeros((B, int(max_holes)) if ok else (0,), dtype=_lib.REPAIR_HOLE_DTYPE)
+        flip = np.zeros(int(self.foff[-1]) if B else 0, dtype=np.uint8)
+        self._chk(self.L.sh_mesh_repair(self.h, _ptr(opt), _ptr(info), None, _ptr(holes), _ptr(flip)))
+        S = int(info[0]["shell_records"])
+        shells = self.fetch("repair.shells", _lib.REPAIR_SHELL_DTYPE)[:B * S].reshape(B, S).copy()
+        off = self.fetch("repair.off", np.int64)[:3 * (B + 1)].reshape(3, B + 1)
+        faces, verts = self.fetch("repair.faces", np.int32), self.fetch("repair.verts", np.float32)
+        meshes = []
+        for b in range(B):
+            f0, v0 = int(off[0, b]), int(off[1, b])
+            meshes.append((verts[3 * v0:3 * (v0 + int(info[b]["verts_out"]))].reshape(-1, 3).copy(), faces[3 * f0:3 * (f0 + int(info[b]["faces_out"]))].reshape(-1, 3).copy()))
+        return dict(info=info, shells=shells, holes=holes, flip=flip, meshes=meshes)
+
     # ---- geodesic distances and shortest paths on the resident batch (include/shoulder_hip.h sh_geodesic) ------------------------
     _GEO_MODES = {"edges": _lib.GEO_EDGES, "unfold": _lib.GEO_UNFOLD}
 
