@@ -14,8 +14,14 @@
 namespace sh {
 
 #define SH_GSLOTS (SH_GROOVE_NROWS * SH_MAXPEAK)
+#define SH_CAND_BATCH 64      // local maxima of a row that k_groove_rows filters at a time
 
-__global__ void k_groove_rows(const double* __restrict__ itr_cs /*[B][600][2][512]*/, const double* __restrict__ prox_zs,
+// One wave per block, 12 752 B of LDS: 12 blocks per CU, i.e. 3 waves per SIMD, is all the LDS admits.  Compiler's resource report
+// (hipcc 6.x, gfx950): no attribute -> 128 VGPRs, 54 spilled, 168 B scratch; __launch_bounds__(64) alone -> 225 VGPRs, no scratch, 2 waves
+// per SIMD; with 3 waves per SIMD asked for -> 168 VGPRs, 44 spilled, 144 B scratch.  bench.py headline, mean of 3 on one MI355X:
+// 8 584 meshes/s (bound alone), 8 635 (this), 8 669 (the kernel with the 64-candidate cap: 75 VGPRs).
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3)))
+k_groove_rows(const double* __restrict__ itr_cs /*[B][600][2][512]*/, const double* __restrict__ prox_zs,
                               const double* __restrict__ canal_axis_ct, int row0,
                               double* __restrict__ xraw, double* __restrict__ ptheta, int* __restrict__ npk,
                               double* __restrict__ r0, int* __restrict__ err, int B) {
@@ -28,17 +34,18 @@ __global__ void k_groove_rows(const double* __restrict__ itr_cs /*[B][600][2][51
   __shared__ double s_bufA[SH_MPROX], s_bufB[SH_MPROX];
   double* const s_r = s_bufA; double* const s_filt = s_bufA;
   double* const s_neg = s_bufB; double* const s_roll = s_bufB;
-  __shared__ int s_cand[SH_PEAK_CAP];
-  __shared__ Peak s_pk[SH_PEAK_CAP];
-  __shared__ int s_pass[SH_PEAK_CAP];
-  __shared__ int s_ncand;
+  // Candidate rule: a row of 512 samples holds up to 255 local maxima.  They are taken in ascending order, SH_CAND_BATCH at a time
+  // (a lane owns 8 consecutive samples, a wave scan of the lanes' counts ranks every maximum: no atomics, nothing depends on
+  // the order lanes arrive in); every batch is filtered and its passing peaks appended, and as soon as more than SH_MAXPEAK are
+  // held they are cut to the SH_MAXPEAK most prominent -- the 7 best of (the 7 best so far + the new ones) are the 7 best of all.
+  __shared__ int s_cand[SH_CAND_BATCH];
+  __shared__ Peak s_pk[SH_MAXPEAK + SH_CAND_BATCH];
   const int M = SH_MPROX;
   const int gid = blockIdx.x, lane = threadIdx.x;
   const int b = gid / SH_GROOVE_NROWS, i = gid % SH_GROOVE_NROWS;
   const double* row = itr_cs + ((size_t)b * SH_NPROX + row0 + i) * 2 * M;
   const double* zs = prox_zs + (size_t)b * SH_NPROX + row0;
   for (int k = lane; k < M; k += 64) s_r[k] = row[M + k];
-  if (lane == 0) s_ncand = 0;
   __syncthreads();
   // np.mean(r): pairwise_sum(512) = (leaf0 + leaf1) + (leaf2 + leaf3), leaf = 8 strided accumulators
   double acc = 0.0;
@@ -73,29 +80,44 @@ __global__ void k_groove_rows(const double* __restrict__ itr_cs /*[B][600][2][51
   __syncthreads();      // (the rolled row takes s_neg's place)
   for (int k = lane; k < M; k += 64) { int src = k + amin; if (src >= M) src -= M; s_roll[k] = s_filt[src]; }
   __syncthreads();
-  // local maxima: every rising edge is examined independently (equivalent to the sequential scan)
-  for (int k = 1 + lane; k < M - 1; k += 64)
-    if (s_roll[k - 1] < s_roll[k]) {
-      int resume;
-      int pk = local_maximum_at(s_roll, M, k, &resume);
-      if (pk >= 0) { int s = atomicAdd(&s_ncand, 1); if (s < SH_PEAK_CAP) s_cand[s] = pk; }
-    }
-  __syncthreads();
-  int nc = s_ncand < SH_PEAK_CAP ? s_ncand : SH_PEAK_CAP;
-  if (lane == 0)      // ascending index
-    for (int a = 1; a < nc; ++a) { int v = s_cand[a]; int q = a - 1; while (q >= 0 && s_cand[q] > v) { s_cand[q + 1] = s_cand[q]; --q; } s_cand[q + 1] = v; }
-  __syncthreads();
   static_assert(SH_MPROX == 512, "8 samples per lane");
+  // local maxima: every rising edge is examined independently (equivalent to the sequential scan), by the lane that holds it
+  double xr[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) xr[q] = s_roll[8 * lane + q];
+  // (the neighbours come from the registers; only a plateau -- the next sample equal -- is followed through LDS)
+  const double x_before = __shfl_up(xr[7], 1), x_after = __shfl_down(xr[0], 1);
+  int pkq[8];      // the maximum the rising edge at sample 8 * lane + q leads to (a plateau's midpoint), or -1
+  int rank0 = 0, nmax = 0;      // maxima in the lanes before this one; in the row
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int k = 8 * lane + q;
+    const double a = q > 0 ? xr[q > 0 ? q - 1 : 0] : x_before, c = q < 7 ? xr[q < 7 ? q + 1 : 7] : x_after;
+    int pk = -1;
+    if (k >= 1 && k < M - 1 && a < xr[q]) {
+      if (c < xr[q]) pk = k;
+      else if (c == xr[q]) { int resume; pk = local_maximum_at(s_roll, M, k, &resume); }
+    }
+    pkq[q] = pk;
+    const unsigned long long bq = __ballot(pk >= 0);
+    rank0 += __popcll(bq & ((1ull << lane) - 1ull));
+    nmax += __popcll(bq);
+  }
   // sh::peak_eval for every candidate.  Its prominence walks (left and right until a higher sample, up to the whole row
   // for the highest peak, one dependent LDS read per step) are done by the whole wave per candidate instead: every lane
   // holds 8 consecutive samples; nearest higher sample, minimum of the stretch up to it and the occurrence of that minimum
   // closest to the peak are wave reductions -- the same values and indices as the sequential walk.
-  __shared__ int s_lb[SH_PEAK_CAP], s_rb[SH_PEAK_CAP];
-  __shared__ double s_lmin[SH_PEAK_CAP], s_rmin[SH_PEAK_CAP];
-  {
-    double xr[8];
+  __shared__ int s_lb[SH_CAND_BATCH], s_rb[SH_CAND_BATCH];
+  __shared__ double s_lmin[SH_CAND_BATCH], s_rmin[SH_CAND_BATCH];
+  int np_ = 0;      // passing peaks held in s_pk, ascending index (the same in every lane)
+  for (int base = 0; base < nmax; base += SH_CAND_BATCH) {
+    const int nc = min(SH_CAND_BATCH, nmax - base);
+    {
+      int r = rank0 - base;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) xr[q] = s_roll[8 * lane + q];
+      for (int q = 0; q < 8; ++q) if (pkq[q] >= 0) { if (r >= 0 && r < SH_CAND_BATCH) s_cand[r] = pkq[q]; ++r; }
+    }
+    __syncthreads();
     for (int cnd = 0; cnd < nc; ++cnd) {
       const int pk = s_cand[cnd];
       const double v = s_roll[pk];
@@ -121,57 +143,57 @@ __global__ void k_groove_rows(const double* __restrict__ itr_cs /*[B][600][2][51
       for (int off = 32; off > 0; off >>= 1) { lb = max(lb, __shfl_xor(lb, off)); rb = min(rb, __shfl_xor(rb, off)); }
       if (lane == 0) { s_lb[cnd] = lb; s_rb[cnd] = rb; s_lmin[cnd] = lm; s_rmin[cnd] = rm; }
     }
-  }
-  __syncthreads();
-  if (lane < nc) {      // heights, prominence threshold, widths at half prominence (short walks): as in sh::peak_eval
-    const double* x = s_roll;
-    const int pk = s_cand[lane], lb = s_lb[lane], rb = s_rb[lane];
-    const double left_min = s_lmin[lane], right_min = s_rmin[lane];
-    bool ok = x[pk] >= -10.0;
-    const double prom = x[pk] - (left_min > right_min ? left_min : right_min);
-    ok = ok && prom >= 0.6;
-    if (ok) {
-      const double h = x[pk] - prom * 0.5;
-      int k = pk;
-      while (lb < k && h < x[k]) --k;
-      double lip = (double)k;
-      if (x[k] < h) lip += (h - x[k]) / (x[k + 1] - x[k]);
-      k = pk;
-      while (k < rb && h < x[k]) ++k;
-      double rip = (double)k;
-      if (x[k] < h) rip -= (h - x[k]) / (x[k - 1] - x[k]);
-      const double w = rip - lip;
-      ok = w >= 0.1;
-      if (ok) { s_pk[lane].idx = pk; s_pk[lane].prominence = prom; s_pk[lane].width = w; s_pk[lane].width_height = h; }
+    __syncthreads();
+    Peak p;
+    bool ok = false;
+    if (lane < nc) {      // heights, prominence threshold, widths at half prominence (short walks): as in sh::peak_eval
+      const double* x = s_roll;
+      const int pk = s_cand[lane], lb = s_lb[lane], rb = s_rb[lane];
+      const double left_min = s_lmin[lane], right_min = s_rmin[lane];
+      ok = x[pk] >= -10.0;
+      const double prom = x[pk] - (left_min > right_min ? left_min : right_min);
+      ok = ok && prom >= 0.6;
+      if (ok) {
+        const double h = x[pk] - prom * 0.5;
+        int k = pk;
+        while (lb < k && h < x[k]) --k;
+        double lip = (double)k;
+        if (x[k] < h) lip += (h - x[k]) / (x[k + 1] - x[k]);
+        k = pk;
+        while (k < rb && h < x[k]) ++k;
+        double rip = (double)k;
+        if (x[k] < h) rip -= (h - x[k]) / (x[k - 1] - x[k]);
+        const double w = rip - lip;
+        ok = w >= 0.1;
+        p.idx = pk; p.prominence = prom; p.width = w; p.width_height = h;
+      }
     }
-    s_pass[lane] = ok ? 1 : 0;
+    // the batch's passing peaks behind those held, in lane (= index) order
+    const unsigned long long pm = __ballot(ok);
+    if (ok) s_pk[np_ + __popcll(pm & ((1ull << lane) - 1ull))] = p;
+    np_ += __popcll(pm);
+    __syncthreads();
+    if (np_ > SH_MAXPEAK) {      // keep the 7 most prominent (B-5: ascending index order among the kept)
+      if (lane == 0) {
+        bool keep[SH_MAXPEAK + SH_CAND_BATCH];
+        for (int k = 0; k < np_; ++k) keep[k] = false;
+        for (int q = 0; q < SH_MAXPEAK; ++q) {
+          int bq = -1;
+          for (int k = 0; k < np_; ++k)
+            if (!keep[k] && (bq < 0 || s_pk[k].prominence > s_pk[bq].prominence)) bq = k;
+          keep[bq] = true;
+        }
+        int w = 0;
+        for (int k = 0; k < np_; ++k) if (keep[k]) s_pk[w++] = s_pk[k];
+      }
+      np_ = SH_MAXPEAK;
+      __syncthreads();
+    }
   }
-  __syncthreads();
   // Second half of the row (sh::groove_features_from_peaks, same arithmetic per element) spread over the wave: the
   // 7 x 7 wrapped angle differences (atan2 / sin / cos each) take one lane per pair instead of 49 serial evaluations.
-  __shared__ int s_np;
   __shared__ double s_th[SH_MAXPEAK], s_d[SH_MAXPEAK][SH_MAXPEAK];
   __shared__ int s_pidx[SH_MAXPEAK];
-  if (lane == 0) {
-    int np_ = 0;
-    for (int a = 0; a < nc; ++a) if (s_pass[a]) s_pk[np_++] = s_pk[a];
-    if (np_ > SH_MAXPEAK) {      // keep the 7 most prominent (B-5: ascending index order among the kept)
-      bool keep[SH_PEAK_CAP];
-      for (int k = 0; k < np_; ++k) keep[k] = false;
-      for (int q = 0; q < SH_MAXPEAK; ++q) {
-        int bq = -1;
-        for (int k = 0; k < np_; ++k)
-          if (!keep[k] && (bq < 0 || s_pk[k].prominence > s_pk[bq].prominence)) bq = k;
-        keep[bq] = true;
-      }
-      int w = 0;
-      for (int k = 0; k < np_; ++k) if (keep[k]) s_pk[w++] = s_pk[k];
-      np_ = SH_MAXPEAK;
-    }
-    s_np = np_;
-  }
-  __syncthreads();
-  const int np_ = s_np;
   if (lane < np_) {
     const int idx = (s_pk[lane].idx + amin) % M;     // (peaks - rmin) % interp_num with rmin = -amin
     s_pidx[lane] = idx;

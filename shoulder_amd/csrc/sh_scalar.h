@@ -256,7 +256,7 @@ SH_HD int find_peaks_hpw(const double* x, int n, double hmin, double pmin, doubl
 // width_height, canal_dist, n_peaks/7.
 // scratch: 3*M doubles.
 // ======================================================================================
-#define SH_PEAK_CAP 64
+#define SH_PEAK_CAP 256     // passing peaks of a row: 512 samples hold at most 255 strict local maxima, so the cap is never met
 SH_HD int groove_features_from_peaks(const double* theta, const double* r, int M, double z, double z_scaled, const double* canal_u,
                                      Peak* pk, int np_, int amin, double* Xraw, double* peak_theta, int* peak_idx);
 SH_HD double wrapped_abs_diff(double v, double a) { return fabs(atan2(sin(v - a), cos(v - a))); }

@@ -12,28 +12,7 @@ import scipy.signal
 from conftest import GOLDEN, ROOT
 from oracle import cpd, fits, groove, obb, slices, te, xform
 
-HC = os.path.join(ROOT, "tests", "hostcheck")
-D = ctypes.POINTER(ctypes.c_double)
-I = ctypes.POINTER(ctypes.c_int)
-
-
-def dp(a):
-    return a.ctypes.data_as(D)
-
-
-@pytest.fixture(scope="module")
-def hc():
-    so = os.path.join(HC, "libhostcheck.so")
-    src = os.path.join(HC, "hostcheck.cpp")
-    hdrs = [os.path.join(ROOT, "shoulder_amd", "csrc", h) for h in ("sh_scalar.h", "sh_common.h", "sh_hull.h")] + [os.path.join(HC, "hull_rounds_ref.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, src])
-    lib = ctypes.CDLL(so)
-    lib.hc_circle.restype = ctypes.c_double
-    lib.hc_rfc.restype = ctypes.c_float
-    lib.hc_interp.restype = ctypes.c_double
-    lib.hc_linspace.restype = ctypes.c_double
-    return lib
+from hostcheck_lib import D, HC, I, dp, hc  # noqa: E402,F401  (hc: the fixture that builds and loads the shim)
 
 
 def test_savgol(hc):
