@@ -1240,6 +1240,77 @@ int sh_mesh_repair(sh_ctx*, const sh_repair_options* options, sh_repair_info* in
                    sh_repair_shell* shells /* B x shell_records, host, nullable */, sh_repair_hole* holes /* B x max_holes, host, nullable */,
                    unsigned char* flip /* sumF, host, nullable */);
 
+/* ---- simplification of the resident batch: vertex clustering with quadric placement -------------------------------------------------
+ * sh_mesh_simplify makes every resident mesh smaller (k_simplify.h): the used vertices that fall into one cell of a grid become one
+ * vertex, placed at their mean or where the quadric of their faces is smallest, and the faces that survive are renumbered
+ * (Rossignac-Borrel clustering with Garland-Heckbert quadrics, as in Lindstrom's out-of-core simplification).  The placement is
+ * Lindstrom's cell clamp with a Tikhonov term towards the mean in place of his SVD; equality with any other library is not claimed.
+ * "verts" and "faces" are NOT written: the meshes come back in "simp.verts" and "simp.faces", ready for an upload.  Clustering does
+ * not preserve topology: it may leave border and non-manifold edges, which sh_mesh_topology of the re-upload reports.  Every rule is
+ * per mesh with indices local to the mesh, float64 operation by operation with + - x / sqrt and floor only, no contraction, dot3(a, b) =
+ * (a0 b0 + a1 b1) + a2 b2, cross3(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0); "degenerate" and "row" mean what they mean in
+ * sh_mesh_topology; a result depends on the mesh, its cell and the options alone: not on B, the mesh's place in the batch or a
+ * schedule.  The rules are sh_scalar.h simp_*, restated by tests/simplify_oracle.py.
+ *   used       a vertex is used when a non-degenerate face names it (its row is not empty).  An unused vertex takes no part in
+ *              anything; its map entry is -1.
+ *   grid       lo, hi: the float32 minima and maxima of the used vertices, widened; h = cell[b]; per axis n = (int64) floor((hi - lo) / h)
+ *              + 1; the cell of a vertex per axis i = min((int64) floor(((double) x - lo) / h), n - 1); key = (iz ny + iy) nx + ix.  A
+ *              mesh with n > SH_SIMPLIFY_MAX_CELLS on an axis, or with more than SH_SIMPLIFY_MAX_CLUSTERS clusters, gets status
+ *              SH_ERR_CAPACITY, empty outputs, a map of -1 and, of the counts, verts_used and clusters (0 for the axis limit) alone --
+ *              never the batch.
+ *   clusters   a cluster is the set of used vertices with one key; clusters are numbered ascending by key; the members of a cluster
+ *              are taken ascending by vertex index (part of the definition: the sums below run in that order); o = lo + ((double) i +
+ *              0.5) h per axis, the centre of the cell.
+ *   mean       m = S / (double) count, S the sum of the widened positions, one member after the other, from 0.0.
+ *   quadric    of a vertex, relative to the o of its cluster: over its row in row order, from 0.0, each face with the widened corners
+ *              A, B, C adds n = cross3(B - A, C - A) and d = -dot3(n, A - o) to the ten sums n0n0, n0n1, n0n2, n1n1, n1n2, n2n2, n0d,
+ *              n1d, n2d, dd.  n is not normalised: a face weighs by its squared area; a face with two corners in a cluster counts
+ *              twice, as Garland-Heckbert's Q1 + Q2 does.  Of a cluster: the quadrics of its members added in member order from 0.0.
+ *              With A the 3 x 3 matrix (a00 a01 a02; . a11 a12; . . a22) of the first six sums and b the next three:
+ *   place      SH_SIMPLIFY_MEAN: float32(m).  SH_SIMPLIFY_QUADRIC: tr = (a00 + a11) + a22, lam = reg tr, m00 = a00 + lam, m11 = a11 +
+ *              lam, m22 = a22 + lam, r = lam (m - o) - b per axis, then term by term
+ *                l00 = sqrt(m00); l10 = a01 / l00; l20 = a02 / l00; p1 = m11 - l10 l10; l11 = sqrt(p1); l21 = (a12 - l20 l10) / l11;
+ *                p2 = (m22 - l20 l20) - l21 l21; l22 = sqrt(p2); y0 = r0 / l00; y1 = (r1 - l10 y0) / l11;
+ *                y2 = ((r2 - l20 y0) - l21 y1) / l22; x2 = y2 / l22; x1 = (y1 - l21 x2) / l11; x0 = ((y0 - l10 x1) - l20 x2) / l00
+ *              and the position is float32(o + x).  The cluster takes float32(m) instead, and counts in fallbacks, when tr is 0.0 or
+ *              not finite, a radicand (m00, p1, p2) is <= 0.0 or not finite, a component of x is not finite, or |x_c| > (0.5 h) clamp.
+ *   faces      a non-degenerate face (a, b, c) becomes (c(a), c(b), c(c)), its winding kept; it is COLLAPSED and dropped when two of
+ *              the three are equal; of the rest, those with the same set of three clusters are DUPLICATES and the one with the
+ *              smallest face index stays; kept faces keep the order of their indices.  Clusters no kept face names are dropped and
+ *              the rest renumbered in key order: the output has no unreferenced vertex.  map[v] = the output vertex of v's cluster,
+ *              or -1.
+ *   outputs    the regions of mesh b start at voff[b] (in "simp.verts" and "simp.map") and foff[b] (in "simp.faces"); an output is
+ *              never larger than its input, so the host sizes nothing from the device and reads nothing between the launches.  The
+ *              tail of a region behind verts_out / faces_out is zero.
+ *   records    sh_simplify_info per mesh ("simp.info"): status (0, SH_ERR_CAPACITY, or SH_ERR_GEOMETRY with faces_out = 0 when every
+ *              face collapsed or the mesh has no used vertex); verts_used; clusters; verts_out; faces_out; faces_collapsed;
+ *              faces_duplicate (the dropped ones); fallbacks; largest_cluster (members); reserved 0; cell = cell[b]; max_move = the
+ *              largest sqrt(dot3(d, d)), d = a used vertex (widened) minus its cluster's float32 position (widened), 0.0 for a d that
+ *              gives no number; 8 bytes of 0.
+ * Arguments in this order: the context and options (SH_ERR_ARG); place SH_SIMPLIFY_MEAN or SH_SIMPLIFY_QUADRIC, reserved == 0, reg
+ * finite in [0, 1], clamp finite and > 0 (SH_ERR_ARG); a cell array, every cell[b] of the resident meshes finite and > 0 (SH_ERR_ARG,
+ * naming b); a resident batch and no runs in flight (SH_ERR_STATE); the incidence of THIS
+ * batch resident (SH_ERR_STATE: call sh_mesh_topology first); SH_ERR_NOMEM when the buffers do not fit or the batch has more than
+ * 2^31 - 1 vertices.  A fixed list of launches; every output pointer may be NULL.  Reads "verts", "faces", the offsets, "topo.vrow",
+ * "topo.vface".  Resident afterwards: "simp.verts" (float32, 3 sumV), "simp.faces" (int32, 3 sumF), "simp.map" (int32, sumV),
+ * "simp.info" and the scratch "simp.state", "simp.seg", "simp.cell", "simp.key", "simp.sorted", "simp.ukey", "simp.start", "simp.cid",
+ * "simp.mark", "simp.rank", "simp.quad", "simp.pos", "simp.keep", "simp.frank", "simp.tmp"; they are removed together with "topo.*" by
+ * the next upload / commit / sh_store("verts").  Every other buffer keeps its bytes. */
+#define SH_SIMPLIFY_MEAN          0
+#define SH_SIMPLIFY_QUADRIC       1
+#define SH_SIMPLIFY_MAX_CELLS     1048576
+#define SH_SIMPLIFY_MAX_CLUSTERS  2097152
+struct sh_simplify_options { int32_t place, reserved; double reg, clamp; };                                     /* 24 B */
+typedef struct sh_simplify_options sh_simplify_options;
+struct sh_simplify_info {
+  int32_t status, verts_used, clusters, verts_out, faces_out, faces_collapsed, faces_duplicate, fallbacks, largest_cluster, reserved;
+  double cell, max_move;
+  int32_t pad[2];
+};                                                                                                             /* 64 B */
+typedef struct sh_simplify_info sh_simplify_info;
+int sh_mesh_simplify(sh_ctx*, const sh_simplify_options* options, const double* cell /* B, host */, sh_simplify_info* info /* B, host, nullable */,
+                     float* verts /* sumV x 3, host, nullable */, int32_t* faces /* sumF x 3, host, nullable */, int32_t* map /* sumV, host, nullable */);
+
 /* ---- a face hierarchy of the resident batch, and the closest-point step through it -------------------------------------------------
  * sh_mesh_bvh builds, per resident mesh, a bounding-box hierarchy over its faces (k_bvh.h; the rules are sh_scalar.h bvh_*, all float32
  * min / max, one float64 quantisation and integer work, restated by tests/bvh_oracle.py):

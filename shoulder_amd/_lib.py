@@ -43,6 +43,7 @@ REPAIR_NONE, REPAIR_WINDING, REPAIR_OUTWARD, REPAIR_NESTED, REPAIR_FILL_NONE, RE
 REPAIR_NONORIENTABLE, REPAIR_AMBIGUOUS, REPAIR_CHANGED, REPAIR_SHELLS_LEFT = 1, 2, 1, 2
 REPAIR_HOLE_FILLED, REPAIR_HOLE_TOO_LONG, REPAIR_HOLE_SHELL, REPAIR_HOLE_OPEN, REPAIR_HOLE_TOO_SHORT = 0, 1, 2, 3, 4
 REPAIR_MAX_HOLES, REPAIR_MAX_ROUNDS, REPAIR_LDS_FACES = 65536, 1048576, 131072
+SIMPLIFY_MEAN, SIMPLIFY_QUADRIC, SIMPLIFY_MAX_CELLS, SIMPLIFY_MAX_CLUSTERS = 0, 1, 1048576, 2097152
 ACCEL_OFF, ACCEL_BVH, BVH_INFO_BYTES = 0, 1, 48
 
 # ---- the records ------------------------------------------------------------------------------------------------------------------------
@@ -237,6 +238,12 @@ REPAIR_INFO_DTYPE = np.dtype([(n, "<i4") for n in ("status", "shells_nonorientab
 REPAIR_SHELL_DTYPE = np.dtype([(n, "<i4") for n in ("status", "parity_flips", "inverted", "depth", "holes", "holes_filled")] + [("V6", "<f8"), ("W", "<f8")])
 REPAIR_HOLE_DTYPE = np.dtype([(n, "<i4") for n in ("shell", "start_face", "start_slot", "edges", "status", "first_face", "faces_added", "vertex")])
 assert (REPAIR_OPTIONS_DTYPE.itemsize, REPAIR_INFO_DTYPE.itemsize, REPAIR_SHELL_DTYPE.itemsize, REPAIR_HOLE_DTYPE.itemsize) == (24, 64, 40, 32)
+# the records of sh_mesh_simplify (two statements each in the header, as the repair's); tests/hostcheck/simplify_check.cpp holds the sizes
+# and offsets against a C compile of the header (sc_sizes)
+SIMPLIFY_OPTIONS_DTYPE = np.dtype([("place", "<i4"), ("reserved", "<i4"), ("reg", "<f8"), ("clamp", "<f8")])
+SIMPLIFY_INFO_DTYPE = np.dtype([(n, "<i4") for n in ("status", "verts_used", "clusters", "verts_out", "faces_out", "faces_collapsed", "faces_duplicate", "fallbacks",
+                                                     "largest_cluster", "reserved")] + [("cell", "<f8"), ("max_move", "<f8"), ("pad", "<i4", (2,))])
+assert (SIMPLIFY_OPTIONS_DTYPE.itemsize, SIMPLIFY_INFO_DTYPE.itemsize) == (24, 64)
 # sh_bvh_info per mesh (sh_mesh_bvh): the header declares the struct and its typedef in two statements; stated here once, beside its bytes
 BVH_INFO_DTYPE = np.dtype([(n, "<i4") for n in ("tight", "loose", "leaves", "levels", "nodes", "reserved")] + [("lo", "<f4", (3,)), ("hi", "<f4", (3,))])
 assert BVH_INFO_DTYPE.itemsize == BVH_INFO_BYTES
@@ -330,6 +337,7 @@ SIGNATURES = {      # name -> (argtypes, restype, optional)
     "sh_geodesic": _f(_vp, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, optional=True),
     "sh_smooth_vertices": _f(_vp, _i, _i, _i, _i, _d, _d, _vp, _vp, _vp, optional=True),
     "sh_mesh_repair": _f(_vp, _vp, _vp, _vp, _vp, _vp, optional=True),
+    "sh_mesh_simplify": _f(_vp, _vp, _vp, _vp, _vp, _vp, _vp, optional=True),
     "sh_mesh_bvh": _f(_vp, _vp, optional=True),
     "sh_set_query_accel": _f(_vp, _i, optional=True),
     "sh_get_query_accel": _f(_vp, optional=True),

@@ -683,6 +683,23 @@ class ProximalHumerus(Bone):
         verts, faces = r["meshes"][0]
         return self._engine.transform_points(np.ascontiguousarray(verts, dtype=np.float64), T), faces
 
+    # -- simplification --------------------------------------------------------------------------------------------------
+    def simplified_mesh(self, cell=None, target_faces=None, place="quadric"):
+        """This bone made smaller by vertex clustering (Engine.simplify with `cell` in mm, or Engine.simplify_to with `target_faces`:
+        exactly one of the two) -> (verts (V', 3) float64, faces (F', 3) int32) in the CURRENT coordinate system, ready for
+        Engine.upload as repaired_mesh's result is.  The resident mesh is not changed.  Clustering does not preserve topology.
+        Raises ValueError when the mesh could not be simplified (a status in its info record: every face collapsed, or the cell is too
+        small for the grid)."""
+        if (cell is None) == (target_faces is None):
+            raise ValueError("simplified_mesh needs cell or target_faces, not both")
+        self._ensure_loaded()
+        T = np.array(self._tfrm.matrix, dtype=np.float64)
+        meshes, info, _ = self._engine.simplify(cell, place=place) if cell is not None else self._engine.simplify_to(target_faces, place=place)
+        if info[0]["status"] != 0:
+            raise ValueError(f"simplified_mesh failed with status {int(info[0]['status'])}: the mesh was not simplified")
+        verts, faces = meshes[0]
+        return self._engine.transform_points(np.ascontiguousarray(verts, dtype=np.float64), T), faces
+
     # -- distances along the surface -------------------------------------------------------------------------------
     def _geodesic_seeds(self, where):
         """a vertex index, or a 3-D point in the CURRENT coordinate system -> (vertices, d0): the vertex itself with 0.0, or the point

@@ -1,8 +1,8 @@
 // sh_query.h -- what the queries of the resident batch decide on the host: the rays (sh_ray_cast / sh_anp_axis_hits), the closest surface
 // points (sh_closest_points), the generalized winding numbers (sh_winding_numbers), the registration of point sets (sh_register_points,
-// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields), the geodesics (sh_geodesic), the smoothing of the vertices (sh_smooth_vertices), the repair (sh_mesh_repair) and the face hierarchy (sh_mesh_bvh, sh_set_query_accel).  A query reads the mesh and changes no state of the
+// sh_register_multistart), the mass properties (sh_mass_properties), the surface samples (sh_sample_surface), the mesh topology (sh_mesh_topology), the vertex fields (sh_vertex_fields), the geodesics (sh_geodesic), the smoothing of the vertices (sh_smooth_vertices), the repair (sh_mesh_repair), the simplification (sh_mesh_simplify) and the face hierarchy (sh_mesh_bvh, sh_set_query_accel).  A query reads the mesh and changes no state of the
 // arthroplasty chain; it is no link of it.  Per query: the buffer list, the plan with the bytes of every buffer, and one ordered
-// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo,bvh,smooth,repair}_check.cpp).
+// precheck.  No kernels, no HIP types: sh_ctx.h includes it, and so does a plain g++ (tests/hostcheck/{ray,closest,winding,icp,mass,sample,topo,vert,geo,bvh,smooth,repair,simplify}_check.cpp).
 // The entry points are sh_query_host.h.  From sh_arthro.h: SH_BUF_LIST, ArthroError and the refusal texts, ArthroFacts (the anatomic-neck
 // rays ask the chain's state for the last run), `resident`, tiles_of.
 #pragma once
@@ -76,6 +76,17 @@ struct RayKey; struct CpPart; struct GeoInfo;
   X(repair_info, "repair.info", sh_repair_info, 4) X(repair_shells, "repair.shells", sh_repair_shell, 8)                           \
   X(repair_holes, "repair.holes", sh_repair_hole, 4) X(repair_off, "repair.off", long long, 8) X(repair_par, "repair.par", unsigned char, 1) \
   X(repair_work, "repair.work", int, 4) X(repair_edge, "repair.edge", int, 4) X(repair_term, "repair.term", double, 8)
+// the simplified meshes (mesh b at voff[b] / foff[b]), the map and the records; scratch: AR_SIMP_HEAD words per mesh (the box as topo_enc
+// words, the counts, the largest move), the segments of the sorts (B + 1), the cells, the keys before and behind a sort, the key and the
+// first sorted place of every cluster, the cluster of every vertex, the marks (heads, then named clusters) and their scan, the vertex
+// quadrics, the cluster positions, the kept faces and their scan.  ("simp.tmp", the sorts' storage, is sized by rocPRIM beside the list.)
+#define SIMPLIFY_BUFS(X)                                                                                                           \
+  X(simp_verts, "simp.verts", float, 4) X(simp_faces, "simp.faces", int, 4) X(simp_map, "simp.map", int, 4)                        \
+  X(simp_info, "simp.info", sh_simplify_info, 8) X(simp_state, "simp.state", unsigned, 4) X(simp_seg, "simp.seg", unsigned, 4)     \
+  X(simp_cell, "simp.cell", double, 8) X(simp_key, "simp.key", unsigned long long, 8) X(simp_sorted, "simp.sorted", unsigned long long, 8) \
+  X(simp_ukey, "simp.ukey", unsigned long long, 8) X(simp_start, "simp.start", int, 4) X(simp_cid, "simp.cid", int, 4)             \
+  X(simp_mark, "simp.mark", int, 4) X(simp_rank, "simp.rank", int, 4) X(simp_quad, "simp.quad", double, 8)                         \
+  X(simp_pos, "simp.pos", float, 4) X(simp_keep, "simp.keep", int, 4) X(simp_frank, "simp.frank", int, 4)
 // (RayBytes, RayBufs and RayView, the mesh's pointers and the list's: what a query hands to its kernels)
 #define SH_QUERY_LIST(Name, LIST) SH_BUF_LIST(Name, LIST) using Name##View = BufJoin<MeshBufs, Name##Bufs>;
 SH_QUERY_LIST(Ray, RAY_BUFS)
@@ -95,6 +106,8 @@ SH_BUF_LIST(Smooth, SMOOTH_BUFS)
 using SmoothView = BufJoin<MeshBufs, TopoBufs, SmoothBufs>;
 SH_BUF_LIST(Repair, REPAIR_BUFS)
 using RepairView = BufJoin<MeshBufs, TopoBufs, RepairBufs>;
+SH_BUF_LIST(Simplify, SIMPLIFY_BUFS)
+using SimplifyView = BufJoin<MeshBufs, TopoBufs, SimplifyBufs>;
 
 // what the kernel headers fix, restated (shoulder_hip.hip holds each against its header with a static_assert)
 constexpr int AR_RAY_TILE = 256, AR_RAY_CHUNK = 256, AR_RAY_KEY_BYTES = 16;       // SH_RAY_TILE, SH_RAY_CHUNK, sizeof(RayKey)
@@ -111,6 +124,7 @@ constexpr int AR_GEO_BLOCK = 256, AR_GEO_FACE = 6, AR_GEO_STATE = 8;            
 constexpr int AR_BVH_BLOCK = 256, AR_BVH_HEAD = 8, AR_BVH_CHUNK = 64;             // SH_BVH_BLOCK, SH_BVH_HEAD, SH_BVH_CHUNK
 constexpr int AR_SMOOTH_BLOCK = 256;                                              // SH_SMOOTH_BLOCK
 constexpr int AR_REPAIR_BLOCK = 256, AR_REPAIR_HEAD = 16, AR_REPAIR_EDGE_ARRAYS = 18;      // SH_REPAIR_BLOCK, SH_REPAIR_HEAD, SH_REPAIR_EDGE_ARRAYS
+constexpr int AR_SIMP_BLOCK = 256, AR_SIMP_HEAD = 20, AR_SIMP_Q = 10;                      // SH_SIMP_BLOCK, SH_SIMP_HEAD, SH_SIMP_Q
 
 // ---- the checks, each once --------------------------------------------------------------------------------------------------------
 // n rays: the index of the first one that is not six finite doubles with a non-zero direction, or -1
@@ -353,6 +367,30 @@ inline RepairPlan repair_plan(int B, int shell_records, int max_holes, long long
   return p;
 }
 
+// The simplification.  Every array follows the vertices (mesh b at voff[b]; "simp.verts" and "simp.pos" three float32 and "simp.quad"
+// AR_SIMP_Q doubles per vertex) or the faces (mesh b at foff[b]; "simp.faces" three int32 per face): an output is never larger than its
+// input, so every size follows from the batch alone and a second call allocates nothing.  seg: the first vertex of every mesh, the
+// segments of both sorts; state0: an empty box (lo above, hi below everything) and zero counts.
+struct SimplifyPlan { int blocks = 0, vblocks = 0, fblocks = 0; std::vector<unsigned> seg, state0; SimplifyBytes bytes; };
+inline ArthroError simplify_plan(int B, long long maxV, long long maxF, const long long* voff /* B + 1 */, long long sumF, SimplifyPlan* out) {
+  SimplifyPlan p;
+  if (voff[B] > 0x7fffffffLL) return {SH_ERR_NOMEM, "the batch has more than 2^31 - 1 vertices: its keys do not sort in one call"};
+  p.vblocks = (int)tiles_of(maxV, AR_SIMP_BLOCK); p.fblocks = (int)tiles_of(maxF, AR_SIMP_BLOCK);
+  p.blocks = p.vblocks > p.fblocks ? p.vblocks : p.fblocks;
+  p.seg.resize((size_t)B + 1); p.state0.assign((size_t)B * AR_SIMP_HEAD, 0u);
+  for (int b = 0; b <= B; ++b) p.seg[b] = (unsigned)voff[b];
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < 3; ++k) p.state0[(size_t)b * AR_SIMP_HEAD + k] = 0xffffffffu;
+  const size_t v = (size_t)(voff[B] > 0 ? voff[B] : 1), f = (size_t)(sumF > 0 ? sumF : 1);
+  SimplifyBytes& z = p.bytes;
+  z.simp_verts = v * 12; z.simp_faces = f * 12; z.simp_map = v * 4; z.simp_info = (size_t)B * sizeof(sh_simplify_info);
+  z.simp_state = (size_t)B * AR_SIMP_HEAD * 4; z.simp_seg = ((size_t)B + 1) * 4; z.simp_cell = (size_t)B * 8;
+  z.simp_key = v * 8; z.simp_sorted = v * 8; z.simp_ukey = v * 8; z.simp_start = v * 4; z.simp_cid = v * 4; z.simp_mark = v * 4; z.simp_rank = v * 4;
+  z.simp_quad = v * AR_SIMP_Q * 8; z.simp_pos = v * 12; z.simp_keep = f * 4; z.simp_frank = f * 4;
+  *out = std::move(p);
+  return arthro_ok();
+}
+
 // The face hierarchy (sh_scalar.h bvh_*).  "bvh.order", "bvh.loose", "bvh.key" and "bvh.sorted" follow the faces (mesh b at foff[b]) and
 // "bvh.tri" nine float32 per face; "bvh.box" has six float32 per node, mesh b from base[b] = the sum of bvh_nodes_of(F_a) over the meshes
 // before it -- room for a mesh without a loose face, known before the device has counted them; "bvh.off" SH_BVH_OFF_WORDS int32 and
@@ -545,6 +583,20 @@ inline ArthroError precheck_repair(const sh_repair_options* opt, bool topology, 
     return {SH_ERR_ARG, "bad options (orient in 0..3, fill in 0..2, max_hole_edges >= 3, max_holes in 1..65536, max_rounds in 1..1048576, reserved 0)"};
   if (const ArthroError e = resident(f); e.code) return e;
   if (!topology) return {SH_ERR_STATE, "no topology of the resident batch: call sh_mesh_topology first"};
+  return arthro_ok();
+}
+
+// incidence: "topo.vrow" and "topo.vface" of the resident batch are there (a new batch removes them); cell: f.B entries
+inline ArthroError precheck_simplify(const sh_simplify_options* opt, const double* cell, bool incidence, const ArthroFacts& f) {
+  if (!f.ctx || !opt) return {SH_ERR_ARG, "bad argument (context and options must be given)"};
+  if ((opt->place != SH_SIMPLIFY_MEAN && opt->place != SH_SIMPLIFY_QUADRIC) || opt->reserved != 0 || !std::isfinite(opt->reg) || !(opt->reg >= 0.0 && opt->reg <= 1.0) ||
+      !std::isfinite(opt->clamp) || !(opt->clamp > 0.0))
+    return {SH_ERR_ARG, "bad options (place 0 or 1, reserved 0, reg finite in 0..1, clamp finite and > 0)"};
+  if (!cell) return {SH_ERR_ARG, "bad argument (cell must be given: one per resident mesh)"};
+  for (int b = 0; b < f.B; ++b)
+    if (!std::isfinite(cell[b]) || !(cell[b] > 0.0)) return {SH_ERR_ARG, "bad argument (cell[" + std::to_string(b) + "] is not finite and > 0)"};
+  if (const ArthroError e = resident(f); e.code) return e;
+  if (!incidence) return {SH_ERR_STATE, "no incidence of the resident batch: call sh_mesh_topology first"};
   return arthro_ok();
 }
 

@@ -1,7 +1,7 @@
 // sh_query_host.h -- the entry points of the queries of the resident batch: the rays, sh_ray_cast / sh_anp_axis_hits (k_rays.h), the
 // closest surface points, sh_closest_points (k_closest.h), the winding numbers, sh_winding_numbers (k_winding.h), the registration of
 // point sets, sh_register_points (k_icp.h) and sh_register_multistart (k_ms.h), the mass properties, sh_mass_properties (k_mass.h), the surface samples, sh_sample_surface
-// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), the geodesics, sh_geodesic (k_geo.h), the smoothing of the vertices, sh_smooth_vertices (k_smooth.h), the repair, sh_mesh_repair (k_repair.h), and the face hierarchy, sh_mesh_bvh / sh_set_query_accel (k_bvh.h).
+// (k_sample.h), the mesh topology, sh_mesh_topology (k_topo.h), the vertex fields, sh_vertex_fields (k_vert.h), the geodesics, sh_geodesic (k_geo.h), the smoothing of the vertices, sh_smooth_vertices (k_smooth.h), the repair, sh_mesh_repair (k_repair.h), the simplification, sh_mesh_simplify (k_simplify.h), and the face hierarchy, sh_mesh_bvh / sh_set_query_accel (k_bvh.h).
 // Every one reads the mesh and changes no state of the arthroplasty chain.  Host code of shoulder_hip.hip, included there EXACTLY
 // ONCE, right behind sh_arthro_host.h (arthro_facts, arthro_refuse) and for its reason: a header, not a unit.
 // What a query DECIDES is sh_query.h (checks, first refusal, plan, buffer sizes).  Every entry point here reads:
@@ -568,6 +568,69 @@ int sh_mesh_repair(sh_ctx* c, const sh_repair_options* opt, sh_repair_info* info
   if (shells) HIPCHK(c, hipMemcpyAsync(shells, v.repair_shells, plan.bytes.repair_shells, hipMemcpyDeviceToHost, c->stream));
   if (holes) HIPCHK(c, hipMemcpyAsync(holes, v.repair_holes, plan.bytes.repair_holes, hipMemcpyDeviceToHost, c->stream));
   if (flip) HIPCHK(c, hipMemcpyAsync(flip, v.repair_flip, (size_t)sumF, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SH_OK;
+}
+
+// ---- simplification: vertex clustering with quadric placement (k_simplify.h) ----
+// the segments, the empty boxes and the cells to the device, zeroed outputs -> box -> key -> sort -> heads -> scan -> ukey -> assign ->
+// quadric -> sort -> cluster -> faces -> scan, scan -> emit -> info; the host looks at nothing in between (the temporary storage of the
+// sorts is sized on the host)
+static_assert(AR_SIMP_BLOCK == SH_SIMP_BLOCK && AR_SIMP_HEAD == SH_SIMP_HEAD && AR_SIMP_Q == SH_SIMP_Q, "sh_query.h: simplification block, head of simp.state, sums of a quadric");
+
+int sh_mesh_simplify(sh_ctx* c, const sh_simplify_options* opt, const double* cell, sh_simplify_info* info, float* verts, int32_t* faces, int32_t* map) {
+  const bool incidence = c && c->at("topo.vrow") && c->at("topo.vface");
+  if (const ArthroError e = precheck_simplify(opt, cell, incidence, arthro_facts(c)); e.code) return arthro_refuse(c, "sh_mesh_simplify", e);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int B = c->B;
+  SimplifyPlan plan;
+  if (const ArthroError e = simplify_plan(B, c->maxV, c->maxF, c->h_voff.data(), c->sumF, &plan); e.code) return arthro_refuse(c, "sh_mesh_simplify", e);
+  if (int rc = ensure_bytes(c, plan.bytes)) return rc;
+  SimplifyView v = view_of<SimplifyView>(c);
+  const unsigned nkeys = (unsigned)c->sumV;
+  size_t tmp_bytes = 0;
+  HIPCHK(c, rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, (const unsigned long long*)v.simp_key, v.simp_sorted, nkeys, (unsigned)B, (const unsigned*)v.simp_seg,
+                                               (const unsigned*)v.simp_seg + 1, 0u, 64u, c->stream));
+  if (int rc = ensure_shared(c, "simp.tmp", tmp_bytes ? tmp_bytes : 16, 1)) return rc;
+  v = view_of<SimplifyView>(c);
+  void* tmp = c->at("simp.tmp");
+  HIPCHK(c, hipMemcpyAsync(v.simp_seg, plan.seg.data(), plan.bytes.simp_seg, hipMemcpyHostToDevice, c->stream));      // (pageable: staged before the call returns)
+  HIPCHK(c, hipMemcpyAsync(v.simp_state, plan.state0.data(), plan.bytes.simp_state, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(v.simp_cell, cell, plan.bytes.simp_cell, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.simp_verts, 0, plan.bytes.simp_verts, c->stream));
+  HIPCHK(c, hipMemsetAsync(v.simp_faces, 0, plan.bytes.simp_faces, c->stream));
+  const dim3 vblocks((unsigned)plan.vblocks, (unsigned)B), fblocks((unsigned)plan.fblocks, (unsigned)B), blocks((unsigned)plan.blocks, (unsigned)B), lanes(SH_SIMP_BLOCK),
+      meshes((unsigned)B), scan(SH_SIMP_SCAN);
+  const int* vrow = v.topo_vrow;
+  const int* vface = v.topo_vface;
+  const double* cells = v.simp_cell;
+  LAUNCH(c, "k_simp_box", k_simp_box, vblocks, lanes, v.verts, v.voff, vrow, v.simp_state);
+  LAUNCH(c, "k_simp_key", k_simp_key, vblocks, lanes, v.verts, v.voff, vrow, cells, v.simp_state, v.simp_key);
+  HIPCHK(c, rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, (const unsigned long long*)v.simp_key, v.simp_sorted, nkeys, (unsigned)B, (const unsigned*)v.simp_seg,
+                                               (const unsigned*)v.simp_seg + 1, 0u, 64u, c->stream));
+  LAUNCH(c, "k_simp_heads", k_simp_heads, vblocks, lanes, (const unsigned long long*)v.simp_sorted, v.voff, v.simp_mark);
+  LAUNCH(c, "k_simp_scan", k_simp_scan, meshes, scan, (const int*)v.simp_mark, v.voff, SH_SIMP_W_CLUSTERS, v.simp_rank, v.simp_state);
+  LAUNCH(c, "k_simp_ukey", k_simp_ukey, vblocks, lanes, (const unsigned long long*)v.simp_sorted, (const int*)v.simp_mark, (const int*)v.simp_rank, v.voff, v.simp_ukey,
+         v.simp_start);
+  LAUNCH(c, "k_simp_assign", k_simp_assign, vblocks, lanes, (const unsigned long long*)v.simp_ukey, v.voff, (const unsigned*)v.simp_state, v.simp_cid, v.simp_key);
+  LAUNCH(c, "k_simp_quadric", k_simp_quadric, vblocks, lanes, v.verts, v.faces, v.voff, v.foff, vrow, vface, cells, (const unsigned*)v.simp_state, (const int*)v.simp_cid,
+         v.simp_quad);
+  HIPCHK(c, rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, (const unsigned long long*)v.simp_key, v.simp_sorted, nkeys, (unsigned)B, (const unsigned*)v.simp_seg,
+                                               (const unsigned*)v.simp_seg + 1, 0u, 64u, c->stream));
+  LAUNCH(c, "k_simp_cluster", k_simp_cluster, vblocks, lanes, v.verts, v.voff, cells, v.simp_state, (const unsigned long long*)v.simp_sorted,
+         (const unsigned long long*)v.simp_ukey, (const int*)v.simp_start, (const double*)v.simp_quad, (int)opt->place, opt->reg, opt->clamp, v.simp_pos);
+  HIPCHK(c, hipMemsetAsync(v.simp_mark, 0, plan.bytes.simp_mark, c->stream));      // (the heads are spent: the marks of the named clusters)
+  LAUNCH(c, "k_simp_faces", k_simp_faces, fblocks, lanes, v.faces, v.voff, v.foff, vrow, vface, v.simp_state, (const int*)v.simp_cid, (const unsigned long long*)v.simp_sorted,
+         (const int*)v.simp_start, v.simp_keep, v.simp_mark);
+  LAUNCH(c, "k_simp_scan", k_simp_scan, meshes, scan, (const int*)v.simp_keep, v.foff, SH_SIMP_W_FACES, v.simp_frank, v.simp_state);
+  LAUNCH(c, "k_simp_scan", k_simp_scan, meshes, scan, (const int*)v.simp_mark, v.voff, SH_SIMP_W_VERTS, v.simp_rank, v.simp_state);
+  LAUNCH(c, "k_simp_emit", k_simp_emit, blocks, lanes, v.verts, v.faces, v.voff, v.foff, v.simp_state, (const int*)v.simp_cid, (const float*)v.simp_pos, (const int*)v.simp_keep,
+         (const int*)v.simp_frank, (const int*)v.simp_mark, (const int*)v.simp_rank, v.simp_verts, v.simp_faces, v.simp_map);
+  LAUNCH(c, "k_simp_info", k_simp_info, dim3((unsigned)((B + SH_SIMP_BLOCK - 1) / SH_SIMP_BLOCK)), lanes, (const unsigned*)v.simp_state, cells, B, v.simp_info);
+  if (info) HIPCHK(c, hipMemcpyAsync(info, v.simp_info, plan.bytes.simp_info, hipMemcpyDeviceToHost, c->stream));
+  if (verts) HIPCHK(c, hipMemcpyAsync(verts, v.simp_verts, (size_t)c->sumV * 12, hipMemcpyDeviceToHost, c->stream));
+  if (faces) HIPCHK(c, hipMemcpyAsync(faces, v.simp_faces, (size_t)c->sumF * 12, hipMemcpyDeviceToHost, c->stream));
+  if (map) HIPCHK(c, hipMemcpyAsync(map, v.simp_map, (size_t)c->sumV * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SH_OK;
 }

@@ -2414,4 +2414,98 @@ struct RayHitNear {
   SH_HD void operator()(double th, int f, int s) { if (ray_key_less(th, f, t, face)) { t = th; face = f; side = s; } }
 };
 
+// ---- simplification of the resident batch by vertex clustering (include/shoulder_hip.h sh_mesh_simplify; k_simplify.h) ----------------
+// float64, operation by operation in the written order (-ffp-contract=off), + - x / sqrt and floor only; restated by
+// tests/simplify_oracle.py.  The placements and limits are the header's SH_SIMPLIFY_* (k_simplify.h holds them equal).
+#define SH_SIMP_MEAN 0
+#define SH_SIMP_QUADRIC 1
+#define SH_SIMP_MAX_CELLS 1048576        // per axis
+#define SH_SIMP_MAX_CLUSTERS 2097152     // per mesh
+#define SH_SIMP_NO_KEY 0xffffffffffffffffull      // the key of a vertex that takes no part: above every cell (a key is below 2^60)
+#define SH_SIMP_Q 10                     // the sums of a quadric: n0n0 n0n1 n0n2 n1n1 n1n2 n2n2 n0d n1d n2d dd
+
+SH_HD bool simp_finite(double x) { return x - x == 0.0; }
+
+// the cells per axis of the box [lo, hi] (float32, widened) at the cell h; false when an axis has more than SH_SIMP_MAX_CELLS (or the
+// quotient is not a number)
+SH_HD bool simp_grid(const float* lo, const float* hi, double h, long long* n /* 3 */) {
+  bool ok = true;
+  for (int k = 0; k < 3; ++k) {
+    const double q = floor(((double)hi[k] - (double)lo[k]) / h);
+    if (!(q >= 0.0 && q < (double)SH_SIMP_MAX_CELLS)) { ok = false; n[k] = 0; continue; }
+    n[k] = (long long)q + 1;
+  }
+  return ok;
+}
+// the cell of the coordinate x on an axis of n cells that starts at lo
+SH_HD long long simp_cell(float x, float lo, double h, long long n) {
+  const long long i = (long long)floor(((double)x - (double)lo) / h);
+  return i < n - 1 ? i : n - 1;
+}
+SH_HD unsigned long long simp_key(const long long* i, const long long* n) { return (unsigned long long)((i[2] * n[1] + i[1]) * n[0] + i[0]); }
+SH_HD void simp_unkey(unsigned long long key, const long long* n, long long* i) {
+  const unsigned long long nx = (unsigned long long)n[0], ny = (unsigned long long)n[1];
+  i[0] = (long long)(key % nx); i[1] = (long long)((key / nx) % ny); i[2] = (long long)((key / nx) / ny);
+}
+// the centre of cell i on an axis
+SH_HD double simp_center(long long i, float lo, double h) { return (double)lo + ((double)i + 0.5) * h; }
+
+// the face with the widened corners A, B, C added to the ten sums q, relative to o: n = cross3(B - A, C - A), not normalised, d = -dot3(n, A - o)
+SH_HD void simp_face_quadric(const double* A, const double* B, const double* C, const double* o, double* q /* SH_SIMP_Q */) {
+  const double e1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, e2[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]}, t[3] = {A[0] - o[0], A[1] - o[1], A[2] - o[2]};
+  double n[3];
+  cross3(e1, e2, n);
+  const double d = -dot3(n, t);
+  q[0] = q[0] + n[0] * n[0]; q[1] = q[1] + n[0] * n[1]; q[2] = q[2] + n[0] * n[2]; q[3] = q[3] + n[1] * n[1]; q[4] = q[4] + n[1] * n[2];
+  q[5] = q[5] + n[2] * n[2]; q[6] = q[6] + n[0] * d; q[7] = q[7] + n[1] * d; q[8] = q[8] + n[2] * d; q[9] = q[9] + d * d;
+}
+
+// The placement of a cluster from its quadric q, its mean m and its cell centre o: x, relative to o, solves (A + lambda I) x =
+// lambda (m - o) - b, lambda = reg tr(A), by the 3 x 3 Cholesky factorisation written out.  false: the cluster takes its mean (tr 0.0 or
+// not finite; a radicand <= 0.0 or not finite; an x that is not finite or leaves the clamped cell, |x_c| > 0.5 h clamp).
+SH_HD bool simp_solve(const double* q, const double* m, const double* o, double h, double reg, double clamp, double* x /* 3 */) {
+  const double tr = (q[0] + q[3]) + q[5];
+  if (tr == 0.0 || !simp_finite(tr)) return false;
+  const double lam = reg * tr;
+  const double m00 = q[0] + lam, m11 = q[3] + lam, m22 = q[5] + lam;
+  const double r0 = lam * (m[0] - o[0]) - q[6], r1 = lam * (m[1] - o[1]) - q[7], r2 = lam * (m[2] - o[2]) - q[8];
+  if (!(m00 > 0.0) || !simp_finite(m00)) return false;
+  const double l00 = sqrt(m00);
+  const double l10 = q[1] / l00, l20 = q[2] / l00;
+  const double p1 = m11 - l10 * l10;
+  if (!(p1 > 0.0) || !simp_finite(p1)) return false;
+  const double l11 = sqrt(p1);
+  const double l21 = (q[4] - l20 * l10) / l11;
+  const double p2 = (m22 - l20 * l20) - l21 * l21;
+  if (!(p2 > 0.0) || !simp_finite(p2)) return false;
+  const double l22 = sqrt(p2);
+  const double y0 = r0 / l00;
+  const double y1 = (r1 - l10 * y0) / l11;
+  const double y2 = ((r2 - l20 * y0) - l21 * y1) / l22;
+  x[2] = y2 / l22;
+  x[1] = (y1 - l21 * x[2]) / l11;
+  x[0] = ((y0 - l10 * x[1]) - l20 * x[2]) / l00;
+  const double lim = (0.5 * h) * clamp;
+  for (int k = 0; k < 3; ++k)
+    if (!simp_finite(x[k]) || fabs(x[k]) > lim) return false;
+  return true;
+}
+
+// the three clusters of a face ascending -> s; false: two of them are equal (the face is collapsed)
+SH_HD bool simp_triple(int a, int b, int c, int* s /* 3 */) {
+  if (a == b || b == c || a == c) return false;
+  int lo = a < b ? a : b, hi = a < b ? b : a;
+  if (c < lo) { s[0] = c; s[1] = lo; s[2] = hi; }
+  else if (c < hi) { s[0] = lo; s[1] = c; s[2] = hi; }
+  else { s[0] = lo; s[1] = hi; s[2] = c; }
+  return true;
+}
+
+// the distance a vertex moves: between the widened float32 positions x and p; 0.0 when it is not a number
+SH_HD double simp_move(const float* x, const float* p) {
+  const double d[3] = {(double)x[0] - (double)p[0], (double)x[1] - (double)p[1], (double)x[2] - (double)p[2]};
+  const double r = sqrt(dot3(d, d));
+  return r == r ? r : 0.0;
+}
+
 }  // namespace sh

@@ -27,6 +27,7 @@
 #include "k_geo.h"
 #include "k_smooth.h"
 #include "k_repair.h"
+#include "k_simplify.h"
 #include "k_bvh.h"
 #include "k_raytree.h"
 #include "k_te.h"
@@ -478,7 +479,7 @@ static int stl_enqueue_emit(sh_ctx* timed, hipStream_t st, int B, const StlPlan&
 #undef STL_LAUNCH
 
 // "ray.near" (sh_ray_nearest), "cp.out" (sh_closest_points), "wn.out" (sh_winding_numbers), "icp.out" and "icp.near" (sh_register_points), "mass.out" and "mass.part"
-// (sh_mass_properties), "samp.*" (sh_sample_surface), "topo.*" (sh_mesh_topology), "vert.*" (sh_vertex_fields), "geo.*" (sh_geodesic), "smooth.*" (sh_smooth_vertices), "repair.*" (sh_mesh_repair), "bvh.*" (sh_mesh_bvh) answer for the batch they were asked about: a new batch removes them
+// (sh_mass_properties), "samp.*" (sh_sample_surface), "topo.*" (sh_mesh_topology), "vert.*" (sh_vertex_fields), "geo.*" (sh_geodesic), "smooth.*" (sh_smooth_vertices), "repair.*" (sh_mesh_repair), "simp.*" (sh_mesh_simplify: the list SIMPLIFY_BUFS of sh_query.h and the sorts' "simp.tmp"), "bvh.*" (sh_mesh_bvh) answer for the batch they were asked about: a new batch removes them
 static void drop_closest(sh_ctx* c) {
   for (const char* name : {"ray.near", "cp.out", "wn.out", "icp.out", "icp.near", "mass.out", "mass.part", "samp.cdf", "samp.base", "samp.out", "samp.info", "samp.state",
                            "topo.vrow", "topo.vface", "topo.adj", "topo.label", "topo.info", "topo.shells", "topo.state", "topo.cursor", "topo.tmp", "topo.p",
@@ -487,6 +488,10 @@ static void drop_closest(sh_ctx* c) {
                            "smooth.nrow", "smooth.nbr", "smooth.w", "smooth.pos", "smooth.info", "smooth.plane", "smooth.pin", "smooth.mask", "smooth.part",
                            "repair.flip", "repair.faces", "repair.verts", "repair.info", "repair.shells", "repair.holes", "repair.off", "repair.par", "repair.work", "repair.edge",
                            "repair.term",
+#define X(f, name, T, elem) name,
+                           SIMPLIFY_BUFS(X)
+#undef X
+                           "simp.tmp",
                            "bvh.order", "bvh.loose", "bvh.off", "bvh.box", "bvh.tri", "bvh.info", "bvh.state", "bvh.base", "bvh.seg", "bvh.key", "bvh.sorted", "bvh.tmp"}) {
     auto it = c->bufs.find(name);
     if (it == c->bufs.end()) continue;

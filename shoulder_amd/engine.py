@@ -1080,6 +1080,80 @@ class Engine:
             meshes.append((verts[3 * v0:3 * (v0 + int(info[b]["verts_out"]))].reshape(-1, 3).copy(), faces[3 * f0:3 * (f0 + int(info[b]["faces_out"]))].reshape(-1, 3).copy()))
         return dict(info=info, shells=shells, holes=holes, flip=flip, meshes=meshes)
 
+    # ---- simplification of the resident batch (include/shoulder_hip.h sh_mesh_simplify) -------------------------------------------
+    _SIMPLIFY_PLACES = {"mean": _lib.SIMPLIFY_MEAN, "quadric": _lib.SIMPLIFY_QUADRIC}
+
+    def simplify(self, cell, place="quadric", reg=1e-3, clamp=1.0):
+        """Every resident mesh made smaller by vertex clustering, on the device: the used vertices in one cell of a grid of `cell` mm
+        (a scalar, or (B,): one per mesh) become one vertex -- at their mean ("mean") or where the quadric of their faces is smallest,
+        clamped to the cell and regularised towards the mean by reg ("quadric") -- collapsed and duplicate faces are dropped and the
+        rest renumbered.  What trimesh's simplify_vertex_clustering / simplify_quadric_decimation are reached for: the mesh at the
+        density the question needs.  The topology() of this batch is made first when it is not resident.  -> (meshes, info, map):
+        meshes a list of (verts float32, faces int32), one per resident mesh, each ready for upload(); info (B,) of
+        _lib.SIMPLIFY_INFO_DTYPE; map (sumV,) int32, the output vertex of every input vertex at voff[b], or -1.  A mesh with a status
+        (SH_ERR_CAPACITY: more than SIMPLIFY_MAX_CELLS cells on an axis or SIMPLIFY_MAX_CLUSTERS clusters; SH_ERR_GEOMETRY: every face
+        collapsed) comes back empty.  Clustering does not preserve topology: topology() of the re-upload says what it left.  "verts"
+        and "faces" are not written.  The same bytes wherever the rule runs."""
+        p = self._SIMPLIFY_PLACES.get(place, place)
+        if not isinstance(p, (int, np.integer)):
+            raise ValueError("place must be 'mean' or 'quadric'")
+        B = max(self.B, 0)
+        cells = np.ascontiguousarray(np.broadcast_to(np.asarray(cell, dtype=np.float64), (B,)) if np.ndim(cell) == 0 else np.asarray(cell, dtype=np.float64))
+        if cells.shape != (B,):
+            raise ValueError("cell must be a scalar or one value per resident mesh")
+        if B >= 1 and not self._has_buffer("topo.vrow"):
+            self.topology()
+        opt = np.zeros(1, dtype=_lib.SIMPLIFY_OPTIONS_DTYPE)
+        opt["place"], opt["reg"], opt["clamp"] = int(p), float(reg), float(clamp)
+        nv, nf = (int(self.voff[-1]), int(self.foff[-1])) if B else (0, 0)
+        info = np.zeros(B, dtype=_lib.SIMPLIFY_INFO_DTYPE)
+        verts, faces, vmap = np.zeros((nv, 3), np.float32), np.zeros((nf, 3), np.int32), np.zeros(nv, np.int32)
+        # (without a batch there is no cell to read: the library gets a placeholder and reports the state)
+        self._chk(self.L.sh_mesh_simplify(self.h, _ptr(opt), _ptr(cells if B else np.ones(1)), _ptr(info), _ptr(verts), _ptr(faces), _ptr(vmap)))
+        meshes = []
+        for b in range(B):
+            v0, f0 = int(self.voff[b]), int(self.foff[b])
+            meshes.append((verts[v0:v0 + int(info[b]["verts_out"])].copy(), faces[f0:f0 + int(info[b]["faces_out"])].copy()))
+        return meshes, info, vmap
+
+    def simplify_to(self, target_faces, place="quadric", reg=1e-3, clamp=1.0, steps=16):
+        """simplify() at, per mesh, the smallest cell tried whose result has at most target_faces faces (a scalar or (B,)): `steps`
+        rounds of bisection on the cell per mesh, all meshes in every call, from [box diagonal / 2^20 raised to the cell limit, box
+        diagonal].  -> (meshes, info, map) as simplify(): per mesh exactly the bytes simplify gives for info[b]["cell"].  At the box
+        diagonal a mesh is one cluster and comes back empty (SH_ERR_GEOMETRY): that is the answer when no cell tried fits."""
+        B = max(self.B, 0)
+        target = np.broadcast_to(np.asarray(target_faces, dtype=np.int64), (B,))
+        verts = self.fetch("verts", np.float32)
+        lo, hi = np.ones(B), np.ones(B)
+        for b in range(B):
+            v = verts[3 * int(self.voff[b]):3 * int(self.voff[b + 1])].reshape(-1, 3).astype(np.float64)
+            ext = v.max(axis=0) - v.min(axis=0)
+            diag = float(np.sqrt((ext * ext).sum()))
+            if diag > 0.0:
+                hi[b], lo[b] = diag, max(diag / 2.0 ** 20, float(ext.max()) / (_lib.SIMPLIFY_MAX_CELLS - 2))
+        meshes, info, vmap = self.simplify(hi, place, reg, clamp)      # (one cluster per mesh: it fits every target)
+        vmap = vmap.copy()
+        done = np.zeros(B, dtype=bool)
+
+        def trial(cells):
+            """-> per mesh: does the result at this cell fit?  A result that fits at a smaller cell than the best so far is taken."""
+            r = self.simplify(cells, place, reg, clamp)
+            fits = (r[1]["status"] != -4) & (r[1]["faces_out"] <= target)      # (SH_ERR_CAPACITY: no result)
+            for b in np.nonzero(fits & (cells < info["cell"]))[0]:
+                meshes[b], info[b] = r[0][b], r[1][b]
+                vmap[int(self.voff[b]):int(self.voff[b + 1])] = r[2][int(self.voff[b]):int(self.voff[b + 1])]
+            return fits
+        done = trial(lo)
+        hi[done] = lo[done]
+        for _ in range(int(steps)):
+            if done.all():
+                break
+            mid = np.where(done, hi, 0.5 * (lo + hi))
+            fits = trial(mid)
+            hi = np.where(fits, mid, hi)
+            lo = np.where(fits | done, lo, mid)
+        return meshes, info, vmap
+
     # ---- geodesic distances and shortest paths on the resident batch (include/shoulder_hip.h sh_geodesic) ------------------------
     _GEO_MODES = {"edges": _lib.GEO_EDGES, "unfold": _lib.GEO_UNFOLD}
 
